@@ -25,6 +25,11 @@ CPU baseline (rank 0, N = 1): the oracle (CPU restatement, `-O3 -DNDEBUG -msse3`
 fast mode = the full batch (doubling as a full-size parity check), sahlin mode = a bounded sample with the oracle's
 own SCALAR aligner (not parasail's striped SIMD scan).  min over the runs that fit the time budget (<= 3).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up and K timed
+steps of the headline mode, the line.  Everything else above — the fast-mode leg beside the sahlin headline, the other
+aligner, the golden parity, the rooflines, the core and cli regions, the CPU baselines, the merge of N > 1 — runs with
+`--full`.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's batch) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -139,6 +144,22 @@ def timed_steps(ctx, torch, dist, dev, steps, warmup):
     for k in acc:
         acc[k] /= steps
     return cls, strand, st, tm, elapsed, acc
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: `arrays` (one entry per read of the sorted batch each, float32 / float64) as DIR/<name>.npy.  Over
+    DUMP_MAX_BYTES in all, the same seeded sample of entries is taken from every array; its indices go to sample_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    per_entry = sum(x.dtype.itemsize for x in arrays.values())
+    if n * per_entry > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (per_entry + 8), replace=False))
+        arrays = dict({name: x[idx] for name, x in arrays.items()}, sample_index=idx.astype(np.float64))
+    for name, x in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), x)
 
 
 def core_region(ctx, api, pipeline, sb, k, w, mode, runs):
@@ -516,7 +537,15 @@ def main():
     ap.add_argument("--no-native-merge", action="store_true", help="N > 1: skip the second merge leg through the library's own C++ / RCCL binding (ioc_dist_merge)")
     ap.add_argument("--strict", action="store_true", help="exit code 3 when a leg of the merge (after the timed region) never came back; default: the line reports it, exit 0")
     ap.add_argument("--no-cpu-node", action="store_true", help="skip the node-level CPU leg (P concurrent single-batch oracle processes on P cores)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline (fast-mode leg, other aligner, golden parity, rooflines, core / cli regions, "
+                         "CPU baselines, merge of N > 1); default: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's batch) as DIR/<name>.npy (float64 / float32)")
     a = ap.parse_args()
+    if not a.full:
+        # a plain run measures the headline only: the legs these switches control are --full's
+        a.no_cpu_baseline = a.no_core = a.no_cli = a.no_merge = a.no_cpu_node = True
 
     if a.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(a))
@@ -546,7 +575,7 @@ def main():
     dev = torch.device("cuda", dev_index) if (dist is None or a.backend == "nccl") else torch.device("cpu")
 
     ctx = api.Context(dev_index)
-    want_fast = a.mode in ("both", "fast")
+    want_fast = a.mode == "fast" or (a.mode == "both" and a.full)     # (beside the sahlin headline: a --full leg)
     want_sahlin = a.mode in ("both", "sahlin")
     seed = 1 if a.same_seed else 1 + rank
     rs, sb, order = prepare(ctx, api, pipeline, synth, a.config, seed, k, w, rank)
@@ -585,10 +614,11 @@ def main():
             os.environ.pop("IOC_ALIGN_ARENA", None)
             return r
         other = "fat" if a.aligner == "lean" else "lean"
-        cls, strand, st, tm, elapsed, acc = sahlin_run(other)          # the mode that is NOT the headline, reported beside it
-        sah_lean = {"aligner": other, "ms_per_step": elapsed / a.steps * 1e3, "value": total_reads * a.steps / elapsed, "align_fwd_ms": acc["ms_align_fwd"],
-                    "align_trace_ms": acc["ms_align_trace"], "arena_bytes": tm.get("align_arena_bytes"), "aligner_version": tm.get("align_version"),
-                    "clusters": st["n_clusters"], "_res": (cls, strand, st)}
+        if a.full:
+            cls, strand, st, tm, elapsed, acc = sahlin_run(other)          # the mode that is NOT the headline, reported beside it
+            sah_lean = {"aligner": other, "ms_per_step": elapsed / a.steps * 1e3, "value": total_reads * a.steps / elapsed, "align_fwd_ms": acc["ms_align_fwd"],
+                        "align_trace_ms": acc["ms_align_trace"], "arena_bytes": tm.get("align_arena_bytes"), "aligner_version": tm.get("align_version"),
+                        "clusters": st["n_clusters"], "_res": (cls, strand, st)}
         cls, strand, st, tm, elapsed, acc = sahlin_run(a.aligner)
         sah = {"value": total_reads * a.steps / elapsed, "unit": "reads/s", "ms_per_step": elapsed / a.steps * 1e3,
                "phase_ms": {"index_build": acc["ms_build"], "score": acc["ms_score"], "resolve_last": acc["ms_resolve"],
@@ -602,6 +632,10 @@ def main():
         sah["alignment"].update(arena_bytes=tm.get("align_arena_bytes"), aligner_version=tm.get("align_version"))
         os.environ.pop("IOC_ALIGN_ARENA", None)     # core / cli / merge below: the library default
 
+    if a.dump_outputs and rank == 0:
+        head_res = sah_res if want_sahlin else fast_res
+        dump_outputs(a.dump_outputs, {"cluster": head_res[0].astype(np.float64), "strand": head_res[1].astype(np.float32)})
+
     # ---- every rank's own result against the committed oracle digest of ITS batch (tests/golden, tools/gen_golden.py) ----
     golden = {}
     try:
@@ -613,7 +647,7 @@ def main():
     lean_res = sah_lean.pop("_res") if sah_lean else None
     for mode_name, res in (("fast", fast_res if want_fast else None), ("sahlin", sah_res if want_sahlin else None),
                            ("sahlin_other_aligner", lean_res)):
-        if res is None or a.config != "config2":
+        if res is None or a.config != "config2" or not a.full:
             continue
         g = golden.get(f"config2:{seed}" + ("" if mode_name == "fast" else ":sahlin"))  # (the other aligner: the same golden)
         ok = -1 if g is None else int(f"{fnv1a(res[0], res[1]):016x}" == g["fnv1a"] and res[2]["n_clusters"] == g["clusters"])
@@ -631,7 +665,7 @@ def main():
     # ---- roofline inputs that need the resident fast-mode clustering (rank 0) ----
     roof = roof_aln = None
     fcls = fstrand = None
-    if rank == 0 and fast is not None:
+    if rank == 0 and fast is not None and a.full:
         ctx.set_params(api.default_params(k, w, "fast"))
         fcls, fstrand, fst = ctx.cluster_resident()     # untimed: leaves the fast-mode clustering on the device
         M = fast_res[3]["n_minimizers"]
@@ -683,7 +717,7 @@ def main():
 
     if rank == 0:
         # ---- fast mode (configs[1]): HBM roofline of the scoring kernels + full-batch CPU baseline / parity ----
-        if fast is not None:
+        if fast is not None and a.full:
             M, H, Cs, fst = roof_counts
             h_source = "device count (ioc_count_reference_postings)"
             if single:
@@ -728,7 +762,7 @@ def main():
             cells = sah_res[3].get("n_align_cells_computed") or sah_res[3]["n_align_cells"]
             cells_matrix = sah_res[3]["n_align_cells"]
             ms_fwd = sah_res[4]["ms_align_fwd"]
-            if cells and ms_fwd > 0:
+            if cells and ms_fwd > 0 and a.full:
                 peak, src = valu_peak()
                 v2 = sah_res[3].get("align_version") == 2
                 # useful lane-operations per cell: version 1 — add with byte select, max3, sub, max, max; version 2 — 7 per

@@ -1,10 +1,12 @@
 """Pins the CPU oracle: (1) against every known-answer vector the reference's own unit tests hold
 for the hot path (tests/golden/reference_kat.json <- test/isONclust2_test.cpp), (2) function by
-function against oracle/_ref (reference TUs compiled where they lie) when that library was built.
+function against the stand-alone reference TUs' stored answers (tests/golden/reference_tu.npz), and against
+oracle/_ref (those TUs compiled where they lie) when that library was built.
 CPU only.
 """
 import ctypes as C
 import math
+import os
 import struct
 
 import numpy as np
@@ -107,56 +109,74 @@ def test_gap_limit_matches_pow_predicate():
 
 
 # ---- cross-checks against the stand-alone reference TUs (oracle/_ref) ---------------------------
-needs_ref = pytest.mark.skipif(po.ref() is None, reason="oracle/_ref not built (reference tree absent)")
+# Their answers, inputs beside them, are stored in tests/golden/reference_tu.npz (tools/gen_golden_ref_tu.py): the oracle is
+# checked against those everywhere, and where oracle/_ref was built the stored answers are checked against the live library.
+REF_TU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_tu.npz")
 
 
-@needs_ref
-def test_ref_kmer_encode_and_revcomp():
+@pytest.fixture(scope="module")
+def ref_tu():
+    with np.load(REF_TU) as d:
+        return {k: d[k] for k in d.files}
+
+
+def test_ref_kmer_encode_and_revcomp(ref_tu):
+    g = ref_tu
     R = po.ref()
-    rng = np.random.default_rng(7)
-    for trial in range(300):
-        n = int(rng.integers(0, 200))
-        k = int(rng.integers(1, 20))
-        alpha = b"ACGT" if trial % 5 else b"ACGTN"
-        s = bytes(rng.choice(list(alpha), n).astype(np.uint8))
-        out = np.zeros(max(n, 1), np.uint32)
-        m = R.ref_kmer_encode(s, n, k, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    seq, off, oo = g["kmer_seq"].tobytes(), g["kmer_seq_off"], g["kmer_out_off"]
+    for t in range(len(g["kmer_k"])):
+        s, k = seq[off[t]:off[t + 1]], int(g["kmer_k"][t])
+        n = len(s)
+        m, ref_out = int(g["kmer_m"][t]), g["kmer_out"][oo[t]:oo[t + 1]]
+        rc, ref_rc = int(g["rc_rc"][t]), g["rc_out"][off[t]:off[t + 1]].tobytes()
+        if R is not None:
+            out = np.zeros(max(n, 1), np.uint32)
+            assert R.ref_kmer_encode(s, n, k, out.ctypes.data_as(C.POINTER(C.c_uint32))) == m
+            assert np.array_equal(out[:m], ref_out)
+            o = C.create_string_buffer(n + 1)
+            assert R.ref_revcomp(s, n, o) == rc
+            assert rc != 0 or o.raw[:n] == ref_rc
         mine = po.kmer_encode(s, k)
         assert m == len(mine)
-        assert np.array_equal(out[:m], mine)
-        o = C.create_string_buffer(n + 1)
-        rc = R.ref_revcomp(s, n, o)
+        assert np.array_equal(ref_out, mine)
         if rc == 0:
-            assert po.revcomp(s) == o.raw[:n]
+            assert po.revcomp(s) == ref_rc
         else:
             with pytest.raises(ValueError):
                 po.revcomp(s)
 
 
-@needs_ref
-def test_ref_round_and_pmin_all_cells():
+def test_ref_round_and_pmin_all_cells(ref_tu):
+    g = ref_tu
     R = po.ref()
-    rng = np.random.default_rng(11)
-    for x in list(rng.random(2000) * 0.3) + [0.005, 0.015, 0.025, 0.125, 0.145, 0.155, 0.0, 1.0]:
-        assert R.ref_round(float(x), 2) == po.lib().orc_round(float(x), 2)
-    for k, w in [(11, 15), (13, 20), (10, 12), (15, 19), (30, 32), (31, 40), (12, 200)]:
-        h = R.ref_pmin_init(k, w)
-        tab, filled = po.pmin_table(k, w)
-        assert R.ref_pmin_size(h) == filled
-        if filled:
-            for e1 in np.linspace(0.0, 0.2, 41):
-                for e2 in np.linspace(0.0, 0.2, 41):
+    for x, y in zip(g["round_x"], g["round_y"]):
+        if R is not None:
+            assert R.ref_round(float(x), 2) == y
+        assert y == po.lib().orc_round(float(x), 2)
+    grid = g["pmin_e"]
+    for i, (k, w) in enumerate(g["pmin_kw"].tolist()):
+        size, look, errs = int(g["pmin_size"][i]), g["pmin_lookup"][i], g["pmin_err"][i]
+        if R is not None:
+            h = R.ref_pmin_init(k, w)
+            assert R.ref_pmin_size(h) == size
+            for a, e1 in enumerate(grid):
+                for b, e2 in enumerate(grid):
                     err = C.c_int(0)
                     r = R.ref_pmin_lookup(h, float(e1), float(e2), C.byref(err))
-                    assert err.value == 0
-                    assert r == po.pmin_lookup(tab, float(e1), float(e2))
+                    assert err.value == errs[a, b]
+                    assert err.value != 0 or r == look[a, b]
+            R.ref_pmin_free(h)
+        tab, filled = po.pmin_table(k, w)
+        assert size == filled
+        if filled:
+            for a, e1 in enumerate(grid):
+                for b, e2 in enumerate(grid):
+                    assert errs[a, b] == 0
+                    assert look[a, b] == po.pmin_lookup(tab, float(e1), float(e2))
         else:
-            err = C.c_int(0)
-            R.ref_pmin_lookup(h, 0.05, 0.05, C.byref(err))
-            assert err.value == -1
+            assert (errs == -1).all()
             with pytest.raises(KeyError):
                 po.pmin_lookup(tab, 0.05, 0.05)
-        R.ref_pmin_free(h)
 
 
 def test_minimizers_equal_argmin_change_formulation():

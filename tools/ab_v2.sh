@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of aligner-v2 knobs on the config-3 batch: tools/ab_v2.sh "ENV1=a ENV2=b" "ENV1=c" ...   (one bench run per argument)
 for cfg in "$@"; do
-  env $cfg timeout -k 10 200 python bench.py --mode sahlin --steps ${STEPS:-4} --warmup ${WARM:-1} --no-cpu-baseline --no-cli --no-core > /tmp/ab.json 2>/tmp/ab.err
+  env $cfg timeout -k 10 200 python bench.py --full --mode sahlin --steps ${STEPS:-4} --warmup ${WARM:-1} --no-cpu-baseline --no-cli --no-core > /tmp/ab.json 2>/tmp/ab.err
   python - "$cfg" <<'PY'
 import json, sys
 try:

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_align
 mkdir -p "$OUT"
-CMD="python3 bench.py --mode sahlin --steps 1 --warmup 0 --no-cpu-baseline"
+CMD="python3 bench.py --full --mode sahlin --steps 1 --warmup 0 --no-cpu-baseline"
 for v in packed plain; do
   if [ $v = packed ]; then export IOC_ALIGN_PACKED=1; else unset IOC_ALIGN_PACKED; fi
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_SALU --kernel-trace --output-format csv -d "$OUT/$v" -- $CMD > "$OUT/$v.log" 2>&1

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_align2
 mkdir -p "$OUT"
-CMD="python3 bench.py --mode sahlin --steps 1 --warmup 0 --no-cpu-baseline --no-cli --no-core"
+CMD="python3 bench.py --full --mode sahlin --steps 1 --warmup 0 --no-cpu-baseline --no-cli --no-core"
 for v in v2 v1; do
   if [ $v = v1 ]; then export IOC_ALIGN_V1=1; else unset IOC_ALIGN_V1; fi
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_SALU --kernel-trace --output-format csv -d "$OUT/$v" -- $CMD > "$OUT/$v.log" 2>&1

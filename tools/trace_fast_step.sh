@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/trace_fast_$1
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --mode fast --steps 3 --warmup 1 --no-cpu-baseline --no-cli --no-core > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --mode fast --steps 3 --warmup 1 --no-cpu-baseline --no-cli --no-core > $OUT/run.log 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob("$OUT/**/*kernel_trace.csv", recursive=True)[0]
