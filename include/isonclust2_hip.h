@@ -223,7 +223,7 @@ typedef struct {
     float ms_align_trace;      /* k_align_trace: tiled traceback + windows   */
     int64_t n_align_pairs;
     int64_t n_align_cells;     /* sum of query length x reference length     */
-    int64_t n_align_refused;   /* pairs the packed 16-bit forward pass handed to the 32-bit one */
+    int64_t n_align_refused;   /* pairs redone: version 2 refusals on aligner version 1, split pairs whole */
     /* the scoring kernel's variant (decided once, in ioc_ctx_create): 1 = counters at the end of the LDS allocation, no
      * window test (the hardware's bounds check drops what the test would reject), 0 = window test per posting.
      * score_oob_probe: result of the context's run-time probe of that hardware behaviour — 0 passed, > 0 failed (bit 0 a

@@ -5,8 +5,8 @@
 //  * TWO PAIRS PER WAVE.  Every register of the forward pass holds two 16-bit scores: the low half belongs to pair A, the
 //    high half to pair B of a COUPLE (two pairs of similar size), both at the same (row, column) of their own matrices.
 //    v_pk_add_i16 / v_pk_max_i16 issue at the rate of their 32-bit cousins, so a cell costs 3.5 instead of 5 VALU.  16 bits
-//    hold a score relative to a wave-uniform base per half that follows the sweep (k_align_fwd16's scheme: rebased every 16
-//    steps, guarded; a pair that leaves the window is flagged and goes to the 32-bit kernel).
+//    hold a score relative to a wave-uniform base per half that follows the sweep (rebased every 16 steps, guarded: a pair
+//    that leaves the window is flagged and goes to the 32-bit kernel).
 //  * DATAFLOW SCHEDULING instead of generations of equal workgroups.  The (band, strip) tiles of all couples form ONE list,
 //    ordered by anti-diagonal; persistent waves take the next tile off an atomic counter, wait (bounded) for the flags of the
 //    tile above and the tile to the left, compute, publish their flag.  A tile only ever waits for tiles earlier in the
@@ -47,7 +47,7 @@ struct V2Couple {
     uint32_t lrow0[2];        // per pair: first entry of its last-row bests [strip][lane] (int2)
     uint32_t best0[2];        // per pair: first entry of its per-band bests of the last column (int2)
     // band b covers the coarse rows [bstart[b], bstart[b + 1]).  (Heights may differ: short bands at the top and the bottom
-    // of the matrix were tried as a way to shorten the ramp of the tile grid — IOC_ALIGN_V2_RAMP=1 — and measured slower.)
+    // of the matrix were tried as a way to shorten the ramp of the tile grid, and measured slower.)
     uint16_t bstart[V2_MAX_BANDS + 1];
     // THE CORRIDOR: only the tiles (band b, strips plo[b] .. phi[b]) are computed — those that meet |row - column| <= B —, the
     // others count as "no score".  What comes out is the alignment restricted to paths inside the computed tiles; it IS the

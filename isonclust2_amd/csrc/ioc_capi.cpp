@@ -860,7 +860,6 @@ int ioc_score(ioc_ctx* c)
     const uint32_t range = env_u32("IOC_SCORE_RANGE", 8192);
     // XCD-partitioned scoring keeps 8 partial histograms per query (single-pass case only)
     uint32_t* d_part = nullptr;
-    iock_set_score_variant(int(env_u32("IOC_SCORE_VARIANT", 0)));
     iock_set_part32(int(env_u32("IOC_PART32", 0)));
     iock_set_score_oob(c->score_oob);
     const bool aln_mode_s = c->params.mode == IOC_MODE_SAHLIN || c->params.mode == IOC_MODE_FURIOUS;
@@ -905,7 +904,6 @@ int ioc_score(ioc_ctx* c)
                          P<uint32_t>(c->b_pmins), P<uint32_t>(c->b_pbnd)));
     iock_set_score_shard(1, 0);
     iock_set_score_keep(nullptr);
-    c->have_guess = d_part != nullptr && !c->scored_sharded;  // (b_top_all holds the owned queries only)
     HIPCHK(c, hipEventRecord(c->ev[3], s));
     if (count_trav) {
         unsigned long long t = 0;
@@ -1088,15 +1086,10 @@ int ioc_resolve(ioc_ctx* c, int32_t* n_iter)
     c->shard_exchanges = 0;
     auto exchange = [&](void* buf, int64_t count, int kind) -> int { return ioc_shard_exchange(c, buf, count, kind); };
     // initial guess (any guess converges to the same fixed point): "every query opens a cluster".
-    // A guess from the all-pairs top Size (IOC_RESOLVE_GUESS=1) was measured SLOWER on config 2
-    // (4 sweeps / 3.5 ms vs 3 sweeps / 2.0 ms): many entries with a large top still fail the mapped-ratio
-    // test and do open clusters, and that side of the error cascades.
-    if (n > 0 && !warm) {
-        if (c->have_guess && env_u32("IOC_RESOLVE_GUESS", 0) == 1)
-            HIPCHK(c, iock_guess_valid(s, n, c->d_off_fwd, c->d_off_rev, P<uint32_t>(c->b_top_all), P<uint8_t>(c->b_valid0)));
-        else
-            HIPCHK(c, hipMemsetAsync(c->b_valid0.p, 1, size_t(n), s));
-    }
+    // A guess from the all-pairs top Size was measured SLOWER on config 2 (4 sweeps / 3.5 ms vs
+    // 3 sweeps / 2.0 ms): many entries with a large top still fail the mapped-ratio test and do open
+    // clusters, and that side of the error cascades.
+    if (n > 0 && !warm) HIPCHK(c, hipMemsetAsync(c->b_valid0.p, 1, size_t(n), s));
     if (!warm) c->cur_valid = 0;
     uint32_t* d_first_changed = P<uint32_t>(c->b_misc) + 8;
     unsigned long long* d_evals = reinterpret_cast<unsigned long long*>(P<uint8_t>(c->b_misc) + 128);
@@ -1156,7 +1149,7 @@ int ioc_resolve(ioc_ctx* c, int32_t* n_iter)
     a.q_count = P<uint32_t>(c->b_misc) + 9;
     a.q_cap = q_cap;
     a.incomplete = P<uint32_t>(c->b_misc) + 10;
-    const int eval_blocks = int(env_u32("IOC_EVAL_BLOCKS", 256 * 4));  // (what the chip holds: 4 workgroups of k_eval per CU)
+    const int eval_blocks = 256 * 4;  // (what the chip holds: 4 workgroups of k_eval per CU)
     const bool diag = getenv("IOC_EVAL_DIAG") != nullptr;
     a.diag = nullptr;
     if (diag) {

@@ -84,7 +84,6 @@ struct ioc_ctx {
     DevBuf b_cand_key, b_cand_size, b_cand_mapped, b_cand_count, b_qinfo, b_part, b_diag, b_top_all, b_pmins, b_pbnd;
     DevBuf b_dlong;  // ioc_index_build: the long queries' values gathered / sorted (iock_distinct_long)
     DevBuf b_exp_cid, b_exp_cnt, b_exp_off, b_exp_out, b_exp_work;  // ioc_index_export: final ids, per-slot counts / offsets, compact postings
-    bool have_guess = false;
     int64_t cand_capacity = 0;
 
     // ---- resolve ----
@@ -132,7 +131,7 @@ struct ioc_ctx {
     std::vector<double> res_err;
     bool have_res_seq = false;
     bool res_pool_ready = false;  // a_pool holds exactly res_seq
-    size_t aln_lds_max = 0, aln_lds_max2 = 0, aln_lds_max3 = 0;  // dynamic LDS a k_align_fwd<true/false> workgroup may reserve (residency cap)
+    size_t aln_lds_max = 0, aln_lds_max2 = 0;  // dynamic LDS a k_align_fwd<true/false> workgroup may reserve (residency cap)
 
     // ---- alignment results kept across the device passes of ioc_cluster_consensus (see AlnDriver) ----
     std::vector<uint64_t> aln_qid, aln_lid;  // sequence identity of every right entry / left representative

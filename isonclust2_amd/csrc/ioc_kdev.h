@@ -29,9 +29,6 @@
 #define IOC_SCORE_TRAV_CAPACITY 0  // 1 (instrumentation builds): IOC_COUNT_TRAVERSED counts the posting SLOTS of the wave steps, filled or not
 #endif
 #define IOC_OOB_FAR_BASE 0x00100000u  // counter base of lanes past the end of a chunk in the OOB variant (1 MB: outside any LDS)
-#ifndef IOC_SCORE_ABL
-#define IOC_SCORE_ABL 0
-#endif
 #ifndef IOC_SCORE_OLD_TRAVERSE
 #define IOC_SCORE_OLD_TRAVERSE 0  // 1: round 1's per-posting code in k_score_part (ablation builds)
 #endif

@@ -132,8 +132,6 @@ hipError_t iock_gap_bounds(hipStream_t st, int n, const int64_t* off_fwd, const 
                            const uint32_t* hpc_len, const uint8_t* err_cell, const int32_t* glim, uint2* out, const uint32_t* min_total,
                            uint32_t keep, uint32_t* keep_q);
 void iock_set_score_keep(const uint32_t* keep_q);
-hipError_t iock_guess_valid(hipStream_t st, int n, const int64_t* off_fwd, const int64_t* off_rev,
-                            const uint32_t* top_all, uint8_t* valid);
 hipError_t iock_decide_sweep(hipStream_t st, const void* args, int nblocks, int eval_blocks, uint32_t* q_count2);
 hipError_t iock_decide_phase2(hipStream_t st, const void* args, int nblocks, int eval_blocks, uint32_t* q_count2);
 hipError_t iock_copy_prefix_valid(hipStream_t st, int first, const uint8_t* vin, uint8_t* vout, uint32_t* ctl = nullptr);
@@ -146,7 +144,6 @@ hipError_t iock_query_table(hipStream_t st, int j, uint32_t L, const int64_t* of
                             const uint32_t* mins, const void* rows, uint32_t cap, uint32_t shift, const void* post,
                             const uint8_t* valid, uint32_t* hist, uint32_t* first, int post16);
 size_t iock_decide_args_size();
-void iock_set_score_variant(int v);
 void iock_set_part32(int v);
 void iock_set_score_oob(int v);
 void iock_set_score_shard(int stride, int offset);

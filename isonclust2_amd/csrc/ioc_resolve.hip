@@ -911,21 +911,6 @@ k_decide_pick(DecideArgs a)
     }
 }
 
-// First guess of "entry j opens a cluster" for the fixed-point resolve: j probably joins an earlier
-// cluster when some earlier entry shares more than ~5 % of its minimizers (background between unrelated
-// reads is ~1.6 % at k = 11).  Any guess converges to the same result; a good one saves sweeps and
-// evaluations.
-__global__ void __launch_bounds__(IOC_BLOCK)
-k_guess_valid(int n, const int64_t* __restrict__ off_fwd, const int64_t* __restrict__ off_rev,
-              const uint32_t* __restrict__ top_all, uint8_t* __restrict__ valid)
-{
-    const int j = blockIdx.x * IOC_BLOCK + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t nf = uint32_t(off_fwd[j + 1] - off_fwd[j]), nr = uint32_t(off_rev[j + 1] - off_rev[j]);
-    const uint32_t m = nf < nr ? nf : nr;
-    valid[j] = (uint64_t(top_all[j]) * 20ull < uint64_t(m)) ? 1 : 0;
-}
-
 __global__ void __launch_bounds__(IOC_BLOCK)
 k_copy_prefix_valid(int first, const uint8_t* __restrict__ vin, uint8_t* __restrict__ vout, uint32_t* __restrict__ ctl)
 {
@@ -1018,15 +1003,6 @@ hipError_t iock_gap_bounds(hipStream_t st, int n, const int64_t* off_fwd, const 
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_gap_bounds, dim3(n), dim3(IOC_BLOCK), 0, st, n, off_fwd, off_rev, pos, hpc_len, err_cell, glim, out, min_total, keep,
                        keep_q);
-    return hipGetLastError();
-}
-
-hipError_t iock_guess_valid(hipStream_t st, int n, const int64_t* off_fwd, const int64_t* off_rev,
-                            const uint32_t* top_all, uint8_t* valid)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_guess_valid, dim3((n + IOC_BLOCK - 1) / IOC_BLOCK), dim3(IOC_BLOCK), 0, st, n, off_fwd, off_rev,
-                       top_all, valid);
     return hipGetLastError();
 }
 

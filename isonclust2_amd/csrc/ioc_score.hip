@@ -41,11 +41,11 @@ __device__ __forceinline__ uint32_t list_lower_bound(const PT* __restrict__ p, u
 // a 6-step search per posting.  The kernel is VALU-issue bound, so instructions per posting are what
 // counts: the list bookkeeping is amortised over 4 postings.
 #define IOC_BM_WORDS 128  // + IOC_FLAT_UNROLL words of slack are allocated
-template <int V, typename PT>
+template <typename PT>
 __device__ __forceinline__ void flat_traverse(const PT* __restrict__ post, uint32_t o, uint32_t len,
                                               uint32_t* __restrict__ wb, unsigned long long* __restrict__ bm,
                                               uint32_t* __restrict__ h, uint32_t rbase, uint32_t hi,
-                                              unsigned long long& trav, uint32_t& abl)
+                                              unsigned long long& trav)
 {
     const int lane = lane_id();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -94,12 +94,7 @@ __device__ __forceinline__ void flat_traverse(const PT* __restrict__ post, uint3
             for (int u = 0; u < IOC_FLAT_UNROLL; ++u) {
                 const uint32_t p = (w0 + u) * 64u + uint32_t(lane);
                 const bool in = p < total;
-                const uint32_t a = in ? base[u] + p : 0u;
-                if (V == 2 || V == 6 || V == 7) {  // ablation: no posting loads
-                    tg[u] = make_uint4(a & 2047u, (a + 1) & 2047u, (a + 2) & 2047u, (a + 3) & 2047u);
-                } else {
-                    tg[u] = post4[a];
-                }
+                tg[u] = post4[in ? base[u] + p : 0u];
                 if (!in) tg[u] = make_uint4(IOC_EMPTY, IOC_EMPTY, IOC_EMPTY, IOC_EMPTY);
             }
 #pragma unroll
@@ -120,15 +115,9 @@ __device__ __forceinline__ void flat_traverse(const PT* __restrict__ post, uint3
                 }
 #pragma unroll
                 for (int e = 0; e < int(PER); ++e) {
-                    if (V == 1 || V == 6) {  // ablation: no LDS atomics
-                        if (t4[e] < hi) abl += t4[e];
-                    } else if (V == 7) {  // ablation: plain LDS stores instead of atomics
-                        if (t4[e] < hi) h[t4[e] - rbase] = t4[e];
-                    } else {
-                        // ascending list: entries >= hi (later targets, padding) are not visible;
-                        // t - rbase wraps for entries below a range pass's window
-                        if (t4[e] - rbase < hi - rbase) atomicAdd(&h[t4[e] - rbase], 1u);
-                    }
+                    // ascending list: entries >= hi (later targets, padding) are not visible;
+                    // t - rbase wraps for entries below a range pass's window
+                    if (t4[e] - rbase < hi - rbase) atomicAdd(&h[t4[e] - rbase], 1u);
                 }
             }
         }
@@ -185,17 +174,7 @@ __device__ __forceinline__ void count_word_u16(uint32_t w, uint32_t T, uint32_t 
 {
     uint32_t a;
     unsigned long long sv;
-#if IOC_SCORE_ABL == 1   // ablation build: no LDS atomics
-    asm volatile("v_cmp_lt_u32_sdwa vcc, %2, %3 src0_sel:WORD_0 src1_sel:DWORD\n\tv_mad_u32_u16 %0, %2, 4, %4 op_sel:[0,0,0,0]\n\t"
-                 "v_cmp_lt_u32_sdwa vcc, %2, %3 src0_sel:WORD_1 src1_sel:DWORD\n\tv_mad_u32_u16 %0, %2, 4, %4 op_sel:[1,0,0,0]"
-                 : "=&v"(a), "=&s"(sv) : "v"(w), "v"(T), "v"(hbase), "v"(one) : "vcc", "memory");
-    return;
-#elif IOC_SCORE_ABL == 2  // ablation build: conflict-free atomics (every lane its own bank)
-    hbase += (threadIdx.x & 31u) * 4u;
-    w = 0;
-    T = T ? 1u : 0u;
-#endif
-    if constexpr (OOB && IOC_SCORE_ABL == 0) {
+    if constexpr (OOB) {
         uint32_t a2;
         (void)sv;
         (void)T;
@@ -239,7 +218,7 @@ static_assert(IOC_FLAT_UNROLL16 <= IOC_FLAT_UNROLL, "the bitmap's slack words ar
 template <bool OOB>
 __device__ __forceinline__ void flat_traverse_u16(const uint16_t* __restrict__ post, uint32_t o, uint32_t len,
                                                   uint32_t* __restrict__ wb, unsigned long long* __restrict__ bm,
-                                                  uint32_t* __restrict__ h, uint32_t T, unsigned long long& trav, uint32_t& abl)
+                                                  uint32_t* __restrict__ h, uint32_t T, unsigned long long& trav)
 {
     const int lane = lane_id();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -252,7 +231,7 @@ __device__ __forceinline__ void flat_traverse_u16(const uint16_t* __restrict__ p
     const uint32_t excl = incl - lenU;
     const uint32_t nwords = (total + 63) >> 6;
     if (nwords > IOC_BM_WORDS) {  // a very long chunk: the general path (6-step search)
-        flat_traverse<0, uint16_t>(post, o, len, wb, bm, h, 0u, T, trav, abl);
+        flat_traverse<uint16_t>(post, o, len, wb, bm, h, 0u, T, trav);
         return;
     }
     const uint4* __restrict__ post4 = reinterpret_cast<const uint4*>(post);
@@ -295,7 +274,7 @@ __device__ __forceinline__ void flat_traverse_u16(const uint16_t* __restrict__ p
             // (a lane past the end of the concatenation loaded unit 0: a window of 0 targets rejects all of it)
             const bool inl = (w0 + u) * 64u + uint32_t(lane) < total;
             const uint32_t Tl = inl ? T : 0u;
-            const uint32_t hb = (OOB && IOC_SCORE_ABL == 0) ? (inl ? hbase : IOC_OOB_FAR_BASE) : hbase;  // (1 MB: outside any LDS)
+            const uint32_t hb = OOB ? (inl ? hbase : IOC_OOB_FAR_BASE) : hbase;  // (1 MB: outside any LDS)
             count_word_u16<OOB>(tg[u].x, Tl, hb, one);
             count_word_u16<OOB>(tg[u].y, Tl, hb, one);
             count_word_u16<OOB>(tg[u].z, Tl, hb, one);
@@ -311,7 +290,7 @@ __device__ __forceinline__ void flat_traverse_u16(const uint16_t* __restrict__ p
     __builtin_amdgcn_wave_barrier();
 }
 
-template <int V, typename PT>
+template <typename PT>
 __global__ void __launch_bounds__(IOC_BLOCK)
 k_score_t(int n, uint32_t L, const int64_t* __restrict__ off_fwd, const int64_t* __restrict__ off_rev,
         const uint32_t* __restrict__ mins, const uint4* __restrict__ rows, uint32_t cap, uint32_t shift,
@@ -336,7 +315,6 @@ k_score_t(int n, uint32_t L, const int64_t* __restrict__ off_fwd, const int64_t*
     const uint64_t cbase = 2ull * L * uint64_t(j) + uint64_t(j) * uint64_t(j > 0 ? j - 1 : 0);
     uint32_t written = 0;
     unsigned long long trav = 0;
-    uint32_t abl = 0;
     uint32_t* const wb_ = s_wb[wave];
     unsigned long long* const bm_ = s_bm[wave];
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -358,7 +336,6 @@ k_score_t(int n, uint32_t L, const int64_t* __restrict__ off_fwd, const int64_t*
                 const int64_t t = b + wave * 64 + lane;
                 if (t < e) index_lookup(rows, cap, shift, mins[t], o_nx, c_nx, q_nx);
             }
-            if (V == 5) continue;  // ablation: no probes, no traversal
             for (int64_t c0 = b + wave * 64; c0 < e; c0 += IOC_WAVES * 64) {
                 uint32_t o = o_nx, len = c_nx;
                 const uint2 qi = q_nx;
@@ -385,11 +362,7 @@ k_score_t(int n, uint32_t L, const int64_t* __restrict__ off_fwd, const int64_t*
                         o += i0;
                     }
                 }
-                if (V == 4) {  // ablation: probes only
-                    abl += len + o;
-                } else {
-                    flat_traverse<V, PT>(post, o, len, wb_, bm_, h, rbase, hi, trav, abl);
-                }
+                flat_traverse<PT>(post, o, len, wb_, bm_, h, rbase, hi, trav);
             }
         }
         __syncthreads();
@@ -442,7 +415,6 @@ k_score_t(int n, uint32_t L, const int64_t* __restrict__ off_fwd, const int64_t*
         __syncthreads();
     }
     if (threadIdx.x == 0 && !audit_valid) cand_count[j] = written;
-    if (V != 0 && abl == 0x12345678u) cand_count[j] = abl;  // keeps the ablated loads alive
     if (traversed && lane == 0) atomicAdd(traversed, trav);
 }
 
@@ -537,7 +509,6 @@ k_score_part(int n, uint32_t L, const int64_t* __restrict__ off_fwd, const int64
     uint32_t* const wb_ = s_wb[wave];
     unsigned long long* const bm_ = s_bm[wave];
     unsigned long long trav = 0;
-    uint32_t abl = 0;
     const bool narrow = *max_len < 65536u;  // two u16 counts per word (cbase and 2T are even)
     for (int s = 0; s < 2; ++s) {
         for (uint32_t i = threadIdx.x; i < T; i += IOC_BLOCK) hist[i] = 0;
@@ -578,9 +549,9 @@ k_score_part(int n, uint32_t L, const int64_t* __restrict__ off_fwd, const int64
                     len = list_lower_bound(post + o, len, T);
             }
             if (sizeof(PT) == 2 && !IOC_SCORE_OLD_TRAVERSE)
-                flat_traverse_u16<OOB>(reinterpret_cast<const uint16_t*>(post), o, len, wb_, bm_, h, T, trav, abl);
+                flat_traverse_u16<OOB>(reinterpret_cast<const uint16_t*>(post), o, len, wb_, bm_, h, T, trav);
             else
-                flat_traverse<0, PT>(post, o, len, wb_, bm_, h, 0u, T, trav, abl);
+                flat_traverse<PT>(post, o, len, wb_, bm_, h, 0u, T, trav);
         }
         __syncthreads();
         // the partial histogram of (query, partition) is [strand][target]: this strand's slice
@@ -699,7 +670,7 @@ k_score_compact(int n, uint32_t L, const uint32_t* __restrict__ part, uint32_t k
     if (threadIdx.x == 0 && top_all && !audit_valid) {
         uint32_t t = 0;
         for (int w = 0; w < IOC_WAVES; ++w) t = wtop[w] > t ? wtop[w] : t;
-        top_all[j] = t;  // largest Size against ANY earlier entry: seeds the resolve's first guess
+        top_all[j] = t;  // largest Size against ANY earlier entry
     }
     if (audit_valid) {
         unsigned long long sum = 0;
@@ -855,7 +826,6 @@ __global__ void __launch_bounds__(256) k_query_compact_many(const int32_t* __res
 // =====================================================================================================
 // launchers
 // =====================================================================================================
-static int g_score_variant = 0;
 static int g_part32 = 0;
 static int g_score_oob = 0;  // k_score_part without a window test (ioc_ctx_create's probe passed, or IOC_SCORE_OOB=1)
 // sharded merge: this rank scores the queries j with j % stride == offset 
@@ -866,7 +836,6 @@ static thread_local const uint32_t* g_keep_q = nullptr;  // per-query compaction
 
 extern "C" {
 
-void iock_set_score_variant(int v) { g_score_variant = v; }
 void iock_set_part32(int v) { g_part32 = v; }
 void iock_set_score_oob(int v) { g_score_oob = v; }
 void iock_set_score_keep(const uint32_t* keep_q) { g_keep_q = keep_q; }
@@ -935,28 +904,19 @@ hipError_t iock_score(hipStream_t st, int n, uint32_t L, const int64_t* off_fwd,
         return hipGetLastError();
     }
     const Epochs E = iock_epoch_bounds(L, uint32_t(n));
-#define LAUNCH_SCORE(V, PT, PP)                                                                                      \
+#define LAUNCH_SCORE(PT, PP)                                                                                         \
     do {                                                                                                             \
         if (lds > 48 * 1024)                                                                                         \
-            CK(hipFuncSetAttribute((const void*)k_score_t<V, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds))); \
-        hipLaunchKernelGGL((k_score_t<V, PT>), dim3(nown), dim3(IOC_BLOCK), lds, st, n, L, off_fwd, off_rev, mins,   \
+            CK(hipFuncSetAttribute((const void*)k_score_t<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds))); \
+        hipLaunchKernelGGL((k_score_t<PT>), dim3(nown), dim3(IOC_BLOCK), lds, st, n, L, off_fwd, off_rev, mins,   \
                            (const uint4*)rows, cap, shift, PP, range, keep, cand_key, cand_size, cand_count,         \
                            traversed, E, audit_valid, audit_sum, own_s, own_o, audit_valid ? nullptr : g_keep_q); \
     } while (0)
-    if (post16) {
-        LAUNCH_SCORE(0, uint16_t, post_h);
-        return hipGetLastError();
-    }
-    switch (g_score_variant) {  // ablation builds for profiling only (IOC_SCORE_VARIANT); 0 = production
-        case 1: LAUNCH_SCORE(1, uint32_t, post); break;
-        case 2: LAUNCH_SCORE(2, uint32_t, post); break;
-        case 3: LAUNCH_SCORE(3, uint32_t, post); break;
-        case 4: LAUNCH_SCORE(4, uint32_t, post); break;
-        case 5: LAUNCH_SCORE(5, uint32_t, post); break;
-        case 6: LAUNCH_SCORE(6, uint32_t, post); break;
-        case 7: LAUNCH_SCORE(7, uint32_t, post); break;
-        default: LAUNCH_SCORE(0, uint32_t, post); break;
-    }
+    if (post16)
+        LAUNCH_SCORE(uint16_t, post_h);
+    else
+        LAUNCH_SCORE(uint32_t, post);
+#undef LAUNCH_SCORE
     return hipGetLastError();
 }
 
