@@ -237,7 +237,9 @@ int ioc_cluster_consensus(ioc_ctx* c, const ioc_params* p, const char* table_pat
     // away anyway.  The window follows the distance between events (fast mode: thousands of entries, sahlin mode
     // with small clusters: a handful).
     DirtyIndex dirty;
-    const int dirty_thr = std::max(1, int(double(p->min_shared) * p->min_fraction));
+    // (the smallest Size a walk can reach: int(MinShared * MinFraction) in the mapping, but never above MinShared — with
+    // MinFraction > 1 the mapping walks nothing and the alignment fallback still tries the candidates of Size top >= MinShared)
+    const int dirty_thr = std::max(1, std::min(p->min_shared, int(double(p->min_shared) * p->min_fraction)));
     const bool one_event_per_pass = getenv("IOC_CONS_RESTART_ALWAYS") != nullptr;  // (the first version of this driver)
     int window = n;
     if (const char* e = getenv("IOC_CONS_WINDOW")) window = std::max(1, atoi(e));

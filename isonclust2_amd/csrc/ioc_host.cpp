@@ -199,8 +199,14 @@ int ioc_host_gap_limits(const char* table_path, int32_t k, int32_t w, double min
         // predicate of cluster.cpp:333-347: pow(pError, double(n)) >= MinProbNoHits, monotone in n
         int32_t lim = -1;
         if (pow(pe, 0.0) >= min_prob_no_hits) {
+            // the search starts near log(p0) / log(pError) and settles on the pow() predicate itself: the same limit as a walk
+            // from 0, without its 4 M calls per cell where every gap passes (p0 <= 0, or pError == 1)
             lim = 0;
-            while (lim < INT32_MAX - 2 && pow(pe, double(lim + 1)) >= min_prob_no_hits) {
+            const double est = std::floor(std::log(min_prob_no_hits) / std::log(pe));
+            if (std::isfinite(est) && est > 2.0) lim = est > double(1 << 22) ? (1 << 22) : int32_t(est) - 2;
+            if (!(min_prob_no_hits > 0.0) || pe >= 1.0) lim = (1 << 22);  // (the predicate holds for every n)
+            while (lim > 0 && !(pow(pe, double(lim)) >= min_prob_no_hits)) lim--;
+            while (pow(pe, double(lim + 1)) >= min_prob_no_hits) {
                 lim++;
                 if (lim > (1 << 22)) {  // pError == 1 (or p0 <= 0): every gap passes
                     lim = INT32_MAX - 2;

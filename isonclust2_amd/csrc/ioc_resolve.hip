@@ -65,9 +65,12 @@ k_gap_bounds(int n, const int64_t* __restrict__ off_fwd, const int64_t* __restri
     // (keep_q: fast mode only — the tie sets of the alignment fallback are made of candidates that fail the mapping)
     const uint32_t need = min_total ? min_total[j] : 0u;
     uint32_t smin = 0xFFFFFFFFu;
-    uint32_t lim[15];
+    uint32_t lim[15], lim_max = 0;
 #pragma unroll
-    for (int e = 0; e < 15; ++e) lim[e] = ecr >= 0 ? uint32_t(glim[e * 15 + ecr] + 1) : 0u;
+    for (int e = 0; e < 15; ++e) {
+        lim[e] = ecr >= 0 ? uint32_t(glim[e * 15 + ecr] + 1) : 0u;
+        lim_max = lim[e] > lim_max ? lim[e] : lim_max;
+    }
     for (int s = 0; s < 2; ++s) {
         const int64_t b = s ? off_rev[j] : off_fwd[j];
         const uint32_t M = uint32_t((s ? off_rev[j + 1] : off_fwd[j + 1]) - b);
@@ -76,10 +79,12 @@ k_gap_bounds(int n, const int64_t* __restrict__ off_fwd, const int64_t* __restri
 #pragma unroll
         for (int e = 0; e < 15; ++e) d[e] = hd[e] = tl[e] = 0;
         if (ecr >= 0 && M > 0) {
-            // the widest span of lim[e] consecutive minimizers: the limits of a column of the table ascend with the target's cell,
-            // equal neighbours (6 - 13 distinct values of 15) share their maximum
+            // the widest span of lim[e] consecutive minimizers, per target cell; equal neighbours (6 - 13 distinct values of 15) share
+            // their maximum.  The limits of a column of the table do NOT always ascend with the target's cell (the reference's
+            // table is empirical: at (k, w) = (21, 50), query cell 11, they end 82, 113, 111), so every extent below is taken from
+            // the column's largest limit, never from lim[14].
             // (the positions pass through LDS, GB_CHUNK at a time with a halo of GB_HALO behind them: the 6 - 13 reads per entry
-            // are latency in global memory; a limit above the halo — none in the reference's table — reads global memory)
+            // are latency in global memory; a limit above the halo — k >= 16 at 0.1, or a small MinProbNoHits — reads global memory)
             for (uint32_t c0 = 0; c0 < M; c0 += GB_CHUNK) {
                 const uint32_t cn = (M - c0 < GB_CHUNK + GB_HALO) ? M - c0 : GB_CHUNK + GB_HALO;  // staged entries
                 __syncthreads();
@@ -89,7 +94,7 @@ k_gap_bounds(int n, const int64_t* __restrict__ off_fwd, const int64_t* __restri
                     if (c0 + x + 1u < M && p[c0 + x + 1u] < v) s_nonmono = 1u;  // (a list that does not ascend: no bound for this query)
                 }
                 const uint32_t ce = (M - c0 < GB_CHUNK) ? M - c0 : GB_CHUNK;
-                const bool in_lds = lim[14] <= GB_HALO;
+                const bool in_lds = lim_max <= GB_HALO;
                 // (the list's end inside the staged stretch: the last position repeated behind it, so that "the minimizer lim
                 // places on, or the last one" is a plain read)
                 if (c0 + cn == M && in_lds)
@@ -119,8 +124,8 @@ k_gap_bounds(int n, const int64_t* __restrict__ off_fwd, const int64_t* __restri
             for (int e = 1; e < 15; ++e)
                 if (lim[e] == lim[e - 1]) d[e] = d[e - 1];
             // the farthest head (a first hit at index < lim still counts its position) and the longest tail (a last hit with fewer
-            // than lim minimizers behind it still counts the rest of the sequence): the first / last lim[14] entries
-            const uint32_t lmax = lim[14] < M ? lim[14] : M;
+            // than lim minimizers behind it still counts the rest of the sequence): the first / last max_e lim[e] entries
+            const uint32_t lmax = lim_max < M ? lim_max : M;
             for (uint32_t i = threadIdx.x; i < lmax; i += IOC_BLOCK) {
                 const uint32_t a0 = p[i], a1 = p[M - 1u - i];
                 const uint32_t t1 = hl > a1 ? hl - a1 : 0u;
@@ -255,7 +260,9 @@ k_decide_scan(DecideArgs a)
         }
         __syncthreads();
         top = s_top;
-        if (top < uint32_t(a.min_shared)) {
+        // no candidate is a cluster (top == 0: the reference's order is empty, cluster.cpp:371-373 — with MinShared <= 0 the Size
+        // rule below would otherwise walk the empty register slots past the list), or the top Size is below MinShared: new cluster
+        if (top == 0 || top < uint32_t(a.min_shared)) {
             if (threadIdx.x == 0) {
                 a.cut[j] = IOC_CUT_NEG;
                 a.walk_n[j] = 0;
@@ -278,10 +285,14 @@ k_decide_scan(DecideArgs a)
     // phase 2 the rest of the walk for the undecided queries.  A walk candidate whose totalMapped is not cached yet — and that its
     // upper bound does not reject — is an item for k_eval.
     const uint32_t need = a.min_total[j];
+    // MinFraction > 1 can put the cut above top: the reference's walk stops at its first candidate (cluster.cpp:386-388), no
+    // candidate passes the mapping.  The candidates of Size top still make the walk — k_decide_pick takes the alignment
+    // fallback's tie set from it (cluster.cpp:481-489) — but none of them is evaluated, and k_decide_pick skips them.
+    const int wcut = cut < int(top) ? cut : int(top);
     auto take = [&](uint32_t c, uint32_t sz) {  // candidate c is a cluster and passes the Size rule of the phase
         const uint32_t pw = atomicAdd(&s_nw, 1u);
         if (pw < IOC_WALK_SLOTS) s_walk[pw] = c;
-        if (a.cand_mapped[cbase + c] != 0xFFFFFFFFu) return;
+        if (int(sz) < cut || a.cand_mapped[cbase + c] != 0xFFFFFFFFu) return;
         if (a.gap_bound && bound_rejects(a, j, a.cand_key[cbase + c], sz, need)) {
             a.cand_mapped[cbase + c] = IOC_MAPPED_REJECTED;
             return;
@@ -300,7 +311,7 @@ k_decide_scan(DecideArgs a)
     if (a.phase == 1) {
 #pragma unroll
         for (int k = 0; k < IOC_SCAN_CACHE; ++k)
-            if (csz[k] == top) take(uint32_t(k) * IOC_BLOCK + threadIdx.x, top);  // (top >= MinShared > 0: never an empty slot)
+            if (csz[k] == top) take(uint32_t(k) * IOC_BLOCK + threadIdx.x, top);  // (top > 0: never an empty slot)
         for (uint32_t c = IOC_SCAN_CACHE * IOC_BLOCK + threadIdx.x; c < C; c += IOC_BLOCK) {
             const uint32_t sz = a.cand_size[cbase + c];
             if (sz != top) continue;
@@ -310,7 +321,7 @@ k_decide_scan(DecideArgs a)
     } else {
         for (uint32_t c = threadIdx.x; c < C; c += IOC_BLOCK) {
             const uint32_t sz = a.cand_size[cbase + c];
-            if (int(sz) < cut) continue;
+            if (int(sz) < wcut) continue;
             const uint32_t tg = a.cand_key[cbase + c] >> 1;
             if ((tg < L) || a.valid_in[tg - L]) take(c, sz);
         }
@@ -819,7 +830,7 @@ k_decide_pick(DecideArgs a)
                 const uint32_t pos = atomicAdd(&s_tn, 1u);
                 if (pos < IOC_TIE_SLOTS) s_tk[pos] = key;
             }
-            if (!ok || (a.phase == 1 ? sz != top : int(sz) < cut)) continue;
+            if (!ok || int(sz) < cut || (a.phase == 1 && sz != top)) continue;
             const uint32_t tm = a.cand_mapped[cbase + c];
             if (tm == IOC_MAPPED_REJECTED) continue;  // fails by its upper bound
             if (tm == 0xFFFFFFFFu) {

@@ -18,7 +18,7 @@ import numpy as np
 
 from isonclust2_amd import _lib, api, pipeline, synth
 from oracle import pyoracle as po
-from tests.helpers import ToyGraphs, oracle_entry_assignments, oracle_sorted_batch
+from tests.helpers import ToyGraphs, oracle_entry_assignments, oracle_sorted_batch, param_pair
 
 
 def _with_sequences(rs, view):
@@ -46,14 +46,31 @@ def draw_parity(rng, aln_mode=None):
     return dict(n=n, g=g, ln=ln, qlo=qlo, qhi=qhi, dup=dup, jit=jit, k=k, w=w, seed=seed, mode=aln_mode or "fast")
 
 
+def draw_parity_params(rng):
+    """A fast-mode parity case away from the default point: (k, w) anywhere in the table (k 10 - 30, w k - k+31) and the
+    thresholds drawn from the values the clustering shortcuts treat differently (the `params` key of a case)."""
+    c = draw_parity(rng)
+    k = int(rng.integers(10, 31))
+    w = int(rng.integers(k, k + 32))
+    params = dict(min_shared=int(rng.choice([-1, 0, 1, 2, 3, 5, 12])),
+                  min_fraction=float(rng.choice([0.0, 0.5, 0.8, 1.0, 1.25])),
+                  mapped_threshold=float(rng.choice([0.0, 0.3, 0.65, 0.9, 0.99, 1.0, 1.2])),
+                  min_prob_no_hits=float(rng.choice([1e-4, 0.01, 0.05, 0.1, 0.5, 1.0, 1.5])))
+    c.update(k=k, w=w, params=params)
+    return c
+
+
 def run_parity(ctx, c, merge=False):
-    """c: a dict as draw_parity makes it.  Returns (ok, detail)."""
+    """c: a dict as draw_parity makes it; its optional `params` (tests/helpers.param_pair keys) override the defaults on both
+    sides.  Returns (ok, detail)."""
     rs = synth.generate(c["n"], c["g"], c["ln"], c["qlo"], c["qhi"], seed=c["seed"], dup_every=c["dup"], len_jitter=c["jit"])
     k, w, mode = c["k"], c["w"], c["mode"]
-    B, view = oracle_sorted_batch(rs, k, w)
+    pd = dict(c.get("params") or {}, k=k, w=w)
+    ap, op = param_pair(pd, mode)
+    B, view = oracle_sorted_batch(rs, k, w, params=op)
     ocl, ost, _ = oracle_entry_assignments(B, view, mode=mode)
     v = _with_sequences(rs, view) if mode != "fast" else view
-    cls, strand, st = ctx.cluster_batch(api.default_params(k, w, mode), v)
+    cls, strand, st = ctx.cluster_batch(ap, v)
     if not (np.array_equal(cls, ocl) and np.array_equal(strand, ost)):
         d = np.nonzero((cls != ocl) | (strand != ost))[0]
         return False, f"entries {d[:5].tolist()}: device {cls[d[:5]].tolist()} oracle {ocl[d[:5]].tolist()}"
@@ -61,7 +78,7 @@ def run_parity(ctx, c, merge=False):
         n = c["n"]
         R = po.ReadSet.from_flat(rs.seq, rs.qual, rs.offs)
         R.score_sort(k, w)
-        p = po.default_params(k, w)
+        afast, p = param_pair(pd, "fast")
         cut = n // 2
         obs, cbs = [], []
         for b, (lo, hi) in enumerate(((0, cut - 1), (cut, n - 1))):
@@ -73,9 +90,9 @@ def run_parity(ctx, c, merge=False):
             sb = pipeline.SortedBatch(view=vw, read_ids=info["orig"].astype(np.int64), batch_nr=b, batch_start=lo, batch_end=hi)
             Bo.cluster(mode="fast")
             obs.append(Bo)
-            cbs.append(pipeline.cluster_single(ctx, api.default_params(k, w, "fast"), sb))
+            cbs.append(pipeline.cluster_single(ctx, afast, sb))
         obs[0].cluster(right=obs[1], mode="fast")
-        merged = pipeline.cluster_merge(ctx, api.default_params(k, w, "fast"), cbs[0], cbs[1])
+        merged = pipeline.cluster_merge(ctx, afast, cbs[0], cbs[1])
         mo, ms = obs[0].assignments(rs.n)
         mc, mst = merged.assignments(rs.n)
         if not (np.array_equal(mc, mo) and np.array_equal(mst, ms)):
@@ -99,10 +116,10 @@ def draw_consensus(rng, mode="fast"):
     return dict(n=n, g=g, ln=ln, cmax=cmax, cmin=cmin, period=period, seed=seed, dup=dup, mode=mode, qlo=11, qhi=22)
 
 
-def oracle_consensus_run(rs, cons_max, cons_min, period, mode="fast", k=11, w=15, graphs=None, ops_pointer=None):
+def oracle_consensus_run(rs, cons_max, cons_min, period, mode="fast", k=11, w=15, graphs=None, ops_pointer=None, params=None):
     R = po.ReadSet.from_flat(rs.seq, rs.qual, rs.offs)
     R.score_sort(k, w)
-    p = po.default_params(k, w)
+    p = param_pair(dict(params or {}, k=k, w=w))[1]
     p.cons_max_size = cons_max
     B = po.Batch(R, 0, rs.n - 1, p)
     info, off_f, off_r, mn, ps = B.minimizer_soa()
@@ -122,7 +139,7 @@ def run_consensus(ctx, c, speculate=None):
     """speculate: None = the library's default (deferred consensus), False = IOC_CONS_SPECULATE=0 (every event at once)."""
     rs = synth.generate(c["n"], c["g"], c["ln"], c["qlo"], c["qhi"], seed=c["seed"], dup_every=c["dup"])
     mode = c["mode"]
-    B, view, ost, og = oracle_consensus_run(rs, c["cmax"], c["cmin"], c["period"], mode=mode)
+    B, view, ost, og = oracle_consensus_run(rs, c["cmax"], c["cmin"], c["period"], mode=mode, params=c.get("params"))
     acl, ast = B.assignments(rs.n)
     ocl, ostr = acl[view["orig"]], ast[view["orig"]]
     v = _with_sequences(rs, view)
@@ -132,7 +149,7 @@ def run_consensus(ctx, c, speculate=None):
     if speculate is False:
         os.environ["IOC_CONS_SPECULATE"] = "0"
     try:
-        cls, strand, st = ctx.cluster_consensus(api.default_params(11, 15, mode), None, v, cargs, pg.ops)
+        cls, strand, st = ctx.cluster_consensus(param_pair(c.get("params"), mode)[0], None, v, cargs, pg.ops)
     finally:
         if speculate is False:
             if old is None:

@@ -29,6 +29,73 @@ def oracle_entry_assignments(B, view, mode="fast"):
     return acl[view["orig"]], ast[view["orig"]], st
 
 
+PARAM_KEYS = ("min_shared", "min_fraction", "mapped_threshold", "min_prob_no_hits", "aligned_threshold")
+
+
+def param_pair(d=None, mode="fast"):
+    """(api.Params, po.Params) with the same values: the defaults of CmdArgs overridden by the dict `d` (k, w and any of
+    PARAM_KEYS).  The one place the product's and the oracle's parameters are made alike."""
+    from isonclust2_amd import api
+    d = d or {}
+    bad = set(d) - set(PARAM_KEYS) - {"k", "w"}
+    assert not bad, bad
+    k, w = int(d.get("k", 11)), int(d.get("w", 15))
+    a, o = api.default_params(k, w, mode), po.default_params(k, w, mode)
+    for key in PARAM_KEYS:
+        if key in d:
+            setattr(a, key, d[key])
+            setattr(o, key, d[key])
+    return a, o
+
+
+def compare_candidate_tables(ctx, view, rows, calls, entries, tgt, thr=0.65, size_cut=0):
+    """The device's candidate table of every traced entry (ctx.query_candidates) against the oracle's trace rows: the multiset of
+    (cluster, strand, Size, first index), and every totalMapped either side evaluated.  thr: the MappedThreshold of the run (a
+    candidate the upper bound rejected must fail it on the oracle's exact total).  size_cut: the Size below which the Size rule
+    alone excludes a candidate whatever its total (int(MinShared * MinFraction), see ioc_set_params' `keep`), which the list
+    cut also marks rejected: allowed to pass the threshold, never walked by the oracle.  Returns (rows, walked,
+    device-evaluated)."""
+    from isonclust2_amd import api
+    n = len(tgt)
+    opener = tgt < 0
+    # single batch, L = 0: target = entry that opened the cluster -> cluster id in creation order
+    cid = np.full(n, -1, np.int64)
+    gated = np.asarray(view["state"]) != 0
+    cid[opener & ~gated] = np.arange(int((opener & ~gated).sum()))
+    n_rows = n_walked = n_dev_eval = n_bound = 0
+    for e in entries:
+        m = rows["entry"] == e
+        t, s, sz, fi, tm = ctx.query_candidates(int(e), 2 * n + 2)
+        dev = sorted(zip(cid[t].tolist(), s.tolist(), sz.tolist(), fi.tolist()))
+        orc = sorted(zip(rows["cls"][m].tolist(), rows["strand"][m].tolist(), rows["size"][m].tolist(),
+                         rows["first_index"][m].tolist()))
+        assert dev == orc, (e, len(dev), len(orc))
+        n_rows += len(orc)
+        tot = {(c, st): (x, w) for c, st, x, w in zip(rows["cls"][m].tolist(), rows["strand"][m].tolist(),
+                                                      rows["total_mapped"][m].tolist(), rows["walked"][m].tolist())}
+        need = api.host_min_total(int(view["hpc_len"][e]), thr)
+        for c, st, x, z in zip(cid[t].tolist(), s.tolist(), tm.tolist(), sz.tolist()):
+            want, walked = tot[(c, st)]
+            if x == 0xFFFFFFFE and z < size_cut and want >= need:
+                assert not walked, (e, c, st, z, size_cut)
+                n_bound += 1
+                continue
+            if x == 0xFFFFFFFE:
+                # rejected by the upper bound of totalMapped (k_gap_bounds) without an evaluation: the bound is sound iff the
+                # oracle's exact total fails the threshold as well
+                assert want < need, (e, c, st, want, need)
+                n_bound += 1
+                n_walked += 1 if walked else 0
+                continue
+            if walked:
+                assert x == want, (e, c, st, x, want)          # the reference called getMappedRatio here
+                n_walked += 1
+            if x != 0xFFFFFFFF:
+                assert x == want, (e, c, st, x, want)          # whatever the device evaluated is the oracle's value
+                n_dev_eval += 1
+    return n_rows, n_walked, n_dev_eval + n_bound
+
+
 from isonclust2_amd.digest import fnv1a  # noqa: E402,F401  (one definition for tests, goldens and bench)
 
 

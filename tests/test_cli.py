@@ -136,13 +136,27 @@ def _write_fastq(rs, path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["fast", "sahlin"])
 def test_sort_cluster_merge_dump_matches_oracle(tmp_path, mode):
-    from oracle import pyoracle as po
     rs = synth.generate(360, 30, 700, 9, 21, seed=21) if mode == "fast" else synth.generate(160, 16, 450, 9, 20, seed=22)
+    sort_cluster_merge_dump_vs_oracle(tmp_path, mode, rs)
+
+
+SORT_FLAGS = (("k", "-k"), ("w", "-w"), ("min_shared", "-m"), ("min_fraction", "-f"), ("mapped_threshold", "-r"),
+              ("min_prob_no_hits", "-p"), ("aligned_threshold", "-a"))
+
+
+def sort_cluster_merge_dump_vs_oracle(tmp_path, mode, rs, params=None):
+    """`sort` into two batches, `cluster` each, merge them, `dump`, against the oracle's same global sort, two batches and fold.
+    params: (k, w and) thresholds as tests/helpers.param_pair takes them, given to `sort` as its flags and to the oracle."""
+    from oracle import pyoracle as po
+    from tests.helpers import param_pair
+    d = dict(params or {})
+    _, p = param_pair(d)
+    flags = [x for key, fl in SORT_FLAGS if key in d for x in (fl, str(d[key]))]
     half = rs.n // 2
     fq = tmp_path / "reads.fq"
     _write_fastq(rs, fq)
     out = tmp_path / "sorted"
-    r = run("sort", "-v", "-B", "1000000", "-M", str(half), "-o", str(out), str(fq))
+    r = run("sort", "-v", *flags, "-B", "1000000", "-M", str(half), "-o", str(out), str(fq))
     assert r.returncode == 0, r.stderr
     b0, b1 = out / "batches" / "isONbatch_0.cer", out / "batches" / "isONbatch_1.cer"
     assert b0.exists() and b1.exists()
@@ -158,9 +172,8 @@ def test_sort_cluster_merge_dump_matches_oracle(tmp_path, mode):
 
     # ---- oracle: same global sort, same two batches, same fold ----
     R = po.ReadSet.from_flat(rs.seq, rs.qual, rs.offs)
-    R.score_sort(11, 15)
+    R.score_sort(p.k, p.w)
     order, score, _ = R.order()
-    p = po.default_params(11, 15)
     A, B = po.Batch(R, 0, half - 1, p, 0), po.Batch(R, half, rs.n - 1, p, 1)
     A.cluster(mode=mode)      # (sahlin: the oracle aligns with its own scalar aligner)
     B.cluster(mode=mode)

@@ -8,7 +8,7 @@ import pytest
 
 from isonclust2_amd import api, synth
 from oracle import pyoracle as po
-from tests.helpers import oracle_entry_assignments, oracle_sorted_batch
+from tests.helpers import compare_candidate_tables, oracle_entry_assignments, oracle_sorted_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -18,43 +18,6 @@ def ctx():
     c = api.Context(0)
     yield c
     c.close()
-
-
-def _compare(ctx, view, rows, calls, entries, tgt):
-    n = len(tgt)
-    opener = tgt < 0
-    # single batch, L = 0: target = entry that opened the cluster -> cluster id in creation order
-    cid = np.full(n, -1, np.int64)
-    gated = np.asarray(view["state"]) != 0
-    cid[opener & ~gated] = np.arange(int((opener & ~gated).sum()))
-    n_rows = n_walked = n_dev_eval = n_bound = 0
-    for e in entries:
-        m = rows["entry"] == e
-        t, s, sz, fi, tm = ctx.query_candidates(int(e), 2 * n + 2)
-        dev = sorted(zip(cid[t].tolist(), s.tolist(), sz.tolist(), fi.tolist()))
-        orc = sorted(zip(rows["cls"][m].tolist(), rows["strand"][m].tolist(), rows["size"][m].tolist(),
-                         rows["first_index"][m].tolist()))
-        assert dev == orc, (e, len(dev), len(orc))
-        n_rows += len(orc)
-        tot = {(c, st): (x, w) for c, st, x, w in zip(rows["cls"][m].tolist(), rows["strand"][m].tolist(),
-                                                      rows["total_mapped"][m].tolist(), rows["walked"][m].tolist())}
-        need = api.host_min_total(int(view["hpc_len"][e]), 0.65)
-        for c, st, x in zip(cid[t].tolist(), s.tolist(), tm.tolist()):
-            want, walked = tot[(c, st)]
-            if x == 0xFFFFFFFE:
-                # rejected by the upper bound of totalMapped (k_gap_bounds) without an evaluation: the bound is sound iff the
-                # oracle's exact total fails the threshold as well
-                assert want < need, (e, c, st, want, need)
-                n_bound += 1
-                n_walked += 1 if walked else 0
-                continue
-            if walked:
-                assert x == want, (e, c, st, x, want)          # the reference called getMappedRatio here
-                n_walked += 1
-            if x != 0xFFFFFFFF:
-                assert x == want, (e, c, st, x, want)          # whatever the device evaluated is the oracle's value
-                n_dev_eval += 1
-    return n_rows, n_walked, n_dev_eval + n_bound
 
 
 @pytest.mark.parametrize("cfg,seed,step", [("config1", 1, 7), ("short_dup", 1, 1), ("tiny", 7, 1)])
@@ -74,7 +37,7 @@ def test_candidate_tables_and_mapped_totals(ctx, cfg, seed, step):
     cls, strand, st = ctx.cluster_batch(p, view)
     assert np.array_equal(cls, ocl) and np.array_equal(strand, ost)
     tgt, _, _ = ctx.decisions()
-    n_rows, n_walked, n_dev = _compare(ctx, view, rows, calls, entries, tgt)
+    n_rows, n_walked, n_dev = compare_candidate_tables(ctx, view, rows, calls, entries, tgt, thr=p.mapped_threshold)
     assert n_rows == len(rows["entry"]) and n_rows > 10 * len(entries) // 4
     # every getMappedRatio call of the traced entries was seen
     assert n_walked == int(np.isin(calls["entry"], entries).sum())

@@ -83,6 +83,30 @@ def test_fuzz_parity(ctx, mode):
     assert not bad, f"{len(bad)} of {n + len(fixed)} cases differ from the oracle; first: python tools/fuzz_parity.py --case \"{bad[0][0]}\"  ({bad[0][1]})"
 
 
+# off the default point (fuzz_cases.draw_parity_params): a query without a cluster candidate under MinShared 0, MinFraction above 1,
+# a non-ascending gap-limit column with a limit above the LDS halo of k_gap_bounds
+_PARAMS_FIXED = [
+    dict(n=180, g=10, ln=300, qlo=9.0, qhi=20.0, dup=2, jit=0.0, k=11, w=15, seed=601, mode="fast",
+         params=dict(min_shared=0, min_fraction=0.5, mapped_threshold=0.65, min_prob_no_hits=1e-4)),
+    dict(n=120, g=6, ln=600, qlo=11.0, qhi=19.0, dup=0, jit=0.0, k=13, w=20, seed=602, mode="fast",
+         params=dict(min_shared=3, min_fraction=1.25, mapped_threshold=0.3, min_prob_no_hits=0.1)),
+    dict(n=40, g=4, ln=2500, qlo=8.0, qhi=11.0, dup=2, jit=0.0, k=21, w=50, seed=603, mode="fast",
+         params=dict(min_shared=1, min_fraction=0.8, mapped_threshold=0.99, min_prob_no_hits=0.1)),
+]
+
+
+def test_fuzz_parity_params(ctx):
+    rng = np.random.default_rng([SEED, 4])
+    count = [0]
+
+    def run(c):
+        count[0] += 1
+        return fz.run_parity(ctx, c, merge=(count[0] % 4 == 0))
+
+    bad, n = _slice(run, _PARAMS_FIXED, lambda: fz.draw_parity_params(rng))
+    assert not bad, f"{len(bad)} of {n + len(_PARAMS_FIXED)} cases differ from the oracle; first: python tools/fuzz_parity.py --case \"{bad[0][0]}\"  ({bad[0][1]})"
+
+
 _CONS_FIXED = [
     # tools/fuzz_consensus.py seed 34, case 52 (round 3): entry 82 meets two clusters tied at the top Size, both pass, and the
     # reference's hit order between them hangs on a Size-1 key of a THIRD cluster whose representative changed one entry earlier

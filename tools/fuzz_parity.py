@@ -3,7 +3,10 @@
 transcripts, (k, w); single batches and (fast mode) two-batch merges.  The cases are tests/fuzz_cases.py's — the same ones
 tests/test_gpu_fuzz.py runs in bounded slices.
     tools/fuzz_parity.py [cases] [seed] [sahlin|furious]
-    tools/fuzz_parity.py --case "{'n': 162, ...}"      replay one case (the reproducer a failing test prints)"""
+    tools/fuzz_parity.py --case "{'n': 162, ...}"      replay one case (the reproducer a failing test prints); a case's
+                                                     optional 'params' dict (min_shared, min_fraction, mapped_threshold,
+                                                     min_prob_no_hits, aligned_threshold) applies to both sides
+    tools/fuzz_parity.py [cases] [seed] params       draw the thresholds and (k, w) too (fuzz_cases.draw_parity_params)"""
 import ast
 import sys
 import time
@@ -25,7 +28,7 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1000)
 aln_mode = sys.argv[3] if len(sys.argv) > 3 else None
 bad, t0 = 0, time.time()
 for case in range(n_cases):
-    c = fz.draw_parity(rng, aln_mode)
+    c = fz.draw_parity_params(rng) if aln_mode == "params" else fz.draw_parity(rng, aln_mode)
     try:
         ok, why = fz.run_parity(ctx, c, merge=(case % 4 == 0))
     except Exception as e:   # noqa: BLE001
