@@ -1029,10 +1029,6 @@ k_align_trace(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__
     WinStat ws;
     ws.blanks((m - j) + (n - i), kmask, k, il);  // trailing end gaps are the tail of the string
 
-#ifdef TR_PROF
-    unsigned long long tp_load = 0, tp_comp = 0, tp_walk = 0, tp_t = __builtin_readcyclecounter();
-    uint32_t tp_tiles = 0;
-#endif
     while (i > 0 && j > 0) {
         const uint32_t r0 = ((i - 1) / TILE) * TILE, c0 = ((j - 1) / TILE) * TILE;
         const uint32_t rows = i - r0, cols = j - c0;
@@ -1080,9 +1076,6 @@ k_align_trace(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__
             if (jb > 0 && jb <= m) dg = roh[jb - 1];
         }
         tr_wave_sync();
-#ifdef TR_PROF
-        { const unsigned long long t = __builtin_readcyclecounter(); tp_load += t - tp_t; tp_t = t; ++tp_tiles; }
-#endif
         const uint32_t nact = (cols + TR_C - 1) / TR_C;
         const uint32_t nsteps = rows + nact - 1;
         int out_h = 0, out_e = ALN_NEG;
@@ -1149,9 +1142,6 @@ k_align_trace(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__
             if (s < nsteps) tstep(s);
         }
         tr_wave_sync();
-#ifdef TR_PROF
-        { const unsigned long long t = __builtin_readcyclecounter(); tp_comp += t - tp_t; tp_t = t; }
-#endif
         // the host aligner's traceback loop inside this tile (identical in every lane)
         while (i > r0 && j > c0) {
             const uint32_t cj = j - c0 - 1;
@@ -1190,17 +1180,11 @@ k_align_trace(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__
             }
         }
         tr_wave_sync();
-#ifdef TR_PROF
-        { const unsigned long long t = __builtin_readcyclecounter(); tp_walk += t - tp_t; tp_t = t; }
-#endif
     }
     ws.blanks(i + j, kmask, k, il);  // leading end gaps
     if (lane == 0) {
         out_score[pid] = en.x;
         out_count[pid] = ws.cnt;
-#ifdef TR_PROF
-        if (pslot == 0) printf("trace profile (cycles of the 100 MHz counter x tiles %u): load %llu, recompute %llu, walk %llu\n", tp_tiles, tp_load, tp_comp, tp_walk);
-#endif
     }
 }
 
@@ -1222,14 +1206,6 @@ k_seq_flags(const uint8_t* __restrict__ pool, const int64_t* __restrict__ offs, 
     __syncthreads();
     if (threadIdx.x == 0) flags[blockIdx.x] = uint8_t(s_any);
 }
-
-struct DevTmp {
-    void* p = nullptr;
-    ~DevTmp()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
 
 int reserve(ioc_ctx* c, DevBuf& b, size_t bytes)
 {
@@ -1261,61 +1237,73 @@ int reserve(ioc_ctx* c, DevBuf& b, size_t bytes)
 
 #include "ioc_align_v2.inc"
 
-// ---- host side of version 2 -------------------------------------------------------------------------------------------
-// the pairs order[0 .. cnt) (all of the query-profile kind, heaviest first) through k_fwd2 / k_fwd2_ends / k_trace2.
-// Returns IOC_OK with *fell_back = true when a bounded wait of the forward pass ran out (the caller then runs the same
-// pairs through version 1).
-// set while pairs the corridor could not vouch for are re-run: every tile of their grids
-thread_local bool g_no_corridor = false;
+// ---- host side ----------------------------------------------------------------------------------------------------------
+
+// events of a call's launches, three per slice: the forward pass, the traceback, the end (destroyed on every way out, the
+// ACHK returns included)
+struct EventSet {
+    std::vector<hipEvent_t> v;
+    ~EventSet()
+    {
+        for (auto& e : v)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// the device time of the first `used` events' slices, into ms_align_fwd / ms_align_trace
+void add_elapsed(ioc_ctx* c, const std::vector<hipEvent_t>& evs, size_t used)
+{
+    for (size_t x = 0; x + 2 < used && x + 2 < evs.size(); x += 3) {
+        float a = 0, b = 0;
+        if (hipEventElapsedTime(&a, evs[x], evs[x + 1]) == hipSuccess) c->tm.ms_align_fwd += a;
+        if (hipEventElapsedTime(&b, evs[x + 1], evs[x + 2]) == hipSuccess) c->tm.ms_align_trace += b;
+    }
+}
+
+int compute_units(const ioc_ctx* c)
+{
+    int n_cu = 256;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
+    return n_cu < 1 ? 256 : n_cu;
+}
+
+// half of what is free (the checkpoint arena's own reservation counted as free), or IOC_ALIGN_CK_BUDGET_MB
+int ck_budget(ioc_ctx* c, uint64_t* budget)
+{
+    size_t free_b = 0, total_b = 0;
+    ACHK(c, hipMemGetInfo(&free_b, &total_b));
+    *budget = uint64_t(free_b + c->a_ck.cap) / 2;
+    if (const char* e = getenv("IOC_ALIGN_CK_BUDGET_MB")) *budget = uint64_t(atoll(e)) << 20;
+    return IOC_OK;
+}
+
+// ---- version 2 (ioc_align_v2.inc) ---------------------------------------------------------------------------------------
 
 // the bound on |relative H| at a rebase of version 2's 16-bit window: what is live in a wave at one time differs by a few
 // thousand at most, two cells of it being joined through a common ancestor by paths no longer than the window
 constexpr int P16_GUARD = 28000;
 
-int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* order, uint32_t cnt, const uint32_t* d_order,
-                 const AlnParams& P, int32_t* d_score, uint32_t* d_count, bool* fell_back)
-{
-    *fell_back = false;
-    if (cnt == 0) return IOC_OK;
-    hipStream_t s = c->stream;
-    int r;
-    const auto t_plan0 = std::chrono::steady_clock::now();  // (IOC_TRACE: host time of the planning up to the first launch)
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-    if (n_cu < 1) n_cu = 256;
-    size_t free_b = 0, total_b = 0;
-    ACHK(c, hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = uint64_t(free_b + c->a_ck.cap) / 2;
-    if (const char* e = getenv("IOC_ALIGN_CK_BUDGET_MB")) budget = uint64_t(atoll(e)) << 20;
-    // the 16-bit window's guard (|relative score| at a rebase): a pair beyond it is flagged and re-run by version 1
-    int guard = P16_GUARD;
-    if (const char* e = getenv("IOC_ALIGN_V2_GUARD")) guard = std::max(1, std::min(P16_GUARD, atoi(e)));
-    const uint32_t np = uint32_t(dp.size());
-    const uint32_t ncouples = (cnt + 1u) / 2u;
-    const uint32_t probe_rows = 1024;
-    std::vector<int32_t> pend_cert(np, INT32_MIN);
-    uint64_t tiles_skipped = 0, tiles_all = 0;
-    // The corridor's half width as a fraction of the longer sequence (V2Couple; IOC_ALIGN_CORRIDOR=0: every tile; a pair whose
-    // result the corridor cannot vouch for is run again with g_no_corridor set).  0.2: a pair of one transcript scores 1.62 - 1.8
-    // per base at match 2 — it passes if 2 (1 - B / len) < 1.62 — and the tile grid of a 16.7 kb pair shrinks to about half.
-    double corridor_frac = g_no_corridor ? 0.0 : 0.2;
-    bool corridor_fixed = false;  // (IOC_ALIGN_CORRIDOR: one fraction for every couple, as in round 4)
-    if (const char* e = getenv("IOC_ALIGN_CORRIDOR")) {
-        corridor_frac = g_no_corridor ? 0.0 : std::max(0.0, std::min(1.0, atof(e)));
-        corridor_fixed = true;
-    }
-    // ROUND 5: the half width PER COUPLE, from the pairs' summed error rates.  A pair of one transcript scores
-    // rho = match - e x c per base, and passes the certificate iff B / length > 1 - rho / match.  Before anything has been aligned
-    // c comes from the error model behind setGapOpen's classes — a third each of substitutions (match - mismatch lost), insertions
-    // and deletions (gap open + the match) — plus 0.02 x length; once a gap-open class has 64 related pairs behind it (this
-    // context's earlier batches: ioc_ctx::aln_fit, fed in ioc_align_pairs) the line fitted to THEM, 4.5 standard deviations down.
-    // Config 3: mean width 0.157 x length (round 4: 0.2 for everybody — set by the least similar pair of the batch).  A wrong
-    // guess costs time (the probe widens, or the pair is refuted and run again), never a result.
-    const bool fit_ok = c->aln_fit_sig[0] == P.match && c->aln_fit_sig[1] == P.mismatch && c->aln_fit_sig[2] == P.gap_extend && !getenv("IOC_ALIGN_CORRIDOR_NO_FIT");
-    auto pair_frac = [&](const AlnPairDev& d) -> double {
-        if (corridor_fixed || !(P.match > 0)) return corridor_frac;
+// The corridor's half width as a fraction of the longer sequence (V2Couple; IOC_ALIGN_CORRIDOR=0: every tile; a pair whose
+// result the corridor cannot vouch for is run again by the every-tile route).  0.2: a pair of one transcript scores 1.62 - 1.8
+// per base at match 2 — it passes if 2 (1 - B / len) < 1.62 — and the tile grid of a 16.7 kb pair shrinks to about half.
+// ROUND 5: the half width PER COUPLE, from the pairs' summed error rates.  A pair of one transcript scores
+// rho = match - e x c per base, and passes the certificate iff B / length > 1 - rho / match.  Before anything has been aligned
+// c comes from the error model behind setGapOpen's classes — a third each of substitutions (match - mismatch lost), insertions
+// and deletions (gap open + the match) — plus 0.02 x length; once a gap-open class has 64 related pairs behind it (this
+// context's earlier batches: ioc_ctx::aln_fit, fed by learn_corridor) the line fitted to THEM, 4.5 standard deviations down.
+// Config 3: mean width 0.157 x length (round 4: 0.2 for everybody — set by the least similar pair of the batch).  A wrong
+// guess costs time (the probe widens, or the pair is refuted and run again), never a result.
+struct CorridorModel {
+    const ioc_ctx* c;
+    AlnParams P;
+    double frac;  // the fraction without a model (0: no corridor)
+    bool fixed;   // (IOC_ALIGN_CORRIDOR: one fraction for every couple, as in round 4)
+    bool fit_ok;  // ioc_ctx::aln_fit belongs to these scores
+    double pair_frac(const AlnPairDev& d) const
+    {
+        if (fixed || !(P.match > 0)) return frac;
         const double e = double(d.e_sum);
-        if (!(e > 0.0) || !(e < 1.0)) return corridor_frac;
+        if (!(e > 0.0) || !(e < 1.0)) return frac;
         const int go = std::max(2, std::min(5, d.gap_open));
         double rho = double(P.match) - e * (double(P.match - P.mismatch) / 3.0 + 2.0 / 3.0 * double(go + P.match)), margin = 0.02;
         const ioc_ctx::CorridorFit& f = c->aln_fit[go - 2];
@@ -1327,173 +1315,220 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
             margin = 0.003;
         }
         return std::max(0.03, std::min(0.45, 1.0 - rho / double(P.match) + margin));
-    };
-    // Bands per couple.  A full batch (config 3: 811 couples) is bound by throughput: 11 bands of 1536 rows (66.8 ms; 7 of 2560:
-    // 69.2; 17 of 1024: worse again).  A small one (a merge aligns a few hundred representatives) is bound by ONE couple's
-    // critical path, (bands + strips - 1) tiles of rows / (4 bands) + 63 steps: more, shorter bands shorten it as long as the
-    // waves the chip holds outnumber the tiles in flight.
-    uint32_t few_limit = 128;  // couples in a launch up to which its tiles wait for rows instead of tiles (IOC_ALIGN_V2_FEW; 0: never)
-    if (const char* e = getenv("IOC_ALIGN_V2_FEW")) few_limit = uint32_t(std::max(0, atoi(e)));
-    uint32_t want_bands = 12;
-    {
-        int occ0 = 3;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ0, reinterpret_cast<const void*>(k_fwd2), 64 * V2_WAVES, 0) != hipSuccess || occ0 < 1) occ0 = 3;
-        (void)hipGetLastError();
-        const uint32_t waves = uint32_t(occ0) * uint32_t(n_cu) * uint32_t(V2_WAVES);
-        want_bands = std::max(12u, std::min(uint32_t(V2_MAX_BANDS), (waves + ncouples - 1u) / std::max(1u, ncouples)));
-        // (with tiles that follow their left neighbours row by row — v2_wait_rows — a strip starts ~120 steps after the one on its
-        // left whatever the band's height: fewer, taller bands win again.  A second round of 31 couples of 16.7 kb: 33 bands of 512
-        // rows 16.6 ms, 17 of 1024 rows 14.9, 11 of 1536 rows 16.2; without: 16.9 / 19.4 / 23.5)
-        if (few_limit && ncouples <= few_limit) want_bands = std::min(want_bands, 17u);
     }
-    std::vector<V2Couple> cps(ncouples);
-    std::vector<V2PairCk> pck(np);
-    std::vector<V2PairEnd> pend(np);
-    std::vector<uint64_t> cwords(ncouples);  // arena words of a couple
-    auto up4 = [](uint64_t x) { return (x + 3u) & ~uint64_t(3); };
+};
+
+CorridorModel corridor_model(const ioc_ctx* c, const AlnParams& P, bool corridor)
+{
+    CorridorModel m{c, P, corridor ? 0.2 : 0.0, false, false};
+    if (const char* e = getenv("IOC_ALIGN_CORRIDOR")) {
+        m.frac = corridor ? std::max(0.0, std::min(1.0, atof(e))) : 0.0;
+        m.fixed = true;
+    }
+    m.fit_ok = c->aln_fit_sig[0] == P.match && c->aln_fit_sig[1] == P.mismatch && c->aln_fit_sig[2] == P.gap_extend && !getenv("IOC_ALIGN_CORRIDOR_NO_FIT");
+    return m;
+}
+
+// Bands per couple.  A full batch (config 3: 811 couples) is bound by throughput: 11 bands of 1536 rows (66.8 ms; 7 of 2560:
+// 69.2; 17 of 1024: worse again).  A small one (a merge aligns a few hundred representatives) is bound by ONE couple's
+// critical path, (bands + strips - 1) tiles of rows / (4 bands) + 63 steps: more, shorter bands shorten it as long as the
+// waves the chip holds outnumber the tiles in flight.
+uint32_t band_target(uint32_t ncouples, uint32_t few_limit, int occ, int n_cu)
+{
+    const uint32_t waves = uint32_t(occ) * uint32_t(n_cu) * uint32_t(V2_WAVES);
+    uint32_t want = std::max(12u, std::min(uint32_t(V2_MAX_BANDS), (waves + ncouples - 1u) / std::max(1u, ncouples)));
+    // (with tiles that follow their left neighbours row by row — v2_wait_rows — a strip starts ~120 steps after the one on its
+    // left whatever the band's height: fewer, taller bands win again.  A second round of 31 couples of 16.7 kb: 33 bands of 512
+    // rows 16.6 ms, 17 of 1024 rows 14.9, 11 of 1536 rows 16.2; without: 16.9 / 19.4 / 23.5)
+    if (few_limit && ncouples <= few_limit) want = std::min(want, 17u);
+    return want;
+}
+
+// what align_v2_run plans on the host before its first launch
+struct V2Plan {
+    uint32_t cnt = 0, np = 0, ncouples = 0;
+    std::vector<V2Couple> cps;
+    std::vector<V2PairCk> pck;
+    std::vector<V2PairEnd> pend;
+    std::vector<uint64_t> cwords;  // arena words of a couple
     uint32_t lrow_total = 0, best_total = 0, max_strips = 1;
-    uint64_t prof_total = 0;
-    for (uint32_t k2 = 0; k2 < ncouples; ++k2) {
-        V2Couple& cp = cps[k2];
+    uint64_t tiles_skipped = 0, tiles_all = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> slices;  // [first couple, count)
+    uint64_t arena_words = 0, prof_total = 0;
+    std::vector<std::vector<V2Item>> items;  // per slice
+    std::vector<uint32_t> n_probe;           // (the probe launch's tiles come first in a slice's list)
+    uint32_t max_items = 0, max_flags = 0, max_pairs = 0;
+};
+
+// bands of whole coarse rows: enough of them for the anti-diagonals of the tile grid to keep the chip busy, each long enough
+// (>= 1024 rows = 256 steps) for the 63 steps of pipeline fill to stay small (V2Couple::bstart)
+void plan_bands(V2Couple& cp, uint32_t ncoarse, uint32_t want_bands, bool corridor)
+{
+    // (a pair long enough for a corridor: shorter bands follow the diagonal more closely — config 3 with the corridor: 17 bands
+    // of 1024 rows 45.9 ms, 11 of 1536 47.6, 22 of 1024 / 512 46.1)
+    const uint32_t wb = (corridor && ncoarse >= 16u) ? std::max(want_bands, 17u) : want_bands;
+    const uint32_t reg = std::max<uint32_t>(want_bands > 16u ? 1u : 2u, (ncoarse + wb - 1) / wb);  // (coarse rows per band)
+    // (measured on config 3: short first and last bands — 1, 2, 4 coarse rows, then the regular height, then 4, 2, 1 — cost
+    // more in pipeline fill than they win: 69.9 against 69.2 ms at 7 regular bands)
+    std::vector<uint32_t> hts;
+    for (uint32_t left = ncoarse; left;) {
+        const uint32_t hgt = std::min(reg, left);
+        hts.push_back(hgt);
+        left -= hgt;
+    }
+    while (hts.size() > size_t(V2_MAX_BANDS)) {  // (very long pairs: merge from the middle)
+        const size_t mid = hts.size() / 2;
+        hts[mid - 1] += hts[mid];
+        hts.erase(hts.begin() + long(mid));
+    }
+    cp.nbands = uint32_t(hts.size());
+    cp.tpb = reg;
+    uint32_t acc = 0;
+    for (uint32_t b = 0; b <= uint32_t(V2_MAX_BANDS); ++b) {
+        cp.bstart[b] = uint16_t(std::min<uint32_t>(acc, 0xFFFFu));
+        if (b < cp.nbands) acc += hts[b];
+    }
+}
+
+// The corridor (V2Couple): tiles that meet |row - column| <= B, if that leaves out a fifth of the grid or more, and the probe.
+// Returns the tiles the corridor skips; cert[h]: the score pair h has to beat (V2PairEnd::cert).
+uint32_t plan_corridor(V2Couple& cp, const std::vector<AlnPairDev>& dp, const CorridorModel& cm, uint32_t nmax, uint32_t mmax, int32_t cert[2])
+{
+    const AlnParams& P = cm.P;
+    constexpr uint32_t probe_rows = 1024;
+    cp.corridor = 0;
+    for (uint32_t b = 0; b < uint32_t(V2_MAX_BANDS); ++b) {
+        cp.plo[b] = 0;
+        cp.phi[b] = uint16_t(std::min<uint32_t>(65535u, cp.nstrips - 1u));  // (V2Item::strip is 16 bits wide)
+    }
+    const uint32_t strip_cols = 64u * FW_C;
+    double frac = 0.0;
+    for (int h = 0; h < 2; ++h)
+        if (cp.pid[h] != 0xFFFFFFFFu) frac = std::max(frac, cm.pair_frac(dp[cp.pid[h]]));
+    if (cm.frac <= 0.0) frac = 0.0;
+    const uint32_t B = uint32_t(frac * double(std::max(nmax, mmax)));
+    cp.b0 = B;
+    int64_t beff = INT64_MAX;
+    uint32_t skipped = 0;
+    uint16_t lo[V2_MAX_BANDS], hi[V2_MAX_BANDS];
+    // (the bound behind the certificate: a column of an alignment scores `match` at most — no reward for mismatches or gaps)
+    bool fits = cm.frac > 0.0 && B >= strip_cols && cp.nstrips <= 65535u && cp.nbands <= uint32_t(V2_MAX_BANDS) && P.match > 0 && P.mismatch <= P.match &&
+                P.gap_extend >= 0;
+    for (int h = 0; fits && h < 2; ++h)
+        if (cp.pid[h] != 0xFFFFFFFFu) fits = dp[cp.pid[h]].gap_open >= 0;
+    for (uint32_t b = 0; fits && b < cp.nbands; ++b) {
+        const uint32_t r0 = uint32_t(cp.bstart[b]) * uint32_t(CK2), r1 = std::min(nmax, uint32_t(cp.bstart[b + 1u]) * uint32_t(CK2));
+        const uint32_t c_lo = r0 > B ? r0 - B : 0u, c_hi = std::min<uint64_t>(mmax, uint64_t(r1) + B);
+        if (c_hi <= c_lo) {  // (a band wholly below the last column's corridor: rows the longer query has alone)
+            fits = false;
+            break;
+        }
+        lo[b] = uint16_t(c_lo / strip_cols);
+        hi[b] = uint16_t((c_hi - 1u) / strip_cols);
+        skipped += lo[b] + (cp.nstrips - 1u - hi[b]);
+        if (lo[b] > 0) beff = std::min<int64_t>(beff, int64_t(r0) - int64_t(lo[b]) * strip_cols);
+        if ((uint64_t(hi[b]) + 1u) * strip_cols < mmax) beff = std::min<int64_t>(beff, int64_t(hi[b] + 1u) * strip_cols - int64_t(r1));
+    }
+    // the probe (V2Couple): the first band that ends at row 2048 or below, the strip its last diagonal cell is in; every tile
+    // above and to the left of it must be inside the corridor with nothing missing around it, both pairs must reach it
+    uint32_t pb = 0, ps = 0;
+    if (fits) {
+        while (pb + 1u < cp.nbands && uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2) < probe_rows) ++pb;  // (3072 rows: a probe launch of 4.2 ms; 2048: 2.3)
+        const uint32_t R = uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2);
+        ps = (R - 1u) / strip_cols;
+        fits = pb + 1u < cp.nbands && R >= probe_rows;
+        for (uint32_t b = 0; fits && b <= pb; ++b) fits = lo[b] == 0 && hi[b] >= ps;
+        for (int h = 0; fits && h < 2; ++h)
+            if (cp.pid[h] != 0xFFFFFFFFu) fits = dp[cp.pid[h]].n >= R && dp[cp.pid[h]].m > ps * strip_cols;
+    }
+    cp.probe_band = uint16_t(pb);
+    cp.probe_strip = uint16_t(ps);
+    if (fits && skipped * 5u >= cp.nbands * cp.nstrips && beff > 0 && beff < INT64_MAX) {
+        cp.corridor = 1;
+        for (uint32_t b = 0; b < cp.nbands; ++b) {
+            cp.plo[b] = lo[b];
+            cp.phi[b] = hi[b];
+        }
+    }
+    for (int h = 0; h < 2; ++h) {
+        cert[h] = INT32_MIN;
+        if (cp.pid[h] == 0xFFFFFFFFu || !cp.corridor) continue;
+        const AlnPairDev& d = dp[cp.pid[h]];
+        // (a path through a skipped cell has at most max(n, m) - Beff - 1 diagonal steps, each worth `match` at most)
+        cert[h] = int32_t(std::min<int64_t>(INT32_MAX, int64_t(P.match) * std::max<int64_t>(0, int64_t(std::max(d.n, d.m)) - beff - 1)));
+    }
+    return cp.corridor ? skipped : 0u;
+}
+
+// the couple's checkpoints (V2Couple: rdat, rbase, cdat, cbase from the couple's start; slice_couples places them) in arena words
+uint64_t couple_words(V2Couple& cp, uint32_t nmax, uint32_t mmax)
+{
+    auto up4 = [](uint64_t x) { return (x + 3u) & ~uint64_t(3); };
+    cp.mpad = uint32_t((uint64_t(mmax) + 15u) & ~uint64_t(15));
+    cp.nq = (nmax + 3u) / 4u;
+    const uint64_t ncr = (nmax - 1u) / CK2, ncc = (mmax - 1u) / CK2;
+    uint64_t w = 0;
+    cp.rdat = w;
+    w += up4(ncr * 2u * cp.mpad);
+    cp.rbase = w;
+    w += up4(ncr * (cp.mpad / 16u) * 2u);
+    cp.cdat = w;
+    w += up4(ncc * uint64_t(cp.nq) * 8u);
+    cp.cbase = w;
+    w += up4(ncc * uint64_t(cp.nq) * 2u);
+    return w;
+}
+
+// the couples (pairs order[2 k2], order[2 k2 + 1]): tile grid, bands, corridor, probe, checkpoint words, and every pair's entries of
+// the last-row and last-column bests
+void plan_couples(V2Plan& pl, const std::vector<AlnPairDev>& dp, const uint32_t* order, const CorridorModel& cm, uint32_t want_bands)
+{
+    pl.cps.resize(pl.ncouples);
+    pl.pck.resize(pl.np);
+    pl.pend.resize(pl.np);
+    pl.cwords.resize(pl.ncouples);
+    for (uint32_t k2 = 0; k2 < pl.ncouples; ++k2) {
+        V2Couple& cp = pl.cps[k2];
         cp.pid[0] = order[2u * k2];
-        cp.pid[1] = 2u * k2 + 1u < cnt ? order[2u * k2 + 1u] : 0xFFFFFFFFu;
+        cp.pid[1] = 2u * k2 + 1u < pl.cnt ? order[2u * k2 + 1u] : 0xFFFFFFFFu;
         uint32_t nmax = 0, mmax = 0;
         for (int h = 0; h < 2; ++h)
             if (cp.pid[h] != 0xFFFFFFFFu) {
                 nmax = std::max(nmax, dp[cp.pid[h]].n);
                 mmax = std::max(mmax, dp[cp.pid[h]].m);
             }
-        const uint32_t ncoarse = (nmax + CK2 - 1) / CK2;
         cp.nstrips = (mmax + 64u * FW_C - 1) / (64u * FW_C);
-        // bands of whole coarse rows: enough of them for the anti-diagonals of the tile grid to keep the chip busy, each long
-        // enough (>= 1024 rows = 256 steps) for the 63 steps of pipeline fill to stay small (V2Couple::bstart)
-        {
-            // (a pair long enough for a corridor: shorter bands follow the diagonal more closely — config 3 with the corridor: 17 bands
-            // of 1024 rows 45.9 ms, 11 of 1536 47.6, 22 of 1024 / 512 46.1)
-            const uint32_t wb = (corridor_frac > 0.0 && ncoarse >= 16u) ? std::max(want_bands, 17u) : want_bands;
-            const uint32_t reg = std::max<uint32_t>(want_bands > 16u ? 1u : 2u, (ncoarse + wb - 1) / wb);  // (coarse rows per band)
-            // (measured on config 3: short first and last bands — 1, 2, 4 coarse rows, then the regular height, then 4, 2, 1 — cost
-            // more in pipeline fill than they win: 69.9 against 69.2 ms at 7 regular bands)
-            std::vector<uint32_t> hts;
-            for (uint32_t left = ncoarse; left;) {
-                const uint32_t hgt = std::min(reg, left);
-                hts.push_back(hgt);
-                left -= hgt;
-            }
-            while (hts.size() > size_t(V2_MAX_BANDS)) {  // (very long pairs: merge from the middle)
-                const size_t mid = hts.size() / 2;
-                hts[mid - 1] += hts[mid];
-                hts.erase(hts.begin() + long(mid));
-            }
-            cp.nbands = uint32_t(hts.size());
-            cp.tpb = reg;
-            uint32_t acc = 0;
-            for (uint32_t b = 0; b <= uint32_t(V2_MAX_BANDS); ++b) {
-                cp.bstart[b] = uint16_t(std::min<uint32_t>(acc, 0xFFFFu));
-                if (b < cp.nbands) acc += hts[b];
-            }
-        }
-        {   // the corridor (V2Couple): tiles that meet |row - column| <= B, if that leaves out a fifth of the grid or more
-            cp.corridor = 0;
-            for (uint32_t b = 0; b < uint32_t(V2_MAX_BANDS); ++b) {
-                cp.plo[b] = 0;
-                cp.phi[b] = uint16_t(std::min<uint32_t>(65535u, cp.nstrips - 1u));  // (V2Item::strip is 16 bits wide)
-            }
-            const uint32_t strip_cols = 64u * FW_C;
-            double frac = 0.0;
-            for (int h = 0; h < 2; ++h)
-                if (cp.pid[h] != 0xFFFFFFFFu) frac = std::max(frac, pair_frac(dp[cp.pid[h]]));
-            if (corridor_frac <= 0.0) frac = 0.0;
-            const uint32_t B = uint32_t(frac * double(std::max(nmax, mmax)));
-            cp.b0 = B;
-            int64_t beff = INT64_MAX;
-            uint32_t skipped = 0;
-            uint16_t lo[V2_MAX_BANDS], hi[V2_MAX_BANDS];
-            // (the bound behind the certificate: a column of an alignment scores `match` at most — no reward for mismatches or gaps)
-            bool fits = corridor_frac > 0.0 && B >= strip_cols && cp.nstrips <= 65535u && cp.nbands <= uint32_t(V2_MAX_BANDS) && P.match > 0 && P.mismatch <= P.match &&
-                        P.gap_extend >= 0;
-            for (int h = 0; fits && h < 2; ++h)
-                if (cp.pid[h] != 0xFFFFFFFFu) fits = dp[cp.pid[h]].gap_open >= 0;
-            for (uint32_t b = 0; fits && b < cp.nbands; ++b) {
-                const uint32_t r0 = uint32_t(cp.bstart[b]) * uint32_t(CK2), r1 = std::min(nmax, uint32_t(cp.bstart[b + 1u]) * uint32_t(CK2));
-                const uint32_t c_lo = r0 > B ? r0 - B : 0u, c_hi = std::min<uint64_t>(mmax, uint64_t(r1) + B);
-                if (c_hi <= c_lo) {  // (a band wholly below the last column's corridor: rows the longer query has alone)
-                    fits = false;
-                    break;
-                }
-                lo[b] = uint16_t(c_lo / strip_cols);
-                hi[b] = uint16_t((c_hi - 1u) / strip_cols);
-                skipped += lo[b] + (cp.nstrips - 1u - hi[b]);
-                if (lo[b] > 0) beff = std::min<int64_t>(beff, int64_t(r0) - int64_t(lo[b]) * strip_cols);
-                if ((uint64_t(hi[b]) + 1u) * strip_cols < mmax) beff = std::min<int64_t>(beff, int64_t(hi[b] + 1u) * strip_cols - int64_t(r1));
-            }
-            // the probe (V2Couple): the first band that ends at row 2048 or below, the strip its last diagonal cell is in; every tile
-            // above and to the left of it must be inside the corridor with nothing missing around it, both pairs must reach it
-            uint32_t pb = 0, ps = 0;
-            if (fits) {
-                while (pb + 1u < cp.nbands && uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2) < probe_rows) ++pb;  // (3072 rows: a probe launch of 4.2 ms; 2048: 2.3)
-                const uint32_t R = uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2);
-                ps = (R - 1u) / strip_cols;
-                fits = pb + 1u < cp.nbands && R >= probe_rows;
-                for (uint32_t b = 0; fits && b <= pb; ++b) fits = lo[b] == 0 && hi[b] >= ps;
-                for (int h = 0; fits && h < 2; ++h)
-                    if (cp.pid[h] != 0xFFFFFFFFu) fits = dp[cp.pid[h]].n >= R && dp[cp.pid[h]].m > ps * strip_cols;
-            }
-            cp.probe_band = uint16_t(pb);
-            cp.probe_strip = uint16_t(ps);
-            if (fits && skipped * 5u >= cp.nbands * cp.nstrips && beff > 0 && beff < INT64_MAX) {
-                cp.corridor = 1;
-                for (uint32_t b = 0; b < cp.nbands; ++b) {
-                    cp.plo[b] = lo[b];
-                    cp.phi[b] = hi[b];
-                }
-                tiles_skipped += skipped;
-            }
-            tiles_all += uint64_t(cp.nbands) * cp.nstrips;
-            for (int h = 0; h < 2; ++h)
-                if (cp.pid[h] != 0xFFFFFFFFu) {
-                    const AlnPairDev& d = dp[cp.pid[h]];
-                    // (a path through a skipped cell has at most max(n, m) - Beff - 1 diagonal steps, each worth `match` at most)
-                    pend_cert[cp.pid[h]] = cp.corridor ? int32_t(std::min<int64_t>(INT32_MAX, int64_t(P.match) * std::max<int64_t>(0, int64_t(std::max(d.n, d.m)) - beff - 1))) : INT32_MIN;
-                }
-        }
-        cp.mpad = uint32_t((uint64_t(mmax) + 15u) & ~uint64_t(15));
-        cp.nq = (nmax + 3u) / 4u;
-        const uint64_t ncr = (nmax - 1u) / CK2, ncc = (mmax - 1u) / CK2;
-        uint64_t w = 0;
-        cp.rdat = w;
-        w += up4(ncr * 2u * cp.mpad);
-        cp.rbase = w;
-        w += up4(ncr * (cp.mpad / 16u) * 2u);
-        cp.cdat = w;
-        w += up4(ncc * uint64_t(cp.nq) * 8u);
-        cp.cbase = w;
-        w += up4(ncc * uint64_t(cp.nq) * 2u);
-        cwords[k2] = w;
-        cp.prof = 0;  // (uint4 entries; placed per slice below: the profiles of a slice's couples count against the budget with its checkpoints)
-        max_strips = std::max(max_strips, cp.nstrips);
+        plan_bands(cp, (nmax + CK2 - 1) / CK2, want_bands, cm.frac > 0.0);
+        int32_t cert[2];
+        pl.tiles_skipped += plan_corridor(cp, dp, cm, nmax, mmax, cert);
+        pl.tiles_all += uint64_t(cp.nbands) * cp.nstrips;
+        pl.cwords[k2] = couple_words(cp, nmax, mmax);
+        cp.prof = 0;  // (uint4 entries; placed per slice: the profiles of a slice's couples count against the budget with its checkpoints)
+        pl.max_strips = std::max(pl.max_strips, cp.nstrips);
         for (int h = 0; h < 2; ++h) {
-            cp.lrow0[h] = lrow_total;
-            cp.best0[h] = best_total;
+            cp.lrow0[h] = pl.lrow_total;
+            cp.best0[h] = pl.best_total;
             if (cp.pid[h] == 0xFFFFFFFFu) continue;
             const AlnPairDev& d = dp[cp.pid[h]];
             const uint32_t nstr = (d.m + 64u * FW_C - 1) / (64u * FW_C);
-            pend[cp.pid[h]] = V2PairEnd{lrow_total, best_total, cp.nbands, k2, pend_cert[cp.pid[h]]};
-            lrow_total += nstr * 64u;
-            best_total += cp.nbands;
+            pl.pend[cp.pid[h]] = V2PairEnd{pl.lrow_total, pl.best_total, cp.nbands, k2, cert[h]};
+            pl.lrow_total += nstr * 64u;
+            pl.best_total += cp.nbands;
         }
     }
-    // slices of couples whose checkpoints fit the budget together
-    std::vector<std::pair<uint32_t, uint32_t>> slices;
-    uint64_t arena_words = 0;
-    for (uint32_t first = 0; first < ncouples;) {
+}
+
+// slices of couples whose checkpoints and query profiles fit the budget together
+void slice_couples(V2Plan& pl, uint64_t budget)
+{
+    for (uint32_t first = 0; first < pl.ncouples;) {
         uint64_t used = 0;
         uint32_t k2 = first;
         uint64_t prof_used = 0;  // uint4 entries of query profiles in this slice (they used to be made for every couple of the call at once)
-        while (k2 < ncouples) {
-            const uint64_t prof_k = uint64_t(cps[k2].nstrips) * 2u * 5u * 64u;
-            if (k2 != first && (used + cwords[k2]) * 4ull + (prof_used + prof_k) * sizeof(uint4) > budget) break;
-            V2Couple& cp = cps[k2];
+        while (k2 < pl.ncouples) {
+            const uint64_t prof_k = uint64_t(pl.cps[k2].nstrips) * 2u * 5u * 64u;
+            if (k2 != first && (used + pl.cwords[k2]) * 4ull + (prof_used + prof_k) * sizeof(uint4) > budget) break;
+            V2Couple& cp = pl.cps[k2];
             cp.prof = prof_used;
             prof_used += prof_k;
             cp.rdat += used;
@@ -1501,35 +1536,30 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
             cp.cdat += used;
             cp.cbase += used;
             for (int h = 0; h < 2; ++h)
-                if (cp.pid[h] != 0xFFFFFFFFu) pck[cp.pid[h]] = V2PairCk{cp.rdat, cp.rbase, cp.cdat, cp.cbase, cp.mpad, cp.nq, uint32_t(h), k2};
-            used += cwords[k2];
+                if (cp.pid[h] != 0xFFFFFFFFu) pl.pck[cp.pid[h]] = V2PairCk{cp.rdat, cp.rbase, cp.cdat, cp.cbase, cp.mpad, cp.nq, uint32_t(h), k2};
+            used += pl.cwords[k2];
             ++k2;
         }
-        arena_words = std::max(arena_words, used);
-        prof_total = std::max(prof_total, prof_used);
-        slices.emplace_back(first, k2 - first);
+        pl.arena_words = std::max(pl.arena_words, used);
+        pl.prof_total = std::max(pl.prof_total, prof_used);
+        pl.slices.emplace_back(first, k2 - first);
         first = k2;
     }
-    const auto t_res0 = std::chrono::steady_clock::now();
-    if ((r = reserve(c, c->a_ck, size_t(arena_words) * 4)) != IOC_OK) return r;
-    c->tm.align_arena_bytes = int64_t(arena_words) * 4;
-    c->tm.align_slices = int32_t(slices.size());
-    c->tm.align_version = 2;
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner v2: %u couples, checkpoint arena %.1f MB (%zu slice(s)) reserved in %.3f ms; corridor: %llu of %llu tiles skipped\n", ncouples,
-                double(arena_words) * 4e-6, slices.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_res0).count(),
-                (unsigned long long)tiles_skipped, (unsigned long long)tiles_all);
-    // flags and items per slice; the static tables once
-    uint32_t max_items = 0, max_flags = 0, max_pairs = 0;
-    std::vector<std::vector<V2Item>> items(slices.size());
-    std::vector<uint32_t> n_probe(slices.size(), 0);  // (the probe launch's tiles come first in a slice's list)
-    for (size_t si = 0; si < slices.size(); ++si) {
+}
+
+// every slice's list of tiles and flags (V2Couple::flag0)
+void tile_lists(V2Plan& pl)
+{
+    pl.items.resize(pl.slices.size());
+    pl.n_probe.assign(pl.slices.size(), 0);
+    for (size_t si = 0; si < pl.slices.size(); ++si) {
+        const uint32_t k_lo = pl.slices[si].first, k_hi = pl.slices[si].first + pl.slices[si].second;
         uint32_t nf = 0;
-        auto& it = items[si];
+        auto& it = pl.items[si];
         uint32_t maxdiag = 0;
         size_t total_items = 0;
-        for (uint32_t k2 = slices[si].first; k2 < slices[si].first + slices[si].second; ++k2) {
-            V2Couple& cp = cps[k2];
+        for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
+            V2Couple& cp = pl.cps[k2];
             cp.flag0 = nf;
             nf += cp.nbands * cp.nstrips;
             total_items += size_t(cp.nbands) * cp.nstrips;
@@ -1537,12 +1567,12 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
         }
         // anti-diagonal by anti-diagonal, couples side by side: every tile comes after the tile above it and the tile to its left
         // (generated in that order: sorting 150 000 items cost 4 ms of host time per call)
-        it.reserve(total_items + 64u * slices[si].second);
+        it.reserve(total_items + 64u * pl.slices[si].second);
         // first the probe's tiles (couples with a corridor: the top left corner of the grid, V2Couple), in the same order
         for (uint32_t dg = 0; dg <= maxdiag; ++dg) {
             bool any = false;
-            for (uint32_t k2 = slices[si].first; k2 < slices[si].first + slices[si].second; ++k2) {
-                const V2Couple& cp = cps[k2];
+            for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
+                const V2Couple& cp = pl.cps[k2];
                 if (!cp.corridor || dg > uint32_t(cp.probe_band) + cp.probe_strip) continue;
                 any = true;
                 const uint32_t b_lo = dg >= uint32_t(cp.probe_strip) + 1u ? dg - cp.probe_strip : 0u, b_hi = std::min<uint32_t>(dg, cp.probe_band);
@@ -1550,273 +1580,329 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
             }
             if (!any && dg > 64u) break;
         }
-        n_probe[si] = uint32_t(it.size());
+        pl.n_probe[si] = uint32_t(it.size());
         for (uint32_t dg = 0; dg <= maxdiag; ++dg)
-            for (uint32_t k2 = slices[si].first; k2 < slices[si].first + slices[si].second; ++k2) {
-                const V2Couple& cp = cps[k2];
+            for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
+                const V2Couple& cp = pl.cps[k2];
                 if (dg > cp.nbands + cp.nstrips - 2u) continue;
                 const uint32_t b_lo = dg >= cp.nstrips ? dg - cp.nstrips + 1u : 0u, b_hi = std::min(dg, cp.nbands - 1u);
                 for (uint32_t b = b_lo; b <= b_hi; ++b) it.push_back(V2Item{k2, uint16_t(b), uint16_t(dg - b)});
             }
-        max_items = std::max<uint32_t>(max_items, uint32_t(it.size()));
-        max_flags = std::max(max_flags, nf);
-        max_pairs = std::max(max_pairs, std::min(cnt, 2u * (slices[si].first + slices[si].second)) - 2u * slices[si].first);
+        pl.max_items = std::max<uint32_t>(pl.max_items, uint32_t(it.size()));
+        pl.max_flags = std::max(pl.max_flags, nf);
+        pl.max_pairs = std::max(pl.max_pairs, std::min(pl.cnt, 2u * k_hi) - 2u * k_lo);
     }
-    const size_t tab_bytes = size_t(ncouples) * sizeof(V2Couple) + size_t(np) * (sizeof(V2PairCk) + sizeof(V2PairEnd)) + size_t(max_items) * sizeof(V2Item) + 256;
+}
+
+// the launch settings of align_v2_run (environment switches and the chip)
+struct V2Opts {
+    int n_cu, occ, guard;
+    uint32_t few_limit;                  // couples in a launch up to which its tiles wait for rows instead of tiles (IOC_ALIGN_V2_FEW; 0: never)
+    uint32_t deadline;                   // traceback blocks before a walk is parked for the second launch (IOC_TRACE2_DEADLINE; 0: one launch)
+    unsigned long long deadline_cycles;  // ... or cycles of the first launch (IOC_TRACE2_CYCLES; 0: the block count alone)
+    uint32_t help_wgs;                   // workgroups of the helper launches
+    bool side_help;                      // the wrong candidates' walks on the side stream, beside the first launch (IOC_TRACE2_EARLY)
+};
+
+// where the plan lives on the device, in the context's buffers
+struct V2Dev {
+    V2Couple* cps;
+    V2PairCk* pck;
+    V2PairEnd* pend;
+    V2Item* items;
+    int2 *lrow, *best;
+    uint32_t* ctl;  // [queue][err][pad ...][flags][rows of a tile's right edge that are out (v2_wait_rows)][ovf per pair][computed cells, 8-byte aligned]
+    size_t ctl_words;
+    V2Scratch *scratch, *hscratch;
+    uint32_t* resume;  // per pair: V2_RESUME_WORDS of parked state and records
+    uint32_t* park;    // [count][pair slots of the slice]: parked by the first traceback launch
+    uint32_t* early;   // ... and sent to the helper launch by k_fwd2_ends (wrong candidates, by their score)
+    uint32_t* gate;    // workgroups of that launch that have started
+    size_t resume_words;
+};
+
+// the plan's tables on the device and every buffer of the launches (after the checkpoint arena)
+int v2_tables(ioc_ctx* c, const V2Plan& pl, uint32_t help_wgs, V2Dev& t)
+{
+    hipStream_t s = c->stream;
+    int r;
+    const uint32_t ncouples = pl.ncouples, np = pl.np;
+    const size_t tab_bytes = size_t(ncouples) * sizeof(V2Couple) + size_t(np) * (sizeof(V2PairCk) + sizeof(V2PairEnd)) + size_t(pl.max_items) * sizeof(V2Item) + 256;
     if ((r = reserve(c, c->a_cko, tab_bytes)) != IOC_OK) return r;
     uint8_t* tb = static_cast<uint8_t*>(c->a_cko.p);
-    V2Couple* d_cps = reinterpret_cast<V2Couple*>(tb);
-    V2PairCk* d_pck = reinterpret_cast<V2PairCk*>(tb + size_t(ncouples) * sizeof(V2Couple));
-    V2PairEnd* d_pend = reinterpret_cast<V2PairEnd*>(reinterpret_cast<uint8_t*>(d_pck) + size_t(np) * sizeof(V2PairCk));
-    V2Item* d_items = reinterpret_cast<V2Item*>(reinterpret_cast<uint8_t*>(d_pend) + size_t(np) * sizeof(V2PairEnd));
-    ACHK(c, hipMemcpyAsync(d_cps, cps.data(), size_t(ncouples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));
-    ACHK(c, hipMemcpyAsync(d_pck, pck.data(), size_t(np) * sizeof(V2PairCk), hipMemcpyHostToDevice, s));
-    ACHK(c, hipMemcpyAsync(d_pend, pend.data(), size_t(np) * sizeof(V2PairEnd), hipMemcpyHostToDevice, s));
-    // the query profiles of every (couple, strip), once per batch
-    if ((r = reserve(c, c->a_prof, size_t(prof_total) * sizeof(uint4) + 256)) != IOC_OK) return r;
-    // (the profiles themselves are made slice by slice, in front of the slice's forward pass)
+    t.cps = reinterpret_cast<V2Couple*>(tb);
+    t.pck = reinterpret_cast<V2PairCk*>(tb + size_t(ncouples) * sizeof(V2Couple));
+    t.pend = reinterpret_cast<V2PairEnd*>(reinterpret_cast<uint8_t*>(t.pck) + size_t(np) * sizeof(V2PairCk));
+    t.items = reinterpret_cast<V2Item*>(reinterpret_cast<uint8_t*>(t.pend) + size_t(np) * sizeof(V2PairEnd));
+    ACHK(c, hipMemcpyAsync(t.cps, pl.cps.data(), size_t(ncouples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));
+    ACHK(c, hipMemcpyAsync(t.pck, pl.pck.data(), size_t(np) * sizeof(V2PairCk), hipMemcpyHostToDevice, s));
+    ACHK(c, hipMemcpyAsync(t.pend, pl.pend.data(), size_t(np) * sizeof(V2PairEnd), hipMemcpyHostToDevice, s));
+    // the query profiles of every (couple, strip) of a slice (made slice by slice, in front of the slice's forward pass)
+    if ((r = reserve(c, c->a_prof, size_t(pl.prof_total) * sizeof(uint4) + 256)) != IOC_OK) return r;
     if ((r = reserve(c, c->a_ends2, size_t(np) * sizeof(int4))) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_lrow, (size_t(lrow_total) + best_total + 16) * sizeof(int2))) != IOC_OK) return r;
-    int2* d_lrow = static_cast<int2*>(c->a_lrow.p);
-    int2* d_best = d_lrow + lrow_total;
-    // [queue][err][pad ...][flags][rows of a tile's right edge that are out (v2_wait_rows)][ovf per pair][computed cells, 8-byte aligned]
-    const size_t ctl_words = ((16 + 2 * size_t(max_flags) + np + 1) & ~size_t(1)) + 2;
-    if ((r = reserve(c, c->a_xflags, ctl_words * 4)) != IOC_OK) return r;
-    uint32_t* d_ctl = static_cast<uint32_t*>(c->a_xflags.p);
+    if ((r = reserve(c, c->a_lrow, (size_t(pl.lrow_total) + pl.best_total + 16) * sizeof(int2))) != IOC_OK) return r;
+    t.lrow = static_cast<int2*>(c->a_lrow.p);
+    t.best = t.lrow + pl.lrow_total;
+    t.ctl_words = ((16 + 2 * size_t(pl.max_flags) + np + 1) & ~size_t(1)) + 2;
+    if ((r = reserve(c, c->a_xflags, t.ctl_words * 4)) != IOC_OK) return r;
+    t.ctl = static_cast<uint32_t*>(c->a_xflags.p);
+    // per pair: its own scratch and 16 words of parked state and records; (the helper buffers belong to the second launch's
+    // WORKGROUPS — one per compute unit — not to the pairs: 0.66 MB each)
+    const size_t n_scratch = size_t(pl.max_pairs) + size_t(help_wgs) * V2_NHELP * V2_HBUF;
+    t.resume_words = size_t(np) * V2_RESUME_WORDS + 2u * (size_t(pl.max_pairs) + 1u) + 4u;  // (parked state, the two lists of walks for the helper launches)
+    if ((r = reserve(c, c->a_bnd, n_scratch * sizeof(V2Scratch) + t.resume_words * 4)) != IOC_OK) return r;
+    t.scratch = static_cast<V2Scratch*>(c->a_bnd.p);
+    t.hscratch = t.scratch + pl.max_pairs;
+    t.resume = reinterpret_cast<uint32_t*>(t.scratch + n_scratch);
+    t.park = t.resume + size_t(np) * V2_RESUME_WORDS;
+    t.early = t.park + size_t(pl.max_pairs) + 1u;
+    t.gate = t.early + size_t(pl.max_pairs) + 1u;
+    return IOC_OK;
+}
+
+// Workgroups per compute unit of a slice's main launch.  A tile waits for the tile above and the tile to its left, so a couple's
+// grid offers only its current anti-diagonal — with the corridor 2 - 3 tiles of a 16.7 kb pair — and a tile takes 0.5 - 0.9 ms:
+// the pass is bound by tiles in flight as much as by throughput (config 3: 37 ms for a critical path of ~18).  Waves beyond the
+// tiles that can run sit on a tile whose neighbours are still being computed, and they sit unevenly: a SIMD with three busy
+// waves next to one with a single busy wave and two waiting.  So: as many workgroups per CU as the list's tiles per
+// anti-diagonal keep busy, the same number on every CU (config 3 with the corridor: 2 per CU 37.2 ms, 3 per CU 39.8,
+// 2.25 per CU 40.6; every tile: 3 per CU 67.6, 2 per CU 72.7; a quarter of the batch: 1 per CU 22.7, 3 per CU 25.1).
+uint32_t v2_per_cu(const V2Plan& pl, size_t si, const V2Opts& o, bool few_couples)
+{
+    if (few_couples) return uint32_t(o.occ);
+    uint64_t tiles = 0;
+    uint32_t diags = 1;
+    for (uint32_t k2 = pl.slices[si].first; k2 < pl.slices[si].first + pl.slices[si].second; ++k2) {
+        const V2Couple& cp = pl.cps[k2];
+        for (uint32_t b = 0; b < cp.nbands; ++b) tiles += uint32_t(cp.phi[b]) - uint32_t(cp.plo[b]) + 1u;
+        diags = std::max(diags, cp.nbands + cp.nstrips - 1u);
+    }
+    const double x = double(tiles) / double(diags) / double(uint32_t(o.n_cu) * uint32_t(V2_WAVES));
+    return x < 1.0 ? 1u : x < 2.75 ? std::min(2u, uint32_t(o.occ)) : uint32_t(o.occ);
+}
+
+// One slice's launches: profiles, probe, forward pass, ends, traceback (events ev[0 .. 3) around them), then its error word
+// (*xe: a bounded wait ran out) and computed cells.
+int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Opts& o, const AlnParams& P, const uint32_t* d_order,
+             int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, uint32_t* xe)
+{
+    hipStream_t s = c->stream;
+    const uint32_t k_first = pl.slices[si].first, n_couples = pl.slices[si].second;
+    const uint32_t first_pair = 2u * k_first, n_pairs = std::min(pl.cnt, 2u * (k_first + n_couples)) - first_pair;
+    const uint32_t n_items = uint32_t(pl.items[si].size()), n_probe = pl.n_probe[si];
+    const AlnPairDev* d_pairs = static_cast<const AlnPairDev*>(c->a_pairs.p);
+    const uint8_t* d_pool = static_cast<const uint8_t*>(c->a_pool.p);
+    uint32_t* d_ctl = t.ctl;
+    // (few couples: bound by ONE grid's critical path — tiles follow their left neighbours row by row, v2_wait_rows; a tile
+    // publishes its progress every block of 64 rows)
+    const bool few_couples = n_couples <= o.few_limit;
+    const uint32_t prog_every = few_couples ? 1u : 0u;
+    ACHK(c, hipMemcpyAsync(t.items, pl.items[si].data(), size_t(n_items) * sizeof(V2Item), hipMemcpyHostToDevice, s));
+    ACHK(c, hipMemcpyAsync(t.cps + k_first, pl.cps.data() + k_first, size_t(n_couples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));  // (flag0)
+    hipLaunchKernelGGL(k_fwd2_prof, dim3(n_couples, pl.max_strips), dim3(128), 0, s, d_pairs, t.cps + k_first, d_pool, P, static_cast<uint4*>(c->a_prof.p));
+    ACHK(c, hipGetLastError());
+    ACHK(c, hipMemsetAsync(d_ctl, 0, t.ctl_words * 4, s));
+    ACHK(c, hipMemsetAsync(t.resume, 0, t.resume_words * 4, s));  // (parked state and the two lists of walks; k_fwd2_ends writes into them)
+    if (pl.tiles_skipped)  // (the bests of the last row and the last column that a skipped tile does not write: far below any score)
+        ACHK(c, hipMemsetAsync(t.lrow, 0x80, (size_t(pl.lrow_total) + pl.best_total) * sizeof(int2), s));
+    if (getenv("IOC_ALIGN_V2_FAKE_TIMEOUT")) {  // (tests: as if a bounded wait had run out — every later wait gives up at once,
+        const uint32_t one = 1;                 // tiles run on whatever is there, the host must fall back to version 1)
+        ACHK(c, hipMemcpyAsync(d_ctl + 1, &one, 4, hipMemcpyHostToDevice, s));
+    }
+    ACHK(c, hipEventRecord(ev[0], s));
+    // persistent waves: as many workgroups as the chip holds, but no more waves than tiles
+    auto fwd = [&](decltype(&k_fwd2) kernel, uint32_t n_wg, const V2Item* items, uint32_t n) {
+        hipLaunchKernelGGL(kernel, dim3(n_wg), dim3(64 * V2_WAVES), 0, s, d_pairs, t.cps, items, n, d_ctl, d_ctl + 16, d_ctl + 1, d_pool, P,
+                           static_cast<uint32_t*>(c->a_ck.p), t.lrow, t.best, d_ctl + 16 + 2 * pl.max_flags, o.guard, static_cast<const uint4*>(c->a_prof.p),
+                           reinterpret_cast<unsigned long long*>(d_ctl + t.ctl_words - 2), few_couples ? d_ctl + 16 + pl.max_flags : static_cast<uint32_t*>(nullptr),
+                           prog_every);
+    };
+    if (n_probe) {  // the probe launch and its verdicts (V2Couple): all on the device, nothing comes back to the host
+        fwd(k_fwd2, std::max(1u, std::min(uint32_t(o.occ) * uint32_t(o.n_cu), (n_probe + V2_WAVES - 1) / V2_WAVES)), t.items, n_probe);
+        ACHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_fwd2_probe, dim3(n_couples), dim3(64), 0, s, d_pairs, t.cps + k_first, t.pend, static_cast<const uint32_t*>(c->a_ck.p), P);
+        ACHK(c, hipGetLastError());
+        ACHK(c, hipMemsetAsync(d_ctl, 0, 4, s));  // (the queue's counter; the flags of the probe's tiles stay)
+    }
+    const uint32_t n_main = n_items - n_probe, per_cu = v2_per_cu(pl, si, o, few_couples);
+    const uint32_t n_wg = std::max(1u, std::min(per_cu * uint32_t(o.n_cu), (n_main + V2_WAVES - 1) / V2_WAVES));
+    // (two workgroups per CU: the build of the kernel that may use the registers of the third)
+    fwd((per_cu <= 2 && !getenv("IOC_ALIGN_V2_NO_W2")) ? k_fwd2_w2 : k_fwd2, n_wg, t.items + n_probe, n_main);
+    ACHK(c, hipGetLastError());
+    const uint32_t n_help = std::min<uint32_t>(n_pairs, o.help_wgs);
+    hipLaunchKernelGGL(k_fwd2_ends, dim3(n_pairs), dim3(64), 0, s, d_pairs, t.cps, d_order + first_pair, n_pairs, t.pend, t.lrow, t.best,
+                       d_ctl + 16 + 2 * pl.max_flags, static_cast<int4*>(c->a_ends2.p), t.resume, t.early, o.side_help ? int(P.match) : 0, n_help);
+    ACHK(c, hipGetLastError());
+    ACHK(c, hipEventRecord(ev[1], s));
     // the traceback in two launches: walks that need more than `deadline` blocks go on in the second one, with helper waves
-    // (IOC_TRACE2_DEADLINE=0: one launch).  Per pair: its own scratch and 16 words of parked state and records.
-    uint32_t deadline = 4;  // (blocks of slack on top of what a pair of one transcript needs to be decided: 2 per 512 windows of its threshold)
-    if (const char* e = getenv("IOC_TRACE2_DEADLINE")) deadline = uint32_t(std::max(0, atoi(e)));
-    // ... or that are still undecided after this many cycles of the first launch (s_memtime; 0: the block count alone)
-    unsigned long long deadline_cycles = 0;
-    if (const char* e = getenv("IOC_TRACE2_CYCLES")) deadline_cycles = (unsigned long long)std::max(0.0, atof(e));
-    // (the helper buffers belong to the second launch's WORKGROUPS — one per compute unit — not to the pairs: 0.66 MB each)
-    const uint32_t help_wgs = deadline ? std::min<uint32_t>(max_pairs, uint32_t(n_cu)) : 0u;
-    const size_t n_scratch = size_t(max_pairs) + size_t(help_wgs) * V2_NHELP * V2_HBUF;
-    const size_t resume_words = size_t(np) * V2_RESUME_WORDS + 2u * (size_t(max_pairs) + 1u) + 4u;  // (parked state, the two lists of walks for the helper launches)
-    if ((r = reserve(c, c->a_bnd, n_scratch * sizeof(V2Scratch) + resume_words * 4)) != IOC_OK) return r;
-    V2Scratch* d_scratch = static_cast<V2Scratch*>(c->a_bnd.p);
-    V2Scratch* d_hscratch = d_scratch + max_pairs;
-    uint32_t* d_resume = reinterpret_cast<uint32_t*>(d_scratch + n_scratch);
-    uint32_t* d_park = d_resume + size_t(np) * V2_RESUME_WORDS;  // [count][pair slots of the slice]: parked by the first traceback launch
-    uint32_t* d_early = d_park + size_t(max_pairs) + 1u;         // ... and sent to the helper launch by k_fwd2_ends (wrong candidates, by their score)
-    uint32_t* d_gate = d_early + size_t(max_pairs) + 1u;         // workgroups of that launch that have started
-    // The helper launch for those runs on a side stream BESIDE the first traceback launch (IOC_TRACE2_EARLY=0: everything goes
-    // through the first launch, as before): the walks of the wrong candidates are the longest of the batch, and the first launch —
-    // one pair's latency long, with the chip half empty — no longer waits for them to reach their deadline first.
-    const bool route = deadline && !(getenv("IOC_TRACE2_EARLY") && atoi(getenv("IOC_TRACE2_EARLY")) == 0);
-    if (route && !c->side_stream) {
+    auto help = [&](hipStream_t hs, uint32_t* list, uint32_t which, uint32_t* gate) {
+        hipLaunchKernelGGL(k_trace2_help, dim3(n_help), dim3(64 * V2_HWAVES), 0, hs, d_pairs, d_order + first_pair, d_pool, P,
+                           static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.hscratch, t.resume,
+                           list, d_score, d_count, n_pairs, which, gate);
+    };
+    if (o.side_help) {  // (issued before the first launch: its workgroups — a walker and ten helpers each — take their places first)
+        ACHK(c, hipEventRecord(c->ev_side[0], s));
+        ACHK(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
+        help(c->side_stream, t.early, 2u, t.gate);
+        ACHK(c, hipGetLastError());
+        ACHK(c, hipEventRecord(c->ev_side[1], c->side_stream));
+        hipLaunchKernelGGL(k_trace2_gate, dim3(1), dim3(1), 0, s, t.early, t.gate, n_help);
+        ACHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_trace2, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
+                       static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.resume, t.park, d_score,
+                       d_count, n_pairs, o.deadline, o.deadline_cycles);
+    ACHK(c, hipGetLastError());
+    if (o.side_help) ACHK(c, hipStreamWaitEvent(s, c->ev_side[1], 0));  // (the two helper launches share the helpers' buffers)
+    if (o.deadline) {  // (one workgroup per compute unit: a walker and its helpers fill one; more parked walks than that take turns)
+        help(s, t.park, 1u, nullptr);
+        ACHK(c, hipGetLastError());
+    }
+    ACHK(c, hipEventRecord(ev[2], s));
+    unsigned long long cells_done = 0;
+    ACHK(c, hipMemcpyAsync(xe, d_ctl + 1, 4, hipMemcpyDeviceToHost, s));
+    ACHK(c, hipMemcpyAsync(&cells_done, d_ctl + t.ctl_words - 2, 8, hipMemcpyDeviceToHost, s));
+    ACHK(c, hipStreamSynchronize(s));
+    c->tm.n_align_cells_computed += int64_t(cells_done);
+    return IOC_OK;
+}
+
+// developer aids after a slice (tools/corridor_rates.py): IOC_V2_TRACE_RATES prints the score per base against the
+// summed error rate, pair by pair (the corridor's calibration); IOC_V2_TRACE_TIMES the slowest walks of the slice (k_trace2
+// ends when its slowest wave does)
+int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* order, const V2Plan& pl, const V2Dev& t, size_t si, uint32_t deadline)
+{
+    const bool rates = getenv("IOC_V2_TRACE_RATES") != nullptr, times = getenv("IOC_V2_TRACE_TIMES") != nullptr;
+    if (!rates && !times) return IOC_OK;
+    const uint32_t np = pl.np, first_pair = 2u * pl.slices[si].first;
+    const uint32_t n_pairs = std::min(pl.cnt, 2u * (pl.slices[si].first + pl.slices[si].second)) - first_pair;
+    std::vector<int4> he(np);
+    ACHK(c, hipMemcpy(he.data(), c->a_ends2.p, size_t(np) * sizeof(int4), hipMemcpyDeviceToHost));
+    if (rates)
+        for (uint32_t x = 0; x < n_pairs; ++x) {
+            const uint32_t pid = order[first_pair + x];
+            const AlnPairDev& d = dp[pid];
+            fprintf(stderr, "[rate] e %.5f n %u m %u score %d per_base %.5f go %d flags %d corridor %u\n", double(d.e_sum), d.n, d.m, he[pid].x,
+                    double(he[pid].x) / double(std::max(d.n, d.m)), d.gap_open, he[pid].w, pl.cps[pl.pend[pid].couple].corridor);
+        }
+    if (!times) return IOC_OK;
+    std::vector<uint32_t> rw(size_t(np) * V2_RESUME_WORDS);
+    ACHK(c, hipMemcpy(rw.data(), t.resume, rw.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> ids(n_pairs);
+    for (uint32_t x = 0; x < n_pairs; ++x) ids[x] = order[first_pair + x];
+    // (first launch + second launch: the second starts when the first has ended, so the sum orders the pairs by what they cost)
+    auto rec = [&](uint32_t pid, uint32_t w) { return rw[size_t(pid) * V2_RESUME_WORDS + w]; };
+    auto cost = [&](uint32_t pid) { return (double(rec(pid, 8)) + double(rec(pid, 12))) * 256.0; };
+    std::sort(ids.begin(), ids.end(), [&](uint32_t a, uint32_t b) { return cost(a) > cost(b); });
+    double sum = 0;
+    uint32_t parked = 0;
+    for (uint32_t pid : ids) {
+        sum += cost(pid);
+        parked += rec(pid, 6) ? 1u : 0u;
+    }
+    fprintf(stderr, "[ioc] k_trace2: %u pairs, %u walks went on in the second launch (deadline %u blocks); mean %.3e cycles (s_memtime), slowest first:\n", n_pairs, parked,
+            deadline, sum / n_pairs);
+    auto line = [&](const char* tag, uint32_t pid) {
+        const AlnPairDev& d = dp[pid];
+        fprintf(stderr, "[ioc]   %s pair %u: %.3e + %.3e cycles, n %u m %u, blocks %u (%u on the diagonal) + %u (%u by helpers), tiles %u + %u, gap steps %u, windows %u\n", tag, pid,
+                double(rec(pid, 8)) * 256.0, double(rec(pid, 12)) * 256.0, d.n, d.m, rec(pid, 9) & 0xFFFFu, rec(pid, 9) >> 16, rec(pid, 13) & 0xFFFFu, rec(pid, 13) >> 16,
+                rec(pid, 10), rec(pid, 14), rec(pid, 11), rec(pid, 15));
+    };
+    {   // how well does the forward score tell the walks that get parked (wrong candidates) from the others?  score / shorter length
+        double pk_max = -1e9, un_min = 1e9, pk_sum = 0, un_sum = 0;
+        uint32_t npk = 0, nun = 0;
+        std::vector<double> pks, uns;
+        for (uint32_t pid : ids) {
+            const AlnPairDev& d = dp[pid];
+            const double q = double(he[pid].x) / double(std::max(1u, std::min(d.n, d.m)));
+            if (rec(pid, 6)) {
+                pk_max = std::max(pk_max, q), pk_sum += q, ++npk;
+                pks.push_back(q);
+            } else {
+                un_min = std::min(un_min, q), un_sum += q, ++nun;
+                uns.push_back(q);
+            }
+        }
+        std::sort(pks.begin(), pks.end());
+        std::sort(uns.begin(), uns.end());
+        auto qt = [](const std::vector<double>& v, double f) { return v.empty() ? 0.0 : v[std::min(v.size() - 1, size_t(f * double(v.size())))]; };
+        fprintf(stderr, "[ioc]   forward score / shorter length: parked walks (%u) mean %.3f, 50 %% %.3f, 90 %% %.3f, 99 %% %.3f, max %.3f | others (%u) min %.3f, 1 %% %.3f, 10 %% %.3f, mean %.3f\n", npk,
+                npk ? pk_sum / npk : 0.0, qt(pks, 0.5), qt(pks, 0.9), qt(pks, 0.99), pk_max, nun, un_min, qt(uns, 0.01), qt(uns, 0.1), nun ? un_sum / nun : 0.0);
+    }
+    for (uint32_t x = 0; x < std::min(n_pairs, 10u); ++x) line("", ids[x]);
+    for (uint32_t qx : {n_pairs / 4u, n_pairs / 2u, 3u * n_pairs / 4u}) line("rank", ids[qx]);
+    return IOC_OK;
+}
+
+// Version 2: the pairs order[0 .. cnt) (all of the query-profile kind, heaviest first) through k_fwd2 / k_fwd2_ends / k_trace2, with
+// the corridor (`corridor` false: every tile).  Returns IOC_OK with *fell_back = true when a bounded wait of the forward pass ran
+// out (the caller then runs the same pairs through version 1).
+int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* order, uint32_t cnt, const uint32_t* d_order,
+                 const AlnParams& P, int32_t* d_score, uint32_t* d_count, bool corridor, bool* fell_back)
+{
+    *fell_back = false;
+    if (cnt == 0) return IOC_OK;
+    int r;
+    const auto t_plan0 = std::chrono::steady_clock::now();  // (IOC_TRACE: host time of the planning up to the first launch)
+    V2Opts o{};
+    o.n_cu = compute_units(c);
+    uint64_t budget = 0;
+    if ((r = ck_budget(c, &budget)) != IOC_OK) return r;
+    // the 16-bit window's guard (|relative score| at a rebase): a pair beyond it is flagged and re-run by version 1
+    o.guard = P16_GUARD;
+    if (const char* e = getenv("IOC_ALIGN_V2_GUARD")) o.guard = std::max(1, std::min(P16_GUARD, atoi(e)));
+    o.few_limit = 128;
+    if (const char* e = getenv("IOC_ALIGN_V2_FEW")) o.few_limit = uint32_t(std::max(0, atoi(e)));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o.occ, reinterpret_cast<const void*>(k_fwd2), 64 * V2_WAVES, 0) != hipSuccess) o.occ = 0;
+    (void)hipGetLastError();
+    if (o.occ < 1) o.occ = 3;
+
+    V2Plan pl;
+    pl.cnt = cnt;
+    pl.np = uint32_t(dp.size());
+    pl.ncouples = (cnt + 1u) / 2u;
+    plan_couples(pl, dp, order, corridor_model(c, P, corridor), band_target(pl.ncouples, o.few_limit, o.occ, o.n_cu));
+    slice_couples(pl, budget);
+    const auto t_res0 = std::chrono::steady_clock::now();
+    if ((r = reserve(c, c->a_ck, size_t(pl.arena_words) * 4)) != IOC_OK) return r;
+    c->tm.align_arena_bytes = int64_t(pl.arena_words) * 4;
+    c->tm.align_slices = int32_t(pl.slices.size());
+    c->tm.align_version = 2;
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner v2: %u couples, checkpoint arena %.1f MB (%zu slice(s)) reserved in %.3f ms; corridor: %llu of %llu tiles skipped\n", pl.ncouples,
+                double(pl.arena_words) * 4e-6, pl.slices.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_res0).count(),
+                (unsigned long long)pl.tiles_skipped, (unsigned long long)pl.tiles_all);
+    tile_lists(pl);
+
+    o.deadline = 4;  // (blocks of slack on top of what a pair of one transcript needs to be decided: 2 per 512 windows of its threshold)
+    if (const char* e = getenv("IOC_TRACE2_DEADLINE")) o.deadline = uint32_t(std::max(0, atoi(e)));
+    if (const char* e = getenv("IOC_TRACE2_CYCLES")) o.deadline_cycles = (unsigned long long)std::max(0.0, atof(e));
+    o.help_wgs = o.deadline ? std::min<uint32_t>(pl.max_pairs, uint32_t(o.n_cu)) : 0u;
+    V2Dev t{};
+    if ((r = v2_tables(c, pl, o.help_wgs, t)) != IOC_OK) return r;
+    // The helper launch for the wrong candidates runs on a side stream BESIDE the first traceback launch (IOC_TRACE2_EARLY=0:
+    // everything goes through the first launch, as before): their walks are the longest of the batch, and the first launch — one
+    // pair's latency long, with the chip half empty — no longer waits for them to reach their deadline first.
+    o.side_help = o.deadline && !(getenv("IOC_TRACE2_EARLY") && atoi(getenv("IOC_TRACE2_EARLY")) == 0);
+    if (o.side_help && !c->side_stream) {
         ACHK(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
         for (auto& e : c->ev_side) ACHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(k_fwd2), 64 * V2_WAVES, 0) != hipSuccess) occ = 0;
-    (void)hipGetLastError();
-    if (occ < 1) occ = 3;
-    struct EventSet {  // (destroyed on every way out, the ACHK returns included)
-        std::vector<hipEvent_t> v;
-        ~EventSet()
-        {
-            for (auto& e : v)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evset;
-    evset.v.assign(slices.size() * 3, nullptr);
-    std::vector<hipEvent_t>& evs = evset.v;
-    for (auto& e : evs) ACHK(c, hipEventCreate(&e));
-    size_t evi = 0;
-    bool bad = false;
+    EventSet evs;
+    evs.v.assign(pl.slices.size() * 3, nullptr);
+    for (auto& e : evs.v) ACHK(c, hipEventCreate(&e));
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner v2: planning (couples, corridors, tile lists, tables) took the host %.3f ms\n",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan0).count());
-    for (size_t si = 0; si < slices.size() && !bad; ++si) {
-        const uint32_t first_pair = 2u * slices[si].first, n_pairs = std::min(cnt, 2u * (slices[si].first + slices[si].second)) - first_pair;
-        const uint32_t n_items = uint32_t(items[si].size());
-        // (few couples: bound by ONE grid's critical path — tiles follow their left neighbours row by row, v2_wait_rows; a tile
-        // publishes its progress every block of 64 rows)
-        const bool few_couples = slices[si].second <= few_limit;
-        const uint32_t prog_every = few_couples ? 1u : 0u;
-        ACHK(c, hipMemcpyAsync(d_items, items[si].data(), size_t(n_items) * sizeof(V2Item), hipMemcpyHostToDevice, s));
-        ACHK(c, hipMemcpyAsync(d_cps + slices[si].first, cps.data() + slices[si].first, size_t(slices[si].second) * sizeof(V2Couple), hipMemcpyHostToDevice, s));  // (flag0)
-        hipLaunchKernelGGL(k_fwd2_prof, dim3(slices[si].second, max_strips), dim3(128), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), d_cps + slices[si].first,
-                           static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<uint4*>(c->a_prof.p));
-        ACHK(c, hipGetLastError());
-        ACHK(c, hipMemsetAsync(d_ctl, 0, ctl_words * 4, s));
-        ACHK(c, hipMemsetAsync(d_resume, 0, resume_words * 4, s));  // (parked state and the two lists of walks; k_fwd2_ends writes into them)
-        if (tiles_skipped)  // (the bests of the last row and the last column that a skipped tile does not write: far below any score)
-            ACHK(c, hipMemsetAsync(d_lrow, 0x80, (size_t(lrow_total) + best_total) * sizeof(int2), s));
-        if (getenv("IOC_ALIGN_V2_FAKE_TIMEOUT")) {  // (tests: as if a bounded wait had run out — every later wait gives up at once,
-            const uint32_t one = 1;                 // tiles run on whatever is there, the host must fall back to version 1)
-            ACHK(c, hipMemcpyAsync(d_ctl + 1, &one, 4, hipMemcpyHostToDevice, s));
-        }
-        ACHK(c, hipEventRecord(evs[evi++], s));
-        // persistent waves: as many workgroups as the chip holds, but no more waves than tiles
-        if (n_probe[si]) {  // the probe launch and its verdicts (V2Couple): all on the device, nothing comes back to the host
-            const uint32_t n_wg0 = std::max(1u, std::min(uint32_t(occ) * uint32_t(n_cu), (n_probe[si] + V2_WAVES - 1) / V2_WAVES));
-            hipLaunchKernelGGL(k_fwd2, dim3(n_wg0), dim3(64 * V2_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), d_cps, d_items, n_probe[si],
-                               d_ctl, d_ctl + 16, d_ctl + 1, static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<uint32_t*>(c->a_ck.p), d_lrow,
-                               d_best, d_ctl + 16 + 2 * max_flags, guard, static_cast<const uint4*>(c->a_prof.p), reinterpret_cast<unsigned long long*>(d_ctl + ctl_words - 2), few_couples ? d_ctl + 16 + max_flags : static_cast<uint32_t*>(nullptr), prog_every);
-            ACHK(c, hipGetLastError());
-            hipLaunchKernelGGL(k_fwd2_probe, dim3(slices[si].second), dim3(64), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), d_cps + slices[si].first, d_pend,
-                               static_cast<const uint32_t*>(c->a_ck.p), P);
-            ACHK(c, hipGetLastError());
-            ACHK(c, hipMemsetAsync(d_ctl, 0, 4, s));  // (the queue's counter; the flags of the probe's tiles stay)
-        }
-        const uint32_t n_main = n_items - n_probe[si];
-        // Workgroups per compute unit.  A tile waits for the tile above and the tile to its left, so a couple's grid offers only
-        // its current anti-diagonal — with the corridor 2 - 3 tiles of a 16.7 kb pair — and a tile takes 0.5 - 0.9 ms: the pass is
-        // bound by tiles in flight as much as by throughput (config 3: 37 ms for a critical path of ~18).  Waves beyond the tiles
-        // that can run sit on a tile whose neighbours are still being computed, and they sit unevenly: a SIMD with three busy
-        // waves next to one with a single busy wave and two waiting.  So: as many workgroups per CU as the list's tiles per
-        // anti-diagonal keep busy, the same number on every CU (config 3 with the corridor: 2 per CU 37.2 ms, 3 per CU 39.8,
-        // 2.25 per CU 40.6; every tile: 3 per CU 67.6, 2 per CU 72.7; a quarter of the batch: 1 per CU 22.7, 3 per CU 25.1).
-        uint32_t per_cu = uint32_t(occ);
-        {
-            uint64_t tiles = 0;
-            uint32_t diags = 1;
-            for (uint32_t k2 = slices[si].first; k2 < slices[si].first + slices[si].second; ++k2) {
-                const V2Couple& cp = cps[k2];
-                for (uint32_t b = 0; b < cp.nbands; ++b) tiles += uint32_t(cp.phi[b]) - uint32_t(cp.plo[b]) + 1u;
-                diags = std::max(diags, cp.nbands + cp.nstrips - 1u);
-            }
-            const double x = double(tiles) / double(diags) / double(uint32_t(n_cu) * uint32_t(V2_WAVES));
-            if (!few_couples) per_cu = x < 1.0 ? 1u : x < 2.75 ? std::min(2u, uint32_t(occ)) : uint32_t(occ);
-        }
-        const uint32_t n_wg = std::max(1u, std::min(per_cu * uint32_t(n_cu), (n_main + V2_WAVES - 1) / V2_WAVES));
-        // (two workgroups per CU: the build of the kernel that may use the registers of the third)
-        auto* fwd_kernel = (per_cu <= 2 && !getenv("IOC_ALIGN_V2_NO_W2")) ? k_fwd2_w2 : k_fwd2;
-        hipLaunchKernelGGL(fwd_kernel, dim3(n_wg), dim3(64 * V2_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), d_cps, d_items + n_probe[si], n_main,
-                               d_ctl, d_ctl + 16, d_ctl + 1, static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<uint32_t*>(c->a_ck.p), d_lrow,
-                               d_best, d_ctl + 16 + 2 * max_flags, guard, static_cast<const uint4*>(c->a_prof.p), reinterpret_cast<unsigned long long*>(d_ctl + ctl_words - 2), few_couples ? d_ctl + 16 + max_flags : static_cast<uint32_t*>(nullptr), prog_every);
-        ACHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_fwd2_ends, dim3(n_pairs), dim3(64), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), d_cps, d_order + first_pair, n_pairs,
-                           d_pend, d_lrow, d_best, d_ctl + 16 + 2 * max_flags, static_cast<int4*>(c->a_ends2.p), d_resume, d_early, route ? int(P.match) : 0,
-                           std::min<uint32_t>(n_pairs, help_wgs));
-        ACHK(c, hipGetLastError());
-        ACHK(c, hipEventRecord(evs[evi++], s));
-        if (route) {  // (issued before the first launch: its workgroups — a walker and ten helpers each — take their places first)
-            ACHK(c, hipEventRecord(c->ev_side[0], s));
-            ACHK(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
-            hipLaunchKernelGGL(k_trace2_help, dim3(std::min<uint32_t>(n_pairs, help_wgs)), dim3(64 * V2_HWAVES), 0, c->side_stream,
-                               static_cast<const AlnPairDev*>(c->a_pairs.p), d_order + first_pair, static_cast<const uint8_t*>(c->a_pool.p), P,
-                               static_cast<const uint32_t*>(c->a_ck.p), d_cps, d_pck, static_cast<const int4*>(c->a_ends2.p), d_scratch, d_hscratch, d_resume,
-                               d_early, d_score, d_count, n_pairs, 2u, d_gate);
-            ACHK(c, hipGetLastError());
-            ACHK(c, hipEventRecord(c->ev_side[1], c->side_stream));
-            hipLaunchKernelGGL(k_trace2_gate, dim3(1), dim3(1), 0, s, d_early, d_gate, std::min<uint32_t>(n_pairs, help_wgs));
-            ACHK(c, hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_trace2, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p),
-                           d_order + first_pair, static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<const uint32_t*>(c->a_ck.p), d_cps, d_pck,
-                           static_cast<const int4*>(c->a_ends2.p), d_scratch, d_resume, d_park, d_score, d_count, n_pairs, deadline, deadline_cycles);
-        ACHK(c, hipGetLastError());
-        if (route) ACHK(c, hipStreamWaitEvent(s, c->ev_side[1], 0));  // (the two helper launches share the helpers' buffers)
-        if (deadline) {  // (one workgroup per compute unit: a walker and its helpers fill one; more parked walks than that take turns)
-            hipLaunchKernelGGL(k_trace2_help, dim3(std::min<uint32_t>(n_pairs, help_wgs)), dim3(64 * V2_HWAVES), 0, s,
-                               static_cast<const AlnPairDev*>(c->a_pairs.p), d_order + first_pair, static_cast<const uint8_t*>(c->a_pool.p), P,
-                               static_cast<const uint32_t*>(c->a_ck.p), d_cps, d_pck, static_cast<const int4*>(c->a_ends2.p), d_scratch, d_hscratch, d_resume,
-                               d_park, d_score, d_count, n_pairs, 1u, nullptr);
-            ACHK(c, hipGetLastError());
-        }
-        ACHK(c, hipEventRecord(evs[evi++], s));
-        if (getenv("IOC_V2_PROGRESS")) {  // debug watchdog: where are the kernels after 10 s?  (build with -DIOC_V2_MARKS)
-            const auto tw = std::chrono::steady_clock::now();
-            while (hipStreamQuery(s) == hipErrorNotReady) {
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count() > 10.0) {
-                    hipStream_t s2 = nullptr;
-                    uint32_t pg[16] = {0};
-                    (void)hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-                    (void)hipMemcpyAsync(pg, d_ctl, sizeof pg, hipMemcpyDeviceToHost, s2);
-                    (void)hipStreamSynchronize(s2);
-                    fprintf(stderr, "[ioc] v2 WATCHDOG: queue %u err %u | dequeued %u, past waits %x, nsteps %u, step %u, after loop %u, published %u, wave exits %x %x %x %x, end marks %u %u %u\n",
-                            pg[0], pg[1], pg[2], pg[3], pg[4], pg[5], pg[6], pg[7], pg[8], pg[9], pg[10], pg[11], pg[12], pg[13], pg[14]);
-                    fflush(stderr);
-                    abort();
-                }
-            }
-        }
+    size_t evi = 0;
+    bool bad = false;
+    for (size_t si = 0; si < pl.slices.size() && !bad; ++si, evi += 3) {
         uint32_t xe = 0;
-        unsigned long long cells_done = 0;
-        ACHK(c, hipMemcpyAsync(&xe, d_ctl + 1, 4, hipMemcpyDeviceToHost, s));
-        ACHK(c, hipMemcpyAsync(&cells_done, d_ctl + ctl_words - 2, 8, hipMemcpyDeviceToHost, s));
-        ACHK(c, hipStreamSynchronize(s));
-        c->tm.n_align_cells_computed += int64_t(cells_done);
-        if (getenv("IOC_V2_PROGRESS")) {  // (marks build: cycles the waves spent waiting for tiles / alive / the longest-lived wave)
-            unsigned long long t[3] = {0, 0, 0};
-            uint32_t pg[16] = {0};
-            ACHK(c, hipMemcpy(pg, d_ctl, sizeof pg, hipMemcpyDeviceToHost));
-            memcpy(&t[0], &pg[12], 8);
-            memcpy(&t[1], &pg[14], 8);
-            memcpy(&t[2], &pg[10], 8);
-            fprintf(stderr, "[ioc] v2 marks: waiting %.3e cycles of %.3e wave-cycles alive (%.1f %%), longest wave %.3e cycles, %u workgroups\n", double(t[0]), double(t[1]),
-                    100.0 * double(t[0]) / std::max(1.0, double(t[1])), double(t[2]), n_wg);
-        }
-        if (getenv("IOC_V2_TRACE_RATES")) {  // developer aid: score per base against the summed error rate, pair by pair (the corridor's calibration)
-            std::vector<int4> he(np);
-            ACHK(c, hipMemcpy(he.data(), c->a_ends2.p, size_t(np) * sizeof(int4), hipMemcpyDeviceToHost));
-            for (uint32_t x = 0; x < n_pairs; ++x) {
-                const uint32_t pid = order[first_pair + x];
-                const AlnPairDev& d = dp[pid];
-                fprintf(stderr, "[rate] e %.5f n %u m %u score %d per_base %.5f go %d flags %d corridor %u\n", double(d.e_sum), d.n, d.m, he[pid].x,
-                        double(he[pid].x) / double(std::max(d.n, d.m)), d.gap_open, he[pid].w, cps[pend[pid].couple].corridor);
-            }
-        }
-        if (getenv("IOC_V2_TRACE_TIMES")) {  // developer aid: the slowest walks of the slice (k_trace2 ends when its slowest wave does)
-            std::vector<uint32_t> rw(size_t(np) * V2_RESUME_WORDS);
-            ACHK(c, hipMemcpy(rw.data(), d_resume, rw.size() * 4, hipMemcpyDeviceToHost));
-            std::vector<uint32_t> ids(n_pairs);
-            for (uint32_t x = 0; x < n_pairs; ++x) ids[x] = order[first_pair + x];
-            // (first launch + second launch: the second starts when the first has ended, so the sum orders the pairs by what they cost)
-            auto rec = [&](uint32_t pid, uint32_t w) { return rw[size_t(pid) * V2_RESUME_WORDS + w]; };
-            auto cost = [&](uint32_t pid) { return (double(rec(pid, 8)) + double(rec(pid, 12))) * 256.0; };
-            std::sort(ids.begin(), ids.end(), [&](uint32_t a, uint32_t b) { return cost(a) > cost(b); });
-            double sum = 0;
-            uint32_t parked = 0;
-            for (uint32_t pid : ids) {
-                sum += cost(pid);
-                parked += rec(pid, 6) ? 1u : 0u;
-            }
-            fprintf(stderr, "[ioc] k_trace2: %u pairs, %u walks went on in the second launch (deadline %u blocks); mean %.3e cycles (s_memtime), slowest first:\n", n_pairs, parked,
-                    deadline, sum / n_pairs);
-            auto line = [&](const char* tag, uint32_t pid) {
-                const AlnPairDev& d = dp[pid];
-                fprintf(stderr, "[ioc]   %s pair %u: %.3e + %.3e cycles, n %u m %u, blocks %u (%u on the diagonal) + %u (%u by helpers), tiles %u + %u, gap steps %u, windows %u\n", tag, pid,
-                        double(rec(pid, 8)) * 256.0, double(rec(pid, 12)) * 256.0, d.n, d.m, rec(pid, 9) & 0xFFFFu, rec(pid, 9) >> 16, rec(pid, 13) & 0xFFFFu, rec(pid, 13) >> 16,
-                        rec(pid, 10), rec(pid, 14), rec(pid, 11), rec(pid, 15));
-            };
-            {   // how well does the forward score tell the walks that get parked (wrong candidates) from the others?  score / shorter length
-                std::vector<int4> he(np);
-                ACHK(c, hipMemcpy(he.data(), c->a_ends2.p, size_t(np) * sizeof(int4), hipMemcpyDeviceToHost));
-                double pk_max = -1e9, un_min = 1e9, pk_sum = 0, un_sum = 0;
-                uint32_t npk = 0, nun = 0;
-                std::vector<double> pks, uns;
-                for (uint32_t pid : ids) {
-                    const AlnPairDev& d = dp[pid];
-                    const double q = double(he[pid].x) / double(std::max(1u, std::min(d.n, d.m)));
-                    if (rec(pid, 6)) {
-                        pk_max = std::max(pk_max, q), pk_sum += q, ++npk;
-                        pks.push_back(q);
-                    } else {
-                        un_min = std::min(un_min, q), un_sum += q, ++nun;
-                        uns.push_back(q);
-                    }
-                }
-                std::sort(pks.begin(), pks.end());
-                std::sort(uns.begin(), uns.end());
-                auto qt = [](const std::vector<double>& v, double f) { return v.empty() ? 0.0 : v[std::min(v.size() - 1, size_t(f * double(v.size())))]; };
-                fprintf(stderr, "[ioc]   forward score / shorter length: parked walks (%u) mean %.3f, 50 %% %.3f, 90 %% %.3f, 99 %% %.3f, max %.3f | others (%u) min %.3f, 1 %% %.3f, 10 %% %.3f, mean %.3f\n", npk,
-                        npk ? pk_sum / npk : 0.0, qt(pks, 0.5), qt(pks, 0.9), qt(pks, 0.99), pk_max, nun, un_min, qt(uns, 0.01), qt(uns, 0.1), nun ? un_sum / nun : 0.0);
-            }
-            for (uint32_t x = 0; x < std::min(n_pairs, 10u); ++x) line("", ids[x]);
-            for (uint32_t qx : {n_pairs / 4u, n_pairs / 2u, 3u * n_pairs / 4u}) line("rank", ids[qx]);
-        }
-        if (xe) bad = true;
+        if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe)) != IOC_OK) return r;
+        if ((r = v2_report(c, dp, order, pl, t, si, o.deadline)) != IOC_OK) return r;
+        bad = xe != 0;
     }
-    for (size_t x = 0; x + 2 < evi + 0 && x + 2 < evs.size(); x += 3) {
-        float a = 0, b = 0;
-        if (hipEventElapsedTime(&a, evs[x], evs[x + 1]) == hipSuccess) c->tm.ms_align_fwd += a;
-        if (hipEventElapsedTime(&b, evs[x + 1], evs[x + 2]) == hipSuccess) c->tm.ms_align_trace += b;
-    }
+    add_elapsed(c, evs.v, evi);
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner v2: forward %.3f ms, traceback %.3f ms (device, all slices so far)%s\n", c->tm.ms_align_fwd,
                 c->tm.ms_align_trace, bad ? " — a wait ran out: falling back to version 1" : "");
@@ -1824,17 +1910,602 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     return IOC_OK;
 }
 
+// ---- ioc_align_pairs, stage by stage ------------------------------------------------------------------------------------
+
+// which pairs a call may send where: everything (normal), the same without a corridor (the re-run of pairs the corridor could not
+// vouch for), or version 1 alone (the re-run of pairs version 2's 16-bit window refused)
+enum class AlnRoute { normal, every_tile, v1_only };
+
+// the caller's answer arrays (each may be null)
+struct AlnOut {
+    int32_t* score;
+    int64_t* windows;
+    double* ratio;
+    void set(size_t i, int32_t s, int64_t w, double r) const
+    {
+        if (score) score[i] = s;
+        if (windows) windows[i] = w;
+        if (ratio) ratio[i] = r;
+    }
+};
+
+// the pairs of a call that need the device
+struct AlnBatch {
+    std::vector<AlnPairDev> dp;
+    std::vector<uint32_t> back;   // device pair -> caller pair
+    std::vector<uint32_t> order;  // the device pairs in the order the launches take them
+    uint32_t max_n = 1, max_m = 1;
+};
+
+// 1. the device records; a pair with an empty sequence is answered here
+int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const AlnParams& P, const AlnOut& out, AlnBatch& b)
+{
+    const int32_t n_seqs = c->aln_offs.empty() ? 0 : int32_t(c->aln_offs.size() - 1);
+    const int32_t k = int32_t(P.k);
+    b.dp.reserve(size_t(n_pairs));
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        const ioc_aln_pair& a = pairs[i];
+        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs)
+            return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
+        const int64_t n = c->aln_offs[size_t(a.query) + 1] - c->aln_offs[size_t(a.query)];
+        const int64_t m = c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)];
+        if (n + m >= (int64_t(1) << ALN_LEN_SHIFT))
+            return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: sequences above 2^26 bases");
+        const double limit = std::floor((1.0 - a.e) * double(k));  // getAlnRatio, cluster.cpp:446
+        const int32_t il = limit < -1.0 ? -1 : limit > 64.0 ? 64 : int32_t(limit);
+        if (n == 0 || m == 0) {
+            // nothing to align: the comparison string is n + m blanks
+            const int64_t len = n + m;
+            const int64_t cnt = (il <= 0 && len > k) ? len - k : 0;
+            out.set(size_t(i), 0, cnt, n == 0 ? 0.0 : double(cnt) / double(n));
+            continue;
+        }
+        AlnPairDev d{};
+        d.q_off = uint32_t(c->aln_offs[size_t(a.query)]);
+        d.n = uint32_t(n);
+        d.r_off = uint32_t(c->aln_offs[size_t(a.ref)]);
+        d.m = uint32_t(m);
+        d.gap_open = ioc_host_gap_open(a.e);
+        d.e_sum = float(a.e);
+        d.ilimit = il;
+        d.rc = a.ref_revcomp ? 1u : 0u;
+        d.stop_at = 0;
+        if (c->aln_verdict_thr > 0.0 && n > 0) {
+            // smallest count a with double(a) / double(n) >= threshold: the comparison the caller will make (getAlnRatio / slen)
+            double a0 = std::ceil(c->aln_verdict_thr * double(n));
+            while (a0 > 0 && (a0 - 1.0) / double(n) >= c->aln_verdict_thr) a0 -= 1.0;
+            while (a0 / double(n) < c->aln_verdict_thr) a0 += 1.0;
+            d.stop_at = a0 >= 1.0 && a0 < 4.0e9 ? uint32_t(a0) : 0u;
+        }
+        {   // query-profile kernel: four-letter sequences, diagonal increments that fit a byte
+            const int gd = d.gap_open - P.gap_extend, cm = P.match + 2 * P.gap_extend + gd, cx = P.mismatch + 2 * P.gap_extend + gd;
+            const bool ok = !c->aln_other[size_t(a.query)] && !c->aln_other[size_t(a.ref)] && cm >= 0 && cm <= 255 &&
+                            cx >= 0 && cx <= 255 && !getenv("IOC_ALIGN_NO_PROFILE");
+            d.pad = ok ? 1u : 0u;
+        }
+        b.dp.push_back(d);
+        b.back.push_back(uint32_t(i));
+        b.max_n = std::max(b.max_n, d.n);
+        b.max_m = std::max(b.max_m, d.m);
+    }
+    return IOC_OK;
+}
+
+// 2. the order of the launches (stable sorts and partitions: order only, never a result)
+void order_pairs(AlnBatch& b, const ioc_aln_pair* pairs)
+{
+    const std::vector<AlnPairDev>& dp = b.dp;
+    const uint32_t np = uint32_t(dp.size());
+    std::vector<uint32_t>& order = b.order;
+    // heaviest pairs first
+    order.resize(np);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return uint64_t(dp[x].n) * dp[x].m > uint64_t(dp[y].n) * dp[y].m;
+    });
+    // Pairs with the same tile grid (coarse rows x strips) in the order of their summed error rates: a couple's corridor is as wide as
+    // its less similar pair needs (align_v2_run), so like goes with like.
+    {
+        auto rows = [&](uint32_t x) { return uint64_t((dp[x].n + 511u) / 512u); };
+        auto cols = [&](uint32_t x) { return uint64_t((dp[x].m + 511u) / 512u); };
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+            const uint64_t tx = rows(x) * cols(x), ty = rows(y) * cols(y);
+            if (tx != ty) return tx > ty;  // (heaviest first, as before — by tiles)
+            if (rows(x) != rows(y)) return rows(x) > rows(y);
+            return dp[x].e_sum > dp[y].e_sum;
+        });
+    }
+    // The caller's similarity hints (ioc_aln_pair::reserved, 0 = none): pairs hinted far below the batch's median — a quarter of
+    // it — are taken for unrelated and sorted behind the others, so that version 2 couples them with each other: a couple with
+    // an unrelated pair gets no corridor, and a pair of one transcript coupled with it pays for every tile too (config 3: 19 %
+    // of the couples hold a wrong candidate when they are coupled by size alone, 10 % of the pairs are one).
+    {
+        std::vector<int32_t> hp;
+        for (uint32_t x = 0; x < np; ++x)
+            if (pairs[b.back[x]].reserved > 0) hp.push_back(pairs[b.back[x]].reserved);
+        if (hp.size() >= 8 && !getenv("IOC_ALIGN_NO_HINTS")) {
+            std::nth_element(hp.begin(), hp.begin() + long(hp.size() / 2), hp.end());
+            const int64_t med = hp[hp.size() / 2];
+            std::stable_partition(order.begin(), order.end(), [&](uint32_t x) {
+                const int64_t h = pairs[b.back[x]].reserved;
+                return !(h > 0 && h * 4 < med);
+            });
+        }
+    }
+    // trace variant: the pairs of the query-profile kernel first, the comparing kernel's after them
+    std::stable_partition(order.begin(), order.end(), [&](uint32_t x) { return dp[x].pad != 0; });
+}
+
+// 3. waves per pair: few pairs -> wide workgroups (latency), many pairs -> narrow ones (no fill/drain waste)
+struct WavePlan {
+    uint32_t waves;
+    bool few_pairs;  // a handful of long pairs (the later alignment rounds of a batch): 4-wave workgroups, several per pair (v1_slice)
+};
+WavePlan plan_waves(const AlnBatch& b, bool carry)
+{
+    const uint32_t np = uint32_t(b.dp.size());
+    uint32_t waves = ALN_MAXW;
+    if (const char* e = getenv("IOC_ALIGN_WAVES")) {
+        const int v = atoi(e);
+        if (v >= 1 && v <= ALN_MAXW) waves = uint32_t(v);
+    } else {
+        while (waves > 1 && uint64_t(np) * waves > 4096) waves >>= 1;
+        if (carry) {
+            while (waves > 1 && uint64_t(waves / 2) * 64 * ALN_C >= b.max_m) waves >>= 1;
+        } else {
+            // row bands x column strips run as a pipeline: it needs a few strips per band to fill, and
+            // whole tiles per band
+            const uint32_t strips = (b.max_m + 64 * FW_C - 1) / (64 * FW_C), tiles = (b.max_n + TILE - 1) / TILE;
+            while (waves > 1 && (strips < 2 * waves || tiles < 2 * waves)) waves >>= 1;
+        }
+    }
+    const bool few_pairs = !carry && !getenv("IOC_ALIGN_WAVES") && np <= 64 && waves >= 4 && !getenv("IOC_ALIGN_NO_CROSS_TAIL");
+    return WavePlan{few_pairs ? 4u : waves, few_pairs};
+}
+
+// 4. version 2 takes the query-profile pairs — the front of `order`; *n_v2: how many it answered (0 when a bounded wait ran out
+// and they all go to version 1)
+int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2)
+{
+    const uint32_t np = uint32_t(b.dp.size());
+    uint32_t n = 0;
+    while (n < np && b.dp[b.order[n]].pad != 0) ++n;
+    bool fell_back = false;
+    const int r = align_v2_run(c, b.dp, b.order.data(), n, static_cast<const uint32_t*>(c->a_order.p), P, d_score, d_count, route != AlnRoute::every_tile,
+                               &fell_back);
+    if (r != IOC_OK) return r;
+    if (fell_back) {
+        c->tm.n_align_refused += n;
+        n = 0;
+    }
+    *n_v2 = n;
+    return IOC_OK;
+}
+
+// 5. the carry variant (IOC_ALIGN_VARIANT=carry): every pair, in slices when the whole batch would not fit the budget
+int run_carry(ioc_ctx* c, const AlnBatch& b, uint32_t waves, const AlnParams& P, int32_t* d_score, uint32_t* d_count)
+{
+    const uint32_t np = uint32_t(b.dp.size()), NT = waves * 64;
+    const uint64_t bnd_stride = 2ull * 6ull * b.max_n;
+    const uint64_t lrow_entries = uint64_t((b.max_m + NT * ALN_C - 1) / (NT * ALN_C)) * NT;
+    const uint64_t lrow_stride = lrow_entries * 4ull;
+    // scratch is per workgroup
+    const uint64_t budget = 8ull << 30;
+    const uint64_t per_pair = (bnd_stride + lrow_stride) * 4ull;
+    const uint32_t slice = uint32_t(std::min<uint64_t>(np, std::max<uint64_t>(1, budget / per_pair)));
+    int r;
+    if ((r = reserve(c, c->a_bnd, size_t(slice) * bnd_stride * 4)) != IOC_OK) return r;
+    if ((r = reserve(c, c->a_lrow, size_t(slice) * lrow_stride * 4)) != IOC_OK) return r;
+    for (uint32_t first = 0; first < np; first += slice) {
+        const uint32_t cnt = std::min(slice, np - first);
+        hipLaunchKernelGGL(k_align_carry, dim3(cnt), dim3(NT), 0, c->stream, static_cast<const AlnPairDev*>(c->a_pairs.p),
+                           static_cast<const uint32_t*>(c->a_order.p) + first, static_cast<const uint8_t*>(c->a_pool.p), P,
+                           static_cast<uint32_t*>(c->a_bnd.p), bnd_stride, static_cast<uint32_t*>(c->a_lrow.p), lrow_stride, d_score, d_count);
+        ACHK(c, hipGetLastError());
+    }
+    return IOC_OK;
+}
+
+// ---- 6. version 1 ---------------------------------------------------------------------------------------------------------
+
+// The static LDS of a k_align_fwd variant (`fallback` when the runtime cannot tell), and the most dynamic LDS one of its
+// workgroups may reserve on top: more than the default 64 KB per workgroup needs the kernel attribute, asked for once per
+// variant and context (best effort).
+size_t fwd_lds_limit(ioc_ctx* c, bool prof, const void* kfn, size_t fallback, size_t* stat)
+{
+    hipFuncAttributes fa{};
+    *stat = fallback;
+    if (hipFuncGetAttributes(&fa, kfn) == hipSuccess) *stat = fa.sharedSizeBytes;
+    size_t& lim = prof ? c->aln_lds_max : c->aln_lds_max2;
+    if (lim == 0) {
+        int mx = 0;
+        (void)hipDeviceGetAttribute(&mx, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device);
+        lim = 64 * 1024 > *stat ? 64 * 1024 - *stat : 1;
+        if (mx > 72 * 1024 && hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, mx - int(*stat)) == hipSuccess)
+            lim = size_t(mx) - *stat;
+        (void)hipGetLastError();
+    }
+    return lim;
+}
+
+// checkpoint arena: slices of pairs (in `order`, from n_v2 on) whose checkpoints fit the budget together, one kernel per slice
+struct V1Plan {
+    std::vector<AlnCk> cko;
+    std::vector<std::pair<uint32_t, uint32_t>> slices;  // [first, count) in `order`
+    uint64_t arena = 0;                                 // int2 units
+    uint32_t max_cnt = 0;
+};
+uint64_t v1_row_units(const AlnPairDev& d) { return uint64_t((d.n - 1) / TILE) * row_pitch(d.m); }
+
+V1Plan plan_v1(const AlnBatch& b, uint32_t n_v2, uint64_t budget)
+{
+    const std::vector<AlnPairDev>& dp = b.dp;
+    const uint32_t np = uint32_t(dp.size());
+    V1Plan pl;
+    pl.cko.resize(np);
+    for (uint32_t first = n_v2; first < np;) {
+        uint64_t used = 0;
+        uint32_t cnt = 0;
+        while (first + cnt < np) {
+            const AlnPairDev& d = dp[b.order[first + cnt]];
+            const uint64_t u = v1_row_units(d) + uint64_t((d.m - 1) / TILE) * col_pitch(d.n);
+            if (cnt > 0 && (used + u) * 8ull > budget) break;
+            if (cnt > 0 && d.pad != dp[b.order[first]].pad) break;  // one kernel per slice
+            // (rows first: their pitch is a multiple of 16 int2, `used` stays 16-byte aligned for the int4 stores)
+            pl.cko[b.order[first + cnt]] = AlnCk{used, used + v1_row_units(d)};
+            used += u;
+            ++cnt;
+        }
+        pl.arena = std::max(pl.arena, used);
+        pl.slices.emplace_back(first, cnt);
+        pl.max_cnt = std::max(pl.max_cnt, cnt);
+        first += cnt;
+    }
+    return pl;
+}
+
+// version 1's forward pass over the pairs o[0 .. cnt) of a slice (k_align_fwd, see there for the arguments)
+struct V1Fwd {
+    ioc_ctx* c;
+    bool prof;
+    AlnParams P;
+    uint64_t lrow_stride;
+    int operator()(const uint32_t* o, uint32_t cnt, uint32_t wv, uint32_t wgw, uint32_t nwg, uint32_t nmain, uint32_t wtail, size_t lds,
+                   uint32_t lrow_first, const AlnCross& X) const
+    {
+        const AlnPairDev* dpairs = static_cast<const AlnPairDev*>(c->a_pairs.p);
+        const uint8_t* dpool = static_cast<const uint8_t*>(c->a_pool.p);
+        int2* dck = static_cast<int2*>(c->a_ck.p);
+        const AlnCk* dcko = static_cast<const AlnCk*>(c->a_cko.p);
+        int2* lr = static_cast<int2*>(c->a_lrow.p) + uint64_t(lrow_first) * lrow_stride;
+        int4* dends = static_cast<int4*>(c->a_ends2.p);
+        if (prof)
+            hipLaunchKernelGGL(k_align_fwd<true>, dim3(nwg), dim3(wgw * 64), lds, c->stream, dpairs, o, cnt, wv, nmain, wtail, dpool, P, dck, dcko, lr,
+                               lrow_stride, dends, X);
+        else
+            hipLaunchKernelGGL(k_align_fwd<false>, dim3(nwg), dim3(wgw * 64), lds, c->stream, dpairs, o, cnt, wv, nmain, wtail, dpool, P, dck, dcko, lr,
+                               lrow_stride, dends, X);
+        ACHK(c, hipGetLastError());
+        return IOC_OK;
+    }
+};
+
+// The tail generation of a slice — its pairs from `first_cnt` on — split over `groups` workgroups each, the first band of a
+// workgroup waiting on a flag for the row checkpoints of the band above.  `inl`: in the SAME launch as the ordinary workgroups
+// (n_main of them), behind them; otherwise in a launch of its own.  The waits are bounded: when one runs out (the workgroups
+// were not all resident) the tail is done again the usual way.
+int v1_cross_tail(ioc_ctx* c, const AlnBatch& b, const V1Fwd& fwd, const std::pair<uint32_t, uint32_t>& sl, uint32_t waves, uint32_t wg_waves,
+                  uint32_t n_main, uint32_t ppw, uint32_t groups, bool inl, size_t lds_pad, const void* kfn)
+{
+    hipStream_t s = c->stream;
+    const uint32_t* ord = static_cast<const uint32_t*>(c->a_order.p) + sl.first;
+    const uint32_t first_cnt = n_main * ppw, rest = sl.second - first_cnt, nb = 4 * groups;
+    // flags are indexed [band][strip] with every pair's OWN strip count: a pair with fewer cells than the slice's first one may
+    // still have the longer reference, so the slot holds the largest count of the pairs that are actually split
+    uint32_t strips = 1;
+    for (uint32_t x = first_cnt; x < sl.second; ++x) strips = std::max(strips, (b.dp[b.order[sl.first + x]].m + 64 * FW_C - 1) / (64 * FW_C));
+    AlnCross X;
+    X.groups = groups;
+    X.flag_stride = nb * strips;
+    const size_t fbytes = size_t(rest) * X.flag_stride * 4, bbytes = size_t(rest) * nb * sizeof(int2);
+    int r;
+    if ((r = reserve(c, c->a_xflags, fbytes + bbytes + 64)) != IOC_OK) return r;
+    X.err = static_cast<uint32_t*>(c->a_xflags.p);
+    X.flags = X.err + 16;
+    X.best = reinterpret_cast<int2*>(reinterpret_cast<uint8_t*>(c->a_xflags.p) + 64 + fbytes);
+    ACHK(c, hipMemsetAsync(c->a_xflags.p, 0, 64 + fbytes, s));
+    if (inl && first_cnt) {
+        // one launch: ordinary workgroups, then the split pairs behind them
+        X.first_wg = n_main;
+        X.first_pair = first_cnt;
+        if ((r = fwd(ord, sl.second, waves, wg_waves, n_main + rest * groups, n_main + rest * groups, waves, lds_pad, 0, X)) != IOC_OK) return r;
+    } else {
+        if (first_cnt && (r = fwd(ord, first_cnt, waves, wg_waves, n_main, n_main, waves, lds_pad, 0, AlnCross{})) != IOC_OK) return r;
+        size_t stat = 0, xlds = 0;  // more than half a CU's LDS: the dispatcher cannot stack two of them
+        const size_t lim = fwd_lds_limit(c, fwd.prof, kfn, 52 * 1024, &stat), want = 84 * 1024;
+        if (want > stat && want - stat <= lim) xlds = (want - stat) & ~size_t(255);
+        if ((r = fwd(ord + first_cnt, rest, 4, 4, rest * groups, rest * groups, 4, xlds, first_cnt, X)) != IOC_OK) return r;
+    }
+    uint32_t xe = 0;
+    ACHK(c, hipMemcpyAsync(&xe, X.err, 4, hipMemcpyDeviceToHost, s));
+    ACHK(c, hipStreamSynchronize(s));
+    if (xe) {  // a wait ran out: the tail again, the usual way
+        if ((r = fwd(ord + first_cnt, rest, 4, 4, rest, rest, 4, 0, first_cnt, AlnCross{})) != IOC_OK) return r;
+        c->tm.n_align_refused += rest;
+    }
+    return IOC_OK;
+}
+
+// one slice of version 1: the forward pass (ordinary workgroups, a partly filled second generation, or the split tail) and the
+// traceback, events ev[0 .. 3) around them
+int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>& sl, const WavePlan& wp, const AlnParams& P, int n_cu,
+             uint64_t lrow_stride, int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev)
+{
+    hipStream_t s = c->stream;
+    const uint32_t waves = wp.waves;
+    const uint32_t* ord = static_cast<const uint32_t*>(c->a_order.p) + sl.first;
+    // Every workgroup lives for the whole launch (equal-sized pairs), so the launch ends with the
+    // fullest CU: cap the residency at ceil(workgroups / CUs) per CU with an LDS reservation, or the
+    // dispatcher may stack 8 workgroups on some CUs and leave others with 3.
+    const bool prof = b.dp[b.order[sl.first]].pad != 0;
+    const void* kfn = prof ? reinterpret_cast<const void*>(k_align_fwd<true>) : reinterpret_cast<const void*>(k_align_fwd<false>);
+    const V1Fwd fwd{c, prof, P, lrow_stride};
+    size_t lds_pad = 0;
+    const uint32_t wg_waves = waves > 4 ? waves : 4, ppw = wg_waves / waves;
+    uint32_t n_wg = (sl.second + ppw - 1) / ppw, n_main = n_wg, wpp_tail = waves;
+    {   // a second, partly filled generation of workgroups: give its pairs twice the waves
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, int(wg_waves * 64), 0) != hipSuccess) occ = 0;
+        (void)hipGetLastError();
+        const uint32_t gen = uint32_t(occ > 0 ? occ : 3) * uint32_t(n_cu);  // resident workgroups
+        if (n_wg > gen && n_wg < gen + gen / 2 && 2 * waves <= wg_waves) {
+            n_main = gen;
+            wpp_tail = 2 * waves;
+            const uint32_t rest = sl.second - n_main * ppw, ppw_tail = wg_waves / wpp_tail;
+            n_wg = n_main + (rest + ppw_tail - 1) / ppw_tail;
+        }
+    }
+    const uint32_t per_cu = (n_main + uint32_t(n_cu) - 1) / uint32_t(n_cu);
+    if (per_cu * wg_waves < 32) {
+        // per-workgroup LDS (static + reservation) halfway between 160 KB / (per_cu + 1) and 160 KB / per_cu
+        size_t stat = 0;
+        const size_t lim = fwd_lds_limit(c, prof, kfn, 48 * 1024, &stat);
+        const size_t want = size_t(160u * 1024u) * (2 * per_cu + 1) / (2 * per_cu * (per_cu + 1));
+        lds_pad = want > stat + 1024 ? (want - stat - 512) & ~size_t(255) : 0;
+        lds_pad = std::min(lds_pad, lim > 1 ? lim : 0);
+    }
+    ACHK(c, hipEventRecord(ev[0], s));
+    // The tail generation runs on a mostly empty chip: its pairs are split over SEVERAL workgroups each
+    // (4 x 4 = 16 bands on 4 CUs; an 8-wave workgroup lands on one CU, two waves per SIMD, and was slower).
+    uint32_t groups = 1;
+    // the whole slice the tail's way: forced (tests), or a handful of pairs on an otherwise idle chip
+    const bool force_cross = getenv("IOC_ALIGN_FORCE_CROSS") != nullptr || (wp.few_pairs && waves == 4);
+    if (force_cross && wg_waves == 4) {
+        n_main = 0;
+        n_wg = 1;
+    }
+    // Default: in the SAME launch, behind the ordinary workgroups, so that a split pair starts on whatever CU
+    // frees up first (config 3: 105.2 -> 96.0 ms).  A launch of its own (one workgroup per CU by an LDS reservation) was
+    // measured slower — it cannot backfill, 112 ms — and is left to slices without ordinary workgroups (the forced split).
+    // IOC_ALIGN_NO_CROSS_TAIL=1 keeps the tail pairs whole with twice the waves (the first version).
+    // Workgroups of a launch are handed out in index order and a workgroup only waits for a smaller index;
+    // the split ones are at most two thirds of an XCD's slots, so they can never fill an XCD with waiters.
+    const bool inl = !force_cross;
+    if (n_main < n_wg && wg_waves == 4 && !getenv("IOC_ALIGN_NO_CROSS_TAIL")) {
+        const AlnPairDev& big = b.dp[b.order[sl.first]];
+        const uint32_t strips = (big.m + 64 * FW_C - 1) / (64 * FW_C), tiles = (big.n + TILE - 1) / TILE;
+        groups = force_cross ? 4 : 2;  // (behind a full generation 4 was measured slower: 99 ms)
+        if (const char* eg = getenv("IOC_ALIGN_CROSS_GROUPS")) groups = uint32_t(std::max(1, std::min(4, atoi(eg))));
+        while (groups > 1 && (strips < 4 * groups || tiles < 8 * groups)) groups >>= 1;  // bands = 4 * groups
+        const uint32_t rest = sl.second - n_main * ppw;
+        // one workgroup per CU (two on a CU run at half speed and hold up the whole chain of their pair), all
+        // resident together
+        // (in-launch: at most 2 split workgroups per CU's worth, i.e. 64 of an XCD's 96 slots — waiters cannot
+        // fill an XCD; a launch of its own: one per CU)
+        while (groups > 1 && uint64_t(rest) * groups > uint64_t(inl ? 2 : 1) * uint64_t(n_cu)) groups >>= 1;
+    }
+    int r;
+    if (groups > 1) {
+        if ((r = v1_cross_tail(c, b, fwd, sl, waves, wg_waves, n_main, ppw, groups, inl, lds_pad, kfn)) != IOC_OK) return r;
+    } else {
+        if (force_cross && n_main == 0) {  // (the forced split did not fit this slice)
+            n_wg = (sl.second + ppw - 1) / ppw;
+            n_main = n_wg;
+        }
+        if ((r = fwd(ord, sl.second, waves, wg_waves, n_wg, n_main, wpp_tail, lds_pad, 0, AlnCross{})) != IOC_OK) return r;
+    }
+    ACHK(c, hipEventRecord(ev[1], s));
+    const uint32_t tr_wg = (sl.second + TR_WAVES - 1) / TR_WAVES;  // (an LDS reservation that caps the workgroups per CU changed nothing here)
+    hipLaunchKernelGGL(k_align_trace, dim3(tr_wg), dim3(64 * TR_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), ord,
+                       static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<const int2*>(c->a_ck.p), static_cast<const AlnCk*>(c->a_cko.p),
+                       static_cast<const int4*>(c->a_ends2.p), d_score, d_count, sl.second);
+    ACHK(c, hipGetLastError());
+    ACHK(c, hipEventRecord(ev[2], s));
+    return IOC_OK;
+}
+
+// Version 1 takes the pairs from order[n_v2] on: pairs with other letters, pairs the 16-bit window refused, the whole batch
+// should a bounded wait of version 2 run out, and everything under IOC_ALIGN_V1=1 or IOC_ALIGN_ARENA=fat.
+int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, const AlnParams& P, int32_t* d_score, uint32_t* d_count)
+{
+    hipStream_t s = c->stream;
+    const uint32_t np = uint32_t(b.dp.size());
+    int r;
+    uint64_t budget = 0;
+    if ((r = ck_budget(c, &budget)) != IOC_OK) return r;
+    const uint64_t lrow_stride = uint64_t((b.max_m + 64 * FW_C - 1) / (64 * FW_C)) * 64;  // int2 per pair
+    // (the forward pass addresses a pair's row checkpoints by a 32-bit offset in ints: 2^29 int2 units = 4 GB per pair,
+    // reads of ~260 kb against each other)
+    for (const AlnPairDev& d : b.dp)
+        if (v1_row_units(d) >= (uint64_t(1) << 29))
+            return ioc_fail(c, IOC_ERR_CAPACITY, "alignment of " + std::to_string(d.n) + " x " + std::to_string(d.m) + " bases: row checkpoints above 4 GB per pair");
+    const V1Plan pl = plan_v1(b, n_v2, budget);
+    const auto t_res0 = std::chrono::steady_clock::now();
+    if ((r = reserve(c, c->a_ck, size_t(pl.arena) * 8)) != IOC_OK) return r;
+    c->tm.align_arena_bytes = int64_t(pl.arena) * 8;
+    c->tm.align_slices = int32_t(pl.slices.size());
+    c->tm.align_version = 1;
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: checkpoint arena %.1f MB (%zu slice(s)) reserved in %.3f ms\n", double(pl.arena) * 8e-6, pl.slices.size(),
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_res0).count());
+    if ((r = reserve(c, c->a_cko, size_t(np) * sizeof(AlnCk))) != IOC_OK) return r;
+    if ((r = reserve(c, c->a_ends2, size_t(np) * sizeof(int4))) != IOC_OK) return r;
+    if ((r = reserve(c, c->a_lrow, size_t(pl.max_cnt) * lrow_stride * 8)) != IOC_OK) return r;
+    ACHK(c, hipMemcpyAsync(c->a_cko.p, pl.cko.data(), size_t(np) * sizeof(AlnCk), hipMemcpyHostToDevice, s));
+    const int n_cu = compute_units(c);
+    EventSet evs;
+    evs.v.assign(pl.slices.size() * 3, nullptr);
+    for (auto& e : evs.v) ACHK(c, hipEventCreate(&e));
+    for (size_t si = 0; si < pl.slices.size(); ++si)
+        if ((r = v1_slice(c, b, pl.slices[si], wp, P, n_cu, lrow_stride, d_score, d_count, &evs.v[3 * si])) != IOC_OK) return r;
+    ACHK(c, hipStreamSynchronize(s));
+    add_elapsed(c, evs.v, evs.v.size());
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: forward %.3f ms, traceback %.3f ms (device, all slices so far)\n", c->tm.ms_align_fwd, c->tm.ms_align_trace);
+    return IOC_OK;
+}
+
+// ---- 7. read back -------------------------------------------------------------------------------------------------------
+
+// what the corridor model learns from a batch (ioc_ctx::aln_fit): related pairs long enough to have had a corridor
+void learn_corridor(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, const std::vector<int32_t>& hs, const std::vector<uint32_t>& hc)
+{
+    if (c->aln_fit_sig[0] != P.match || c->aln_fit_sig[1] != P.mismatch || c->aln_fit_sig[2] != P.gap_extend) {
+        for (auto& f : c->aln_fit) f = ioc_ctx::CorridorFit();
+        c->aln_fit_sig[0] = P.match, c->aln_fit_sig[1] = P.mismatch, c->aln_fit_sig[2] = P.gap_extend;
+    }
+    for (size_t x = 0; x < b.dp.size(); ++x) {
+        const AlnPairDev& d = b.dp[x];
+        const uint32_t len = std::max(d.n, d.m);
+        if (hc[x] == 0xFFFFFFFFu || len < 4096u || !(d.e_sum > 0.0f) || std::min(d.n, d.m) * 10u < len * 9u) continue;
+        const double rho = double(hs[x]) / double(len), e = double(d.e_sum);
+        if (rho * 2.0 < double(P.match)) continue;  // (not a pair of one transcript)
+        ioc_ctx::CorridorFit& f = c->aln_fit[std::max(2, std::min(5, d.gap_open)) - 2];
+        if (f.n >= 1e6) continue;  // (enough)
+        f.n += 1.0, f.se += e, f.sr += rho, f.see += e * e, f.ser += e * rho, f.srr += rho * rho;
+        f.e_lo = std::min(f.e_lo, e), f.e_hi = std::max(f.e_hi, e);
+    }
+}
+
+// the statistics of the call and its answers (score, windows) on the host
+int read_results(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const int32_t* d_score, const uint32_t* d_count, std::vector<int32_t>& hs,
+                 std::vector<uint32_t>& hc)
+{
+    const uint32_t np = uint32_t(b.dp.size());
+    c->tm.n_align_pairs += np;
+    for (auto& d : b.dp) c->tm.n_align_cells += int64_t(d.n) * int64_t(d.m);
+    for (uint32_t x = n_v2; x < np; ++x)  // (version 1: every cell; version 2 counts its tiles)
+        c->tm.n_align_cells_computed += int64_t(b.dp[b.order[x]].n) * int64_t(b.dp[b.order[x]].m);
+    hs.resize(np);
+    hc.resize(np);
+    ACHK(c, hipMemcpyAsync(hs.data(), d_score, size_t(np) * 4, hipMemcpyDeviceToHost, c->stream));
+    ACHK(c, hipMemcpyAsync(hc.data(), d_count, size_t(np) * 4, hipMemcpyDeviceToHost, c->stream));
+    ACHK(c, hipStreamSynchronize(c->stream));
+    return IOC_OK;
+}
+
+// ---- 8. answers and re-runs ---------------------------------------------------------------------------------------------
+
+int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                const AlnOut& out, AlnRoute route);
+
+// the caller's pairs `idx` once more, by `route`, their answers in the caller's arrays
+int align_again(ioc_ctx* c, const ioc_aln_pair* pairs, const std::vector<int32_t>& idx, const AlnParams& P, AlnRoute route, const AlnOut& out)
+{
+    std::vector<ioc_aln_pair> sub(idx.size());
+    std::vector<int32_t> sc(idx.size());
+    std::vector<int64_t> sw(idx.size());
+    std::vector<double> sr(idx.size());
+    for (size_t x = 0; x < idx.size(); ++x) sub[x] = pairs[idx[x]];
+    const int r = align_pairs(c, int32_t(sub.size()), sub.data(), int32_t(P.k), P.match, P.mismatch, P.gap_extend, AlnOut{sc.data(), sw.data(), sr.data()}, route);
+    if (r != IOC_OK) return r;
+    for (size_t x = 0; x < idx.size(); ++x) out.set(size_t(idx[x]), sc[x], sw[x], sr[x]);
+    return IOC_OK;
+}
+
+// The answers into the caller's arrays; version 2's pairs that came back without one are run again.  The statistics count
+// the two re-runs differently (kept as they have always been): a pair the corridor could not vouch for counts once in
+// n_align_pairs / n_align_cells (its re-run's counts are taken back), a pair the 16-bit window refused counts twice there and
+// once more in n_align_refused.  align_version / align_slices / align_arena_bytes are the last run's, a re-run's included.
+int scatter_results(ioc_ctx* c, const AlnBatch& b, const ioc_aln_pair* pairs, bool v2, const AlnParams& P, const std::vector<int32_t>& hs,
+                    const std::vector<uint32_t>& hc, const AlnOut& out)
+{
+    std::vector<int32_t> again;       // pairs version 2 refused: scores outside its 16-bit window
+    std::vector<int32_t> again_full;  // pairs whose result the corridor cannot vouch for (V2Couple): every tile this time
+    for (size_t x = 0; x < b.dp.size(); ++x) {
+        const uint32_t i = b.back[x];
+        if (v2 && hc[x] == 0xFFFFFFFFu && hs[x] == INT32_MIN) {
+            again.push_back(int32_t(i));
+            continue;
+        }
+        if (v2 && hc[x] == 0xFFFFFFFFu && hs[x] == INT32_MIN + 1) {
+            again_full.push_back(int32_t(i));
+            continue;
+        }
+        out.set(i, hs[x], int64_t(hc[x]), double(hc[x]) / double(b.dp[x].n));  // getAlnRatio: aligned / slen
+    }
+    int r;
+    if (!again_full.empty()) {
+        const int64_t pairs_so_far = c->tm.n_align_pairs, cells_so_far = c->tm.n_align_cells;
+        if ((r = align_again(c, pairs, again_full, P, AlnRoute::every_tile, out)) != IOC_OK) return r;
+        c->tm.n_align_pairs = pairs_so_far;
+        c->tm.n_align_cells = cells_so_far;
+        if (getenv("IOC_TRACE")) fprintf(stderr, "[ioc]   aligner v2: %zu of %zu pairs run again without a corridor\n", again_full.size(), b.dp.size());
+    }
+    if (!again.empty()) {
+        if ((r = align_again(c, pairs, again, P, AlnRoute::v1_only, out)) != IOC_OK) return r;
+        c->tm.n_align_refused += int64_t(again.size());
+    }
+    return IOC_OK;
+}
+
+// Version 2 (ioc_align_v2.inc) takes the query-profile pairs: two pairs per wave, tiles scheduled by dataflow, coarse checkpoints.
+// IOC_ALIGN_V1=1 keeps everything on version 1.  IOC_ALIGN_ARENA=fat: a long-lived process that can spare the HBM (35 MB per
+// 16.7 kb pair, 56 GB for config 3's batch, allocated once and kept) takes version 1 — fine checkpoints straight from the forward
+// pass, a traceback half as long, ~6 % less time per batch.  The default is the lean version: a `cluster` process that starts by
+// allocating tens of GB pays seconds for the driver to hand them out.
+int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                const AlnOut& out, AlnRoute route)
+{
+    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs)) return IOC_ERR_ARG;
+    if (k < 1 || k > 32) return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: window length k must be in 1..32");
+    ACHK(c, hipSetDevice(c->device));
+    if (n_pairs == 0) return IOC_OK;
+    const AlnParams P{match, mismatch, gap_extend, uint32_t(k), 1u << (32 - k)};
+    AlnBatch b;
+    int r;
+    if ((r = prepare_pairs(c, n_pairs, pairs, P, out, b)) != IOC_OK) return r;
+    const uint32_t np = uint32_t(b.dp.size());
+    if (np == 0) return IOC_OK;
+    order_pairs(b, pairs);
+    const char* ev = getenv("IOC_ALIGN_VARIANT");
+    const bool carry = ev && strcmp(ev, "carry") == 0;
+    const WavePlan wp = plan_waves(b, carry);
+    if ((r = reserve(c, c->a_pairs, size_t(np) * sizeof(AlnPairDev))) != IOC_OK) return r;
+    if ((r = reserve(c, c->a_order, size_t(np) * 4)) != IOC_OK) return r;
+    if ((r = reserve(c, c->a_out, size_t(np) * 8)) != IOC_OK) return r;
+    ACHK(c, hipMemcpyAsync(c->a_pairs.p, b.dp.data(), size_t(np) * sizeof(AlnPairDev), hipMemcpyHostToDevice, c->stream));
+    ACHK(c, hipMemcpyAsync(c->a_order.p, b.order.data(), size_t(np) * 4, hipMemcpyHostToDevice, c->stream));
+    int32_t* d_score = static_cast<int32_t*>(c->a_out.p);
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(d_score + np);
+    const char* arena_mode = getenv("IOC_ALIGN_ARENA");
+    const bool v2 = route != AlnRoute::v1_only && !carry && !getenv("IOC_ALIGN_V1") && !(arena_mode && strcmp(arena_mode, "fat") == 0);
+    uint32_t n_v2 = 0;
+    if (v2 && (r = run_v2(c, b, P, d_score, d_count, route, &n_v2)) != IOC_OK) return r;
+    if (carry)
+        r = run_carry(c, b, wp.waves, P, d_score, d_count);
+    else if (n_v2 < np)
+        r = run_v1(c, b, n_v2, wp, P, d_score, d_count);
+    if (r != IOC_OK) return r;
+    std::vector<int32_t> hs;
+    std::vector<uint32_t> hc;
+    if ((r = read_results(c, b, n_v2, d_score, d_count, hs, hc)) != IOC_OK) return r;
+    // (the corridor model learns from the pairs of a call's own version-2 run, never from a re-run's)
+    if (v2 && route == AlnRoute::normal) learn_corridor(c, b, P, hs, hc);
+    return scatter_results(c, b, pairs, v2, P, hs, hc, out);
+}
+
 }  // namespace
-
-#define ACHK_UNUSED(c, call)                                                                             \
-    do {                                                                                          \
-        hipError_t e__ = (call);                                                                  \
-        if (e__ != hipSuccess)                                                                    \
-            return ioc_fail((c), IOC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-// set while pairs version 2 refused are re-run on version 1
-static thread_local bool g_force32 = false;
 
 extern "C" {
 
@@ -1877,485 +2548,7 @@ int ioc_align_set_verdict_threshold(ioc_ctx* c, double aligned_threshold)
 int ioc_align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
                     int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio)
 {
-    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs)) return IOC_ERR_ARG;
-    if (k < 1 || k > 32) return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: window length k must be in 1..32");
-    ACHK(c, hipSetDevice(c->device));
-    if (n_pairs == 0) return IOC_OK;
-    const int32_t n_seqs = c->aln_offs.empty() ? 0 : int32_t(c->aln_offs.size() - 1);
-    std::vector<AlnPairDev> dp;
-    std::vector<uint32_t> back;  // device pair -> caller pair
-    dp.reserve(size_t(n_pairs));
-    uint32_t max_n = 1, max_m = 1;
-    for (int32_t i = 0; i < n_pairs; ++i) {
-        const ioc_aln_pair& a = pairs[i];
-        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs)
-            return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
-        const int64_t n = c->aln_offs[size_t(a.query) + 1] - c->aln_offs[size_t(a.query)];
-        const int64_t m = c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)];
-        if (n + m >= (int64_t(1) << ALN_LEN_SHIFT))
-            return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: sequences above 2^26 bases");
-        const double limit = std::floor((1.0 - a.e) * double(k));  // getAlnRatio, cluster.cpp:446
-        const int32_t il = limit < -1.0 ? -1 : limit > 64.0 ? 64 : int32_t(limit);
-        if (n == 0 || m == 0) {
-            // nothing to align: the comparison string is n + m blanks
-            const int64_t len = n + m;
-            const int64_t cnt = (il <= 0 && len > k) ? len - k : 0;
-            if (out_score) out_score[i] = 0;
-            if (out_windows) out_windows[i] = cnt;
-            if (out_ratio) out_ratio[i] = n == 0 ? 0.0 : double(cnt) / double(n);
-            continue;
-        }
-        AlnPairDev d{};
-        d.q_off = uint32_t(c->aln_offs[size_t(a.query)]);
-        d.n = uint32_t(n);
-        d.r_off = uint32_t(c->aln_offs[size_t(a.ref)]);
-        d.m = uint32_t(m);
-        d.gap_open = ioc_host_gap_open(a.e);
-        d.e_sum = float(a.e);
-        d.ilimit = il;
-        d.rc = a.ref_revcomp ? 1u : 0u;
-        d.stop_at = 0;
-        if (c->aln_verdict_thr > 0.0 && n > 0) {
-            // smallest count a with double(a) / double(n) >= threshold: the comparison the caller will make (getAlnRatio / slen)
-            double a0 = std::ceil(c->aln_verdict_thr * double(n));
-            while (a0 > 0 && (a0 - 1.0) / double(n) >= c->aln_verdict_thr) a0 -= 1.0;
-            while (a0 / double(n) < c->aln_verdict_thr) a0 += 1.0;
-            d.stop_at = a0 >= 1.0 && a0 < 4.0e9 ? uint32_t(a0) : 0u;
-        }
-        {   // query-profile kernel: four-letter sequences, diagonal increments that fit a byte
-            const int gd = d.gap_open - gap_extend, cm = match + 2 * gap_extend + gd, cx = mismatch + 2 * gap_extend + gd;
-            const bool ok = !c->aln_other[size_t(a.query)] && !c->aln_other[size_t(a.ref)] && cm >= 0 && cm <= 255 &&
-                            cx >= 0 && cx <= 255 && !getenv("IOC_ALIGN_NO_PROFILE");
-            d.pad = ok ? 1u : 0u;
-        }
-        dp.push_back(d);
-        back.push_back(uint32_t(i));
-        max_n = std::max(max_n, d.n);
-        max_m = std::max(max_m, d.m);
-    }
-    const uint32_t np = uint32_t(dp.size());
-    if (np == 0) return IOC_OK;
-    // heaviest pairs first
-    std::vector<uint32_t> order(np);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        return uint64_t(dp[x].n) * dp[x].m > uint64_t(dp[y].n) * dp[y].m;
-    });
-    // Pairs with the same tile grid (coarse rows x strips) in the order of their summed error rates: a couple's corridor is as wide as
-    // its less similar pair needs (align_v2_run), so like goes with like.  Order only.
-    {
-        auto rows = [&](uint32_t x) { return uint64_t((dp[x].n + 511u) / 512u); };
-        auto cols = [&](uint32_t x) { return uint64_t((dp[x].m + 511u) / 512u); };
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-            const uint64_t tx = rows(x) * cols(x), ty = rows(y) * cols(y);
-            if (tx != ty) return tx > ty;  // (heaviest first, as before — by tiles)
-            if (rows(x) != rows(y)) return rows(x) > rows(y);
-            return dp[x].e_sum > dp[y].e_sum;
-        });
-    }
-    // The caller's similarity hints (ioc_aln_pair::reserved, 0 = none): pairs hinted far below the batch's median — a quarter of
-    // it — are taken for unrelated and sorted behind the others, so that version 2 couples them with each other: a couple with
-    // an unrelated pair gets no corridor, and a pair of one transcript coupled with it pays for every tile too (config 3: 19 %
-    // of the couples hold a wrong candidate when they are coupled by size alone, 10 % of the pairs are one).  Order only.
-    {
-        std::vector<int32_t> hp;
-        for (uint32_t x = 0; x < np; ++x)
-            if (pairs[back[x]].reserved > 0) hp.push_back(pairs[back[x]].reserved);
-        if (hp.size() >= 8 && !getenv("IOC_ALIGN_NO_HINTS")) {
-            std::nth_element(hp.begin(), hp.begin() + long(hp.size() / 2), hp.end());
-            const int64_t med = hp[hp.size() / 2];
-            std::stable_partition(order.begin(), order.end(), [&](uint32_t x) {
-                const int64_t h = pairs[back[x]].reserved;
-                return !(h > 0 && h * 4 < med);
-            });
-        }
-    }
-    // trace variant: the pairs of the query-profile kernel first, the comparing kernel's after them
-    std::stable_partition(order.begin(), order.end(), [&](uint32_t x) { return dp[x].pad != 0; });
-    const char* ev = getenv("IOC_ALIGN_VARIANT");
-    const bool carry = ev && strcmp(ev, "carry") == 0;
-    const uint32_t colsper = carry ? ALN_C : FW_C;
-    // waves per pair: few pairs -> wide workgroups (latency), many pairs -> narrow ones (no fill/drain waste)
-    uint32_t waves = ALN_MAXW;
-    if (const char* e = getenv("IOC_ALIGN_WAVES")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= ALN_MAXW) waves = uint32_t(v);
-    } else {
-        while (waves > 1 && uint64_t(np) * waves > 4096) waves >>= 1;
-        if (carry) {
-            while (waves > 1 && uint64_t(waves / 2) * 64 * colsper >= max_m) waves >>= 1;
-        } else {
-            // row bands x column strips run as a pipeline: it needs a few strips per band to fill, and
-            // whole tiles per band
-            const uint32_t strips = (max_m + 64 * FW_C - 1) / (64 * FW_C), tiles = (max_n + TILE - 1) / TILE;
-            while (waves > 1 && (strips < 2 * waves || tiles < 2 * waves)) waves >>= 1;
-        }
-    }
-    // a handful of long pairs (the later alignment rounds of a batch): 4-wave workgroups, several per pair (below)
-    const bool few_pairs = !carry && !getenv("IOC_ALIGN_WAVES") && np <= 64 && waves >= 4 && !getenv("IOC_ALIGN_NO_CROSS_TAIL");
-    if (few_pairs) waves = 4;
-    const uint32_t NT = waves * 64;
-    int r;
-    if ((r = reserve(c, c->a_pairs, size_t(np) * sizeof(AlnPairDev))) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_order, size_t(np) * 4)) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_out, size_t(np) * 8)) != IOC_OK) return r;
-    hipStream_t s = c->stream;
-    ACHK(c, hipMemcpyAsync(c->a_pairs.p, dp.data(), size_t(np) * sizeof(AlnPairDev), hipMemcpyHostToDevice, s));
-    ACHK(c, hipMemcpyAsync(c->a_order.p, order.data(), size_t(np) * 4, hipMemcpyHostToDevice, s));
-    AlnParams P{match, mismatch, gap_extend, uint32_t(k), 1u << (32 - k)};
-    int32_t* d_score = static_cast<int32_t*>(c->a_out.p);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(d_score + np);
-    // Version 2 (ioc_align_v2.inc) takes the query-profile pairs — the front of `order`: two pairs per wave, tiles scheduled
-    // by dataflow, coarse checkpoints.  IOC_ALIGN_V1=1 keeps everything on the first version (which also serves pairs with
-    // other letters, pairs the 16-bit window refuses, and the whole batch should a bounded wait of version 2 run out).
-    // IOC_ALIGN_ARENA=fat: a long-lived process that can spare the HBM (35 MB per 16.7 kb pair, 56 GB for config 3's batch,
-    // allocated once and kept) takes version 1 — fine checkpoints straight from the forward pass, a traceback half as long,
-    // ~6 % less time per batch.  The default is the lean version: a `cluster` process that starts by allocating tens of GB
-    // pays seconds for the driver to hand them out.
-    uint32_t n_v2 = 0;
-    const char* arena_mode = getenv("IOC_ALIGN_ARENA");
-    const bool v2 = !carry && !g_force32 && !getenv("IOC_ALIGN_V1") && !(arena_mode && strcmp(arena_mode, "fat") == 0);
-    if (v2) {
-        while (n_v2 < np && dp[order[n_v2]].pad != 0) ++n_v2;
-        bool fell_back = false;
-        if ((r = align_v2_run(c, dp, order.data(), n_v2, static_cast<const uint32_t*>(c->a_order.p), P, d_score, d_count, &fell_back)) != IOC_OK) return r;
-        if (fell_back) {
-            c->tm.n_align_refused += n_v2;
-            n_v2 = 0;
-        }
-    }
-    if (carry) {
-        const uint64_t bnd_stride = 2ull * 6ull * max_n;
-        const uint64_t lrow_entries = uint64_t((max_m + NT * ALN_C - 1) / (NT * ALN_C)) * NT;
-        const uint64_t lrow_stride = lrow_entries * 4ull;
-        // scratch is per workgroup; run in slices when the whole batch would not fit the budget
-        const uint64_t budget = 8ull << 30;
-        const uint64_t per_pair = (bnd_stride + lrow_stride) * 4ull;
-        const uint32_t slice = uint32_t(std::min<uint64_t>(np, std::max<uint64_t>(1, budget / per_pair)));
-        if ((r = reserve(c, c->a_bnd, size_t(slice) * bnd_stride * 4)) != IOC_OK) return r;
-        if ((r = reserve(c, c->a_lrow, size_t(slice) * lrow_stride * 4)) != IOC_OK) return r;
-        for (uint32_t first = 0; first < np; first += slice) {
-            const uint32_t cnt = std::min(slice, np - first);
-            hipLaunchKernelGGL(k_align_carry, dim3(cnt), dim3(NT), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p),
-                               static_cast<const uint32_t*>(c->a_order.p) + first, static_cast<const uint8_t*>(c->a_pool.p), P,
-                               static_cast<uint32_t*>(c->a_bnd.p), bnd_stride, static_cast<uint32_t*>(c->a_lrow.p),
-                               lrow_stride, d_score, d_count);
-            ACHK(c, hipGetLastError());
-        }
-    } else if (n_v2 < np) {
-        // checkpoint arena: slices of pairs (in `order`) whose checkpoints fit the budget together
-        size_t free_b = 0, total_b = 0;
-        ACHK(c, hipMemGetInfo(&free_b, &total_b));
-        uint64_t budget = uint64_t(free_b + c->a_ck.cap) / 2;
-        if (const char* e = getenv("IOC_ALIGN_CK_BUDGET_MB")) budget = uint64_t(atoll(e)) << 20;
-        auto row_units = [&](const AlnPairDev& d) { return uint64_t((d.n - 1) / TILE) * row_pitch(d.m); };
-        auto ck_units = [&](const AlnPairDev& d) { return row_units(d) + uint64_t((d.m - 1) / TILE) * col_pitch(d.n); };
-        const uint64_t lrow_stride = uint64_t((max_m + 64 * FW_C - 1) / (64 * FW_C)) * 64;  // int2 per pair
-        // (the forward pass addresses a pair's row checkpoints by a 32-bit offset in ints: 2^29 int2 units = 4 GB per pair,
-        // reads of ~260 kb against each other)
-        for (uint32_t x = 0; x < np; ++x)
-            if (row_units(dp[x]) >= (uint64_t(1) << 29))
-                return ioc_fail(c, IOC_ERR_CAPACITY, "alignment of " + std::to_string(dp[x].n) + " x " + std::to_string(dp[x].m) +
-                                                        " bases: row checkpoints above 4 GB per pair");
-        std::vector<AlnCk> cko(np);
-        std::vector<std::pair<uint32_t, uint32_t>> slices;  // [first, count) in `order`
-        uint64_t arena = 0;
-        for (uint32_t first = n_v2; first < np;) {
-            uint64_t used = 0;
-            uint32_t cnt = 0;
-            while (first + cnt < np) {
-                const AlnPairDev& d = dp[order[first + cnt]];
-                const uint64_t u = ck_units(d);
-                if (cnt > 0 && (used + u) * 8ull > budget) break;
-                if (cnt > 0 && d.pad != dp[order[first]].pad) break;  // one kernel per slice
-                // (rows first: their pitch is a multiple of 16 int2, `used` stays 16-byte aligned for the int4 stores)
-                cko[order[first + cnt]] = AlnCk{used, used + row_units(d)};
-                used += u;
-                ++cnt;
-            }
-            arena = std::max(arena, used);
-            slices.emplace_back(first, cnt);
-            first += cnt;
-        }
-        uint32_t max_cnt = 0;
-        for (auto& sl : slices) max_cnt = std::max(max_cnt, sl.second);
-        const auto t_res0 = std::chrono::steady_clock::now();
-        if ((r = reserve(c, c->a_ck, size_t(arena) * 8)) != IOC_OK) return r;
-        c->tm.align_arena_bytes = int64_t(arena) * 8;
-        c->tm.align_slices = int32_t(slices.size());
-        c->tm.align_version = 1;
-        if (getenv("IOC_TRACE"))
-            fprintf(stderr, "[ioc]   aligner: checkpoint arena %.1f MB (%zu slice(s)) reserved in %.3f ms\n", double(arena) * 8e-6, slices.size(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_res0).count());
-        if ((r = reserve(c, c->a_cko, size_t(np) * sizeof(AlnCk))) != IOC_OK) return r;
-        if ((r = reserve(c, c->a_ends2, size_t(np) * sizeof(int4))) != IOC_OK) return r;
-        if ((r = reserve(c, c->a_lrow, size_t(max_cnt) * lrow_stride * 8)) != IOC_OK) return r;
-        ACHK(c, hipMemcpyAsync(c->a_cko.p, cko.data(), size_t(np) * sizeof(AlnCk), hipMemcpyHostToDevice, s));
-        int n_cu = 256;
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-        if (n_cu < 1) n_cu = 256;
-        std::vector<hipEvent_t> evs(slices.size() * 3, nullptr);
-        for (auto& e : evs) ACHK(c, hipEventCreate(&e));
-        size_t evi = 0;
-        for (auto& sl : slices) {
-            const uint32_t* ord = static_cast<const uint32_t*>(c->a_order.p) + sl.first;
-            // Every workgroup lives for the whole launch (equal-sized pairs), so the launch ends with the
-            // fullest CU: cap the residency at ceil(workgroups / CUs) per CU with an LDS reservation, or the
-            // dispatcher may stack 8 workgroups on some CUs and leave others with 3.
-            const bool prof = dp[order[sl.first]].pad != 0;
-            const void* kfn = prof ? reinterpret_cast<const void*>(k_align_fwd<true>) : reinterpret_cast<const void*>(k_align_fwd<false>);
-            size_t lds_pad = 0;
-            const uint32_t wg_waves = waves > 4 ? waves : 4, ppw = wg_waves / waves;
-            uint32_t n_wg = (sl.second + ppw - 1) / ppw, n_main = n_wg, wpp_tail = waves;
-            {   // a second, partly filled generation of workgroups: give its pairs twice the waves
-                int occ = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, int(wg_waves * 64), 0) != hipSuccess) occ = 0;
-                (void)hipGetLastError();
-                const uint32_t gen = uint32_t(occ > 0 ? occ : 3) * uint32_t(n_cu);  // resident workgroups
-                if (n_wg > gen && n_wg < gen + gen / 2 && 2 * waves <= wg_waves) {
-                    n_main = gen;
-                    wpp_tail = 2 * waves;
-                    const uint32_t rest = sl.second - n_main * ppw, ppw_tail = wg_waves / wpp_tail;
-                    n_wg = n_main + (rest + ppw_tail - 1) / ppw_tail;
-                }
-            }
-            const uint32_t per_cu = (n_main + uint32_t(n_cu) - 1) / uint32_t(n_cu);
-            if (per_cu * wg_waves < 32) {
-                // per-workgroup LDS (static + reservation) halfway between 160 KB / (per_cu + 1) and 160 KB / per_cu
-                hipFuncAttributes fa{};
-                size_t stat = 48 * 1024;
-                if (hipFuncGetAttributes(&fa, kfn) == hipSuccess) stat = fa.sharedSizeBytes;
-                const size_t want = size_t(160u * 1024u) * (2 * per_cu + 1) / (2 * per_cu * (per_cu + 1));
-                lds_pad = want > stat + 1024 ? (want - stat - 512) & ~size_t(255) : 0;
-                // more than the default 64 KB per workgroup needs the kernel attribute (best effort)
-                size_t& lim = prof ? c->aln_lds_max : c->aln_lds_max2;
-                if (lim == 0) {
-                    int mx = 0;
-                    (void)hipDeviceGetAttribute(&mx, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device);
-                    lim = 64 * 1024 > stat ? 64 * 1024 - stat : 1;
-                    if (mx > 72 * 1024 && hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, mx - int(stat)) == hipSuccess)
-                        lim = size_t(mx) - stat;
-                    (void)hipGetLastError();
-                }
-                lds_pad = std::min(lds_pad, lim > 1 ? lim : 0);
-            }
-            ACHK(c, hipEventRecord(evs[evi++], s));
-            auto launch_fwd = [&](const uint32_t* o, uint32_t cnt, uint32_t wv, uint32_t wgw, uint32_t nwg, uint32_t nmain,
-                                  uint32_t wtail, size_t lds, int2* lr, const AlnCross& X) {
-                const AlnPairDev* dpairs = static_cast<const AlnPairDev*>(c->a_pairs.p);
-                const uint8_t* dpool = static_cast<const uint8_t*>(c->a_pool.p);
-                int2* dck = static_cast<int2*>(c->a_ck.p);
-                const AlnCk* dcko = static_cast<const AlnCk*>(c->a_cko.p);
-                int4* dends = static_cast<int4*>(c->a_ends2.p);
-                if (prof)
-                    hipLaunchKernelGGL(k_align_fwd<true>, dim3(nwg), dim3(wgw * 64), lds, s, dpairs, o, cnt, wv, nmain, wtail, dpool, P,
-                                       dck, dcko, lr, lrow_stride, dends, X);
-                else
-                    hipLaunchKernelGGL(k_align_fwd<false>, dim3(nwg), dim3(wgw * 64), lds, s, dpairs, o, cnt, wv, nmain, wtail, dpool, P,
-                                       dck, dcko, lr, lrow_stride, dends, X);
-            };
-            // The tail generation runs on a mostly empty chip: its pairs are split over SEVERAL workgroups each
-            // (4 x 4 = 16 bands on 4 CUs; an 8-wave workgroup lands on one CU, two waves per SIMD, and was slower),
-            // the first band of a workgroup waiting on a flag for the row checkpoints of the band above.  Its own
-            // launch: all its workgroups are resident together, and the waits are bounded anyway (then the pairs
-            // are simply done again the usual way).
-            uint32_t groups = 1;
-            // the whole slice the tail's way: forced (tests), or a handful of pairs on an otherwise idle chip
-            const bool force_cross = getenv("IOC_ALIGN_FORCE_CROSS") != nullptr || (few_pairs && waves == 4);
-            if (force_cross && wg_waves == 4) {
-                n_main = 0;
-                n_wg = 1;
-            }
-            // Default: in the SAME launch, behind the ordinary workgroups, so that a split pair starts on whatever CU
-            // frees up first (config 3: 105.2 -> 96.0 ms).  A launch of its own (one workgroup per CU by an LDS reservation) was
-            // measured slower — it cannot backfill, 112 ms — and is left to slices without ordinary workgroups (the forced split).
-            // IOC_ALIGN_NO_CROSS_TAIL=1 keeps the tail pairs whole with twice the waves (the first version).
-            // Workgroups of a launch are handed out in index order and a workgroup only waits for a smaller index;
-            // the split ones are at most two thirds of an XCD's slots, so they can never fill an XCD with waiters.
-            const bool inl = !force_cross;
-            if (n_main < n_wg && wg_waves == 4 && !getenv("IOC_ALIGN_NO_CROSS_TAIL")) {
-                const AlnPairDev& big = dp[order[sl.first]];
-                const uint32_t strips = (big.m + 64 * FW_C - 1) / (64 * FW_C), tiles = (big.n + TILE - 1) / TILE;
-                groups = force_cross ? 4 : 2;  // (behind a full generation 4 was measured slower: 99 ms)
-                if (const char* eg = getenv("IOC_ALIGN_CROSS_GROUPS")) groups = uint32_t(std::max(1, std::min(4, atoi(eg))));
-                while (groups > 1 && (strips < 4 * groups || tiles < 8 * groups)) groups >>= 1;  // bands = 4 * groups
-                const uint32_t rest = sl.second - n_main * ppw;
-                // one workgroup per CU (two on a CU run at half speed and hold up the whole chain of their pair), all
-                // resident together
-                // (in-launch: at most 2 split workgroups per CU's worth, i.e. 64 of an XCD's 96 slots — waiters cannot
-                // fill an XCD; a launch of its own: one per CU)
-                while (groups > 1 && uint64_t(rest) * groups > uint64_t(inl ? 2 : 1) * uint64_t(n_cu)) groups >>= 1;
-            }
-            if (groups > 1) {
-                const uint32_t first_cnt = n_main * ppw, rest = sl.second - first_cnt, nb = 4 * groups;
-                // flags are indexed [band][strip] with every pair's OWN strip count: a pair with fewer cells than the
-                // slice's first one may still have the longer reference, so the slot holds the largest count of the
-                // pairs that are actually split
-                uint32_t strips = 1;
-                for (uint32_t x = first_cnt; x < sl.second; ++x)
-                    strips = std::max(strips, (dp[order[sl.first + x]].m + 64 * FW_C - 1) / (64 * FW_C));
-                AlnCross X;
-                X.groups = groups;
-                X.flag_stride = nb * strips;
-                const size_t fbytes = size_t(rest) * X.flag_stride * 4, bbytes = size_t(rest) * nb * sizeof(int2);
-                if ((r = reserve(c, c->a_xflags, fbytes + bbytes + 64)) != IOC_OK) return r;
-                X.err = static_cast<uint32_t*>(c->a_xflags.p);
-                X.flags = X.err + 16;
-                X.best = reinterpret_cast<int2*>(reinterpret_cast<uint8_t*>(c->a_xflags.p) + 64 + fbytes);
-                ACHK(c, hipMemsetAsync(c->a_xflags.p, 0, 64 + fbytes, s));
-                if (inl && first_cnt) {
-                    // one launch: ordinary workgroups, then the split pairs behind them
-                    X.first_wg = n_main;
-                    X.first_pair = first_cnt;
-                    launch_fwd(ord, sl.second, waves, wg_waves, n_main + rest * groups, n_main + rest * groups, waves, lds_pad,
-                               static_cast<int2*>(c->a_lrow.p), X);
-                    ACHK(c, hipGetLastError());
-                    uint32_t xe = 0;
-                    ACHK(c, hipMemcpyAsync(&xe, X.err, 4, hipMemcpyDeviceToHost, s));
-                    ACHK(c, hipStreamSynchronize(s));
-                    if (xe) {
-                        launch_fwd(ord + first_cnt, rest, 4, 4, rest, rest, 4, 0, static_cast<int2*>(c->a_lrow.p) + uint64_t(first_cnt) * lrow_stride, AlnCross{});
-                        c->tm.n_align_refused += rest;
-                    }
-                } else {
-                if (first_cnt) launch_fwd(ord, first_cnt, waves, wg_waves, n_main, n_main, waves, lds_pad, static_cast<int2*>(c->a_lrow.p), AlnCross{});
-                ACHK(c, hipGetLastError());
-                size_t xlds = 0;  // more than half a CU's LDS: the dispatcher cannot stack two of them
-                {
-                    hipFuncAttributes fa{};
-                    size_t stat = 52 * 1024;
-                    if (hipFuncGetAttributes(&fa, kfn) == hipSuccess) stat = fa.sharedSizeBytes;
-                    size_t& lim = prof ? c->aln_lds_max : c->aln_lds_max2;
-                    if (lim == 0) {
-                        int mx = 0;
-                        (void)hipDeviceGetAttribute(&mx, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device);
-                        lim = 64 * 1024 > stat ? 64 * 1024 - stat : 1;
-                        if (mx > 72 * 1024 && hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, mx - int(stat)) == hipSuccess)
-                            lim = size_t(mx) - stat;
-                        (void)hipGetLastError();
-                    }
-                    const size_t want = 84 * 1024;
-                    if (want > stat && want - stat <= lim) xlds = (want - stat) & ~size_t(255);
-                }
-                launch_fwd(ord + first_cnt, rest, 4, 4, rest * groups, rest * groups, 4, xlds,
-                           static_cast<int2*>(c->a_lrow.p) + uint64_t(first_cnt) * lrow_stride, X);
-                ACHK(c, hipGetLastError());
-                uint32_t xerr = 0;
-                ACHK(c, hipMemcpyAsync(&xerr, X.err, 4, hipMemcpyDeviceToHost, s));
-                ACHK(c, hipStreamSynchronize(s));
-                if (xerr) {  // a wait ran out (the workgroups were not all resident): the tail again, the usual way
-                    launch_fwd(ord + first_cnt, rest, 4, 4, rest, rest, 4, 0,
-                               static_cast<int2*>(c->a_lrow.p) + uint64_t(first_cnt) * lrow_stride, AlnCross{});
-                    c->tm.n_align_refused += rest;
-                }
-                }
-            } else {
-                if (force_cross && n_main == 0) {  // (the forced split did not fit this slice)
-                    n_wg = (sl.second + ppw - 1) / ppw;
-                    n_main = n_wg;
-                }
-                launch_fwd(ord, sl.second, waves, wg_waves, n_wg, n_main, wpp_tail, lds_pad, static_cast<int2*>(c->a_lrow.p), AlnCross{});
-            }
-            ACHK(c, hipGetLastError());
-            ACHK(c, hipEventRecord(evs[evi++], s));
-            const uint32_t tr_wg = (sl.second + TR_WAVES - 1) / TR_WAVES;  // (an LDS reservation that caps the workgroups per CU changed nothing here)
-            hipLaunchKernelGGL(k_align_trace, dim3(tr_wg), dim3(64 * TR_WAVES), 0, s,
-                               static_cast<const AlnPairDev*>(c->a_pairs.p), ord, static_cast<const uint8_t*>(c->a_pool.p), P,
-                               static_cast<const int2*>(c->a_ck.p), static_cast<const AlnCk*>(c->a_cko.p),
-                               static_cast<const int4*>(c->a_ends2.p), d_score, d_count, sl.second);
-            ACHK(c, hipGetLastError());
-            ACHK(c, hipEventRecord(evs[evi++], s));
-        }
-        ACHK(c, hipStreamSynchronize(s));
-        for (size_t x = 0; x + 2 < evs.size() + 0 && x < evi; x += 3) {
-            float a = 0, b = 0;
-            if (hipEventElapsedTime(&a, evs[x], evs[x + 1]) == hipSuccess) c->tm.ms_align_fwd += a;
-            if (hipEventElapsedTime(&b, evs[x + 1], evs[x + 2]) == hipSuccess) c->tm.ms_align_trace += b;
-        }
-        if (getenv("IOC_TRACE"))
-            fprintf(stderr, "[ioc]   aligner: forward %.3f ms, traceback %.3f ms (device, all slices so far)\n", c->tm.ms_align_fwd, c->tm.ms_align_trace);
-        for (auto& e : evs) (void)hipEventDestroy(e);
-    }
-    c->tm.n_align_pairs += np;
-    for (auto& d : dp) c->tm.n_align_cells += int64_t(d.n) * int64_t(d.m);
-    for (uint32_t x = n_v2; x < np; ++x) c->tm.n_align_cells_computed += int64_t(dp[order[x]].n) * int64_t(dp[order[x]].m);  // (version 1: every cell; version 2 counts its tiles)
-    std::vector<int32_t> hs(np);
-    std::vector<uint32_t> hc(np);
-    ACHK(c, hipMemcpyAsync(hs.data(), d_score, size_t(np) * 4, hipMemcpyDeviceToHost, s));
-    ACHK(c, hipMemcpyAsync(hc.data(), d_count, size_t(np) * 4, hipMemcpyDeviceToHost, s));
-    ACHK(c, hipStreamSynchronize(s));
-    if (v2 && !g_no_corridor) {
-        // what the corridor model learns from this batch (ioc_ctx::aln_fit): related pairs long enough to have had a corridor
-        if (c->aln_fit_sig[0] != match || c->aln_fit_sig[1] != mismatch || c->aln_fit_sig[2] != gap_extend) {
-            for (auto& f : c->aln_fit) f = ioc_ctx::CorridorFit();
-            c->aln_fit_sig[0] = match, c->aln_fit_sig[1] = mismatch, c->aln_fit_sig[2] = gap_extend;
-        }
-        for (uint32_t x = 0; x < np; ++x) {
-            const AlnPairDev& d = dp[x];
-            const uint32_t len = std::max(d.n, d.m);
-            if (hc[x] == 0xFFFFFFFFu || len < 4096u || !(d.e_sum > 0.0f) || std::min(d.n, d.m) * 10u < len * 9u) continue;
-            const double rho = double(hs[x]) / double(len), e = double(d.e_sum);
-            if (rho * 2.0 < double(match)) continue;  // (not a pair of one transcript)
-            ioc_ctx::CorridorFit& f = c->aln_fit[std::max(2, std::min(5, d.gap_open)) - 2];
-            if (f.n >= 1e6) continue;  // (enough)
-            f.n += 1.0, f.se += e, f.sr += rho, f.see += e * e, f.ser += e * rho, f.srr += rho * rho;
-            f.e_lo = std::min(f.e_lo, e), f.e_hi = std::max(f.e_hi, e);
-        }
-    }
-    std::vector<int32_t> again;  // pairs version 2 refused: scores outside its 16-bit window
-    std::vector<int32_t> again_full;  // pairs whose result the corridor cannot vouch for (V2Couple): every tile this time
-    for (uint32_t x = 0; x < np; ++x) {
-        const uint32_t i = back[x];
-        if (v2 && hc[x] == 0xFFFFFFFFu && hs[x] == INT32_MIN) {
-            again.push_back(int32_t(i));
-            continue;
-        }
-        if (v2 && hc[x] == 0xFFFFFFFFu && hs[x] == INT32_MIN + 1) {
-            again_full.push_back(int32_t(i));
-            continue;
-        }
-        if (out_score) out_score[i] = hs[x];
-        if (out_windows) out_windows[i] = int64_t(hc[x]);
-        if (out_ratio) out_ratio[i] = double(hc[x]) / double(dp[x].n);  // getAlnRatio: aligned / slen
-    }
-    if (!again_full.empty()) {
-        std::vector<ioc_aln_pair> sub(again_full.size());
-        std::vector<int32_t> sc(again_full.size());
-        std::vector<int64_t> sw(again_full.size());
-        std::vector<double> sr(again_full.size());
-        for (size_t x = 0; x < again_full.size(); ++x) sub[x] = pairs[again_full[x]];
-        const int64_t pairs_so_far = c->tm.n_align_pairs, cells_so_far = c->tm.n_align_cells;  // (a pair counts once)
-        g_no_corridor = true;
-        const int rr = ioc_align_pairs(c, int32_t(sub.size()), sub.data(), k, match, mismatch, gap_extend, sc.data(), sw.data(), sr.data());
-        g_no_corridor = false;
-        if (rr != IOC_OK) return rr;
-        c->tm.n_align_pairs = pairs_so_far;
-        c->tm.n_align_cells = cells_so_far;
-        if (getenv("IOC_TRACE")) fprintf(stderr, "[ioc]   aligner v2: %zu of %u pairs run again without a corridor\n", again_full.size(), np);
-        for (size_t x = 0; x < again_full.size(); ++x) {
-            if (out_score) out_score[again_full[x]] = sc[x];
-            if (out_windows) out_windows[again_full[x]] = sw[x];
-            if (out_ratio) out_ratio[again_full[x]] = sr[x];
-        }
-    }
-    if (!again.empty()) {
-        std::vector<ioc_aln_pair> sub(again.size());
-        std::vector<int32_t> sc(again.size());
-        std::vector<int64_t> sw(again.size());
-        std::vector<double> sr(again.size());
-        for (size_t x = 0; x < again.size(); ++x) sub[x] = pairs[again[x]];
-        g_force32 = true;
-        const int rr = ioc_align_pairs(c, int32_t(sub.size()), sub.data(), k, match, mismatch, gap_extend, sc.data(), sw.data(), sr.data());
-        g_force32 = false;
-        if (rr != IOC_OK) return rr;
-        c->tm.n_align_refused += int64_t(again.size());
-        for (size_t x = 0; x < again.size(); ++x) {
-            if (out_score) out_score[again[x]] = sc[x];
-            if (out_windows) out_windows[again[x]] = sw[x];
-            if (out_ratio) out_ratio[again[x]] = sr[x];
-        }
-    }
-    return IOC_OK;
+    return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
 }
 
 // (ioc_ctx_prewarm)

@@ -254,15 +254,6 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
        uint32_t* __restrict__ arena, int2* __restrict__ lrow, int2* __restrict__ bandbest, uint32_t* __restrict__ ovf_out, int guard,
        const uint4* __restrict__ prof, unsigned long long* __restrict__ cells_done, uint32_t* __restrict__ prog, uint32_t prog_every)
 {
-    // debug marks in the control block behind `err` (words 2..11 of the block the queue counter heads): IOC_V2_PROGRESS
-#ifdef IOC_V2_MARKS
-#define V2_MARK(slot, val)                                                                                              \
-    do {                                                                                                                 \
-        __hip_atomic_store(&err[1 + (slot)], uint32_t(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
-    } while (0)
-#else
-#define V2_MARK(slot, val) do { } while (0)
-#endif
     __shared__ __attribute__((aligned(16))) uint32_t s_look_all[V2_WAVES][3][128];
     __shared__ __attribute__((aligned(16))) uint32_t s_prof_all[V2_WAVES][2][5][64][4];  // [wave][pair][base code][lane][4 words]
     __shared__ uint32_t s_par_all[V2_WAVES][VP_COUNT];
@@ -279,12 +270,8 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
         const uint32_t code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
         return code * 1024u;
     };
-#ifdef IOC_V2_MARKS
-    const unsigned long long tl0 = __builtin_amdgcn_s_memtime();
-#endif
     uint32_t it = v2_dequeue(queue);
     while (it < n_items) {
-        V2_MARK(0, it + 1u);
         uint32_t band, p, r_lo, nblk[2];
         bool vh[2], last_band[2];
         bool left_ok = true;  // (corridor: the tile to the left is computed, or this is strip 0)
@@ -314,9 +301,6 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
             }
             // the tile above and the tile to the left have published their checkpoints?  (a wait that ran out flags the launch: the
             // host runs the batch again the old way; the tile still runs, on whatever is there, so that nobody behind it waits for ever)
-#ifdef IOC_V2_MARKS
-            const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
-#endif
             // (corridor: a neighbour that is not computed is neither waited for nor read — its side of the tile is "no score")
             const bool top_in = band > 0 && p >= cp.plo[band - 1u] && p <= cp.phi[band - 1u];
             const bool left_in = p > cp.plo[band];
@@ -334,11 +318,7 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
             }
             if (left_in && !left_rows) (void)v2_wait(&flags[left_idx], err);
             if (left_rows) (void)v2_wait_rows(&prog[left_idx], &flags[left_idx], min(32u, nblk_band), err, left_avail);  // (the first two fetches: 128 rows)
-#ifdef IOC_V2_MARKS
-            if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(err + 11), __builtin_amdgcn_s_memtime() - tw0);  // cycles spent waiting for tiles
-#endif
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            V2_MARK(1, 0x100u + it);
             r_lo = uint32_t(cp.bstart[band]) * uint32_t(CK2);  // (both pairs: bands start on the same coarse rows)
             const uint32_t jb = p * strip_cols + lane * FW_C;
             uint32_t n[2], m[2], r_hi[2];
@@ -745,13 +725,10 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
         };
         {
             uint32_t s = 0;
-            V2_MARK(2, nsteps);
             for (; s + 1u < nsteps; s += 2) {
-                if ((s & 15u) == 0) V2_MARK(3, s + 1u);
                 step(s, std::true_type{});
                 step(s + 1u, std::false_type{});
             }
-            V2_MARK(4, s + 1u);
             for (; s < nsteps; ++s) step(s, std::true_type{});
         }
 #pragma unroll
@@ -777,14 +754,6 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
         __hip_atomic_store(&flags[my_flag], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (every lane the same word, the same value)
         it = v2_dequeue(queue);
     }
-#ifdef IOC_V2_MARKS
-    if (lane == 0) {
-        const unsigned long long tl = __builtin_amdgcn_s_memtime() - tl0;
-        atomicAdd(reinterpret_cast<unsigned long long*>(err + 13), tl);   // wave lifetimes
-        atomicMax(reinterpret_cast<unsigned long long*>(err + 9), tl);    // the longest one
-    }
-#endif
-#undef V2_MARK
 }
 
 #define V2_FWD_ARGS                                                                                                                        \

@@ -827,6 +827,33 @@ static uint32_t hash_shift(uint32_t cap)
     return 32 - bits;
 }
 
+// what ioc_score and the audit of ioc_count_reference_postings hand iock_score alike: the queries, the index, the candidate
+// tables and the context's settings (each caller adds its own)
+static IocScore score_args(ioc_ctx* c, uint32_t range)
+{
+    IocScore a{};
+    a.n = c->n;
+    a.L = uint32_t(c->L);
+    a.off_fwd = c->d_off_fwd;
+    a.off_rev = c->d_off_rev;
+    a.mins = c->d_min;
+    a.rows = c->b_rows.p;
+    a.cap = c->cap;
+    a.shift = hash_shift(c->cap);
+    a.post = c->b_post.p;
+    a.post16 = c->post16;
+    a.range = range;
+    a.keep = uint32_t(c->keep);
+    a.cand_key = P<uint32_t>(c->b_cand_key);
+    a.cand_size = P<uint32_t>(c->b_cand_size);
+    a.cand_count = P<uint32_t>(c->b_cand_count);
+    a.pmins = P<uint32_t>(c->b_pmins);
+    a.pbnd = P<uint32_t>(c->b_pbnd);
+    a.part32 = c->score_part32;
+    a.score_oob = c->score_oob;
+    return a;
+}
+
 int ioc_score(ioc_ctx* c)
 {
     if (!c) return IOC_ERR_ARG;
@@ -860,8 +887,7 @@ int ioc_score(ioc_ctx* c)
     const uint32_t range = env_u32("IOC_SCORE_RANGE", 8192);
     // XCD-partitioned scoring keeps 8 partial histograms per query (single-pass case only)
     uint32_t* d_part = nullptr;
-    iock_set_part32(int(env_u32("IOC_PART32", 0)));
-    iock_set_score_oob(c->score_oob);
+    c->score_part32 = int(env_u32("IOC_PART32", 0));
     const bool aln_mode_s = c->params.mode == IOC_MODE_SAHLIN || c->params.mode == IOC_MODE_FURIOUS;
     // Upper bounds of totalMapped (k_gap_bounds): the sweeps of ioc_resolve reject candidates by them, and in fast mode the
     // candidate lists are cut at the smallest Size that passes any bound of the query (below it nothing passes, and the top
@@ -876,17 +902,7 @@ int ioc_score(ioc_ctx* c)
     } else {
         c->gap_bound_gen = ~0ull;
     }
-    // (the launcher's per-thread settings are taken back on EVERY way out of this function, the error returns included)
-    struct ScoreSettings {
-        ~ScoreSettings()
-        {
-            iock_set_score_shard(1, 0);
-            iock_set_score_keep(nullptr);
-        }
-    } score_settings_guard;
-    iock_set_score_keep(c->keep_q_on ? P<uint32_t>(c->b_keep_q) : nullptr);
     c->scored_sharded = c->shard_world > 1 && c->shard_fn && !aln_mode_s;
-    iock_set_score_shard(c->scored_sharded ? c->shard_world : 1, c->shard_rank);
     if (env_u32("IOC_SCORE_PARTS", 1) == 1 && L + uint64_t(n) <= range && capacity * 8 * 4 + (1ull << 28) < have - need) {
         RESERVE(c, c->b_part, size_t(capacity) * 8 * 4);
         RESERVE(c, c->b_pmins, size_t(c->total) * 4);
@@ -897,13 +913,16 @@ int ioc_score(ioc_ctx* c)
         dev_free(c->b_part);
     }
     HIPCHK(c, hipEventRecord(c->ev[2], s));
-    HIPCHK(c, iock_score(s, n, uint32_t(L), c->d_off_fwd, c->d_off_rev, c->d_min, c->b_rows.p, c->cap,
-                         hash_shift(c->cap), c->b_post.p, range, uint32_t(c->keep),
-                         P<uint32_t>(c->b_cand_key), P<uint32_t>(c->b_cand_size), P<uint32_t>(c->b_cand_count),
-                         count_trav ? d_trav : nullptr, nullptr, nullptr, d_part, P<uint32_t>(c->b_top_all), c->post16,
-                         P<uint32_t>(c->b_pmins), P<uint32_t>(c->b_pbnd)));
-    iock_set_score_shard(1, 0);
-    iock_set_score_keep(nullptr);
+    IocScore a = score_args(c, range);
+    a.traversed = count_trav ? d_trav : nullptr;
+    a.part = d_part;
+    a.top_all = P<uint32_t>(c->b_top_all);
+    a.keep_q = c->keep_q_on ? P<uint32_t>(c->b_keep_q) : nullptr;
+    if (c->scored_sharded) {
+        a.own_stride = c->shard_world;
+        a.own_offset = c->shard_rank;
+    }
+    HIPCHK(c, iock_score(s, &a));
     HIPCHK(c, hipEventRecord(c->ev[3], s));
     if (count_trav) {
         unsigned long long t = 0;
@@ -1759,12 +1778,12 @@ int ioc_count_reference_postings(ioc_ctx* c, int64_t* n_postings)
     HIPCHK(c, hipMemsetAsync(d_sum, 0, 8, s));
     const uint8_t* valid = c->cur_valid == 0 ? P<uint8_t>(c->b_valid0) : P<uint8_t>(c->b_valid1);
     const uint32_t range = env_u32("IOC_SCORE_RANGE", 8192);
-    iock_set_score_oob(c->score_oob);
-    HIPCHK(c, iock_score(s, c->n, uint32_t(c->L), c->d_off_fwd, c->d_off_rev, c->d_min, c->b_rows.p, c->cap,
-                         hash_shift(c->cap), c->b_post.p, range, uint32_t(c->keep),
-                         P<uint32_t>(c->b_cand_key), P<uint32_t>(c->b_cand_size), P<uint32_t>(c->b_cand_count),
-                         nullptr, valid, d_sum, P<uint32_t>(c->b_part), nullptr, c->post16, P<uint32_t>(c->b_pmins),
-                         P<uint32_t>(c->b_pbnd)));
+    // (the audit visits every query and cuts no list: no shard, no keep_q)
+    IocScore a = score_args(c, range);
+    a.audit_valid = valid;
+    a.audit_sum = d_sum;
+    a.part = P<uint32_t>(c->b_part);
+    HIPCHK(c, iock_score(s, &a));
     unsigned long long h = 0;
     HIPCHK(c, hipMemcpyAsync(&h, d_sum, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));

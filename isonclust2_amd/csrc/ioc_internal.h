@@ -179,6 +179,7 @@ struct ioc_ctx {
     bool keep_q_on = false;          // the candidate lists of the last ioc_score were cut at b_keep_q
     std::vector<uint32_t> h_keep_q;  // host copy, fetched when a candidate table is exported
     int score_oob = 0, score_oob_probe = -1;  // k_score_part's variant and the probe behind it (ioc_ctx_create)
+    int score_part32 = 0;  // u32 partials forced (IOC_PART32) in the last ioc_score: ioc_count_reference_postings' audit uses it too
 };
 
 int ioc_fail(ioc_ctx* c, int code, const std::string& msg);

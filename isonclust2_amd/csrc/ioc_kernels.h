@@ -123,15 +123,33 @@ hipError_t iock_gather_lists(hipStream_t st, uint32_t nlists, const int64_t* src
                              const uint32_t* smin, const uint32_t* spos, uint32_t* dmin, uint32_t* dpos);
 hipError_t iock_pack_rows(hipStream_t st, uint32_t nslots, const uint32_t* keys, const uint32_t* off,
                           const uint32_t* cnt, const uint32_t* qinfo, void* rows);
-hipError_t iock_score(hipStream_t st, int n, uint32_t L, const int64_t* off_fwd, const int64_t* off_rev,
-                      const uint32_t* mins, const void* rows, uint32_t cap, uint32_t shift, const void* post,
-                      uint32_t range, uint32_t keep, uint32_t* cand_key, uint32_t* cand_size, uint32_t* cand_count,
-                      unsigned long long* traversed, const uint8_t* audit_valid, unsigned long long* audit_sum,
-                      uint32_t* part, uint32_t* top_all, int post16, uint32_t* pmins, uint32_t* pbnd);
+// ---- scoring (ioc_score.hip): the candidate lists of every query, or the audit sum of the reference postings ----
+struct IocScore {
+    int n;                        // queries
+    uint32_t L;                   // left clusters: query j is target L + j
+    const int64_t *off_fwd, *off_rev;
+    const uint32_t* mins;
+    const void* rows;             // the index: hash rows, capacity, hash shift, postings (u16 when post16)
+    uint32_t cap, shift;
+    const void* post;
+    int post16;
+    uint32_t range, keep;
+    uint32_t *cand_key, *cand_size, *cand_count;
+    unsigned long long* traversed = nullptr;  // postings visited (IOC_COUNT_TRAVERSED; null: not counted)
+    const uint8_t* audit_valid = nullptr;     // audit launch: the postings of these targets are summed into audit_sum
+    unsigned long long* audit_sum = nullptr;
+    uint32_t* part = nullptr;                 // XCD-partitioned path (with pmins and pbnd; null: the single-pass kernel)
+    uint32_t* top_all = nullptr;
+    uint32_t *pmins = nullptr, *pbnd = nullptr;
+    int part32 = 0;                           // u32 partials forced (IOC_PART32)
+    int score_oob = 0;                        // k_score_part without a window test (ioc_ctx_create's probe passed, or IOC_SCORE_OOB=1)
+    const uint32_t* keep_q = nullptr;         // per-query compaction threshold (fast mode; null: the uniform `keep`)
+    int own_stride = 1, own_offset = 0;       // sharded merge: this rank scores the queries j with j % own_stride == own_offset
+};
+hipError_t iock_score(hipStream_t st, const IocScore* a);
 hipError_t iock_gap_bounds(hipStream_t st, int n, const int64_t* off_fwd, const int64_t* off_rev, const uint32_t* pos,
                            const uint32_t* hpc_len, const uint8_t* err_cell, const int32_t* glim, uint2* out, const uint32_t* min_total,
                            uint32_t keep, uint32_t* keep_q);
-void iock_set_score_keep(const uint32_t* keep_q);
 hipError_t iock_decide_sweep(hipStream_t st, const void* args, int nblocks, int eval_blocks, uint32_t* q_count2);
 hipError_t iock_decide_phase2(hipStream_t st, const void* args, int nblocks, int eval_blocks, uint32_t* q_count2);
 hipError_t iock_copy_prefix_valid(hipStream_t st, int first, const uint8_t* vin, uint8_t* vout, uint32_t* ctl = nullptr);
@@ -144,9 +162,6 @@ hipError_t iock_query_table(hipStream_t st, int j, uint32_t L, const int64_t* of
                             const uint32_t* mins, const void* rows, uint32_t cap, uint32_t shift, const void* post,
                             const uint8_t* valid, uint32_t* hist, uint32_t* first, int post16);
 size_t iock_decide_args_size();
-void iock_set_part32(int v);
-void iock_set_score_oob(int v);
-void iock_set_score_shard(int stride, int offset);
 hipError_t iock_shard_mask_u8(hipStream_t st, uint8_t* a, uint8_t* b, int from, int n, int stride, int offset, uint32_t* ctl);
 hipError_t iock_shard_mask_i32(hipStream_t st, int32_t* a, int n, int stride, int offset);
 hipError_t iock_lds_oob_probe(hipStream_t st, uint32_t* d_result, uint32_t* h_result);

@@ -826,24 +826,7 @@ __global__ void __launch_bounds__(256) k_query_compact_many(const int32_t* __res
 // =====================================================================================================
 // launchers
 // =====================================================================================================
-static int g_part32 = 0;
-static int g_score_oob = 0;  // k_score_part without a window test (ioc_ctx_create's probe passed, or IOC_SCORE_OOB=1)
-// sharded merge: this rank scores the queries j with j % stride == offset 
-// (per calling thread: two contexts driven from two threads do not see each other's setting; ioc_score resets both through a
-// scope guard on every way out)
-static thread_local int g_own_stride = 1, g_own_offset = 0;
-static thread_local const uint32_t* g_keep_q = nullptr;  // per-query compaction threshold (fast mode; null: the uniform `keep`)
-
 extern "C" {
-
-void iock_set_part32(int v) { g_part32 = v; }
-void iock_set_score_oob(int v) { g_score_oob = v; }
-void iock_set_score_keep(const uint32_t* keep_q) { g_keep_q = keep_q; }
-void iock_set_score_shard(int stride, int offset)
-{
-    g_own_stride = stride > 1 ? stride : 1;
-    g_own_offset = stride > 1 ? offset : 0;
-}
 
 hipError_t iock_lds_oob_probe(hipStream_t st, uint32_t* d_result /* 2 words, zeroed here */, uint32_t* h_result)
 {
@@ -860,24 +843,23 @@ hipError_t iock_lds_oob_probe(hipStream_t st, uint32_t* d_result /* 2 words, zer
 }
 
 
-hipError_t iock_score(hipStream_t st, int n, uint32_t L, const int64_t* off_fwd, const int64_t* off_rev,
-                      const uint32_t* mins, const void* rows, uint32_t cap, uint32_t shift, const void* post_,
-                      uint32_t range, uint32_t keep, uint32_t* cand_key, uint32_t* cand_size, uint32_t* cand_count,
-                      unsigned long long* traversed, const uint8_t* audit_valid, unsigned long long* audit_sum,
-                      uint32_t* part, uint32_t* top_all, int post16, uint32_t* pmins, uint32_t* pbnd)
+hipError_t iock_score(hipStream_t st, const IocScore* a)
 {
-    const uint32_t* post = (const uint32_t*)post_;
-    const uint16_t* post_h = (const uint16_t*)post_;
+    const int n = a->n;
+    const uint32_t L = a->L;
     if (n <= 0) return hipSuccess;
     // sharded merge: one workgroup (or IOC_PARTS of them) per OWNED query; the others have no candidates here
-    const int own_s = audit_valid ? 1 : g_own_stride, own_o = audit_valid ? 0 : g_own_offset;  // (an audit launch visits every query)
+    const int own_s = a->own_stride, own_o = a->own_offset;
     const int nown = owned_count(0, n, own_s, own_o);
-    if (nown != n) CK(hipMemsetAsync(cand_count, 0, size_t(n) * 4, st));
+    if (nown != n) CK(hipMemsetAsync(a->cand_count, 0, size_t(n) * 4, st));
     if (nown <= 0) return hipSuccess;
     uint32_t tmax = L + uint32_t(n - 1);
-    uint32_t r = tmax < range ? (tmax ? tmax : 1) : range;
+    uint32_t r = tmax < a->range ? (tmax ? tmax : 1) : a->range;
     size_t lds = size_t(2) * r * 4;
-    if (part && pmins && pbnd && tmax <= range && cap >= 1024) {
+    const uint4* rows = (const uint4*)a->rows;
+    const uint32_t* post = (const uint32_t*)a->post;
+    const uint16_t* post_h = (const uint16_t*)a->post;
+    if (a->part && a->pmins && a->pbnd && tmax <= a->range && a->cap >= 1024) {
         const Epochs E = iock_epoch_bounds(L, uint32_t(n));
         if (lds > 40 * 1024) {
             CK(hipFuncSetAttribute((const void*)k_score_part<uint32_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
@@ -885,22 +867,22 @@ hipError_t iock_score(hipStream_t st, int n, uint32_t L, const int64_t* off_fwd,
             CK(hipFuncSetAttribute((const void*)k_score_part<uint16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
             CK(hipFuncSetAttribute((const void*)k_score_compact, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
         }
-        uint32_t* max_len = pbnd + size_t(n) * 2 * (IOC_PARTS + 1);  // one extra word behind the boundaries
-        CK(hipMemsetAsync(max_len, g_part32 ? 0xFF : 0, 4, st));  // IOC_PART32=1 forces u32 partials (tests)
-        hipLaunchKernelGGL(k_partition_mins, dim3(nown), dim3(IOC_BLOCK), 0, st, n, off_fwd, off_rev, mins, shift, pmins, pbnd,
+        uint32_t* max_len = a->pbnd + size_t(n) * 2 * (IOC_PARTS + 1);  // one extra word behind the boundaries
+        CK(hipMemsetAsync(max_len, a->part32 ? 0xFF : 0, 4, st));  // IOC_PART32=1 forces u32 partials (tests)
+        hipLaunchKernelGGL(k_partition_mins, dim3(nown), dim3(IOC_BLOCK), 0, st, n, a->off_fwd, a->off_rev, a->mins, a->shift, a->pmins, a->pbnd,
                            max_len, own_s, own_o);
 #define LAUNCH_PART(PT, OOB, PP)                                                                                          \
-    hipLaunchKernelGGL((k_score_part<PT, OOB>), dim3(unsigned(nown) * IOC_PARTS), dim3(IOC_BLOCK), lds / 2, st, n, L, off_fwd, \
-                       off_rev, pmins, pbnd, (const uint4*)rows, cap, shift, PP, part, E, traversed, max_len, uint32_t(lds / 2), own_s, own_o)
-        if (post16 && g_score_oob && IOC_SCORE_OOB)
+    hipLaunchKernelGGL((k_score_part<PT, OOB>), dim3(unsigned(nown) * IOC_PARTS), dim3(IOC_BLOCK), lds / 2, st, n, L, a->off_fwd, \
+                       a->off_rev, a->pmins, a->pbnd, rows, a->cap, a->shift, PP, a->part, E, a->traversed, max_len, uint32_t(lds / 2), own_s, own_o)
+        if (a->post16 && a->score_oob && IOC_SCORE_OOB)
             LAUNCH_PART(uint16_t, true, post_h);
-        else if (post16)
+        else if (a->post16)
             LAUNCH_PART(uint16_t, false, post_h);
         else
             LAUNCH_PART(uint32_t, false, post);   // (u32 postings keep their window test: flat_traverse)
 #undef LAUNCH_PART
-        hipLaunchKernelGGL(k_score_compact, dim3(nown), dim3(IOC_BLOCK), lds, st, n, L, part, keep, cand_key, cand_size,
-                           cand_count, audit_valid, audit_sum, top_all, max_len, own_s, own_o, audit_valid ? nullptr : g_keep_q);
+        hipLaunchKernelGGL(k_score_compact, dim3(nown), dim3(IOC_BLOCK), lds, st, n, L, a->part, a->keep, a->cand_key, a->cand_size,
+                           a->cand_count, a->audit_valid, a->audit_sum, a->top_all, max_len, own_s, own_o, a->keep_q);
         return hipGetLastError();
     }
     const Epochs E = iock_epoch_bounds(L, uint32_t(n));
@@ -908,11 +890,11 @@ hipError_t iock_score(hipStream_t st, int n, uint32_t L, const int64_t* off_fwd,
     do {                                                                                                             \
         if (lds > 48 * 1024)                                                                                         \
             CK(hipFuncSetAttribute((const void*)k_score_t<PT>, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds))); \
-        hipLaunchKernelGGL((k_score_t<PT>), dim3(nown), dim3(IOC_BLOCK), lds, st, n, L, off_fwd, off_rev, mins,   \
-                           (const uint4*)rows, cap, shift, PP, range, keep, cand_key, cand_size, cand_count,         \
-                           traversed, E, audit_valid, audit_sum, own_s, own_o, audit_valid ? nullptr : g_keep_q); \
+        hipLaunchKernelGGL((k_score_t<PT>), dim3(nown), dim3(IOC_BLOCK), lds, st, n, L, a->off_fwd, a->off_rev, a->mins,   \
+                           rows, a->cap, a->shift, PP, a->range, a->keep, a->cand_key, a->cand_size, a->cand_count,         \
+                           a->traversed, E, a->audit_valid, a->audit_sum, own_s, own_o, a->keep_q); \
     } while (0)
-    if (post16)
+    if (a->post16)
         LAUNCH_SCORE(uint16_t, post_h);
     else
         LAUNCH_SCORE(uint32_t, post);
