@@ -469,10 +469,24 @@ int ioc_cluster_consensus(ioc_ctx* ctx, const ioc_params* p, const char* table_p
 
 /* ---- a POA engine of its own behind those five operations (spoa is absent from the reference tree: parity with
  * spoa's alignments and consensus tie-breaks is unpinned).  Graphs and heaviest-bundle consensus on the host, the
- * sequence-to-graph DP (local alignment, convex gaps as two affine pieces, src/main.cpp:285-324: m 4, n -8, g -8, e -4,
- * q -20, c -1) on the GPU.  Limits: sequences <= 29 999 bases, <= 127 predecessors per node. ------------------- */
+ * sequence-to-graph DP (local, global or semi-global alignment — `cluster -A`, src/main.cpp:292-324 —, convex gaps as
+ * two affine pieces, src/main.cpp:285-290: m 4, n -8, g -8, e -4, q -20, c -1) on the GPU.  Limits: sequences
+ * <= 29 999 bases, <= 127 predecessors per node; scores are int32 (negative in global and semi-global alignment).
+ * The DP's rows: 0 = a virtual source, 1..R = the nodes in topological order; columns 0..L = the read;
+ * gap(k) = max(g + (k-1) e, q + (k-1) c).
+ *   local:        H >= 0 everywhere (row 0 and column 0: 0); the best cell of the matrix ends it; the walk ends at a 0.
+ *   global:       row 0: gap(j); column 0: the vertical moves from row 0; ends in column L of a sink (no out-edges);
+ *                 the walk ends at (0, 0): read bases left on row 0 are insertions (-1, pos), nodes on column 0 (node, -1).
+ *   semi-global:  row 0: gap(j); column 0: 0; ends in column L of any node or in any column of a sink; the walk ends on
+ *                 row 0 or column 0 (a read head left on row 0 is unaligned, as in local alignment).
+ * Among end cells the first maximum in (row, column) order wins.  A graph does not record the type that built it. ---- */
+#define IOC_POA_LOCAL 0       /* numbered like `cluster -A` (spoa kSW) */
+#define IOC_POA_GLOBAL 1      /* (kNW) */
+#define IOC_POA_SEMI_GLOBAL 2 /* (kOV) */
 typedef struct ioc_poa ioc_poa;
+/* ioc_poa_create: local alignment.  ioc_poa_create_mode: mode = IOC_POA_*, anything else IOC_ERR_ARG. */
 int ioc_poa_create(ioc_ctx* ctx, int32_t m, int32_t n, int32_t g, int32_t e, int32_t q, int32_t c, ioc_poa** out);
+int ioc_poa_create_mode(ioc_ctx* ctx, int32_t mode, int32_t m, int32_t n, int32_t g, int32_t e, int32_t q, int32_t c, ioc_poa** out);
 void ioc_poa_destroy(ioc_poa* poa);
 /* fills user + create / size / add / consensus / purge + spec of *ops (rep_changed is left to the caller) */
 void ioc_poa_bind(ioc_poa* poa, ioc_consensus_ops* ops);

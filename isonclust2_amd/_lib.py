@@ -121,7 +121,7 @@ SYMBOLS = [
     "ioc_cluster_batch", "ioc_cluster_merge", "ioc_cluster_resident", "ioc_host_align", "ioc_host_gap_open",
     "ioc_host_aln_ratio", "ioc_align_set_pool", "ioc_align_pairs", "ioc_set_aln_verdicts", "ioc_get_ties", "ioc_resident_set_sequences",
     "ioc_index_update", "ioc_left_export", "ioc_cluster_consensus",
-    "ioc_poa_create", "ioc_poa_destroy", "ioc_poa_bind", "ioc_poa_graph_export", "ioc_poa_last_alignment",
+    "ioc_poa_create", "ioc_poa_create_mode", "ioc_poa_destroy", "ioc_poa_bind", "ioc_poa_graph_export", "ioc_poa_last_alignment",
     "ioc_poa_graph_save", "ioc_poa_graph_load", "ioc_poa_graph_load_many", "ioc_gather_records_device", "ioc_queries_generation", "ioc_scored_candidates",
     "ioc_dist_unique_id", "ioc_dist_init", "ioc_dist_shutdown", "ioc_dist_info", "ioc_dist_allgather_device",
     "ioc_dist_allgatherv_device", "ioc_dist_allgather_i64", "ioc_dist_allgatherv_host", "ioc_dist_allreduce_max",
@@ -196,6 +196,7 @@ def load():
     L.ioc_cluster_consensus.argtypes = [vp, C.POINTER(Params), C.c_char_p, C.POINTER(LeftView), C.POINTER(BatchView),
                                         C.POINTER(ConsensusArgs), C.POINTER(ConsensusOps), pi32, pi8, C.POINTER(ClusterStats)]
     L.ioc_poa_create.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    L.ioc_poa_create_mode.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.ioc_poa_destroy.argtypes = [vp]
     L.ioc_poa_destroy.restype = None
     L.ioc_poa_bind.argtypes = [vp, C.POINTER(ConsensusOps)]

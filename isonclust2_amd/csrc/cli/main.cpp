@@ -447,6 +447,7 @@ static int main_cluster(int argc, char** argv)
         {"right-batch", required_argument, 0, 'r'}, {0, 0, 0, 0}};
     string left_path, right_path, out_path;
     int mode = None, min_cls = -1;
+    int spoa_algo = IOC_POA_LOCAL;  // (the reference's code default is 2, semi-global: DESIGN.md §9)
     bool min_purge = false, keep_seq = false;
     int o;
     while ((o = getopt_long(argc, argv, "Vdhvo:l:r:Qx:A:zjF:", lo, nullptr)) != -1) {
@@ -459,7 +460,11 @@ static int main_cluster(int argc, char** argv)
             case 'j': keep_seq = true; break;
             case 'F': min_cls = atoi(optarg); break;
             case 'x': mode = parse_mode(optarg); break;
-            case 'h': cerr << "isONclust2-hip cluster -l left.cer [-r right.cer] -o out.cer [-x fast|sahlin|furious] [-F n] [-z] [-j] [-v]" << endl; exit(0);
+            case 'A': spoa_algo = atoi(optarg); break;
+            case 'h':
+                cerr << "isONclust2-hip cluster -l left.cer [-r right.cer] -o out.cer [-x fast|sahlin|furious] [-A 0|1|2] [-F n] [-z] [-j] [-v]" << endl
+                     << "\t-A --spoa-algo  consensus alignment: 0 local (the default here; the reference's code defaults to 2), 1 global, 2 semi-global" << endl;
+                exit(0);
             default: break;
         }
     }
@@ -699,7 +704,12 @@ static int main_cluster(int argc, char** argv)
     } poa_guard{poa};
     if (cons_on) {
         if (mode == None) die("Invalid clustering mode: 3");
-        check(c, ioc_poa_create(c, 4, -8, -8, -4, -20, -1, &poa), "consensus engine");  // src/main.cpp:285-290
+        // -A as src/main.cpp:292-318 reads it: 0 local, 1 global, 2 semi-global, anything else local (its line names no algorithm then)
+        const int poa_type = (spoa_algo == IOC_POA_GLOBAL || spoa_algo == IOC_POA_SEMI_GLOBAL) ? spoa_algo : IOC_POA_LOCAL;
+        if (VERBOSE)
+            cerr << "Generating consensus using spoa algorithm: "
+                 << (spoa_algo == 0 ? "local" : spoa_algo == 1 ? "global" : spoa_algo == 2 ? "semi-global" : "") << endl;
+        check(c, ioc_poa_create_mode(c, poa_type, 4, -8, -8, -4, -20, -1, &poa), "consensus engine");  // src/main.cpp:285-290
         auto load_side = [&](int side, const decltype(left.ConsGs)& gs, size_t limit, const char* what) {
             std::vector<int32_t> ids;
             std::vector<const uint8_t*> ptr;

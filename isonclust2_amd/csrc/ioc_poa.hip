@@ -85,14 +85,18 @@ struct PoaJob {
     uint8_t* ebits;
     int4* carry;
     int4* tile_best;
-    int* best;  // score, row, column
+    int* best;  // score, row, column; [4..7] g, e, q, c (the host's: row 0 of global and semi-global alignment)
     int32_t* out_node;
     int32_t* out_pos;
     int32_t* out_n;
     int cap;
 };
+// (global and semi-global alignment, T = IOC_POA_GLOBAL / IOC_POA_SEMI_GLOBAL: base[R + 1 + r] = 1 when row r is a sink —
+// no out-edges —, right after the R + 1 bases; DESIGN.md 5.7 has the three types' boundaries and end cells)
 
-// row 0 = virtual source (H = 0: local alignment)
+// row 0 = virtual source: H = 0 (local alignment) or gap(j) = max(g + (j - 1) e, q + (j - 1) c), the read's prefix costs (global,
+// semi-global).  The gap scores come in the job's best block: the local instantiation keeps its signature, and so its code.
+template <int T>
 __global__ void k_poa_init(const PoaJob* __restrict__ jobs)
 {
     const PoaJob J = jobs[blockIdx.y];
@@ -102,7 +106,12 @@ __global__ void k_poa_init(const PoaJob* __restrict__ jobs)
     uint8_t* ebits = J.ebits;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < W) {
-        H[j] = 0;
+        if constexpr (T == IOC_POA_LOCAL) {
+            H[j] = 0;
+        } else {
+            const int* gs = J.best + 4;
+            H[j] = j == 0 ? 0 : max(gs[0] + (j - 1) * gs[1], gs[2] + (j - 1) * gs[3]);
+        }
         F1[j] = POA_NEG;
         F2[j] = POA_NEG;
         dirs[j] = SRC_STOP;
@@ -153,6 +162,9 @@ __device__ __forceinline__ void wave_prefix_max2(int& a, int& b)
 // rows 1..R = nodes in topological order; pred_off[r] .. pred_off[r+1]: predecessor ROWS of row r (row 0 for a
 // node without in-edges).  carry[cb][r] = (prefix max of Hn[x] - e x, of Hn[x] - c x, over all columns up to the
 // tile's last one; Hn and H of that last column): what the tile to the right needs of row r.
+// T, the alignment type, decides column 0 of the node rows (local and semi-global: H = 0, a stop; global: the vertical moves from
+// row 0), the floor of H (0 in local alignment only) and which cells may end the alignment (the tile's best cell is among those).
+template <int T>
 __global__ void __launch_bounds__(POA_THREADS)
 k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
 {
@@ -169,7 +181,7 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
     __shared__ int s_pred[POA_PRED_LDS], s_pslot[POA_PRED_LDS];
     __shared__ int s_base[POA_RB + 1], s_slot[POA_RB + 1];  // (one past the last row: read ahead, never used)
     __shared__ int s_red[3 * POA_WAVES];
-    __shared__ int4 s_rec[POA_RB + 1];  // per row: end of its predecessor list, base, plane row, first predecessor — what a wave fetches one row ahead
+    __shared__ int4 s_rec[POA_RB + 1];  // per row: end of its predecessor list, base (| sink << 8 unless local), plane row, first predecessor — what a wave fetches one row ahead
     const PoaJob J = jobs[blockIdx.y];
     const int R = J.R, L = J.L, nrb = J.nrb;
     const int cb_first = max(0, diag - nrb + 1), cb_last = min(J.ncb - 1, diag);
@@ -206,7 +218,10 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
     for (int t = tid; t < nrows; t += POA_THREADS) {
         s_base[t] = ((const GU8*)J.base)[r_lo + t];
         s_slot[t] = ((const GI32*)J.slot)[r_lo + t];
-        s_rec[t] = int4{pred_off[r_lo + t + 1], int(((const GU8*)J.base)[r_lo + t]), ((const GI32*)J.slot)[r_lo + t], pred[pred_off[r_lo + t]]};
+        const int sink = T != IOC_POA_LOCAL ? int(((const GU8*)J.base)[R + 1 + r_lo + t]) << 8 : 0;
+        s_rec[t] = int4{pred_off[r_lo + t + 1], int(((const GU8*)J.base)[r_lo + t]) | sink, ((const GI32*)J.slot)[r_lo + t], pred[pred_off[r_lo + t]]};
+        // (the left edge of the matrix: prefix maxima of nothing; its H is never read — the diagonal move needs j > 0 — whatever
+        // the type's column 0)
         const GI32* ci = cin_row + int64_t(r_lo + t) * 4;
         s_carry[0][t] = cb > 0 ? int4{ci[0], ci[1], ci[3], ci[2] | ((t + 1) << 2)} : int4{POA_NEG, POA_NEG, 0, (t + 1) << 2};
     }
@@ -220,7 +235,7 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
     int my_base = j > 0 ? seq[jj - 1] : 0;
     asm volatile("" : "+v"(my_base));  // loaded before the row loop starts: no memory-counter wait inside it
     __syncthreads();
-    int my_best = 0, my_r = 0, my_j = 0;
+    int my_best = T == IOC_POA_LOCAL ? 0 : POA_NEG, my_r = 0, my_j = 0;  // (global, semi-global: no end cell yet)
     // what the wave's next row starts with, fetched one step ahead: list bounds, base, first predecessor
     int pb = __builtin_amdgcn_readfirstlane(s_poff[0]), pe = __builtin_amdgcn_readfirstlane(s_poff[1]), bs = s_rec[0].y, pr0 = s_rec[0].w;
     int my_slot = s_rec[0].z;
@@ -244,21 +259,23 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
             const int r = r_lo + t;
             const int4 nx = s_rec[t + 1];  // the next row (made uniform at the end of the step: no wait for it up here)
             const int pe_nv = nx.x, bs_n = nx.y, slot_n = nx.z, pr0_n = nx.w;
-            int hn = 0, f1 = POA_NEG, f2 = POA_NEG;
+            // the floor of H: 0 in local alignment, and in column 0 of semi-global alignment (the graph's prefix is free); none
+            // elsewhere (global alignment's column 0 is the best vertical move from row 0)
+            int hn = (T == IOC_POA_LOCAL || (T == IOC_POA_SEMI_GLOBAL && j == 0)) ? 0 : POA_NEG, f1 = POA_NEG, f2 = POA_NEG;
             uint32_t d = SRC_STOP;
             {
                 uint32_t pw = 0, f1x = 0, f2x = 0, ft = 0;  // pw: the predecessors the three moves came from (0 on a chain row); ft: the tie bits
                 uint32_t f1p = 0, f2p = 0;
                 int dg = POA_NEG;
-                const int sc = (bs == my_base) ? S.m : S.n;
+                const int sc = ((T == IOC_POA_LOCAL ? bs : bs & 0xff) == my_base) ? S.m : S.n;
                 const int pr0u = __builtin_amdgcn_readfirstlane(pr0);
                 if (pe - pb == 1 && t > 0 && pr0u == r - 1) {
                     // the common row: ONE predecessor, the row above, in this tile — straight-line code (the general
                     // loop below spends more time in its branches than in its arithmetic); same values bit for bit
                     const int hu = ph, u1 = p1, u2 = p2;
                     const int hl = __builtin_amdgcn_update_dpp(edge_prev, hu, 0x138, 0xf, 0xf, false);  // wave_shr:1
-                    // (H of a row is >= 0: hl + sc, hu + g and hu + q are far above POA_NEG, the general loop's "is it better
-                    // than nothing" tests are true here)
+                    // (H of a row is far above POA_NEG — >= 0 in local alignment, >= minus a few gaps in the others: hl + sc,
+                    // hu + g and hu + q are too, the general loop's "is it better than nothing" tests are true here)
                     if (j > 0) dg = hl + sc;
                     const int o1 = hu + S.g, x1 = u1 + S.e;
                     f1 = max(o1, x1);
@@ -438,9 +455,19 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
                 asm volatile("" : "+s"(bd), "+s"(be), "+v"(o4), "+v"(o1));
                 *(GU32*)((GU8*)bd + o4) = d;
                 *((GU8*)be + o1) = uint8_t(eb);
-                if (h > my_best) {  // rows ascend in time: the first row wins ties (the column is the lane's own: set after the loop)
-                    my_best = h;
-                    my_r = r;
+                if constexpr (T == IOC_POA_LOCAL) {
+                    if (h > my_best) {  // rows ascend in time: the first row wins ties (the column is the lane's own: set after the loop)
+                        my_best = h;
+                        my_r = r;
+                    }
+                } else {
+                    // end cells only — global: column L of a sink row; semi-global: column L of any row, any column of a sink row
+                    const bool sink = (bs >> 8) != 0;
+                    const bool end = T == IOC_POA_GLOBAL ? (sink && j == W - 1) : (sink || j == W - 1);
+                    if (end && h > my_best) {
+                        my_best = h;
+                        my_r = r;
+                    }
                 }
                 if (tid == POA_CB - 1 || j == W - 1) {
                     GI32* co = cout_row + int64_t(r) * 4;
@@ -469,7 +496,7 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
     if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && diag == 10)
         printf("tile profile (wave %d, %d rows): predecessors %llu, scan + E %llu, stores %llu, waiting for the wave on the left %llu cycles\n", wave, nrows, tp[0], tp[1], tp[2], tp[3]);
 #endif
-    if (my_best > 0) my_j = j;
+    if (T == IOC_POA_LOCAL ? my_best > 0 : my_r > 0) my_j = j;
     // ---- the tile's best cell: maximum score, ties to the smallest row, then the smallest column ----
     auto better = [](int s1, int r1, int c1, int s2, int r2, int c2) {
         return s1 > s2 || (s1 == s2 && (r1 < r2 || (r1 == r2 && c1 < c2)));
@@ -505,23 +532,26 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
     }
 }
 
-// best cell of each job over its tiles: maximum score, ties to the smallest row, then the smallest column
+// best cell of each job over its tiles: maximum score, ties to the smallest row, then the smallest column.  Local alignment: a
+// score of 0 is no alignment, (0, 0, 0); the other types: a tile without an end cell reports (POA_NEG, 0, 0), and some tile has one.
+template <int T>
 __global__ void __launch_bounds__(256) k_poa_best(const PoaJob* __restrict__ jobs)
 {
     __shared__ int4 s_b[256];
     const PoaJob J = jobs[blockIdx.x];
     const int nt = J.nrb * J.ncb;
-    int4 b{0, 0, 0, 0};
+    constexpr bool any = T != IOC_POA_LOCAL;  // (whether ties are broken at every score)
+    int4 b{T == IOC_POA_LOCAL ? 0 : INT32_MIN, 0, 0, 0};
     for (int t = threadIdx.x; t < nt; t += 256) {
         const int4 x = J.tile_best[t];
-        if (x.x > b.x || (x.x == b.x && x.x > 0 && (x.y < b.y || (x.y == b.y && x.z < b.z)))) b = x;
+        if (x.x > b.x || (x.x == b.x && (any || x.x > 0) && (x.y < b.y || (x.y == b.y && x.z < b.z)))) b = x;
     }
     s_b[threadIdx.x] = b;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (int(threadIdx.x) < o) {
             const int4 x = s_b[threadIdx.x + o], y = s_b[threadIdx.x];
-            if (x.x > y.x || (x.x == y.x && x.x > 0 && (x.y < y.y || (x.y == y.y && x.z < y.z)))) s_b[threadIdx.x] = x;
+            if (x.x > y.x || (x.x == y.x && (any || x.x > 0) && (x.y < y.y || (x.y == y.y && x.z < y.z)))) s_b[threadIdx.x] = x;
         }
         __syncthreads();
     }
@@ -537,7 +567,10 @@ __global__ void __launch_bounds__(256) k_poa_best(const PoaJob* __restrict__ job
 // out_n = number of pairs.  One wave per alignment: every step is a chain of dependent loads (direction word,
 // then the predecessor it names), so the 64 lanes read the cells (r - k, j - k) ahead of the walk and the run of
 // plain diagonal steps through consecutive rows they confirm is emitted at once; whatever else comes next is
-// one ordinary step.
+// one ordinary step.  The walk ends on row 0 or at a stop (local alignment: anywhere; semi-global: column 0, so its walk ends on
+// row 0 or column 0 and a read head left on row 0 stays unaligned); global alignment has no stop in the node rows, and the read
+// bases left of the column it reaches row 0 in are insertions, (-1, column - 1) down to (-1, 0).
+template <int T>
 __global__ void __launch_bounds__(64) k_poa_trace(const PoaJob* __restrict__ jobs)
 {
     const PoaJob J = jobs[blockIdx.x];
@@ -619,6 +652,16 @@ __global__ void __launch_bounds__(64) k_poa_trace(const PoaJob* __restrict__ job
             const bool ext = state == 4 ? (eb >> 3) & 1u : (eb >> 4) & 1u;
             --j;
             if (!ext) state = 1;  // the gap was opened from Hn of the column to the left
+        }
+    }
+    if constexpr (T == IOC_POA_GLOBAL) {
+        if (r == 0) {  // (row 0's H is gap(j): one run of insertions; capacity R + L + 2 holds every node and base once)
+            const int k = min(j, cap - n);
+            for (int x = lane; x < k; x += 64) {
+                out_node[n + x] = -1;
+                out_pos[n + x] = j - 1 - x;
+            }
+            n += k;
         }
     }
     if (lane == 0) *J.out_n = n;
@@ -841,7 +884,7 @@ struct PGraph {
     // per predecessor entry besides (bases in row order, the plane row of each predecessor) — the batch layout copies
     // the five arrays as they are.
     std::vector<int32_t> p_poff, p_pred, p_slot, p_pslot;
-    std::vector<uint8_t> p_base;
+    std::vector<uint8_t> p_base, p_sink;  // (p_sink: 1 for a row without out-edges — where global / semi-global alignment ends)
     int32_t p_nkeep = 1, p_max_preds = 0;
     bool planned = false;
     void plan()
@@ -852,6 +895,7 @@ struct PGraph {
         p_poff.assign(size_t(R) + 2, 0);
         p_pred.clear();
         p_base.assign(size_t(R) + 1, 0);
+        p_sink.assign(size_t(R) + 1, 0);
         p_max_preds = 0;
         std::vector<uint8_t> keep(size_t(R) + 1, 0);
         keep[0] = 1;
@@ -859,6 +903,7 @@ struct PGraph {
             const int u = rank[size_t(i)];
             const int q = i + 1;
             p_base[size_t(q)] = uint8_t(base[size_t(u)]);
+            p_sink[size_t(q)] = out_head[size_t(u)] < 0 ? 1 : 0;
             p_max_preds = std::max(p_max_preds, in_deg[size_t(u)]);
             p_poff[size_t(q)] = int32_t(p_pred.size());
             if (in_head[size_t(u)] < 0) p_pred.push_back(0);
@@ -967,6 +1012,7 @@ struct PoaPending {
 struct ioc_poa {
     ioc_ctx* ctx = nullptr;
     PoaScores S{4, -8, -8, -4, -20, -1};
+    int type = IOC_POA_LOCAL;  // the alignment type of every batch (a graph does not record the type that built it)
     int pred_lds = POA_PRED_LDS;  // IOC_POA_PRED_LDS: a smaller staging area, for the tests of the overflow path
     std::map<int, PGraph> g[2];
     // additions not aligned yet: graphs are independent until somebody reads one, so additions are queued and the
@@ -1052,6 +1098,23 @@ struct HostJob {
     }
 };
 
+// the kernels of one batch, for alignment type T
+template <int T>
+int poa_launch(ioc_poa* p, hipStream_t s, const PoaJob* djobs, size_t K, int max_w, int max_diag, int max_ncb)
+{
+    hipLaunchKernelGGL(k_poa_init<T>, dim3(unsigned((max_w + 255) / 256), unsigned(K)), dim3(256), 0, s, djobs);
+    PCHK(p, hipGetLastError());
+    for (int dg = 0; dg < max_diag; ++dg) {  // one anti-diagonal of tiles (of every job) per launch
+        hipLaunchKernelGGL(k_poa_tile<T>, dim3(unsigned(std::min(max_ncb, dg + 1)), unsigned(K)), dim3(POA_THREADS), 0, s, djobs, dg, p->S, p->pred_lds);
+        PCHK(p, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_poa_best<T>, dim3(unsigned(K)), dim3(256), 0, s, djobs);
+    PCHK(p, hipGetLastError());
+    hipLaunchKernelGGL(k_poa_trace<T>, dim3(unsigned(K)), dim3(64), 0, s, djobs);
+    PCHK(p, hipGetLastError());
+    return IOC_OK;
+}
+
 // align every job's read to its graph: one batch of launches
 int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
 {
@@ -1111,6 +1174,7 @@ int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
             return o;
         };
         l.o_base = put8(G.p_base);
+        if (p->type != IOC_POA_LOCAL) small.insert(small.end(), G.p_sink.begin(), G.p_sink.end());  // (right after the bases)
         l.o_poff = put32(G.p_poff);
         l.o_pred = put32(G.p_pred);
         l.o_pslot = put32(G.p_pslot);
@@ -1119,7 +1183,9 @@ int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
         small.insert(small.end(), seq.begin(), seq.end());
         align16();
         l.o_best = small.size();
-        small.resize(small.size() + 16, 0);
+        small.resize(small.size() + 32, 0);
+        const int32_t gaps[4] = {p->S.g, p->S.e, p->S.q, p->S.c};  // (best[4..7]: row 0 of global / semi-global alignment)
+        memcpy(small.data() + l.o_best + 16, gaps, 16);
         l.o_n = small.size();
         small.resize(small.size() + 16, 0);
     }
@@ -1173,16 +1239,12 @@ int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
     PCHK(p, hipMemcpyAsync(p->d_jobs.p, dj.data(), K * sizeof(PoaJob), hipMemcpyHostToDevice, s));
     if (trace) PCHK(p, hipEventRecord(p->ev[1], s));
     const PoaJob* djobs = static_cast<const PoaJob*>(p->d_jobs.p);
-    hipLaunchKernelGGL(k_poa_init, dim3(unsigned((max_w + 255) / 256), unsigned(K)), dim3(256), 0, s, djobs);
-    PCHK(p, hipGetLastError());
-    for (int dg = 0; dg < max_diag; ++dg) {  // one anti-diagonal of tiles (of every job) per launch
-        hipLaunchKernelGGL(k_poa_tile, dim3(unsigned(std::min(max_ncb, dg + 1)), unsigned(K)), dim3(POA_THREADS), 0, s, djobs, dg, p->S, p->pred_lds);
-        PCHK(p, hipGetLastError());
+    switch (p->type) {
+        case IOC_POA_GLOBAL: r = poa_launch<IOC_POA_GLOBAL>(p, s, djobs, K, max_w, max_diag, max_ncb); break;
+        case IOC_POA_SEMI_GLOBAL: r = poa_launch<IOC_POA_SEMI_GLOBAL>(p, s, djobs, K, max_w, max_diag, max_ncb); break;
+        default: r = poa_launch<IOC_POA_LOCAL>(p, s, djobs, K, max_w, max_diag, max_ncb); break;
     }
-    hipLaunchKernelGGL(k_poa_best, dim3(unsigned(K)), dim3(256), 0, s, djobs);
-    PCHK(p, hipGetLastError());
-    hipLaunchKernelGGL(k_poa_trace, dim3(unsigned(K)), dim3(64), 0, s, djobs);
-    PCHK(p, hipGetLastError());
+    if (r != IOC_OK) return r;
     if (trace) PCHK(p, hipEventRecord(p->ev[2], s));
     std::vector<uint8_t> back(small.size());
     std::vector<int32_t> haln(tot_aln);
@@ -1563,13 +1625,21 @@ extern "C" {
 
 int ioc_poa_create(ioc_ctx* ctx, int32_t m, int32_t n, int32_t g, int32_t e, int32_t q, int32_t c, ioc_poa** out)
 {
+    return ioc_poa_create_mode(ctx, IOC_POA_LOCAL, m, n, g, e, q, c, out);
+}
+
+int ioc_poa_create_mode(ioc_ctx* ctx, int32_t mode, int32_t m, int32_t n, int32_t g, int32_t e, int32_t q, int32_t c, ioc_poa** out)
+{
     if (!ctx || !out) return IOC_ERR_ARG;
+    if (mode != IOC_POA_LOCAL && mode != IOC_POA_GLOBAL && mode != IOC_POA_SEMI_GLOBAL)
+        return ioc_fail(ctx, IOC_ERR_ARG, "POA alignment type: need 0 (local), 1 (global) or 2 (semi-global)");
     // the row scan computes horizontal gaps from H-without-gaps: valid when opening is no cheaper than extending
     if (!(g <= e && e <= 0 && q <= c && c <= 0 && n <= 0 && m >= 0))
         return ioc_fail(ctx, IOC_ERR_ARG, "POA scores: need m >= 0, n <= 0, g <= e <= 0, q <= c <= 0");
     ioc_poa* p = new ioc_poa;
     p->ctx = ctx;
     p->S = PoaScores{m, n, g, e, q, c};
+    p->type = mode;
     g_row_stats_on = getenv("IOC_TRACE") != nullptr;
     if (const char* e2 = getenv("IOC_POA_PRED_LDS")) p->pred_lds = std::max(1, std::min(POA_PRED_LDS, atoi(e2)));
     *out = p;
