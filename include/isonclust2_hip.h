@@ -267,6 +267,18 @@ uint32_t ioc_host_min_total(uint32_t hpc_len, double mapped_threshold);
 int ioc_host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match,
                    int32_t mismatch, int32_t gap_open, int32_t gap_extend, char* comp, int32_t comp_cap,
                    int32_t* score_out);
+/* The same aligner — same cells, same walk — returning the alignment itself: one operation byte per column of comp, in forward
+ * order, NUL-terminated (ops_cap >= qlen + rlen + 1); returns the length.
+ *   '='  query base and reference base, equal   (comp: 0x7C)      'I'  query base against a gap
+ *   'X'  query base and reference base, differ                    'D'  reference base against a gap
+ *   'i' / 'd'  the same as 'I' / 'D' in a free end gap; order: leading i, leading d, the walk, trailing i, trailing d
+ * comp is this string with '=' -> 0x7C and every other byte -> ' '.  This is what to diff against parasail's traceback. */
+int ioc_host_align_ops(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match,
+                       int32_t mismatch, int32_t gap_open, int32_t gap_extend, char* ops, int32_t ops_cap,
+                       int32_t* score_out);
+/* Run-length text of an operation string ("12=1X3I...", end gaps as runs of i / d), NUL-terminated; returns its length,
+ * IOC_ERR_CAPACITY if cap is too small (2 bytes per operation + 1 always suffice), IOC_ERR_ARG for a byte that is no operation. */
+int64_t ioc_host_ops_to_cigar(const char* ops, int64_t len, char* out, int64_t cap);
 int32_t ioc_host_gap_open(double e1_plus_e2);                     /* setGapOpen,  src/cluster.cpp:425-440 */
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
@@ -294,6 +306,18 @@ int ioc_align_set_pool(ioc_ctx* ctx, int32_t n_seqs, const char* seqs, const int
 int ioc_align_pairs(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
                     int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
                     double* out_ratio);
+/* ioc_align_pairs + the alignments themselves (the operation bytes of ioc_host_align_ops, byte for byte, relative to the
+ * reverse-complemented reference where ref_revcomp is set).  The bytes of pair i are out_ops[ops_off[i] .. ops_off[i + 1])
+ * — packed, forward order, not NUL-terminated; ops_off has n_pairs + 1 entries.  ops_cap >= ioc_align_ops_bound(...) (the sum
+ * over the pairs of query length + reference length; negative ioc_status for a pair outside the pool), else IOC_ERR_CAPACITY
+ * and nothing is written.  The counts are always exact: the verdict threshold below is not applied to this call (and stays
+ * set for the next ioc_align_pairs).  IOC_ALIGN_VARIANT=carry has no walk: this call takes the traced route regardless.
+ * Any of out_score / out_windows / out_ratio may be NULL.  The device buffer of the bytes shares the checkpoint arena's
+ * budget: a call whose bound does not fit beside the arena runs in slices. */
+int64_t ioc_align_ops_bound(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs);
+int ioc_align_pairs_ops(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
+                        int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
+                        double* out_ratio, char* out_ops, int64_t ops_cap, int64_t* ops_off);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

@@ -41,6 +41,30 @@ def host_min_total(hpc_len, thr=0.65):
     return int(_lib.load().ioc_host_min_total(int(hpc_len), float(thr)))
 
 
+def host_align_ops(query, ref, match=2, mismatch=-2, gap_open=3, gap_extend=1):
+    """ioc_host_align_ops: (operation bytes, score) of the host aligner — '=' 'X' 'I' 'D', free end gaps 'i' 'd'."""
+    buf, sc = C.create_string_buffer(len(query) + len(ref) + 1), C.c_int32(0)
+    n = _lib.load().ioc_host_align_ops(query, len(query), ref, len(ref), match, mismatch, gap_open, gap_extend, buf,
+                                       len(query) + len(ref) + 1, C.byref(sc))
+    if n < 0:
+        raise RuntimeError(f"ioc_host_align_ops failed ({n})")
+    return buf.raw[:n], sc.value
+
+
+def ops_to_cigar(ops):
+    """ioc_host_ops_to_cigar: run-length text of an operation string, e.g. b"==X=II" -> "2=1X1=2I"."""
+    out = C.create_string_buffer(2 * len(ops) + 1)
+    n = _lib.load().ioc_host_ops_to_cigar(bytes(ops), len(ops), out, len(out))
+    if n < 0:
+        raise ValueError(f"ioc_host_ops_to_cigar failed ({n})")
+    return out.raw[:n].decode()
+
+
+def ops_to_comp(ops):
+    """The comparison string of an operation string: '|' where the bases are equal, ' ' in every other column."""
+    return bytes(ops).translate(bytes(0x7C if b == 0x3D else 0x20 for b in range(256)))
+
+
 class Context:
     """One context per GPU (ioc_ctx)."""
 
@@ -215,19 +239,36 @@ class Context:
         """ioc_align_set_verdict_threshold: > 0 lets tracebacks stop once ratio >= thr is decided (windows / ratio become bounds)."""
         self._chk(self.L.ioc_align_set_verdict_threshold(self.h, float(thr)))
 
-    def align_pairs(self, pairs, k, match=2, mismatch=-2, gap_extend=1):
-        """ParasailAlign + getAlnRatio (src/cluster.cpp:408-459) for (query, ref, ref_revcomp, e[, hint]) tuples:
-        returns (score, qualifying windows, ratio) arrays."""
-        n = len(pairs)
-        arr = (_lib.AlnPair * max(n, 1))()
+    @staticmethod
+    def _aln_pairs(pairs):
+        arr = (_lib.AlnPair * max(len(pairs), 1))()
         for i, pr in enumerate(pairs):        # (a fifth element: the similarity hint, ioc_aln_pair::reserved)
             qi, ri, rc, e = pr[:4]
             arr[i].query, arr[i].ref, arr[i].ref_revcomp, arr[i].e = int(qi), int(ri), int(bool(rc)), float(e)
             arr[i].reserved = int(pr[4]) if len(pr) > 4 else 0
+        return arr
+
+    def align_pairs(self, pairs, k, match=2, mismatch=-2, gap_extend=1):
+        """ParasailAlign + getAlnRatio (src/cluster.cpp:408-459) for (query, ref, ref_revcomp, e[, hint]) tuples:
+        returns (score, qualifying windows, ratio) arrays."""
+        n = len(pairs)
+        arr = self._aln_pairs(pairs)
         score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
         self._chk(self.L.ioc_align_pairs(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32),
                                          _p(win, C.c_int64), _p(ratio, C.c_double)))
         return score, win, ratio
+
+    def align_pairs_ops(self, pairs, k, match=2, mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_ops: align_pairs plus the alignments themselves — returns (score, windows, ratio, [bytes per pair]),
+        the bytes as host_align_ops gives them.  Always exact counts (the verdict threshold is not applied)."""
+        n = len(pairs)
+        arr = self._aln_pairs(pairs)
+        bound = self._chk(self.L.ioc_align_ops_bound(self.h, n, arr))
+        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        ops, off = np.zeros(max(bound, 1), np.uint8), np.zeros(n + 1, np.int64)
+        self._chk(self.L.ioc_align_pairs_ops(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
+                                             _p(ratio, C.c_double), ops.ctypes.data, bound, _p(off, C.c_int64)))
+        return score, win, ratio, [ops[off[i]:off[i + 1]].tobytes() for i in range(n)]
 
     # ---- sort-stage feeders --------------------------------------------------------------------
     def qual_scores(self, offs, qual, k):

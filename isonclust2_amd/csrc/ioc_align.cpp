@@ -23,17 +23,16 @@ namespace {
 // direction bits of the traceback matrix, 1 byte per cell
 enum : uint8_t { H_DIAG = 0, H_FROM_E = 1, H_FROM_F = 2, H_MASK = 3, E_EXT = 4, F_EXT = 8 };
 
-}  // namespace
-
-extern "C" {
-
-// Semi-global alignment of query (rows) against ref (columns).  Writes the comparison string of the
-// whole alignment ('|' identical bases, ' ' otherwise, end-gap columns included) into comp (capacity
-// comp_cap >= qlen + rlen + 1) and returns its length, or a negative ioc_status.
-int ioc_host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match,
-                   int32_t mismatch, int32_t gap_open, int32_t gap_extend, char* comp, int32_t comp_cap,
-                   int32_t* score_out)
+// The aligner behind ioc_host_align and ioc_host_align_ops: one DP, one walk.  `comp` receives one byte per alignment column,
+// forward order, NUL-terminated — OPS: the operation bytes ('=' 'X' 'I' 'D', free end gaps 'i' 'd'), else the comparison
+// string ('|' where the operation is '=', ' ' everywhere else).  Returns the length, or a negative ioc_status.
+template <bool OPS>
+int host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match, int32_t mismatch, int32_t gap_open,
+               int32_t gap_extend, char* comp, int32_t comp_cap, int32_t* score_out)
 {
+    // what a column of each kind is written as
+    constexpr char C_EQ = OPS ? '=' : '|', C_X = OPS ? 'X' : ' ', C_I = OPS ? 'I' : ' ', C_D = OPS ? 'D' : ' ', C_EI = OPS ? 'i' : ' ',
+                   C_ED = OPS ? 'd' : ' ';
     if (!query || !ref || !comp || qlen < 0 || rlen < 0) return IOC_ERR_ARG;
     if (comp_cap < qlen + rlen + 1) return IOC_ERR_CAPACITY;
     const int n = qlen, m = rlen;
@@ -101,15 +100,15 @@ int ioc_host_align(const char* query, int32_t qlen, const char* ref, int32_t rle
     // traceback from (bi, bj); trailing end gaps first (they are the tail of the strings)
     std::string rev;
     rev.reserve(size_t(n + m));
-    for (int j = m; j > bj; --j) rev.push_back(' ');
-    for (int i = n; i > bi; --i) rev.push_back(' ');
+    for (int j = m; j > bj; --j) rev.push_back(C_ED);
+    for (int i = n; i > bi; --i) rev.push_back(C_EI);
     int i = bi, j = bj, state = 0;  // 0 = H, 1 = E, 2 = F
     while (i > 0 && j > 0) {
         const uint8_t t = tb[size_t(i) * size_t(m + 1) + size_t(j)];
         if (state == 0) {
             const uint8_t from = t & H_MASK;
             if (from == H_DIAG) {
-                rev.push_back(query[i - 1] == ref[j - 1] ? '|' : ' ');
+                rev.push_back(query[i - 1] == ref[j - 1] ? C_EQ : C_X);
                 --i;
                 --j;
             } else if (from == H_FROM_E) {
@@ -118,22 +117,66 @@ int ioc_host_align(const char* query, int32_t qlen, const char* ref, int32_t rle
                 state = 2;
             }
         } else if (state == 1) {
-            rev.push_back(' ');
+            rev.push_back(C_D);
             if (!(t & E_EXT)) state = 0;
             --j;
         } else {
-            rev.push_back(' ');
+            rev.push_back(C_I);
             if (!(t & F_EXT)) state = 0;
             --i;
         }
     }
-    for (; j > 0; --j) rev.push_back(' ');
-    for (; i > 0; --i) rev.push_back(' ');
+    for (; j > 0; --j) rev.push_back(C_ED);
+    for (; i > 0; --i) rev.push_back(C_EI);
     const int len = int(rev.size());
     if (len + 1 > comp_cap) return IOC_ERR_CAPACITY;
     for (int k = 0; k < len; ++k) comp[k] = rev[size_t(len - 1 - k)];
     comp[len] = 0;
     return len;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Semi-global alignment of query (rows) against ref (columns).  Writes the comparison string of the
+// whole alignment ('|' identical bases, ' ' otherwise, end-gap columns included) into comp (capacity
+// comp_cap >= qlen + rlen + 1) and returns its length, or a negative ioc_status.
+int ioc_host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match,
+                   int32_t mismatch, int32_t gap_open, int32_t gap_extend, char* comp, int32_t comp_cap,
+                   int32_t* score_out)
+{
+    return host_align<false>(query, qlen, ref, rlen, match, mismatch, gap_open, gap_extend, comp, comp_cap, score_out);
+}
+
+// The same cells and the same walk, one operation byte per column in place of '|' / ' ': '=' equal bases, 'X' different bases,
+// 'I' a query base against a gap (the walk's F state), 'D' a reference base against a gap (E state); 'i' / 'd' the same in a
+// free end gap.  Order of the end gaps: leading 'i's, leading 'd's, the walk, trailing 'i's, trailing 'd's.
+int ioc_host_align_ops(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match, int32_t mismatch,
+                       int32_t gap_open, int32_t gap_extend, char* ops, int32_t ops_cap, int32_t* score_out)
+{
+    return host_align<true>(query, qlen, ref, rlen, match, mismatch, gap_open, gap_extend, ops, ops_cap, score_out);
+}
+
+// Run-length text of an operation string ("12=1X3I", end gaps as runs of 'i' / 'd'), NUL-terminated.  Returns its length,
+// IOC_ERR_CAPACITY when cap cannot hold it with the terminator, IOC_ERR_ARG for a byte that is no operation.
+int64_t ioc_host_ops_to_cigar(const char* ops, int64_t len, char* out, int64_t cap)
+{
+    if (len < 0 || (len > 0 && !ops) || !out || cap < 1) return IOC_ERR_ARG;
+    int64_t w = 0;
+    for (int64_t a = 0; a < len;) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        int64_t b = a;
+        while (b < len && ops[b] == op) ++b;
+        const std::string run = std::to_string(b - a) + op;
+        if (w + int64_t(run.size()) + 1 > cap) return IOC_ERR_CAPACITY;
+        memcpy(out + w, run.data(), run.size());
+        w += int64_t(run.size());
+        a = b;
+    }
+    out[w] = 0;
+    return w;
 }
 
 // setGapOpen, src/cluster.cpp:425-440

@@ -14,6 +14,8 @@
 //                             sliding window counter.  Only ~(n + m) / 256 * 2 tiles are ever recomputed.
 //  * "carry" (IOC_ALIGN_VARIANT=carry) — single pass, every DP state carries the window statistics of its
 //      best path (~39 VALU per cell); kept as an independent cross-check of the trace variant.
+//      It has no walk: ioc_align_pairs_ops (the alignment itself as an operation string, written by the emitting variants of the
+//      walk kernels: OpsOut below) takes the trace formulation whatever IOC_ALIGN_VARIANT says.
 //
 // Mapping of the forward passes: one workgroup per pair, NT = 64 * waves threads.  Thread g owns C
 // consecutive columns of a strip of NT * C columns and walks down the rows skewed by g (systolic wavefront):
@@ -984,6 +986,65 @@ struct WinStat {
     }
 };
 
+// ioc_align_pairs_ops: where the walks write the alignment itself.  A pair's operation bytes ('=' 'X' 'I' 'D', end gaps 'i' 'd':
+// ioc_host_align_ops) go DOWNWARDS from the end of its region of query length + reference length bytes — the walk runs
+// backwards, so the bytes stand in forward order at the region's end — and the count comes out beside score and windows.
+struct AlnOpsDev {
+    uint8_t* buf;
+    const uint64_t* end;  // per pair: one past the last byte of its region
+    uint32_t* len;        // per pair: bytes written (0: the pair came back without an answer)
+};
+
+// The hooks of an emitting walk, beside the window counter's (push_run, push, blanks).  EMIT false: an empty object whose calls are
+// nothing at all — the walk's code is what it was.  The cursor is the same in every lane; global memory directly, plain vector
+// stores, no LDS.
+struct NoOpsDev {};
+template <bool EMIT>
+struct OpsOut {
+    using Dev = NoOpsDev;
+    __device__ __forceinline__ void begin(Dev, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void run(unsigned long long, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void step(uint8_t, uint32_t) {}
+    __device__ __forceinline__ void fill(uint8_t, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void end(Dev, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void none(Dev, uint32_t) {}
+};
+template <>
+struct OpsOut<true> {
+    using Dev = AlnOpsDev;
+    uint8_t* cur = nullptr;  // the lowest byte written so far
+    uint8_t* lo = nullptr;   // the region's first byte.  A walk never gets there before it ends — every column takes a base of the
+                             // query's or the reference's — unless it runs on a forward pass that was given up (a wait ran out: the
+                             // host throws the slice away): nothing is stored below `lo` then either.
+    __device__ __forceinline__ void begin(const Dev& od, uint32_t pid, uint32_t room)
+    {
+        cur = od.buf + od.end[pid];
+        lo = cur - room;
+    }
+    // a run of m <= 64 diagonal moves, bit x of `bits` = the x-th of them (in walk order) joins equal bases: one store by the wave
+    __device__ __forceinline__ void run(unsigned long long bits, uint32_t m, uint32_t lane)
+    {
+        if (lane < m && cur - 1 - lane >= lo) cur[-1 - int(lane)] = (bits >> lane) & 1ull ? uint8_t('=') : uint8_t('X');
+        cur -= m;
+    }
+    __device__ __forceinline__ void step(uint8_t op, uint32_t lane)  // one E ('D') or F ('I') move
+    {
+        if (lane == 0 && cur > lo) cur[-1] = op;
+        cur -= 1;
+    }
+    __device__ __forceinline__ void fill(uint8_t op, uint32_t g, uint32_t lane)  // g end-gap columns: a strided fill by the wave
+    {
+        const uint64_t room = uint64_t(cur > lo ? cur - lo : 0);
+        for (uint32_t x = lane; x < g && x < room; x += 64) cur[-1 - int64_t(x)] = op;
+        cur -= g;
+    }
+    __device__ __forceinline__ void end(const Dev& od, uint32_t pid, uint32_t lane)
+    {
+        if (lane == 0) od.len[pid] = cur >= lo ? uint32_t((od.buf + od.end[pid]) - cur) : 0xFFFFFFFFu;
+    }
+    __device__ __forceinline__ void none(const Dev& od, uint32_t pid) { od.len[pid] = 0u; }  // (one lane: the pair has no answer)
+};
+
 // Pass 2: one wave per pair.  Direction nibble of a cell: bits 0-1 = where H came from (0 diagonal with
 // identical bases, 3 diagonal with different bases, 1 E, 2 F), bit 2 = E extended, bit 3 = F extended.
 constexpr int TR_WAVES = 4;
@@ -995,198 +1056,17 @@ __device__ __forceinline__ void tr_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-__global__ void __launch_bounds__(64 * TR_WAVES)
-k_align_trace(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__ order, const uint8_t* __restrict__ pool,
-              AlnParams P, const int2* __restrict__ ck, const AlnCk* __restrict__ cko, const int4* __restrict__ ends,
-              int32_t* __restrict__ out_score, uint32_t* __restrict__ out_count, uint32_t count)
-{
-    // A workgroup is TR_WAVES = 4 independent waves, one pair each, with LDS of their own: a workgroup of four waves puts
-    // one on every SIMD of its CU, whereas one-wave workgroups were seen three to a SIMD on some CUs (each of them then
-    // half as fast: 14.5 against 7.6 ms) while other SIMDs held one.  No workgroup barrier anywhere: a wave only ever
-    // reads what it wrote itself, in program order.
-    __shared__ uint16_t dirs_all[TR_WAVES][TILE * TR_C / 4][64];  // TR_C nibbles per lane and row (TILE 128: used as bytes [row][lane])
-    __shared__ int2 s_left_all[TR_WAVES][TILE];
-    __shared__ uint32_t s_q_all[TR_WAVES][TILE];
-    const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));  // uniform: the pair's state stays in SGPRs
-    const uint32_t pslot = blockIdx.x * TR_WAVES + wv;
-    if (pslot >= count) return;
-    uint16_t(*dirs)[64] = dirs_all[wv];
-    int2* s_left = s_left_all[wv];
-    uint32_t* s_q = s_q_all[wv];
-    const uint32_t pid = order[pslot];
-    const AlnPairDev pr = pairs[pid];
-    const uint32_t n = pr.n, m = pr.m;
-    const int go = pr.gap_open, il = pr.ilimit;
-    const uint8_t* __restrict__ q = pool + pr.q_off;
-    const uint8_t* __restrict__ r = pool + pr.r_off;
-    const int2* __restrict__ rowck = ck + cko[pid].row_off;
-    const int2* __restrict__ colck = ck + cko[pid].col_off;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t k = P.k, kmask = k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
-    const int4 en = ends[pid];
-    uint32_t i = uint32_t(en.y), j = uint32_t(en.z);
-    int state = 0;  // 0 = H, 1 = E, 2 = F
-    WinStat ws;
-    ws.blanks((m - j) + (n - i), kmask, k, il);  // trailing end gaps are the tail of the string
-
-    while (i > 0 && j > 0) {
-        const uint32_t r0 = ((i - 1) / TILE) * TILE, c0 = ((j - 1) / TILE) * TILE;
-        const uint32_t rows = i - r0, cols = j - c0;
-        // The tile is recomputed on the forward pass's own SLANTED scores (see fwd_cells: X* = X + ge (i + j), Hq = H* - gd),
-        // exactly as the checkpoints hold them: a gap extension costs nothing, an opening is already inside Hq, so a cell is
-        // two max + max3 + add + sub, and every decision of the host aligner's cell is a comparison of the same operands
-        // (E extended <=> E* > Hq of the left cell; H from the diagonal <=> H* equals it, which wins ties, else from E if
-        // equal to E*, else from F) — 18 VALU per cell where the unslanted form took 24.  This kernel is bound by VALU
-        // issue on the SIMDs that hold two of its waves.
-        const int gd = go - P.gap_extend, ge = P.gap_extend;
-        int cm = P.match + 2 * ge + gd, cx = P.mismatch + 2 * ge + gd;
-        asm volatile("" : "+v"(cm), "+v"(cx));  // kept in VGPRs: the select below cannot take two scalars, and the compiler would copy them over in every step
-        for (uint32_t x = lane; x < rows; x += 64) {
-            s_q[x] = q[r0 + x];
-            int2 le{ge * int(r0 + x + 1) - gd, ALN_NEG};  // column 0: H = 0, no gap to extend
-            if (c0) le = colck[uint64_t(c0 / TILE - 1) * col_pitch(n) + r0 + x];  // (Hq, E*) as passed between lanes
-            s_left[x] = le;
-        }
-        const uint32_t jb = c0 + lane * TR_C;  // columns to the left of this lane's block
-        uint32_t rpk[1];
-        {
-            uint32_t w = 0;
-#pragma unroll
-            for (int e = 0; e < TR_C; ++e) w |= ref_byte(r, m, pr.rc, jb + e) << (8 * e);
-            rpk[0] = w;
-        }
-        int Hp[TR_C], F[TR_C];  // (Hq, F*) of the row above
-        int dg = ge * int(r0 + jb) - gd;  // Hq(r0, jb) where H = 0: row 0, or column 0
-        if (r0 == 0) {
-#pragma unroll
-            for (int c = 0; c < TR_C; ++c) {
-                Hp[c] = ge * int(jb + c + 1) - gd;
-                F[c] = ALN_NEG;
-            }
-        } else {
-            const int* roh = reinterpret_cast<const int*>(rowck + uint64_t(r0 / TILE - 1) * row_pitch(m));
-            const int* rof = roh + row_pitch(m);
-#pragma unroll
-            for (int c = 0; c < TR_C; ++c) {
-                int2 v{0, ALN_NEG};
-                if (jb + c < m) v = int2{roh[jb + c], rof[jb + c]};
-                Hp[c] = v.x;
-                F[c] = v.y;
-            }
-            if (jb > 0 && jb <= m) dg = roh[jb - 1];
-        }
-        tr_wave_sync();
-        const uint32_t nact = (cols + TR_C - 1) / TR_C;
-        const uint32_t nsteps = rows + nact - 1;
-        int out_h = 0, out_e = ALN_NEG;
-        uint32_t out_q = 0;
-        // lane 0's inputs of a step (left edge and query byte of row s) are read one step AHEAD, by every lane at one address,
-        // and enter the wave as the `old` operand of the shifts
-        int2 nle = s_left[0];
-        uint32_t nq = s_q[0];
-        auto tstep = [&](const uint32_t s) __attribute__((always_inline)) {
-            int hl = int(from_left_or(uint32_t(out_h), uint32_t(nle.x)));
-            int el = int(from_left_or(uint32_t(out_e), uint32_t(nle.y)));
-            uint32_t qc = from_left_or(out_q, nq);
-            {
-                const uint32_t sn = s + 1u < rows ? s + 1u : rows - 1u;  // (rows past the end are never looked at)
-                nle = s_left[sn];
-                nq = s_q[sn];
-            }
-            const int ri = int(s) - int(lane);
-            if (ri >= 0 && uint32_t(ri) < rows && lane < nact) {
-                const int hl_in = hl;
-                uint32_t bits = 0;
-#pragma unroll
-                for (int c = 0; c < TR_C; ++c) {
-                    const bool ex = el > hl;
-                    const int E = max(el, hl);
-                    const bool fx = F[c] > Hp[c];
-                    const int Fn = max(F[c], Hp[c]);
-                    const bool mt = qc == ((rpk[0] >> (8 * c)) & 0xFFu);
-                    const int hd = dg + (mt ? cm : cx);
-                    const int h = max(max(hd, E), Fn);
-                    // the host aligner's cell (ioc_align.cpp): H = diagonal, replaced by E if E > H, then by F if F > H
-                    const uint32_t from = h == hd ? (mt ? 0u : 3u << (4 * c)) : (h == E ? 1u << (4 * c) : 2u << (4 * c));
-                    bits |= from | (ex ? 4u << (4 * c) : 0u) | (fx ? 8u << (4 * c) : 0u);
-                    dg = Hp[c];
-                    Hp[c] = h - gd;
-                    F[c] = Fn;
-                    hl = h - gd;
-                    el = E;
-                }
-                dg = hl_in;
-                if (TR_C == 4)
-                    dirs[ri][lane] = uint16_t(bits);
-                else
-                    reinterpret_cast<uint8_t*>(&dirs[0][0])[uint32_t(ri) * 64u + lane] = uint8_t(bits);  // (TILE 128: a byte per lane and row, row-major)
-            }
-            out_h = hl;
-            out_e = el;
-            out_q = qc;
-        };
-        {   // two steps per iteration (the compiler does not unroll a loop with wave-level operations): fewer register copies
-            uint32_t s = 0;
-#if IOC_TR_STEP_UNROLL == 4
-            for (; s + 3u < nsteps; s += 4) {
-                tstep(s);
-                tstep(s + 1u);
-                tstep(s + 2u);
-                tstep(s + 3u);
-            }
-#endif
-            for (; s + 1u < nsteps; s += 2) {
-                tstep(s);
-                tstep(s + 1u);
-            }
-            if (s < nsteps) tstep(s);
-        }
-        tr_wave_sync();
-        // the host aligner's traceback loop inside this tile (identical in every lane)
-        while (i > r0 && j > c0) {
-            const uint32_t cj = j - c0 - 1;
-            const uint32_t ri = i - r0 - 1;
-            const uint32_t t = TR_C == 4 ? (uint32_t(dirs[ri][cj / TR_C]) >> (4 * (cj % TR_C))) & 0xFu
-                                         : (uint32_t(reinterpret_cast<const uint8_t*>(&dirs[0][0])[ri * 64u + cj / TR_C]) >> (4 * (cj % TR_C))) & 0xFu;
-            if (state == 0) {
-                // look ahead along the diagonal: lane l reads the cell l steps up-left; the run of diagonal moves
-                // from here on goes into the window counter at once
-                const bool inr = i - r0 > lane && j - c0 > lane;
-                uint32_t tl = 1u;
-                if (inr) {
-                    const uint32_t rl = ri - lane, cl = cj - lane;
-                    tl = (TR_C == 4 ? (uint32_t(dirs[rl][cl / TR_C]) >> (4 * (cl % TR_C)))
-                                    : (uint32_t(reinterpret_cast<const uint8_t*>(&dirs[0][0])[rl * 64u + cl / TR_C]) >> (4 * (cl % TR_C)))) & 3u;
-                }
-                const bool dgl = inr && (tl == 0u || tl == 3u);
-                const unsigned long long dm = __ballot(dgl);
-                const uint32_t run = ~dm ? uint32_t(__builtin_ctzll(~dm)) : 64u;
-                if (run > 0) {
-                    const unsigned long long mb = __ballot(dgl && tl == 0u) & (run == 64u ? ~0ull : ((1ull << run) - 1ull));
-                    ws.push_run(mb, run, kmask, k, il, lane);
-                    i -= run;
-                    j -= run;
-                } else {
-                    state = (t & 3u) == 1u ? 1 : 2;
-                }
-            } else if (state == 1) {
-                ws.push(0u, kmask, k, il);
-                if (!(t & 4u)) state = 0;
-                --j;
-            } else {
-                ws.push(0u, kmask, k, il);
-                if (!(t & 8u)) state = 0;
-                --i;
-            }
-        }
-        tr_wave_sync();
-    }
-    ws.blanks(i + j, kmask, k, il);  // leading end gaps
-    if (lane == 0) {
-        out_score[pid] = en.x;
-        out_count[pid] = ws.cnt;
-    }
-}
+#define ALN_TRACE_KERNEL k_align_trace
+#define ALN_TRACE_EMIT 0
+#include "ioc_align_trace.inc"
+#undef ALN_TRACE_KERNEL
+#undef ALN_TRACE_EMIT
+// the emitting variant (ioc_align_pairs_ops)
+#define ALN_TRACE_KERNEL k_align_trace_ops
+#define ALN_TRACE_EMIT 1
+#include "ioc_align_trace.inc"
+#undef ALN_TRACE_KERNEL
+#undef ALN_TRACE_EMIT
 
 // per sequence: does it hold a byte other than A C G T?  (The query-profile kernel knows four bases; a pair
 // with anything else — the host aligner matches any two equal bytes — takes the comparing kernel.)
@@ -1274,6 +1154,64 @@ int ck_budget(ioc_ctx* c, uint64_t* budget)
     ACHK(c, hipMemGetInfo(&free_b, &total_b));
     *budget = uint64_t(free_b + c->a_ck.cap) / 2;
     if (const char* e = getenv("IOC_ALIGN_CK_BUDGET_MB")) *budget = uint64_t(atoll(e)) << 20;
+    return IOC_OK;
+}
+
+// ---- the operation bytes of an emitting call (ioc_align_pairs_ops) ------------------------------------------------------
+
+// the caller's side, indexed by the caller's pair: pair i's bytes go to buf + base[i] (room: query length + reference length),
+// len[i] of them, in forward order; the public function packs them when the call is over
+struct AlnOpsHost {
+    uint8_t* buf;
+    const int64_t* base;
+    int64_t* len;
+    double* ms_copy;  // what the copies from the device took the host, and ...
+    int64_t* copied;  // ... how many bytes they were (IOC_TRACE)
+};
+
+// One run's side (version 2's, version 1's).  The pairs of a slice get consecutive regions of ONE device buffer, as large as the
+// largest slice needs — its bytes count against the checkpoint arena's budget (slice_couples, plan_v1) — and the buffer is
+// copied out after every slice.
+struct OpsRun {
+    const AlnOpsHost* host;
+    const uint32_t* back;       // device pair -> caller's pair
+    std::vector<uint64_t> end;  // per device pair: the end of its region within its slice's bytes
+    AlnOpsDev dev{};
+    std::vector<uint8_t> stage;
+    std::vector<uint32_t> len;
+};
+
+// the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled)
+int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes)
+{
+    const size_t np = o.end.size(), tab = (np * 12 + 15) & ~size_t(15);
+    const int r = reserve(c, c->a_ops, tab + size_t(max_slice_bytes));
+    if (r != IOC_OK) return r;
+    uint8_t* p = static_cast<uint8_t*>(c->a_ops.p);
+    o.dev = AlnOpsDev{p + tab, reinterpret_cast<const uint64_t*>(p), reinterpret_cast<uint32_t*>(p + np * 8)};
+    ACHK(c, hipMemcpyAsync(p, o.end.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+    return IOC_OK;
+}
+
+// after a slice: its pairs' bytes to the caller's regions.  A pair that came back without an answer (len 0: refused by the 16-bit
+// window or by the corridor's certificate; out of range: the walk of a forward pass that was given up) is left to its re-run.
+int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, uint32_t cnt, uint64_t bytes)
+{
+    ACHK(c, hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    o.len.resize(dp.size());
+    if (o.stage.size() < bytes) o.stage.resize(size_t(bytes));
+    ACHK(c, hipMemcpy(o.len.data(), o.dev.len, dp.size() * 4, hipMemcpyDeviceToHost));
+    ACHK(c, hipMemcpy(o.stage.data(), o.dev.buf, size_t(bytes), hipMemcpyDeviceToHost));
+    for (uint32_t x = 0; x < cnt; ++x) {
+        const uint32_t pid = ord[x], i = o.back[pid];
+        const uint64_t L = o.len[pid];
+        if (L == 0 || L > uint64_t(dp[pid].n) + dp[pid].m || L > o.end[pid]) continue;
+        memcpy(o.host->buf + o.host->base[i], o.stage.data() + (o.end[pid] - L), size_t(L));
+        o.host->len[i] = int64_t(L);
+    }
+    *o.host->ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *o.host->copied += int64_t(bytes);
     return IOC_OK;
 }
 
@@ -1518,16 +1456,18 @@ void plan_couples(V2Plan& pl, const std::vector<AlnPairDev>& dp, const uint32_t*
     }
 }
 
-// slices of couples whose checkpoints and query profiles fit the budget together
-void slice_couples(V2Plan& pl, uint64_t budget)
+// slices of couples whose checkpoints and query profiles — and, in an emitting call, the operation bytes of their pairs (cops:
+// per couple; empty otherwise) — fit the budget together
+void slice_couples(V2Plan& pl, uint64_t budget, const std::vector<uint64_t>& cops)
 {
     for (uint32_t first = 0; first < pl.ncouples;) {
         uint64_t used = 0;
         uint32_t k2 = first;
         uint64_t prof_used = 0;  // uint4 entries of query profiles in this slice (they used to be made for every couple of the call at once)
+        uint64_t ops_used = 0;
         while (k2 < pl.ncouples) {
-            const uint64_t prof_k = uint64_t(pl.cps[k2].nstrips) * 2u * 5u * 64u;
-            if (k2 != first && (used + pl.cwords[k2]) * 4ull + (prof_used + prof_k) * sizeof(uint4) > budget) break;
+            const uint64_t prof_k = uint64_t(pl.cps[k2].nstrips) * 2u * 5u * 64u, ops_k = cops.empty() ? 0u : cops[k2];
+            if (k2 != first && (used + pl.cwords[k2]) * 4ull + (prof_used + prof_k) * sizeof(uint4) + ops_used + ops_k > budget) break;
             V2Couple& cp = pl.cps[k2];
             cp.prof = prof_used;
             prof_used += prof_k;
@@ -1538,6 +1478,7 @@ void slice_couples(V2Plan& pl, uint64_t budget)
             for (int h = 0; h < 2; ++h)
                 if (cp.pid[h] != 0xFFFFFFFFu) pl.pck[cp.pid[h]] = V2PairCk{cp.rdat, cp.rbase, cp.cdat, cp.cbase, cp.mpad, cp.nq, uint32_t(h), k2};
             used += pl.cwords[k2];
+            ops_used += ops_k;
             ++k2;
         }
         pl.arena_words = std::max(pl.arena_words, used);
@@ -1683,8 +1624,9 @@ uint32_t v2_per_cu(const V2Plan& pl, size_t si, const V2Opts& o, bool few_couple
 
 // One slice's launches: profiles, probe, forward pass, ends, traceback (events ev[0 .. 3) around them), then its error word
 // (*xe: a bounded wait ran out) and computed cells.
+// `od`: an emitting call — the traceback launches are the emitting kernels, the same launches otherwise.
 int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Opts& o, const AlnParams& P, const uint32_t* d_order,
-             int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, uint32_t* xe)
+             int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, uint32_t* xe, const AlnOpsDev* od)
 {
     hipStream_t s = c->stream;
     const uint32_t k_first = pl.slices[si].first, n_couples = pl.slices[si].second;
@@ -1736,9 +1678,14 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     ACHK(c, hipEventRecord(ev[1], s));
     // the traceback in two launches: walks that need more than `deadline` blocks go on in the second one, with helper waves
     auto help = [&](hipStream_t hs, uint32_t* list, uint32_t which, uint32_t* gate) {
-        hipLaunchKernelGGL(k_trace2_help, dim3(n_help), dim3(64 * V2_HWAVES), 0, hs, d_pairs, d_order + first_pair, d_pool, P,
-                           static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.hscratch, t.resume,
-                           list, d_score, d_count, n_pairs, which, gate);
+        if (od)
+            hipLaunchKernelGGL(k_trace2_help_ops, dim3(n_help), dim3(64 * V2_HWAVES), 0, hs, d_pairs, d_order + first_pair, d_pool, P,
+                               static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.hscratch,
+                               t.resume, list, d_score, d_count, n_pairs, which, gate, *od);
+        else
+            hipLaunchKernelGGL(k_trace2_help, dim3(n_help), dim3(64 * V2_HWAVES), 0, hs, d_pairs, d_order + first_pair, d_pool, P,
+                               static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.hscratch,
+                               t.resume, list, d_score, d_count, n_pairs, which, gate);
     };
     if (o.side_help) {  // (issued before the first launch: its workgroups — a walker and ten helpers each — take their places first)
         ACHK(c, hipEventRecord(c->ev_side[0], s));
@@ -1749,9 +1696,14 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
         hipLaunchKernelGGL(k_trace2_gate, dim3(1), dim3(1), 0, s, t.early, t.gate, n_help);
         ACHK(c, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_trace2, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
-                       static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.resume, t.park, d_score,
-                       d_count, n_pairs, o.deadline, o.deadline_cycles);
+    if (od)
+        hipLaunchKernelGGL(k_trace2_ops, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
+                           static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.resume, t.park,
+                           d_score, d_count, n_pairs, o.deadline, o.deadline_cycles, *od);
+    else
+        hipLaunchKernelGGL(k_trace2, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
+                           static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.resume, t.park,
+                           d_score, d_count, n_pairs, o.deadline, o.deadline_cycles);
     ACHK(c, hipGetLastError());
     if (o.side_help) ACHK(c, hipStreamWaitEvent(s, c->ev_side[1], 0));  // (the two helper launches share the helpers' buffers)
     if (o.deadline) {  // (one workgroup per compute unit: a walker and its helpers fill one; more parked walks than that take turns)
@@ -1837,8 +1789,9 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
 // Version 2: the pairs order[0 .. cnt) (all of the query-profile kind, heaviest first) through k_fwd2 / k_fwd2_ends / k_trace2, with
 // the corridor (`corridor` false: every tile).  Returns IOC_OK with *fell_back = true when a bounded wait of the forward pass ran
 // out (the caller then runs the same pairs through version 1).
+// `ops`: an emitting call (null otherwise).
 int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* order, uint32_t cnt, const uint32_t* d_order,
-                 const AlnParams& P, int32_t* d_score, uint32_t* d_count, bool corridor, bool* fell_back)
+                 const AlnParams& P, int32_t* d_score, uint32_t* d_count, bool corridor, bool* fell_back, OpsRun* ops)
 {
     *fell_back = false;
     if (cnt == 0) return IOC_OK;
@@ -1862,7 +1815,23 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     pl.np = uint32_t(dp.size());
     pl.ncouples = (cnt + 1u) / 2u;
     plan_couples(pl, dp, order, corridor_model(c, P, corridor), band_target(pl.ncouples, o.few_limit, o.occ, o.n_cu));
-    slice_couples(pl, budget);
+    std::vector<uint64_t> cops;  // (emitting call) the operation bytes of a couple's pairs: query length + reference length each
+    if (ops) {
+        cops.assign(pl.ncouples, 0);
+        for (uint32_t x = 0; x < cnt; ++x) cops[x / 2u] += uint64_t(dp[order[x]].n) + dp[order[x]].m;
+    }
+    slice_couples(pl, budget, cops);
+    std::vector<uint64_t> slice_ops(pl.slices.size(), 0);
+    if (ops) {  // a slice's pairs, in the slice's order, one region behind the other
+        ops->end.assign(dp.size(), 0);
+        uint64_t most = 0;
+        for (size_t si = 0; si < pl.slices.size(); ++si) {
+            const uint32_t x0 = 2u * pl.slices[si].first, x1 = std::min(cnt, 2u * (pl.slices[si].first + pl.slices[si].second));
+            for (uint32_t x = x0; x < x1; ++x) ops->end[order[x]] = slice_ops[si] += uint64_t(dp[order[x]].n) + dp[order[x]].m;
+            most = std::max(most, slice_ops[si]);
+        }
+        if ((r = ops_reserve(c, *ops, most)) != IOC_OK) return r;
+    }
     const auto t_res0 = std::chrono::steady_clock::now();
     if ((r = reserve(c, c->a_ck, size_t(pl.arena_words) * 4)) != IOC_OK) return r;
     c->tm.align_arena_bytes = int64_t(pl.arena_words) * 4;
@@ -1898,7 +1867,11 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     bool bad = false;
     for (size_t si = 0; si < pl.slices.size() && !bad; ++si, evi += 3) {
         uint32_t xe = 0;
-        if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe)) != IOC_OK) return r;
+        if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe, ops ? &ops->dev : nullptr)) != IOC_OK) return r;
+        if (ops && !xe) {
+            const uint32_t x0 = 2u * pl.slices[si].first, x1 = std::min(cnt, 2u * (pl.slices[si].first + pl.slices[si].second));
+            if ((r = ops_fetch(c, *ops, dp, order + x0, x1 - x0, slice_ops[si])) != IOC_OK) return r;
+        }
         if ((r = v2_report(c, dp, order, pl, t, si, o.deadline)) != IOC_OK) return r;
         bad = xe != 0;
     }
@@ -1921,6 +1894,7 @@ struct AlnOut {
     int32_t* score;
     int64_t* windows;
     double* ratio;
+    const AlnOpsHost* ops = nullptr;  // an emitting call (ioc_align_pairs_ops): where the operation bytes go
     void set(size_t i, int32_t s, int64_t w, double r) const
     {
         if (score) score[i] = s;
@@ -1958,6 +1932,10 @@ int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const 
             const int64_t len = n + m;
             const int64_t cnt = (il <= 0 && len > k) ? len - k : 0;
             out.set(size_t(i), 0, cnt, n == 0 ? 0.0 : double(cnt) / double(n));
+            if (out.ops) {  // (all of it one free end gap)
+                memset(out.ops->buf + out.ops->base[i], n ? 'i' : 'd', size_t(len));
+                out.ops->len[i] = len;
+            }
             continue;
         }
         AlnPairDev d{};
@@ -1970,7 +1948,7 @@ int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const 
         d.ilimit = il;
         d.rc = a.ref_revcomp ? 1u : 0u;
         d.stop_at = 0;
-        if (c->aln_verdict_thr > 0.0 && n > 0) {
+        if (c->aln_verdict_thr > 0.0 && n > 0 && !out.ops) {  // (an emitting call is always exact)
             // smallest count a with double(a) / double(n) >= threshold: the comparison the caller will make (getAlnRatio / slen)
             double a0 = std::ceil(c->aln_verdict_thr * double(n));
             while (a0 > 0 && (a0 - 1.0) / double(n) >= c->aln_verdict_thr) a0 -= 1.0;
@@ -2065,14 +2043,15 @@ WavePlan plan_waves(const AlnBatch& b, bool carry)
 
 // 4. version 2 takes the query-profile pairs — the front of `order`; *n_v2: how many it answered (0 when a bounded wait ran out
 // and they all go to version 1)
-int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2)
+int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2, const AlnOpsHost* oh)
 {
     const uint32_t np = uint32_t(b.dp.size());
     uint32_t n = 0;
     while (n < np && b.dp[b.order[n]].pad != 0) ++n;
     bool fell_back = false;
+    OpsRun ops{oh, b.back.data()};
     const int r = align_v2_run(c, b.dp, b.order.data(), n, static_cast<const uint32_t*>(c->a_order.p), P, d_score, d_count, route != AlnRoute::every_tile,
-                               &fell_back);
+                               &fell_back, oh ? &ops : nullptr);
     if (r != IOC_OK) return r;
     if (fell_back) {
         c->tm.n_align_refused += n;
@@ -2134,28 +2113,36 @@ struct V1Plan {
     std::vector<std::pair<uint32_t, uint32_t>> slices;  // [first, count) in `order`
     uint64_t arena = 0;                                 // int2 units
     uint32_t max_cnt = 0;
+    std::vector<uint64_t> ops_end, slice_ops;           // (emitting call) per pair: the end of its region of operation bytes; per slice: its bytes
+    uint64_t ops_most = 0;
 };
 uint64_t v1_row_units(const AlnPairDev& d) { return uint64_t((d.n - 1) / TILE) * row_pitch(d.m); }
 
-V1Plan plan_v1(const AlnBatch& b, uint32_t n_v2, uint64_t budget)
+V1Plan plan_v1(const AlnBatch& b, uint32_t n_v2, uint64_t budget, bool emit)
 {
     const std::vector<AlnPairDev>& dp = b.dp;
     const uint32_t np = uint32_t(dp.size());
     V1Plan pl;
     pl.cko.resize(np);
+    if (emit) pl.ops_end.assign(np, 0);
     for (uint32_t first = n_v2; first < np;) {
-        uint64_t used = 0;
+        uint64_t used = 0, ops_used = 0;
         uint32_t cnt = 0;
         while (first + cnt < np) {
             const AlnPairDev& d = dp[b.order[first + cnt]];
             const uint64_t u = v1_row_units(d) + uint64_t((d.m - 1) / TILE) * col_pitch(d.n);
-            if (cnt > 0 && (used + u) * 8ull > budget) break;
+            const uint64_t ops_u = emit ? uint64_t(d.n) + d.m : 0u;
+            if (cnt > 0 && (used + u) * 8ull + ops_used + ops_u > budget) break;
             if (cnt > 0 && d.pad != dp[b.order[first]].pad) break;  // one kernel per slice
             // (rows first: their pitch is a multiple of 16 int2, `used` stays 16-byte aligned for the int4 stores)
             pl.cko[b.order[first + cnt]] = AlnCk{used, used + v1_row_units(d)};
             used += u;
+            ops_used += ops_u;
+            if (emit) pl.ops_end[b.order[first + cnt]] = ops_used;
             ++cnt;
         }
+        pl.slice_ops.push_back(ops_used);
+        pl.ops_most = std::max(pl.ops_most, ops_used);
         pl.arena = std::max(pl.arena, used);
         pl.slices.emplace_back(first, cnt);
         pl.max_cnt = std::max(pl.max_cnt, cnt);
@@ -2239,7 +2226,7 @@ int v1_cross_tail(ioc_ctx* c, const AlnBatch& b, const V1Fwd& fwd, const std::pa
 // one slice of version 1: the forward pass (ordinary workgroups, a partly filled second generation, or the split tail) and the
 // traceback, events ev[0 .. 3) around them
 int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>& sl, const WavePlan& wp, const AlnParams& P, int n_cu,
-             uint64_t lrow_stride, int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev)
+             uint64_t lrow_stride, int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, const AlnOpsDev* od)
 {
     hipStream_t s = c->stream;
     const uint32_t waves = wp.waves;
@@ -2316,9 +2303,14 @@ int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>&
     }
     ACHK(c, hipEventRecord(ev[1], s));
     const uint32_t tr_wg = (sl.second + TR_WAVES - 1) / TR_WAVES;  // (an LDS reservation that caps the workgroups per CU changed nothing here)
-    hipLaunchKernelGGL(k_align_trace, dim3(tr_wg), dim3(64 * TR_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), ord,
-                       static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<const int2*>(c->a_ck.p), static_cast<const AlnCk*>(c->a_cko.p),
-                       static_cast<const int4*>(c->a_ends2.p), d_score, d_count, sl.second);
+    if (od)
+        hipLaunchKernelGGL(k_align_trace_ops, dim3(tr_wg), dim3(64 * TR_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), ord,
+                           static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<const int2*>(c->a_ck.p), static_cast<const AlnCk*>(c->a_cko.p),
+                           static_cast<const int4*>(c->a_ends2.p), d_score, d_count, sl.second, *od);
+    else
+        hipLaunchKernelGGL(k_align_trace, dim3(tr_wg), dim3(64 * TR_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), ord,
+                           static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<const int2*>(c->a_ck.p), static_cast<const AlnCk*>(c->a_cko.p),
+                           static_cast<const int4*>(c->a_ends2.p), d_score, d_count, sl.second);
     ACHK(c, hipGetLastError());
     ACHK(c, hipEventRecord(ev[2], s));
     return IOC_OK;
@@ -2326,7 +2318,7 @@ int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>&
 
 // Version 1 takes the pairs from order[n_v2] on: pairs with other letters, pairs the 16-bit window refused, the whole batch
 // should a bounded wait of version 2 run out, and everything under IOC_ALIGN_V1=1 or IOC_ALIGN_ARENA=fat.
-int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, const AlnParams& P, int32_t* d_score, uint32_t* d_count)
+int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, const AlnParams& P, int32_t* d_score, uint32_t* d_count, const AlnOpsHost* oh)
 {
     hipStream_t s = c->stream;
     const uint32_t np = uint32_t(b.dp.size());
@@ -2339,7 +2331,12 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
     for (const AlnPairDev& d : b.dp)
         if (v1_row_units(d) >= (uint64_t(1) << 29))
             return ioc_fail(c, IOC_ERR_CAPACITY, "alignment of " + std::to_string(d.n) + " x " + std::to_string(d.m) + " bases: row checkpoints above 4 GB per pair");
-    const V1Plan pl = plan_v1(b, n_v2, budget);
+    V1Plan pl = plan_v1(b, n_v2, budget, oh != nullptr);
+    OpsRun ops{oh, b.back.data()};
+    if (oh) {
+        ops.end.swap(pl.ops_end);
+        if ((r = ops_reserve(c, ops, pl.ops_most)) != IOC_OK) return r;
+    }
     const auto t_res0 = std::chrono::steady_clock::now();
     if ((r = reserve(c, c->a_ck, size_t(pl.arena) * 8)) != IOC_OK) return r;
     c->tm.align_arena_bytes = int64_t(pl.arena) * 8;
@@ -2356,8 +2353,10 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
     EventSet evs;
     evs.v.assign(pl.slices.size() * 3, nullptr);
     for (auto& e : evs.v) ACHK(c, hipEventCreate(&e));
-    for (size_t si = 0; si < pl.slices.size(); ++si)
-        if ((r = v1_slice(c, b, pl.slices[si], wp, P, n_cu, lrow_stride, d_score, d_count, &evs.v[3 * si])) != IOC_OK) return r;
+    for (size_t si = 0; si < pl.slices.size(); ++si) {
+        if ((r = v1_slice(c, b, pl.slices[si], wp, P, n_cu, lrow_stride, d_score, d_count, &evs.v[3 * si], oh ? &ops.dev : nullptr)) != IOC_OK) return r;
+        if (oh && (r = ops_fetch(c, ops, b.dp, b.order.data() + pl.slices[si].first, pl.slices[si].second, pl.slice_ops[si])) != IOC_OK) return r;
+    }
     ACHK(c, hipStreamSynchronize(s));
     add_elapsed(c, evs.v, evs.v.size());
     if (getenv("IOC_TRACE"))
@@ -2417,9 +2416,20 @@ int align_again(ioc_ctx* c, const ioc_aln_pair* pairs, const std::vector<int32_t
     std::vector<int64_t> sw(idx.size());
     std::vector<double> sr(idx.size());
     for (size_t x = 0; x < idx.size(); ++x) sub[x] = pairs[idx[x]];
-    const int r = align_pairs(c, int32_t(sub.size()), sub.data(), int32_t(P.k), P.match, P.mismatch, P.gap_extend, AlnOut{sc.data(), sw.data(), sr.data()}, route);
+    // (emitting call: the re-run writes straight into the regions of the caller's pairs — the bytes of the run that counted)
+    std::vector<int64_t> sbase, slen(out.ops ? idx.size() : 0, 0);
+    AlnOpsHost soh{};
+    if (out.ops) {
+        for (int32_t i : idx) sbase.push_back(out.ops->base[i]);
+        soh = AlnOpsHost{out.ops->buf, sbase.data(), slen.data(), out.ops->ms_copy, out.ops->copied};
+    }
+    const int r = align_pairs(c, int32_t(sub.size()), sub.data(), int32_t(P.k), P.match, P.mismatch, P.gap_extend,
+                              AlnOut{sc.data(), sw.data(), sr.data(), out.ops ? &soh : nullptr}, route);
     if (r != IOC_OK) return r;
-    for (size_t x = 0; x < idx.size(); ++x) out.set(size_t(idx[x]), sc[x], sw[x], sr[x]);
+    for (size_t x = 0; x < idx.size(); ++x) {
+        out.set(size_t(idx[x]), sc[x], sw[x], sr[x]);
+        if (out.ops) out.ops->len[idx[x]] = slen[x];
+    }
     return IOC_OK;
 }
 
@@ -2479,7 +2489,7 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     if (np == 0) return IOC_OK;
     order_pairs(b, pairs);
     const char* ev = getenv("IOC_ALIGN_VARIANT");
-    const bool carry = ev && strcmp(ev, "carry") == 0;
+    const bool carry = ev && strcmp(ev, "carry") == 0 && !out.ops;  // (the carry variant has no walk: an emitting call takes the traced route)
     const WavePlan wp = plan_waves(b, carry);
     if ((r = reserve(c, c->a_pairs, size_t(np) * sizeof(AlnPairDev))) != IOC_OK) return r;
     if ((r = reserve(c, c->a_order, size_t(np) * 4)) != IOC_OK) return r;
@@ -2491,11 +2501,11 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     const char* arena_mode = getenv("IOC_ALIGN_ARENA");
     const bool v2 = route != AlnRoute::v1_only && !carry && !getenv("IOC_ALIGN_V1") && !(arena_mode && strcmp(arena_mode, "fat") == 0);
     uint32_t n_v2 = 0;
-    if (v2 && (r = run_v2(c, b, P, d_score, d_count, route, &n_v2)) != IOC_OK) return r;
+    if (v2 && (r = run_v2(c, b, P, d_score, d_count, route, &n_v2, out.ops)) != IOC_OK) return r;
     if (carry)
         r = run_carry(c, b, wp.waves, P, d_score, d_count);
     else if (n_v2 < np)
-        r = run_v1(c, b, n_v2, wp, P, d_score, d_count);
+        r = run_v1(c, b, n_v2, wp, P, d_score, d_count, out.ops);
     if (r != IOC_OK) return r;
     std::vector<int32_t> hs;
     std::vector<uint32_t> hc;
@@ -2549,6 +2559,49 @@ int ioc_align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int3
                     int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio)
 {
     return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
+}
+
+int64_t ioc_align_ops_bound(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs)
+{
+    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs)) return IOC_ERR_ARG;
+    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
+    int64_t bound = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        const ioc_aln_pair& a = pairs[i];
+        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
+        bound += (c->aln_offs[size_t(a.query) + 1] - c->aln_offs[size_t(a.query)]) + (c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)]);
+    }
+    return bound;
+}
+
+// The walks write a pair's bytes into a region of its own of the caller's buffer (as long as the pair's share of the bound);
+// the regions are packed when all runs — the call's own, the re-runs' — are over.
+int ioc_align_pairs_ops(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                        int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, char* out_ops, int64_t ops_cap,
+                        int64_t* ops_off)
+{
+    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs) || !ops_off || ops_cap < 0 || (ops_cap > 0 && !out_ops)) return IOC_ERR_ARG;
+    const int64_t bound = ioc_align_ops_bound(c, n_pairs, pairs);
+    if (bound < 0) return int(bound);
+    if (ops_cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_ops: ops_cap " + std::to_string(ops_cap) + " below the bound " + std::to_string(bound));
+    std::vector<int64_t> base(size_t(n_pairs) + 1, 0), len(size_t(n_pairs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i)
+        base[size_t(i) + 1] = base[size_t(i)] + (c->aln_offs[size_t(pairs[i].query) + 1] - c->aln_offs[size_t(pairs[i].query)]) +
+                              (c->aln_offs[size_t(pairs[i].ref) + 1] - c->aln_offs[size_t(pairs[i].ref)]);
+    double ms_copy = 0;
+    int64_t copied = 0;
+    const AlnOpsHost oh{reinterpret_cast<uint8_t*>(out_ops), base.data(), len.data(), &ms_copy, &copied};
+    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, &oh}, AlnRoute::normal);
+    if (r != IOC_OK) return r;
+    ops_off[0] = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {  // (a packed position never lies behind the region's own)
+        if (len[size_t(i)] > 0 && ops_off[i] != base[size_t(i)]) memmove(out_ops + ops_off[i], out_ops + base[size_t(i)], size_t(len[size_t(i)]));
+        ops_off[i + 1] = ops_off[i] + len[size_t(i)];
+    }
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: operation bytes: %.1f MB copied from the device in %.3f ms, %.1f MB packed\n", double(copied) * 1e-6, ms_copy,
+                double(ops_off[n_pairs]) * 1e-6);
+    return IOC_OK;
 }
 
 // (ioc_ctx_prewarm)

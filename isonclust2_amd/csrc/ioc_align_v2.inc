@@ -972,13 +972,16 @@ enum V2Help : uint32_t { VH_SEQ = 0, VH_RB, VH_CB, VH_I, VH_J, VH_QUIT, VH_WORK 
 // than max_blocks blocks parks its state in `resume` and leaves — the second launch (HELP = true) takes it on with helper
 // waves: by then the pairs of one transcript are done (verdict mode: ~15 blocks) and the chip is all but empty, so the wrong
 // candidates, whose walks wander off the diagonal through ~60 full blocks, get six waves each.
-template <bool HELP>
+// EMIT (ioc_align_pairs_ops): the walk also writes its operation bytes (OpsOut) and is always exact — no stop_at, so it is never
+// parked and never routed to the helper launch by k_fwd2_ends; global stores only, the LDS is the non-emitting variant's.
+template <bool HELP, bool EMIT>
 __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__ order, const uint8_t* __restrict__ pool,
                                             const AlnParams& P, const uint32_t* __restrict__ arena, const V2Couple* __restrict__ couples, const V2PairCk* __restrict__ pck,
                                             const int4* __restrict__ ends, V2Scratch* __restrict__ scratch, V2Scratch* __restrict__ hscratch,
                                             uint32_t* __restrict__ resume, uint32_t* __restrict__ park, int32_t* __restrict__ out_score,
                                             uint32_t* __restrict__ out_count, const uint32_t count, const uint32_t max_blocks,
-                                            const unsigned long long max_cycles, const uint32_t pslot, const uint32_t wv, const uint32_t want)
+                                            const unsigned long long max_cycles, const uint32_t pslot, const uint32_t wv, const uint32_t want,
+                                            const typename OpsOut<EMIT>::Dev od)
 {
     constexpr int NW = HELP ? int(V2_HWAVES) : TR_WAVES, NDIRS = HELP ? 1 : TR_WAVES;  // (only a walker keeps direction nibbles)
     // LDS of a wave: the left column and the query bytes of the TILE the walk is in (walkers only), and ONE area that holds, by
@@ -1023,6 +1026,7 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
         if (lane == 0) {  // corridor's result does not stand: the host runs the pair again without a corridor
             out_score[pid] = (en.w & 1) ? INT32_MIN : INT32_MIN + 1;
             out_count[pid] = 0xFFFFFFFFu;
+            OpsOut<EMIT>{}.none(od, pid);
         }
         return;
     }
@@ -1035,7 +1039,9 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
     uint32_t i = uint32_t(en.y), j = uint32_t(en.z);
     int state = 0;  // 0 = H, 1 = E, 2 = F
     WinStat ws;
-    if (HELP && want == 1u) {  // the walk the first launch parked
+    OpsOut<EMIT> ops;
+    ops.begin(od, pid, n + m);
+    if (!EMIT && HELP && want == 1u) {  // the walk the first launch parked
         i = rs[0];
         j = rs[1];
         state = int(rs[2]);
@@ -1044,6 +1050,8 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
         ws.cnt = rs[5];
     } else {
         ws.blanks((m - j) + (n - i), kmask, k, il);  // trailing end gaps are the tail of the string
+        ops.fill('d', m - j, lane);
+        ops.fill('i', n - i, lane);
     }
     uint32_t blk_r = 0xFFFFFFFFu, blk_c = 0xFFFFFFFFu;  // the block whose fine checkpoints the scratch holds
     // coarse checkpoints, decoded: row R (a multiple of CK2, > 0), 0-based column index x; column C, 0-based row index y
@@ -1209,7 +1217,7 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
 
     // verdict mode: the walk ends as soon as the count has reached stop_at (the windows still to come can only add) or cannot
     // reach it any more (every further column of the alignment ends at most one more window: at most i + j + k of them)
-    const uint32_t stop_at = pr.stop_at;
+    const uint32_t stop_at = EMIT ? 0u : pr.stop_at;
     // ... or, second bound: a window that still counts holds >= il matches, a match column lies in at most k windows, and at most
     // min(i, j) match columns are left (plus what the k - 1 windows that reach back into the walked part find there): no more than
     // (k min(i, j) + (k - 1)^2) / il windows can follow.  With il of k = 9 of 11 that is 1.22 min(i, j) against i + j.
@@ -1450,6 +1458,7 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
                 if (run > 0) {
                     const unsigned long long mb = __ballot(dgl && tl == 0u) & (run == 64u ? ~0ull : ((1ull << run) - 1ull));
                     ws.push_run(mb, run, kmask, k, il, lane);
+                    ops.run(mb, run, lane);
                     i -= run;
                     j -= run;
                 } else {
@@ -1457,11 +1466,13 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
                 }
             } else if (state == 1) {
                 ws.push(0u, kmask, k, il);
+                ops.step('D', lane);
                 if (!(t & 4u)) state = 0;
                 --j;
                 ++n_gapsteps;
             } else {
                 ws.push(0u, kmask, k, il);
+                ops.step('I', lane);
                 if (!(t & 8u)) state = 0;
                 --i;
                 ++n_gapsteps;
@@ -1472,6 +1483,11 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
     }
     if (HELP) v2_lds_store(help_addr + 4u * VH_QUIT, 1u);  // (the helpers leave)
     if (!decided) ws.blanks(i + j, kmask, k, il);  // leading end gaps
+    if (EMIT) {  // (never decided early)
+        ops.fill('d', j, lane);
+        ops.fill('i', i, lane);
+        ops.end(od, pid, lane);
+    }
     if (lane == 0) {
         out_score[pid] = en.x;
         out_count[pid] = ws.cnt;
@@ -1506,24 +1522,34 @@ __global__ void k_trace2_gate(const uint32_t* __restrict__ early, const uint32_t
 }
 
 // first launch: four pairs per workgroup, one wave each
-__global__ void __launch_bounds__(64 * TR_WAVES)
-k_trace2(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__ order, const uint8_t* __restrict__ pool, AlnParams P,
-         const uint32_t* __restrict__ arena, const V2Couple* __restrict__ couples, const V2PairCk* __restrict__ pck, const int4* __restrict__ ends,
-         V2Scratch* __restrict__ scratch, uint32_t* __restrict__ resume, uint32_t* __restrict__ park, int32_t* __restrict__ out_score,
-         uint32_t* __restrict__ out_count, uint32_t count, uint32_t max_blocks, unsigned long long max_cycles)
+#define V2_TRACE_ARGS                                                                                                                   \
+    const AlnPairDev *__restrict__ pairs, const uint32_t *__restrict__ order, const uint8_t *__restrict__ pool, AlnParams P,             \
+        const uint32_t *__restrict__ arena, const V2Couple *__restrict__ couples, const V2PairCk *__restrict__ pck,                      \
+        const int4 *__restrict__ ends, V2Scratch *__restrict__ scratch, uint32_t *__restrict__ resume, uint32_t *__restrict__ park,      \
+        int32_t *__restrict__ out_score, uint32_t *__restrict__ out_count, uint32_t count, uint32_t max_blocks, unsigned long long max_cycles
+__global__ void __launch_bounds__(64 * TR_WAVES) k_trace2(V2_TRACE_ARGS)
 {
     const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
-    trace2_body<false>(pairs, order, pool, P, arena, couples, pck, ends, scratch, nullptr, resume, park, out_score, out_count, count, max_blocks, max_cycles,
-                       blockIdx.x * TR_WAVES + wv, wv, 0u);
+    trace2_body<false, false>(pairs, order, pool, P, arena, couples, pck, ends, scratch, nullptr, resume, park, out_score, out_count, count, max_blocks,
+                              max_cycles, blockIdx.x * TR_WAVES + wv, wv, 0u, NoOpsDev{});
+}
+// ... emitting (ioc_align_pairs_ops)
+__global__ void __launch_bounds__(64 * TR_WAVES) k_trace2_ops(V2_TRACE_ARGS, AlnOpsDev od)
+{
+    const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+    trace2_body<false, true>(pairs, order, pool, P, arena, couples, pck, ends, scratch, nullptr, resume, park, out_score, out_count, count, max_blocks,
+                             max_cycles, blockIdx.x * TR_WAVES + wv, wv, 0u, od);
 }
 
 // second launch: the parked walks (park[0] of them, listed behind it), one per workgroup of a walker and five helper waves; the
 // grid is fixed (the host does not know the count), a workgroup takes every gridDim.x-th entry
-__global__ void __launch_bounds__(64 * V2_HWAVES)
-k_trace2_help(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__ order, const uint8_t* __restrict__ pool, AlnParams P,
-              const uint32_t* __restrict__ arena, const V2Couple* __restrict__ couples, const V2PairCk* __restrict__ pck, const int4* __restrict__ ends,
-              V2Scratch* __restrict__ scratch, V2Scratch* __restrict__ hscratch, uint32_t* __restrict__ resume, uint32_t* __restrict__ park, int32_t* __restrict__ out_score,
-              uint32_t* __restrict__ out_count, uint32_t count, uint32_t want, uint32_t* __restrict__ gate)
+#define V2_HELP_ARGS                                                                                                                    \
+    const AlnPairDev *__restrict__ pairs, const uint32_t *__restrict__ order, const uint8_t *__restrict__ pool, AlnParams P,             \
+        const uint32_t *__restrict__ arena, const V2Couple *__restrict__ couples, const V2PairCk *__restrict__ pck,                      \
+        const int4 *__restrict__ ends, V2Scratch *__restrict__ scratch, V2Scratch *__restrict__ hscratch, uint32_t *__restrict__ resume, \
+        uint32_t *__restrict__ park, int32_t *__restrict__ out_score, uint32_t *__restrict__ out_count, uint32_t count, uint32_t want,   \
+        uint32_t *__restrict__ gate
+__global__ void __launch_bounds__(64 * V2_HWAVES) k_trace2_help(V2_HELP_ARGS)
 {
     const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
     uint32_t n_parked = uint32_t(__builtin_amdgcn_readfirstlane(int(park[0])));
@@ -1531,7 +1557,23 @@ k_trace2_help(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__
     if (gate && threadIdx.x == 0) atomicAdd(gate, 1u);  // (this workgroup has its place on the chip: k_trace2_gate)
     for (uint32_t e = blockIdx.x; e < n_parked; e += gridDim.x) {
         const uint32_t pslot = uint32_t(__builtin_amdgcn_readfirstlane(int(park[1u + e])));
-        trace2_body<true>(pairs, order, pool, P, arena, couples, pck, ends, scratch, hscratch, resume, park, out_score, out_count, count, 0u, 0ull, pslot, wv, want);
+        trace2_body<true, false>(pairs, order, pool, P, arena, couples, pck, ends, scratch, hscratch, resume, park, out_score, out_count, count, 0u, 0ull, pslot, wv,
+                                 want, NoOpsDev{});
         __syncthreads();  // (walker and helpers have left the pair: its LDS words are free)
+    }
+}
+// ... emitting.  (An emitting call's pairs have no stop_at: nothing parks them and k_fwd2_ends routes none of them here, so this
+// launch finds its lists empty today; it exists so that the emitting call's launches are the plain call's, whatever is routed where.)
+__global__ void __launch_bounds__(64 * V2_HWAVES) k_trace2_help_ops(V2_HELP_ARGS, AlnOpsDev od)
+{
+    const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+    uint32_t n_parked = uint32_t(__builtin_amdgcn_readfirstlane(int(park[0])));
+    if (want == 2u) n_parked = min(n_parked, gridDim.x);
+    if (gate && threadIdx.x == 0) atomicAdd(gate, 1u);
+    for (uint32_t e = blockIdx.x; e < n_parked; e += gridDim.x) {
+        const uint32_t pslot = uint32_t(__builtin_amdgcn_readfirstlane(int(park[1u + e])));
+        trace2_body<true, true>(pairs, order, pool, P, arena, couples, pck, ends, scratch, hscratch, resume, park, out_score, out_count, count, 0u, 0ull, pslot, wv,
+                                want, od);
+        __syncthreads();
     }
 }

@@ -23,7 +23,7 @@ print("context", flush=True)
 ctx = api.Context(0)
 ctx.align_set_pool(seqs)
 print("aligning", NP, "pairs of", L, flush=True)
-sc, win, ratio = ctx.align_pairs(pairs, 11)
+sc, win, ratio, ops = ctx.align_pairs_ops(pairs, 11)
 print("device done", ctx.timings()["ms_align_fwd"], ctx.timings()["ms_align_trace"], flush=True)
 Lh = _lib.load()
 comp = {65: 84, 67: 71, 71: 67, 84: 65}
@@ -31,11 +31,16 @@ bad = 0
 for i, (qi, ri, rc, e) in enumerate(pairs):
     q, r = seqs[qi], seqs[ri]
     if rc: r = bytes(comp[ch] for ch in reversed(r))
-    cap = len(q) + len(r) + 2
-    buf = C.create_string_buffer(cap); s = C.c_int32()
-    n = Lh.ioc_host_align(q, len(q), r, len(r), 2, -2, Lh.ioc_host_gap_open(e), 1, buf, cap, C.byref(s))
-    hr = Lh.ioc_host_aln_ratio(buf, n, e, len(q), 11)
-    if s.value != sc[i] or hr != ratio[i]:
+    hops, hs = api.host_align_ops(q, r, gap_open=Lh.ioc_host_gap_open(e))
+    hcomp = api.ops_to_comp(hops)
+    hr = Lh.ioc_host_aln_ratio(hcomp, len(hcomp), e, len(q), 11)
+    if hs != sc[i] or hr != ratio[i] or hops != ops[i]:
         bad += 1
-        if bad < 6: print("MISMATCH pair", i, len(q), len(r), "host", s.value, hr, "device", sc[i], ratio[i], flush=True)
+        if bad < 6:
+            print("MISMATCH pair", i, len(q), len(r), "host", hs, hr, "device", sc[i], ratio[i], flush=True)
+            # where the device's walk leaves the host's: the first column that differs, its position in both sequences
+            d = next((x for x in range(min(len(hops), len(ops[i]))) if hops[x] != ops[i][x]), min(len(hops), len(ops[i])))
+            qi_, rj_ = sum(hops[:d].count(c) for c in b"=XIi"), sum(hops[:d].count(c) for c in b"=XDd")
+            print(f"  first difference at column {d} (query base {qi_}, reference base {rj_}; host {len(hops)} columns, device {len(ops[i])})")
+            print("  host  ", hops[max(0, d - 10):d + 10].decode(), "\n  device", ops[i][max(0, d - 10):d + 10].decode(), flush=True)
 print("pairs", NP, "mismatches", bad, flush=True)
