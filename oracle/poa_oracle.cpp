@@ -27,6 +27,23 @@
  *   - AddAlignment: unaligned prefix and suffix of the read as fresh chains (the suffix BEFORE the aligned part), then the
  *     aligned part base by base;
  *   - consensus: heaviest bundle with branch completion.
+ * The three alignment types (numbered like `cluster -A` and spoa's kSW / kNW / kOV: 0 local, 1 global, 2 semi-global; DESIGN.md
+ * 5.7 has the table).  Row 0 is the virtual source, rows 1..R the nodes in topological order, columns 0..L the read, gap(k) =
+ * max(g + (k - 1) e, q + (k - 1) c).  Local alignment is the description above.  For global and semi-global alignment:
+ *   - row 0: H[0][0] = 0, H[0][j] = gap(j), E[0][j] = g + (j - 1) e, Q[0][j] = q + (j - 1) c, F / O = -inf;
+ *   - column 0 of the node rows: global F / O through the predecessors like any other column (a node without predecessors
+ *     has row 0 as its predecessor) and H = max(F, O); semi-global H = 0 and F / O = -inf (a free start anywhere in the graph);
+ *     E / Q = -inf in column 0 under every type;
+ *   - no floor on H: scores may be negative;
+ *   - end cells: global column L of the sinks (nodes without out-edges); semi-global column L of every node row and every
+ *     column of the sinks, column 0 included;
+ *   - the best end cell is the FIRST maximum in (row, column) order among the end cells;
+ *   - the traceback inside the matrix is the one above, unchanged (diagonal, vertical, horizontal; predecessors in in-edge
+ *     order), column 0 of a global alignment included: its vertical moves are found by the same tests on F / H / O;
+ *   - a global walk ends at (0, 0): read bases consumed on row 0 are (-1, pos) pairs, nodes consumed on column 0 (node, -1)
+ *     pairs; a semi-global walk ends as soon as it stands on row 0 or on column 0: a read head left on row 0 is NOT in the
+ *     alignment (AddAlignment makes it the unaligned prefix), and a walk whose best end cell is column 0 of a sink is empty;
+ *   - AddAlignment treats an alignment without any read position like an empty one: the read becomes a chain of its own.
  * PARITY UNPINNED: no vector of the reference's tests touches a graph, and the source this was written after is not in the
  * tree.  What this oracle pins is the product's POA engine (isonclust2_amd/csrc/ioc_poa.hip) against an INDEPENDENT scalar
  * implementation of the same published algorithm, tie rules included — "parity with the oracle's POA; spoa unpinned".
@@ -148,6 +165,12 @@ struct Graph {
         std::vector<uint32_t> valid;
         for (const auto& a : aln)
             if (a.second != -1) valid.push_back(uint32_t(a.second));
+        if (valid.empty()) {  // no read base takes part: nothing to fuse with
+            add_sequence(s, w, 0, len);
+            ++num_sequences;
+            topological_sort();
+            return;
+        }
         const size_t before = nodes.size();
         add_sequence(s, w, 0, valid.front());
         int prev = before == nodes.size() ? -1 : int(nodes.size()) - 1;
@@ -246,9 +269,12 @@ struct Graph {
     }
 };
 
+enum { kLocal = 0, kGlobal = 1, kSemiGlobal = 2 };
+
 struct Engine {
     int32_t m, n, g, e, q, c;
-    // local alignment of s against G: (node id | -1, read position | -1) in read order; *score = the best cell
+    int type = kLocal;
+    // alignment of s against G under the engine's type: (node id | -1, read position | -1) in read order; *score = the best cell
     std::vector<std::pair<int, int>> align(const std::string& s, const Graph& G, int32_t* score) const
     {
         std::vector<std::pair<int, int>> aln;
@@ -266,8 +292,24 @@ struct Engine {
             if (ps.empty()) ps.push_back(0);
             return ps;
         };
+        const bool local = type == kLocal;
+        if (!local)  // row 0: the read's head against nothing
+            for (size_t j = 1; j < W; ++j) {
+                E[j] = g + int32_t(j - 1) * e;
+                Q[j] = q + int32_t(j - 1) * c;
+                H[j] = std::max(E[j], Q[j]);
+            }
         int32_t best = 0;
         size_t bi = 0, bj = 0;
+        bool have = local;  // (local: the empty alignment at (0, 0) is what every cell has to beat)
+        auto offer = [&](size_t i, size_t j) {
+            if (!have || best < H[i * W + j]) {
+                best = H[i * W + j];
+                bi = i;
+                bj = j;
+                have = true;
+            }
+        };
         for (size_t r = 0; r < R; ++r) {
             const Node& nd = G.nodes[size_t(G.rank_to_node[r])];
             const size_t i = r + 1;
@@ -288,10 +330,19 @@ struct Engine {
                     }
                 }
             }
+            if (type == kGlobal) {  // column 0: the graph's head against nothing
+                for (size_t x = 0; x < ps.size(); ++x) {
+                    const int32_t f = std::max(H[ps[x] * W] + g, F[ps[x] * W] + e), o = std::max(H[ps[x] * W] + q, O[ps[x] * W] + c);
+                    Fr[0] = x == 0 ? f : std::max(Fr[0], f);
+                    Or[0] = x == 0 ? o : std::max(Or[0], o);
+                }
+                Hr[0] = std::max(Fr[0], Or[0]);
+            }
             for (size_t j = 1; j < W; ++j) {
                 Er[j] = std::max(Hr[j - 1] + g, Er[j - 1] + e);
                 Qr[j] = std::max(Hr[j - 1] + q, Qr[j - 1] + c);
                 Hr[j] = std::max(Hr[j], std::max(std::max(Fr[j], Er[j]), std::max(Or[j], Qr[j])));
+                if (!local) continue;
                 Hr[j] = std::max(Hr[j], 0);
                 if (best < Hr[j]) {
                     best = Hr[j];
@@ -299,6 +350,11 @@ struct Engine {
                     bj = j;
                 }
             }
+            if (local) continue;
+            const bool sink = nd.out.empty();
+            if (sink && type == kSemiGlobal)
+                for (size_t j = 0; j < L; ++j) offer(i, j);
+            if (sink || type == kSemiGlobal) offer(i, L);
         }
         *score = best;
         // ---- traceback ----
@@ -309,7 +365,17 @@ struct Engine {
         // extended gap while EITHER piece looks extended, which can run past the opening; unverifiable here — the source is
         // absent — and not restated.)
         size_t i = bi, j = bj;
-        while (H[i * W + j] != 0) {
+        auto walking = [&]() {
+            if (type == kGlobal) return i != 0 || j != 0;
+            if (type == kSemiGlobal) return i != 0 && j != 0;
+            return H[i * W + j] != 0;
+        };
+        while (walking()) {
+            if (i == 0) {  // (global only) the rest of the read's head, on row 0
+                aln.emplace_back(-1, int(j) - 1);
+                --j;
+                continue;
+            }
             const int32_t Hij = H[i * W + j];
             bool found = false;
             int ext_left = 0, ext_up = 0;  // 1: first piece (E / F), 2: second piece (Q / O)
@@ -397,7 +463,7 @@ struct Engine {
 };
 
 struct Store {
-    Engine eng;
+    Engine eng{};
     std::map<int, std::unique_ptr<Graph>> g[2];
     std::vector<std::pair<int, int>> last_aln;
     int32_t last_score = 0;
@@ -469,12 +535,16 @@ struct orp_ops {
     int (*purge)(void*, int, int, const char*, int, unsigned);
 };
 
-void* orp_create(int m, int n, int g, int e, int q, int c)
+// type: 0 local, 1 global, 2 semi-global (`cluster -A`); NULL for any other
+void* orp_create_mode(int type, int m, int n, int g, int e, int q, int c)
 {
+    if (type != kLocal && type != kGlobal && type != kSemiGlobal) return nullptr;
     Store* S = new Store;
-    S->eng = Engine{m, n, g, e, q, c};
+    S->eng.m = m, S->eng.n = n, S->eng.g = g, S->eng.e = e, S->eng.q = q, S->eng.c = c;
+    S->eng.type = type;
     return S;
 }
+void* orp_create(int m, int n, int g, int e, int q, int c) { return orp_create_mode(kLocal, m, n, g, e, q, c); }
 void orp_destroy(void* s) { delete static_cast<Store*>(s); }
 void orp_bind(void* s, orp_ops* ops)
 {

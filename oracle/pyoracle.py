@@ -118,6 +118,8 @@ def lib():
     # the scalar partial-order alignment (poa_oracle.cpp)
     L.orp_create.argtypes = [i32] * 6
     L.orp_create.restype = vp
+    L.orp_create_mode.argtypes = [i32] * 7
+    L.orp_create_mode.restype = vp
     L.orp_destroy.argtypes = [vp]
     L.orp_destroy.restype = None
     L.orp_bind.argtypes = [vp, vp]
@@ -420,13 +422,16 @@ class PoaOps(C.Structure):
 
 class OraclePoa:
     """One store of partial-order graphs {(side, idx)} with spoa 4.0's operations restated (poa_oracle.cpp): create / add /
-    size / consensus / purge, plus inspection of a graph and of the last alignment."""
+    size / consensus / purge, plus inspection of a graph and of the last alignment.  mode: the alignment type, numbered like
+    `cluster -A` (0 local, 1 global, 2 semi-global)."""
     SC = dict(m=4, n=-8, g=-8, e=-4, q=-20, c=-1)   # src/main.cpp:285-290
 
-    def __init__(self, **sc):
+    def __init__(self, mode=0, **sc):
         sc = dict(self.SC, **sc)
         self.L = lib()
-        self.h = self.L.orp_create(sc["m"], sc["n"], sc["g"], sc["e"], sc["q"], sc["c"])
+        self.mode = mode
+        self.h = self.L.orp_create_mode(mode, sc["m"], sc["n"], sc["g"], sc["e"], sc["q"], sc["c"])
+        assert self.h, f"unknown alignment type {mode}"
         self.ops = PoaOps()
         self.L.orp_bind(self.h, C.addressof(self.ops))
         proto = lambda *a: C.CFUNCTYPE(C.c_int, C.c_void_p, *a)

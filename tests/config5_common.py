@@ -60,6 +60,15 @@ def mindb_sha(keys, offs, post):
 # of the string, one entry per consensus event), and at the end every cluster's graph (letters, topological ranks, weighted
 # edges) and consensus.  spoa itself stays unpinned: this is parity with the oracle's restatement of it.
 REAL_NB, REAL_PER, REAL_G = 2, 3000, 60
+# A small workload whose LEAVES take consensus events (200 reads over 60 transcripts never reach ConsMinSize 20): the same reads
+# generator over REAL_SMALL_G transcripts, ~ 30 reads per cluster and leaf, 30 clusters to join in the merge.  Records real<PER>, real<PER>_A1, real<PER>_A2 (the
+# alignment type of `cluster -A`).
+REAL_SMALL_PER, REAL_SMALL_G = 900, 30
+
+
+def real_g(per):
+    """the number of transcripts of the real-graph workload with `per` reads per leaf"""
+    return REAL_SMALL_G if per == REAL_SMALL_PER else REAL_G
 
 
 def real_reads(nb=REAL_NB, per=REAL_PER, g=REAL_G):

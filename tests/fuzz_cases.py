@@ -173,16 +173,19 @@ def run_consensus(ctx, c, speculate=None):
 def run_consensus_poa(ctx, c):
     """Consensus mode with REAL partial-order graphs on both sides: the product's engine (ioc_poa.hip) behind
     ioc_cluster_consensus, the oracle's scalar POA (oracle/poa_oracle.cpp) behind the oracle's hook.  Compared: assignments,
-    the event count, the MinDB, and every cluster's graph (letters, weighted edges, order) and consensus."""
+    the event count, the MinDB, and every cluster's graph (letters, weighted edges, order) and consensus.  c["poa_type"]: the
+    alignment type of `cluster -A` on both sides (default 0, local)."""
     from tests.test_gpu_poa import Poa
+    from tests.test_gpu_poa_modes import ModePoa
+    poa_type = int(c.get("poa_type", 0))
     rs = synth.generate(c["n"], c["g"], c["ln"], c["qlo"], c["qhi"], seed=c["seed"], dup_every=c["dup"])
     mode = c["mode"]
-    o_poa = po.OraclePoa()
+    o_poa = po.OraclePoa(mode=poa_type)
     B, view, ost, _ = oracle_consensus_run(rs, c["cmax"], c["cmin"], c["period"], mode=mode, graphs=o_poa, ops_pointer=o_poa.ops_pointer())
     acl, ast = B.assignments(rs.n)
     ocl, ostr = acl[view["orig"]], ast[view["orig"]]
     v = _with_sequences(rs, view)
-    p_poa = Poa(ctx)
+    p_poa = ModePoa(ctx, poa_type) if poa_type else Poa(ctx)
     what = []
     try:
         cargs = _lib.ConsensusArgs(cons_min_size=c["cmin"], cons_max_size=c["cmax"], cons_period=c["period"], left_depth=-1, left_sizes=None)

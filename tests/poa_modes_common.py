@@ -1,6 +1,8 @@
 """Plain-Python statements of the three alignment types of the POA engine (`cluster -A`: 0 local, 1 global, 2 semi-global;
 DESIGN.md 5.7): the sequence-to-graph recurrence over an exported graph, a path scorer that knows the types' boundaries, and
-a brute force over the source-to-sink paths of a small graph.  oracle/poa_oracle.cpp states local alignment only."""
+a brute force over the source-to-sink paths of a small graph.  oracle/poa_oracle.cpp states the three types too, tie rules
+included; what is here is what pins IT (tests/test_oracle_poa_modes.py: scores, rescored paths, boundaries, the brute force),
+before the engine is compared with it pair by pair (tests/test_gpu_poa_oracle.py).  This file knows scores, not tie rules."""
 import numpy as np
 
 from tests.poa_common import NEG, SC, _path_score

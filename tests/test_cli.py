@@ -224,9 +224,15 @@ def test_consensus_mode_sort_cluster_merge_dump(tmp_path):
     and updates the MinDB; the merge runs with the Depth != -1 rules.  The oracle runs the same three steps with ITS OWN
     scalar POA (oracle/poa_oracle.cpp) behind its consensus hook — nothing of the product on that side —, the graphs of
     step 2 serving as the right batch's in the merge.  Parity with the oracle's POA; spoa itself is unpinned."""
-    import ctypes as C
-    from isonclust2_amd import api
+    consensus_mode_sort_cluster_merge_dump_vs_oracle(tmp_path, None)
+
+
+def consensus_mode_sort_cluster_merge_dump_vs_oracle(tmp_path, poa_type):
+    """poa_type None: no -A on the command line (local alignment); 0 | 1 | 2: `-A <type>` to the two leaves AND to the merge (a
+    graph does not record the type that built it), OraclePoa(mode=type) on the oracle's side"""
     from oracle import pyoracle as po
+    A_opt = [] if poa_type is None else ["-A", str(poa_type)]
+    mode = 0 if poa_type is None else poa_type
     rs = synth.generate(200, 6, 800, 12, 21, seed=31)
     half = rs.n // 2
     fq = tmp_path / "reads.fq"
@@ -236,10 +242,10 @@ def test_consensus_mode_sort_cluster_merge_dump(tmp_path):
     assert r.returncode == 0, r.stderr
     b0, b1 = out / "batches" / "isONbatch_0.cer", out / "batches" / "isONbatch_1.cer"
     for b, o in ((b0, "c0.cer"), (b1, "c1.cer")):
-        r = run("cluster", "-v", "-l", str(b), "-o", str(tmp_path / o), "-x", "fast")
+        r = run("cluster", "-v", "-l", str(b), "-o", str(tmp_path / o), "-x", "fast", *A_opt)
         assert r.returncode == 0, r.stderr
         assert "Consensus invocation count" in r.stderr
-    r = run("cluster", "-l", str(tmp_path / "c0.cer"), "-r", str(tmp_path / "c1.cer"), "-o", str(tmp_path / "m.cer"), "-x", "fast")
+    r = run("cluster", "-l", str(tmp_path / "c0.cer"), "-r", str(tmp_path / "c1.cer"), "-o", str(tmp_path / "m.cer"), "-x", "fast", *A_opt)
     assert r.returncode == 0, r.stderr
     r = run("dump", "-i", str(out / "sorted_reads_idx.cer"), "-o", str(tmp_path / "dump"), str(tmp_path / "m.cer"))
     assert r.returncode == 0, r.stderr
@@ -250,7 +256,7 @@ def test_consensus_mode_sort_cluster_merge_dump(tmp_path):
     p = po.default_params(11, 15)
     p.cons_max_size = 8
     A, B = po.Batch(R, 0, half - 1, p, 0), po.Batch(R, half, rs.n - 1, p, 1)
-    ga, gb = po.OraclePoa(), po.OraclePoa()
+    ga, gb = po.OraclePoa(mode=mode), po.OraclePoa(mode=mode)
     events = 0
     for Bo, g in ((A, ga), (B, gb)):
         po.lib().orc_set_consensus(g.ops_pointer(), 3, 400)
@@ -260,7 +266,7 @@ def test_consensus_mode_sort_cluster_merge_dump(tmp_path):
             po.lib().orc_set_consensus(None, 50, 500)
     assert events > 5
     # merge: left graphs = ga's side 0, right graphs = gb's side 0 presented as side 1
-    gm = po.OraclePoa()
+    gm = po.OraclePoa(mode=mode)
     for src, dst_side in ((ga, 0), (gb, 1)):
         for c_id in range((A if src is ga else B).n_clusters()):
             src.copy_graph_to(c_id, gm, dst_side, c_id)

@@ -1,5 +1,7 @@
 """`cluster -A 0|1|2` (src/main.cpp:292-324): the consensus engine's alignment type on the command line.  Without -A, with
--A 0 and with a value the reference's switch does not know the engine aligns locally, as it did before -A was read."""
+-A 0 and with a value the reference's switch does not know the engine aligns locally, as it did before -A was read.  Under
+-A 1 and -A 2 the whole command-line path (sort, two leaves, their merge, dump) is held to the oracle with its own POA of the
+same type behind its hook, as tests/test_cli.py does without -A."""
 import os
 import shutil
 import subprocess
@@ -8,7 +10,7 @@ import tempfile
 import pytest
 
 from isonclust2_amd import synth
-from tests.test_cli import CLI, _write_fastq, run
+from tests.test_cli import CLI, _write_fastq, consensus_mode_sort_cluster_merge_dump_vs_oracle, run
 
 
 def test_help_names_the_option():
@@ -50,3 +52,12 @@ def test_cluster_A_selects_the_consensus_alignment(tmp_path):
     finally:
         run("serve", "stop", env=env)
         shutil.rmtree(srv, ignore_errors=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("poa_type", [0, 1, 2])
+def test_consensus_mode_sort_cluster_merge_dump_under_A(tmp_path, poa_type):
+    """test_cli.test_consensus_mode_sort_cluster_merge_dump with `-A <type>` on the three `cluster` calls and the oracle's POA
+    of that type: the assignments after the merge, which hang on every consensus string on the way (a representative replaced
+    by a different consensus is re-minimized differently)"""
+    consensus_mode_sort_cluster_merge_dump_vs_oracle(tmp_path, poa_type)

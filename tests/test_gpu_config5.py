@@ -117,13 +117,15 @@ def test_config5_tree_merge(full):
 class PoaStore:
     """The product's POA engine (ioc_poa.hip) as the graph store of ioc_cluster_consensus, with what the pipeline needs around
     it: the replaced representatives' records (rep_changed: the consensus strings arrive there in event order) and the transfer of
-    graphs between engines (ioc_poa_graph_save / load: what the `.cer` files carry from a leaf to a merge)."""
+    graphs between engines (ioc_poa_graph_save / load: what the `.cer` files carry from a leaf to a merge).  poa_type: the
+    alignment type of `cluster -A` (0 local, 1 global, 2 semi-global)."""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, poa_type=0):
         import ctypes as C
         from isonclust2_amd import _lib
         from tests.test_gpu_poa import Poa
-        self.C, self.poa = C, Poa(ctx)
+        from tests.test_gpu_poa_modes import ModePoa
+        self.C, self.poa = C, (ModePoa(ctx, poa_type) if poa_type else Poa(ctx))
         self.rep_records, self.events = [], []
 
         def rep_changed(user, cls, rec):
@@ -170,29 +172,58 @@ def _check_real(tag, cb, store, g, n_total):
     assert got == want, (tag, {k: (got[k], want[k]) for k in got if got[k] != want[k]})
 
 
-@pytest.mark.parametrize("per", [200, c5.REAL_PER])
-def test_config5_real_graphs(ctx, per):
+def _real_name(per, poa_type):
+    return f"real{per}" if poa_type == 0 else f"real{per}_A{poa_type}"
+
+
+# (the ids of the two records that existed before the alignment types stay "200" and "3000")
+_REAL_RECORDS = [pytest.param(200, 0, id="200"), pytest.param(c5.REAL_PER, 0, id=str(c5.REAL_PER)),
+                 pytest.param(c5.REAL_PER, 2, id=f"{c5.REAL_PER}_A2")] + [
+                     pytest.param(c5.REAL_SMALL_PER, t, id=_real_name(c5.REAL_SMALL_PER, t)[4:]) for t in (0, 1, 2)]
+
+
+def test_real_graph_goldens_depend_on_the_alignment_type():
+    """from the goldens alone: the records of one workload under different types hold different graphs (otherwise they would
+    not test the type), and the small workload's leaves and merge take consensus events under every type"""
+    for per, types in ((c5.REAL_SMALL_PER, (0, 1, 2)), (c5.REAL_PER, (0, 2))):
+        recs = [GOLD[_real_name(per, t)] for t in types]
+        for step in [lambda r, b=b: r["leaves"][b] for b in range(c5.REAL_NB)] + [lambda r: r["merges"][0]]:
+            shas = [step(r)["graphs_sha"] for r in recs]
+            assert len(set(shas)) == len(shas), (per, shas)
+    for t in (0, 1, 2):
+        rec = GOLD[_real_name(c5.REAL_SMALL_PER, t)]
+        assert all(leaf["cons_invoked"] >= 50 for leaf in rec["leaves"]) and rec["merges"][0]["cons_invoked"] >= 20, t
+        assert all("oracle_seconds_1core" in step for step in rec["leaves"] + rec["merges"])
+    assert "alignment type 2" in GOLD[_real_name(c5.REAL_PER, 2)]["workload"]
+
+
+@pytest.mark.parametrize("per,poa_type", _REAL_RECORDS)
+def test_config5_real_graphs(ctx, per, poa_type):
     """Two leaves of `per` reads x 2 kb (sahlin, -c 150, ConsMinSize 20) and their merge with the product's POA engine behind the
     consensus, against the goldens the ORACLE computed with its own scalar POA behind its hook (tools/gen_golden_config5.py
     --real-graphs): assignments, event counts, the consensus strings in event order, every cluster's final graph (letters,
-    ranks, weighted edges) and consensus, the MinDB.  (src/consensus.cpp:34-126, src/cluster.cpp:263-309; spoa itself: unpinned.)"""
-    gold = GOLD[f"real{per}"]
+    ranks, weighted edges) and consensus, the MinDB.  (src/consensus.cpp:34-126, src/cluster.cpp:263-309; spoa itself: unpinned.)
+    Records `real<per>_A<type>`: the same under global (1) and semi-global (2) alignment on both sides, leaves and merge alike;
+    `real900*` is a workload of 30 transcripts whose leaves take consensus events at a size the oracle computes in minutes."""
+    gold = GOLD[_real_name(per, poa_type)]
     nb = c5.REAL_NB
-    rs = c5.real_reads(nb, per)
+    rs = c5.real_reads(nb, per, c5.real_g(per))
     p = api.default_params(c5.K, c5.W, c5.MODE)
     srt, _ = pipeline.sort_stage(ctx, rs, c5.K, c5.W)
     cbs, stores = [], []
     try:
         for b in range(nb):
             sb = pipeline.slice_sorted(srt, b * per, (b + 1) * per, batch_nr=b)
-            store = PoaStore(ctx)
+            store = PoaStore(ctx, poa_type)
             stores.append(store)
             cb = pipeline.cluster_consensus_single(ctx, p, sb, CONS, store)
             _check_real(f"leaf {b}", cb, store, gold["leaves"][b], rs.n)
             cbs.append(cb)
         if per == c5.REAL_PER:
             assert gold["leaves"][0]["cons_invoked"] > 500      # the leaves really take consensus events
-        gm = PoaStore(ctx)
+        if per == c5.REAL_SMALL_PER:
+            assert all(leaf["cons_invoked"] >= 50 for leaf in gold["leaves"])
+        gm = PoaStore(ctx, poa_type)
         stores.append(gm)
         for src, side in ((stores[0], 0), (stores[1], 1)):
             for c_id in range(cbs[side].n_clusters):

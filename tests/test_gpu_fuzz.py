@@ -126,18 +126,30 @@ def test_fuzz_consensus(ctx, mode, speculate):
     assert not bad, f"{len(bad)} of {n + len(fixed)} cases differ from the oracle; first: {env}python tools/fuzz_consensus.py --case \"{bad[0][0]}\"  ({bad[0][1]})"
 
 
-def test_fuzz_consensus_with_real_graphs(ctx):
-    """the POA engine behind the product, the oracle's scalar POA behind the oracle (spoa itself: unpinned)"""
-    rng = np.random.default_rng([SEED, 20])
+def _fuzz_real_graphs(ctx, poa_type):
+    rng = np.random.default_rng([SEED, 20] if poa_type == 0 else [SEED, 20, poa_type])
+    more = {"poa_type": poa_type} if poa_type else {}        # (type 0: the cases and the draws as before the types existed)
 
     def draw():
         c = fz.draw_consensus(rng, "fast")
-        c.update(n=min(c["n"], 150), ln=min(c["ln"], 500))
+        c.update(n=min(c["n"], 150), ln=min(c["ln"], 500), **more)
         return c
 
-    fixed = [dict(c, n=min(c["n"], 150), ln=min(c["ln"], 500)) for c in _CONS_FIXED[1:]]
+    fixed = [dict(c, n=min(c["n"], 150), ln=min(c["ln"], 500), **more) for c in _CONS_FIXED[1:]]
     bad, n = _slice(lambda c: fz.run_consensus_poa(ctx, c), fixed, draw, min_random=3)
-    assert not bad, f"{len(bad)} of {n + len(fixed)} cases differ from the oracle; first: {bad[0][0]}  ({bad[0][1]})"
+    assert not bad, (f"{len(bad)} of {n + len(fixed)} cases differ from the oracle; first: python tools/fuzz_poa.py --case \"{bad[0][0]}\""
+                     f"  ({bad[0][1]})")
+
+
+def test_fuzz_consensus_with_real_graphs(ctx):
+    """the POA engine behind the product, the oracle's scalar POA behind the oracle (spoa itself: unpinned)"""
+    _fuzz_real_graphs(ctx, 0)
+
+
+@pytest.mark.parametrize("poa_type", [1, 2])
+def test_fuzz_consensus_with_real_graphs_off_local(ctx, poa_type):
+    """the same under global and semi-global alignment (`cluster -A 1 | 2`) on both sides"""
+    _fuzz_real_graphs(ctx, poa_type)
 
 
 def test_fuzz_align(ctx):

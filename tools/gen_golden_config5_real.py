@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""tests/golden/config5.json, record `real<PER>`: the consensus branch with REAL partial-order graphs on the ORACLE's side —
+"""tests/golden/config5.json, record `real<PER>` (`real<PER>_A<TYPE>` under --poa-type 1 | 2): the consensus branch with REAL partial-order graphs on the ORACLE's side —
 oracle/poa_oracle.cpp behind the oracle's consensus hook — on the workload of tests/config5_common.py (REAL_NB leaves of REAL_PER
 reads x 2 kb, sahlin, -c 150, ConsMinSize 20, and their merge).  Run once in the build container (CPU, minutes):
 
-    python tools/gen_golden_config5.py --real-graphs        (or this file directly, [--per N])
+    python tools/gen_golden_config5.py --real-graphs        (or this file directly, [--per N] [--poa-type 0|1|2] [--out FILE])
+
+--per tests.config5_common.REAL_SMALL_PER selects the small workload (REAL_SMALL_G transcripts: its leaves take consensus events).
+--poa-type is the alignment type of `cluster -A` for every graph operation, leaves and merge alike.  --out writes the record
+into another JSON file than the golden (several records can then be generated side by side and merged by hand).
 
 Per step: the digests of the toy-graph record plus the consensus strings in event order, every cluster's graph and consensus."""
 import argparse
@@ -23,12 +27,17 @@ from tests.helpers import fnv1a  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--per", type=int, default=c5.REAL_PER)
+ap.add_argument("--poa-type", type=int, default=0, choices=[0, 1, 2])
+ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "config5.json"))
 a = ap.parse_args()
-PATH = os.path.join(ROOT, "tests", "golden", "config5.json")
+PATH = a.out
+NAME = f"real{a.per}" if a.poa_type == 0 else f"real{a.per}_A{a.poa_type}"
+G = c5.real_g(a.per)
 out = json.load(open(PATH)) if os.path.exists(PATH) else {}
 NB = c5.REAL_NB
-rec = {"workload": f"{NB} x {a.per} reads of {c5.LEN} b, G={c5.REAL_G}, chunk seeds 2000.., transcript seed {c5.TR_SEED + 1}, global sort; {c5.MODE} "
-                   f"k={c5.K} w={c5.W}; ConsMinSize {c5.CONS_MIN} ConsMaxSize {c5.CONS_MAX} ConsPeriod {c5.CONS_PERIOD}; graphs: oracle/poa_oracle.cpp",
+rec = {"workload": f"{NB} x {a.per} reads of {c5.LEN} b, G={G}, chunk seeds 2000.., transcript seed {c5.TR_SEED + 1}, global sort; {c5.MODE} "
+                   f"k={c5.K} w={c5.W}; ConsMinSize {c5.CONS_MIN} ConsMaxSize {c5.CONS_MAX} ConsPeriod {c5.CONS_PERIOD}; graphs: oracle/poa_oracle.cpp"
+                   + (f", alignment type {a.poa_type}" if a.poa_type else ""),
        "leaves": [], "merges": []}
 t00 = time.time()
 
@@ -41,7 +50,7 @@ class LoggedPoa:
     """An OraclePoa whose consensus operation also records (cluster, string) per call: the events in their order."""
 
     def __init__(self):
-        self.poa = po.OraclePoa()
+        self.poa = po.OraclePoa(mode=a.poa_type)
         self.events = []
         inner = self.poa._cons
         user = self.poa.ops.user
@@ -59,7 +68,7 @@ class LoggedPoa:
         return C.cast(C.pointer(self.ops), C.c_void_p)
 
 
-rs = c5.real_reads(NB, a.per)
+rs = c5.real_reads(NB, a.per, G)
 n_total = rs.n
 R = po.ReadSet.from_flat(rs.seq, rs.qual, rs.offs)
 R.score_sort(c5.K, c5.W)
@@ -95,7 +104,7 @@ for b in range(NB):
     log("leaf", r)
     batches.append(B)
     stores.append(g)
-    out[f"real{a.per}"] = rec
+    out[NAME] = rec
     json.dump(out, open(PATH, "w"), indent=1, sort_keys=True)
 
 gm = LoggedPoa()
@@ -112,6 +121,6 @@ r = record(batches[0], gm, st, time.time() - t0)
 r["left"], r["right"] = 0, 1
 rec["merges"].append(r)
 log("merge", r)
-out[f"real{a.per}"] = rec
+out[NAME] = rec
 json.dump(out, open(PATH, "w"), indent=1, sort_keys=True)
 log("done")
