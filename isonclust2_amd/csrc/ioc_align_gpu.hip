@@ -1559,6 +1559,7 @@ struct V2Dev {
     uint32_t* park;    // [count][pair slots of the slice]: parked by the first traceback launch
     uint32_t* early;   // ... and sent to the helper launch by k_fwd2_ends (wrong candidates, by their score)
     uint32_t* gate;    // workgroups of that launch that have started
+    uint32_t* split;   // per pair: V2_SPLIT_WORDS, where the walk's time went in either launch
     size_t resume_words;
 };
 
@@ -1590,7 +1591,8 @@ int v2_tables(ioc_ctx* c, const V2Plan& pl, uint32_t help_wgs, V2Dev& t)
     // per pair: its own scratch and 16 words of parked state and records; (the helper buffers belong to the second launch's
     // WORKGROUPS — one per compute unit — not to the pairs: 0.66 MB each)
     const size_t n_scratch = size_t(pl.max_pairs) + size_t(help_wgs) * V2_NHELP * V2_HBUF;
-    t.resume_words = size_t(np) * V2_RESUME_WORDS + 2u * (size_t(pl.max_pairs) + 1u) + 4u;  // (parked state, the two lists of walks for the helper launches)
+    // (parked state, the two lists of walks for the helper launches, the walks' time records)
+    t.resume_words = size_t(np) * V2_RESUME_WORDS + 2u * (size_t(pl.max_pairs) + 1u) + 4u + size_t(np) * V2_SPLIT_WORDS;
     if ((r = reserve(c, c->a_bnd, n_scratch * sizeof(V2Scratch) + t.resume_words * 4)) != IOC_OK) return r;
     t.scratch = static_cast<V2Scratch*>(c->a_bnd.p);
     t.hscratch = t.scratch + pl.max_pairs;
@@ -1598,6 +1600,7 @@ int v2_tables(ioc_ctx* c, const V2Plan& pl, uint32_t help_wgs, V2Dev& t)
     t.park = t.resume + size_t(np) * V2_RESUME_WORDS;
     t.early = t.park + size_t(pl.max_pairs) + 1u;
     t.gate = t.early + size_t(pl.max_pairs) + 1u;
+    t.split = t.gate + 4u;
     return IOC_OK;
 }
 
@@ -1681,11 +1684,11 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
         if (od)
             hipLaunchKernelGGL(k_trace2_help_ops, dim3(n_help), dim3(64 * V2_HWAVES), 0, hs, d_pairs, d_order + first_pair, d_pool, P,
                                static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.hscratch,
-                               t.resume, list, d_score, d_count, n_pairs, which, gate, *od);
+                               t.resume, list, t.split, d_score, d_count, n_pairs, which, gate, *od);
         else
             hipLaunchKernelGGL(k_trace2_help, dim3(n_help), dim3(64 * V2_HWAVES), 0, hs, d_pairs, d_order + first_pair, d_pool, P,
                                static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.hscratch,
-                               t.resume, list, d_score, d_count, n_pairs, which, gate);
+                               t.resume, list, t.split, d_score, d_count, n_pairs, which, gate);
     };
     if (o.side_help) {  // (issued before the first launch: its workgroups — a walker and ten helpers each — take their places first)
         ACHK(c, hipEventRecord(c->ev_side[0], s));
@@ -1699,11 +1702,11 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     if (od)
         hipLaunchKernelGGL(k_trace2_ops, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
                            static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.resume, t.park,
-                           d_score, d_count, n_pairs, o.deadline, o.deadline_cycles, *od);
+                           t.split, d_score, d_count, n_pairs, o.deadline, o.deadline_cycles, *od);
     else
         hipLaunchKernelGGL(k_trace2, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
                            static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.resume, t.park,
-                           d_score, d_count, n_pairs, o.deadline, o.deadline_cycles);
+                           t.split, d_score, d_count, n_pairs, o.deadline, o.deadline_cycles);
     ACHK(c, hipGetLastError());
     if (o.side_help) ACHK(c, hipStreamWaitEvent(s, c->ev_side[1], 0));  // (the two helper launches share the helpers' buffers)
     if (o.deadline) {  // (one workgroup per compute unit: a walker and its helpers fill one; more parked walks than that take turns)
@@ -1783,6 +1786,38 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
     }
     for (uint32_t x = 0; x < std::min(n_pairs, 10u); ++x) line("", ids[x]);
     for (uint32_t qx : {n_pairs / 4u, n_pairs / 2u, 3u * n_pairs / 4u}) line("rank", ids[qx]);
+    // where a walk's time goes, per launch: its blocks (waiting for a helper's, or recomputing), the recomputation of its tiles, its walk loop
+    std::vector<uint32_t> sw(size_t(np) * V2_SPLIT_WORDS);
+    ACHK(c, hipMemcpy(sw.data(), t.split, sw.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t l = 0; l < 2u; ++l) {
+        auto cyc = [&](uint32_t pid) { return double(rec(pid, l ? 12 : 8)) * 256.0; };
+        auto spl = [&](uint32_t pid, uint32_t w) { return sw[size_t(pid) * V2_SPLIT_WORDS + l * (V2_SPLIT_WORDS / 2u) + w]; };
+        std::vector<uint32_t> in;
+        for (uint32_t pid : ids)
+            if (rec(pid, l ? 12 : 8)) in.push_back(pid);
+        std::sort(in.begin(), in.end(), [&](uint32_t a, uint32_t b) { return cyc(a) > cyc(b); });
+        double tot[8] = {};
+        for (uint32_t pid : in) {
+            tot[0] += cyc(pid);
+            for (uint32_t w = 0; w < 3u; ++w) tot[1 + w] += double(spl(pid, w)) * 256.0;
+            tot[4] += double(spl(pid, 3) & 0xFFFFu);
+            tot[5] += double(spl(pid, 4));
+            tot[6] += double(spl(pid, 5));
+            tot[7] += double(spl(pid, 6));
+        }
+        const double nn = double(std::max<size_t>(1, in.size()));
+        fprintf(stderr, "[ioc] split of %s: %zu walks; mean %.3e cycles: blocks %.1f %%, tile recomputation %.1f %%, walk loop %.1f %%; %.1f cycles per tile step; "
+                        "blocks of <= 64 columns: %.2f per walk, %.1f %% of the block steps recomputed by walkers\n",
+                l ? "k_trace2_help" : "k_trace2", in.size(), tot[0] / nn, 100.0 * tot[1] / std::max(1.0, tot[0]), 100.0 * tot[2] / std::max(1.0, tot[0]),
+                100.0 * tot[3] / std::max(1.0, tot[0]), tot[2] / std::max(1.0, tot[7]), tot[4] / nn, 100.0 * tot[6] / std::max(1.0, tot[5]));
+        for (size_t x = 0; x < std::min<size_t>(in.size(), 10); ++x) {
+            const uint32_t pid = in[x];
+            const uint32_t nb = l ? rec(pid, 13) & 0xFFFFu : rec(pid, 9) & 0xFFFFu;
+            fprintf(stderr, "[ioc]   split pair %u: %.3e cycles: blocks %.3e, tiles %.3e, walk %.3e; blocks %u (<= 64 columns %u, <= 64 rows %u), own block steps %u (%u in thin), tiles %u, tile steps %u\n",
+                    pid, cyc(pid), double(spl(pid, 0)) * 256.0, double(spl(pid, 1)) * 256.0, double(spl(pid, 2)) * 256.0, nb, spl(pid, 3) & 0xFFFFu, spl(pid, 3) >> 16,
+                    spl(pid, 4), spl(pid, 5), rec(pid, l ? 14 : 10), spl(pid, 6));
+        }
+    }
     return IOC_OK;
 }
 

@@ -782,6 +782,10 @@ struct V2PairEnd {
 // per pair: i, j, state, window bits, pushed, count, flag (0 done / not parked, 1 parked by the first traceback launch, 2 sent to the
 // helper launch before any traceback: see k_fwd2_ends), - | the two launches' walk records (IOC_V2_TRACE_TIMES)
 constexpr uint32_t V2_RESUME_WORDS = 16;
+// ... and, in words of their own behind the lists of walks, where a walk's time went, per launch (IOC_V2_TRACE_TIMES): cycles / 256 for
+// its blocks (waiting or recomputing), its tiles' recomputation and its walk loop | blocks of <= 64 columns, << 16: of <= 64 rows |
+// systolic steps of the blocks it recomputed itself | ... of those of <= 64 columns | systolic steps of its tiles
+constexpr uint32_t V2_SPLIT_WORDS = 16;
 
 // After the probe launch (V2Couple): does either pair of the couple look like a wrong candidate?  Then the couple gets every tile.
 // And: at the score per row the probe saw, will the pairs beat the certificate of the corridor the host planned (half width B0)?
@@ -978,19 +982,21 @@ template <bool HELP, bool EMIT>
 __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__ order, const uint8_t* __restrict__ pool,
                                             const AlnParams& P, const uint32_t* __restrict__ arena, const V2Couple* __restrict__ couples, const V2PairCk* __restrict__ pck,
                                             const int4* __restrict__ ends, V2Scratch* __restrict__ scratch, V2Scratch* __restrict__ hscratch,
-                                            uint32_t* __restrict__ resume, uint32_t* __restrict__ park, int32_t* __restrict__ out_score,
-                                            uint32_t* __restrict__ out_count, const uint32_t count, const uint32_t max_blocks,
+                                            uint32_t* __restrict__ resume, uint32_t* __restrict__ park, uint32_t* __restrict__ split,
+                                            int32_t* __restrict__ out_score, uint32_t* __restrict__ out_count, const uint32_t count, const uint32_t max_blocks,
                                             const unsigned long long max_cycles, const uint32_t pslot, const uint32_t wv, const uint32_t want,
                                             const typename OpsOut<EMIT>::Dev od)
 {
     constexpr int NW = HELP ? int(V2_HWAVES) : TR_WAVES, NDIRS = HELP ? 1 : TR_WAVES;  // (only a walker keeps direction nibbles)
-    // LDS of a wave: the left column and the query bytes of the TILE the walk is in (walkers only), and ONE area that holds, by
-    // turns, what the recomputation of a block needs (its left column, its query codes, the profile of its columns: 8.5 KB) and the
-    // direction nibbles of a tile (8 KB) — a walker does the one, then the other.  10 KB per walker instead of 16.5: a compute
-    // unit that holds a workgroup of the helper launch still has room for one of the first launch (they run side by side).
+    // LDS of a wave: the left column and the query bytes of the TILE the walk is in (walkers only: one 12-byte record per row), and
+    // ONE area that holds, by turns, what the recomputation of a block needs (its left column, its query codes, the profile of its
+    // columns: 8.5 KB) and the direction nibbles of a tile (8 KB, and behind them the 128 reference bytes of the tile's columns: the
+    // walk tells identical from different bases by the bytes themselves) — a walker does the one, then the other.  10 KB per
+    // walker instead of 16.5: a compute unit that holds a workgroup of the helper launch still has room for one of the first
+    // launch (they run side by side).
     constexpr uint32_t B_LEFT = uint32_t(CK2) * 8u, B_Q = uint32_t(CK2) * 4u, B_PROF = 5u * 64u * uint32_t(V2_BLK_C / 4) * 4u;
     constexpr uint32_t D_BYTES = uint32_t(TILE) * uint32_t(TR_C) / 4u * 64u * 2u;
-    constexpr uint32_t U_BYTES = (B_LEFT + B_Q + B_PROF) > D_BYTES ? (B_LEFT + B_Q + B_PROF) : D_BYTES;
+    constexpr uint32_t U_BYTES = (B_LEFT + B_Q + B_PROF) > D_BYTES + uint32_t(TILE) ? (B_LEFT + B_Q + B_PROF) : D_BYTES + uint32_t(TILE);
     __shared__ __attribute__((aligned(16))) uint8_t s_union_all[NW][U_BYTES];
     __shared__ __attribute__((aligned(16))) uint8_t s_tile_all[NDIRS][uint32_t(TILE) * 12u];  // (walkers: the tile's left column, its query bytes)
     __shared__ uint32_t s_help[VH_COUNT];
@@ -999,8 +1005,13 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
     int2* const b_left = reinterpret_cast<int2*>(&s_union_all[wv][0]);                        // a block's left column
     uint32_t* const b_q = reinterpret_cast<uint32_t*>(&s_union_all[wv][B_LEFT]);             // ... its query bytes as profile-row offsets
     uint32_t* const b_prof = reinterpret_cast<uint32_t*>(&s_union_all[wv][B_LEFT + B_Q]);    // ... the query profile of its columns: [code][lane][V2_BLK_C / 4]
-    int2* const s_left = reinterpret_cast<int2*>(&s_tile_all[HELP ? 0u : wv][0]);            // a tile's left column
-    uint32_t* const s_q = reinterpret_cast<uint32_t*>(&s_tile_all[HELP ? 0u : wv][uint32_t(TILE) * 8u]);  // ... its query bytes
+    struct TRec {  // a tile's row as its first lane takes it in: (Hq, E*) of the column left of the tile, the query byte
+        int hq, e;
+        uint32_t q;
+    };
+    static_assert(sizeof(TRec) == 12, "a row's record");
+    TRec* const s_rec = reinterpret_cast<TRec*>(&s_tile_all[HELP ? 0u : wv][0]);
+    uint8_t* const s_rb = &s_union_all[wv][D_BYTES];  // ... and the reference bytes of its columns (behind the nibbles, for the walk)
     const uint32_t pid = order[pslot];
     const AlnPairDev pr = pairs[pid];
     const V2PairCk ck = pck[pid];
@@ -1015,6 +1026,19 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
     V2Scratch* scp = &scratch[pslot];  // where the current block's fine checkpoints are (a helper's buffer, when it made them)
     const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
     uint32_t n_blocks = 0, n_diag = 0, n_tiles = 0, n_gapsteps = 0;  // (IOC_V2_TRACE_TIMES: what this pair's walk was made of)
+    // ... and where its time went: getting a block (waiting for a helper's, or recomputing it), recomputing tiles, walking them
+    unsigned long long t_blk = 0, t_tile = 0, t_walk = 0;
+    uint32_t n_thin_c = 0, n_thin_r = 0, n_bsteps = 0, n_bsteps_thin = 0, n_tsteps = 0;  // (blocks of <= 64 columns / rows; systolic steps)
+    uint32_t* const sp = split + size_t(pid) * V2_SPLIT_WORDS + (HELP ? V2_SPLIT_WORDS / 2u : 0u);
+    auto split_out = [&]() {  // (lane 0, at the end of the walk in this launch)
+        sp[0] = uint32_t(t_blk >> 8);
+        sp[1] = uint32_t(t_tile >> 8);
+        sp[2] = uint32_t(t_walk >> 8);
+        sp[3] = n_thin_c | (n_thin_r << 16);
+        sp[4] = n_bsteps;
+        sp[5] = n_bsteps_thin;
+        sp[6] = n_tsteps;
+    };
     const uint32_t n = pr.n, m = pr.m;
     const int go = pr.gap_open, il = pr.ilimit;
     const uint8_t* __restrict__ q = pool + pr.q_off;
@@ -1072,7 +1096,12 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
 
     // the fine checkpoints of the block (Rb, Cb) — rows Rb + 1 .. Rb + brows, columns Cb + 1 .. Cb + bcols — recomputed into dst
     // from the coarse row above and the coarse column to the left (uses this wave's LDS: b_left, b_q, b_prof)
-    auto recompute_block = [&](const uint32_t Rb, const uint32_t Cb, const uint32_t brows, const uint32_t bcols, V2Scratch& dst) __attribute__((always_inline)) {
+    auto recompute_block_c = [&](auto cpl, const uint32_t Rb, const uint32_t Cb, const uint32_t brows, const uint32_t bcols, V2Scratch& dst) __attribute__((always_inline)) {
+        constexpr int BC = decltype(cpl)::value;  // columns per lane
+        // (an opaque copy: what a variant derives from the lane stays inside it.  Derived from `lane` itself it is hoisted out of the
+        // walk's loop for both variants at once — 144 registers in k_trace2_help instead of 111, and three helper waves and a
+        // first-launch wave no longer share a SIMD's 512)
+        const uint32_t ln = opaque(lane);
         // Corridor: a block lies in ONE tile of the forward pass (bands are whole coarse rows, a strip is two coarse columns); what
         // that tile took for "no score" because its neighbour above / to the left / above-left was not computed is "no score"
         // here too (the checkpoints of a skipped tile were never written)
@@ -1093,7 +1122,7 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             if (Rb && Cb) corner_ok = in(bt, pl);
         }
         // fine row 0 and fine column 0: the coarse checkpoints (or the matrix edges)
-        for (uint32_t x = lane; x <= bcols; x += 64) {  // entry x = column Cb + x (x = 0: left of the block)
+        for (uint32_t x = ln; x <= bcols; x += 64) {  // entry x = column Cb + x (x = 0: left of the block)
             int2 v;
             if (Rb == 0)
                 v = int2{ge * int(Cb + x) - gd, ALN_NEG};              // row 0: H = 0
@@ -1105,50 +1134,50 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
                 v = int2{ALN_NEG, ALN_NEG};
             dst.frow[0][x] = v;
         }
-        for (uint32_t y = lane; y < brows; y += 64) {  // entry y = row Rb + 1 + y
+        for (uint32_t y = ln; y < brows; y += 64) {  // entry y = row Rb + 1 + y
             int2 v{ge * int(Rb + y + 1) - gd, ALN_NEG};  // column 0: H = 0, no gap to extend
             if (Cb) v = left_ok ? coarse_col(Cb, Rb + y) : int2{ALN_NEG, ALN_NEG};
             dst.fcol[0][y] = v;
             b_left[y] = v;
             const uint32_t ch = q[Rb + y];
-            b_q[y] = (ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u) * uint32_t(64 * (V2_BLK_C / 4) * 4);  // byte offset of the profile row
+            b_q[y] = (ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u) * uint32_t(64 * (BC / 4) * 4);  // byte offset of the profile row
         }
-        for (uint32_t y = brows + lane; y < ((brows + 3u) & ~3u) + 4u && y < uint32_t(CK2); y += 64) {
+        for (uint32_t y = brows + ln; y < ((brows + 3u) & ~3u) + 4u && y < uint32_t(CK2); y += 64) {
             b_left[y] = int2{0, ALN_NEG};
             b_q[y] = 0;
         }
-        const uint32_t jb8 = Cb + lane * V2_BLK_C;
-        uint32_t rpk[V2_BLK_C / 4];
+        const uint32_t jb8 = Cb + ln * BC;
+        uint32_t rpk[BC / 4];
 #pragma unroll
-        for (int c4 = 0; c4 < V2_BLK_C / 4; ++c4) {
+        for (int c4 = 0; c4 < BC / 4; ++c4) {
             uint32_t w = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) w |= ref_byte(r, m, pr.rc, jb8 + c4 * 4 + e) << (8 * e);
             rpk[c4] = w;
         }
-        {   // the diagonal increments of this lane's 8 columns for each query base, four to a word (k_align_fwd's profile)
+        {   // the diagonal increments of this lane's BC columns for each query base, four to a word (k_align_fwd's profile)
             const uint32_t bases = 'A' | ('C' << 8) | ('G' << 16) | ('T' << 24);
 #pragma unroll
             for (int code = 0; code < 5; ++code) {
                 const uint32_t bq = code < 4 ? (bases >> (8 * code)) & 0xFFu : 0x100u;  // 0x100: equals no byte
 #pragma unroll
-                for (int c4 = 0; c4 < V2_BLK_C / 4; ++c4) {
+                for (int c4 = 0; c4 < BC / 4; ++c4) {
                     uint32_t w = 0;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) w |= uint32_t(((rpk[c4] >> (8 * e)) & 0xFFu) == bq ? K.cm : K.cx) << (8 * e);
-                    b_prof[(uint32_t(code) * 64u + lane) * uint32_t(V2_BLK_C / 4) + uint32_t(c4)] = w;
+                    b_prof[(uint32_t(code) * 64u + ln) * uint32_t(BC / 4) + uint32_t(c4)] = w;
                 }
             }
         }
-        const uint8_t* bprof = reinterpret_cast<const uint8_t*>(&b_prof[lane * uint32_t(V2_BLK_C / 4)]);
+        const uint8_t* bprof = reinterpret_cast<const uint8_t*>(&b_prof[ln * uint32_t(BC / 4)]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         tr_wave_sync();
-        int Hb[V2_BLK_C], Fb[V2_BLK_C];
+        int Hb[BC], Fb[BC];
         int dgb;
         {
-            const uint32_t x0 = lane * V2_BLK_C;  // this lane's first column is entry x0 + 1
+            const uint32_t x0 = ln * BC;  // this lane's first column is entry x0 + 1
 #pragma unroll
-            for (int c = 0; c < V2_BLK_C; ++c) {
+            for (int c = 0; c < BC; ++c) {
                 int2 v{0, ALN_NEG};
                 if (x0 + c + 1 <= bcols) v = v2_ld(&dst.frow[0][x0 + c + 1]);
                 Hb[c] = v.x;
@@ -1156,7 +1185,7 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             }
             dgb = x0 <= bcols ? v2_ld(&dst.frow[0][x0]).x : 0;
         }
-        const uint32_t nactb = (bcols + V2_BLK_C - 1) / V2_BLK_C;
+        const uint32_t nactb = (bcols + BC - 1) / BC;
         const uint32_t nblkb = (brows + FW_R - 1) / FW_R, nstepb = nblkb + nactb - 1u;
         int hl4[FW_R], el4[FW_R];
         uint32_t qc4[FW_R];
@@ -1169,8 +1198,8 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
         // lane 0's inputs of a step are read one step ahead, by every lane at one address
         uint4 nl0 = *reinterpret_cast<const uint4*>(&b_left[0]), nl1 = *reinterpret_cast<const uint4*>(&b_left[2]);
         uint4 nq4 = *reinterpret_cast<const uint4*>(&b_q[0]);
-        const bool fine_col_lane = ((lane + 1u) * V2_BLK_C) % TILE == 0 && (lane + 1u) * V2_BLK_C < uint32_t(CK2);
-        const uint32_t fine_col_k = ((lane + 1u) * V2_BLK_C) / TILE;
+        const bool fine_col_lane = ((ln + 1u) * BC) % TILE == 0 && (ln + 1u) * BC < uint32_t(CK2);
+        const uint32_t fine_col_k = ((ln + 1u) * BC) / TILE;
         for (uint32_t s = 0; s < nstepb; ++s) {
             {
                 const uint32_t h4[FW_R] = {nl0.x, nl0.z, nl1.x, nl1.z}, e4[FW_R] = {nl0.y, nl0.w, nl1.y, nl1.w},
@@ -1186,14 +1215,21 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
                 nl1 = *reinterpret_cast<const uint4*>(&b_left[sn + 2u]);
                 nq4 = *reinterpret_cast<const uint4*>(&b_q[sn]);
             }
-            const int bi = int(s) - int(lane);
-            if (bi >= 0 && uint32_t(bi) < nblkb && lane < nactb) {
+            const int bi = int(s) - int(ln);
+            if (bi >= 0 && uint32_t(bi) < nblkb && ln < nactb) {
 #pragma unroll
                 for (int rr = 0; rr < FW_R; ++rr) {
                     const int hl_in = hl4[rr];
-                    const uint2 xw2 = *reinterpret_cast<const uint2*>(bprof + qc4[rr]);
-                    const uint32_t xw[V2_BLK_C / 4] = {xw2.x, xw2.y};
-                    fwd_cells<V2_BLK_C, true>(Hb, Fb, xw, hl4[rr], el4[rr], dgb, qc4[rr], K);
+                    uint32_t xw[BC / 4];
+                    if constexpr (BC == 8) {
+                        const uint2 xw2 = *reinterpret_cast<const uint2*>(bprof + qc4[rr]);
+                        xw[0] = xw2.x;
+                        xw[1] = xw2.y;
+                    } else {
+                        static_assert(BC == 4, "one or two profile words per ln");
+                        xw[0] = *reinterpret_cast<const uint32_t*>(bprof + qc4[rr]);
+                    }
+                    fwd_cells<BC, true>(Hb, Fb, xw, hl4[rr], el4[rr], dgb, qc4[rr], K);
                     dgb = hl_in;
                 }
                 const uint32_t y0 = uint32_t(bi) * FW_R;  // block row index of the step's first row
@@ -1204,15 +1240,25 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
                 }
                 const uint32_t y1 = y0 + FW_R;  // rows of the block that are done
                 if ((y1 % TILE) == 0 && y1 < uint32_t(CK2) && y1 <= brows) {
-                    int2* fr = &dst.frow[y1 / TILE][1u + lane * V2_BLK_C];
+                    int2* fr = &dst.frow[y1 / TILE][1u + ln * BC];
 #pragma unroll
-                    for (int c = 0; c < V2_BLK_C; ++c) fr[c] = int2{Hb[c], Fb[c]};
-                    if (lane == 0) dst.frow[y1 / TILE][0] = int2{b_left[y1 - 1u].x, ALN_NEG};  // Hq(Rb + y1, Cb): the diagonal input
+                    for (int c = 0; c < BC; ++c) fr[c] = int2{Hb[c], Fb[c]};
+                    if (ln == 0) dst.frow[y1 / TILE][0] = int2{b_left[y1 - 1u].x, ALN_NEG};  // Hq(Rb + y1, Cb): the diagonal input
                 }
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         tr_wave_sync();
+    };
+
+    // A block's step costs what its 4 x BC cells per lane cost, and a block runs rows / 4 + lanes - 1 of them: a block clipped to
+    // half of its columns or fewer (every other block of a walk next to the diagonal is) takes 4 columns per lane — half the
+    // cells in a step, at most 32 steps more.  Same cells, same checkpoints at the same places.
+    auto recompute_block = [&](const uint32_t Rb, const uint32_t Cb, const uint32_t brows, const uint32_t bcols, V2Scratch& dst) __attribute__((always_inline)) {
+        if (bcols <= 64u * uint32_t(V2_BLK_C / 2))
+            recompute_block_c(std::integral_constant<int, V2_BLK_C / 2>{}, Rb, Cb, brows, bcols, dst);
+        else
+            recompute_block_c(std::integral_constant<int, V2_BLK_C>{}, Rb, Cb, brows, bcols, dst);
     };
 
     // verdict mode: the walk ends as soon as the count has reached stop_at (the windows still to come can only add) or cannot
@@ -1308,9 +1354,13 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
                     rs[9] = (n_blocks - 1u) | (n_diag << 16);
                     rs[10] = n_tiles;
                     rs[11] = n_gapsteps;
+                    split_out();
                 }
                 return;
             }
+            const unsigned long long t_blk0 = __builtin_amdgcn_s_memtime();
+            n_thin_c += bcols <= 64u ? 1u : 0u;
+            n_thin_r += brows <= 64u ? 1u : 0u;
             bool have = false;
             if (HELP && help_seq) {
                 // a helper's result for this block, out of the last two requests (help_seq: the one posted in the block before this)
@@ -1341,6 +1391,10 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             if (!have) {
                 scp = &scratch[pslot];
                 recompute_block(Rb, Cb, brows, bcols, *scp);
+                const uint32_t bcpl = bcols <= 64u * uint32_t(V2_BLK_C / 2) ? uint32_t(V2_BLK_C / 2) : uint32_t(V2_BLK_C);  // (recompute_block)
+                const uint32_t bsteps = (brows + FW_R - 1) / FW_R + (bcols + bcpl - 1u) / bcpl - 1u;
+                n_bsteps += bsteps;
+                n_bsteps_thin += bcols <= 64u ? bsteps : 0u;
             }
             if (HELP) {  // the blocks the walk can enter next: above and to the left of this one (entry point: the bounds of what they need)
                 v2_lds_store(help_addr + 4u * VH_RB, Rb);
@@ -1350,15 +1404,17 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
                 ++help_seq;
                 v2_lds_store(help_addr + 4u * VH_SEQ, help_seq);
             }
+            t_blk += __builtin_amdgcn_s_memtime() - t_blk0;
         }
         // ================= the tile (r0, c0) inside the block, as k_align_trace =================
         int cm = K.cm, cx = K.cx;
         asm volatile("" : "+v"(cm), "+v"(cx));
         const uint32_t kr = (r0 - Rb) / TILE, kc = (c0 - Cb) / TILE;
         ++n_tiles;
+        const unsigned long long t_tile0 = __builtin_amdgcn_s_memtime();
         for (uint32_t x = lane; x < rows; x += 64) {
-            s_q[x] = q[r0 + x];
-            s_left[x] = v2_ld(&scp->fcol[kc][(r0 - Rb) + x]);
+            const int2 v = v2_ld(&scp->fcol[kc][(r0 - Rb) + x]);
+            s_rec[x] = TRec{v.x, v.y, q[r0 + x]};
         }
         const uint32_t jb = c0 + lane * TR_C;  // columns to the left of this lane's block
         uint32_t rpk[1];
@@ -1368,6 +1424,13 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             for (int e = 0; e < TR_C; ++e) w |= ref_byte(r, m, pr.rc, jb + e) << (8 * e);
             rpk[0] = w;
         }
+        if (TR_C == 4)
+            reinterpret_cast<uint32_t*>(s_rb)[lane] = rpk[0];
+        else
+            reinterpret_cast<uint16_t*>(s_rb)[lane] = uint16_t(rpk[0]);
+        uint32_t rb[TR_C];
+#pragma unroll
+        for (int c = 0; c < TR_C; ++c) rb[c] = (rpk[0] >> (8 * c)) & 0xFFu;
         int Hp[TR_C], F[TR_C];  // (Hq, F*) of the row above
         int dg;
         {
@@ -1384,102 +1447,135 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
         tr_wave_sync();
         const uint32_t nact = (cols + TR_C - 1) / TR_C;
         const uint32_t nsteps = rows + nact - 1;
-        int out_h = 0, out_e = ALN_NEG;
-        uint32_t out_q = 0;
-        int2 nle = s_left[0];
-        uint32_t nq = s_q[0];
-        auto tstep = [&](const uint32_t s) __attribute__((always_inline)) {
-            int hl = int(from_left_or(uint32_t(out_h), uint32_t(nle.x)));
-            int el = int(from_left_or(uint32_t(out_e), uint32_t(nle.y)));
-            uint32_t qc = from_left_or(out_q, nq);
-            {
-                const uint32_t sn = s + 1u < rows ? s + 1u : rows - 1u;  // (rows past the end are never looked at)
-                nle = s_left[sn];
-                nq = s_q[sn];
-            }
-            const int ri = int(s) - int(lane);
-            if (ri >= 0 && uint32_t(ri) < rows && lane < nact) {
-                const int hl_in = hl;
-                uint32_t bits = 0;
+        // Lane l has row s - l at step s: it works while l <= s < l + rows.  The loop is peeled by what that takes: lanes still
+        // switching on (LO: l <= s is tested), all of them at work (nothing is), lanes switching off (HI: s - rows < l), and both
+        // at once in a tile of fewer rows than lanes.  Lane 0's inputs of step s + 1 — one record — are read at step s (PRE) while
+        // rows are left; the tile's last row and the steps behind it read nothing.  Every address is a pointer that runs along.
+        if (lane < nact) {
+            int out_h = 0, out_e = ALN_NEG;
+            uint32_t out_q = 0;
+            const TRec* rp = s_rec;
+            TRec nrec = rp[0];
+            uint8_t* dp = reinterpret_cast<uint8_t*>(&dirs[0][0]) + lane * uint32_t(TR_C / 2) - lane * (64u * uint32_t(TR_C / 2));  // (row s - lane, this lane's cells)
+            auto tstep = [&](auto lo, auto hi, auto pre, const uint32_t s) __attribute__((always_inline)) {
+                int hl = int(from_left_or(uint32_t(out_h), uint32_t(nrec.hq)));
+                int el = int(from_left_or(uint32_t(out_e), uint32_t(nrec.e)));
+                const uint32_t qc = from_left_or(out_q, nrec.q);
+                if (decltype(pre)::value) nrec = rp[1];
+                ++rp;
+                bool act = true;
+                if (decltype(lo)::value) act = lane <= s;
+                if (decltype(hi)::value) act = act && int(lane) > int(s) - int(rows);
+                if (act) {
+                    const int hl_in = hl;
+                    // a cell's nibble: 1 = not from the diagonal, 2 = nor from E (so from F), 4 = E extends, 8 = F extends; the cells
+                    // of a lane from the top of the byte down.  Each bit is the sign of a difference whose operands are ordered
+                    // (h >= hd, h >= E) or far from overflow (scores and ALN_NEG: |.| < 2^30), shifted in by one v_alignbit: no
+                    // compare, no mask register, no select.
+                    uint32_t acc = 0;
 #pragma unroll
-                for (int c = 0; c < TR_C; ++c) {
-                    const bool ex = el > hl;
-                    const int E = max(el, hl);
-                    const bool fx = F[c] > Hp[c];
-                    const int Fn = max(F[c], Hp[c]);
-                    const bool mt = qc == ((rpk[0] >> (8 * c)) & 0xFFu);
-                    const int hd = dg + (mt ? cm : cx);
-                    const int h = max(max(hd, E), Fn);
-                    // the host aligner's cell (ioc_align.cpp): H = diagonal, replaced by E if E > H, then by F if F > H
-                    const uint32_t from = h == hd ? (mt ? 0u : 3u << (4 * c)) : (h == E ? 1u << (4 * c) : 2u << (4 * c));
-                    bits |= from | (ex ? 4u << (4 * c) : 0u) | (fx ? 8u << (4 * c) : 0u);
-                    dg = Hp[c];
-                    Hp[c] = h - gd;
-                    F[c] = Fn;
-                    hl = h - gd;
-                    el = E;
+                    for (int c = 0; c < TR_C; ++c) {
+                        const int E = max(el, hl);
+                        const int Fn = max(F[c], Hp[c]);
+                        const int hd = dg + (qc == rb[c] ? cm : cx);
+                        // the host aligner's cell (ioc_align.cpp): H = diagonal, replaced by E if E > H, then by F if F > H
+                        const int h = max(max(hd, E), Fn);
+                        acc = __builtin_amdgcn_alignbit(acc, uint32_t(Hp[c]) - uint32_t(F[c]), 31);
+                        acc = __builtin_amdgcn_alignbit(acc, uint32_t(hl) - uint32_t(el), 31);
+                        acc = __builtin_amdgcn_alignbit(acc, uint32_t(E) - uint32_t(h), 31);
+                        acc = __builtin_amdgcn_alignbit(acc, uint32_t(hd) - uint32_t(h), 31);
+                        dg = Hp[c];
+                        Hp[c] = h - gd;
+                        F[c] = Fn;
+                        hl = h - gd;
+                        el = E;
+                    }
+                    dg = hl_in;
+                    if (TR_C == 4)
+                        *reinterpret_cast<uint16_t*>(dp) = uint16_t(acc);
+                    else
+                        *dp = uint8_t(acc);
                 }
-                dg = hl_in;
-                if (TR_C == 4)
-                    dirs[ri][lane] = uint16_t(bits);
-                else
-                    reinterpret_cast<uint8_t*>(&dirs[0][0])[uint32_t(ri) * 64u + lane] = uint8_t(bits);
-            }
-            out_h = hl;
-            out_e = el;
-            out_q = qc;
-        };
-        {
+                dp += 64u * uint32_t(TR_C / 2);
+                out_h = hl;
+                out_e = el;
+                out_q = qc;
+            };
+            auto run = [&](auto lo, auto hi, auto pre, uint32_t& s, const uint32_t end) __attribute__((always_inline)) {
+                for (; s + 1u < end; s += 2) {
+                    tstep(lo, hi, pre, s);
+                    tstep(lo, hi, pre, s + 1u);
+                }
+                if (s < end) {
+                    tstep(lo, hi, pre, s);
+                    ++s;
+                }
+            };
+            constexpr std::true_type yes{};
+            constexpr std::false_type no{};
             uint32_t s = 0;
-            for (; s + 1u < nsteps; s += 2) {
-                tstep(s);
-                tstep(s + 1u);
-            }
-            if (s < nsteps) tstep(s);
+            run(yes, no, yes, s, min(nact, rows) - 1u);
+            run(no, no, yes, s, rows - 1u);    // (rows > nact)
+            run(yes, yes, no, s, nact - 1u);   // (rows < nact)
+            run(no, yes, no, s, nsteps);
         }
         tr_wave_sync();
+        const unsigned long long t_walk0 = __builtin_amdgcn_s_memtime();
+        t_tile += t_walk0 - t_tile0;
+        n_tsteps += nsteps;
         // the host aligner's traceback loop inside this tile (identical in every lane)
+        auto nib = [&](uint32_t row, uint32_t col) {  // the nibble of the tile's cell (row, col), as the tile step packs it
+            const uint32_t sh = 4u * (uint32_t(TR_C) - 1u - col % TR_C);
+            return TR_C == 4 ? (uint32_t(dirs[row][col / TR_C]) >> sh) & 0xFu
+                             : (uint32_t(reinterpret_cast<const uint8_t*>(&dirs[0][0])[row * 64u + col / TR_C]) >> sh) & 0xFu;
+        };
         while (i > r0 && j > c0 && !decided) {
             const uint32_t cj = j - c0 - 1;
             const uint32_t ri = i - r0 - 1;
-            const uint32_t t = TR_C == 4 ? (uint32_t(dirs[ri][cj / TR_C]) >> (4 * (cj % TR_C))) & 0xFu
-                                         : (uint32_t(reinterpret_cast<const uint8_t*>(&dirs[0][0])[ri * 64u + cj / TR_C]) >> (4 * (cj % TR_C))) & 0xFu;
             if (state == 0) {
                 const bool inr = i - r0 > lane && j - c0 > lane;
                 uint32_t tl = 1u;
+                bool mtl = false;
                 if (inr) {
                     const uint32_t rl = ri - lane, cl = cj - lane;
-                    tl = (TR_C == 4 ? (uint32_t(dirs[rl][cl / TR_C]) >> (4 * (cl % TR_C)))
-                                    : (uint32_t(reinterpret_cast<const uint8_t*>(&dirs[0][0])[rl * 64u + cl / TR_C]) >> (4 * (cl % TR_C)))) & 3u;
+                    tl = nib(rl, cl);
+                    mtl = s_rec[rl].q == uint32_t(s_rb[cl]);  // (the tile step's own test: the query byte against ref_byte)
                 }
-                const bool dgl = inr && (tl == 0u || tl == 3u);
+                const bool dgl = inr && (tl & 1u) == 0u;
                 const unsigned long long dm = __ballot(dgl);
                 const uint32_t run = ~dm ? uint32_t(__builtin_ctzll(~dm)) : 64u;
                 if (run > 0) {
-                    const unsigned long long mb = __ballot(dgl && tl == 0u) & (run == 64u ? ~0ull : ((1ull << run) - 1ull));
+                    const unsigned long long mb = __ballot(dgl && mtl) & (run == 64u ? ~0ull : ((1ull << run) - 1ull));
                     ws.push_run(mb, run, kmask, k, il, lane);
                     ops.run(mb, run, lane);
                     i -= run;
                     j -= run;
                 } else {
-                    state = (t & 3u) == 1u ? 1 : 2;
+                    state = (uint32_t(__builtin_amdgcn_readfirstlane(int(tl))) & 2u) ? 2 : 1;
                 }
-            } else if (state == 1) {
-                ws.push(0u, kmask, k, il);
-                ops.step('D', lane);
-                if (!(t & 4u)) state = 0;
-                --j;
-                ++n_gapsteps;
             } else {
-                ws.push(0u, kmask, k, il);
-                ops.step('I', lane);
-                if (!(t & 8u)) state = 0;
-                --i;
-                ++n_gapsteps;
+                // a gap's steps at once: lane l looks at the l-th cell along the row (E, to the left) or the column (F, upwards); the
+                // gap takes the cell the walk is in and goes on while the cells' extension bits say so — as far as the tile reaches
+                const bool hor = state == 1;
+                const uint32_t avail = min(hor ? cj + 1u : ri + 1u, 64u);
+                bool ext = false;
+                if (lane < avail) ext = (nib(hor ? ri : ri - lane, hor ? cj - lane : cj) & (hor ? 4u : 8u)) != 0u;
+                const unsigned long long em = __ballot(ext);
+                const uint32_t reach = ~em ? uint32_t(__builtin_ctzll(~em)) : 64u;  // (<= avail: the lanes beyond say no)
+                const uint32_t g = reach < avail ? reach + 1u : avail;
+                if (reach < avail) state = 0;  // (the cell that does not extend is the gap's first: H from here on)
+                ws.push_run(0ull, g, kmask, k, il, lane);
+                ops.fill(hor ? 'D' : 'I', g, lane);
+                if (hor)
+                    j -= g;
+                else
+                    i -= g;
+                n_gapsteps += g;
             }
             decided = stop_at && (ws.cnt >= stop_at || cannot_reach(ws.cnt, i, j));
         }
         tr_wave_sync();
+        t_walk += __builtin_amdgcn_s_memtime() - t_walk0;
     }
     if (HELP) v2_lds_store(help_addr + 4u * VH_QUIT, 1u);  // (the helpers leave)
     if (!decided) ws.blanks(i + j, kmask, k, il);  // leading end gaps
@@ -1505,6 +1601,7 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             rs[11] = n_gapsteps;
             rs[15] = ws.cnt;
         }
+        split_out();
     }
 }
 
@@ -1526,18 +1623,19 @@ __global__ void k_trace2_gate(const uint32_t* __restrict__ early, const uint32_t
     const AlnPairDev *__restrict__ pairs, const uint32_t *__restrict__ order, const uint8_t *__restrict__ pool, AlnParams P,             \
         const uint32_t *__restrict__ arena, const V2Couple *__restrict__ couples, const V2PairCk *__restrict__ pck,                      \
         const int4 *__restrict__ ends, V2Scratch *__restrict__ scratch, uint32_t *__restrict__ resume, uint32_t *__restrict__ park,      \
-        int32_t *__restrict__ out_score, uint32_t *__restrict__ out_count, uint32_t count, uint32_t max_blocks, unsigned long long max_cycles
+        uint32_t *__restrict__ split, int32_t *__restrict__ out_score, uint32_t *__restrict__ out_count, uint32_t count, uint32_t max_blocks,             \
+        unsigned long long max_cycles
 __global__ void __launch_bounds__(64 * TR_WAVES) k_trace2(V2_TRACE_ARGS)
 {
     const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
-    trace2_body<false, false>(pairs, order, pool, P, arena, couples, pck, ends, scratch, nullptr, resume, park, out_score, out_count, count, max_blocks,
+    trace2_body<false, false>(pairs, order, pool, P, arena, couples, pck, ends, scratch, nullptr, resume, park, split, out_score, out_count, count, max_blocks,
                               max_cycles, blockIdx.x * TR_WAVES + wv, wv, 0u, NoOpsDev{});
 }
 // ... emitting (ioc_align_pairs_ops)
 __global__ void __launch_bounds__(64 * TR_WAVES) k_trace2_ops(V2_TRACE_ARGS, AlnOpsDev od)
 {
     const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
-    trace2_body<false, true>(pairs, order, pool, P, arena, couples, pck, ends, scratch, nullptr, resume, park, out_score, out_count, count, max_blocks,
+    trace2_body<false, true>(pairs, order, pool, P, arena, couples, pck, ends, scratch, nullptr, resume, park, split, out_score, out_count, count, max_blocks,
                              max_cycles, blockIdx.x * TR_WAVES + wv, wv, 0u, od);
 }
 
@@ -1547,8 +1645,8 @@ __global__ void __launch_bounds__(64 * TR_WAVES) k_trace2_ops(V2_TRACE_ARGS, Aln
     const AlnPairDev *__restrict__ pairs, const uint32_t *__restrict__ order, const uint8_t *__restrict__ pool, AlnParams P,             \
         const uint32_t *__restrict__ arena, const V2Couple *__restrict__ couples, const V2PairCk *__restrict__ pck,                      \
         const int4 *__restrict__ ends, V2Scratch *__restrict__ scratch, V2Scratch *__restrict__ hscratch, uint32_t *__restrict__ resume, \
-        uint32_t *__restrict__ park, int32_t *__restrict__ out_score, uint32_t *__restrict__ out_count, uint32_t count, uint32_t want,   \
-        uint32_t *__restrict__ gate
+        uint32_t *__restrict__ park, uint32_t *__restrict__ split, int32_t *__restrict__ out_score, uint32_t *__restrict__ out_count,    \
+        uint32_t count, uint32_t want, uint32_t *__restrict__ gate
 __global__ void __launch_bounds__(64 * V2_HWAVES) k_trace2_help(V2_HELP_ARGS)
 {
     const uint32_t wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
@@ -1557,7 +1655,7 @@ __global__ void __launch_bounds__(64 * V2_HWAVES) k_trace2_help(V2_HELP_ARGS)
     if (gate && threadIdx.x == 0) atomicAdd(gate, 1u);  // (this workgroup has its place on the chip: k_trace2_gate)
     for (uint32_t e = blockIdx.x; e < n_parked; e += gridDim.x) {
         const uint32_t pslot = uint32_t(__builtin_amdgcn_readfirstlane(int(park[1u + e])));
-        trace2_body<true, false>(pairs, order, pool, P, arena, couples, pck, ends, scratch, hscratch, resume, park, out_score, out_count, count, 0u, 0ull, pslot, wv,
+        trace2_body<true, false>(pairs, order, pool, P, arena, couples, pck, ends, scratch, hscratch, resume, park, split, out_score, out_count, count, 0u, 0ull, pslot, wv,
                                  want, NoOpsDev{});
         __syncthreads();  // (walker and helpers have left the pair: its LDS words are free)
     }
@@ -1572,7 +1670,7 @@ __global__ void __launch_bounds__(64 * V2_HWAVES) k_trace2_help_ops(V2_HELP_ARGS
     if (gate && threadIdx.x == 0) atomicAdd(gate, 1u);
     for (uint32_t e = blockIdx.x; e < n_parked; e += gridDim.x) {
         const uint32_t pslot = uint32_t(__builtin_amdgcn_readfirstlane(int(park[1u + e])));
-        trace2_body<true, true>(pairs, order, pool, P, arena, couples, pck, ends, scratch, hscratch, resume, park, out_score, out_count, count, 0u, 0ull, pslot, wv,
+        trace2_body<true, true>(pairs, order, pool, P, arena, couples, pck, ends, scratch, hscratch, resume, park, split, out_score, out_count, count, 0u, 0ull, pslot, wv,
                                 want, od);
         __syncthreads();
     }
