@@ -38,7 +38,7 @@ typedef enum {
     IOC_ERR_ARG = -1,       /* bad argument / shape */
     IOC_ERR_HIP = -2,       /* HIP runtime error (ioc_last_error has the text) */
     IOC_ERR_STATE = -3,     /* call order violated */
-    IOC_ERR_CAPACITY = -4,  /* a documented device-side limit was exceeded */
+    IOC_ERR_CAPACITY = -4,  /* a documented device-side limit was exceeded, or device memory ran out (the ioc_dist_* calls included) */
     IOC_ERR_TABLE = -5,     /* empirical probability table lookup failure (p_emp_prob.cpp:87-89) */
     IOC_ERR_NO_DEVICE = -6,
     IOC_ERR_INPUT = -7      /* input the reference would exit(1)/throw on */

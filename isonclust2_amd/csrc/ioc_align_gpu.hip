@@ -1087,40 +1087,12 @@ k_seq_flags(const uint8_t* __restrict__ pool, const int64_t* __restrict__ offs, 
     if (threadIdx.x == 0) flags[blockIdx.x] = uint8_t(s_any);
 }
 
-int reserve(ioc_ctx* c, DevBuf& b, size_t bytes)
-{
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return IOC_OK;
-    if (b.p) {
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return ioc_fail(c, IOC_ERR_HIP, "stream synchronize failed");
-        (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    const size_t want = bytes + bytes / 8 + 256;
-    const hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return ioc_fail(c, IOC_ERR_CAPACITY, "hipMalloc(" + std::to_string(want) + " B) failed: " + hipGetErrorString(e));
-    }
-    b.cap = want;
-    ioc_poison(b.p, want);
-    return IOC_OK;
-}
-
-#define ACHK(c, call)                                                                             \
-    do {                                                                                          \
-        hipError_t e__ = (call);                                                                  \
-        if (e__ != hipSuccess)                                                                    \
-            return ioc_fail((c), IOC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 #include "ioc_align_v2.inc"
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
 // events of a call's launches, three per slice: the forward pass, the traceback, the end (destroyed on every way out, the
-// ACHK returns included)
+// IOC_CHK returns included)
 struct EventSet {
     std::vector<hipEvent_t> v;
     ~EventSet()
@@ -1151,7 +1123,7 @@ int compute_units(const ioc_ctx* c)
 int ck_budget(ioc_ctx* c, uint64_t* budget)
 {
     size_t free_b = 0, total_b = 0;
-    ACHK(c, hipMemGetInfo(&free_b, &total_b));
+    IOC_CHK(c, hipMemGetInfo(&free_b, &total_b));
     *budget = uint64_t(free_b + c->a_ck.cap) / 2;
     if (const char* e = getenv("IOC_ALIGN_CK_BUDGET_MB")) *budget = uint64_t(atoll(e)) << 20;
     return IOC_OK;
@@ -1185,11 +1157,11 @@ struct OpsRun {
 int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes)
 {
     const size_t np = o.end.size(), tab = (np * 12 + 15) & ~size_t(15);
-    const int r = reserve(c, c->a_ops, tab + size_t(max_slice_bytes));
+    const int r = ioc_reserve(c, c->a_ops, tab + size_t(max_slice_bytes));
     if (r != IOC_OK) return r;
     uint8_t* p = static_cast<uint8_t*>(c->a_ops.p);
     o.dev = AlnOpsDev{p + tab, reinterpret_cast<const uint64_t*>(p), reinterpret_cast<uint32_t*>(p + np * 8)};
-    ACHK(c, hipMemcpyAsync(p, o.end.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(p, o.end.data(), np * 8, hipMemcpyHostToDevice, c->stream));
     return IOC_OK;
 }
 
@@ -1197,12 +1169,12 @@ int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes)
 // window or by the corridor's certificate; out of range: the walk of a forward pass that was given up) is left to its re-run.
 int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, uint32_t cnt, uint64_t bytes)
 {
-    ACHK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
     if (o.stage.size() < bytes) o.stage.resize(size_t(bytes));
-    ACHK(c, hipMemcpy(o.len.data(), o.dev.len, dp.size() * 4, hipMemcpyDeviceToHost));
-    ACHK(c, hipMemcpy(o.stage.data(), o.dev.buf, size_t(bytes), hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(o.len.data(), o.dev.len, dp.size() * 4, hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(o.stage.data(), o.dev.buf, size_t(bytes), hipMemcpyDeviceToHost));
     for (uint32_t x = 0; x < cnt; ++x) {
         const uint32_t pid = ord[x], i = o.back[pid];
         const uint64_t L = o.len[pid];
@@ -1567,33 +1539,32 @@ struct V2Dev {
 int v2_tables(ioc_ctx* c, const V2Plan& pl, uint32_t help_wgs, V2Dev& t)
 {
     hipStream_t s = c->stream;
-    int r;
     const uint32_t ncouples = pl.ncouples, np = pl.np;
     const size_t tab_bytes = size_t(ncouples) * sizeof(V2Couple) + size_t(np) * (sizeof(V2PairCk) + sizeof(V2PairEnd)) + size_t(pl.max_items) * sizeof(V2Item) + 256;
-    if ((r = reserve(c, c->a_cko, tab_bytes)) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_cko, tab_bytes));
     uint8_t* tb = static_cast<uint8_t*>(c->a_cko.p);
     t.cps = reinterpret_cast<V2Couple*>(tb);
     t.pck = reinterpret_cast<V2PairCk*>(tb + size_t(ncouples) * sizeof(V2Couple));
     t.pend = reinterpret_cast<V2PairEnd*>(reinterpret_cast<uint8_t*>(t.pck) + size_t(np) * sizeof(V2PairCk));
     t.items = reinterpret_cast<V2Item*>(reinterpret_cast<uint8_t*>(t.pend) + size_t(np) * sizeof(V2PairEnd));
-    ACHK(c, hipMemcpyAsync(t.cps, pl.cps.data(), size_t(ncouples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));
-    ACHK(c, hipMemcpyAsync(t.pck, pl.pck.data(), size_t(np) * sizeof(V2PairCk), hipMemcpyHostToDevice, s));
-    ACHK(c, hipMemcpyAsync(t.pend, pl.pend.data(), size_t(np) * sizeof(V2PairEnd), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(t.cps, pl.cps.data(), size_t(ncouples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(t.pck, pl.pck.data(), size_t(np) * sizeof(V2PairCk), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(t.pend, pl.pend.data(), size_t(np) * sizeof(V2PairEnd), hipMemcpyHostToDevice, s));
     // the query profiles of every (couple, strip) of a slice (made slice by slice, in front of the slice's forward pass)
-    if ((r = reserve(c, c->a_prof, size_t(pl.prof_total) * sizeof(uint4) + 256)) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_ends2, size_t(np) * sizeof(int4))) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_lrow, (size_t(pl.lrow_total) + pl.best_total + 16) * sizeof(int2))) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_prof, size_t(pl.prof_total) * sizeof(uint4) + 256));
+    IOC_TRY(ioc_reserve(c, c->a_ends2, size_t(np) * sizeof(int4)));
+    IOC_TRY(ioc_reserve(c, c->a_lrow, (size_t(pl.lrow_total) + pl.best_total + 16) * sizeof(int2)));
     t.lrow = static_cast<int2*>(c->a_lrow.p);
     t.best = t.lrow + pl.lrow_total;
     t.ctl_words = ((16 + 2 * size_t(pl.max_flags) + np + 1) & ~size_t(1)) + 2;
-    if ((r = reserve(c, c->a_xflags, t.ctl_words * 4)) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_xflags, t.ctl_words * 4));
     t.ctl = static_cast<uint32_t*>(c->a_xflags.p);
     // per pair: its own scratch and 16 words of parked state and records; (the helper buffers belong to the second launch's
     // WORKGROUPS — one per compute unit — not to the pairs: 0.66 MB each)
     const size_t n_scratch = size_t(pl.max_pairs) + size_t(help_wgs) * V2_NHELP * V2_HBUF;
     // (parked state, the two lists of walks for the helper launches, the walks' time records)
     t.resume_words = size_t(np) * V2_RESUME_WORDS + 2u * (size_t(pl.max_pairs) + 1u) + 4u + size_t(np) * V2_SPLIT_WORDS;
-    if ((r = reserve(c, c->a_bnd, n_scratch * sizeof(V2Scratch) + t.resume_words * 4)) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_bnd, n_scratch * sizeof(V2Scratch) + t.resume_words * 4));
     t.scratch = static_cast<V2Scratch*>(c->a_bnd.p);
     t.hscratch = t.scratch + pl.max_pairs;
     t.resume = reinterpret_cast<uint32_t*>(t.scratch + n_scratch);
@@ -1642,19 +1613,19 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     // publishes its progress every block of 64 rows)
     const bool few_couples = n_couples <= o.few_limit;
     const uint32_t prog_every = few_couples ? 1u : 0u;
-    ACHK(c, hipMemcpyAsync(t.items, pl.items[si].data(), size_t(n_items) * sizeof(V2Item), hipMemcpyHostToDevice, s));
-    ACHK(c, hipMemcpyAsync(t.cps + k_first, pl.cps.data() + k_first, size_t(n_couples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));  // (flag0)
+    IOC_CHK(c, hipMemcpyAsync(t.items, pl.items[si].data(), size_t(n_items) * sizeof(V2Item), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(t.cps + k_first, pl.cps.data() + k_first, size_t(n_couples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));  // (flag0)
     hipLaunchKernelGGL(k_fwd2_prof, dim3(n_couples, pl.max_strips), dim3(128), 0, s, d_pairs, t.cps + k_first, d_pool, P, static_cast<uint4*>(c->a_prof.p));
-    ACHK(c, hipGetLastError());
-    ACHK(c, hipMemsetAsync(d_ctl, 0, t.ctl_words * 4, s));
-    ACHK(c, hipMemsetAsync(t.resume, 0, t.resume_words * 4, s));  // (parked state and the two lists of walks; k_fwd2_ends writes into them)
+    IOC_CHK(c, hipGetLastError());
+    IOC_CHK(c, hipMemsetAsync(d_ctl, 0, t.ctl_words * 4, s));
+    IOC_CHK(c, hipMemsetAsync(t.resume, 0, t.resume_words * 4, s));  // (parked state and the two lists of walks; k_fwd2_ends writes into them)
     if (pl.tiles_skipped)  // (the bests of the last row and the last column that a skipped tile does not write: far below any score)
-        ACHK(c, hipMemsetAsync(t.lrow, 0x80, (size_t(pl.lrow_total) + pl.best_total) * sizeof(int2), s));
+        IOC_CHK(c, hipMemsetAsync(t.lrow, 0x80, (size_t(pl.lrow_total) + pl.best_total) * sizeof(int2), s));
     if (getenv("IOC_ALIGN_V2_FAKE_TIMEOUT")) {  // (tests: as if a bounded wait had run out — every later wait gives up at once,
         const uint32_t one = 1;                 // tiles run on whatever is there, the host must fall back to version 1)
-        ACHK(c, hipMemcpyAsync(d_ctl + 1, &one, 4, hipMemcpyHostToDevice, s));
+        IOC_CHK(c, hipMemcpyAsync(d_ctl + 1, &one, 4, hipMemcpyHostToDevice, s));
     }
-    ACHK(c, hipEventRecord(ev[0], s));
+    IOC_CHK(c, hipEventRecord(ev[0], s));
     // persistent waves: as many workgroups as the chip holds, but no more waves than tiles
     auto fwd = [&](decltype(&k_fwd2) kernel, uint32_t n_wg, const V2Item* items, uint32_t n) {
         hipLaunchKernelGGL(kernel, dim3(n_wg), dim3(64 * V2_WAVES), 0, s, d_pairs, t.cps, items, n, d_ctl, d_ctl + 16, d_ctl + 1, d_pool, P,
@@ -1664,21 +1635,21 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     };
     if (n_probe) {  // the probe launch and its verdicts (V2Couple): all on the device, nothing comes back to the host
         fwd(k_fwd2, std::max(1u, std::min(uint32_t(o.occ) * uint32_t(o.n_cu), (n_probe + V2_WAVES - 1) / V2_WAVES)), t.items, n_probe);
-        ACHK(c, hipGetLastError());
+        IOC_CHK(c, hipGetLastError());
         hipLaunchKernelGGL(k_fwd2_probe, dim3(n_couples), dim3(64), 0, s, d_pairs, t.cps + k_first, t.pend, static_cast<const uint32_t*>(c->a_ck.p), P);
-        ACHK(c, hipGetLastError());
-        ACHK(c, hipMemsetAsync(d_ctl, 0, 4, s));  // (the queue's counter; the flags of the probe's tiles stay)
+        IOC_CHK(c, hipGetLastError());
+        IOC_CHK(c, hipMemsetAsync(d_ctl, 0, 4, s));  // (the queue's counter; the flags of the probe's tiles stay)
     }
     const uint32_t n_main = n_items - n_probe, per_cu = v2_per_cu(pl, si, o, few_couples);
     const uint32_t n_wg = std::max(1u, std::min(per_cu * uint32_t(o.n_cu), (n_main + V2_WAVES - 1) / V2_WAVES));
     // (two workgroups per CU: the build of the kernel that may use the registers of the third)
     fwd((per_cu <= 2 && !getenv("IOC_ALIGN_V2_NO_W2")) ? k_fwd2_w2 : k_fwd2, n_wg, t.items + n_probe, n_main);
-    ACHK(c, hipGetLastError());
+    IOC_CHK(c, hipGetLastError());
     const uint32_t n_help = std::min<uint32_t>(n_pairs, o.help_wgs);
     hipLaunchKernelGGL(k_fwd2_ends, dim3(n_pairs), dim3(64), 0, s, d_pairs, t.cps, d_order + first_pair, n_pairs, t.pend, t.lrow, t.best,
                        d_ctl + 16 + 2 * pl.max_flags, static_cast<int4*>(c->a_ends2.p), t.resume, t.early, o.side_help ? int(P.match) : 0, n_help);
-    ACHK(c, hipGetLastError());
-    ACHK(c, hipEventRecord(ev[1], s));
+    IOC_CHK(c, hipGetLastError());
+    IOC_CHK(c, hipEventRecord(ev[1], s));
     // the traceback in two launches: walks that need more than `deadline` blocks go on in the second one, with helper waves
     auto help = [&](hipStream_t hs, uint32_t* list, uint32_t which, uint32_t* gate) {
         if (od)
@@ -1691,13 +1662,13 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
                                t.resume, list, t.split, d_score, d_count, n_pairs, which, gate);
     };
     if (o.side_help) {  // (issued before the first launch: its workgroups — a walker and ten helpers each — take their places first)
-        ACHK(c, hipEventRecord(c->ev_side[0], s));
-        ACHK(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
+        IOC_CHK(c, hipEventRecord(c->ev_side[0], s));
+        IOC_CHK(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
         help(c->side_stream, t.early, 2u, t.gate);
-        ACHK(c, hipGetLastError());
-        ACHK(c, hipEventRecord(c->ev_side[1], c->side_stream));
+        IOC_CHK(c, hipGetLastError());
+        IOC_CHK(c, hipEventRecord(c->ev_side[1], c->side_stream));
         hipLaunchKernelGGL(k_trace2_gate, dim3(1), dim3(1), 0, s, t.early, t.gate, n_help);
-        ACHK(c, hipGetLastError());
+        IOC_CHK(c, hipGetLastError());
     }
     if (od)
         hipLaunchKernelGGL(k_trace2_ops, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
@@ -1707,17 +1678,17 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
         hipLaunchKernelGGL(k_trace2, dim3((n_pairs + TR_WAVES - 1) / TR_WAVES), dim3(64 * TR_WAVES), 0, s, d_pairs, d_order + first_pair, d_pool, P,
                            static_cast<const uint32_t*>(c->a_ck.p), t.cps, t.pck, static_cast<const int4*>(c->a_ends2.p), t.scratch, t.resume, t.park,
                            t.split, d_score, d_count, n_pairs, o.deadline, o.deadline_cycles);
-    ACHK(c, hipGetLastError());
-    if (o.side_help) ACHK(c, hipStreamWaitEvent(s, c->ev_side[1], 0));  // (the two helper launches share the helpers' buffers)
+    IOC_CHK(c, hipGetLastError());
+    if (o.side_help) IOC_CHK(c, hipStreamWaitEvent(s, c->ev_side[1], 0));  // (the two helper launches share the helpers' buffers)
     if (o.deadline) {  // (one workgroup per compute unit: a walker and its helpers fill one; more parked walks than that take turns)
         help(s, t.park, 1u, nullptr);
-        ACHK(c, hipGetLastError());
+        IOC_CHK(c, hipGetLastError());
     }
-    ACHK(c, hipEventRecord(ev[2], s));
+    IOC_CHK(c, hipEventRecord(ev[2], s));
     unsigned long long cells_done = 0;
-    ACHK(c, hipMemcpyAsync(xe, d_ctl + 1, 4, hipMemcpyDeviceToHost, s));
-    ACHK(c, hipMemcpyAsync(&cells_done, d_ctl + t.ctl_words - 2, 8, hipMemcpyDeviceToHost, s));
-    ACHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipMemcpyAsync(xe, d_ctl + 1, 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipMemcpyAsync(&cells_done, d_ctl + t.ctl_words - 2, 8, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     c->tm.n_align_cells_computed += int64_t(cells_done);
     return IOC_OK;
 }
@@ -1732,7 +1703,7 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
     const uint32_t np = pl.np, first_pair = 2u * pl.slices[si].first;
     const uint32_t n_pairs = std::min(pl.cnt, 2u * (pl.slices[si].first + pl.slices[si].second)) - first_pair;
     std::vector<int4> he(np);
-    ACHK(c, hipMemcpy(he.data(), c->a_ends2.p, size_t(np) * sizeof(int4), hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(he.data(), c->a_ends2.p, size_t(np) * sizeof(int4), hipMemcpyDeviceToHost));
     if (rates)
         for (uint32_t x = 0; x < n_pairs; ++x) {
             const uint32_t pid = order[first_pair + x];
@@ -1742,7 +1713,7 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
         }
     if (!times) return IOC_OK;
     std::vector<uint32_t> rw(size_t(np) * V2_RESUME_WORDS);
-    ACHK(c, hipMemcpy(rw.data(), t.resume, rw.size() * 4, hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(rw.data(), t.resume, rw.size() * 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> ids(n_pairs);
     for (uint32_t x = 0; x < n_pairs; ++x) ids[x] = order[first_pair + x];
     // (first launch + second launch: the second starts when the first has ended, so the sum orders the pairs by what they cost)
@@ -1788,7 +1759,7 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
     for (uint32_t qx : {n_pairs / 4u, n_pairs / 2u, 3u * n_pairs / 4u}) line("rank", ids[qx]);
     // where a walk's time goes, per launch: its blocks (waiting for a helper's, or recomputing), the recomputation of its tiles, its walk loop
     std::vector<uint32_t> sw(size_t(np) * V2_SPLIT_WORDS);
-    ACHK(c, hipMemcpy(sw.data(), t.split, sw.size() * 4, hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(sw.data(), t.split, sw.size() * 4, hipMemcpyDeviceToHost));
     for (uint32_t l = 0; l < 2u; ++l) {
         auto cyc = [&](uint32_t pid) { return double(rec(pid, l ? 12 : 8)) * 256.0; };
         auto spl = [&](uint32_t pid, uint32_t w) { return sw[size_t(pid) * V2_SPLIT_WORDS + l * (V2_SPLIT_WORDS / 2u) + w]; };
@@ -1868,7 +1839,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
         if ((r = ops_reserve(c, *ops, most)) != IOC_OK) return r;
     }
     const auto t_res0 = std::chrono::steady_clock::now();
-    if ((r = reserve(c, c->a_ck, size_t(pl.arena_words) * 4)) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_ck, size_t(pl.arena_words) * 4));
     c->tm.align_arena_bytes = int64_t(pl.arena_words) * 4;
     c->tm.align_slices = int32_t(pl.slices.size());
     c->tm.align_version = 2;
@@ -1889,12 +1860,12 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     // pair's latency long, with the chip half empty — no longer waits for them to reach their deadline first.
     o.side_help = o.deadline && !(getenv("IOC_TRACE2_EARLY") && atoi(getenv("IOC_TRACE2_EARLY")) == 0);
     if (o.side_help && !c->side_stream) {
-        ACHK(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-        for (auto& e : c->ev_side) ACHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        IOC_CHK(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+        for (auto& e : c->ev_side) IOC_CHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     EventSet evs;
     evs.v.assign(pl.slices.size() * 3, nullptr);
-    for (auto& e : evs.v) ACHK(c, hipEventCreate(&e));
+    for (auto& e : evs.v) IOC_CHK(c, hipEventCreate(&e));
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner v2: planning (couples, corridors, tile lists, tables) took the host %.3f ms\n",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan0).count());
@@ -2107,15 +2078,14 @@ int run_carry(ioc_ctx* c, const AlnBatch& b, uint32_t waves, const AlnParams& P,
     const uint64_t budget = 8ull << 30;
     const uint64_t per_pair = (bnd_stride + lrow_stride) * 4ull;
     const uint32_t slice = uint32_t(std::min<uint64_t>(np, std::max<uint64_t>(1, budget / per_pair)));
-    int r;
-    if ((r = reserve(c, c->a_bnd, size_t(slice) * bnd_stride * 4)) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_lrow, size_t(slice) * lrow_stride * 4)) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_bnd, size_t(slice) * bnd_stride * 4));
+    IOC_TRY(ioc_reserve(c, c->a_lrow, size_t(slice) * lrow_stride * 4));
     for (uint32_t first = 0; first < np; first += slice) {
         const uint32_t cnt = std::min(slice, np - first);
         hipLaunchKernelGGL(k_align_carry, dim3(cnt), dim3(NT), 0, c->stream, static_cast<const AlnPairDev*>(c->a_pairs.p),
                            static_cast<const uint32_t*>(c->a_order.p) + first, static_cast<const uint8_t*>(c->a_pool.p), P,
                            static_cast<uint32_t*>(c->a_bnd.p), bnd_stride, static_cast<uint32_t*>(c->a_lrow.p), lrow_stride, d_score, d_count);
-        ACHK(c, hipGetLastError());
+        IOC_CHK(c, hipGetLastError());
     }
     return IOC_OK;
 }
@@ -2207,7 +2177,7 @@ struct V1Fwd {
         else
             hipLaunchKernelGGL(k_align_fwd<false>, dim3(nwg), dim3(wgw * 64), lds, c->stream, dpairs, o, cnt, wv, nmain, wtail, dpool, P, dck, dcko, lr,
                                lrow_stride, dends, X);
-        ACHK(c, hipGetLastError());
+        IOC_CHK(c, hipGetLastError());
         return IOC_OK;
     }
 };
@@ -2231,11 +2201,11 @@ int v1_cross_tail(ioc_ctx* c, const AlnBatch& b, const V1Fwd& fwd, const std::pa
     X.flag_stride = nb * strips;
     const size_t fbytes = size_t(rest) * X.flag_stride * 4, bbytes = size_t(rest) * nb * sizeof(int2);
     int r;
-    if ((r = reserve(c, c->a_xflags, fbytes + bbytes + 64)) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_xflags, fbytes + bbytes + 64));
     X.err = static_cast<uint32_t*>(c->a_xflags.p);
     X.flags = X.err + 16;
     X.best = reinterpret_cast<int2*>(reinterpret_cast<uint8_t*>(c->a_xflags.p) + 64 + fbytes);
-    ACHK(c, hipMemsetAsync(c->a_xflags.p, 0, 64 + fbytes, s));
+    IOC_CHK(c, hipMemsetAsync(c->a_xflags.p, 0, 64 + fbytes, s));
     if (inl && first_cnt) {
         // one launch: ordinary workgroups, then the split pairs behind them
         X.first_wg = n_main;
@@ -2249,8 +2219,8 @@ int v1_cross_tail(ioc_ctx* c, const AlnBatch& b, const V1Fwd& fwd, const std::pa
         if ((r = fwd(ord + first_cnt, rest, 4, 4, rest * groups, rest * groups, 4, xlds, first_cnt, X)) != IOC_OK) return r;
     }
     uint32_t xe = 0;
-    ACHK(c, hipMemcpyAsync(&xe, X.err, 4, hipMemcpyDeviceToHost, s));
-    ACHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipMemcpyAsync(&xe, X.err, 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     if (xe) {  // a wait ran out: the tail again, the usual way
         if ((r = fwd(ord + first_cnt, rest, 4, 4, rest, rest, 4, 0, first_cnt, AlnCross{})) != IOC_OK) return r;
         c->tm.n_align_refused += rest;
@@ -2296,7 +2266,7 @@ int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>&
         lds_pad = want > stat + 1024 ? (want - stat - 512) & ~size_t(255) : 0;
         lds_pad = std::min(lds_pad, lim > 1 ? lim : 0);
     }
-    ACHK(c, hipEventRecord(ev[0], s));
+    IOC_CHK(c, hipEventRecord(ev[0], s));
     // The tail generation runs on a mostly empty chip: its pairs are split over SEVERAL workgroups each
     // (4 x 4 = 16 bands on 4 CUs; an 8-wave workgroup lands on one CU, two waves per SIMD, and was slower).
     uint32_t groups = 1;
@@ -2336,7 +2306,7 @@ int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>&
         }
         if ((r = fwd(ord, sl.second, waves, wg_waves, n_wg, n_main, wpp_tail, lds_pad, 0, AlnCross{})) != IOC_OK) return r;
     }
-    ACHK(c, hipEventRecord(ev[1], s));
+    IOC_CHK(c, hipEventRecord(ev[1], s));
     const uint32_t tr_wg = (sl.second + TR_WAVES - 1) / TR_WAVES;  // (an LDS reservation that caps the workgroups per CU changed nothing here)
     if (od)
         hipLaunchKernelGGL(k_align_trace_ops, dim3(tr_wg), dim3(64 * TR_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), ord,
@@ -2346,8 +2316,8 @@ int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>&
         hipLaunchKernelGGL(k_align_trace, dim3(tr_wg), dim3(64 * TR_WAVES), 0, s, static_cast<const AlnPairDev*>(c->a_pairs.p), ord,
                            static_cast<const uint8_t*>(c->a_pool.p), P, static_cast<const int2*>(c->a_ck.p), static_cast<const AlnCk*>(c->a_cko.p),
                            static_cast<const int4*>(c->a_ends2.p), d_score, d_count, sl.second);
-    ACHK(c, hipGetLastError());
-    ACHK(c, hipEventRecord(ev[2], s));
+    IOC_CHK(c, hipGetLastError());
+    IOC_CHK(c, hipEventRecord(ev[2], s));
     return IOC_OK;
 }
 
@@ -2373,26 +2343,26 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
         if ((r = ops_reserve(c, ops, pl.ops_most)) != IOC_OK) return r;
     }
     const auto t_res0 = std::chrono::steady_clock::now();
-    if ((r = reserve(c, c->a_ck, size_t(pl.arena) * 8)) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_ck, size_t(pl.arena) * 8));
     c->tm.align_arena_bytes = int64_t(pl.arena) * 8;
     c->tm.align_slices = int32_t(pl.slices.size());
     c->tm.align_version = 1;
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: checkpoint arena %.1f MB (%zu slice(s)) reserved in %.3f ms\n", double(pl.arena) * 8e-6, pl.slices.size(),
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_res0).count());
-    if ((r = reserve(c, c->a_cko, size_t(np) * sizeof(AlnCk))) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_ends2, size_t(np) * sizeof(int4))) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_lrow, size_t(pl.max_cnt) * lrow_stride * 8)) != IOC_OK) return r;
-    ACHK(c, hipMemcpyAsync(c->a_cko.p, pl.cko.data(), size_t(np) * sizeof(AlnCk), hipMemcpyHostToDevice, s));
+    IOC_TRY(ioc_reserve(c, c->a_cko, size_t(np) * sizeof(AlnCk)));
+    IOC_TRY(ioc_reserve(c, c->a_ends2, size_t(np) * sizeof(int4)));
+    IOC_TRY(ioc_reserve(c, c->a_lrow, size_t(pl.max_cnt) * lrow_stride * 8));
+    IOC_CHK(c, hipMemcpyAsync(c->a_cko.p, pl.cko.data(), size_t(np) * sizeof(AlnCk), hipMemcpyHostToDevice, s));
     const int n_cu = compute_units(c);
     EventSet evs;
     evs.v.assign(pl.slices.size() * 3, nullptr);
-    for (auto& e : evs.v) ACHK(c, hipEventCreate(&e));
+    for (auto& e : evs.v) IOC_CHK(c, hipEventCreate(&e));
     for (size_t si = 0; si < pl.slices.size(); ++si) {
         if ((r = v1_slice(c, b, pl.slices[si], wp, P, n_cu, lrow_stride, d_score, d_count, &evs.v[3 * si], oh ? &ops.dev : nullptr)) != IOC_OK) return r;
         if (oh && (r = ops_fetch(c, ops, b.dp, b.order.data() + pl.slices[si].first, pl.slices[si].second, pl.slice_ops[si])) != IOC_OK) return r;
     }
-    ACHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     add_elapsed(c, evs.v, evs.v.size());
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: forward %.3f ms, traceback %.3f ms (device, all slices so far)\n", c->tm.ms_align_fwd, c->tm.ms_align_trace);
@@ -2432,9 +2402,9 @@ int read_results(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const int32_t* d_
         c->tm.n_align_cells_computed += int64_t(b.dp[b.order[x]].n) * int64_t(b.dp[b.order[x]].m);
     hs.resize(np);
     hc.resize(np);
-    ACHK(c, hipMemcpyAsync(hs.data(), d_score, size_t(np) * 4, hipMemcpyDeviceToHost, c->stream));
-    ACHK(c, hipMemcpyAsync(hc.data(), d_count, size_t(np) * 4, hipMemcpyDeviceToHost, c->stream));
-    ACHK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipMemcpyAsync(hs.data(), d_score, size_t(np) * 4, hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(hc.data(), d_count, size_t(np) * 4, hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     return IOC_OK;
 }
 
@@ -2514,7 +2484,7 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
 {
     if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs)) return IOC_ERR_ARG;
     if (k < 1 || k > 32) return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: window length k must be in 1..32");
-    ACHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     if (n_pairs == 0) return IOC_OK;
     const AlnParams P{match, mismatch, gap_extend, uint32_t(k), 1u << (32 - k)};
     AlnBatch b;
@@ -2526,11 +2496,11 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     const char* ev = getenv("IOC_ALIGN_VARIANT");
     const bool carry = ev && strcmp(ev, "carry") == 0 && !out.ops;  // (the carry variant has no walk: an emitting call takes the traced route)
     const WavePlan wp = plan_waves(b, carry);
-    if ((r = reserve(c, c->a_pairs, size_t(np) * sizeof(AlnPairDev))) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_order, size_t(np) * 4)) != IOC_OK) return r;
-    if ((r = reserve(c, c->a_out, size_t(np) * 8)) != IOC_OK) return r;
-    ACHK(c, hipMemcpyAsync(c->a_pairs.p, b.dp.data(), size_t(np) * sizeof(AlnPairDev), hipMemcpyHostToDevice, c->stream));
-    ACHK(c, hipMemcpyAsync(c->a_order.p, b.order.data(), size_t(np) * 4, hipMemcpyHostToDevice, c->stream));
+    IOC_TRY(ioc_reserve(c, c->a_pairs, size_t(np) * sizeof(AlnPairDev)));
+    IOC_TRY(ioc_reserve(c, c->a_order, size_t(np) * 4));
+    IOC_TRY(ioc_reserve(c, c->a_out, size_t(np) * 8));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pairs.p, b.dp.data(), size_t(np) * sizeof(AlnPairDev), hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(c->a_order.p, b.order.data(), size_t(np) * 4, hipMemcpyHostToDevice, c->stream));
     int32_t* d_score = static_cast<int32_t*>(c->a_out.p);
     uint32_t* d_count = reinterpret_cast<uint32_t*>(d_score + np);
     const char* arena_mode = getenv("IOC_ALIGN_ARENA");
@@ -2557,7 +2527,7 @@ extern "C" {
 int ioc_align_set_pool(ioc_ctx* c, int32_t n_seqs, const char* seqs, const int64_t* offs)
 {
     if (!c || n_seqs < 0 || (n_seqs > 0 && (!seqs || !offs))) return IOC_ERR_ARG;
-    ACHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     c->res_pool_ready = false;
     c->aln_offs.assign(offs, offs + (n_seqs > 0 ? n_seqs + 1 : 0));
     if (n_seqs == 0) return IOC_OK;
@@ -2566,20 +2536,20 @@ int ioc_align_set_pool(ioc_ctx* c, int32_t n_seqs, const char* seqs, const int64
         if (offs[i + 1] < offs[i]) return ioc_fail(c, IOC_ERR_ARG, "sequence pool offsets must be ascending");
     const int64_t total = offs[n_seqs];
     if (total >= (int64_t(1) << 32)) return ioc_fail(c, IOC_ERR_CAPACITY, "sequence pool above 4 GiB");
-    int r = reserve(c, c->a_pool, size_t(total));
+    int r = ioc_reserve(c, c->a_pool, size_t(total));
     if (r != IOC_OK) return r;
-    ACHK(c, hipMemcpyAsync(c->a_pool.p, seqs, size_t(total), hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pool.p, seqs, size_t(total), hipMemcpyHostToDevice, c->stream));
     // which sequences hold something else than A C G T
-    if ((r = reserve(c, c->a_ends, size_t(n_seqs + 1) * 8 + size_t(n_seqs))) != IOC_OK) return r;
+    IOC_TRY(ioc_reserve(c, c->a_ends, size_t(n_seqs + 1) * 8 + size_t(n_seqs)));
     int64_t* d_offs = static_cast<int64_t*>(c->a_ends.p);
     uint8_t* d_flags = reinterpret_cast<uint8_t*>(d_offs + n_seqs + 1);
-    ACHK(c, hipMemcpyAsync(d_offs, offs, size_t(n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(d_offs, offs, size_t(n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_seq_flags, dim3(uint32_t(n_seqs)), dim3(256), 0, c->stream,
                        static_cast<const uint8_t*>(c->a_pool.p), d_offs, d_flags);
-    ACHK(c, hipGetLastError());
+    IOC_CHK(c, hipGetLastError());
     c->aln_other.assign(size_t(n_seqs), 0);
-    ACHK(c, hipMemcpyAsync(c->aln_other.data(), d_flags, size_t(n_seqs), hipMemcpyDeviceToHost, c->stream));
-    ACHK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipMemcpyAsync(c->aln_other.data(), d_flags, size_t(n_seqs), hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     return IOC_OK;
 }
 

@@ -102,11 +102,6 @@ struct ioc_dist_state {
             return ioc_fail(c, IOC_ERR_HIP, std::string("RCCL: ") + rccl()->GetErrorString(r_) + " (" #x "); communicator aborted"); \
         }                                                                                           \
     } while (0)
-#define HCK(c, x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) return ioc_fail(c, IOC_ERR_HIP, std::string(hipGetErrorString(e_)) + " (" #x ")"); \
-    } while (0)
 
 static int need_dist(ioc_ctx* c)
 {
@@ -154,20 +149,6 @@ static int agree(ioc_dist_state* d, int local_status)
     return worst;
 }
 
-static int reserve(ioc_ctx* c, DevBuf& b, size_t bytes)
-{
-    if (b.cap >= bytes && b.p) return IOC_OK;
-    if (b.p) {
-        HCK(c, hipStreamSynchronize(c->stream));
-        HCK(c, hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    HCK(c, hipMalloc(&b.p, bytes ? bytes : 256));
-    b.cap = bytes ? bytes : 256;
-    return IOC_OK;
-}
-
 // ioc_set_shard's exchange over the context's communicator: in-place all-reduce on the context's stream
 static int rccl_exchange(void* user, void* d_buf, int64_t count, int32_t kind, void* hip_stream)
 {
@@ -203,7 +184,7 @@ int ioc_dist_init(ioc_ctx* c, const uint8_t* id, int32_t rank, int32_t world)
 {
     if (!c || !id || world < 1 || rank < 0 || rank >= world) return IOC_ERR_ARG;
     if (c->dist) return ioc_fail(c, IOC_ERR_STATE, "ioc_dist_init: the context already has a communicator");
-    HCK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     ncclUniqueId u;
     std::memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
     ioc_dist_state* d = new ioc_dist_state;
@@ -239,7 +220,6 @@ int ioc_dist_shutdown(ioc_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     if (c->dist->comm) (void)rccl()->CommDestroy(c->dist->comm);
-    if (c->dist->stage.p) (void)hipFree(c->dist->stage.p);
     if (c->dist->d_status) (void)hipFree(c->dist->d_status);
     if (c->dist->h_status) (void)hipHostFree(c->dist->h_status);
     delete c->dist;
@@ -260,7 +240,7 @@ int ioc_dist_allgather_device(ioc_ctx* c, const void* d_send, void* d_recv, int6
 {
     if (int rc = need_dist(c)) return rc;
     if (bytes < 0 || (bytes && (!d_send || !d_recv))) return IOC_ERR_ARG;
-    HCK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     if (bytes) NCK(c, rccl()->AllGather(d_send, d_recv, size_t(bytes), ncclUint8, c->dist->comm, c->stream));
     return IOC_OK;
 }
@@ -272,7 +252,7 @@ int ioc_dist_allgatherv_device(ioc_ctx* c, const void* d_send, void* d_recv, con
 {
     if (int rc = need_dist(c)) return rc;
     if (!counts || !displs || esize <= 0) return IOC_ERR_ARG;
-    HCK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     ioc_dist_state* d = c->dist;
     NCK(c, rccl()->GroupStart());
     for (int r = 0; r < d->world; ++r) {
@@ -296,13 +276,13 @@ int ioc_dist_allgather_i64(ioc_ctx* c, int64_t mine, int64_t* all)
     if (int rc = need_dist(c)) return rc;
     if (!all) return IOC_ERR_ARG;
     ioc_dist_state* d = c->dist;
-    HCK(c, hipSetDevice(c->device));
-    if (int rc = reserve(c, d->stage, size_t(d->world + 1) * 8)) return rc;
+    IOC_CHK(c, hipSetDevice(c->device));
+    if (int rc = ioc_reserve(c, d->stage, size_t(d->world + 1) * 8)) return rc;
     int64_t* dv = static_cast<int64_t*>(d->stage.p);
-    HCK(c, hipMemcpyAsync(dv + d->world, &mine, 8, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(dv + d->world, &mine, 8, hipMemcpyHostToDevice, c->stream));
     NCK(c, rccl()->AllGather(dv + d->world, dv, 1, ncclInt64, d->comm, c->stream));
-    HCK(c, hipMemcpyAsync(all, dv, size_t(d->world) * 8, hipMemcpyDeviceToHost, c->stream));
-    HCK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipMemcpyAsync(all, dv, size_t(d->world) * 8, hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     return IOC_OK;
 }
 
@@ -319,12 +299,12 @@ int ioc_dist_allgatherv_host(ioc_ctx* c, const void* send, int64_t bytes, void* 
     for (int r = 0; r < d->world; ++r) displs[size_t(r) + 1] = displs[size_t(r)] + sizes[r];
     const int64_t total = displs[size_t(d->world)];
     if (total == 0) return IOC_OK;
-    if (int rc = reserve(c, d->stage, size_t(total) + 256)) return rc;
+    if (int rc = ioc_reserve(c, d->stage, size_t(total) + 256)) return rc;
     char* dv = static_cast<char*>(d->stage.p);
-    if (bytes) HCK(c, hipMemcpyAsync(dv + displs[size_t(d->rank)], send, size_t(bytes), hipMemcpyHostToDevice, c->stream));
+    if (bytes) IOC_CHK(c, hipMemcpyAsync(dv + displs[size_t(d->rank)], send, size_t(bytes), hipMemcpyHostToDevice, c->stream));
     if (int rc = ioc_dist_allgatherv_device(c, dv + displs[size_t(d->rank)], dv, sizes, displs.data(), 1)) return rc;
-    HCK(c, hipMemcpyAsync(recv, dv, size_t(total), hipMemcpyDeviceToHost, c->stream));
-    HCK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipMemcpyAsync(recv, dv, size_t(total), hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     return IOC_OK;
 }
 
@@ -333,13 +313,13 @@ int ioc_dist_allreduce_max(ioc_ctx* c, double* x)
     if (int rc = need_dist(c)) return rc;
     if (!x) return IOC_ERR_ARG;
     ioc_dist_state* d = c->dist;
-    HCK(c, hipSetDevice(c->device));
-    if (int rc = reserve(c, d->stage, 16)) return rc;
+    IOC_CHK(c, hipSetDevice(c->device));
+    if (int rc = ioc_reserve(c, d->stage, 16)) return rc;
     double* dv = static_cast<double*>(d->stage.p);
-    HCK(c, hipMemcpyAsync(dv, x, 8, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(dv, x, 8, hipMemcpyHostToDevice, c->stream));
     NCK(c, rccl()->AllReduce(dv, dv + 1, 1, ncclDouble, ncclMax, d->comm, c->stream));
-    HCK(c, hipMemcpyAsync(x, dv + 1, 8, hipMemcpyDeviceToHost, c->stream));
-    HCK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipMemcpyAsync(x, dv + 1, 8, hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     return IOC_OK;
 }
 
@@ -362,7 +342,7 @@ int ioc_dist_exchange(ioc_ctx* c, void* d_buf, int64_t count, int32_t kind)
 {
     if (int rc = need_dist(c)) return rc;
     if (!d_buf || count < 0 || kind < IOC_XCHG_MAX_U8 || kind > IOC_XCHG_SUM_I32) return IOC_ERR_ARG;
-    HCK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     if (rccl_exchange(c->dist, d_buf, count, kind, c->stream) != 0) return ioc_fail(c, IOC_ERR_HIP, "RCCL: ncclAllReduce failed");
     return IOC_OK;
 }
@@ -385,10 +365,10 @@ int ioc_dist_merge(ioc_ctx* c, const ioc_params* p, const char* table_path, cons
     if (!p || !reps || !out_counts || reps->n < 0) return IOC_ERR_ARG;
     ioc_dist_state* d = c->dist;
     const int W = d->world;
-    HCK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     hipEvent_t e0, e1;
-    HCK(c, hipEventCreate(&e0));
-    HCK(c, hipEventCreate(&e1));
+    IOC_CHK(c, hipEventCreate(&e0));
+    IOC_CHK(c, hipEventCreate(&e1));
     struct EvGuard {
         hipEvent_t a, b;
         ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
@@ -420,8 +400,8 @@ int ioc_dist_merge(ioc_ctx* c, const ioc_params* p, const char* table_path, cons
     if (out_cap < N) local = ioc_fail(c, IOC_ERR_ARG, "ioc_dist_merge: out_cap is smaller than the number of representatives of all ranks");
     else if (N > INT32_MAX) local = ioc_fail(c, IOC_ERR_CAPACITY, "too many representatives");
     // 2. the minimizer lists, HBM to HBM, into [all forward lists][all reverse lists]
-    if (local == IOC_OK) local = reserve(c, c->b_dist_min, size_t(FW + RW) * 4 + 256);
-    if (local == IOC_OK) local = reserve(c, c->b_dist_pos, size_t(FW + RW) * 4 + 256);
+    if (local == IOC_OK) local = ioc_reserve(c, c->b_dist_min, size_t(FW + RW) * 4 + 256);
+    if (local == IOC_OK) local = ioc_reserve(c, c->b_dist_pos, size_t(FW + RW) * 4 + 256);
     if (agree(d, local) != 0)
         return local != IOC_OK ? local : ioc_fail(c, IOC_ERR_STATE, "ioc_dist_merge: another rank could not start the exchange (its own error says why)");
     // Everything between the opening agreement and the closing one runs inside `exchange_and_merge`: whatever way it ends — a HIP call
@@ -433,7 +413,7 @@ int ioc_dist_merge(ioc_ctx* c, const ioc_params* p, const char* table_path, cons
     bool shard = false;
     auto t0 = std::chrono::steady_clock::now();
     auto exchange_and_merge = [&]() -> int {
-        HCK(c, hipEventRecord(e0, c->stream));
+        IOC_CHK(c, hipEventRecord(e0, c->stream));
         uint32_t* gmin = static_cast<uint32_t*>(c->b_dist_min.p);
         uint32_t* gpos = static_cast<uint32_t*>(c->b_dist_pos.p);
         std::vector<int64_t> dF(static_cast<size_t>(W)), dR(static_cast<size_t>(W));
@@ -448,18 +428,18 @@ int ioc_dist_merge(ioc_ctx* c, const ioc_params* p, const char* table_path, cons
         }
         const hipMemcpyKind kind = reps->minimizers_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         if (fw) {
-            HCK(c, hipMemcpyAsync(gmin + dF[size_t(d->rank)], reps->min_val + f0, size_t(fw) * 4, kind, c->stream));
-            HCK(c, hipMemcpyAsync(gpos + dF[size_t(d->rank)], reps->min_pos + f0, size_t(fw) * 4, kind, c->stream));
+            IOC_CHK(c, hipMemcpyAsync(gmin + dF[size_t(d->rank)], reps->min_val + f0, size_t(fw) * 4, kind, c->stream));
+            IOC_CHK(c, hipMemcpyAsync(gpos + dF[size_t(d->rank)], reps->min_pos + f0, size_t(fw) * 4, kind, c->stream));
         }
         if (rw) {
-            HCK(c, hipMemcpyAsync(gmin + dR[size_t(d->rank)], reps->min_val + r0, size_t(rw) * 4, kind, c->stream));
-            HCK(c, hipMemcpyAsync(gpos + dR[size_t(d->rank)], reps->min_pos + r0, size_t(rw) * 4, kind, c->stream));
+            IOC_CHK(c, hipMemcpyAsync(gmin + dR[size_t(d->rank)], reps->min_val + r0, size_t(rw) * 4, kind, c->stream));
+            IOC_CHK(c, hipMemcpyAsync(gpos + dR[size_t(d->rank)], reps->min_pos + r0, size_t(rw) * 4, kind, c->stream));
         }
         if (int rc = ioc_dist_allgatherv_device(c, gmin + dF[size_t(d->rank)], gmin, fws.data(), dF.data(), 4)) return rc;
         if (int rc = ioc_dist_allgatherv_device(c, gmin + dR[size_t(d->rank)], gmin, rws.data(), dR.data(), 4)) return rc;
         if (int rc = ioc_dist_allgatherv_device(c, gpos + dF[size_t(d->rank)], gpos, fws.data(), dF.data(), 4)) return rc;
         if (int rc = ioc_dist_allgatherv_device(c, gpos + dR[size_t(d->rank)], gpos, rws.data(), dR.data(), 4)) return rc;
-        HCK(c, hipEventRecord(e1, c->stream));
+        IOC_CHK(c, hipEventRecord(e1, c->stream));
         // 3. the per-representative host records (and the raw sequences)
         std::vector<RepMeta> all(static_cast<size_t>(N));
         for (int32_t i = 0; i < n; ++i) {
@@ -489,7 +469,7 @@ int ioc_dist_merge(ioc_ctx* c, const ioc_params* p, const char* table_path, cons
             for (int64_t i = 0; i < N; ++i) seq_off[size_t(i) + 1] = seq_off[size_t(i)] + all[size_t(i)].raw_len;
             if (seq_off[size_t(N)] != SB) return ioc_fail(c, IOC_ERR_INPUT, "ioc_dist_merge: raw_len does not add up to the sequences gathered");
         }
-        HCK(c, hipEventSynchronize(e1));
+        IOC_CHK(c, hipEventSynchronize(e1));
         (void)hipEventElapsedTime(&ms_comm, e0, e1);
         // 4. the combined view: rank 0's representatives are clusters from the start (the left fold ((b0 + b1) + b2) ... of freshly
         //    clustered batches makes the decisions of one loop over all representatives in rank order: ioc_batch_view::is_cluster)
@@ -533,7 +513,7 @@ int ioc_dist_merge(ioc_ctx* c, const ioc_params* p, const char* table_path, cons
         v.min_cls_size = min_cls_size;
         v.is_cluster = is_cluster.data();
         v.minimizers_on_device = 1;
-        HCK(c, hipStreamSynchronize(c->stream));
+        IOC_CHK(c, hipStreamSynchronize(c->stream));
         t0 = std::chrono::steady_clock::now();
         // fast mode: score + resolve sharded over the ranks (query j on rank j % W), `valid` all-reduced after every sweep;
         // sahlin / furious: the alignment rounds sharded by owner of the query, their verdicts summed over the ranks (ioc_host.cpp)

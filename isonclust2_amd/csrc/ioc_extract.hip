@@ -407,34 +407,6 @@ hipError_t iock_minimizers(hipStream_t st, int n, const int64_t* offs, const uin
 // =====================================================================================================
 namespace {
 
-struct Tmp {
-    void* p = nullptr;
-    ~Tmp()
-    {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes)
-    {
-        const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-        if (e == hipSuccess) ioc_poison(p, bytes ? bytes : 16);
-        return e;
-    }
-    template <class T>
-    T* as()
-    {
-        return static_cast<T*>(p);
-    }
-};
-
-struct Borrow {
-    void* p;
-    template <class T>
-    T* as()
-    {
-        return static_cast<T*>(p);
-    }
-};
-
 // InitQualTab / InitQualTabNomin, src/qualscore.cpp:156-180 (host libm pow, uploaded)
 void qual_tables(double* capped, double* nomin)
 {
@@ -446,31 +418,7 @@ void qual_tables(double* capped, double* nomin)
     }
 }
 
-int reserve_x(ioc_ctx* c, DevBuf& b, size_t bytes)
-{
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return IOC_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        b.p = nullptr;
-        return ioc_fail(c, IOC_ERR_CAPACITY, "hipMalloc failed in extraction");
-    }
-    b.cap = want;
-    ioc_poison(b.p, want);
-    return IOC_OK;
-}
-
 }  // namespace
-
-#define XCHK(c, call)                                                                             \
-    do {                                                                                          \
-        hipError_t e__ = (call);                                                                  \
-        if (e__ != hipSuccess)                                                                    \
-            return ioc_fail((c), IOC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 extern "C" {
 
@@ -478,25 +426,25 @@ int ioc_qual_scores(ioc_ctx* c, int32_t n, const int64_t* offs, const uint8_t* q
                     double* err_rate)
 {
     if (!c || n < 0 || (n > 0 && (!offs || !qual || !score || !err_rate)) || k < 1) return IOC_ERR_ARG;
-    XCHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     if (n == 0) return IOC_OK;
     const int64_t total = offs[n];
-    Tmp d_offs, d_qual, d_tab, d_out;
-    XCHK(c, d_offs.alloc(size_t(n + 1) * 8));
-    XCHK(c, d_qual.alloc(size_t(total)));
-    XCHK(c, d_tab.alloc(2 * 129 * 8));
-    XCHK(c, d_out.alloc(size_t(n) * 16));
+    DevBuf d_offs, d_qual, d_tab, d_out;
+    IOC_TRY(ioc_alloc(c, d_offs, size_t(n + 1) * 8));
+    IOC_TRY(ioc_alloc(c, d_qual, size_t(total)));
+    IOC_TRY(ioc_alloc(c, d_tab, 2 * 129 * 8));
+    IOC_TRY(ioc_alloc(c, d_out, size_t(n) * 16));
     double tabs[2 * 129];
     qual_tables(tabs, tabs + 129);
     hipStream_t s = c->stream;
-    XCHK(c, hipMemcpyAsync(d_offs.p, offs, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
-    XCHK(c, hipMemcpyAsync(d_qual.p, qual, size_t(total), hipMemcpyHostToDevice, s));
-    XCHK(c, hipMemcpyAsync(d_tab.p, tabs, sizeof(tabs), hipMemcpyHostToDevice, s));
-    XCHK(c, iock_qual_scores(s, n, d_offs.as<int64_t>(), d_qual.as<uint8_t>(), k, d_tab.as<double>(),
-                             d_tab.as<double>() + 129, d_out.as<double>(), d_out.as<double>() + n));
-    XCHK(c, hipMemcpyAsync(score, d_out.p, size_t(n) * 8, hipMemcpyDeviceToHost, s));
-    XCHK(c, hipMemcpyAsync(err_rate, d_out.as<double>() + n, size_t(n) * 8, hipMemcpyDeviceToHost, s));
-    XCHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipMemcpyAsync(d_offs.p, offs, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(d_qual.p, qual, size_t(total), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(d_tab.p, tabs, sizeof(tabs), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, iock_qual_scores(s, n, d_offs.as<int64_t>(), d_qual.as<uint8_t>(), k, d_tab.as<double>(),
+                                d_tab.as<double>() + 129, d_out.as<double>(), d_out.as<double>() + n));
+    IOC_CHK(c, hipMemcpyAsync(score, d_out.p, size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipMemcpyAsync(err_rate, d_out.as<double>() + n, size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i)
         if (std::isnan(score[i])) return ioc_fail(c, IOC_ERR_INPUT, "quality byte > 128 (the reference's table lookup throws)");
     return IOC_OK;
@@ -509,47 +457,40 @@ int ioc_extract_minimizers(ioc_ctx* c, int32_t n, const int64_t* offs, const uin
     if (!c || n < 0 || (n > 0 && (!offs || !seq || !qual || !hpc_len || !hpc_err || !off_fwd || !off_rev || !status)))
         return IOC_ERR_ARG;
     if (k < 1 || k > 32 || w < k || w - k + 1 > 32) return ioc_fail(c, IOC_ERR_ARG, "need 1 <= k <= 32, k <= w <= k+31");
-    XCHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     c->x_n = 0;
     c->x_total = 0;
     if (n == 0) return IOC_OK;
     const int64_t total = offs[n];
     hipStream_t s = c->stream;
-    Tmp d_offs, d_seq, d_qual, d_status, d_err, d_cnt, d_tab;
-    Borrow d_hseq{nullptr}, d_hqual{nullptr};  // the HPC strings stay in the context (ioc_extracted_hpc_download)
-    XCHK(c, d_offs.alloc(size_t(n + 1) * 8));
-    XCHK(c, d_seq.alloc(size_t(total)));
-    XCHK(c, d_qual.alloc(size_t(total)));
-    {
-        int rc0;
-        if ((rc0 = reserve_x(c, c->x_hseq, size_t(total))) != IOC_OK) return rc0;
-        if ((rc0 = reserve_x(c, c->x_hqual, size_t(total))) != IOC_OK) return rc0;
-        d_hseq.p = c->x_hseq.p;
-        d_hqual.p = c->x_hqual.p;
-    }
-    XCHK(c, d_status.alloc(size_t(n) * 4));
-    XCHK(c, d_err.alloc(size_t(n) * 8));
-    XCHK(c, d_cnt.alloc(size_t(n) * 8));
-    XCHK(c, d_tab.alloc(2 * 129 * 8));
-    int rc;
-    if ((rc = reserve_x(c, c->x_hpc_len, size_t(n) * 4)) != IOC_OK) return rc;
-    if ((rc = reserve_x(c, c->x_off_fwd, size_t(n + 1) * 8)) != IOC_OK) return rc;
-    if ((rc = reserve_x(c, c->x_off_rev, size_t(n + 1) * 8)) != IOC_OK) return rc;
+    DevBuf d_offs, d_seq, d_qual, d_status, d_err, d_cnt, d_tab;
+    IOC_TRY(ioc_alloc(c, d_offs, size_t(n + 1) * 8));
+    IOC_TRY(ioc_alloc(c, d_seq, size_t(total)));
+    IOC_TRY(ioc_alloc(c, d_qual, size_t(total)));
+    IOC_TRY(ioc_reserve(c, c->x_hseq, size_t(total)));  // the HPC strings stay in the context (ioc_extracted_hpc_download)
+    IOC_TRY(ioc_reserve(c, c->x_hqual, size_t(total)));
+    IOC_TRY(ioc_alloc(c, d_status, size_t(n) * 4));
+    IOC_TRY(ioc_alloc(c, d_err, size_t(n) * 8));
+    IOC_TRY(ioc_alloc(c, d_cnt, size_t(n) * 8));
+    IOC_TRY(ioc_alloc(c, d_tab, 2 * 129 * 8));
+    IOC_TRY(ioc_reserve(c, c->x_hpc_len, size_t(n) * 4));
+    IOC_TRY(ioc_reserve(c, c->x_off_fwd, size_t(n + 1) * 8));
+    IOC_TRY(ioc_reserve(c, c->x_off_rev, size_t(n + 1) * 8));
     double tabs[2 * 129];
     qual_tables(tabs, tabs + 129);
-    XCHK(c, hipMemcpyAsync(d_offs.p, offs, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
-    XCHK(c, hipMemcpyAsync(d_seq.p, seq, size_t(total), hipMemcpyHostToDevice, s));
-    XCHK(c, hipMemcpyAsync(d_qual.p, qual, size_t(total), hipMemcpyHostToDevice, s));
-    XCHK(c, hipMemcpyAsync(d_tab.p, tabs, sizeof(tabs), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(d_offs.p, offs, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(d_seq.p, seq, size_t(total), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(d_qual.p, qual, size_t(total), hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(d_tab.p, tabs, sizeof(tabs), hipMemcpyHostToDevice, s));
     uint32_t* d_hlen = static_cast<uint32_t*>(c->x_hpc_len.p);
-    XCHK(c, iock_hpc(s, n, d_offs.as<int64_t>(), d_seq.as<uint8_t>(), d_qual.as<uint8_t>(), d_hseq.as<uint8_t>(),
-                     d_hqual.as<uint8_t>(), d_hlen, d_status.as<int32_t>()));
-    XCHK(c, iock_hpc_error(s, n, d_offs.as<int64_t>(), d_hqual.as<uint8_t>(), d_hlen, d_tab.as<double>() + 129,
-                           d_err.as<double>()));
-    XCHK(c, hipMemcpyAsync(hpc_len, d_hlen, size_t(n) * 4, hipMemcpyDeviceToHost, s));
-    XCHK(c, hipMemcpyAsync(status, d_status.p, size_t(n) * 4, hipMemcpyDeviceToHost, s));
-    XCHK(c, hipMemcpyAsync(hpc_err, d_err.p, size_t(n) * 8, hipMemcpyDeviceToHost, s));
-    XCHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, iock_hpc(s, n, d_offs.as<int64_t>(), d_seq.as<uint8_t>(), d_qual.as<uint8_t>(), c->x_hseq.as<uint8_t>(),
+                        c->x_hqual.as<uint8_t>(), d_hlen, d_status.as<int32_t>()));
+    IOC_CHK(c, iock_hpc_error(s, n, d_offs.as<int64_t>(), c->x_hqual.as<uint8_t>(), d_hlen, d_tab.as<double>() + 129,
+                              d_err.as<double>()));
+    IOC_CHK(c, hipMemcpyAsync(hpc_len, d_hlen, size_t(n) * 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipMemcpyAsync(status, d_status.p, size_t(n) * 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipMemcpyAsync(hpc_err, d_err.p, size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     uint32_t max_hlen = 1;
     for (int i = 0; i < n; ++i) {
         max_hlen = std::max(max_hlen, hpc_len[i]);
@@ -558,17 +499,17 @@ int ioc_extract_minimizers(ioc_ctx* c, int32_t n, const int64_t* offs, const uin
     }
     if ((uint64_t(max_hlen) + 15) / 16 * 4 > 64 * 1024 - 2048)
         return ioc_fail(c, IOC_ERR_CAPACITY, "a read has more than ~250k HPC bases");
-    XCHK(c, hipMemcpyAsync(d_status.p, status, size_t(n) * 4, hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(d_status.p, status, size_t(n) * 4, hipMemcpyHostToDevice, s));
     uint32_t* d_cf = d_cnt.as<uint32_t>();
     uint32_t* d_cr = d_cf + n;
-    XCHK(c, iock_minimizers(s, n, d_offs.as<int64_t>(), d_hseq.as<uint8_t>(), d_hlen, d_status.as<int32_t>(), k, w, 0,
-                            nullptr, nullptr, d_cf, d_cr, nullptr, nullptr, max_hlen));
+    IOC_CHK(c, iock_minimizers(s, n, d_offs.as<int64_t>(), c->x_hseq.as<uint8_t>(), d_hlen, d_status.as<int32_t>(), k, w, 0,
+                               nullptr, nullptr, d_cf, d_cr, nullptr, nullptr, max_hlen));
     std::vector<uint32_t> cf, cr;
     cf.resize(size_t(n));
     cr.resize(size_t(n));
-    XCHK(c, hipMemcpyAsync(cf.data(), d_cf, size_t(n) * 4, hipMemcpyDeviceToHost, s));
-    XCHK(c, hipMemcpyAsync(cr.data(), d_cr, size_t(n) * 4, hipMemcpyDeviceToHost, s));
-    XCHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipMemcpyAsync(cf.data(), d_cf, size_t(n) * 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipMemcpyAsync(cr.data(), d_cr, size_t(n) * 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     int64_t tot = 0;
     for (int i = 0; i < n; ++i) {
         off_fwd[i] = tot;
@@ -580,14 +521,14 @@ int ioc_extract_minimizers(ioc_ctx* c, int32_t n, const int64_t* offs, const uin
         tot += cr[size_t(i)];
     }
     off_rev[n] = tot;
-    if ((rc = reserve_x(c, c->x_min, size_t(tot) * 4)) != IOC_OK) return rc;
-    if ((rc = reserve_x(c, c->x_pos, size_t(tot) * 4)) != IOC_OK) return rc;
-    XCHK(c, hipMemcpyAsync(c->x_off_fwd.p, off_fwd, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
-    XCHK(c, hipMemcpyAsync(c->x_off_rev.p, off_rev, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
-    XCHK(c, iock_minimizers(s, n, d_offs.as<int64_t>(), d_hseq.as<uint8_t>(), d_hlen, d_status.as<int32_t>(), k, w, 1,
-                            static_cast<int64_t*>(c->x_off_fwd.p), static_cast<int64_t*>(c->x_off_rev.p), d_cf, d_cr,
-                            static_cast<uint32_t*>(c->x_min.p), static_cast<uint32_t*>(c->x_pos.p), max_hlen));
-    XCHK(c, hipStreamSynchronize(s));
+    IOC_TRY(ioc_reserve(c, c->x_min, size_t(tot) * 4));
+    IOC_TRY(ioc_reserve(c, c->x_pos, size_t(tot) * 4));
+    IOC_CHK(c, hipMemcpyAsync(c->x_off_fwd.p, off_fwd, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemcpyAsync(c->x_off_rev.p, off_rev, size_t(n + 1) * 8, hipMemcpyHostToDevice, s));
+    IOC_CHK(c, iock_minimizers(s, n, d_offs.as<int64_t>(), c->x_hseq.as<uint8_t>(), d_hlen, d_status.as<int32_t>(), k, w, 1,
+                               static_cast<int64_t*>(c->x_off_fwd.p), static_cast<int64_t*>(c->x_off_rev.p), d_cf, d_cr,
+                               static_cast<uint32_t*>(c->x_min.p), static_cast<uint32_t*>(c->x_pos.p), max_hlen));
+    IOC_CHK(c, hipStreamSynchronize(s));
     c->x_n = n;
     c->x_total = tot;
     c->xh_off_fwd.assign(off_fwd, off_fwd + n + 1);
@@ -601,15 +542,15 @@ int ioc_extract_minimizers(ioc_ctx* c, int32_t n, const int64_t* offs, const uin
 int ioc_extracted_hpc_download(ioc_ctx* c, char* hpc_seq, char* hpc_qual, int64_t cap)
 {
     if (!c || !hpc_seq || !hpc_qual) return IOC_ERR_ARG;
-    XCHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     const int n = c->x_n;
     if (n <= 0) return ioc_fail(c, IOC_ERR_STATE, "ioc_extract_minimizers first");
     const int64_t total = c->xh_offs[size_t(n)];
     if (cap < total) return ioc_fail(c, IOC_ERR_CAPACITY, "buffer smaller than the raw sequence bytes");
     // layout: read i's HPC string occupies [offs[i], offs[i] + hpc_len[i]) (capacity = raw length)
-    XCHK(c, hipMemcpyAsync(hpc_seq, c->x_hseq.p, size_t(total), hipMemcpyDeviceToHost, c->stream));
-    XCHK(c, hipMemcpyAsync(hpc_qual, c->x_hqual.p, size_t(total), hipMemcpyDeviceToHost, c->stream));
-    XCHK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipMemcpyAsync(hpc_seq, c->x_hseq.p, size_t(total), hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(hpc_qual, c->x_hqual.p, size_t(total), hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     static const char L[5] = {'A', 'C', 'G', 'T', 'N'};
     for (int i = 0; i < n; ++i)
         for (int64_t t = c->xh_offs[size_t(i)]; t < c->xh_offs[size_t(i)] + c->xh_hpc_len[size_t(i)]; ++t)
@@ -620,31 +561,30 @@ int ioc_extracted_hpc_download(ioc_ctx* c, char* hpc_seq, char* hpc_qual, int64_
 int ioc_extracted_download(ioc_ctx* c, uint32_t* min_val, uint32_t* min_pos, int64_t cap)
 {
     if (!c || !min_val || !min_pos) return IOC_ERR_ARG;
-    XCHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     if (cap < c->x_total) return ioc_fail(c, IOC_ERR_CAPACITY, "buffer smaller than the extracted minimizers");
     if (c->x_total == 0) return IOC_OK;
-    XCHK(c, hipMemcpyAsync(min_val, c->x_min.p, size_t(c->x_total) * 4, hipMemcpyDeviceToHost, c->stream));
-    XCHK(c, hipMemcpyAsync(min_pos, c->x_pos.p, size_t(c->x_total) * 4, hipMemcpyDeviceToHost, c->stream));
-    XCHK(c, hipStreamSynchronize(c->stream));
+    IOC_CHK(c, hipMemcpyAsync(min_val, c->x_min.p, size_t(c->x_total) * 4, hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(min_pos, c->x_pos.p, size_t(c->x_total) * 4, hipMemcpyDeviceToHost, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
     return IOC_OK;
 }
 
 int ioc_queries_from_extracted(ioc_ctx* c, const uint8_t* keep, const uint8_t* err_cell, const uint32_t* min_total)
 {
     if (!c || !keep || !err_cell || !min_total) return IOC_ERR_ARG;
-    XCHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     const int n = c->x_n;
     if (n <= 0) return ioc_fail(c, IOC_ERR_STATE, "ioc_extract_minimizers first");
     std::vector<uint8_t> cell(err_cell, err_cell + n);
     for (int i = 0; i < n; ++i)
         if (!keep[i] || cell[size_t(i)] < 1 || cell[size_t(i)] > 15) cell[size_t(i)] = 1;
-    int rc;
-    if ((rc = reserve_x(c, c->b_err_cell, size_t(n))) != IOC_OK) return rc;
-    if ((rc = reserve_x(c, c->b_min_total, size_t(n) * 4)) != IOC_OK) return rc;
-    XCHK(c, hipMemcpyAsync(c->b_err_cell.p, cell.data(), size_t(n), hipMemcpyHostToDevice, c->stream));
-    XCHK(c, hipMemcpyAsync(c->b_min_total.p, min_total, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
-    XCHK(c, hipStreamSynchronize(c->stream));
-    rc = ioc_queries_bind_device(c, n, static_cast<int64_t*>(c->x_off_fwd.p), static_cast<int64_t*>(c->x_off_rev.p),
+    IOC_TRY(ioc_reserve(c, c->b_err_cell, size_t(n)));
+    IOC_TRY(ioc_reserve(c, c->b_min_total, size_t(n) * 4));
+    IOC_CHK(c, hipMemcpyAsync(c->b_err_cell.p, cell.data(), size_t(n), hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(c->b_min_total.p, min_total, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    const int rc = ioc_queries_bind_device(c, n, static_cast<int64_t*>(c->x_off_fwd.p), static_cast<int64_t*>(c->x_off_rev.p),
                                  static_cast<uint32_t*>(c->x_min.p), static_cast<uint32_t*>(c->x_pos.p), c->x_total,
                                  static_cast<uint32_t*>(c->x_hpc_len.p), static_cast<uint8_t*>(c->b_err_cell.p),
                                  static_cast<uint32_t*>(c->b_min_total.p), c->xh_off_fwd.data(), c->xh_off_rev.data());

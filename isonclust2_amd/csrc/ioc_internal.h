@@ -1,12 +1,17 @@
-// ioc_internal.h — context layout shared by the device TU (ioc_device.hip) and the host driver
-// (ioc_host.cpp).  Not part of the public C ABI (include/isonclust2_hip.h).
+// ioc_internal.h — the context's layout and the device helpers shared by the host code of every translation unit: the C ABI
+// (ioc_capi.cpp and the host halves of ioc_extract.hip, ioc_update.hip, ioc_align_gpu.hip, ioc_poa.hip), the drivers on top of it
+// (ioc_host.cpp, ioc_consensus.cpp) and the multi-GPU binding (ioc_dist.cpp).  Not part of the public C ABI
+// (include/isonclust2_hip.h).
 #ifndef IOC_INTERNAL_H
 #define IOC_INTERNAL_H
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -15,9 +20,32 @@
 
 #include "isonclust2_hip.h"
 
+// A block of device memory and its owner: freed when the DevBuf goes (a member of a context with the context, a local at the end
+// of its scope), movable, not copyable.  No DevBuf has static storage: the destructor calls into HIP, which a destructor
+// that runs after the runtime's teardown must not do.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release();  // hipFree now (no synchronisation of its own: the caller knows what may still use the block)
+    template <class T>
+    T* as() const
+    {
+        return static_cast<T*>(p);
+    }
 };
 
 // IOC_POISON=<byte>: every fresh device allocation of the library is filled with that byte (debug aid: a kernel that reads
@@ -26,15 +54,53 @@ void ioc_poison(void* p, size_t bytes);
 
 struct ioc_dist_state;  // ioc_dist.cpp: the context's RCCL communicator
 
+// The control words kernels and host share: the first 256 bytes of b_misc (kernels get pointers INTO this block: the byte
+// positions are part of no interface, but index build, scoring, resolve and the timings must agree on them) ...
+struct IocMisc {
+    uint32_t build_err;  // index build: the table is full (the hash build tries again with a larger one)
+    uint32_t pad0[7];
+    uint32_t first_changed;        // resolve, per sweep: first query whose `valid` changed (0xFFFFFFFF: none)
+    uint32_t q_count;              // ... fill of the work queue, first half of a sweep
+    uint32_t incomplete;           // ... the queue overflowed: the same sweep again
+    uint32_t q_count2;             // ... fill of the work queue, second half
+    uint32_t pad1[4];
+    unsigned long long traversed;  // scoring: postings traversed (IOC_COUNT_TRAVERSED)
+    uint32_t pad2[14];
+    unsigned long long n_evals;    // resolve: totalMapped evaluations of the call
+    uint32_t pad3[14];
+    unsigned long long audit_sum;  // ioc_count_reference_postings
+    uint32_t pad4[14];
+};
+static_assert(sizeof(IocMisc) == 256 && offsetof(IocMisc, first_changed) == 32 && offsetof(IocMisc, traversed) == 64 &&
+                  offsetof(IocMisc, n_evals) == 128 && offsetof(IocMisc, audit_sum) == 192,
+              "kernels are handed pointers to these bytes");
+// ... and the words of the 256 pinned bytes of h_pin they are read back into.  One copy per sweep brings IocMisc from
+// first_changed through n_evals to the start of h_pin; the build's read-back lies inside that window (a build and a sweep are never
+// in flight together), the sorted build's postings count beyond it (it is read when the timings are asked for).
+constexpr size_t IOC_PIN_BYTES = 256;
+constexpr size_t IOC_SWEEP_BYTES = offsetof(IocMisc, n_evals) + 8 - offsetof(IocMisc, first_changed);
+enum : uint32_t {
+    IOC_PIN_FIRST_CHANGED = 0,
+    IOC_PIN_INCOMPLETE = (offsetof(IocMisc, incomplete) - offsetof(IocMisc, first_changed)) / 4,
+    IOC_PIN_BUILD = 8,  // two words: (real pairs, runs) of the sorted build, (error word, padded postings) of the hash build
+    IOC_PIN_EVALS = (offsetof(IocMisc, n_evals) - offsetof(IocMisc, first_changed)) / 4,  // two words
+    IOC_PIN_NPOST = 40,  // the sorted build's padded postings
+};
+static_assert(IOC_SWEEP_BYTES == 104 && IOC_PIN_INCOMPLETE == 2 && IOC_PIN_EVALS == 24 && IOC_PIN_NPOST * 4 >= IOC_SWEEP_BYTES && IOC_PIN_NPOST * 4 + 4 <= IOC_PIN_BYTES, "h_pin layout");
+
 struct ioc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     std::string err;
+    DevBuf b_misc;              // IocMisc; behind it ioc_gather_records_device's list table
+    uint32_t* h_pin = nullptr;  // IOC_PIN_BYTES of pinned host memory (IOC_PIN_*): the read-backs of the build and of the resolve's sweeps
 
+    // ---- parameters (ioc_set_params) ----
     bool have_params = false;
     ioc_params params{};
     int32_t h_glim[225]{};
+    DevBuf b_glim;
     int32_t keep = 1;  // candidates with Size < keep can never be evaluated (cluster.cpp:376-389)
 
     // ---- queries ----
@@ -51,18 +117,17 @@ struct ioc_ctx {
     const uint32_t* d_min_total = nullptr;
     DevBuf b_off_fwd, b_off_rev, b_min, b_pos, b_hpc_len, b_err_cell, b_min_total, b_doff;
     int32_t max_fwd = 0, max_rev = 0;
+    uint64_t query_gen = 0;  // bumped whenever the context's queries are replaced (ioc_queries_generation)
+    bool chunked_call = false;  // the last ioc_cluster_merge ran its right batch in chunks: the resident queries are the last chunk's
     // ioc_cluster_merge (caller's arrays valid for the whole call): the index build needs the forward minimizer values
     // only, the scoring the reverse ones too, the resolve the positions — the latter two go up on a copy stream from a
     // thread of their own while the first kernels run (ioc_queries_upload, ioc_wait_uploads)
     bool defer_uploads = false;
     std::thread up_thread;
+    hipStream_t copy_stream = nullptr;
     std::atomic<int> up_stage{2};  // 1: all minimizer values are in HBM, 2: the positions too
     std::atomic<bool> up_failed{false};  // a copy of the upload thread failed (up_err holds the text): set before the stage moves on
-    uint64_t query_gen = 0;  // bumped whenever the context's queries are replaced (ioc_queries_generation)
     std::string up_err;
-    hipStream_t copy_stream = nullptr;
-    hipStream_t side_stream = nullptr;  // the aligner's helper launch for the wrong candidates, beside the first traceback launch
-    hipEvent_t ev_side[2]{};
 
     // ---- left state ----
     int32_t L = 0;
@@ -72,36 +137,58 @@ struct ioc_ctx {
     DevBuf b_lset_off, b_lset_val;
     std::vector<int64_t> h_lset_off;  // host copy of the value-set offsets (ioc_index_update)
 
-    // ---- index ----
+    // ---- index (ioc_index_build) ----
     bool built = false;
     uint32_t cap = 0;  // power of two; slot `cap` is reserved for the key 0xFFFFFFFF
     DevBuf b_keys, b_cnt, b_off, b_fill, b_rows, b_post, b_dvals, b_dcount, b_dslot, b_scan;
+    DevBuf b_qinfo;  // two words per slot: length + epoch cuts (ioc_kernels.hip, index_lookup)
+    DevBuf b_dlong;  // the long queries' values gathered / sorted (iock_distinct_long)
+    DevBuf b_bsort;  // the sorted build's arena (ioc_build_sort.hip)
     int64_t n_post = 0;
     int post16 = 0;  // postings stored as uint16_t (L + N <= 65535)
 
-    // ---- scoring ----
+    // ---- scoring (ioc_score) ----
     bool scored = false;
-    DevBuf b_cand_key, b_cand_size, b_cand_mapped, b_cand_count, b_qinfo, b_part, b_diag, b_top_all, b_pmins, b_pbnd;
-    DevBuf b_dlong;  // ioc_index_build: the long queries' values gathered / sorted (iock_distinct_long)
-    DevBuf b_exp_cid, b_exp_cnt, b_exp_off, b_exp_out, b_exp_work;  // ioc_index_export: final ids, per-slot counts / offsets, compact postings
+    DevBuf b_cand_key, b_cand_size, b_cand_mapped, b_cand_count, b_part, b_top_all, b_pmins, b_pbnd;
     int64_t cand_capacity = 0;
+    DevBuf b_gap_bound, b_keep_q;  // k_gap_bounds' table of the current queries; the per-query compaction threshold (fast mode)
+    uint64_t gap_bound_gen = ~0ull;  // query_gen the table was computed for (ioc_set_params resets it)
+    bool gap_bound_cut = false;      // ... with keep_q written
+    bool keep_q_on = false;          // the candidate lists of the last ioc_score were cut at b_keep_q
+    std::vector<uint32_t> h_keep_q;  // host copy, fetched when a candidate table is exported
+    int score_oob = 0, score_oob_probe = -1;  // k_score_part's variant and the probe behind it (ioc_ctx_create)
+    int score_part32 = 0;  // u32 partials forced (IOC_PART32) in the last ioc_score: ioc_count_reference_postings' audit uses it too
 
-    // ---- resolve ----
+    // ---- resolve (ioc_resolve, ioc_get_decisions) ----
     bool resolved = false;
-    DevBuf b_valid0, b_valid1, b_dec_target, b_dec_strand, b_flags, b_forced_t, b_forced_s, b_misc,
-        b_glim, b_queue, b_cut;
+    DevBuf b_valid0, b_valid1, b_dec_target, b_dec_strand, b_flags, b_forced_t, b_forced_s, b_queue, b_cut, b_diag;
     int cur_valid = 0;
     std::vector<int32_t> h_forced_t;
     std::vector<int8_t> h_forced_s;
     bool forced_dirty = false;
-    std::vector<std::vector<std::pair<int32_t, int8_t>>> last_dep_set;  // ... and the (cluster, strand) candidates among which that order picks the first
-    bool want_dep_sets = false;  // (ioc_cluster_consensus: run_pipeline leaves last_order_dep / last_dep_set)
-    std::vector<uint8_t> last_order_dep;  // per query of the last run_pipeline: its decision hangs on the reference's hit ORDER (a tie at the top Size, or several candidates that align)
     bool forced_host_clear = false, forced_dev_clear = false;  // nothing forced in the host arrays / in what the device holds (no upload then)
-    std::vector<uint32_t> h_min_total;  // host copy of d_min_total for ioc_cluster_resident's tie replays, of queries `h_min_total_gen`
-    uint64_t h_min_total_gen = ~0ull;
-    uint8_t* h_pin_big = nullptr;   // pinned staging for the per-call read-backs of n-sized arrays (decisions)
+    // verdicts of the alignment fallback (ioc_set_aln_verdicts) and the candidates tied at the top Size (ioc_get_ties)
+    DevBuf b_aln_t, b_aln_s, b_tie_count, b_tie_keys;
+    std::vector<int32_t> h_aln_t;
+    std::vector<int8_t> h_aln_s;
+    bool aln_verdicts = false, aln_dirty = false;
+    // warm start: first query whose alignment verdict changed since the last resolve (n: none; -1: no
+    // resolved state to start from).  Everything before it keeps its decision (it depends on earlier queries only).
+    int32_t warm_first = -1;
+    uint8_t* h_pin_big = nullptr;  // pinned staging for the per-call read-backs of n-sized arrays (decisions)
     size_t h_pin_big_cap = 0;
+    DevBuf b_qhist, b_qfirst, b_qout, b_qlist;  // ioc_query_candidates: the query's hit table (kept between calls)
+
+    // ---- ioc_index_export result of the current resolve ----
+    DevBuf b_exp_cid, b_exp_cnt, b_exp_off, b_exp_out, b_exp_work;  // final ids, per-slot counts / offsets, compact postings
+    bool exp_valid = false;   // exp_keys / exp_offs / exp_post hold the export (consensus driver; IOC_EXPORT_HOST_ORDER)
+    bool exp_dev = false;     // the export is ready ON THE DEVICE: exp_nrows keys at b_exp_work + exp_o_keys, exp_nrows + 1 int64
+                              // offsets at + exp_o_offs, exp_total postings in b_exp_out (copied straight into the caller's arrays)
+    uint32_t exp_nrows = 0;
+    uint64_t exp_total = 0;
+    size_t exp_o_keys = 0, exp_o_offs = 0;
+    std::vector<uint32_t> exp_keys, exp_post;
+    std::vector<int64_t> exp_offs;
 
     // ---- extraction (K1) outputs ----
     DevBuf x_min, x_pos, x_off_fwd, x_off_rev, x_hpc_len, x_hseq, x_hqual;
@@ -117,39 +204,39 @@ struct ioc_ctx {
     DevBuf a_pool, a_pairs, a_order, a_out, a_bnd, a_lrow, a_ck, a_cko, a_ends, a_ends2, a_xflags, a_prof, a_ops;
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
-    DevBuf b_aln_t, b_aln_s, b_tie_count, b_tie_keys;
-    DevBuf b_qhist, b_qfirst, b_qout, b_qlist;
-    // ioc_resolve warm start: first query whose alignment verdict changed since the last resolve (n: none; -1: no
-    // resolved state to start from).  Everything before it keeps its decision (it depends on earlier queries only).
-    int32_t warm_first = -1;  // ioc_query_candidates: the query's hit table (kept between calls)
-    std::vector<int32_t> h_aln_t;
-    std::vector<int8_t> h_aln_s;
-    bool aln_verdicts = false, aln_dirty = false;
+    hipStream_t side_stream = nullptr;  // the aligner's helper launch for the wrong candidates, beside the first traceback launch
+    hipEvent_t ev_side[2]{};
+    size_t aln_lds_max = 0, aln_lds_max2 = 0;  // dynamic LDS a k_align_fwd<true/false> workgroup may reserve (residency cap)
+    double aln_verdict_thr = -1.0;  // ioc_align_set_verdict_threshold (<= 0: exact counts)
+    // The aligner's corridor model (ioc_align_gpu.hip, align_v2_run): score per base of the pairs aligned so far against their summed
+    // error rate, one straight line per gap-open class (setGapOpen: 2..5).  Decides how wide a couple's corridor is PLANNED — which
+    // tiles are computed, never what comes out (the certificate and the re-run see to that).
+    struct CorridorFit {
+        double n = 0, se = 0, sr = 0, see = 0, ser = 0, srr = 0, e_lo = 1e9, e_hi = -1e9;
+    };
+    CorridorFit aln_fit[4];
+    int32_t aln_fit_sig[3] = {0, 0, 0};  // (match, mismatch, gap_extend) the sums belong to
+
+    // ---- host drivers (ioc_host.cpp, ioc_consensus.cpp) ----
     // raw sequences of the resident queries (ioc_resident_set_sequences): sahlin on ioc_cluster_resident
     std::string res_seq;
     std::vector<int64_t> res_off;
     std::vector<double> res_err;
     bool have_res_seq = false;
     bool res_pool_ready = false;  // a_pool holds exactly res_seq
-    size_t aln_lds_max = 0, aln_lds_max2 = 0;  // dynamic LDS a k_align_fwd<true/false> workgroup may reserve (residency cap)
-
-    // ---- alignment results kept across the device passes of ioc_cluster_consensus (see AlnDriver) ----
+    std::vector<uint32_t> h_min_total;  // host copy of d_min_total for ioc_cluster_resident's tie replays, of queries `h_min_total_gen`
+    uint64_t h_min_total_gen = ~0ull;
+    bool want_dep_sets = false;  // (ioc_cluster_consensus: run_pipeline leaves last_order_dep / last_dep_set)
+    std::vector<uint8_t> last_order_dep;  // per query of the last run_pipeline: its decision hangs on the reference's hit ORDER (a tie at the top Size, or several candidates that align)
+    std::vector<std::vector<std::pair<int32_t, int8_t>>> last_dep_set;  // ... and the (cluster, strand) candidates among which that order picks the first
+    // alignment results kept across the device passes of ioc_cluster_consensus (see AlnDriver)
     std::vector<uint64_t> aln_qid, aln_lid;  // sequence identity of every right entry / left representative
     std::map<std::pair<uint64_t, uint64_t>, double> aln_cache;
-
-    // ---- ioc_index_export result of the current resolve ----
-    bool exp_valid = false;   // exp_keys / exp_offs / exp_post hold the export (consensus driver; IOC_EXPORT_HOST_ORDER)
-    bool exp_dev = false;     // the export is ready ON THE DEVICE: exp_nrows keys at b_exp_work + exp_o_keys, exp_nrows + 1 int64
-                              // offsets at + exp_o_offs, exp_total postings in b_exp_out (copied straight into the caller's arrays)
-    uint32_t exp_nrows = 0;
-    uint64_t exp_total = 0;
-    size_t exp_o_keys = 0, exp_o_offs = 0;
-    std::vector<uint32_t> exp_keys, exp_post;
-    std::vector<int64_t> exp_offs;
 
     // ---- instrumentation ----
     hipEvent_t ev[6]{};
     ioc_timings tm{};
+
     // ---- multi-GPU (ioc_dist.cpp) ----
     ioc_dist_state* dist = nullptr;
     DevBuf b_dist_min, b_dist_pos;  // the gathered representatives' minimizer lists of ioc_dist_merge (used in place as queries)
@@ -161,35 +248,36 @@ struct ioc_ctx {
     int shard_exchanges = 0;
     int64_t shard_aln_pairs = 0;  // pairs THIS rank aligned in sharded alignment rounds since ioc_set_shard
     DevBuf b_shard_stage;
-    bool chunked_call = false;  // the last ioc_cluster_merge ran its right batch in chunks: the resident queries are the last chunk's
-    double aln_verdict_thr = -1.0;  // ioc_align_set_verdict_threshold (<= 0: exact counts)
-    // The aligner's corridor model (ioc_align_gpu.hip, align_v2_run): score per base of the pairs aligned so far against their summed
-    // error rate, one straight line per gap-open class (setGapOpen: 2..5).  Decides how wide a couple's corridor is PLANNED — which
-    // tiles are computed, never what comes out (the certificate and the re-run see to that).
-    struct CorridorFit {
-        double n = 0, se = 0, sr = 0, see = 0, ser = 0, srr = 0, e_lo = 1e9, e_hi = -1e9;
-    };
-    CorridorFit aln_fit[4];
-    int32_t aln_fit_sig[3] = {0, 0, 0};  // (match, mismatch, gap_extend) the sums belong to
-    uint32_t* h_pin = nullptr;     // 256 bytes of pinned host memory: the read-backs of the resolve's sweeps
-    DevBuf b_bsort;                // the sorted index build's arena (ioc_build_sort.hip)
-    DevBuf b_gap_bound, b_keep_q;  // k_gap_bounds' table of the current queries; the per-query compaction threshold (fast mode)
-    uint64_t gap_bound_gen = ~0ull;  // query_gen the table was computed for (ioc_set_params resets it)
-    bool gap_bound_cut = false;      // ... with keep_q written
-    bool keep_q_on = false;          // the candidate lists of the last ioc_score were cut at b_keep_q
-    std::vector<uint32_t> h_keep_q;  // host copy, fetched when a candidate table is exported
-    int score_oob = 0, score_oob_probe = -1;  // k_score_part's variant and the probe behind it (ioc_ctx_create)
-    int score_part32 = 0;  // u32 partials forced (IOC_PART32) in the last ioc_score: ioc_count_reference_postings' audit uses it too
 };
 
 int ioc_fail(ioc_ctx* c, int code, const std::string& msg);
+
+// a HIP call of a function that returns an ioc status: on failure "<call text>: <hipGetErrorString>" and IOC_ERR_HIP
+#define IOC_CHK(c, call)                                                                           \
+    do {                                                                                           \
+        hipError_t e__ = (call);                                                                   \
+        if (e__ != hipSuccess)                                                                     \
+            return ioc_fail((c), IOC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+
+// a call that returns an ioc status: anything but IOC_OK is returned at once (the callee has set the message)
+#define IOC_TRY(call)                  \
+    do {                               \
+        int r__ = (call);              \
+        if (r__ != IOC_OK) return r__; \
+    } while (0)
+
+// `b` holds at least `bytes` bytes afterwards (0 bytes: 16).  A block that has to grow is freed behind a synchronisation of
+// c->stream and allocated anew at bytes + bytes / 8 + 256, poisoned (IOC_POISON); its old contents are gone.  Out of memory:
+// IOC_ERR_CAPACITY, with the size in the message.
+int ioc_reserve(ioc_ctx* c, DevBuf& b, size_t bytes);
+// the scoped temporary: a fresh block of exactly `bytes` bytes (0: 16) in an empty DevBuf, which frees it at the end of its scope
+int ioc_alloc(ioc_ctx* c, DevBuf& b, size_t bytes);
 // sharded score + resolve (ioc_set_shard): one all-reduce through the caller's hook / a host array of words summed over ranks
 int ioc_shard_exchange(ioc_ctx* c, void* d_buf, int64_t count, int kind);
 int ioc_shard_sum_host(ioc_ctx* c, int32_t* words, int64_t count);
 // waits until the background upload of the query arrays has reached `stage` (see ioc_ctx::up_stage); 2 also ends the thread
 int ioc_wait_uploads(ioc_ctx* c, int stage);
-
-
 
 // ioc_query_candidates for many queries at once (one launch per chunk, one synchronisation): per query the same
 // lists — target, strand (+1 / -1), Size, first hitting Index, cached totalMapped (0xFFFFFFFF: not evaluated) —
@@ -207,13 +295,9 @@ extern "C" int ioc_queries_upload_devmins(ioc_ctx* c, int32_t n, const int64_t* 
                                           const uint32_t* d_min_pos, int64_t total, const uint32_t* hpc_len, const uint8_t* err_cell,
                                           const uint32_t* min_total);
 
-
 // f(0) .. f(count - 1) on the host's cores (independent items only).  The workers are a pool that lives with the process
 // (ioc_host.cpp): the consensus path comes here ~1000 times per batch, and starting 16 threads per call cost 0.4 s of it.
 // A region entered while another one runs (another context on another thread, or a nested call) starts threads of its own.
-#include <atomic>
-#include <functional>
-#include <thread>
 void ioc_pool_run(size_t count, size_t nthreads, const std::function<void(size_t)>& f);
 template <typename F>
 static inline void ioc_parallel_for(size_t count, F f, size_t serial_below = 4)

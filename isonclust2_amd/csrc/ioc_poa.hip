@@ -1048,41 +1048,28 @@ struct ioc_poa {
 
 namespace {
 
+// ioc_reserve with a growth rule of its own, which was measured (nothing is in flight on these buffers between batches):
+// hipMalloc costs ~0.1 ms per MB (3.4 s of a 31 250-read batch's 17 s went there while buffers grew by factors towards a
+// 48 GB budget).  Batches grow as the graphs do and — with deferred consensus — as the passes do, up to the budget of
+// poa_flush: small buffers double; past a gigabyte the next size is `hint`, the buffer's share of that budget (one more
+// allocation, the last), or half as much again.  When that much is not to be had: what the batch needs.
 int poa_reserve(ioc_poa* p, DevBuf& b, size_t bytes, size_t hint = 0)
 {
     if (b.cap >= bytes) return IOC_OK;
     const size_t old_cap = b.cap;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    // hipMalloc costs ~0.1 ms per MB (3.4 s of a 31 250-read batch's 17 s went there while buffers grew by factors towards a
-    // 48 GB budget).  Batches grow as the graphs do and — with deferred consensus — as the passes do, up to the budget of
-    // poa_flush: small buffers double; past a gigabyte the next size is `hint`, the buffer's share of that budget (one more
-    // allocation, the last), or half as much again.
+    b.release();
     size_t want = bytes + bytes / 8 + 4096;
     if (want < (size_t(1) << 30))
         want = std::max(want, std::min(2 * old_cap, size_t(1) << 30));
     else
         want = std::max(want, hint ? hint : old_cap + old_cap / 2);
-    if (hipMalloc(&b.p, want) != hipSuccess) {
+    for (const size_t sz : {want, bytes + 4096}) {
+        if (ioc_alloc(p->ctx, b, sz) == IOC_OK) return IOC_OK;
         (void)hipGetLastError();
-        want = bytes + 4096;
-        b.p = nullptr;
+        want = sz;
     }
-    if (!b.p && hipMalloc(&b.p, want) != hipSuccess) {
-        b.p = nullptr;
-        (void)hipGetLastError();
-        return ioc_fail(p->ctx, IOC_ERR_CAPACITY, "POA: hipMalloc of the DP matrices failed (" + std::to_string(want >> 20) + " MB)");
-    }
-    b.cap = want;
-    return IOC_OK;
+    return ioc_fail(p->ctx, IOC_ERR_CAPACITY, "POA: hipMalloc of the DP matrices failed (" + std::to_string(want >> 20) + " MB)");
 }
-
-#define PCHK(p, call)                                                                                      \
-    do {                                                                                                   \
-        hipError_t e__ = (call);                                                                           \
-        if (e__ != hipSuccess) return ioc_fail((p)->ctx, IOC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 struct HostJob {
     PGraph* G = nullptr;
@@ -1103,15 +1090,15 @@ template <int T>
 int poa_launch(ioc_poa* p, hipStream_t s, const PoaJob* djobs, size_t K, int max_w, int max_diag, int max_ncb)
 {
     hipLaunchKernelGGL(k_poa_init<T>, dim3(unsigned((max_w + 255) / 256), unsigned(K)), dim3(256), 0, s, djobs);
-    PCHK(p, hipGetLastError());
+    IOC_CHK(p->ctx, hipGetLastError());
     for (int dg = 0; dg < max_diag; ++dg) {  // one anti-diagonal of tiles (of every job) per launch
         hipLaunchKernelGGL(k_poa_tile<T>, dim3(unsigned(std::min(max_ncb, dg + 1)), unsigned(K)), dim3(POA_THREADS), 0, s, djobs, dg, p->S, p->pred_lds);
-        PCHK(p, hipGetLastError());
+        IOC_CHK(p->ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(k_poa_best<T>, dim3(unsigned(K)), dim3(256), 0, s, djobs);
-    PCHK(p, hipGetLastError());
+    IOC_CHK(p->ctx, hipGetLastError());
     hipLaunchKernelGGL(k_poa_trace<T>, dim3(unsigned(K)), dim3(64), 0, s, djobs);
-    PCHK(p, hipGetLastError());
+    IOC_CHK(p->ctx, hipGetLastError());
     return IOC_OK;
 }
 
@@ -1119,7 +1106,7 @@ int poa_launch(ioc_poa* p, hipStream_t s, const PoaJob* djobs, size_t K, int max
 int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
 {
     ioc_ctx* c = p->ctx;
-    PCHK(p, hipSetDevice(c->device));
+    IOC_CHK(p->ctx, hipSetDevice(c->device));
     const size_t K = jobs.size();
     if (K == 0) return IOC_OK;
     hipStream_t s = c->stream;
@@ -1233,11 +1220,11 @@ int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
     p->ms_layout += t_gpu - t_in;
     const bool trace = getenv("IOC_TRACE") != nullptr;
     if (trace && !p->ev[0])
-        for (auto& e : p->ev) PCHK(p, hipEventCreate(&e));
-    if (trace) PCHK(p, hipEventRecord(p->ev[0], s));
-    PCHK(p, hipMemcpyAsync(sm, small.data(), small.size(), hipMemcpyHostToDevice, s));
-    PCHK(p, hipMemcpyAsync(p->d_jobs.p, dj.data(), K * sizeof(PoaJob), hipMemcpyHostToDevice, s));
-    if (trace) PCHK(p, hipEventRecord(p->ev[1], s));
+        for (auto& e : p->ev) IOC_CHK(p->ctx, hipEventCreate(&e));
+    if (trace) IOC_CHK(p->ctx, hipEventRecord(p->ev[0], s));
+    IOC_CHK(p->ctx, hipMemcpyAsync(sm, small.data(), small.size(), hipMemcpyHostToDevice, s));
+    IOC_CHK(p->ctx, hipMemcpyAsync(p->d_jobs.p, dj.data(), K * sizeof(PoaJob), hipMemcpyHostToDevice, s));
+    if (trace) IOC_CHK(p->ctx, hipEventRecord(p->ev[1], s));
     const PoaJob* djobs = static_cast<const PoaJob*>(p->d_jobs.p);
     switch (p->type) {
         case IOC_POA_GLOBAL: r = poa_launch<IOC_POA_GLOBAL>(p, s, djobs, K, max_w, max_diag, max_ncb); break;
@@ -1245,13 +1232,13 @@ int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
         default: r = poa_launch<IOC_POA_LOCAL>(p, s, djobs, K, max_w, max_diag, max_ncb); break;
     }
     if (r != IOC_OK) return r;
-    if (trace) PCHK(p, hipEventRecord(p->ev[2], s));
+    if (trace) IOC_CHK(p->ctx, hipEventRecord(p->ev[2], s));
     std::vector<uint8_t> back(small.size());
     std::vector<int32_t> haln(tot_aln);
-    PCHK(p, hipMemcpyAsync(back.data(), sm, small.size(), hipMemcpyDeviceToHost, s));
-    PCHK(p, hipMemcpyAsync(haln.data(), p->d_aln.p, tot_aln * 4, hipMemcpyDeviceToHost, s));
-    if (trace) PCHK(p, hipEventRecord(p->ev[3], s));
-    PCHK(p, hipStreamSynchronize(s));
+    IOC_CHK(p->ctx, hipMemcpyAsync(back.data(), sm, small.size(), hipMemcpyDeviceToHost, s));
+    IOC_CHK(p->ctx, hipMemcpyAsync(haln.data(), p->d_aln.p, tot_aln * 4, hipMemcpyDeviceToHost, s));
+    if (trace) IOC_CHK(p->ctx, hipEventRecord(p->ev[3], s));
+    IOC_CHK(p->ctx, hipStreamSynchronize(s));
     p->ms_gpu += now() - t_gpu;
     if (trace)
         for (int x = 0; x < 3; ++x) {
@@ -1661,9 +1648,7 @@ void ioc_poa_destroy(ioc_poa* p)
                 (long long)g_row_stats[0].load(), (long long)g_row_stats[1].load(), (long long)g_row_stats[2].load(), (long long)g_row_stats[3].load());
     for (auto& e : p->ev)
         if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&p->d_int, &p->d_dirs, &p->d_eb, &p->d_carry, &p->d_tbest, &p->d_small, &p->d_aln, &p->d_jobs})
-        if (b->p) (void)hipFree(b->p);
-    delete p;
+    delete p;  // (its DevBufs free their blocks)
 }
 
 void ioc_poa_bind(ioc_poa* p, ioc_consensus_ops* ops)

@@ -147,38 +147,7 @@ k_upd_sets(int32_t L, int32_t cls, const int64_t* __restrict__ set_off, const ui
     if (t < n_new) out_val[a + t] = new_set[t];
 }
 
-struct Tmp {
-    void* p = nullptr;
-    ~Tmp()
-    {
-        if (p) (void)hipFree(p);
-    }
-    template <class T>
-    T* as() const
-    {
-        return static_cast<T*>(p);
-    }
-};
-
 }  // namespace
-
-#define UCHK(c, call)                                                                             \
-    do {                                                                                          \
-        hipError_t e__ = (call);                                                                  \
-        if (e__ != hipSuccess)                                                                    \
-            return ioc_fail((c), IOC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-static int dev_alloc(ioc_ctx* c, Tmp& t, size_t bytes)
-{
-    const hipError_t e = hipMalloc(&t.p, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        t.p = nullptr;
-        return ioc_fail(c, IOC_ERR_CAPACITY, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    }
-    ioc_poison(t.p, bytes ? bytes : 16);
-    return IOC_OK;
-}
 
 extern "C" {
 
@@ -186,7 +155,7 @@ int ioc_index_update(ioc_ctx* c, int32_t cls, const uint32_t* old_min, int64_t n
                      int64_t n_new, uint8_t new_err_cell)
 {
     if (!c || n_old < 0 || n_new < 0 || (n_old > 0 && !old_min) || (n_new > 0 && !new_min)) return IOC_ERR_ARG;
-    UCHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     if (cls < 0 || cls >= c->L) return ioc_fail(c, IOC_ERR_ARG, "ioc_index_update: cluster id outside the left clusters");
     if (new_err_cell > 15) return ioc_fail(c, IOC_ERR_ARG, "ioc_index_update: err_cell outside 1..15 (0 = unchanged)");
     // ---- the two difference sets (std::set + set_difference of minimizer.cpp:127-143), on the host ----
@@ -203,40 +172,39 @@ int ioc_index_update(ioc_ctx* c, int32_t cls, const uint32_t* old_min, int64_t n
     {
         const int64_t a = c->h_lset_off[size_t(cls)], b = c->h_lset_off[size_t(cls) + 1];
         std::vector<uint32_t> cur(size_t(b - a));
-        if (b > a) UCHK(c, hipMemcpyAsync(cur.data(), static_cast<uint32_t*>(c->b_lset_val.p) + a, size_t(b - a) * 4, hipMemcpyDeviceToHost, s));
-        UCHK(c, hipStreamSynchronize(s));
+        if (b > a) IOC_CHK(c, hipMemcpyAsync(cur.data(), static_cast<uint32_t*>(c->b_lset_val.p) + a, size_t(b - a) * 4, hipMemcpyDeviceToHost, s));
+        IOC_CHK(c, hipStreamSynchronize(s));
         if (cur != olds)
             return ioc_fail(c, IOC_ERR_INPUT, "ioc_index_update: old minimizers differ from the cluster's values in the index");
     }
     if (new_err_cell) {  // the consensus also re-weights the representative's HPC error rate (consensus.cpp:56-58)
-        UCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(c->b_left_err.p) + cls, &new_err_cell, 1, hipMemcpyHostToDevice, s));
-        UCHK(c, hipStreamSynchronize(s));
+        IOC_CHK(c, hipMemcpyAsync(static_cast<uint8_t*>(c->b_left_err.p) + cls, &new_err_cell, 1, hipMemcpyHostToDevice, s));
+        IOC_CHK(c, hipStreamSynchronize(s));
         c->built = c->scored = c->resolved = false;
     }
     const int64_t n_keys = c->n_left_keys, n_post = c->n_left_post;
     const int64_t n_del = int64_t(to_del.size()), n_ins = int64_t(to_ins.size());
     if (n_del == 0 && n_ins == 0) return IOC_OK;
-    int r;
-    Tmp d_del, d_ins, d_kind, d_newlen, d_hit;
-    if ((r = dev_alloc(c, d_del, size_t(n_del) * 4)) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_ins, size_t(n_ins) * 4)) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_kind, size_t(n_keys))) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_newlen, size_t(n_keys) * 4)) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_hit, size_t(n_del + n_ins))) != IOC_OK) return r;
-    if (n_del) UCHK(c, hipMemcpyAsync(d_del.p, to_del.data(), size_t(n_del) * 4, hipMemcpyHostToDevice, s));
-    if (n_ins) UCHK(c, hipMemcpyAsync(d_ins.p, to_ins.data(), size_t(n_ins) * 4, hipMemcpyHostToDevice, s));
-    UCHK(c, hipMemsetAsync(d_hit.p, 0, size_t(n_del + n_ins) ? size_t(n_del + n_ins) : 1, s));
+    DevBuf d_del, d_ins, d_kind, d_newlen, d_hit;
+    IOC_TRY(ioc_alloc(c, d_del, size_t(n_del) * 4));
+    IOC_TRY(ioc_alloc(c, d_ins, size_t(n_ins) * 4));
+    IOC_TRY(ioc_alloc(c, d_kind, size_t(n_keys)));
+    IOC_TRY(ioc_alloc(c, d_newlen, size_t(n_keys) * 4));
+    IOC_TRY(ioc_alloc(c, d_hit, size_t(n_del + n_ins)));
+    if (n_del) IOC_CHK(c, hipMemcpyAsync(d_del.p, to_del.data(), size_t(n_del) * 4, hipMemcpyHostToDevice, s));
+    if (n_ins) IOC_CHK(c, hipMemcpyAsync(d_ins.p, to_ins.data(), size_t(n_ins) * 4, hipMemcpyHostToDevice, s));
+    IOC_CHK(c, hipMemsetAsync(d_hit.p, 0, size_t(n_del + n_ins) ? size_t(n_del + n_ins) : 1, s));
     if (n_keys > 0) {
         hipLaunchKernelGGL(k_upd_classify, dim3(uint32_t((n_keys + 255) / 256)), dim3(256), 0, s, n_keys,
                            static_cast<const uint32_t*>(c->b_lkeys.p), static_cast<const int64_t*>(c->b_loffs.p),
                            static_cast<const uint32_t*>(c->b_lpost.p), uint32_t(cls), d_del.as<uint32_t>(), n_del,
                            d_ins.as<uint32_t>(), n_ins, d_kind.as<uint8_t>(), d_newlen.as<uint32_t>(), d_hit.as<uint8_t>(),
                            d_hit.as<uint8_t>() + n_del);
-        UCHK(c, hipGetLastError());
+        IOC_CHK(c, hipGetLastError());
     }
     std::vector<uint8_t> hit(size_t(n_del + n_ins) + 1, 0);
-    UCHK(c, hipMemcpyAsync(hit.data(), d_hit.p, size_t(n_del + n_ins), hipMemcpyDeviceToHost, s));
-    UCHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipMemcpyAsync(hit.data(), d_hit.p, size_t(n_del + n_ins), hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     // difference-set values that are not keys yet: `db[m]` creates them (empty for toDel, [cls] for toIns)
     std::vector<uint32_t> abs_key;
     std::vector<uint8_t> abs_ins;
@@ -261,93 +229,59 @@ int ioc_index_update(ioc_ctx* c, int32_t cls, const uint32_t* old_min, int64_t n
     }
     const int64_t n_abs = int64_t(abs_key.size()), n_new_keys = n_keys + n_abs;
     if (n_post + n_ins >= (int64_t(1) << 31)) return ioc_fail(c, IOC_ERR_CAPACITY, "more than 2^31 index postings");
-    Tmp d_abs_key, d_abs_ins, d_len, d_src, d_off32, d_scan;
-    DevBuf nk, no, np, nso, nsv;  // the new left state
-    auto drop = [&]() {
-        for (DevBuf* b : {&nk, &no, &np, &nso, &nsv})
-            if (b->p) (void)hipFree(b->p);
-    };
-    auto grab = [&](DevBuf& b, size_t bytes) {
-        b.cap = bytes ? bytes : 16;
-        if (hipMalloc(&b.p, b.cap) != hipSuccess) return false;
-        ioc_poison(b.p, b.cap);
-        return true;
-    };
-    if ((r = dev_alloc(c, d_abs_key, size_t(n_abs) * 4)) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_abs_ins, size_t(n_abs))) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_len, size_t(n_new_keys + 1) * 4)) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_src, size_t(n_new_keys) * 8)) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_off32, size_t(n_new_keys + 1) * 4)) != IOC_OK) return r;
-    if ((r = dev_alloc(c, d_scan, size_t((n_new_keys + 1) / 256 + 1024) * 4 * 2)) != IOC_OK) return r;
+    DevBuf d_abs_key, d_abs_ins, d_len, d_src, d_off32, d_scan;
+    DevBuf nk, no, np, nso, nsv;  // the new left state (freed on every way out before it is swapped in)
+    IOC_TRY(ioc_alloc(c, d_abs_key, size_t(n_abs) * 4));
+    IOC_TRY(ioc_alloc(c, d_abs_ins, size_t(n_abs)));
+    IOC_TRY(ioc_alloc(c, d_len, size_t(n_new_keys + 1) * 4));
+    IOC_TRY(ioc_alloc(c, d_src, size_t(n_new_keys) * 8));
+    IOC_TRY(ioc_alloc(c, d_off32, size_t(n_new_keys + 1) * 4));
+    IOC_TRY(ioc_alloc(c, d_scan, size_t((n_new_keys + 1) / 256 + 1024) * 4 * 2));
     if (n_abs) {
-        UCHK(c, hipMemcpyAsync(d_abs_key.p, abs_key.data(), size_t(n_abs) * 4, hipMemcpyHostToDevice, s));
-        UCHK(c, hipMemcpyAsync(d_abs_ins.p, abs_ins.data(), size_t(n_abs), hipMemcpyHostToDevice, s));
+        IOC_CHK(c, hipMemcpyAsync(d_abs_key.p, abs_key.data(), size_t(n_abs) * 4, hipMemcpyHostToDevice, s));
+        IOC_CHK(c, hipMemcpyAsync(d_abs_ins.p, abs_ins.data(), size_t(n_abs), hipMemcpyHostToDevice, s));
     }
     const int64_t set_total = c->h_lset_off[size_t(c->L)];
     const int64_t new_set_total = set_total - int64_t(olds.size()) + int64_t(news.size());
     // postings: every toDel key that held cls loses one, every toIns key gains one (exact total: the scan)
-    if (!grab(nk, size_t(n_new_keys) * 4) || !grab(no, size_t(n_new_keys + 1) * 8) ||
-        !grab(np, size_t(n_post + n_ins) * 4) || !grab(nso, size_t(c->L + 1) * 8) ||
-        !grab(nsv, size_t(new_set_total) * 4)) {
-        drop();
-        return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_index_update: hipMalloc of the rewritten index failed");
-    }
+    IOC_TRY(ioc_alloc(c, nk, size_t(n_new_keys) * 4));
+    IOC_TRY(ioc_alloc(c, no, size_t(n_new_keys + 1) * 8));
+    IOC_TRY(ioc_alloc(c, np, size_t(n_post + n_ins) * 4));
+    IOC_TRY(ioc_alloc(c, nso, size_t(c->L + 1) * 8));
+    IOC_TRY(ioc_alloc(c, nsv, size_t(new_set_total) * 4));
     hipLaunchKernelGGL(k_upd_place, dim3(uint32_t((n_new_keys + 255) / 256)), dim3(256), 0, s, n_keys,
                        static_cast<const uint32_t*>(c->b_lkeys.p), d_newlen.as<uint32_t>(), n_abs, d_abs_key.as<uint32_t>(),
                        d_abs_ins.as<uint8_t>(), static_cast<uint32_t*>(nk.p), d_len.as<uint32_t>(), d_src.as<int64_t>());
-    if (hipGetLastError() != hipSuccess) {
-        drop();
-        return ioc_fail(c, IOC_ERR_HIP, "k_upd_place launch failed");
-    }
-    if (iock_exclusive_scan(s, d_len.as<uint32_t>(), n_new_keys, d_off32.as<uint32_t>(), d_scan.as<uint32_t>(), 0u) != hipSuccess) {
-        drop();
+    if (hipGetLastError() != hipSuccess) return ioc_fail(c, IOC_ERR_HIP, "k_upd_place launch failed");
+    if (iock_exclusive_scan(s, d_len.as<uint32_t>(), n_new_keys, d_off32.as<uint32_t>(), d_scan.as<uint32_t>(), 0u) != hipSuccess)
         return ioc_fail(c, IOC_ERR_HIP, "exclusive scan of the new list lengths failed");
-    }
     uint32_t total = 0;  // out[n] of the scan
-    UCHK(c, hipMemcpyAsync(&total, d_off32.as<uint32_t>() + n_new_keys, 4, hipMemcpyDeviceToHost, s));
-    UCHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipMemcpyAsync(&total, d_off32.as<uint32_t>() + n_new_keys, 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     hipLaunchKernelGGL(k_upd_copy, dim3(uint32_t(((n_new_keys + 1) * 64 + 255) / 256)), dim3(256), 0, s, n_new_keys,
                        d_src.as<int64_t>(), d_off32.as<uint32_t>(), static_cast<const int64_t*>(c->b_loffs.p),
                        static_cast<const uint32_t*>(c->b_lpost.p), d_kind.as<uint8_t>(), uint32_t(cls),
                        static_cast<uint32_t*>(np.p), static_cast<int64_t*>(no.p), total);
-    if (hipGetLastError() != hipSuccess) {
-        drop();
-        return ioc_fail(c, IOC_ERR_HIP, "k_upd_copy launch failed");
-    }
+    if (hipGetLastError() != hipSuccess) return ioc_fail(c, IOC_ERR_HIP, "k_upd_copy launch failed");
     // ---- value sets: the cluster's segment becomes its new sorted set ----
-    Tmp d_newset;
-    if ((r = dev_alloc(c, d_newset, news.size() * 4)) != IOC_OK) {
-        drop();
-        return r;
-    }
-    if (!news.empty()) UCHK(c, hipMemcpyAsync(d_newset.p, news.data(), news.size() * 4, hipMemcpyHostToDevice, s));
+    DevBuf d_newset;
+    IOC_TRY(ioc_alloc(c, d_newset, news.size() * 4));
+    if (!news.empty()) IOC_CHK(c, hipMemcpyAsync(d_newset.p, news.data(), news.size() * 4, hipMemcpyHostToDevice, s));
     {
         const int64_t span = std::max<int64_t>(std::max<int64_t>(set_total, int64_t(news.size())), int64_t(c->L) + 1);
         hipLaunchKernelGGL(k_upd_sets, dim3(uint32_t((span + 255) / 256)), dim3(256), 0, s, c->L, cls,
                            static_cast<const int64_t*>(c->b_lset_off.p), static_cast<const uint32_t*>(c->b_lset_val.p), set_total,
                            d_newset.as<uint32_t>(), int64_t(news.size()), static_cast<int64_t*>(nso.p), static_cast<uint32_t*>(nsv.p));
-        if (hipGetLastError() != hipSuccess) {
-            drop();
-            return ioc_fail(c, IOC_ERR_HIP, "k_upd_sets launch failed");
-        }
+        if (hipGetLastError() != hipSuccess) return ioc_fail(c, IOC_ERR_HIP, "k_upd_sets launch failed");
     }
-    UCHK(c, hipStreamSynchronize(s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     // ---- swap the new state in ----
-    for (DevBuf* b : {&c->b_lkeys, &c->b_loffs, &c->b_lpost, &c->b_lset_off, &c->b_lset_val})
-        if (b->p) (void)hipFree(b->p);
-    c->b_lkeys = nk;
-    c->b_loffs = no;
-    c->b_lpost = np;
-    c->b_lset_off = nso;
-    c->b_lset_val = nsv;
-    if (c->b_lslot.cap < size_t(n_new_keys) * 4) {
-        if (c->b_lslot.p) (void)hipFree(c->b_lslot.p);
-        c->b_lslot.p = nullptr;
-        c->b_lslot.cap = 0;
-        if (hipMalloc(&c->b_lslot.p, size_t(n_new_keys) * 4 + 16) != hipSuccess)
-            return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_index_update: hipMalloc failed");
-        c->b_lslot.cap = size_t(n_new_keys) * 4 + 16;
-    }
+    c->b_lkeys = std::move(nk);  // (the old blocks are freed: the stream is idle)
+    c->b_loffs = std::move(no);
+    c->b_lpost = std::move(np);
+    c->b_lset_off = std::move(nso);
+    c->b_lset_val = std::move(nsv);
+    IOC_TRY(ioc_reserve(c, c->b_lslot, size_t(n_new_keys) * 4));
     c->n_left_keys = n_new_keys;
     c->n_left_post = int64_t(total);
     const int64_t a = c->h_lset_off[size_t(cls)], b = c->h_lset_off[size_t(cls) + 1];
@@ -360,19 +294,19 @@ int ioc_index_update(ioc_ctx* c, int32_t cls, const uint32_t* old_min, int64_t n
 int ioc_left_export(ioc_ctx* c, int64_t* n_keys, int64_t* n_postings, uint32_t* keys, int64_t* offs, uint32_t* postings)
 {
     if (!c) return IOC_ERR_ARG;
-    UCHK(c, hipSetDevice(c->device));
+    IOC_CHK(c, hipSetDevice(c->device));
     if (n_keys) *n_keys = c->n_left_keys;
     if (n_postings) *n_postings = c->n_left_post;
     hipStream_t s = c->stream;
-    if (keys && c->n_left_keys) UCHK(c, hipMemcpyAsync(keys, c->b_lkeys.p, size_t(c->n_left_keys) * 4, hipMemcpyDeviceToHost, s));
+    if (keys && c->n_left_keys) IOC_CHK(c, hipMemcpyAsync(keys, c->b_lkeys.p, size_t(c->n_left_keys) * 4, hipMemcpyDeviceToHost, s));
     if (offs) {
         if (c->n_left_keys)
-            UCHK(c, hipMemcpyAsync(offs, c->b_loffs.p, size_t(c->n_left_keys + 1) * 8, hipMemcpyDeviceToHost, s));
+            IOC_CHK(c, hipMemcpyAsync(offs, c->b_loffs.p, size_t(c->n_left_keys + 1) * 8, hipMemcpyDeviceToHost, s));
         else
             offs[0] = 0;
     }
-    if (postings && c->n_left_post) UCHK(c, hipMemcpyAsync(postings, c->b_lpost.p, size_t(c->n_left_post) * 4, hipMemcpyDeviceToHost, s));
-    UCHK(c, hipStreamSynchronize(s));
+    if (postings && c->n_left_post) IOC_CHK(c, hipMemcpyAsync(postings, c->b_lpost.p, size_t(c->n_left_post) * 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
     return IOC_OK;
 }
 

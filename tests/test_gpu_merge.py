@@ -71,6 +71,33 @@ def test_distinct_by_radix_sort_equals_the_bitonic_network(ctx, monkeypatch):
     assert np.array_equal(ca, cb) and np.array_equal(sa, sb_)
 
 
+@pytest.fixture(scope="module")
+def small_oracle_runs():
+    """The oracle's clustering of two small read sets, computed once: sorted batch, MinDB, assignments."""
+    runs = {}
+    for cfg, seed in (("tiny", 1), ("short_dup", 2)):
+        rs = synth.generate_config(cfg, seed=seed)
+        obs, sbs = _batches(rs, 1)
+        obs[0].cluster(mode="fast")
+        runs[cfg] = (rs.n, sbs[0], obs[0], obs[0].assignments(rs.n))
+    return runs
+
+
+@pytest.mark.parametrize("cfg", ["tiny", "short_dup"])
+@pytest.mark.parametrize("switches", [{"IOC_POST16": "0"}, {"IOC_BUILD_SORT": "0"}, {"IOC_POST16": "0", "IOC_BUILD_SORT": "0"}],
+                         ids=["post32", "hash_build", "post32_hash_build"])
+def test_both_builds_and_both_posting_widths_equal_the_oracle(ctx, monkeypatch, small_oracle_runs, switches, cfg):
+    """ioc_index_build has two build methods (sorted; hash, otherwise reached only through k > 16) and two posting widths
+    (16 bits while L + N <= 65535; 32 bits): each combination that is not the default gives the oracle's assignments and MinDB."""
+    n, sb, B, (ocl, ost) = small_oracle_runs[cfg]
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    cb = pipeline.cluster_single(ctx, api.default_params(11, 15, "fast"), sb)
+    cls, strand = cb.assignments(n)
+    assert np.array_equal(cls, ocl) and np.array_equal(strand, ost)
+    _same_index(cb, B)
+
+
 def test_index_export_ordered_on_the_device_equals_the_host_ordered_one(ctx, monkeypatch):
     """ioc_index_export orders the keys on the device (ioc_sort.hip); IOC_EXPORT_HOST_ORDER=1 is the host's std::sort
     of round 2's first version: same CSR, also for a merge (left lists + right lists in one index)."""
