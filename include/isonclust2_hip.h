@@ -120,6 +120,17 @@ int ioc_index_update(ioc_ctx* ctx, int32_t cls, const uint32_t* old_min, int64_t
  * keys with empty lists included.  Call with keys == NULL to size. */
 int ioc_left_export(ioc_ctx* ctx, int64_t* n_keys, int64_t* n_postings, uint32_t* keys, int64_t* offs,
                     uint32_t* postings);
+/* After a resolved pass (ioc_resolve, ioc_cluster_batch / _merge, chunked or not): the clusters as they stand,
+ * i.e. the left clusters plus every query that opened one, in final ids, BECOME the context's left state, on the device.
+ * The result is what ioc_index_export followed by ioc_left_load (with the representatives' err cells) would
+ * have loaded: keys strictly ascending, posting lists strictly ascending, no empty lists, the per-cluster
+ * sorted value sets, the err cell of every cluster, n_left_keys / n_left_post / L updated.  The queries are
+ * released (built / scored / resolved false).  *n_clusters receives the new L (may be NULL).
+ * IOC_ERR_STATE without a resolved pass.
+ * No key and no posting travels to the host: the next pass runs against the resident left view (ioc_left_view::n_keys
+ * == -1), ioc_index_update edits the adopted state, ioc_left_export reads it back.  (After ioc_cluster_consensus the
+ * MinDB lives on the host — UpdateMinDB's edits are made there — and there is nothing to adopt: IOC_ERR_STATE.) */
+int ioc_left_adopt(ioc_ctx* ctx, int32_t* n_clusters);
 
 /* ---- the hot path ---------------------------------------------------------------------------- */
 /* AddMinimizers for every tentative representative at once (src/minimizer.cpp:31-42): per-query
@@ -381,7 +392,7 @@ typedef struct {
     int32_t n_clusters;
     const double* cls_hpc_err; /* [n_clusters] HpcSeq->ErrorRate() of each representative */
     int64_t n_keys;            /* -1 with keys == NULL: keep the left state that is on the device
-                                  (ioc_left_load, then any ioc_index_update); n_clusters must match it */
+                                  (ioc_left_load or ioc_left_adopt, then any ioc_index_update); n_clusters must match it */
     const uint32_t* keys;
     const int64_t* offs;       /* [n_keys+1] */
     const uint32_t* postings;
@@ -420,7 +431,8 @@ int ioc_cluster_batch(ioc_ctx* ctx, const ioc_params* p, const char* table_path,
  * uploaded, by a thread of the library, while the first kernels run.)
  * A right batch of more than 131 072 entries (one device pass: the all-pairs candidate tables grow with the square of the
  * entries) runs in chunks of that many, in order, each against the left state the chunks before it left behind — the
- * reference's one loop; the results are those of one pass.  After such a call the context's resident queries are the last
+ * reference's one loop; the results are those of one pass.  Between two chunks the clustering so far is adopted as the left
+ * state on the device (ioc_left_adopt); the call may start from a resident left state.  After such a call the context's resident queries are the last
  * chunk's (ioc_gather_records_device refuses).  No limit on a read's length: queries of more than 8192 forward minimizers
  * are sorted in global memory instead of LDS (src/minimizer.cpp:78-123 has plain vectors). */
 int ioc_cluster_merge(ioc_ctx* ctx, const ioc_params* p, const char* table_path, const ioc_left_view* left,

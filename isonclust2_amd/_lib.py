@@ -121,7 +121,7 @@ SYMBOLS = [
     "ioc_cluster_batch", "ioc_cluster_merge", "ioc_cluster_resident", "ioc_host_align", "ioc_host_gap_open",
     "ioc_host_aln_ratio", "ioc_host_align_ops", "ioc_host_ops_to_cigar", "ioc_align_set_pool", "ioc_align_pairs", "ioc_align_ops_bound",
     "ioc_align_pairs_ops", "ioc_set_aln_verdicts", "ioc_get_ties", "ioc_resident_set_sequences",
-    "ioc_index_update", "ioc_left_export", "ioc_cluster_consensus",
+    "ioc_index_update", "ioc_left_export", "ioc_left_adopt", "ioc_cluster_consensus",
     "ioc_poa_create", "ioc_poa_create_mode", "ioc_poa_destroy", "ioc_poa_bind", "ioc_poa_graph_export", "ioc_poa_last_alignment",
     "ioc_poa_graph_save", "ioc_poa_graph_load", "ioc_poa_graph_load_many", "ioc_gather_records_device", "ioc_queries_generation", "ioc_scored_candidates",
     "ioc_dist_unique_id", "ioc_dist_init", "ioc_dist_shutdown", "ioc_dist_info", "ioc_dist_allgather_device",
@@ -169,6 +169,7 @@ def load():
     L.ioc_left_load.argtypes = [vp, i32, pu8, i64, pu32, pi64, pu32]
     L.ioc_index_update.argtypes = [vp, i32, pu32, i64, pu32, i64, C.c_uint8]
     L.ioc_left_export.argtypes = [vp, pi64, pi64, pu32, pi64, pu32]
+    L.ioc_left_adopt.argtypes = [vp, pi32]
     L.ioc_index_build.argtypes = [vp]
     L.ioc_score.argtypes = [vp]
     L.ioc_resolve.argtypes = [vp, pi32]

@@ -148,6 +148,14 @@ class Context:
                                          _p(offs, C.c_int64), _p(post, C.c_uint32)))
         return keys, offs, post[:npost.value]
 
+    def left_adopt(self):
+        """ioc_left_adopt: the clustering just resolved (left clusters + every query that opened one) becomes the left
+        state, on the device.  Returns the new cluster count; the next call runs against it with left = dict(resident=True,
+        cls_hpc_err=...)."""
+        ncl = C.c_int32(0)
+        self._chk(self.L.ioc_left_adopt(self.h, C.byref(ncl)))
+        return int(ncl.value)
+
     def index_build(self):
         self._chk(self.L.ioc_index_build(self.h))
 
@@ -392,10 +400,17 @@ class Context:
         v, n, _alive = self._make_view(batch)
         lv = None
         if left is not None and left.get("resident"):
-            # the left state already on the device (left_load + index_update) is used as it is
+            # the left state already on the device (left_load / left_adopt + index_update) is used as it is; the
+            # representatives' sequences (sahlin / furious) are host data all the same
             le = np.ascontiguousarray(left["cls_hpc_err"], np.float64)
+            lseq = loff = lerr = None
+            if left.get("rep_seq") is not None:
+                lseq = left["rep_seq"] if isinstance(left["rep_seq"], bytes) else np.asarray(left["rep_seq"], np.uint8).tobytes()
+                loff = np.ascontiguousarray(left["rep_off"], np.int64)
+                lerr = np.ascontiguousarray(left["cls_raw_err"], np.float64)
             lv = LeftView(n_clusters=len(le), cls_hpc_err=_p(le, C.c_double), n_keys=-1, keys=None, offs=None,
-                          postings=None, rep_seq=None, rep_off=None, cls_raw_err=None)
+                          postings=None, rep_seq=lseq, rep_off=_p(loff, C.c_int64) if loff is not None else None,
+                          cls_raw_err=_p(lerr, C.c_double) if lerr is not None else None)
         elif left is not None:
             le = np.ascontiguousarray(left["cls_hpc_err"], np.float64)
             lk = np.ascontiguousarray(left["keys"], np.uint32)

@@ -602,7 +602,8 @@ int build_plan(ioc_ctx* c, BuildPlan& pl)
     pl.NP = pl.nfwd_total + c->n_left_post;
     if (pl.NP >= (int64_t(1) << 31)) return ioc_fail(c, IOC_ERR_CAPACITY, "more than 2^31 index postings");
     if (uint64_t(c->L) + uint64_t(n) >= (1ull << 31)) return ioc_fail(c, IOC_ERR_CAPACITY, "too many targets");
-    if (uint32_t(n) > 131072u) return ioc_fail(c, IOC_ERR_CAPACITY, "more than 131072 queries per device pass (ioc_cluster_merge runs a larger batch in chunks)");
+    if (n > IOC_PASS_ENTRIES)
+        return ioc_fail(c, IOC_ERR_CAPACITY, "more than " + std::to_string(IOC_PASS_ENTRIES) + " queries per device pass (ioc_cluster_merge and ioc_cluster_consensus cut a larger batch themselves)");
     while (pl.pmax < uint32_t(c->max_fwd)) pl.pmax <<= 1;
     // (IOC_DISTINCT_BITONIC=1, the round-1 network kept for comparison, sorts up to 32768 in LDS instead)
     const bool bitonic = pl.pmax > IOC_DISTINCT_LDS_MAX && env_u32("IOC_DISTINCT_BITONIC", 0) == 1;
@@ -1771,7 +1772,7 @@ struct ExportLap {
 static int export_device_order(ioc_ctx* c, uint32_t nslots, ExportLap& lap);
 static int export_host_order(ioc_ctx* c, uint32_t nslots, ExportLap& lap);
 
-static int index_export_compute(ioc_ctx* c)
+static int index_export_compute(ioc_ctx* c, bool on_device = false)
 {
     // The final MinDB = the index's posting lists restricted to the targets that are clusters, with final ids
     // (AddMinimizers for every query that opened a cluster, minimizer.cpp:31-42).  Filtering and renumbering run on the
@@ -1791,6 +1792,7 @@ static int index_export_compute(ioc_ctx* c)
     int32_t next = c->L;
     for (int i = 0; i < c->n; ++i)
         if (valid[size_t(i)]) cid[size_t(i)] = next++;
+    c->exp_clusters = next;
     IOC_TRY(ioc_reserve(c, c->b_exp_cid, (size_t(c->n) + 1) * 4));
     IOC_TRY(ioc_reserve(c, c->b_exp_cnt, size_t(nslots) * 4));
     IOC_TRY(ioc_reserve(c, c->b_exp_off, size_t(nslots) * 8));
@@ -1799,7 +1801,7 @@ static int index_export_compute(ioc_ctx* c)
                                  c->b_exp_cid.as<int32_t>(), c->b_exp_cnt.as<uint32_t>()));
     // keys whose every contributor joined another cluster were never inserted by AddMinimizers: no entry (the reference
     // keeps keys with emptied lists only through UpdateMinDB, i.e. in consensus mode)
-    return env_u32("IOC_EXPORT_HOST_ORDER", 0) == 0 ? export_device_order(c, nslots, lap) : export_host_order(c, nslots, lap);
+    return on_device || env_u32("IOC_EXPORT_HOST_ORDER", 0) == 0 ? export_device_order(c, nslots, lap) : export_host_order(c, nslots, lap);
 }
 
 // the kept keys in ascending order, the offsets of their lists and every slot's place: on the device (ioc_sort.hip)
@@ -1879,6 +1881,22 @@ static int export_host_order(ioc_ctx* c, uint32_t nslots, ExportLap& lap)
     c->exp_valid = true;
     return IOC_OK;
 }
+
+}  // extern "C"
+
+int32_t ioc_pass_entries()
+{
+    if (const char* e = getenv("IOC_MERGE_CHUNK")) return std::max(1, std::min<int>(IOC_PASS_ENTRIES, atoi(e)));
+    return IOC_PASS_ENTRIES;
+}
+
+int ioc_export_on_device(ioc_ctx* c)
+{
+    if (!c->resolved) return ioc_fail(c, IOC_ERR_STATE, "ioc_resolve first");
+    return c->exp_dev ? IOC_OK : index_export_compute(c, true);
+}
+
+extern "C" {
 
 int ioc_index_export(ioc_ctx* c, int64_t* n_keys, int64_t* n_postings, uint32_t* keys, int64_t* offs,
                      uint32_t* postings)

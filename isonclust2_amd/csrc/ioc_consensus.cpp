@@ -244,6 +244,7 @@ int ioc_cluster_consensus(ioc_ctx* c, const ioc_params* p, const char* table_pat
     int window = n;
     if (const char* e = getenv("IOC_CONS_WINDOW")) window = std::max(1, atoi(e));
     const bool fixed_window = getenv("IOC_CONS_WINDOW") != nullptr;
+    const int pass_cap = ioc_pass_entries();
     std::vector<uint32_t> wval, wpos;
     // Deferred consensus (ioc_consensus_spec_ops; IOC_CONS_SPECULATE=0 switches it off): the walk does not wait for a
     // consensus — it records the event, queues the request and goes on as long as the entries it meets cannot see the
@@ -318,7 +319,7 @@ int ioc_cluster_consensus(ioc_ctx* c, const ioc_params* p, const char* table_pat
         return false;
     };
     while (pos < n) {
-        const int m = std::min(n - pos, window);
+        const int m = std::min(std::min(n - pos, window), pass_cap);  // (no window beyond one device pass)
         double t0 = now();
         // ---- left view of the current state ----
         const int32_t Lc = int32_t(cl.size());

@@ -136,6 +136,8 @@ struct ioc_ctx {
     // left clusters' value sets (transposed MinDB), built by ioc_left_load
     DevBuf b_lset_off, b_lset_val;
     std::vector<int64_t> h_lset_off;  // host copy of the value-set offsets (ioc_index_update)
+    // ioc_left_adopt builds the next left state here and swaps it in: the blocks the swap retires serve the adoption after it
+    DevBuf b_alt_err, b_alt_keys, b_alt_offs, b_alt_set_off, b_alt_set_val, b_adopt_work;
 
     // ---- index (ioc_index_build) ----
     bool built = false;
@@ -184,6 +186,7 @@ struct ioc_ctx {
     bool exp_valid = false;   // exp_keys / exp_offs / exp_post hold the export (consensus driver; IOC_EXPORT_HOST_ORDER)
     bool exp_dev = false;     // the export is ready ON THE DEVICE: exp_nrows keys at b_exp_work + exp_o_keys, exp_nrows + 1 int64
                               // offsets at + exp_o_offs, exp_total postings in b_exp_out (copied straight into the caller's arrays)
+    int32_t exp_clusters = 0;  // clusters of the exported state: L + the queries that opened one
     uint32_t exp_nrows = 0;
     uint64_t exp_total = 0;
     size_t exp_o_keys = 0, exp_o_offs = 0;
@@ -251,6 +254,15 @@ struct ioc_ctx {
 };
 
 int ioc_fail(ioc_ctx* c, int code, const std::string& msg);
+
+// Entries one device pass takes (the all-pairs candidate tables grow with the square of the entries).  ioc_index_build refuses
+// more; ioc_cluster_merge runs a larger right batch in chunks, ioc_cluster_consensus in windows of at most this many entries.
+constexpr int32_t IOC_PASS_ENTRIES = 131072;
+// ... and what the two drivers cut at: IOC_MERGE_CHUNK (entries, 1 .. IOC_PASS_ENTRIES) when set, else IOC_PASS_ENTRIES
+int32_t ioc_pass_entries();
+// ioc_capi.cpp: the export of the current resolve (ioc_index_export) ready ON THE DEVICE (ioc_ctx::exp_dev), whatever
+// IOC_EXPORT_HOST_ORDER says
+int ioc_export_on_device(ioc_ctx* c);
 
 // a HIP call of a function that returns an ioc status: on failure "<call text>: <hipGetErrorString>" and IOC_ERR_HIP
 #define IOC_CHK(c, call)                                                                           \

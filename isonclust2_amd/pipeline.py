@@ -171,6 +171,59 @@ def cluster_single(ctx, params, sb: SortedBatch, timing=None) -> ClusteredBatch:
                           batch_start=sb.batch_start, batch_end=sb.batch_end, stats=st)
 
 
+def cluster_stream(ctx, params, sorted_batches) -> ClusteredBatch:
+    """Consecutive sorted batches (e.g. `slice_sorted` slices of one sorted read set, in order) clustered into ONE
+    ClusteredBatch: the reference's loop (src/cluster.cpp:115) over all their entries.  Between two batches the clustering
+    so far becomes the left state ON THE DEVICE (Context.left_adopt): no MinDB travels to the host until the final export.
+    The host keeps the bookkeeping and, for sahlin / furious (batches that carry raw_seq), the representatives' sequences
+    and raw error rates.  For slices of one sorted batch the result equals `cluster_single` of that batch."""
+    sbs = list(sorted_batches)
+    if not sbs:
+        raise ValueError("cluster_stream: no batch")
+    L, base = 0, 0
+    seqs = all(sb.view.get("raw_seq") is not None for sb in sbs)
+    rep_view, rep_seq, rep_off = None, (b"" if seqs else None), (np.zeros(1, np.int64) if seqs else None)
+    rep_entry, m_cls, m_read, m_strand = [], [], [], []
+    stats = {}
+    for j, sb in enumerate(sbs):
+        left = None
+        if j > 0:
+            if ctx.left_adopt() != L:
+                raise RuntimeError("cluster_stream: the adopted left state holds a different number of clusters")
+            left = dict(resident=True, cls_hpc_err=rep_view["hpc_err"] if L else np.zeros(0, np.float64))
+            if seqs and L:
+                left.update(rep_seq=rep_seq, rep_off=rep_off, cls_raw_err=rep_view["raw_err"])
+        cls, strand, st = ctx.cluster_merge(params, left, sb.view)
+        for k, v in st.items():
+            stats[k] = v if k in ("n_clusters",) else (max(stats.get(k, 0), v) if k == "resolve_iters" else stats.get(k, 0) + v)
+        ok = cls >= 0
+        new = np.nonzero(cls >= L)[0]
+        uniq, first = np.unique(cls[new], return_index=True)   # entries are in loop order: the first one of an id opened it
+        created = new[first]
+        assert np.array_equal(uniq, L + np.arange(len(uniq))) and L + len(uniq) == int(st["n_clusters"])
+        if len(created):
+            rv = gather_records(sb.view, created)
+            rep_view = rv if rep_view is None else concat_records(rep_view, rv)
+            if seqs:
+                add, ao = gather_seqs(sb.view["raw_seq"], sb.view["raw_off"], created)
+                rep_seq = rep_seq + add
+                rep_off = np.concatenate([rep_off, ao[1:] + rep_off[-1]])
+            rep_entry.append(base + created)
+            L += len(created)
+        m_cls.append(cls[ok].astype(np.int32))
+        m_read.append(np.asarray(sb.read_ids)[ok].astype(np.int64))
+        m_strand.append(strand[ok].astype(np.int32))
+        base += len(cls)
+    keys, offs, post = ctx.index_export()
+    if rep_view is None:
+        rep_view = gather_records(sbs[0].view, np.zeros(0, np.int64))
+    return ClusteredBatch(rep_view=rep_view, rep_seq=rep_seq, rep_off=rep_off,
+                          rep_entry=(np.concatenate(rep_entry) if rep_entry else np.zeros(0, np.int64)).astype(np.int32),
+                          ctx_serial=-1, member_cls=np.concatenate(m_cls), member_read=np.concatenate(m_read),
+                          member_strand=np.concatenate(m_strand), mindb=(keys, offs, post), depth=sbs[0].depth + 1,
+                          batch_start=sbs[0].batch_start, batch_end=sbs[-1].batch_end, stats=stats)
+
+
 def cluster_merge(ctx, params, left: ClusteredBatch, right: ClusteredBatch, min_cls_size=3) -> ClusteredBatch:
     """`cluster -l L -r R` (src/main.cpp:247-261 + src/cluster.cpp:67-322): every right cluster's
     representative is matched against the left MinDB; members move with their strands flipped on a
