@@ -280,16 +280,23 @@ def _run_consensus(ctx, rs, mode, cons, window=None, speculate=True, monkeypatch
     return cls, strand, st, events, db, graphs
 
 
-@pytest.mark.parametrize("shape,mode,cons,window", [((300, 6, 600), "fast", (3, 12, 500), None), ((300, 6, 600), "fast", (3, 12, 500), 7),
-                                                    ((260, 10, 500), "sahlin", (2, 8, 40), None), ((400, 5, 400), "fast", (4, 1000, 500), 64),
-                                                    ((220, 3, 900), "sahlin", (3, 6, 500), 16)])
+_CONSENSUS_CASES = [((300, 6, 600), "fast", (3, 12, 500), None), ((300, 6, 600), "fast", (3, 12, 500), 7),
+                    ((260, 10, 500), "sahlin", (2, 8, 40), None), ((400, 5, 400), "fast", (4, 1000, 500), 64),
+                    ((220, 3, 900), "sahlin", (3, 6, 500), 16)]
+
+
+def _consensus_reads(shape, mode):
+    from isonclust2_amd import synth
+    return synth.generate(shape[0], shape[1], shape[2], 11, 21, seed=sum(shape) + len(mode), dup_every=2 if shape[1] > 8 else 0)
+
+
+@pytest.mark.parametrize("shape,mode,cons,window", _CONSENSUS_CASES)
 def test_deferred_consensus_equals_immediate(ctx, monkeypatch, shape, mode, cons, window):
     """The driver with deferred consensus requests (ioc_consensus_spec_ops: events of many clusters of a pass batched,
     verification afterwards, rollback on a violation) against the same driver taking every consensus at once, as the
     reference does: assignments, the sequence of representative replacements with their consensus sequences, the final
     MinDB and every cluster's final graph must be the same."""
-    from isonclust2_amd import synth
-    rs = synth.generate(shape[0], shape[1], shape[2], 11, 21, seed=sum(shape) + len(mode), dup_every=2 if shape[1] > 8 else 0)
+    rs = _consensus_reads(shape, mode)
     a = _run_consensus(ctx, rs, mode, cons, window, speculate=False, monkeypatch=monkeypatch)
     b = _run_consensus(ctx, rs, mode, cons, window, speculate=True, monkeypatch=monkeypatch)
     assert a[2]["n_cons_invoked"] > 5
@@ -312,6 +319,50 @@ def test_deferred_consensus_equals_immediate(ctx, monkeypatch, shape, mode, cons
         for x, y in zip(a[4], c[4]):
             assert np.array_equal(x, y)
         assert a[5] == c[5]
+
+
+# the three legs of the driver recorded in tests/golden/consensus_driver_parent.json: (IOC_CONS_SPECULATE, IOC_CONS_FORCE_ROLLBACK)
+_DRIVER_LEGS = {"immediate": (False, None), "deferred": (True, None), "deferred_rollback2": (True, "2")}
+
+
+def _case_key(shape, mode, cons, window):
+    return "-".join(str(v) for v in (*shape, mode, *cons, "w%s" % window))
+
+
+def _driver_record(ctx, monkeypatch, shape, mode, cons, window):
+    """Per leg: the whole stats dict and a sha256 over assignments, strands, the exported MinDB and the representative events."""
+    import hashlib
+    rs = _consensus_reads(shape, mode)
+    out = {}
+    for leg, (speculate, force) in _DRIVER_LEGS.items():
+        if force:
+            monkeypatch.setenv("IOC_CONS_FORCE_ROLLBACK", force)
+        else:
+            monkeypatch.delenv("IOC_CONS_FORCE_ROLLBACK", raising=False)
+        cls, strand, st, events, db, _ = _run_consensus(ctx, rs, mode, cons, window, speculate=speculate, monkeypatch=monkeypatch)
+        h = hashlib.sha256()
+        for arr, dt in ((cls, np.int32), (strand, np.int8), (db[0], np.uint32), (db[1], np.int64), (db[2], np.uint32)):
+            h.update(np.ascontiguousarray(arr, dt).tobytes())
+        h.update(repr(events).encode())
+        out[leg] = {"stats": {k: int(v) for k, v in st.items()}, "sha256": h.hexdigest()}
+    return out
+
+
+@pytest.mark.parametrize("shape,mode,cons,window", _CONSENSUS_CASES)
+def test_driver_equals_the_recorded_parent(ctx, monkeypatch, shape, mode, cons, window):
+    """The consensus driver against numbers recorded from the commit before it was split into stages (tests/golden/
+    consensus_driver_parent.json): same decisions, MinDB and representative events (sha256), and the same counters —
+    n_cons_restarts and the alignment counters are functions of the walk and of the window rule, so equality there is
+    what "same speed" means for this host driver."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(__file__), "golden", "consensus_driver_parent.json")) as f:
+        want = json.load(f)[_case_key(shape, mode, cons, window)]
+    got = _driver_record(ctx, monkeypatch, shape, mode, cons, window)
+    for leg in _DRIVER_LEGS:
+        print(leg, got[leg])
+        assert got[leg]["stats"] == want[leg]["stats"], leg
+        assert got[leg]["sha256"] == want[leg]["sha256"], leg
 
 
 @pytest.mark.gpu
