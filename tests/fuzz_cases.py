@@ -43,7 +43,54 @@ def draw_parity(rng, aln_mode=None):
     seed = int(rng.integers(0, 1 << 30))
     if aln_mode:
         n, ln = min(n, 70), min(ln, 350)
-    return dict(n=n, g=g, ln=ln, qlo=qlo, qhi=qhi, dup=dup, jit=jit, k=k, w=w, seed=seed, mode=aln_mode or "fast")
+    c = dict(n=n, g=g, ln=ln, qlo=qlo, qhi=qhi, dup=dup, jit=jit, k=k, w=w, seed=seed, mode=aln_mode or "fast")
+    c.update(draw_shape(c))
+    return c
+
+
+def draw_shape(c):
+    """The `shape` of a parity case's reads (and its `sargs`): about two in three `random` (synth.generate, as before the
+    key existed), the others structured (tests/structured_reads.py).  Drawn from a generator split off the case's seed, so the
+    stream `rng` of draw_parity yields the cases it always did."""
+    srng = np.random.default_rng([int(c["seed"]), 0x5A])
+    shape = str(srng.choice(["random", "random", "random", "random", "random", "random", "family", "isoforms", "repeat"]))
+    trunc = float(srng.choice([0.0, 0.0, 0.4]))
+    if shape == "family":
+        return dict(shape=shape, sargs=dict(core_frac=float(srng.choice([0.2, 0.3, 0.55, 0.8])), truncate=trunc))
+    if shape == "isoforms":
+        return dict(shape=shape, sargs=dict(per_gene=int(srng.integers(2, 6)), exons=int(srng.integers(3, 8)), truncate=trunc))
+    if shape == "repeat":
+        return dict(shape=shape, sargs=dict(period=int(srng.choice([2, 3, 4, 5, 7, 12, 30])),
+                                            block_frac=float(srng.choice([0.25, 0.5])), truncate=trunc))
+    return dict(shape=shape)
+
+
+def parity_reads(c):
+    """The reads of a parity case.  No `shape` key (a reproducer from before the key existed) means `random`.  A structured
+    shape takes n, g, ln, jit, the quality range and the seed from the case and has no use for `dup` (exact duplicates are
+    synth.generate's own structure); its reads are as long as the case draws them (up to ~3000 bases), not held to the 900
+    bases of the fixed cases of structured_reads.CASES."""
+    shape = c.get("shape", "random")
+    if shape == "random":
+        return synth.generate(c["n"], c["g"], c["ln"], c["qlo"], c["qhi"], seed=c["seed"], dup_every=c["dup"], len_jitter=c["jit"])
+    from tests import structured_reads as sr
+    a = dict(c.get("sargs") or {})
+    trunc = float(a.pop("truncate", 0.0))
+    g, ln = int(c["g"]), int(c["ln"])
+    length = (max(64, int(ln * (1 - c["jit"]))), int(ln * (1 + c["jit"]))) if c["jit"] else ln
+    if shape == "family":
+        builder, args = "core_family", dict(members=g, length=length, core_frac=a.get("core_frac", 0.55))
+    elif shape == "isoforms":
+        per_gene, exons = int(a.get("per_gene", 4)), int(a.get("exons", 6))
+        builder, args = "isoforms", dict(genes=max(1, g // per_gene), exons=exons, per_gene=per_gene,
+                                         exon_len=(max(20, ln // (2 * exons)), max(21, (3 * ln) // (2 * exons))))
+    elif shape == "repeat":
+        period = int(a.get("period", 3))
+        builder, args = "repeat_block", dict(members=g, length=length, period=period,
+                                             block_len=max(period, int(ln * a.get("block_frac", 0.5))))
+    else:
+        raise ValueError(f"unknown shape {shape!r}")
+    return sr.generate(builder, args, c["n"], c["seed"], q=(c["qlo"], c["qhi"]), truncate=trunc)
 
 
 def draw_parity_params(rng):
@@ -61,9 +108,9 @@ def draw_parity_params(rng):
 
 
 def run_parity(ctx, c, merge=False):
-    """c: a dict as draw_parity makes it; its optional `params` (tests/helpers.param_pair keys) override the defaults on both
+    """c: a dict as draw_parity makes it (its reads: parity_reads); its optional `params` (tests/helpers.param_pair keys) override the defaults on both
     sides.  Returns (ok, detail)."""
-    rs = synth.generate(c["n"], c["g"], c["ln"], c["qlo"], c["qhi"], seed=c["seed"], dup_every=c["dup"], len_jitter=c["jit"])
+    rs = parity_reads(c)
     k, w, mode = c["k"], c["w"], c["mode"]
     pd = dict(c.get("params") or {}, k=k, w=w)
     ap, op = param_pair(pd, mode)

@@ -29,6 +29,34 @@ def oracle_entry_assignments(B, view, mode="fast"):
     return acl[view["orig"]], ast[view["orig"]], st
 
 
+def oracle_traced_run(rs, entries=None, k=11, w=15):
+    """One fast-mode run of the oracle over `rs` as a single batch with the candidate tables of `entries` (default: all)
+    traced.  Returns dict(batch, view, cls, strand, stats, rows, calls, entries)."""
+    B, view = oracle_sorted_batch(rs, k, w)
+    entries = list(range(rs.n)) if entries is None else list(entries)
+    po.trace_set(entries, mapped_calls=True)
+    try:
+        ocl, ost, ostat = oracle_entry_assignments(B, view)
+        rows, calls = po.trace_rows(), po.trace_mapped_calls()
+    finally:
+        po.trace_set(())
+    return dict(batch=B, view=view, cls=ocl, strand=ost, stats=ostat, rows=rows, calls=calls, entries=entries)
+
+
+def walk_lengths(rows, n, min_shared=5, min_fraction=0.8):
+    """Per entry the number of candidates getBestClusterMapping's walk can reach (src/cluster.cpp:355-406): those with
+    int(Size) >= int(top * MinFraction), 0 where top < MinShared or the entry has no candidate."""
+    out = np.zeros(n, np.int64)
+    order = np.argsort(rows["entry"], kind="stable")
+    ent, size = rows["entry"][order], rows["size"][order].astype(np.int64)
+    cuts = np.flatnonzero(np.diff(ent)) + 1
+    for e, sz in zip(ent[np.r_[0, cuts]] if len(ent) else [], np.split(size, cuts)):
+        top = int(sz.max())
+        if top >= min_shared:
+            out[e] = int((sz >= int(float(top) * min_fraction)).sum())
+    return out
+
+
 PARAM_KEYS = ("min_shared", "min_fraction", "mapped_threshold", "min_prob_no_hits", "aligned_threshold")
 
 
@@ -48,24 +76,33 @@ def param_pair(d=None, mode="fast"):
     return a, o
 
 
-def compare_candidate_tables(ctx, view, rows, calls, entries, tgt, thr=0.65, size_cut=0):
+def compare_candidate_tables(ctx, view, rows, calls, entries, tgt, thr=0.65, size_cut=0, cid=None, bound=None, size_rule=0,
+                             floor=None):
     """The device's candidate table of every traced entry (ctx.query_candidates) against the oracle's trace rows: the multiset of
     (cluster, strand, Size, first index), and every totalMapped either side evaluated.  thr: the MappedThreshold of the run (a
     candidate the upper bound rejected must fail it on the oracle's exact total).  size_cut: the Size below which the Size rule
     alone excludes a candidate whatever its total (int(MinShared * MinFraction), see ioc_set_params' `keep`), which the list
-    cut also marks rejected: allowed to pass the threshold, never walked by the oracle.  Returns (rows, walked,
-    device-evaluated)."""
+    cut also marks rejected: allowed to pass the threshold, never walked by the oracle.
+    cid: cluster id (in the oracle's numbering) of every device target, for runs with left clusters (default: a single batch,
+    L = 0, where target = the entry that opened the cluster).  bound(entry, target, strand, Size): an independent restatement of
+    the upper bound of totalMapped (tests/bound_common.MappedBound) — a candidate the device rejected must be rejected by it
+    too, unless the Size rule alone excludes it (Size < size_rule = int(MinShared * MinFraction)): a sound but over-tight
+    device bound fails here.  floor(entry, need): the restated per-query cut of the candidate lists (tests/bound_common.size_floor,
+    fast mode) — the converse for the cut: a candidate with size_rule <= Size < floor is exported as rejected, so a device cut that
+    is too slack fails here.  Returns (rows, walked, device-evaluated)."""
     from isonclust2_amd import api
     n = len(tgt)
     opener = tgt < 0
     # single batch, L = 0: target = entry that opened the cluster -> cluster id in creation order
-    cid = np.full(n, -1, np.int64)
-    gated = np.asarray(view["state"]) != 0
-    cid[opener & ~gated] = np.arange(int((opener & ~gated).sum()))
+    if cid is None:
+        cid = np.full(n, -1, np.int64)
+        gated = np.asarray(view["state"]) != 0
+        cid[opener & ~gated] = np.arange(int((opener & ~gated).sum()))
+    cid = np.asarray(cid, np.int64)
     n_rows = n_walked = n_dev_eval = n_bound = 0
     for e in entries:
         m = rows["entry"] == e
-        t, s, sz, fi, tm = ctx.query_candidates(int(e), 2 * n + 2)
+        t, s, sz, fi, tm = ctx.query_candidates(int(e), 2 * max(n, len(cid)) + 2)
         dev = sorted(zip(cid[t].tolist(), s.tolist(), sz.tolist(), fi.tolist()))
         orc = sorted(zip(rows["cls"][m].tolist(), rows["strand"][m].tolist(), rows["size"][m].tolist(),
                          rows["first_index"][m].tolist()))
@@ -74,8 +111,12 @@ def compare_candidate_tables(ctx, view, rows, calls, entries, tgt, thr=0.65, siz
         tot = {(c, st): (x, w) for c, st, x, w in zip(rows["cls"][m].tolist(), rows["strand"][m].tolist(),
                                                       rows["total_mapped"][m].tolist(), rows["walked"][m].tolist())}
         need = api.host_min_total(int(view["hpc_len"][e]), thr)
-        for c, st, x, z in zip(cid[t].tolist(), s.tolist(), tm.tolist(), sz.tolist()):
+        for c, st, x, z, tg in zip(cid[t].tolist(), s.tolist(), tm.tolist(), sz.tolist(), t.tolist()):
             want, walked = tot[(c, st)]
+            if bound is not None and x == 0xFFFFFFFE and z >= size_rule:
+                assert bound(int(e), tg, st, z) < need, (e, c, st, z, bound(int(e), tg, st, z), need)
+            if floor is not None and size_rule <= z < floor(int(e), need):
+                assert x == 0xFFFFFFFE, (e, c, st, z, floor(int(e), need), x)
             if x == 0xFFFFFFFE and z < size_cut and want >= need:
                 assert not walked, (e, c, st, z, size_cut)
                 n_bound += 1

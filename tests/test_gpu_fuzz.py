@@ -66,6 +66,12 @@ _PARITY_FIXED = [
     dict(n=259, g=23, ln=120, qlo=9.0, qhi=21.0, dup=3, jit=0.3, k=10, w=14, seed=202, mode="fast"),
     dict(n=150, g=6, ln=350, qlo=7.0, qhi=11.0, dup=2, jit=0.0, k=13, w=20, seed=303, mode="fast"),
     dict(n=1, g=1, ln=120, qlo=14.0, qhi=18.0, dup=0, jit=0.0, k=15, w=22, seed=404, mode="fast"),
+    # structured reads (fuzz_cases.parity_reads): a gene family that shares a core — walks of dozens of near-equal candidates —,
+    # and a shared tandem repeat — reads that repeat one minimizer value, one posting list hit by every query
+    dict(n=160, g=40, ln=600, qlo=10.0, qhi=21.0, dup=0, jit=0.0, k=11, w=15, seed=505, mode="fast", shape="family",
+         sargs=dict(core_frac=0.55, truncate=0.0)),
+    dict(n=120, g=10, ln=700, qlo=11.0, qhi=19.0, dup=0, jit=0.0, k=11, w=15, seed=606, mode="fast", shape="repeat",
+         sargs=dict(period=3, block_frac=0.5, truncate=0.4)),
 ]
 
 

@@ -5,7 +5,9 @@ tests/test_gpu_fuzz.py runs in bounded slices.
     tools/fuzz_parity.py [cases] [seed] [sahlin|furious]
     tools/fuzz_parity.py --case "{'n': 162, ...}"      replay one case (the reproducer a failing test prints); a case's
                                                      optional 'params' dict (min_shared, min_fraction, mapped_threshold,
-                                                     min_prob_no_hits, aligned_threshold) applies to both sides
+                                                     min_prob_no_hits, aligned_threshold) applies to both sides; its
+                                                     optional 'shape' ('random', 'family', 'isoforms', 'repeat') and
+                                                     'sargs' choose the read generator (none: 'random')
     tools/fuzz_parity.py [cases] [seed] params       draw the thresholds and (k, w) too (fuzz_cases.draw_parity_params)"""
 import ast
 import sys
