@@ -290,6 +290,26 @@ int ioc_host_align_ops(const char* query, int32_t qlen, const char* ref, int32_t
 /* Run-length text of an operation string ("12=1X3I...", end gaps as runs of i / d), NUL-terminated; returns its length,
  * IOC_ERR_CAPACITY if cap is too small (2 bytes per operation + 1 always suffice), IOC_ERR_ARG for a byte that is no operation. */
 int64_t ioc_host_ops_to_cigar(const char* ops, int64_t len, char* out, int64_t cap);
+/* What an operation string says about its alignment, in integers (parasail's _stats family gives matches, similar and length;
+ * this is that and the gaps).  The WALK is the part from the first to the last byte of "=XID"; the free end gaps lie before and
+ * behind it.  Leading bytes are the bytes before the first walk byte, trailing bytes the ones after the last; a string without a
+ * walk byte counts all its bytes as leading.  A run is maximal over ONE byte value: 'I' next to 'i' or to 'D' ends it. */
+typedef struct {
+    int32_t length;       /* all bytes of the operation string */
+    int32_t columns;      /* bytes in "=XID" */
+    int32_t matches;      /* '=' */
+    int32_t mismatches;   /* 'X' */
+    int32_t ins, del;     /* 'I' bytes, 'D' bytes */
+    int32_t ins_runs, del_runs;        /* maximal runs of 'I' / of 'D' */
+    int32_t longest_ins, longest_del;  /* longest such run, 0 if none */
+    int32_t lead_i, lead_d, trail_i, trail_d;  /* 'i' / 'd' among the leading / trailing bytes: the alignment takes the query's
+                                                * bases [lead_i, query length - trail_i) and the reference's [lead_d, reference
+                                                * length - trail_d) */
+    int32_t reserved[2];  /* written as 0 */
+} ioc_aln_stats;          /* 64 bytes */
+/* The definition of the statistics (the device's k_ops_stats is tested against it); runs on the CPU.  IOC_ERR_ARG for a byte
+ * that is no operation (as ioc_host_ops_to_cigar) or len >= 2^31; len == 0 gives all zeros. */
+int ioc_host_ops_stats(const char* ops, int64_t len, ioc_aln_stats* out);
 int32_t ioc_host_gap_open(double e1_plus_e2);                     /* setGapOpen,  src/cluster.cpp:425-440 */
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
@@ -329,6 +349,15 @@ int64_t ioc_align_ops_bound(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* p
 int ioc_align_pairs_ops(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
                         int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
                         double* out_ratio, char* out_ops, int64_t ops_cap, int64_t* ops_off);
+/* ioc_align_pairs + the statistics of the alignments (ioc_host_ops_stats of what ioc_align_pairs_ops would return for the same
+ * pairs, field by field), reduced ON THE DEVICE: the walks write their bytes as for ioc_align_pairs_ops, a kernel of its own
+ * (k_ops_stats) counts them there, and 64 bytes per pair come back in place of the bytes themselves.  An emitting call like
+ * ioc_align_pairs_ops: always exact, the verdict threshold not applied, IOC_ALIGN_VARIANT=carry not honoured, the device buffer
+ * of the bytes counted against the checkpoint arena's budget.  out_stats (n_pairs records, zeroed first) must not be NULL when
+ * n_pairs > 0; any of out_score / out_windows / out_ratio may be. */
+int ioc_align_pairs_stats(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
+                          int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
+                          double* out_ratio, ioc_aln_stats* out_stats);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

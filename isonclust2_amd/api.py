@@ -60,6 +60,21 @@ def ops_to_cigar(ops):
     return out.raw[:n].decode()
 
 
+# ioc_aln_stats as a numpy record (Context.align_pairs_stats returns an array of them)
+ALN_STATS_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.AlnStats._fields_[:-1]] + [("reserved", np.int32, (2,))])
+ALN_STATS_FIELDS = tuple(n for n, _ in _lib.AlnStats._fields_[:-1])
+
+
+def ops_stats(ops):
+    """ioc_host_ops_stats: what an operation string says about its alignment, as a dict — length, columns, matches, mismatches,
+    ins, del, ins_runs, del_runs, longest_ins, longest_del and the end gaps lead_i, lead_d, trail_i, trail_d."""
+    st = _lib.AlnStats()
+    rc = _lib.load().ioc_host_ops_stats(bytes(ops), len(ops), C.byref(st))
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_stats failed ({rc})")
+    return {n: int(getattr(st, n)) for n in ALN_STATS_FIELDS}
+
+
 def ops_to_comp(ops):
     """The comparison string of an operation string: '|' where the bases are equal, ' ' in every other column."""
     return bytes(ops).translate(bytes(0x7C if b == 0x3D else 0x20 for b in range(256)))
@@ -277,6 +292,18 @@ class Context:
         self._chk(self.L.ioc_align_pairs_ops(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
                                              _p(ratio, C.c_double), ops.ctypes.data, bound, _p(off, C.c_int64)))
         return score, win, ratio, [ops[off[i]:off[i + 1]].tobytes() for i in range(n)]
+
+    def align_pairs_stats(self, pairs, k, match=2, mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_stats: align_pairs plus the statistics of the alignments (ops_stats of what align_pairs_ops returns),
+        counted on the device — returns (score, windows, ratio, stats), stats a structured array (ALN_STATS_DTYPE).  Always exact
+        counts (the verdict threshold is not applied)."""
+        n = len(pairs)
+        arr = self._aln_pairs(pairs)
+        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        stats = np.zeros(n, ALN_STATS_DTYPE)
+        self._chk(self.L.ioc_align_pairs_stats(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
+                                               _p(ratio, C.c_double), stats.ctypes.data if n else None))
+        return score, win, ratio, stats
 
     # ---- sort-stage feeders --------------------------------------------------------------------
     def qual_scores(self, offs, qual, k):

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <future>
 #include <iostream>
 #include <map>
@@ -937,18 +938,139 @@ static int main_cluster(int argc, char** argv)
 // ===================================================================================================
 // dump  (src/main.cpp:204-236, 430-453; src/output.cpp:151-275)   and   info (src/main.cpp:384-399)
 // ===================================================================================================
+// dump --read-stats: <outdir>/read_stats.tsv, one row per row of clusters.tsv whose cluster has a record in cluster_cons.fq.  The
+// read as cluster_fastq/<id>.fq has it (reverse-complemented when its strand is -1) is aligned against the representative as
+// cluster_cons.fq has it, e = CalcErrorRate of the two quality lines as those files have them, k the batch's k-mer size, scores
+// 2 / -2 / extend 1 as the cluster drivers use — so the files `dump` writes determine the report.  The alignments are reduced to
+// their statistics on the device (ioc_align_pairs_stats), in groups of whole clusters whose sequence pool stays under 256 MB.
+struct ReadStatRow {
+    unsigned cls;
+    int strand;
+    const char* id;
+    size_t id_len;
+    const char* seq;
+    size_t seq_len;
+    const char* qual;
+    size_t qual_len;
+};
+static void write_read_stats(const Batch& b, const string& outdir, size_t n_rows, const std::function<ReadStatRow(size_t)>& row)
+{
+    constexpr size_t POOL_MAX = size_t(256) << 20;
+    const int k = b.SortArgs.KmerSize;
+    std::vector<std::vector<size_t>> rows_of(b.Cls.size());  // per cluster with a consensus record: its rows, in the order of clusters.tsv
+    std::vector<size_t> kept;
+    for (size_t x = 0; x < n_rows; ++x) {
+        const ReadStatRow r = row(x);
+        if (r.cls >= b.Cls.size() || b.Cls[r.cls]->at(0)->RawSeq->score < 0) continue;
+        rows_of[r.cls].push_back(kept.size());
+        kept.push_back(x);
+    }
+    struct Result {
+        int32_t score = 0;
+        int64_t windows = 0;
+        ioc_aln_stats st{};
+        size_t rep_len = 0;
+    };
+    std::vector<Result> res(kept.size());
+    ioc_ctx* c = kept.empty() ? nullptr : make_ctx();
+    auto comp = [](char ch) { return ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch; };
+
+    // one group: the clusters [c0, c1)
+    string pool, quals;
+    std::vector<int64_t> offs, qoffs;
+    std::vector<ioc_aln_pair> pairs;
+    std::vector<size_t> pair_row;
+    std::vector<int32_t> pair_q, pair_rep_q;  // per pair: the quality lines of its read and of its representative (indices into qoffs)
+    auto flush = [&]() {
+        if (pairs.empty()) return;
+        const size_t nq = qoffs.size() - 1, np = pairs.size();
+        std::vector<double> qs(nq), qe(nq);
+        check(c, ioc_qual_scores(c, int32_t(nq), qoffs.data(), reinterpret_cast<const uint8_t*>(quals.data()), k, qs.data(), qe.data()), "quality scores");
+        for (size_t x = 0; x < np; ++x) pairs[x].e = qe[size_t(pair_q[x])] + qe[size_t(pair_rep_q[x])];
+        check(c, ioc_align_set_pool(c, int32_t(offs.size() - 1), pool.data(), offs.data()), "sequence pool");
+        std::vector<int32_t> sc(np);
+        std::vector<int64_t> win(np);
+        std::vector<ioc_aln_stats> st(np);
+        check(c, ioc_align_pairs_stats(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, st.data()), "alignment statistics");
+        for (size_t x = 0; x < np; ++x) {
+            Result& r = res[pair_row[x]];
+            r.score = sc[x], r.windows = win[x], r.st = st[x];
+        }
+        pool.clear(), quals.clear(), offs.clear(), qoffs.clear(), pairs.clear(), pair_row.clear(), pair_q.clear(), pair_rep_q.clear();
+    };
+    for (size_t ci = 0; ci < b.Cls.size(); ++ci) {
+        if (rows_of[ci].empty()) continue;
+        const auto& rep = b.Cls[ci]->at(0);
+        size_t need = rep->RawSeq->seq.size();
+        for (size_t y : rows_of[ci]) need += row(kept[y]).seq_len;
+        if (!pairs.empty() && pool.size() + need > POOL_MAX) flush();
+        if (offs.empty()) offs.push_back(0), qoffs.push_back(0);
+        // the representative: its stored sequence (the pair asks for the reverse complement when its strand is -1), its quality
+        // line as cluster_cons.fq has it
+        const int32_t rep_seq = int32_t(offs.size() - 1), rep_q = int32_t(qoffs.size() - 1);
+        pool.append(rep->RawSeq->seq.data(), rep->RawSeq->seq.size());
+        offs.push_back(int64_t(pool.size()));
+        quals.append(rep->RawSeq->qual.data(), rep->RawSeq->qual.size());
+        qoffs.push_back(int64_t(quals.size()));
+        for (size_t y : rows_of[ci]) {
+            const ReadStatRow r = row(kept[y]);
+            const int32_t q_seq = int32_t(offs.size() - 1), q_q = int32_t(qoffs.size() - 1);
+            if (r.strand == -1) {
+                for (size_t t = r.seq_len; t > 0; --t) pool += comp(r.seq[t - 1]);
+                for (size_t t = r.qual_len; t > 0; --t) quals += r.qual[t - 1];
+            } else {
+                pool.append(r.seq, r.seq_len);
+                quals.append(r.qual, r.qual_len);
+            }
+            offs.push_back(int64_t(pool.size()));
+            qoffs.push_back(int64_t(quals.size()));
+            pairs.push_back(ioc_aln_pair{q_seq, rep_seq, rep->MatchStrand == -1 ? 1 : 0, 0 /* no hint */, 0.0 /* flush() */});
+            pair_row.push_back(y);
+            pair_q.push_back(q_q);
+            pair_rep_q.push_back(rep_q);
+            res[y].rep_len = rep->RawSeq->seq.size();
+        }
+    }
+    flush();
+    if (c) ioc_ctx_destroy(c);
+
+    std::ofstream out;
+    create_file(outdir + "/read_stats.tsv", out);
+    out << "ClusterId\tStrand\tRead\tReadLen\tRepLen\tScore\tWindows\tColumns\tMatches\tMismatches\tIns\tDel\tInsRuns\tDelRuns\tLongestIns\tLongestDel\t"
+           "ReadStart\tReadEnd\tRepStart\tRepEnd\tIdentity\n";
+    for (size_t y = 0; y < kept.size(); ++y) {
+        const ReadStatRow r = row(kept[y]);
+        const Result& a = res[y];
+        const ioc_aln_stats& s = a.st;
+        char ident[32];
+        snprintf(ident, sizeof ident, "%.6f", s.columns > 0 ? double(s.matches) / double(s.columns) : 0.0);
+        out << r.cls << '\t' << r.strand << '\t';
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << r.seq_len << '\t' << a.rep_len << '\t' << a.score << '\t' << a.windows << '\t' << s.columns << '\t' << s.matches << '\t' << s.mismatches
+            << '\t' << s.ins << '\t' << s.del << '\t' << s.ins_runs << '\t' << s.del_runs << '\t' << s.longest_ins << '\t' << s.longest_del << '\t' << s.lead_i
+            << '\t' << int64_t(r.seq_len) - s.trail_i << '\t' << s.lead_d << '\t' << int64_t(a.rep_len) - s.trail_d << '\t' << ident << '\n';
+    }
+}
+
 static int main_dump(int argc, char** argv)
 {
     static const struct option lo[] = {{"verbose", no_argument, 0, 'v'}, {"debug", no_argument, 0, 'd'}, {"help", no_argument, 0, 'h'},
-                                       {"outdir", required_argument, 0, 'o'}, {"index", required_argument, 0, 'i'}, {0, 0, 0, 0}};
+                                       {"outdir", required_argument, 0, 'o'}, {"index", required_argument, 0, 'i'},
+                                       {"read-stats", no_argument, 0, 1000}, {0, 0, 0, 0}};
     string outdir, index;
+    bool read_stats = false;  // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
     int o;
     while ((o = getopt_long(argc, argv, "dhvo:i:", lo, nullptr)) != -1) {
         switch (o) {
             case 'o': outdir = optarg; break;
             case 'i': index = optarg; break;
             case 'v': VERBOSE = true; break;
-            case 'h': cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir final.cer" << endl; exit(0);
+            case 1000: read_stats = true; break;
+            case 'h':
+                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] final.cer" << endl
+                     << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
+                     << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl;
+                exit(0);
             default: break;
         }
     }
@@ -1042,6 +1164,12 @@ static int main_dump(int argc, char** argv)
         bool whole;     // the record ends with its newline: it can go out as it lies
     };
     std::unordered_map<unsigned, std::vector<Piece>> per_cluster;
+    struct StatRow {  // (--read-stats) a row of clusters.tsv: the read's sequence and quality lines in the mapping
+        unsigned cls;
+        int strand;
+        const char *hb, *he, *sb, *se, *qb, *qe;
+    };
+    std::vector<StatRow> stat_rows;
     {
         const char* p = fqmap.data;
         const char* const e = fqmap.data + fqmap.size;
@@ -1061,6 +1189,7 @@ static int main_dump(int argc, char** argv)
             if (it == id2cls.end()) continue;
             tsv << it->second.cls << "\t" << it->second.strand << "\t" << id << "\n";
             per_cluster[it->second.cls].push_back(Piece{hb, sb, pb, qb, qe, it->second.strand == -1, p == qe + 1});
+            if (read_stats) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
         }
     }
     lap("sorted fastq walked, clusters.tsv");
@@ -1114,6 +1243,13 @@ static int main_dump(int argc, char** argv)
         if (failed) die("Failed to write the cluster FASTQ files!");
     }
     lap("cluster fastq files written");
+    if (read_stats) {
+        write_read_stats(b, outdir, stat_rows.size(), [&](size_t x) {
+            const StatRow& r = stat_rows[x];
+            return ReadStatRow{r.cls, r.strand, r.hb, size_t(r.he - r.hb), r.sb, size_t(r.se - r.sb), r.qb, size_t(r.qe - r.qb)};
+        });
+        lap("read_stats.tsv (GPU alignments)");
+    }
     if (VERBOSE) cerr << "Dump complete." << endl;
     return 0;
 }

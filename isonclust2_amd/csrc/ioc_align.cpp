@@ -179,6 +179,41 @@ int64_t ioc_host_ops_to_cigar(const char* ops, int64_t len, char* out, int64_t c
     return w;
 }
 
+// The statistics of an operation string: counts per byte, the maximal runs of 'I' and of 'D', and the end gaps on either side of
+// the walk (the bytes from the first to the last of "=XID").  The definition the device's reduction (k_ops_stats) is tested against.
+int ioc_host_ops_stats(const char* ops, int64_t len, ioc_aln_stats* out)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || !out) return IOC_ERR_ARG;
+    ioc_aln_stats s{};
+    int64_t first = len, last = -1;  // the walk's first and last byte
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        if (op == 'i' || op == 'd') continue;
+        if (first == len) first = a;
+        last = a;
+    }
+    s.length = int32_t(len);
+    for (int64_t a = 0; a < len;) {
+        const char op = ops[a];
+        int64_t b = a;
+        while (b < len && ops[b] == op) ++b;
+        const int32_t run = int32_t(b - a);
+        switch (op) {
+        case '=': s.matches += run; break;
+        case 'X': s.mismatches += run; break;
+        case 'I': s.ins += run, s.ins_runs += 1, s.longest_ins = std::max(s.longest_ins, run); break;
+        case 'D': s.del += run, s.del_runs += 1, s.longest_del = std::max(s.longest_del, run); break;
+        case 'i': a < first ? s.lead_i += run : a > last ? s.trail_i += run : 0; break;
+        default: a < first ? s.lead_d += run : a > last ? s.trail_d += run : 0; break;  // ('d')
+        }
+        a = b;
+    }
+    s.columns = s.matches + s.mismatches + s.ins + s.del;
+    *out = s;
+    return IOC_OK;
+}
+
 // setGapOpen, src/cluster.cpp:425-440
 int32_t ioc_host_gap_open(double e)
 {

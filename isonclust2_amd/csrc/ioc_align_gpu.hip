@@ -1139,6 +1139,11 @@ struct AlnOpsHost {
     int64_t* len;
     double* ms_copy;  // what the copies from the device took the host, and ...
     int64_t* copied;  // ... how many bytes they were (IOC_TRACE)
+    // ioc_align_pairs_stats: the sink is statistics — pair i's record goes to stats[i], the bytes stay on the device (buf and base
+    // are null), len[i] is still the length written
+    ioc_aln_stats* stats = nullptr;
+    double* ms_kernel = nullptr;  // k_ops_stats' device time, and ...
+    int64_t* records = nullptr;   // ... how many records came back (IOC_TRACE)
 };
 
 // One run's side (version 2's, version 1's).  The pairs of a slice get consecutive regions of ONE device buffer, as large as the
@@ -1151,24 +1156,69 @@ struct OpsRun {
     AlnOpsDev dev{};
     std::vector<uint8_t> stage;
     std::vector<uint32_t> len;
+    std::vector<uint32_t> room;        // (statistics) per device pair: query length + reference length ...
+    const uint32_t* d_room = nullptr;  // ... and where that table is on the device
+    std::vector<ioc_aln_stats> recs;   // (statistics) a slice's records, in the slice's order
 };
 
-// the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled)
-int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes)
+// the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled).  A statistics call:
+// [end][len][room per pair][the bytes][4 spare bytes: k_ops_stats reads the dword that holds a string's last byte whole].
+int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vector<AlnPairDev>& dp)
 {
-    const size_t np = o.end.size(), tab = (np * 12 + 15) & ~size_t(15);
-    const int r = ioc_reserve(c, c->a_ops, tab + size_t(max_slice_bytes));
+    const bool st = o.host->stats != nullptr;
+    const size_t np = o.end.size(), tab = (np * (st ? 16 : 12) + 15) & ~size_t(15);
+    const int r = ioc_reserve(c, c->a_ops, tab + size_t(max_slice_bytes) + (st ? 4 : 0));
     if (r != IOC_OK) return r;
     uint8_t* p = static_cast<uint8_t*>(c->a_ops.p);
     o.dev = AlnOpsDev{p + tab, reinterpret_cast<const uint64_t*>(p), reinterpret_cast<uint32_t*>(p + np * 8)};
     IOC_CHK(c, hipMemcpyAsync(p, o.end.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+    if (st) {
+        o.room.resize(np);
+        for (size_t x = 0; x < np; ++x) o.room[x] = dp[x].n + dp[x].m;
+        o.d_room = reinterpret_cast<const uint32_t*>(p + np * 12);
+        IOC_CHK(c, hipMemcpyAsync(p + np * 12, o.room.data(), np * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    return IOC_OK;
+}
+
+// a slice's sink in a statistics call (ioc_align_pairs_stats): k_ops_stats over the slice's pairs where their bytes lie; the
+// lengths and the 64-byte records come back, the bytes do not.  The same pairs are skipped as in ops_fetch.
+int ops_fetch_stats(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, const uint32_t* d_ord, uint32_t cnt)
+{
+    int r;
+    if ((r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
+    EventSet ev;
+    ev.v.assign(2, nullptr);
+    for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
+    IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
+    IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
+    IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    o.len.resize(dp.size());
+    o.recs.resize(cnt);
+    IOC_CHK(c, hipMemcpy(o.len.data(), o.dev.len, dp.size() * 4, hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(o.recs.data(), c->a_ostats.p, size_t(cnt) * sizeof(ioc_aln_stats), hipMemcpyDeviceToHost));
+    for (uint32_t x = 0; x < cnt; ++x) {
+        const uint32_t pid = ord[x], i = o.back[pid];
+        const uint64_t L = o.len[pid];
+        if (L == 0 || L > uint64_t(dp[pid].n) + dp[pid].m || L > o.end[pid]) continue;
+        o.host->stats[i] = o.recs[x];
+        o.host->len[i] = int64_t(L);
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) *o.host->ms_kernel += double(ms);
+    *o.host->ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *o.host->copied += int64_t(dp.size() * 4 + size_t(cnt) * sizeof(ioc_aln_stats));
+    *o.host->records += int64_t(cnt);
     return IOC_OK;
 }
 
 // after a slice: its pairs' bytes to the caller's regions.  A pair that came back without an answer (len 0: refused by the 16-bit
 // window or by the corridor's certificate; out of range: the walk of a forward pass that was given up) is left to its re-run.
-int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, uint32_t cnt, uint64_t bytes)
+int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, const uint32_t* d_ord, uint32_t cnt, uint64_t bytes)
 {
+    if (o.host->stats) return ops_fetch_stats(c, o, dp, ord, d_ord, cnt);
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
@@ -1836,7 +1886,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
             for (uint32_t x = x0; x < x1; ++x) ops->end[order[x]] = slice_ops[si] += uint64_t(dp[order[x]].n) + dp[order[x]].m;
             most = std::max(most, slice_ops[si]);
         }
-        if ((r = ops_reserve(c, *ops, most)) != IOC_OK) return r;
+        if ((r = ops_reserve(c, *ops, most, dp)) != IOC_OK) return r;
     }
     const auto t_res0 = std::chrono::steady_clock::now();
     IOC_TRY(ioc_reserve(c, c->a_ck, size_t(pl.arena_words) * 4));
@@ -1876,7 +1926,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
         if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe, ops ? &ops->dev : nullptr)) != IOC_OK) return r;
         if (ops && !xe) {
             const uint32_t x0 = 2u * pl.slices[si].first, x1 = std::min(cnt, 2u * (pl.slices[si].first + pl.slices[si].second));
-            if ((r = ops_fetch(c, *ops, dp, order + x0, x1 - x0, slice_ops[si])) != IOC_OK) return r;
+            if ((r = ops_fetch(c, *ops, dp, order + x0, d_order + x0, x1 - x0, slice_ops[si])) != IOC_OK) return r;
         }
         if ((r = v2_report(c, dp, order, pl, t, si, o.deadline)) != IOC_OK) return r;
         bad = xe != 0;
@@ -1938,7 +1988,13 @@ int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const 
             const int64_t len = n + m;
             const int64_t cnt = (il <= 0 && len > k) ? len - k : 0;
             out.set(size_t(i), 0, cnt, n == 0 ? 0.0 : double(cnt) / double(n));
-            if (out.ops) {  // (all of it one free end gap)
+            if (out.ops && out.ops->stats) {  // (all of it one free end gap, and no walk: leading)
+                ioc_aln_stats& s = out.ops->stats[i];
+                s = ioc_aln_stats{};
+                s.length = int32_t(len);
+                (n ? s.lead_i : s.lead_d) = int32_t(len);
+                out.ops->len[i] = len;
+            } else if (out.ops) {  // (all of it one free end gap)
                 memset(out.ops->buf + out.ops->base[i], n ? 'i' : 'd', size_t(len));
                 out.ops->len[i] = len;
             }
@@ -2340,7 +2396,7 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
     OpsRun ops{oh, b.back.data()};
     if (oh) {
         ops.end.swap(pl.ops_end);
-        if ((r = ops_reserve(c, ops, pl.ops_most)) != IOC_OK) return r;
+        if ((r = ops_reserve(c, ops, pl.ops_most, b.dp)) != IOC_OK) return r;
     }
     const auto t_res0 = std::chrono::steady_clock::now();
     IOC_TRY(ioc_reserve(c, c->a_ck, size_t(pl.arena) * 8));
@@ -2360,7 +2416,9 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
     for (auto& e : evs.v) IOC_CHK(c, hipEventCreate(&e));
     for (size_t si = 0; si < pl.slices.size(); ++si) {
         if ((r = v1_slice(c, b, pl.slices[si], wp, P, n_cu, lrow_stride, d_score, d_count, &evs.v[3 * si], oh ? &ops.dev : nullptr)) != IOC_OK) return r;
-        if (oh && (r = ops_fetch(c, ops, b.dp, b.order.data() + pl.slices[si].first, pl.slices[si].second, pl.slice_ops[si])) != IOC_OK) return r;
+        if (oh && (r = ops_fetch(c, ops, b.dp, b.order.data() + pl.slices[si].first, static_cast<const uint32_t*>(c->a_order.p) + pl.slices[si].first,
+                                  pl.slices[si].second, pl.slice_ops[si])) != IOC_OK)
+            return r;
     }
     IOC_CHK(c, hipStreamSynchronize(s));
     add_elapsed(c, evs.v, evs.v.size());
@@ -2424,7 +2482,12 @@ int align_again(ioc_ctx* c, const ioc_aln_pair* pairs, const std::vector<int32_t
     // (emitting call: the re-run writes straight into the regions of the caller's pairs — the bytes of the run that counted)
     std::vector<int64_t> sbase, slen(out.ops ? idx.size() : 0, 0);
     AlnOpsHost soh{};
-    if (out.ops) {
+    std::vector<ioc_aln_stats> sstats(out.ops && out.ops->stats ? idx.size() : 0, ioc_aln_stats{});
+    if (out.ops && out.ops->stats) {  // (statistics call: the re-run's records, scattered below)
+        soh = *out.ops;
+        soh.len = slen.data();
+        soh.stats = sstats.data();
+    } else if (out.ops) {
         for (int32_t i : idx) sbase.push_back(out.ops->base[i]);
         soh = AlnOpsHost{out.ops->buf, sbase.data(), slen.data(), out.ops->ms_copy, out.ops->copied};
     }
@@ -2434,6 +2497,7 @@ int align_again(ioc_ctx* c, const ioc_aln_pair* pairs, const std::vector<int32_t
     for (size_t x = 0; x < idx.size(); ++x) {
         out.set(size_t(idx[x]), sc[x], sw[x], sr[x]);
         if (out.ops) out.ops->len[idx[x]] = slen[x];
+        if (out.ops && out.ops->stats) out.ops->stats[idx[x]] = sstats[x];
     }
     return IOC_OK;
 }
@@ -2606,6 +2670,28 @@ int ioc_align_pairs_ops(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, 
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: operation bytes: %.1f MB copied from the device in %.3f ms, %.1f MB packed\n", double(copied) * 1e-6, ms_copy,
                 double(ops_off[n_pairs]) * 1e-6);
+    return IOC_OK;
+}
+
+// The walks write a slice's bytes as for ioc_align_pairs_ops; k_ops_stats (ioc_ops_stats.hip) reduces them where they lie, and
+// the records of the run that counted — the call's own, a re-run's — end up in out_stats.
+int ioc_align_pairs_stats(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                          int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats)
+{
+    if (!c || n_pairs < 0 || (n_pairs > 0 && (!pairs || !out_stats))) return IOC_ERR_ARG;
+    for (int32_t i = 0; i < n_pairs; ++i) out_stats[i] = ioc_aln_stats{};
+    std::vector<int64_t> len(size_t(n_pairs), 0);
+    double ms_copy = 0, ms_kernel = 0;
+    int64_t copied = 0, records = 0;
+    AlnOpsHost oh{nullptr, nullptr, len.data(), &ms_copy, &copied};
+    oh.stats = out_stats;
+    oh.ms_kernel = &ms_kernel;
+    oh.records = &records;
+    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, &oh}, AlnRoute::normal);
+    if (r != IOC_OK) return r;
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: alignment statistics: %lld records (%.3f MB with the lengths) copied from the device in %.3f ms, k_ops_stats %.3f ms\n",
+                (long long)records, double(copied) * 1e-6, ms_copy, ms_kernel);
     return IOC_OK;
 }
 

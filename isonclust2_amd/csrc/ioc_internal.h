@@ -205,6 +205,7 @@ struct ioc_ctx {
 
     // ---- GPU alignment fallback (ioc_align_gpu.hip) ----
     DevBuf a_pool, a_pairs, a_order, a_out, a_bnd, a_lrow, a_ck, a_cko, a_ends, a_ends2, a_xflags, a_prof, a_ops;
+    DevBuf a_ostats;  // ioc_align_pairs_stats: the records of a slice (k_ops_stats)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
     hipStream_t side_stream = nullptr;  // the aligner's helper launch for the wrong candidates, beside the first traceback launch
@@ -301,6 +302,12 @@ struct IocCandTable {
     std::vector<uint32_t> sz, fi, tm;
 };
 int ioc_query_candidates_many(ioc_ctx* c, const std::vector<int>& qs, std::vector<IocCandTable>& out);
+
+// ioc_ops_stats.hip: the statistics (ioc_host_ops_stats) of the operation strings an emitting slice of the aligner left on the
+// device — pair ord[x]'s string is buf[end[pid] - len[pid] .. end[pid]), its record out[x]; a pair with len == 0, len > room or
+// len > end is skipped
+hipError_t iock_ops_stats(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room,
+                          const uint32_t* ord, uint32_t cnt, ioc_aln_stats* out);
 
 // ioc_capi.cpp: queries whose minimizer arrays are already in HBM (ioc_batch_view::minimizers_on_device)
 extern "C" int ioc_queries_upload_devmins(ioc_ctx* c, int32_t n, const int64_t* off_fwd, const int64_t* off_rev, const uint32_t* d_min_val,
