@@ -310,6 +310,22 @@ typedef struct {
 /* The definition of the statistics (the device's k_ops_stats is tested against it); runs on the CPU.  IOC_ERR_ARG for a byte
  * that is no operation (as ioc_host_ops_to_cigar) or len >= 2^31; len == 0 gives all zeros. */
 int ioc_host_ops_stats(const char* ops, int64_t len, ioc_aln_stats* out);
+/* One row of a pileup: what the reads of a cluster say at one position of their reference.  A reference of length R owns R + 1
+ * consecutive rows; row p is reference position p IN THE FRAME OF THE OPERATION STRING (the reverse complement of the stored
+ * sequence where the pair sets ref_revcomp; the query is never complemented).  Walk a string with r = reference bases and
+ * q = query bases consumed so far: 'd' r++; 'i' q++; '=' / 'X' add 1 to row r in the channel of query[q] (a, c, g, t; `other`
+ * for any other byte), r++, q++; 'D' del of row r += 1, r++; 'I' ins_bases of row r += 1, and ins_runs of row r += 1 where
+ * the byte before it is not 'I', q++.  So insertions belong to the position they stand in front of, row R holds insertion
+ * counts only, and a + c + g + t + other + del is a row's depth. */
+typedef struct {
+    uint32_t a, c, g, t, other;
+    uint32_t del;
+    uint32_t ins_runs, ins_bases;
+} ioc_pileup_col;         /* 32 bytes */
+/* The definition of the pileup (the device's k_ops_pileup is tested against it); runs on the CPU.  ADDS the string's counts to
+ * cols[0 .. rlen].  IOC_ERR_ARG, with cols untouched, for a byte that is no operation, for a string that does not consume
+ * exactly qlen query bases and rlen reference bases, and for len >= 2^31. */
+int ioc_host_ops_pileup(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, ioc_pileup_col* cols);
 int32_t ioc_host_gap_open(double e1_plus_e2);                     /* setGapOpen,  src/cluster.cpp:425-440 */
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
@@ -358,6 +374,19 @@ int ioc_align_pairs_ops(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs
 int ioc_align_pairs_stats(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
                           int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
                           double* out_ratio, ioc_aln_stats* out_stats);
+/* ioc_align_pairs + the pileup of the alignments on their references, reduced ON THE DEVICE (k_ops_pileup): pair i adds what
+ * ioc_host_ops_pileup makes of its operation string and its query into rows row_base[i] .. row_base[i] + reference length of
+ * out_cols (n_rows records, zeroed first).  Pairs that share a row_base are piled together; they must then have references of
+ * one length, taken in one frame — the caller's business.  Every pair adds exactly once, whichever run answered it.
+ * IOC_ERR_ARG, with nothing written, for row_base[i] < 0, row_base[i] + reference length + 1 > n_rows, n_rows < 0, and a NULL
+ * row_base or out_cols with n_pairs > 0.  out_stats != NULL: the records of ioc_align_pairs_stats as well, from the same
+ * alignments.  An emitting call like ioc_align_pairs_stats: always exact, the verdict threshold not applied,
+ * IOC_ALIGN_VARIANT=carry not honoured; the device table (32 bytes per row) and the operation bytes count against the
+ * checkpoint arena's budget.  Any of out_score / out_windows / out_ratio may be NULL. */
+int ioc_align_pairs_pileup(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
+                           int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
+                           double* out_ratio, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows,
+                           ioc_pileup_col* out_cols);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

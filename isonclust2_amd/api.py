@@ -75,6 +75,26 @@ def ops_stats(ops):
     return {n: int(getattr(st, n)) for n in ALN_STATS_FIELDS}
 
 
+# ioc_pileup_col as a numpy record (ops_pileup and Context.align_pairs_pileup return arrays of them, one per row)
+PILEUP_DTYPE = np.dtype([(n, np.uint32) for n, _ in _lib.PileupCol._fields_])
+PILEUP_FIELDS = PILEUP_DTYPE.names
+
+
+def ops_pileup(ops, query, rlen, cols=None):
+    """ioc_host_ops_pileup: the pileup of one operation string and its query on a reference of rlen bases — rlen + 1 rows
+    (PILEUP_DTYPE), row p what the query says at reference position p, insertions at the position they stand in front of.  ADDED
+    to `cols` where given (a contiguous array of rlen + 1 rows, returned), else to a fresh table of zeros.  ValueError, with
+    cols untouched, for a byte that is no operation or a string that does not consume exactly len(query) and rlen bases."""
+    if cols is None:
+        cols = np.zeros(rlen + 1, PILEUP_DTYPE)
+    if cols.dtype != PILEUP_DTYPE or cols.shape != (rlen + 1,) or not cols.flags["C_CONTIGUOUS"]:
+        raise ValueError("cols must be a contiguous array of rlen + 1 rows of PILEUP_DTYPE")
+    rc = _lib.load().ioc_host_ops_pileup(bytes(ops), len(ops), bytes(query), len(query), int(rlen), cols.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_pileup failed ({rc})")
+    return cols
+
+
 def ops_to_comp(ops):
     """The comparison string of an operation string: '|' where the bases are equal, ' ' in every other column."""
     return bytes(ops).translate(bytes(0x7C if b == 0x3D else 0x20 for b in range(256)))
@@ -304,6 +324,24 @@ class Context:
         self._chk(self.L.ioc_align_pairs_stats(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
                                                _p(ratio, C.c_double), stats.ctypes.data if n else None))
         return score, win, ratio, stats
+
+    def align_pairs_pileup(self, pairs, k, row_base, n_rows, stats=False, match=2, mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_pileup: align_pairs plus the pileup of the alignments on their references, added up on the device —
+        pair i adds ops_pileup of its alignment into rows row_base[i] .. row_base[i] + len(reference) of a table of n_rows rows
+        (PILEUP_DTYPE); pairs with one row_base are piled together.  Returns (score, windows, ratio, cols), with stats=True
+        (score, windows, ratio, cols, stats) — the records of align_pairs_stats from the same alignments.  Always exact counts."""
+        n = len(pairs)
+        arr = self._aln_pairs(pairs)
+        row_base = np.ascontiguousarray(row_base, np.int64)
+        if row_base.shape != (n,):
+            raise ValueError("row_base must hold one entry per pair")
+        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        cols = np.zeros(max(int(n_rows), 0), PILEUP_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        self._chk(self.L.ioc_align_pairs_pileup(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
+                                                _p(ratio, C.c_double), st.ctypes.data if stats and n else None, _p(row_base, C.c_int64),
+                                                int(n_rows), cols.ctypes.data))
+        return (score, win, ratio, cols, st) if stats else (score, win, ratio, cols)
 
     # ---- sort-stage feeders --------------------------------------------------------------------
     def qual_scores(self, offs, qual, k):

@@ -943,6 +943,12 @@ static int main_cluster(int argc, char** argv)
 // cluster_cons.fq has it, e = CalcErrorRate of the two quality lines as those files have them, k the batch's k-mer size, scores
 // 2 / -2 / extend 1 as the cluster drivers use — so the files `dump` writes determine the report.  The alignments are reduced to
 // their statistics on the device (ioc_align_pairs_stats), in groups of whole clusters whose sequence pool stays under 256 MB.
+//
+// dump --pileup: <outdir>/cluster_pileup.tsv from the same pairs in the same groups, piled on the device onto their cluster's
+// representative (ioc_align_pairs_pileup): for every cluster with a record in cluster_cons.fq, in cluster order, one row per
+// position of the representative as that file has it — how many reads cover the base, what they say there, how many have an
+// insertion in front of it — and a last row (RepBase '-') for the insertions behind the last base.  With both options a group
+// is aligned once: the pileup call returns the statistics of the same alignments.
 struct ReadStatRow {
     unsigned cls;
     int strand;
@@ -953,7 +959,8 @@ struct ReadStatRow {
     const char* qual;
     size_t qual_len;
 };
-static void write_read_stats(const Batch& b, const string& outdir, size_t n_rows, const std::function<ReadStatRow(size_t)>& row)
+static void write_read_reports(const Batch& b, const string& outdir, size_t n_rows, const std::function<ReadStatRow(size_t)>& row, bool want_stats,
+                               bool want_pileup)
 {
     constexpr size_t POOL_MAX = size_t(256) << 20;
     const int k = b.SortArgs.KmerSize;
@@ -981,8 +988,44 @@ static void write_read_stats(const Batch& b, const string& outdir, size_t n_rows
     std::vector<ioc_aln_pair> pairs;
     std::vector<size_t> pair_row;
     std::vector<int32_t> pair_q, pair_rep_q;  // per pair: the quality lines of its read and of its representative (indices into qoffs)
+    // (--pileup) the group's clusters in cluster order with the first of their rows in the group's table (-1: a cluster without a
+    // row of clusters.tsv, all zeros), and per pair its cluster's first row
+    std::vector<std::pair<size_t, int64_t>> group_cls;
+    std::vector<int64_t> row_base;
+    std::vector<ioc_pileup_col> cols;
+    int64_t group_rows = 0;
+    std::ofstream pile_out;
+    if (want_pileup) {
+        create_file(outdir + "/cluster_pileup.tsv", pile_out);
+        pile_out << "ClusterId\tPos\tRepBase\tDepth\tA\tC\tG\tT\tN\tDel\tInsReads\tInsBases\n";
+    }
+    auto write_pileup = [&]() {
+        string text;
+        for (const auto& gc : group_cls) {
+            const auto& rep = b.Cls[gc.first]->at(0);
+            string frame = rep->RawSeq->seq.str();  // (as cluster_cons.fq has it)
+            if (rep->MatchStrand == -1) {
+                std::reverse(frame.begin(), frame.end());
+                for (char& ch : frame) ch = comp(ch);
+            }
+            text.clear();
+            for (size_t p = 0; p <= frame.size(); ++p) {
+                const ioc_pileup_col z = gc.second < 0 ? ioc_pileup_col{} : cols[size_t(gc.second) + p];
+                text += std::to_string(gc.first) + '\t' + std::to_string(p) + '\t' + (p < frame.size() ? frame[p] : '-') + '\t' +
+                        std::to_string(uint64_t(z.a) + z.c + z.g + z.t + z.other + z.del) + '\t' + std::to_string(z.a) + '\t' + std::to_string(z.c) + '\t' +
+                        std::to_string(z.g) + '\t' + std::to_string(z.t) + '\t' + std::to_string(z.other) + '\t' + std::to_string(z.del) + '\t' +
+                        std::to_string(z.ins_runs) + '\t' + std::to_string(z.ins_bases) + '\n';
+            }
+            pile_out.write(text.data(), std::streamsize(text.size()));
+        }
+        group_cls.clear(), row_base.clear(), cols.clear();
+        group_rows = 0;
+    };
     auto flush = [&]() {
-        if (pairs.empty()) return;
+        if (pairs.empty()) {
+            if (want_pileup) write_pileup();
+            return;
+        }
         const size_t nq = qoffs.size() - 1, np = pairs.size();
         std::vector<double> qs(nq), qe(nq);
         check(c, ioc_qual_scores(c, int32_t(nq), qoffs.data(), reinterpret_cast<const uint8_t*>(quals.data()), k, qs.data(), qe.data()), "quality scores");
@@ -990,16 +1033,27 @@ static void write_read_stats(const Batch& b, const string& outdir, size_t n_rows
         check(c, ioc_align_set_pool(c, int32_t(offs.size() - 1), pool.data(), offs.data()), "sequence pool");
         std::vector<int32_t> sc(np);
         std::vector<int64_t> win(np);
-        std::vector<ioc_aln_stats> st(np);
-        check(c, ioc_align_pairs_stats(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, st.data()), "alignment statistics");
-        for (size_t x = 0; x < np; ++x) {
+        std::vector<ioc_aln_stats> st(want_stats ? np : 0);
+        if (want_pileup) {
+            cols.assign(size_t(group_rows), ioc_pileup_col{});
+            check(c, ioc_align_pairs_pileup(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
+                                            row_base.data(), group_rows, cols.data()),
+                  "alignment pileup");
+            write_pileup();
+        } else {
+            check(c, ioc_align_pairs_stats(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, st.data()), "alignment statistics");
+        }
+        for (size_t x = 0; x < np && want_stats; ++x) {
             Result& r = res[pair_row[x]];
             r.score = sc[x], r.windows = win[x], r.st = st[x];
         }
         pool.clear(), quals.clear(), offs.clear(), qoffs.clear(), pairs.clear(), pair_row.clear(), pair_q.clear(), pair_rep_q.clear();
     };
     for (size_t ci = 0; ci < b.Cls.size(); ++ci) {
-        if (rows_of[ci].empty()) continue;
+        if (rows_of[ci].empty()) {
+            if (want_pileup && b.Cls[ci]->at(0)->RawSeq->score >= 0) group_cls.emplace_back(ci, int64_t(-1));
+            continue;
+        }
         const auto& rep = b.Cls[ci]->at(0);
         size_t need = rep->RawSeq->seq.size();
         for (size_t y : rows_of[ci]) need += row(kept[y]).seq_len;
@@ -1012,6 +1066,11 @@ static void write_read_stats(const Batch& b, const string& outdir, size_t n_rows
         offs.push_back(int64_t(pool.size()));
         quals.append(rep->RawSeq->qual.data(), rep->RawSeq->qual.size());
         qoffs.push_back(int64_t(quals.size()));
+        if (want_pileup) {
+            group_cls.emplace_back(ci, group_rows);
+            row_base.insert(row_base.end(), rows_of[ci].size(), group_rows);
+            group_rows += int64_t(rep->RawSeq->seq.size()) + 1;
+        }
         for (size_t y : rows_of[ci]) {
             const ReadStatRow r = row(kept[y]);
             const int32_t q_seq = int32_t(offs.size() - 1), q_q = int32_t(qoffs.size() - 1);
@@ -1033,6 +1092,7 @@ static void write_read_stats(const Batch& b, const string& outdir, size_t n_rows
     }
     flush();
     if (c) ioc_ctx_destroy(c);
+    if (!want_stats) return;
 
     std::ofstream out;
     create_file(outdir + "/read_stats.tsv", out);
@@ -1056,9 +1116,10 @@ static int main_dump(int argc, char** argv)
 {
     static const struct option lo[] = {{"verbose", no_argument, 0, 'v'}, {"debug", no_argument, 0, 'd'}, {"help", no_argument, 0, 'h'},
                                        {"outdir", required_argument, 0, 'o'}, {"index", required_argument, 0, 'i'},
-                                       {"read-stats", no_argument, 0, 1000}, {0, 0, 0, 0}};
+                                       {"read-stats", no_argument, 0, 1000}, {"pileup", no_argument, 0, 1001}, {0, 0, 0, 0}};
     string outdir, index;
     bool read_stats = false;  // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
+    bool pileup = false;      // --pileup: cluster_pileup.tsv, the same alignments piled onto the representative position by position
     int o;
     while ((o = getopt_long(argc, argv, "dhvo:i:", lo, nullptr)) != -1) {
         switch (o) {
@@ -1066,10 +1127,13 @@ static int main_dump(int argc, char** argv)
             case 'i': index = optarg; break;
             case 'v': VERBOSE = true; break;
             case 1000: read_stats = true; break;
+            case 1001: pileup = true; break;
             case 'h':
-                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] final.cer" << endl
+                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] final.cer" << endl
                      << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
-                     << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl;
+                     << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
+                     << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
+                     << "                 its cluster cover it, the bases they have there, deletions, and insertions in front of it (GPU)" << endl;
                 exit(0);
             default: break;
         }
@@ -1189,7 +1253,7 @@ static int main_dump(int argc, char** argv)
             if (it == id2cls.end()) continue;
             tsv << it->second.cls << "\t" << it->second.strand << "\t" << id << "\n";
             per_cluster[it->second.cls].push_back(Piece{hb, sb, pb, qb, qe, it->second.strand == -1, p == qe + 1});
-            if (read_stats) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
+            if (read_stats || pileup) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
         }
     }
     lap("sorted fastq walked, clusters.tsv");
@@ -1243,12 +1307,12 @@ static int main_dump(int argc, char** argv)
         if (failed) die("Failed to write the cluster FASTQ files!");
     }
     lap("cluster fastq files written");
-    if (read_stats) {
-        write_read_stats(b, outdir, stat_rows.size(), [&](size_t x) {
+    if (read_stats || pileup) {
+        write_read_reports(b, outdir, stat_rows.size(), [&](size_t x) {
             const StatRow& r = stat_rows[x];
             return ReadStatRow{r.cls, r.strand, r.hb, size_t(r.he - r.hb), r.sb, size_t(r.se - r.sb), r.qb, size_t(r.qe - r.qb)};
-        });
-        lap("read_stats.tsv (GPU alignments)");
+        }, read_stats, pileup);
+        lap(pileup ? (read_stats ? "read_stats.tsv, cluster_pileup.tsv (GPU alignments)" : "cluster_pileup.tsv (GPU alignments)") : "read_stats.tsv (GPU alignments)");
     }
     if (VERBOSE) cerr << "Dump complete." << endl;
     return 0;

@@ -214,6 +214,45 @@ int ioc_host_ops_stats(const char* ops, int64_t len, ioc_aln_stats* out)
     return IOC_OK;
 }
 
+// The pileup of one operation string on its reference (ioc_pileup_col, isonclust2_hip.h), ADDED to cols[0 .. rlen].  The
+// definition the device's reduction (k_ops_pileup) is tested against.  A string that is refused leaves cols untouched.
+int ioc_host_ops_pileup(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, ioc_pileup_col* cols)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || qlen < 0 || rlen < 0 || (qlen > 0 && !query) || !cols) return IOC_ERR_ARG;
+    int64_t q = 0, r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        q += op == '=' || op == 'X' || op == 'I' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (q != qlen || r != rlen) return IOC_ERR_ARG;
+    q = r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        switch (ops[a]) {
+        case 'd': ++r; break;
+        case 'i': ++q; break;
+        case 'D': cols[r++].del += 1; break;
+        case 'I':
+            cols[r].ins_bases += 1;
+            if (a == 0 || ops[a - 1] != 'I') cols[r].ins_runs += 1;
+            ++q;
+            break;
+        default: {  // ('=' 'X')
+            ioc_pileup_col& c = cols[r++];
+            switch (query[q++]) {
+            case 'A': c.a += 1; break;
+            case 'C': c.c += 1; break;
+            case 'G': c.g += 1; break;
+            case 'T': c.t += 1; break;
+            default: c.other += 1; break;
+            }
+        }
+        }
+    }
+    return IOC_OK;
+}
+
 // setGapOpen, src/cluster.cpp:425-440
 int32_t ioc_host_gap_open(double e)
 {

@@ -1119,13 +1119,15 @@ int compute_units(const ioc_ctx* c)
     return n_cu < 1 ? 256 : n_cu;
 }
 
-// half of what is free (the checkpoint arena's own reservation counted as free), or IOC_ALIGN_CK_BUDGET_MB
-int ck_budget(ioc_ctx* c, uint64_t* budget)
+// half of what is free (the checkpoint arena's own reservation counted as free), or IOC_ALIGN_CK_BUDGET_MB.  `held`: bytes the
+// call holds beside the arena for its whole length (a pileup call's table) — counted as free, then taken off the budget.
+int ck_budget(ioc_ctx* c, uint64_t* budget, uint64_t held = 0)
 {
     size_t free_b = 0, total_b = 0;
     IOC_CHK(c, hipMemGetInfo(&free_b, &total_b));
-    *budget = uint64_t(free_b + c->a_ck.cap) / 2;
+    *budget = (uint64_t(free_b + c->a_ck.cap) + held) / 2;
     if (const char* e = getenv("IOC_ALIGN_CK_BUDGET_MB")) *budget = uint64_t(atoll(e)) << 20;
+    *budget -= std::min(*budget, held);
     return IOC_OK;
 }
 
@@ -1144,6 +1146,15 @@ struct AlnOpsHost {
     ioc_aln_stats* stats = nullptr;
     double* ms_kernel = nullptr;  // k_ops_stats' device time, and ...
     int64_t* records = nullptr;   // ... how many records came back (IOC_TRACE)
+    // ioc_align_pairs_pileup: a third sink (beside the statistics if `stats` is set, alone otherwise) — pair i's alignment is added
+    // to the rows from row_base[i] on of the call's table on the device, ONCE: piled[i] says that it has been, whichever run did it
+    ioc_pileup_col* pile = nullptr;  // (device) the table, pile_rows records
+    int64_t pile_rows = 0;
+    const int64_t* row_base = nullptr;
+    uint8_t* piled = nullptr;
+    double* ms_pileup = nullptr;  // k_ops_pileup's device time (IOC_TRACE)
+    bool reduced() const { return stats || pile; }  // the bytes stay on the device
+    uint64_t pile_bytes() const { return pile ? uint64_t(pile_rows) * sizeof(ioc_pileup_col) : 0; }
 };
 
 // One run's side (version 2's, version 1's).  The pairs of a slice get consecutive regions of ONE device buffer, as large as the
@@ -1159,14 +1170,19 @@ struct OpsRun {
     std::vector<uint32_t> room;        // (statistics) per device pair: query length + reference length ...
     const uint32_t* d_room = nullptr;  // ... and where that table is on the device
     std::vector<ioc_aln_stats> recs;   // (statistics) a slice's records, in the slice's order
+    std::vector<int64_t> row_base;     // (pileup) per device pair: its first row, -1 for a pair that has been added already ...
+    std::vector<uint32_t> q_off;       // ... and where its query starts in the pool
+    const int64_t* d_row_base = nullptr;
+    const uint32_t* d_q_off = nullptr;
 };
 
 // the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled).  A statistics call:
-// [end][len][room per pair][the bytes][4 spare bytes: k_ops_stats reads the dword that holds a string's last byte whole].
+// [end][len][room per pair][the bytes][4 spare bytes: k_ops_stats reads the dword that holds a string's last byte whole]; a
+// pileup call: [end][len][room][first row][query offset per pair][the bytes][4 spare bytes].
 int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vector<AlnPairDev>& dp)
 {
-    const bool st = o.host->stats != nullptr;
-    const size_t np = o.end.size(), tab = (np * (st ? 16 : 12) + 15) & ~size_t(15);
+    const bool st = o.host->reduced(), pile = o.host->pile != nullptr;
+    const size_t np = o.end.size(), tab = (np * (pile ? 28 : st ? 16 : 12) + 15) & ~size_t(15);
     const int r = ioc_reserve(c, c->a_ops, tab + size_t(max_slice_bytes) + (st ? 4 : 0));
     if (r != IOC_OK) return r;
     uint8_t* p = static_cast<uint8_t*>(c->a_ops.p);
@@ -1178,39 +1194,61 @@ int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vect
         o.d_room = reinterpret_cast<const uint32_t*>(p + np * 12);
         IOC_CHK(c, hipMemcpyAsync(p + np * 12, o.room.data(), np * 4, hipMemcpyHostToDevice, c->stream));
     }
+    if (pile) {
+        o.row_base.resize(np);
+        o.q_off.resize(np);
+        for (size_t x = 0; x < np; ++x) {
+            o.row_base[x] = o.host->piled[o.back[x]] ? -1 : o.host->row_base[o.back[x]];
+            o.q_off[x] = dp[x].q_off;
+        }
+        o.d_row_base = reinterpret_cast<const int64_t*>(p + np * 16);
+        o.d_q_off = reinterpret_cast<const uint32_t*>(p + np * 24);
+        IOC_CHK(c, hipMemcpyAsync(p + np * 16, o.row_base.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+        IOC_CHK(c, hipMemcpyAsync(p + np * 24, o.q_off.data(), np * 4, hipMemcpyHostToDevice, c->stream));
+    }
     return IOC_OK;
 }
 
-// a slice's sink in a statistics call (ioc_align_pairs_stats): k_ops_stats over the slice's pairs where their bytes lie; the
-// lengths and the 64-byte records come back, the bytes do not.  The same pairs are skipped as in ops_fetch.
-int ops_fetch_stats(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, const uint32_t* d_ord, uint32_t cnt)
+// a slice's sink in a call that reduces on the device (ioc_align_pairs_stats, ioc_align_pairs_pileup): k_ops_stats and / or
+// k_ops_pileup over the slice's pairs where their bytes lie; the lengths and the 64-byte records come back, the bytes do not (the
+// pileup's table stays where it is until the call is over).  The same pairs are skipped as in ops_fetch.
+int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, const uint32_t* d_ord, uint32_t cnt)
 {
+    const AlnOpsHost& h = *o.host;
     int r;
-    if ((r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
+    if (h.stats && (r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
     EventSet ev;
-    ev.v.assign(2, nullptr);
+    ev.v.assign(3, nullptr);
     for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
-    IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
+    if (h.stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
     IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
+    if (h.pile)
+        IOC_CHK(c, iock_ops_pileup(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off,
+                                   static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), h.pile, uint64_t(h.pile_rows)));
+    IOC_CHK(c, hipEventRecord(ev.v[2], c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
-    o.recs.resize(cnt);
     IOC_CHK(c, hipMemcpy(o.len.data(), o.dev.len, dp.size() * 4, hipMemcpyDeviceToHost));
-    IOC_CHK(c, hipMemcpy(o.recs.data(), c->a_ostats.p, size_t(cnt) * sizeof(ioc_aln_stats), hipMemcpyDeviceToHost));
+    if (h.stats) {
+        o.recs.resize(cnt);
+        IOC_CHK(c, hipMemcpy(o.recs.data(), c->a_ostats.p, size_t(cnt) * sizeof(ioc_aln_stats), hipMemcpyDeviceToHost));
+    }
     for (uint32_t x = 0; x < cnt; ++x) {
         const uint32_t pid = ord[x], i = o.back[pid];
         const uint64_t L = o.len[pid];
         if (L == 0 || L > uint64_t(dp[pid].n) + dp[pid].m || L > o.end[pid]) continue;
-        o.host->stats[i] = o.recs[x];
-        o.host->len[i] = int64_t(L);
+        if (h.stats) h.stats[i] = o.recs[x];
+        if (h.pile) h.piled[i] = 1;
+        h.len[i] = int64_t(L);
     }
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) *o.host->ms_kernel += double(ms);
-    *o.host->ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *o.host->copied += int64_t(dp.size() * 4 + size_t(cnt) * sizeof(ioc_aln_stats));
-    *o.host->records += int64_t(cnt);
+    if (h.stats && hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) *h.ms_kernel += double(ms);
+    if (h.pile && hipEventElapsedTime(&ms, ev.v[1], ev.v[2]) == hipSuccess) *h.ms_pileup += double(ms);
+    *h.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *h.copied += int64_t(dp.size() * 4 + (h.stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
+    if (h.stats) *h.records += int64_t(cnt);
     return IOC_OK;
 }
 
@@ -1218,7 +1256,7 @@ int ops_fetch_stats(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, co
 // window or by the corridor's certificate; out of range: the walk of a forward pass that was given up) is left to its re-run.
 int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, const uint32_t* d_ord, uint32_t cnt, uint64_t bytes)
 {
-    if (o.host->stats) return ops_fetch_stats(c, o, dp, ord, d_ord, cnt);
+    if (o.host->reduced()) return ops_fetch_reduced(c, o, dp, ord, d_ord, cnt);
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
@@ -1856,7 +1894,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     V2Opts o{};
     o.n_cu = compute_units(c);
     uint64_t budget = 0;
-    if ((r = ck_budget(c, &budget)) != IOC_OK) return r;
+    if ((r = ck_budget(c, &budget, ops ? ops->host->pile_bytes() : 0)) != IOC_OK) return r;
     // the 16-bit window's guard (|relative score| at a rebase): a pair beyond it is flagged and re-run by version 1
     o.guard = P16_GUARD;
     if (const char* e = getenv("IOC_ALIGN_V2_GUARD")) o.guard = std::max(1, std::min(P16_GUARD, atoi(e)));
@@ -1988,11 +2026,13 @@ int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const 
             const int64_t len = n + m;
             const int64_t cnt = (il <= 0 && len > k) ? len - k : 0;
             out.set(size_t(i), 0, cnt, n == 0 ? 0.0 : double(cnt) / double(n));
-            if (out.ops && out.ops->stats) {  // (all of it one free end gap, and no walk: leading)
-                ioc_aln_stats& s = out.ops->stats[i];
-                s = ioc_aln_stats{};
-                s.length = int32_t(len);
-                (n ? s.lead_i : s.lead_d) = int32_t(len);
+            if (out.ops && out.ops->reduced()) {  // (all of it one free end gap, and no walk: leading; nothing for a pileup)
+                if (out.ops->stats) {
+                    ioc_aln_stats& s = out.ops->stats[i];
+                    s = ioc_aln_stats{};
+                    s.length = int32_t(len);
+                    (n ? s.lead_i : s.lead_d) = int32_t(len);
+                }
                 out.ops->len[i] = len;
             } else if (out.ops) {  // (all of it one free end gap)
                 memset(out.ops->buf + out.ops->base[i], n ? 'i' : 'd', size_t(len));
@@ -2385,7 +2425,7 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
     const uint32_t np = uint32_t(b.dp.size());
     int r;
     uint64_t budget = 0;
-    if ((r = ck_budget(c, &budget)) != IOC_OK) return r;
+    if ((r = ck_budget(c, &budget, oh ? oh->pile_bytes() : 0)) != IOC_OK) return r;
     const uint64_t lrow_stride = uint64_t((b.max_m + 64 * FW_C - 1) / (64 * FW_C)) * 64;  // int2 per pair
     // (the forward pass addresses a pair's row checkpoints by a 32-bit offset in ints: 2^29 int2 units = 4 GB per pair,
     // reads of ~260 kb against each other)
@@ -2483,10 +2523,17 @@ int align_again(ioc_ctx* c, const ioc_aln_pair* pairs, const std::vector<int32_t
     std::vector<int64_t> sbase, slen(out.ops ? idx.size() : 0, 0);
     AlnOpsHost soh{};
     std::vector<ioc_aln_stats> sstats(out.ops && out.ops->stats ? idx.size() : 0, ioc_aln_stats{});
-    if (out.ops && out.ops->stats) {  // (statistics call: the re-run's records, scattered below)
+    std::vector<int64_t> srow;   // (pileup call: the re-run's pairs add into the same table, at their own rows)
+    std::vector<uint8_t> spiled;
+    if (out.ops && out.ops->reduced()) {  // (statistics call: the re-run's records, scattered below)
         soh = *out.ops;
         soh.len = slen.data();
-        soh.stats = sstats.data();
+        if (out.ops->stats) soh.stats = sstats.data();
+        if (out.ops->pile) {
+            for (int32_t i : idx) srow.push_back(out.ops->row_base[i]), spiled.push_back(out.ops->piled[i]);
+            soh.row_base = srow.data();
+            soh.piled = spiled.data();
+        }
     } else if (out.ops) {
         for (int32_t i : idx) sbase.push_back(out.ops->base[i]);
         soh = AlnOpsHost{out.ops->buf, sbase.data(), slen.data(), out.ops->ms_copy, out.ops->copied};
@@ -2498,6 +2545,7 @@ int align_again(ioc_ctx* c, const ioc_aln_pair* pairs, const std::vector<int32_t
         out.set(size_t(idx[x]), sc[x], sw[x], sr[x]);
         if (out.ops) out.ops->len[idx[x]] = slen[x];
         if (out.ops && out.ops->stats) out.ops->stats[idx[x]] = sstats[x];
+        if (out.ops && out.ops->pile) out.ops->piled[idx[x]] = spiled[x];
     }
     return IOC_OK;
 }
@@ -2692,6 +2740,55 @@ int ioc_align_pairs_stats(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: alignment statistics: %lld records (%.3f MB with the lengths) copied from the device in %.3f ms, k_ops_stats %.3f ms\n",
                 (long long)records, double(copied) * 1e-6, ms_copy, ms_kernel);
+    return IOC_OK;
+}
+
+// The walks write a slice's bytes as for ioc_align_pairs_ops; k_ops_pileup (ioc_ops_pileup.hip) adds them, where they lie, into a
+// table of the call's rows that stays on the device over the slices and the re-runs and is copied out once.
+int ioc_align_pairs_pileup(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                           const int64_t* row_base, int64_t n_rows, ioc_pileup_col* out_cols)
+{
+    if (!c || n_pairs < 0 || n_rows < 0 || (n_pairs > 0 && (!pairs || !row_base || !out_cols))) return IOC_ERR_ARG;
+    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        const ioc_aln_pair& a = pairs[i];
+        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
+        const int64_t m = c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)];
+        if (row_base[i] < 0 || row_base[i] > n_rows - m - 1)
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_pileup: the rows of pair " + std::to_string(i) + " lie outside the table");
+    }
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    if (out_cols && n_rows > 0) memset(out_cols, 0, size_t(n_rows) * sizeof(ioc_pileup_col));
+    if (n_pairs == 0 || n_rows == 0) return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
+    IOC_CHK(c, hipSetDevice(c->device));
+    const size_t bytes = size_t(n_rows) * sizeof(ioc_pileup_col);
+    IOC_TRY(ioc_reserve(c, c->a_pile, bytes));
+    IOC_CHK(c, hipMemsetAsync(c->a_pile.p, 0, bytes, c->stream));
+    std::vector<int64_t> len(size_t(n_pairs), 0);
+    std::vector<uint8_t> piled(size_t(n_pairs), 0);
+    double ms_copy = 0, ms_kernel = 0, ms_pileup = 0;
+    int64_t copied = 0, records = 0;
+    AlnOpsHost oh{nullptr, nullptr, len.data(), &ms_copy, &copied};
+    oh.stats = out_stats;
+    oh.ms_kernel = &ms_kernel;
+    oh.records = &records;
+    oh.pile = c->a_pile.as<ioc_pileup_col>();
+    oh.pile_rows = n_rows;
+    oh.row_base = row_base;
+    oh.piled = piled.data();
+    oh.ms_pileup = &ms_pileup;
+    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, &oh}, AlnRoute::normal);
+    if (r != IOC_OK) return r;
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    IOC_CHK(c, hipMemcpy(out_cols, c->a_pile.p, bytes, hipMemcpyDeviceToHost));
+    ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    copied += int64_t(bytes);
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: pileup: %lld rows, %.3f MB (table, lengths%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms%s\n",
+                (long long)n_rows, double(copied) * 1e-6, out_stats ? ", statistics" : "", ms_copy, ms_pileup,
+                out_stats ? (", k_ops_stats " + std::to_string(ms_kernel) + " ms").c_str() : "");
     return IOC_OK;
 }
 

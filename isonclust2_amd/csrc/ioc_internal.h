@@ -206,6 +206,7 @@ struct ioc_ctx {
     // ---- GPU alignment fallback (ioc_align_gpu.hip) ----
     DevBuf a_pool, a_pairs, a_order, a_out, a_bnd, a_lrow, a_ck, a_cko, a_ends, a_ends2, a_xflags, a_prof, a_ops;
     DevBuf a_ostats;  // ioc_align_pairs_stats: the records of a slice (k_ops_stats)
+    DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
     hipStream_t side_stream = nullptr;  // the aligner's helper launch for the wrong candidates, beside the first traceback launch
@@ -308,6 +309,12 @@ int ioc_query_candidates_many(ioc_ctx* c, const std::vector<int>& qs, std::vecto
 // len > end is skipped
 hipError_t iock_ops_stats(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room,
                           const uint32_t* ord, uint32_t cnt, ioc_aln_stats* out);
+
+// ioc_ops_pileup.hip: the same strings piled onto their references (ioc_host_ops_pileup) — pair pid adds into the records of
+// `cols` from row_base[pid] on (negative: skipped), its query bases read at pool + q_off[pid]; the same pairs are skipped
+hipError_t iock_ops_pileup(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room,
+                           const uint32_t* ord, uint32_t cnt, const int64_t* row_base, const uint32_t* q_off, const uint8_t* pool,
+                           uint64_t pool_bytes, ioc_pileup_col* cols, uint64_t n_rows);
 
 // ioc_capi.cpp: queries whose minimizer arrays are already in HBM (ioc_batch_view::minimizers_on_device)
 extern "C" int ioc_queries_upload_devmins(ioc_ctx* c, int32_t n, const int64_t* off_fwd, const int64_t* off_rev, const uint32_t* d_min_val,

@@ -1,0 +1,58 @@
+// ioc_ops_pileup.h — the step logic of k_ops_pileup (ioc_ops_pileup.hip), callable on the host as well: tools/pileup_acc_check.cpp
+// drives it over strings on the CPU, under the sanitizers, against the definition (ioc_host_ops_pileup).
+#pragma once
+
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define IOC_PILE_HD __host__ __device__ __forceinline__
+#else
+#define IOC_PILE_HD inline
+#endif
+
+// the channels of a row as words of ioc_pileup_col
+enum : uint32_t { PILE_A = 0, PILE_C, PILE_G, PILE_T, PILE_OTHER, PILE_DEL, PILE_INS_RUNS, PILE_INS_BASES, PILE_WORDS };
+
+// Where a wave stands in its string; one step per 64 bytes, bit l of a mask = the l-th of them (bytes outside the string are 0
+// in every mask).  The members are the same in every lane (the masks are ballots); what differs per lane is the argument l.
+struct PileAcc {
+    uint32_t r = 0, q = 0;  // reference / query bases consumed before this step
+    bool open_i = false;    // the byte before this step is 'I'
+    unsigned long long m_ref = 0, m_qry = 0, m_base = 0, m_del = 0, m_ins = 0;
+
+    IOC_PILE_HD void begin(unsigned long long m_eq, unsigned long long m_x, unsigned long long m_i, unsigned long long m_d,
+                           unsigned long long e_i, unsigned long long e_d)
+    {
+        m_base = m_eq | m_x;
+        m_del = m_d;
+        m_ins = m_i;
+        m_ref = m_base | m_d | e_d;
+        m_qry = m_base | m_i | e_i;
+    }
+    static IOC_PILE_HD unsigned long long below(uint32_t l) { return (1ull << l) - 1ull; }
+    // the reference position lane l's byte stands at (in front of, for an 'I'), and the query base it takes
+    IOC_PILE_HD uint32_t row(uint32_t l) const { return r + uint32_t(__builtin_popcountll(m_ref & below(l))); }
+    IOC_PILE_HD uint32_t qpos(uint32_t l) const { return q + uint32_t(__builtin_popcountll(m_qry & below(l))); }
+    IOC_PILE_HD bool is_base(uint32_t l) const { return (m_base >> l) & 1ull; }
+    IOC_PILE_HD bool is_del(uint32_t l) const { return (m_del >> l) & 1ull; }
+    // The 'I' bytes of a step are added piece by piece — a piece: consecutive 'I's within the step, all in front of one row — by
+    // the lane of the piece's first byte: its length, 0 for every other lane.  One add per piece, not one per byte on one address.
+    IOC_PILE_HD uint32_t ins_piece(uint32_t l) const
+    {
+        if (!(((m_ins & ~(m_ins << 1)) >> l) & 1ull)) return 0u;
+        const unsigned long long x = ~(m_ins >> l);  // (0 only for l == 0 under a mask of all ones)
+        return x ? uint32_t(__builtin_ctzll(x)) : 64u;
+    }
+    // a maximal run of 'I' starts at lane l: the piece's first lane, unless the run came in from the step before
+    IOC_PILE_HD bool run_start(uint32_t l) const { return ((m_ins & ~((m_ins << 1) | (open_i ? 1ull : 0ull))) >> l) & 1ull; }
+    IOC_PILE_HD void end()
+    {
+        r += uint32_t(__builtin_popcountll(m_ref));
+        q += uint32_t(__builtin_popcountll(m_qry));
+        open_i = (m_ins >> 63) != 0ull;
+    }
+    static IOC_PILE_HD uint32_t channel(uint8_t base)
+    {
+        return base == uint8_t('A') ? PILE_A : base == uint8_t('C') ? PILE_C : base == uint8_t('G') ? PILE_G : base == uint8_t('T') ? PILE_T : PILE_OTHER;
+    }
+};
