@@ -326,6 +326,40 @@ typedef struct {
  * cols[0 .. rlen].  IOC_ERR_ARG, with cols untouched, for a byte that is no operation, for a string that does not consume
  * exactly qlen query bases and rlen reference bases, and for len >= 2^31. */
 int ioc_host_ops_pileup(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, ioc_pileup_col* cols);
+/* What the reads insert in front of a row, beside ioc_pileup_col's ins_runs / ins_bases: a second record per row, R + 1 rows for
+ * a reference of R bases.  An 'I' byte that is the j-th byte of its maximal run of 'I' (j from 0) adds 1 to
+ * slot[j][channel of query[q]] of row r where j < IOC_PILE_INS_SLOTS, else to `longer`.  For one string, per row: the sum over
+ * slot[0] is ins_runs, the sum over all slots plus `longer` is ins_bases. */
+#define IOC_PILE_INS_SLOTS 6
+typedef struct {
+    uint32_t slot[IOC_PILE_INS_SLOTS][5]; /* [s][a,c,g,t,other]: reads whose insertion in front of this row has an (s+1)-th base, by that base */
+    uint32_t longer;                      /* inserted bases at index >= IOC_PILE_INS_SLOTS */
+    uint32_t reserved;                    /* 0 */
+} ioc_pileup_ins;                          /* 128 bytes */
+/* The definition of the insertion table (the ins variant of k_ops_pileup is tested against it): the walk of
+ * ioc_host_ops_pileup, the same inputs refused (ins untouched), ADDS to ins[0 .. rlen]. */
+int ioc_host_ops_pileup_ins(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, ioc_pileup_ins* ins);
+/* What a consensus call made of one reference (ioc_host_pileup_call and the device's call kernels). */
+typedef struct {
+    int32_t out_len;              /* bytes written */
+    int32_t n_sub, n_del, n_ins;  /* positions called as another base / as deleted; inserted bases emitted */
+    int32_t n_low;                /* positions below min_depth, kept as the frame has them (quality 0) */
+    int32_t reserved[3];
+} ioc_polish_stats;               /* 32 bytes */
+/* The definition of the consensus call: the majority call over the two tables of one reference (`frame`, rlen bases, in the
+ * frame of the tables).  depth(p) = a + c + g + t + other + del of row p; all arithmetic in 64 bits.  For p = 0 .. rlen:
+ *  - insertions in front of p: D = depth(p) for p < rlen, depth(rlen - 1) for p == rlen, 0 for rlen == 0.  For s = 0 .. 5 in
+ *    turn, n = the sum of slot[s]: the slots of the row stop unless D >= min_depth and 2n > D; else the first maximal channel
+ *    of slot[s] in the order A C G T other (written 'N') is emitted with quality min(40, 40 max / D), and n_ins counts it;
+ *  - the base, for p < rlen: depth(p) < min_depth: frame[p] with quality 0, n_low.  Else m = the largest of the six counters;
+ *    the winner is the channel of frame[p] if its count is m, else the first maximal one in the order A C G T other del.  del:
+ *    nothing is emitted, n_del; the frame's channel: frame[p] as it is; another: its letter ('N' for other), n_sub.  Quality
+ *    min(40, 40 m / depth(p)).
+ * Qualities are written as 33 + q.  Returns the length written (also st->out_len; st may be NULL); IOC_ERR_ARG for
+ * min_depth < 1, rlen < 0 or a NULL table / frame / output that is needed; IOC_ERR_CAPACITY, with nothing written, for
+ * cap < rlen + IOC_PILE_INS_SLOTS * (rlen + 1). */
+int64_t ioc_host_pileup_call(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen,
+                             int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st);
 int32_t ioc_host_gap_open(double e1_plus_e2);                     /* setGapOpen,  src/cluster.cpp:425-440 */
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
@@ -387,6 +421,35 @@ int ioc_align_pairs_pileup(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pa
                            int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
                            double* out_ratio, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows,
                            ioc_pileup_col* out_cols);
+/* The consensus call of many references at once ON THE DEVICE (ioc_pile_call.hip), from host tables that are uploaded: segment
+ * g is a reference of rlen[g] bases, its frame at frames + frame_off[g], its rlen[g] + 1 rows of `cols` / `ins` from the sum
+ * over the earlier segments of (rlen + 1) on.  Segment g's sequence and qualities, as ioc_host_pileup_call defines them, stand
+ * at out_seq / out_qual + out_off[g] .. out_off[g + 1] (packed, in segment order; out_off has n_segs + 1 entries), its record in
+ * out_stats[g] (may be NULL).  For callers who add pileups up over several calls before they call.  IOC_ERR_ARG for
+ * min_depth < 1, a negative rlen or a NULL array that is needed; IOC_ERR_CAPACITY, with nothing written, for cap below the
+ * sum of the segments' bounds (rlen + IOC_PILE_INS_SLOTS * (rlen + 1) each), and for a segment whose bound exceeds 2^31 - 1. */
+int ioc_pileup_call(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                    const ioc_pileup_col* cols, const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual,
+                    int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats);
+/* A segment of ioc_align_pairs_polish: the pool sequence that is its frame, reverse-complemented where ref_revcomp is set. */
+typedef struct {
+    int32_t ref;
+    int32_t ref_revcomp;
+} ioc_polish_seg;
+/* ioc_align_pairs + the polished consensus of every segment: the pairs are aligned, pair i is piled into both tables (the ins
+ * variant of k_ops_pileup) at the rows of segment seg_of_pair[i], the segments are called on the device where the tables lie,
+ * and the sequences, qualities, offsets and records come back as from ioc_pileup_call (out_polish: n_segs records).  The tables
+ * come back only where asked for: out_cols / out_ins (sum of frame length + 1 rows, may be NULL).  A segment without pairs
+ * returns its frame with quality 0 throughout.  An emitting call like ioc_align_pairs_pileup: always exact, the verdict
+ * threshold not applied, IOC_ALIGN_VARIANT=carry not honoured; both device tables (160 bytes per row) count against the
+ * checkpoint arena's budget.  IOC_ERR_ARG, with nothing written, for a pair whose reference length differs from its segment's
+ * frame, seg_of_pair outside the segments, a segment or pair outside the pool and min_depth < 1; IOC_ERR_CAPACITY for cap
+ * below the sum of the per-segment bounds.  out_stats and any of out_score / out_windows / out_ratio may be NULL. */
+int ioc_align_pairs_polish(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio,
+                           ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair,
+                           int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                           ioc_polish_stats* out_polish, ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

@@ -95,6 +95,53 @@ def ops_pileup(ops, query, rlen, cols=None):
     return cols
 
 
+# ioc_pileup_ins / ioc_polish_stats as numpy records
+PILEUP_INS_DTYPE = np.dtype([("slot", np.uint32, (_lib.PILE_INS_SLOTS, 5)), ("longer", np.uint32), ("reserved", np.uint32)])
+POLISH_STATS_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.PolishStats._fields_[:-1]] + [("reserved", np.int32, (3,))])
+POLISH_STATS_FIELDS = tuple(n for n, _ in _lib.PolishStats._fields_[:-1])
+PILE_CALL_CHUNK = 256  # rows a workgroup of the call kernels takes per step (IOC_PILE_CALL_CHUNK; the tests place sizes around it)
+
+
+def pileup_call_bound(rlen):
+    """What a consensus call of a reference of rlen bases may write at most: rlen + IOC_PILE_INS_SLOTS * (rlen + 1)."""
+    return int(rlen) + _lib.PILE_INS_SLOTS * (int(rlen) + 1)
+
+
+def ops_pileup_ins(ops, query, rlen, ins=None):
+    """ioc_host_ops_pileup_ins: what the 'I' bytes of one operation string insert, by the row they stand in front of, their index
+    in their run and the query's base — rlen + 1 rows (PILEUP_INS_DTYPE), ADDED to `ins` where given (returned), else to zeros.
+    ValueError, with ins untouched, for what ops_pileup refuses."""
+    if ins is None:
+        ins = np.zeros(rlen + 1, PILEUP_INS_DTYPE)
+    if ins.dtype != PILEUP_INS_DTYPE or ins.shape != (rlen + 1,) or not ins.flags["C_CONTIGUOUS"]:
+        raise ValueError("ins must be a contiguous array of rlen + 1 rows of PILEUP_INS_DTYPE")
+    rc = _lib.load().ioc_host_ops_pileup_ins(bytes(ops), len(ops), bytes(query), len(query), int(rlen), ins.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_pileup_ins failed ({rc})")
+    return ins
+
+
+def _tables(cols, ins, n_rows):
+    cols, ins = np.ascontiguousarray(cols, PILEUP_DTYPE), np.ascontiguousarray(ins, PILEUP_INS_DTYPE)
+    if cols.shape != (n_rows,) or ins.shape != (n_rows,):
+        raise ValueError(f"cols and ins must hold {n_rows} rows each")
+    return cols, ins
+
+
+def pileup_call(cols, ins, frame, min_depth=3, cap=None):
+    """ioc_host_pileup_call: the majority call of one reference (`frame`, bytes) from its two tables (len(frame) + 1 rows each) —
+    returns (sequence, qualities, stats), bytes, bytes and a dict of POLISH_STATS_FIELDS.  IocError for min_depth < 1 and for a
+    `cap` (default: the bound) below the bound."""
+    rlen = len(frame)
+    cols, ins = _tables(cols, ins, rlen + 1)
+    cap = pileup_call_bound(rlen) if cap is None else int(cap)
+    seq, qual, st = C.create_string_buffer(max(cap, 1)), C.create_string_buffer(max(cap, 1)), _lib.PolishStats()
+    n = _lib.load().ioc_host_pileup_call(cols.ctypes.data, ins.ctypes.data, bytes(frame), rlen, int(min_depth), seq, qual, cap, C.byref(st))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_pileup_call")
+    return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in POLISH_STATS_FIELDS}
+
+
 def ops_to_comp(ops):
     """The comparison string of an operation string: '|' where the bases are equal, ' ' in every other column."""
     return bytes(ops).translate(bytes(0x7C if b == 0x3D else 0x20 for b in range(256)))
@@ -277,6 +324,11 @@ class Context:
         np.cumsum([len(x) for x in seqs], out=offs[1:])
         blob = b"".join(seqs)
         self._chk(self.L.ioc_align_set_pool(self.h, len(seqs), blob, _p(offs, C.c_int64)))
+        self._aln_pool_offs = offs
+
+    def align_pool_offsets(self):
+        """Where the sequences of the last align_set_pool start (n + 1 offsets; empty pool: [0])."""
+        return getattr(self, "_aln_pool_offs", np.zeros(1, np.int64))
 
     def align_set_verdict_threshold(self, thr):
         """ioc_align_set_verdict_threshold: > 0 lets tracebacks stop once ratio >= thr is decided (windows / ratio become bounds)."""
@@ -342,6 +394,66 @@ class Context:
                                                 _p(ratio, C.c_double), st.ctypes.data if stats and n else None, _p(row_base, C.c_int64),
                                                 int(n_rows), cols.ctypes.data))
         return (score, win, ratio, cols, st) if stats else (score, win, ratio, cols)
+
+    def pileup_call(self, frames, cols, ins, min_depth=3, cap=None):
+        """ioc_pileup_call: the consensus call of many references at once on the device, from host tables — `frames` a list of
+        bytes, segment g's len(frames[g]) + 1 rows of cols / ins following those of the earlier segments.  Returns
+        ([sequence per segment], [qualities per segment], stats), stats an array of POLISH_STATS_DTYPE; each segment as
+        pileup_call defines it."""
+        n = len(frames)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        cols, ins = _tables(cols, ins, int(rlen.sum()) + n)
+        f_off = np.zeros(n + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        bound = sum(pileup_call_bound(r) for r in rlen)
+        cap = bound if cap is None else int(cap)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, st = np.zeros(n + 1, np.int64), np.zeros(n, POLISH_STATS_DTYPE)
+        self._chk(self.L.ioc_pileup_call(self.h, n, _p(rlen, C.c_int32), b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+                                         cols.ctypes.data, ins.ctypes.data, int(min_depth), seq.ctypes.data, qual.ctypes.data, cap,
+                                         _p(off, C.c_int64), st.ctypes.data if n else None))
+        return ([seq[off[g]:off[g + 1]].tobytes() for g in range(n)], [qual[off[g]:off[g + 1]].tobytes() for g in range(n)], st)
+
+    def align_pairs_polish(self, pairs, k, segs, seg_of_pair, min_depth=3, stats=False, tables=False, cap=None, match=2, mismatch=-2,
+                           gap_extend=1):
+        """ioc_align_pairs_polish: align_pairs, both pileup tables and the consensus call of every segment, all on the device —
+        segs: (pool sequence, revcomp) per segment, the frame the segment's pairs were aligned against; seg_of_pair: the segment
+        pair i is piled into.  Returns a dict: score, windows, ratio, seq and qual (lists of bytes per segment), polish
+        (POLISH_STATS_DTYPE per segment), with stats=True `stats` (ALN_STATS_DTYPE per pair), with tables=True `cols` and `ins`
+        (the rows of segment g from sum(len(frame) + 1) of the earlier ones on) and `row0` (the first row per segment)."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr = (_lib.PolishSeg * max(ns, 1))()
+        for g, (ref, rc) in enumerate(segs):
+            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair must hold one entry per pair")
+        offs = self.align_pool_offsets()
+        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
+        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
+        n_rows = sum(rlen) + ns
+        bound = sum(pileup_call_bound(r) for r in rlen)
+        cap = bound if cap is None else int(cap)
+        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, pol = np.zeros(ns + 1, np.int64), np.zeros(ns, POLISH_STATS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        ins = np.zeros(n_rows, PILEUP_INS_DTYPE) if tables else None
+        self._chk(self.L.ioc_align_pairs_polish(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
+                                                _p(ratio, C.c_double), st.ctypes.data if stats and n else None, ns, sarr, _p(sop, C.c_int32),
+                                                int(min_depth), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64),
+                                                pol.ctypes.data if ns else None, cols.ctypes.data if tables and n_rows else None,
+                                                ins.ctypes.data if tables and n_rows else None))
+        out = {"score": score, "windows": win, "ratio": ratio, "polish": pol,
+               "seq": [seq[off[g]:off[g + 1]].tobytes() for g in range(ns)], "qual": [qual[off[g]:off[g + 1]].tobytes() for g in range(ns)]}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out["cols"], out["ins"] = cols, ins
+            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
+        return out
 
     # ---- sort-stage feeders --------------------------------------------------------------------
     def qual_scores(self, offs, qual, k):

@@ -949,6 +949,12 @@ static int main_cluster(int argc, char** argv)
 // position of the representative as that file has it — how many reads cover the base, what they say there, how many have an
 // insertion in front of it — and a last row (RepBase '-') for the insertions behind the last base.  With both options a group
 // is aligned once: the pileup call returns the statistics of the same alignments.
+//
+// dump --polish: <outdir>/cluster_polished.fq from the same pairs, groups and frames — one record per record of cluster_cons.fq, in
+// its order and frame: the majority call over the cluster's reads (ioc_align_pairs_polish: both pileup tables and the call on the
+// device, only the sequences come back), header "@cluster_<id> reads=<pairs> subs= dels= ins= low=".  A cluster without a row of
+// clusters.tsv keeps its representative, with '!' qualities.  Beside the other options a group is still aligned once: the
+// polish call returns the statistics and the first table as well.
 struct ReadStatRow {
     unsigned cls;
     int strand;
@@ -960,8 +966,9 @@ struct ReadStatRow {
     size_t qual_len;
 };
 static void write_read_reports(const Batch& b, const string& outdir, size_t n_rows, const std::function<ReadStatRow(size_t)>& row, bool want_stats,
-                               bool want_pileup)
+                               bool want_pileup, int polish_min_depth /* 0: no --polish */)
 {
+    const bool want_polish = polish_min_depth > 0, want_groups = want_pileup || want_polish;
     constexpr size_t POOL_MAX = size_t(256) << 20;
     const int k = b.SortArgs.KmerSize;
     std::vector<std::vector<size_t>> rows_of(b.Cls.size());  // per cluster with a consensus record: its rows, in the order of clusters.tsv
@@ -999,15 +1006,49 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         create_file(outdir + "/cluster_pileup.tsv", pile_out);
         pile_out << "ClusterId\tPos\tRepBase\tDepth\tA\tC\tG\tT\tN\tDel\tInsReads\tInsBases\n";
     }
+    // (--polish) the group's segments: one per cluster with rows, in the order of group_cls (group_seg: its index there, -1 for a
+    // cluster without a row), and what the call returned for them
+    std::vector<ioc_polish_seg> segs;
+    std::vector<int32_t> seg_of_pair, seg_reads, group_seg;
+    string pol_seq, pol_qual;
+    std::vector<int64_t> pol_off;
+    std::vector<ioc_polish_stats> pol;
+    std::ofstream polish_out;
+    if (want_polish) create_file(outdir + "/cluster_polished.fq", polish_out);
+    auto frame_of = [&](size_t ci) {
+        const auto& rep = b.Cls[ci]->at(0);
+        string frame = rep->RawSeq->seq.str();  // (as cluster_cons.fq has it)
+        if (rep->MatchStrand == -1) {
+            std::reverse(frame.begin(), frame.end());
+            for (char& ch : frame) ch = comp(ch);
+        }
+        return frame;
+    };
+    auto write_polish = [&]() {
+        string text;
+        for (size_t x = 0; x < group_cls.size(); ++x) {
+            const int32_t g = group_seg[x];
+            ioc_polish_stats z{};
+            string seq, qual;
+            if (g < 0) {
+                seq = frame_of(group_cls[x].first);
+                qual.assign(seq.size(), '!');
+                z.n_low = int32_t(seq.size());
+            } else {
+                z = pol[size_t(g)];
+                seq.assign(pol_seq, size_t(pol_off[size_t(g)]), size_t(pol_off[size_t(g) + 1] - pol_off[size_t(g)]));
+                qual.assign(pol_qual, size_t(pol_off[size_t(g)]), size_t(pol_off[size_t(g) + 1] - pol_off[size_t(g)]));
+            }
+            text = "@cluster_" + std::to_string(group_cls[x].first) + " reads=" + std::to_string(g < 0 ? 0 : seg_reads[size_t(g)]) +
+                   " subs=" + std::to_string(z.n_sub) + " dels=" + std::to_string(z.n_del) + " ins=" + std::to_string(z.n_ins) +
+                   " low=" + std::to_string(z.n_low) + "\n" + seq + "\n+\n" + qual + "\n";
+            polish_out.write(text.data(), std::streamsize(text.size()));
+        }
+    };
     auto write_pileup = [&]() {
         string text;
         for (const auto& gc : group_cls) {
-            const auto& rep = b.Cls[gc.first]->at(0);
-            string frame = rep->RawSeq->seq.str();  // (as cluster_cons.fq has it)
-            if (rep->MatchStrand == -1) {
-                std::reverse(frame.begin(), frame.end());
-                for (char& ch : frame) ch = comp(ch);
-            }
+            const string frame = frame_of(gc.first);
             text.clear();
             for (size_t p = 0; p <= frame.size(); ++p) {
                 const ioc_pileup_col z = gc.second < 0 ? ioc_pileup_col{} : cols[size_t(gc.second) + p];
@@ -1018,12 +1059,17 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             }
             pile_out.write(text.data(), std::streamsize(text.size()));
         }
+    };
+    auto write_groups = [&]() {
+        if (want_pileup) write_pileup();
+        if (want_polish) write_polish();
         group_cls.clear(), row_base.clear(), cols.clear();
+        segs.clear(), seg_of_pair.clear(), seg_reads.clear(), group_seg.clear();
         group_rows = 0;
     };
     auto flush = [&]() {
         if (pairs.empty()) {
-            if (want_pileup) write_pileup();
+            if (want_groups) write_groups();
             return;
         }
         const size_t nq = qoffs.size() - 1, np = pairs.size();
@@ -1034,12 +1080,26 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         std::vector<int32_t> sc(np);
         std::vector<int64_t> win(np);
         std::vector<ioc_aln_stats> st(want_stats ? np : 0);
-        if (want_pileup) {
+        if (want_polish) {
+            int64_t cap = 0;
+            for (const ioc_polish_seg& sg : segs) {
+                const int64_t m = offs[size_t(sg.ref) + 1] - offs[size_t(sg.ref)];
+                cap += m + IOC_PILE_INS_SLOTS * (m + 1);
+            }
+            pol_seq.assign(size_t(cap), '\0'), pol_qual.assign(size_t(cap), '\0');
+            pol_off.assign(segs.size() + 1, 0), pol.assign(segs.size(), ioc_polish_stats{});
+            if (want_pileup) cols.assign(size_t(group_rows), ioc_pileup_col{});
+            check(c, ioc_align_pairs_polish(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
+                                            int32_t(segs.size()), segs.data(), seg_of_pair.data(), polish_min_depth, &pol_seq[0], &pol_qual[0], cap,
+                                            pol_off.data(), pol.data(), want_pileup ? cols.data() : nullptr, nullptr),
+                  "polished consensus");
+            write_groups();
+        } else if (want_pileup) {
             cols.assign(size_t(group_rows), ioc_pileup_col{});
             check(c, ioc_align_pairs_pileup(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
                                             row_base.data(), group_rows, cols.data()),
                   "alignment pileup");
-            write_pileup();
+            write_groups();
         } else {
             check(c, ioc_align_pairs_stats(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, st.data()), "alignment statistics");
         }
@@ -1051,7 +1111,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
     };
     for (size_t ci = 0; ci < b.Cls.size(); ++ci) {
         if (rows_of[ci].empty()) {
-            if (want_pileup && b.Cls[ci]->at(0)->RawSeq->score >= 0) group_cls.emplace_back(ci, int64_t(-1));
+            if (want_groups && b.Cls[ci]->at(0)->RawSeq->score >= 0) group_cls.emplace_back(ci, int64_t(-1)), group_seg.push_back(-1);
             continue;
         }
         const auto& rep = b.Cls[ci]->at(0);
@@ -1066,10 +1126,16 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         offs.push_back(int64_t(pool.size()));
         quals.append(rep->RawSeq->qual.data(), rep->RawSeq->qual.size());
         qoffs.push_back(int64_t(quals.size()));
-        if (want_pileup) {
+        if (want_groups) {
             group_cls.emplace_back(ci, group_rows);
+            group_seg.push_back(int32_t(segs.size()));
             row_base.insert(row_base.end(), rows_of[ci].size(), group_rows);
             group_rows += int64_t(rep->RawSeq->seq.size()) + 1;
+        }
+        if (want_polish) {
+            seg_of_pair.insert(seg_of_pair.end(), rows_of[ci].size(), int32_t(segs.size()));
+            seg_reads.push_back(int32_t(rows_of[ci].size()));
+            segs.push_back(ioc_polish_seg{rep_seq, rep->MatchStrand == -1 ? 1 : 0});
         }
         for (size_t y : rows_of[ci]) {
             const ReadStatRow r = row(kept[y]);
@@ -1116,10 +1182,13 @@ static int main_dump(int argc, char** argv)
 {
     static const struct option lo[] = {{"verbose", no_argument, 0, 'v'}, {"debug", no_argument, 0, 'd'}, {"help", no_argument, 0, 'h'},
                                        {"outdir", required_argument, 0, 'o'}, {"index", required_argument, 0, 'i'},
-                                       {"read-stats", no_argument, 0, 1000}, {"pileup", no_argument, 0, 1001}, {0, 0, 0, 0}};
+                                       {"read-stats", no_argument, 0, 1000}, {"pileup", no_argument, 0, 1001},
+                                       {"polish", no_argument, 0, 1002}, {"polish-min-depth", required_argument, 0, 1003}, {0, 0, 0, 0}};
     string outdir, index;
     bool read_stats = false;  // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
     bool pileup = false;      // --pileup: cluster_pileup.tsv, the same alignments piled onto the representative position by position
+    bool polish = false;      // --polish: cluster_polished.fq, every representative called anew from both pileup tables of its reads
+    int polish_min_depth = 3;  // --polish-min-depth: positions covered by fewer reads keep the representative's base
     int o;
     while ((o = getopt_long(argc, argv, "dhvo:i:", lo, nullptr)) != -1) {
         switch (o) {
@@ -1128,18 +1197,25 @@ static int main_dump(int argc, char** argv)
             case 'v': VERBOSE = true; break;
             case 1000: read_stats = true; break;
             case 1001: pileup = true; break;
+            case 1002: polish = true; break;
+            case 1003: polish_min_depth = atoi(optarg); break;
             case 'h':
-                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] final.cer" << endl
+                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N]] final.cer" << endl
                      << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
                      << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
                      << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
-                     << "                 its cluster cover it, the bases they have there, deletions, and insertions in front of it (GPU)" << endl;
+                     << "                 its cluster cover it, the bases they have there, deletions, and insertions in front of it (GPU)" << endl
+                     << "  --polish       also write outdir/cluster_polished.fq: one record per record of cluster_cons.fq, the majority call over the" << endl
+                     << "                 cluster's reads aligned against it — substitutions, deletions and insertions of up to 6 bases (GPU);" << endl
+                     << "                 header: reads, and how many positions were substituted, deleted, inserted or left as they were" << endl
+                     << "  --polish-min-depth N   positions covered by fewer than N reads keep the representative's base, quality '!' (default 3)" << endl;
                 exit(0);
             default: break;
         }
     }
     if (optind >= argc) die("No input batch specified!");
     if (outdir.empty()) die("Specifying output directory is mandatory!");
+    if (polish && polish_min_depth < 1) die("--polish-min-depth must be at least 1!");
     if (index.empty()) die("Specifying the sorted read index is mandatory!");
     Batch b;
     string err, fastq;
@@ -1253,7 +1329,7 @@ static int main_dump(int argc, char** argv)
             if (it == id2cls.end()) continue;
             tsv << it->second.cls << "\t" << it->second.strand << "\t" << id << "\n";
             per_cluster[it->second.cls].push_back(Piece{hb, sb, pb, qb, qe, it->second.strand == -1, p == qe + 1});
-            if (read_stats || pileup) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
+            if (read_stats || pileup || polish) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
         }
     }
     lap("sorted fastq walked, clusters.tsv");
@@ -1307,12 +1383,13 @@ static int main_dump(int argc, char** argv)
         if (failed) die("Failed to write the cluster FASTQ files!");
     }
     lap("cluster fastq files written");
-    if (read_stats || pileup) {
+    if (read_stats || pileup || polish) {
         write_read_reports(b, outdir, stat_rows.size(), [&](size_t x) {
             const StatRow& r = stat_rows[x];
             return ReadStatRow{r.cls, r.strand, r.hb, size_t(r.he - r.hb), r.sb, size_t(r.se - r.sb), r.qb, size_t(r.qe - r.qb)};
-        }, read_stats, pileup);
-        lap(pileup ? (read_stats ? "read_stats.tsv, cluster_pileup.tsv (GPU alignments)" : "cluster_pileup.tsv (GPU alignments)") : "read_stats.tsv (GPU alignments)");
+        }, read_stats, pileup, polish ? polish_min_depth : 0);
+        const string reports = string(read_stats ? "read_stats.tsv, " : "") + (pileup ? "cluster_pileup.tsv, " : "") + (polish ? "cluster_polished.fq, " : "");
+        lap((reports.substr(0, reports.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;
     return 0;

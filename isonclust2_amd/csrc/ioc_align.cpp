@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "isonclust2_hip.h"
+#include "ioc_pile_call.h"
 
 namespace {
 
@@ -251,6 +252,63 @@ int ioc_host_ops_pileup(const char* ops, int64_t len, const char* query, int32_t
         }
     }
     return IOC_OK;
+}
+
+// What the 'I' bytes of one string insert (ioc_pileup_ins, isonclust2_hip.h), ADDED to ins[0 .. rlen]: the walk and the refusals
+// of ioc_host_ops_pileup.  The definition the ins variant of k_ops_pileup is tested against.
+int ioc_host_ops_pileup_ins(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, ioc_pileup_ins* ins)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || qlen < 0 || rlen < 0 || (qlen > 0 && !query) || !ins) return IOC_ERR_ARG;
+    int64_t q = 0, r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        q += op == '=' || op == 'X' || op == 'I' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (q != qlen || r != rlen) return IOC_ERR_ARG;
+    q = r = 0;
+    int64_t j = 0;  // the index of an 'I' in its run
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (op == 'I') {
+            if (j < IOC_PILE_INS_SLOTS)
+                ins[r].slot[j][PileAcc::channel(uint8_t(query[q]))] += 1;
+            else
+                ins[r].longer += 1;
+            ++j, ++q;
+            continue;
+        }
+        j = 0;
+        q += op == '=' || op == 'X' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    return IOC_OK;
+}
+
+// The consensus call of one reference from its two tables (isonclust2_hip.h has the rules; pile_call_row, ioc_pile_call.h, decides
+// a row for this function and for the kernels of ioc_pile_call.hip alike).
+int64_t ioc_host_pileup_call(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth,
+                             char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st)
+{
+    if (min_depth < 1 || rlen < 0 || !cols || !ins || (rlen > 0 && !frame)) return IOC_ERR_ARG;
+    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1);
+    if (cap < bound) return IOC_ERR_CAPACITY;
+    if (!out_seq || !out_qual) return IOC_ERR_ARG;
+    ioc_polish_stats s{};
+    int64_t at = 0;
+    for (int32_t p = 0; p <= rlen; ++p) {
+        const unsigned long long d_ins = p < rlen ? pile_depth(cols[p]) : rlen > 0 ? pile_depth(cols[rlen - 1]) : 0ull;
+        const PileRowCall row = pile_call_row(cols[p], ins[p], d_ins, p < rlen, p < rlen ? uint8_t(frame[p]) : uint8_t(0), min_depth);
+        for (uint32_t x = 0; x < row.n; ++x) {
+            out_seq[at] = char((row.seq >> (8u * x)) & 0xFFu);
+            out_qual[at++] = char((row.qual >> (8u * x)) & 0xFFu);
+        }
+        s.n_ins += int32_t(row.n_ins), s.n_sub += int32_t(row.n_sub), s.n_del += int32_t(row.n_del), s.n_low += int32_t(row.n_low);
+    }
+    s.out_len = int32_t(at);
+    if (st) *st = s;
+    return at;
 }
 
 // setGapOpen, src/cluster.cpp:425-440

@@ -1153,8 +1153,10 @@ struct AlnOpsHost {
     const int64_t* row_base = nullptr;
     uint8_t* piled = nullptr;
     double* ms_pileup = nullptr;  // k_ops_pileup's device time (IOC_TRACE)
+    // ioc_align_pairs_polish: a second table beside `pile`, of as many rows, carried the same way — what the pairs insert
+    ioc_pileup_ins* pile_ins = nullptr;  // (device)
     bool reduced() const { return stats || pile; }  // the bytes stay on the device
-    uint64_t pile_bytes() const { return pile ? uint64_t(pile_rows) * sizeof(ioc_pileup_col) : 0; }
+    uint64_t pile_bytes() const { return pile ? uint64_t(pile_rows) * (sizeof(ioc_pileup_col) + (pile_ins ? sizeof(ioc_pileup_ins) : 0)) : 0; }
 };
 
 // One run's side (version 2's, version 1's).  The pairs of a slice get consecutive regions of ONE device buffer, as large as the
@@ -1223,7 +1225,11 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
     if (h.stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
     IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
-    if (h.pile)
+    if (h.pile && h.pile_ins)
+        IOC_CHK(c, iock_ops_pileup_ins(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off,
+                                       static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), h.pile, h.pile_ins,
+                                       uint64_t(h.pile_rows)));
+    else if (h.pile)
         IOC_CHK(c, iock_ops_pileup(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off,
                                    static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), h.pile, uint64_t(h.pile_rows)));
     IOC_CHK(c, hipEventRecord(ev.v[2], c->stream));
@@ -2789,6 +2795,174 @@ int ioc_align_pairs_pileup(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
         fprintf(stderr, "[ioc]   aligner: pileup: %lld rows, %.3f MB (table, lengths%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms%s\n",
                 (long long)n_rows, double(copied) * 1e-6, out_stats ? ", statistics" : "", ms_copy, ms_pileup,
                 out_stats ? (", k_ops_stats " + std::to_string(ms_kernel) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+namespace {
+
+// the segments' bound: what ioc_host_pileup_call asks of cap, summed
+int64_t pile_call_bound(const std::vector<IocPileSeg>& segs)
+{
+    int64_t b = 0;
+    for (const IocPileSeg& s : segs) b += int64_t(s.rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(s.rlen) + 1);
+    return b;
+}
+
+// The call kernels over tables that lie on the device (n_rows records each), and what they made copied back: a_call holds
+// [segments][seg_len][out_off][records][sequence][qualities].  ms: the kernels' device time, ms_copy: the host's time over the
+// copies, copied: their bytes (all added to; the last two may be NULL).
+int pile_call_device(ioc_ctx* c, const std::vector<IocPileSeg>& segs, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins, int64_t n_rows,
+                     const uint8_t* d_frames, uint64_t frame_bytes, int32_t min_depth, char* out_seq, char* out_qual, int64_t* out_off,
+                     ioc_polish_stats* out_stats, double* ms, double* ms_copy, int64_t* copied)
+{
+    const size_t n = segs.size();
+    const size_t bound = size_t(pile_call_bound(segs));
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t o_seg = 0, o_len = up16(n * sizeof(IocPileSeg)), o_off = o_len + up16(n * 8), o_st = o_off + up16((n + 1) * 8),
+                 o_seq = o_st + n * sizeof(ioc_polish_stats), o_qual = o_seq + up16(bound), total = o_qual + up16(bound);
+    IOC_TRY(ioc_reserve(c, c->a_call, total));
+    uint8_t* p = static_cast<uint8_t*>(c->a_call.p);
+    IOC_CHK(c, hipMemcpyAsync(p + o_seg, segs.data(), n * sizeof(IocPileSeg), hipMemcpyHostToDevice, c->stream));
+    EventSet ev;
+    ev.v.assign(2, nullptr);
+    for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
+    IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
+    IOC_CHK(c, iock_pile_call(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_cols, d_ins, uint64_t(n_rows), d_frames,
+                              frame_bytes, min_depth, reinterpret_cast<int64_t*>(p + o_len), reinterpret_cast<ioc_polish_stats*>(p + o_st),
+                              reinterpret_cast<int64_t*>(p + o_off), p + o_seq, p + o_qual, uint64_t(bound)));
+    IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    IOC_CHK(c, hipMemcpy(out_off, p + o_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+    const int64_t len = out_off[n];
+    if (len < 0 || size_t(len) > bound) return ioc_fail(c, IOC_ERR_HIP, "the consensus call returned a length outside its bound");
+    if (out_stats) IOC_CHK(c, hipMemcpy(out_stats, p + o_st, n * sizeof(ioc_polish_stats), hipMemcpyDeviceToHost));
+    if (len > 0) {
+        IOC_CHK(c, hipMemcpy(out_seq, p + o_seq, size_t(len), hipMemcpyDeviceToHost));
+        IOC_CHK(c, hipMemcpy(out_qual, p + o_qual, size_t(len), hipMemcpyDeviceToHost));
+    }
+    float t = 0;
+    if (ms && hipEventElapsedTime(&t, ev.v[0], ev.v[1]) == hipSuccess) *ms += double(t);
+    if (ms_copy) *ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (copied) *copied += int64_t((n + 1) * 8 + (out_stats ? n * sizeof(ioc_polish_stats) : 0) + 2 * size_t(len));
+    return IOC_OK;
+}
+
+}  // namespace
+
+// The tables are uploaded and called where they lie then (ioc_pile_call.hip); the frames travel as one pool of bytes.
+int ioc_pileup_call(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
+                    const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                    ioc_polish_stats* out_stats)
+{
+    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !ins))) return IOC_ERR_ARG;
+    std::vector<IocPileSeg> segs(static_cast<size_t>(n_segs));
+    int64_t n_rows = 0, frame_bytes = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (rlen[g] < 0 || frame_off[g] < 0 || (rlen[g] > 0 && !frames)) return ioc_fail(c, IOC_ERR_ARG, "ioc_pileup_call: segment " + std::to_string(g) + " has a negative length or frame offset");
+        if (int64_t(rlen[g]) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen[g]) + 1) > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
+            return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_call: segment " + std::to_string(g) + " may call more than 2^31 - 1 bytes");
+        segs[size_t(g)] = IocPileSeg{n_rows, frame_off[g], rlen[g], 0};
+        n_rows += int64_t(rlen[g]) + 1;
+        frame_bytes = std::max(frame_bytes, frame_off[g] + rlen[g]);
+    }
+    const int64_t bound = pile_call_bound(segs);
+    if (cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_call: cap " + std::to_string(cap) + " below the bound " + std::to_string(bound));
+    if (bound > 0 && (!out_seq || !out_qual)) return IOC_ERR_ARG;
+    out_off[0] = 0;
+    if (n_segs == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
+    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
+    IOC_TRY(ioc_reserve(c, c->a_pile_ins, b_ins));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(frame_bytes)));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pile.p, cols, b_cols, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pile_ins.p, ins, b_ins, hipMemcpyHostToDevice, c->stream));
+    if (frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(frame_bytes), hipMemcpyHostToDevice, c->stream));
+    double ms = 0;
+    IOC_TRY(pile_call_device(c, segs, c->a_pile.as<ioc_pileup_col>(), c->a_pile_ins.as<ioc_pileup_ins>(), n_rows, static_cast<const uint8_t*>(d_frames.p),
+                             uint64_t(frame_bytes), min_depth, out_seq, out_qual, out_off, out_stats, &ms, nullptr, nullptr));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   consensus call: %d segments, %lld rows, %lld bytes called, k_pile_call %.3f ms\n", n_segs, (long long)n_rows,
+                (long long)out_off[n_segs], ms);
+    return IOC_OK;
+}
+
+// ioc_align_pairs_pileup with the second table beside the first, and the call kernels over both where they lie: what comes back
+// is the called bytes (at most 7 per row), not the tables, unless they are asked for.
+int ioc_align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                           int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
+                           char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
+                           ioc_pileup_ins* out_ins)
+{
+    if (!c || n_pairs < 0 || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_pairs > 0 && (!pairs || !seg_of_pair)) ||
+        (n_segs > 0 && (!segs || !out_polish)))
+        return IOC_ERR_ARG;
+    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
+    std::vector<IocPileSeg> ds(static_cast<size_t>(n_segs));
+    int64_t n_rows = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (segs[g].ref < 0 || segs[g].ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: segment " + std::to_string(g) + " refers to a sequence outside the pool");
+        const int64_t off = c->aln_offs[size_t(segs[g].ref)], m = c->aln_offs[size_t(segs[g].ref) + 1] - off;
+        ds[size_t(g)] = IocPileSeg{n_rows, off, int32_t(m), segs[g].ref_revcomp ? 1 : 0};
+        n_rows += m + 1;
+    }
+    std::vector<int64_t> row_base(size_t(n_pairs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        const ioc_aln_pair& a = pairs[i];
+        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
+        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: pair " + std::to_string(i) + " names no segment");
+        const int64_t m = c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)];
+        if (m != ds[size_t(seg_of_pair[i])].rlen)
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: the reference of pair " + std::to_string(i) + " is not as long as its segment's frame");
+        row_base[size_t(i)] = ds[size_t(seg_of_pair[i])].row0;
+    }
+    const int64_t bound = pile_call_bound(ds);
+    if (cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_polish: cap " + std::to_string(cap) + " below the bound " + std::to_string(bound));
+    if (bound > 0 && (!out_seq || !out_qual)) return IOC_ERR_ARG;
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    out_off[0] = 0;
+    if (n_segs == 0) return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
+    IOC_CHK(c, hipSetDevice(c->device));
+    const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
+    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
+    IOC_TRY(ioc_reserve(c, c->a_pile_ins, b_ins));
+    IOC_CHK(c, hipMemsetAsync(c->a_pile.p, 0, b_cols, c->stream));
+    IOC_CHK(c, hipMemsetAsync(c->a_pile_ins.p, 0, b_ins, c->stream));
+    std::vector<int64_t> len(size_t(n_pairs), 0);
+    std::vector<uint8_t> piled(size_t(n_pairs), 0);
+    double ms_copy = 0, ms_kernel = 0, ms_pileup = 0, ms_call = 0;
+    int64_t copied = 0, records = 0;
+    AlnOpsHost oh{nullptr, nullptr, len.data(), &ms_copy, &copied};
+    oh.stats = out_stats;
+    oh.ms_kernel = &ms_kernel;
+    oh.records = &records;
+    oh.pile = c->a_pile.as<ioc_pileup_col>();
+    oh.pile_ins = c->a_pile_ins.as<ioc_pileup_ins>();
+    oh.pile_rows = n_rows;
+    oh.row_base = row_base.data();
+    oh.piled = piled.data();
+    oh.ms_pileup = &ms_pileup;
+    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, n_pairs > 0 ? &oh : nullptr}, AlnRoute::normal);
+    if (r != IOC_OK) return r;
+    IOC_TRY(pile_call_device(c, ds, oh.pile, oh.pile_ins, n_rows, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), min_depth,
+                             out_seq, out_qual, out_off, out_polish, &ms_call, &ms_copy, &copied));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (out_cols) {
+        IOC_CHK(c, hipMemcpy(out_cols, c->a_pile.p, b_cols, hipMemcpyDeviceToHost));
+        copied += int64_t(b_cols);
+    }
+    if (out_ins) {
+        IOC_CHK(c, hipMemcpy(out_ins, c->a_pile_ins.p, b_ins, hipMemcpyDeviceToHost));
+        copied += int64_t(b_ins);
+    }
+    ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: polish: %d segments, %lld rows, %.3f MB (called bytes, records, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup<ins> %.3f ms, k_pile_call %.3f ms%s\n",
+                n_segs, (long long)n_rows, double(copied) * 1e-6, out_cols || out_ins ? ", tables" : "", out_stats ? ", statistics" : "", ms_copy,
+                ms_pileup, ms_call, out_stats ? (", k_ops_stats " + std::to_string(ms_kernel) + " ms").c_str() : "");
     return IOC_OK;
 }
 

@@ -5,7 +5,7 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
-#define IOC_PILE_HD __host__ __device__ __forceinline__
+#define IOC_PILE_HD __host__ __device__ inline __attribute__((always_inline))  // (__forceinline__, also where no HIP header came first)
 #else
 #define IOC_PILE_HD inline
 #endif
@@ -18,6 +18,7 @@ enum : uint32_t { PILE_A = 0, PILE_C, PILE_G, PILE_T, PILE_OTHER, PILE_DEL, PILE
 struct PileAcc {
     uint32_t r = 0, q = 0;  // reference / query bases consumed before this step
     bool open_i = false;    // the byte before this step is 'I'
+    uint32_t open_len = 0;  // (the ins variant, end_len) ... and the 'I's that end there: open_i is open_len != 0
     unsigned long long m_ref = 0, m_qry = 0, m_base = 0, m_del = 0, m_ins = 0;
 
     IOC_PILE_HD void begin(unsigned long long m_eq, unsigned long long m_x, unsigned long long m_i, unsigned long long m_d,
@@ -45,6 +46,20 @@ struct PileAcc {
     }
     // a maximal run of 'I' starts at lane l: the piece's first lane, unless the run came in from the step before
     IOC_PILE_HD bool run_start(uint32_t l) const { return ((m_ins & ~((m_ins << 1) | (open_i ? 1ull : 0ull))) >> l) & 1ull; }
+    // (the ins variant) the index of lane l's 'I' within its maximal run: the 'I's directly below the lane, and the run's length
+    // before this step where they reach down to the step's first byte
+    IOC_PILE_HD bool is_ins(uint32_t l) const { return (m_ins >> l) & 1ull; }
+    IOC_PILE_HD uint32_t ins_index(uint32_t l) const
+    {
+        const unsigned long long t = ~m_ins & below(l);  // the bytes below the lane that are no 'I'
+        return t ? l - (64u - uint32_t(__builtin_clzll(t))) : l + open_len;
+    }
+    // (the ins variant) called in front of end(): carries the length of a run that reaches the step's last byte
+    IOC_PILE_HD void end_len()
+    {
+        const unsigned long long t = ~m_ins;
+        open_len = t ? uint32_t(__builtin_clzll(t)) : open_len + 64u;  // (the ones at the top of m_ins)
+    }
     IOC_PILE_HD void end()
     {
         r += uint32_t(__builtin_popcountll(m_ref));

@@ -17,6 +17,7 @@
 // alignments that take a hundred.  profiles/align_pileup.txt has the measured rate.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "ioc_internal.h"
@@ -25,17 +26,21 @@
 namespace {
 
 constexpr int OP_WAVES = 4;  // pairs per workgroup (nothing is shared between them)
+constexpr uint32_t INS_WORDS = sizeof(ioc_pileup_ins) / 4, INS_LONGER = IOC_PILE_INS_SLOTS * 5;  // ioc_pileup_ins in words
 
 __device__ __forceinline__ void pile_add(uint32_t* word, uint32_t v)
 {
     (void)__hip_atomic_fetch_add(word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (result unused: the no-return form)
 }
 
+// INS: the variant of ioc_align_pairs_polish, which adds what the 'I' bytes insert into a second table as well (ioc_pileup_ins:
+// 32 words per row), one add per 'I' byte, by its index in its run and its query base.
+template <bool INS>
 __global__ void __launch_bounds__(64 * OP_WAVES)
 k_ops_pileup(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ end, const uint32_t* __restrict__ len,
              const uint32_t* __restrict__ room, const uint32_t* __restrict__ ord, uint32_t cnt, const int64_t* __restrict__ row_base,
              const uint32_t* __restrict__ q_off, const uint8_t* __restrict__ pool, uint64_t pool_bytes, uint32_t* __restrict__ cols,
-             uint64_t n_rows)
+             uint64_t n_rows, uint32_t* __restrict__ ins)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t x = blockIdx.x * OP_WAVES + (threadIdx.x >> 6);
@@ -78,7 +83,14 @@ k_ops_pileup(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ end, 
                     pile_add(rec + PILE_INS_BASES, piece);
                     if (acc.run_start(lane)) pile_add(rec + PILE_INS_RUNS, 1u);
                 }
+                if (INS && acc.is_ins(lane)) {
+                    const uint64_t at = qo + acc.qpos(lane);
+                    const uint32_t j = acc.ins_index(lane);
+                    if (at < pool_bytes)
+                        pile_add(ins + row * INS_WORDS + (j < uint32_t(IOC_PILE_INS_SLOTS) ? j * 5u + PileAcc::channel(pool[at]) : INS_LONGER), 1u);
+                }
             }
+            if (INS) acc.end_len();
             acc.end();
         }
         w = w_next;
@@ -97,7 +109,20 @@ hipError_t iock_ops_pileup(hipStream_t st, const uint8_t* buf, const uint64_t* e
                            uint64_t pool_bytes, ioc_pileup_col* cols, uint64_t n_rows)
 {
     if (cnt == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ops_pileup, dim3((cnt + OP_WAVES - 1) / OP_WAVES), dim3(64 * OP_WAVES), 0, st, buf, end, len, room, ord, cnt, row_base,
-                       q_off, pool, pool_bytes, reinterpret_cast<uint32_t*>(cols), n_rows);
+    hipLaunchKernelGGL(k_ops_pileup<false>, dim3((cnt + OP_WAVES - 1) / OP_WAVES), dim3(64 * OP_WAVES), 0, st, buf, end, len, room, ord, cnt,
+                       row_base, q_off, pool, pool_bytes, reinterpret_cast<uint32_t*>(cols), n_rows, static_cast<uint32_t*>(nullptr));
+    return hipGetLastError();
+}
+
+static_assert(sizeof(ioc_pileup_ins) == 128 && offsetof(ioc_pileup_ins, longer) == INS_LONGER * 4, "the second table is laid out as the public record");
+
+// ... and into `ins` (n_rows records) what they insert (ioc_host_ops_pileup_ins): the variant ioc_align_pairs_polish runs
+hipError_t iock_ops_pileup_ins(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room,
+                               const uint32_t* ord, uint32_t cnt, const int64_t* row_base, const uint32_t* q_off, const uint8_t* pool,
+                               uint64_t pool_bytes, ioc_pileup_col* cols, ioc_pileup_ins* ins, uint64_t n_rows)
+{
+    if (cnt == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ops_pileup<true>, dim3((cnt + OP_WAVES - 1) / OP_WAVES), dim3(64 * OP_WAVES), 0, st, buf, end, len, room, ord, cnt,
+                       row_base, q_off, pool, pool_bytes, reinterpret_cast<uint32_t*>(cols), n_rows, reinterpret_cast<uint32_t*>(ins));
     return hipGetLastError();
 }

@@ -1,0 +1,81 @@
+// ioc_pile_call.h — the decision of one row of a consensus call (ioc_host_pileup_call, isonclust2_hip.h), shared between the
+// definition on the host (ioc_align.cpp) and the call kernels (ioc_pile_call.hip): a lane decides a row with this function.
+// tools/pile_call_check.cpp drives it on the CPU under the sanitizers; the tests hold both against a restatement in Python.
+#pragma once
+
+#include <cstdint>
+
+#include "isonclust2_hip.h"
+#include "ioc_ops_pileup.h"
+
+// What a row emits: 0 to IOC_PILE_INS_SLOTS inserted bases and then 0 or 1 base of its own, byte x of `seq` / `qual` in bits
+// 8x .. 8x + 7 (qualities as written: 33 + q), and what it adds to the segment's record.
+struct PileRowCall {
+    unsigned long long seq = 0, qual = 0;
+    uint32_t n = 0;
+    uint32_t n_ins = 0, n_sub = 0, n_del = 0, n_low = 0;
+    IOC_PILE_HD void put(uint8_t base, uint32_t q)
+    {
+        seq |= (unsigned long long)base << (8u * n);
+        qual |= (unsigned long long)(33u + q) << (8u * n);
+        ++n;
+    }
+};
+
+#define IOC_PILE_CALL_CHUNK 256  // rows a workgroup of the call kernels takes per step (ioc_pile_call.hip)
+constexpr uint32_t PILE_CALL_MAX_ROW = IOC_PILE_INS_SLOTS + 1;  // bytes a row can emit
+
+IOC_PILE_HD unsigned long long pile_depth(const ioc_pileup_col& c)
+{
+    return (unsigned long long)c.a + c.c + c.g + c.t + c.other + c.del;
+}
+
+IOC_PILE_HD uint32_t pile_qual(unsigned long long most, unsigned long long depth)  // (depth > 0; most < 2^33: no overflow)
+{
+    const unsigned long long q = 40ull * most / depth;
+    return q < 40ull ? uint32_t(q) : 40u;
+}
+
+// Row p of a segment.  col / in: its records (col is not read where has_base is false and d_ins comes from the row before);
+// d_ins: the depth its insertions are held against; has_base: p < rlen, and then `frame` is frame[p].
+IOC_PILE_HD PileRowCall pile_call_row(const ioc_pileup_col& col, const ioc_pileup_ins& in, unsigned long long d_ins, bool has_base,
+                                      uint8_t frame, int32_t min_depth)
+{
+    const char letter[5] = {'A', 'C', 'G', 'T', 'N'};
+    PileRowCall out;
+    const unsigned long long need = (unsigned long long)min_depth;
+    if (d_ins >= need) {
+        for (uint32_t s = 0; s < uint32_t(IOC_PILE_INS_SLOTS); ++s) {
+            unsigned long long n = 0;
+            uint32_t most = 0, who = 0;
+            for (uint32_t ch = 0; ch < 5u; ++ch) {
+                const uint32_t v = in.slot[s][ch];
+                n += v;
+                if (v > most) most = v, who = ch;
+            }
+            if (!(2ull * n > d_ins)) break;
+            out.put(uint8_t(letter[who]), pile_qual(most, d_ins));
+            ++out.n_ins;
+        }
+    }
+    if (!has_base) return out;
+    const unsigned long long depth = pile_depth(col);
+    if (depth < need) {
+        out.put(frame, 0u);
+        ++out.n_low;
+        return out;
+    }
+    const uint32_t cnt[6] = {col.a, col.c, col.g, col.t, col.other, col.del};
+    uint32_t most = 0, who = 0;
+    for (uint32_t ch = 0; ch < 6u; ++ch)
+        if (cnt[ch] > most) most = cnt[ch], who = ch;
+    const uint32_t fch = PileAcc::channel(frame);
+    if (cnt[fch] == most) who = fch;
+    if (who == uint32_t(PILE_DEL)) {
+        ++out.n_del;
+        return out;
+    }
+    if (who != fch) ++out.n_sub;
+    out.put(who == fch ? frame : uint8_t(letter[who]), pile_qual(most, depth));
+    return out;
+}
