@@ -11,6 +11,9 @@ from . import _lib
 from ._lib import BatchView, ClusterStats, IocError, LeftView, Params, Timings
 
 MODE = {"sahlin": 0, "fast": 1, "furious": 2, "none": 3}
+TIE_SLOTS = 16                 # keys per query ioc_get_ties returns (IOC_TIE_SLOTS)
+CUT_NONE = 2 ** 31 - 1         # ioc_get_cuts of a query without a walk
+NO_VERDICT = -2 ** 31          # ioc_set_aln_verdicts: no verdict for this query
 
 
 def default_params(k=11, w=15, mode="fast"):
@@ -255,8 +258,37 @@ class Context:
         self._chk(self.L.ioc_get_decisions(self.h, _p(t, C.c_int32), _p(s, C.c_int8), _p(f, C.c_uint8)))
         return t, s, f
 
+    def cuts(self):
+        """ioc_get_cuts: per query int(top * MinFraction) of the last resolve, CUT_NONE where the query has no walk."""
+        cut = np.zeros(self.n, np.int32)
+        self._chk(self.L.ioc_get_cuts(self.h, _p(cut, C.c_int32)))
+        return cut
+
     def force_decision(self, q, target, strand=1):
         self._chk(self.L.ioc_force_decision(self.h, q, target, strand))
+
+    def clear_forced(self):
+        self._chk(self.L.ioc_clear_forced(self.h))
+
+    def set_aln_verdicts(self, target, strand=None):
+        """ioc_set_aln_verdicts: per query the alignment fallback's verdict — NO_VERDICT, -1 (open a cluster) or an earlier
+        target with its strand (+1 / -1) —, taken where the mapping walk finds nothing although top >= MinShared.  While
+        verdicts are set the resolve also collects the tie sets (ties()).  target None switches both off."""
+        if target is None:
+            self._chk(self.L.ioc_set_aln_verdicts(self.h, None, None))
+            return
+        target = np.ascontiguousarray(target, np.int32)
+        strand = np.ascontiguousarray(strand, np.int8)
+        if target.shape != (self.n,) or strand.shape != (self.n,):
+            raise ValueError("one verdict and one strand per query")
+        self._chk(self.L.ioc_set_aln_verdicts(self.h, _p(target, C.c_int32), _p(strand, C.c_int8)))
+
+    def ties(self):
+        """ioc_get_ties: (count uint32[n], keys uint32[n, TIE_SLOTS]) — per query the candidates tied at the top Size among the
+        clusters that exist, key = target << 1 | (strand == -1); of a longer tie set the count and TIE_SLOTS of its keys."""
+        count, keys = np.zeros(self.n, np.uint32), np.zeros((self.n, TIE_SLOTS), np.uint32)
+        self._chk(self.L.ioc_get_ties(self.h, _p(count, C.c_uint32), _p(keys, C.c_uint32)))
+        return count, keys
 
     def query_candidates(self, q, cap):
         t, s = np.zeros(cap, np.int32), np.zeros(cap, np.int8)

@@ -1026,7 +1026,8 @@ int ioc_set_aln_verdicts(ioc_ctx* c, const int32_t* target, const int8_t* strand
 }
 
 // Candidates tied at the top Size among the current clusters, per query, as of the last ioc_resolve
-// (only collected while verdicts are set): count[n], keys[n * 4] = target << 1 | (strand == -1).
+// (only collected while verdicts are set): count[n] (0 for a query without a walk: top < MinShared, or a forced
+// decision), keys[n * IOC_TIE_SLOTS] = target << 1 | (strand == -1).
 int ioc_get_ties(ioc_ctx* c, uint32_t* count, uint32_t* keys)
 {
     if (!c || !count || !keys) return IOC_ERR_ARG;

@@ -792,6 +792,7 @@ k_decide_pick(DecideArgs a)
             a.dec_target[j] = ft;
             a.dec_strand[j] = (ft < 0) ? 0 : a.forced_s[j];
             a.flags[j] = 0;
+            if (a.tie_count) a.tie_count[j] = 0u;  // (no walk, no tie set: not what an earlier resolve left in the slot)
             a.valid_out[j] = nv;
             a.done[j] = 1;
             if (nv != a.valid_in[j]) atomicMin(a.first_changed, uint32_t(j));
