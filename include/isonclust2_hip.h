@@ -360,6 +360,32 @@ typedef struct {
  * cap < rlen + IOC_PILE_INS_SLOTS * (rlen + 1). */
 int64_t ioc_host_pileup_call(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen,
                              int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st);
+/* ---- the quality-weighted pileup and call: every vote counts by the base quality of the read that casts it ----
+ * The weight of a quality byte b (as a FASTQ line has it): w(b) = 1 for b <= 34, else min(b - 33, 93) — the Phred value, at
+ * least 1, so that no base of a read is ever without a vote.  Integer weights: the sums are as reproducible as the counts. */
+uint32_t ioc_host_qual_weight(uint8_t b);
+/* The definition of the weighted pileup (the weighted variant of k_ops_pileup is tested against it): the walk of
+ * ioc_host_ops_pileup over a query with one quality byte per base (`qual`, qlen bytes).  The same inputs are refused with the
+ * tables untouched, and a NULL qual with qlen > 0.  ADDS to wcols[0 .. rlen] and, where wins is not NULL, to wins[0 .. rlen];
+ * the records are those of the counts, the counters hold sums of weights modulo 2^32.  '=' / 'X': the channel of query[q] in
+ * row r += w(qual[q]).  'D': del of row r += the smaller of w(qual[q - 1]) (where q > 0) and w(qual[q]) (where q < qlen), 1 if
+ * neither exists.  'I', the j-th byte of its maximal run: wins[r].slot[j][channel] += w(qual[q]) for j < IOC_PILE_INS_SLOTS,
+ * else wins[r].longer += w(qual[q]).  'i' / 'd' add nothing; ins_runs / ins_bases of wcols are not touched. */
+int ioc_host_ops_pileup_weighted(const char* ops, int64_t len, const char* query, const char* qual, int32_t qlen, int32_t rlen,
+                                 ioc_pileup_col* wcols, ioc_pileup_ins* wins);
+/* The definition of the weighted call.  `cols` (the counts) gates, the weights decide: Dc(p) = depth of cols[p], Dw(p) = the
+ * same sum of six counters of wcols[p], in 64 bits.  For p = 0 .. rlen:
+ *  - insertions in front of p: (Dc, Dw) of row p for p < rlen, of row rlen - 1 for p == rlen, (0, 0) for rlen == 0.  For
+ *    s = 0 .. 5 in turn, n = the sum of wins[p].slot[s]: the slots stop unless Dc >= min_depth, Dw > 0 and 2n > Dw; else the
+ *    first maximal channel of the slot in the order A C G T other ('N') is emitted with quality min(40, 40 max / Dw), n_ins;
+ *  - the base, for p < rlen: Dc(p) < min_depth or Dw(p) == 0: frame[p] with quality 0, n_low.  Else m = the largest of the six
+ *    counters of wcols[p]; the winner is the channel of frame[p] if its weight is m, else the first maximal one in the order
+ *    A C G T other del; emitted, counted and given its quality min(40, 40 m / Dw(p)) as in ioc_host_pileup_call.
+ * Capacity bound, refusals, the record and the 33 + q encoding as in ioc_host_pileup_call.  With every quality byte <= 34, or
+ * all of them equal, the weighted call is the majority call byte for byte. */
+int64_t ioc_host_pileup_call_weighted(const ioc_pileup_col* cols, const ioc_pileup_col* wcols, const ioc_pileup_ins* wins,
+                                      const char* frame, int32_t rlen, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
+                                      ioc_polish_stats* st);
 int32_t ioc_host_gap_open(double e1_plus_e2);                     /* setGapOpen,  src/cluster.cpp:425-440 */
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
@@ -450,6 +476,27 @@ int ioc_align_pairs_polish(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pa
                            ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair,
                            int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
                            ioc_polish_stats* out_polish, ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins);
+/* One quality byte per byte of the current pool, at the same offsets (n_bytes: the pool's total, else IOC_ERR_ARG): what
+ * ioc_align_pairs_polish_weighted weights the reads' votes by.  A NULL `quals` drops them; every ioc_align_set_pool drops them. */
+int ioc_align_set_pool_qual(ioc_ctx* ctx, const char* quals, int64_t n_bytes);
+/* ioc_pileup_call with the weighted decision (ioc_host_pileup_call_weighted per segment): `cols` gates, `wcols` / `wins` decide;
+ * all three are uploaded, rows as in ioc_pileup_call.  The same refusals, and a NULL wcols / wins with n_segs > 0. */
+int ioc_pileup_call_weighted(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                             const ioc_pileup_col* cols, const ioc_pileup_col* wcols, const ioc_pileup_ins* wins, int32_t min_depth,
+                             char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats);
+/* ioc_align_pairs_polish by weight: pair i is piled by the weighted variant of k_ops_pileup — the counts into a first table as
+ * ioc_align_pairs_polish piles them (bit-identical), the weights of ioc_host_ops_pileup_weighted, under the qualities of
+ * ioc_align_set_pool_qual, into two more — and the segments are called on the device as ioc_host_pileup_call_weighted defines.
+ * The tables come back only where asked for (out_cols, out_wcols, out_wins; each may be NULL).  An emitting call like the
+ * others: always exact, no verdict threshold, IOC_ALIGN_VARIANT=carry not honoured, all three device tables (192 bytes per
+ * row) counted against the checkpoint arena's budget, every pair added exactly once.  Refuses, with nothing written, what
+ * ioc_align_pairs_polish refuses, and with IOC_ERR_ARG a pool without qualities. */
+int ioc_align_pairs_polish_weighted(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
+                                    int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
+                                    double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
+                                    const int32_t* seg_of_pair, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
+                                    int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
+                                    ioc_pileup_col* out_wcols, ioc_pileup_ins* out_wins);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

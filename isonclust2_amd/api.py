@@ -145,6 +145,51 @@ def pileup_call(cols, ins, frame, min_depth=3, cap=None):
     return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in POLISH_STATS_FIELDS}
 
 
+def qual_weight(b):
+    """ioc_host_qual_weight: the weight a quality byte (0 .. 255, as a FASTQ line has it) gives its base in the weighted pileup —
+    1 for b <= 34, else min(b - 33, 93)."""
+    return int(_lib.load().ioc_host_qual_weight(int(b)))
+
+
+def ops_pileup_weighted(ops, query, qual, rlen, wcols=None, wins=None):
+    """ioc_host_ops_pileup_weighted: the pileup of one operation string by weight — `qual` one quality byte per base of `query`;
+    sums of qual_weight ADDED to `wcols` (PILEUP_DTYPE; ins_runs / ins_bases untouched) and `wins` (PILEUP_INS_DTYPE), rlen + 1
+    rows each, where given, else to zeros.  Returns (wcols, wins).  ValueError, with both untouched, for what ops_pileup refuses
+    and for a `qual` that is not as long as `query`."""
+    if wcols is None:
+        wcols = np.zeros(rlen + 1, PILEUP_DTYPE)
+    if wins is None:
+        wins = np.zeros(rlen + 1, PILEUP_INS_DTYPE)
+    if wcols.dtype != PILEUP_DTYPE or wcols.shape != (rlen + 1,) or not wcols.flags["C_CONTIGUOUS"]:
+        raise ValueError("wcols must be a contiguous array of rlen + 1 rows of PILEUP_DTYPE")
+    if wins.dtype != PILEUP_INS_DTYPE or wins.shape != (rlen + 1,) or not wins.flags["C_CONTIGUOUS"]:
+        raise ValueError("wins must be a contiguous array of rlen + 1 rows of PILEUP_INS_DTYPE")
+    if len(qual) != len(query):
+        raise ValueError("qual must hold one byte per base of query")
+    rc = _lib.load().ioc_host_ops_pileup_weighted(bytes(ops), len(ops), bytes(query), bytes(qual), len(query), int(rlen), wcols.ctypes.data,
+                                                  wins.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_pileup_weighted failed ({rc})")
+    return wcols, wins
+
+
+def pileup_call_weighted(cols, wcols, wins, frame, min_depth=3, cap=None):
+    """ioc_host_pileup_call_weighted: the call of one reference by weight — `cols` (the counts) for the depth gates, `wcols` and
+    `wins` (sums of weights) for everything else.  Returns what pileup_call returns."""
+    rlen = len(frame)
+    cols, wins = _tables(cols, wins, rlen + 1)
+    wcols = np.ascontiguousarray(wcols, PILEUP_DTYPE)
+    if wcols.shape != (rlen + 1,):
+        raise ValueError(f"wcols must hold {rlen + 1} rows")
+    cap = pileup_call_bound(rlen) if cap is None else int(cap)
+    seq, qual, st = C.create_string_buffer(max(cap, 1)), C.create_string_buffer(max(cap, 1)), _lib.PolishStats()
+    n = _lib.load().ioc_host_pileup_call_weighted(cols.ctypes.data, wcols.ctypes.data, wins.ctypes.data, bytes(frame), rlen, int(min_depth),
+                                                  seq, qual, cap, C.byref(st))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_pileup_call_weighted")
+    return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in POLISH_STATS_FIELDS}
+
+
 def ops_to_comp(ops):
     """The comparison string of an operation string: '|' where the bases are equal, ' ' in every other column."""
     return bytes(ops).translate(bytes(0x7C if b == 0x3D else 0x20 for b in range(256)))
@@ -358,6 +403,15 @@ class Context:
         self._chk(self.L.ioc_align_set_pool(self.h, len(seqs), blob, _p(offs, C.c_int64)))
         self._aln_pool_offs = offs
 
+    def align_set_pool_qual(self, quals):
+        """ioc_align_set_pool_qual: the quality lines (list of bytes, laid out like align_set_pool's sequences) of the current
+        pool, for align_pairs_polish_weighted; None drops them, as every align_set_pool does."""
+        if quals is None:
+            self._chk(self.L.ioc_align_set_pool_qual(self.h, None, 0))
+            return
+        blob = b"".join(bytes(x) for x in quals)
+        self._chk(self.L.ioc_align_set_pool_qual(self.h, blob, len(blob)))
+
     def align_pool_offsets(self):
         """Where the sequences of the last align_set_pool start (n + 1 offsets; empty pool: [0])."""
         return getattr(self, "_aln_pool_offs", np.zeros(1, np.int64))
@@ -484,6 +538,69 @@ class Context:
             out["stats"] = st
         if tables:
             out["cols"], out["ins"] = cols, ins
+            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
+        return out
+
+    def pileup_call_weighted(self, frames, cols, wcols, wins, min_depth=3, cap=None):
+        """ioc_pileup_call_weighted: pileup_call by weight, from host tables — `cols` gates, `wcols` / `wins` decide; each segment as
+        pileup_call_weighted (the function) defines it.  Returns what pileup_call returns."""
+        n = len(frames)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        n_rows = int(rlen.sum()) + n
+        cols, wins = _tables(cols, wins, n_rows)
+        wcols = np.ascontiguousarray(wcols, PILEUP_DTYPE)
+        if wcols.shape != (n_rows,):
+            raise ValueError(f"wcols must hold {n_rows} rows")
+        f_off = np.zeros(n + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        bound = sum(pileup_call_bound(r) for r in rlen)
+        cap = bound if cap is None else int(cap)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, st = np.zeros(n + 1, np.int64), np.zeros(n, POLISH_STATS_DTYPE)
+        self._chk(self.L.ioc_pileup_call_weighted(self.h, n, _p(rlen, C.c_int32), b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+                                                  cols.ctypes.data, wcols.ctypes.data, wins.ctypes.data, int(min_depth), seq.ctypes.data,
+                                                  qual.ctypes.data, cap, _p(off, C.c_int64), st.ctypes.data if n else None))
+        return ([seq[off[g]:off[g + 1]].tobytes() for g in range(n)], [qual[off[g]:off[g + 1]].tobytes() for g in range(n)], st)
+
+    def align_pairs_polish_weighted(self, pairs, k, segs, seg_of_pair, min_depth=3, stats=False, tables=False, cap=None, match=2,
+                                    mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_polish_weighted: align_pairs_polish with every vote weighted by the base quality of the read that casts
+        it (align_set_pool_qual first).  Returns the same dict; with tables=True `cols` (the counts, as align_pairs_polish has
+        them), `wcols` and `wins` (the sums of weights) and `row0`."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr = (_lib.PolishSeg * max(ns, 1))()
+        for g, (ref, rc) in enumerate(segs):
+            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair must hold one entry per pair")
+        offs = self.align_pool_offsets()
+        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
+        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
+        n_rows = sum(rlen) + ns
+        bound = sum(pileup_call_bound(r) for r in rlen)
+        cap = bound if cap is None else int(cap)
+        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, pol = np.zeros(ns + 1, np.int64), np.zeros(ns, POLISH_STATS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        wcols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        wins = np.zeros(n_rows, PILEUP_INS_DTYPE) if tables else None
+        give = tables and n_rows
+        self._chk(self.L.ioc_align_pairs_polish_weighted(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32),
+                                                         _p(win, C.c_int64), _p(ratio, C.c_double), st.ctypes.data if stats and n else None,
+                                                         ns, sarr, _p(sop, C.c_int32), int(min_depth), seq.ctypes.data, qual.ctypes.data, cap,
+                                                         _p(off, C.c_int64), pol.ctypes.data if ns else None,
+                                                         cols.ctypes.data if give else None, wcols.ctypes.data if give else None,
+                                                         wins.ctypes.data if give else None))
+        out = {"score": score, "windows": win, "ratio": ratio, "polish": pol,
+               "seq": [seq[off[g]:off[g + 1]].tobytes() for g in range(ns)], "qual": [qual[off[g]:off[g + 1]].tobytes() for g in range(ns)]}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out["cols"], out["wcols"], out["wins"] = cols, wcols, wins
             out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
         return out
 

@@ -955,6 +955,10 @@ static int main_cluster(int argc, char** argv)
 // device, only the sequences come back), header "@cluster_<id> reads=<pairs> subs= dels= ins= low=".  A cluster without a row of
 // clusters.tsv keeps its representative, with '!' qualities.  Beside the other options a group is still aligned once: the
 // polish call returns the statistics and the first table as well.
+//
+// dump --polish --polish-weighted: the same records, order and frames, called by weight (ioc_align_pairs_polish_weighted): every
+// read votes with the base qualities of its line as cluster_fastq/<id>.fq has it (reversed with the read when its strand is
+// -1), the pool's qualities being the lines e is computed from already.  The header gains a last field " weighted=1".
 struct ReadStatRow {
     unsigned cls;
     int strand;
@@ -966,7 +970,7 @@ struct ReadStatRow {
     size_t qual_len;
 };
 static void write_read_reports(const Batch& b, const string& outdir, size_t n_rows, const std::function<ReadStatRow(size_t)>& row, bool want_stats,
-                               bool want_pileup, int polish_min_depth /* 0: no --polish */)
+                               bool want_pileup, int polish_min_depth /* 0: no --polish */, bool polish_weighted)
 {
     const bool want_polish = polish_min_depth > 0, want_groups = want_pileup || want_polish;
     constexpr size_t POOL_MAX = size_t(256) << 20;
@@ -1041,7 +1045,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             }
             text = "@cluster_" + std::to_string(group_cls[x].first) + " reads=" + std::to_string(g < 0 ? 0 : seg_reads[size_t(g)]) +
                    " subs=" + std::to_string(z.n_sub) + " dels=" + std::to_string(z.n_del) + " ins=" + std::to_string(z.n_ins) +
-                   " low=" + std::to_string(z.n_low) + "\n" + seq + "\n+\n" + qual + "\n";
+                   " low=" + std::to_string(z.n_low) + (polish_weighted ? " weighted=1" : "") + "\n" + seq + "\n+\n" + qual + "\n";
             polish_out.write(text.data(), std::streamsize(text.size()));
         }
     };
@@ -1089,10 +1093,21 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             pol_seq.assign(size_t(cap), '\0'), pol_qual.assign(size_t(cap), '\0');
             pol_off.assign(segs.size() + 1, 0), pol.assign(segs.size(), ioc_polish_stats{});
             if (want_pileup) cols.assign(size_t(group_rows), ioc_pileup_col{});
-            check(c, ioc_align_pairs_polish(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
-                                            int32_t(segs.size()), segs.data(), seg_of_pair.data(), polish_min_depth, &pol_seq[0], &pol_qual[0], cap,
-                                            pol_off.data(), pol.data(), want_pileup ? cols.data() : nullptr, nullptr),
-                  "polished consensus");
+            if (polish_weighted) {
+                // (the quality lines lie in `quals` in the order and at the lengths of the sequences in `pool`)
+                if (qoffs != offs) die("--polish-weighted: a quality line is not as long as its sequence!");
+                check(c, ioc_align_set_pool_qual(c, quals.data(), int64_t(quals.size())), "pool qualities");
+                check(c, ioc_align_pairs_polish_weighted(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr,
+                                                         want_stats ? st.data() : nullptr, int32_t(segs.size()), segs.data(), seg_of_pair.data(),
+                                                         polish_min_depth, &pol_seq[0], &pol_qual[0], cap, pol_off.data(), pol.data(),
+                                                         want_pileup ? cols.data() : nullptr, nullptr, nullptr),
+                      "weighted polished consensus");
+            } else {
+                check(c, ioc_align_pairs_polish(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
+                                                int32_t(segs.size()), segs.data(), seg_of_pair.data(), polish_min_depth, &pol_seq[0], &pol_qual[0], cap,
+                                                pol_off.data(), pol.data(), want_pileup ? cols.data() : nullptr, nullptr),
+                      "polished consensus");
+            }
             write_groups();
         } else if (want_pileup) {
             cols.assign(size_t(group_rows), ioc_pileup_col{});
@@ -1183,12 +1198,14 @@ static int main_dump(int argc, char** argv)
     static const struct option lo[] = {{"verbose", no_argument, 0, 'v'}, {"debug", no_argument, 0, 'd'}, {"help", no_argument, 0, 'h'},
                                        {"outdir", required_argument, 0, 'o'}, {"index", required_argument, 0, 'i'},
                                        {"read-stats", no_argument, 0, 1000}, {"pileup", no_argument, 0, 1001},
-                                       {"polish", no_argument, 0, 1002}, {"polish-min-depth", required_argument, 0, 1003}, {0, 0, 0, 0}};
+                                       {"polish", no_argument, 0, 1002}, {"polish-min-depth", required_argument, 0, 1003},
+                                       {"polish-weighted", no_argument, 0, 1004}, {0, 0, 0, 0}};
     string outdir, index;
     bool read_stats = false;  // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
     bool pileup = false;      // --pileup: cluster_pileup.tsv, the same alignments piled onto the representative position by position
     bool polish = false;      // --polish: cluster_polished.fq, every representative called anew from both pileup tables of its reads
     int polish_min_depth = 3;  // --polish-min-depth: positions covered by fewer reads keep the representative's base
+    bool polish_weighted = false;  // --polish-weighted: the call of --polish with every read's vote weighted by its base quality
     int o;
     while ((o = getopt_long(argc, argv, "dhvo:i:", lo, nullptr)) != -1) {
         switch (o) {
@@ -1199,8 +1216,9 @@ static int main_dump(int argc, char** argv)
             case 1001: pileup = true; break;
             case 1002: polish = true; break;
             case 1003: polish_min_depth = atoi(optarg); break;
+            case 1004: polish_weighted = true; break;
             case 'h':
-                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N]] final.cer" << endl
+                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N] [--polish-weighted]] final.cer" << endl
                      << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
                      << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
                      << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -1208,7 +1226,9 @@ static int main_dump(int argc, char** argv)
                      << "  --polish       also write outdir/cluster_polished.fq: one record per record of cluster_cons.fq, the majority call over the" << endl
                      << "                 cluster's reads aligned against it — substitutions, deletions and insertions of up to 6 bases (GPU);" << endl
                      << "                 header: reads, and how many positions were substituted, deleted, inserted or left as they were" << endl
-                     << "  --polish-min-depth N   positions covered by fewer than N reads keep the representative's base, quality '!' (default 3)" << endl;
+                     << "  --polish-min-depth N   positions covered by fewer than N reads keep the representative's base, quality '!' (default 3)" << endl
+                     << "  --polish-weighted      with --polish: every read votes with its base qualities (Phred, 1 .. 93) instead of 1, so that" << endl
+                     << "                 a few confident reads outvote many doubtful ones; min-depth still counts reads; header: weighted=1" << endl;
                 exit(0);
             default: break;
         }
@@ -1216,6 +1236,7 @@ static int main_dump(int argc, char** argv)
     if (optind >= argc) die("No input batch specified!");
     if (outdir.empty()) die("Specifying output directory is mandatory!");
     if (polish && polish_min_depth < 1) die("--polish-min-depth must be at least 1!");
+    if (polish_weighted && !polish) die("--polish-weighted asks for --polish!");
     if (index.empty()) die("Specifying the sorted read index is mandatory!");
     Batch b;
     string err, fastq;
@@ -1387,7 +1408,7 @@ static int main_dump(int argc, char** argv)
         write_read_reports(b, outdir, stat_rows.size(), [&](size_t x) {
             const StatRow& r = stat_rows[x];
             return ReadStatRow{r.cls, r.strand, r.hb, size_t(r.he - r.hb), r.sb, size_t(r.se - r.sb), r.qb, size_t(r.qe - r.qb)};
-        }, read_stats, pileup, polish ? polish_min_depth : 0);
+        }, read_stats, pileup, polish ? polish_min_depth : 0, polish_weighted);
         const string reports = string(read_stats ? "read_stats.tsv, " : "") + (pileup ? "cluster_pileup.tsv, " : "") + (polish ? "cluster_polished.fq, " : "");
         lap((reports.substr(0, reports.size() - 2) + " (GPU alignments)").c_str());
     }

@@ -311,6 +311,89 @@ int64_t ioc_host_pileup_call(const ioc_pileup_col* cols, const ioc_pileup_ins* i
     return at;
 }
 
+// The weight a quality byte gives its base in the weighted pileup: the Phred value it writes, at least 1 and at most 93.
+uint32_t ioc_host_qual_weight(uint8_t b) { return pile_qual_weight(b); }
+
+// The weighted pileup of one operation string (isonclust2_hip.h has the rules): the walk and the refusals of ioc_host_ops_pileup,
+// sums of weights ADDED to wcols[0 .. rlen] and, where wins is given, to wins[0 .. rlen].  The definition the weighted variant of
+// k_ops_pileup is tested against.
+int ioc_host_ops_pileup_weighted(const char* ops, int64_t len, const char* query, const char* qual, int32_t qlen, int32_t rlen,
+                                 ioc_pileup_col* wcols, ioc_pileup_ins* wins)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || qlen < 0 || rlen < 0 || (qlen > 0 && (!query || !qual)) || !wcols) return IOC_ERR_ARG;
+    int64_t q = 0, r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        q += op == '=' || op == 'X' || op == 'I' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (q != qlen || r != rlen) return IOC_ERR_ARG;
+    q = r = 0;
+    int64_t j = 0;  // the index of an 'I' in its run
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (op == 'I') {
+            const uint32_t w = pile_qual_weight(uint8_t(qual[q]));
+            if (wins && j < IOC_PILE_INS_SLOTS)
+                wins[r].slot[j][PileAcc::channel(uint8_t(query[q]))] += w;
+            else if (wins)
+                wins[r].longer += w;
+            ++j, ++q;
+            continue;
+        }
+        j = 0;
+        switch (op) {
+        case 'd': ++r; break;
+        case 'i': ++q; break;
+        case 'D': {
+            const uint32_t wa = q > 0 ? pile_qual_weight(uint8_t(qual[q - 1])) : 0u, wb = q < qlen ? pile_qual_weight(uint8_t(qual[q])) : 0u;
+            wcols[r++].del += wa == 0u ? (wb == 0u ? 1u : wb) : wb == 0u ? wa : std::min(wa, wb);
+            break;
+        }
+        default: {  // ('=' 'X')
+            ioc_pileup_col& c = wcols[r++];
+            const uint32_t w = pile_qual_weight(uint8_t(qual[q]));
+            switch (query[q++]) {
+            case 'A': c.a += w; break;
+            case 'C': c.c += w; break;
+            case 'G': c.g += w; break;
+            case 'T': c.t += w; break;
+            default: c.other += w; break;
+            }
+        }
+        }
+    }
+    return IOC_OK;
+}
+
+// The weighted consensus call of one reference: the depths of the table of counts gate, the tables of weights decide
+// (pile_call_row with both gates, as the weighted mode of the kernels of ioc_pile_call.hip has it).
+int64_t ioc_host_pileup_call_weighted(const ioc_pileup_col* cols, const ioc_pileup_col* wcols, const ioc_pileup_ins* wins, const char* frame,
+                                      int32_t rlen, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st)
+{
+    if (min_depth < 1 || rlen < 0 || !cols || !wcols || !wins || (rlen > 0 && !frame)) return IOC_ERR_ARG;
+    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1);
+    if (cap < bound) return IOC_ERR_CAPACITY;
+    if (!out_seq || !out_qual) return IOC_ERR_ARG;
+    ioc_polish_stats s{};
+    int64_t at = 0;
+    for (int32_t p = 0; p <= rlen; ++p) {
+        const int32_t pi = p < rlen ? p : rlen - 1;  // the row the insertions in front of p are held against
+        const unsigned long long dw_ins = pi >= 0 ? pile_depth(wcols[pi]) : 0ull, dc_ins = pi >= 0 ? pile_depth(cols[pi]) : 0ull;
+        const PileRowCall row = pile_call_row(wcols[p], wins[p], dw_ins, p < rlen, p < rlen ? uint8_t(frame[p]) : uint8_t(0), min_depth, dc_ins,
+                                              p < rlen ? pile_depth(cols[p]) : 0ull);
+        for (uint32_t x = 0; x < row.n; ++x) {
+            out_seq[at] = char((row.seq >> (8u * x)) & 0xFFu);
+            out_qual[at++] = char((row.qual >> (8u * x)) & 0xFFu);
+        }
+        s.n_ins += int32_t(row.n_ins), s.n_sub += int32_t(row.n_sub), s.n_del += int32_t(row.n_del), s.n_low += int32_t(row.n_low);
+    }
+    s.out_len = int32_t(at);
+    if (st) *st = s;
+    return at;
+}
+
 // setGapOpen, src/cluster.cpp:425-440
 int32_t ioc_host_gap_open(double e)
 {

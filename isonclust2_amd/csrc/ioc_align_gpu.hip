@@ -1155,8 +1155,16 @@ struct AlnOpsHost {
     double* ms_pileup = nullptr;  // k_ops_pileup's device time (IOC_TRACE)
     // ioc_align_pairs_polish: a second table beside `pile`, of as many rows, carried the same way — what the pairs insert
     ioc_pileup_ins* pile_ins = nullptr;  // (device)
+    // ioc_align_pairs_polish_weighted: beside `pile` (and no pile_ins), two tables of as many rows for the sums of weights
+    ioc_pileup_col* pile_wcols = nullptr;  // (device)
+    ioc_pileup_ins* pile_wins = nullptr;   // (device)
     bool reduced() const { return stats || pile; }  // the bytes stay on the device
-    uint64_t pile_bytes() const { return pile ? uint64_t(pile_rows) * (sizeof(ioc_pileup_col) + (pile_ins ? sizeof(ioc_pileup_ins) : 0)) : 0; }
+    uint64_t pile_bytes() const
+    {
+        return pile ? uint64_t(pile_rows) * (sizeof(ioc_pileup_col) + (pile_ins ? sizeof(ioc_pileup_ins) : 0) +
+                                             (pile_wcols ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins) : 0))
+                    : 0;
+    }
 };
 
 // One run's side (version 2's, version 1's).  The pairs of a slice get consecutive regions of ONE device buffer, as large as the
@@ -1176,15 +1184,18 @@ struct OpsRun {
     std::vector<uint32_t> q_off;       // ... and where its query starts in the pool
     const int64_t* d_row_base = nullptr;
     const uint32_t* d_q_off = nullptr;
+    std::vector<uint32_t> q_len;  // (weighted pileup) per device pair: its query's length
+    const uint32_t* d_q_len = nullptr;
 };
 
 // the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled).  A statistics call:
 // [end][len][room per pair][the bytes][4 spare bytes: k_ops_stats reads the dword that holds a string's last byte whole]; a
-// pileup call: [end][len][room][first row][query offset per pair][the bytes][4 spare bytes].
+// pileup call: [end][len][room][first row][query offset per pair][the bytes][4 spare bytes], a weighted one with [query length
+// per pair] behind the query offsets.
 int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vector<AlnPairDev>& dp)
 {
-    const bool st = o.host->reduced(), pile = o.host->pile != nullptr;
-    const size_t np = o.end.size(), tab = (np * (pile ? 28 : st ? 16 : 12) + 15) & ~size_t(15);
+    const bool st = o.host->reduced(), pile = o.host->pile != nullptr, weighted = o.host->pile_wcols != nullptr;
+    const size_t np = o.end.size(), tab = (np * (weighted ? 32 : pile ? 28 : st ? 16 : 12) + 15) & ~size_t(15);
     const int r = ioc_reserve(c, c->a_ops, tab + size_t(max_slice_bytes) + (st ? 4 : 0));
     if (r != IOC_OK) return r;
     uint8_t* p = static_cast<uint8_t*>(c->a_ops.p);
@@ -1208,6 +1219,12 @@ int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vect
         IOC_CHK(c, hipMemcpyAsync(p + np * 16, o.row_base.data(), np * 8, hipMemcpyHostToDevice, c->stream));
         IOC_CHK(c, hipMemcpyAsync(p + np * 24, o.q_off.data(), np * 4, hipMemcpyHostToDevice, c->stream));
     }
+    if (weighted) {
+        o.q_len.resize(np);
+        for (size_t x = 0; x < np; ++x) o.q_len[x] = dp[x].n;
+        o.d_q_len = reinterpret_cast<const uint32_t*>(p + np * 28);
+        IOC_CHK(c, hipMemcpyAsync(p + np * 28, o.q_len.data(), np * 4, hipMemcpyHostToDevice, c->stream));
+    }
     return IOC_OK;
 }
 
@@ -1225,7 +1242,11 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
     if (h.stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
     IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
-    if (h.pile && h.pile_ins)
+    if (h.pile && h.pile_wcols)
+        IOC_CHK(c, iock_ops_pileup_weighted(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_q_len,
+                                            static_cast<const uint8_t*>(c->a_pool.p), static_cast<const uint8_t*>(c->a_qual.p),
+                                            uint64_t(c->aln_offs.back()), h.pile, h.pile_wcols, h.pile_wins, uint64_t(h.pile_rows)));
+    else if (h.pile && h.pile_ins)
         IOC_CHK(c, iock_ops_pileup_ins(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off,
                                        static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), h.pile, h.pile_ins,
                                        uint64_t(h.pile_rows)));
@@ -2647,6 +2668,7 @@ int ioc_align_set_pool(ioc_ctx* c, int32_t n_seqs, const char* seqs, const int64
     if (!c || n_seqs < 0 || (n_seqs > 0 && (!seqs || !offs))) return IOC_ERR_ARG;
     IOC_CHK(c, hipSetDevice(c->device));
     c->res_pool_ready = false;
+    c->aln_qual_set = false;
     c->aln_offs.assign(offs, offs + (n_seqs > 0 ? n_seqs + 1 : 0));
     if (n_seqs == 0) return IOC_OK;
     if (offs[0] != 0) return ioc_fail(c, IOC_ERR_ARG, "sequence pool offsets must start at 0");
@@ -2668,6 +2690,21 @@ int ioc_align_set_pool(ioc_ctx* c, int32_t n_seqs, const char* seqs, const int64
     c->aln_other.assign(size_t(n_seqs), 0);
     IOC_CHK(c, hipMemcpyAsync(c->aln_other.data(), d_flags, size_t(n_seqs), hipMemcpyDeviceToHost, c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
+    return IOC_OK;
+}
+
+int ioc_align_set_pool_qual(ioc_ctx* c, const char* quals, int64_t n_bytes)
+{
+    if (!c) return IOC_ERR_ARG;
+    c->aln_qual_set = false;
+    if (!quals) return IOC_OK;
+    const int64_t total = c->aln_offs.empty() ? 0 : c->aln_offs.back();
+    if (n_bytes != total) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_set_pool_qual: " + std::to_string(n_bytes) + " quality bytes for a pool of " + std::to_string(total));
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_qual, size_t(total)));
+    if (total > 0) IOC_CHK(c, hipMemcpyAsync(c->a_qual.p, quals, size_t(total), hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    c->aln_qual_set = true;
     return IOC_OK;
 }
 
@@ -2811,7 +2848,8 @@ int64_t pile_call_bound(const std::vector<IocPileSeg>& segs)
 // The call kernels over tables that lie on the device (n_rows records each), and what they made copied back: a_call holds
 // [segments][seg_len][out_off][records][sequence][qualities].  ms: the kernels' device time, ms_copy: the host's time over the
 // copies, copied: their bytes (all added to; the last two may be NULL).
-int pile_call_device(ioc_ctx* c, const std::vector<IocPileSeg>& segs, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins, int64_t n_rows,
+int pile_call_device(ioc_ctx* c, const std::vector<IocPileSeg>& segs, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
+                     const ioc_pileup_col* d_gate /* the weighted call: d_cols / d_ins are weights, this the counts; else NULL */, int64_t n_rows,
                      const uint8_t* d_frames, uint64_t frame_bytes, int32_t min_depth, char* out_seq, char* out_qual, int64_t* out_off,
                      ioc_polish_stats* out_stats, double* ms, double* ms_copy, int64_t* copied)
 {
@@ -2827,9 +2865,15 @@ int pile_call_device(ioc_ctx* c, const std::vector<IocPileSeg>& segs, const ioc_
     ev.v.assign(2, nullptr);
     for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
-    IOC_CHK(c, iock_pile_call(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_cols, d_ins, uint64_t(n_rows), d_frames,
-                              frame_bytes, min_depth, reinterpret_cast<int64_t*>(p + o_len), reinterpret_cast<ioc_polish_stats*>(p + o_st),
-                              reinterpret_cast<int64_t*>(p + o_off), p + o_seq, p + o_qual, uint64_t(bound)));
+    if (d_gate)
+        IOC_CHK(c, iock_pile_call_weighted(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_gate, d_cols, d_ins,
+                                           uint64_t(n_rows), d_frames, frame_bytes, min_depth, reinterpret_cast<int64_t*>(p + o_len),
+                                           reinterpret_cast<ioc_polish_stats*>(p + o_st), reinterpret_cast<int64_t*>(p + o_off), p + o_seq,
+                                           p + o_qual, uint64_t(bound)));
+    else
+        IOC_CHK(c, iock_pile_call(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_cols, d_ins, uint64_t(n_rows), d_frames,
+                                  frame_bytes, min_depth, reinterpret_cast<int64_t*>(p + o_len), reinterpret_cast<ioc_polish_stats*>(p + o_st),
+                                  reinterpret_cast<int64_t*>(p + o_off), p + o_seq, p + o_qual, uint64_t(bound)));
     IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
@@ -2848,14 +2892,12 @@ int pile_call_device(ioc_ctx* c, const std::vector<IocPileSeg>& segs, const ioc_
     return IOC_OK;
 }
 
-}  // namespace
-
+// ioc_pileup_call (wcols NULL: cols / ins are called by majority) and ioc_pileup_call_weighted (cols gates, wcols / ins decide).
 // The tables are uploaded and called where they lie then (ioc_pile_call.hip); the frames travel as one pool of bytes.
-int ioc_pileup_call(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
-                    const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
-                    ioc_polish_stats* out_stats)
+int pileup_call_tables(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
+                       const ioc_pileup_col* wcols, const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
+                       int64_t* out_off, ioc_polish_stats* out_stats)
 {
-    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !ins))) return IOC_ERR_ARG;
     std::vector<IocPileSeg> segs(static_cast<size_t>(n_segs));
     int64_t n_rows = 0, frame_bytes = 0;
     for (int32_t g = 0; g < n_segs; ++g) {
@@ -2879,27 +2921,55 @@ int ioc_pileup_call(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char*
     IOC_TRY(ioc_alloc(c, d_frames, size_t(frame_bytes)));
     IOC_CHK(c, hipMemcpyAsync(c->a_pile.p, cols, b_cols, hipMemcpyHostToDevice, c->stream));
     IOC_CHK(c, hipMemcpyAsync(c->a_pile_ins.p, ins, b_ins, hipMemcpyHostToDevice, c->stream));
+    if (wcols) {
+        IOC_TRY(ioc_reserve(c, c->a_pile_w, b_cols));
+        IOC_CHK(c, hipMemcpyAsync(c->a_pile_w.p, wcols, b_cols, hipMemcpyHostToDevice, c->stream));
+    }
     if (frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(frame_bytes), hipMemcpyHostToDevice, c->stream));
     double ms = 0;
-    IOC_TRY(pile_call_device(c, segs, c->a_pile.as<ioc_pileup_col>(), c->a_pile_ins.as<ioc_pileup_ins>(), n_rows, static_cast<const uint8_t*>(d_frames.p),
+    IOC_TRY(pile_call_device(c, segs, wcols ? c->a_pile_w.as<ioc_pileup_col>() : c->a_pile.as<ioc_pileup_col>(), c->a_pile_ins.as<ioc_pileup_ins>(),
+                             wcols ? c->a_pile.as<ioc_pileup_col>() : nullptr, n_rows, static_cast<const uint8_t*>(d_frames.p),
                              uint64_t(frame_bytes), min_depth, out_seq, out_qual, out_off, out_stats, &ms, nullptr, nullptr));
     if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   consensus call: %d segments, %lld rows, %lld bytes called, k_pile_call %.3f ms\n", n_segs, (long long)n_rows,
-                (long long)out_off[n_segs], ms);
+        fprintf(stderr, "[ioc]   consensus call: %d segments, %lld rows, %lld bytes called, k_pile_call%s %.3f ms\n", n_segs, (long long)n_rows,
+                (long long)out_off[n_segs], wcols ? "<weighted>" : "", ms);
     return IOC_OK;
 }
 
+}  // namespace
+
+int ioc_pileup_call(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
+                    const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                    ioc_polish_stats* out_stats)
+{
+    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !ins))) return IOC_ERR_ARG;
+    return pileup_call_tables(c, n_segs, rlen, frames, frame_off, cols, nullptr, ins, min_depth, out_seq, out_qual, cap, out_off, out_stats);
+}
+
+int ioc_pileup_call_weighted(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                             const ioc_pileup_col* cols, const ioc_pileup_col* wcols, const ioc_pileup_ins* wins, int32_t min_depth, char* out_seq,
+                             char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats)
+{
+    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !wcols || !wins))) return IOC_ERR_ARG;
+    return pileup_call_tables(c, n_segs, rlen, frames, frame_off, cols, wcols, wins, min_depth, out_seq, out_qual, cap, out_off, out_stats);
+}
+
+namespace {
+
 // ioc_align_pairs_pileup with the second table beside the first, and the call kernels over both where they lie: what comes back
-// is the called bytes (at most 7 per row), not the tables, unless they are asked for.
-int ioc_align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
-                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
-                           int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
-                           char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
-                           ioc_pileup_ins* out_ins)
+// is the called bytes (at most 7 per row), not the tables, unless they are asked for.  weighted (ioc_align_pairs_polish_weighted):
+// the weighted variant of k_ops_pileup adds the counts into the first table and the weights into two tables of a_pile_w, [wcols]
+// [wins], and the call is the weighted one; out_ins is then out_wins.
+int align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                       int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                       int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
+                       char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
+                       ioc_pileup_ins* out_ins, bool weighted, ioc_pileup_col* out_wcols)
 {
     if (!c || n_pairs < 0 || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_pairs > 0 && (!pairs || !seg_of_pair)) ||
         (n_segs > 0 && (!segs || !out_polish)))
         return IOC_ERR_ARG;
+    if (weighted && !c->aln_qual_set) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish_weighted: no qualities are set for the current pool (ioc_align_set_pool_qual)");
     const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
     std::vector<IocPileSeg> ds(static_cast<size_t>(n_segs));
     int64_t n_rows = 0;
@@ -2927,10 +2997,12 @@ int ioc_align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
     if (n_segs == 0) return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
     IOC_CHK(c, hipSetDevice(c->device));
     const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
+    DevBuf& second = weighted ? c->a_pile_w : c->a_pile_ins;  // [ins], or [wcols][wins]
+    const size_t b_second = weighted ? b_cols + b_ins : b_ins;
     IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
-    IOC_TRY(ioc_reserve(c, c->a_pile_ins, b_ins));
+    IOC_TRY(ioc_reserve(c, second, b_second));
     IOC_CHK(c, hipMemsetAsync(c->a_pile.p, 0, b_cols, c->stream));
-    IOC_CHK(c, hipMemsetAsync(c->a_pile_ins.p, 0, b_ins, c->stream));
+    IOC_CHK(c, hipMemsetAsync(second.p, 0, b_second, c->stream));
     std::vector<int64_t> len(size_t(n_pairs), 0);
     std::vector<uint8_t> piled(size_t(n_pairs), 0);
     double ms_copy = 0, ms_kernel = 0, ms_pileup = 0, ms_call = 0;
@@ -2940,30 +3012,62 @@ int ioc_align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
     oh.ms_kernel = &ms_kernel;
     oh.records = &records;
     oh.pile = c->a_pile.as<ioc_pileup_col>();
-    oh.pile_ins = c->a_pile_ins.as<ioc_pileup_ins>();
+    if (weighted) {
+        oh.pile_wcols = second.as<ioc_pileup_col>();
+        oh.pile_wins = reinterpret_cast<ioc_pileup_ins*>(static_cast<uint8_t*>(second.p) + b_cols);  // (b_cols: a multiple of 32)
+    } else {
+        oh.pile_ins = second.as<ioc_pileup_ins>();
+    }
     oh.pile_rows = n_rows;
     oh.row_base = row_base.data();
     oh.piled = piled.data();
     oh.ms_pileup = &ms_pileup;
     const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, n_pairs > 0 ? &oh : nullptr}, AlnRoute::normal);
     if (r != IOC_OK) return r;
-    IOC_TRY(pile_call_device(c, ds, oh.pile, oh.pile_ins, n_rows, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), min_depth,
-                             out_seq, out_qual, out_off, out_polish, &ms_call, &ms_copy, &copied));
+    IOC_TRY(pile_call_device(c, ds, weighted ? oh.pile_wcols : oh.pile, weighted ? oh.pile_wins : oh.pile_ins, weighted ? oh.pile : nullptr, n_rows,
+                             static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), min_depth, out_seq, out_qual, out_off, out_polish,
+                             &ms_call, &ms_copy, &copied));
     const auto t0 = std::chrono::steady_clock::now();
     if (out_cols) {
         IOC_CHK(c, hipMemcpy(out_cols, c->a_pile.p, b_cols, hipMemcpyDeviceToHost));
         copied += int64_t(b_cols);
     }
+    if (out_wcols) {
+        IOC_CHK(c, hipMemcpy(out_wcols, oh.pile_wcols, b_cols, hipMemcpyDeviceToHost));
+        copied += int64_t(b_cols);
+    }
     if (out_ins) {
-        IOC_CHK(c, hipMemcpy(out_ins, c->a_pile_ins.p, b_ins, hipMemcpyDeviceToHost));
+        IOC_CHK(c, hipMemcpy(out_ins, weighted ? oh.pile_wins : oh.pile_ins, b_ins, hipMemcpyDeviceToHost));
         copied += int64_t(b_ins);
     }
     ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: polish: %d segments, %lld rows, %.3f MB (called bytes, records, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup<ins> %.3f ms, k_pile_call %.3f ms%s\n",
-                n_segs, (long long)n_rows, double(copied) * 1e-6, out_cols || out_ins ? ", tables" : "", out_stats ? ", statistics" : "", ms_copy,
-                ms_pileup, ms_call, out_stats ? (", k_ops_stats " + std::to_string(ms_kernel) + " ms").c_str() : "");
+        fprintf(stderr, "[ioc]   aligner: polish: %d segments, %lld rows, %.3f MB (called bytes, records, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup<%s> %.3f ms, k_pile_call%s %.3f ms%s\n",
+                n_segs, (long long)n_rows, double(copied) * 1e-6, out_cols || out_ins || out_wcols ? ", tables" : "", out_stats ? ", statistics" : "", ms_copy,
+                weighted ? "weighted" : "ins", ms_pileup, weighted ? "<weighted>" : "", ms_call, out_stats ? (", k_ops_stats " + std::to_string(ms_kernel) + " ms").c_str() : "");
     return IOC_OK;
+}
+
+}  // namespace
+
+int ioc_align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                           int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
+                           char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
+                           ioc_pileup_ins* out_ins)
+{
+    return align_pairs_polish(c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs,
+                              seg_of_pair, min_depth, out_seq, out_qual, cap, out_off, out_polish, out_cols, out_ins, false, nullptr);
+}
+
+int ioc_align_pairs_polish_weighted(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                    int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                    int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
+                                    char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
+                                    ioc_pileup_col* out_wcols, ioc_pileup_ins* out_wins)
+{
+    return align_pairs_polish(c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs,
+                              seg_of_pair, min_depth, out_seq, out_qual, cap, out_off, out_polish, out_cols, out_wins, true, out_wcols);
 }
 
 // (ioc_ctx_prewarm)

@@ -208,6 +208,10 @@ struct ioc_ctx {
     DevBuf a_ostats;  // ioc_align_pairs_stats: the records of a slice (k_ops_stats)
     DevBuf a_pile_ins;  // ioc_align_pairs_polish: the second table, what the reads insert (the ins variant of k_ops_pileup)
     DevBuf a_call;      // ioc_pileup_call, ioc_align_pairs_polish: segments, offsets, records and the called bytes (ioc_pile_call.hip)
+    DevBuf a_pile_w;    // ioc_align_pairs_polish_weighted: the tables of weights, [wcols][wins] of the call's rows (ioc_pileup_call_weighted: wcols
+                        // alone, wins where ioc_pileup_call has ins)
+    DevBuf a_qual;      // ioc_align_set_pool_qual: one quality byte per byte of a_pool ...
+    bool aln_qual_set = false;  // ... which it holds for the current pool
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
@@ -323,6 +327,13 @@ hipError_t iock_ops_pileup_ins(hipStream_t st, const uint8_t* buf, const uint64_
                                const uint32_t* ord, uint32_t cnt, const int64_t* row_base, const uint32_t* q_off, const uint8_t* pool,
                                uint64_t pool_bytes, ioc_pileup_col* cols, ioc_pileup_ins* ins, uint64_t n_rows);
 
+// ... and the weights of the same events into wcols / wins (ioc_host_ops_pileup_weighted): the variant of
+// ioc_align_pairs_polish_weighted; q_len[pid]: the pair's query length, quals: one quality byte per byte of the pool
+hipError_t iock_ops_pileup_weighted(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room,
+                                    const uint32_t* ord, uint32_t cnt, const int64_t* row_base, const uint32_t* q_off, const uint32_t* q_len,
+                                    const uint8_t* pool, const uint8_t* quals, uint64_t pool_bytes, ioc_pileup_col* cols,
+                                    ioc_pileup_col* wcols, ioc_pileup_ins* wins, uint64_t n_rows);
+
 // ioc_pile_call.hip: the consensus call (ioc_host_pileup_call) of many references from device tables.  A segment: rlen + 1 rows
 // of both tables from row0 on, its frame rlen bytes at f_off of a pool of sequences, read reverse-complemented where rc is set.
 struct IocPileSeg {
@@ -332,6 +343,12 @@ struct IocPileSeg {
 hipError_t iock_pile_call(hipStream_t st, const IocPileSeg* segs, uint32_t n_segs, const ioc_pileup_col* cols, const ioc_pileup_ins* ins,
                           uint64_t n_rows, const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth, int64_t* seg_len,
                           ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);
+
+// ... by weight (ioc_host_pileup_call_weighted): cols gates, wcols / wins decide
+hipError_t iock_pile_call_weighted(hipStream_t st, const IocPileSeg* segs, uint32_t n_segs, const ioc_pileup_col* cols, const ioc_pileup_col* wcols,
+                                   const ioc_pileup_ins* wins, uint64_t n_rows, const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth,
+                                   int64_t* seg_len, ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual,
+                                   uint64_t out_bytes);
 
 // ioc_capi.cpp: queries whose minimizer arrays are already in HBM (ioc_batch_view::minimizers_on_device)
 extern "C" int ioc_queries_upload_devmins(ioc_ctx* c, int32_t n, const int64_t* off_fwd, const int64_t* off_rev, const uint32_t* d_min_val,

@@ -1,5 +1,6 @@
 // ioc_ops_pileup.h — the step logic of k_ops_pileup (ioc_ops_pileup.hip), callable on the host as well: tools/pileup_acc_check.cpp
-// drives it over strings on the CPU, under the sanitizers, against the definition (ioc_host_ops_pileup).
+// drives it over strings on the CPU, under the sanitizers, against the definition (ioc_host_ops_pileup), tools/pile_weight_check.cpp
+// the weights of the weighted variant against ioc_host_ops_pileup_weighted.
 #pragma once
 
 #include <cstdint>
@@ -12,6 +13,9 @@
 
 // the channels of a row as words of ioc_pileup_col
 enum : uint32_t { PILE_A = 0, PILE_C, PILE_G, PILE_T, PILE_OTHER, PILE_DEL, PILE_INS_RUNS, PILE_INS_BASES, PILE_WORDS };
+
+// the weight of a quality byte in the weighted pileup (ioc_host_qual_weight): 1 .. 93, never 0
+IOC_PILE_HD uint32_t pile_qual_weight(uint8_t b) { return b <= 34u ? 1u : b - 33u < 93u ? b - 33u : 93u; }
 
 // Where a wave stands in its string; one step per 64 bytes, bit l of a mask = the l-th of them (bytes outside the string are 0
 // in every mask).  The members are the same in every lane (the masks are ballots); what differs per lane is the argument l.
@@ -36,6 +40,15 @@ struct PileAcc {
     IOC_PILE_HD uint32_t qpos(uint32_t l) const { return q + uint32_t(__builtin_popcountll(m_qry & below(l))); }
     IOC_PILE_HD bool is_base(uint32_t l) const { return (m_base >> l) & 1ull; }
     IOC_PILE_HD bool is_del(uint32_t l) const { return (m_del >> l) & 1ull; }
+    // (the weighted variant) the weight of a 'D' lane: the smaller of the weights of the query bases on its two sides, q - 1 and
+    // q of the qlen bases whose quality bytes stand at `qual`, where they exist; 1 where neither does
+    IOC_PILE_HD uint32_t del_weight(uint32_t l, uint32_t qlen, const uint8_t* qual) const
+    {
+        const uint32_t at = qpos(l);
+        const uint32_t a = at > 0u && at - 1u < qlen ? pile_qual_weight(qual[at - 1u]) : 0u;
+        const uint32_t b = at < qlen ? pile_qual_weight(qual[at]) : 0u;
+        return a == 0u ? (b == 0u ? 1u : b) : b == 0u || a < b ? a : b;
+    }
     // The 'I' bytes of a step are added piece by piece — a piece: consecutive 'I's within the step, all in front of one row — by
     // the lane of the piece's first byte: its length, 0 for every other lane.  One add per piece, not one per byte on one address.
     IOC_PILE_HD uint32_t ins_piece(uint32_t l) const

@@ -1,6 +1,7 @@
 // ioc_pile_call.h — the decision of one row of a consensus call (ioc_host_pileup_call, isonclust2_hip.h), shared between the
 // definition on the host (ioc_align.cpp) and the call kernels (ioc_pile_call.hip): a lane decides a row with this function.
-// tools/pile_call_check.cpp drives it on the CPU under the sanitizers; the tests hold both against a restatement in Python.
+// tools/pile_call_check.cpp and tools/pile_weight_check.cpp drive it on the CPU under the sanitizers; the tests hold both against a
+// restatement in Python.
 #pragma once
 
 #include <cstdint>
@@ -37,14 +38,17 @@ IOC_PILE_HD uint32_t pile_qual(unsigned long long most, unsigned long long depth
 }
 
 // Row p of a segment.  col / in: its records (col is not read where has_base is false and d_ins comes from the row before);
-// d_ins: the depth its insertions are held against; has_base: p < rlen, and then `frame` is frame[p].
+// d_ins: the depth its insertions are held against; has_base: p < rlen, and then `frame` is frame[p].  The two gates: c_ins and
+// c_base are the depths that min_depth is held against, of the insertions and of the row's own base.  The majority call passes
+// d_ins and the depth of col; the weighted call (ioc_host_pileup_call_weighted) decides on tables of weights and passes the
+// depths of the table of counts, and a row whose weights sum to 0 is then as good as not covered.
 IOC_PILE_HD PileRowCall pile_call_row(const ioc_pileup_col& col, const ioc_pileup_ins& in, unsigned long long d_ins, bool has_base,
-                                      uint8_t frame, int32_t min_depth)
+                                      uint8_t frame, int32_t min_depth, unsigned long long c_ins, unsigned long long c_base)
 {
     const char letter[5] = {'A', 'C', 'G', 'T', 'N'};
     PileRowCall out;
     const unsigned long long need = (unsigned long long)min_depth;
-    if (d_ins >= need) {
+    if (c_ins >= need && d_ins > 0ull) {
         for (uint32_t s = 0; s < uint32_t(IOC_PILE_INS_SLOTS); ++s) {
             unsigned long long n = 0;
             uint32_t most = 0, who = 0;
@@ -60,7 +64,7 @@ IOC_PILE_HD PileRowCall pile_call_row(const ioc_pileup_col& col, const ioc_pileu
     }
     if (!has_base) return out;
     const unsigned long long depth = pile_depth(col);
-    if (depth < need) {
+    if (c_base < need || depth == 0ull) {
         out.put(frame, 0u);
         ++out.n_low;
         return out;
@@ -78,4 +82,11 @@ IOC_PILE_HD PileRowCall pile_call_row(const ioc_pileup_col& col, const ioc_pileu
     if (who != fch) ++out.n_sub;
     out.put(who == fch ? frame : uint8_t(letter[who]), pile_qual(most, depth));
     return out;
+}
+
+// the majority call's row: one table, which is its own gate
+IOC_PILE_HD PileRowCall pile_call_row(const ioc_pileup_col& col, const ioc_pileup_ins& in, unsigned long long d_ins, bool has_base,
+                                      uint8_t frame, int32_t min_depth)
+{
+    return pile_call_row(col, in, d_ins, has_base, frame, min_depth, d_ins, has_base ? pile_depth(col) : 0ull);
 }

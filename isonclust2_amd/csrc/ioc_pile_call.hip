@@ -6,6 +6,8 @@
 // walks it in chunks of IOC_PILE_CALL_CHUNK rows, a lane per row: the lane decides its row (pile_call_row, ioc_pile_call.h — the
 // function the definition uses) and holds the 0 to 7 bytes it emits, sequence and qualities, in two 64-bit registers.
 //
+//   (each of the two passes in two modes: the majority call, and the weighted call of ioc_host_pileup_call_weighted, which
+//   decides on the tables of weights and reads the table of counts for the depth gates only — 32 bytes more per row)
 //   k_pile_call<false>  counts: per lane the bytes and the record's counters over the segment's chunks, summed over the workgroup
 //                       at the end: seg_len[g] and the 32-byte record.
 //   k_pile_scan         one wave: out_off[0 .. n_segs] = the exclusive scan of seg_len, 64 segments a step, a running carry.
@@ -62,9 +64,12 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     return v;
 }
 
-// row p of segment s (p <= s.rlen), or nothing where its records or its frame byte lie outside what was passed
+// row p of segment s (p <= s.rlen), or nothing where its records or its frame byte lie outside what was passed.  WEIGHTED
+// (ioc_host_pileup_call_weighted): cols / ins are the tables of weights, which decide, and `gate` is the table of counts, whose
+// depths min_depth is held against (n_rows records like the others); the majority call does not read `gate`.
+template <bool WEIGHTED>
 __device__ __forceinline__ PileRowCall decide(const IocPileSeg& s, uint32_t p, const ioc_pileup_col* __restrict__ cols,
-                                              const ioc_pileup_ins* __restrict__ ins, uint64_t n_rows,
+                                              const ioc_pileup_ins* __restrict__ ins, const ioc_pileup_col* __restrict__ gate, uint64_t n_rows,
                                               const uint8_t* __restrict__ frames, uint64_t frame_bytes, int32_t min_depth)
 {
     const uint32_t rlen = uint32_t(s.rlen);
@@ -78,14 +83,16 @@ __device__ __forceinline__ PileRowCall decide(const IocPileSeg& s, uint32_t p, c
         fb = s.rc ? comp_base(frames[at]) : frames[at];
     }
     const unsigned long long d_ins = has_base ? pile_depth(cols[row]) : rlen > 0u ? pile_depth(cols[row - 1u]) : 0ull;
-    return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth);
+    if (!WEIGHTED) return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth);
+    const unsigned long long c_ins = has_base ? pile_depth(gate[row]) : rlen > 0u ? pile_depth(gate[row - 1u]) : 0ull;
+    return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth, c_ins, has_base ? pile_depth(gate[row]) : 0ull);
 }
 
-template <bool EMIT>
+template <bool EMIT, bool WEIGHTED>
 __global__ void __launch_bounds__(CHUNK)
 k_pile_call(const IocPileSeg* __restrict__ segs, uint32_t n_segs, const ioc_pileup_col* __restrict__ cols,
-            const ioc_pileup_ins* __restrict__ ins, uint64_t n_rows, const uint8_t* __restrict__ frames, uint64_t frame_bytes,
-            int32_t min_depth, long long* __restrict__ seg_len, ioc_polish_stats* __restrict__ stats,
+            const ioc_pileup_ins* __restrict__ ins, const ioc_pileup_col* __restrict__ gate, uint64_t n_rows,
+            const uint8_t* __restrict__ frames, uint64_t frame_bytes, int32_t min_depth, long long* __restrict__ seg_len, ioc_polish_stats* __restrict__ stats,
             const long long* __restrict__ out_off, uint8_t* __restrict__ out_seq, uint8_t* __restrict__ out_qual, uint64_t out_bytes)
 {
     __shared__ uint32_t part[2][WAVES * 5u];
@@ -100,7 +107,7 @@ k_pile_call(const IocPileSeg* __restrict__ segs, uint32_t n_segs, const ioc_pile
         for (uint32_t c = 0; c < nchunks; ++c) {
             const uint32_t p = c * CHUNK + tid;
             if (p >= rows) break;
-            const PileRowCall r = decide(s, p, cols, ins, n_rows, frames, frame_bytes, min_depth);
+            const PileRowCall r = decide<WEIGHTED>(s, p, cols, ins, gate, n_rows, frames, frame_bytes, min_depth);
             n += r.n, k_ins += r.n_ins, k_sub += r.n_sub, k_del += r.n_del, k_low += r.n_low;
         }
         // (the bytes of a segment, at most 7 per row, fit 32 bits like the record's out_len: the entries refuse longer segments)
@@ -124,7 +131,7 @@ k_pile_call(const IocPileSeg* __restrict__ segs, uint32_t n_segs, const ioc_pile
     for (uint32_t c = 0; c < nchunks; ++c) {  // (every lane of the workgroup takes every step: there are barriers in it)
         const uint32_t p = c * CHUNK + tid;
         PileRowCall r{};
-        if (p < rows) r = decide(s, p, cols, ins, n_rows, frames, frame_bytes, min_depth);
+        if (p < rows) r = decide<WEIGHTED>(s, p, cols, ins, gate, n_rows, frames, frame_bytes, min_depth);
         const uint32_t incl = wave_scan_incl(r.n, lane);
         uint32_t* tot = part[c & 1u];  // (two sets: a wave may be a step ahead of another one's reads)
         if (lane == 63u) tot[wave] = incl;
@@ -165,6 +172,24 @@ k_pile_scan(const long long* __restrict__ seg_len, uint32_t n_segs, long long* _
     }
 }
 
+template <bool WEIGHTED>
+hipError_t pile_call_launch(hipStream_t st, const IocPileSeg* segs, uint32_t n_segs, const ioc_pileup_col* cols, const ioc_pileup_ins* ins,
+                            const ioc_pileup_col* gate, uint64_t n_rows, const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth,
+                            int64_t* seg_len, ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets");
+    if (n_segs == 0) return hipSuccess;
+    hipLaunchKernelGGL((k_pile_call<false, WEIGHTED>), dim3(n_segs), dim3(CHUNK), 0, st, segs, n_segs, cols, ins, gate, n_rows, frames, frame_bytes,
+                       min_depth, reinterpret_cast<long long*>(seg_len), stats, static_cast<const long long*>(nullptr),
+                       static_cast<uint8_t*>(nullptr), static_cast<uint8_t*>(nullptr), uint64_t(0));
+    hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(64), 0, st, reinterpret_cast<const long long*>(seg_len), n_segs,
+                       reinterpret_cast<long long*>(out_off));
+    hipLaunchKernelGGL((k_pile_call<true, WEIGHTED>), dim3(n_segs), dim3(CHUNK), 0, st, segs, n_segs, cols, ins, gate, n_rows, frames, frame_bytes,
+                       min_depth, static_cast<long long*>(nullptr), static_cast<ioc_polish_stats*>(nullptr),
+                       reinterpret_cast<const long long*>(out_off), out_seq, out_qual, out_bytes);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 // The segments segs[0 .. n_segs) (device) are called from `cols` / `ins` (n_rows records each) and the frames at `frames`
@@ -174,15 +199,16 @@ hipError_t iock_pile_call(hipStream_t st, const IocPileSeg* segs, uint32_t n_seg
                           uint64_t n_rows, const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth, int64_t* seg_len,
                           ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes)
 {
-    static_assert(sizeof(long long) == sizeof(int64_t), "offsets");
-    if (n_segs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pile_call<false>, dim3(n_segs), dim3(CHUNK), 0, st, segs, n_segs, cols, ins, n_rows, frames, frame_bytes, min_depth,
-                       reinterpret_cast<long long*>(seg_len), stats, static_cast<const long long*>(nullptr), static_cast<uint8_t*>(nullptr),
-                       static_cast<uint8_t*>(nullptr), uint64_t(0));
-    hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(64), 0, st, reinterpret_cast<const long long*>(seg_len), n_segs,
-                       reinterpret_cast<long long*>(out_off));
-    hipLaunchKernelGGL(k_pile_call<true>, dim3(n_segs), dim3(CHUNK), 0, st, segs, n_segs, cols, ins, n_rows, frames, frame_bytes, min_depth,
-                       static_cast<long long*>(nullptr), static_cast<ioc_polish_stats*>(nullptr), reinterpret_cast<const long long*>(out_off),
-                       out_seq, out_qual, out_bytes);
-    return hipGetLastError();
+    return pile_call_launch<false>(st, segs, n_segs, cols, ins, nullptr, n_rows, frames, frame_bytes, min_depth, seg_len, stats, out_off, out_seq,
+                                   out_qual, out_bytes);
+}
+
+// ... by weight (ioc_host_pileup_call_weighted): `cols` (the counts) gates, wcols / wins decide
+hipError_t iock_pile_call_weighted(hipStream_t st, const IocPileSeg* segs, uint32_t n_segs, const ioc_pileup_col* cols, const ioc_pileup_col* wcols,
+                                   const ioc_pileup_ins* wins, uint64_t n_rows, const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth,
+                                   int64_t* seg_len, ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual,
+                                   uint64_t out_bytes)
+{
+    return pile_call_launch<true>(st, segs, n_segs, wcols, wins, cols, n_rows, frames, frame_bytes, min_depth, seg_len, stats, out_off, out_seq,
+                                  out_qual, out_bytes);
 }
