@@ -429,15 +429,19 @@ class Context:
             arr[i].reserved = int(pr[4]) if len(pr) > 4 else 0
         return arr
 
+    @staticmethod
+    def _aln_out(n):
+        """the (score, windows, ratio) arrays of n pairs, and the three pointers an aligning call takes"""
+        out = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        return out, (_p(out[0], C.c_int32), _p(out[1], C.c_int64), _p(out[2], C.c_double))
+
     def align_pairs(self, pairs, k, match=2, mismatch=-2, gap_extend=1):
         """ParasailAlign + getAlnRatio (src/cluster.cpp:408-459) for (query, ref, ref_revcomp, e[, hint]) tuples:
         returns (score, qualifying windows, ratio) arrays."""
         n = len(pairs)
-        arr = self._aln_pairs(pairs)
-        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
-        self._chk(self.L.ioc_align_pairs(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32),
-                                         _p(win, C.c_int64), _p(ratio, C.c_double)))
-        return score, win, ratio
+        out, ptrs = self._aln_out(n)
+        self._chk(self.L.ioc_align_pairs(self.h, n, self._aln_pairs(pairs), k, match, mismatch, gap_extend, *ptrs))
+        return out
 
     def align_pairs_ops(self, pairs, k, match=2, mismatch=-2, gap_extend=1):
         """ioc_align_pairs_ops: align_pairs plus the alignments themselves — returns (score, windows, ratio, [bytes per pair]),
@@ -445,23 +449,21 @@ class Context:
         n = len(pairs)
         arr = self._aln_pairs(pairs)
         bound = self._chk(self.L.ioc_align_ops_bound(self.h, n, arr))
-        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        out, ptrs = self._aln_out(n)
         ops, off = np.zeros(max(bound, 1), np.uint8), np.zeros(n + 1, np.int64)
-        self._chk(self.L.ioc_align_pairs_ops(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
-                                             _p(ratio, C.c_double), ops.ctypes.data, bound, _p(off, C.c_int64)))
-        return score, win, ratio, [ops[off[i]:off[i + 1]].tobytes() for i in range(n)]
+        self._chk(self.L.ioc_align_pairs_ops(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, ops.ctypes.data, bound, _p(off, C.c_int64)))
+        return (*out, [ops[off[i]:off[i + 1]].tobytes() for i in range(n)])
 
     def align_pairs_stats(self, pairs, k, match=2, mismatch=-2, gap_extend=1):
         """ioc_align_pairs_stats: align_pairs plus the statistics of the alignments (ops_stats of what align_pairs_ops returns),
         counted on the device — returns (score, windows, ratio, stats), stats a structured array (ALN_STATS_DTYPE).  Always exact
         counts (the verdict threshold is not applied)."""
         n = len(pairs)
-        arr = self._aln_pairs(pairs)
-        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        out, ptrs = self._aln_out(n)
         stats = np.zeros(n, ALN_STATS_DTYPE)
-        self._chk(self.L.ioc_align_pairs_stats(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
-                                               _p(ratio, C.c_double), stats.ctypes.data if n else None))
-        return score, win, ratio, stats
+        self._chk(self.L.ioc_align_pairs_stats(self.h, n, self._aln_pairs(pairs), k, match, mismatch, gap_extend, *ptrs,
+                                               stats.ctypes.data if n else None))
+        return (*out, stats)
 
     def align_pairs_pileup(self, pairs, k, row_base, n_rows, stats=False, match=2, mismatch=-2, gap_extend=1):
         """ioc_align_pairs_pileup: align_pairs plus the pileup of the alignments on their references, added up on the device —
@@ -473,32 +475,82 @@ class Context:
         row_base = np.ascontiguousarray(row_base, np.int64)
         if row_base.shape != (n,):
             raise ValueError("row_base must hold one entry per pair")
-        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        out, ptrs = self._aln_out(n)
         cols = np.zeros(max(int(n_rows), 0), PILEUP_DTYPE)
         st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        self._chk(self.L.ioc_align_pairs_pileup(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
-                                                _p(ratio, C.c_double), st.ctypes.data if stats and n else None, _p(row_base, C.c_int64),
-                                                int(n_rows), cols.ctypes.data))
-        return (score, win, ratio, cols, st) if stats else (score, win, ratio, cols)
+        self._chk(self.L.ioc_align_pairs_pileup(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None,
+                                                _p(row_base, C.c_int64), int(n_rows), cols.ctypes.data))
+        return (*out, cols, st) if stats else (*out, cols)
 
-    def pileup_call(self, frames, cols, ins, min_depth=3, cap=None):
-        """ioc_pileup_call: the consensus call of many references at once on the device, from host tables — `frames` a list of
-        bytes, segment g's len(frames[g]) + 1 rows of cols / ins following those of the earlier segments.  Returns
-        ([sequence per segment], [qualities per segment], stats), stats an array of POLISH_STATS_DTYPE; each segment as
-        pileup_call defines it."""
+    def _pileup_call(self, weighted, frames, cols, wcols, ins, min_depth, cap):
+        """pileup_call (ins: what the reads insert) and pileup_call_weighted (wcols; ins: wins)"""
         n = len(frames)
         rlen = np.array([len(f) for f in frames], np.int32)
-        cols, ins = _tables(cols, ins, int(rlen.sum()) + n)
+        n_rows = int(rlen.sum()) + n
+        cols, ins = _tables(cols, ins, n_rows)
+        if weighted:
+            wcols = np.ascontiguousarray(wcols, PILEUP_DTYPE)
+            if wcols.shape != (n_rows,):
+                raise ValueError(f"wcols must hold {n_rows} rows")
         f_off = np.zeros(n + 1, np.int64)
         np.cumsum(rlen, out=f_off[1:])
         bound = sum(pileup_call_bound(r) for r in rlen)
         cap = bound if cap is None else int(cap)
         seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
         off, st = np.zeros(n + 1, np.int64), np.zeros(n, POLISH_STATS_DTYPE)
-        self._chk(self.L.ioc_pileup_call(self.h, n, _p(rlen, C.c_int32), b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
-                                         cols.ctypes.data, ins.ctypes.data, int(min_depth), seq.ctypes.data, qual.ctypes.data, cap,
-                                         _p(off, C.c_int64), st.ctypes.data if n else None))
+        fn = self.L.ioc_pileup_call_weighted if weighted else self.L.ioc_pileup_call
+        tables = (cols.ctypes.data, wcols.ctypes.data, ins.ctypes.data) if weighted else (cols.ctypes.data, ins.ctypes.data)
+        self._chk(fn(self.h, n, _p(rlen, C.c_int32), b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64), *tables, int(min_depth),
+                     seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64), st.ctypes.data if n else None))
         return ([seq[off[g]:off[g + 1]].tobytes() for g in range(n)], [qual[off[g]:off[g + 1]].tobytes() for g in range(n)], st)
+
+    def pileup_call(self, frames, cols, ins, min_depth=3, cap=None):
+        """ioc_pileup_call: the consensus call of many references at once on the device, from host tables — `frames` a list of
+        bytes, segment g's len(frames[g]) + 1 rows of cols / ins following those of the earlier segments.  Returns
+        ([sequence per segment], [qualities per segment], stats), stats an array of POLISH_STATS_DTYPE; each segment as
+        pileup_call defines it."""
+        return self._pileup_call(False, frames, cols, None, ins, min_depth, cap)
+
+    def pileup_call_weighted(self, frames, cols, wcols, wins, min_depth=3, cap=None):
+        """ioc_pileup_call_weighted: pileup_call by weight, from host tables — `cols` gates, `wcols` / `wins` decide; each segment as
+        pileup_call_weighted (the function) defines it.  Returns what pileup_call returns."""
+        return self._pileup_call(True, frames, cols, wcols, wins, min_depth, cap)
+
+    def _align_pairs_polish(self, weighted, pairs, k, segs, seg_of_pair, min_depth, stats, tables, cap, match, mismatch, gap_extend):
+        """align_pairs_polish, and align_pairs_polish_weighted with its third table"""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr = (_lib.PolishSeg * max(ns, 1))()
+        for g, (ref, rc) in enumerate(segs):
+            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair must hold one entry per pair")
+        offs = self.align_pool_offsets()
+        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
+        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
+        n_rows = sum(rlen) + ns
+        bound = sum(pileup_call_bound(r) for r in rlen)
+        cap = bound if cap is None else int(cap)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, pol = np.zeros(ns + 1, np.int64), np.zeros(ns, POLISH_STATS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        # the tables in the order both the C function and the dict name them: cols, (wcols,) ins / wins
+        names = ("cols", "wcols", "wins") if weighted else ("cols", "ins")
+        tabs = [np.zeros(n_rows, PILEUP_INS_DTYPE if name in ("ins", "wins") else PILEUP_DTYPE) if tables else None for name in names]
+        fn = self.L.ioc_align_pairs_polish_weighted if weighted else self.L.ioc_align_pairs_polish
+        self._chk(fn(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+                     _p(sop, C.c_int32), int(min_depth), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64),
+                     pol.ctypes.data if ns else None, *(t.ctypes.data if tables and n_rows else None for t in tabs)))
+        out = {"score": score, "windows": win, "ratio": ratio, "polish": pol,
+               "seq": [seq[off[g]:off[g + 1]].tobytes() for g in range(ns)], "qual": [qual[off[g]:off[g + 1]].tobytes() for g in range(ns)]}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out.update(zip(names, tabs))
+            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
+        return out
 
     def align_pairs_polish(self, pairs, k, segs, seg_of_pair, min_depth=3, stats=False, tables=False, cap=None, match=2, mismatch=-2,
                            gap_extend=1):
@@ -507,102 +559,14 @@ class Context:
         pair i is piled into.  Returns a dict: score, windows, ratio, seq and qual (lists of bytes per segment), polish
         (POLISH_STATS_DTYPE per segment), with stats=True `stats` (ALN_STATS_DTYPE per pair), with tables=True `cols` and `ins`
         (the rows of segment g from sum(len(frame) + 1) of the earlier ones on) and `row0` (the first row per segment)."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr = (_lib.PolishSeg * max(ns, 1))()
-        for g, (ref, rc) in enumerate(segs):
-            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
-        sop = np.ascontiguousarray(seg_of_pair, np.int32)
-        if sop.shape != (n,):
-            raise ValueError("seg_of_pair must hold one entry per pair")
-        offs = self.align_pool_offsets()
-        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
-        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
-        n_rows = sum(rlen) + ns
-        bound = sum(pileup_call_bound(r) for r in rlen)
-        cap = bound if cap is None else int(cap)
-        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
-        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
-        off, pol = np.zeros(ns + 1, np.int64), np.zeros(ns, POLISH_STATS_DTYPE)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        ins = np.zeros(n_rows, PILEUP_INS_DTYPE) if tables else None
-        self._chk(self.L.ioc_align_pairs_polish(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32), _p(win, C.c_int64),
-                                                _p(ratio, C.c_double), st.ctypes.data if stats and n else None, ns, sarr, _p(sop, C.c_int32),
-                                                int(min_depth), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64),
-                                                pol.ctypes.data if ns else None, cols.ctypes.data if tables and n_rows else None,
-                                                ins.ctypes.data if tables and n_rows else None))
-        out = {"score": score, "windows": win, "ratio": ratio, "polish": pol,
-               "seq": [seq[off[g]:off[g + 1]].tobytes() for g in range(ns)], "qual": [qual[off[g]:off[g + 1]].tobytes() for g in range(ns)]}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out["cols"], out["ins"] = cols, ins
-            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
-        return out
-
-    def pileup_call_weighted(self, frames, cols, wcols, wins, min_depth=3, cap=None):
-        """ioc_pileup_call_weighted: pileup_call by weight, from host tables — `cols` gates, `wcols` / `wins` decide; each segment as
-        pileup_call_weighted (the function) defines it.  Returns what pileup_call returns."""
-        n = len(frames)
-        rlen = np.array([len(f) for f in frames], np.int32)
-        n_rows = int(rlen.sum()) + n
-        cols, wins = _tables(cols, wins, n_rows)
-        wcols = np.ascontiguousarray(wcols, PILEUP_DTYPE)
-        if wcols.shape != (n_rows,):
-            raise ValueError(f"wcols must hold {n_rows} rows")
-        f_off = np.zeros(n + 1, np.int64)
-        np.cumsum(rlen, out=f_off[1:])
-        bound = sum(pileup_call_bound(r) for r in rlen)
-        cap = bound if cap is None else int(cap)
-        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
-        off, st = np.zeros(n + 1, np.int64), np.zeros(n, POLISH_STATS_DTYPE)
-        self._chk(self.L.ioc_pileup_call_weighted(self.h, n, _p(rlen, C.c_int32), b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
-                                                  cols.ctypes.data, wcols.ctypes.data, wins.ctypes.data, int(min_depth), seq.ctypes.data,
-                                                  qual.ctypes.data, cap, _p(off, C.c_int64), st.ctypes.data if n else None))
-        return ([seq[off[g]:off[g + 1]].tobytes() for g in range(n)], [qual[off[g]:off[g + 1]].tobytes() for g in range(n)], st)
+        return self._align_pairs_polish(False, pairs, k, segs, seg_of_pair, min_depth, stats, tables, cap, match, mismatch, gap_extend)
 
     def align_pairs_polish_weighted(self, pairs, k, segs, seg_of_pair, min_depth=3, stats=False, tables=False, cap=None, match=2,
                                     mismatch=-2, gap_extend=1):
         """ioc_align_pairs_polish_weighted: align_pairs_polish with every vote weighted by the base quality of the read that casts
         it (align_set_pool_qual first).  Returns the same dict; with tables=True `cols` (the counts, as align_pairs_polish has
         them), `wcols` and `wins` (the sums of weights) and `row0`."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr = (_lib.PolishSeg * max(ns, 1))()
-        for g, (ref, rc) in enumerate(segs):
-            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
-        sop = np.ascontiguousarray(seg_of_pair, np.int32)
-        if sop.shape != (n,):
-            raise ValueError("seg_of_pair must hold one entry per pair")
-        offs = self.align_pool_offsets()
-        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
-        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
-        n_rows = sum(rlen) + ns
-        bound = sum(pileup_call_bound(r) for r in rlen)
-        cap = bound if cap is None else int(cap)
-        score, win, ratio = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.float64)
-        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
-        off, pol = np.zeros(ns + 1, np.int64), np.zeros(ns, POLISH_STATS_DTYPE)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        wcols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        wins = np.zeros(n_rows, PILEUP_INS_DTYPE) if tables else None
-        give = tables and n_rows
-        self._chk(self.L.ioc_align_pairs_polish_weighted(self.h, n, arr, k, match, mismatch, gap_extend, _p(score, C.c_int32),
-                                                         _p(win, C.c_int64), _p(ratio, C.c_double), st.ctypes.data if stats and n else None,
-                                                         ns, sarr, _p(sop, C.c_int32), int(min_depth), seq.ctypes.data, qual.ctypes.data, cap,
-                                                         _p(off, C.c_int64), pol.ctypes.data if ns else None,
-                                                         cols.ctypes.data if give else None, wcols.ctypes.data if give else None,
-                                                         wins.ctypes.data if give else None))
-        out = {"score": score, "windows": win, "ratio": ratio, "polish": pol,
-               "seq": [seq[off[g]:off[g + 1]].tobytes() for g in range(ns)], "qual": [qual[off[g]:off[g + 1]].tobytes() for g in range(ns)]}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out["cols"], out["wcols"], out["wins"] = cols, wcols, wins
-            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
-        return out
+        return self._align_pairs_polish(True, pairs, k, segs, seg_of_pair, min_depth, stats, tables, cap, match, mismatch, gap_extend)
 
     # ---- sort-stage feeders --------------------------------------------------------------------
     def qual_scores(self, offs, qual, k):

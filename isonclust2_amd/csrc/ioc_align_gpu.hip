@@ -33,6 +33,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "ioc_align_sink.h"
 #include "ioc_internal.h"
 
 namespace {
@@ -1091,17 +1092,6 @@ k_seq_flags(const uint8_t* __restrict__ pool, const int64_t* __restrict__ offs, 
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
-// events of a call's launches, three per slice: the forward pass, the traceback, the end (destroyed on every way out, the
-// IOC_CHK returns included)
-struct EventSet {
-    std::vector<hipEvent_t> v;
-    ~EventSet()
-    {
-        for (auto& e : v)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 // the device time of the first `used` events' slices, into ms_align_fwd / ms_align_trace
 void add_elapsed(ioc_ctx* c, const std::vector<hipEvent_t>& evs, size_t used)
 {
@@ -1133,45 +1123,13 @@ int ck_budget(ioc_ctx* c, uint64_t* budget, uint64_t held = 0)
 
 // ---- the operation bytes of an emitting call (ioc_align_pairs_ops) ------------------------------------------------------
 
-// the caller's side, indexed by the caller's pair: pair i's bytes go to buf + base[i] (room: query length + reference length),
-// len[i] of them, in forward order; the public function packs them when the call is over
-struct AlnOpsHost {
-    uint8_t* buf;
-    const int64_t* base;
-    int64_t* len;
-    double* ms_copy;  // what the copies from the device took the host, and ...
-    int64_t* copied;  // ... how many bytes they were (IOC_TRACE)
-    // ioc_align_pairs_stats: the sink is statistics — pair i's record goes to stats[i], the bytes stay on the device (buf and base
-    // are null), len[i] is still the length written
-    ioc_aln_stats* stats = nullptr;
-    double* ms_kernel = nullptr;  // k_ops_stats' device time, and ...
-    int64_t* records = nullptr;   // ... how many records came back (IOC_TRACE)
-    // ioc_align_pairs_pileup: a third sink (beside the statistics if `stats` is set, alone otherwise) — pair i's alignment is added
-    // to the rows from row_base[i] on of the call's table on the device, ONCE: piled[i] says that it has been, whichever run did it
-    ioc_pileup_col* pile = nullptr;  // (device) the table, pile_rows records
-    int64_t pile_rows = 0;
-    const int64_t* row_base = nullptr;
-    uint8_t* piled = nullptr;
-    double* ms_pileup = nullptr;  // k_ops_pileup's device time (IOC_TRACE)
-    // ioc_align_pairs_polish: a second table beside `pile`, of as many rows, carried the same way — what the pairs insert
-    ioc_pileup_ins* pile_ins = nullptr;  // (device)
-    // ioc_align_pairs_polish_weighted: beside `pile` (and no pile_ins), two tables of as many rows for the sums of weights
-    ioc_pileup_col* pile_wcols = nullptr;  // (device)
-    ioc_pileup_ins* pile_wins = nullptr;   // (device)
-    bool reduced() const { return stats || pile; }  // the bytes stay on the device
-    uint64_t pile_bytes() const
-    {
-        return pile ? uint64_t(pile_rows) * (sizeof(ioc_pileup_col) + (pile_ins ? sizeof(ioc_pileup_ins) : 0) +
-                                             (pile_wcols ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins) : 0))
-                    : 0;
-    }
-};
+// (the caller's side, indexed by the caller's pair: AlnSink, ioc_align_sink.h)
 
 // One run's side (version 2's, version 1's).  The pairs of a slice get consecutive regions of ONE device buffer, as large as the
 // largest slice needs — its bytes count against the checkpoint arena's budget (slice_couples, plan_v1) — and the buffer is
 // copied out after every slice.
 struct OpsRun {
-    const AlnOpsHost* host;
+    const AlnSink* host;
     const uint32_t* back;       // device pair -> caller's pair
     std::vector<uint64_t> end;  // per device pair: the end of its region within its slice's bytes
     AlnOpsDev dev{};
@@ -1188,42 +1146,41 @@ struct OpsRun {
     const uint32_t* d_q_len = nullptr;
 };
 
-// the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled).  A statistics call:
-// [end][len][room per pair][the bytes][4 spare bytes: k_ops_stats reads the dword that holds a string's last byte whole]; a
-// pileup call: [end][len][room][first row][query offset per pair][the bytes][4 spare bytes], a weighted one with [query length
-// per pair] behind the query offsets.
+// the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled); the columns a
+// reduced sink adds, and the spare bytes behind the slice's: OpsLayout
 int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vector<AlnPairDev>& dp)
 {
-    const bool st = o.host->reduced(), pile = o.host->pile != nullptr, weighted = o.host->pile_wcols != nullptr;
-    const size_t np = o.end.size(), tab = (np * (weighted ? 32 : pile ? 28 : st ? 16 : 12) + 15) & ~size_t(15);
-    const int r = ioc_reserve(c, c->a_ops, tab + size_t(max_slice_bytes) + (st ? 4 : 0));
+    const AlnSink& h = *o.host;
+    const size_t np = o.end.size();
+    const OpsLayout lay = h.layout(np);
+    const int r = ioc_reserve(c, c->a_ops, lay.bytes + size_t(max_slice_bytes) + lay.spare);
     if (r != IOC_OK) return r;
     uint8_t* p = static_cast<uint8_t*>(c->a_ops.p);
-    o.dev = AlnOpsDev{p + tab, reinterpret_cast<const uint64_t*>(p), reinterpret_cast<uint32_t*>(p + np * 8)};
-    IOC_CHK(c, hipMemcpyAsync(p, o.end.data(), np * 8, hipMemcpyHostToDevice, c->stream));
-    if (st) {
+    o.dev = AlnOpsDev{p + lay.bytes, reinterpret_cast<const uint64_t*>(p + lay.end), reinterpret_cast<uint32_t*>(p + lay.len)};
+    IOC_CHK(c, hipMemcpyAsync(p + lay.end, o.end.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+    if (h.reduced()) {
         o.room.resize(np);
         for (size_t x = 0; x < np; ++x) o.room[x] = dp[x].n + dp[x].m;
-        o.d_room = reinterpret_cast<const uint32_t*>(p + np * 12);
-        IOC_CHK(c, hipMemcpyAsync(p + np * 12, o.room.data(), np * 4, hipMemcpyHostToDevice, c->stream));
+        o.d_room = reinterpret_cast<const uint32_t*>(p + lay.room);
+        IOC_CHK(c, hipMemcpyAsync(p + lay.room, o.room.data(), np * 4, hipMemcpyHostToDevice, c->stream));
     }
-    if (pile) {
+    if (h.has_pile()) {
         o.row_base.resize(np);
         o.q_off.resize(np);
         for (size_t x = 0; x < np; ++x) {
-            o.row_base[x] = o.host->piled[o.back[x]] ? -1 : o.host->row_base[o.back[x]];
+            o.row_base[x] = h.pile.piled[o.back[x]] ? -1 : h.pile.row_base[o.back[x]];
             o.q_off[x] = dp[x].q_off;
         }
-        o.d_row_base = reinterpret_cast<const int64_t*>(p + np * 16);
-        o.d_q_off = reinterpret_cast<const uint32_t*>(p + np * 24);
-        IOC_CHK(c, hipMemcpyAsync(p + np * 16, o.row_base.data(), np * 8, hipMemcpyHostToDevice, c->stream));
-        IOC_CHK(c, hipMemcpyAsync(p + np * 24, o.q_off.data(), np * 4, hipMemcpyHostToDevice, c->stream));
+        o.d_row_base = reinterpret_cast<const int64_t*>(p + lay.row_base);
+        o.d_q_off = reinterpret_cast<const uint32_t*>(p + lay.q_off);
+        IOC_CHK(c, hipMemcpyAsync(p + lay.row_base, o.row_base.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+        IOC_CHK(c, hipMemcpyAsync(p + lay.q_off, o.q_off.data(), np * 4, hipMemcpyHostToDevice, c->stream));
     }
-    if (weighted) {
+    if (h.has_pile() && h.pile.kind == PileKind::weighted) {
         o.q_len.resize(np);
         for (size_t x = 0; x < np; ++x) o.q_len[x] = dp[x].n;
-        o.d_q_len = reinterpret_cast<const uint32_t*>(p + np * 28);
-        IOC_CHK(c, hipMemcpyAsync(p + np * 28, o.q_len.data(), np * 4, hipMemcpyHostToDevice, c->stream));
+        o.d_q_len = reinterpret_cast<const uint32_t*>(p + lay.q_len);
+        IOC_CHK(c, hipMemcpyAsync(p + lay.q_len, o.q_len.data(), np * 4, hipMemcpyHostToDevice, c->stream));
     }
     return IOC_OK;
 }
@@ -1233,32 +1190,41 @@ int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vect
 // pileup's table stays where it is until the call is over).  The same pairs are skipped as in ops_fetch.
 int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const uint32_t* ord, const uint32_t* d_ord, uint32_t cnt)
 {
-    const AlnOpsHost& h = *o.host;
+    const AlnSink& h = *o.host;
+    const AlnSink::Pile& pl = h.pile;
+    const bool stats = h.has_stats(), pile = h.has_pile();
+    AlnTally& t = *h.tally;
     int r;
-    if (h.stats && (r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
+    if (stats && (r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
     EventSet ev;
     ev.v.assign(3, nullptr);
     for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
-    if (h.stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
+    if (stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
     IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
-    if (h.pile && h.pile_wcols)
-        IOC_CHK(c, iock_ops_pileup_weighted(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_q_len,
-                                            static_cast<const uint8_t*>(c->a_pool.p), static_cast<const uint8_t*>(c->a_qual.p),
-                                            uint64_t(c->aln_offs.back()), h.pile, h.pile_wcols, h.pile_wins, uint64_t(h.pile_rows)));
-    else if (h.pile && h.pile_ins)
-        IOC_CHK(c, iock_ops_pileup_ins(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off,
-                                       static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), h.pile, h.pile_ins,
-                                       uint64_t(h.pile_rows)));
-    else if (h.pile)
-        IOC_CHK(c, iock_ops_pileup(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off,
-                                   static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), h.pile, uint64_t(h.pile_rows)));
+    const uint8_t* pool = static_cast<const uint8_t*>(c->a_pool.p);
+    const uint64_t pool_bytes = uint64_t(c->aln_offs.back());
+    switch (pile ? pl.kind : PileKind::none) {
+    case PileKind::none: break;
+    case PileKind::counts:
+        IOC_CHK(c, iock_ops_pileup(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, pool, pool_bytes,
+                                   pl.cols, uint64_t(pl.rows)));
+        break;
+    case PileKind::ins:
+        IOC_CHK(c, iock_ops_pileup_ins(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, pool, pool_bytes,
+                                       pl.cols, pl.ins, uint64_t(pl.rows)));
+        break;
+    case PileKind::weighted:
+        IOC_CHK(c, iock_ops_pileup_weighted(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_q_len, pool,
+                                            static_cast<const uint8_t*>(c->a_qual.p), pool_bytes, pl.cols, pl.wcols, pl.wins, uint64_t(pl.rows)));
+        break;
+    }
     IOC_CHK(c, hipEventRecord(ev.v[2], c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
     IOC_CHK(c, hipMemcpy(o.len.data(), o.dev.len, dp.size() * 4, hipMemcpyDeviceToHost));
-    if (h.stats) {
+    if (stats) {
         o.recs.resize(cnt);
         IOC_CHK(c, hipMemcpy(o.recs.data(), c->a_ostats.p, size_t(cnt) * sizeof(ioc_aln_stats), hipMemcpyDeviceToHost));
     }
@@ -1266,16 +1232,16 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
         const uint32_t pid = ord[x], i = o.back[pid];
         const uint64_t L = o.len[pid];
         if (L == 0 || L > uint64_t(dp[pid].n) + dp[pid].m || L > o.end[pid]) continue;
-        if (h.stats) h.stats[i] = o.recs[x];
-        if (h.pile) h.piled[i] = 1;
+        if (stats) h.stats[i] = o.recs[x];
+        if (pile) pl.piled[i] = 1;
         h.len[i] = int64_t(L);
     }
     float ms = 0;
-    if (h.stats && hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) *h.ms_kernel += double(ms);
-    if (h.pile && hipEventElapsedTime(&ms, ev.v[1], ev.v[2]) == hipSuccess) *h.ms_pileup += double(ms);
-    *h.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *h.copied += int64_t(dp.size() * 4 + (h.stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
-    if (h.stats) *h.records += int64_t(cnt);
+    if (stats && hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) t.ms_stats += double(ms);
+    if (pile && hipEventElapsedTime(&ms, ev.v[1], ev.v[2]) == hipSuccess) t.ms_pileup += double(ms);
+    t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t.copied += int64_t(dp.size() * 4 + (stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
+    if (stats) t.records += int64_t(cnt);
     return IOC_OK;
 }
 
@@ -1294,11 +1260,11 @@ int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const ui
         const uint32_t pid = ord[x], i = o.back[pid];
         const uint64_t L = o.len[pid];
         if (L == 0 || L > uint64_t(dp[pid].n) + dp[pid].m || L > o.end[pid]) continue;
-        memcpy(o.host->buf + o.host->base[i], o.stage.data() + (o.end[pid] - L), size_t(L));
+        memcpy(o.host->bytes.buf + o.host->bytes.base[i], o.stage.data() + (o.end[pid] - L), size_t(L));
         o.host->len[i] = int64_t(L);
     }
-    *o.host->ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *o.host->copied += int64_t(bytes);
+    o.host->tally->ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o.host->tally->copied += int64_t(bytes);
     return IOC_OK;
 }
 
@@ -2015,7 +1981,7 @@ struct AlnOut {
     int32_t* score;
     int64_t* windows;
     double* ratio;
-    const AlnOpsHost* ops = nullptr;  // an emitting call (ioc_align_pairs_ops): where the operation bytes go
+    const AlnSink* ops = nullptr;  // an emitting call (ioc_align_pairs_ops): where the operation bytes go
     void set(size_t i, int32_t s, int64_t w, double r) const
     {
         if (score) score[i] = s;
@@ -2035,15 +2001,12 @@ struct AlnBatch {
 // 1. the device records; a pair with an empty sequence is answered here
 int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const AlnParams& P, const AlnOut& out, AlnBatch& b)
 {
-    const int32_t n_seqs = c->aln_offs.empty() ? 0 : int32_t(c->aln_offs.size() - 1);
     const int32_t k = int32_t(P.k);
     b.dp.reserve(size_t(n_pairs));
     for (int32_t i = 0; i < n_pairs; ++i) {
         const ioc_aln_pair& a = pairs[i];
-        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs)
-            return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
-        const int64_t n = c->aln_offs[size_t(a.query) + 1] - c->aln_offs[size_t(a.query)];
-        const int64_t m = c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)];
+        IOC_TRY(ioc_pair_in_pool(c, a));
+        const int64_t n = ioc_seq_len(c, a.query), m = ioc_seq_len(c, a.ref);
         if (n + m >= (int64_t(1) << ALN_LEN_SHIFT))
             return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: sequences above 2^26 bases");
         const double limit = std::floor((1.0 - a.e) * double(k));  // getAlnRatio, cluster.cpp:446
@@ -2053,18 +2016,7 @@ int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const 
             const int64_t len = n + m;
             const int64_t cnt = (il <= 0 && len > k) ? len - k : 0;
             out.set(size_t(i), 0, cnt, n == 0 ? 0.0 : double(cnt) / double(n));
-            if (out.ops && out.ops->reduced()) {  // (all of it one free end gap, and no walk: leading; nothing for a pileup)
-                if (out.ops->stats) {
-                    ioc_aln_stats& s = out.ops->stats[i];
-                    s = ioc_aln_stats{};
-                    s.length = int32_t(len);
-                    (n ? s.lead_i : s.lead_d) = int32_t(len);
-                }
-                out.ops->len[i] = len;
-            } else if (out.ops) {  // (all of it one free end gap)
-                memset(out.ops->buf + out.ops->base[i], n ? 'i' : 'd', size_t(len));
-                out.ops->len[i] = len;
-            }
+            if (out.ops) out.ops->answer_empty(size_t(i), n, m);  // (all of it one free end gap, and no walk)
             continue;
         }
         AlnPairDev d{};
@@ -2172,7 +2124,7 @@ WavePlan plan_waves(const AlnBatch& b, bool carry)
 
 // 4. version 2 takes the query-profile pairs — the front of `order`; *n_v2: how many it answered (0 when a bounded wait ran out
 // and they all go to version 1)
-int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2, const AlnOpsHost* oh)
+int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2, const AlnSink* oh)
 {
     const uint32_t np = uint32_t(b.dp.size());
     uint32_t n = 0;
@@ -2446,7 +2398,7 @@ int v1_slice(ioc_ctx* c, const AlnBatch& b, const std::pair<uint32_t, uint32_t>&
 
 // Version 1 takes the pairs from order[n_v2] on: pairs with other letters, pairs the 16-bit window refused, the whole batch
 // should a bounded wait of version 2 run out, and everything under IOC_ALIGN_V1=1 or IOC_ALIGN_ARENA=fat.
-int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, const AlnParams& P, int32_t* d_score, uint32_t* d_count, const AlnOpsHost* oh)
+int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, const AlnParams& P, int32_t* d_score, uint32_t* d_count, const AlnSink* oh)
 {
     hipStream_t s = c->stream;
     const uint32_t np = uint32_t(b.dp.size());
@@ -2546,34 +2498,14 @@ int align_again(ioc_ctx* c, const ioc_aln_pair* pairs, const std::vector<int32_t
     std::vector<int64_t> sw(idx.size());
     std::vector<double> sr(idx.size());
     for (size_t x = 0; x < idx.size(); ++x) sub[x] = pairs[idx[x]];
-    // (emitting call: the re-run writes straight into the regions of the caller's pairs — the bytes of the run that counted)
-    std::vector<int64_t> sbase, slen(out.ops ? idx.size() : 0, 0);
-    AlnOpsHost soh{};
-    std::vector<ioc_aln_stats> sstats(out.ops && out.ops->stats ? idx.size() : 0, ioc_aln_stats{});
-    std::vector<int64_t> srow;   // (pileup call: the re-run's pairs add into the same table, at their own rows)
-    std::vector<uint8_t> spiled;
-    if (out.ops && out.ops->reduced()) {  // (statistics call: the re-run's records, scattered below)
-        soh = *out.ops;
-        soh.len = slen.data();
-        if (out.ops->stats) soh.stats = sstats.data();
-        if (out.ops->pile) {
-            for (int32_t i : idx) srow.push_back(out.ops->row_base[i]), spiled.push_back(out.ops->piled[i]);
-            soh.row_base = srow.data();
-            soh.piled = spiled.data();
-        }
-    } else if (out.ops) {
-        for (int32_t i : idx) sbase.push_back(out.ops->base[i]);
-        soh = AlnOpsHost{out.ops->buf, sbase.data(), slen.data(), out.ops->ms_copy, out.ops->copied};
-    }
+    // (emitting call: the re-run writes straight into the regions of the caller's pairs — the bytes of the run that counted — and
+    // adds into the same tables, at their own rows)
+    const AlnSubSink sub_ops = out.ops ? out.ops->subset(idx) : AlnSubSink();
     const int r = align_pairs(c, int32_t(sub.size()), sub.data(), int32_t(P.k), P.match, P.mismatch, P.gap_extend,
-                              AlnOut{sc.data(), sw.data(), sr.data(), out.ops ? &soh : nullptr}, route);
+                              AlnOut{sc.data(), sw.data(), sr.data(), out.ops ? &sub_ops.sink : nullptr}, route);
     if (r != IOC_OK) return r;
-    for (size_t x = 0; x < idx.size(); ++x) {
-        out.set(size_t(idx[x]), sc[x], sw[x], sr[x]);
-        if (out.ops) out.ops->len[idx[x]] = slen[x];
-        if (out.ops && out.ops->stats) out.ops->stats[idx[x]] = sstats[x];
-        if (out.ops && out.ops->pile) out.ops->piled[idx[x]] = spiled[x];
-    }
+    for (size_t x = 0; x < idx.size(); ++x) out.set(size_t(idx[x]), sc[x], sw[x], sr[x]);
+    if (out.ops) out.ops->take_back(idx, sub_ops);
     return IOC_OK;
 }
 
@@ -2721,354 +2653,16 @@ int ioc_align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int3
     return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
 }
 
-int64_t ioc_align_ops_bound(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs)
+}  // extern "C"
+
+// what the entry points of ioc_align_sinks.cpp call
+int ioc_align_pairs_sink(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                         int32_t* out_score, int64_t* out_windows, double* out_ratio, const AlnSink* sink)
 {
-    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs)) return IOC_ERR_ARG;
-    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
-    int64_t bound = 0;
-    for (int32_t i = 0; i < n_pairs; ++i) {
-        const ioc_aln_pair& a = pairs[i];
-        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
-        bound += (c->aln_offs[size_t(a.query) + 1] - c->aln_offs[size_t(a.query)]) + (c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)]);
-    }
-    return bound;
+    return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, sink}, AlnRoute::normal);
 }
 
-// The walks write a pair's bytes into a region of its own of the caller's buffer (as long as the pair's share of the bound);
-// the regions are packed when all runs — the call's own, the re-runs' — are over.
-int ioc_align_pairs_ops(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
-                        int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, char* out_ops, int64_t ops_cap,
-                        int64_t* ops_off)
-{
-    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs) || !ops_off || ops_cap < 0 || (ops_cap > 0 && !out_ops)) return IOC_ERR_ARG;
-    const int64_t bound = ioc_align_ops_bound(c, n_pairs, pairs);
-    if (bound < 0) return int(bound);
-    if (ops_cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_ops: ops_cap " + std::to_string(ops_cap) + " below the bound " + std::to_string(bound));
-    std::vector<int64_t> base(size_t(n_pairs) + 1, 0), len(size_t(n_pairs), 0);
-    for (int32_t i = 0; i < n_pairs; ++i)
-        base[size_t(i) + 1] = base[size_t(i)] + (c->aln_offs[size_t(pairs[i].query) + 1] - c->aln_offs[size_t(pairs[i].query)]) +
-                              (c->aln_offs[size_t(pairs[i].ref) + 1] - c->aln_offs[size_t(pairs[i].ref)]);
-    double ms_copy = 0;
-    int64_t copied = 0;
-    const AlnOpsHost oh{reinterpret_cast<uint8_t*>(out_ops), base.data(), len.data(), &ms_copy, &copied};
-    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, &oh}, AlnRoute::normal);
-    if (r != IOC_OK) return r;
-    ops_off[0] = 0;
-    for (int32_t i = 0; i < n_pairs; ++i) {  // (a packed position never lies behind the region's own)
-        if (len[size_t(i)] > 0 && ops_off[i] != base[size_t(i)]) memmove(out_ops + ops_off[i], out_ops + base[size_t(i)], size_t(len[size_t(i)]));
-        ops_off[i + 1] = ops_off[i] + len[size_t(i)];
-    }
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: operation bytes: %.1f MB copied from the device in %.3f ms, %.1f MB packed\n", double(copied) * 1e-6, ms_copy,
-                double(ops_off[n_pairs]) * 1e-6);
-    return IOC_OK;
-}
-
-// The walks write a slice's bytes as for ioc_align_pairs_ops; k_ops_stats (ioc_ops_stats.hip) reduces them where they lie, and
-// the records of the run that counted — the call's own, a re-run's — end up in out_stats.
-int ioc_align_pairs_stats(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
-                          int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats)
-{
-    if (!c || n_pairs < 0 || (n_pairs > 0 && (!pairs || !out_stats))) return IOC_ERR_ARG;
-    for (int32_t i = 0; i < n_pairs; ++i) out_stats[i] = ioc_aln_stats{};
-    std::vector<int64_t> len(size_t(n_pairs), 0);
-    double ms_copy = 0, ms_kernel = 0;
-    int64_t copied = 0, records = 0;
-    AlnOpsHost oh{nullptr, nullptr, len.data(), &ms_copy, &copied};
-    oh.stats = out_stats;
-    oh.ms_kernel = &ms_kernel;
-    oh.records = &records;
-    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, &oh}, AlnRoute::normal);
-    if (r != IOC_OK) return r;
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: alignment statistics: %lld records (%.3f MB with the lengths) copied from the device in %.3f ms, k_ops_stats %.3f ms\n",
-                (long long)records, double(copied) * 1e-6, ms_copy, ms_kernel);
-    return IOC_OK;
-}
-
-// The walks write a slice's bytes as for ioc_align_pairs_ops; k_ops_pileup (ioc_ops_pileup.hip) adds them, where they lie, into a
-// table of the call's rows that stays on the device over the slices and the re-runs and is copied out once.
-int ioc_align_pairs_pileup(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
-                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
-                           const int64_t* row_base, int64_t n_rows, ioc_pileup_col* out_cols)
-{
-    if (!c || n_pairs < 0 || n_rows < 0 || (n_pairs > 0 && (!pairs || !row_base || !out_cols))) return IOC_ERR_ARG;
-    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
-    for (int32_t i = 0; i < n_pairs; ++i) {
-        const ioc_aln_pair& a = pairs[i];
-        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
-        const int64_t m = c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)];
-        if (row_base[i] < 0 || row_base[i] > n_rows - m - 1)
-            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_pileup: the rows of pair " + std::to_string(i) + " lie outside the table");
-    }
-    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
-    if (out_cols && n_rows > 0) memset(out_cols, 0, size_t(n_rows) * sizeof(ioc_pileup_col));
-    if (n_pairs == 0 || n_rows == 0) return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
-    IOC_CHK(c, hipSetDevice(c->device));
-    const size_t bytes = size_t(n_rows) * sizeof(ioc_pileup_col);
-    IOC_TRY(ioc_reserve(c, c->a_pile, bytes));
-    IOC_CHK(c, hipMemsetAsync(c->a_pile.p, 0, bytes, c->stream));
-    std::vector<int64_t> len(size_t(n_pairs), 0);
-    std::vector<uint8_t> piled(size_t(n_pairs), 0);
-    double ms_copy = 0, ms_kernel = 0, ms_pileup = 0;
-    int64_t copied = 0, records = 0;
-    AlnOpsHost oh{nullptr, nullptr, len.data(), &ms_copy, &copied};
-    oh.stats = out_stats;
-    oh.ms_kernel = &ms_kernel;
-    oh.records = &records;
-    oh.pile = c->a_pile.as<ioc_pileup_col>();
-    oh.pile_rows = n_rows;
-    oh.row_base = row_base;
-    oh.piled = piled.data();
-    oh.ms_pileup = &ms_pileup;
-    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, &oh}, AlnRoute::normal);
-    if (r != IOC_OK) return r;
-    IOC_CHK(c, hipStreamSynchronize(c->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    IOC_CHK(c, hipMemcpy(out_cols, c->a_pile.p, bytes, hipMemcpyDeviceToHost));
-    ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    copied += int64_t(bytes);
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: pileup: %lld rows, %.3f MB (table, lengths%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms%s\n",
-                (long long)n_rows, double(copied) * 1e-6, out_stats ? ", statistics" : "", ms_copy, ms_pileup,
-                out_stats ? (", k_ops_stats " + std::to_string(ms_kernel) + " ms").c_str() : "");
-    return IOC_OK;
-}
-
-namespace {
-
-// the segments' bound: what ioc_host_pileup_call asks of cap, summed
-int64_t pile_call_bound(const std::vector<IocPileSeg>& segs)
-{
-    int64_t b = 0;
-    for (const IocPileSeg& s : segs) b += int64_t(s.rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(s.rlen) + 1);
-    return b;
-}
-
-// The call kernels over tables that lie on the device (n_rows records each), and what they made copied back: a_call holds
-// [segments][seg_len][out_off][records][sequence][qualities].  ms: the kernels' device time, ms_copy: the host's time over the
-// copies, copied: their bytes (all added to; the last two may be NULL).
-int pile_call_device(ioc_ctx* c, const std::vector<IocPileSeg>& segs, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
-                     const ioc_pileup_col* d_gate /* the weighted call: d_cols / d_ins are weights, this the counts; else NULL */, int64_t n_rows,
-                     const uint8_t* d_frames, uint64_t frame_bytes, int32_t min_depth, char* out_seq, char* out_qual, int64_t* out_off,
-                     ioc_polish_stats* out_stats, double* ms, double* ms_copy, int64_t* copied)
-{
-    const size_t n = segs.size();
-    const size_t bound = size_t(pile_call_bound(segs));
-    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
-    const size_t o_seg = 0, o_len = up16(n * sizeof(IocPileSeg)), o_off = o_len + up16(n * 8), o_st = o_off + up16((n + 1) * 8),
-                 o_seq = o_st + n * sizeof(ioc_polish_stats), o_qual = o_seq + up16(bound), total = o_qual + up16(bound);
-    IOC_TRY(ioc_reserve(c, c->a_call, total));
-    uint8_t* p = static_cast<uint8_t*>(c->a_call.p);
-    IOC_CHK(c, hipMemcpyAsync(p + o_seg, segs.data(), n * sizeof(IocPileSeg), hipMemcpyHostToDevice, c->stream));
-    EventSet ev;
-    ev.v.assign(2, nullptr);
-    for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
-    IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
-    if (d_gate)
-        IOC_CHK(c, iock_pile_call_weighted(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_gate, d_cols, d_ins,
-                                           uint64_t(n_rows), d_frames, frame_bytes, min_depth, reinterpret_cast<int64_t*>(p + o_len),
-                                           reinterpret_cast<ioc_polish_stats*>(p + o_st), reinterpret_cast<int64_t*>(p + o_off), p + o_seq,
-                                           p + o_qual, uint64_t(bound)));
-    else
-        IOC_CHK(c, iock_pile_call(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_cols, d_ins, uint64_t(n_rows), d_frames,
-                                  frame_bytes, min_depth, reinterpret_cast<int64_t*>(p + o_len), reinterpret_cast<ioc_polish_stats*>(p + o_st),
-                                  reinterpret_cast<int64_t*>(p + o_off), p + o_seq, p + o_qual, uint64_t(bound)));
-    IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
-    IOC_CHK(c, hipStreamSynchronize(c->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    IOC_CHK(c, hipMemcpy(out_off, p + o_off, (n + 1) * 8, hipMemcpyDeviceToHost));
-    const int64_t len = out_off[n];
-    if (len < 0 || size_t(len) > bound) return ioc_fail(c, IOC_ERR_HIP, "the consensus call returned a length outside its bound");
-    if (out_stats) IOC_CHK(c, hipMemcpy(out_stats, p + o_st, n * sizeof(ioc_polish_stats), hipMemcpyDeviceToHost));
-    if (len > 0) {
-        IOC_CHK(c, hipMemcpy(out_seq, p + o_seq, size_t(len), hipMemcpyDeviceToHost));
-        IOC_CHK(c, hipMemcpy(out_qual, p + o_qual, size_t(len), hipMemcpyDeviceToHost));
-    }
-    float t = 0;
-    if (ms && hipEventElapsedTime(&t, ev.v[0], ev.v[1]) == hipSuccess) *ms += double(t);
-    if (ms_copy) *ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (copied) *copied += int64_t((n + 1) * 8 + (out_stats ? n * sizeof(ioc_polish_stats) : 0) + 2 * size_t(len));
-    return IOC_OK;
-}
-
-// ioc_pileup_call (wcols NULL: cols / ins are called by majority) and ioc_pileup_call_weighted (cols gates, wcols / ins decide).
-// The tables are uploaded and called where they lie then (ioc_pile_call.hip); the frames travel as one pool of bytes.
-int pileup_call_tables(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
-                       const ioc_pileup_col* wcols, const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
-                       int64_t* out_off, ioc_polish_stats* out_stats)
-{
-    std::vector<IocPileSeg> segs(static_cast<size_t>(n_segs));
-    int64_t n_rows = 0, frame_bytes = 0;
-    for (int32_t g = 0; g < n_segs; ++g) {
-        if (rlen[g] < 0 || frame_off[g] < 0 || (rlen[g] > 0 && !frames)) return ioc_fail(c, IOC_ERR_ARG, "ioc_pileup_call: segment " + std::to_string(g) + " has a negative length or frame offset");
-        if (int64_t(rlen[g]) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen[g]) + 1) > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
-            return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_call: segment " + std::to_string(g) + " may call more than 2^31 - 1 bytes");
-        segs[size_t(g)] = IocPileSeg{n_rows, frame_off[g], rlen[g], 0};
-        n_rows += int64_t(rlen[g]) + 1;
-        frame_bytes = std::max(frame_bytes, frame_off[g] + rlen[g]);
-    }
-    const int64_t bound = pile_call_bound(segs);
-    if (cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_call: cap " + std::to_string(cap) + " below the bound " + std::to_string(bound));
-    if (bound > 0 && (!out_seq || !out_qual)) return IOC_ERR_ARG;
-    out_off[0] = 0;
-    if (n_segs == 0) return IOC_OK;
-    IOC_CHK(c, hipSetDevice(c->device));
-    const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
-    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
-    IOC_TRY(ioc_reserve(c, c->a_pile_ins, b_ins));
-    DevBuf d_frames;
-    IOC_TRY(ioc_alloc(c, d_frames, size_t(frame_bytes)));
-    IOC_CHK(c, hipMemcpyAsync(c->a_pile.p, cols, b_cols, hipMemcpyHostToDevice, c->stream));
-    IOC_CHK(c, hipMemcpyAsync(c->a_pile_ins.p, ins, b_ins, hipMemcpyHostToDevice, c->stream));
-    if (wcols) {
-        IOC_TRY(ioc_reserve(c, c->a_pile_w, b_cols));
-        IOC_CHK(c, hipMemcpyAsync(c->a_pile_w.p, wcols, b_cols, hipMemcpyHostToDevice, c->stream));
-    }
-    if (frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(frame_bytes), hipMemcpyHostToDevice, c->stream));
-    double ms = 0;
-    IOC_TRY(pile_call_device(c, segs, wcols ? c->a_pile_w.as<ioc_pileup_col>() : c->a_pile.as<ioc_pileup_col>(), c->a_pile_ins.as<ioc_pileup_ins>(),
-                             wcols ? c->a_pile.as<ioc_pileup_col>() : nullptr, n_rows, static_cast<const uint8_t*>(d_frames.p),
-                             uint64_t(frame_bytes), min_depth, out_seq, out_qual, out_off, out_stats, &ms, nullptr, nullptr));
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   consensus call: %d segments, %lld rows, %lld bytes called, k_pile_call%s %.3f ms\n", n_segs, (long long)n_rows,
-                (long long)out_off[n_segs], wcols ? "<weighted>" : "", ms);
-    return IOC_OK;
-}
-
-}  // namespace
-
-int ioc_pileup_call(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
-                    const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
-                    ioc_polish_stats* out_stats)
-{
-    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !ins))) return IOC_ERR_ARG;
-    return pileup_call_tables(c, n_segs, rlen, frames, frame_off, cols, nullptr, ins, min_depth, out_seq, out_qual, cap, out_off, out_stats);
-}
-
-int ioc_pileup_call_weighted(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
-                             const ioc_pileup_col* cols, const ioc_pileup_col* wcols, const ioc_pileup_ins* wins, int32_t min_depth, char* out_seq,
-                             char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats)
-{
-    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !wcols || !wins))) return IOC_ERR_ARG;
-    return pileup_call_tables(c, n_segs, rlen, frames, frame_off, cols, wcols, wins, min_depth, out_seq, out_qual, cap, out_off, out_stats);
-}
-
-namespace {
-
-// ioc_align_pairs_pileup with the second table beside the first, and the call kernels over both where they lie: what comes back
-// is the called bytes (at most 7 per row), not the tables, unless they are asked for.  weighted (ioc_align_pairs_polish_weighted):
-// the weighted variant of k_ops_pileup adds the counts into the first table and the weights into two tables of a_pile_w, [wcols]
-// [wins], and the call is the weighted one; out_ins is then out_wins.
-int align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
-                       int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
-                       int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
-                       char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
-                       ioc_pileup_ins* out_ins, bool weighted, ioc_pileup_col* out_wcols)
-{
-    if (!c || n_pairs < 0 || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_pairs > 0 && (!pairs || !seg_of_pair)) ||
-        (n_segs > 0 && (!segs || !out_polish)))
-        return IOC_ERR_ARG;
-    if (weighted && !c->aln_qual_set) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish_weighted: no qualities are set for the current pool (ioc_align_set_pool_qual)");
-    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
-    std::vector<IocPileSeg> ds(static_cast<size_t>(n_segs));
-    int64_t n_rows = 0;
-    for (int32_t g = 0; g < n_segs; ++g) {
-        if (segs[g].ref < 0 || segs[g].ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: segment " + std::to_string(g) + " refers to a sequence outside the pool");
-        const int64_t off = c->aln_offs[size_t(segs[g].ref)], m = c->aln_offs[size_t(segs[g].ref) + 1] - off;
-        ds[size_t(g)] = IocPileSeg{n_rows, off, int32_t(m), segs[g].ref_revcomp ? 1 : 0};
-        n_rows += m + 1;
-    }
-    std::vector<int64_t> row_base(size_t(n_pairs), 0);
-    for (int32_t i = 0; i < n_pairs; ++i) {
-        const ioc_aln_pair& a = pairs[i];
-        if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
-        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: pair " + std::to_string(i) + " names no segment");
-        const int64_t m = c->aln_offs[size_t(a.ref) + 1] - c->aln_offs[size_t(a.ref)];
-        if (m != ds[size_t(seg_of_pair[i])].rlen)
-            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: the reference of pair " + std::to_string(i) + " is not as long as its segment's frame");
-        row_base[size_t(i)] = ds[size_t(seg_of_pair[i])].row0;
-    }
-    const int64_t bound = pile_call_bound(ds);
-    if (cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_polish: cap " + std::to_string(cap) + " below the bound " + std::to_string(bound));
-    if (bound > 0 && (!out_seq || !out_qual)) return IOC_ERR_ARG;
-    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
-    out_off[0] = 0;
-    if (n_segs == 0) return align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio}, AlnRoute::normal);
-    IOC_CHK(c, hipSetDevice(c->device));
-    const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
-    DevBuf& second = weighted ? c->a_pile_w : c->a_pile_ins;  // [ins], or [wcols][wins]
-    const size_t b_second = weighted ? b_cols + b_ins : b_ins;
-    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
-    IOC_TRY(ioc_reserve(c, second, b_second));
-    IOC_CHK(c, hipMemsetAsync(c->a_pile.p, 0, b_cols, c->stream));
-    IOC_CHK(c, hipMemsetAsync(second.p, 0, b_second, c->stream));
-    std::vector<int64_t> len(size_t(n_pairs), 0);
-    std::vector<uint8_t> piled(size_t(n_pairs), 0);
-    double ms_copy = 0, ms_kernel = 0, ms_pileup = 0, ms_call = 0;
-    int64_t copied = 0, records = 0;
-    AlnOpsHost oh{nullptr, nullptr, len.data(), &ms_copy, &copied};
-    oh.stats = out_stats;
-    oh.ms_kernel = &ms_kernel;
-    oh.records = &records;
-    oh.pile = c->a_pile.as<ioc_pileup_col>();
-    if (weighted) {
-        oh.pile_wcols = second.as<ioc_pileup_col>();
-        oh.pile_wins = reinterpret_cast<ioc_pileup_ins*>(static_cast<uint8_t*>(second.p) + b_cols);  // (b_cols: a multiple of 32)
-    } else {
-        oh.pile_ins = second.as<ioc_pileup_ins>();
-    }
-    oh.pile_rows = n_rows;
-    oh.row_base = row_base.data();
-    oh.piled = piled.data();
-    oh.ms_pileup = &ms_pileup;
-    const int r = align_pairs(c, n_pairs, pairs, k, match, mismatch, gap_extend, AlnOut{out_score, out_windows, out_ratio, n_pairs > 0 ? &oh : nullptr}, AlnRoute::normal);
-    if (r != IOC_OK) return r;
-    IOC_TRY(pile_call_device(c, ds, weighted ? oh.pile_wcols : oh.pile, weighted ? oh.pile_wins : oh.pile_ins, weighted ? oh.pile : nullptr, n_rows,
-                             static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), min_depth, out_seq, out_qual, out_off, out_polish,
-                             &ms_call, &ms_copy, &copied));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (out_cols) {
-        IOC_CHK(c, hipMemcpy(out_cols, c->a_pile.p, b_cols, hipMemcpyDeviceToHost));
-        copied += int64_t(b_cols);
-    }
-    if (out_wcols) {
-        IOC_CHK(c, hipMemcpy(out_wcols, oh.pile_wcols, b_cols, hipMemcpyDeviceToHost));
-        copied += int64_t(b_cols);
-    }
-    if (out_ins) {
-        IOC_CHK(c, hipMemcpy(out_ins, weighted ? oh.pile_wins : oh.pile_ins, b_ins, hipMemcpyDeviceToHost));
-        copied += int64_t(b_ins);
-    }
-    ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: polish: %d segments, %lld rows, %.3f MB (called bytes, records, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup<%s> %.3f ms, k_pile_call%s %.3f ms%s\n",
-                n_segs, (long long)n_rows, double(copied) * 1e-6, out_cols || out_ins || out_wcols ? ", tables" : "", out_stats ? ", statistics" : "", ms_copy,
-                weighted ? "weighted" : "ins", ms_pileup, weighted ? "<weighted>" : "", ms_call, out_stats ? (", k_ops_stats " + std::to_string(ms_kernel) + " ms").c_str() : "");
-    return IOC_OK;
-}
-
-}  // namespace
-
-int ioc_align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
-                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
-                           int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
-                           char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
-                           ioc_pileup_ins* out_ins)
-{
-    return align_pairs_polish(c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs,
-                              seg_of_pair, min_depth, out_seq, out_qual, cap, out_off, out_polish, out_cols, out_ins, false, nullptr);
-}
-
-int ioc_align_pairs_polish_weighted(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
-                                    int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
-                                    int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq,
-                                    char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
-                                    ioc_pileup_col* out_wcols, ioc_pileup_ins* out_wins)
-{
-    return align_pairs_polish(c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs,
-                              seg_of_pair, min_depth, out_seq, out_qual, cap, out_off, out_polish, out_cols, out_wins, true, out_wcols);
-}
+extern "C" {
 
 // (ioc_ctx_prewarm)
 hipError_t iock_warm_align()

@@ -1,0 +1,156 @@
+// ioc_align_sink.h — where the batched aligner's walks leave their operation bytes: the caller's side of an emitting call
+// (ioc_align_gpu.hip runs it, ioc_align_sinks.cpp's entry points describe it).  Host code only, and no HIP header: the device
+// tables are plain pointers here, and tools/align_sink_check.cpp drives everything below on the CPU.
+#ifndef IOC_ALIGN_SINK_H
+#define IOC_ALIGN_SINK_H
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "isonclust2_hip.h"
+
+#pragma GCC visibility push(hidden)  // (internal to the library: none of this is part of its exported symbols)
+
+// what a call's IOC_TRACE line reports; owned by the entry point, added to by every run — the call's own, the re-runs'
+struct AlnTally {
+    double ms_copy = 0;    // what the copies from the device took the host, and ...
+    int64_t copied = 0;    // ... how many bytes they were
+    double ms_stats = 0;   // k_ops_stats' device time, and ...
+    int64_t records = 0;   // ... how many records came back
+    double ms_pileup = 0;  // k_ops_pileup's device time
+    double ms_call = 0;    // k_pile_call's device time (the polish path)
+};
+
+enum class SinkKind { bytes, reduced };               // the bytes go to the host / stay on the device and are reduced there
+enum class PileKind { none, counts, ins, weighted };  // the variant of k_ops_pileup a reduced sink runs
+
+// The per-slice table of a run in front of the slice's bytes (ops_reserve): a column per device pair each, np pairs.  The offsets
+// do not depend on the kind; the kind says how many of the columns there are.
+struct OpsLayout {
+    size_t end;       // uint64: one past the last byte of the pair's region
+    size_t len;       // uint32: bytes written
+    size_t room;      // uint32: query length + reference length (a reduced sink)
+    size_t row_base;  // int64: first row, -1 for a pair that has been added already (a pile)
+    size_t q_off;     // uint32: where the query starts in the pool (a pile)
+    size_t q_len;     // uint32: the query's length (a weighted pile)
+    size_t bytes;     // the slice's bytes: the table, rounded up to 16
+    size_t spare;     // behind the bytes: k_ops_stats and k_ops_pileup read the dword that holds a string's last byte whole
+};
+inline OpsLayout ops_layout(size_t np, SinkKind kind, PileKind pile)
+{
+    const bool reduced = kind == SinkKind::reduced;
+    const size_t per_pair = !reduced ? 12 : pile == PileKind::weighted ? 32 : pile != PileKind::none ? 28 : 16;
+    return OpsLayout{0, np * 8, np * 12, np * 16, np * 24, np * 28, (np * per_pair + 15) & ~size_t(15), reduced ? size_t(4) : size_t(0)};
+}
+
+struct AlnSubSink;
+
+// The caller's side, indexed by the caller's pair.  len[i]: the length written for pair i, whatever the kind (0: no answer yet).
+struct AlnSink {
+    SinkKind kind = SinkKind::bytes;
+    int64_t* len = nullptr;
+    AlnTally* tally = nullptr;
+    // bytes: pair i's go to buf + base[i] (room: query length + reference length), in forward order; ioc_align_pairs_ops packs them
+    // when the call is over
+    struct Bytes {
+        uint8_t* buf = nullptr;
+        const int64_t* base = nullptr;
+    } bytes;
+    // reduced, optional (with_stats): pair i's record goes to stats[i]
+    bool with_stats = false;
+    ioc_aln_stats* stats = nullptr;
+    // reduced, optional: pair i's alignment is added to the rows from row_base[i] on of the call's tables on the device, ONCE:
+    // piled[i] says that it has been, whichever run did it
+    struct Pile {
+        PileKind kind = PileKind::none;
+        ioc_pileup_col* cols = nullptr;   // (device) counts: every kind
+        ioc_pileup_ins* ins = nullptr;    // (device) ins: what the pairs insert
+        ioc_pileup_col* wcols = nullptr;  // (device) weighted: the sums of weights, and ...
+        ioc_pileup_ins* wins = nullptr;   // (device) ... those of what the pairs insert
+        int64_t rows = 0;                 // records per table
+        const int64_t* row_base = nullptr;
+        uint8_t* piled = nullptr;
+    } pile;
+
+    bool reduced() const { return kind == SinkKind::reduced; }
+    bool has_stats() const { return reduced() && with_stats; }
+    bool has_pile() const { return reduced() && pile.kind != PileKind::none; }
+    // what the tables hold of the device for the whole call (ck_budget's `held`)
+    uint64_t pile_bytes() const
+    {
+        if (!has_pile()) return 0;
+        const uint64_t per_row = pile.kind == PileKind::counts ? sizeof(ioc_pileup_col)
+                                 : pile.kind == PileKind::ins  ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins)
+                                                               : 2 * sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins);
+        return uint64_t(pile.rows) * per_row;
+    }
+    OpsLayout layout(size_t np) const { return ops_layout(np, kind, reduced() ? pile.kind : PileKind::none); }
+
+    // Pair i has an empty sequence (query length n, reference length m, one of them 0): all of it is one free end gap, and no walk —
+    // n + m bytes 'i' or 'd', a record that is all lead_i or lead_d, nothing for a pile.
+    void answer_empty(size_t i, int64_t n, int64_t m) const
+    {
+        const int64_t l = n + m;
+        if (!reduced()) memset(bytes.buf + bytes.base[i], n ? 'i' : 'd', size_t(l));
+        if (has_stats()) {
+            ioc_aln_stats& s = stats[i];
+            s = ioc_aln_stats{};
+            s.length = int32_t(l);
+            (n ? s.lead_i : s.lead_d) = int32_t(l);
+        }
+        len[i] = l;
+    }
+
+    // A re-run of the caller's pairs idx: the sink of pair x of the re-run is that of the caller's pair idx[x].  The bytes go straight
+    // to the caller's regions and the tables are the call's own; lengths, records and `piled` are the re-run's until take_back.
+    AlnSubSink subset(const std::vector<int32_t>& idx) const;
+    // ... and what the re-run left, into the caller's arrays: every pair of idx gets the re-run's length and record (nothing, if the
+    // re-run had no answer either) and keeps `piled` if it was or has now been added
+    void take_back(const std::vector<int32_t>& idx, const AlnSubSink& sub) const;
+};
+
+struct AlnSubSink {
+    AlnSink sink;
+    std::vector<int64_t> len, base, row_base;
+    std::vector<ioc_aln_stats> stats;
+    std::vector<uint8_t> piled;
+    AlnSubSink() = default;
+    AlnSubSink(AlnSubSink&&) = default;  // (a moved vector keeps its block: sink's pointers stay good; there is no copy)
+};
+
+inline AlnSubSink AlnSink::subset(const std::vector<int32_t>& idx) const
+{
+    AlnSubSink s;
+    s.sink = *this;
+    s.len.assign(idx.size(), 0);
+    s.sink.len = s.len.data();
+    if (!reduced()) {
+        for (int32_t i : idx) s.base.push_back(bytes.base[i]);
+        s.sink.bytes.base = s.base.data();
+    }
+    if (has_stats()) {
+        s.stats = std::vector<ioc_aln_stats>(idx.size(), ioc_aln_stats{});
+        s.sink.stats = s.stats.data();
+    }
+    if (has_pile()) {
+        for (int32_t i : idx) s.row_base.push_back(pile.row_base[i]), s.piled.push_back(pile.piled[i]);
+        s.sink.pile.row_base = s.row_base.data();
+        s.sink.pile.piled = s.piled.data();
+    }
+    return s;
+}
+
+inline void AlnSink::take_back(const std::vector<int32_t>& idx, const AlnSubSink& sub) const
+{
+    for (size_t x = 0; x < idx.size(); ++x) {
+        len[idx[x]] = sub.len[x];
+        if (has_stats()) stats[idx[x]] = sub.stats[x];
+        if (has_pile()) pile.piled[idx[x]] = sub.piled[x];
+    }
+}
+
+#pragma GCC visibility pop
+
+#endif

@@ -1,0 +1,341 @@
+// ioc_align_sinks.cpp — the entry points of the batched GPU aligner that ask for the alignment itself, and the consensus call on
+// top of them: each describes where the walks' operation bytes go (AlnSink, ioc_align_sink.h) and runs ioc_align_pairs_sink
+// (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ioc_align_sink.h"
+#include "ioc_internal.h"
+
+namespace {
+
+struct AlnCall {  // what every aligning entry point passes on
+    int32_t n_pairs;
+    const ioc_aln_pair* pairs;
+    int32_t k, match, mismatch, gap_extend;
+    int32_t* score;
+    int64_t* windows;
+    double* ratio;
+    int run(ioc_ctx* c, const AlnSink* sink) const { return ioc_align_pairs_sink(c, n_pairs, pairs, k, match, mismatch, gap_extend, score, windows, ratio, sink); }
+};
+
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+}  // namespace
+
+// (pile_call_bound, pile_call_device, pileup_call_tables and align_pairs_polish stand inside extern "C", where they have always
+// stood: their plain names stay in the library's symbol list)
+extern "C" {
+namespace {
+
+// the segments' bound: what ioc_host_pileup_call asks of cap, summed
+int64_t pile_call_bound(const std::vector<IocPileSeg>& segs)
+{
+    int64_t b = 0;
+    for (const IocPileSeg& s : segs) b += int64_t(s.rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(s.rlen) + 1);
+    return b;
+}
+
+// where a consensus call reads its frames and leaves what it called
+struct PileCall {
+    const std::vector<IocPileSeg>& segs;
+    const uint8_t* d_frames;
+    uint64_t frame_bytes;
+    int32_t min_depth;
+    char *out_seq, *out_qual;
+    int64_t* out_off;
+    ioc_polish_stats* out_stats;
+};
+
+// The call kernels over tables that lie on the device (n_rows records each), and what they made copied back: a_call holds
+// [segments][seg_len][out_off][records][sequence][qualities].  The kernels' device time is added to t.ms_call, the host's time
+// over the copies and their bytes to t.ms_copy / t.copied.
+int pile_call_device(ioc_ctx* c, const PileCall& pc, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
+                     const ioc_pileup_col* d_gate /* the weighted call: d_cols / d_ins are weights, this the counts; else NULL */, int64_t n_rows,
+                     AlnTally& t)
+{
+    const size_t n = pc.segs.size();
+    const size_t bound = size_t(pile_call_bound(pc.segs));
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t o_seg = 0, o_len = up16(n * sizeof(IocPileSeg)), o_off = o_len + up16(n * 8), o_st = o_off + up16((n + 1) * 8),
+                 o_seq = o_st + n * sizeof(ioc_polish_stats), o_qual = o_seq + up16(bound), total = o_qual + up16(bound);
+    IOC_TRY(ioc_reserve(c, c->a_call, total));
+    uint8_t* p = static_cast<uint8_t*>(c->a_call.p);
+    IOC_CHK(c, hipMemcpyAsync(p + o_seg, pc.segs.data(), n * sizeof(IocPileSeg), hipMemcpyHostToDevice, c->stream));
+    EventSet ev;
+    ev.v.assign(2, nullptr);
+    for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
+    IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
+    if (d_gate)
+        IOC_CHK(c, iock_pile_call_weighted(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_gate, d_cols, d_ins,
+                                           uint64_t(n_rows), pc.d_frames, pc.frame_bytes, pc.min_depth, reinterpret_cast<int64_t*>(p + o_len),
+                                           reinterpret_cast<ioc_polish_stats*>(p + o_st), reinterpret_cast<int64_t*>(p + o_off), p + o_seq,
+                                           p + o_qual, uint64_t(bound)));
+    else
+        IOC_CHK(c, iock_pile_call(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_cols, d_ins, uint64_t(n_rows), pc.d_frames,
+                                  pc.frame_bytes, pc.min_depth, reinterpret_cast<int64_t*>(p + o_len), reinterpret_cast<ioc_polish_stats*>(p + o_st),
+                                  reinterpret_cast<int64_t*>(p + o_off), p + o_seq, p + o_qual, uint64_t(bound)));
+    IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    IOC_CHK(c, hipMemcpy(pc.out_off, p + o_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+    const int64_t len = pc.out_off[n];
+    if (len < 0 || size_t(len) > bound) return ioc_fail(c, IOC_ERR_HIP, "the consensus call returned a length outside its bound");
+    if (pc.out_stats) IOC_CHK(c, hipMemcpy(pc.out_stats, p + o_st, n * sizeof(ioc_polish_stats), hipMemcpyDeviceToHost));
+    if (len > 0) {
+        IOC_CHK(c, hipMemcpy(pc.out_seq, p + o_seq, size_t(len), hipMemcpyDeviceToHost));
+        IOC_CHK(c, hipMemcpy(pc.out_qual, p + o_qual, size_t(len), hipMemcpyDeviceToHost));
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) t.ms_call += double(ms);
+    t.ms_copy += ms_since(t0);
+    t.copied += int64_t((n + 1) * 8 + (pc.out_stats ? n * sizeof(ioc_polish_stats) : 0) + 2 * size_t(len));
+    return IOC_OK;
+}
+
+// ioc_pileup_call (wcols NULL: cols / ins are called by majority) and ioc_pileup_call_weighted (cols gates, wcols / ins decide).
+// The tables are uploaded and called where they lie then (ioc_pile_call.hip); the frames travel as one pool of bytes.
+int pileup_call_tables(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
+                       const ioc_pileup_col* wcols, const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
+                       int64_t* out_off, ioc_polish_stats* out_stats)
+{
+    std::vector<IocPileSeg> segs(static_cast<size_t>(n_segs));
+    int64_t n_rows = 0, frame_bytes = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (rlen[g] < 0 || frame_off[g] < 0 || (rlen[g] > 0 && !frames)) return ioc_fail(c, IOC_ERR_ARG, "ioc_pileup_call: segment " + std::to_string(g) + " has a negative length or frame offset");
+        if (int64_t(rlen[g]) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen[g]) + 1) > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
+            return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_call: segment " + std::to_string(g) + " may call more than 2^31 - 1 bytes");
+        segs[size_t(g)] = IocPileSeg{n_rows, frame_off[g], rlen[g], 0};
+        n_rows += int64_t(rlen[g]) + 1;
+        frame_bytes = std::max(frame_bytes, frame_off[g] + rlen[g]);
+    }
+    const int64_t bound = pile_call_bound(segs);
+    if (cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_call: cap " + std::to_string(cap) + " below the bound " + std::to_string(bound));
+    if (bound > 0 && (!out_seq || !out_qual)) return IOC_ERR_ARG;
+    out_off[0] = 0;
+    if (n_segs == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
+    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
+    IOC_TRY(ioc_reserve(c, c->a_pile_ins, b_ins));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(frame_bytes)));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pile.p, cols, b_cols, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pile_ins.p, ins, b_ins, hipMemcpyHostToDevice, c->stream));
+    if (wcols) {
+        IOC_TRY(ioc_reserve(c, c->a_pile_w, b_cols));
+        IOC_CHK(c, hipMemcpyAsync(c->a_pile_w.p, wcols, b_cols, hipMemcpyHostToDevice, c->stream));
+    }
+    if (frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(frame_bytes), hipMemcpyHostToDevice, c->stream));
+    AlnTally t;
+    const PileCall pc{segs, static_cast<const uint8_t*>(d_frames.p), uint64_t(frame_bytes), min_depth, out_seq, out_qual, out_off, out_stats};
+    IOC_TRY(pile_call_device(c, pc, wcols ? c->a_pile_w.as<ioc_pileup_col>() : c->a_pile.as<ioc_pileup_col>(), c->a_pile_ins.as<ioc_pileup_ins>(),
+                             wcols ? c->a_pile.as<ioc_pileup_col>() : nullptr, n_rows, t));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   consensus call: %d segments, %lld rows, %lld bytes called, k_pile_call%s %.3f ms\n", n_segs, (long long)n_rows,
+                (long long)out_off[n_segs], wcols ? "<weighted>" : "", t.ms_call);
+    return IOC_OK;
+}
+
+// What ioc_align_pairs_pileup and the polish calls share.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it
+// (ins), or a_pile_w as [wcols][wins] (weighted) — are reserved and zeroed, the pairs aligned into them (k_ops_pileup adds, where
+// the walks' bytes lie, slice after slice and re-run after re-run) and, where `call` is given, called where they lie; then the
+// tables asked for are copied out, once.  out_ins: the second table of its kind (ins, or wins).
+static int align_pairs_piled(ioc_ctx* c, const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows,
+                             const PileCall* call, ioc_pileup_col* out_cols, ioc_pileup_col* out_wcols, ioc_pileup_ins* out_ins, AlnTally& t)
+{
+    IOC_CHK(c, hipSetDevice(c->device));
+    const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
+    std::vector<int64_t> len(size_t(a.n_pairs), 0);
+    std::vector<uint8_t> piled(size_t(a.n_pairs), 0);
+    const bool weighted = kind == PileKind::weighted;
+    DevBuf* second = kind == PileKind::ins ? &c->a_pile_ins : weighted ? &c->a_pile_w : nullptr;  // [ins], or [wcols][wins]
+    const size_t b_second = weighted ? b_cols + b_ins : b_ins;
+    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
+    if (second) IOC_TRY(ioc_reserve(c, *second, b_second));
+    IOC_CHK(c, hipMemsetAsync(c->a_pile.p, 0, b_cols, c->stream));
+    if (second) IOC_CHK(c, hipMemsetAsync(second->p, 0, b_second, c->stream));
+    AlnSink::Pile pl{kind, c->a_pile.as<ioc_pileup_col>(), nullptr, nullptr, nullptr, n_rows, row_base, piled.data()};
+    if (kind == PileKind::ins) pl.ins = second->as<ioc_pileup_ins>();
+    if (weighted) pl.wcols = second->as<ioc_pileup_col>(), pl.wins = reinterpret_cast<ioc_pileup_ins*>(second->as<uint8_t>() + b_cols);  // (b_cols: a multiple of 32)
+    const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, out_stats != nullptr, out_stats, pl};
+    IOC_TRY(a.run(c, a.n_pairs > 0 ? &sink : nullptr));
+    if (call)
+        IOC_TRY(pile_call_device(c, *call, weighted ? pl.wcols : pl.cols, weighted ? pl.wins : pl.ins, weighted ? pl.cols : nullptr, n_rows, t));
+    else
+        IOC_CHK(c, hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    const struct { void* dst; const void* src; size_t bytes; } outs[] = {{out_cols, pl.cols, b_cols}, {out_wcols, pl.wcols, b_cols}, {out_ins, weighted ? pl.wins : pl.ins, b_ins}};
+    for (const auto& o : outs)
+        if (o.dst) {
+            IOC_CHK(c, hipMemcpy(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost));
+            t.copied += int64_t(o.bytes);
+        }
+    t.ms_copy += ms_since(t0);
+    return IOC_OK;
+}
+
+// ioc_align_pairs_pileup with the second table beside the first, and the call kernels over both where they lie: what comes back
+// is the called bytes (at most 7 per row), not the tables, unless they are asked for.  weighted (ioc_align_pairs_polish_weighted):
+// the weighted variant of k_ops_pileup adds the counts into the first table and the weights into two tables of a_pile_w, [wcols]
+// [wins], and the call is the weighted one; out_ins is then out_wins.
+int align_pairs_polish(ioc_ctx* c, const AlnCall& a, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair,
+                       int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                       ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins, bool weighted, ioc_pileup_col* out_wcols)
+{
+    if (!c || a.n_pairs < 0 || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (a.n_pairs > 0 && (!a.pairs || !seg_of_pair)) ||
+        (n_segs > 0 && (!segs || !out_polish)))
+        return IOC_ERR_ARG;
+    if (weighted && !c->aln_qual_set) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish_weighted: no qualities are set for the current pool (ioc_align_set_pool_qual)");
+    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
+    std::vector<IocPileSeg> ds(static_cast<size_t>(n_segs));
+    int64_t n_rows = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (segs[g].ref < 0 || segs[g].ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: segment " + std::to_string(g) + " refers to a sequence outside the pool");
+        const int64_t m = ioc_seq_len(c, segs[g].ref);
+        ds[size_t(g)] = IocPileSeg{n_rows, c->aln_offs[size_t(segs[g].ref)], int32_t(m), segs[g].ref_revcomp ? 1 : 0};
+        n_rows += m + 1;
+    }
+    std::vector<int64_t> row_base(size_t(a.n_pairs), 0);
+    for (int32_t i = 0; i < a.n_pairs; ++i) {
+        IOC_TRY(ioc_pair_in_pool(c, a.pairs[i]));
+        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: pair " + std::to_string(i) + " names no segment");
+        if (ioc_seq_len(c, a.pairs[i].ref) != ds[size_t(seg_of_pair[i])].rlen)
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_polish: the reference of pair " + std::to_string(i) + " is not as long as its segment's frame");
+        row_base[size_t(i)] = ds[size_t(seg_of_pair[i])].row0;
+    }
+    const int64_t bound = pile_call_bound(ds);
+    if (cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_polish: cap " + std::to_string(cap) + " below the bound " + std::to_string(bound));
+    if (bound > 0 && (!out_seq || !out_qual)) return IOC_ERR_ARG;
+    for (int32_t i = 0; i < a.n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    out_off[0] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    AlnTally t;
+    const PileCall pc{ds, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), min_depth, out_seq, out_qual, out_off, out_polish};
+    IOC_TRY(align_pairs_piled(c, a, weighted ? PileKind::weighted : PileKind::ins, out_stats, row_base.data(), n_rows, &pc, out_cols, out_wcols, out_ins, t));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: polish: %d segments, %lld rows, %.3f MB (called bytes, records, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup<%s> %.3f ms, k_pile_call%s %.3f ms%s\n",
+                n_segs, (long long)n_rows, double(t.copied) * 1e-6, out_cols || out_ins || out_wcols ? ", tables" : "", out_stats ? ", statistics" : "", t.ms_copy,
+                weighted ? "weighted" : "ins", t.ms_pileup, weighted ? "<weighted>" : "", t.ms_call, out_stats ? (", k_ops_stats " + std::to_string(t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+}  // namespace
+
+int64_t ioc_align_ops_bound(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs)
+{
+    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs)) return IOC_ERR_ARG;
+    int64_t bound = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        IOC_TRY(ioc_pair_in_pool(c, pairs[i]));
+        bound += ioc_seq_len(c, pairs[i].query) + ioc_seq_len(c, pairs[i].ref);
+    }
+    return bound;
+}
+
+// The walks write a pair's bytes into a region of its own of the caller's buffer (as long as the pair's share of the bound);
+// the regions are packed when all runs — the call's own, the re-runs' — are over.
+int ioc_align_pairs_ops(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                        int32_t* out_score, int64_t* out_windows, double* out_ratio, char* out_ops, int64_t ops_cap, int64_t* ops_off)
+{
+    if (!c || n_pairs < 0 || (n_pairs > 0 && !pairs) || !ops_off || ops_cap < 0 || (ops_cap > 0 && !out_ops)) return IOC_ERR_ARG;
+    const int64_t bound = ioc_align_ops_bound(c, n_pairs, pairs);
+    if (bound < 0) return int(bound);
+    if (ops_cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_ops: ops_cap " + std::to_string(ops_cap) + " below the bound " + std::to_string(bound));
+    std::vector<int64_t> base(size_t(n_pairs) + 1, 0), len(size_t(n_pairs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i) base[size_t(i) + 1] = base[size_t(i)] + ioc_seq_len(c, pairs[i].query) + ioc_seq_len(c, pairs[i].ref);
+    AlnTally t;
+    const AlnSink sink{SinkKind::bytes, len.data(), &t, {reinterpret_cast<uint8_t*>(out_ops), base.data()}};
+    IOC_TRY((AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}.run(c, &sink)));
+    ops_off[0] = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {  // (a packed position never lies behind the region's own)
+        if (len[size_t(i)] > 0 && ops_off[i] != base[size_t(i)]) memmove(out_ops + ops_off[i], out_ops + base[size_t(i)], size_t(len[size_t(i)]));
+        ops_off[i + 1] = ops_off[i] + len[size_t(i)];
+    }
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: operation bytes: %.1f MB copied from the device in %.3f ms, %.1f MB packed\n", double(t.copied) * 1e-6, t.ms_copy,
+                double(ops_off[n_pairs]) * 1e-6);
+    return IOC_OK;
+}
+
+// The walks write a slice's bytes as for ioc_align_pairs_ops; k_ops_stats (ioc_ops_stats.hip) reduces them where they lie, and
+// the records of the run that counted — the call's own, a re-run's — end up in out_stats.
+int ioc_align_pairs_stats(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                          int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats)
+{
+    if (!c || n_pairs < 0 || (n_pairs > 0 && (!pairs || !out_stats))) return IOC_ERR_ARG;
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    std::vector<int64_t> len(size_t(n_pairs), 0);
+    AlnTally t;
+    const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, true, out_stats};
+    IOC_TRY((AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}.run(c, &sink)));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: alignment statistics: %lld records (%.3f MB with the lengths) copied from the device in %.3f ms, k_ops_stats %.3f ms\n",
+                (long long)t.records, double(t.copied) * 1e-6, t.ms_copy, t.ms_stats);
+    return IOC_OK;
+}
+
+// The walks write a slice's bytes as for ioc_align_pairs_ops; k_ops_pileup (ioc_ops_pileup.hip) adds them, where they lie, into a
+// table of the call's rows that stays on the device over the slices and the re-runs and is copied out once.
+int ioc_align_pairs_pileup(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                           int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t
+                           n_rows, ioc_pileup_col* out_cols)
+{
+    if (!c || n_pairs < 0 || n_rows < 0 || (n_pairs > 0 && (!pairs || !row_base || !out_cols))) return IOC_ERR_ARG;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        IOC_TRY(ioc_pair_in_pool(c, pairs[i]));
+        if (row_base[i] < 0 || row_base[i] > n_rows - ioc_seq_len(c, pairs[i].ref) - 1)
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_pileup: the rows of pair " + std::to_string(i) + " lie outside the table");
+    }
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    if (out_cols && n_rows > 0) memset(out_cols, 0, size_t(n_rows) * sizeof(ioc_pileup_col));
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    if (n_pairs == 0 || n_rows == 0) return a.run(c, nullptr);
+    AlnTally t;
+    IOC_TRY(align_pairs_piled(c, a, PileKind::counts, out_stats, row_base, n_rows, nullptr, out_cols, nullptr, nullptr, t));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: pileup: %lld rows, %.3f MB (table, lengths%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms%s\n",
+                (long long)n_rows, double(t.copied) * 1e-6, out_stats ? ", statistics" : "", t.ms_copy, t.ms_pileup,
+                out_stats ? (", k_ops_stats " + std::to_string(t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+int ioc_pileup_call(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
+                    const ioc_pileup_ins* ins, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats)
+{
+    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !ins))) return IOC_ERR_ARG;
+    return pileup_call_tables(c, n_segs, rlen, frames, frame_off, cols, nullptr, ins, min_depth, out_seq, out_qual, cap, out_off, out_stats);
+}
+
+int ioc_pileup_call_weighted(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                             const ioc_pileup_col* cols, const ioc_pileup_col* wcols, const ioc_pileup_ins* wins, int32_t min_depth, char* out_seq, char* out_qual, int64_t
+                             cap, int64_t* out_off, ioc_polish_stats* out_stats)
+{
+    if (!c || n_segs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off || !cols || !wcols || !wins))) return IOC_ERR_ARG;
+    return pileup_call_tables(c, n_segs, rlen, frames, frame_off, cols, wcols, wins, min_depth, out_seq, out_qual, cap, out_off, out_stats);
+}
+
+int ioc_align_pairs_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                           int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                           const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
+                           int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins)
+{
+    return align_pairs_polish(c, AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs,
+                              seg_of_pair, min_depth, out_seq, out_qual, cap, out_off, out_polish, out_cols, out_ins, false, nullptr);
+}
+
+int ioc_align_pairs_polish_weighted(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t
+                                    gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                    const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, char* out_seq, char* out_qual, int64_t
+                                    cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols, ioc_pileup_col* out_wcols,
+                                    ioc_pileup_ins* out_wins)
+{
+    return align_pairs_polish(c, AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs,
+                              seg_of_pair, min_depth, out_seq, out_qual, cap, out_off, out_polish, out_cols, out_wins, true, out_wcols);
+}
+
+}  // extern "C"

@@ -310,6 +310,34 @@ struct IocCandTable {
 };
 int ioc_query_candidates_many(ioc_ctx* c, const std::vector<int>& qs, std::vector<IocCandTable>& out);
 
+// events of a call's launches (the aligner: three per slice — the forward pass, the traceback, the end), destroyed on every way
+// out, the IOC_CHK returns included
+struct __attribute__((visibility("hidden"))) EventSet {
+    std::vector<hipEvent_t> v;
+    ~EventSet()
+    {
+        for (auto& e : v)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// the aligner's sequence pool (ioc_align_set_pool): the length of sequence `id`, and the one check that a pair's two lie in it
+static inline int64_t ioc_seq_len(const ioc_ctx* c, int32_t id) { return c->aln_offs[size_t(id) + 1] - c->aln_offs[size_t(id)]; }
+static inline int ioc_pair_in_pool(ioc_ctx* c, const ioc_aln_pair& a)
+{
+    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
+    if (a.query < 0 || a.query >= n_seqs || a.ref < 0 || a.ref >= n_seqs)
+        return ioc_fail(c, IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
+    return IOC_OK;
+}
+
+// ioc_align_gpu.hip: ioc_align_pairs with the walks' operation bytes handed to `sink` (ioc_align_sink.h; null: no walk emits) —
+// what the emitting entry points of ioc_align_sinks.cpp run
+struct AlnSink;
+__attribute__((visibility("hidden"))) int ioc_align_pairs_sink(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
+                                                               int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
+                                                               double* out_ratio, const AlnSink* sink);
+
 // ioc_ops_stats.hip: the statistics (ioc_host_ops_stats) of the operation strings an emitting slice of the aligner left on the
 // device — pair ord[x]'s string is buf[end[pid] - len[pid] .. end[pid]), its record out[x]; a pair with len == 0, len > room or
 // len > end is skipped
