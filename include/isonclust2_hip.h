@@ -386,6 +386,48 @@ int ioc_host_ops_pileup_weighted(const char* ops, int64_t len, const char* query
 int64_t ioc_host_pileup_call_weighted(const ioc_pileup_col* cols, const ioc_pileup_col* wcols, const ioc_pileup_ins* wins,
                                       const char* frame, int32_t rlen, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
                                       ioc_polish_stats* st);
+/* ---- the variable sites of a reference and every read's alleles at them: where the reads of a cluster disagree, and which
+ * read is on which side.  All arithmetic in 64-bit integers; no floats. ----
+ * The projection of one operation string on its reference: what ONE read says at every row.  `base` and `insf` are rlen + 1
+ * bytes each; the call sets base[0 .. rlen] to IOC_ALLELE_NONE and insf[0 .. rlen] to 0 and then walks the string as
+ * ioc_host_ops_pileup does (r / q: reference / query bases consumed): 'd' r++; 'i' q++; '=' / 'X' base[r] = the channel of
+ * query[q] (0 .. 4 for A C G T other), r++, q++; 'D' base[r] = IOC_ALLELE_DEL, r++; 'I' insf[r] = 1 where the byte before it is
+ * not 'I', q++.  So base[r] != IOC_ALLELE_NONE exactly where the read covers row r, and the sum of the projections of many reads
+ * is their pileup: the six counters of ioc_pileup_col count the values 0 .. 5 of base[r], ins_runs counts insf[r] (of strings
+ * with at most one run of 'I' in front of a row, as every aligner's are: a second run there would count again).  The inputs
+ * ioc_host_ops_pileup refuses are refused (IOC_ERR_ARG), with both outputs untouched. */
+#define IOC_ALLELE_DEL 5
+#define IOC_ALLELE_NONE 7
+int ioc_host_ops_project(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, uint8_t* base, uint8_t* insf);
+/* One variable site.  kind IOC_SITE_BASE: the alleles are the channels 0 .. 5 (A C G T other del) of row `row`; kind
+ * IOC_SITE_INS: the alleles are 0 (no insertion in front of row `row`) and 1 (one).  depth / n_major / n_minor are the 64-bit
+ * values of the definition below, saturated at 2^32 - 1. */
+#define IOC_SITE_BASE 0
+#define IOC_SITE_INS 1
+typedef struct {
+    int32_t row, kind;
+    int32_t major, minor;
+    uint32_t depth, n_major, n_minor;
+    uint32_t reserved; /* 0 */
+} ioc_pile_site;       /* 32 bytes */
+/* The definition of the sites of one reference from its table of counts (rlen + 1 rows).  depth(p) as in ioc_host_pileup_call;
+ * D(p) = depth(p) for p < rlen, depth(rlen - 1) for p == rlen, 0 for rlen == 0; need(D) = max(min_alt, (min_pct * D + 99) / 100).
+ * For p = 0 .. rlen in turn, the insertion site of row p before its base site:
+ *  - insertion site: with = ins_runs(p), without = D(p) > with ? D(p) - with : 0.  A site iff D(p) >= min_depth,
+ *    with >= need(D(p)) and without >= need(D(p)).  major = 1 where with > without, else 0 (a tie goes to "absent"); depth = D(p);
+ *  - base site, p < rlen: iff depth(p) >= min_depth and n_minor >= need(depth(p)), where major is the first maximal of the six
+ *    counters in the order A C G T other del and minor the first maximal of the other five in that order.
+ * The first max_sites sites in this order are written to `out`; returns how many were written, and *n_found (may be NULL) is how
+ * many there were: n_found > max_sites says that the list was cut.  IOC_ERR_ARG for min_depth < 1, min_alt < 1, min_pct outside
+ * 1 .. 50, max_sites < 1, rlen < 0 or a NULL cols / out. */
+int64_t ioc_host_pileup_sites(const ioc_pileup_col* cols, int32_t rlen, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                              int32_t max_sites, ioc_pile_site* out, int64_t* n_found);
+/* The alleles of one read (its projection) at n_sites sites of its reference: out[s] = base[row] at a base site; at an insertion
+ * site insf[row] where the read spans the row — base[row] != IOC_ALLELE_NONE for row < rlen, rlen > 0 and
+ * base[rlen - 1] != IOC_ALLELE_NONE for row == rlen — else IOC_ALLELE_NONE.  IOC_ERR_ARG for a negative count or length, a NULL
+ * that is needed, a row outside 0 .. rlen, a base site at row rlen and a kind that is neither; `out` is then untouched. */
+int ioc_host_site_alleles(const uint8_t* base, const uint8_t* insf, int32_t rlen, const ioc_pile_site* sites, int32_t n_sites,
+                          uint8_t* out);
 int32_t ioc_host_gap_open(double e1_plus_e2);                     /* setGapOpen,  src/cluster.cpp:425-440 */
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
@@ -497,6 +539,35 @@ int ioc_align_pairs_polish_weighted(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln
                                     const int32_t* seg_of_pair, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
                                     int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_cols,
                                     ioc_pileup_col* out_wcols, ioc_pileup_ins* out_wins);
+/* The sites of many references at once ON THE DEVICE (ioc_pile_sites.hip), from a host table that is uploaded: segment g is a
+ * reference of rlen[g] bases, its rows laid out as in ioc_pileup_call.  Segment g's sites, as ioc_host_pileup_sites defines them
+ * (at most max_sites of them), stand at out_sites[site_off[g] .. site_off[g + 1]) — packed, in segment order; site_off has
+ * n_segs + 1 entries — and n_found[g] is how many it has in all.  IOC_ERR_ARG for what ioc_host_pileup_sites refuses;
+ * IOC_ERR_CAPACITY, with nothing written, for sites_cap below the sum over the segments of min(max_sites, 2 * rlen + 1). */
+int ioc_pileup_sites(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const ioc_pileup_col* cols, int32_t min_depth,
+                     int32_t min_alt, int32_t min_pct, int32_t max_sites, ioc_pile_site* out_sites, int64_t sites_cap,
+                     int64_t* site_off, int64_t* n_found);
+/* ioc_align_pairs + the variable sites of every segment and every pair's alleles at them, all ON THE DEVICE: the pairs are
+ * aligned, pair i is piled into the table of counts at the rows of segment seg_of_pair[i] (k_ops_pileup) and projected into two
+ * byte planes of its own (k_ops_project: ioc_host_ops_project of its operation string, 2 * (reference length + 1) bytes), the
+ * sites of every segment are found where the table lies (ioc_host_pileup_sites: out_sites, site_off, n_found as from
+ * ioc_pileup_sites), and pair i's alleles at the kept sites of its segment (ioc_host_site_alleles) stand at
+ * out_alleles[allele_off[i] .. allele_off[i + 1]) — one byte per (read, site); allele_off has n_pairs + 1 entries.  What comes
+ * back is that, not the alignments.  Segments as in ioc_align_pairs_polish, and its refusals (a pair whose reference length
+ * differs from its segment's frame, seg_of_pair outside the segments, a segment or pair outside the pool — that the pairs of
+ * a segment take their references in one frame stays the caller's business, as there); IOC_ERR_ARG as well for the thresholds
+ * ioc_host_pileup_sites refuses.  IOC_ERR_CAPACITY, with nothing written, for sites_cap below the
+ * sum over the segments of min(max_sites, 2 * rlen + 1) and alleles_cap below the sum over the pairs of the same bound of their
+ * segment.  A segment without pairs has no sites.  out_cols (the table, sum of rlen + 1 rows), out_stats and any of out_score /
+ * out_windows / out_ratio may be NULL.  An emitting call like the others: always exact, no verdict threshold,
+ * IOC_ALIGN_VARIANT=carry not honoured; the table (32 bytes per row) and the planes count against the checkpoint arena's budget,
+ * every pair is added and projected exactly once. */
+int ioc_align_pairs_alleles(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                            int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio,
+                            ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair,
+                            int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites, ioc_pile_site* out_sites,
+                            int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap,
+                            int64_t* allele_off, ioc_pileup_col* out_cols);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

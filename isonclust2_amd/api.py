@@ -190,6 +190,58 @@ def pileup_call_weighted(cols, wcols, wins, frame, min_depth=3, cap=None):
     return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in POLISH_STATS_FIELDS}
 
 
+# ioc_pile_site as a numpy record, and the allele bytes
+PILE_SITE_DTYPE = np.dtype([(n, np.int32) for n in ("row", "kind", "major", "minor")] + [(n, np.uint32) for n in ("depth", "n_major", "n_minor", "reserved")])
+ALLELE_DEL, ALLELE_NONE = _lib.ALLELE_DEL, _lib.ALLELE_NONE
+SITE_BASE, SITE_INS = _lib.SITE_BASE, _lib.SITE_INS
+
+
+def pileup_sites_bound(rlen, max_sites):
+    """What a site search of a reference of rlen bases may keep at most: min(max_sites, 2 * rlen + 1)."""
+    return min(int(max_sites), 2 * int(rlen) + 1)
+
+
+def ops_project(ops, query, rlen):
+    """ioc_host_ops_project: what one read says at every row of its reference — (base, insf), two uint8 arrays of rlen + 1 bytes:
+    base[r] the channel 0 .. 4 of the read's base at reference position r, ALLELE_DEL where it deletes it, ALLELE_NONE where it does
+    not cover it; insf[r] 1 where it inserts in front of r.  ValueError for what ops_pileup refuses."""
+    base, insf = np.full(rlen + 1, 0xEE, np.uint8), np.full(rlen + 1, 0xEE, np.uint8)
+    rc = _lib.load().ioc_host_ops_project(bytes(ops), len(ops), bytes(query), len(query), int(rlen), base.ctypes.data, insf.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_project failed ({rc})")
+    return base, insf
+
+
+def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
+    """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
+    returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
+    many there are in all.  IocError for thresholds outside their ranges."""
+    cols = np.ascontiguousarray(cols, PILEUP_DTYPE)
+    if cols.ndim != 1 or len(cols) < 1:
+        raise ValueError("cols must hold rlen + 1 rows")
+    rlen = len(cols) - 1
+    out, found = np.zeros(max(pileup_sites_bound(rlen, max(int(max_sites), 1)), 1), PILE_SITE_DTYPE), C.c_int64(0)
+    n = _lib.load().ioc_host_pileup_sites(cols.ctypes.data, rlen, int(min_depth), int(min_alt), int(min_pct), int(max_sites), out.ctypes.data,
+                                          C.byref(found))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_pileup_sites")
+    return out[:n].copy(), int(found.value)
+
+
+def site_alleles(base, insf, sites):
+    """ioc_host_site_alleles: the alleles of one read (its projection, ops_project) at `sites` (PILE_SITE_DTYPE) — one uint8 per
+    site: the channel, ALLELE_DEL or ALLELE_NONE at a base site; 0 / 1 at an insertion site the read spans, else ALLELE_NONE."""
+    base, insf = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(insf, np.uint8)
+    sites = np.ascontiguousarray(sites, PILE_SITE_DTYPE)
+    if base.shape != insf.shape or base.ndim != 1 or len(base) < 1:
+        raise ValueError("base and insf must hold rlen + 1 bytes each")
+    out = np.zeros(max(len(sites), 1), np.uint8)
+    rc = _lib.load().ioc_host_site_alleles(base.ctypes.data, insf.ctypes.data, len(base) - 1, sites.ctypes.data, len(sites), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_site_alleles failed ({rc})")
+    return out[:len(sites)]
+
+
 def ops_to_comp(ops):
     """The comparison string of an operation string: '|' where the bases are equal, ' ' in every other column."""
     return bytes(ops).translate(bytes(0x7C if b == 0x3D else 0x20 for b in range(256)))
@@ -567,6 +619,65 @@ class Context:
         it (align_set_pool_qual first).  Returns the same dict; with tables=True `cols` (the counts, as align_pairs_polish has
         them), `wcols` and `wins` (the sums of weights) and `row0`."""
         return self._align_pairs_polish(True, pairs, k, segs, seg_of_pair, min_depth, stats, tables, cap, match, mismatch, gap_extend)
+
+    def pileup_sites(self, rlen, cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096, cap=None):
+        """ioc_pileup_sites: the variable sites of many references at once on the device, from a host table — segment g's
+        rlen[g] + 1 rows of `cols` following those of the earlier segments.  Returns ([sites per segment], n_found): arrays of
+        PILE_SITE_DTYPE, each segment as pileup_sites (the function) defines it, and how many sites each has in all."""
+        rlen = np.ascontiguousarray(rlen, np.int32)
+        n = len(rlen)
+        n_rows = int(rlen.astype(np.int64).sum()) + n
+        cols = np.ascontiguousarray(cols, PILEUP_DTYPE)
+        if cols.shape != (n_rows,):
+            raise ValueError(f"cols must hold {n_rows} rows")
+        bound = sum(pileup_sites_bound(r, max(int(max_sites), 1)) for r in rlen)
+        cap = bound if cap is None else int(cap)
+        sites, off, found = np.zeros(max(cap, 1), PILE_SITE_DTYPE), np.zeros(n + 1, np.int64), np.zeros(max(n, 1), np.int64)
+        self._chk(self.L.ioc_pileup_sites(self.h, n, _p(rlen, C.c_int32) if n else None, cols.ctypes.data if n else None, int(min_depth),
+                                          int(min_alt), int(min_pct), int(max_sites), sites.ctypes.data, cap, _p(off, C.c_int64),
+                                          _p(found, C.c_int64)))
+        return [sites[off[g]:off[g + 1]].copy() for g in range(n)], found[:n]
+
+    def align_pairs_alleles(self, pairs, k, segs, seg_of_pair, min_depth=3, min_alt=3, min_pct=25, max_sites=4096, stats=False, tables=False,
+                            match=2, mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_alleles: align_pairs, the pileup of every segment, its variable sites and every pair's alleles at them,
+        all on the device — segs and seg_of_pair as for align_pairs_polish.  Returns a dict: score, windows, ratio, `sites` (a list
+        of PILE_SITE_DTYPE arrays per segment, at most max_sites each), `n_found` (sites per segment in all), `alleles` (a list of
+        uint8 arrays per pair: one byte per kept site of its segment — the channel 0 .. 4, ALLELE_DEL or ALLELE_NONE at a base site,
+        0 / 1 or ALLELE_NONE at an insertion site), with stats=True `stats` (ALN_STATS_DTYPE per pair), with tables=True `cols`
+        (the table of counts) and `row0` (the first row per segment)."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr = (_lib.PolishSeg * max(ns, 1))()
+        for g, (ref, rc) in enumerate(segs):
+            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair must hold one entry per pair")
+        offs = self.align_pool_offsets()
+        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
+        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
+        n_rows = sum(rlen) + ns
+        per_seg = [pileup_sites_bound(r, max(int(max_sites), 1)) for r in rlen]
+        s_cap = sum(per_seg)
+        a_cap = sum(per_seg[g] for g in sop if 0 <= g < ns)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        sites, s_off, found = np.zeros(max(s_cap, 1), PILE_SITE_DTYPE), np.zeros(ns + 1, np.int64), np.zeros(max(ns, 1), np.int64)
+        alleles, a_off = np.zeros(max(a_cap, 1), np.uint8), np.zeros(n + 1, np.int64)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        self._chk(self.L.ioc_align_pairs_alleles(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns,
+                                                 sarr, _p(sop, C.c_int32), int(min_depth), int(min_alt), int(min_pct), int(max_sites),
+                                                 sites.ctypes.data, s_cap, _p(s_off, C.c_int64), _p(found, C.c_int64), alleles.ctypes.data, a_cap,
+                                                 _p(a_off, C.c_int64), cols.ctypes.data if tables and n_rows else None))
+        out = {"score": score, "windows": win, "ratio": ratio, "sites": [sites[s_off[g]:s_off[g + 1]].copy() for g in range(ns)],
+               "n_found": found[:ns], "alleles": [alleles[a_off[i]:a_off[i + 1]].copy() for i in range(n)]}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out["cols"] = cols
+            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
+        return out
 
     # ---- sort-stage feeders --------------------------------------------------------------------
     def qual_scores(self, offs, qual, k):

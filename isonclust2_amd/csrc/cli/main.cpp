@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -959,6 +960,20 @@ static int main_cluster(int argc, char** argv)
 // dump --polish --polish-weighted: the same records, order and frames, called by weight (ioc_align_pairs_polish_weighted): every
 // read votes with the base qualities of its line as cluster_fastq/<id>.fq has it (reversed with the read when its strand is
 // -1), the pool's qualities being the lines e is computed from already.  The header gains a last field " weighted=1".
+//
+// dump --sites: <outdir>/cluster_sites.tsv and <outdir>/read_alleles.tsv from the same pairs, groups and frames
+// (ioc_align_pairs_alleles: the table, every read's projection, the sites and the alleles on the device; one byte per read and
+// site comes back).  cluster_sites.tsv: for every cluster in cluster order one row per variable site of its representative —
+// position, kind (base | ins: an insertion in front of the position), depth, and the two alleles with their counts, written
+// A C G T N - at a base site, '.' (absent) and '+' (present) at an insertion site; a cluster cut at --sites-max gets a line
+// "# cluster X: kept K of F sites".  read_alleles.tsv: one row per row read_stats.tsv has, the read's allele at every kept site
+// of its cluster as one character, '?' where the read does not cover the site, "*" for a cluster without sites.  Beside
+// --read-stats and --pileup a group is still aligned once: the call returns the statistics and the table as well.  With
+// --polish a group is aligned a second time, for the second table.
+struct SitesOpt {
+    bool on = false;
+    int min_depth = 3, min_alt = 3, min_pct = 25, max_sites = 4096;
+};
 struct ReadStatRow {
     unsigned cls;
     int strand;
@@ -970,9 +985,10 @@ struct ReadStatRow {
     size_t qual_len;
 };
 static void write_read_reports(const Batch& b, const string& outdir, size_t n_rows, const std::function<ReadStatRow(size_t)>& row, bool want_stats,
-                               bool want_pileup, int polish_min_depth /* 0: no --polish */, bool polish_weighted)
+                               bool want_pileup, int polish_min_depth /* 0: no --polish */, bool polish_weighted, const SitesOpt& sites_opt)
 {
-    const bool want_polish = polish_min_depth > 0, want_groups = want_pileup || want_polish;
+    const bool want_polish = polish_min_depth > 0, want_sites = sites_opt.on, want_segs = want_polish || want_sites,
+               want_groups = want_pileup || want_segs;
     constexpr size_t POOL_MAX = size_t(256) << 20;
     const int k = b.SortArgs.KmerSize;
     std::vector<std::vector<size_t>> rows_of(b.Cls.size());  // per cluster with a consensus record: its rows, in the order of clusters.tsv
@@ -988,6 +1004,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         int64_t windows = 0;
         ioc_aln_stats st{};
         size_t rep_len = 0;
+        string alleles;  // (--sites) one character per kept site of the read's cluster
     };
     std::vector<Result> res(kept.size());
     ioc_ctx* c = kept.empty() ? nullptr : make_ctx();
@@ -1019,6 +1036,33 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
     std::vector<ioc_polish_stats> pol;
     std::ofstream polish_out;
     if (want_polish) create_file(outdir + "/cluster_polished.fq", polish_out);
+    // (--sites) what the call returned for the group's segments
+    std::vector<ioc_pile_site> sites;
+    std::vector<int64_t> site_off, site_found;
+    std::ofstream sites_out;
+    if (want_sites) {
+        create_file(outdir + "/cluster_sites.tsv", sites_out);
+        sites_out << "ClusterId\tPos\tKind\tDepth\tMajor\tNMajor\tMinor\tNMinor\n";
+    }
+    auto allele_char = [](int32_t kind, int32_t a) { return kind == IOC_SITE_INS ? (a == 0 ? '.' : a == 1 ? '+' : '?') : (a >= 0 && a <= IOC_ALLELE_DEL ? "ACGTN-"[a] : '?'); };
+    auto write_sites = [&]() {
+        string text;
+        for (size_t x = 0; x < group_cls.size(); ++x) {
+            const int32_t g = group_seg[x];
+            if (g < 0) continue;
+            text.clear();
+            const int64_t s0 = site_off[size_t(g)], s1 = site_off[size_t(g) + 1];
+            if (site_found[size_t(g)] > s1 - s0)
+                text += "# cluster " + std::to_string(group_cls[x].first) + ": kept " + std::to_string(s1 - s0) + " of " + std::to_string(site_found[size_t(g)]) + " sites\n";
+            for (int64_t s = s0; s < s1; ++s) {
+                const ioc_pile_site& t = sites[size_t(s)];
+                text += std::to_string(group_cls[x].first) + '\t' + std::to_string(t.row) + '\t' + (t.kind == IOC_SITE_INS ? "ins" : "base") + '\t' +
+                        std::to_string(t.depth) + '\t' + allele_char(t.kind, t.major) + '\t' + std::to_string(t.n_major) + '\t' + allele_char(t.kind, t.minor) +
+                        '\t' + std::to_string(t.n_minor) + '\n';
+            }
+            sites_out.write(text.data(), std::streamsize(text.size()));
+        }
+    };
     auto frame_of = [&](size_t ci) {
         const auto& rep = b.Cls[ci]->at(0);
         string frame = rep->RawSeq->seq.str();  // (as cluster_cons.fq has it)
@@ -1067,6 +1111,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
     auto write_groups = [&]() {
         if (want_pileup) write_pileup();
         if (want_polish) write_polish();
+        if (want_sites && !segs.empty()) write_sites();
         group_cls.clear(), row_base.clear(), cols.clear();
         segs.clear(), seg_of_pair.clear(), seg_reads.clear(), group_seg.clear();
         group_rows = 0;
@@ -1084,6 +1129,33 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         std::vector<int32_t> sc(np);
         std::vector<int64_t> win(np);
         std::vector<ioc_aln_stats> st(want_stats ? np : 0);
+        bool have_first = false;  // the statistics and the first table are in st / cols already
+        if (want_sites) {
+            int64_t s_cap = 0, a_cap = 0;
+            std::vector<int64_t> seg_cap(segs.size());
+            for (size_t g = 0; g < segs.size(); ++g) {
+                const int64_t m = offs[size_t(segs[g].ref) + 1] - offs[size_t(segs[g].ref)];
+                seg_cap[g] = std::min<int64_t>(sites_opt.max_sites, 2 * m + 1);
+                s_cap += seg_cap[g];
+            }
+            for (size_t x = 0; x < np; ++x) a_cap += seg_cap[size_t(seg_of_pair[x])];
+            sites.assign(size_t(s_cap), ioc_pile_site{}), site_off.assign(segs.size() + 1, 0), site_found.assign(segs.size(), 0);
+            std::vector<uint8_t> alleles(size_t(a_cap) + 1);
+            std::vector<int64_t> allele_off(np + 1, 0);
+            if (want_pileup) cols.assign(size_t(group_rows), ioc_pileup_col{});
+            check(c, ioc_align_pairs_alleles(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
+                                             int32_t(segs.size()), segs.data(), seg_of_pair.data(), sites_opt.min_depth, sites_opt.min_alt, sites_opt.min_pct,
+                                             sites_opt.max_sites, sites.data(), s_cap, site_off.data(), site_found.data(), alleles.data(), a_cap,
+                                             allele_off.data(), want_pileup ? cols.data() : nullptr),
+                  "variable sites");
+            for (size_t x = 0; x < np; ++x) {
+                string& text = res[pair_row[x]].alleles;
+                const int64_t s0 = site_off[size_t(seg_of_pair[x])];
+                for (int64_t a = allele_off[x]; a < allele_off[x + 1]; ++a) text += allele_char(sites[size_t(s0 + a - allele_off[x])].kind, alleles[size_t(a)]);
+                if (text.empty()) text = "*";
+            }
+            have_first = true;
+        }
         if (want_polish) {
             int64_t cap = 0;
             for (const ioc_polish_seg& sg : segs) {
@@ -1092,22 +1164,25 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             }
             pol_seq.assign(size_t(cap), '\0'), pol_qual.assign(size_t(cap), '\0');
             pol_off.assign(segs.size() + 1, 0), pol.assign(segs.size(), ioc_polish_stats{});
-            if (want_pileup) cols.assign(size_t(group_rows), ioc_pileup_col{});
+            if (want_pileup && !have_first) cols.assign(size_t(group_rows), ioc_pileup_col{});
+            ioc_aln_stats* const st_out = want_stats && !have_first ? st.data() : nullptr;
+            ioc_pileup_col* const cols_out = want_pileup && !have_first ? cols.data() : nullptr;
             if (polish_weighted) {
                 // (the quality lines lie in `quals` in the order and at the lengths of the sequences in `pool`)
                 if (qoffs != offs) die("--polish-weighted: a quality line is not as long as its sequence!");
                 check(c, ioc_align_set_pool_qual(c, quals.data(), int64_t(quals.size())), "pool qualities");
-                check(c, ioc_align_pairs_polish_weighted(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr,
-                                                         want_stats ? st.data() : nullptr, int32_t(segs.size()), segs.data(), seg_of_pair.data(),
-                                                         polish_min_depth, &pol_seq[0], &pol_qual[0], cap, pol_off.data(), pol.data(),
-                                                         want_pileup ? cols.data() : nullptr, nullptr, nullptr),
+                check(c, ioc_align_pairs_polish_weighted(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, st_out,
+                                                         int32_t(segs.size()), segs.data(), seg_of_pair.data(), polish_min_depth, &pol_seq[0], &pol_qual[0],
+                                                         cap, pol_off.data(), pol.data(), cols_out, nullptr, nullptr),
                       "weighted polished consensus");
             } else {
-                check(c, ioc_align_pairs_polish(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
-                                                int32_t(segs.size()), segs.data(), seg_of_pair.data(), polish_min_depth, &pol_seq[0], &pol_qual[0], cap,
-                                                pol_off.data(), pol.data(), want_pileup ? cols.data() : nullptr, nullptr),
+                check(c, ioc_align_pairs_polish(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, st_out, int32_t(segs.size()),
+                                                segs.data(), seg_of_pair.data(), polish_min_depth, &pol_seq[0], &pol_qual[0], cap, pol_off.data(), pol.data(),
+                                                cols_out, nullptr),
                       "polished consensus");
             }
+            write_groups();
+        } else if (have_first) {
             write_groups();
         } else if (want_pileup) {
             cols.assign(size_t(group_rows), ioc_pileup_col{});
@@ -1147,7 +1222,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             row_base.insert(row_base.end(), rows_of[ci].size(), group_rows);
             group_rows += int64_t(rep->RawSeq->seq.size()) + 1;
         }
-        if (want_polish) {
+        if (want_segs) {
             seg_of_pair.insert(seg_of_pair.end(), rows_of[ci].size(), int32_t(segs.size()));
             seg_reads.push_back(int32_t(rows_of[ci].size()));
             segs.push_back(ioc_polish_seg{rep_seq, rep->MatchStrand == -1 ? 1 : 0});
@@ -1173,6 +1248,16 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
     }
     flush();
     if (c) ioc_ctx_destroy(c);
+    if (want_sites) {
+        std::ofstream out;
+        create_file(outdir + "/read_alleles.tsv", out);
+        out << "Read\tClusterId\tAlleles\n";
+        for (size_t y = 0; y < kept.size(); ++y) {
+            const ReadStatRow r = row(kept[y]);
+            out.write(r.id, std::streamsize(r.id_len));
+            out << '\t' << r.cls << '\t' << res[y].alleles << '\n';
+        }
+    }
     if (!want_stats) return;
 
     std::ofstream out;
@@ -1199,13 +1284,25 @@ static int main_dump(int argc, char** argv)
                                        {"outdir", required_argument, 0, 'o'}, {"index", required_argument, 0, 'i'},
                                        {"read-stats", no_argument, 0, 1000}, {"pileup", no_argument, 0, 1001},
                                        {"polish", no_argument, 0, 1002}, {"polish-min-depth", required_argument, 0, 1003},
-                                       {"polish-weighted", no_argument, 0, 1004}, {0, 0, 0, 0}};
+                                       {"polish-weighted", no_argument, 0, 1004}, {"sites", no_argument, 0, 1005},
+                                       {"sites-min-depth", required_argument, 0, 1006}, {"sites-min-alt", required_argument, 0, 1007},
+                                       {"sites-min-pct", required_argument, 0, 1008}, {"sites-max", required_argument, 0, 1009}, {0, 0, 0, 0}};
     string outdir, index;
     bool read_stats = false;  // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
     bool pileup = false;      // --pileup: cluster_pileup.tsv, the same alignments piled onto the representative position by position
     bool polish = false;      // --polish: cluster_polished.fq, every representative called anew from both pileup tables of its reads
     int polish_min_depth = 3;  // --polish-min-depth: positions covered by fewer reads keep the representative's base
     bool polish_weighted = false;  // --polish-weighted: the call of --polish with every read's vote weighted by its base quality
+    SitesOpt sites;  // --sites: cluster_sites.tsv and read_alleles.tsv, where the reads of a cluster disagree and which read says what there
+    // a whole number of [lo, hi], or the end of the run
+    auto number = [](const char* name, const char* text, long lo, long hi) {
+        char* end = nullptr;
+        errno = 0;
+        const long v = strtol(text, &end, 10);
+        if (errno != 0 || end == text || *end != '\0' || v < lo || v > hi)
+            die(string(name) + " must be a whole number" + (hi < INT32_MAX ? " from " + std::to_string(lo) + " to " + std::to_string(hi) : " of at least " + std::to_string(lo)) + "!");
+        return int(v);
+    };
     int o;
     while ((o = getopt_long(argc, argv, "dhvo:i:", lo, nullptr)) != -1) {
         switch (o) {
@@ -1217,8 +1314,14 @@ static int main_dump(int argc, char** argv)
             case 1002: polish = true; break;
             case 1003: polish_min_depth = atoi(optarg); break;
             case 1004: polish_weighted = true; break;
+            case 1005: sites.on = true; break;
+            case 1006: sites.min_depth = number("--sites-min-depth", optarg, 1, INT32_MAX); break;
+            case 1007: sites.min_alt = number("--sites-min-alt", optarg, 1, INT32_MAX); break;
+            case 1008: sites.min_pct = number("--sites-min-pct", optarg, 1, 50); break;
+            case 1009: sites.max_sites = number("--sites-max", optarg, 1, INT32_MAX); break;
             case 'h':
-                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N] [--polish-weighted]] final.cer" << endl
+                cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N] [--polish-weighted]]" << endl
+                     << "                    [--sites [--sites-min-depth N] [--sites-min-alt N] [--sites-min-pct P] [--sites-max N]] final.cer" << endl
                      << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
                      << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
                      << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -1228,7 +1331,15 @@ static int main_dump(int argc, char** argv)
                      << "                 header: reads, and how many positions were substituted, deleted, inserted or left as they were" << endl
                      << "  --polish-min-depth N   positions covered by fewer than N reads keep the representative's base, quality '!' (default 3)" << endl
                      << "  --polish-weighted      with --polish: every read votes with its base qualities (Phred, 1 .. 93) instead of 1, so that" << endl
-                     << "                 a few confident reads outvote many doubtful ones; min-depth still counts reads; header: weighted=1" << endl;
+                     << "                 a few confident reads outvote many doubtful ones; min-depth still counts reads; header: weighted=1" << endl
+                     << "  --sites        also write outdir/cluster_sites.tsv, the positions of every representative where a second allele has real" << endl
+                     << "                 support among the cluster's reads (a base, a deletion, an insertion in front of the position), and" << endl
+                     << "                 outdir/read_alleles.tsv, every read's allele at each of its cluster's sites, one character per site (GPU);" << endl
+                     << "                 with --read-stats / --pileup the reads are still aligned once, with --polish a second time" << endl
+                     << "  --sites-min-depth N    only positions covered by at least N reads can be sites (default 3)" << endl
+                     << "  --sites-min-alt N      the second allele needs at least N reads (default 3) ..." << endl
+                     << "  --sites-min-pct P      ... and at least P percent of the depth, 1 .. 50 (default 25)" << endl
+                     << "  --sites-max N          keep the first N sites of a cluster (default 4096); a cluster with more gets a '#' line" << endl;
                 exit(0);
             default: break;
         }
@@ -1350,7 +1461,7 @@ static int main_dump(int argc, char** argv)
             if (it == id2cls.end()) continue;
             tsv << it->second.cls << "\t" << it->second.strand << "\t" << id << "\n";
             per_cluster[it->second.cls].push_back(Piece{hb, sb, pb, qb, qe, it->second.strand == -1, p == qe + 1});
-            if (read_stats || pileup || polish) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
+            if (read_stats || pileup || polish || sites.on) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
         }
     }
     lap("sorted fastq walked, clusters.tsv");
@@ -1404,12 +1515,13 @@ static int main_dump(int argc, char** argv)
         if (failed) die("Failed to write the cluster FASTQ files!");
     }
     lap("cluster fastq files written");
-    if (read_stats || pileup || polish) {
+    if (read_stats || pileup || polish || sites.on) {
         write_read_reports(b, outdir, stat_rows.size(), [&](size_t x) {
             const StatRow& r = stat_rows[x];
             return ReadStatRow{r.cls, r.strand, r.hb, size_t(r.he - r.hb), r.sb, size_t(r.se - r.sb), r.qb, size_t(r.qe - r.qb)};
-        }, read_stats, pileup, polish ? polish_min_depth : 0, polish_weighted);
-        const string reports = string(read_stats ? "read_stats.tsv, " : "") + (pileup ? "cluster_pileup.tsv, " : "") + (polish ? "cluster_polished.fq, " : "");
+        }, read_stats, pileup, polish ? polish_min_depth : 0, polish_weighted, sites);
+        const string reports = string(read_stats ? "read_stats.tsv, " : "") + (pileup ? "cluster_pileup.tsv, " : "") + (polish ? "cluster_polished.fq, " : "") +
+                               (sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "");
         lap((reports.substr(0, reports.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

@@ -18,6 +18,7 @@
 
 #include "isonclust2_hip.h"
 #include "ioc_pile_call.h"
+#include "ioc_pile_sites.h"
 
 namespace {
 
@@ -392,6 +393,69 @@ int64_t ioc_host_pileup_call_weighted(const ioc_pileup_col* cols, const ioc_pile
     s.out_len = int32_t(at);
     if (st) *st = s;
     return at;
+}
+
+// The projection of one operation string on its reference (isonclust2_hip.h has the rules): what ioc_host_ops_pileup adds to a
+// row, kept per read — the definition k_ops_project (ioc_pile_sites.hip) is tested against.
+int ioc_host_ops_project(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, uint8_t* base, uint8_t* insf)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || qlen < 0 || rlen < 0 || (qlen > 0 && !query) || !base || !insf) return IOC_ERR_ARG;
+    int64_t q = 0, r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        q += op == '=' || op == 'X' || op == 'I' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (q != qlen || r != rlen) return IOC_ERR_ARG;
+    memset(base, IOC_ALLELE_NONE, size_t(rlen) + 1);
+    memset(insf, 0, size_t(rlen) + 1);
+    q = r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        switch (ops[a]) {
+        case 'd': ++r; break;
+        case 'i': ++q; break;
+        case 'D': base[r++] = uint8_t(IOC_ALLELE_DEL); break;
+        case 'I':
+            if (a == 0 || ops[a - 1] != 'I') insf[r] = 1;
+            ++q;
+            break;
+        default: base[r++] = uint8_t(PileAcc::channel(uint8_t(query[q++]))); break;  // ('=' 'X')
+        }
+    }
+    return IOC_OK;
+}
+
+// The sites of one reference from its table of counts (isonclust2_hip.h has the rules; pile_sites_row, ioc_pile_sites.h, decides a
+// row for this function and for the kernels of ioc_pile_sites.hip alike).
+int64_t ioc_host_pileup_sites(const ioc_pileup_col* cols, int32_t rlen, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,
+                              ioc_pile_site* out, int64_t* n_found)
+{
+    if (min_depth < 1 || min_alt < 1 || min_pct < 1 || min_pct > 50 || max_sites < 1 || rlen < 0 || !cols || !out) return IOC_ERR_ARG;
+    const PileSiteRule rule{min_depth, min_alt, min_pct};
+    int64_t found = 0, written = 0;
+    for (int32_t p = 0; p <= rlen; ++p) {
+        const unsigned long long d_ins = p < rlen ? pile_depth(cols[p]) : rlen > 0 ? pile_depth(cols[rlen - 1]) : 0ull;
+        const PileRowSites row = pile_sites_row(cols[p], d_ins, p < rlen, p, rule);
+        if (row.has_ins && found++ < max_sites) out[written++] = row.ins;
+        if (row.has_base && found++ < max_sites) out[written++] = row.base;
+    }
+    if (n_found) *n_found = found;
+    return written;
+}
+
+// The alleles of one read, given by its projection, at the sites of its reference (pile_site_allele, ioc_pile_sites.h, as
+// k_site_alleles has it).
+int ioc_host_site_alleles(const uint8_t* base, const uint8_t* insf, int32_t rlen, const ioc_pile_site* sites, int32_t n_sites, uint8_t* out)
+{
+    if (rlen < 0 || n_sites < 0 || !base || !insf || (n_sites > 0 && (!sites || !out))) return IOC_ERR_ARG;
+    for (int32_t s = 0; s < n_sites; ++s) {
+        const ioc_pile_site& t = sites[s];
+        if (t.row < 0 || t.row > rlen || (t.kind != IOC_SITE_BASE && t.kind != IOC_SITE_INS) || (t.kind == IOC_SITE_BASE && t.row == rlen)) return IOC_ERR_ARG;
+    }
+    const uint8_t b_last = rlen > 0 ? base[rlen - 1] : uint8_t(IOC_ALLELE_NONE);
+    for (int32_t s = 0; s < n_sites; ++s) out[s] = pile_site_allele(sites[s].kind, sites[s].row == rlen, base[sites[s].row], insf[sites[s].row], b_last);
+    return IOC_OK;
 }
 
 // setGapOpen, src/cluster.cpp:425-440

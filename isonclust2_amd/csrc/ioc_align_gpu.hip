@@ -1144,6 +1144,8 @@ struct OpsRun {
     const uint32_t* d_q_off = nullptr;
     std::vector<uint32_t> q_len;  // (weighted pileup) per device pair: its query's length
     const uint32_t* d_q_len = nullptr;
+    std::vector<uint64_t> plane;  // (a pile that projects) per device pair: where its planes start
+    const uint64_t* d_plane = nullptr;
 };
 
 // the buffer [end per pair][len per pair][the bytes of a slice] and the table of ends (after o.end is filled); the columns a
@@ -1182,6 +1184,12 @@ int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vect
         o.d_q_len = reinterpret_cast<const uint32_t*>(p + lay.q_len);
         IOC_CHK(c, hipMemcpyAsync(p + lay.q_len, o.q_len.data(), np * 4, hipMemcpyHostToDevice, c->stream));
     }
+    if (h.projects()) {
+        o.plane.resize(np);
+        for (size_t x = 0; x < np; ++x) o.plane[x] = uint64_t(h.pile.plane[o.back[x]]);
+        o.d_plane = reinterpret_cast<const uint64_t*>(p + lay.plane);
+        IOC_CHK(c, hipMemcpyAsync(p + lay.plane, o.plane.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+    }
     return IOC_OK;
 }
 
@@ -1197,7 +1205,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     int r;
     if (stats && (r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
     EventSet ev;
-    ev.v.assign(3, nullptr);
+    ev.v.assign(4, nullptr);
     for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
     if (stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
@@ -1220,6 +1228,10 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
         break;
     }
     IOC_CHK(c, hipEventRecord(ev.v[2], c->stream));
+    if (h.projects())
+        IOC_CHK(c, iock_ops_project(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_plane, pool, pool_bytes,
+                                    pl.base_planes, pl.ins_planes, uint64_t(pl.plane_bytes)));
+    IOC_CHK(c, hipEventRecord(ev.v[3], c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
@@ -1239,6 +1251,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     float ms = 0;
     if (stats && hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) t.ms_stats += double(ms);
     if (pile && hipEventElapsedTime(&ms, ev.v[1], ev.v[2]) == hipSuccess) t.ms_pileup += double(ms);
+    if (h.projects() && hipEventElapsedTime(&ms, ev.v[2], ev.v[3]) == hipSuccess) t.ms_project += double(ms);
     t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t.copied += int64_t(dp.size() * 4 + (stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
     if (stats) t.records += int64_t(cnt);

@@ -21,6 +21,9 @@ struct AlnTally {
     int64_t records = 0;   // ... how many records came back
     double ms_pileup = 0;  // k_ops_pileup's device time
     double ms_call = 0;    // k_pile_call's device time (the polish path)
+    double ms_project = 0; // k_ops_project's device time (a pile that projects), ...
+    double ms_sites = 0;   // ... k_pile_sites' and ...
+    double ms_alleles = 0; // ... k_site_alleles' (ioc_align_pairs_alleles)
 };
 
 enum class SinkKind { bytes, reduced };               // the bytes go to the host / stay on the device and are reduced there
@@ -35,14 +38,15 @@ struct OpsLayout {
     size_t row_base;  // int64: first row, -1 for a pair that has been added already (a pile)
     size_t q_off;     // uint32: where the query starts in the pool (a pile)
     size_t q_len;     // uint32: the query's length (a weighted pile)
+    size_t plane;     // uint64: where the pair's planes start (a pile that projects)
     size_t bytes;     // the slice's bytes: the table, rounded up to 16
     size_t spare;     // behind the bytes: k_ops_stats and k_ops_pileup read the dword that holds a string's last byte whole
 };
-inline OpsLayout ops_layout(size_t np, SinkKind kind, PileKind pile)
+inline OpsLayout ops_layout(size_t np, SinkKind kind, PileKind pile, bool project = false)
 {
     const bool reduced = kind == SinkKind::reduced;
-    const size_t per_pair = !reduced ? 12 : pile == PileKind::weighted ? 32 : pile != PileKind::none ? 28 : 16;
-    return OpsLayout{0, np * 8, np * 12, np * 16, np * 24, np * 28, (np * per_pair + 15) & ~size_t(15), reduced ? size_t(4) : size_t(0)};
+    const size_t per_pair = !reduced ? 12 : pile == PileKind::none ? 16 : project ? 40 : pile == PileKind::weighted ? 32 : 28;
+    return OpsLayout{0, np * 8, np * 12, np * 16, np * 24, np * 28, np * 32, (np * per_pair + 15) & ~size_t(15), reduced ? size_t(4) : size_t(0)};
 }
 
 struct AlnSubSink;
@@ -72,11 +76,19 @@ struct AlnSink {
         int64_t rows = 0;                 // records per table
         const int64_t* row_base = nullptr;
         uint8_t* piled = nullptr;
+        // optional, with any kind (project): pair i's alignment is projected as well (k_ops_project), by the run that piles it,
+        // into reference length + 1 bytes of each of the two planes from byte plane[i] on
+        bool project = false;
+        uint8_t* base_planes = nullptr;  // (device) what the pair says at every row, IOC_ALLELE_NONE where nothing, and ...
+        uint8_t* ins_planes = nullptr;   // (device) ... whether it inserts in front of it
+        int64_t plane_bytes = 0;         // bytes per plane
+        const int64_t* plane = nullptr;
     } pile;
 
     bool reduced() const { return kind == SinkKind::reduced; }
     bool has_stats() const { return reduced() && with_stats; }
     bool has_pile() const { return reduced() && pile.kind != PileKind::none; }
+    bool projects() const { return has_pile() && pile.project; }
     // what the tables hold of the device for the whole call (ck_budget's `held`)
     uint64_t pile_bytes() const
     {
@@ -84,9 +96,9 @@ struct AlnSink {
         const uint64_t per_row = pile.kind == PileKind::counts ? sizeof(ioc_pileup_col)
                                  : pile.kind == PileKind::ins  ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins)
                                                                : 2 * sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins);
-        return uint64_t(pile.rows) * per_row;
+        return uint64_t(pile.rows) * per_row + (pile.project ? 2 * uint64_t(pile.plane_bytes) : 0);
     }
-    OpsLayout layout(size_t np) const { return ops_layout(np, kind, reduced() ? pile.kind : PileKind::none); }
+    OpsLayout layout(size_t np) const { return ops_layout(np, kind, reduced() ? pile.kind : PileKind::none, projects()); }
 
     // Pair i has an empty sequence (query length n, reference length m, one of them 0): all of it is one free end gap, and no walk —
     // n + m bytes 'i' or 'd', a record that is all lead_i or lead_d, nothing for a pile.
@@ -113,7 +125,7 @@ struct AlnSink {
 
 struct AlnSubSink {
     AlnSink sink;
-    std::vector<int64_t> len, base, row_base;
+    std::vector<int64_t> len, base, row_base, plane;
     std::vector<ioc_aln_stats> stats;
     std::vector<uint8_t> piled;
     AlnSubSink() = default;
@@ -138,6 +150,10 @@ inline AlnSubSink AlnSink::subset(const std::vector<int32_t>& idx) const
         for (int32_t i : idx) s.row_base.push_back(pile.row_base[i]), s.piled.push_back(pile.piled[i]);
         s.sink.pile.row_base = s.row_base.data();
         s.sink.pile.piled = s.piled.data();
+    }
+    if (projects()) {
+        for (int32_t i : idx) s.plane.push_back(pile.plane[i]);
+        s.sink.pile.plane = s.plane.data();
     }
     return s;
 }

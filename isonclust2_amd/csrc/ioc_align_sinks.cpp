@@ -1,6 +1,7 @@
 // ioc_align_sinks.cpp — the entry points of the batched GPU aligner that ask for the alignment itself, and the consensus call on
 // top of them: each describes where the walks' operation bytes go (AlnSink, ioc_align_sink.h) and runs ioc_align_pairs_sink
 // (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +25,94 @@ struct AlnCall {  // what every aligning entry point passes on
 };
 
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+
+// the segments' bound on kept sites: a row yields at most two, its insertion site and its base site, and row rlen one
+int64_t pile_sites_bound(const std::vector<IocPileSeg>& segs, int32_t max_sites)
+{
+    int64_t b = 0;
+    for (const IocPileSeg& s : segs) b += std::min<int64_t>(max_sites, 2 * int64_t(s.rlen) + 1);
+    return b;
+}
+
+// where a site search leaves what it found and, where there are pairs with planes, their alleles
+struct SitesCall {
+    const std::vector<IocPileSeg>& segs;
+    int32_t min_depth, min_alt, min_pct, max_sites;
+    ioc_pile_site* out_sites;
+    int64_t *site_off, *n_found;
+    // the pairs (ioc_align_pairs_alleles; n_pairs 0: none): pair i's planes start at byte plane[i] of each of the two planes
+    int32_t n_pairs = 0;
+    const int32_t* seg_of_pair = nullptr;
+    const int64_t* plane = nullptr;
+    int64_t plane_bytes = 0, alleles_bound = 0;
+    uint8_t* out_alleles = nullptr;
+    int64_t* allele_off = nullptr;
+};
+
+// The site kernels over a table that lies on the device (n_rows records), then k_site_alleles over the planes d_base / d_ins where
+// the call has pairs, and what they made copied back: a_call holds [segments][seg_len][site_off][n_found][sites] and behind them
+// [seg_of_pair][plane][allele_off][alleles].  Device times go to t.ms_sites / t.ms_alleles, the copies to t.ms_copy / t.copied.
+int pile_sites_device(ioc_ctx* c, const SitesCall& sc, const ioc_pileup_col* d_cols, int64_t n_rows, const uint8_t* d_base, const uint8_t* d_ins,
+                      AlnTally& t)
+{
+    const size_t n = sc.segs.size(), np = size_t(sc.n_pairs);
+    const size_t bound = size_t(pile_sites_bound(sc.segs, sc.max_sites)), a_bound = size_t(sc.alleles_bound);
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t o_seg = 0, o_len = up16(n * sizeof(IocPileSeg)), o_off = o_len + up16(n * 8), o_found = o_off + up16((n + 1) * 8),
+                 o_sites = o_found + up16(n * 8), o_sop = o_sites + up16(bound * sizeof(ioc_pile_site)), o_plane = o_sop + up16(np * 4),
+                 o_aoff = o_plane + up16(np * 8), o_all = o_aoff + up16((np + 1) * 8), total = o_all + up16(a_bound);
+    IOC_TRY(ioc_reserve(c, c->a_call, total));
+    uint8_t* p = static_cast<uint8_t*>(c->a_call.p);
+    IOC_CHK(c, hipMemcpyAsync(p + o_seg, sc.segs.data(), n * sizeof(IocPileSeg), hipMemcpyHostToDevice, c->stream));
+    EventSet ev;
+    ev.v.assign(4, nullptr);
+    for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
+    IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
+    IOC_CHK(c, iock_pile_sites(c->stream, reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), d_cols, uint64_t(n_rows), sc.min_depth, sc.min_alt,
+                               sc.min_pct, sc.max_sites, reinterpret_cast<int64_t*>(p + o_found), reinterpret_cast<int64_t*>(p + o_len),
+                               reinterpret_cast<int64_t*>(p + o_off), reinterpret_cast<ioc_pile_site*>(p + o_sites), uint64_t(bound)));
+    IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    auto t0 = std::chrono::steady_clock::now();
+    IOC_CHK(c, hipMemcpy(sc.site_off, p + o_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(sc.n_found, p + o_found, n * 8, hipMemcpyDeviceToHost));
+    const int64_t kept = sc.site_off[n];
+    if (kept < 0 || size_t(kept) > bound) return ioc_fail(c, IOC_ERR_HIP, "the site search returned a count outside its bound");
+    if (kept > 0) IOC_CHK(c, hipMemcpy(sc.out_sites, p + o_sites, size_t(kept) * sizeof(ioc_pile_site), hipMemcpyDeviceToHost));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) t.ms_sites += double(ms);
+    t.ms_copy += ms_since(t0);
+    t.copied += int64_t((2 * n + 1) * 8 + size_t(kept) * sizeof(ioc_pile_site));
+    if (!sc.allele_off) return IOC_OK;
+    sc.allele_off[0] = 0;
+    for (size_t i = 0; i < np; ++i) sc.allele_off[i + 1] = sc.allele_off[i] + (sc.site_off[sc.seg_of_pair[i] + 1] - sc.site_off[sc.seg_of_pair[i]]);
+    const int64_t bytes = sc.allele_off[np];
+    if (bytes > sc.alleles_bound) return ioc_fail(c, IOC_ERR_HIP, "the site search kept more sites than its bound");
+    if (bytes == 0) return IOC_OK;
+    IOC_CHK(c, hipMemcpyAsync(p + o_sop, sc.seg_of_pair, np * 4, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(p + o_plane, sc.plane, np * 8, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(p + o_aoff, sc.allele_off, (np + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipEventRecord(ev.v[2], c->stream));
+    IOC_CHK(c, iock_site_alleles(c->stream, uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop), reinterpret_cast<const IocPileSeg*>(p + o_seg),
+                                 uint32_t(n), reinterpret_cast<const uint64_t*>(p + o_plane), d_base, d_ins, uint64_t(sc.plane_bytes),
+                                 reinterpret_cast<const ioc_pile_site*>(p + o_sites), reinterpret_cast<const int64_t*>(p + o_off),
+                                 reinterpret_cast<const int64_t*>(p + o_aoff), p + o_all, uint64_t(bytes)));
+    IOC_CHK(c, hipEventRecord(ev.v[3], c->stream));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    t0 = std::chrono::steady_clock::now();
+    IOC_CHK(c, hipMemcpy(sc.out_alleles, p + o_all, size_t(bytes), hipMemcpyDeviceToHost));
+    if (hipEventElapsedTime(&ms, ev.v[2], ev.v[3]) == hipSuccess) t.ms_alleles += double(ms);
+    t.ms_copy += ms_since(t0);
+    t.copied += bytes;
+    return IOC_OK;
+}
+
+// the thresholds ioc_host_pileup_sites refuses
+bool sites_rule_ok(int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites)
+{
+    return min_depth >= 1 && min_alt >= 1 && min_pct >= 1 && min_pct <= 50 && max_sites >= 1;
+}
 
 }  // namespace
 
@@ -144,9 +233,12 @@ int pileup_call_tables(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const ch
 // What ioc_align_pairs_pileup and the polish calls share.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it
 // (ins), or a_pile_w as [wcols][wins] (weighted) — are reserved and zeroed, the pairs aligned into them (k_ops_pileup adds, where
 // the walks' bytes lie, slice after slice and re-run after re-run) and, where `call` is given, called where they lie; then the
-// tables asked for are copied out, once.  out_ins: the second table of its kind (ins, or wins).
+// tables asked for are copied out, once.  out_ins: the second table of its kind (ins, or wins).  `sites` (ioc_align_pairs_alleles):
+// every pair is projected as well, into the planes of a_planes, [base planes][ins planes], set to IOC_ALLELE_NONE / 0 once here,
+// and the sites are found and the alleles gathered where the table and the planes lie.
 static int align_pairs_piled(ioc_ctx* c, const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows,
-                             const PileCall* call, ioc_pileup_col* out_cols, ioc_pileup_col* out_wcols, ioc_pileup_ins* out_ins, AlnTally& t)
+                             const PileCall* call, ioc_pileup_col* out_cols, ioc_pileup_col* out_wcols, ioc_pileup_ins* out_ins, AlnTally& t,
+                             const SitesCall* sites = nullptr)
 {
     IOC_CHK(c, hipSetDevice(c->device));
     const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
@@ -162,9 +254,21 @@ static int align_pairs_piled(ioc_ctx* c, const AlnCall& a, PileKind kind, ioc_al
     AlnSink::Pile pl{kind, c->a_pile.as<ioc_pileup_col>(), nullptr, nullptr, nullptr, n_rows, row_base, piled.data()};
     if (kind == PileKind::ins) pl.ins = second->as<ioc_pileup_ins>();
     if (weighted) pl.wcols = second->as<ioc_pileup_col>(), pl.wins = reinterpret_cast<ioc_pileup_ins*>(second->as<uint8_t>() + b_cols);  // (b_cols: a multiple of 32)
+    if (sites) {
+        const size_t b_plane = size_t(sites->plane_bytes);
+        IOC_TRY(ioc_reserve(c, c->a_planes, 2 * b_plane));
+        pl.project = true, pl.base_planes = c->a_planes.as<uint8_t>(), pl.ins_planes = pl.base_planes + b_plane;
+        pl.plane_bytes = sites->plane_bytes, pl.plane = sites->plane;
+        if (b_plane > 0) {
+            IOC_CHK(c, hipMemsetAsync(pl.base_planes, IOC_ALLELE_NONE, b_plane, c->stream));
+            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, b_plane, c->stream));
+        }
+    }
     const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, out_stats != nullptr, out_stats, pl};
     IOC_TRY(a.run(c, a.n_pairs > 0 ? &sink : nullptr));
-    if (call)
+    if (sites)
+        IOC_TRY(pile_sites_device(c, *sites, pl.cols, n_rows, pl.base_planes, pl.ins_planes, t));
+    else if (call)
         IOC_TRY(pile_call_device(c, *call, weighted ? pl.wcols : pl.cols, weighted ? pl.wins : pl.ins, weighted ? pl.cols : nullptr, n_rows, t));
     else
         IOC_CHK(c, hipStreamSynchronize(c->stream));
@@ -300,6 +404,94 @@ int ioc_align_pairs_pileup(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: pileup: %lld rows, %.3f MB (table, lengths%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms%s\n",
                 (long long)n_rows, double(t.copied) * 1e-6, out_stats ? ", statistics" : "", t.ms_copy, t.ms_pileup,
+                out_stats ? (", k_ops_stats " + std::to_string(t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+int ioc_pileup_sites(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const ioc_pileup_col* cols, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                     int32_t max_sites, ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found)
+{
+    if (!c || n_segs < 0 || !sites_rule_ok(min_depth, min_alt, min_pct, max_sites) || !site_off || sites_cap < 0 ||
+        (n_segs > 0 && (!rlen || !cols || !n_found)))
+        return IOC_ERR_ARG;
+    std::vector<IocPileSeg> segs(static_cast<size_t>(n_segs));
+    int64_t n_rows = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (rlen[g] < 0) return ioc_fail(c, IOC_ERR_ARG, "ioc_pileup_sites: segment " + std::to_string(g) + " has a negative length");
+        if (rlen[g] > (1 << 30)) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_sites: segment " + std::to_string(g) + " is longer than 2^30 bases");
+        segs[size_t(g)] = IocPileSeg{n_rows, 0, rlen[g], 0};
+        n_rows += int64_t(rlen[g]) + 1;
+    }
+    const int64_t bound = pile_sites_bound(segs, max_sites);
+    if (sites_cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_pileup_sites: sites_cap " + std::to_string(sites_cap) + " below the bound " + std::to_string(bound));
+    if (bound > 0 && !out_sites) return IOC_ERR_ARG;
+    site_off[0] = 0;
+    if (n_segs == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col);
+    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pile.p, cols, b_cols, hipMemcpyHostToDevice, c->stream));
+    AlnTally t;
+    const SitesCall sc{segs, min_depth, min_alt, min_pct, max_sites, out_sites, site_off, n_found};
+    IOC_TRY(pile_sites_device(c, sc, c->a_pile.as<ioc_pileup_col>(), n_rows, nullptr, nullptr, t));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   site search: %d segments, %lld rows, %lld sites kept, k_pile_sites %.3f ms\n", n_segs, (long long)n_rows,
+                (long long)site_off[n_segs], t.ms_sites);
+    return IOC_OK;
+}
+
+// ioc_align_pairs_pileup into the rows of the segments, with every pair projected beside it, and the site kernels over the table
+// and the planes where they lie: what comes back is the sites and one byte per (pair, kept site of its segment).
+int ioc_align_pairs_alleles(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                            int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                            const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,
+                            ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap,
+                            int64_t* allele_off, ioc_pileup_col* out_cols)
+{
+    if (!c || n_pairs < 0 || n_segs < 0 || !sites_rule_ok(min_depth, min_alt, min_pct, max_sites) || !site_off || !allele_off || sites_cap < 0 ||
+        alleles_cap < 0 || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && (!segs || !n_found)))
+        return IOC_ERR_ARG;
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    const int64_t n_seqs = c->aln_offs.empty() ? 0 : int64_t(c->aln_offs.size()) - 1;
+    std::vector<IocPileSeg> ds(static_cast<size_t>(n_segs));
+    int64_t n_rows = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (segs[g].ref < 0 || segs[g].ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_alleles: segment " + std::to_string(g) + " refers to a sequence outside the pool");
+        const int64_t m = ioc_seq_len(c, segs[g].ref);
+        if (m > (1 << 30)) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_alleles: segment " + std::to_string(g) + " is longer than 2^30 bases");
+        ds[size_t(g)] = IocPileSeg{n_rows, c->aln_offs[size_t(segs[g].ref)], int32_t(m), segs[g].ref_revcomp ? 1 : 0};
+        n_rows += m + 1;
+    }
+    std::vector<int64_t> row_base(size_t(n_pairs), 0), plane(size_t(n_pairs), 0);
+    int64_t plane_bytes = 0, alleles_bound = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        IOC_TRY(ioc_pair_in_pool(c, pairs[i]));
+        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_alleles: pair " + std::to_string(i) + " names no segment");
+        const IocPileSeg& sg = ds[size_t(seg_of_pair[i])];
+        if (ioc_seq_len(c, pairs[i].ref) != sg.rlen)
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_alleles: the reference of pair " + std::to_string(i) + " is not as long as its segment's frame");
+        row_base[size_t(i)] = sg.row0;
+        plane[size_t(i)] = plane_bytes;
+        plane_bytes += int64_t(sg.rlen) + 1;
+        alleles_bound += std::min<int64_t>(max_sites, 2 * int64_t(sg.rlen) + 1);
+    }
+    const int64_t bound = pile_sites_bound(ds, max_sites);
+    if (sites_cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_alleles: sites_cap " + std::to_string(sites_cap) + " below the bound " + std::to_string(bound));
+    if (alleles_cap < alleles_bound)
+        return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_alleles: alleles_cap " + std::to_string(alleles_cap) + " below the bound " + std::to_string(alleles_bound));
+    if ((bound > 0 && !out_sites) || (alleles_bound > 0 && !out_alleles)) return IOC_ERR_ARG;
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    site_off[0] = 0;
+    for (int32_t i = 0; i <= n_pairs; ++i) allele_off[i] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    AlnTally t;
+    const SitesCall sc{ds, min_depth, min_alt, min_pct, max_sites, out_sites, site_off, n_found, n_pairs, seg_of_pair, plane.data(), plane_bytes,
+                       alleles_bound, out_alleles, allele_off};
+    IOC_TRY(align_pairs_piled(c, a, PileKind::counts, out_stats, row_base.data(), n_rows, nullptr, out_cols, nullptr, nullptr, t, &sc));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: sites: %d segments, %lld rows, %lld sites kept, %lld allele bytes, %.3f MB (sites, alleles, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_pile_sites %.3f ms, k_site_alleles %.3f ms%s\n",
+                n_segs, (long long)n_rows, (long long)site_off[n_segs], (long long)allele_off[n_pairs], double(t.copied) * 1e-6, out_cols ? ", table" : "",
+                out_stats ? ", statistics" : "", t.ms_copy, t.ms_pileup, t.ms_project, t.ms_sites, t.ms_alleles,
                 out_stats ? (", k_ops_stats " + std::to_string(t.ms_stats) + " ms").c_str() : "");
     return IOC_OK;
 }

@@ -212,6 +212,7 @@ struct ioc_ctx {
                         // alone, wins where ioc_pileup_call has ins)
     DevBuf a_qual;      // ioc_align_set_pool_qual: one quality byte per byte of a_pool ...
     bool aln_qual_set = false;  // ... which it holds for the current pool
+    DevBuf a_planes;  // ioc_align_pairs_alleles: every pair's projection, [base planes][ins planes] (k_ops_project)
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
@@ -377,6 +378,22 @@ hipError_t iock_pile_call_weighted(hipStream_t st, const IocPileSeg* segs, uint3
                                    const ioc_pileup_ins* wins, uint64_t n_rows, const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth,
                                    int64_t* seg_len, ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual,
                                    uint64_t out_bytes);
+
+// ioc_pile_sites.hip: the projection of the same strings into byte planes of the pairs' own (ioc_host_ops_project) — pair pid's
+// base plane from base_planes + plane[pid] on, its ins plane from ins_planes + plane[pid] on (plane_bytes bytes each, set to
+// IOC_ALLELE_NONE / 0 by the caller); launched beside iock_ops_pileup*, the same pairs are skipped
+hipError_t iock_ops_project(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room,
+                            const uint32_t* ord, uint32_t cnt, const int64_t* row_base, const uint32_t* q_off, const uint64_t* plane,
+                            const uint8_t* pool, uint64_t pool_bytes, uint8_t* base_planes, uint8_t* ins_planes, uint64_t plane_bytes);
+// ... the sites of many segments from a device table (ioc_host_pileup_sites per segment; of IocPileSeg row0 and rlen are read) ...
+hipError_t iock_pile_sites(hipStream_t st, const IocPileSeg* segs, uint32_t n_segs, const ioc_pileup_col* cols, uint64_t n_rows, int32_t min_depth,
+                           int32_t min_alt, int32_t min_pct, int32_t max_sites, int64_t* n_found, int64_t* seg_len, int64_t* site_off,
+                           ioc_pile_site* out, uint64_t sites_cap);
+// ... and every pair's alleles at the kept sites of its segment, from its planes (ioc_host_site_alleles)
+hipError_t iock_site_alleles(hipStream_t st, uint32_t n_pairs, const int32_t* seg_of_pair, const IocPileSeg* segs, uint32_t n_segs,
+                             const uint64_t* plane, const uint8_t* base_planes, const uint8_t* ins_planes, uint64_t plane_bytes,
+                             const ioc_pile_site* sites, const int64_t* site_off, const int64_t* allele_off, uint8_t* alleles,
+                             uint64_t alleles_cap);
 
 // ioc_capi.cpp: queries whose minimizer arrays are already in HBM (ioc_batch_view::minimizers_on_device)
 extern "C" int ioc_queries_upload_devmins(ioc_ctx* c, int32_t n, const int64_t* off_fwd, const int64_t* off_rev, const uint32_t* d_min_val,
