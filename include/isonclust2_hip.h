@@ -428,7 +428,38 @@ int64_t ioc_host_pileup_sites(const ioc_pileup_col* cols, int32_t rlen, int32_t 
  * that is needed, a row outside 0 .. rlen, a base site at row rlen and a kind that is neither; `out` is then untouched. */
 int ioc_host_site_alleles(const uint8_t* base, const uint8_t* insf, int32_t rlen, const ioc_pile_site* sites, int32_t n_sites,
                           uint8_t* out);
-int32_t ioc_host_gap_open(double e1_plus_e2);                     /* setGapOpen,  src/cluster.cpp:425-440 */
+/* ---- the split of a cluster's reads in two by linked variable sites: which sites vary together, and which side of that
+ * pattern each read is on.  Integers only. ----
+ * One segment: n_sites kept sites and n_reads reads; `alleles` is read-major, alleles[i * n_sites + s] the allele of read i at
+ * site s, as ioc_host_site_alleles writes it.
+ *  - mark:    m(i, s) = +1 where the byte equals sites[s].minor, else -1 where it equals sites[s].major, else 0 (a third allele,
+ *             IOC_ALLELE_NONE, any other byte).
+ *  - linkage: d(s, t) = the sum over the reads of m(i, s) * m(i, t): reads that agree minus reads that disagree, among those that
+ *             have a say at both sites.  link(s) = the sum of |d(s, t)| over t != s with |d(s, t)| >= min_link (64 bits).
+ *  - seed:    the first site with the largest link.  Without sites, or with a largest link of 0, there is NO SPLIT: seed -1,
+ *             every phase 0, every group IOC_SPLIT_NONE, every vote 0.
+ *  - phase:   phase(seed) = +1; for t != seed, phase(t) = sign(d(seed, t)) where |d(seed, t)| >= min_link, else 0.
+ *  - vote:    vote(i) = the sum over t of phase(t) * m(i, t).  Read i is in group 1 where vote >= min_margin, in group 0 where
+ *             vote <= -min_margin, else IOC_SPLIT_NONE.  Group 1 starts as the side that carries the seed's minor allele.
+ *  - rounds:  exactly `rounds` times, no early exit: g(i) = +1 / -1 / 0 for a read of group 1 / group 0 / neither;
+ *             dg(t) = the sum over the reads of g(i) * m(i, t); phase(t) = sign(dg(t)) where |dg(t)| >= min_link, else 0 (the
+ *             seed's too); then the vote again.  This carries the split along a reference that no read spans.
+ * out_link[s] = link(s), out_phase[s] and out_group[i] / out_vote[i] are the final ones; the record: seed, n_linked (sites whose
+ * final phase is not 0), n_reads, the reads of group 0, of group 1 and of neither, and link(seed) (0 without a split).  Any of
+ * out_link / out_phase / out_vote may be NULL.  IOC_ERR_ARG, with nothing written, for min_link < 1, min_margin < 1, rounds
+ * outside 0 .. 64, a negative count and a NULL that is needed (out_seg; out_group with reads; sites with sites; alleles with
+ * both).  This function is the plain triple loop, O(n_sites^2 * n_reads): it is the definition, ioc_site_split.hip the fast
+ * form.  Whether a split is "real" is the caller's reading of n_linked, n_group0 and n_group1: the library applies no verdict. */
+#define IOC_SPLIT_NONE 255
+typedef struct {
+    int32_t seed, n_linked;
+    int32_t n_reads, n_group0, n_group1, n_none;
+    int64_t seed_link;
+} ioc_split_seg; /* 32 bytes */
+int ioc_host_alleles_split(const ioc_pile_site* sites, int32_t n_sites, const uint8_t* alleles, int32_t n_reads, int32_t min_link,
+                           int32_t min_margin, int32_t rounds, int64_t* out_link, int8_t* out_phase, uint8_t* out_group,
+                           int32_t* out_vote, ioc_split_seg* out_seg);
+int32_t ioc_host_gap_open(double e1_plus_e2);                    /* setGapOpen,  src/cluster.cpp:425-440 */
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
 
@@ -568,6 +599,32 @@ int ioc_align_pairs_alleles(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* p
                             int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites, ioc_pile_site* out_sites,
                             int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap,
                             int64_t* allele_off, ioc_pileup_col* out_cols);
+/* The split of many segments at once ON THE DEVICE (ioc_site_split.hip: bit planes and popcounts, no atomics, every output word
+ * has one writer), from host tables that are uploaded: segment g has the sites sites[site_off[g] .. site_off[g + 1]) and the
+ * pairs i with seg_of_pair[i] == g as its reads, in ascending i; pair i's alleles stand at alleles[allele_off[i] ..
+ * allele_off[i + 1]), one byte per site of its segment (the layout ioc_align_pairs_alleles returns).  Per segment what
+ * ioc_host_alleles_split defines: out_link / out_phase per site (at the sites' positions), out_group / out_vote per pair, out_seg
+ * per segment; any of out_link / out_phase / out_vote may be NULL.  IOC_ERR_ARG, with nothing written, for what the host function
+ * refuses, seg_of_pair outside the segments, offsets that do not start at 0 or descend, and an allele_off row whose length is not
+ * its segment's site count. */
+int ioc_alleles_split(ioc_ctx* ctx, int32_t n_segs, int32_t n_pairs, const int32_t* seg_of_pair, const ioc_pile_site* sites,
+                      const int64_t* site_off, const uint8_t* alleles, const int64_t* allele_off, int32_t min_link,
+                      int32_t min_margin, int32_t rounds, int64_t* out_link, int8_t* out_phase, uint8_t* out_group,
+                      int32_t* out_vote, ioc_split_seg* out_seg);
+/* ioc_align_pairs_alleles with the split run where the alleles lie: the sites, site_off and n_found come back as from that call,
+ * and the split's outputs as from ioc_alleles_split (out_link / out_phase: sites_cap entries; out_group / out_vote: n_pairs;
+ * out_seg: n_segs; out_group and out_seg are needed, the others may be NULL).  out_alleles (with alleles_cap) and out_cols are
+ * optional: NULL, not copied; allele_off (n_pairs + 1 entries) always comes back.  The same refusals and capacity checks
+ * (alleles_cap is checked where out_alleles is given), and those of ioc_host_alleles_split.  Every pair is aligned, piled and projected exactly once.
+ * The split's own device memory — the bit planes (16 bytes per site and 64 reads of its segment), 21 bytes per site, 21 per pair
+ * and 32 per segment — is allocated after the walks have finished, so it does not count against the checkpoint arena's budget. */
+int ioc_align_pairs_split(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                          int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                          int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt,
+                          int32_t min_pct, int32_t max_sites, ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off,
+                          int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap, int64_t* allele_off, ioc_pileup_col* out_cols,
+                          int32_t min_link, int32_t min_margin, int32_t rounds, int64_t* out_link, int8_t* out_phase,
+                          uint8_t* out_group, int32_t* out_vote, ioc_split_seg* out_seg);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

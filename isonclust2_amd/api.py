@@ -242,6 +242,30 @@ def site_alleles(base, insf, sites):
     return out[:len(sites)]
 
 
+# ioc_split_seg as a numpy record, and the group byte of a read on neither side
+SPLIT_SEG_DTYPE = np.dtype([(n, np.int32) for n in ("seed", "n_linked", "n_reads", "n_group0", "n_group1", "n_none")] + [("seed_link", np.int64)])
+SPLIT_NONE = _lib.SPLIT_NONE
+
+
+def alleles_split(sites, alleles, min_link=3, min_margin=1, rounds=2):
+    """ioc_host_alleles_split: the split of one segment's reads in two by its linked sites — sites: PILE_SITE_DTYPE (minor and
+    major are read), alleles: uint8 of shape (n_reads, n_sites), read-major, as site_alleles writes a read's.  Returns a dict:
+    `link` (int64 per site), `phase` (int8 per site), `group` (uint8 per read: 0, 1 or SPLIT_NONE), `vote` (int32 per read) and
+    `seg` (one SPLIT_SEG_DTYPE record).  IocError for min_link < 1, min_margin < 1 and rounds outside 0 .. 64."""
+    sites = np.ascontiguousarray(sites, PILE_SITE_DTYPE)
+    alleles = np.ascontiguousarray(alleles, np.uint8)
+    if sites.ndim != 1 or alleles.ndim != 2 or alleles.shape[1] != len(sites):
+        raise ValueError("alleles must have one row per read and one column per site")
+    nr, ns = alleles.shape
+    link, phase = np.zeros(max(ns, 1), np.int64), np.zeros(max(ns, 1), np.int8)
+    group, vote, seg = np.zeros(max(nr, 1), np.uint8), np.zeros(max(nr, 1), np.int32), np.zeros(1, SPLIT_SEG_DTYPE)
+    rc = _lib.load().ioc_host_alleles_split(sites.ctypes.data, ns, alleles.ctypes.data, nr, int(min_link), int(min_margin), int(rounds),
+                                            link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data)
+    if rc != 0:
+        raise IocError(int(rc), "ioc_host_alleles_split")
+    return {"link": link[:ns], "phase": phase[:ns], "group": group[:nr], "vote": vote[:nr], "seg": seg[0]}
+
+
 def ops_to_comp(ops):
     """The comparison string of an operation string: '|' where the bases are equal, ' ' in every other column."""
     return bytes(ops).translate(bytes(0x7C if b == 0x3D else 0x20 for b in range(256)))
@@ -672,6 +696,81 @@ class Context:
                                                  _p(a_off, C.c_int64), cols.ctypes.data if tables and n_rows else None))
         out = {"score": score, "windows": win, "ratio": ratio, "sites": [sites[s_off[g]:s_off[g + 1]].copy() for g in range(ns)],
                "n_found": found[:ns], "alleles": [alleles[a_off[i]:a_off[i + 1]].copy() for i in range(n)]}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out["cols"] = cols
+            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
+        return out
+
+    @staticmethod
+    def _split_out(s_off, a_off_unused, sop, ns, n, link, phase, group, vote, seg):
+        """The split's flat outputs as a dict of per-segment lists: link / phase by the sites' offsets, group / vote by the pairs of
+        every segment in ascending pair order."""
+        members = [np.flatnonzero(sop == g) for g in range(ns)]
+        return {"link": [link[s_off[g]:s_off[g + 1]].copy() for g in range(ns)], "phase": [phase[s_off[g]:s_off[g + 1]].copy() for g in range(ns)],
+                "group": group[:n], "vote": vote[:n], "seg": seg[:ns], "members": members}
+
+    def alleles_split(self, sites, alleles, seg_of_pair, min_link=3, min_margin=1, rounds=2):
+        """ioc_alleles_split: the split of many segments at once on the device, from host tables — sites: a list of PILE_SITE_DTYPE
+        arrays per segment; alleles: a list of uint8 arrays per pair, one byte per site of segment seg_of_pair[i] (what
+        align_pairs_alleles returns).  A segment's reads are its pairs in ascending order.  Returns a dict: `link` and `phase`
+        (lists of arrays per segment), `group` (uint8 per pair), `vote` (int32 per pair), `seg` (SPLIT_SEG_DTYPE per segment) and
+        `members` (the pairs of every segment), each segment as alleles_split (the function) defines it."""
+        ns, n = len(sites), len(alleles)
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair must hold one entry per pair")
+        s_off = np.concatenate([[0], np.cumsum([len(x) for x in sites])]).astype(np.int64)
+        a_off = np.concatenate([[0], np.cumsum([len(x) for x in alleles])]).astype(np.int64)
+        flat_s = np.ascontiguousarray(np.concatenate([np.zeros(0, PILE_SITE_DTYPE)] + [np.asarray(x, PILE_SITE_DTYPE) for x in sites]))
+        flat_a = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(x, np.uint8) for x in alleles]))
+        S = int(s_off[-1])
+        link, phase = np.zeros(max(S, 1), np.int64), np.zeros(max(S, 1), np.int8)
+        group, vote, seg = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(ns, 1), SPLIT_SEG_DTYPE)
+        self._chk(self.L.ioc_alleles_split(self.h, ns, n, _p(sop, C.c_int32) if n else None, flat_s.ctypes.data if S else None, _p(s_off, C.c_int64),
+                                           flat_a.ctypes.data if len(flat_a) else None, _p(a_off, C.c_int64), int(min_link), int(min_margin),
+                                           int(rounds), link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data))
+        return self._split_out(s_off, a_off, sop, ns, n, link, phase, group, vote, seg)
+
+    def align_pairs_split(self, pairs, k, segs, seg_of_pair, min_depth=3, min_alt=3, min_pct=25, max_sites=4096, min_link=3, min_margin=1, rounds=2,
+                          stats=False, tables=False, alleles=False, match=2, mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_split: align_pairs_alleles with the split of every segment's reads run where the alleles lie.  Returns
+        align_pairs_alleles' dict — `alleles` only with alleles=True, `cols` and `row0` only with tables=True — and the split's:
+        `link`, `phase` (lists per segment), `group`, `vote` (per pair), `seg` (SPLIT_SEG_DTYPE per segment), `members`."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr = (_lib.PolishSeg * max(ns, 1))()
+        for g, (ref, rc) in enumerate(segs):
+            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair must hold one entry per pair")
+        offs = self.align_pool_offsets()
+        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
+        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
+        n_rows = sum(rlen) + ns
+        per_seg = [pileup_sites_bound(r, max(int(max_sites), 1)) for r in rlen]
+        s_cap = sum(per_seg)
+        a_cap = sum(per_seg[g] for g in sop if 0 <= g < ns)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        sites, s_off, found = np.zeros(max(s_cap, 1), PILE_SITE_DTYPE), np.zeros(ns + 1, np.int64), np.zeros(max(ns, 1), np.int64)
+        alle, a_off = (np.zeros(max(a_cap, 1), np.uint8) if alleles else None), np.zeros(n + 1, np.int64)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        link, phase = np.zeros(max(s_cap, 1), np.int64), np.zeros(max(s_cap, 1), np.int8)
+        group, vote, seg = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(ns, 1), SPLIT_SEG_DTYPE)
+        self._chk(self.L.ioc_align_pairs_split(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns,
+                                               sarr, _p(sop, C.c_int32), int(min_depth), int(min_alt), int(min_pct), int(max_sites),
+                                               sites.ctypes.data, s_cap, _p(s_off, C.c_int64), _p(found, C.c_int64),
+                                               alle.ctypes.data if alleles else None, a_cap if alleles else 0, _p(a_off, C.c_int64),
+                                               cols.ctypes.data if tables and n_rows else None, int(min_link), int(min_margin), int(rounds),
+                                               link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data))
+        out = {"score": score, "windows": win, "ratio": ratio, "sites": [sites[s_off[g]:s_off[g + 1]].copy() for g in range(ns)],
+               "n_found": found[:ns]}
+        out.update(self._split_out(s_off, a_off, sop, ns, n, link, phase, group, vote, seg))
+        if alleles:
+            out["alleles"] = [alle[a_off[i]:a_off[i + 1]].copy() for i in range(n)]
         if stats:
             out["stats"] = st
         if tables:

@@ -970,6 +970,18 @@ static int main_cluster(int argc, char** argv)
 // of its cluster as one character, '?' where the read does not cover the site, "*" for a cluster without sites.  Beside
 // --read-stats and --pileup a group is still aligned once: the call returns the statistics and the table as well.  With
 // --polish a group is aligned a second time, for the second table.
+//
+// dump --split: <outdir>/cluster_split.tsv and <outdir>/read_split.tsv (ioc_align_pairs_split: the call of --sites with the reads
+// of every cluster split in two by its linked sites where the alleles lie; the thresholds of the site search are the --sites-*
+// ones, whether --sites is given or not).  cluster_split.tsv: one row per cluster in cluster order — how many sites it kept, how
+// many of them ended up linked, the seed site's position and kind ("." for a cluster without a split), its reads and how many
+// of them are in group 0, in group 1 and in neither.  read_split.tsv: one row per row read_stats.tsv has — the read's group
+// (0 | 1 | .) and its vote.  Whether a split is real is the reader's judgement of those counts.  Beside --sites, --read-stats and
+// --pileup a group is still aligned once.
+struct SplitOpt {
+    bool on = false;
+    int min_link = 3, min_margin = 1, rounds = 2;
+};
 struct SitesOpt {
     bool on = false;
     int min_depth = 3, min_alt = 3, min_pct = 25, max_sites = 4096;
@@ -985,9 +997,9 @@ struct ReadStatRow {
     size_t qual_len;
 };
 static void write_read_reports(const Batch& b, const string& outdir, size_t n_rows, const std::function<ReadStatRow(size_t)>& row, bool want_stats,
-                               bool want_pileup, int polish_min_depth /* 0: no --polish */, bool polish_weighted, const SitesOpt& sites_opt)
+                               bool want_pileup, int polish_min_depth /* 0: no --polish */, bool polish_weighted, const SitesOpt& sites_opt, const SplitOpt& split_opt)
 {
-    const bool want_polish = polish_min_depth > 0, want_sites = sites_opt.on, want_segs = want_polish || want_sites,
+    const bool want_polish = polish_min_depth > 0, want_sites = sites_opt.on, want_split = split_opt.on, want_segs = want_polish || want_sites || want_split,
                want_groups = want_pileup || want_segs;
     constexpr size_t POOL_MAX = size_t(256) << 20;
     const int k = b.SortArgs.KmerSize;
@@ -1005,6 +1017,8 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         ioc_aln_stats st{};
         size_t rep_len = 0;
         string alleles;  // (--sites) one character per kept site of the read's cluster
+        uint8_t group = IOC_SPLIT_NONE;  // (--split) the read's side, and ...
+        int32_t vote = 0;                // ... its vote
     };
     std::vector<Result> res(kept.size());
     ioc_ctx* c = kept.empty() ? nullptr : make_ctx();
@@ -1044,6 +1058,30 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         create_file(outdir + "/cluster_sites.tsv", sites_out);
         sites_out << "ClusterId\tPos\tKind\tDepth\tMajor\tNMajor\tMinor\tNMinor\n";
     }
+    // (--split) the records of the group's segments
+    std::vector<ioc_split_seg> split_seg;
+    std::ofstream split_out;
+    if (want_split) {
+        create_file(outdir + "/cluster_split.tsv", split_out);
+        split_out << "ClusterId\tNSites\tNLinked\tSeedPos\tSeedKind\tNReads\tNGroup0\tNGroup1\tNNone\n";
+    }
+    auto write_split = [&]() {
+        string text;
+        for (size_t x = 0; x < group_cls.size(); ++x) {
+            const int32_t g = group_seg[x];
+            const ioc_split_seg z = g < 0 ? ioc_split_seg{-1, 0, 0, 0, 0, 0, 0} : split_seg[size_t(g)];
+            const int64_t s0 = g < 0 ? 0 : site_off[size_t(g)], n_sites = g < 0 ? 0 : site_off[size_t(g) + 1] - s0;
+            text = std::to_string(group_cls[x].first) + '\t' + std::to_string(n_sites) + '\t' + std::to_string(z.n_linked) + '\t';
+            if (z.seed >= 0 && z.seed < n_sites) {
+                const ioc_pile_site& t = sites[size_t(s0 + z.seed)];
+                text += std::to_string(t.row) + '\t' + (t.kind == IOC_SITE_INS ? "ins" : "base");
+            } else {
+                text += ".\t.";
+            }
+            text += '\t' + std::to_string(z.n_reads) + '\t' + std::to_string(z.n_group0) + '\t' + std::to_string(z.n_group1) + '\t' + std::to_string(z.n_none) + '\n';
+            split_out.write(text.data(), std::streamsize(text.size()));
+        }
+    };
     auto allele_char = [](int32_t kind, int32_t a) { return kind == IOC_SITE_INS ? (a == 0 ? '.' : a == 1 ? '+' : '?') : (a >= 0 && a <= IOC_ALLELE_DEL ? "ACGTN-"[a] : '?'); };
     auto write_sites = [&]() {
         string text;
@@ -1112,6 +1150,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         if (want_pileup) write_pileup();
         if (want_polish) write_polish();
         if (want_sites && !segs.empty()) write_sites();
+        if (want_split) write_split();
         group_cls.clear(), row_base.clear(), cols.clear();
         segs.clear(), seg_of_pair.clear(), seg_reads.clear(), group_seg.clear();
         group_rows = 0;
@@ -1130,7 +1169,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         std::vector<int64_t> win(np);
         std::vector<ioc_aln_stats> st(want_stats ? np : 0);
         bool have_first = false;  // the statistics and the first table are in st / cols already
-        if (want_sites) {
+        if (want_sites || want_split) {
             int64_t s_cap = 0, a_cap = 0;
             std::vector<int64_t> seg_cap(segs.size());
             for (size_t g = 0; g < segs.size(); ++g) {
@@ -1140,15 +1179,28 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             }
             for (size_t x = 0; x < np; ++x) a_cap += seg_cap[size_t(seg_of_pair[x])];
             sites.assign(size_t(s_cap), ioc_pile_site{}), site_off.assign(segs.size() + 1, 0), site_found.assign(segs.size(), 0);
-            std::vector<uint8_t> alleles(size_t(a_cap) + 1);
+            std::vector<uint8_t> alleles(want_sites ? size_t(a_cap) + 1 : size_t(1));
             std::vector<int64_t> allele_off(np + 1, 0);
             if (want_pileup) cols.assign(size_t(group_rows), ioc_pileup_col{});
-            check(c, ioc_align_pairs_alleles(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
-                                             int32_t(segs.size()), segs.data(), seg_of_pair.data(), sites_opt.min_depth, sites_opt.min_alt, sites_opt.min_pct,
-                                             sites_opt.max_sites, sites.data(), s_cap, site_off.data(), site_found.data(), alleles.data(), a_cap,
-                                             allele_off.data(), want_pileup ? cols.data() : nullptr),
-                  "variable sites");
-            for (size_t x = 0; x < np; ++x) {
+            if (want_split) {
+                std::vector<uint8_t> group(np);
+                std::vector<int32_t> vote(np);
+                split_seg.assign(segs.size(), ioc_split_seg{});
+                check(c, ioc_align_pairs_split(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
+                                               int32_t(segs.size()), segs.data(), seg_of_pair.data(), sites_opt.min_depth, sites_opt.min_alt, sites_opt.min_pct,
+                                               sites_opt.max_sites, sites.data(), s_cap, site_off.data(), site_found.data(), want_sites ? alleles.data() : nullptr,
+                                               want_sites ? a_cap : 0, allele_off.data(), want_pileup ? cols.data() : nullptr, split_opt.min_link,
+                                               split_opt.min_margin, split_opt.rounds, nullptr, nullptr, group.data(), vote.data(), split_seg.data()),
+                      "split by linked sites");
+                for (size_t x = 0; x < np; ++x) res[pair_row[x]].group = group[x], res[pair_row[x]].vote = vote[x];
+            } else {
+                check(c, ioc_align_pairs_alleles(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
+                                                 int32_t(segs.size()), segs.data(), seg_of_pair.data(), sites_opt.min_depth, sites_opt.min_alt, sites_opt.min_pct,
+                                                 sites_opt.max_sites, sites.data(), s_cap, site_off.data(), site_found.data(), alleles.data(), a_cap,
+                                                 allele_off.data(), want_pileup ? cols.data() : nullptr),
+                      "variable sites");
+            }
+            for (size_t x = 0; x < np && want_sites; ++x) {
                 string& text = res[pair_row[x]].alleles;
                 const int64_t s0 = site_off[size_t(seg_of_pair[x])];
                 for (int64_t a = allele_off[x]; a < allele_off[x + 1]; ++a) text += allele_char(sites[size_t(s0 + a - allele_off[x])].kind, alleles[size_t(a)]);
@@ -1258,6 +1310,16 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             out << '\t' << r.cls << '\t' << res[y].alleles << '\n';
         }
     }
+    if (want_split) {
+        std::ofstream out;
+        create_file(outdir + "/read_split.tsv", out);
+        out << "Read\tClusterId\tGroup\tVote\n";
+        for (size_t y = 0; y < kept.size(); ++y) {
+            const ReadStatRow r = row(kept[y]);
+            out.write(r.id, std::streamsize(r.id_len));
+            out << '\t' << r.cls << '\t' << (res[y].group == 0 ? "0" : res[y].group == 1 ? "1" : ".") << '\t' << res[y].vote << '\n';
+        }
+    }
     if (!want_stats) return;
 
     std::ofstream out;
@@ -1286,7 +1348,9 @@ static int main_dump(int argc, char** argv)
                                        {"polish", no_argument, 0, 1002}, {"polish-min-depth", required_argument, 0, 1003},
                                        {"polish-weighted", no_argument, 0, 1004}, {"sites", no_argument, 0, 1005},
                                        {"sites-min-depth", required_argument, 0, 1006}, {"sites-min-alt", required_argument, 0, 1007},
-                                       {"sites-min-pct", required_argument, 0, 1008}, {"sites-max", required_argument, 0, 1009}, {0, 0, 0, 0}};
+                                       {"sites-min-pct", required_argument, 0, 1008}, {"sites-max", required_argument, 0, 1009},
+                                       {"split", no_argument, 0, 1010}, {"split-min-link", required_argument, 0, 1011},
+                                       {"split-min-margin", required_argument, 0, 1012}, {"split-rounds", required_argument, 0, 1013}, {0, 0, 0, 0}};
     string outdir, index;
     bool read_stats = false;  // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
     bool pileup = false;      // --pileup: cluster_pileup.tsv, the same alignments piled onto the representative position by position
@@ -1294,6 +1358,7 @@ static int main_dump(int argc, char** argv)
     int polish_min_depth = 3;  // --polish-min-depth: positions covered by fewer reads keep the representative's base
     bool polish_weighted = false;  // --polish-weighted: the call of --polish with every read's vote weighted by its base quality
     SitesOpt sites;  // --sites: cluster_sites.tsv and read_alleles.tsv, where the reads of a cluster disagree and which read says what there
+    SplitOpt split;  // --split: cluster_split.tsv and read_split.tsv, the reads of a cluster in two groups by its linked sites
     // a whole number of [lo, hi], or the end of the run
     auto number = [](const char* name, const char* text, long lo, long hi) {
         char* end = nullptr;
@@ -1319,9 +1384,14 @@ static int main_dump(int argc, char** argv)
             case 1007: sites.min_alt = number("--sites-min-alt", optarg, 1, INT32_MAX); break;
             case 1008: sites.min_pct = number("--sites-min-pct", optarg, 1, 50); break;
             case 1009: sites.max_sites = number("--sites-max", optarg, 1, INT32_MAX); break;
+            case 1010: split.on = true; break;
+            case 1011: split.min_link = number("--split-min-link", optarg, 1, INT32_MAX); break;
+            case 1012: split.min_margin = number("--split-min-margin", optarg, 1, INT32_MAX); break;
+            case 1013: split.rounds = number("--split-rounds", optarg, 0, 64); break;
             case 'h':
                 cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N] [--polish-weighted]]" << endl
-                     << "                    [--sites [--sites-min-depth N] [--sites-min-alt N] [--sites-min-pct P] [--sites-max N]] final.cer" << endl
+                     << "                    [--sites [--sites-min-depth N] [--sites-min-alt N] [--sites-min-pct P] [--sites-max N]]" << endl
+                     << "                    [--split [--split-min-link N] [--split-min-margin N] [--split-rounds N]] final.cer" << endl
                      << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
                      << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
                      << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -1339,7 +1409,13 @@ static int main_dump(int argc, char** argv)
                      << "  --sites-min-depth N    only positions covered by at least N reads can be sites (default 3)" << endl
                      << "  --sites-min-alt N      the second allele needs at least N reads (default 3) ..." << endl
                      << "  --sites-min-pct P      ... and at least P percent of the depth, 1 .. 50 (default 25)" << endl
-                     << "  --sites-max N          keep the first N sites of a cluster (default 4096); a cluster with more gets a '#' line" << endl;
+                     << "  --sites-max N          keep the first N sites of a cluster (default 4096); a cluster with more gets a '#' line" << endl
+                     << "  --split        also write outdir/cluster_split.tsv, per cluster how many of its sites (found under the --sites-* thresholds) vary" << endl
+                     << "                 together and how many reads stand on either side of that pattern, and outdir/read_split.tsv, every read's" << endl
+                     << "                 group (0 | 1 | .) and vote (GPU); whether a cluster is one thing or two is the reader's judgement of the counts" << endl
+                     << "  --split-min-link N     two sites are linked when their reads agree or disagree by at least N (default 3)" << endl
+                     << "  --split-min-margin N   a read joins a group when its vote is at least N on that side (default 1)" << endl
+                     << "  --split-rounds N       refinement rounds, 0 .. 64, which carry the split along a representative no read spans (default 2)" << endl;
                 exit(0);
             default: break;
         }
@@ -1461,7 +1537,7 @@ static int main_dump(int argc, char** argv)
             if (it == id2cls.end()) continue;
             tsv << it->second.cls << "\t" << it->second.strand << "\t" << id << "\n";
             per_cluster[it->second.cls].push_back(Piece{hb, sb, pb, qb, qe, it->second.strand == -1, p == qe + 1});
-            if (read_stats || pileup || polish || sites.on) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
+            if (read_stats || pileup || polish || sites.on || split.on) stat_rows.push_back(StatRow{it->second.cls, it->second.strand, hb + 1, he, sb, se, qb, qe});
         }
     }
     lap("sorted fastq walked, clusters.tsv");
@@ -1515,13 +1591,13 @@ static int main_dump(int argc, char** argv)
         if (failed) die("Failed to write the cluster FASTQ files!");
     }
     lap("cluster fastq files written");
-    if (read_stats || pileup || polish || sites.on) {
+    if (read_stats || pileup || polish || sites.on || split.on) {
         write_read_reports(b, outdir, stat_rows.size(), [&](size_t x) {
             const StatRow& r = stat_rows[x];
             return ReadStatRow{r.cls, r.strand, r.hb, size_t(r.he - r.hb), r.sb, size_t(r.se - r.sb), r.qb, size_t(r.qe - r.qb)};
-        }, read_stats, pileup, polish ? polish_min_depth : 0, polish_weighted, sites);
+        }, read_stats, pileup, polish ? polish_min_depth : 0, polish_weighted, sites, split);
         const string reports = string(read_stats ? "read_stats.tsv, " : "") + (pileup ? "cluster_pileup.tsv, " : "") + (polish ? "cluster_polished.fq, " : "") +
-                               (sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "");
+                               (sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") + (split.on ? "cluster_split.tsv, read_split.tsv, " : "");
         lap((reports.substr(0, reports.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

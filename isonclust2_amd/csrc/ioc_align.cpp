@@ -19,6 +19,7 @@
 #include "isonclust2_hip.h"
 #include "ioc_pile_call.h"
 #include "ioc_pile_sites.h"
+#include "ioc_site_split.h"
 
 namespace {
 
@@ -455,6 +456,68 @@ int ioc_host_site_alleles(const uint8_t* base, const uint8_t* insf, int32_t rlen
     }
     const uint8_t b_last = rlen > 0 ? base[rlen - 1] : uint8_t(IOC_ALLELE_NONE);
     for (int32_t s = 0; s < n_sites; ++s) out[s] = pile_site_allele(sites[s].kind, sites[s].row == rlen, base[sites[s].row], insf[sites[s].row], b_last);
+    return IOC_OK;
+}
+
+// The split of one segment's reads by its linked sites (isonclust2_hip.h has the rules; the mark, the phase and the group rule are
+// ioc_site_split.h's, as the kernels of ioc_site_split.hip have them).  The plain triple loop: sites x sites x reads.
+int ioc_host_alleles_split(const ioc_pile_site* sites, int32_t n_sites, const uint8_t* alleles, int32_t n_reads, int32_t min_link, int32_t min_margin,
+                           int32_t rounds, int64_t* out_link, int8_t* out_phase, uint8_t* out_group, int32_t* out_vote, ioc_split_seg* out_seg)
+{
+    if (min_link < 1 || min_margin < 1 || rounds < 0 || rounds > 64 || n_sites < 0 || n_reads < 0 || !out_seg || (n_reads > 0 && !out_group) ||
+        (n_sites > 0 && !sites) || (n_sites > 0 && n_reads > 0 && !alleles))
+        return IOC_ERR_ARG;
+    const size_t ns = size_t(n_sites), nr = size_t(n_reads);
+    auto m = [&](size_t i, size_t s) { return split_mark(alleles[i * ns + s], sites[s].minor, sites[s].major); };
+    auto d = [&](size_t s, size_t t) {
+        int64_t v = 0;
+        for (size_t i = 0; i < nr; ++i) v += int64_t(m(i, s) * m(i, t));
+        return v;
+    };
+    std::vector<int64_t> link(ns, 0);
+    std::vector<int8_t> phase(ns, 0);
+    std::vector<int32_t> vote(nr, 0);
+    std::vector<uint8_t> group(nr, uint8_t(IOC_SPLIT_NONE));
+    int32_t seed = -1;
+    for (size_t s = 0; s < ns; ++s) {
+        for (size_t t = 0; t < ns; ++t) {
+            const int64_t v = t != s ? std::llabs(d(s, t)) : 0;
+            if (v >= min_link) link[s] += v;
+        }
+        if (link[s] > (seed < 0 ? 0 : link[size_t(seed)])) seed = int32_t(s);  // (the first of the largest; a largest of 0 is none)
+    }
+    auto cast_votes = [&]() {
+        for (size_t i = 0; i < nr; ++i) {
+            int64_t v = 0;
+            for (size_t t = 0; t < ns; ++t) v += int64_t(phase[t]) * m(i, t);
+            vote[i] = int32_t(v);
+            group[i] = split_group(v, min_margin);
+        }
+    };
+    if (seed >= 0) {
+        for (size_t t = 0; t < ns; ++t) phase[t] = t == size_t(seed) ? int8_t(1) : split_phase(d(size_t(seed), t), min_link);
+        cast_votes();
+        for (int32_t r = 0; r < rounds; ++r) {
+            for (size_t t = 0; t < ns; ++t) {
+                int64_t dg = 0;
+                for (size_t i = 0; i < nr; ++i) dg += (group[i] == 1 ? 1 : group[i] == 0 ? -1 : 0) * m(i, t);
+                phase[t] = split_phase(dg, min_link);
+            }
+            cast_votes();
+        }
+    }
+    ioc_split_seg rec{seed, 0, n_reads, 0, 0, 0, seed >= 0 ? link[size_t(seed)] : 0};
+    for (size_t t = 0; t < ns; ++t) rec.n_linked += phase[t] != 0;
+    for (size_t i = 0; i < nr; ++i) (group[i] == 1 ? rec.n_group1 : group[i] == 0 ? rec.n_group0 : rec.n_none) += 1;
+    for (size_t t = 0; t < ns; ++t) {
+        if (out_link) out_link[t] = link[t];
+        if (out_phase) out_phase[t] = phase[t];
+    }
+    for (size_t i = 0; i < nr; ++i) {
+        out_group[i] = group[i];
+        if (out_vote) out_vote[i] = vote[i];
+    }
+    *out_seg = rec;
     return IOC_OK;
 }
 

@@ -24,6 +24,8 @@ struct AlnTally {
     double ms_project = 0; // k_ops_project's device time (a pile that projects), ...
     double ms_sites = 0;   // ... k_pile_sites' and ...
     double ms_alleles = 0; // ... k_site_alleles' (ioc_align_pairs_alleles)
+    double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
+    int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };
 
 enum class SinkKind { bytes, reduced };               // the bytes go to the host / stay on the device and are reduced there

@@ -35,6 +35,126 @@ int64_t pile_sites_bound(const std::vector<IocPileSeg>& segs, int32_t max_sites)
     return b;
 }
 
+// what a split is run with and where it leaves what it made (ioc_host_alleles_split's parameters and outputs, per call)
+struct SplitCall {
+    int32_t min_link, min_margin, rounds;
+    int64_t* out_link;
+    int8_t* out_phase;
+    uint8_t* out_group;
+    int32_t* out_vote;
+    ioc_split_seg* out_seg;
+};
+
+// the parameters ioc_host_alleles_split refuses
+bool split_rule_ok(int32_t min_link, int32_t min_margin, int32_t rounds) { return min_link >= 1 && min_margin >= 1 && rounds >= 0 && rounds <= 64; }
+
+// The split kernels (ioc_site_split.hip) over sites and alleles that lie on the device — or on the host (on_device false), and are
+// uploaded then — and what they made copied back.  site_off / allele_off / seg_of_pair are the host's; the member lists come from
+// a counting sort of seg_of_pair (a segment's reads are its pairs in ascending order).  a_split holds, in this order, the host's
+// tables [site_off][allele_off][seg_of_pair][mem_off][members][word_off][bit_off][tile_seg][seg_of_site], the kernels' own
+// [marks][bits minor][bits major][g1][g0][link][phase][seed][group][vote][records] and, uploaded, [sites][alleles].  Under
+// IOC_TRACE the steps are timed one by one (t.ms_split, in the order of IocSplitStep).
+int split_device(ioc_ctx* c, const SplitCall& sp, size_t n, size_t np, const int32_t* seg_of_pair, const int64_t* site_off, const int64_t* allele_off,
+                 const ioc_pile_site* sites, const uint8_t* alleles, bool on_device, AlnTally& t)
+{
+    const size_t S = n ? size_t(site_off[n]) : 0, bytes = np ? size_t(allele_off[np]) : 0;
+    std::vector<uint32_t> mem_off(n + 1, 0), members(np), word_off(n + 1, 0);
+    std::vector<int64_t> bit_off(n + 1, 0);
+    for (size_t i = 0; i < np; ++i) ++mem_off[size_t(seg_of_pair[i]) + 1];
+    for (size_t g = 0; g < n; ++g) mem_off[g + 1] += mem_off[g];
+    {
+        std::vector<uint32_t> next(mem_off.begin(), mem_off.end() - 1);
+        for (size_t i = 0; i < np; ++i) members[next[size_t(seg_of_pair[i])]++] = uint32_t(i);
+    }
+    for (size_t g = 0; g < n; ++g) {
+        const uint32_t words = (mem_off[g + 1] - mem_off[g] + 63u) / 64u;
+        word_off[g + 1] = word_off[g] + words;
+        bit_off[g + 1] = bit_off[g] + int64_t(words) * (site_off[g + 1] - site_off[g]);
+    }
+    const size_t T = word_off[n], P = size_t(bit_off[n]);
+    std::vector<int32_t> tile_seg(T), seg_of_site(S);
+    for (size_t g = 0; g < n; ++g) {
+        std::fill(tile_seg.begin() + word_off[g], tile_seg.begin() + word_off[g + 1], int32_t(g));
+        std::fill(seg_of_site.begin() + site_off[g], seg_of_site.begin() + site_off[g + 1], int32_t(g));
+    }
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    size_t at = 0;
+    auto take = [&](size_t b) { const size_t o = at; at += up16(b); return o; };
+    const size_t o_soff = take((n + 1) * 8), o_aoff = take((np + 1) * 8), o_sop = take(np * 4), o_moff = take((n + 1) * 4), o_mem = take(np * 4),
+                 o_woff = take((n + 1) * 4), o_boff = take((n + 1) * 8), o_tseg = take(T * 4), o_sos = take(S * 4), tables = at;
+    const size_t o_marks = take(S * 8), o_bm = take(P * 8), o_bM = take(P * 8), o_g1 = take(T * 8), o_g0 = take(T * 8), o_link = take(S * 8),
+                 o_phase = take(S), o_seed = take(n * 4), o_group = take(np), o_vote = take(np * 4), o_rec = take(n * sizeof(ioc_split_seg));
+    const size_t o_sites = take(on_device ? 0 : S * sizeof(ioc_pile_site)), o_all = take(on_device ? 0 : bytes);
+    std::vector<uint8_t> stage(tables, 0);
+    const int64_t zero = 0;
+    auto put = [&](size_t o, const void* src, size_t b) { if (b) memcpy(stage.data() + o, src, b); };
+    put(o_soff, n ? site_off : &zero, (n + 1) * 8), put(o_aoff, np ? allele_off : &zero, (np + 1) * 8), put(o_sop, seg_of_pair, np * 4);
+    put(o_moff, mem_off.data(), (n + 1) * 4), put(o_mem, members.data(), np * 4), put(o_woff, word_off.data(), (n + 1) * 4);
+    put(o_boff, bit_off.data(), (n + 1) * 8), put(o_tseg, tile_seg.data(), T * 4), put(o_sos, seg_of_site.data(), S * 4);
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_split, at));
+    uint8_t* p = static_cast<uint8_t*>(c->a_split.p);
+    IOC_CHK(c, hipMemcpyAsync(p, stage.data(), tables, hipMemcpyHostToDevice, c->stream));
+    t.split_uploaded += int64_t(tables);
+    if (!on_device) {
+        if (S) IOC_CHK(c, hipMemcpyAsync(p + o_sites, sites, S * sizeof(ioc_pile_site), hipMemcpyHostToDevice, c->stream));
+        if (bytes) IOC_CHK(c, hipMemcpyAsync(p + o_all, alleles, bytes, hipMemcpyHostToDevice, c->stream));
+        t.split_uploaded += int64_t(S * sizeof(ioc_pile_site) + bytes);
+    }
+    auto u64p = [&](size_t o) { return reinterpret_cast<unsigned long long*>(p + o); };
+    uint64_t most = 0;
+    for (size_t g = 0; g < n; ++g) most = std::max<uint64_t>(most, uint64_t(site_off[g + 1] - site_off[g]));
+    const IocSplitDev v{uint32_t(n), uint32_t(np), uint32_t(T), uint64_t(S), uint64_t(bytes), uint64_t(P), most,
+                        on_device ? sites : reinterpret_cast<const ioc_pile_site*>(p + o_sites), reinterpret_cast<const long long*>(p + o_soff),
+                        on_device ? alleles : p + o_all, reinterpret_cast<const long long*>(p + o_aoff), reinterpret_cast<const int32_t*>(p + o_sop),
+                        reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem),
+                        reinterpret_cast<const uint32_t*>(p + o_woff), reinterpret_cast<const long long*>(p + o_boff),
+                        reinterpret_cast<const int32_t*>(p + o_tseg), reinterpret_cast<const int32_t*>(p + o_sos), reinterpret_cast<int2*>(p + o_marks),
+                        u64p(o_bm), u64p(o_bM), u64p(o_g1), u64p(o_g0), reinterpret_cast<long long*>(p + o_link), reinterpret_cast<int8_t*>(p + o_phase),
+                        reinterpret_cast<int32_t*>(p + o_seed), p + o_group, reinterpret_cast<int32_t*>(p + o_vote),
+                        reinterpret_cast<ioc_split_seg*>(p + o_rec)};
+    std::vector<IocSplitStep> steps{IocSplitStep::marks, IocSplitStep::bits, IocSplitStep::link, IocSplitStep::seed, IocSplitStep::phase0,
+                                    IocSplitStep::vote};
+    for (int32_t r = 0; r < sp.rounds; ++r) steps.insert(steps.end(), {IocSplitStep::group_bits, IocSplitStep::rephase, IocSplitStep::vote});
+    steps.push_back(IocSplitStep::record);
+    const bool timed = getenv("IOC_TRACE") != nullptr;
+    EventSet ev;
+    if (timed) {
+        ev.v.assign(steps.size() + 1, nullptr);
+        for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
+        IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
+    }
+    for (size_t x = 0; x < steps.size(); ++x) {
+        IOC_CHK(c, iock_site_split(c->stream, v, steps[x], sp.min_link, sp.min_margin));
+        if (timed) IOC_CHK(c, hipEventRecord(ev.v[x + 1], c->stream));
+    }
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    for (size_t x = 0; timed && x < steps.size(); ++x) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev.v[x], ev.v[x + 1]) == hipSuccess) t.ms_split[size_t(steps[x])] += double(ms);
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const struct { void* dst; size_t off, b; } outs[] = {{sp.out_link, o_link, S * 8}, {sp.out_phase, o_phase, S}, {sp.out_group, o_group, np},
+                                                         {sp.out_vote, o_vote, np * 4}, {sp.out_seg, o_rec, n * sizeof(ioc_split_seg)}};
+    for (const auto& o : outs)
+        if (o.dst && o.b) {
+            IOC_CHK(c, hipMemcpy(o.dst, p + o.off, o.b, hipMemcpyDeviceToHost));
+            t.copied += int64_t(o.b);
+        }
+    t.ms_copy += ms_since(t0);
+    return IOC_OK;
+}
+
+// the split's part of a trace line
+std::string split_trace(const AlnTally& t)
+{
+    char buf[480];
+    snprintf(buf, sizeof buf, "k_site_marks %.3f ms, k_allele_bits %.3f ms, k_site_link %.3f ms, k_split_seed %.3f ms, k_split_phase0 %.3f ms, k_split_vote %.3f ms, k_group_bits %.3f ms, k_split_rephase %.3f ms, k_split_record %.3f ms, %lld bytes uploaded",
+             t.ms_split[0], t.ms_split[1], t.ms_split[2], t.ms_split[3], t.ms_split[4], t.ms_split[5], t.ms_split[6], t.ms_split[7], t.ms_split[8],
+             (long long)t.split_uploaded);
+    return buf;
+}
+
 // where a site search leaves what it found and, where there are pairs with planes, their alleles
 struct SitesCall {
     const std::vector<IocPileSeg>& segs;
@@ -46,8 +166,9 @@ struct SitesCall {
     const int32_t* seg_of_pair = nullptr;
     const int64_t* plane = nullptr;
     int64_t plane_bytes = 0, alleles_bound = 0;
-    uint8_t* out_alleles = nullptr;
+    uint8_t* out_alleles = nullptr;  // (NULL with a split: the alleles stay on the device)
     int64_t* allele_off = nullptr;
+    const SplitCall* split = nullptr;  // (ioc_align_pairs_split) the split, run where the sites and the alleles lie
 };
 
 // The site kernels over a table that lies on the device (n_rows records), then k_site_alleles over the planes d_base / d_ins where
@@ -89,7 +210,12 @@ int pile_sites_device(ioc_ctx* c, const SitesCall& sc, const ioc_pileup_col* d_c
     for (size_t i = 0; i < np; ++i) sc.allele_off[i + 1] = sc.allele_off[i] + (sc.site_off[sc.seg_of_pair[i] + 1] - sc.site_off[sc.seg_of_pair[i]]);
     const int64_t bytes = sc.allele_off[np];
     if (bytes > sc.alleles_bound) return ioc_fail(c, IOC_ERR_HIP, "the site search kept more sites than its bound");
-    if (bytes == 0) return IOC_OK;
+    auto split = [&]() {
+        return sc.split ? split_device(c, *sc.split, n, np, sc.seg_of_pair, sc.site_off, sc.allele_off, reinterpret_cast<const ioc_pile_site*>(p + o_sites),
+                                       p + o_all, true, t)
+                        : IOC_OK;
+    };
+    if (bytes == 0) return split();
     IOC_CHK(c, hipMemcpyAsync(p + o_sop, sc.seg_of_pair, np * 4, hipMemcpyHostToDevice, c->stream));
     IOC_CHK(c, hipMemcpyAsync(p + o_plane, sc.plane, np * 8, hipMemcpyHostToDevice, c->stream));
     IOC_CHK(c, hipMemcpyAsync(p + o_aoff, sc.allele_off, (np + 1) * 8, hipMemcpyHostToDevice, c->stream));
@@ -101,11 +227,11 @@ int pile_sites_device(ioc_ctx* c, const SitesCall& sc, const ioc_pileup_col* d_c
     IOC_CHK(c, hipEventRecord(ev.v[3], c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     t0 = std::chrono::steady_clock::now();
-    IOC_CHK(c, hipMemcpy(sc.out_alleles, p + o_all, size_t(bytes), hipMemcpyDeviceToHost));
+    if (sc.out_alleles) IOC_CHK(c, hipMemcpy(sc.out_alleles, p + o_all, size_t(bytes), hipMemcpyDeviceToHost));
     if (hipEventElapsedTime(&ms, ev.v[2], ev.v[3]) == hipSuccess) t.ms_alleles += double(ms);
     t.ms_copy += ms_since(t0);
-    t.copied += bytes;
-    return IOC_OK;
+    t.copied += sc.out_alleles ? bytes : 0;
+    return split();
 }
 
 // the thresholds ioc_host_pileup_sites refuses
@@ -442,12 +568,16 @@ int ioc_pileup_sites(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const ioc_
 
 // ioc_align_pairs_pileup into the rows of the segments, with every pair projected beside it, and the site kernels over the table
 // and the planes where they lie: what comes back is the sites and one byte per (pair, kept site of its segment).
-int ioc_align_pairs_alleles(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
-                            int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
-                            const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,
-                            ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap,
-                            int64_t* allele_off, ioc_pileup_col* out_cols)
+// (`split`: ioc_align_pairs_split — the split runs behind k_site_alleles, out_alleles is optional)
+static int align_pairs_alleles(const char* who_, ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                               int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                               const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                               int32_t max_sites, ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles,
+                               int64_t alleles_cap, int64_t* allele_off, ioc_pileup_col* out_cols, const SplitCall* split)
 {
+    const std::string who = who_;
+    if (split && (!split_rule_ok(split->min_link, split->min_margin, split->rounds) || (n_pairs > 0 && !split->out_group) || (n_segs > 0 && !split->out_seg)))
+        return IOC_ERR_ARG;
     if (!c || n_pairs < 0 || n_segs < 0 || !sites_rule_ok(min_depth, min_alt, min_pct, max_sites) || !site_off || !allele_off || sites_cap < 0 ||
         alleles_cap < 0 || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && (!segs || !n_found)))
         return IOC_ERR_ARG;
@@ -456,9 +586,9 @@ int ioc_align_pairs_alleles(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pai
     std::vector<IocPileSeg> ds(static_cast<size_t>(n_segs));
     int64_t n_rows = 0;
     for (int32_t g = 0; g < n_segs; ++g) {
-        if (segs[g].ref < 0 || segs[g].ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_alleles: segment " + std::to_string(g) + " refers to a sequence outside the pool");
+        if (segs[g].ref < 0 || segs[g].ref >= n_seqs) return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " refers to a sequence outside the pool");
         const int64_t m = ioc_seq_len(c, segs[g].ref);
-        if (m > (1 << 30)) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_alleles: segment " + std::to_string(g) + " is longer than 2^30 bases");
+        if (m > (1 << 30)) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": segment " + std::to_string(g) + " is longer than 2^30 bases");
         ds[size_t(g)] = IocPileSeg{n_rows, c->aln_offs[size_t(segs[g].ref)], int32_t(m), segs[g].ref_revcomp ? 1 : 0};
         n_rows += m + 1;
     }
@@ -466,33 +596,90 @@ int ioc_align_pairs_alleles(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pai
     int64_t plane_bytes = 0, alleles_bound = 0;
     for (int32_t i = 0; i < n_pairs; ++i) {
         IOC_TRY(ioc_pair_in_pool(c, pairs[i]));
-        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_alleles: pair " + std::to_string(i) + " names no segment");
+        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, who + ": pair " + std::to_string(i) + " names no segment");
         const IocPileSeg& sg = ds[size_t(seg_of_pair[i])];
         if (ioc_seq_len(c, pairs[i].ref) != sg.rlen)
-            return ioc_fail(c, IOC_ERR_ARG, "ioc_align_pairs_alleles: the reference of pair " + std::to_string(i) + " is not as long as its segment's frame");
+            return ioc_fail(c, IOC_ERR_ARG, who + ": the reference of pair " + std::to_string(i) + " is not as long as its segment's frame");
         row_base[size_t(i)] = sg.row0;
         plane[size_t(i)] = plane_bytes;
         plane_bytes += int64_t(sg.rlen) + 1;
         alleles_bound += std::min<int64_t>(max_sites, 2 * int64_t(sg.rlen) + 1);
     }
     const int64_t bound = pile_sites_bound(ds, max_sites);
-    if (sites_cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_alleles: sites_cap " + std::to_string(sites_cap) + " below the bound " + std::to_string(bound));
-    if (alleles_cap < alleles_bound)
-        return ioc_fail(c, IOC_ERR_CAPACITY, "ioc_align_pairs_alleles: alleles_cap " + std::to_string(alleles_cap) + " below the bound " + std::to_string(alleles_bound));
-    if ((bound > 0 && !out_sites) || (alleles_bound > 0 && !out_alleles)) return IOC_ERR_ARG;
+    if (sites_cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": sites_cap " + std::to_string(sites_cap) + " below the bound " + std::to_string(bound));
+    if ((out_alleles || !split) && alleles_cap < alleles_bound)
+        return ioc_fail(c, IOC_ERR_CAPACITY, who + ": alleles_cap " + std::to_string(alleles_cap) + " below the bound " + std::to_string(alleles_bound));
+    if ((bound > 0 && !out_sites) || (alleles_bound > 0 && !out_alleles && !split)) return IOC_ERR_ARG;
     for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
     site_off[0] = 0;
     for (int32_t i = 0; i <= n_pairs; ++i) allele_off[i] = 0;
     if (n_segs == 0) return a.run(c, nullptr);
     AlnTally t;
     const SitesCall sc{ds, min_depth, min_alt, min_pct, max_sites, out_sites, site_off, n_found, n_pairs, seg_of_pair, plane.data(), plane_bytes,
-                       alleles_bound, out_alleles, allele_off};
+                       alleles_bound, out_alleles, allele_off, split};
     IOC_TRY(align_pairs_piled(c, a, PileKind::counts, out_stats, row_base.data(), n_rows, nullptr, out_cols, nullptr, nullptr, t, &sc));
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: sites: %d segments, %lld rows, %lld sites kept, %lld allele bytes, %.3f MB (sites, alleles, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_pile_sites %.3f ms, k_site_alleles %.3f ms%s\n",
                 n_segs, (long long)n_rows, (long long)site_off[n_segs], (long long)allele_off[n_pairs], double(t.copied) * 1e-6, out_cols ? ", table" : "",
                 out_stats ? ", statistics" : "", t.ms_copy, t.ms_pileup, t.ms_project, t.ms_sites, t.ms_alleles,
                 out_stats ? (", k_ops_stats " + std::to_string(t.ms_stats) + " ms").c_str() : "");
+    if (split && getenv("IOC_TRACE")) fprintf(stderr, "[ioc]   aligner: split: %s\n", split_trace(t).c_str());
+    return IOC_OK;
+}
+
+int ioc_align_pairs_alleles(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                            int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                            const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,
+                            ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap,
+                            int64_t* allele_off, ioc_pileup_col* out_cols)
+{
+    return align_pairs_alleles("ioc_align_pairs_alleles", c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats,
+                               n_segs, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, out_sites, sites_cap, site_off, n_found, out_alleles,
+                               alleles_cap, allele_off, out_cols, nullptr);
+}
+
+// ioc_align_pairs_alleles with the split kernels (ioc_site_split.hip) run over the sites and the alleles where k_pile_sites and
+// k_site_alleles left them: one byte per read comes back, and the alleles only where they are asked for.
+int ioc_align_pairs_split(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                          int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                          const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,
+                          ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap,
+                          int64_t* allele_off, ioc_pileup_col* out_cols, int32_t min_link, int32_t min_margin, int32_t rounds, int64_t* out_link,
+                          int8_t* out_phase, uint8_t* out_group, int32_t* out_vote, ioc_split_seg* out_seg)
+{
+    const SplitCall sp{min_link, min_margin, rounds, out_link, out_phase, out_group, out_vote, out_seg};
+    return align_pairs_alleles("ioc_align_pairs_split", c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats,
+                               n_segs, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, out_sites, sites_cap, site_off, n_found, out_alleles,
+                               alleles_cap, allele_off, out_cols, &sp);
+}
+
+// The split of segments whose sites and alleles the caller holds: both are uploaded, and the kernels run as behind
+// ioc_align_pairs_split.
+int ioc_alleles_split(ioc_ctx* c, int32_t n_segs, int32_t n_pairs, const int32_t* seg_of_pair, const ioc_pile_site* sites, const int64_t* site_off,
+                      const uint8_t* alleles, const int64_t* allele_off, int32_t min_link, int32_t min_margin, int32_t rounds, int64_t* out_link,
+                      int8_t* out_phase, uint8_t* out_group, int32_t* out_vote, ioc_split_seg* out_seg)
+{
+    if (!c || n_segs < 0 || n_pairs < 0 || !split_rule_ok(min_link, min_margin, rounds) || (n_segs > 0 && (!site_off || !out_seg)) ||
+        (n_pairs > 0 && (!seg_of_pair || !allele_off || !out_group)))
+        return IOC_ERR_ARG;
+    if (n_segs > 0 && site_off[0] != 0) return ioc_fail(c, IOC_ERR_ARG, "ioc_alleles_split: site_off does not start at 0");
+    for (int32_t g = 0; g < n_segs; ++g)
+        if (site_off[g + 1] < site_off[g] || site_off[g + 1] - site_off[g] > INT32_MAX)
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_alleles_split: site_off descends or segment " + std::to_string(g) + " has more than 2^31 - 1 sites");
+    if (n_pairs > 0 && allele_off[0] != 0) return ioc_fail(c, IOC_ERR_ARG, "ioc_alleles_split: allele_off does not start at 0");
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, "ioc_alleles_split: pair " + std::to_string(i) + " names no segment");
+        if (allele_off[i + 1] - allele_off[i] != site_off[seg_of_pair[i] + 1] - site_off[seg_of_pair[i]])
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_alleles_split: the alleles of pair " + std::to_string(i) + " are not one byte per site of its segment");
+    }
+    if ((n_segs > 0 && site_off[n_segs] > 0 && !sites) || (n_pairs > 0 && allele_off[n_pairs] > 0 && !alleles)) return IOC_ERR_ARG;
+    if (n_segs == 0) return IOC_OK;
+    AlnTally t;
+    const SplitCall sp{min_link, min_margin, rounds, out_link, out_phase, out_group, out_vote, out_seg};
+    IOC_TRY(split_device(c, sp, size_t(n_segs), size_t(n_pairs), seg_of_pair, site_off, allele_off, sites, alleles, false, t));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   split: %d segments, %d pairs, %lld sites, %lld allele bytes, %s\n", n_segs, n_pairs, (long long)site_off[n_segs],
+                (long long)(n_pairs ? allele_off[n_pairs] : 0), split_trace(t).c_str());
     return IOC_OK;
 }
 

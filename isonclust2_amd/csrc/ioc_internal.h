@@ -213,6 +213,7 @@ struct ioc_ctx {
     DevBuf a_qual;      // ioc_align_set_pool_qual: one quality byte per byte of a_pool ...
     bool aln_qual_set = false;  // ... which it holds for the current pool
     DevBuf a_planes;  // ioc_align_pairs_alleles: every pair's projection, [base planes][ins planes] (k_ops_project)
+    DevBuf a_split;   // ioc_alleles_split, ioc_align_pairs_split: member lists, bit planes, per-site and per-pair words (ioc_site_split.hip)
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
@@ -394,6 +395,34 @@ hipError_t iock_site_alleles(hipStream_t st, uint32_t n_pairs, const int32_t* se
                              const uint64_t* plane, const uint8_t* base_planes, const uint8_t* ins_planes, uint64_t plane_bytes,
                              const ioc_pile_site* sites, const int64_t* site_off, const int64_t* allele_off, uint8_t* alleles,
                              uint64_t alleles_cap);
+
+// ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
+// is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in
+// ascending order as its reads, word_off[g + 1] - word_off[g] = ceil(reads / 64) words a plane and site, its planes from word
+// bit_off[g] on (words x sites of them each); tile_seg: the segment of every word of the call, seg_of_site that of every site.
+struct IocSplitDev {
+    uint32_t n_segs, n_pairs, n_tiles;
+    uint64_t n_sites, allele_bytes, plane_words, max_seg_sites;
+    const ioc_pile_site* sites;
+    const long long* site_off;    // [n_segs + 1]
+    const uint8_t* alleles;       // pair i's bytes from allele_off[i] on, one per site of its segment
+    const long long* allele_off;  // [n_pairs + 1]
+    const int32_t* seg_of_pair;
+    const uint32_t *mem_off, *members, *word_off;  // [n_segs + 1], [n_pairs], [n_segs + 1]
+    const long long* bit_off;                      // [n_segs + 1]
+    const int32_t *tile_seg, *seg_of_site;         // [n_tiles], [n_sites]
+    int2* marks;                                   // [n_sites] (minor, major)
+    unsigned long long *bits_minor, *bits_major;   // [plane_words] each
+    unsigned long long *g1, *g0;                   // [n_tiles] each
+    long long* link;                               // [n_sites]
+    int8_t* phase;                                 // [n_sites]
+    int32_t* seed;                                 // [n_segs]
+    uint8_t* group;                                // [n_pairs]
+    int32_t* vote;                                 // [n_pairs]
+    ioc_split_seg* rec;                            // [n_segs]
+};
+enum class IocSplitStep { marks, bits, link, seed, phase0, vote, group_bits, rephase, record };
+hipError_t iock_site_split(hipStream_t st, const IocSplitDev& v, IocSplitStep step, int32_t min_link, int32_t min_margin);
 
 // ioc_capi.cpp: queries whose minimizer arrays are already in HBM (ioc_batch_view::minimizers_on_device)
 extern "C" int ioc_queries_upload_devmins(ioc_ctx* c, int32_t n, const int64_t* off_fwd, const int64_t* off_rev, const uint32_t* d_min_val,
