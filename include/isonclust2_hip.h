@@ -460,6 +460,11 @@ int ioc_host_alleles_split(const ioc_pile_site* sites, int32_t n_sites, const ui
                            int32_t min_margin, int32_t rounds, int64_t* out_link, int8_t* out_phase, uint8_t* out_group,
                            int32_t* out_vote, ioc_split_seg* out_seg);
 int32_t ioc_host_gap_open(double e1_plus_e2);                    /* setGapOpen,  src/cluster.cpp:425-440 */
+/* Which kernel family the batched GPU aligner gives a pair of four-letter sequences with these scoring parameters (a pair with
+ * another letter always takes 0): 0 the comparing kernel (32-bit cells), 1 the query-profile kernel with 32-bit cells, 2 version 2
+ * (query profiles, 16-bit cells) may take it.  With cm = match + gap_extend + gap_open and cx = mismatch + gap_extend + gap_open:
+ * 1 and 2 need 0 <= cm, cx <= 255; 2 also gap_open >= gap_extend and max(cm, cx) <= 31.  No result depends on the family. */
+int ioc_host_align_route(int32_t match, int32_t mismatch, int32_t gap_extend, int32_t gap_open);
 double ioc_host_aln_ratio(const char* comp, int32_t comp_len, double e, uint32_t slen, uint32_t k);
                                                                   /* getAlnRatio, src/cluster.cpp:442-459 */
 
@@ -482,7 +487,12 @@ typedef struct {
 /* Upload the sequence pool (concatenated raw sequences, offs[n_seqs + 1], offs[0] == 0). */
 int ioc_align_set_pool(ioc_ctx* ctx, int32_t n_seqs, const char* seqs, const int64_t* offs);
 /* Align n_pairs pairs; any of the outputs may be NULL.  out_windows = number of qualifying k-windows
- * (`aligned` of getAlnRatio), out_ratio = out_windows / query length (its return value). */
+ * (`aligned` of getAlnRatio), out_ratio = out_windows / query length (its return value).
+ * Accepted scoring parameters, for this call and every ioc_align_pairs_* form: gap_extend >= 0;
+ * w = max(|match|, |mismatch|) + 2 gap_extend + 5 at most 2^24; and w x (query length + reference length) at most 2^30 for
+ * every pair with two non-empty sequences (match 2, mismatch -2, gap_extend 1: every pair the pool can hold).  Within that
+ * range the results are ioc_host_align's, whatever the sign of the parameters, gap_extend above gap_open included.  Anything
+ * else is refused with IOC_ERR_ARG before an output is written. */
 int ioc_align_pairs(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
                     int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows,
                     double* out_ratio);

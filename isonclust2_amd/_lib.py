@@ -155,7 +155,7 @@ SYMBOLS = [
     "ioc_clear_forced", "ioc_query_candidates", "ioc_index_export", "ioc_qual_scores",
     "ioc_extract_minimizers", "ioc_extracted_download", "ioc_extracted_hpc_download", "ioc_queries_from_extracted",
     "ioc_get_timings", "ioc_count_reference_postings", "ioc_host_gap_limits", "ioc_host_err_cell", "ioc_host_min_total",
-    "ioc_cluster_batch", "ioc_cluster_merge", "ioc_cluster_resident", "ioc_host_align", "ioc_host_gap_open",
+    "ioc_cluster_batch", "ioc_cluster_merge", "ioc_cluster_resident", "ioc_host_align", "ioc_host_gap_open", "ioc_host_align_route",
     "ioc_host_aln_ratio", "ioc_host_align_ops", "ioc_host_ops_to_cigar", "ioc_host_ops_stats", "ioc_host_ops_pileup", "ioc_host_ops_pileup_ins", "ioc_host_pileup_call", "ioc_host_qual_weight", "ioc_host_ops_pileup_weighted", "ioc_host_pileup_call_weighted", "ioc_host_ops_project", "ioc_host_pileup_sites", "ioc_host_site_alleles", "ioc_host_alleles_split", "ioc_align_set_pool", "ioc_align_pairs", "ioc_align_ops_bound",
     "ioc_align_pairs_ops", "ioc_align_pairs_stats", "ioc_align_pairs_pileup", "ioc_pileup_call", "ioc_align_pairs_polish", "ioc_align_set_pool_qual", "ioc_pileup_call_weighted", "ioc_align_pairs_polish_weighted", "ioc_pileup_sites", "ioc_align_pairs_alleles", "ioc_alleles_split", "ioc_align_pairs_split", "ioc_set_aln_verdicts", "ioc_get_ties", "ioc_resident_set_sequences",
     "ioc_index_update", "ioc_left_export", "ioc_left_adopt", "ioc_cluster_consensus",
@@ -267,6 +267,7 @@ def load():
     L.ioc_host_site_alleles.argtypes = [C.c_void_p, C.c_void_p, i32, C.c_void_p, i32, C.c_void_p]
     L.ioc_host_alleles_split.argtypes = [C.c_void_p, i32, C.c_void_p, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_host_gap_open.argtypes = [C.c_double]
+    L.ioc_host_align_route.argtypes = [i32, i32, i32, i32]
     L.ioc_host_aln_ratio.argtypes = [C.c_char_p, i32, C.c_double, C.c_uint32, C.c_uint32]
     L.ioc_host_aln_ratio.restype = C.c_double
     L.ioc_cluster_resident.argtypes = [vp, pi32, pi8, C.POINTER(ClusterStats)]

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "isonclust2_hip.h"
+#include "ioc_align_sink.h"
 #include "ioc_pile_call.h"
 #include "ioc_pile_sites.h"
 #include "ioc_site_split.h"
@@ -528,6 +529,12 @@ int32_t ioc_host_gap_open(double e)
     if (e <= 0.04) return 4;
     if (e <= 0.1) return 3;
     return 2;
+}
+
+// the kernel family of a pair by its scoring parameters: aln_route (ioc_align_sink.h), which the GPU aligner's prepare_pairs asks too
+int ioc_host_align_route(int32_t match, int32_t mismatch, int32_t gap_extend, int32_t gap_open)
+{
+    return aln_route(match, mismatch, gap_extend, gap_open);
 }
 
 // getAlnRatio, src/cluster.cpp:442-459

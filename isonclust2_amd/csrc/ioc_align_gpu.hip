@@ -1285,7 +1285,7 @@ int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const ui
 
 // the bound on |relative H| at a rebase of version 2's 16-bit window: what is live in a wave at one time differs by a few
 // thousand at most, two cells of it being joined through a common ancestor by paths no longer than the window
-constexpr int P16_GUARD = 28000;
+constexpr int P16_GUARD = ALN_V2_GUARD;  // (ioc_align_sink.h: the routing predicate reasons from it)
 
 // The corridor's half width as a fraction of the longer sequence (V2Couple; IOC_ALIGN_CORRIDOR=0: every tile; a pair whose
 // result the corridor cannot vouch for is run again by the every-tile route).  0.2: a pair of one transcript scores 1.62 - 1.8
@@ -2015,13 +2015,22 @@ struct AlnBatch {
 int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const AlnParams& P, const AlnOut& out, AlnBatch& b)
 {
     const int32_t k = int32_t(P.k);
+    // what the call refuses, before any answer is written (the accepted ranges: isonclust2_hip.h, next to ioc_align_pairs)
+    if (!aln_params_ok(P.match, P.mismatch, P.gap_extend))
+        return ioc_fail(c, IOC_ERR_ARG, "GPU aligner: gap_extend must be >= 0 and max(|match|, |mismatch|) + 2 gap_extend + 5 at most 2^24");
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        IOC_TRY(ioc_pair_in_pool(c, pairs[i]));
+        const int64_t n = ioc_seq_len(c, pairs[i].query), m = ioc_seq_len(c, pairs[i].ref);
+        if (n + m >= (int64_t(1) << ALN_LEN_SHIFT))
+            return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: sequences above 2^26 bases");
+        if (n > 0 && m > 0 && !aln_span_ok(P.match, P.mismatch, P.gap_extend, n, m))
+            return ioc_fail(c, IOC_ERR_ARG, "GPU aligner: (max(|match|, |mismatch|) + 2 gap_extend + 5) x (" + std::to_string(n) + " + " + std::to_string(m) +
+                                                " bases) is above 2^30: the scores of this pair do not fit the kernels' 32-bit cells");
+    }
     b.dp.reserve(size_t(n_pairs));
     for (int32_t i = 0; i < n_pairs; ++i) {
         const ioc_aln_pair& a = pairs[i];
-        IOC_TRY(ioc_pair_in_pool(c, a));
         const int64_t n = ioc_seq_len(c, a.query), m = ioc_seq_len(c, a.ref);
-        if (n + m >= (int64_t(1) << ALN_LEN_SHIFT))
-            return ioc_fail(c, IOC_ERR_CAPACITY, "GPU aligner: sequences above 2^26 bases");
         const double limit = std::floor((1.0 - a.e) * double(k));  // getAlnRatio, cluster.cpp:446
         const int32_t il = limit < -1.0 ? -1 : limit > 64.0 ? 64 : int32_t(limit);
         if (n == 0 || m == 0) {
@@ -2049,12 +2058,10 @@ int prepare_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, const 
             while (a0 / double(n) < c->aln_verdict_thr) a0 += 1.0;
             d.stop_at = a0 >= 1.0 && a0 < 4.0e9 ? uint32_t(a0) : 0u;
         }
-        {   // query-profile kernel: four-letter sequences, diagonal increments that fit a byte
-            const int gd = d.gap_open - P.gap_extend, cm = P.match + 2 * P.gap_extend + gd, cx = P.mismatch + 2 * P.gap_extend + gd;
-            const bool ok = !c->aln_other[size_t(a.query)] && !c->aln_other[size_t(a.ref)] && cm >= 0 && cm <= 255 &&
-                            cx >= 0 && cx <= 255 && !getenv("IOC_ALIGN_NO_PROFILE");
-            d.pad = ok ? 1u : 0u;
-        }
+        // the kernel family (aln_route, ioc_align_sink.h), in `pad`: 0 the comparing kernel — also for every pair with a letter
+        // other than A C G T —, 1 the query-profile kernel of version 1, 2 version 2 may take the pair
+        const bool four = !c->aln_other[size_t(a.query)] && !c->aln_other[size_t(a.ref)] && !getenv("IOC_ALIGN_NO_PROFILE");
+        d.pad = four ? uint32_t(aln_route(P.match, P.mismatch, P.gap_extend, d.gap_open)) : uint32_t(ALN_ROUTE_COMPARE);
         b.dp.push_back(d);
         b.back.push_back(uint32_t(i));
         b.max_n = std::max(b.max_n, d.n);
@@ -2104,8 +2111,9 @@ void order_pairs(AlnBatch& b, const ioc_aln_pair* pairs)
             });
         }
     }
-    // trace variant: the pairs of the query-profile kernel first, the comparing kernel's after them
+    // trace variant: version 2's pairs first, then the other pairs of the query-profile kernel, the comparing kernel's after them
     std::stable_partition(order.begin(), order.end(), [&](uint32_t x) { return dp[x].pad != 0; });
+    std::stable_partition(order.begin(), order.end(), [&](uint32_t x) { return dp[x].pad == uint32_t(ALN_ROUTE_V2); });
 }
 
 // 3. waves per pair: few pairs -> wide workgroups (latency), many pairs -> narrow ones (no fill/drain waste)
@@ -2135,13 +2143,13 @@ WavePlan plan_waves(const AlnBatch& b, bool carry)
     return WavePlan{few_pairs ? 4u : waves, few_pairs};
 }
 
-// 4. version 2 takes the query-profile pairs — the front of `order`; *n_v2: how many it answered (0 when a bounded wait ran out
+// 4. version 2 takes the pairs it may (aln_v2_ok) — the front of `order`; *n_v2: how many it answered (0 when a bounded wait ran out
 // and they all go to version 1)
 int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2, const AlnSink* oh)
 {
     const uint32_t np = uint32_t(b.dp.size());
     uint32_t n = 0;
-    while (n < np && b.dp[b.order[n]].pad != 0) ++n;
+    while (n < np && b.dp[b.order[n]].pad == uint32_t(ALN_ROUTE_V2)) ++n;
     bool fell_back = false;
     OpsRun ops{oh, b.back.data()};
     const int r = align_v2_run(c, b.dp, b.order.data(), n, static_cast<const uint32_t*>(c->a_order.p), P, d_score, d_count, route != AlnRoute::every_tile,
@@ -2226,7 +2234,7 @@ V1Plan plan_v1(const AlnBatch& b, uint32_t n_v2, uint64_t budget, bool emit)
             const uint64_t u = v1_row_units(d) + uint64_t((d.m - 1) / TILE) * col_pitch(d.n);
             const uint64_t ops_u = emit ? uint64_t(d.n) + d.m : 0u;
             if (cnt > 0 && (used + u) * 8ull + ops_used + ops_u > budget) break;
-            if (cnt > 0 && d.pad != dp[b.order[first]].pad) break;  // one kernel per slice
+            if (cnt > 0 && (d.pad != 0) != (dp[b.order[first]].pad != 0)) break;  // one kernel per slice
             // (rows first: their pitch is a multiple of 16 int2, `used` stays 16-byte aligned for the int4 stores)
             pl.cko[b.order[first + cnt]] = AlnCk{used, used + v1_row_units(d)};
             used += u;

@@ -28,6 +28,61 @@ struct AlnTally {
     int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };
 
+// ---- which kernel family a pair takes, by its scoring parameters (ioc_host_align_route; prepare_pairs asks nothing else) ----
+// The forward passes add cm = match + gap_extend + gap_open on a diagonal step over equal bases, cx = mismatch + gap_extend +
+// gap_open over different ones, and subtract gd = gap_open - gap_extend where a gap may open (fwd_cells, ioc_align_gpu.hip).
+constexpr int ALN_V2_GUARD = 28000;     // version 2: |value - 32768| a rebase accepts
+constexpr int ALN_V2_STRIP_COLS = 1024;  // ... the columns of a tile, whose top row is cut to 16 bits around its first column
+constexpr int ALN_V2_ROWS_PER_CHECK = 64;  // ... and the rows a lane runs between two rebases (16 steps of 4 rows)
+constexpr int ALN_V2_RISE_MOST = 32767 / ALN_V2_STRIP_COLS;  // 31
+static_assert(ALN_V2_RISE_MOST * ALN_V2_ROWS_PER_CHECK <= 65535 - (32768 + ALN_V2_GUARD), "64 rows' rise fits above the guard");
+enum : int { ALN_ROUTE_COMPARE = 0, ALN_ROUTE_PROFILE = 1, ALN_ROUTE_V2 = 2 };
+
+// the query-profile kernels hold cm and cx as bytes (32-bit cells: version 1's profile form; version 2)
+inline bool aln_profile_ok(int64_t match, int64_t mismatch, int64_t gap_extend, int64_t gap_open)
+{
+    const int64_t cm = match + gap_extend + gap_open, cx = mismatch + gap_extend + gap_open;
+    return cm >= 0 && cm <= 255 && cx >= 0 && cx <= 255;
+}
+
+// Version 2's 16-bit halves on top of that.  gd goes into a half as an unsigned number and is subtracted with one 32-bit
+// operation for both halves: it must not be negative.  And a slanted score rises by at most max(cm, cx) per column along a row
+// and per row down a column, which the window has to survive where nothing looks at it: the top row of a tile is cut to 16 bits
+// around its first column before a lane's first rebase (1024 columns' rise must stay inside a half: max(cm, cx) <= 31), and a
+// value the guard accepted runs 64 rows until the next rebase (64 x 31 is below the 4767 a half has left above the guard).  A
+// half that overflows carries into the other pair of the couple, so this is a matter of both pairs' results.
+inline bool aln_v2_ok(int64_t match, int64_t mismatch, int64_t gap_extend, int64_t gap_open)
+{
+    const int64_t rise = (match > mismatch ? match : mismatch) + gap_extend + gap_open;
+    return aln_profile_ok(match, mismatch, gap_extend, gap_open) && gap_open - gap_extend >= 0 && rise <= ALN_V2_RISE_MOST;
+}
+
+inline int aln_route(int64_t match, int64_t mismatch, int64_t gap_extend, int64_t gap_open)
+{
+    return aln_v2_ok(match, mismatch, gap_extend, gap_open)        ? ALN_ROUTE_V2
+           : aln_profile_ok(match, mismatch, gap_extend, gap_open) ? ALN_ROUTE_PROFILE
+                                                                    : ALN_ROUTE_COMPARE;
+}
+
+// What the 32-bit kernels can hold at all (isonclust2_hip.h states it next to ioc_align_pairs).  A score lies within
+// max(|match|, |mismatch|) x min(n, m) of 0 and its slanted form within gap_extend x (n + m) of that: under the bound below
+// both stay inside 2^29, the kernels' "no score" (ALN_NEG), and the sum of two of them inside an int.
+constexpr int64_t ALN_PARAM_MOST = int64_t(1) << 24;
+constexpr int64_t ALN_SPAN_MOST = int64_t(1) << 30;
+inline int64_t aln_param_weight(int64_t match, int64_t mismatch, int64_t gap_extend)
+{
+    const int64_t a = match < 0 ? -match : match, b = mismatch < 0 ? -mismatch : mismatch;
+    return (a > b ? a : b) + 2 * gap_extend + 5;  // (5: the largest gap_open, ioc_host_gap_open)
+}
+inline bool aln_params_ok(int64_t match, int64_t mismatch, int64_t gap_extend)
+{
+    return gap_extend >= 0 && aln_param_weight(match, mismatch, gap_extend) <= ALN_PARAM_MOST;
+}
+inline bool aln_span_ok(int64_t match, int64_t mismatch, int64_t gap_extend, int64_t n, int64_t m)
+{
+    return aln_param_weight(match, mismatch, gap_extend) * (n + m) <= ALN_SPAN_MOST;
+}
+
 enum class SinkKind { bytes, reduced };               // the bytes go to the host / stay on the device and are reduced there
 enum class PileKind { none, counts, ins, weighted };  // the variant of k_ops_pileup a reduced sink runs
 

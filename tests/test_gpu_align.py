@@ -114,16 +114,22 @@ def test_automatic_width_and_many_pairs(ctx):
     _check(ctx, seqs, pairs, 11)
 
 
+def tile_sequences(lens):
+    """One 2200-base sequence mutated by 10 % and cut to each of `lens` (every one a mutation of its own), then the first 1024
+    bases of the base twice; and the generator, for the caller's pairs."""
+    rng = random.Random(17)
+    base = bytes(rng.choice(b"ACGT") for _ in range(2200))
+    return [_mutate(rng, base, 0.1)[:ln] for ln in lens] + [base[:1024], base[:1024]], rng
+
+
 @pytest.mark.parametrize("waves", ["1", "2", "4", "8"])
 def test_tile_boundaries(ctx, monkeypatch, waves):
     """Lengths around the checkpoint pitch (256) and the strip width (1024): row bands that end exactly on a
     tile, bands without rows, last column on / next to a lane edge, last row on / next to a tile edge."""
     monkeypatch.setenv("IOC_ALIGN_WAVES", waves)
-    rng = random.Random(17)
-    base = bytes(rng.choice(b"ACGT") for _ in range(2200))
     # (1536 / 1537, 512 / 513: the last strip switches to 8 columns per lane when no more than 512 columns are left)
     lens = [255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 1040, 1535, 1536, 1537, 1544, 2047, 2049]
-    seqs = [_mutate(rng, base, 0.1)[:ln] for ln in lens] + [base[:1024], base[:1024]]
+    seqs, rng = tile_sequences(lens)
     pairs = []
     for a in range(len(lens)):
         for b in (a, (a + 5) % len(lens), (a + 8) % len(lens)):
@@ -311,18 +317,22 @@ def test_v2_fallbacks(ctx, monkeypatch):
     assert ctx.timings()["n_align_refused"] - t1 == len(pairs) and ctx.timings()["align_version"] == 1
 
 
-def test_verdict_mode_decides_every_comparison_like_the_full_count(ctx):
-    """ioc_align_set_verdict_threshold: tracebacks stop once `ratio >= threshold` is decided.  For related pairs (pass early),
-    unrelated ones (fail late), pairs near the threshold and degenerate lengths: the comparison comes out as with the exact
-    counts at every threshold, the scores are exact, a stopped walk never reports more windows than the full one — and related
-    long pairs do stop early (fewer windows than the full count)."""
+def verdict_pairs():
+    """Related pairs (pass early), unrelated ones (fail late), pairs near the threshold and degenerate lengths."""
     rng = random.Random(43)
     base = bytes(rng.choice(b"ACGT") for _ in range(5000))
     other = bytes(rng.choice(b"ACGT") for _ in range(4800))
     seqs = [base, _mutate(rng, base, 0.06), _mutate(rng, base, 0.15), _mutate(rng, base, 0.3), other, _mutate(rng, other, 0.1),
             base[:700] + other[700:3000], base[:40], b"ACGT" * 3, b""]
     n = len(seqs)
-    pairs = [(i, j, (i + j) % 2, 0.12) for i in range(n) for j in range(n) if i != j and (i + 2 * j) % 3 != 0]
+    return seqs, [(i, j, (i + j) % 2, 0.12) for i in range(n) for j in range(n) if i != j and (i + 2 * j) % 3 != 0]
+
+
+def test_verdict_mode_decides_every_comparison_like_the_full_count(ctx):
+    """ioc_align_set_verdict_threshold: tracebacks stop once `ratio >= threshold` is decided.  For the pairs of verdict_pairs:
+    the comparison comes out as with the exact counts at every threshold, the scores are exact, a stopped walk never reports
+    more windows than the full one — and related long pairs do stop early (fewer windows than the full count)."""
+    seqs, pairs = verdict_pairs()
     ctx.align_set_pool(seqs)
     ctx.align_set_verdict_threshold(0.0)
     s0, w0, r0 = ctx.align_pairs(pairs, 11)

@@ -46,12 +46,11 @@ def _mutate(rng, s, rate):
     return bytes(out)
 
 
-def test_oracle_aligner_equals_product_host_aligner():
-    """600 pairs: related, unrelated, low-complexity (many equal-score paths), with other letters, empty / one
-    base; every gap-open class.  Score and the whole comparison string are compared."""
-    rng = random.Random(5)
-    n_checked = 0
-    for t in range(600):
+def aligner_pairs(count, seed=5):
+    """(t, query, reference, gap_open) of `count` pairs: related, unrelated, low-complexity (many equal-score paths), with other
+    letters, empty / one base; every gap-open class.  (tests/test_align_params_host.py aligns the first 150 at other parameters.)"""
+    rng = random.Random(seed)
+    for t in range(count):
         n, m = rng.randint(0, 300), rng.randint(0, 300)
         kind = t % 4
         alpha = b"ACGT" if kind != 2 else b"AC"
@@ -60,7 +59,14 @@ def test_oracle_aligner_equals_product_host_aligner():
         r = (_mutate(rng, base[rng.randint(0, 12):], 0.15) if kind != 1 else bytes(rng.choice(b"ACGT") for _ in range(m)))[:m]
         if kind == 3 and q:
             q = q[: len(q) // 2] + b"N" + q[len(q) // 2 + 1:]
-        go = rng.choice([2, 3, 4, 5])
+        yield t, q, r, rng.choice([2, 3, 4, 5])
+
+
+def test_oracle_aligner_equals_product_host_aligner():
+    """600 pairs (aligner_pairs).  Score and the whole comparison string are compared."""
+    n_checked = 0
+    for t, q, r, go in aligner_pairs(600):
+        n, m = len(q), len(r)
         comp = C.create_string_buffer(len(q) + len(r) + 2)
         sc = C.c_int32()
         ln = po.lib().orc_align(q, len(q), r, len(r), 2, -2, go, 1, comp, len(q) + len(r) + 2, C.byref(sc))

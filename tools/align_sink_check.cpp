@@ -5,7 +5,9 @@
 //    row_base reaches the re-run unchanged (ops_reserve turns it into -1 from `piled`), a pair the re-run leaves unanswered keeps
 //    len == 0 and piled == 0, the records of pairs outside idx are untouched, the bytes' regions are the caller's own;
 //  * AlnSink::answer_empty, the closed forms of a pair with an empty sequence, for every kind and both empty sides;
-//  * ops_layout, the per-slice table's offsets: those the kernels' launchers have always been handed, for np in {0, 1, 3, 5, 1000}.
+//  * ops_layout, the per-slice table's offsets: those the kernels' launchers have always been handed, for np in {0, 1, 3, 5, 1000};
+//  * aln_route and the accepted parameter range, at their edges and with the extreme values an int32 argument can carry (no
+//    overflow on the way: the sums are 64-bit).
 //
 // Host code only (the header includes no HIP header); meant for the sanitizers:
 //
@@ -209,10 +211,33 @@ void check_layout(const Kind& k)
     }
 }
 
+void check_routes()
+{
+    g_what = "routes";
+    for (int go = 2; go <= 5; ++go) EXPECT(aln_route(2, -2, 1, go) == ALN_ROUTE_V2);  // the default parameters: version 2, as ever
+    EXPECT(aln_route(2, -6, 1, 5) == ALN_ROUTE_V2 && aln_route(2, -6, 1, 4) == ALN_ROUTE_COMPARE);       // cx 0 / -1
+    EXPECT(aln_route(250, -2, 1, 4) == ALN_ROUTE_PROFILE && aln_route(250, -2, 1, 5) == ALN_ROUTE_COMPARE);  // cm 255 / 256
+    EXPECT(aln_route(2, -2, 2, 2) == ALN_ROUTE_V2 && aln_route(2, -2, 3, 2) == ALN_ROUTE_PROFILE);       // gd 0 / -1
+    EXPECT(aln_route(28, -2, 1, 2) == ALN_ROUTE_V2 && aln_route(29, -2, 1, 2) == ALN_ROUTE_PROFILE);     // max(cm, cx) 31 / 32
+    const int32_t lo = INT32_MIN, hi = INT32_MAX;
+    for (int32_t a : {lo, -1, 0, 1, hi})
+        for (int32_t b : {lo, -1, 0, 1, hi})
+            for (int32_t g : {lo, -1, 0, 1, hi}) {
+                const int r = aln_route(a, b, g, 5);
+                EXPECT(r >= ALN_ROUTE_COMPARE && r <= ALN_ROUTE_V2);
+                EXPECT(aln_params_ok(a, b, g) == (g >= 0 && aln_param_weight(a, b, g) <= ALN_PARAM_MOST));
+                EXPECT(aln_params_ok(a, b, g) == (a > -(1 << 24) && a < (1 << 24) && b > -(1 << 24) && b < (1 << 24) && g >= 0 && g <= 1));
+            }
+    // the default parameters: every pair a pool can hold (n + m < 2^26, prepare_pairs)
+    EXPECT(aln_params_ok(2, -2, 1) && aln_span_ok(2, -2, 1, (int64_t(1) << 26) - 1, 0));
+    EXPECT(aln_span_ok(1 << 20, -2, 0, 500, 523) && !aln_span_ok(1 << 20, -2, 0, 500, 524));  // (2^20 + 5) x 1023 <= 2^30 < ... x 1024
+}
+
 }  // namespace
 
 int main()
 {
+    check_routes();
     for (const Kind& k : KINDS) {
         Caller c(k);
         g_what = k.name;
@@ -237,6 +262,6 @@ int main()
         check_layout(k);
     }
     if (!g_ok) return 1;
-    printf("ok: %ld checks of subset / take_back, answer_empty and ops_layout over %zu sink kinds\n", g_checks, sizeof KINDS / sizeof KINDS[0]);
+    printf("ok: %ld checks of subset / take_back, answer_empty, ops_layout over %zu sink kinds, and the routes\n", g_checks, sizeof KINDS / sizeof KINDS[0]);
     return 0;
 }
