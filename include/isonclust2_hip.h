@@ -399,6 +399,25 @@ int64_t ioc_host_pileup_call_weighted(const ioc_pileup_col* cols, const ioc_pile
 #define IOC_ALLELE_DEL 5
 #define IOC_ALLELE_NONE 7
 int ioc_host_ops_project(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, uint8_t* base, uint8_t* insf);
+/* The insertion part of a read's projection: WHICH bases it inserts in front of every row.  `slots` holds
+ * IOC_PILE_INS_SLOTS * (rlen + 1) bytes, slot-major: slots[j * (rlen + 1) + r].  The call sets all of them to 0 and then walks the
+ * string exactly as ioc_host_ops_pileup_ins does: an 'I' byte that is the j-th (from 0) of its maximal run of 'I', standing in
+ * front of row r and taking query[q], stores 1 + the channel of query[q] (1 .. 5 for A C G T other) at slots[j][r] where
+ * j < IOC_PILE_INS_SLOTS, and nothing otherwise.  Nothing is ever cleared: a second run in front of the same row overwrites, in
+ * string order.  The inputs ioc_host_ops_pileup refuses are refused (IOC_ERR_ARG), with `slots` untouched. */
+int ioc_host_ops_project_ins(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, uint8_t* slots);
+/* One read's planes — `base` as ioc_host_ops_project writes it, `slots` as ioc_host_ops_project_ins does — ADDED to the two tables
+ * of its reference, rlen + 1 rows each: base[r] in 0 .. 4 adds 1 to that channel of cols[r], IOC_ALLELE_DEL adds 1 to del,
+ * IOC_ALLELE_NONE adds nothing; a slot byte s in 1 .. 5 at slots[j][r] adds 1 to ins[r].slot[j][s - 1] and 1 to cols[r].ins_bases,
+ * and a non-zero slots[0][r] adds 1 to cols[r].ins_runs; `longer` is never touched.  Any other byte, a negative rlen or a NULL:
+ * IOC_ERR_ARG, with both tables untouched.
+ * The relation to the pileup: for a string with at most one run of 'I' in front of any row — every string an aligner returns is
+ * one — the tables piled from its planes equal ioc_host_ops_pileup and ioc_host_ops_pileup_ins of the string in every field but
+ * two: ins_bases, which counts at most IOC_PILE_INS_SLOTS bases per run here, and `longer`, which stays 0.  The consensus call
+ * reads neither (pile_call_row), so ioc_host_pileup_call gives the same sequence, qualities and record from either pair of tables.
+ * That is what the planes are kept for: the tables of ANY subset of a cluster's reads can be added up after the alignments are
+ * gone — the two sides of a split (ioc_planes_polish, ioc_align_pairs_split_polish). */
+int ioc_host_planes_pile(const uint8_t* base, const uint8_t* slots, int32_t rlen, ioc_pileup_col* cols, ioc_pileup_ins* ins);
 /* One variable site.  kind IOC_SITE_BASE: the alleles are the channels 0 .. 5 (A C G T other del) of row `row`; kind
  * IOC_SITE_INS: the alleles are 0 (no insertion in front of row `row`) and 1 (one).  depth / n_major / n_minor are the 64-bit
  * values of the definition below, saturated at 2^32 - 1. */
@@ -635,6 +654,43 @@ int ioc_align_pairs_split(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pai
                           int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap, int64_t* allele_off, ioc_pileup_col* out_cols,
                           int32_t min_link, int32_t min_margin, int32_t rounds, int64_t* out_link, int8_t* out_phase,
                           uint8_t* out_group, int32_t* out_vote, ioc_split_seg* out_seg);
+/* The polished consensus of each side of a split, from the reads' planes, ON THE DEVICE.  Group-segment 2 g + h (segment g, group
+ * h in {0, 1}) is ioc_host_pileup_call(frame of g, min_depth) on the tables piled (ioc_host_planes_pile) from the planes of the
+ * pairs i with seg_of_pair[i] == g and group[i] == h; pairs in IOC_SPLIT_NONE are in no table, and a group-segment without reads
+ * returns its frame with quality 0 throughout.  The library applies no verdict on whether the split is real.
+ * This entry works from host planes, which are uploaded: segment g has rlen[g] bases and its frame at frames + frame_off[g] (as
+ * for ioc_pileup_call); pair i's rows start at the sum over the earlier pairs of (their segment's rlen + 1), P rows in all, and
+ * the planes are base[P] and slots[IOC_PILE_INS_SLOTS * P], slot-major over the whole array (slot j of row x at slots[j * P + x]).
+ * k_plane_pile adds the planes of every group's reads up (a lane per row, the waves of a workgroup share the reads, no atomics:
+ * every table word has one writer) and the call kernels of ioc_pileup_call run over the 2 * n_segs group-segments: out_off has
+ * 2 * n_segs + 1 entries, out_polish (may be NULL) 2 * n_segs records, and out_gcols / out_gins (optional, both or either) receive
+ * the tables, the sum over g of 2 * (rlen[g] + 1) rows, in group-segment order.  Plane bytes other than those the two projections
+ * write count for nothing.  IOC_ERR_ARG, with nothing written, for min_depth < 1, a negative count, length or frame offset,
+ * seg_of_pair outside the segments, a group byte other than 0, 1 or IOC_SPLIT_NONE and a NULL array that is needed;
+ * IOC_ERR_CAPACITY, with nothing written, for cap below twice the sum of the segments' bounds (ioc_pileup_call) and for a segment
+ * whose bound exceeds 2^31 - 1. */
+int ioc_planes_polish(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                      int32_t n_pairs, const int32_t* seg_of_pair, const uint8_t* group, const uint8_t* base, const uint8_t* slots,
+                      int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                      ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins);
+/* ioc_align_pairs_split with the consensus of both groups of every segment called where the planes lie: everything
+ * ioc_align_pairs_split returns comes back unchanged, and behind the split k_plane_pile and the call kernels run over the planes
+ * the walks left — k_ops_project's base plane and the six slot planes of k_ops_project_ins, 8 bytes per row and pair in all,
+ * which count against the checkpoint arena's budget like the table — with the groups the split just made: out_seq / out_qual /
+ * out_off / out_polish / out_gcols / out_gins as from ioc_planes_polish, the frame of segment g being its representative as the
+ * pairs were aligned against it.  Every pair is aligned, piled and projected exactly once: no read is aligned a second time for
+ * its group's consensus.  The group tables (160 bytes per row and group-segment) are reserved after the walks have finished, like
+ * the split's memory.  The refusals of ioc_align_pairs_split and of ioc_planes_polish (polish_min_depth < 1, cap, a NULL out_off,
+ * NULL out_seq / out_qual where something may be written); nothing is written on any of them. */
+int ioc_align_pairs_split_polish(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                 int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio,
+                                 ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair,
+                                 int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites, ioc_pile_site* out_sites,
+                                 int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles, int64_t alleles_cap,
+                                 int64_t* allele_off, ioc_pileup_col* out_cols, int32_t min_link, int32_t min_margin, int32_t rounds,
+                                 int64_t* out_link, int8_t* out_phase, uint8_t* out_group, int32_t* out_vote, ioc_split_seg* out_seg,
+                                 int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                                 ioc_polish_stats* out_polish, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins);
 /* Verdict mode.  The clustering loop only ever asks whether out_ratio >= AlignedThreshold (src/cluster.cpp:503).  With a
  * threshold > 0 set here, the traceback of a pair may stop as soon as that comparison is decided — the count of good windows
  * has reached the smallest count whose ratio passes (what is still to come can only add), or can no longer reach it (every

@@ -212,6 +212,41 @@ def ops_project(ops, query, rlen):
     return base, insf
 
 
+def ops_project_ins(ops, query, rlen):
+    """ioc_host_ops_project_ins: which bases one read inserts in front of every row of its reference — a uint8 array of shape
+    (PILE_INS_SLOTS, rlen + 1), slot-major: slots[j, r] is 1 + the channel (1 .. 5 for A C G T other) of the j-th base of the
+    insertion in front of r, 0 where there is none; bases behind the sixth are not kept.  ValueError for what ops_pileup refuses."""
+    slots = np.full((_lib.PILE_INS_SLOTS, rlen + 1), 0xEE, np.uint8)
+    rc = _lib.load().ioc_host_ops_project_ins(bytes(ops), len(ops), bytes(query), len(query), int(rlen), slots.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_project_ins failed ({rc})")
+    return slots
+
+
+def planes_pile(base, slots, cols=None, ins=None):
+    """ioc_host_planes_pile: one read's planes — `base` as ops_project writes it (rlen + 1 bytes), `slots` as ops_project_ins does
+    (PILE_INS_SLOTS x (rlen + 1)) — ADDED to `cols` (PILEUP_DTYPE) and `ins` (PILEUP_INS_DTYPE), rlen + 1 rows each, where given,
+    else to zeros.  Returns (cols, ins): for a string with at most one insertion run per row what ops_pileup and ops_pileup_ins
+    give, except that ins_bases counts at most PILE_INS_SLOTS per run and `longer` stays 0.  ValueError, with both tables
+    untouched, for a byte neither projection writes."""
+    base, slots = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(slots, np.uint8)
+    if base.ndim != 1 or len(base) < 1 or slots.shape != (_lib.PILE_INS_SLOTS, len(base)):
+        raise ValueError("base must hold rlen + 1 bytes and slots PILE_INS_SLOTS x (rlen + 1)")
+    rlen = len(base) - 1
+    if cols is None:
+        cols = np.zeros(rlen + 1, PILEUP_DTYPE)
+    if ins is None:
+        ins = np.zeros(rlen + 1, PILEUP_INS_DTYPE)
+    if cols.dtype != PILEUP_DTYPE or cols.shape != (rlen + 1,) or not cols.flags["C_CONTIGUOUS"]:
+        raise ValueError("cols must be a contiguous array of rlen + 1 rows of PILEUP_DTYPE")
+    if ins.dtype != PILEUP_INS_DTYPE or ins.shape != (rlen + 1,) or not ins.flags["C_CONTIGUOUS"]:
+        raise ValueError("ins must be a contiguous array of rlen + 1 rows of PILEUP_INS_DTYPE")
+    rc = _lib.load().ioc_host_planes_pile(base.ctypes.data, slots.ctypes.data, rlen, cols.ctypes.data, ins.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_planes_pile failed ({rc})")
+    return cols, ins
+
+
 def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
     """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
     returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
@@ -733,11 +768,71 @@ class Context:
                                            int(rounds), link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data))
         return self._split_out(s_off, a_off, sop, ns, n, link, phase, group, vote, seg)
 
+    def planes_polish(self, frames, seg_of_pair, group, base, slots, min_depth=3, tables=False, cap=None):
+        """ioc_planes_polish: the consensus of both groups of every segment on the device, from host planes — `frames` a list of
+        bytes per segment; seg_of_pair / group (0, 1 or SPLIT_NONE) per pair; base / slots lists per pair of what ops_project and
+        ops_project_ins give for that pair (len(frame) + 1 bytes, PILE_INS_SLOTS x (len(frame) + 1)).  Returns a dict: `gseq` and
+        `gqual` (lists of [group 0, group 1] per segment), `gpolish` (POLISH_STATS_DTYPE, shape (segments, 2)), with tables=True
+        `gcols` and `gins` (2 * (len(frame) + 1) rows per segment, group 0's before group 1's) and `grow0` (shape (segments, 2)) —
+        each group-segment as pileup_call defines it on the tables planes_pile adds up from the group's reads."""
+        ns, n = len(frames), len(base)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        sop, grp = np.ascontiguousarray(seg_of_pair, np.int32), np.ascontiguousarray(group, np.uint8)
+        if sop.shape != (n,) or grp.shape != (n,) or len(slots) != n:
+            raise ValueError("seg_of_pair, group, base and slots must hold one entry per pair")
+        rows = [int(rlen[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (rows[i],) or np.shape(slots[i]) != (_lib.PILE_INS_SLOTS, rows[i]):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        P = sum(rows)
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        fs = np.ascontiguousarray(np.concatenate([np.zeros((_lib.PILE_INS_SLOTS, 0), np.uint8)] + [np.asarray(x, np.uint8) for x in slots], axis=1))
+        f_off = np.zeros(ns + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        bound = 2 * sum(pileup_call_bound(r) for r in rlen)
+        cap = bound if cap is None else int(cap)
+        n_rows = 2 * (int(rlen.sum()) + ns)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, pol = np.zeros(2 * ns + 1, np.int64), np.zeros(2 * ns, POLISH_STATS_DTYPE)
+        gcols, gins = (np.zeros(n_rows, PILEUP_DTYPE), np.zeros(n_rows, PILEUP_INS_DTYPE)) if tables else (None, None)
+        self._chk(self.L.ioc_planes_polish(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64), n,
+                                           _p(sop, C.c_int32) if n else None, grp.ctypes.data if n else None, fb.ctypes.data if P else None,
+                                           fs.ctypes.data if P else None, int(min_depth), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64),
+                                           pol.ctypes.data if ns else None, gcols.ctypes.data if tables and n_rows else None,
+                                           gins.ctypes.data if tables and n_rows else None))
+        return self._gpolish_out(ns, rlen, seq, qual, off, pol, gcols, gins, tables)
+
+    @staticmethod
+    def _gpolish_out(ns, rlen, seq, qual, off, pol, gcols, gins, tables):
+        """The group polish's flat outputs as a dict: group-segment 2 g + h becomes entry [g][h]."""
+        out = {"gseq": [[seq[off[2 * g + h]:off[2 * g + h + 1]].tobytes() for h in (0, 1)] for g in range(ns)],
+               "gqual": [[qual[off[2 * g + h]:off[2 * g + h + 1]].tobytes() for h in (0, 1)] for g in range(ns)], "gpolish": pol.reshape(ns, 2)}
+        if tables:
+            rows = np.asarray(rlen, np.int64) + 1
+            first = 2 * np.concatenate([[0], np.cumsum(rows)])[:ns]
+            out.update(gcols=gcols, gins=gins, grow0=np.stack([first, first + rows], axis=1).reshape(ns, 2))
+        return out
+
     def align_pairs_split(self, pairs, k, segs, seg_of_pair, min_depth=3, min_alt=3, min_pct=25, max_sites=4096, min_link=3, min_margin=1, rounds=2,
                           stats=False, tables=False, alleles=False, match=2, mismatch=-2, gap_extend=1):
         """ioc_align_pairs_split: align_pairs_alleles with the split of every segment's reads run where the alleles lie.  Returns
         align_pairs_alleles' dict — `alleles` only with alleles=True, `cols` and `row0` only with tables=True — and the split's:
         `link`, `phase` (lists per segment), `group`, `vote` (per pair), `seg` (SPLIT_SEG_DTYPE per segment), `members`."""
+        return self._align_pairs_split(None, pairs, k, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, min_link, min_margin, rounds, stats,
+                                       tables, alleles, match, mismatch, gap_extend)
+
+    def align_pairs_split_polish(self, pairs, k, segs, seg_of_pair, min_depth=3, min_alt=3, min_pct=25, max_sites=4096, min_link=3, min_margin=1,
+                                 rounds=2, polish_min_depth=3, stats=False, tables=False, alleles=False, cap=None, match=2, mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_split_polish: align_pairs_split with the consensus of both groups of every segment called from the reads'
+        planes where they lie — no read is aligned a second time.  Returns align_pairs_split's dict plus `gseq` and `gqual` (lists of
+        [group 0, group 1] per segment), `gpolish` (POLISH_STATS_DTYPE, shape (segments, 2)) and, with tables=True, `gcols`, `gins`
+        and `grow0` as planes_polish returns them.  A group without reads returns the segment's frame at quality '!'."""
+        return self._align_pairs_split((int(polish_min_depth), cap), pairs, k, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, min_link,
+                                       min_margin, rounds, stats, tables, alleles, match, mismatch, gap_extend)
+
+    def _align_pairs_split(self, polish, pairs, k, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, min_link, min_margin, rounds, stats,
+                           tables, alleles, match, mismatch, gap_extend):
+        """align_pairs_split, and align_pairs_split_polish with polish = (polish_min_depth, cap)"""
         n, ns = len(pairs), len(segs)
         arr = self._aln_pairs(pairs)
         sarr = (_lib.PolishSeg * max(ns, 1))()
@@ -760,15 +855,26 @@ class Context:
         cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
         link, phase = np.zeros(max(s_cap, 1), np.int64), np.zeros(max(s_cap, 1), np.int8)
         group, vote, seg = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(ns, 1), SPLIT_SEG_DTYPE)
-        self._chk(self.L.ioc_align_pairs_split(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns,
-                                               sarr, _p(sop, C.c_int32), int(min_depth), int(min_alt), int(min_pct), int(max_sites),
-                                               sites.ctypes.data, s_cap, _p(s_off, C.c_int64), _p(found, C.c_int64),
-                                               alle.ctypes.data if alleles else None, a_cap if alleles else 0, _p(a_off, C.c_int64),
-                                               cols.ctypes.data if tables and n_rows else None, int(min_link), int(min_margin), int(rounds),
-                                               link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data))
+        args = (self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr, _p(sop, C.c_int32),
+                int(min_depth), int(min_alt), int(min_pct), int(max_sites), sites.ctypes.data, s_cap, _p(s_off, C.c_int64), _p(found, C.c_int64),
+                alle.ctypes.data if alleles else None, a_cap if alleles else 0, _p(a_off, C.c_int64), cols.ctypes.data if tables and n_rows else None,
+                int(min_link), int(min_margin), int(rounds), link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data)
+        if polish is None:
+            self._chk(self.L.ioc_align_pairs_split(*args))
+        else:
+            bound = 2 * sum(pileup_call_bound(r) for r in rlen)
+            g_cap = bound if polish[1] is None else int(polish[1])
+            g_seq, g_qual = np.zeros(max(g_cap, 1), np.uint8), np.zeros(max(g_cap, 1), np.uint8)
+            g_off, g_pol = np.zeros(2 * ns + 1, np.int64), np.zeros(2 * ns, POLISH_STATS_DTYPE)
+            gcols, gins = (np.zeros(2 * n_rows, PILEUP_DTYPE), np.zeros(2 * n_rows, PILEUP_INS_DTYPE)) if tables else (None, None)
+            self._chk(self.L.ioc_align_pairs_split_polish(*args, polish[0], g_seq.ctypes.data, g_qual.ctypes.data, g_cap, _p(g_off, C.c_int64),
+                                                          g_pol.ctypes.data if ns else None, gcols.ctypes.data if tables and n_rows else None,
+                                                          gins.ctypes.data if tables and n_rows else None))
         out = {"score": score, "windows": win, "ratio": ratio, "sites": [sites[s_off[g]:s_off[g + 1]].copy() for g in range(ns)],
                "n_found": found[:ns]}
         out.update(self._split_out(s_off, a_off, sop, ns, n, link, phase, group, vote, seg))
+        if polish is not None:
+            out.update(self._gpolish_out(ns, rlen, g_seq, g_qual, g_off, g_pol, gcols, gins, tables))
         if alleles:
             out["alleles"] = [alle[a_off[i]:a_off[i + 1]].copy() for i in range(n)]
         if stats:

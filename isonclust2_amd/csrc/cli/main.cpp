@@ -978,9 +978,17 @@ static int main_cluster(int argc, char** argv)
 // of them are in group 0, in group 1 and in neither.  read_split.tsv: one row per row read_stats.tsv has — the read's group
 // (0 | 1 | .) and its vote.  Whether a split is real is the reader's judgement of those counts.  Beside --sites, --read-stats and
 // --pileup a group is still aligned once.
+//
+// dump --split --split-polish: <outdir>/cluster_split_polished.fq (ioc_align_pairs_split_polish: the call of --split with the
+// consensus of both groups of every cluster called on the device from the reads' planes, no read aligned a second time).  For
+// every cluster that has a split (a seed site), in cluster order, one record per group that has reads, group 0 before group 1,
+// named after the cluster's record in cluster_cons.fq with "/0" or "/1" appended: "@cluster_<id>/<group> reads=<the group's reads>
+// subs= dels= ins= low=", in the frame of that record; positions covered by fewer than --split-polish-min-depth reads of the
+// group keep the representative's base with quality '!'.  The other report files are what they are without the option.
 struct SplitOpt {
     bool on = false;
     int min_link = 3, min_margin = 1, rounds = 2;
+    int polish_min_depth = 0;  // --split-polish: > 0, the depth below which a group's call keeps the representative's base
 };
 struct SitesOpt {
     bool on = false;
@@ -1082,6 +1090,30 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
             split_out.write(text.data(), std::streamsize(text.size()));
         }
     };
+    // (--split-polish) what the call returned for the two groups of the group's segments
+    const bool want_gpolish = want_split && split_opt.polish_min_depth > 0;
+    string gpol_seq, gpol_qual;
+    std::vector<int64_t> gpol_off;
+    std::vector<ioc_polish_stats> gpol;
+    std::ofstream gpolish_out;
+    if (want_gpolish) create_file(outdir + "/cluster_split_polished.fq", gpolish_out);
+    auto write_gpolish = [&]() {
+        string text;
+        for (size_t x = 0; x < group_cls.size(); ++x) {
+            const int32_t g = group_seg[x];
+            if (g < 0 || split_seg[size_t(g)].seed < 0) continue;
+            for (size_t h = 0; h < 2; ++h) {
+                const int32_t reads = h ? split_seg[size_t(g)].n_group1 : split_seg[size_t(g)].n_group0;
+                if (reads <= 0) continue;
+                const size_t gs = 2 * size_t(g) + h, at = size_t(gpol_off[gs]), len = size_t(gpol_off[gs + 1] - gpol_off[gs]);
+                const ioc_polish_stats& z = gpol[gs];
+                text = "@cluster_" + std::to_string(group_cls[x].first) + '/' + std::to_string(h) + " reads=" + std::to_string(reads) +
+                       " subs=" + std::to_string(z.n_sub) + " dels=" + std::to_string(z.n_del) + " ins=" + std::to_string(z.n_ins) +
+                       " low=" + std::to_string(z.n_low) + "\n" + gpol_seq.substr(at, len) + "\n+\n" + gpol_qual.substr(at, len) + "\n";
+                gpolish_out.write(text.data(), std::streamsize(text.size()));
+            }
+        }
+    };
     auto allele_char = [](int32_t kind, int32_t a) { return kind == IOC_SITE_INS ? (a == 0 ? '.' : a == 1 ? '+' : '?') : (a >= 0 && a <= IOC_ALLELE_DEL ? "ACGTN-"[a] : '?'); };
     auto write_sites = [&]() {
         string text;
@@ -1151,6 +1183,7 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
         if (want_polish) write_polish();
         if (want_sites && !segs.empty()) write_sites();
         if (want_split) write_split();
+        if (want_gpolish && !segs.empty()) write_gpolish();
         group_cls.clear(), row_base.clear(), cols.clear();
         segs.clear(), seg_of_pair.clear(), seg_reads.clear(), group_seg.clear();
         group_rows = 0;
@@ -1186,6 +1219,23 @@ static void write_read_reports(const Batch& b, const string& outdir, size_t n_ro
                 std::vector<uint8_t> group(np);
                 std::vector<int32_t> vote(np);
                 split_seg.assign(segs.size(), ioc_split_seg{});
+                if (want_gpolish) {
+                    int64_t cap = 0;
+                    for (const ioc_polish_seg& sg : segs) {
+                        const int64_t m = offs[size_t(sg.ref) + 1] - offs[size_t(sg.ref)];
+                        cap += 2 * (m + IOC_PILE_INS_SLOTS * (m + 1));
+                    }
+                    gpol_seq.assign(size_t(cap), '\0'), gpol_qual.assign(size_t(cap), '\0');
+                    gpol_off.assign(2 * segs.size() + 1, 0), gpol.assign(2 * segs.size(), ioc_polish_stats{});
+                    check(c, ioc_align_pairs_split_polish(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
+                                                          int32_t(segs.size()), segs.data(), seg_of_pair.data(), sites_opt.min_depth, sites_opt.min_alt,
+                                                          sites_opt.min_pct, sites_opt.max_sites, sites.data(), s_cap, site_off.data(), site_found.data(),
+                                                          want_sites ? alleles.data() : nullptr, want_sites ? a_cap : 0, allele_off.data(),
+                                                          want_pileup ? cols.data() : nullptr, split_opt.min_link, split_opt.min_margin, split_opt.rounds, nullptr,
+                                                          nullptr, group.data(), vote.data(), split_seg.data(), split_opt.polish_min_depth, &gpol_seq[0],
+                                                          &gpol_qual[0], cap, gpol_off.data(), gpol.data(), nullptr, nullptr),
+                          "split by linked sites with the groups' consensus");
+                } else
                 check(c, ioc_align_pairs_split(c, int32_t(np), pairs.data(), k, 2, -2, 1, sc.data(), win.data(), nullptr, want_stats ? st.data() : nullptr,
                                                int32_t(segs.size()), segs.data(), seg_of_pair.data(), sites_opt.min_depth, sites_opt.min_alt, sites_opt.min_pct,
                                                sites_opt.max_sites, sites.data(), s_cap, site_off.data(), site_found.data(), want_sites ? alleles.data() : nullptr,
@@ -1350,7 +1400,8 @@ static int main_dump(int argc, char** argv)
                                        {"sites-min-depth", required_argument, 0, 1006}, {"sites-min-alt", required_argument, 0, 1007},
                                        {"sites-min-pct", required_argument, 0, 1008}, {"sites-max", required_argument, 0, 1009},
                                        {"split", no_argument, 0, 1010}, {"split-min-link", required_argument, 0, 1011},
-                                       {"split-min-margin", required_argument, 0, 1012}, {"split-rounds", required_argument, 0, 1013}, {0, 0, 0, 0}};
+                                       {"split-min-margin", required_argument, 0, 1012}, {"split-rounds", required_argument, 0, 1013},
+                                       {"split-polish", no_argument, 0, 1014}, {"split-polish-min-depth", required_argument, 0, 1015}, {0, 0, 0, 0}};
     string outdir, index;
     bool read_stats = false;  // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
     bool pileup = false;      // --pileup: cluster_pileup.tsv, the same alignments piled onto the representative position by position
@@ -1358,6 +1409,8 @@ static int main_dump(int argc, char** argv)
     int polish_min_depth = 3;  // --polish-min-depth: positions covered by fewer reads keep the representative's base
     bool polish_weighted = false;  // --polish-weighted: the call of --polish with every read's vote weighted by its base quality
     SitesOpt sites;  // --sites: cluster_sites.tsv and read_alleles.tsv, where the reads of a cluster disagree and which read says what there
+    bool split_polish = false;       // --split-polish: cluster_split_polished.fq, the consensus of each group of every cluster that has a split
+    int split_polish_min_depth = 3;  // --split-polish-min-depth: positions covered by fewer reads of the group keep the representative's base
     SplitOpt split;  // --split: cluster_split.tsv and read_split.tsv, the reads of a cluster in two groups by its linked sites
     // a whole number of [lo, hi], or the end of the run
     auto number = [](const char* name, const char* text, long lo, long hi) {
@@ -1388,10 +1441,13 @@ static int main_dump(int argc, char** argv)
             case 1011: split.min_link = number("--split-min-link", optarg, 1, INT32_MAX); break;
             case 1012: split.min_margin = number("--split-min-margin", optarg, 1, INT32_MAX); break;
             case 1013: split.rounds = number("--split-rounds", optarg, 0, 64); break;
+            case 1014: split_polish = true; break;
+            case 1015: split_polish_min_depth = number("--split-polish-min-depth", optarg, 1, INT32_MAX); break;
             case 'h':
                 cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N] [--polish-weighted]]" << endl
                      << "                    [--sites [--sites-min-depth N] [--sites-min-alt N] [--sites-min-pct P] [--sites-max N]]" << endl
-                     << "                    [--split [--split-min-link N] [--split-min-margin N] [--split-rounds N]] final.cer" << endl
+                     << "                    [--split [--split-min-link N] [--split-min-margin N] [--split-rounds N]" << endl
+                     << "                     [--split-polish [--split-polish-min-depth N]]] final.cer" << endl
                      << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
                      << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
                      << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -1415,7 +1471,11 @@ static int main_dump(int argc, char** argv)
                      << "                 group (0 | 1 | .) and vote (GPU); whether a cluster is one thing or two is the reader's judgement of the counts" << endl
                      << "  --split-min-link N     two sites are linked when their reads agree or disagree by at least N (default 3)" << endl
                      << "  --split-min-margin N   a read joins a group when its vote is at least N on that side (default 1)" << endl
-                     << "  --split-rounds N       refinement rounds, 0 .. 64, which carry the split along a representative no read spans (default 2)" << endl;
+                     << "  --split-rounds N       refinement rounds, 0 .. 64, which carry the split along a representative no read spans (default 2)" << endl
+                     << "  --split-polish         with --split: also write outdir/cluster_split_polished.fq, for every cluster that has a split the" << endl
+                     << "                 consensus of each group that has reads (records <cluster>/0 and <cluster>/1), called from the alignments" << endl
+                     << "                 of --split: no read is aligned again" << endl
+                     << "  --split-polish-min-depth N   positions covered by fewer than N reads of the group keep the representative's base (default 3)" << endl;
                 exit(0);
             default: break;
         }
@@ -1424,6 +1484,8 @@ static int main_dump(int argc, char** argv)
     if (outdir.empty()) die("Specifying output directory is mandatory!");
     if (polish && polish_min_depth < 1) die("--polish-min-depth must be at least 1!");
     if (polish_weighted && !polish) die("--polish-weighted asks for --polish!");
+    if (split_polish && !split.on) die("--split-polish asks for --split!");
+    if (split_polish) split.polish_min_depth = split_polish_min_depth;
     if (index.empty()) die("Specifying the sorted read index is mandatory!");
     Batch b;
     string err, fastq;
@@ -1597,7 +1659,8 @@ static int main_dump(int argc, char** argv)
             return ReadStatRow{r.cls, r.strand, r.hb, size_t(r.he - r.hb), r.sb, size_t(r.se - r.sb), r.qb, size_t(r.qe - r.qb)};
         }, read_stats, pileup, polish ? polish_min_depth : 0, polish_weighted, sites, split);
         const string reports = string(read_stats ? "read_stats.tsv, " : "") + (pileup ? "cluster_pileup.tsv, " : "") + (polish ? "cluster_polished.fq, " : "") +
-                               (sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") + (split.on ? "cluster_split.tsv, read_split.tsv, " : "");
+                               (sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") + (split.on ? "cluster_split.tsv, read_split.tsv, " : "") +
+                               (split_polish ? "cluster_split_polished.fq, " : "");
         lap((reports.substr(0, reports.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

@@ -428,6 +428,62 @@ int ioc_host_ops_project(const char* ops, int64_t len, const char* query, int32_
     return IOC_OK;
 }
 
+// The insertion part of a read's projection (isonclust2_hip.h has the rules): which bases the read inserts in front of every row,
+// slot-major — the definition k_ops_project_ins (ioc_plane_pile.hip) is tested against.  The walk and the refusals of
+// ioc_host_ops_pileup_ins.
+int ioc_host_ops_project_ins(const char* ops, int64_t len, const char* query, int32_t qlen, int32_t rlen, uint8_t* slots)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || qlen < 0 || rlen < 0 || (qlen > 0 && !query) || !slots) return IOC_ERR_ARG;
+    int64_t q = 0, r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        q += op == '=' || op == 'X' || op == 'I' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (q != qlen || r != rlen) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1;
+    memset(slots, 0, size_t(IOC_PILE_INS_SLOTS) * rows);
+    q = r = 0;
+    int64_t j = 0;  // the index of an 'I' in its run
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (op == 'I') {
+            if (j < IOC_PILE_INS_SLOTS) slots[size_t(j) * rows + size_t(r)] = uint8_t(1u + PileAcc::channel(uint8_t(query[q])));
+            ++j, ++q;
+            continue;
+        }
+        j = 0;
+        q += op == '=' || op == 'X' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    return IOC_OK;
+}
+
+// One read's planes ADDED to the two tables of its reference (isonclust2_hip.h has the rules) — the definition k_plane_pile
+// (ioc_plane_pile.hip) is tested against.  Both tables are checked before either is touched.
+int ioc_host_planes_pile(const uint8_t* base, const uint8_t* slots, int32_t rlen, ioc_pileup_col* cols, ioc_pileup_ins* ins)
+{
+    if (rlen < 0 || !base || !slots || !cols || !ins) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1;
+    for (size_t r = 0; r < rows; ++r)
+        if (base[r] > IOC_ALLELE_DEL && base[r] != IOC_ALLELE_NONE) return IOC_ERR_ARG;
+    for (size_t x = 0; x < size_t(IOC_PILE_INS_SLOTS) * rows; ++x)
+        if (slots[x] > 5) return IOC_ERR_ARG;
+    for (size_t r = 0; r < rows; ++r) {
+        uint32_t* const word = reinterpret_cast<uint32_t*>(&cols[r]);  // (a c g t other del: the record's first six words, PILE_A .. PILE_DEL)
+        if (base[r] != IOC_ALLELE_NONE) word[base[r]] += 1;
+        for (size_t j = 0; j < size_t(IOC_PILE_INS_SLOTS); ++j) {
+            const uint8_t s = slots[j * rows + r];
+            if (s == 0) continue;
+            ins[r].slot[j][s - 1] += 1;
+            cols[r].ins_bases += 1;
+            if (j == 0) cols[r].ins_runs += 1;
+        }
+    }
+    return IOC_OK;
+}
+
 // The sites of one reference from its table of counts (isonclust2_hip.h has the rules; pile_sites_row, ioc_pile_sites.h, decides a
 // row for this function and for the kernels of ioc_pile_sites.hip alike).
 int64_t ioc_host_pileup_sites(const ioc_pileup_col* cols, int32_t rlen, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,

@@ -1205,7 +1205,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     int r;
     if (stats && (r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
     EventSet ev;
-    ev.v.assign(4, nullptr);
+    ev.v.assign(5, nullptr);
     for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
     if (stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
@@ -1232,6 +1232,10 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
         IOC_CHK(c, iock_ops_project(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_plane, pool, pool_bytes,
                                     pl.base_planes, pl.ins_planes, uint64_t(pl.plane_bytes)));
     IOC_CHK(c, hipEventRecord(ev.v[3], c->stream));
+    if (h.projects_ins())
+        IOC_CHK(c, iock_ops_project_ins(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_plane, pool,
+                                        pool_bytes, pl.slot_planes, uint64_t(pl.plane_bytes)));
+    IOC_CHK(c, hipEventRecord(ev.v[4], c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
@@ -1252,6 +1256,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     if (stats && hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) t.ms_stats += double(ms);
     if (pile && hipEventElapsedTime(&ms, ev.v[1], ev.v[2]) == hipSuccess) t.ms_pileup += double(ms);
     if (h.projects() && hipEventElapsedTime(&ms, ev.v[2], ev.v[3]) == hipSuccess) t.ms_project += double(ms);
+    if (h.projects_ins() && hipEventElapsedTime(&ms, ev.v[3], ev.v[4]) == hipSuccess) t.ms_project_ins += double(ms);
     t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t.copied += int64_t(dp.size() * 4 + (stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
     if (stats) t.records += int64_t(cnt);

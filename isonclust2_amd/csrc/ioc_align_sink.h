@@ -24,6 +24,8 @@ struct AlnTally {
     double ms_project = 0; // k_ops_project's device time (a pile that projects), ...
     double ms_sites = 0;   // ... k_pile_sites' and ...
     double ms_alleles = 0; // ... k_site_alleles' (ioc_align_pairs_alleles)
+    double ms_project_ins = 0;  // k_ops_project_ins' device time (a pile that projects what the pairs insert as well), and ...
+    double ms_plane_pile = 0;   // ... k_plane_pile's (ioc_planes_polish, ioc_align_pairs_split_polish)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
     int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };
@@ -140,12 +142,17 @@ struct AlnSink {
         uint8_t* ins_planes = nullptr;   // (device) ... whether it inserts in front of it
         int64_t plane_bytes = 0;         // bytes per plane
         const int64_t* plane = nullptr;
+        // optional, with project (project_ins): what the pair inserts is projected too (k_ops_project_ins), into reference length + 1
+        // bytes of each of IOC_PILE_INS_SLOTS more planes, one behind the other, from byte plane[i] of each on
+        bool project_ins = false;
+        uint8_t* slot_planes = nullptr;  // (device) [all slot-0 planes] .. [all slot-5 planes], plane_bytes each
     } pile;
 
     bool reduced() const { return kind == SinkKind::reduced; }
     bool has_stats() const { return reduced() && with_stats; }
     bool has_pile() const { return reduced() && pile.kind != PileKind::none; }
     bool projects() const { return has_pile() && pile.project; }
+    bool projects_ins() const { return projects() && pile.project_ins; }
     // what the tables hold of the device for the whole call (ck_budget's `held`)
     uint64_t pile_bytes() const
     {
@@ -153,7 +160,7 @@ struct AlnSink {
         const uint64_t per_row = pile.kind == PileKind::counts ? sizeof(ioc_pileup_col)
                                  : pile.kind == PileKind::ins  ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins)
                                                                : 2 * sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins);
-        return uint64_t(pile.rows) * per_row + (pile.project ? 2 * uint64_t(pile.plane_bytes) : 0);
+        return uint64_t(pile.rows) * per_row + (pile.project ? (pile.project_ins ? 2 + uint64_t(IOC_PILE_INS_SLOTS) : 2) * uint64_t(pile.plane_bytes) : 0);
     }
     OpsLayout layout(size_t np) const { return ops_layout(np, kind, reduced() ? pile.kind : PileKind::none, projects()); }
 

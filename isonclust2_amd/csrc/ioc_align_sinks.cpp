@@ -11,6 +11,7 @@
 
 #include "ioc_align_sink.h"
 #include "ioc_internal.h"
+#include "ioc_plane_pile.h"
 
 namespace {
 
@@ -43,6 +44,12 @@ struct SplitCall {
     uint8_t* out_group;
     int32_t* out_vote;
     ioc_split_seg* out_seg;
+    // (ioc_align_pairs_split_polish) where the split left the member lists and the group bytes on the device (a_split), for the
+    // stage behind it; NULL: nobody asks
+    struct Laid {
+        const uint32_t *mem_off = nullptr, *members = nullptr;
+        const uint8_t* group = nullptr;
+    }* laid = nullptr;
 };
 
 // the parameters ioc_host_alleles_split refuses
@@ -113,6 +120,7 @@ int split_device(ioc_ctx* c, const SplitCall& sp, size_t n, size_t np, const int
                         u64p(o_bm), u64p(o_bM), u64p(o_g1), u64p(o_g0), reinterpret_cast<long long*>(p + o_link), reinterpret_cast<int8_t*>(p + o_phase),
                         reinterpret_cast<int32_t*>(p + o_seed), p + o_group, reinterpret_cast<int32_t*>(p + o_vote),
                         reinterpret_cast<ioc_split_seg*>(p + o_rec)};
+    if (sp.laid) *sp.laid = SplitCall::Laid{reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem), p + o_group};
     std::vector<IocSplitStep> steps{IocSplitStep::marks, IocSplitStep::bits, IocSplitStep::link, IocSplitStep::seed, IocSplitStep::phase0,
                                     IocSplitStep::vote};
     for (int32_t r = 0; r < sp.rounds; ++r) steps.insert(steps.end(), {IocSplitStep::group_bits, IocSplitStep::rephase, IocSplitStep::vote});
@@ -169,6 +177,7 @@ struct SitesCall {
     uint8_t* out_alleles = nullptr;  // (NULL with a split: the alleles stay on the device)
     int64_t* allele_off = nullptr;
     const SplitCall* split = nullptr;  // (ioc_align_pairs_split) the split, run where the sites and the alleles lie
+    bool project_ins = false;          // (ioc_align_pairs_split_polish) the six slot planes behind the two: what every pair inserts
 };
 
 // The site kernels over a table that lies on the device (n_rows records), then k_site_alleles over the planes d_base / d_ins where
@@ -356,12 +365,140 @@ int pileup_call_tables(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const ch
     return IOC_OK;
 }
 
+// what a polish of the groups of a split is run with and where it leaves what it made (ioc_planes_polish's outputs)
+struct GroupPolish {
+    int32_t min_depth;
+    char *out_seq, *out_qual;
+    int64_t cap;
+    int64_t* out_off;
+    ioc_polish_stats* out_polish;
+    ioc_pileup_col* out_gcols;
+    ioc_pileup_ins* out_gins;
+};
+
+// what a group polish refuses once the segments are known: IOC_OK, or the status with the message set
+int group_polish_ok(ioc_ctx* c, const std::string& who, const GroupPolish& gp, const std::vector<IocPileSeg>& ds)
+{
+    for (size_t g = 0; g < ds.size(); ++g)
+        if (int64_t(ds[g].rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(ds[g].rlen) + 1) > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
+            return ioc_fail(c, IOC_ERR_CAPACITY, who + ": segment " + std::to_string(g) + " may call more than 2^31 - 1 bytes");
+    const int64_t bound = 2 * pile_call_bound(ds);
+    if (gp.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": cap " + std::to_string(gp.cap) + " below the bound " + std::to_string(bound));
+    if (bound > 0 && (!gp.out_seq || !gp.out_qual)) return IOC_ERR_ARG;
+    return IOC_OK;
+}
+
+// where the planes, the member lists and the group bytes of a group polish lie on the device; a NULL pointer: the host's array is
+// uploaded (ioc_planes_polish: all of them; behind a split: none)
+struct PlanesDev {
+    const uint32_t *mem_off, *members;
+    const uint8_t *group, *base, *slots;
+    uint64_t plane_bytes;
+};
+struct PlanesHost {
+    const int32_t* seg_of_pair;
+    const uint8_t* group;  // per pair: 0, 1 or IOC_SPLIT_NONE
+    const int64_t* plane;  // per pair: where its rows start in every plane
+    const uint8_t *base, *slots;
+};
+
+// k_plane_pile and the call kernels over the 2 n group-segments of the segments ds (frames in d_frames): a_gpile holds
+// [group-segments][work items][plane offsets][mem_off][members][group][base plane][slot planes][gcols][gins], the middle five only
+// where they are uploaded.  Group-segment 2 g + h owns the rows 2 * row0(g) + h * (rlen(g) + 1) .. of both tables, which are set
+// to 0 first: k_plane_pile is launched over the group-segments that have reads alone.  Device times go to t.ms_plane_pile /
+// t.ms_call, the copies to t.ms_copy / t.copied.
+int group_polish_device(ioc_ctx* c, const GroupPolish& gp, const std::vector<IocPileSeg>& ds, const uint8_t* d_frames, uint64_t frame_bytes, size_t np,
+                        const PlanesHost& ph, PlanesDev pd, AlnTally& t)
+{
+    const size_t n = ds.size();
+    std::vector<IocPileSeg> gsegs(2 * n);
+    std::vector<uint32_t> reads(2 * n, 0);
+    int64_t n_rows = 0;
+    for (size_t g = 0; g < n; ++g)
+        for (int64_t h = 0; h < 2; ++h) {
+            gsegs[2 * g + size_t(h)] = IocPileSeg{2 * ds[g].row0 + h * (int64_t(ds[g].rlen) + 1), ds[g].f_off, ds[g].rlen, ds[g].rc};
+            n_rows += int64_t(ds[g].rlen) + 1;
+        }
+    for (size_t i = 0; i < np; ++i)
+        if (ph.group[i] <= 1) ++reads[2 * size_t(ph.seg_of_pair[i]) + ph.group[i]];
+    std::vector<IocPlaneWork> work;
+    for (size_t x = 0; x < 2 * n; ++x)
+        for (int64_t row = 0; reads[x] > 0 && row <= int64_t(gsegs[x].rlen); row += IOC_PLANE_PILE_ROWS) work.push_back(IocPlaneWork{uint32_t(x), uint32_t(row)});
+    if (work.size() > size_t(INT32_MAX)) return ioc_fail(c, IOC_ERR_CAPACITY, "the group tables have more than 2^31 - 1 blocks of rows");
+    std::vector<uint32_t> mem_off, members;
+    if (!pd.members) {  // (a segment's reads are its pairs in ascending order, as the split has them)
+        mem_off.assign(n + 1, 0), members.resize(np);
+        for (size_t i = 0; i < np; ++i) ++mem_off[size_t(ph.seg_of_pair[i]) + 1];
+        for (size_t g = 0; g < n; ++g) mem_off[g + 1] += mem_off[g];
+        std::vector<uint32_t> next(mem_off.begin(), mem_off.end() - 1);
+        for (size_t i = 0; i < np; ++i) members[next[size_t(ph.seg_of_pair[i])]++] = uint32_t(i);
+    }
+    const size_t P = size_t(pd.plane_bytes);
+    auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    size_t at = 0;
+    auto take = [&](size_t b) { const size_t o = at; at += up16(b); return o; };
+    const size_t o_gseg = take(2 * n * sizeof(IocPileSeg)), o_work = take(work.size() * sizeof(IocPlaneWork)), o_plane = take(np * 8),
+                 o_moff = take(pd.members ? 0 : (n + 1) * 4), o_mem = take(pd.members ? 0 : np * 4), o_group = take(pd.group ? 0 : np),
+                 o_base = take(pd.base ? 0 : P), o_slots = take(pd.slots ? 0 : size_t(IOC_PILE_INS_SLOTS) * P),
+                 o_cols = take(size_t(n_rows) * sizeof(ioc_pileup_col)), o_ins = take(size_t(n_rows) * sizeof(ioc_pileup_ins));
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_gpile, at));
+    uint8_t* p = static_cast<uint8_t*>(c->a_gpile.p);
+    auto up = [&](size_t o, const void* src, size_t b) { return b ? hipMemcpyAsync(p + o, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(o_gseg, gsegs.data(), 2 * n * sizeof(IocPileSeg)));
+    IOC_CHK(c, up(o_work, work.data(), work.size() * sizeof(IocPlaneWork)));
+    IOC_CHK(c, up(o_plane, ph.plane, np * 8));
+    if (!pd.members) {
+        IOC_CHK(c, up(o_moff, mem_off.data(), (n + 1) * 4));
+        IOC_CHK(c, up(o_mem, members.data(), np * 4));
+        pd.mem_off = reinterpret_cast<const uint32_t*>(p + o_moff), pd.members = reinterpret_cast<const uint32_t*>(p + o_mem);
+    }
+    if (!pd.group) {
+        IOC_CHK(c, up(o_group, ph.group, np));
+        pd.group = p + o_group;
+    }
+    if (!pd.base) {
+        IOC_CHK(c, up(o_base, ph.base, P));
+        pd.base = p + o_base;
+    }
+    if (!pd.slots) {
+        IOC_CHK(c, up(o_slots, ph.slots, size_t(IOC_PILE_INS_SLOTS) * P));
+        pd.slots = p + o_slots;
+    }
+    ioc_pileup_col* const d_cols = reinterpret_cast<ioc_pileup_col*>(p + o_cols);
+    ioc_pileup_ins* const d_ins = reinterpret_cast<ioc_pileup_ins*>(p + o_ins);
+    if (n_rows > 0) IOC_CHK(c, hipMemsetAsync(p + o_cols, 0, at - o_cols, c->stream));
+    EventSet ev;
+    ev.v.assign(2, nullptr);
+    for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
+    IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
+    IOC_CHK(c, iock_plane_pile(c->stream, reinterpret_cast<const IocPlaneWork*>(p + o_work), uint32_t(work.size()), reinterpret_cast<const IocPileSeg*>(p + o_gseg),
+                               pd.mem_off, pd.members, uint32_t(np), pd.group, reinterpret_cast<const uint64_t*>(p + o_plane), pd.base, pd.slots,
+                               pd.plane_bytes, d_cols, d_ins, uint64_t(n_rows)));
+    IOC_CHK(c, hipEventRecord(ev.v[1], c->stream));
+    const PileCall pc{gsegs, d_frames, frame_bytes, gp.min_depth, gp.out_seq, gp.out_qual, gp.out_off, gp.out_polish};
+    IOC_TRY(pile_call_device(c, pc, d_cols, d_ins, nullptr, n_rows, t));  // (waits for the stream)
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess) t.ms_plane_pile += double(ms);
+    const auto t0 = std::chrono::steady_clock::now();
+    const struct { void* dst; const void* src; size_t bytes; } outs[] = {{gp.out_gcols, d_cols, size_t(n_rows) * sizeof(ioc_pileup_col)},
+                                                                         {gp.out_gins, d_ins, size_t(n_rows) * sizeof(ioc_pileup_ins)}};
+    for (const auto& o : outs)
+        if (o.dst && o.bytes) {
+            IOC_CHK(c, hipMemcpy(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost));
+            t.copied += int64_t(o.bytes);
+        }
+    t.ms_copy += ms_since(t0);
+    return IOC_OK;
+}
+
 // What ioc_align_pairs_pileup and the polish calls share.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it
 // (ins), or a_pile_w as [wcols][wins] (weighted) — are reserved and zeroed, the pairs aligned into them (k_ops_pileup adds, where
 // the walks' bytes lie, slice after slice and re-run after re-run) and, where `call` is given, called where they lie; then the
 // tables asked for are copied out, once.  out_ins: the second table of its kind (ins, or wins).  `sites` (ioc_align_pairs_alleles):
-// every pair is projected as well, into the planes of a_planes, [base planes][ins planes], set to IOC_ALLELE_NONE / 0 once here,
-// and the sites are found and the alleles gathered where the table and the planes lie.
+// every pair is projected as well, into the planes of a_planes, [base planes][ins planes] and, where the call polishes the groups
+// of a split, [slot planes x 6] behind them, set to IOC_ALLELE_NONE / 0 once here, and the sites are found and the alleles
+// gathered where the table and the planes lie.
 static int align_pairs_piled(ioc_ctx* c, const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows,
                              const PileCall* call, ioc_pileup_col* out_cols, ioc_pileup_col* out_wcols, ioc_pileup_ins* out_ins, AlnTally& t,
                              const SitesCall* sites = nullptr)
@@ -382,12 +519,13 @@ static int align_pairs_piled(ioc_ctx* c, const AlnCall& a, PileKind kind, ioc_al
     if (weighted) pl.wcols = second->as<ioc_pileup_col>(), pl.wins = reinterpret_cast<ioc_pileup_ins*>(second->as<uint8_t>() + b_cols);  // (b_cols: a multiple of 32)
     if (sites) {
         const size_t b_plane = size_t(sites->plane_bytes);
-        IOC_TRY(ioc_reserve(c, c->a_planes, 2 * b_plane));
+        IOC_TRY(ioc_reserve(c, c->a_planes, (sites->project_ins ? 2 + size_t(IOC_PILE_INS_SLOTS) : 2) * b_plane));
         pl.project = true, pl.base_planes = c->a_planes.as<uint8_t>(), pl.ins_planes = pl.base_planes + b_plane;
         pl.plane_bytes = sites->plane_bytes, pl.plane = sites->plane;
+        if (sites->project_ins) pl.project_ins = true, pl.slot_planes = pl.base_planes + 2 * b_plane;
         if (b_plane > 0) {
             IOC_CHK(c, hipMemsetAsync(pl.base_planes, IOC_ALLELE_NONE, b_plane, c->stream));
-            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, b_plane, c->stream));
+            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, (sites->project_ins ? 1 + size_t(IOC_PILE_INS_SLOTS) : 1) * b_plane, c->stream));  // (and the slot planes)
         }
     }
     const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, out_stats != nullptr, out_stats, pl};
@@ -573,9 +711,11 @@ static int align_pairs_alleles(const char* who_, ioc_ctx* c, int32_t n_pairs, co
                                int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
                                const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct,
                                int32_t max_sites, ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles,
-                               int64_t alleles_cap, int64_t* allele_off, ioc_pileup_col* out_cols, const SplitCall* split)
+                               int64_t alleles_cap, int64_t* allele_off, ioc_pileup_col* out_cols, const SplitCall* split,
+                               const GroupPolish* gp = nullptr /* (ioc_align_pairs_split_polish, with `split`) both groups of every segment are called */)
 {
     const std::string who = who_;
+    if (gp && (!split || gp->min_depth < 1 || !gp->out_off || gp->cap < 0)) return IOC_ERR_ARG;
     if (split && (!split_rule_ok(split->min_link, split->min_margin, split->rounds) || (n_pairs > 0 && !split->out_group) || (n_segs > 0 && !split->out_seg)))
         return IOC_ERR_ARG;
     if (!c || n_pairs < 0 || n_segs < 0 || !sites_rule_ok(min_depth, min_alt, min_pct, max_sites) || !site_off || !allele_off || sites_cap < 0 ||
@@ -610,20 +750,35 @@ static int align_pairs_alleles(const char* who_, ioc_ctx* c, int32_t n_pairs, co
     if ((out_alleles || !split) && alleles_cap < alleles_bound)
         return ioc_fail(c, IOC_ERR_CAPACITY, who + ": alleles_cap " + std::to_string(alleles_cap) + " below the bound " + std::to_string(alleles_bound));
     if ((bound > 0 && !out_sites) || (alleles_bound > 0 && !out_alleles && !split)) return IOC_ERR_ARG;
+    if (gp) IOC_TRY(group_polish_ok(c, who, *gp, ds));
     for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    if (gp) gp->out_off[0] = 0;
     site_off[0] = 0;
     for (int32_t i = 0; i <= n_pairs; ++i) allele_off[i] = 0;
     if (n_segs == 0) return a.run(c, nullptr);
     AlnTally t;
+    SplitCall::Laid laid;
+    SplitCall sp_laid = split ? *split : SplitCall{};
+    sp_laid.laid = &laid;
     const SitesCall sc{ds, min_depth, min_alt, min_pct, max_sites, out_sites, site_off, n_found, n_pairs, seg_of_pair, plane.data(), plane_bytes,
-                       alleles_bound, out_alleles, allele_off, split};
+                       alleles_bound, out_alleles, allele_off, gp ? &sp_laid : split, gp != nullptr};
     IOC_TRY(align_pairs_piled(c, a, PileKind::counts, out_stats, row_base.data(), n_rows, nullptr, out_cols, nullptr, nullptr, t, &sc));
+    if (gp) {  // (the planes are where the walks left them, the lists and the group bytes where the split did; the groups are the host's too)
+        const uint8_t* planes = c->a_planes.as<uint8_t>();
+        const PlanesDev pd{laid.mem_off, laid.members, laid.group, planes, planes + 2 * size_t(plane_bytes), uint64_t(plane_bytes)};
+        if (!pd.members || !pd.group) return ioc_fail(c, IOC_ERR_HIP, who + ": the split left no member lists");
+        IOC_TRY(group_polish_device(c, *gp, ds, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), size_t(n_pairs),
+                                    PlanesHost{seg_of_pair, split->out_group, plane.data(), nullptr, nullptr}, pd, t));
+    }
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: sites: %d segments, %lld rows, %lld sites kept, %lld allele bytes, %.3f MB (sites, alleles, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_pile_sites %.3f ms, k_site_alleles %.3f ms%s\n",
                 n_segs, (long long)n_rows, (long long)site_off[n_segs], (long long)allele_off[n_pairs], double(t.copied) * 1e-6, out_cols ? ", table" : "",
                 out_stats ? ", statistics" : "", t.ms_copy, t.ms_pileup, t.ms_project, t.ms_sites, t.ms_alleles,
                 out_stats ? (", k_ops_stats " + std::to_string(t.ms_stats) + " ms").c_str() : "");
     if (split && getenv("IOC_TRACE")) fprintf(stderr, "[ioc]   aligner: split: %s\n", split_trace(t).c_str());
+    if (gp && getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: split polish: %d group-segments, %lld bytes called, k_ops_project_ins %.3f ms, k_plane_pile %.3f ms, k_pile_call %.3f ms\n",
+                2 * n_segs, (long long)gp->out_off[2 * n_segs], t.ms_project_ins, t.ms_plane_pile, t.ms_call);
     return IOC_OK;
 }
 
@@ -651,6 +806,66 @@ int ioc_align_pairs_split(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs
     return align_pairs_alleles("ioc_align_pairs_split", c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats,
                                n_segs, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, out_sites, sites_cap, site_off, n_found, out_alleles,
                                alleles_cap, allele_off, out_cols, &sp);
+}
+
+// ioc_align_pairs_split with the six slot planes projected beside the two, and behind k_split_record k_plane_pile and the call
+// kernels over the planes: the consensus of both groups of every segment, with no pair aligned a second time.
+int ioc_align_pairs_split_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                 int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                 const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                 int32_t max_sites, ioc_pile_site* out_sites, int64_t sites_cap, int64_t* site_off, int64_t* n_found, uint8_t* out_alleles,
+                                 int64_t alleles_cap, int64_t* allele_off, ioc_pileup_col* out_cols, int32_t min_link, int32_t min_margin, int32_t rounds,
+                                 int64_t* out_link, int8_t* out_phase, uint8_t* out_group, int32_t* out_vote, ioc_split_seg* out_seg,
+                                 int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                                 ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins)
+{
+    const SplitCall sp{min_link, min_margin, rounds, out_link, out_phase, out_group, out_vote, out_seg};
+    const GroupPolish gp{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish, out_gcols, out_gins};
+    return align_pairs_alleles("ioc_align_pairs_split_polish", c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio,
+                               out_stats, n_segs, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, out_sites, sites_cap, site_off, n_found,
+                               out_alleles, alleles_cap, allele_off, out_cols, &sp, &gp);
+}
+
+// The group polish from planes the caller holds: everything is uploaded, and the kernels run as behind ioc_align_pairs_split_polish.
+int ioc_planes_polish(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, int32_t n_pairs,
+                      const int32_t* seg_of_pair, const uint8_t* group, const uint8_t* base, const uint8_t* slots, int32_t min_depth, char* out_seq,
+                      char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins)
+{
+    if (!c || n_segs < 0 || n_pairs < 0 || min_depth < 1 || !out_off || cap < 0 || (n_segs > 0 && (!rlen || !frame_off)) ||
+        (n_pairs > 0 && (!seg_of_pair || !group)))
+        return IOC_ERR_ARG;
+    std::vector<IocPileSeg> ds(static_cast<size_t>(n_segs));
+    int64_t n_rows = 0, frame_bytes = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (rlen[g] < 0 || frame_off[g] < 0 || (rlen[g] > 0 && !frames)) return ioc_fail(c, IOC_ERR_ARG, "ioc_planes_polish: segment " + std::to_string(g) + " has a negative length or frame offset");
+        ds[size_t(g)] = IocPileSeg{n_rows, frame_off[g], rlen[g], 0};
+        n_rows += int64_t(rlen[g]) + 1;
+        frame_bytes = std::max(frame_bytes, frame_off[g] + rlen[g]);
+    }
+    std::vector<int64_t> plane(size_t(n_pairs), 0);
+    int64_t plane_bytes = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        if (seg_of_pair[i] < 0 || seg_of_pair[i] >= n_segs) return ioc_fail(c, IOC_ERR_ARG, "ioc_planes_polish: pair " + std::to_string(i) + " names no segment");
+        if (group[i] > 1 && group[i] != IOC_SPLIT_NONE) return ioc_fail(c, IOC_ERR_ARG, "ioc_planes_polish: the group byte of pair " + std::to_string(i) + " is neither 0, 1 nor IOC_SPLIT_NONE");
+        plane[size_t(i)] = plane_bytes;
+        plane_bytes += int64_t(ds[size_t(seg_of_pair[i])].rlen) + 1;
+    }
+    if (plane_bytes > 0 && (!base || !slots)) return IOC_ERR_ARG;
+    const GroupPolish gp{min_depth, out_seq, out_qual, cap, out_off, out_polish, out_gcols, out_gins};
+    IOC_TRY(group_polish_ok(c, "ioc_planes_polish", gp, ds));
+    out_off[0] = 0;
+    if (n_segs == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(frame_bytes)));
+    if (frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(frame_bytes), hipMemcpyHostToDevice, c->stream));
+    AlnTally t;
+    IOC_TRY(group_polish_device(c, gp, ds, static_cast<const uint8_t*>(d_frames.p), uint64_t(frame_bytes), size_t(n_pairs),
+                                PlanesHost{seg_of_pair, group, plane.data(), base, slots}, PlanesDev{nullptr, nullptr, nullptr, nullptr, nullptr, uint64_t(plane_bytes)}, t));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes polish: %d group-segments, %lld rows, %d pairs, %lld plane bytes, %lld bytes called, k_plane_pile %.3f ms, k_pile_call %.3f ms\n",
+                2 * n_segs, (long long)(2 * n_rows), n_pairs, (long long)(8 * plane_bytes), (long long)out_off[2 * n_segs], t.ms_plane_pile, t.ms_call);
+    return IOC_OK;
 }
 
 // The split of segments whose sites and alleles the caller holds: both are uploaded, and the kernels run as behind

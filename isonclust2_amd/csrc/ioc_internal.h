@@ -213,7 +213,10 @@ struct ioc_ctx {
     DevBuf a_qual;      // ioc_align_set_pool_qual: one quality byte per byte of a_pool ...
     bool aln_qual_set = false;  // ... which it holds for the current pool
     DevBuf a_planes;  // ioc_align_pairs_alleles: every pair's projection, [base planes][ins planes] (k_ops_project)
+                      // and, for ioc_align_pairs_split_polish, [slot planes x 6] behind them (k_ops_project_ins)
     DevBuf a_split;   // ioc_alleles_split, ioc_align_pairs_split: member lists, bit planes, per-site and per-pair words (ioc_site_split.hip)
+    DevBuf a_gpile;   // ioc_planes_polish, ioc_align_pairs_split_polish: the group-segments, their work items and tables (k_plane_pile) and,
+                      // from host planes, the uploaded member lists and planes
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
@@ -395,6 +398,18 @@ hipError_t iock_site_alleles(hipStream_t st, uint32_t n_pairs, const int32_t* se
                              const uint64_t* plane, const uint8_t* base_planes, const uint8_t* ins_planes, uint64_t plane_bytes,
                              const ioc_pile_site* sites, const int64_t* site_off, const int64_t* allele_off, uint8_t* alleles,
                              uint64_t alleles_cap);
+
+// ioc_plane_pile.hip: what the same strings insert, into six byte planes of the pairs' own (ioc_host_ops_project_ins) — slot j of
+// pair pid from slot_planes + j * plane_bytes + plane[pid] on (set to 0 by the caller); launched beside iock_ops_project
+hipError_t iock_ops_project_ins(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room,
+                                const uint32_t* ord, uint32_t cnt, const int64_t* row_base, const uint32_t* q_off, const uint64_t* plane,
+                                const uint8_t* pool, uint64_t pool_bytes, uint8_t* slot_planes, uint64_t plane_bytes);
+// ... and the tables of the two groups of every segment added up from the planes (ioc_host_planes_pile per member): everything is
+// a device pointer; group-segment 2 g + h takes the pairs members[mem_off[g] .. mem_off[g + 1]) whose group byte is h
+struct IocPlaneWork;  // (ioc_plane_pile.h: 64 rows of a group-segment)
+hipError_t iock_plane_pile(hipStream_t st, const IocPlaneWork* work, uint32_t n_work, const IocPileSeg* gsegs, const uint32_t* mem_off,
+                           const uint32_t* members, uint32_t n_pairs, const uint8_t* group, const uint64_t* plane, const uint8_t* base_planes,
+                           const uint8_t* slot_planes, uint64_t plane_bytes, ioc_pileup_col* gcols, ioc_pileup_ins* gins, uint64_t n_rows);
 
 // ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
 // is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in

@@ -3,7 +3,8 @@
 //  * AlnSink::subset / take_back, which decide what a re-run (every tile, version 1) sees of the caller's pairs and what it leaves
 //    them: for every sink kind, idx empty, one pair, all pairs, out of order — a pair piled before the re-run stays piled and its
 //    row_base reaches the re-run unchanged (ops_reserve turns it into -1 from `piled`), a pair the re-run leaves unanswered keeps
-//    len == 0 and piled == 0, the records of pairs outside idx are untouched, the bytes' regions are the caller's own;
+//    len == 0 and piled == 0, the records of pairs outside idx are untouched, the bytes' regions are the caller's own; a pile
+//    that projects (project, project_ins) hands the re-run its pairs' plane offsets, the planes' addresses and both flags;
 //  * AlnSink::answer_empty, the closed forms of a pair with an empty sequence, for every kind and both empty sides;
 //  * ops_layout, the per-slice table's offsets: those the kernels' launchers have always been handed, for np in {0, 1, 3, 5, 1000};
 //  * aln_route and the accepted parameter range, at their edges and with the extreme values an int32 argument can carry (no
@@ -41,6 +42,7 @@ struct Kind {
     SinkKind kind;
     bool stats;
     PileKind pile;
+    int project = 0;  // 1: the pile projects (two planes); 2: and what the pairs insert (project_ins: six more)
 };
 const Kind KINDS[] = {{"bytes", SinkKind::bytes, false, PileKind::none},
                       {"stats", SinkKind::reduced, true, PileKind::none},
@@ -49,7 +51,11 @@ const Kind KINDS[] = {{"bytes", SinkKind::bytes, false, PileKind::none},
                       {"ins", SinkKind::reduced, false, PileKind::ins},
                       {"ins+stats", SinkKind::reduced, true, PileKind::ins},
                       {"weighted", SinkKind::reduced, false, PileKind::weighted},
-                      {"weighted+stats", SinkKind::reduced, true, PileKind::weighted}};
+                      {"weighted+stats", SinkKind::reduced, true, PileKind::weighted},
+                      {"counts+project", SinkKind::reduced, false, PileKind::counts, 1},
+                      {"counts+project+stats", SinkKind::reduced, true, PileKind::counts, 1},
+                      {"counts+project_ins", SinkKind::reduced, false, PileKind::counts, 2},
+                      {"counts+project_ins+stats", SinkKind::reduced, true, PileKind::counts, 2}};
 
 // the caller's arrays of a call over P pairs, of exactly the sizes an entry point gives them (a read or write outside them is the
 // sanitizer's to find); the device tables are never dereferenced by the host: distinct addresses do
@@ -57,7 +63,9 @@ struct Caller {
     static constexpr int P = 6;
     static constexpr int64_t ROOM = 10;  // bytes per pair's region
     std::vector<uint8_t> buf;
-    std::vector<int64_t> base, len, row_base;
+    std::vector<int64_t> base, len, row_base, plane;
+    static constexpr int64_t PLANE_BYTES = 1234;
+    uint8_t t_planes[8];  // (one byte per plane: only the addresses count)
     std::vector<ioc_aln_stats> stats;
     std::vector<uint8_t> piled;
     AlnTally tally;
@@ -92,6 +100,14 @@ struct Caller {
             sink.pile.rows = 700;
             sink.pile.row_base = row_base.data();
             sink.pile.piled = piled.data();
+        }
+        if (k.project) {
+            for (int i = 0; i < P; ++i) plane.push_back(200 * i + 3);
+            sink.pile.project = true;
+            sink.pile.base_planes = t_planes, sink.pile.ins_planes = t_planes + 1;
+            sink.pile.plane_bytes = PLANE_BYTES;
+            sink.pile.plane = plane.data();
+            if (k.project == 2) sink.pile.project_ins = true, sink.pile.slot_planes = t_planes + 2;
         }
     }
 };
@@ -131,6 +147,15 @@ void check_subset(const Kind& k, const std::vector<int32_t>& idx, const std::vec
             EXPECT(s.pile.row_base[x] == c.row_base[size_t(idx[x])]);  // (unchanged, piled or not)
             EXPECT(s.pile.piled[x] == piled_b[size_t(idx[x])]);
         }
+    }
+    EXPECT(s.projects() == (k.project != 0) && s.projects_ins() == (k.project == 2));
+    if (k.project) {
+        EXPECT(sub.plane.size() == idx.size() && s.pile.plane == sub.plane.data() && s.pile.plane_bytes == Caller::PLANE_BYTES);
+        EXPECT(s.pile.base_planes == c.sink.pile.base_planes && s.pile.ins_planes == c.sink.pile.ins_planes && s.pile.slot_planes == c.sink.pile.slot_planes);
+        EXPECT((s.pile.slot_planes != nullptr) == (k.project == 2));
+        for (size_t x = 0; x < idx.size(); ++x) EXPECT(s.pile.plane[x] == c.plane[size_t(idx[x])]);
+    } else {
+        EXPECT(sub.plane.empty());
     }
 
     // the re-run, as ops_fetch / ops_fetch_reduced write through the sink
@@ -195,10 +220,11 @@ void check_empty(const Kind& k)
 void check_layout(const Kind& k)
 {
     g_what = k.name;
-    const size_t per_pair = k.kind == SinkKind::bytes ? 12 : k.pile == PileKind::weighted ? 32 : k.pile != PileKind::none ? 28 : 16;
+    // (project_ins adds no column: the slot planes sit at the pair's `plane` offset like the two)
+    const size_t per_pair = k.kind == SinkKind::bytes ? 12 : k.project ? 40 : k.pile == PileKind::weighted ? 32 : k.pile != PileKind::none ? 28 : 16;
     for (size_t np : {size_t(0), size_t(1), size_t(3), size_t(5), size_t(1000)}) {
         Caller c(k);
-        const OpsLayout a = ops_layout(np, k.kind, k.pile), b = c.sink.layout(np);
+        const OpsLayout a = ops_layout(np, k.kind, k.pile, k.project != 0), b = c.sink.layout(np);
         EXPECT(memcmp(&a, &b, sizeof a) == 0);
         EXPECT(a.end == 0 && a.len == 8 * np && a.room == 12 * np && a.row_base == 16 * np && a.q_off == 24 * np && a.q_len == 28 * np);
         EXPECT(a.bytes == ((np * per_pair + 15) / 16) * 16 && a.bytes % 16 == 0 && a.bytes >= np * per_pair && a.bytes < np * per_pair + 16);
@@ -208,6 +234,7 @@ void check_layout(const Kind& k)
         if (k.kind == SinkKind::reduced) EXPECT(a.room + 4 * np <= a.bytes);
         if (k.pile != PileKind::none) EXPECT(a.q_off + 4 * np <= a.bytes);
         if (k.pile == PileKind::weighted) EXPECT(a.q_len + 4 * np <= a.bytes);
+        if (k.project) EXPECT(a.plane == 32 * np && a.plane % 8 == 0 && a.plane + 8 * np <= a.bytes);
     }
 }
 
@@ -245,7 +272,9 @@ int main()
                                  : k.pile == PileKind::counts ? sizeof(ioc_pileup_col)
                                  : k.pile == PileKind::ins    ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins)
                                                               : 2 * sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins);
-        EXPECT(c.sink.pile_bytes() == 700 * per_row);
+        // the planes: a byte per row and pair each, two of them, and six more with project_ins
+        const uint64_t planes = k.project == 2 ? 2 + IOC_PILE_INS_SLOTS : k.project == 1 ? 2 : 0;
+        EXPECT(c.sink.pile_bytes() == 700 * per_row + planes * uint64_t(Caller::PLANE_BYTES));
         EXPECT(c.sink.reduced() == (k.kind == SinkKind::reduced) && c.sink.has_stats() == k.stats && c.sink.has_pile() == (k.pile != PileKind::none));
         check_subset(k, {}, {}, {});
         check_subset(k, {}, {}, {1, 4});
