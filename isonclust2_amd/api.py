@@ -627,10 +627,10 @@ class Context:
         pileup_call_weighted (the function) defines it.  Returns what pileup_call returns."""
         return self._pileup_call(True, frames, cols, wcols, wins, min_depth, cap)
 
-    def _align_pairs_polish(self, weighted, pairs, k, segs, seg_of_pair, min_depth, stats, tables, cap, match, mismatch, gap_extend):
-        """align_pairs_polish, and align_pairs_polish_weighted with its third table"""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
+    def _seg_args(self, n, segs, seg_of_pair):
+        """The segment arguments of a call over the pool: (PolishSeg array, seg_of_pair as int32, the segments' lengths, the rows
+        of a table of theirs) — the lengths all 0 where a segment lies outside the pool (the library refuses the call then)."""
+        ns = len(segs)
         sarr = (_lib.PolishSeg * max(ns, 1))()
         for g, (ref, rc) in enumerate(segs):
             sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
@@ -640,7 +640,29 @@ class Context:
         offs = self.align_pool_offsets()
         ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
         rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
-        n_rows = sum(rlen) + ns
+        return sarr, sop, rlen, sum(rlen) + ns
+
+    @staticmethod
+    def _site_outs(n, rlen, sop, max_sites, alleles=True):
+        """The outputs of a site search over segments of lengths rlen and the alleles of n pairs, with their caps:
+        (sites, s_cap, s_off, found, alleles or None, a_cap, a_off)."""
+        ns = len(rlen)
+        per_seg = [pileup_sites_bound(r, max(int(max_sites), 1)) for r in rlen]
+        s_cap = sum(per_seg)
+        a_cap = sum(per_seg[g] for g in sop if 0 <= g < ns)
+        return (np.zeros(max(s_cap, 1), PILE_SITE_DTYPE), s_cap, np.zeros(ns + 1, np.int64), np.zeros(max(ns, 1), np.int64),
+                np.zeros(max(a_cap, 1), np.uint8) if alleles else None, a_cap, np.zeros(n + 1, np.int64))
+
+    @staticmethod
+    def _row0(rlen):
+        """the first row of every segment of a table"""
+        return np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:len(rlen)]
+
+    def _align_pairs_polish(self, weighted, pairs, k, segs, seg_of_pair, min_depth, stats, tables, cap, match, mismatch, gap_extend):
+        """align_pairs_polish, and align_pairs_polish_weighted with its third table"""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
         bound = sum(pileup_call_bound(r) for r in rlen)
         cap = bound if cap is None else int(cap)
         (score, win, ratio), ptrs = self._aln_out(n)
@@ -660,7 +682,7 @@ class Context:
             out["stats"] = st
         if tables:
             out.update(zip(names, tabs))
-            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
+            out["row0"] = self._row0(rlen)
         return out
 
     def align_pairs_polish(self, pairs, k, segs, seg_of_pair, min_depth=3, stats=False, tables=False, cap=None, match=2, mismatch=-2,
@@ -705,38 +727,8 @@ class Context:
         uint8 arrays per pair: one byte per kept site of its segment — the channel 0 .. 4, ALLELE_DEL or ALLELE_NONE at a base site,
         0 / 1 or ALLELE_NONE at an insertion site), with stats=True `stats` (ALN_STATS_DTYPE per pair), with tables=True `cols`
         (the table of counts) and `row0` (the first row per segment)."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr = (_lib.PolishSeg * max(ns, 1))()
-        for g, (ref, rc) in enumerate(segs):
-            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
-        sop = np.ascontiguousarray(seg_of_pair, np.int32)
-        if sop.shape != (n,):
-            raise ValueError("seg_of_pair must hold one entry per pair")
-        offs = self.align_pool_offsets()
-        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
-        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
-        n_rows = sum(rlen) + ns
-        per_seg = [pileup_sites_bound(r, max(int(max_sites), 1)) for r in rlen]
-        s_cap = sum(per_seg)
-        a_cap = sum(per_seg[g] for g in sop if 0 <= g < ns)
-        (score, win, ratio), ptrs = self._aln_out(n)
-        sites, s_off, found = np.zeros(max(s_cap, 1), PILE_SITE_DTYPE), np.zeros(ns + 1, np.int64), np.zeros(max(ns, 1), np.int64)
-        alleles, a_off = np.zeros(max(a_cap, 1), np.uint8), np.zeros(n + 1, np.int64)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        self._chk(self.L.ioc_align_pairs_alleles(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns,
-                                                 sarr, _p(sop, C.c_int32), int(min_depth), int(min_alt), int(min_pct), int(max_sites),
-                                                 sites.ctypes.data, s_cap, _p(s_off, C.c_int64), _p(found, C.c_int64), alleles.ctypes.data, a_cap,
-                                                 _p(a_off, C.c_int64), cols.ctypes.data if tables and n_rows else None))
-        out = {"score": score, "windows": win, "ratio": ratio, "sites": [sites[s_off[g]:s_off[g + 1]].copy() for g in range(ns)],
-               "n_found": found[:ns], "alleles": [alleles[a_off[i]:a_off[i + 1]].copy() for i in range(n)]}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out["cols"] = cols
-            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
-        return out
+        return self._align_pairs_split(None, pairs, k, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, None, None, None, stats, tables, True,
+                                       match, mismatch, gap_extend, split=False)
 
     @staticmethod
     def _split_out(s_off, a_off_unused, sop, ns, n, link, phase, group, vote, seg):
@@ -831,37 +823,28 @@ class Context:
                                        min_margin, rounds, stats, tables, alleles, match, mismatch, gap_extend)
 
     def _align_pairs_split(self, polish, pairs, k, segs, seg_of_pair, min_depth, min_alt, min_pct, max_sites, min_link, min_margin, rounds, stats,
-                           tables, alleles, match, mismatch, gap_extend):
-        """align_pairs_split, and align_pairs_split_polish with polish = (polish_min_depth, cap)"""
+                           tables, alleles, match, mismatch, gap_extend, split=True):
+        """align_pairs_split, align_pairs_split_polish with polish = (polish_min_depth, cap), and align_pairs_alleles with split=False"""
         n, ns = len(pairs), len(segs)
         arr = self._aln_pairs(pairs)
-        sarr = (_lib.PolishSeg * max(ns, 1))()
-        for g, (ref, rc) in enumerate(segs):
-            sarr[g].ref, sarr[g].ref_revcomp = int(ref), int(bool(rc))
-        sop = np.ascontiguousarray(seg_of_pair, np.int32)
-        if sop.shape != (n,):
-            raise ValueError("seg_of_pair must hold one entry per pair")
-        offs = self.align_pool_offsets()
-        ok = all(0 <= int(ref) < len(offs) - 1 for ref, _ in segs)
-        rlen = [int(offs[int(ref) + 1] - offs[int(ref)]) if ok else 0 for ref, _ in segs]
-        n_rows = sum(rlen) + ns
-        per_seg = [pileup_sites_bound(r, max(int(max_sites), 1)) for r in rlen]
-        s_cap = sum(per_seg)
-        a_cap = sum(per_seg[g] for g in sop if 0 <= g < ns)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        sites, s_cap, s_off, found, alle, a_cap, a_off = self._site_outs(n, rlen, sop, max_sites, alleles)
         (score, win, ratio), ptrs = self._aln_out(n)
-        sites, s_off, found = np.zeros(max(s_cap, 1), PILE_SITE_DTYPE), np.zeros(ns + 1, np.int64), np.zeros(max(ns, 1), np.int64)
-        alle, a_off = (np.zeros(max(a_cap, 1), np.uint8) if alleles else None), np.zeros(n + 1, np.int64)
         st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
         cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        link, phase = np.zeros(max(s_cap, 1), np.int64), np.zeros(max(s_cap, 1), np.int8)
-        group, vote, seg = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(ns, 1), SPLIT_SEG_DTYPE)
         args = (self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr, _p(sop, C.c_int32),
                 int(min_depth), int(min_alt), int(min_pct), int(max_sites), sites.ctypes.data, s_cap, _p(s_off, C.c_int64), _p(found, C.c_int64),
-                alle.ctypes.data if alleles else None, a_cap if alleles else 0, _p(a_off, C.c_int64), cols.ctypes.data if tables and n_rows else None,
-                int(min_link), int(min_margin), int(rounds), link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data)
-        if polish is None:
-            self._chk(self.L.ioc_align_pairs_split(*args))
+                alle.ctypes.data if alleles else None, a_cap if alleles else 0, _p(a_off, C.c_int64), cols.ctypes.data if tables and n_rows else None)
+        out = {"score": score, "windows": win, "ratio": ratio}
+        if not split:
+            self._chk(self.L.ioc_align_pairs_alleles(*args))
         else:
+            link, phase = np.zeros(max(s_cap, 1), np.int64), np.zeros(max(s_cap, 1), np.int8)
+            group, vote, seg = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(ns, 1), SPLIT_SEG_DTYPE)
+            args += (int(min_link), int(min_margin), int(rounds), link.ctypes.data, phase.ctypes.data, group.ctypes.data, vote.ctypes.data, seg.ctypes.data)
+        if split and polish is None:
+            self._chk(self.L.ioc_align_pairs_split(*args))
+        elif split:
             bound = 2 * sum(pileup_call_bound(r) for r in rlen)
             g_cap = bound if polish[1] is None else int(polish[1])
             g_seq, g_qual = np.zeros(max(g_cap, 1), np.uint8), np.zeros(max(g_cap, 1), np.uint8)
@@ -870,9 +853,9 @@ class Context:
             self._chk(self.L.ioc_align_pairs_split_polish(*args, polish[0], g_seq.ctypes.data, g_qual.ctypes.data, g_cap, _p(g_off, C.c_int64),
                                                           g_pol.ctypes.data if ns else None, gcols.ctypes.data if tables and n_rows else None,
                                                           gins.ctypes.data if tables and n_rows else None))
-        out = {"score": score, "windows": win, "ratio": ratio, "sites": [sites[s_off[g]:s_off[g + 1]].copy() for g in range(ns)],
-               "n_found": found[:ns]}
-        out.update(self._split_out(s_off, a_off, sop, ns, n, link, phase, group, vote, seg))
+        out.update(sites=[sites[s_off[g]:s_off[g + 1]].copy() for g in range(ns)], n_found=found[:ns])
+        if split:
+            out.update(self._split_out(s_off, a_off, sop, ns, n, link, phase, group, vote, seg))
         if polish is not None:
             out.update(self._gpolish_out(ns, rlen, g_seq, g_qual, g_off, g_pol, gcols, gins, tables))
         if alleles:
@@ -881,7 +864,7 @@ class Context:
             out["stats"] = st
         if tables:
             out["cols"] = cols
-            out["row0"] = np.concatenate([[0], np.cumsum(np.array(rlen, np.int64) + 1)])[:ns]
+            out["row0"] = self._row0(rlen)
         return out
 
     # ---- sort-stage feeders --------------------------------------------------------------------

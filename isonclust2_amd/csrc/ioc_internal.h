@@ -18,6 +18,7 @@
 #include <utility>
 #include <vector>
 
+#include "ioc_sink_plan.h"
 #include "isonclust2_hip.h"
 
 // A block of device memory and its owner: freed when the DevBuf goes (a member of a context with the context, a local at the end
@@ -367,12 +368,8 @@ hipError_t iock_ops_pileup_weighted(hipStream_t st, const uint8_t* buf, const ui
                                     const uint8_t* pool, const uint8_t* quals, uint64_t pool_bytes, ioc_pileup_col* cols,
                                     ioc_pileup_col* wcols, ioc_pileup_ins* wins, uint64_t n_rows);
 
-// ioc_pile_call.hip: the consensus call (ioc_host_pileup_call) of many references from device tables.  A segment: rlen + 1 rows
-// of both tables from row0 on, its frame rlen bytes at f_off of a pool of sequences, read reverse-complemented where rc is set.
-struct IocPileSeg {
-    int64_t row0, f_off;
-    int32_t rlen, rc;
-};
+// ioc_pile_call.hip: the consensus call (ioc_host_pileup_call) of many references from device tables (a segment: IocPileSeg,
+// ioc_sink_plan.h)
 hipError_t iock_pile_call(hipStream_t st, const IocPileSeg* segs, uint32_t n_segs, const ioc_pileup_col* cols, const ioc_pileup_ins* ins,
                           uint64_t n_rows, const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth, int64_t* seg_len,
                           ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);

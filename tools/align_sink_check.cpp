@@ -1,4 +1,5 @@
-// align_sink_check.cpp — the host side of the aligner's sink description (isonclust2_amd/csrc/ioc_align_sink.h), driven on the CPU:
+// align_sink_check.cpp — the host side of the aligner's sink description (isonclust2_amd/csrc/ioc_align_sink.h) and what the sink
+// entry points plan before they launch anything (ioc_sink_plan.h), driven on the CPU:
 //
 //  * AlnSink::subset / take_back, which decide what a re-run (every tile, version 1) sees of the caller's pairs and what it leaves
 //    them: for every sink kind, idx empty, one pair, all pairs, out of order — a pair piled before the re-run stays piled and its
@@ -8,7 +9,12 @@
 //  * AlnSink::answer_empty, the closed forms of a pair with an empty sequence, for every kind and both empty sides;
 //  * ops_layout, the per-slice table's offsets: those the kernels' launchers have always been handed, for np in {0, 1, 3, 5, 1000};
 //  * aln_route and the accepted parameter range, at their edges and with the extreme values an int32 argument can carry (no
-//    overflow on the way: the sums are 64-bit).
+//    overflow on the way: the sums are 64-bit);
+//  * ioc_sink_plan.h, each planner against a plain restatement written here: the arena layout (block sizes 0, 1, 15, 16, 17; the
+//    totals of one case per stage against the hand-chained sums the stages used to carry), member_lists (no segments, no pairs,
+//    segments without pairs, pairs out of segment order, one segment for all), the split's tables (0, 1, 64, 65 and 128 members,
+//    a segment without sites between two with), the bounds at their edges, and both constructors of SinkPlan with every refusal's
+//    status and message as the entry points have always worded them.
 //
 // Host code only (the header includes no HIP header); meant for the sanitizers:
 //
@@ -19,9 +25,11 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ioc_align_sink.h"
+#include "ioc_sink_plan.h"
 
 namespace {
 
@@ -260,11 +268,223 @@ void check_routes()
     EXPECT(aln_span_ok(1 << 20, -2, 0, 500, 523) && !aln_span_ok(1 << 20, -2, 0, 500, 524));  // (2^20 + 5) x 1023 <= 2^30 < ... x 1024
 }
 
+
+// ---- ioc_sink_plan.h ----
+size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
+void check_arena()
+{
+    g_what = "arena";
+    Arena a;
+    size_t want = 0;
+    for (size_t b : {size_t(0), size_t(1), size_t(15), size_t(16), size_t(17), size_t(0), size_t(0), size_t(33)}) {
+        EXPECT(a.take(b) == want && want % 16 == 0);  // (a block of 0 bytes: the next one starts where it does)
+        want += b == 0 ? 0 : b <= 16 ? 16 : b <= 32 ? 32 : 48;
+        EXPECT(a.size() == want);
+    }
+    // one case per stage: the blocks in the stage's order against the sums that were chained by hand
+    const size_t n = 3, np = 5, bound = 7, ab = 11, seg = sizeof(IocPileSeg), site = sizeof(ioc_pile_site), st = sizeof(ioc_polish_stats);
+    {  // the site search and the allele gather (a_call)
+        const size_t o_len = up16(n * seg), o_off = o_len + up16(n * 8), o_found = o_off + up16((n + 1) * 8), o_sites = o_found + up16(n * 8),
+                     o_sop = o_sites + up16(bound * site), o_plane = o_sop + up16(np * 4), o_aoff = o_plane + up16(np * 8), o_all = o_aoff + up16((np + 1) * 8),
+                     total = o_all + up16(ab);
+        Arena l;
+        EXPECT(l.take(n * seg) == 0 && l.take(n * 8) == o_len && l.take((n + 1) * 8) == o_off && l.take(n * 8) == o_found && l.take(bound * site) == o_sites);
+        EXPECT(l.take(np * 4) == o_sop && l.take(np * 8) == o_plane && l.take((np + 1) * 8) == o_aoff && l.take(ab) == o_all && l.size() == total);
+    }
+    {  // the call (a_call): the records are 32 bytes, so the block behind them starts where the unrounded sum put it
+        const size_t o_len = up16(n * seg), o_off = o_len + up16(n * 8), o_st = o_off + up16((n + 1) * 8), o_seq = o_st + n * st, o_qual = o_seq + up16(bound),
+                     total = o_qual + up16(bound);
+        Arena l;
+        EXPECT(st % 16 == 0 && l.take(n * seg) == 0 && l.take(n * 8) == o_len && l.take((n + 1) * 8) == o_off && l.take(n * st) == o_st);
+        EXPECT(l.take(bound) == o_seq && l.take(bound) == o_qual && l.size() == total);
+    }
+    for (int on_device = 0; on_device < 2; ++on_device) {  // the split (a_split) and the group pile (a_gpile): blocks that are 0 bytes where nothing is uploaded
+        const size_t S = 9, T = 4, P = 13, bytes = 21, rows = 17, work = 6;
+        const size_t split[] = {(n + 1) * 8, (np + 1) * 8, np * 4, (n + 1) * 4, np * 4, (n + 1) * 4, (n + 1) * 8, T * 4, S * 4, S * 8, P * 8, P * 8, T * 8, T * 8, S * 8,
+                                S, n * 4, np, np * 4, n * sizeof(ioc_split_seg), on_device ? 0 : S * site, on_device ? 0 : bytes};
+        const size_t gpile[] = {2 * n * seg, work * 8, np * 8, on_device ? 0 : (n + 1) * 4, on_device ? 0 : np * 4, on_device ? 0 : np, on_device ? 0 : P,
+                                on_device ? 0 : 6 * P, rows * sizeof(ioc_pileup_col), rows * sizeof(ioc_pileup_ins)};
+        Arena l, g;
+        size_t at = 0;
+        for (size_t b : split) {
+            EXPECT(l.take(b) == at);
+            at += up16(b);
+        }
+        EXPECT(l.size() == at);
+        at = 0;
+        for (size_t b : gpile) {
+            EXPECT(g.take(b) == at);
+            at += up16(b);
+        }
+        EXPECT(g.size() == at);
+    }
+}
+
+void check_member_lists()
+{
+    g_what = "member_lists";
+    const struct { size_t n; std::vector<int32_t> sop; } cases[] = {
+        {0, {}}, {3, {}}, {4, {1, 1, 3}} /* none at the front, in the middle */, {4, {0, 2, 0}} /* ... at the end */, {3, {2, 0, 1, 0, 2, 2, 1}} /* out of order */,
+        {3, {1, 1, 1, 1}} /* all in one */, {1, {0}}};
+    for (const auto& k : cases) {
+        const MemberLists m = member_lists(k.n, k.sop.size(), k.sop.data());
+        std::vector<uint32_t> off{0}, mem;
+        for (size_t g = 0; g < k.n; ++g) {
+            for (size_t i = 0; i < k.sop.size(); ++i)
+                if (size_t(k.sop[i]) == g) mem.push_back(uint32_t(i));
+            off.push_back(uint32_t(mem.size()));
+        }
+        EXPECT(m.mem_off == off && m.members == mem);
+    }
+}
+
+void check_split_tables()
+{
+    g_what = "split_tables";
+    static_assert(std::is_same<decltype(SplitTables::bit_off), std::vector<int64_t>>::value, "words x sites are summed in 64 bits");
+    const std::vector<uint32_t> members{0, 1, 64, 65, 128, 3};
+    const std::vector<int64_t> sites{3, 2, 0, 5, 1, 4};  // (a segment without sites between two with)
+    for (size_t n = 0; n <= members.size(); ++n) {
+        std::vector<uint32_t> mem_off{0};
+        std::vector<int64_t> site_off{0};
+        for (size_t g = 0; g < n; ++g) mem_off.push_back(mem_off[g] + members[g]), site_off.push_back(site_off[g] + sites[g]);
+        const SplitTables s = split_tables(n, site_off.data(), mem_off);
+        std::vector<uint32_t> word_off{0};
+        std::vector<int64_t> bit_off{0};
+        std::vector<int32_t> tile_seg, seg_of_site;
+        size_t most = 0;
+        for (size_t g = 0; g < n; ++g) {
+            uint32_t words = 0;
+            while (64 * words < members[g]) ++words;
+            word_off.push_back(word_off[g] + words), bit_off.push_back(bit_off[g] + int64_t(words) * sites[g]);
+            tile_seg.insert(tile_seg.end(), words, int32_t(g)), seg_of_site.insert(seg_of_site.end(), size_t(sites[g]), int32_t(g));
+            most = sites[g] > int64_t(most) ? size_t(sites[g]) : most;
+        }
+        EXPECT(s.word_off == word_off && s.bit_off == bit_off && s.tile_seg == tile_seg && s.seg_of_site == seg_of_site);
+        EXPECT(s.T == word_off[n] && s.P == size_t(bit_off[n]) && s.most == most);
+    }
+    const std::vector<uint32_t> words_of{0, 1, 1, 2, 2};  // 0, 1, 64 | 65, 128 members: a word boundary either side
+    for (size_t g = 0; g < 5; ++g) EXPECT(split_tables(1, std::vector<int64_t>{0, 1}.data(), {0, members[g]}).T == words_of[g]);
+}
+
+void check_bounds()
+{
+    g_what = "bounds";
+    const int32_t rlen = 5;
+    const std::vector<IocPileSeg> one{{0, 0, rlen, 0}}, two{{0, 0, 0, 0}, {1, 0, 1, 0}};
+    EXPECT(pile_sites_bound(one, 1) == 1 && pile_sites_bound(one, 2 * rlen) == 2 * rlen && pile_sites_bound(one, 2 * rlen + 1) == 2 * rlen + 1 &&
+           pile_sites_bound(one, 2 * rlen + 2) == 2 * rlen + 1);
+    EXPECT(pile_call_most(0) == IOC_PILE_INS_SLOTS && pile_call_most(1) == 1 + 2 * IOC_PILE_INS_SLOTS && pile_call_bound(two) == 1 + 3 * IOC_PILE_INS_SLOTS);
+    EXPECT(pile_call_bound({}) == 0 && pile_sites_bound({}, 7) == 0 && pile_sites_bound(two, 2) == 1 + 2 && pile_sites_bound(two, INT32_MAX) == 1 + 3);
+}
+
+// a constructor's verdict: the status, and the message where it refuses
+#define REFUSED(call, st, text)                        \
+    do {                                               \
+        SinkPlan p_;                                   \
+        EXPECT(p_.call == (st) && p_.msg == (text));   \
+    } while (0)
+
+void check_plan_rlen()
+{
+    g_what = "plan from rlen";
+    const char frames[16] = {};
+    {  // lengths 0 among the others; frames that overlap: frame_bytes is the largest end, not the sum
+        const int32_t rlen[] = {5, 0, 3};
+        const int64_t f_off[] = {10, 2, 0};
+        const int32_t sop[] = {2, 0, 2, 1};
+        const uint8_t group[] = {0, 1, IOC_SPLIT_NONE, 1};
+        SinkPlan p;
+        EXPECT(p.from_rlen("ioc_planes_polish", 3, rlen, frames, f_off, 4, sop, group, 0) == IOC_OK && p.msg.empty());
+        EXPECT(p.n_rows == 6 + 1 + 4 && p.frame_bytes == 15 && p.plane_bytes == 4 + 6 + 4 + 1 && p.alleles_bound == 0);
+        const int64_t row0[] = {0, 6, 7}, plane[] = {0, 4, 10, 14};
+        for (int g = 0; g < 3; ++g) EXPECT(p.segs[g].row0 == row0[g] && p.segs[g].f_off == f_off[g] && p.segs[g].rlen == rlen[g] && p.segs[g].rc == 0);
+        for (int i = 0; i < 4; ++i) EXPECT(p.row_base[i] == row0[sop[i]] && p.plane[i] == plane[i]);
+        REFUSED(from_rlen("ioc_planes_polish", 3, rlen, frames, f_off, 4, std::vector<int32_t>{2, -1, 2, 1}.data(), group, 0), IOC_ERR_ARG, "ioc_planes_polish: pair 1 names no segment");
+        REFUSED(from_rlen("ioc_planes_polish", 3, rlen, frames, f_off, 4, std::vector<int32_t>{2, 0, 2, 3}.data(), group, 0), IOC_ERR_ARG, "ioc_planes_polish: pair 3 names no segment");
+        REFUSED(from_rlen("ioc_planes_polish", 3, rlen, frames, f_off, 4, sop, std::vector<uint8_t>{0, 1, 2, 1}.data(), 0), IOC_ERR_ARG,
+                "ioc_planes_polish: the group byte of pair 2 is neither 0, 1 nor IOC_SPLIT_NONE");
+        SinkPlan q;  // (no group bytes: not looked at; no frame offsets: a site search, f_off 0)
+        EXPECT(q.from_rlen("ioc_pileup_sites", 3, rlen, nullptr, nullptr, 0, nullptr, nullptr, PLAN_REFUSE_LONG) == IOC_OK && q.frame_bytes == 0 && q.n_rows == 11 && q.segs[2].f_off == 0);
+    }
+    const int32_t zeros[] = {0, 0}, mixed[] = {0, 2}, neg[] = {1, -1};
+    const int64_t f0[] = {0, 0}, fneg[] = {0, -1};
+    SinkPlan p;
+    EXPECT(p.from_rlen("ioc_pileup_call", 2, zeros, nullptr, f0, 0, nullptr, nullptr, PLAN_REFUSE_CALLED) == IOC_OK && p.n_rows == 2 && p.frame_bytes == 0);
+    for (const char* who : {"ioc_pileup_call", "ioc_planes_polish"}) {
+        const std::string w = who;
+        REFUSED(from_rlen(w, 2, mixed, nullptr, f0, 0, nullptr, nullptr, 0), IOC_ERR_ARG, w + ": segment 1 has a negative length or frame offset");
+        REFUSED(from_rlen(w, 2, neg, frames, f0, 0, nullptr, nullptr, 0), IOC_ERR_ARG, w + ": segment 1 has a negative length or frame offset");
+        REFUSED(from_rlen(w, 2, zeros, frames, fneg, 0, nullptr, nullptr, 0), IOC_ERR_ARG, w + ": segment 1 has a negative length or frame offset");
+    }
+    REFUSED(from_rlen("ioc_pileup_sites", 2, neg, nullptr, nullptr, 0, nullptr, nullptr, PLAN_REFUSE_LONG), IOC_ERR_ARG, "ioc_pileup_sites: segment 1 has a negative length");
+    // 7 rlen + 6 > 2^31 - 1 first at rlen 306783378; a site search's 2^30
+    const int32_t most[] = {306783377}, over[] = {3, 306783378}, l30[] = {1 << 30}, l30p[] = {(1 << 30) + 1};
+    SinkPlan a, b, d;
+    EXPECT(a.from_rlen("ioc_pileup_call", 1, most, frames, f0, 0, nullptr, nullptr, PLAN_REFUSE_CALLED) == IOC_OK && pile_call_bound(a.segs) == INT32_MAX - 2);
+    REFUSED(from_rlen("ioc_pileup_call", 2, over, frames, f0, 0, nullptr, nullptr, PLAN_REFUSE_CALLED), IOC_ERR_CAPACITY, "ioc_pileup_call: segment 1 may call more than 2^31 - 1 bytes");
+    EXPECT(b.from_rlen("ioc_planes_polish", 2, over, frames, f0, 0, nullptr, nullptr, 0) == IOC_OK);  // (that entry point asks later, once its pairs are known)
+    EXPECT(d.from_rlen("ioc_pileup_sites", 1, l30, nullptr, nullptr, 0, nullptr, nullptr, PLAN_REFUSE_LONG) == IOC_OK && d.n_rows == (int64_t(1) << 30) + 1);
+    REFUSED(from_rlen("ioc_pileup_sites", 1, l30p, nullptr, nullptr, 0, nullptr, nullptr, PLAN_REFUSE_LONG), IOC_ERR_CAPACITY, "ioc_pileup_sites: segment 0 is longer than 2^30 bases");
+}
+
+void check_plan_pool()
+{
+    g_what = "plan from the pool";
+    const std::vector<int64_t> offs{0, 4, 4, 9, 14};  // four sequences: 4, 0, 5 and 5 bases
+    const int32_t n_seqs = 4, max_sites = 9;
+    const ioc_polish_seg segs[] = {{2, 0}, {1, 1}, {0, 0}};  // (an empty sequence as a segment)
+    const ioc_aln_pair pairs[] = {{0, 3, 0, 0, 0.0}, {1, 0, 0, 0, 0.0}, {3, 2, 1, 0, 0.0}, {0, 1, 0, 0, 0.0}};  // references of 5, 4, 5 and 0 bases
+    const int32_t sop[] = {0, 2, 0, 1};
+    for (const char* who : {"ioc_align_pairs_polish", "ioc_align_pairs_alleles", "ioc_align_pairs_split", "ioc_align_pairs_split_polish"}) {
+        const std::string w = who;
+        const unsigned flags = w == "ioc_align_pairs_polish" ? 0 : PLAN_REFUSE_LONG;
+        SinkPlan p;
+        EXPECT(p.from_pool(w, offs, 3, segs, 4, pairs, sop, max_sites, flags) == IOC_OK && p.msg.empty());
+        EXPECT(p.n_rows == 6 + 1 + 5 && p.plane_bytes == 6 + 5 + 6 + 1 && p.frame_bytes == 0);
+        const int64_t row0[] = {0, 6, 7}, f_off[] = {4, 4, 0}, plane[] = {0, 6, 11, 17};
+        const int32_t rlen[] = {5, 0, 4}, rc[] = {0, 1, 0};
+        int64_t ab = 0;
+        for (int g = 0; g < 3; ++g) EXPECT(p.segs[g].row0 == row0[g] && p.segs[g].f_off == f_off[g] && p.segs[g].rlen == rlen[g] && p.segs[g].rc == rc[g]);
+        for (int i = 0; i < 4; ++i) {
+            EXPECT(p.row_base[i] == row0[sop[i]] && p.plane[i] == plane[i]);
+            ab += 2 * rlen[sop[i]] + 1 < max_sites ? 2 * rlen[sop[i]] + 1 : max_sites;
+        }
+        EXPECT(p.row_base[0] == p.row_base[2] && p.plane[2] == p.plane[0] + 6 + 5 && p.alleles_bound == ab && ab == 9 + 9 + 9 + 1);
+        for (int32_t bad : {-1, n_seqs}) {
+            const ioc_polish_seg sb[] = {{2, 0}, {bad, 0}, {0, 0}};
+            REFUSED(from_pool(w, offs, 3, sb, 4, pairs, sop, max_sites, flags), IOC_ERR_ARG, w + ": segment 1 refers to a sequence outside the pool");
+            const ioc_aln_pair pq[] = {{bad, 3, 0, 0, 0.0}}, pr[] = {{0, bad, 0, 0, 0.0}};
+            REFUSED(from_pool(w, offs, 3, segs, 1, pq, sop, max_sites, flags), IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
+            REFUSED(from_pool(w, offs, 3, segs, 1, pr, sop, max_sites, flags), IOC_ERR_ARG, "alignment pair refers to a sequence outside the pool");
+        }
+        for (int32_t bad : {-1, 3}) {
+            const int32_t sb[] = {0, 2, bad, 1};
+            REFUSED(from_pool(w, offs, 3, segs, 4, pairs, sb, max_sites, flags), IOC_ERR_ARG, w + ": pair 2 names no segment");
+        }
+        const int32_t off_by_one[] = {0, 0, 0, 1};  // pair 1's reference has 4 bases, segment 0's frame 5
+        REFUSED(from_pool(w, offs, 3, segs, 4, pairs, off_by_one, max_sites, flags), IOC_ERR_ARG, w + ": the reference of pair 1 is not as long as its segment's frame");
+        REFUSED(from_pool(w, {}, 1, segs, 0, nullptr, nullptr, max_sites, flags), IOC_ERR_ARG, w + ": segment 0 refers to a sequence outside the pool");
+        const std::vector<int64_t> long_pool{0, (int64_t(1) << 30) + 1};
+        const ioc_polish_seg s0[] = {{0, 0}};
+        SinkPlan q;
+        if (flags) REFUSED(from_pool(w, long_pool, 1, s0, 0, nullptr, nullptr, max_sites, flags), IOC_ERR_CAPACITY, w + ": segment 0 is longer than 2^30 bases");
+        else EXPECT(q.from_pool(w, long_pool, 1, s0, 0, nullptr, nullptr, 0, flags) == IOC_OK && q.n_rows == (int64_t(1) << 30) + 2);
+    }
+}
+
 }  // namespace
 
 int main()
 {
     check_routes();
+    check_arena();
+    check_member_lists();
+    check_split_tables();
+    check_bounds();
+    check_plan_rlen();
+    check_plan_pool();
     for (const Kind& k : KINDS) {
         Caller c(k);
         g_what = k.name;
@@ -291,6 +511,6 @@ int main()
         check_layout(k);
     }
     if (!g_ok) return 1;
-    printf("ok: %ld checks of subset / take_back, answer_empty, ops_layout over %zu sink kinds, and the routes\n", g_checks, sizeof KINDS / sizeof KINDS[0]);
+    printf("ok: %ld checks of subset / take_back, answer_empty, ops_layout over %zu sink kinds, the routes and the sink plans\n", g_checks, sizeof KINDS / sizeof KINDS[0]);
     return 0;
 }
