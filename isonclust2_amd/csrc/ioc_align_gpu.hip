@@ -974,7 +974,7 @@ struct WinStat {
         wb = uint32_t(__builtin_amdgcn_readlane(int(win), int(m - 1u)));
         pushed += m;
     }
-    __device__ void blanks(uint32_t g, uint32_t kmask, uint32_t k, int il)
+    __device__ __forceinline__ void blanks(uint32_t g, uint32_t kmask, uint32_t k, int il)
     {
         const uint32_t t = g < k ? g : k;
         for (uint32_t x = 0; x < t; ++x) push(0u, kmask, k, il);
@@ -1866,7 +1866,7 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
         for (uint32_t pid : ids)
             if (rec(pid, l ? 12 : 8)) in.push_back(pid);
         std::sort(in.begin(), in.end(), [&](uint32_t a, uint32_t b) { return cyc(a) > cyc(b); });
-        double tot[8] = {};
+        double tot[11] = {};
         for (uint32_t pid : in) {
             tot[0] += cyc(pid);
             for (uint32_t w = 0; w < 3u; ++w) tot[1 + w] += double(spl(pid, w)) * 256.0;
@@ -1874,18 +1874,22 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
             tot[5] += double(spl(pid, 4));
             tot[6] += double(spl(pid, 5));
             tot[7] += double(spl(pid, 6));
+            for (uint32_t w = 0; w < 3u; ++w) tot[8 + w] += double(spl(pid, 7 + w)) * 256.0;  // (own blocks: all, <= 64 columns, <= 64 rows)
         }
         const double nn = double(std::max<size_t>(1, in.size()));
         fprintf(stderr, "[ioc] split of %s: %zu walks; mean %.3e cycles: blocks %.1f %%, tile recomputation %.1f %%, walk loop %.1f %%; %.1f cycles per tile step; "
                         "blocks of <= 64 columns: %.2f per walk, %.1f %% of the block steps recomputed by walkers\n",
                 l ? "k_trace2_help" : "k_trace2", in.size(), tot[0] / nn, 100.0 * tot[1] / std::max(1.0, tot[0]), 100.0 * tot[2] / std::max(1.0, tot[0]),
                 100.0 * tot[3] / std::max(1.0, tot[0]), tot[2] / std::max(1.0, tot[7]), tot[4] / nn, 100.0 * tot[6] / std::max(1.0, tot[5]));
+        fprintf(stderr, "[ioc]   own blocks: %.1f %% of the blocks' cycles (the rest: waiting for a helper's); %.1f cycles per own block step in blocks of > 64 columns, %.1f in those of <= 64; "
+                        "blocks of <= 64 rows: %.1f %% of the own blocks' cycles\n",
+                100.0 * tot[8] / std::max(1.0, tot[1]), (tot[8] - tot[9]) / std::max(1.0, tot[5] - tot[6]), tot[9] / std::max(1.0, tot[6]), 100.0 * tot[10] / std::max(1.0, tot[8]));
         for (size_t x = 0; x < std::min<size_t>(in.size(), 10); ++x) {
             const uint32_t pid = in[x];
             const uint32_t nb = l ? rec(pid, 13) & 0xFFFFu : rec(pid, 9) & 0xFFFFu;
-            fprintf(stderr, "[ioc]   split pair %u: %.3e cycles: blocks %.3e, tiles %.3e, walk %.3e; blocks %u (<= 64 columns %u, <= 64 rows %u), own block steps %u (%u in thin), tiles %u, tile steps %u\n",
+            fprintf(stderr, "[ioc]   split pair %u: %.3e cycles: blocks %.3e, tiles %.3e, walk %.3e; blocks %u (<= 64 columns %u, <= 64 rows %u), own block steps %u (%u in thin), own block cycles %.3e (%.3e in <= 64 columns, %.3e in <= 64 rows), tiles %u, tile steps %u\n",
                     pid, cyc(pid), double(spl(pid, 0)) * 256.0, double(spl(pid, 1)) * 256.0, double(spl(pid, 2)) * 256.0, nb, spl(pid, 3) & 0xFFFFu, spl(pid, 3) >> 16,
-                    spl(pid, 4), spl(pid, 5), rec(pid, l ? 14 : 10), spl(pid, 6));
+                    spl(pid, 4), spl(pid, 5), double(spl(pid, 7)) * 256.0, double(spl(pid, 8)) * 256.0, double(spl(pid, 9)) * 256.0, rec(pid, l ? 14 : 10), spl(pid, 6));
         }
     }
     return IOC_OK;

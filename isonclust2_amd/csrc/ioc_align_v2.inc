@@ -785,7 +785,7 @@ constexpr uint32_t V2_RESUME_WORDS = 16;
 // ... and, in words of their own behind the lists of walks, where a walk's time went, per launch (IOC_V2_TRACE_TIMES): cycles / 256 for
 // its blocks (waiting or recomputing), its tiles' recomputation and its walk loop | blocks of <= 64 columns, << 16: of <= 64 rows |
 // systolic steps of the blocks it recomputed itself | ... of those of <= 64 columns | systolic steps of its tiles
-constexpr uint32_t V2_SPLIT_WORDS = 16;
+constexpr uint32_t V2_SPLIT_WORDS = 24;
 
 // After the probe launch (V2Couple): does either pair of the couple look like a wrong candidate?  Then the couple gets every tile.
 // And: at the score per row the probe saw, will the pairs beat the certificate of the corridor the host planned (half width B0)?
@@ -1028,6 +1028,7 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
     uint32_t n_blocks = 0, n_diag = 0, n_tiles = 0, n_gapsteps = 0;  // (IOC_V2_TRACE_TIMES: what this pair's walk was made of)
     // ... and where its time went: getting a block (waiting for a helper's, or recomputing it), recomputing tiles, walking them
     unsigned long long t_blk = 0, t_tile = 0, t_walk = 0;
+    unsigned long long t_own = 0, t_own_thin_c = 0, t_own_thin_r = 0;  // (of t_blk: recomputing blocks itself; in blocks of <= 64 columns / rows)
     uint32_t n_thin_c = 0, n_thin_r = 0, n_bsteps = 0, n_bsteps_thin = 0, n_tsteps = 0;  // (blocks of <= 64 columns / rows; systolic steps)
     uint32_t* const sp = split + size_t(pid) * V2_SPLIT_WORDS + (HELP ? V2_SPLIT_WORDS / 2u : 0u);
     auto split_out = [&]() {  // (lane 0, at the end of the walk in this launch)
@@ -1038,6 +1039,9 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
         sp[4] = n_bsteps;
         sp[5] = n_bsteps_thin;
         sp[6] = n_tsteps;
+        sp[7] = uint32_t(t_own >> 8);
+        sp[8] = uint32_t(t_own_thin_c >> 8);
+        sp[9] = uint32_t(t_own_thin_r >> 8);
     };
     const uint32_t n = pr.n, m = pr.m;
     const int go = pr.gap_open, il = pr.ilimit;
@@ -1094,18 +1098,11 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
         return int2{v2_half(d[y & 3u], hf) + bs, v2_half(d[4u + (y & 3u)], hf) + bs};
     };
 
-    // the fine checkpoints of the block (Rb, Cb) — rows Rb + 1 .. Rb + brows, columns Cb + 1 .. Cb + bcols — recomputed into dst
-    // from the coarse row above and the coarse column to the left (uses this wave's LDS: b_left, b_q, b_prof)
-    auto recompute_block_c = [&](auto cpl, const uint32_t Rb, const uint32_t Cb, const uint32_t brows, const uint32_t bcols, V2Scratch& dst) __attribute__((always_inline)) {
-        constexpr int BC = decltype(cpl)::value;  // columns per lane
-        // (an opaque copy: what a variant derives from the lane stays inside it.  Derived from `lane` itself it is hoisted out of the
-        // walk's loop for both variants at once — 144 registers in k_trace2_help instead of 111, and three helper waves and a
-        // first-launch wave no longer share a SIMD's 512)
-        const uint32_t ln = opaque(lane);
-        // Corridor: a block lies in ONE tile of the forward pass (bands are whole coarse rows, a strip is two coarse columns); what
-        // that tile took for "no score" because its neighbour above / to the left / above-left was not computed is "no score"
-        // here too (the checkpoints of a skipped tile were never written)
-        bool top_ok = true, left_ok = true, corner_ok = true;
+    // Corridor: a block lies in ONE tile of the forward pass (bands are whole coarse rows, a strip is two coarse columns); what
+    // that tile took for "no score" because its neighbour above / to the left / above-left was not computed is "no score"
+    // in the block too (the checkpoints of a skipped tile were never written)
+    auto block_edges = [&](const uint32_t Rb, const uint32_t Cb, bool& top_ok, bool& left_ok, bool& corner_ok) __attribute__((always_inline)) {
+        top_ok = left_ok = corner_ok = true;
         if (corridor) {
             const V2Couple& cq = couples[ck.couple];
             auto band_of = [&](uint32_t row) {
@@ -1121,6 +1118,20 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             if (Cb) left_ok = in(bb, pl);
             if (Rb && Cb) corner_ok = in(bt, pl);
         }
+    };
+
+    // the fine checkpoints of the block (Rb, Cb) — rows Rb + 1 .. Rb + brows, columns Cb + 1 .. Cb + bcols — recomputed into dst
+    // from the coarse row above and the coarse column to the left (uses this wave's LDS: b_left, b_q, b_prof)
+    auto recompute_block_c = [&](auto cpl, auto rps, const uint32_t Rb, const uint32_t Cb, const uint32_t brows, const uint32_t bcols, V2Scratch& dst) __attribute__((always_inline)) {
+        constexpr int BC = decltype(cpl)::value;  // columns per lane
+        constexpr int RS = decltype(rps)::value;  // rows per step
+        static_assert(RS == FW_R || RS == FW_R / 2, "a step's rows of the left column are one or two 16-byte LDS reads");
+        // (an opaque copy: what a variant derives from the lane stays inside it.  Derived from `lane` itself it is hoisted out of the
+        // walk's loop for both variants at once — 144 registers in k_trace2_help instead of 111, and three helper waves and a
+        // first-launch wave no longer share a SIMD's 512)
+        const uint32_t ln = opaque(lane);
+        bool top_ok, left_ok, corner_ok;
+        block_edges(Rb, Cb, top_ok, left_ok, corner_ok);
         // fine row 0 and fine column 0: the coarse checkpoints (or the matrix edges)
         for (uint32_t x = ln; x <= bcols; x += 64) {  // entry x = column Cb + x (x = 0: left of the block)
             int2 v;
@@ -1186,79 +1197,264 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             dgb = x0 <= bcols ? v2_ld(&dst.frow[0][x0]).x : 0;
         }
         const uint32_t nactb = (bcols + BC - 1) / BC;
-        const uint32_t nblkb = (brows + FW_R - 1) / FW_R, nstepb = nblkb + nactb - 1u;
-        int hl4[FW_R], el4[FW_R];
-        uint32_t qc4[FW_R];
+        const uint32_t nblkb = (brows + RS - 1) / RS, nstepb = nblkb + nactb - 1u;
+        // entry 0 of the fine rows 1 .. 3: Hq(Rb + 128 k, Cb), the diagonal input of the first column below the row
+        if (ln >= 1u && ln < uint32_t(CK2 / TILE) && ln * uint32_t(TILE) <= brows) dst.frow[ln][0] = int2{b_left[ln * uint32_t(TILE) - 1u].x, ALN_NEG};
+        // Lane l has the row block s - l at step s: it works while l <= s < l + nblkb.  The loop is peeled as the tile step's is,
+        // by what the lanes' activity takes: switching on (LO), all at work, switching off (HI), both at once in a block of fewer
+        // row blocks than lanes.  Lane 0's inputs of step s + 1 are read at step s (PRE), by every lane at one address, while row
+        // blocks are left.  Every address is a pointer that runs along; two steps to a round, so that what moves one lane per
+        // step changes registers instead of being copied.
+        if (ln < nactb) {
+            int hl4[RS], el4[RS];
+            uint32_t qc4[RS];
 #pragma unroll
-        for (int rr = 0; rr < FW_R; ++rr) {
-            hl4[rr] = 0;
-            el4[rr] = ALN_NEG;
-            qc4[rr] = 0;
-        }
-        // lane 0's inputs of a step are read one step ahead, by every lane at one address
-        uint4 nl0 = *reinterpret_cast<const uint4*>(&b_left[0]), nl1 = *reinterpret_cast<const uint4*>(&b_left[2]);
-        uint4 nq4 = *reinterpret_cast<const uint4*>(&b_q[0]);
-        const bool fine_col_lane = ((ln + 1u) * BC) % TILE == 0 && (ln + 1u) * BC < uint32_t(CK2);
-        const uint32_t fine_col_k = ((ln + 1u) * BC) / TILE;
-        for (uint32_t s = 0; s < nstepb; ++s) {
-            {
-                const uint32_t h4[FW_R] = {nl0.x, nl0.z, nl1.x, nl1.z}, e4[FW_R] = {nl0.y, nl0.w, nl1.y, nl1.w},
-                               q4[FW_R] = {nq4.x, nq4.y, nq4.z, nq4.w};
-#pragma unroll
-                for (int rr = 0; rr < FW_R; ++rr) {
-                    hl4[rr] = int(from_left_or(uint32_t(hl4[rr]), h4[rr]));
-                    el4[rr] = int(from_left_or(uint32_t(el4[rr]), e4[rr]));
-                    qc4[rr] = from_left_or(qc4[rr], q4[rr]);
-                }
-                const uint32_t sn = min(s + 1u, nblkb - 1u) * FW_R;  // (row blocks past the end are never looked at)
-                nl0 = *reinterpret_cast<const uint4*>(&b_left[sn]);
-                nl1 = *reinterpret_cast<const uint4*>(&b_left[sn + 2u]);
-                nq4 = *reinterpret_cast<const uint4*>(&b_q[sn]);
+            for (int rr = 0; rr < RS; ++rr) {
+                hl4[rr] = 0;
+                el4[rr] = ALN_NEG;
+                qc4[rr] = 0;
             }
-            const int bi = int(s) - int(ln);
-            if (bi >= 0 && uint32_t(bi) < nblkb && ln < nactb) {
+            const int2* lp = b_left;
+            const uint32_t* qp = b_q;
+            uint4 nl0, nl1{}, nq4{};
+            auto next_rows = [&]() __attribute__((always_inline)) {  // (Hq, E*) and the profile rows of the RS rows at lp / qp
+                nl0 = *reinterpret_cast<const uint4*>(&lp[0]);
+                if constexpr (RS == 4) {
+                    nl1 = *reinterpret_cast<const uint4*>(&lp[2]);
+                    nq4 = *reinterpret_cast<const uint4*>(&qp[0]);
+                } else {
+                    const uint2 q2 = *reinterpret_cast<const uint2*>(&qp[0]);
+                    nq4.x = q2.x;
+                    nq4.y = q2.y;
+                }
+            };
+            next_rows();
+            // fine column k at block column 128 k: the right edge of the lane whose columns end there, RS rows (16-byte stores)
+            // per step; rows past brows up to the next multiple of RS lie inside the column and are never read
+            const bool fine_col_lane = ((ln + 1u) * BC) % TILE == 0 && (ln + 1u) * BC < uint32_t(CK2);
+            uint8_t* fcp = reinterpret_cast<uint8_t*>(&dst.fcol[fine_col_lane ? ((ln + 1u) * BC) / TILE : 0u][0]) - size_t(ln) * (RS * sizeof(int2));  // (row block s - ln)
+            // fine row k at block row 128 k: a lane's BC columns when it has done 128 k / RS row blocks, k <= 3 and 128 k <= brows
+            uint8_t* frp = reinterpret_cast<uint8_t*>(&dst.frow[1][1u + ln * BC]);
+            const uint32_t fr_last = min(brows / uint32_t(RS), uint32_t((CK2 - TILE) / RS));
+            uint32_t done = 0u - ln;  // row blocks this lane has done (a lane that has not begun: "negative")
+            auto bstep = [&](auto lo, auto hi, auto pre, const uint32_t s) __attribute__((always_inline)) {
+                {
+                    const uint32_t h4[4] = {nl0.x, nl0.z, nl1.x, nl1.z}, e4[4] = {nl0.y, nl0.w, nl1.y, nl1.w},
+                                   q4[4] = {nq4.x, nq4.y, nq4.z, nq4.w};  // (the first RS of them)
 #pragma unroll
-                for (int rr = 0; rr < FW_R; ++rr) {
-                    const int hl_in = hl4[rr];
-                    uint32_t xw[BC / 4];
-                    if constexpr (BC == 8) {
-                        const uint2 xw2 = *reinterpret_cast<const uint2*>(bprof + qc4[rr]);
-                        xw[0] = xw2.x;
-                        xw[1] = xw2.y;
-                    } else {
-                        static_assert(BC == 4, "one or two profile words per ln");
-                        xw[0] = *reinterpret_cast<const uint32_t*>(bprof + qc4[rr]);
+                    for (int rr = 0; rr < RS; ++rr) {
+                        hl4[rr] = int(from_left_or(uint32_t(hl4[rr]), h4[rr]));
+                        el4[rr] = int(from_left_or(uint32_t(el4[rr]), e4[rr]));
+                        qc4[rr] = from_left_or(qc4[rr], q4[rr]);
                     }
-                    fwd_cells<BC, true>(Hb, Fb, xw, hl4[rr], el4[rr], dgb, qc4[rr], K);
-                    dgb = hl_in;
+                    if (decltype(pre)::value) {
+                        lp += RS;
+                        qp += RS;
+                        next_rows();
+                    }
                 }
-                const uint32_t y0 = uint32_t(bi) * FW_R;  // block row index of the step's first row
-                if (fine_col_lane) {
+                ++done;
+                bool act = true;
+                if (decltype(lo)::value) act = ln <= s;
+                if (decltype(hi)::value) act = act && int(ln) > int(s) - int(nblkb);
+                if (act) {
 #pragma unroll
-                    for (int rr = 0; rr < FW_R; ++rr)
-                        if (y0 + rr < brows) dst.fcol[fine_col_k][y0 + rr] = int2{hl4[rr], el4[rr]};
-                }
-                const uint32_t y1 = y0 + FW_R;  // rows of the block that are done
-                if ((y1 % TILE) == 0 && y1 < uint32_t(CK2) && y1 <= brows) {
-                    int2* fr = &dst.frow[y1 / TILE][1u + ln * BC];
+                    for (int rr = 0; rr < RS; ++rr) {
+                        const int hl_in = hl4[rr];
+                        uint32_t xw[BC / 4];
+                        if constexpr (BC == 8) {
+                            const uint2 xw2 = *reinterpret_cast<const uint2*>(bprof + qc4[rr]);
+                            xw[0] = xw2.x;
+                            xw[1] = xw2.y;
+                        } else {
+                            static_assert(BC == 4, "one or two profile words per ln");
+                            xw[0] = *reinterpret_cast<const uint32_t*>(bprof + qc4[rr]);
+                        }
+                        fwd_cells<BC, true>(Hb, Fb, xw, hl4[rr], el4[rr], dgb, qc4[rr], K);
+                        dgb = hl_in;
+                    }
+                    if (fine_col_lane) {
+                        reinterpret_cast<int4*>(fcp)[0] = int4{hl4[0], el4[0], hl4[1], el4[1]};
+                        if constexpr (RS == 4) reinterpret_cast<int4*>(fcp)[1] = int4{hl4[2], el4[2], hl4[3], el4[3]};
+                    }
+                    if ((done & uint32_t(TILE / RS - 1)) == 0u && done <= fr_last) {
+                        int2* f2 = reinterpret_cast<int2*>(frp);  // (entry 1 + BC ln: 8 bytes past a 16-byte boundary)
+                        f2[0] = int2{Hb[0], Fb[0]};
 #pragma unroll
-                    for (int c = 0; c < BC; ++c) fr[c] = int2{Hb[c], Fb[c]};
-                    if (ln == 0) dst.frow[y1 / TILE][0] = int2{b_left[y1 - 1u].x, ALN_NEG};  // Hq(Rb + y1, Cb): the diagonal input
+                        for (int c = 1; c + 1 < BC; c += 2) *reinterpret_cast<int4*>(f2 + c) = int4{Hb[c], Fb[c], Hb[c + 1], Fb[c + 1]};
+                        f2[BC - 1] = int2{Hb[BC - 1], Fb[BC - 1]};
+                        frp += sizeof(dst.frow[0]);
+                    }
                 }
-            }
+                fcp += RS * sizeof(int2);
+            };
+            auto run = [&](auto lo, auto hi, auto pre, uint32_t& s, const uint32_t end) __attribute__((always_inline)) {
+                for (; s + 1u < end; s += 2) {
+                    bstep(lo, hi, pre, s);
+                    bstep(lo, hi, pre, s + 1u);
+                }
+                if (s < end) {
+                    bstep(lo, hi, pre, s);
+                    ++s;
+                }
+            };
+            constexpr std::true_type yes{};
+            constexpr std::false_type no{};
+            uint32_t s = 0;
+            run(yes, no, yes, s, min(nactb, nblkb) - 1u);
+            run(no, no, yes, s, nblkb - 1u);    // (more row blocks than lanes)
+            run(yes, yes, no, s, nactb - 1u);   // (fewer)
+            run(no, yes, no, s, nstepb);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         tr_wave_sync();
+        return nstepb;
     };
 
-    // A block's step costs what its 4 x BC cells per lane cost, and a block runs rows / 4 + lanes - 1 of them: a block clipped to
+    // The same for a block of <= 64 columns, with the lanes along the ROWS.  The recurrence is symmetric: lane l takes the rows
+    // 8 l + 1 .. 8 l + 8 of the block, one column per step, the lanes one step apart — bcols + lanes - 1 steps of 8 cells with
+    // every lane that has rows at work, where the column shapes keep at most 16 lanes busy for 128 steps and more.  What changes
+    // sides: a lane's profile is over its eight QUERY bases and is indexed by the column's reference base; the block's top row
+    // (<= 65 entries, the profile row of each column's base beside them: b_q's place) enters at lane 0 as the left column does
+    // there; a lane keeps (Hq, E*) of its rows from column to column and hands (Hq, F*) of its last row down.  Fine rows 1 .. 3
+    // come out of lanes 15 / 31 / 47, one entry per step; such a block has no fine column but the coarse one.
+    auto recompute_block_t = [&](const uint32_t Rb, const uint32_t Cb, const uint32_t brows, const uint32_t bcols, V2Scratch& dst) __attribute__((always_inline)) {
+        constexpr int BR = V2_BLK_C;  // rows per lane
+        static_assert(BR == 8, "two profile words per lane");
+        const uint32_t ln = opaque(lane);
+        bool top_ok, left_ok, corner_ok;
+        block_edges(Rb, Cb, top_ok, left_ok, corner_ok);
+        int4* const b_top = reinterpret_cast<int4*>(b_q);
+        static_assert((64u + 1u) * sizeof(int4) <= B_Q, "the top row of a block of <= 64 columns");
+        // fine row 0 and fine column 0: the coarse checkpoints (or the matrix edges), as recompute_block_c has them
+        for (uint32_t x = ln; x <= bcols; x += 64) {  // entry x = column Cb + x (x = 0: left of the block)
+            int2 v;
+            if (Rb == 0)
+                v = int2{ge * int(Cb + x) - gd, ALN_NEG};
+            else if (Cb + x == 0)
+                v = int2{ge * int(Rb) - gd, ALN_NEG};
+            else if (x ? top_ok : corner_ok)
+                v = coarse_row(Rb, Cb + x - 1u);
+            else
+                v = int2{ALN_NEG, ALN_NEG};
+            dst.frow[0][x] = v;
+            uint32_t po = 0;
+            if (x) {
+                const uint32_t ch = ref_byte(r, m, pr.rc, Cb + x - 1u);
+                po = (ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u) * uint32_t(64 * (BR / 4) * 4);  // byte offset of the profile row
+            }
+            b_top[x] = int4{v.x, v.y, int(po), 0};
+        }
+        const uint32_t nact = (brows + BR - 1) / BR;
+        for (uint32_t y = ln; y < brows; y += 64) {  // entry y = row Rb + 1 + y
+            int2 v{ge * int(Rb + y + 1) - gd, ALN_NEG};
+            if (Cb) v = left_ok ? coarse_col(Cb, Rb + y) : int2{ALN_NEG, ALN_NEG};
+            dst.fcol[0][y] = v;
+            b_left[y] = v;
+        }
+        for (uint32_t y = brows + ln; y < nact * BR; y += 64) b_left[y] = int2{0, ALN_NEG};
+        {   // the diagonal increments of this lane's BR rows for each reference base, four to a word
+            uint32_t qpk[BR / 4];
+#pragma unroll
+            for (int c4 = 0; c4 < BR / 4; ++c4) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t y = ln * BR + c4 * 4 + e;
+                    w |= (y < brows ? uint32_t(q[Rb + y]) : 0u) << (8 * e);  // (0: equals no base)
+                }
+                qpk[c4] = w;
+            }
+            const uint32_t bases = 'A' | ('C' << 8) | ('G' << 16) | ('T' << 24);
+#pragma unroll
+            for (int code = 0; code < 5; ++code) {
+                const uint32_t bq = code < 4 ? (bases >> (8 * code)) & 0xFFu : 0x100u;  // 0x100: equals no byte
+#pragma unroll
+                for (int c4 = 0; c4 < BR / 4; ++c4) {
+                    uint32_t w = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w |= uint32_t(((qpk[c4] >> (8 * e)) & 0xFFu) == bq ? K.cm : K.cx) << (8 * e);
+                    b_prof[(uint32_t(code) * 64u + ln) * uint32_t(BR / 4) + uint32_t(c4)] = w;
+                }
+            }
+        }
+        const uint8_t* bprof = reinterpret_cast<const uint8_t*>(&b_prof[ln * uint32_t(BR / 4)]);
+        tr_wave_sync();
+        const uint32_t nstep = bcols + nact - 1u;
+        if (ln >= 1u && ln < uint32_t(CK2 / TILE) && ln * uint32_t(TILE) <= brows) dst.frow[ln][0] = int2{b_left[ln * uint32_t(TILE) - 1u].x, ALN_NEG};
+        if (ln < nact) {
+            int Hr[BR], Er[BR];  // (Hq, E*) of this lane's rows in the column to the left
+#pragma unroll
+            for (int c = 0; c < BR; ++c) {
+                const int2 v = b_left[ln * BR + c];
+                Hr[c] = v.x;
+                Er[c] = v.y;
+            }
+            const int dg_left = b_left[ln ? ln * BR - 1u : 0u].x;
+            int dgt = ln ? dg_left : b_top[0].x;  // Hq of the row above in the column left of the block
+            int out_h = 0, out_f = ALN_NEG;
+            uint32_t out_p = 0;
+            const int4* tp = b_top + 1;
+            int4 nrec = tp[0];
+            const bool fine_row_lane = ((ln + 1u) * BR) % TILE == 0 && (ln + 1u) * BR < uint32_t(CK2) && (ln + 1u) * BR <= brows;
+            uint8_t* frp = reinterpret_cast<uint8_t*>(&dst.frow[fine_row_lane ? ((ln + 1u) * BR) / TILE : 0u][1]) - size_t(ln) * sizeof(int2);  // (column s - ln)
+            // lane l has the column s - l at step s; peeled as the other shapes' loops are
+            auto cstep = [&](auto lo, auto hi, auto pre, const uint32_t s) __attribute__((always_inline)) {
+                int hu = int(from_left_or(uint32_t(out_h), uint32_t(nrec.x)));
+                int fu = int(from_left_or(uint32_t(out_f), uint32_t(nrec.y)));
+                const uint32_t po = from_left_or(out_p, uint32_t(nrec.z));
+                if (decltype(pre)::value) nrec = tp[1];
+                ++tp;
+                bool act = true;
+                if (decltype(lo)::value) act = ln <= s;
+                if (decltype(hi)::value) act = act && int(ln) > int(s) - int(bcols);
+                if (act) {
+                    const int hu_in = hu;
+                    const uint2 xw2 = *reinterpret_cast<const uint2*>(bprof + po);
+                    const uint32_t xw[BR / 4] = {xw2.x, xw2.y};
+                    fwd_cells<BR, true>(Hr, Er, xw, hu, fu, dgt, po, K);  // (down the column: F is what runs along, E what stays)
+                    dgt = hu_in;
+                    if (fine_row_lane) *reinterpret_cast<int2*>(frp) = int2{hu, fu};
+                }
+                frp += sizeof(int2);
+                out_h = hu;
+                out_f = fu;
+                out_p = po;
+            };
+            auto run = [&](auto lo, auto hi, auto pre, uint32_t& s, const uint32_t end) __attribute__((always_inline)) {
+                for (; s + 1u < end; s += 2) {
+                    cstep(lo, hi, pre, s);
+                    cstep(lo, hi, pre, s + 1u);
+                }
+                if (s < end) {
+                    cstep(lo, hi, pre, s);
+                    ++s;
+                }
+            };
+            constexpr std::true_type yes{};
+            constexpr std::false_type no{};
+            uint32_t s = 0;
+            run(yes, no, yes, s, min(nact, bcols) - 1u);
+            run(no, no, yes, s, bcols - 1u);   // (more columns than lanes)
+            run(yes, yes, no, s, nact - 1u);   // (fewer)
+            run(no, yes, no, s, nstep);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        tr_wave_sync();
+        return nstep;
+    };
+
+    // A block's step costs what its cells per lane cost, and a column shape runs rows / 4 + lanes - 1 of them: a block clipped to
     // half of its columns or fewer (every other block of a walk next to the diagonal is) takes 4 columns per lane — half the
-    // cells in a step, at most 32 steps more.  Same cells, same checkpoints at the same places.
+    // cells in a step, at most 32 steps more — and one of <= 64 columns the lanes along its rows.  Same cells, same checkpoints
+    // at the same places.  Returns the steps it ran.
     auto recompute_block = [&](const uint32_t Rb, const uint32_t Cb, const uint32_t brows, const uint32_t bcols, V2Scratch& dst) __attribute__((always_inline)) {
+        if (bcols <= 64u) return recompute_block_t(Rb, Cb, brows, bcols, dst);
         if (bcols <= 64u * uint32_t(V2_BLK_C / 2))
-            recompute_block_c(std::integral_constant<int, V2_BLK_C / 2>{}, Rb, Cb, brows, bcols, dst);
-        else
-            recompute_block_c(std::integral_constant<int, V2_BLK_C>{}, Rb, Cb, brows, bcols, dst);
+            return recompute_block_c(std::integral_constant<int, V2_BLK_C / 2>{}, std::integral_constant<int, FW_R>{}, Rb, Cb, brows, bcols, dst);
+        if (brows <= 64u)  // (fill is four fifths of such a block's steps: half the rows in a step)
+            return recompute_block_c(std::integral_constant<int, V2_BLK_C>{}, std::integral_constant<int, FW_R / 2>{}, Rb, Cb, brows, bcols, dst);
+        return recompute_block_c(std::integral_constant<int, V2_BLK_C>{}, std::integral_constant<int, FW_R>{}, Rb, Cb, brows, bcols, dst);
     };
 
     // verdict mode: the walk ends as soon as the count has reached stop_at (the windows still to come can only add) or cannot
@@ -1390,11 +1586,14 @@ __device__ __forceinline__ void trace2_body(const AlnPairDev* __restrict__ pairs
             }
             if (!have) {
                 scp = &scratch[pslot];
-                recompute_block(Rb, Cb, brows, bcols, *scp);
-                const uint32_t bcpl = bcols <= 64u * uint32_t(V2_BLK_C / 2) ? uint32_t(V2_BLK_C / 2) : uint32_t(V2_BLK_C);  // (recompute_block)
-                const uint32_t bsteps = (brows + FW_R - 1) / FW_R + (bcols + bcpl - 1u) / bcpl - 1u;
+                const unsigned long long t_own0 = __builtin_amdgcn_s_memtime();
+                const uint32_t bsteps = recompute_block(Rb, Cb, brows, bcols, *scp);  // (the steps it ran)
+                const unsigned long long t_own1 = __builtin_amdgcn_s_memtime() - t_own0;
                 n_bsteps += bsteps;
                 n_bsteps_thin += bcols <= 64u ? bsteps : 0u;
+                t_own += t_own1;
+                t_own_thin_c += bcols <= 64u ? t_own1 : 0ull;
+                t_own_thin_r += brows <= 64u ? t_own1 : 0ull;
             }
             if (HELP) {  // the blocks the walk can enter next: above and to the left of this one (entry point: the bounds of what they need)
                 v2_lds_store(help_addr + 4u * VH_RB, Rb);
