@@ -1,0 +1,310 @@
+// dump  (src/main.cpp:204-236, 430-453; src/output.cpp:151-275); the read reports beyond the reference's files: reports.cpp
+#include <getopt.h>
+
+#include <atomic>
+#include <cerrno>
+#include <climits>
+#include <cstring>
+#include <iostream>
+#include <unordered_map>
+#include <vector>
+
+#include "common.hpp"
+#include "reports.hpp"
+
+using namespace cer;
+using std::cerr;
+using std::endl;
+using std::string;
+
+namespace {
+
+struct DumpOptions {
+    string outdir, index, batch;
+    // --read-stats: read_stats.tsv, every read aligned against its cluster's representative (on the GPU)
+    // --pileup: cluster_pileup.tsv, the same alignments piled onto the representative position by position
+    // --polish: cluster_polished.fq, every representative called anew from both pileup tables of its reads
+    // --polish-min-depth: positions covered by fewer reads keep the representative's base
+    // --polish-weighted: the call of --polish with every read's vote weighted by its base quality
+    // --sites: cluster_sites.tsv and read_alleles.tsv, where the reads of a cluster disagree and which read says what there
+    // --split: cluster_split.tsv and read_split.tsv, the reads of a cluster in two groups by its linked sites
+    // --split-polish: cluster_split_polished.fq, the consensus of each group of every cluster that has a split
+    // --split-polish-min-depth: positions covered by fewer reads of the group keep the representative's base
+    ReportOpts reports;
+};
+
+// a whole number of [lo, hi], or the end of the run
+int number(const char* name, const char* text, long lo, long hi)
+{
+    char* end = nullptr;
+    errno = 0;
+    const long v = strtol(text, &end, 10);
+    if (errno != 0 || end == text || *end != '\0' || v < lo || v > hi)
+        die(string(name) + " must be a whole number" + (hi < INT32_MAX ? " from " + std::to_string(lo) + " to " + std::to_string(hi) : " of at least " + std::to_string(lo)) + "!");
+    return int(v);
+}
+
+void print_dump_help()
+{
+    cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N] [--polish-weighted]]" << endl
+         << "                    [--sites [--sites-min-depth N] [--sites-min-alt N] [--sites-min-pct P] [--sites-max N]]" << endl
+         << "                    [--split [--split-min-link N] [--split-min-margin N] [--split-rounds N]" << endl
+         << "                     [--split-polish [--split-polish-min-depth N]]] final.cer" << endl
+         << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
+         << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
+         << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
+         << "                 its cluster cover it, the bases they have there, deletions, and insertions in front of it (GPU)" << endl
+         << "  --polish       also write outdir/cluster_polished.fq: one record per record of cluster_cons.fq, the majority call over the" << endl
+         << "                 cluster's reads aligned against it — substitutions, deletions and insertions of up to 6 bases (GPU);" << endl
+         << "                 header: reads, and how many positions were substituted, deleted, inserted or left as they were" << endl
+         << "  --polish-min-depth N   positions covered by fewer than N reads keep the representative's base, quality '!' (default 3)" << endl
+         << "  --polish-weighted      with --polish: every read votes with its base qualities (Phred, 1 .. 93) instead of 1, so that" << endl
+         << "                 a few confident reads outvote many doubtful ones; min-depth still counts reads; header: weighted=1" << endl
+         << "  --sites        also write outdir/cluster_sites.tsv, the positions of every representative where a second allele has real" << endl
+         << "                 support among the cluster's reads (a base, a deletion, an insertion in front of the position), and" << endl
+         << "                 outdir/read_alleles.tsv, every read's allele at each of its cluster's sites, one character per site (GPU);" << endl
+         << "                 with --read-stats / --pileup the reads are still aligned once, with --polish a second time" << endl
+         << "  --sites-min-depth N    only positions covered by at least N reads can be sites (default 3)" << endl
+         << "  --sites-min-alt N      the second allele needs at least N reads (default 3) ..." << endl
+         << "  --sites-min-pct P      ... and at least P percent of the depth, 1 .. 50 (default 25)" << endl
+         << "  --sites-max N          keep the first N sites of a cluster (default 4096); a cluster with more gets a '#' line" << endl
+         << "  --split        also write outdir/cluster_split.tsv, per cluster how many of its sites (found under the --sites-* thresholds) vary" << endl
+         << "                 together and how many reads stand on either side of that pattern, and outdir/read_split.tsv, every read's" << endl
+         << "                 group (0 | 1 | .) and vote (GPU); whether a cluster is one thing or two is the reader's judgement of the counts" << endl
+         << "  --split-min-link N     two sites are linked when their reads agree or disagree by at least N (default 3)" << endl
+         << "  --split-min-margin N   a read joins a group when its vote is at least N on that side (default 1)" << endl
+         << "  --split-rounds N       refinement rounds, 0 .. 64, which carry the split along a representative no read spans (default 2)" << endl
+         << "  --split-polish         with --split: also write outdir/cluster_split_polished.fq, for every cluster that has a split the" << endl
+         << "                 consensus of each group that has reads (records <cluster>/0 and <cluster>/1), called from the alignments" << endl
+         << "                 of --split: no read is aligned again" << endl
+         << "  --split-polish-min-depth N   positions covered by fewer than N reads of the group keep the representative's base (default 3)" << endl;
+}
+
+DumpOptions parse_dump_options(int argc, char** argv)
+{
+    static const struct option lo[] = {{"verbose", no_argument, 0, 'v'}, {"debug", no_argument, 0, 'd'}, {"help", no_argument, 0, 'h'},
+                                       {"outdir", required_argument, 0, 'o'}, {"index", required_argument, 0, 'i'},
+                                       {"read-stats", no_argument, 0, 1000}, {"pileup", no_argument, 0, 1001},
+                                       {"polish", no_argument, 0, 1002}, {"polish-min-depth", required_argument, 0, 1003},
+                                       {"polish-weighted", no_argument, 0, 1004}, {"sites", no_argument, 0, 1005},
+                                       {"sites-min-depth", required_argument, 0, 1006}, {"sites-min-alt", required_argument, 0, 1007},
+                                       {"sites-min-pct", required_argument, 0, 1008}, {"sites-max", required_argument, 0, 1009},
+                                       {"split", no_argument, 0, 1010}, {"split-min-link", required_argument, 0, 1011},
+                                       {"split-min-margin", required_argument, 0, 1012}, {"split-rounds", required_argument, 0, 1013},
+                                       {"split-polish", no_argument, 0, 1014}, {"split-polish-min-depth", required_argument, 0, 1015}, {0, 0, 0, 0}};
+    DumpOptions d;
+    ReportOpts& r = d.reports;
+    bool polish = false, split_polish = false;
+    int polish_min_depth = 3, split_polish_min_depth = 3;
+    int o;
+    while ((o = getopt_long(argc, argv, "dhvo:i:", lo, nullptr)) != -1) {
+        switch (o) {
+            case 'o': d.outdir = optarg; break;
+            case 'i': d.index = optarg; break;
+            case 'v': VERBOSE = true; break;
+            case 1000: r.stats = true; break;
+            case 1001: r.pileup = true; break;
+            case 1002: polish = true; break;
+            case 1003: polish_min_depth = atoi(optarg); break;
+            case 1004: r.polish_weighted = true; break;
+            case 1005: r.sites.on = true; break;
+            case 1006: r.sites.min_depth = number("--sites-min-depth", optarg, 1, INT32_MAX); break;
+            case 1007: r.sites.min_alt = number("--sites-min-alt", optarg, 1, INT32_MAX); break;
+            case 1008: r.sites.min_pct = number("--sites-min-pct", optarg, 1, 50); break;
+            case 1009: r.sites.max_sites = number("--sites-max", optarg, 1, INT32_MAX); break;
+            case 1010: r.split.on = true; break;
+            case 1011: r.split.min_link = number("--split-min-link", optarg, 1, INT32_MAX); break;
+            case 1012: r.split.min_margin = number("--split-min-margin", optarg, 1, INT32_MAX); break;
+            case 1013: r.split.rounds = number("--split-rounds", optarg, 0, 64); break;
+            case 1014: split_polish = true; break;
+            case 1015: split_polish_min_depth = number("--split-polish-min-depth", optarg, 1, INT32_MAX); break;
+            case 'h': print_dump_help(); exit(0);
+            default: break;
+        }
+    }
+    if (optind >= argc) die("No input batch specified!");
+    if (d.outdir.empty()) die("Specifying output directory is mandatory!");
+    if (polish && polish_min_depth < 1) die("--polish-min-depth must be at least 1!");
+    if (r.polish_weighted && !polish) die("--polish-weighted asks for --polish!");
+    if (split_polish && !r.split.on) die("--split-polish asks for --split!");
+    if (split_polish) r.split.polish_min_depth = split_polish_min_depth;
+    if (polish) r.polish_min_depth = polish_min_depth;
+    if (d.index.empty()) die("Specifying the sorted read index is mandatory!");
+    d.batch = argv[optind];
+    return d;
+}
+
+void write_batch_info(const string& outdir, const Batch& b)
+{
+    std::ofstream bi;
+    create_file(outdir + "/batch_info.tsv", bi);
+    int ncls = 0, nnt = 0;
+    for (auto& c : b.Cls)
+        if (c->at(0)->RawSeq && c->at(0)->RawSeq->score > -1) {
+            ncls++;
+            nnt += c->size() > 2;
+        }
+    bi << "Name\tValue\nBatchNumber\t" << b.BatchNr << "\nBatchStart\t" << b.BatchStart << "\nBatchEnd\t" << b.BatchEnd << "\nDepth\t"
+       << b.Depth << "\nNrBases\t" << b.BatchBases << "\nNrClusters\t" << ncls << "\nNrNontrivialCls\t" << nnt << "\nMinDBsize\t0\n";
+}
+
+struct IdInfo {
+    unsigned cls;
+    int strand;
+};
+typedef std::unordered_map<string, IdInfo> IdMap;
+
+// clusters_info.tsv, the cluster_fastq directory, and every read id's cluster and strand
+IdMap write_clusters_info(const string& outdir, const Batch& b)
+{
+    IdMap id2cls;
+    std::ofstream info;
+    create_file(outdir + "/clusters_info.tsv", info);
+    create_outdir(outdir + "/cluster_fastq");
+    info << "ClusterId\tSize" << endl;
+    unsigned i = 0;
+    for (auto& cl : b.Cls) {
+        info << i << "\t" << cl->size() - 1 << endl;
+        for (auto& m : *cl) id2cls[m->Id] = IdInfo{i, m->MatchStrand};
+        i++;
+    }
+    return id2cls;
+}
+
+void write_cluster_cons(const string& outdir, const Batch& b)
+{
+    std::ofstream cons;
+    create_file(outdir + "/cluster_cons.fq", cons);
+    for (size_t i = 0; i < b.Cls.size(); ++i) {
+        auto& rep = b.Cls[i]->at(0);
+        if (!rep->RawSeq) die("Null pointer instead of cluster rep sequence at index: " + std::to_string(i));
+        if (rep->RawSeq->score < 0) continue;
+        string seq = rep->RawSeq->seq.str();
+        if (rep->MatchStrand == -1) seq = revcomp(seq);
+        cons << "@cluster_" << i << " origin=" << rep->RawSeq->name << ":" << rep->MatchStrand << " length=" << seq.size()
+             << " size=" << b.Cls[i]->size() - 1 << "\n" << seq << "\n+\n" << rep->RawSeq->qual << "\n";
+    }
+}
+
+struct Piece {  // a read's four lines in the mapping
+    const char *hb, *sb, *pb, *qb, *qe;  // header, sequence, separator, qualities; he = sb - 1, se = pb - 1, pe = qb - 1
+    bool flip;      // MatchStrand -1: sequence reverse-complemented, qualities reversed
+    bool whole;     // the record ends with its newline: it can go out as it lies
+};
+typedef std::unordered_map<unsigned, std::vector<Piece>> PieceMap;
+
+// clusters.tsv; every clustered read's piece of the mapping by cluster, and (for the read reports) the rows of clusters.tsv
+void walk_sorted_fastq(const string& outdir, const MappedFile& fqmap, const IdMap& id2cls, PieceMap& per_cluster, std::vector<ReadStatRow>* stat_rows)
+{
+    std::ofstream tsv;
+    create_file(outdir + "/clusters.tsv", tsv);
+    tsv << "ClusterId\tStrand\tRead" << endl;
+    LineCursor in{fqmap.data, fqmap.data + fqmap.size};
+    const char *hb, *he, *sb, *se, *pb, *pe, *qb, *qe;
+    while (in.line(hb, he) && in.line(sb, se) && in.line(pb, pe) && in.line(qb, qe)) {
+        if (he == hb) continue;  // (std::string::substr(1) of an empty header throws in the reference's reader; nothing to keep here)
+        const string id(hb + 1, size_t(he - hb - 1));
+        auto it = id2cls.find(id);
+        if (it == id2cls.end()) continue;
+        const IdInfo& at = it->second;
+        tsv << at.cls << "\t" << at.strand << "\t" << id << "\n";
+        per_cluster[at.cls].push_back(Piece{hb, sb, pb, qb, qe, at.strand == -1, in.p == qe + 1});
+        if (stat_rows) stat_rows->push_back(ReadStatRow{at.cls, at.strand, hb + 1, size_t(he - hb - 1), sb, size_t(se - sb), qb, size_t(qe - qb)});
+    }
+}
+
+// cluster_fastq/<id>.fq: a read that keeps its strand goes into its cluster's file as the four lines it is in the mapping (one
+// piece of a gather), a read of the other strand as a reverse-complemented copy.  False when the file could not be written.
+bool write_cluster_fastq(const string& path, const std::vector<Piece>& pieces, string& stage)
+{
+    GatherFile f;
+    if (!f.open(path)) return false;
+    size_t need = 0;
+    for (auto& pc : pieces)
+        if (pc.flip || !pc.whole) need += size_t(pc.qe - pc.hb) + 2;
+    stage.clear();
+    stage.reserve(need);  // (the gather points into it: it must not move before close())
+    for (auto& pc : pieces) {
+        if (!pc.flip && pc.whole) {
+            f.put(pc.hb, size_t(pc.qe + 1 - pc.hb));
+            continue;
+        }
+        const size_t at = stage.size();
+        stage.append(pc.hb, size_t(pc.sb - pc.hb));            // header line with its newline
+        const char* se = pc.pb - 1;
+        if (pc.flip) {
+            for (const char* c = se; c != pc.sb;) stage += complement(*--c);
+            stage += '\n';
+            stage.append(pc.pb, size_t(pc.qb - pc.pb));        // separator line with its newline
+            stage.append(std::reverse_iterator<const char*>(pc.qe), std::reverse_iterator<const char*>(pc.qb));
+        } else {
+            stage.append(pc.sb, size_t(pc.qe - pc.sb));
+        }
+        stage += '\n';
+        f.put(stage.data() + at, stage.size() - at);
+    }
+    return f.close();
+}
+
+// the cluster files are written side by side by a few threads
+void write_cluster_fastqs(const string& outdir, const PieceMap& per_cluster)
+{
+    std::vector<const PieceMap::value_type*> jobs;
+    for (auto& kv : per_cluster) jobs.push_back(&kv);
+    std::atomic<size_t> next{0};
+    std::atomic<int> failed{0};
+    run_threads(host_threads(8), [&](unsigned) {
+        string stage;  // the flipped records of ONE cluster (and a last record without its newline), built by this thread
+        for (size_t x = next.fetch_add(1); x < jobs.size(); x = next.fetch_add(1))
+            if (!write_cluster_fastq(outdir + "/cluster_fastq/" + std::to_string(jobs[x]->first) + ".fq", jobs[x]->second, stage)) failed = 1;
+    });
+    if (failed) die("Failed to write the cluster FASTQ files!");
+}
+
+}  // namespace
+
+int main_dump(int argc, char** argv)
+{
+    const DumpOptions d = parse_dump_options(argc, argv);
+    const ReportOpts& reports = d.reports;
+    Batch b;
+    string err, fastq;
+    Lap lap("dump");
+    if (!load_batch(b, d.batch, err)) die(err);
+    lap("batch loaded");
+    if (!load_sorted_idx(fastq, d.index)) die("Failed to load index " + d.index);
+    create_outdir(d.outdir);
+    b.Db.clear();
+    // SortClustersBySize, cluster.cpp:570-580 (std::sort, same comparator)
+    std::sort(b.Cls.begin(), b.Cls.end(), [](const std::shared_ptr<Cluster> x, const std::shared_ptr<Cluster> y) {
+        if (x->size() == y->size()) return x->at(0)->RawSeq->score > y->at(0)->RawSeq->score;
+        return x->size() > y->size();
+    });
+    write_batch_info(d.outdir, b);
+    const IdMap id2cls = write_clusters_info(d.outdir, b);
+    write_cluster_cons(d.outdir, b);
+    // The sorted FASTQ is read out of a mapping (src/output.cpp:225-275 reads and writes record by record; per-cluster strings
+    // once held the whole 8 GB of configs[4] in anonymous memory).
+    lap("read ids, info files, consensus fastq");
+    MappedFile fqmap;
+    {
+        string merr;
+        if (!map_file(fastq, fqmap, merr)) die("Failed to open " + fastq + "!");
+    }
+    lap("sorted fastq mapped");
+    PieceMap per_cluster;
+    std::vector<ReadStatRow> stat_rows;
+    walk_sorted_fastq(d.outdir, fqmap, id2cls, per_cluster, reports.any() ? &stat_rows : nullptr);
+    lap("sorted fastq walked, clusters.tsv");
+    write_cluster_fastqs(d.outdir, per_cluster);
+    lap("cluster fastq files written");
+    if (reports.any()) {
+        write_read_reports(b, d.outdir, stat_rows, reports);
+        const string names = string(reports.stats ? "read_stats.tsv, " : "") + (reports.pileup ? "cluster_pileup.tsv, " : "") +
+                             (reports.polish() ? "cluster_polished.fq, " : "") + (reports.sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") +
+                             (reports.split.on ? "cluster_split.tsv, read_split.tsv, " : "") + (reports.group_polish() ? "cluster_split_polished.fq, " : "");
+        lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
+    }
+    if (VERBOSE) cerr << "Dump complete." << endl;
+    return 0;
+}

@@ -1,0 +1,134 @@
+// The host-only half of the read reports: which rows count, how the clusters are cut into groups, what a group holds, how much
+// room the calls need, and the record formats.  Nothing here touches the library (tools/cli_reports_check.cpp links it alone).
+#include <algorithm>
+
+#include "common.hpp"
+#include "reports.hpp"
+
+using namespace cer;
+using std::string;
+
+ReportRows keep_report_rows(const Batch& b, const std::vector<ReadStatRow>& rows)
+{
+    ReportRows out{rows, {}, std::vector<std::vector<size_t>>(b.Cls.size())};
+    for (size_t x = 0; x < rows.size(); ++x) {
+        const ReadStatRow& r = rows[x];
+        if (r.cls >= b.Cls.size() || b.Cls[r.cls]->at(0)->RawSeq->score < 0) continue;
+        out.rows_of[r.cls].push_back(out.kept.size());
+        out.kept.push_back(x);
+    }
+    return out;
+}
+
+void ReportGroup::add_rowless_cluster(size_t ci)
+{
+    group_cls.emplace_back(ci, int64_t(-1));
+    group_seg.push_back(-1);
+}
+
+void ReportGroup::add_cluster(const Batch& b, size_t ci, const ReportRows& rows, const ReportOpts& opts)
+{
+    const auto& rep = b.Cls[ci]->at(0);
+    const std::vector<size_t>& ys = rows.rows_of[ci];
+    const int32_t rc = rep->MatchStrand == -1 ? 1 : 0;
+    if (offs.empty()) offs.push_back(0), qoffs.push_back(0);
+    // the representative: its stored sequence (the pair asks for the reverse complement when its strand is -1), its quality
+    // line as cluster_cons.fq has it
+    const int32_t rep_seq = int32_t(offs.size() - 1), rep_q = int32_t(qoffs.size() - 1);
+    pool.append(rep->RawSeq->seq.data(), rep->RawSeq->seq.size());
+    offs.push_back(int64_t(pool.size()));
+    quals.append(rep->RawSeq->qual.data(), rep->RawSeq->qual.size());
+    qoffs.push_back(int64_t(quals.size()));
+    if (opts.groups()) {
+        group_cls.emplace_back(ci, group_rows);
+        group_seg.push_back(int32_t(segs.size()));
+        row_base.insert(row_base.end(), ys.size(), group_rows);
+        group_rows += int64_t(rep->RawSeq->seq.size()) + 1;
+    }
+    if (opts.segs()) {
+        seg_of_pair.insert(seg_of_pair.end(), ys.size(), int32_t(segs.size()));
+        seg_reads.push_back(int32_t(ys.size()));
+        segs.push_back(ioc_polish_seg{rep_seq, rc});
+    }
+    for (size_t y : ys) {
+        const ReadStatRow& r = rows.row(y);
+        const int32_t q_seq = int32_t(offs.size() - 1), q_q = int32_t(qoffs.size() - 1);
+        if (r.strand == -1) {  // as cluster_fastq/<id>.fq has the read: reverse-complemented, its qualities reversed
+            for (size_t t = r.seq_len; t > 0; --t) pool += complement(r.seq[t - 1]);
+            for (size_t t = r.qual_len; t > 0; --t) quals += r.qual[t - 1];
+        } else {
+            pool.append(r.seq, r.seq_len);
+            quals.append(r.qual, r.qual_len);
+        }
+        offs.push_back(int64_t(pool.size()));
+        qoffs.push_back(int64_t(quals.size()));
+        pairs.push_back(ioc_aln_pair{q_seq, rep_seq, rc, 0 /* no hint */, 0.0 /* set when the group is aligned */});
+        pair_row.push_back(y);
+        pair_q.push_back(q_q);
+        pair_rep_q.push_back(rep_q);
+    }
+}
+
+void ReportGroup::clear()
+{
+    pool.clear(), quals.clear(), offs.clear(), qoffs.clear(), pairs.clear(), pair_row.clear(), pair_q.clear(), pair_rep_q.clear();
+    group_cls.clear(), group_seg.clear(), row_base.clear(), group_rows = 0;
+    segs.clear(), seg_of_pair.clear(), seg_reads.clear();
+}
+
+void plan_report_groups(const Batch& b, const ReportRows& rows, const ReportOpts& opts, const std::function<void(ReportGroup&)>& emit, size_t pool_max)
+{
+    ReportGroup g;
+    for (size_t ci = 0; ci < b.Cls.size(); ++ci) {
+        const auto& rep = b.Cls[ci]->at(0);
+        if (rows.rows_of[ci].empty()) {
+            if (opts.groups() && rep->RawSeq->score >= 0) g.add_rowless_cluster(ci);
+            continue;
+        }
+        size_t need = rep->RawSeq->seq.size();
+        for (size_t y : rows.rows_of[ci]) need += rows.row(y).seq_len;
+        if (g.would_overflow(need, pool_max)) {
+            emit(g);
+            g.clear();
+        }
+        g.add_cluster(b, ci, rows, opts);
+    }
+    emit(g);
+}
+
+static int64_t ref_len(const ReportGroup& g, const ioc_polish_seg& sg) { return g.offs[size_t(sg.ref) + 1] - g.offs[size_t(sg.ref)]; }
+
+int64_t polish_capacity(const ReportGroup& g, int groups)
+{
+    int64_t cap = 0;
+    for (const ioc_polish_seg& sg : g.segs) {
+        const int64_t m = ref_len(g, sg);
+        cap += groups * (m + IOC_PILE_INS_SLOTS * (m + 1));
+    }
+    return cap;
+}
+
+SiteCapacity site_capacity(const ReportGroup& g, int max_sites)
+{
+    SiteCapacity cap;
+    std::vector<int64_t> seg_cap(g.segs.size());
+    for (size_t s = 0; s < g.segs.size(); ++s) {
+        seg_cap[s] = std::min<int64_t>(max_sites, 2 * ref_len(g, g.segs[s]) + 1);
+        cap.sites += seg_cap[s];
+    }
+    for (size_t x = 0; x < g.pairs.size(); ++x) cap.alleles += seg_cap[size_t(g.seg_of_pair[x])];
+    return cap;
+}
+
+char allele_char(int32_t kind, int32_t a)
+{
+    return kind == IOC_SITE_INS ? (a == 0 ? '.' : a == 1 ? '+' : '?') : (a >= 0 && a <= IOC_ALLELE_DEL ? "ACGTN-"[a] : '?');
+}
+
+string polish_record(const string& name, int32_t reads, const ioc_polish_stats& z, const char* tail, const char* seq, const char* qual, size_t len)
+{
+    string text = "@" + name + " reads=" + std::to_string(reads) + " subs=" + std::to_string(z.n_sub) + " dels=" + std::to_string(z.n_del) +
+                  " ins=" + std::to_string(z.n_ins) + " low=" + std::to_string(z.n_low) + tail + "\n";
+    text.append(seq, len).append("\n+\n").append(qual, len).append("\n");
+    return text;
+}

@@ -1,0 +1,395 @@
+// dump --read-stats: <outdir>/read_stats.tsv, one row per row of clusters.tsv whose cluster has a record in cluster_cons.fq.  The
+// read as cluster_fastq/<id>.fq has it (reverse-complemented when its strand is -1) is aligned against the representative as
+// cluster_cons.fq has it, e = CalcErrorRate of the two quality lines as those files have them, k the batch's k-mer size, scores
+// 2 / -2 / extend 1 as the cluster drivers use — so the files `dump` writes determine the report.  The alignments are reduced to
+// their statistics on the device (ioc_align_pairs_stats), in groups of whole clusters whose sequence pool stays under 256 MB.
+//
+// dump --pileup: <outdir>/cluster_pileup.tsv from the same pairs in the same groups, piled on the device onto their cluster's
+// representative (ioc_align_pairs_pileup): for every cluster with a record in cluster_cons.fq, in cluster order, one row per
+// position of the representative as that file has it — how many reads cover the base, what they say there, how many have an
+// insertion in front of it — and a last row (RepBase '-') for the insertions behind the last base.  With both options a group
+// is aligned once: the pileup call returns the statistics of the same alignments.
+//
+// dump --polish: <outdir>/cluster_polished.fq from the same pairs, groups and frames — one record per record of cluster_cons.fq, in
+// its order and frame: the majority call over the cluster's reads (ioc_align_pairs_polish: both pileup tables and the call on the
+// device, only the sequences come back), header "@cluster_<id> reads=<pairs> subs= dels= ins= low=".  A cluster without a row of
+// clusters.tsv keeps its representative, with '!' qualities.  Beside the other options a group is still aligned once: the
+// polish call returns the statistics and the first table as well.
+//
+// dump --polish --polish-weighted: the same records, order and frames, called by weight (ioc_align_pairs_polish_weighted): every
+// read votes with the base qualities of its line as cluster_fastq/<id>.fq has it (reversed with the read when its strand is
+// -1), the pool's qualities being the lines e is computed from already.  The header gains a last field " weighted=1".
+//
+// dump --sites: <outdir>/cluster_sites.tsv and <outdir>/read_alleles.tsv from the same pairs, groups and frames
+// (ioc_align_pairs_alleles: the table, every read's projection, the sites and the alleles on the device; one byte per read and
+// site comes back).  cluster_sites.tsv: for every cluster in cluster order one row per variable site of its representative —
+// position, kind (base | ins: an insertion in front of the position), depth, and the two alleles with their counts, written
+// A C G T N - at a base site, '.' (absent) and '+' (present) at an insertion site; a cluster cut at --sites-max gets a line
+// "# cluster X: kept K of F sites".  read_alleles.tsv: one row per row read_stats.tsv has, the read's allele at every kept site
+// of its cluster as one character, '?' where the read does not cover the site, "*" for a cluster without sites.  Beside
+// --read-stats and --pileup a group is still aligned once: the call returns the statistics and the table as well.  With
+// --polish a group is aligned a second time, for the second table.
+//
+// dump --split: <outdir>/cluster_split.tsv and <outdir>/read_split.tsv (ioc_align_pairs_split: the call of --sites with the reads
+// of every cluster split in two by its linked sites where the alleles lie; the thresholds of the site search are the --sites-*
+// ones, whether --sites is given or not).  cluster_split.tsv: one row per cluster in cluster order — how many sites it kept, how
+// many of them ended up linked, the seed site's position and kind ("." for a cluster without a split), its reads and how many
+// of them are in group 0, in group 1 and in neither.  read_split.tsv: one row per row read_stats.tsv has — the read's group
+// (0 | 1 | .) and its vote.  Whether a split is real is the reader's judgement of those counts.  Beside --sites, --read-stats and
+// --pileup a group is still aligned once.
+//
+// dump --split --split-polish: <outdir>/cluster_split_polished.fq (ioc_align_pairs_split_polish: the call of --split with the
+// consensus of both groups of every cluster called on the device from the reads' planes, no read aligned a second time).  For
+// every cluster that has a split (a seed site), in cluster order, one record per group that has reads, group 0 before group 1,
+// named after the cluster's record in cluster_cons.fq with "/0" or "/1" appended: "@cluster_<id>/<group> reads=<the group's reads>
+// subs= dels= ins= low=", in the frame of that record; positions covered by fewer than --split-polish-min-depth reads of the
+// group keep the representative's base with quality '!'.  The other report files are what they are without the option.
+#include "reports.hpp"
+
+#include <cstdio>
+#include <fstream>
+
+#include "common.hpp"
+
+using namespace cer;
+using std::string;
+
+namespace {
+
+// the sequences and call statistics of a polish call, segment after segment
+struct PolishedSet {
+    string seq, qual;
+    std::vector<int64_t> off;
+    std::vector<ioc_polish_stats> stats;
+    void reset(int64_t cap, size_t n)
+    {
+        seq.assign(size_t(cap), '\0'), qual.assign(size_t(cap), '\0');
+        off.assign(n + 1, 0), stats.assign(n, ioc_polish_stats{});
+    }
+};
+
+// what comes back for one group
+struct GroupResult {
+    std::vector<int32_t> score;  // per pair ...
+    std::vector<int64_t> windows;
+    std::vector<ioc_aln_stats> stats;
+    std::vector<uint8_t> alleles;  // (--sites) pair x's alleles at [allele_off[x], allele_off[x + 1])
+    std::vector<int64_t> allele_off;
+    std::vector<uint8_t> group;  // (--split)
+    std::vector<int32_t> vote;
+    std::vector<ioc_pileup_col> cols;  // (--pileup) the group's table, group_rows rows
+    std::vector<ioc_pile_site> sites;  // (--sites, --split) segment g's sites at [site_off[g], site_off[g + 1]), site_found[g] before the cut
+    std::vector<int64_t> site_off, site_found;
+    std::vector<ioc_split_seg> split_seg;
+    PolishedSet polished;        // (--polish) per segment
+    PolishedSet group_polished;  // (--split-polish) per segment and side: 2 * g + h
+};
+
+// a row of the three per-read tables
+struct RowResult {
+    int32_t score = 0;
+    int64_t windows = 0;
+    ioc_aln_stats st{};
+    size_t rep_len = 0;
+    string alleles;                  // (--sites) one character per kept site of the read's cluster
+    uint8_t group = IOC_SPLIT_NONE;  // (--split) the read's side, and ...
+    int32_t vote = 0;                // ... its vote
+};
+
+// The one place that chooses a library call.  --sites and / or --split come first; --polish is a second call, which takes the
+// statistics and the first table only when the first call did not produce them; otherwise the pileup; otherwise the statistics.
+void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupResult& r)
+{
+    const size_t nq = g.qoffs.size() - 1, np = g.pairs.size(), ns = g.segs.size();
+    std::vector<double> qs(nq), qe(nq);
+    check(c, ioc_qual_scores(c, int32_t(nq), g.qoffs.data(), reinterpret_cast<const uint8_t*>(g.quals.data()), k, qs.data(), qe.data()), "quality scores");
+    for (size_t x = 0; x < np; ++x) g.pairs[x].e = qe[size_t(g.pair_q[x])] + qe[size_t(g.pair_rep_q[x])];
+    check(c, ioc_align_set_pool(c, int32_t(g.offs.size() - 1), g.pool.data(), g.offs.data()), "sequence pool");
+    r.score.assign(np, 0), r.windows.assign(np, 0), r.stats.assign(o.stats ? np : 0, ioc_aln_stats{});
+    const int32_t n = int32_t(np), n_segs = int32_t(ns);
+    const ioc_aln_pair* const pairs = g.pairs.data();
+    int32_t* const sc = r.score.data();
+    int64_t* const win = r.windows.data();
+    ioc_aln_stats* const st = o.stats ? r.stats.data() : nullptr;
+    const SitesOpt& so = o.sites;
+    const SplitOpt& sp = o.split;
+    bool have_first = false;  // the statistics and the first table are in r already
+    if (so.on || sp.on) {
+        const SiteCapacity cap = site_capacity(g, so.max_sites);
+        r.sites.assign(size_t(cap.sites), ioc_pile_site{}), r.site_off.assign(ns + 1, 0), r.site_found.assign(ns, 0);
+        r.alleles.assign(so.on ? size_t(cap.alleles) + 1 : size_t(1), 0), r.allele_off.assign(np + 1, 0);
+        if (o.pileup) r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
+        ioc_pileup_col* const cols = o.pileup ? r.cols.data() : nullptr;
+        uint8_t* const alleles = so.on ? r.alleles.data() : nullptr;
+        const int64_t a_cap = so.on ? cap.alleles : 0;
+        if (sp.on) {
+            r.group.assign(np, 0), r.vote.assign(np, 0), r.split_seg.assign(ns, ioc_split_seg{});
+            if (o.group_polish()) {
+                PolishedSet& gp = r.group_polished;
+                const int64_t gcap = polish_capacity(g, 2);
+                gp.reset(gcap, 2 * ns);
+                check(c, ioc_align_pairs_split_polish(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, st, n_segs, g.segs.data(), g.seg_of_pair.data(), so.min_depth,
+                                                      so.min_alt, so.min_pct, so.max_sites, r.sites.data(), cap.sites, r.site_off.data(), r.site_found.data(),
+                                                      alleles, a_cap, r.allele_off.data(), cols, sp.min_link, sp.min_margin, sp.rounds, nullptr, nullptr,
+                                                      r.group.data(), r.vote.data(), r.split_seg.data(), sp.polish_min_depth, &gp.seq[0], &gp.qual[0], gcap,
+                                                      gp.off.data(), gp.stats.data(), nullptr, nullptr),
+                      "split by linked sites with the groups' consensus");
+            } else {
+                check(c, ioc_align_pairs_split(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, st, n_segs, g.segs.data(), g.seg_of_pair.data(), so.min_depth,
+                                               so.min_alt, so.min_pct, so.max_sites, r.sites.data(), cap.sites, r.site_off.data(), r.site_found.data(), alleles,
+                                               a_cap, r.allele_off.data(), cols, sp.min_link, sp.min_margin, sp.rounds, nullptr, nullptr, r.group.data(),
+                                               r.vote.data(), r.split_seg.data()),
+                      "split by linked sites");
+            }
+        } else {
+            check(c, ioc_align_pairs_alleles(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, st, n_segs, g.segs.data(), g.seg_of_pair.data(), so.min_depth, so.min_alt,
+                                             so.min_pct, so.max_sites, r.sites.data(), cap.sites, r.site_off.data(), r.site_found.data(), r.alleles.data(),
+                                             cap.alleles, r.allele_off.data(), cols),
+                  "variable sites");
+        }
+        have_first = true;
+    }
+    if (o.polish()) {
+        PolishedSet& pol = r.polished;
+        const int64_t cap = polish_capacity(g);
+        pol.reset(cap, ns);
+        if (o.pileup && !have_first) r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
+        ioc_aln_stats* const st_out = have_first ? nullptr : st;
+        ioc_pileup_col* const cols_out = o.pileup && !have_first ? r.cols.data() : nullptr;
+        if (o.polish_weighted) {
+            // (the quality lines lie in `quals` in the order and at the lengths of the sequences in `pool`)
+            if (g.qoffs != g.offs) die("--polish-weighted: a quality line is not as long as its sequence!");
+            check(c, ioc_align_set_pool_qual(c, g.quals.data(), int64_t(g.quals.size())), "pool qualities");
+            check(c, ioc_align_pairs_polish_weighted(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, st_out, n_segs, g.segs.data(), g.seg_of_pair.data(),
+                                                     o.polish_min_depth, &pol.seq[0], &pol.qual[0], cap, pol.off.data(), pol.stats.data(), cols_out, nullptr,
+                                                     nullptr),
+                  "weighted polished consensus");
+        } else {
+            check(c, ioc_align_pairs_polish(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, st_out, n_segs, g.segs.data(), g.seg_of_pair.data(), o.polish_min_depth,
+                                            &pol.seq[0], &pol.qual[0], cap, pol.off.data(), pol.stats.data(), cols_out, nullptr),
+                  "polished consensus");
+        }
+    } else if (!have_first && o.pileup) {
+        r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
+        check(c, ioc_align_pairs_pileup(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, st, g.row_base.data(), g.group_rows, r.cols.data()), "alignment pileup");
+    } else if (!have_first) {
+        check(c, ioc_align_pairs_stats(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, r.stats.data()), "alignment statistics");
+    }
+}
+
+// a group's results into the rows of the per-read tables
+void scatter_to_rows(const ReportOpts& o, const ReportGroup& g, const GroupResult& r, std::vector<RowResult>& res)
+{
+    for (size_t x = 0; x < g.pairs.size(); ++x) {
+        RowResult& row = res[g.pair_row[x]];
+        row.rep_len = size_t(g.offs[size_t(g.pairs[x].ref) + 1] - g.offs[size_t(g.pairs[x].ref)]);
+        if (o.stats) row.score = r.score[x], row.windows = r.windows[x], row.st = r.stats[x];
+        if (o.split.on) row.group = r.group[x], row.vote = r.vote[x];
+        if (o.sites.on) {
+            const int64_t s0 = r.site_off[size_t(g.seg_of_pair[x])];
+            for (int64_t a = r.allele_off[x]; a < r.allele_off[x + 1]; ++a)
+                row.alleles += allele_char(r.sites[size_t(s0 + a - r.allele_off[x])].kind, r.alleles[size_t(a)]);
+            if (row.alleles.empty()) row.alleles = "*";
+        }
+    }
+}
+
+// a cluster's representative as cluster_cons.fq has it
+string frame_of(const Batch& b, size_t ci)
+{
+    const auto& rep = b.Cls[ci]->at(0);
+    return rep->MatchStrand == -1 ? revcomp(rep->RawSeq->seq.str()) : rep->RawSeq->seq.str();
+}
+
+const char* site_kind(const ioc_pile_site& t) { return t.kind == IOC_SITE_INS ? "ins" : "base"; }
+
+void write_pileup(std::ofstream& out, const Batch& b, const ReportGroup& g, const GroupResult& r)
+{
+    string text;
+    for (const auto& gc : g.group_cls) {
+        const string frame = frame_of(b, gc.first);
+        text.clear();
+        for (size_t p = 0; p <= frame.size(); ++p) {
+            const ioc_pileup_col z = gc.second < 0 ? ioc_pileup_col{} : r.cols[size_t(gc.second) + p];
+            text += std::to_string(gc.first) + '\t' + std::to_string(p) + '\t' + (p < frame.size() ? frame[p] : '-') + '\t' +
+                    std::to_string(uint64_t(z.a) + z.c + z.g + z.t + z.other + z.del) + '\t' + std::to_string(z.a) + '\t' + std::to_string(z.c) + '\t' +
+                    std::to_string(z.g) + '\t' + std::to_string(z.t) + '\t' + std::to_string(z.other) + '\t' + std::to_string(z.del) + '\t' +
+                    std::to_string(z.ins_runs) + '\t' + std::to_string(z.ins_bases) + '\n';
+        }
+        out.write(text.data(), std::streamsize(text.size()));
+    }
+}
+
+void write_polish(std::ofstream& out, const Batch& b, const ReportGroup& g, const GroupResult& r, bool weighted)
+{
+    const PolishedSet& pol = r.polished;
+    const char* const tail = weighted ? " weighted=1" : "";
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        const string name = "cluster_" + std::to_string(g.group_cls[x].first);
+        string text;
+        if (s < 0) {  // a cluster without a row: its representative, nothing called
+            const string seq = frame_of(b, g.group_cls[x].first), qual(seq.size(), '!');
+            ioc_polish_stats z{};
+            z.n_low = int32_t(seq.size());
+            text = polish_record(name, 0, z, tail, seq.data(), qual.data(), seq.size());
+        } else {
+            const size_t at = size_t(pol.off[size_t(s)]), len = size_t(pol.off[size_t(s) + 1]) - at;
+            text = polish_record(name, g.seg_reads[size_t(s)], pol.stats[size_t(s)], tail, pol.seq.data() + at, pol.qual.data() + at, len);
+        }
+        out.write(text.data(), std::streamsize(text.size()));
+    }
+}
+
+void write_sites(std::ofstream& out, const ReportGroup& g, const GroupResult& r)
+{
+    string text;
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0) continue;
+        text.clear();
+        const string id = std::to_string(g.group_cls[x].first);
+        const int64_t s0 = r.site_off[size_t(s)], s1 = r.site_off[size_t(s) + 1];
+        if (r.site_found[size_t(s)] > s1 - s0) text += "# cluster " + id + ": kept " + std::to_string(s1 - s0) + " of " + std::to_string(r.site_found[size_t(s)]) + " sites\n";
+        for (int64_t at = s0; at < s1; ++at) {
+            const ioc_pile_site& t = r.sites[size_t(at)];
+            text += id + '\t' + std::to_string(t.row) + '\t' + site_kind(t) + '\t' + std::to_string(t.depth) + '\t' + allele_char(t.kind, t.major) + '\t' +
+                    std::to_string(t.n_major) + '\t' + allele_char(t.kind, t.minor) + '\t' + std::to_string(t.n_minor) + '\n';
+        }
+        out.write(text.data(), std::streamsize(text.size()));
+    }
+}
+
+void write_split(std::ofstream& out, const ReportGroup& g, const GroupResult& r)
+{
+    string text;
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        const ioc_split_seg z = s < 0 ? ioc_split_seg{-1, 0, 0, 0, 0, 0, 0} : r.split_seg[size_t(s)];
+        const int64_t s0 = s < 0 ? 0 : r.site_off[size_t(s)], n_sites = s < 0 ? 0 : r.site_off[size_t(s) + 1] - s0;
+        text = std::to_string(g.group_cls[x].first) + '\t' + std::to_string(n_sites) + '\t' + std::to_string(z.n_linked) + '\t';
+        if (z.seed >= 0 && z.seed < n_sites) {
+            const ioc_pile_site& t = r.sites[size_t(s0 + z.seed)];
+            text += std::to_string(t.row) + '\t' + site_kind(t);
+        } else {
+            text += ".\t.";
+        }
+        text += '\t' + std::to_string(z.n_reads) + '\t' + std::to_string(z.n_group0) + '\t' + std::to_string(z.n_group1) + '\t' + std::to_string(z.n_none) + '\n';
+        out.write(text.data(), std::streamsize(text.size()));
+    }
+}
+
+void write_group_polish(std::ofstream& out, const ReportGroup& g, const GroupResult& r)
+{
+    const PolishedSet& gp = r.group_polished;
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0 || r.split_seg[size_t(s)].seed < 0) continue;
+        for (size_t h = 0; h < 2; ++h) {
+            const int32_t reads = h ? r.split_seg[size_t(s)].n_group1 : r.split_seg[size_t(s)].n_group0;
+            if (reads <= 0) continue;
+            const size_t gs = 2 * size_t(s) + h, at = size_t(gp.off[gs]), len = size_t(gp.off[gs + 1] - gp.off[gs]);
+            const string text = polish_record("cluster_" + std::to_string(g.group_cls[x].first) + '/' + std::to_string(h), reads, gp.stats[gs], "",
+                                              gp.seq.data() + at, gp.qual.data() + at, len);
+            out.write(text.data(), std::streamsize(text.size()));
+        }
+    }
+}
+
+// the files that grow group by group
+struct GroupFiles {
+    std::ofstream pileup, polish, sites, split, group_polish;
+    GroupFiles(const string& outdir, const ReportOpts& o)
+    {
+        if (o.pileup) {
+            create_file(outdir + "/cluster_pileup.tsv", pileup);
+            pileup << "ClusterId\tPos\tRepBase\tDepth\tA\tC\tG\tT\tN\tDel\tInsReads\tInsBases\n";
+        }
+        if (o.polish()) create_file(outdir + "/cluster_polished.fq", polish);
+        if (o.sites.on) {
+            create_file(outdir + "/cluster_sites.tsv", sites);
+            sites << "ClusterId\tPos\tKind\tDepth\tMajor\tNMajor\tMinor\tNMinor\n";
+        }
+        if (o.split.on) {
+            create_file(outdir + "/cluster_split.tsv", split);
+            split << "ClusterId\tNSites\tNLinked\tSeedPos\tSeedKind\tNReads\tNGroup0\tNGroup1\tNNone\n";
+        }
+        if (o.group_polish()) create_file(outdir + "/cluster_split_polished.fq", group_polish);
+    }
+    void write(const Batch& b, const ReportOpts& o, const ReportGroup& g, const GroupResult& r)
+    {
+        if (o.pileup) write_pileup(pileup, b, g, r);
+        if (o.polish()) write_polish(polish, b, g, r, o.polish_weighted);
+        if (o.sites.on && !g.segs.empty()) write_sites(sites, g, r);
+        if (o.split.on) write_split(split, g, r);
+        if (o.group_polish() && !g.segs.empty()) write_group_polish(group_polish, g, r);
+    }
+};
+
+// the three per-read tables, from the flat per-row results
+void write_read_alleles(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/read_alleles.tsv", out);
+    out << "Read\tClusterId\tAlleles\n";
+    for (size_t y = 0; y < rows.kept.size(); ++y) {
+        const ReadStatRow& r = rows.row(y);
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << r.cls << '\t' << res[y].alleles << '\n';
+    }
+}
+
+void write_read_split(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/read_split.tsv", out);
+    out << "Read\tClusterId\tGroup\tVote\n";
+    for (size_t y = 0; y < rows.kept.size(); ++y) {
+        const ReadStatRow& r = rows.row(y);
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << r.cls << '\t' << (res[y].group == 0 ? "0" : res[y].group == 1 ? "1" : ".") << '\t' << res[y].vote << '\n';
+    }
+}
+
+void write_read_stats(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/read_stats.tsv", out);
+    out << "ClusterId\tStrand\tRead\tReadLen\tRepLen\tScore\tWindows\tColumns\tMatches\tMismatches\tIns\tDel\tInsRuns\tDelRuns\tLongestIns\tLongestDel\t"
+           "ReadStart\tReadEnd\tRepStart\tRepEnd\tIdentity\n";
+    for (size_t y = 0; y < rows.kept.size(); ++y) {
+        const ReadStatRow& r = rows.row(y);
+        const RowResult& a = res[y];
+        const ioc_aln_stats& s = a.st;
+        char ident[32];
+        snprintf(ident, sizeof ident, "%.6f", s.columns > 0 ? double(s.matches) / double(s.columns) : 0.0);
+        out << r.cls << '\t' << r.strand << '\t';
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << r.seq_len << '\t' << a.rep_len << '\t' << a.score << '\t' << a.windows << '\t' << s.columns << '\t' << s.matches << '\t' << s.mismatches
+            << '\t' << s.ins << '\t' << s.del << '\t' << s.ins_runs << '\t' << s.del_runs << '\t' << s.longest_ins << '\t' << s.longest_del << '\t' << s.lead_i
+            << '\t' << int64_t(r.seq_len) - s.trail_i << '\t' << s.lead_d << '\t' << int64_t(a.rep_len) - s.trail_d << '\t' << ident << '\n';
+    }
+}
+
+}  // namespace
+
+void write_read_reports(const Batch& b, const string& outdir, const std::vector<ReadStatRow>& all_rows, const ReportOpts& opts)
+{
+    const int k = b.SortArgs.KmerSize;
+    const ReportRows rows = keep_report_rows(b, all_rows);
+    std::vector<RowResult> res(rows.kept.size());
+    ioc_ctx* c = rows.kept.empty() ? nullptr : make_ctx();
+    GroupFiles files(outdir, opts);
+    GroupResult result;
+    plan_report_groups(b, rows, opts, [&](ReportGroup& g) {
+        if (!g.pairs.empty()) {
+            align_group(c, k, opts, g, result);
+            scatter_to_rows(opts, g, result, res);
+        }
+        if (opts.groups()) files.write(b, opts, g, result);
+    });
+    if (c) ioc_ctx_destroy(c);
+    if (opts.sites.on) write_read_alleles(outdir, rows, res);
+    if (opts.split.on) write_read_split(outdir, rows, res);
+    if (opts.stats) write_read_stats(outdir, rows, res);
+}

@@ -1,0 +1,103 @@
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish): every read of clusters.tsv
+// aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
+// formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
+#ifndef ISONCLUST2_CLI_REPORTS_HPP
+#define ISONCLUST2_CLI_REPORTS_HPP
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "cer.hpp"
+#include "isonclust2_hip.h"
+
+struct SitesOpt {
+    bool on = false;
+    int min_depth = 3, min_alt = 3, min_pct = 25, max_sites = 4096;
+};
+struct SplitOpt {
+    bool on = false;
+    int min_link = 3, min_margin = 1, rounds = 2;
+    int polish_min_depth = 0;  // --split-polish: > 0, the depth below which a group's call keeps the representative's base
+};
+struct ReportOpts {
+    bool stats = false;        // --read-stats
+    bool pileup = false;       // --pileup
+    int polish_min_depth = 0;  // --polish: > 0, the depth below which the call keeps the representative's base
+    bool polish_weighted = false;
+    SitesOpt sites;
+    SplitOpt split;
+    bool polish() const { return polish_min_depth > 0; }
+    bool group_polish() const { return split.on && split.polish_min_depth > 0; }
+    bool segs() const { return polish() || sites.on || split.on; }  // the calls that take the clusters as segments
+    bool groups() const { return pileup || segs(); }                // something is written per group
+    bool any() const { return stats || groups(); }
+};
+
+// a row of clusters.tsv: the read's id, sequence and quality lines where they lie in the sorted FASTQ's mapping
+struct ReadStatRow {
+    unsigned cls;
+    int strand;
+    const char* id;
+    size_t id_len;
+    const char* seq;
+    size_t seq_len;
+    const char* qual;
+    size_t qual_len;
+};
+
+// the rows whose cluster has a record in cluster_cons.fq, in the order of clusters.tsv; row y of every per-read table is kept[y]
+struct ReportRows {
+    const std::vector<ReadStatRow>& all;
+    std::vector<size_t> kept;
+    std::vector<std::vector<size_t>> rows_of;  // per cluster: its rows y
+    const ReadStatRow& row(size_t y) const { return all[kept[y]]; }
+};
+ReportRows keep_report_rows(const cer::Batch& b, const std::vector<ReadStatRow>& rows);
+
+// everything one group of clusters sends to the device
+struct ReportGroup {
+    std::string pool, quals;  // the sequences side by side, and their quality lines in the same order
+    std::vector<int64_t> offs, qoffs;
+    std::vector<ioc_aln_pair> pairs;      // (e is set from the quality lines when the group is aligned)
+    std::vector<size_t> pair_row;         // per pair: its row y
+    std::vector<int32_t> pair_q, pair_rep_q;  // per pair: the quality lines of its read and of its representative (indices into qoffs)
+    // the group's clusters in cluster order with the first of their rows in the group's table (-1: a cluster without a row of
+    // clusters.tsv, all zeros) and their segment (-1 likewise); per pair its cluster's first row
+    std::vector<std::pair<size_t, int64_t>> group_cls;
+    std::vector<int32_t> group_seg;
+    std::vector<int64_t> row_base;
+    int64_t group_rows = 0;
+    // one segment per cluster with rows, in the order of group_cls
+    std::vector<ioc_polish_seg> segs;
+    std::vector<int32_t> seg_of_pair, seg_reads;
+
+    // the 256 MB rule: a cluster that needs `need` more bytes of pool opens the next group, unless this one is empty
+    bool would_overflow(size_t need, size_t pool_max) const { return !pairs.empty() && pool.size() + need > pool_max; }
+    void add_rowless_cluster(size_t ci);
+    void add_cluster(const cer::Batch& b, size_t ci, const ReportRows& rows, const ReportOpts& opts);
+    void clear();
+};
+
+constexpr size_t REPORT_POOL_MAX = size_t(256) << 20;
+// Walks the clusters in order and calls emit(group) at every cut and at the end (then possibly with no pair at all).  A cluster
+// is never divided; one without rows goes to the group that is open when it is met.
+void plan_report_groups(const cer::Batch& b, const ReportRows& rows, const ReportOpts& opts, const std::function<void(ReportGroup&)>& emit,
+                        size_t pool_max = REPORT_POOL_MAX);
+
+// what the consensus calls may return at most, for all segments of a group (polish) or for both sides of them (groups = 2)
+int64_t polish_capacity(const ReportGroup& g, int groups = 1);
+// the sites the segments can have at most, and the allele bytes of all pairs at that
+struct SiteCapacity {
+    int64_t sites = 0, alleles = 0;
+};
+SiteCapacity site_capacity(const ReportGroup& g, int max_sites);
+
+char allele_char(int32_t kind, int32_t a);
+// "@<name> reads= subs= dels= ins= low=<tail>", the sequence, "+", the qualities
+std::string polish_record(const std::string& name, int32_t reads, const ioc_polish_stats& z, const char* tail, const char* seq, const char* qual, size_t len);
+
+void write_read_reports(const cer::Batch& b, const std::string& outdir, const std::vector<ReadStatRow>& rows, const ReportOpts& opts);
+
+#endif

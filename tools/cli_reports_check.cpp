@@ -1,0 +1,176 @@
+// cli_reports_check.cpp — how `dump` cuts its clusters into groups for the read reports (isonclust2_amd/csrc/cli/report_plan.cpp),
+// on a batch built in memory: a cluster whose representative has a negative score (its rows do not count), a cluster without
+// rows, a cluster whose representative is on strand -1 with reads of both strands, and three further clusters.
+//
+//  1. With the default cap there is one group; its pool (with the reverse complements), its quality lines (reversed with their
+//     reads), both offset tables, every pair's query, reference and rc flag, row_base, seg_of_pair, seg_reads, group_cls and
+//     group_seg are compared with values written out by hand, and so are the capacity sums of the consensus and site calls.
+//  2. With the cap lowered to every value from the smallest cluster's need to the total, the cuts are exactly where a plain loop
+//     over the needs puts them (pool + need > cap with a non-empty pool): no cluster is divided, a cluster without rows goes to
+//     the group that is open when it is met, and the groups' pairs one after the other are the pairs of the one-group plan.
+//  3. polish_record and allele_char on one hand-made input each.
+//
+// Host code only (the planner does not touch the library, so neither common.cpp nor the library is linked); meant for the sanitizers:
+//
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -Iisonclust2_amd/csrc/cli \
+//       -o /tmp/cli_reports_check tools/cli_reports_check.cpp isonclust2_amd/csrc/cli/report_plan.cpp isonclust2_amd/csrc/cli/cer.cpp \
+//       && /tmp/cli_reports_check
+//
+// Exit status 0 and "ok" when everything agrees.
+#include <cstdio>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "reports.hpp"
+
+using namespace cer;
+using std::string;
+
+namespace {
+
+int faults = 0;
+#define EXPECT(cond)                                                   \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            fprintf(stderr, "line %d: %s does not hold\n", __LINE__, #cond); \
+            ++faults;                                                  \
+        }                                                              \
+    } while (0)
+
+std::shared_ptr<Cluster> cluster_of(const char* seq, const char* qual, double score, int strand)
+{
+    auto cl = std::make_shared<Cluster>();
+    auto rep = std::make_shared<ProcSeq>();
+    rep->RawSeq.reset(new Seq{"rep", seq, qual, score, 0.01});
+    rep->MatchStrand = strand;
+    cl->push_back(rep);
+    return cl;
+}
+
+struct Read {
+    unsigned cls;
+    int strand;
+    string id, seq, qual;
+};
+
+// a pair as the strings it stands for: its row, the query and the reference as the pool has them, the rc flag
+typedef std::tuple<size_t, string, string, int32_t> PairText;
+std::vector<PairText> pair_texts(const ReportGroup& g)
+{
+    std::vector<PairText> out;
+    auto piece = [&](int32_t s) { return g.pool.substr(size_t(g.offs[size_t(s)]), size_t(g.offs[size_t(s) + 1] - g.offs[size_t(s)])); };
+    for (size_t x = 0; x < g.pairs.size(); ++x) out.emplace_back(g.pair_row[x], piece(g.pairs[x].query), piece(g.pairs[x].ref), g.pairs[x].ref_revcomp);
+    return out;
+}
+
+template <class T>
+bool same(const std::vector<T>& got, std::initializer_list<T> want)
+{
+    return got == std::vector<T>(want);
+}
+
+}  // namespace
+
+int main()
+{
+    Batch b;
+    b.Cls = {cluster_of("AAAA", "HHHH", -1.0, 1),      cluster_of("ACGTAC", "IIIIII", 9.0, 1), cluster_of("TTTT", "MMMM", 8.0, 1),
+             cluster_of("TTGCA", "JJJJJ", 7.0, -1),    cluster_of("CCCC", "KKK", 6.0, 1),      cluster_of("GGGGGGG", "LLLLLLL", 5.0, 1)};
+    // the rows of clusters.tsv, in the order of the sorted FASTQ: clusters interleaved, one row of the unusable cluster 0 and one
+    // of a cluster the batch does not have
+    const std::vector<Read> reads = {{3, 1, "r3a", "TGCAA", "abcde"}, {0, 1, "r0", "AAA", "hhh"},    {1, 1, "r1a", "ACGTA", "ABCDE"}, {5, -1, "r5", "GGGG", "opqr"},
+                                     {1, -1, "r1b", "GGTAC", "12345"}, {4, 1, "r4", "CCC", "lmn"},    {3, -1, "r3b", "AACN", "wxyz"},  {99, 1, "r9", "ACGT", "IIII"}};
+    std::vector<ReadStatRow> all;
+    for (const Read& r : reads) all.push_back(ReadStatRow{r.cls, r.strand, r.id.data(), r.id.size(), r.seq.data(), r.seq.size(), r.qual.data(), r.qual.size()});
+    const ReportRows rows = keep_report_rows(b, all);
+    EXPECT(same<size_t>(rows.kept, {0, 2, 3, 4, 5, 6}));
+    EXPECT(rows.rows_of[0].empty() && rows.rows_of[2].empty());
+    EXPECT(same<size_t>(rows.rows_of[1], {1, 3}) && same<size_t>(rows.rows_of[3], {0, 5}) && same<size_t>(rows.rows_of[4], {4}) && same<size_t>(rows.rows_of[5], {2}));
+
+    ReportOpts opts;
+    opts.stats = opts.pileup = opts.sites.on = opts.split.on = true;
+    opts.polish_min_depth = opts.split.polish_min_depth = 3;
+
+    // ---- 1. one group, against values written out by hand ----
+    std::vector<ReportGroup> one;
+    plan_report_groups(b, rows, opts, [&](ReportGroup& g) { one.push_back(g); });
+    EXPECT(one.size() == 1);
+    const ReportGroup& g = one[0];
+    //              c1: rep   r1a    rc(r1b)   c3: rep  r3a    rc(r3b)  c4: rep r4   c5: rep     rc(r5)
+    EXPECT(g.pool == "ACGTAC" "ACGTA" "GTACC"     "TTGCA" "TGCAA" "NGTT"    "CCCC" "CCC"   "GGGGGGG" "CCCC");
+    EXPECT(g.quals == "IIIIII" "ABCDE" "54321"    "JJJJJ" "abcde" "zyxw"    "KKK" "lmn"    "LLLLLLL" "rqpo");
+    EXPECT(same<int64_t>(g.offs, {0, 6, 11, 16, 21, 26, 30, 34, 37, 44, 48}));
+    EXPECT(same<int64_t>(g.qoffs, {0, 6, 11, 16, 21, 26, 30, 33, 36, 43, 47}));
+    const int32_t want_pairs[6][3] = {{1, 0, 0}, {2, 0, 0}, {4, 3, 1}, {5, 3, 1}, {7, 6, 0}, {9, 8, 0}};
+    EXPECT(g.pairs.size() == 6);
+    for (size_t x = 0; x < g.pairs.size() && x < 6; ++x)
+        EXPECT(g.pairs[x].query == want_pairs[x][0] && g.pairs[x].ref == want_pairs[x][1] && g.pairs[x].ref_revcomp == want_pairs[x][2] && g.pairs[x].reserved == 0 &&
+               g.pairs[x].e == 0.0);
+    EXPECT(same<size_t>(g.pair_row, {1, 3, 0, 5, 4, 2}));
+    EXPECT(same<int32_t>(g.pair_q, {1, 2, 4, 5, 7, 9}) && same<int32_t>(g.pair_rep_q, {0, 0, 3, 3, 6, 8}));
+    EXPECT(same<int64_t>(g.row_base, {0, 0, 7, 7, 13, 18}) && g.group_rows == 26);
+    EXPECT(same<int32_t>(g.seg_of_pair, {0, 0, 1, 1, 2, 3}) && same<int32_t>(g.seg_reads, {2, 2, 1, 1}));
+    EXPECT((g.group_cls == std::vector<std::pair<size_t, int64_t>>{{1, 0}, {2, -1}, {3, 7}, {4, 13}, {5, 18}}));
+    EXPECT(same<int32_t>(g.group_seg, {0, -1, 1, 2, 3}));
+    const int32_t want_segs[4][2] = {{0, 0}, {3, 1}, {6, 0}, {8, 0}};
+    EXPECT(g.segs.size() == 4);
+    for (size_t s = 0; s < g.segs.size() && s < 4; ++s) EXPECT(g.segs[s].ref == want_segs[s][0] && g.segs[s].ref_revcomp == want_segs[s][1]);
+    // rlen + IOC_PILE_INS_SLOTS * (rlen + 1) for 6, 5, 4, 7 bases: 48 + 41 + 34 + 55
+    EXPECT(polish_capacity(g) == 178 && polish_capacity(g, 2) == 356);
+    // min(10, 2 * rlen + 1) = 10, 10, 9, 10 sites; times 2, 2, 1, 1 reads
+    EXPECT(site_capacity(g, 10).sites == 39 && site_capacity(g, 10).alleles == 59);
+    // without a per-group file nothing but the pool, the pairs and their maps is kept
+    {
+        ReportOpts stats_only;
+        stats_only.stats = true;
+        std::vector<ReportGroup> plain;
+        plan_report_groups(b, rows, stats_only, [&](ReportGroup& x) { plain.push_back(x); });
+        EXPECT(plain.size() == 1 && plain[0].pool == g.pool && plain[0].pair_row == g.pair_row && plain[0].group_cls.empty() && plain[0].segs.empty() &&
+               plain[0].row_base.empty() && plain[0].group_seg.empty());
+    }
+
+    // ---- 2. every cap from the smallest need to the total ----
+    const std::vector<std::pair<size_t, size_t>> need = {{1, 16}, {3, 14}, {4, 7}, {5, 11}};  // cluster, rep + reads
+    const std::vector<PairText> all_pairs = pair_texts(g);
+    for (size_t cap = 7; cap <= 48; ++cap) {
+        // a plain loop over the needs: which clusters each group must hold, the one without rows (2) where it is met
+        std::vector<std::vector<size_t>> want(1);
+        size_t fill = 0;
+        for (const auto& nd : need) {
+            if (nd.first == 3) want.back().push_back(2);
+            if (fill > 0 && fill + nd.second > cap) want.emplace_back(), fill = 0;
+            want.back().push_back(nd.first);
+            fill += nd.second;
+        }
+        std::vector<std::vector<size_t>> got;
+        std::vector<PairText> got_pairs;
+        plan_report_groups(b, rows, opts, [&](ReportGroup& x) {
+            got.emplace_back();
+            for (const auto& gc : x.group_cls) got.back().push_back(gc.first);
+            for (const PairText& p : pair_texts(x)) got_pairs.push_back(p);
+            size_t reads_in = 0;
+            for (int32_t n : x.seg_reads) reads_in += size_t(n);
+            EXPECT(reads_in == x.pairs.size() && x.group_cls.size() == x.group_seg.size() && x.offs.size() == x.qoffs.size());  // whole clusters only
+            EXPECT(x.segs.size() <= 1 || x.pool.size() <= cap);  // (a single cluster may exceed the cap: it cannot be divided)
+        }, cap);
+        EXPECT(got == want);
+        EXPECT(got_pairs == all_pairs);
+    }
+
+    // ---- 3. the record format and the allele characters ----
+    ioc_polish_stats z{};
+    z.n_sub = 1, z.n_del = 2, z.n_ins = 3, z.n_low = 4;
+    EXPECT(polish_record("cluster_7/1", 3, z, " weighted=1", "ACGTAC", "IIII!!", 4) == "@cluster_7/1 reads=3 subs=1 dels=2 ins=3 low=4 weighted=1\nACGT\n+\nIIII\n");
+    string chars;
+    for (int32_t a = -1; a <= 6; ++a) chars += allele_char(0, a);
+    for (int32_t a = -1; a <= 2; ++a) chars += allele_char(IOC_SITE_INS, a);
+    EXPECT(chars == "?ACGTN-?" "?.+?");
+
+    if (faults) {
+        fprintf(stderr, "%d checks failed\n", faults);
+        return 1;
+    }
+    printf("ok\n");
+    return 0;
+}
