@@ -977,6 +977,67 @@ int ioc_dist_merge(ioc_ctx* ctx, const ioc_params* p, const char* table_path, co
                    int64_t out_cap, int32_t* out_cls, int8_t* out_strand, int64_t* out_counts, ioc_cluster_stats* stats,
                    ioc_dist_merge_times* times);
 
+/* ---- Read correction: every read held against the pileup of its cluster ----
+ * What one read looks like once its cluster has corrected it.  Inputs: the read's own planes — base[rlen + 1] as
+ * ioc_host_ops_project writes it and slots[IOC_PILE_INS_SLOTS][rlen + 1], slot-major, as ioc_host_ops_project_ins does — the two
+ * tables of its reference (rlen + 1 rows each), the reference itself (`frame`) and a rule {min_depth >= 1, min_alt >= 1, min_pct in
+ * 1 .. 50, max_run in 0 .. 64}.  All integers.  depth(p) is the depth of ioc_host_pileup_call, D(p) and need(D) = max(min_alt,
+ * ceil(min_pct * D / 100)) are those of ioc_host_pileup_sites; a plane byte neither projection writes counts for nothing; letters
+ * are written by channel, "ACGTN".  A cluster holds a gene, not one molecule, so this is no majority vote: an allele that enough
+ * reads share is kept.
+ *  The base of row p < rlen, where own = base[p] is a channel or IOC_ALLELE_DEL; cnt[] is the row of cols:
+ *   1. depth(p) < min_depth: "low" — the read's own base (nothing for a deletion) at quality 0; counted in n_low.
+ *   2. cnt[own] >= need(depth(p)): "keep".
+ *   3. otherwise w is the winner of ioc_host_pileup_call's base decision (the frame's channel where its count is maximal, else the
+ *      first maximal of A C G T other del): w == own "keep", own a deletion "fill" with w, w a deletion "remove", else "sub" with w.
+ *  The run guard: a maximal run of consecutive rows decided "fill" — rows the read does not cover and rows decided otherwise end
+ *  it — of more than max_run rows turns back to "keep", row by row counted in n_guarded; "remove" likewise, on its own; "sub" never.
+ *  (A read of an isoform that lacks an exon keeps lacking it.)  max_run 0 applies no fill and no remove at all.
+ *  Keep emits the read's own base, sub and fill emit w, remove and a kept deletion emit nothing; an emitted base of channel c has
+ *  quality min(40, 40 * cnt[c] / depth(p)).
+ *  The insertions in front of row p, 0 <= p <= rlen, where the read spans the row (ioc_host_site_alleles), D = D(p):
+ *   D < min_depth: the read's own slot bytes in slot order at quality 0.  Else for slot j = 0 .. 5 in turn, with n_j the sum of
+ *   ins[p].slot[j], cons_j = cons_(j-1) and 2 * n_j > D (the call's prefix rule), letter_j the first maximal channel and own =
+ *   slots[j][p]:  own set and ins[p].slot[j][own - 1] >= need(D): own is emitted;  own set and not supported: letter_j where cons_j
+ *   holds (n_sub), else nothing (n_ins_drop);  own not set, cons_j, and max(D - n_j, 0) < need(D): letter_j (n_ins_add).  Quality:
+ *   min(40, 40 * the slot's count of the emitted channel / D).
+ * A row emits its insertions and then its base, 7 bytes at most.  Qualities are written as 33 + q: they say how much of the
+ * cluster supports the base, not what the sequencer said. */
+typedef struct {
+    int32_t out_len, n_sub, n_fill, n_remove;
+    int32_t n_ins_add, n_ins_drop, n_low, n_guarded;
+} ioc_correct_stats;              /* 32 bytes */
+/* The definition: one read.  Returns the length written to out_seq / out_qual (no terminator); *st (may be NULL) the record.
+ * IOC_ERR_ARG for a rule outside the ranges above, rlen < 0 or a NULL array that is needed, IOC_ERR_CAPACITY for cap below
+ * rlen + IOC_PILE_INS_SLOTS * (rlen + 1); nothing is written on either. */
+int64_t ioc_host_read_correct(const uint8_t* base, const uint8_t* slots, int32_t rlen, const ioc_pileup_col* cols,
+                              const ioc_pileup_ins* ins, const char* frame, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                              int32_t max_run, char* out_seq, char* out_qual, int64_t cap, ioc_correct_stats* st);
+/* Every pair of many segments at once on the device, from host planes and host tables, all of which are uploaded: the segments,
+ * their frames and the tables as for ioc_pileup_call, the pairs and their planes as for ioc_planes_polish.  k_read_correct
+ * (ioc_read_correct.hip) takes a wave per pair, a lane per row: a count pass, a scan, and a write pass into a buffer as large as
+ * the count says.  Pair i's corrected sequence and qualities stand packed at out_off[i] .. out_off[i + 1] of out_seq / out_qual
+ * (out_off: n_pairs + 1 entries), its record in out_stats[i] (may be NULL); each as ioc_host_read_correct defines it.
+ * IOC_ERR_ARG, with nothing written, for a rule outside its ranges, a negative count, length or frame offset, seg_of_pair outside
+ * the segments and a NULL array that is needed; IOC_ERR_CAPACITY, with nothing written, for cap below the sum over the pairs of
+ * their segment's bound (ioc_pileup_call) and for a segment whose bound exceeds 2^31 - 1. */
+int ioc_planes_correct(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                       const ioc_pileup_col* cols, const ioc_pileup_ins* ins, int32_t n_pairs, const int32_t* seg_of_pair,
+                       const uint8_t* base, const uint8_t* slots, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
+                       char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_correct_stats* out_stats);
+/* ioc_align_pairs_polish's alignment and pileup with every pair projected beside it (the base plane and the six slot planes, 8
+ * bytes per row and pair, which count against the checkpoint arena's budget like the tables), and behind the walks k_read_correct
+ * over the tables and the planes where they lie: scores, windows, ratio, out_stats, the segments and out_cols / out_ins (optional)
+ * as from ioc_align_pairs_polish, out_seq / out_qual / out_off / out_correct per PAIR as from ioc_planes_correct, the frame of a
+ * segment being its representative as the pairs were aligned against it.  Every pair is aligned, piled and projected exactly
+ * once.  A pair without an alignment (an empty query or reference) has nothing in the planes and comes back empty.  The stage's
+ * own memory is reserved after the walks.  The refusals of ioc_align_pairs_polish and of ioc_planes_correct; nothing is written. */
+int ioc_align_pairs_correct(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                            int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                            int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt,
+                            int32_t min_pct, int32_t max_run, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                            ioc_correct_stats* out_correct, ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins);
+
 #ifdef __cplusplus
 }
 #endif

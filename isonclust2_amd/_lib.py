@@ -105,6 +105,10 @@ class PolishStats(C.Structure):  # ioc_polish_stats (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("out_len", "n_sub", "n_del", "n_ins", "n_low")] + [("reserved", C.c_int32 * 3)]
 
 
+class CorrectStats(C.Structure):  # ioc_correct_stats (32 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("out_len", "n_sub", "n_fill", "n_remove", "n_ins_add", "n_ins_drop", "n_low", "n_guarded")]
+
+
 class PileSite(C.Structure):  # ioc_pile_site (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("row", "kind", "major", "minor")] + [(n, C.c_uint32) for n in ("depth", "n_major", "n_minor", "reserved")]
 
@@ -164,6 +168,7 @@ SYMBOLS = [
     "ioc_dist_unique_id", "ioc_dist_init", "ioc_dist_shutdown", "ioc_dist_info", "ioc_dist_allgather_device",
     "ioc_dist_allgatherv_device", "ioc_dist_allgather_i64", "ioc_dist_allgatherv_host", "ioc_dist_allreduce_max",
     "ioc_dist_barrier", "ioc_dist_merge", "ioc_set_shard", "ioc_shard_exchanges", "ioc_shard_aligned_pairs", "ioc_dist_exchange", "ioc_dist_set_shard", "ioc_align_set_verdict_threshold",
+    "ioc_host_read_correct", "ioc_planes_correct", "ioc_align_pairs_correct",
 ]
 
 _lib = None
@@ -307,6 +312,13 @@ def load():
     L.ioc_planes_polish.argtypes = [vp, i32, pi32, C.c_char_p, pi64, i32, pi32, C.c_void_p, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, i64, pi64,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_split_polish.argtypes = L.ioc_align_pairs_split.argtypes + [i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_host_read_correct.argtypes = [C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_char_p, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64,
+                                        C.POINTER(CorrectStats)]
+    L.ioc_host_read_correct.restype = C.c_int64
+    L.ioc_planes_correct.argtypes = [vp, i32, pi32, C.c_char_p, pi64, C.c_void_p, C.c_void_p, i32, pi32, C.c_void_p, C.c_void_p, i32, i32, i32, i32,
+                                     C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p]
+    L.ioc_align_pairs_correct.argtypes = [vp, i32, C.POINTER(AlnPair), i32, i32, i32, i32, pi32, pi64, pd, C.c_void_p, i32, C.POINTER(PolishSeg), pi32,
+                                          i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

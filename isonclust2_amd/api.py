@@ -247,6 +247,32 @@ def planes_pile(base, slots, cols=None, ins=None):
     return cols, ins
 
 
+# ioc_correct_stats as a numpy record
+CORRECT_STATS_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.CorrectStats._fields_])
+CORRECT_STATS_FIELDS = tuple(n for n, _ in _lib.CorrectStats._fields_)
+
+
+def read_correct(base, slots, cols, ins, frame, min_depth=3, min_alt=3, min_pct=25, max_run=10, cap=None):
+    """ioc_host_read_correct: one read corrected against the pileup of its reference — `base` and `slots` the read's planes as
+    ops_project and ops_project_ins give them (len(frame) + 1 bytes, PILE_INS_SLOTS x (len(frame) + 1)), `cols` and `ins` the
+    reference's tables (len(frame) + 1 rows each), `frame` the reference (bytes).  A base that at least need(depth) = max(min_alt,
+    ceil(min_pct * depth / 100)) reads share is kept, anything else goes to the pileup's winner; runs of more than max_run filled or
+    removed rows are left as the read has them.  Returns (sequence, qualities, stats): bytes, bytes and a dict of
+    CORRECT_STATS_FIELDS.  IocError for a rule outside its ranges and for a `cap` (default: the bound) below the bound."""
+    rlen = len(frame)
+    cols, ins = _tables(cols, ins, rlen + 1)
+    base, slots = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(slots, np.uint8)
+    if base.shape != (rlen + 1,) or slots.shape != (_lib.PILE_INS_SLOTS, rlen + 1):
+        raise ValueError("base must hold len(frame) + 1 bytes and slots PILE_INS_SLOTS x (len(frame) + 1)")
+    cap = pileup_call_bound(rlen) if cap is None else int(cap)
+    seq, qual, st = C.create_string_buffer(max(cap, 1)), C.create_string_buffer(max(cap, 1)), _lib.CorrectStats()
+    n = _lib.load().ioc_host_read_correct(base.ctypes.data, slots.ctypes.data, rlen, cols.ctypes.data, ins.ctypes.data, bytes(frame), int(min_depth),
+                                          int(min_alt), int(min_pct), int(max_run), seq, qual, cap, C.byref(st))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_read_correct")
+    return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in CORRECT_STATS_FIELDS}
+
+
 def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
     """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
     returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
@@ -793,6 +819,66 @@ class Context:
                                            pol.ctypes.data if ns else None, gcols.ctypes.data if tables and n_rows else None,
                                            gins.ctypes.data if tables and n_rows else None))
         return self._gpolish_out(ns, rlen, seq, qual, off, pol, gcols, gins, tables)
+
+    def planes_correct(self, frames, cols, ins, seg_of_pair, base, slots, min_depth=3, min_alt=3, min_pct=25, max_run=10, cap=None):
+        """ioc_planes_correct: every read of many segments corrected on the device, from host planes and host tables — `frames` a
+        list of bytes per segment, `cols` / `ins` the segments' tables one behind the other (as for pileup_call), seg_of_pair per pair,
+        base / slots lists per pair of what ops_project and ops_project_ins give for that pair.  Returns ([sequence per pair],
+        [qualities per pair], stats), stats an array of CORRECT_STATS_DTYPE; each pair as read_correct defines it."""
+        ns, n = len(frames), len(base)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        n_rows = int(rlen.sum()) + ns
+        cols, ins = _tables(cols, ins, n_rows)
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,) or len(slots) != n:
+            raise ValueError("seg_of_pair, base and slots must hold one entry per pair")
+        rows = [int(rlen[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (rows[i],) or np.shape(slots[i]) != (_lib.PILE_INS_SLOTS, rows[i]):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        P = sum(rows)
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        fs = np.ascontiguousarray(np.concatenate([np.zeros((_lib.PILE_INS_SLOTS, 0), np.uint8)] + [np.asarray(x, np.uint8) for x in slots], axis=1))
+        f_off = np.zeros(ns + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        bound = sum(pileup_call_bound(rlen[g]) for g in sop if 0 <= g < ns)
+        cap = bound if cap is None else int(cap)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, st = np.zeros(n + 1, np.int64), np.zeros(n, CORRECT_STATS_DTYPE)
+        self._chk(self.L.ioc_planes_correct(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+                                            cols.ctypes.data if n_rows else None, ins.ctypes.data if n_rows else None, n, _p(sop, C.c_int32) if n else None,
+                                            fb.ctypes.data if P else None, fs.ctypes.data if P else None, int(min_depth), int(min_alt), int(min_pct),
+                                            int(max_run), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64), st.ctypes.data if n else None))
+        return ([seq[off[i]:off[i + 1]].tobytes() for i in range(n)], [qual[off[i]:off[i + 1]].tobytes() for i in range(n)], st)
+
+    def align_pairs_correct(self, pairs, k, segs, seg_of_pair, min_depth=3, min_alt=3, min_pct=25, max_run=10, stats=False, tables=False, cap=None,
+                            match=2, mismatch=-2, gap_extend=1):
+        """ioc_align_pairs_correct: align_pairs, both pileup tables, every pair's planes and the correction of every pair's read
+        against its segment's pileup, all on the device, every pair aligned once — segs / seg_of_pair as for align_pairs_polish.
+        Returns a dict: score, windows, ratio, `seq` and `qual` (lists of bytes per PAIR: the corrected aligned part of the query),
+        `correct` (CORRECT_STATS_DTYPE per pair), with stats=True `stats` (ALN_STATS_DTYPE per pair), with tables=True `cols`, `ins`
+        and `row0` as align_pairs_polish returns them.  Each pair as read_correct defines it on the pair's projections."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        bound = sum(pileup_call_bound(rlen[g]) for g in sop if 0 <= g < ns)
+        cap = bound if cap is None else int(cap)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, cor = np.zeros(n + 1, np.int64), np.zeros(n, CORRECT_STATS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols, ins = (np.zeros(n_rows, PILEUP_DTYPE), np.zeros(n_rows, PILEUP_INS_DTYPE)) if tables else (None, None)
+        self._chk(self.L.ioc_align_pairs_correct(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+                                                 _p(sop, C.c_int32), int(min_depth), int(min_alt), int(min_pct), int(max_run), seq.ctypes.data,
+                                                 qual.ctypes.data, cap, _p(off, C.c_int64), cor.ctypes.data if n else None,
+                                                 cols.ctypes.data if tables and n_rows else None, ins.ctypes.data if tables and n_rows else None))
+        out = {"score": score, "windows": win, "ratio": ratio, "correct": cor,
+               "seq": [seq[off[i]:off[i + 1]].tobytes() for i in range(n)], "qual": [qual[off[i]:off[i + 1]].tobytes() for i in range(n)]}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out.update(cols=cols, ins=ins, row0=self._row0(rlen))
+        return out
 
     @staticmethod
     def _gpolish_out(ns, rlen, seq, qual, off, pol, gcols, gins, tables):

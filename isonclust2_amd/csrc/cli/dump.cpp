@@ -30,6 +30,7 @@ struct DumpOptions {
     // --split: cluster_split.tsv and read_split.tsv, the reads of a cluster in two groups by its linked sites
     // --split-polish: cluster_split_polished.fq, the consensus of each group of every cluster that has a split
     // --split-polish-min-depth: positions covered by fewer reads of the group keep the representative's base
+    // --correct: corrected_reads.fq, every read corrected against the pileup of its cluster; --correct-*: its thresholds
     ReportOpts reports;
 };
 
@@ -49,7 +50,8 @@ void print_dump_help()
     cerr << "isONclust2-hip dump -i sorted_reads_idx.cer -o outdir [--read-stats] [--pileup] [--polish [--polish-min-depth N] [--polish-weighted]]" << endl
          << "                    [--sites [--sites-min-depth N] [--sites-min-alt N] [--sites-min-pct P] [--sites-max N]]" << endl
          << "                    [--split [--split-min-link N] [--split-min-margin N] [--split-rounds N]" << endl
-         << "                     [--split-polish [--split-polish-min-depth N]]] final.cer" << endl
+         << "                     [--split-polish [--split-polish-min-depth N]]]" << endl
+         << "                    [--correct [--correct-min-depth N] [--correct-min-alt N] [--correct-min-pct P] [--correct-max-run N]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -77,7 +79,22 @@ void print_dump_help()
          << "  --split-polish         with --split: also write outdir/cluster_split_polished.fq, for every cluster that has a split the" << endl
          << "                 consensus of each group that has reads (records <cluster>/0 and <cluster>/1), called from the alignments" << endl
          << "                 of --split: no read is aligned again" << endl
-         << "  --split-polish-min-depth N   positions covered by fewer than N reads of the group keep the representative's base (default 3)" << endl;
+         << "  --split-polish-min-depth N   positions covered by fewer than N reads of the group keep the representative's base (default 3)" << endl
+         << "  --correct      also write outdir/corrected_reads.fq: every read of clusters.tsv with the part that aligns against its cluster's" << endl
+         << "                 representative corrected by the cluster's reads (GPU): a base, a deletion or an inserted base that enough reads" << endl
+         << "                 share is kept (a cluster holds a gene: haplotypes and isoforms keep what is theirs), anything else becomes what" << endl
+         << "                 most reads say; the unaligned ends stay as they are; qualities: 40 x the share of the cluster's reads that" << endl
+         << "                 support the base, '!' where too few reads cover it; header: cluster, and how many positions were substituted," << endl
+         << "                 filled, removed, inserted, dropped, left for low depth, or held back by --correct-max-run.  A read whose" << endl
+         << "                 alignment inserts more than 6 bases in a row is written as it is, with uncorrected=long_insertion." << endl
+         << "                 The correction is a call of its own: beside --polish, --sites or --split the reads are aligned once more" << endl
+         << "                 for it (beside --read-stats and --pileup alone they are aligned once)" << endl
+         << "  --correct-min-depth N  positions covered by fewer than N reads are left as the read has them (default 3)" << endl
+         << "  --correct-min-alt N    what a read says is kept when at least N reads say it (default 3) ..." << endl
+         << "  --correct-min-pct P    ... and at least P percent of the depth, 1 .. 50 (default 25)" << endl
+         << "  --correct-max-run N    a run of more than N deleted positions in a row is not filled in, and one of more than N bases is not" << endl
+         << "                 removed, 0 .. 64 (default 10: a choice — sequencing indels are short, a missing exon is not — that was not" << endl
+         << "                 measured on real data)" << endl;
 }
 
 DumpOptions parse_dump_options(int argc, char** argv)
@@ -91,7 +108,10 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"sites-min-pct", required_argument, 0, 1008}, {"sites-max", required_argument, 0, 1009},
                                        {"split", no_argument, 0, 1010}, {"split-min-link", required_argument, 0, 1011},
                                        {"split-min-margin", required_argument, 0, 1012}, {"split-rounds", required_argument, 0, 1013},
-                                       {"split-polish", no_argument, 0, 1014}, {"split-polish-min-depth", required_argument, 0, 1015}, {0, 0, 0, 0}};
+                                       {"split-polish", no_argument, 0, 1014}, {"split-polish-min-depth", required_argument, 0, 1015},
+                                       {"correct", no_argument, 0, 1016}, {"correct-min-depth", required_argument, 0, 1017},
+                                       {"correct-min-alt", required_argument, 0, 1018}, {"correct-min-pct", required_argument, 0, 1019},
+                                       {"correct-max-run", required_argument, 0, 1020}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false;
@@ -118,6 +138,11 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1013: r.split.rounds = number("--split-rounds", optarg, 0, 64); break;
             case 1014: split_polish = true; break;
             case 1015: split_polish_min_depth = number("--split-polish-min-depth", optarg, 1, INT32_MAX); break;
+            case 1016: r.correct.on = true; break;
+            case 1017: r.correct.min_depth = number("--correct-min-depth", optarg, 1, INT32_MAX); break;
+            case 1018: r.correct.min_alt = number("--correct-min-alt", optarg, 1, INT32_MAX); break;
+            case 1019: r.correct.min_pct = number("--correct-min-pct", optarg, 1, 50); break;
+            case 1020: r.correct.max_run = number("--correct-max-run", optarg, 0, 64); break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -302,7 +327,8 @@ int main_dump(int argc, char** argv)
         write_read_reports(b, d.outdir, stat_rows, reports);
         const string names = string(reports.stats ? "read_stats.tsv, " : "") + (reports.pileup ? "cluster_pileup.tsv, " : "") +
                              (reports.polish() ? "cluster_polished.fq, " : "") + (reports.sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") +
-                             (reports.split.on ? "cluster_split.tsv, read_split.tsv, " : "") + (reports.group_polish() ? "cluster_split_polished.fq, " : "");
+                             (reports.split.on ? "cluster_split.tsv, read_split.tsv, " : "") + (reports.group_polish() ? "cluster_split_polished.fq, " : "") +
+                             (reports.correct.on ? "corrected_reads.fq, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

@@ -108,6 +108,16 @@ int64_t polish_capacity(const ReportGroup& g, int groups)
     return cap;
 }
 
+int64_t correct_capacity(const ReportGroup& g)
+{
+    int64_t cap = 0;
+    for (size_t x = 0; x < g.pairs.size(); ++x) {
+        const int64_t m = ref_len(g, g.segs[size_t(g.seg_of_pair[x])]);
+        cap += m + IOC_PILE_INS_SLOTS * (m + 1);
+    }
+    return cap;
+}
+
 SiteCapacity site_capacity(const ReportGroup& g, int max_sites)
 {
     SiteCapacity cap;
@@ -130,5 +140,22 @@ string polish_record(const string& name, int32_t reads, const ioc_polish_stats& 
     string text = "@" + name + " reads=" + std::to_string(reads) + " subs=" + std::to_string(z.n_sub) + " dels=" + std::to_string(z.n_del) +
                   " ins=" + std::to_string(z.n_ins) + " low=" + std::to_string(z.n_low) + tail + "\n";
     text.append(seq, len).append("\n+\n").append(qual, len).append("\n");
+    return text;
+}
+
+string corrected_record(const char* id, size_t id_len, unsigned cls, const char* read, size_t read_len, const char* qual, size_t qual_len,
+                        const ioc_aln_stats& a, const ioc_correct_stats& z, const char* cseq, const char* cqual, size_t clen)
+{
+    string own_qual(qual, std::min(qual_len, read_len));
+    own_qual.resize(read_len, '!');
+    const bool as_it_is = a.longest_ins > IOC_PILE_INS_SLOTS;
+    const ioc_correct_stats k = as_it_is ? ioc_correct_stats{} : z;
+    string text = "@" + string(id, id_len) + " cluster=" + std::to_string(cls) + " subs=" + std::to_string(k.n_sub) + " fills=" + std::to_string(k.n_fill) +
+                  " removes=" + std::to_string(k.n_remove) + " ins_add=" + std::to_string(k.n_ins_add) + " ins_drop=" + std::to_string(k.n_ins_drop) +
+                  " low=" + std::to_string(k.n_low) + " guarded=" + std::to_string(k.n_guarded) + (as_it_is ? " uncorrected=long_insertion" : "") + "\n";
+    if (as_it_is) return text.append(read, read_len).append("\n+\n").append(own_qual).append("\n");
+    const size_t lead = std::min(size_t(std::max(a.lead_i, 0)), read_len), trail = std::min(size_t(std::max(a.trail_i, 0)), read_len - lead);
+    text.append(read, lead).append(cseq, clen).append(read + read_len - trail, trail).append("\n+\n");
+    text.append(own_qual, 0, lead).append(cqual, clen).append(own_qual, read_len - trail, trail).append("\n");
     return text;
 }

@@ -44,6 +44,13 @@
 // named after the cluster's record in cluster_cons.fq with "/0" or "/1" appended: "@cluster_<id>/<group> reads=<the group's reads>
 // subs= dels= ins= low=", in the frame of that record; positions covered by fewer than --split-polish-min-depth reads of the
 // group keep the representative's base with quality '!'.  The other report files are what they are without the option.
+//
+// dump --correct: <outdir>/corrected_reads.fq (ioc_align_pairs_correct: the alignment and both tables of --polish with every read
+// projected beside them, and every read corrected against its cluster's pileup where all of that lies; a call of its own, which
+// takes the statistics and the first table when no call before it has).  One record per row read_stats.tsv has, in that order: the
+// read as cluster_fastq/<id>.fq has it with its aligned part corrected, the ends the alignment leaves free as they are (corrected_record,
+// report_plan.cpp); a read whose alignment inserts more than six bases in a row is written as it is and marked.  The other report
+// files are what they are without the option.
 #include "reports.hpp"
 
 #include <cstdio>
@@ -83,6 +90,10 @@ struct GroupResult {
     std::vector<ioc_split_seg> split_seg;
     PolishedSet polished;        // (--polish) per segment
     PolishedSet group_polished;  // (--split-polish) per segment and side: 2 * g + h
+    string cseq, cqual;          // (--correct) pair x's corrected bytes at [coff[x], coff[x + 1]), its record and the statistics of its alignment
+    std::vector<int64_t> coff;
+    std::vector<ioc_correct_stats> cstats;
+    std::vector<ioc_aln_stats> caln;
 };
 
 // a row of the three per-read tables
@@ -94,10 +105,15 @@ struct RowResult {
     string alleles;                  // (--sites) one character per kept site of the read's cluster
     uint8_t group = IOC_SPLIT_NONE;  // (--split) the read's side, and ...
     int32_t vote = 0;                // ... its vote
+    // (--correct) the read's record of corrected_reads.fq.  The file follows clusters.tsv, whose rows are in the order of the sorted
+    // FASTQ and so interleave the clusters, while the groups come cluster by cluster: the records wait here until the last group
+    // is done, the whole corrected read set in host memory (the other per-read tables keep a few words a row)
+    string corrected;
 };
 
-// The one place that chooses a library call.  --sites and / or --split come first; --polish is a second call, which takes the
-// statistics and the first table only when the first call did not produce them; otherwise the pileup; otherwise the statistics.
+// The one place that chooses a library call.  --sites and / or --split come first; --polish and --correct are calls of their own,
+// each of which takes the statistics and the first table only when no call before it produced them; otherwise the pileup;
+// otherwise the statistics.
 void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupResult& r)
 {
     const size_t nq = g.qoffs.size() - 1, np = g.pairs.size(), ns = g.segs.size();
@@ -169,16 +185,32 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
                                             &pol.seq[0], &pol.qual[0], cap, pol.off.data(), pol.stats.data(), cols_out, nullptr),
                   "polished consensus");
         }
-    } else if (!have_first && o.pileup) {
+        have_first = true;
+    }
+    if (o.correct.on) {
+        const CorrectOpt& co = o.correct;
+        const int64_t cap = correct_capacity(g);
+        r.cseq.assign(size_t(cap), '\0'), r.cqual.assign(size_t(cap), '\0');
+        r.coff.assign(np + 1, 0), r.cstats.assign(np, ioc_correct_stats{}), r.caln.assign(np, ioc_aln_stats{});
+        if (o.pileup && !have_first) r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
+        check(c, ioc_align_pairs_correct(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, r.caln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(), co.min_depth,
+                                         co.min_alt, co.min_pct, co.max_run, &r.cseq[0], &r.cqual[0], cap, r.coff.data(), r.cstats.data(),
+                                         o.pileup && !have_first ? r.cols.data() : nullptr, nullptr),
+              "read correction");
+        if (o.stats && !have_first) r.stats = r.caln;
+        have_first = true;
+    }
+    if (have_first) return;
+    if (o.pileup) {
         r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
         check(c, ioc_align_pairs_pileup(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, st, g.row_base.data(), g.group_rows, r.cols.data()), "alignment pileup");
-    } else if (!have_first) {
+    } else {
         check(c, ioc_align_pairs_stats(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, r.stats.data()), "alignment statistics");
     }
 }
 
 // a group's results into the rows of the per-read tables
-void scatter_to_rows(const ReportOpts& o, const ReportGroup& g, const GroupResult& r, std::vector<RowResult>& res)
+void scatter_to_rows(const ReportOpts& o, const ReportRows& rows, const ReportGroup& g, const GroupResult& r, std::vector<RowResult>& res)
 {
     for (size_t x = 0; x < g.pairs.size(); ++x) {
         RowResult& row = res[g.pair_row[x]];
@@ -190,6 +222,12 @@ void scatter_to_rows(const ReportOpts& o, const ReportGroup& g, const GroupResul
             for (int64_t a = r.allele_off[x]; a < r.allele_off[x + 1]; ++a)
                 row.alleles += allele_char(r.sites[size_t(s0 + a - r.allele_off[x])].kind, r.alleles[size_t(a)]);
             if (row.alleles.empty()) row.alleles = "*";
+        }
+        if (o.correct.on) {
+            const ReadStatRow& rd = rows.row(g.pair_row[x]);
+            const size_t q0 = size_t(g.offs[size_t(g.pairs[x].query)]), l0 = size_t(g.qoffs[size_t(g.pair_q[x])]), l1 = size_t(g.qoffs[size_t(g.pair_q[x]) + 1]);
+            row.corrected = corrected_record(rd.id, rd.id_len, rd.cls, g.pool.data() + q0, rd.seq_len, g.quals.data() + l0, l1 - l0, r.caln[x], r.cstats[x],
+                                             r.cseq.data() + r.coff[x], r.cqual.data() + r.coff[x], size_t(r.coff[x + 1] - r.coff[x]));
         }
     }
 }
@@ -351,6 +389,13 @@ void write_read_split(const string& outdir, const ReportRows& rows, const std::v
     }
 }
 
+void write_corrected_reads(const string& outdir, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/corrected_reads.fq", out);
+    for (const RowResult& r : res) out.write(r.corrected.data(), std::streamsize(r.corrected.size()));
+}
+
 void write_read_stats(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
 {
     std::ofstream out;
@@ -384,7 +429,7 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
     plan_report_groups(b, rows, opts, [&](ReportGroup& g) {
         if (!g.pairs.empty()) {
             align_group(c, k, opts, g, result);
-            scatter_to_rows(opts, g, result, res);
+            scatter_to_rows(opts, rows, g, result, res);
         }
         if (opts.groups()) files.write(b, opts, g, result);
     });
@@ -392,4 +437,5 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
     if (opts.sites.on) write_read_alleles(outdir, rows, res);
     if (opts.split.on) write_read_split(outdir, rows, res);
     if (opts.stats) write_read_stats(outdir, rows, res);
+    if (opts.correct.on) write_corrected_reads(outdir, res);
 }

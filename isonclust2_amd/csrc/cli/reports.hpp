@@ -1,4 +1,4 @@
-// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish): every read of clusters.tsv
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct): every read of clusters.tsv
 // aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
 // formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
 #ifndef ISONCLUST2_CLI_REPORTS_HPP
@@ -21,6 +21,10 @@ struct SplitOpt {
     int min_link = 3, min_margin = 1, rounds = 2;
     int polish_min_depth = 0;  // --split-polish: > 0, the depth below which a group's call keeps the representative's base
 };
+struct CorrectOpt {  // --correct: the thresholds of ioc_host_read_correct
+    bool on = false;
+    int min_depth = 3, min_alt = 3, min_pct = 25, max_run = 10;
+};
 struct ReportOpts {
     bool stats = false;        // --read-stats
     bool pileup = false;       // --pileup
@@ -28,9 +32,10 @@ struct ReportOpts {
     bool polish_weighted = false;
     SitesOpt sites;
     SplitOpt split;
+    CorrectOpt correct;
     bool polish() const { return polish_min_depth > 0; }
     bool group_polish() const { return split.on && split.polish_min_depth > 0; }
-    bool segs() const { return polish() || sites.on || split.on; }  // the calls that take the clusters as segments
+    bool segs() const { return polish() || sites.on || split.on || correct.on; }  // the calls that take the clusters as segments
     bool groups() const { return pileup || segs(); }                // something is written per group
     bool any() const { return stats || groups(); }
 };
@@ -94,9 +99,20 @@ struct SiteCapacity {
 };
 SiteCapacity site_capacity(const ReportGroup& g, int max_sites);
 
+// what the correction of every read of a group may return at most: every pair's segment's bound
+int64_t correct_capacity(const ReportGroup& g);
+
 char allele_char(int32_t kind, int32_t a);
 // "@<name> reads= subs= dels= ins= low=<tail>", the sequence, "+", the qualities
 std::string polish_record(const std::string& name, int32_t reads, const ioc_polish_stats& z, const char* tail, const char* seq, const char* qual, size_t len);
+// A record of corrected_reads.fq: "@<id> cluster=<c> subs= fills= removes= ins_add= ins_drop= low= guarded=", then the read's own
+// first lead_i bases with their own qualities, the corrected aligned part (cseq / cqual, clen bytes) and its last trail_i bases
+// likewise, "+", the qualities.  read / qual: the read as it was aligned (as cluster_fastq/<id>.fq has it), read_len bases; a
+// quality line of another length is cut or filled up with '!'.  An alignment whose longest insertion exceeds IOC_PILE_INS_SLOTS:
+// the read as it is, " uncorrected=long_insertion" and counters of 0 (the planes hold six inserted bases a run: the correction
+// would cut it).
+std::string corrected_record(const char* id, size_t id_len, unsigned cls, const char* read, size_t read_len, const char* qual, size_t qual_len,
+                             const ioc_aln_stats& a, const ioc_correct_stats& z, const char* cseq, const char* cqual, size_t clen);
 
 void write_read_reports(const cer::Batch& b, const std::string& outdir, const std::vector<ReadStatRow>& rows, const ReportOpts& opts);
 

@@ -20,6 +20,7 @@
 #include "ioc_align_sink.h"
 #include "ioc_pile_call.h"
 #include "ioc_pile_sites.h"
+#include "ioc_read_correct.h"
 #include "ioc_site_split.h"
 
 namespace {
@@ -576,6 +577,53 @@ int ioc_host_alleles_split(const ioc_pile_site* sites, int32_t n_sites, const ui
     }
     *out_seg = rec;
     return IOC_OK;
+}
+
+// One read corrected against the tables of its reference (isonclust2_hip.h has the rules; read_base_decide and read_correct_row,
+// ioc_read_correct.h, decide and form a row for this function and for k_read_correct alike).  The plain loop: the rows are decided,
+// the runs of "fill" and of "remove" are measured end to end — k_read_correct and tools/read_correct_check.cpp do the same with
+// read_run_exceeds over masks of 64 rows — and the rows are written.
+int64_t ioc_host_read_correct(const uint8_t* base, const uint8_t* slots, int32_t rlen, const ioc_pileup_col* cols, const ioc_pileup_ins* ins,
+                              const char* frame, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run, char* out_seq, char* out_qual,
+                              int64_t cap, ioc_correct_stats* st)
+{
+    const ReadRule rule{min_depth, min_alt, min_pct, max_run};
+    if (!rule.ok() || rlen < 0 || !base || !slots || !cols || !ins || (rlen > 0 && !frame)) return IOC_ERR_ARG;
+    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1);
+    if (cap < bound) return IOC_ERR_CAPACITY;
+    if (!out_seq || !out_qual) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1;
+    std::vector<uint32_t> dec(rows, uint32_t(READ_NONE));
+    std::vector<uint8_t> guarded(rows, 0);
+    for (int32_t p = 0; p < rlen; ++p) dec[size_t(p)] = read_base_decide(cols[p], base[p], uint8_t(frame[p]), rule);
+    for (size_t a = 0; a < size_t(rlen);) {
+        const uint32_t kind = read_kind(dec[a]);
+        size_t b = a + 1;
+        if (kind == READ_FILL || kind == READ_REMOVE) {
+            while (b < size_t(rlen) && read_kind(dec[b]) == kind) ++b;
+            if (b - a > size_t(max_run)) std::fill(guarded.begin() + int64_t(a), guarded.begin() + int64_t(b), uint8_t(1));
+        }
+        a = b;
+    }
+    ioc_correct_stats s{};
+    int64_t at = 0;
+    for (int32_t p = 0; p <= rlen; ++p) {
+        const int32_t pi = p < rlen ? p : rlen - 1;  // the row the insertions in front of p are held against, and the span's
+        const unsigned long long D = pi >= 0 ? pile_depth(cols[pi]) : 0ull;
+        const bool spans = pi >= 0 && read_covers(base[pi]);
+        unsigned long long own_slots = 0;
+        for (size_t j = 0; j < size_t(IOC_PILE_INS_SLOTS); ++j) own_slots |= (unsigned long long)slots[j * rows + size_t(p)] << (8u * j);
+        const ReadRowOut row = read_correct_row(cols[p], ins[p], D, spans, base[p], own_slots, dec[size_t(p)], guarded[size_t(p)] != 0, rule);
+        for (uint32_t x = 0; x < row.n; ++x) {
+            out_seq[at] = char((row.seq >> (8u * x)) & 0xFFu);
+            out_qual[at++] = char((row.qual >> (8u * x)) & 0xFFu);
+        }
+        s.n_sub += int32_t(row.n_sub), s.n_fill += int32_t(row.n_fill), s.n_remove += int32_t(row.n_remove), s.n_ins_add += int32_t(row.n_ins_add);
+        s.n_ins_drop += int32_t(row.n_ins_drop), s.n_low += int32_t(row.n_low), s.n_guarded += int32_t(row.n_guarded);
+    }
+    s.out_len = int32_t(at);
+    if (st) *st = s;
+    return at;
 }
 
 // setGapOpen, src/cluster.cpp:425-440

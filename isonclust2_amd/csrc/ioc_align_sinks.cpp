@@ -2,8 +2,8 @@
 // top of them: each describes where the walks' operation bytes go (AlnSink, ioc_align_sink.h) and runs ioc_align_pairs_sink
 // (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.  An entry point checks its arguments, plans its
 // segments and pairs on the host (SinkPlan, ioc_sink_plan.h) and runs device stages in a row (SinkRun): pile -> sites -> alleles ->
-// [split] -> [group pile -> call] -> copy-out for the alleles family, pile -> call -> copy-out for the polish family, upload -> the same
-// stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
+// [split] -> [group pile -> call] -> copy-out for the alleles family, pile -> call -> copy-out for the polish family, pile -> correct ->
+// copy-out for the read correction, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +15,7 @@
 #include "ioc_align_sink.h"
 #include "ioc_internal.h"
 #include "ioc_plane_pile.h"
+#include "ioc_read_correct.h"
 
 namespace {
 struct AlnCall {  // what every aligning entry point passes on
@@ -52,6 +53,14 @@ struct GroupPolish {  // the call of both groups of every segment of a split, an
     CallOut call;
     ioc_pileup_col* out_gcols;
     ioc_pileup_ins* out_gins;
+};
+struct CorrectOut {  // the rule of a read correction and where it leaves every pair's bytes (cap: what seq and qual hold each)
+    ReadRule rule;
+    char *seq, *qual;
+    int64_t cap;
+    int64_t* off;
+    ioc_correct_stats* stats;
+    bool ok() const { return rule.ok() && off && cap >= 0; }
 };
 // what a call refuses once its bound is known: IOC_OK, or the status with the message set
 int call_room_ok(ioc_ctx* c, const std::string& who, const CallOut& o, int64_t bound)
@@ -132,6 +141,8 @@ struct SinkRun {
     int split(const SplitCall& sp, size_t n, size_t np, const int32_t* seg_of_pair, const int64_t* site_off, const int64_t* allele_off, const ioc_pile_site* sites,
               const uint8_t* alleles, bool on_device, Planes& d);
     int group_pile(const SinkPlan& p, const int32_t* seg_of_pair, const Planes& host, Planes dev, GroupPiled& d);
+    int correct(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* d_frames, uint64_t frame_bytes, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
+                const Planes& host, Planes dev, const CorrectOut& o);
 };
 
 // Pile and project.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it (ins), or a_pile_w as [wcols][wins] (weighted)
@@ -336,6 +347,56 @@ int SinkRun::group_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const Pl
                                pd.mem_off, pd.members, uint32_t(np), pd.group, reinterpret_cast<const uint64_t*>(p + o_plane), pd.base, pd.slots,
                                uint64_t(P), d.cols, d.ins, uint64_t(n_rows)));
     return end();
+}
+
+// k_read_correct over the plan's pairs: tables and frames lie on the device, the planes either do (dev) or are the host's and
+// uploaded.  a_correct holds [segments][seg_of_pair][plane offsets][pair_len][out_off][records] and, uploaded, [base plane][slot
+// planes].  The count pass and the scan run first; the one word that comes back then, out_off[pairs], is what a_call is reserved
+// for — [sequence][qualities], as many bytes as were counted, not as the bound allows — and the write pass fills it.
+int SinkRun::correct(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_t* d_frames, uint64_t frame_bytes, const ioc_pileup_col* d_cols,
+                     const ioc_pileup_ins* d_ins, const Planes& ph, Planes pd, const CorrectOut& o)
+{
+    const size_t n = pn.segs.size(), np = pn.plane.size(), P = size_t(pn.plane_bytes);
+    o.off[0] = 0;
+    if (np == 0) return IOC_OK;
+    Arena l;
+    const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_plane = l.take(np * 8), o_len = l.take(np * 8), o_off = l.take((np + 1) * 8),
+                 o_st = l.take(np * sizeof(ioc_correct_stats)), o_base = l.take(pd.base ? 0 : P), o_slots = l.take(pd.slots ? 0 : size_t(IOC_PILE_INS_SLOTS) * P);
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_correct, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_correct.p);
+    auto up = [&](size_t at, const void* src, size_t b) { return b ? hipMemcpyAsync(p + at, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(o_seg, pn.segs.data(), n * sizeof(IocPileSeg)));
+    IOC_CHK(c, up(o_sop, seg_of_pair, np * 4));
+    IOC_CHK(c, up(o_plane, pn.plane.data(), np * 8));
+    if (!pd.base) IOC_CHK(c, up(o_base, ph.base, P));
+    if (!pd.slots) IOC_CHK(c, up(o_slots, ph.slots, size_t(IOC_PILE_INS_SLOTS) * P));
+    if (!pd.base) pd.base = p + o_base;  // (what does not lie on the device yet was uploaded)
+    if (!pd.slots) pd.slots = p + o_slots;
+    const IocReadCorrectDev v{reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop),
+                              reinterpret_cast<const uint64_t*>(p + o_plane), d_cols, d_ins, uint64_t(pn.n_rows), d_frames, frame_bytes, pd.base, pd.slots,
+                              uint64_t(P), reinterpret_cast<int64_t*>(p + o_len), reinterpret_cast<ioc_correct_stats*>(p + o_st)};
+    const ReadRule& k = o.rule;
+    IOC_TRY(begin(t.ms_correct));
+    IOC_CHK(c, iock_read_correct_count(c->stream, v, k.min_depth, k.min_alt, k.min_pct, k.max_run, reinterpret_cast<int64_t*>(p + o_off)));
+    IOC_TRY(end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    settled();
+    int64_t total = 0;
+    IOC_TRY(copy_out({{&total, p + o_off + np * 8, 8}}));
+    if (total < 0 || total > pn.correct_bound) return ioc_fail(c, IOC_ERR_HIP, "the read correction counted a length outside its bound");
+    Arena w;
+    const size_t o_seq = w.take(size_t(total)), o_qual = w.take(size_t(total));
+    IOC_TRY(ioc_reserve(c, c->a_call, w.size()));
+    uint8_t* q = static_cast<uint8_t*>(c->a_call.p);
+    IOC_TRY(begin(t.ms_correct));
+    IOC_CHK(c, iock_read_correct_emit(c->stream, v, k.min_depth, k.min_alt, k.min_pct, k.max_run, reinterpret_cast<const int64_t*>(p + o_off), q + o_seq,
+                                      q + o_qual, uint64_t(total)));
+    IOC_TRY(end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    settled();
+    return copy_out({{o.off, p + o_off, (np + 1) * 8}, {o.stats, p + o_st, np * sizeof(ioc_correct_stats)}, {o.seq, q + o_seq, size_t(total)},
+                     {o.qual, q + o_qual, size_t(total)}});
 }
 
 }  // namespace
@@ -701,6 +762,80 @@ int ioc_planes_polish(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const cha
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   planes polish: %d group-segments, %lld rows, %d pairs, %lld plane bytes, %lld bytes called, k_plane_pile %.3f ms, k_pile_call %.3f ms\n",
                 2 * n_segs, (long long)(2 * p.n_rows), n_pairs, (long long)(8 * p.plane_bytes), (long long)out_off[2 * n_segs], r.t.ms_plane_pile, r.t.ms_call);
+    return IOC_OK;
+}
+
+// what a read correction refuses once its plan is known: IOC_OK, or the status with the message set
+static int correct_room_ok(ioc_ctx* c, const std::string& who, const CorrectOut& o, const SinkPlan& p)
+{
+    for (size_t g = 0; g < p.segs.size(); ++g)
+        if (pile_call_most(p.segs[g].rlen) > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
+            return ioc_fail(c, IOC_ERR_CAPACITY, who + ": segment " + std::to_string(g) + " may call more than 2^31 - 1 bytes");
+    if (o.cap < p.correct_bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": cap " + std::to_string(o.cap) + " below the bound " + std::to_string(p.correct_bound));
+    return p.correct_bound > 0 && (!o.seq || !o.qual) ? IOC_ERR_ARG : IOC_OK;
+}
+
+// upload -> correct -> copy-out.  The read correction from planes and tables the caller holds: everything is uploaded, and the
+// kernels run as behind ioc_align_pairs_correct.
+int ioc_planes_correct(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const ioc_pileup_col* cols,
+                       const ioc_pileup_ins* ins, int32_t n_pairs, const int32_t* seg_of_pair, const uint8_t* base, const uint8_t* slots, int32_t min_depth,
+                       int32_t min_alt, int32_t min_pct, int32_t max_run, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_correct_stats* out_stats)
+{
+    const CorrectOut o{{min_depth, min_alt, min_pct, max_run}, out_seq, out_qual, cap, out_off, out_stats};
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || (n_segs > 0 && (!rlen || !frame_off || !cols || !ins)) || (n_pairs > 0 && !seg_of_pair)) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen("ioc_planes_correct", n_segs, rlen, frames, frame_off, n_pairs, seg_of_pair, nullptr, PLAN_REFUSE_CALLED)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !slots)) return IOC_ERR_ARG;
+    IOC_TRY(correct_room_ok(c, "ioc_planes_correct", o, p));
+    out_off[0] = 0;
+    if (n_pairs == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    const size_t b_cols = size_t(p.n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(p.n_rows) * sizeof(ioc_pileup_ins);
+    IOC_TRY(ioc_reserve(c, c->a_pile, b_cols));
+    IOC_TRY(ioc_reserve(c, c->a_pile_ins, b_ins));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(p.frame_bytes)));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pile.p, cols, b_cols, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemcpyAsync(c->a_pile_ins.p, ins, b_ins, hipMemcpyHostToDevice, c->stream));
+    if (p.frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(p.frame_bytes), hipMemcpyHostToDevice, c->stream));
+    SinkRun r{c};
+    IOC_TRY(r.correct(p, seg_of_pair, static_cast<const uint8_t*>(d_frames.p), uint64_t(p.frame_bytes), c->a_pile.as<ioc_pileup_col>(), c->a_pile_ins.as<ioc_pileup_ins>(),
+                      Planes{nullptr, nullptr, nullptr, base, slots}, Planes{}, o));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes correct: %d segments, %lld rows, %d pairs, %lld plane bytes, %lld bytes written, k_read_correct %.3f ms\n", n_segs,
+                (long long)p.n_rows, n_pairs, (long long)(7 * p.plane_bytes), (long long)out_off[n_pairs], r.t.ms_correct);
+    return IOC_OK;
+}
+
+// pile -> correct -> copy-out.  ioc_align_pairs_polish's pile with every pair projected beside it, base plane and slot planes, and
+// k_read_correct over the tables and the planes where they lie: what comes back is every pair's corrected bytes and its record,
+// and the tables only where they are asked for.
+int ioc_align_pairs_correct(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                            int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
+                            const int32_t* seg_of_pair, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run, char* out_seq, char* out_qual,
+                            int64_t cap, int64_t* out_off, ioc_correct_stats* out_correct, ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins)
+{
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    const CorrectOut o{{min_depth, min_alt, min_pct, max_run}, out_seq, out_qual, cap, out_off, out_correct};
+    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_pool("ioc_align_pairs_correct", c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, 0)) return ioc_fail(c, st, p.msg);
+    IOC_TRY(correct_room_ok(c, "ioc_align_pairs_correct", o, p));
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    out_off[0] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    SinkRun r{c};
+    PiledDev d;
+    IOC_TRY(r.pile(a, PileKind::ins, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ true, d));
+    IOC_TRY(r.correct(p, seg_of_pair, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), d.cols, d.ins, Planes{},
+                      Planes{nullptr, nullptr, nullptr, d.base, d.slots}, o));
+    IOC_CHK(c, hipStreamSynchronize(c->stream));  // (a call without pairs has launched nothing that waited)
+    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}, {out_ins, d.ins, size_t(p.n_rows) * sizeof(ioc_pileup_ins)}}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: correct: %d segments, %lld rows, %d pairs, %lld bytes written, %.3f MB (corrected bytes, records, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup<ins> %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, k_read_correct %.3f ms%s\n",
+                n_segs, (long long)p.n_rows, n_pairs, (long long)out_off[n_pairs], double(r.t.copied) * 1e-6, out_cols || out_ins ? ", tables" : "",
+                out_stats ? ", statistics" : "", r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_project_ins, r.t.ms_correct,
+                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
     return IOC_OK;
 }
 

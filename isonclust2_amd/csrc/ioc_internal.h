@@ -208,7 +208,8 @@ struct ioc_ctx {
     DevBuf a_pool, a_pairs, a_order, a_out, a_bnd, a_lrow, a_ck, a_cko, a_ends, a_ends2, a_xflags, a_prof, a_ops;
     DevBuf a_ostats;  // ioc_align_pairs_stats: the records of a slice (k_ops_stats)
     DevBuf a_pile_ins;  // ioc_align_pairs_polish: the second table, what the reads insert (the ins variant of k_ops_pileup)
-    DevBuf a_call;      // ioc_pileup_call, ioc_align_pairs_polish: segments, offsets, records and the called bytes (ioc_pile_call.hip)
+    DevBuf a_call;      // ioc_pileup_call, ioc_align_pairs_polish: segments, offsets, records and the called bytes (ioc_pile_call.hip); the
+                        // read correction's write pass: [sequence][qualities], as many bytes as its count pass found
     DevBuf a_pile_w;    // ioc_align_pairs_polish_weighted: the tables of weights, [wcols][wins] of the call's rows (ioc_pileup_call_weighted: wcols
                         // alone, wins where ioc_pileup_call has ins)
     DevBuf a_qual;      // ioc_align_set_pool_qual: one quality byte per byte of a_pool ...
@@ -218,6 +219,8 @@ struct ioc_ctx {
     DevBuf a_split;   // ioc_alleles_split, ioc_align_pairs_split: member lists, bit planes, per-site and per-pair words (ioc_site_split.hip)
     DevBuf a_gpile;   // ioc_planes_polish, ioc_align_pairs_split_polish: the group-segments, their work items and tables (k_plane_pile) and,
                       // from host planes, the uploaded member lists and planes
+    DevBuf a_correct; // ioc_planes_correct, ioc_align_pairs_correct: segments, pairs, offsets, records and the corrected bytes (ioc_read_correct.hip) and,
+                      // from host planes, the uploaded planes
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
@@ -380,6 +383,9 @@ hipError_t iock_pile_call_weighted(hipStream_t st, const IocPileSeg* segs, uint3
                                    int64_t* seg_len, ioc_polish_stats* stats, int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual,
                                    uint64_t out_bytes);
 
+// ... and the scan alone: out_off[0 .. n] (device) = the exclusive scan of len[0 .. n) (k_pile_scan, for the stages that count per item)
+hipError_t iock_pile_scan(hipStream_t st, const int64_t* len, uint32_t n, int64_t* out_off);
+
 // ioc_pile_sites.hip: the projection of the same strings into byte planes of the pairs' own (ioc_host_ops_project) — pair pid's
 // base plane from base_planes + plane[pid] on, its ins plane from ins_planes + plane[pid] on (plane_bytes bytes each, set to
 // IOC_ALLELE_NONE / 0 by the caller); launched beside iock_ops_pileup*, the same pairs are skipped
@@ -407,6 +413,30 @@ struct IocPlaneWork;  // (ioc_plane_pile.h: 64 rows of a group-segment)
 hipError_t iock_plane_pile(hipStream_t st, const IocPlaneWork* work, uint32_t n_work, const IocPileSeg* gsegs, const uint32_t* mem_off,
                            const uint32_t* members, uint32_t n_pairs, const uint8_t* group, const uint64_t* plane, const uint8_t* base_planes,
                            const uint8_t* slot_planes, uint64_t plane_bytes, ioc_pileup_col* gcols, ioc_pileup_ins* gins, uint64_t n_rows);
+
+// ioc_read_correct.hip: every pair's read corrected against the tables of its segment (ioc_host_read_correct per pair).  Everything
+// is a device pointer: pair i belongs to segment seg_of_pair[i] and has its rows from byte plane[i] on of the base plane and of the
+// six slot planes (plane_bytes each, one behind the other); pair_len / stats: n_pairs words of scratch and the records.  The count
+// pass and the scan first; the write pass once out_seq / out_qual hold out_off[n_pairs] bytes.
+struct IocReadCorrectDev {
+    const IocPileSeg* segs;
+    uint32_t n_segs, n_pairs;
+    const int32_t* seg_of_pair;
+    const uint64_t* plane;
+    const ioc_pileup_col* cols;
+    const ioc_pileup_ins* ins;
+    uint64_t n_rows;
+    const uint8_t* frames;
+    uint64_t frame_bytes;
+    const uint8_t *base_planes, *slot_planes;
+    uint64_t plane_bytes;
+    int64_t* pair_len;
+    ioc_correct_stats* stats;
+};
+hipError_t iock_read_correct_count(hipStream_t st, const IocReadCorrectDev& v, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
+                                   int64_t* out_off);
+hipError_t iock_read_correct_emit(hipStream_t st, const IocReadCorrectDev& v, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
+                                  const int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);
 
 // ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
 // is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in

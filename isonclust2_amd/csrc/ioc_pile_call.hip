@@ -212,3 +212,10 @@ hipError_t iock_pile_call_weighted(hipStream_t st, const IocPileSeg* segs, uint3
     return pile_call_launch<true>(st, segs, n_segs, wcols, wins, cols, n_rows, frames, frame_bytes, min_depth, seg_len, stats, out_off, out_seq,
                                   out_qual, out_bytes);
 }
+
+// k_pile_scan for the stages that count per item of their own (ioc_read_correct.hip): out_off[0 .. n] = the exclusive scan of len
+hipError_t iock_pile_scan(hipStream_t st, const int64_t* len, uint32_t n, int64_t* out_off)
+{
+    hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(64), 0, st, reinterpret_cast<const long long*>(len), n, reinterpret_cast<long long*>(out_off));
+    return hipGetLastError();
+}

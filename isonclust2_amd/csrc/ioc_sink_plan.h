@@ -86,7 +86,8 @@ inline int64_t pile_sites_bound(const std::vector<IocPileSeg>& segs, int32_t max
 
 // The segments and the pairs of a call.  Segment g owns the rows segs[g].row0 .. + rlen of the call's tables, n_rows in all; pair
 // i is piled from row_base[i] on, its segment's first row, and has rlen + 1 bytes from plane[i] on in every plane of plane_bytes
-// bytes (the pairs one behind the other); alleles_bound: a byte per pair and site its segment may keep (from_pool).  frame_bytes:
+// bytes (the pairs one behind the other); alleles_bound: a byte per pair and site its segment may keep (from_pool); correct_bound:
+// what the correction of every pair may write, its segment's call bound each (ioc_planes_correct asks it of cap).  frame_bytes:
 // what the frames take of their pool (from_rlen).  A constructor returns IOC_OK, or the status of what it refuses with msg set —
 // the caller hands both to ioc_fail; `who` names the entry point in it.  What only some entry points refuse: a segment of more than
 // 2^30 bases (the site search: two sites a row) / one that may call more than 2^31 - 1 bytes (the record's out_len, the kernels' byte counts).
@@ -94,7 +95,7 @@ enum : unsigned { PLAN_REFUSE_LONG = 1, PLAN_REFUSE_CALLED = 2 };
 struct SinkPlan {
     std::vector<IocPileSeg> segs;
     std::vector<int64_t> row_base, plane;
-    int64_t n_rows = 0, frame_bytes = 0, plane_bytes = 0, alleles_bound = 0;
+    int64_t n_rows = 0, frame_bytes = 0, plane_bytes = 0, alleles_bound = 0, correct_bound = 0;
     std::string msg;
     int refuse(int status, const std::string& who, const std::string& what) { return msg = who.empty() ? what : who + ": " + what, status; }
     void place_pair(size_t i, const IocPileSeg& sg, int32_t max_sites)
@@ -102,6 +103,7 @@ struct SinkPlan {
         row_base[i] = sg.row0, plane[i] = plane_bytes;
         plane_bytes += int64_t(sg.rlen) + 1;
         alleles_bound += pile_sites_most(sg.rlen, max_sites);
+        correct_bound += pile_call_most(sg.rlen);
     }
 
     // the segments are sequences of the aligner's pool (offs: where each starts, and the end), the pairs' references as long as

@@ -8,7 +8,8 @@
 //  2. With the cap lowered to every value from the smallest cluster's need to the total, the cuts are exactly where a plain loop
 //     over the needs puts them (pool + need > cap with a non-empty pool): no cluster is divided, a cluster without rows goes to
 //     the group that is open when it is met, and the groups' pairs one after the other are the pairs of the one-group plan.
-//  3. polish_record and allele_char on one hand-made input each.
+//  3. polish_record and allele_char on one hand-made input each; corrected_record with both clipped ends attached, with a short
+//     quality line, with clips that exceed the read, and with an alignment whose insertion is too long to correct.
 //
 // Host code only (the planner does not touch the library, so neither common.cpp nor the library is linked); meant for the sanitizers:
 //
@@ -166,6 +167,20 @@ int main()
     for (int32_t a = -1; a <= 6; ++a) chars += allele_char(0, a);
     for (int32_t a = -1; a <= 2; ++a) chars += allele_char(IOC_SITE_INS, a);
     EXPECT(chars == "?ACGTN-?" "?.+?");
+
+    // a read of 10 bases whose alignment leaves 2 free in front and 3 behind: its 5 aligned bases became "ACGTTT"
+    ioc_aln_stats a{};
+    a.lead_i = 2, a.trail_i = 3, a.longest_ins = IOC_PILE_INS_SLOTS;
+    ioc_correct_stats k{};
+    k.out_len = 6, k.n_sub = 1, k.n_fill = 2, k.n_remove = 3, k.n_ins_add = 4, k.n_ins_drop = 5, k.n_low = 6, k.n_guarded = 7;
+    const char* const head = "@r1 cluster=4 subs=1 fills=2 removes=3 ins_add=4 ins_drop=5 low=6 guarded=7\n";
+    EXPECT(corrected_record("r1 x", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, k, "ACGTTT", "IIIII!", 6) == string(head) + "ggACGTTTttt\n+\n01IIIII!789\n");
+    EXPECT(corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123", 4, a, k, "ACGTTT", "IIIII!", 6) == string(head) + "ggACGTTTttt\n+\n01IIIII!!!!\n");
+    a.lead_i = 8, a.trail_i = 5;  // (clips that do not fit the read: the trailing one gives way)
+    EXPECT(corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, k, "", "", 0) == string(head) + "ggCCCCCttt\n+\n0123456789\n");
+    a.lead_i = 2, a.trail_i = 3, a.longest_ins = IOC_PILE_INS_SLOTS + 1;
+    EXPECT(corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, k, "ACGTTT", "IIIII!", 6) ==
+           "@r1 cluster=4 subs=0 fills=0 removes=0 ins_add=0 ins_drop=0 low=0 guarded=0 uncorrected=long_insertion\nggCCCCCttt\n+\n0123456789\n");
 
     if (faults) {
         fprintf(stderr, "%d checks failed\n", faults);
