@@ -1102,6 +1102,20 @@ void add_elapsed(ioc_ctx* c, const std::vector<hipEvent_t>& evs, size_t used)
     }
 }
 
+// IOC_TRACE=1: the host's wall-clock between the stages of a call on stderr (developer aid, like the driver's PhaseTrace in
+// ioc_host.cpp; profiles/step_gaps.txt).  A mark takes no synchronisation: a stage that waits for the device says so in its name.
+struct StageTrace {
+    bool on = getenv("IOC_TRACE") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void mark(const char* what)
+    {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[ioc]     align %-24s %9.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+        t = now;
+    }
+};
+
 int compute_units(const ioc_ctx* c)
 {
     int n_cu = 256;
@@ -1364,8 +1378,8 @@ struct V2Plan {
     uint64_t tiles_skipped = 0, tiles_all = 0;
     std::vector<std::pair<uint32_t, uint32_t>> slices;  // [first couple, count)
     uint64_t arena_words = 0, prof_total = 0;
-    std::vector<std::vector<V2Item>> items;  // per slice
-    std::vector<uint32_t> n_probe;           // (the probe launch's tiles come first in a slice's list)
+    std::vector<uint32_t> n_items, n_probe, n_diag;  // per slice: tiles of its list, the probe launch's (they come first), anti-diagonals
+    std::vector<std::vector<V2Item>> items;          // per slice: the host's list (tile_lists: IOC_V2_ITEMS_CHECK alone)
     uint32_t max_items = 0, max_flags = 0, max_pairs = 0;
 };
 
@@ -1559,7 +1573,36 @@ void slice_couples(V2Plan& pl, uint64_t budget, const std::vector<uint64_t>& cop
     }
 }
 
-// every slice's list of tiles and flags (V2Couple::flag0)
+// every slice's flags (V2Couple::flag0) and what the launches need to know of its list of tiles, in closed form from the grids:
+// the list itself is made on the device (k_fwd2_items), in the order tile_lists defines
+void tile_counts(V2Plan& pl)
+{
+    const size_t ns = pl.slices.size();
+    pl.n_items.assign(ns, 0);
+    pl.n_probe.assign(ns, 0);
+    pl.n_diag.assign(ns, 1);
+    for (size_t si = 0; si < ns; ++si) {
+        const uint32_t k_lo = pl.slices[si].first, k_hi = pl.slices[si].first + pl.slices[si].second;
+        uint32_t nf = 0;
+        uint64_t n_all = 0, n_probe = 0;
+        for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
+            V2Couple& cp = pl.cps[k2];
+            cp.flag0 = nf;
+            nf += cp.nbands * cp.nstrips;
+            n_all += uint64_t(cp.nbands) * cp.nstrips;
+            if (cp.corridor) n_probe += (uint64_t(cp.probe_band) + 1u) * (uint64_t(cp.probe_strip) + 1u);
+            pl.n_diag[si] = std::max(pl.n_diag[si], cp.nbands + cp.nstrips - 1u);
+        }
+        pl.n_probe[si] = uint32_t(n_probe);
+        pl.n_items[si] = uint32_t(n_probe + n_all);
+        pl.max_items = std::max(pl.max_items, pl.n_items[si]);
+        pl.max_flags = std::max(pl.max_flags, nf);
+        pl.max_pairs = std::max(pl.max_pairs, std::min(pl.cnt, 2u * k_hi) - 2u * k_lo);
+    }
+}
+
+// every slice's list of tiles and flags (V2Couple::flag0) on the host: the definition of the list's order, and what
+// IOC_V2_ITEMS_CHECK holds the device's list against
 void tile_lists(V2Plan& pl)
 {
     pl.items.resize(pl.slices.size());
@@ -1604,6 +1647,76 @@ void tile_lists(V2Plan& pl)
         pl.max_flags = std::max(pl.max_flags, nf);
         pl.max_pairs = std::max(pl.max_pairs, std::min(pl.cnt, 2u * k_hi) - 2u * k_lo);
     }
+}
+
+// IOC_V2_ITEMS_CHECK (developer switch): the host's lists into pl.items, and tile_counts' closed forms against what they say
+int tile_lists_check(ioc_ctx* c, V2Plan& pl)
+{
+    V2Plan ref = pl;
+    ref.max_items = ref.max_flags = ref.max_pairs = 0;
+    tile_lists(ref);
+    for (size_t si = 0; si < pl.slices.size(); ++si)
+        if (ref.items[si].size() != pl.n_items[si] || ref.n_probe[si] != pl.n_probe[si])
+            return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_ITEMS_CHECK: slice " + std::to_string(si) + ": " + std::to_string(pl.n_items[si]) + " tiles, " +
+                                                  std::to_string(pl.n_probe[si]) + " of the probe planned; the host's list has " +
+                                                  std::to_string(ref.items[si].size()) + " and " + std::to_string(ref.n_probe[si]));
+    for (uint32_t k2 = 0; k2 < pl.ncouples; ++k2)
+        if (ref.cps[k2].flag0 != pl.cps[k2].flag0) return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_ITEMS_CHECK: flag0 of couple " + std::to_string(k2) + " differs");
+    if (ref.max_items != pl.max_items || ref.max_flags != pl.max_flags || ref.max_pairs != pl.max_pairs)
+        return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_ITEMS_CHECK: max_items / max_flags / max_pairs differ from the host lists'");
+    pl.items = std::move(ref.items);
+    return IOC_OK;
+}
+
+// ... and a slice's list as the device made it against the host's, item by item (behind a wait for the stream)
+int device_items_check(ioc_ctx* c, const V2Plan& pl, const V2Item* d_items, size_t si)
+{
+    const std::vector<V2Item>& want = pl.items[si];
+    std::vector<V2Item> got(want.size());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    if (!got.empty()) IOC_CHK(c, hipMemcpy(got.data(), d_items, got.size() * sizeof(V2Item), hipMemcpyDeviceToHost));
+    for (size_t x = 0; x < want.size(); ++x)
+        if (got[x].couple != want[x].couple || got[x].band != want[x].band || got[x].strip != want[x].strip)
+            return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_ITEMS_CHECK: slice " + std::to_string(si) + ": the device's list differs from the host's at index " +
+                                                  std::to_string(x) + " of " + std::to_string(want.size()) + " (" + std::to_string(pl.n_probe[si]) +
+                                                  " of the probe): couple " + std::to_string(got[x].couple) + " band " + std::to_string(got[x].band) + " strip " +
+                                                  std::to_string(got[x].strip) + ", the host has couple " + std::to_string(want[x].couple) + " band " +
+                                                  std::to_string(want[x].band) + " strip " + std::to_string(want[x].strip));
+    if (getenv("IOC_TRACE")) {
+        fprintf(stderr, "[ioc]   aligner v2: IOC_V2_ITEMS_CHECK: slice %zu: %zu tiles (%u of the probe) equal the host's list\n", si, want.size(), pl.n_probe[si]);
+        // (the grids the list was made from, bands x strips per couple; c: a corridor with its probe's grid, 1: a couple of one pair)
+        fprintf(stderr, "[ioc]   aligner v2: IOC_V2_ITEMS_CHECK: slice %zu grids:", si);
+        for (uint32_t k2 = pl.slices[si].first; k2 < pl.slices[si].first + pl.slices[si].second; ++k2) {
+            const V2Couple& cp = pl.cps[k2];
+            fprintf(stderr, " %ux%u", cp.nbands, cp.nstrips);
+            if (cp.corridor) fprintf(stderr, "c%ux%u", uint32_t(cp.probe_band) + 1u, uint32_t(cp.probe_strip) + 1u);
+            if (cp.pid[1] == 0xFFFFFFFFu) fprintf(stderr, "/1");
+        }
+        fprintf(stderr, "\n");
+    }
+    return IOC_OK;
+}
+
+// ... and, after the slice has run, how many of the couples the host planned a corridor for the probe's verdicts opened (every
+// tile) — they come after the list and are no part of it
+int device_probe_report(ioc_ctx* c, const V2Plan& pl, const V2Couple* d_cps, size_t si)
+{
+    if (!getenv("IOC_TRACE")) return IOC_OK;
+    const uint32_t k_first = pl.slices[si].first, n_couples = pl.slices[si].second;
+    std::vector<V2Couple> got(n_couples);
+    IOC_CHK(c, hipMemcpy(got.data(), d_cps + k_first, size_t(n_couples) * sizeof(V2Couple), hipMemcpyDeviceToHost));
+    uint32_t planned = 0, opened = 0;
+    std::string which;
+    for (uint32_t x = 0; x < n_couples; ++x) {
+        planned += pl.cps[k_first + x].corridor ? 1u : 0u;
+        if (pl.cps[k_first + x].corridor && !got[x].corridor) {
+            ++opened;
+            which += " " + std::to_string(k_first + x);
+        }
+    }
+    fprintf(stderr, "[ioc]   aligner v2: IOC_V2_ITEMS_CHECK: slice %zu: %u couples with a corridor planned, %u opened by the probe (couples:%s)\n", si, planned,
+            opened, which.c_str());
+    return IOC_OK;
 }
 
 // the launch settings of align_v2_run (environment switches and the chip)
@@ -1699,12 +1812,12 @@ uint32_t v2_per_cu(const V2Plan& pl, size_t si, const V2Opts& o, bool few_couple
 // (*xe: a bounded wait ran out) and computed cells.
 // `od`: an emitting call — the traceback launches are the emitting kernels, the same launches otherwise.
 int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Opts& o, const AlnParams& P, const uint32_t* d_order,
-             int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, uint32_t* xe, const AlnOpsDev* od)
+             int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, uint32_t* xe, const AlnOpsDev* od, StageTrace& tr)
 {
     hipStream_t s = c->stream;
     const uint32_t k_first = pl.slices[si].first, n_couples = pl.slices[si].second;
     const uint32_t first_pair = 2u * k_first, n_pairs = std::min(pl.cnt, 2u * (k_first + n_couples)) - first_pair;
-    const uint32_t n_items = uint32_t(pl.items[si].size()), n_probe = pl.n_probe[si];
+    const uint32_t n_items = pl.n_items[si], n_probe = pl.n_probe[si];
     const AlnPairDev* d_pairs = static_cast<const AlnPairDev*>(c->a_pairs.p);
     const uint8_t* d_pool = static_cast<const uint8_t*>(c->a_pool.p);
     uint32_t* d_ctl = t.ctl;
@@ -1712,8 +1825,14 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     // publishes its progress every block of 64 rows)
     const bool few_couples = n_couples <= o.few_limit;
     const uint32_t prog_every = few_couples ? 1u : 0u;
-    IOC_CHK(c, hipMemcpyAsync(t.items, pl.items[si].data(), size_t(n_items) * sizeof(V2Item), hipMemcpyHostToDevice, s));
-    IOC_CHK(c, hipMemcpyAsync(t.cps + k_first, pl.cps.data() + k_first, size_t(n_couples) * sizeof(V2Couple), hipMemcpyHostToDevice, s));  // (flag0)
+    // the slice's list of tiles, from the couples as the host planned them (v2_tables sent them up; the probe's verdicts, which
+    // rewrite a couple's corridor, come after the list and never enter it)
+    const bool items_check = !pl.items.empty();  // (IOC_V2_ITEMS_CHECK)
+    if (items_check)  // (no item an earlier call or slice left there can stand in for one the kernel did not write)
+        IOC_CHK(c, hipMemsetAsync(t.items, 0xFF, size_t(n_items) * sizeof(V2Item), s));
+    hipLaunchKernelGGL(k_fwd2_items, dim3(pl.n_diag[si], 2), dim3(V2_ITEMS_T), 0, s, t.cps, k_first, n_couples, n_probe, t.items, n_items);
+    IOC_CHK(c, hipGetLastError());
+    if (items_check) IOC_TRY(device_items_check(c, pl, t.items, si));
     hipLaunchKernelGGL(k_fwd2_prof, dim3(n_couples, pl.max_strips), dim3(128), 0, s, d_pairs, t.cps + k_first, d_pool, P, static_cast<uint4*>(c->a_prof.p));
     IOC_CHK(c, hipGetLastError());
     IOC_CHK(c, hipMemsetAsync(d_ctl, 0, t.ctl_words * 4, s));
@@ -1739,6 +1858,7 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
         IOC_CHK(c, hipGetLastError());
         IOC_CHK(c, hipMemsetAsync(d_ctl, 0, 4, s));  // (the queue's counter; the flags of the probe's tiles stay)
     }
+    tr.mark("v2_slice up to the probe");
     const uint32_t n_main = n_items - n_probe, per_cu = v2_per_cu(pl, si, o, few_couples);
     const uint32_t n_wg = std::max(1u, std::min(per_cu * uint32_t(o.n_cu), (n_main + V2_WAVES - 1) / V2_WAVES));
     // (two workgroups per CU: the build of the kernel that may use the registers of the third)
@@ -1787,8 +1907,11 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     unsigned long long cells_done = 0;
     IOC_CHK(c, hipMemcpyAsync(xe, d_ctl + 1, 4, hipMemcpyDeviceToHost, s));
     IOC_CHK(c, hipMemcpyAsync(&cells_done, d_ctl + t.ctl_words - 2, 8, hipMemcpyDeviceToHost, s));
+    tr.mark("v2_slice other launches");
     IOC_CHK(c, hipStreamSynchronize(s));
+    tr.mark("v2_slice wait (device)");
     c->tm.n_align_cells_computed += int64_t(cells_done);
+    if (items_check) IOC_TRY(device_probe_report(c, pl, t.cps, si));
     return IOC_OK;
 }
 
@@ -1900,7 +2023,7 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
 // out (the caller then runs the same pairs through version 1).
 // `ops`: an emitting call (null otherwise).
 int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* order, uint32_t cnt, const uint32_t* d_order,
-                 const AlnParams& P, int32_t* d_score, uint32_t* d_count, bool corridor, bool* fell_back, OpsRun* ops)
+                 const AlnParams& P, int32_t* d_score, uint32_t* d_count, bool corridor, bool* fell_back, OpsRun* ops, StageTrace& tr)
 {
     *fell_back = false;
     if (cnt == 0) return IOC_OK;
@@ -1918,18 +2041,21 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o.occ, reinterpret_cast<const void*>(k_fwd2), 64 * V2_WAVES, 0) != hipSuccess) o.occ = 0;
     (void)hipGetLastError();
     if (o.occ < 1) o.occ = 3;
+    tr.mark("budget, occupancy");
 
     V2Plan pl;
     pl.cnt = cnt;
     pl.np = uint32_t(dp.size());
     pl.ncouples = (cnt + 1u) / 2u;
     plan_couples(pl, dp, order, corridor_model(c, P, corridor), band_target(pl.ncouples, o.few_limit, o.occ, o.n_cu));
+    tr.mark("plan_couples");
     std::vector<uint64_t> cops;  // (emitting call) the operation bytes of a couple's pairs: query length + reference length each
     if (ops) {
         cops.assign(pl.ncouples, 0);
         for (uint32_t x = 0; x < cnt; ++x) cops[x / 2u] += uint64_t(dp[order[x]].n) + dp[order[x]].m;
     }
     slice_couples(pl, budget, cops);
+    tr.mark("slice_couples");
     std::vector<uint64_t> slice_ops(pl.slices.size(), 0);
     if (ops) {  // a slice's pairs, in the slice's order, one region behind the other
         ops->end.assign(dp.size(), 0);
@@ -1950,7 +2076,10 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
         fprintf(stderr, "[ioc]   aligner v2: %u couples, checkpoint arena %.1f MB (%zu slice(s)) reserved in %.3f ms; corridor: %llu of %llu tiles skipped\n", pl.ncouples,
                 double(pl.arena_words) * 4e-6, pl.slices.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_res0).count(),
                 (unsigned long long)pl.tiles_skipped, (unsigned long long)pl.tiles_all);
-    tile_lists(pl);
+    tr.mark("arena reserve");
+    tile_counts(pl);
+    if (getenv("IOC_V2_ITEMS_CHECK") && (r = tile_lists_check(c, pl)) != IOC_OK) return r;
+    tr.mark("tile_counts");
 
     o.deadline = 4;  // (blocks of slack on top of what a pair of one transcript needs to be decided: 2 per 512 windows of its threshold)
     if (const char* e = getenv("IOC_TRACE2_DEADLINE")) o.deadline = uint32_t(std::max(0, atoi(e)));
@@ -1958,6 +2087,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     o.help_wgs = o.deadline ? std::min<uint32_t>(pl.max_pairs, uint32_t(o.n_cu)) : 0u;
     V2Dev t{};
     if ((r = v2_tables(c, pl, o.help_wgs, t)) != IOC_OK) return r;
+    tr.mark("v2_tables");
     // The helper launch for the wrong candidates runs on a side stream BESIDE the first traceback launch (IOC_TRACE2_EARLY=0:
     // everything goes through the first launch, as before): their walks are the longest of the batch, and the first launch — one
     // pair's latency long, with the chip half empty — no longer waits for them to reach their deadline first.
@@ -1969,6 +2099,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     EventSet evs;
     evs.v.assign(pl.slices.size() * 3, nullptr);
     for (auto& e : evs.v) IOC_CHK(c, hipEventCreate(&e));
+    tr.mark("side stream, events");
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner v2: planning (couples, corridors, tile lists, tables) took the host %.3f ms\n",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan0).count());
@@ -1976,7 +2107,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     bool bad = false;
     for (size_t si = 0; si < pl.slices.size() && !bad; ++si, evi += 3) {
         uint32_t xe = 0;
-        if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe, ops ? &ops->dev : nullptr)) != IOC_OK) return r;
+        if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe, ops ? &ops->dev : nullptr, tr)) != IOC_OK) return r;
         if (ops && !xe) {
             const uint32_t x0 = 2u * pl.slices[si].first, x1 = std::min(cnt, 2u * (pl.slices[si].first + pl.slices[si].second));
             if ((r = ops_fetch(c, *ops, dp, order + x0, d_order + x0, x1 - x0, slice_ops[si])) != IOC_OK) return r;
@@ -1985,6 +2116,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
         bad = xe != 0;
     }
     add_elapsed(c, evs.v, evi);
+    tr.mark("elapsed times");
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner v2: forward %.3f ms, traceback %.3f ms (device, all slices so far)%s\n", c->tm.ms_align_fwd,
                 c->tm.ms_align_trace, bad ? " — a wait ran out: falling back to version 1" : "");
@@ -2154,7 +2286,8 @@ WavePlan plan_waves(const AlnBatch& b, bool carry)
 
 // 4. version 2 takes the pairs it may (aln_v2_ok) — the front of `order`; *n_v2: how many it answered (0 when a bounded wait ran out
 // and they all go to version 1)
-int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2, const AlnSink* oh)
+int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2, const AlnSink* oh,
+           StageTrace& tr)
 {
     const uint32_t np = uint32_t(b.dp.size());
     uint32_t n = 0;
@@ -2162,7 +2295,7 @@ int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, 
     bool fell_back = false;
     OpsRun ops{oh, b.back.data()};
     const int r = align_v2_run(c, b.dp, b.order.data(), n, static_cast<const uint32_t*>(c->a_order.p), P, d_score, d_count, route != AlnRoute::every_tile,
-                               &fell_back, oh ? &ops : nullptr);
+                               &fell_back, oh ? &ops : nullptr, tr);
     if (r != IOC_OK) return r;
     if (fell_back) {
         c->tm.n_align_refused += n;
@@ -2590,10 +2723,13 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     const AlnParams P{match, mismatch, gap_extend, uint32_t(k), 1u << (32 - k)};
     AlnBatch b;
     int r;
+    StageTrace tr;
     if ((r = prepare_pairs(c, n_pairs, pairs, P, out, b)) != IOC_OK) return r;
+    tr.mark("prepare_pairs");
     const uint32_t np = uint32_t(b.dp.size());
     if (np == 0) return IOC_OK;
     order_pairs(b, pairs);
+    tr.mark("order_pairs");
     const char* ev = getenv("IOC_ALIGN_VARIANT");
     const bool carry = ev && strcmp(ev, "carry") == 0 && !out.ops;  // (the carry variant has no walk: an emitting call takes the traced route)
     const WavePlan wp = plan_waves(b, carry);
@@ -2607,7 +2743,8 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     const char* arena_mode = getenv("IOC_ALIGN_ARENA");
     const bool v2 = route != AlnRoute::v1_only && !carry && !getenv("IOC_ALIGN_V1") && !(arena_mode && strcmp(arena_mode, "fat") == 0);
     uint32_t n_v2 = 0;
-    if (v2 && (r = run_v2(c, b, P, d_score, d_count, route, &n_v2, out.ops)) != IOC_OK) return r;
+    tr.mark("pairs and order up");
+    if (v2 && (r = run_v2(c, b, P, d_score, d_count, route, &n_v2, out.ops, tr)) != IOC_OK) return r;
     if (carry)
         r = run_carry(c, b, wp.waves, P, d_score, d_count);
     else if (n_v2 < np)
@@ -2615,10 +2752,14 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     if (r != IOC_OK) return r;
     std::vector<int32_t> hs;
     std::vector<uint32_t> hc;
+    tr.mark("version 1 / carry");
     if ((r = read_results(c, b, n_v2, d_score, d_count, hs, hc)) != IOC_OK) return r;
+    tr.mark("read_results");
     // (the corridor model learns from the pairs of a call's own version-2 run, never from a re-run's)
     if (v2 && route == AlnRoute::normal) learn_corridor(c, b, P, hs, hc);
-    return scatter_results(c, b, pairs, v2, P, hs, hc, out);
+    r = scatter_results(c, b, pairs, v2, P, hs, hc, out);
+    tr.mark("scatter_results");
+    return r;
 }
 
 }  // namespace

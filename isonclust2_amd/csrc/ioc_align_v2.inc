@@ -247,6 +247,71 @@ k_fwd2_prof(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
     }
 }
 
+// A slice's list of tiles, written where the launches read it (tile_lists in ioc_align_gpu.hip is the definition of its order and
+// the host's version of it; IOC_V2_ITEMS_CHECK compares the two): first the probe's tiles — of a couple with a corridor the grid
+// of bands 0 .. probe_band by strips 0 .. probe_strip —, then every couple's full grid, each part anti-diagonal by anti-diagonal,
+// couples side by side, bands ascending.  The list is a function of the grids alone; it takes a quarter of a million items and
+// their upload off the host for every call.
+// One workgroup per (anti-diagonal, part).  Where its anti-diagonal starts in the list: the tiles of every couple on the
+// anti-diagonals before it, min(strips, dg - band) per band; where a couple's tiles start within it: a scan over the couples.
+constexpr int V2_ITEMS_T = 256;
+__global__ void __launch_bounds__(V2_ITEMS_T)
+k_fwd2_items(const V2Couple* __restrict__ couples, uint32_t k_first, uint32_t n_couples, uint32_t n_probe, V2Item* __restrict__ items, uint32_t n_items)
+{
+    __shared__ uint32_t s_scan[V2_ITEMS_T];
+    const uint32_t dg = blockIdx.x, tid = threadIdx.x;
+    const bool probe = blockIdx.y == 0;
+    auto grid = [&](uint32_t x, uint32_t& nb, uint32_t& ns) {
+        const V2Couple& cp = couples[k_first + x];
+        if (probe) {
+            nb = cp.corridor ? uint32_t(cp.probe_band) + 1u : 0u;
+            ns = uint32_t(cp.probe_strip) + 1u;
+        } else {
+            nb = cp.nbands;
+            ns = cp.nstrips;
+        }
+    };
+    uint32_t before = 0;
+    for (uint32_t x = tid; x < n_couples; x += V2_ITEMS_T) {
+        uint32_t nb, ns;
+        grid(x, nb, ns);
+        for (uint32_t b = 0; b < nb && b < dg; ++b) before += min(ns, dg - b);
+    }
+    s_scan[tid] = before;
+    __syncthreads();
+    for (uint32_t d = V2_ITEMS_T / 2; d; d >>= 1) {
+        if (tid < d) s_scan[tid] += s_scan[tid + d];
+        __syncthreads();
+    }
+    uint32_t running = s_scan[0] + (probe ? 0u : n_probe);
+    __syncthreads();
+    for (uint32_t x0 = 0; x0 < n_couples; x0 += V2_ITEMS_T) {
+        const uint32_t x = x0 + tid;
+        uint32_t cnt = 0, b_lo = 0;
+        if (x < n_couples) {
+            uint32_t nb, ns;
+            grid(x, nb, ns);
+            if (nb && dg <= nb + ns - 2u) {
+                b_lo = dg >= ns ? dg - ns + 1u : 0u;
+                cnt = min(dg, nb - 1u) - b_lo + 1u;
+            }
+        }
+        s_scan[tid] = cnt;
+        __syncthreads();
+        for (uint32_t d = 1; d < V2_ITEMS_T; d <<= 1) {  // (inclusive scan)
+            const uint32_t v = tid >= d ? s_scan[tid - d] : 0u;
+            __syncthreads();
+            s_scan[tid] += v;
+            __syncthreads();
+        }
+        const uint32_t pos = running + s_scan[tid] - cnt;
+        for (uint32_t i = 0; i < cnt; ++i)
+            if (pos + i < n_items) items[pos + i] = V2Item{k_first + x, uint16_t(b_lo + i), uint16_t(dg - (b_lo + i))};
+        running += s_scan[V2_ITEMS_T - 1];
+        __syncthreads();
+    }
+}
+
 // (the body of k_fwd2 and of k_fwd2_w2: the same code compiled for three waves per SIMD and 168 registers, or for two and no spills)
 static __device__ __forceinline__ void
 v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ couples, const V2Item* __restrict__ items, uint32_t n_items,

@@ -1357,6 +1357,65 @@ int ioc_resolve(ioc_ctx* c, int32_t* n_iter)
     return IOC_OK;
 }
 
+// h_pin_big holds at least need_b bytes afterwards, or is null (no pinned memory to be had: the caller copies into pageable arrays)
+static void pin_big_reserve(ioc_ctx* c, size_t need_b)
+{
+    if (c->h_pin_big_cap >= need_b) return;
+    if (c->h_pin_big) (void)hipHostFree(c->h_pin_big);
+    c->h_pin_big = nullptr;
+    c->h_pin_big_cap = 0;
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_pin_big), need_b * 2, hipHostMallocDefault) == hipSuccess)
+        c->h_pin_big_cap = need_b * 2;
+    else
+        (void)hipGetLastError();
+}
+
+}  // extern "C"
+
+// What the sahlin driver reads after every resolve — ioc_get_decisions, ioc_get_ties (count and keys both or neither) and
+// ioc_get_cuts (null: left out) — as copies into pinned memory behind ONE wait for the stream instead of three.
+int ioc_get_resolved(ioc_ctx* c, int32_t* target, int8_t* strand, uint8_t* flags, uint32_t* tie_count, uint32_t* tie_keys, int32_t* cut)
+{
+    if (!c || !target || !strand || !flags || (tie_count == nullptr) != (tie_keys == nullptr)) return IOC_ERR_ARG;
+    IOC_CHK(c, hipSetDevice(c->device));
+    if (!c->resolved) return ioc_fail(c, IOC_ERR_STATE, "ioc_resolve first");
+    if (tie_count && !c->aln_verdicts) return ioc_fail(c, IOC_ERR_STATE, "ioc_set_aln_verdicts + ioc_resolve first");
+    const size_t n = size_t(c->n);
+    if (n == 0) return IOC_OK;
+    // [targets][ties' counts][ties' keys][cuts][strands][flags]: the 4-byte arrays first
+    const size_t o_cnt = n * 4, o_keys = o_cnt + (tie_count ? n * 4 : 0), o_cut = o_keys + (tie_count ? n * IOC_TIE_SLOTS * 4 : 0);
+    const size_t o_str = o_cut + (cut ? n * 4 : 0), o_flg = o_str + n, bytes = o_flg + n;
+    pin_big_reserve(c, bytes + 64);
+    if (!c->h_pin_big) {
+        int r = ioc_get_decisions(c, target, strand, flags);
+        if (r == IOC_OK && tie_count) r = ioc_get_ties(c, tie_count, tie_keys);
+        if (r == IOC_OK && cut) r = ioc_get_cuts(c, cut);
+        return r;
+    }
+    hipStream_t s = c->stream;
+    uint8_t* st = c->h_pin_big;
+    IOC_CHK(c, hipMemcpyAsync(st, c->b_dec_target.p, n * 4, hipMemcpyDeviceToHost, s));
+    if (tie_count) {
+        IOC_CHK(c, hipMemcpyAsync(st + o_cnt, c->b_tie_count.p, n * 4, hipMemcpyDeviceToHost, s));
+        IOC_CHK(c, hipMemcpyAsync(st + o_keys, c->b_tie_keys.p, n * IOC_TIE_SLOTS * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (cut) IOC_CHK(c, hipMemcpyAsync(st + o_cut, c->b_cut.p, n * 4, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipMemcpyAsync(st + o_str, c->b_dec_strand.p, n, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipMemcpyAsync(st + o_flg, c->b_flags.p, n, hipMemcpyDeviceToHost, s));
+    IOC_CHK(c, hipStreamSynchronize(s));
+    memcpy(target, st, n * 4);
+    if (tie_count) {
+        memcpy(tie_count, st + o_cnt, n * 4);
+        memcpy(tie_keys, st + o_keys, n * IOC_TIE_SLOTS * 4);
+    }
+    if (cut) memcpy(cut, st + o_cut, n * 4);
+    memcpy(strand, st + o_str, n);
+    memcpy(flags, st + o_flg, n);
+    return IOC_OK;
+}
+
+extern "C" {
+
 int ioc_get_decisions(ioc_ctx* c, int32_t* target, int8_t* strand, uint8_t* flags)
 {
     if (!c) return IOC_ERR_ARG;
@@ -1366,16 +1425,7 @@ int ioc_get_decisions(ioc_ctx* c, int32_t* target, int8_t* strand, uint8_t* flag
     hipStream_t s = c->stream;
     if (n == 0) return IOC_OK;
     // (through pinned memory: three pageable read-backs cost 40 us of host time between them, once per resolve)
-    const size_t need_b = n * 6 + 64;
-    if (c->h_pin_big_cap < need_b) {
-        if (c->h_pin_big) (void)hipHostFree(c->h_pin_big);
-        c->h_pin_big = nullptr;
-        c->h_pin_big_cap = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&c->h_pin_big), need_b * 2, hipHostMallocDefault) == hipSuccess)
-            c->h_pin_big_cap = need_b * 2;
-        else
-            (void)hipGetLastError();
-    }
+    pin_big_reserve(c, n * 6 + 64);
     if (!c->h_pin_big) {
         if (target) IOC_CHK(c, hipMemcpyAsync(target, c->b_dec_target.p, n * 4, hipMemcpyDeviceToHost, s));
         if (strand) IOC_CHK(c, hipMemcpyAsync(strand, c->b_dec_strand.p, n, hipMemcpyDeviceToHost, s));

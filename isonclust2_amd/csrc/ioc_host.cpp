@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ioc_internal.h"
+#include "ioc_tie_sets.h"
 
 // ---- the worker pool behind ioc_parallel_for ---------------------------------------------------------------------------
 namespace {
@@ -540,6 +541,7 @@ struct AlnDriver {
             return IOC_OK;
         }
         if (r != IOC_OK) return r;
+        cache.reserve(cache.size() + todo.size());
         for (size_t i = 0; i < todo.size(); ++i) {
             cache[key(todo[i].first, todo[i].second)] = ratio[i];
             std::pair<uint64_t, uint64_t> pk;
@@ -614,7 +616,7 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
     AlnDriver ad;
     std::vector<int32_t> v_t;
     std::vector<int8_t> v_s;
-    std::vector<std::vector<uint32_t>> v_ties;
+    TieSets v_ties;  // per query: the tie set its verdict was derived from (flat arrays: ioc_tie_sets.h)
     std::vector<uint8_t> order_dep;
     std::vector<uint32_t> tcount, tkeys;
     std::vector<int32_t> cuts;
@@ -626,7 +628,7 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
         tr.mark("sequence pool upload");
         v_t.assign(size_t(n) + 1, INT32_MIN);
         v_s.assign(size_t(n) + 1, 0);
-        v_ties.assign(size_t(n) + 1, std::vector<uint32_t>());
+        v_ties.reset(size_t(n) + 1);
         order_dep.assign(size_t(n) + 1, 0);
         tcount.assign(size_t(n) + 1, 0);
         tkeys.assign(size_t(n) * IOC_TIE_SLOTS + IOC_TIE_SLOTS, 0);
@@ -635,37 +637,42 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
     for (int round = 0;; ++round) {
         if ((r = ioc_resolve(c, &iters)) != IOC_OK) return r;
         total_iters += iters;
-        if ((r = ioc_get_decisions(c, tgt.data(), str.data(), flg.data())) != IOC_OK) return r;
-        tr.mark("resolve + decisions");
+        // (decisions, tie sets and cuts come back behind one wait for the stream)
+        const bool want_cuts = aln_mode && !ad.host_only;
+        if (want_cuts) cuts.resize(size_t(n) + 1);
+        if ((r = ioc_get_resolved(c, tgt.data(), str.data(), flg.data(), aln_mode ? tcount.data() : nullptr, aln_mode ? tkeys.data() : nullptr,
+                                  want_cuts ? cuts.data() : nullptr)) != IOC_OK)
+            return r;
+        tr.mark(aln_mode ? "resolve + decisions, ties, cuts" : "resolve + decisions");
         if (!aln_mode) break;
         if (round > 2 * n + 8) return ioc_fail(c, IOC_ERR_STATE, "alignment fallback did not converge");
-        if ((r = ioc_get_ties(c, tcount.data(), tkeys.data())) != IOC_OK) return r;
-        if (!ad.host_only) {
-            cuts.resize(size_t(n) + 1);
-            if ((r = ioc_get_cuts(c, cuts.data())) != IOC_OK) return r;
-            ad.cuts = cuts.data();
-        }
+        if (want_cuts) ad.cuts = cuts.data();
         int32_t next_id = c->L;
         for (int i = 0; i < n; ++i) cid[size_t(i)] = (!gated[size_t(i)] && tgt[size_t(i)] < 0) ? next_id++ : -1;
         // queries that reach the alignment and whose verdict is missing, stale or order-dependent
         std::vector<int> bad;
-        std::vector<std::vector<uint32_t>> cur;
+        TieSets cur;  // the tie sets of `bad`, in its order
         std::vector<std::pair<int, uint32_t>> want;
         aln_invoked = 0;
+        uint32_t few[IOC_TIE_SLOTS];
+        std::vector<uint32_t> many;  // (a query whose ties overflowed the device's slots)
         for (int i = 0; i < n; ++i) {
             if (gated[size_t(i)] || !(flg[size_t(i)] & 2)) continue;
             aln_invoked++;
-            std::vector<uint32_t> ties;
-            if (tcount[size_t(i)] <= IOC_TIE_SLOTS) {
-                ties.assign(tkeys.begin() + size_t(i) * IOC_TIE_SLOTS, tkeys.begin() + size_t(i) * IOC_TIE_SLOTS + tcount[size_t(i)]);
-                std::sort(ties.begin(), ties.end());
-            } else if ((r = fetch_ties(c, i, cid, ties)) != IOC_OK) {
-                return r;
+            const uint32_t* ties = few;
+            uint32_t n_ties = tcount[size_t(i)];
+            if (n_ties <= IOC_TIE_SLOTS) {
+                std::copy(tkeys.begin() + size_t(i) * IOC_TIE_SLOTS, tkeys.begin() + size_t(i) * IOC_TIE_SLOTS + n_ties, few);
+                std::sort(few, few + n_ties);
+            } else {
+                if ((r = fetch_ties(c, i, cid, many)) != IOC_OK) return r;
+                ties = many.data();
+                n_ties = uint32_t(many.size());
             }
-            if (v_t[size_t(i)] != INT32_MIN && ties == v_ties[size_t(i)] && !order_dep[size_t(i)]) continue;
+            if (v_t[size_t(i)] != INT32_MIN && v_ties.equals(size_t(i), ties, n_ties) && !order_dep[size_t(i)]) continue;
             bad.push_back(i);
-            for (uint32_t t : ties) want.emplace_back(i, t);
-            cur.push_back(std::move(ties));
+            for (uint32_t x = 0; x < n_ties; ++x) want.emplace_back(i, ties[x]);
+            cur.push(ties, n_ties);
             if (ad.host_only && v_t[size_t(i)] == INT32_MIN) break;  // host aligner: no speculation beyond the first
         }
         // Speculation: a tie that is itself a query waiting for its verdict in THIS round stops being a representative if one of its
@@ -676,8 +683,8 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
         // resolve asks for them.  Results only ever come out of the cache under the exact (query, tie key) they were aligned for.
         size_t n_spec = 0;
         if (!ad.host_only && !bad.empty() && !(getenv("IOC_ALIGN_SPECULATE") && atoi(getenv("IOC_ALIGN_SPECULATE")) == 0)) {
-            std::unordered_map<int, size_t> waiting;
-            for (size_t b = 0; b < bad.size(); ++b) waiting[bad[b]] = b;
+            std::vector<int32_t> waiting(size_t(n), -1);  // per query: its place in `bad`
+            for (size_t b = 0; b < bad.size(); ++b) waiting[size_t(bad[b])] = int32_t(b);
             const size_t asked = want.size();
             // (only where both steps look like reads of one transcript — their cuts, the top counts of shared minimizers, are not far
             // below the round's median: a chance candidate of a chance candidate is nobody's fallback)
@@ -693,13 +700,14 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
             }
             auto alike = [&](int q) { return ad.cuts && ad.cuts[q] > 0 && ad.cuts[q] < INT32_MAX && int64_t(ad.cuts[q]) * 4 >= med; };
             for (size_t b = 0; b < bad.size() && n_spec * 4 < asked + 64; ++b)
-                for (uint32_t t : cur[b]) {
+                for (const uint32_t* tp = cur.begin(b); tp != cur.end(b); ++tp) {
+                    const uint32_t t = *tp;
                     const int32_t target = int32_t(t >> 1);
-                    if (target < c->L || !alike(bad[b])) continue;
-                    auto it = waiting.find(target - c->L);
-                    if (it == waiting.end() || !alike(target - c->L)) continue;
-                    for (uint32_t t2 : cur[it->second]) {
-                        want.emplace_back(bad[b], (t2 & ~1u) | ((t ^ t2) & 1u));  // (the strands compose)
+                    if (target < c->L || target - c->L >= n || !alike(bad[b])) continue;
+                    const int32_t wb = waiting[size_t(target - c->L)];
+                    if (wb < 0 || !alike(target - c->L)) continue;
+                    for (const uint32_t* t2 = cur.begin(size_t(wb)); t2 != cur.end(size_t(wb)); ++t2) {
+                        want.emplace_back(bad[b], (*t2 & ~1u) | ((t ^ *t2) & 1u));  // (the strands compose)
                         ++n_spec;
                     }
                 }
@@ -708,9 +716,10 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
             for (size_t b = 0; b < bad.size() && b < 12; ++b) {
                 const int i = bad[b];
                 fprintf(stderr, "[round %d] query %d: verdict so far %d, old ties [", round, i, v_t[size_t(i)]);
-                for (uint32_t t : v_ties[size_t(i)]) fprintf(stderr, " %u%s(v %d)", t >> 1, (t & 1) ? "-" : "+", int32_t(t >> 1) >= c->L ? v_t[size_t(int32_t(t >> 1) - c->L)] : -9);
+                for (const uint32_t* tp = v_ties.begin(size_t(i)); tp != v_ties.end(size_t(i)); ++tp)
+                    fprintf(stderr, " %u%s(v %d)", *tp >> 1, (*tp & 1) ? "-" : "+", int32_t(*tp >> 1) >= c->L ? v_t[size_t(int32_t(*tp >> 1) - c->L)] : -9);
                 fprintf(stderr, " ] new ties [");
-                for (uint32_t t : cur[b]) fprintf(stderr, " %u%s", t >> 1, (t & 1) ? "-" : "+");
+                for (const uint32_t* tp = cur.begin(b); tp != cur.end(b); ++tp) fprintf(stderr, " %u%s", *tp >> 1, (*tp & 1) ? "-" : "+");
                 fprintf(stderr, " ] order_dep %d\n", int(order_dep[size_t(i)]));
             }
         }
@@ -725,12 +734,14 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
         // That order is a std::sort over the iteration order of an unordered_map of ALL the query's hits (thousands
         // on a large batch): the hit tables are fetched from the device one after the other, the containers are
         // rebuilt on the host's cores.
-        std::vector<std::vector<uint32_t>> passes(bad.size());
+        TieSets passes;  // per entry of `bad`: the ties whose alignment passed
         std::vector<size_t> multi;
         for (size_t b = 0; b < bad.size(); ++b) {
-            for (uint32_t t : cur[b])
-                if (ad.cache[AlnDriver::key(bad[b], t)] >= c->params.aligned_threshold) passes[b].push_back(t);
-            if (passes[b].size() > 1) multi.push_back(b);
+            many.clear();
+            for (const uint32_t* tp = cur.begin(b); tp != cur.end(b); ++tp)
+                if (ad.cache[AlnDriver::key(bad[b], *tp)] >= c->params.aligned_threshold) many.push_back(*tp);
+            passes.push(many.data(), uint32_t(many.size()));
+            if (many.size() > 1) multi.push_back(b);
         }
         std::vector<RawCands> raws;
         {
@@ -746,12 +757,12 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
         ioc_parallel_for(multi.size(), [&](size_t x) {
             std::vector<Ordered> order;
             order_from(c, raws[x], cid, order);
-            const std::vector<uint32_t>& pass = passes[multi[x]];
+            const uint32_t *pass0 = passes.begin(multi[x]), *pass1 = passes.end(multi[x]);
             const unsigned top = order.empty() ? 0 : order[0].size;
             for (auto& o : order) {
                 if (o.size < top) break;
                 const uint32_t k = (uint32_t(o.target) << 1) | (o.strand < 0 ? 1u : 0u);
-                if (std::find(pass.begin(), pass.end(), k) != pass.end()) {
+                if (std::find(pass0, pass1, k) != pass1) {
                     win_t[x] = o.target;
                     win_s[x] = o.strand;
                     break;
@@ -765,24 +776,24 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
         size_t mx = 0;
         for (size_t b = 0; b < bad.size(); ++b) {
             const int i = bad[b];
-            const std::vector<uint32_t>& ties = cur[b];
-            const std::vector<uint32_t>& pass = passes[b];
+            const uint32_t n_pass = passes.size(b);
             int32_t vt = -1;
             int8_t vs = 0;
-            order_dep[size_t(i)] = pass.size() > 1;
-            if (pass.size() == 1) {
-                vt = int32_t(pass[0] >> 1);
-                vs = (pass[0] & 1u) ? -1 : 1;
-            } else if (pass.size() > 1) {
+            order_dep[size_t(i)] = n_pass > 1;
+            if (n_pass == 1) {
+                const uint32_t p0 = *passes.begin(b);
+                vt = int32_t(p0 >> 1);
+                vs = (p0 & 1u) ? -1 : 1;
+            } else if (n_pass > 1) {
                 vt = win_t[mx];
                 vs = win_s[mx];
                 ++mx;
                 if (vt < 0) return ioc_fail(c, IOC_ERR_STATE, "aligned candidate missing from the candidate order");
             }
-            if (vt != v_t[size_t(i)] || vs != v_s[size_t(i)] || ties != v_ties[size_t(i)]) changed = true;
+            if (vt != v_t[size_t(i)] || vs != v_s[size_t(i)] || !v_ties.equals(size_t(i), cur.begin(b), cur.size(b))) changed = true;
             v_t[size_t(i)] = vt;
             v_s[size_t(i)] = vs;
-            v_ties[size_t(i)] = ties;
+            v_ties.set(size_t(i), cur.begin(b), cur.size(b));
         }
         tr.mark("verdicts");
         if (!changed) break;
@@ -865,12 +876,14 @@ static int run_pipeline(ioc_ctx* c, const std::vector<uint8_t>& gated, const std
         const bool aln_dep = !order_dep.empty() && order_dep[size_t(i)];
         c->last_order_dep[size_t(i)] = uint8_t(((flg[size_t(i)] & 1) ? 1 : 0) | (aln_dep ? 1 : 0));
         if (aln_dep && !(flg[size_t(i)] & 1))  // the tied candidates that align (cluster.cpp:481-511)
-            for (uint32_t t : v_ties[size_t(i)])
+            for (const uint32_t* tp = v_ties.begin(size_t(i)); tp != v_ties.end(size_t(i)); ++tp) {
+                const uint32_t t = *tp;
                 if (ad.cache[AlnDriver::key(i, t)] >= c->params.aligned_threshold) {
                     const int32_t tg2 = int32_t(t >> 1);
                     const int32_t id = tg2 < c->L ? tg2 : cid[size_t(tg2 - c->L)];
                     if (id >= 0) c->last_dep_set[size_t(i)].emplace_back(id, int8_t((t & 1u) ? -1 : 1));
                 }
+            }
     }
     if (stats) {
         stats->n_clusters = next;

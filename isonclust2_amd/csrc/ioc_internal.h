@@ -318,6 +318,10 @@ struct IocCandTable {
     std::vector<uint32_t> sz, fi, tm;
 };
 int ioc_query_candidates_many(ioc_ctx* c, const std::vector<int>& qs, std::vector<IocCandTable>& out);
+// ioc_capi.cpp: ioc_get_decisions + ioc_get_ties (tie_count and tie_keys, both or neither) + ioc_get_cuts (cut; null: left out)
+// behind one wait for the stream: what run_pipeline reads after every resolve
+__attribute__((visibility("hidden"))) int ioc_get_resolved(ioc_ctx* c, int32_t* target, int8_t* strand, uint8_t* flags, uint32_t* tie_count,
+                                                           uint32_t* tie_keys, int32_t* cut);
 
 // events of a call's launches (the aligner: three per slice — the forward pass, the traceback, the end), destroyed on every way
 // out, the IOC_CHK returns included
