@@ -1862,7 +1862,11 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     const uint32_t n_main = n_items - n_probe, per_cu = v2_per_cu(pl, si, o, few_couples);
     const uint32_t n_wg = std::max(1u, std::min(per_cu * uint32_t(o.n_cu), (n_main + V2_WAVES - 1) / V2_WAVES));
     // (two workgroups per CU: the build of the kernel that may use the registers of the third)
-    fwd((per_cu <= 2 && !getenv("IOC_ALIGN_V2_NO_W2")) ? k_fwd2_w2 : k_fwd2, n_wg, t.items + n_probe, n_main);
+    const bool w2 = per_cu <= 2 && !getenv("IOC_ALIGN_V2_NO_W2");
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner v2: shape: slice %zu: %u couples, waits for %s, per_cu %u, n_wg %u, kernel %s, n_probe %u\n", si, n_couples,
+                few_couples ? "rows" : "tiles", per_cu, n_wg, w2 ? "k_fwd2_w2" : "k_fwd2", n_probe);
+    fwd(w2 ? k_fwd2_w2 : k_fwd2, n_wg, t.items + n_probe, n_main);
     IOC_CHK(c, hipGetLastError());
     const uint32_t n_help = std::min<uint32_t>(n_pairs, o.help_wgs);
     hipLaunchKernelGGL(k_fwd2_ends, dim3(n_pairs), dim3(64), 0, s, d_pairs, t.cps, d_order + first_pair, n_pairs, t.pend, t.lrow, t.best,
@@ -2047,7 +2051,11 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     pl.cnt = cnt;
     pl.np = uint32_t(dp.size());
     pl.ncouples = (cnt + 1u) / 2u;
-    plan_couples(pl, dp, order, corridor_model(c, P, corridor), band_target(pl.ncouples, o.few_limit, o.occ, o.n_cu));
+    const uint32_t want_bands = band_target(pl.ncouples, o.few_limit, o.occ, o.n_cu);
+    if (getenv("IOC_TRACE"))  // (which shape the call runs in: tests/test_gpu_align_shapes.py reads this line and v2_slice's)
+        fprintf(stderr, "[ioc]   aligner v2: shape: %u couples, band target %u, few_limit %u, occ %d, n_cu %d\n", pl.ncouples, want_bands, o.few_limit, o.occ,
+                o.n_cu);
+    plan_couples(pl, dp, order, corridor_model(c, P, corridor), want_bands);
     tr.mark("plan_couples");
     std::vector<uint64_t> cops;  // (emitting call) the operation bytes of a couple's pairs: query length + reference length each
     if (ops) {

@@ -287,22 +287,32 @@ def align_batch(ctx, rng, lmax=1400, npairs=30):
         pairs.append((2 * t, 2 * t + 1, rng.randint(0, 1), rng.choice([0.0, 0.02, 0.05, 0.12, 0.3, 0.95])))
     k = rng.choice([1, 7, 11, 15, 32])
     waves = rng.choice(["1", "2", "4", "8"])
-    old = os.environ.get("IOC_ALIGN_WAVES")
-    os.environ["IOC_ALIGN_WAVES"] = waves
+    # the launch shape of version 2's forward pass (drawn last: a seed's sequences and pairs are what they were before these draws
+    # existed): whole-tile waits instead of row-wise ones, the three-wave build where the two-wave one would run
+    few = rng.choice([None, "0"])
+    no_w2 = rng.choice([None, "1"])
+    env = {"IOC_ALIGN_WAVES": waves, "IOC_ALIGN_V2_FEW": few, "IOC_ALIGN_V2_NO_W2": no_w2}
+    old = {name: os.environ.get(name) for name in env}
     try:
+        for name, v in env.items():
+            if v is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = v
         ctx.align_set_pool(seqs)
         score, win, ratio = ctx.align_pairs(pairs, k)
     finally:
-        if old is None:
-            os.environ.pop("IOC_ALIGN_WAVES", None)
-        else:
-            os.environ["IOC_ALIGN_WAVES"] = old
+        for name, v in old.items():
+            if v is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = v
     bad = []
     for i, (qi, ri, rc, e) in enumerate(pairs):
         hs, hr = _host(L, seqs[qi], seqs[ri], rc, e, k)
         if score[i] != hs or ratio[i] != hr:
             bad.append((i, len(seqs[qi]), len(seqs[ri]), rc, e, int(score[i]), hs, float(ratio[i]), hr))
-    return not bad, f"k={k} waves={waves} pairs {bad[:3]}"
+    return not bad, f"k={k} waves={waves} IOC_ALIGN_V2_FEW={few} IOC_ALIGN_V2_NO_W2={no_w2} pairs {bad[:3]}"
 
 
 def verdict_batch(ctx, rng, lmax=3000, npairs=60):
