@@ -1038,6 +1038,84 @@ int ioc_align_pairs_correct(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* p
                             int32_t min_pct, int32_t max_run, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
                             ioc_correct_stats* out_correct, ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins);
 
+/* ---- Exon blocks: the stretches of a representative that some of its cluster's reads skip, and every read's isoform ----
+ * One segment is a reference of rlen rows with n_reads reads, each read its base plane base[0 .. rlen] as ioc_host_ops_project
+ * writes it: a byte of 0 .. 5 (a channel or IOC_ALLELE_DEL) covers the row, any other byte does not; row rlen takes part in
+ * nothing.  A rule {min_gap >= 1, min_depth >= 1, min_alt >= 1, min_pct in 1 .. 50, min_block >= 1, max_blocks in 1 .. 32}.  All
+ * integers.
+ *  1. A long gap of a read: a maximal run of consecutive rows p < rlen with base[p] == IOC_ALLELE_DEL of at least min_gap rows (no
+ *     upper length).  G_i(p) is 1 on the rows of read i's long gaps.
+ *  2. The row table: D(p) the reads that cover row p, in(p) the sum of G_i(p); need(D) = max(min_alt, ceil(min_pct * D / 100)) as
+ *     in ioc_host_pileup_sites.  Row p is variable iff D(p) >= min_depth, in(p) >= need(D(p)) and D(p) - in(p) >= need(D(p)).
+ *  3. A block [first, end): a maximal run of variable rows of at least min_block rows.  In ascending order; the first max_blocks
+ *     are kept, n_found says how many there were (n_found > max_blocks: the list was cut).
+ *  4. A read's state at a kept block of len rows, of which it covers c and has s deleted (ANY deleted row, not only those of long
+ *     gaps: one stray match cuts a long gap into pieces shorter than min_gap): c < len IOC_BLOCK_NONE, else 4 s >= 3 len
+ *     IOC_BLOCK_SKIP, else 4 s <= len IOC_BLOCK_KEEP, else IOC_BLOCK_PART.
+ *  5. The signature: key = the sum over the kept blocks b of state(b) << (2 b).  A read is complete when no state is NONE; a
+ *     segment without blocks gives every read the complete key 0.
+ *  6. The keys carried by at least min_alt complete reads are supported; in ascending UNSIGNED order they are the isoforms 0 ..
+ *     n_groups - 1.  A complete read of a supported key: that isoform, IOC_ISO_DIRECT; of another key: -1, IOC_ISO_RARE.  An
+ *     incomplete read with a state that is not NONE and exactly one supported key that agrees with it at every block where its
+ *     state is not NONE: that isoform, IOC_ISO_ASSIGNED; any other incomplete read: -1, IOC_ISO_AMBIGUOUS.
+ * No verdict on whether two isoforms are real is applied: that stays the reader's judgement of the counts. */
+#define IOC_BLOCK_KEEP 0
+#define IOC_BLOCK_SKIP 1
+#define IOC_BLOCK_PART 2
+#define IOC_BLOCK_NONE 3
+#define IOC_ISO_DIRECT 0
+#define IOC_ISO_ASSIGNED 1
+#define IOC_ISO_RARE 2
+#define IOC_ISO_AMBIGUOUS 3
+#define IOC_BLOCKS_MAX 32
+typedef struct {
+    uint32_t depth, in_gap;       /* D(p) and in(p); rlen + 1 rows per segment, the last one zero */
+} ioc_block_row;                  /* 8 bytes */
+typedef struct {
+    int32_t first, end;
+    uint32_t n_keep, n_skip, n_part, n_none;  /* over the segment's reads */
+    uint32_t reserved[2];
+} ioc_pile_block;                 /* 32 bytes */
+typedef struct {
+    uint64_t key;
+    int32_t group, how;
+    int32_t first_row, end_row;   /* the first covered row and one past the last (0, 0: the read covers nothing) */
+    int32_t n_gaps, gap_rows;     /* its long gaps and their rows */
+} ioc_read_blocks;                /* 32 bytes */
+typedef struct {
+    int32_t n_blocks, n_found, n_groups, n_reads, n_direct, n_assigned, n_rare, n_ambiguous;
+} ioc_blocks_seg;                 /* 32 bytes */
+/* The definition: one segment, the planes read-major (n_reads x (rlen + 1) bytes), the plain loops above.  out_rows (may be NULL):
+ * rlen + 1 rows; out_blocks: room for min(max_blocks, rlen) records, of which the first out_seg->n_blocks are written; out_reads:
+ * n_reads records.  IOC_ERR_ARG, with nothing written, for a rule outside its ranges, a negative count or length and a NULL
+ * pointer that is needed. */
+int ioc_host_planes_blocks(const uint8_t* base, int32_t n_reads, int32_t rlen, int32_t min_gap, int32_t min_depth, int32_t min_alt,
+                           int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks,
+                           ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg);
+/* Many segments at once on the device, from host base planes, which are uploaded: the pairs' planes one behind the other as for
+ * ioc_planes_polish, a segment's reads its pairs in ascending order.  The kernels of ioc_read_blocks.hip turn every plane into two
+ * bit planes by ballot (covered, deleted) and work on those: run lengths carried across words, a lane per row for the table, a wave
+ * per segment for the blocks, masked popcounts for the states, a wave per read for the isoforms; no atomics.  out_rows (may be NULL):
+ * the segments' tables one behind the other, rlen[g] + 1 rows each; out_blocks: the kept blocks packed in segment order, segment
+ * g's at block_off[g] .. block_off[g + 1] (n_segs + 1 entries); out_reads per pair, out_seg per segment; each as
+ * ioc_host_planes_blocks defines it.  IOC_ERR_ARG, with nothing written, for what the definition refuses, seg_of_pair outside the
+ * segments and a NULL pointer that is needed; IOC_ERR_CAPACITY, with nothing written, for blocks_cap below the sum over the segments
+ * of min(max_blocks, rlen[g]). */
+int ioc_planes_blocks(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const uint8_t* base,
+                      int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks,
+                      ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                      ioc_blocks_seg* out_seg);
+/* ioc_align_pairs_alleles' alignment — the table of counts, and k_ops_project into every pair's planes — and behind the walks the
+ * block kernels over the planes where they lie: scores, windows, ratio, out_stats, the segments and out_cols (optional) as from
+ * ioc_align_pairs_alleles, everything else as from ioc_planes_blocks.  Every pair is aligned, piled and projected exactly once.  The
+ * stage's own memory is reserved after the walks.  The refusals of both calls; nothing is written. */
+int ioc_align_pairs_blocks(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                           int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                           int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                           ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                           ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols);
+
 #ifdef __cplusplus
 }
 #endif

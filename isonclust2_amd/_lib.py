@@ -116,6 +116,25 @@ class PileSite(C.Structure):  # ioc_pile_site (32 bytes)
 ALLELE_DEL, ALLELE_NONE = 5, 7  # IOC_ALLELE_DEL, IOC_ALLELE_NONE
 SITE_BASE, SITE_INS = 0, 1      # IOC_SITE_BASE, IOC_SITE_INS
 SPLIT_NONE = 255                # IOC_SPLIT_NONE
+BLOCK_KEEP, BLOCK_SKIP, BLOCK_PART, BLOCK_NONE = 0, 1, 2, 3    # IOC_BLOCK_*
+ISO_DIRECT, ISO_ASSIGNED, ISO_RARE, ISO_AMBIGUOUS = 0, 1, 2, 3  # IOC_ISO_*
+BLOCKS_MAX = 32                 # IOC_BLOCKS_MAX
+
+
+class BlockRow(C.Structure):  # ioc_block_row (8 bytes)
+    _fields_ = [("depth", C.c_uint32), ("in_gap", C.c_uint32)]
+
+
+class PileBlock(C.Structure):  # ioc_pile_block (32 bytes)
+    _fields_ = [("first", C.c_int32), ("end", C.c_int32)] + [(n, C.c_uint32) for n in ("n_keep", "n_skip", "n_part", "n_none")] + [("reserved", C.c_uint32 * 2)]
+
+
+class ReadBlocks(C.Structure):  # ioc_read_blocks (32 bytes)
+    _fields_ = [("key", C.c_uint64)] + [(n, C.c_int32) for n in ("group", "how", "first_row", "end_row", "n_gaps", "gap_rows")]
+
+
+class BlocksSeg(C.Structure):  # ioc_blocks_seg (32 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("n_blocks", "n_found", "n_groups", "n_reads", "n_direct", "n_assigned", "n_rare", "n_ambiguous")]
 
 
 class SplitSeg(C.Structure):  # ioc_split_seg (32 bytes)
@@ -169,6 +188,7 @@ SYMBOLS = [
     "ioc_dist_allgatherv_device", "ioc_dist_allgather_i64", "ioc_dist_allgatherv_host", "ioc_dist_allreduce_max",
     "ioc_dist_barrier", "ioc_dist_merge", "ioc_set_shard", "ioc_shard_exchanges", "ioc_shard_aligned_pairs", "ioc_dist_exchange", "ioc_dist_set_shard", "ioc_align_set_verdict_threshold",
     "ioc_host_read_correct", "ioc_planes_correct", "ioc_align_pairs_correct",
+    "ioc_host_planes_blocks", "ioc_planes_blocks", "ioc_align_pairs_blocks",
 ]
 
 _lib = None
@@ -319,6 +339,10 @@ def load():
                                      C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p]
     L.ioc_align_pairs_correct.argtypes = [vp, i32, C.POINTER(AlnPair), i32, i32, i32, i32, pi32, pi64, pd, C.c_void_p, i32, C.POINTER(PolishSeg), pi32,
                                           i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_host_planes_blocks.argtypes = [C.c_void_p, i32, i32, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_planes_blocks.argtypes = [vp, i32, pi32, i32, pi32, C.c_void_p, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
+    L.ioc_align_pairs_blocks.argtypes = [vp, i32, C.POINTER(AlnPair), i32, i32, i32, i32, pi32, pi64, pd, C.c_void_p, i32, C.POINTER(PolishSeg), pi32,
+                                         i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

@@ -273,6 +273,53 @@ def read_correct(base, slots, cols, ins, frame, min_depth=3, min_alt=3, min_pct=
     return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in CORRECT_STATS_FIELDS}
 
 
+# ioc_block_row, ioc_pile_block, ioc_read_blocks and ioc_blocks_seg as numpy records
+BLOCK_ROW_DTYPE = np.dtype([("depth", np.uint32), ("in_gap", np.uint32)])
+PILE_BLOCK_DTYPE = np.dtype([("first", np.int32), ("end", np.int32)] + [(n, np.uint32) for n in ("n_keep", "n_skip", "n_part", "n_none")] + [("reserved", np.uint32, 2)])
+READ_BLOCKS_DTYPE = np.dtype([("key", np.uint64)] + [(n, np.int32) for n in ("group", "how", "first_row", "end_row", "n_gaps", "gap_rows")])
+BLOCKS_SEG_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.BlocksSeg._fields_])
+BLOCK_KEEP, BLOCK_SKIP, BLOCK_PART, BLOCK_NONE = _lib.BLOCK_KEEP, _lib.BLOCK_SKIP, _lib.BLOCK_PART, _lib.BLOCK_NONE
+ISO_DIRECT, ISO_ASSIGNED, ISO_RARE, ISO_AMBIGUOUS = _lib.ISO_DIRECT, _lib.ISO_ASSIGNED, _lib.ISO_RARE, _lib.ISO_AMBIGUOUS
+BLOCKS_RULE = dict(min_gap=20, min_depth=3, min_alt=3, min_pct=25, min_block=10, max_blocks=32)
+
+
+def planes_blocks_bound(rlen, max_blocks):
+    """What a block search of a reference of rlen bases may keep at most: min(max_blocks, rlen)."""
+    return min(int(max_blocks), int(rlen))
+
+
+def _blocks_rule(rule):
+    unknown = set(rule) - set(BLOCKS_RULE)
+    if unknown:
+        raise TypeError(f"unknown rule parameters: {sorted(unknown)}")
+    return [int({**BLOCKS_RULE, **rule}[n]) for n in BLOCKS_RULE]
+
+
+def planes_blocks(base, rows=True, **rule):
+    """ioc_host_planes_blocks: the exon blocks of one segment and every read's isoform — `base` the reads' base planes as ops_project
+    gives them, n_reads x (rlen + 1) bytes; the rule as keywords (BLOCKS_RULE has the defaults).  A long gap is a run of at least
+    min_gap deleted rows; a row is variable where enough reads have one and enough have none; a block is a run of at least
+    min_block variable rows; a read's state at a block is keep, skip, part or none, its key the states two bits each, and the keys
+    that at least min_alt complete reads carry are the isoforms, in ascending order.  Returns a dict: `rows` (BLOCK_ROW_DTYPE, rlen +
+    1 rows; with rows=True), `blocks` (PILE_BLOCK_DTYPE, the kept ones), `reads` (READ_BLOCKS_DTYPE per read), `seg` (a
+    BLOCKS_SEG_DTYPE record).  IocError for a rule outside its ranges."""
+    base = np.ascontiguousarray(base, np.uint8)
+    if base.ndim != 2 or base.shape[1] < 1:
+        raise ValueError("base must hold n_reads x (rlen + 1) bytes")
+    n, rlen = base.shape[0], base.shape[1] - 1
+    r = _blocks_rule(rule)
+    tab = np.zeros(rlen + 1, BLOCK_ROW_DTYPE)
+    blocks, reads, seg = np.zeros(max(min(max(r[5], 0), rlen), 1), PILE_BLOCK_DTYPE), np.zeros(n, READ_BLOCKS_DTYPE), np.zeros(1, BLOCKS_SEG_DTYPE)
+    rc = _lib.load().ioc_host_planes_blocks(base.ctypes.data if n else None, n, rlen, *r, tab.ctypes.data if rows else None, blocks.ctypes.data,
+                                            reads.ctypes.data if n else None, seg.ctypes.data)
+    if rc < 0:
+        raise IocError(int(rc), "ioc_host_planes_blocks")
+    out = {"blocks": blocks[:int(seg[0]["n_blocks"])], "reads": reads, "seg": seg[0]}
+    if rows:
+        out["rows"] = tab
+    return out
+
+
 def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
     """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
     returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
@@ -878,6 +925,72 @@ class Context:
             out["stats"] = st
         if tables:
             out.update(cols=cols, ins=ins, row0=self._row0(rlen))
+        return out
+
+    @staticmethod
+    def _blocks_out(ns, rlen, rule, rows, cap):
+        """the output arrays of a block search over segments of these lengths, and the pointers the library takes behind the rule"""
+        bound = sum(planes_blocks_bound(m, rule[5]) for m in rlen)
+        cap = bound if cap is None else int(cap)
+        n_rows = int(sum(rlen)) + ns
+        tab = np.zeros(n_rows, BLOCK_ROW_DTYPE) if rows else None
+        blocks, boff, seg = np.zeros(max(cap, 1), PILE_BLOCK_DTYPE), np.zeros(ns + 1, np.int64), np.zeros(ns, BLOCKS_SEG_DTYPE)
+        return (tab, blocks, boff, seg), cap
+
+    def _blocks_dict(self, ns, rlen, n, tab, blocks, boff, reads, seg):
+        out = {"blocks": [blocks[boff[g]:boff[g + 1]] for g in range(ns)], "block_off": boff, "reads": reads, "seg": seg}
+        if tab is not None:
+            r0 = np.concatenate([self._row0(rlen), [len(tab)]]).astype(np.int64) if ns else np.zeros(1, np.int64)
+            out.update(rows=[tab[r0[g]:r0[g + 1]] for g in range(ns)])
+        return out
+
+    def planes_blocks(self, rlen, seg_of_pair, base, rows=True, cap=None, **rule):
+        """ioc_planes_blocks: the exon blocks of many segments and every read's isoform on the device, from host base planes — `rlen`
+        the segments' lengths, seg_of_pair per pair, `base` a list per pair of what ops_project gives for that pair (a segment's
+        reads are its pairs in ascending order); the rule as keywords.  Returns a dict: `blocks` (a PILE_BLOCK_DTYPE array per
+        segment), `block_off`, `reads` (READ_BLOCKS_DTYPE per pair), `seg` (BLOCKS_SEG_DTYPE per segment) and, with rows=True, `rows`
+        (a BLOCK_ROW_DTYPE array per segment); each segment as api.planes_blocks defines it."""
+        ns, n = len(rlen), len(base)
+        rl = np.ascontiguousarray(rlen, np.int32)
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair and base must hold one entry per pair")
+        want = [int(rl[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (want[i],):
+                raise ValueError(f"the plane of pair {i} is not that of its segment")
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        r = _blocks_rule(rule)
+        (tab, blocks, boff, seg), cap = self._blocks_out(ns, [max(int(m), 0) for m in rl], r, rows, cap)
+        reads = np.zeros(n, READ_BLOCKS_DTYPE)
+        self._chk(self.L.ioc_planes_blocks(self.h, ns, _p(rl, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, fb.ctypes.data if len(fb) else None,
+                                           *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap, _p(boff, C.c_int64),
+                                           reads.ctypes.data if n else None, seg.ctypes.data if ns else None))
+        return self._blocks_dict(ns, [int(m) for m in rl], n, tab, blocks, boff, reads, seg)
+
+    def align_pairs_blocks(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, match=2, mismatch=-2, gap_extend=1, **rule):
+        """ioc_align_pairs_blocks: align_pairs, the table of counts, every pair's base plane and the block search over the planes, all
+        on the device, every pair aligned once — segs / seg_of_pair as for align_pairs_alleles; the rule as keywords.  Returns a dict:
+        score, windows, ratio, and `blocks`, `block_off`, `reads`, `seg`, `rows` as Context.planes_blocks returns them; with stats=True
+        `stats` (ALN_STATS_DTYPE per pair), with tables=True `cols` and `row0`."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        r = _blocks_rule(rule)
+        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        reads = np.zeros(n, READ_BLOCKS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        self._chk(self.L.ioc_align_pairs_blocks(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+                                                _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
+                                                _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
+                                                cols.ctypes.data if tables and n_rows else None))
+        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg)}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out.update(cols=cols, row0=self._row0(rlen))
         return out
 
     @staticmethod

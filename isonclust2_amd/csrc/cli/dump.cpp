@@ -31,6 +31,7 @@ struct DumpOptions {
     // --split-polish: cluster_split_polished.fq, the consensus of each group of every cluster that has a split
     // --split-polish-min-depth: positions covered by fewer reads of the group keep the representative's base
     // --correct: corrected_reads.fq, every read corrected against the pileup of its cluster; --correct-*: its thresholds
+    // --isoforms: cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, the exon blocks of a cluster and every read's isoform; --isoforms-*
     ReportOpts reports;
 };
 
@@ -51,7 +52,9 @@ void print_dump_help()
          << "                    [--sites [--sites-min-depth N] [--sites-min-alt N] [--sites-min-pct P] [--sites-max N]]" << endl
          << "                    [--split [--split-min-link N] [--split-min-margin N] [--split-rounds N]" << endl
          << "                     [--split-polish [--split-polish-min-depth N]]]" << endl
-         << "                    [--correct [--correct-min-depth N] [--correct-min-alt N] [--correct-min-pct P] [--correct-max-run N]] final.cer" << endl
+         << "                    [--correct [--correct-min-depth N] [--correct-min-alt N] [--correct-min-pct P] [--correct-max-run N]]" << endl
+         << "                    [--isoforms [--isoforms-min-gap N] [--isoforms-min-depth N] [--isoforms-min-alt N] [--isoforms-min-pct P]" << endl
+         << "                     [--isoforms-min-block N] [--isoforms-max N]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -94,7 +97,24 @@ void print_dump_help()
          << "  --correct-min-pct P    ... and at least P percent of the depth, 1 .. 50 (default 25)" << endl
          << "  --correct-max-run N    a run of more than N deleted positions in a row is not filled in, and one of more than N bases is not" << endl
          << "                 removed, 0 .. 64 (default 10: a choice — sequencing indels are short, a missing exon is not — that was not" << endl
-         << "                 measured on real data)" << endl;
+         << "                 measured on real data)" << endl
+         << "  --isoforms     also write outdir/cluster_blocks.tsv, cluster_isoforms.tsv and read_isoforms.tsv (GPU): the stretches of a cluster's" << endl
+         << "                 representative that some of its reads skip (exon blocks: first, end, and how many reads keep, skip, partly skip" << endl
+         << "                 or do not reach each; a '#' line where a cluster's list was cut), the signatures that enough complete reads carry" << endl
+         << "                 (one character per block: '=' keep, '-' skip, '~' part) with their reads, and per read its isoform (or '.')," << endl
+         << "                 whether it carries the signature itself (direct), fits exactly one (assigned), carries one too few reads share" << endl
+         << "                 (rare) or fits none or several (ambiguous), its own signature ('.' where it does not reach across a block), the" << endl
+         << "                 representative's positions it covers and its long gaps.  An exon the representative lacks is not found.  The" << endl
+         << "                 report is a call of its own: beside --polish, --sites, --split or --correct the reads are aligned once more for it" << endl
+         << "  --isoforms-min-gap N    a run of at least N deleted positions in a row is a long gap (default 20: a choice that was not" << endl
+         << "                 measured on real data)" << endl
+         << "  --isoforms-min-depth N  positions covered by fewer than N reads are not variable (default 3)" << endl
+         << "  --isoforms-min-alt N    a position is variable when at least N reads have a long gap there and N have none, and a signature" << endl
+         << "                 is an isoform when at least N complete reads carry it (default 3) ..." << endl
+         << "  --isoforms-min-pct P    ... and at least P percent of the depth either way, 1 .. 50 (default 25)" << endl
+         << "  --isoforms-min-block N  a run of at least N variable positions is a block (default 10: a choice that was not measured on" << endl
+         << "                 real data)" << endl
+         << "  --isoforms-max N        keep the first N blocks of a cluster, 1 .. 32 (default 32)" << endl;
 }
 
 DumpOptions parse_dump_options(int argc, char** argv)
@@ -111,7 +131,11 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"split-polish", no_argument, 0, 1014}, {"split-polish-min-depth", required_argument, 0, 1015},
                                        {"correct", no_argument, 0, 1016}, {"correct-min-depth", required_argument, 0, 1017},
                                        {"correct-min-alt", required_argument, 0, 1018}, {"correct-min-pct", required_argument, 0, 1019},
-                                       {"correct-max-run", required_argument, 0, 1020}, {0, 0, 0, 0}};
+                                       {"correct-max-run", required_argument, 0, 1020},
+                                       {"isoforms", no_argument, 0, 1021}, {"isoforms-min-gap", required_argument, 0, 1022},
+                                       {"isoforms-min-depth", required_argument, 0, 1023}, {"isoforms-min-alt", required_argument, 0, 1024},
+                                       {"isoforms-min-pct", required_argument, 0, 1025}, {"isoforms-min-block", required_argument, 0, 1026},
+                                       {"isoforms-max", required_argument, 0, 1027}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false;
@@ -143,6 +167,13 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1018: r.correct.min_alt = number("--correct-min-alt", optarg, 1, INT32_MAX); break;
             case 1019: r.correct.min_pct = number("--correct-min-pct", optarg, 1, 50); break;
             case 1020: r.correct.max_run = number("--correct-max-run", optarg, 0, 64); break;
+            case 1021: r.isoforms.on = true; break;
+            case 1022: r.isoforms.min_gap = number("--isoforms-min-gap", optarg, 1, INT32_MAX); break;
+            case 1023: r.isoforms.min_depth = number("--isoforms-min-depth", optarg, 1, INT32_MAX); break;
+            case 1024: r.isoforms.min_alt = number("--isoforms-min-alt", optarg, 1, INT32_MAX); break;
+            case 1025: r.isoforms.min_pct = number("--isoforms-min-pct", optarg, 1, 50); break;
+            case 1026: r.isoforms.min_block = number("--isoforms-min-block", optarg, 1, INT32_MAX); break;
+            case 1027: r.isoforms.max_blocks = number("--isoforms-max", optarg, 1, 32); break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -328,7 +359,8 @@ int main_dump(int argc, char** argv)
         const string names = string(reports.stats ? "read_stats.tsv, " : "") + (reports.pileup ? "cluster_pileup.tsv, " : "") +
                              (reports.polish() ? "cluster_polished.fq, " : "") + (reports.sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") +
                              (reports.split.on ? "cluster_split.tsv, read_split.tsv, " : "") + (reports.group_polish() ? "cluster_split_polished.fq, " : "") +
-                             (reports.correct.on ? "corrected_reads.fq, " : "");
+                             (reports.correct.on ? "corrected_reads.fq, " : "") +
+                             (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

@@ -118,6 +118,13 @@ int64_t correct_capacity(const ReportGroup& g)
     return cap;
 }
 
+int64_t blocks_capacity(const ReportGroup& g, int max_blocks)
+{
+    int64_t cap = 0;
+    for (const ioc_polish_seg& sg : g.segs) cap += std::min<int64_t>(max_blocks, ref_len(g, sg));
+    return cap;
+}
+
 SiteCapacity site_capacity(const ReportGroup& g, int max_sites)
 {
     SiteCapacity cap;
@@ -158,4 +165,48 @@ string corrected_record(const char* id, size_t id_len, unsigned cls, const char*
     text.append(read, lead).append(cseq, clen).append(read + read_len - trail, trail).append("\n+\n");
     text.append(own_qual, 0, lead).append(cqual, clen).append(own_qual, read_len - trail, trail).append("\n");
     return text;
+}
+
+string blocks_signature(uint64_t key, int32_t n_blocks)
+{
+    string text;
+    for (int32_t b = 0; b < n_blocks && b < IOC_BLOCKS_MAX; ++b) text += "=-~."[(key >> (2 * b)) & 3u];
+    return text.empty() ? "*" : text;
+}
+
+string cluster_blocks_rows(size_t cluster, const ioc_blocks_seg& z, const ioc_pile_block* blocks)
+{
+    const string id = std::to_string(cluster);
+    string text;
+    if (z.n_found > z.n_blocks) text += "# cluster " + id + ": kept " + std::to_string(z.n_blocks) + " of " + std::to_string(z.n_found) + " blocks\n";
+    for (int32_t b = 0; b < z.n_blocks; ++b) {
+        const ioc_pile_block& k = blocks[b];
+        text += id + '\t' + std::to_string(b) + '\t' + std::to_string(k.first) + '\t' + std::to_string(k.end) + '\t' + std::to_string(k.n_keep) + '\t' +
+                std::to_string(k.n_skip) + '\t' + std::to_string(k.n_part) + '\t' + std::to_string(k.n_none) + '\n';
+    }
+    return text;
+}
+
+string cluster_isoforms_rows(size_t cluster, const ioc_blocks_seg& z, const std::vector<ioc_read_blocks>& reads)
+{
+    const size_t n = size_t(std::max(z.n_groups, 0));
+    std::vector<uint64_t> key(n, 0);
+    std::vector<int64_t> direct(n, 0), assigned(n, 0);
+    for (const ioc_read_blocks& r : reads) {
+        if (r.group < 0 || size_t(r.group) >= n) continue;
+        if (r.how == IOC_ISO_DIRECT) key[size_t(r.group)] = r.key, ++direct[size_t(r.group)];
+        if (r.how == IOC_ISO_ASSIGNED) ++assigned[size_t(r.group)];
+    }
+    string text;
+    for (size_t x = 0; x < n; ++x)
+        text += std::to_string(cluster) + '\t' + std::to_string(x) + '\t' + blocks_signature(key[x], z.n_blocks) + '\t' + std::to_string(direct[x]) + '\t' +
+                std::to_string(assigned[x]) + '\n';
+    return text;
+}
+
+string read_isoform_columns(const ioc_read_blocks& r, int32_t n_blocks)
+{
+    const char* const how = r.how == IOC_ISO_DIRECT ? "direct" : r.how == IOC_ISO_ASSIGNED ? "assigned" : r.how == IOC_ISO_RARE ? "rare" : "ambiguous";
+    return (r.group < 0 ? string(".") : std::to_string(r.group)) + '\t' + how + '\t' + blocks_signature(r.key, n_blocks) + '\t' + std::to_string(r.first_row) + '\t' +
+           std::to_string(r.end_row) + '\t' + std::to_string(r.n_gaps) + '\t' + std::to_string(r.gap_rows);
 }

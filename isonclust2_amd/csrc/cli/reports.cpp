@@ -51,6 +51,13 @@
 // read as cluster_fastq/<id>.fq has it with its aligned part corrected, the ends the alignment leaves free as they are (corrected_record,
 // report_plan.cpp); a read whose alignment inserts more than six bases in a row is written as it is and marked.  The other report
 // files are what they are without the option.
+//
+// dump --isoforms: <outdir>/cluster_blocks.tsv, cluster_isoforms.tsv and read_isoforms.tsv (ioc_align_pairs_blocks: the alignment, the
+// table of counts and every read's base plane of --sites, and the block search over the planes where they lie; a call of its own,
+// which takes the statistics and the first table when no call before it has).  cluster_blocks.tsv: the stretches of a cluster's
+// representative that some of its reads skip, with how many reads keep, skip, half-skip or do not reach each; cluster_isoforms.tsv:
+// the signatures that enough reads carry; read_isoforms.tsv: one row per row read_stats.tsv has, in that order (report_plan.cpp
+// formats all three).  The other report files are what they are without the option.
 #include "reports.hpp"
 
 #include <cstdio>
@@ -94,6 +101,10 @@ struct GroupResult {
     std::vector<int64_t> coff;
     std::vector<ioc_correct_stats> cstats;
     std::vector<ioc_aln_stats> caln;
+    std::vector<ioc_pile_block> blocks;  // (--isoforms) segment g's kept blocks at [block_off[g], block_off[g + 1]), its record, and pair x's
+    std::vector<int64_t> block_off;
+    std::vector<ioc_blocks_seg> blocks_seg;
+    std::vector<ioc_read_blocks> read_blocks;
 };
 
 // a row of the three per-read tables
@@ -109,9 +120,11 @@ struct RowResult {
     // FASTQ and so interleave the clusters, while the groups come cluster by cluster: the records wait here until the last group
     // is done, the whole corrected read set in host memory (the other per-read tables keep a few words a row)
     string corrected;
+    ioc_read_blocks iso{};           // (--isoforms) the read's record, and how many blocks its cluster kept
+    int32_t iso_blocks = 0;
 };
 
-// The one place that chooses a library call.  --sites and / or --split come first; --polish and --correct are calls of their own,
+// The one place that chooses a library call.  --sites and / or --split come first; --polish, --correct and --isoforms are calls of their own,
 // each of which takes the statistics and the first table only when no call before it produced them; otherwise the pileup;
 // otherwise the statistics.
 void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupResult& r)
@@ -200,6 +213,20 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
         if (o.stats && !have_first) r.stats = r.caln;
         have_first = true;
     }
+    if (o.isoforms.on) {
+        const IsoformsOpt& io = o.isoforms;
+        const int64_t cap = blocks_capacity(g, io.max_blocks);
+        r.blocks.assign(size_t(std::max<int64_t>(cap, 1)), ioc_pile_block{}), r.block_off.assign(ns + 1, 0), r.blocks_seg.assign(ns, ioc_blocks_seg{});
+        r.read_blocks.assign(np, ioc_read_blocks{});
+        std::vector<ioc_aln_stats> aln(o.stats && !have_first ? np : 0);
+        if (o.pileup && !have_first) r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
+        check(c, ioc_align_pairs_blocks(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
+                                        io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
+                                        r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr),
+              "exon blocks");
+        if (o.stats && !have_first) r.stats = aln;
+        have_first = true;
+    }
     if (have_first) return;
     if (o.pileup) {
         r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
@@ -223,6 +250,7 @@ void scatter_to_rows(const ReportOpts& o, const ReportRows& rows, const ReportGr
                 row.alleles += allele_char(r.sites[size_t(s0 + a - r.allele_off[x])].kind, r.alleles[size_t(a)]);
             if (row.alleles.empty()) row.alleles = "*";
         }
+        if (o.isoforms.on) row.iso = r.read_blocks[x], row.iso_blocks = r.blocks_seg[size_t(g.seg_of_pair[x])].n_blocks;
         if (o.correct.on) {
             const ReadStatRow& rd = rows.row(g.pair_row[x]);
             const size_t q0 = size_t(g.offs[size_t(g.pairs[x].query)]), l0 = size_t(g.qoffs[size_t(g.pair_q[x])]), l1 = size_t(g.qoffs[size_t(g.pair_q[x]) + 1]);
@@ -334,9 +362,23 @@ void write_group_polish(std::ofstream& out, const ReportGroup& g, const GroupRes
     }
 }
 
+void write_blocks(std::ofstream& blocks, std::ofstream& isoforms, const ReportGroup& g, const GroupResult& r)
+{
+    std::vector<std::vector<ioc_read_blocks>> mine(g.segs.size());
+    for (size_t x = 0; x < g.pairs.size(); ++x) mine[size_t(g.seg_of_pair[x])].push_back(r.read_blocks[x]);
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0) continue;
+        const string rows = cluster_blocks_rows(g.group_cls[x].first, r.blocks_seg[size_t(s)], r.blocks.data() + r.block_off[size_t(s)]);
+        const string iso = cluster_isoforms_rows(g.group_cls[x].first, r.blocks_seg[size_t(s)], mine[size_t(s)]);
+        blocks.write(rows.data(), std::streamsize(rows.size()));
+        isoforms.write(iso.data(), std::streamsize(iso.size()));
+    }
+}
+
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -353,6 +395,12 @@ struct GroupFiles {
             split << "ClusterId\tNSites\tNLinked\tSeedPos\tSeedKind\tNReads\tNGroup0\tNGroup1\tNNone\n";
         }
         if (o.group_polish()) create_file(outdir + "/cluster_split_polished.fq", group_polish);
+        if (o.isoforms.on) {
+            create_file(outdir + "/cluster_blocks.tsv", blocks);
+            blocks << "ClusterId\tBlock\tFirst\tEnd\tKeep\tSkip\tPart\tNone\n";
+            create_file(outdir + "/cluster_isoforms.tsv", isoforms);
+            isoforms << "ClusterId\tIsoform\tSignature\tDirect\tAssigned\n";
+        }
     }
     void write(const Batch& b, const ReportOpts& o, const ReportGroup& g, const GroupResult& r)
     {
@@ -361,6 +409,7 @@ struct GroupFiles {
         if (o.sites.on && !g.segs.empty()) write_sites(sites, g, r);
         if (o.split.on) write_split(split, g, r);
         if (o.group_polish() && !g.segs.empty()) write_group_polish(group_polish, g, r);
+        if (o.isoforms.on && !g.segs.empty()) write_blocks(blocks, isoforms, g, r);
     }
 };
 
@@ -386,6 +435,19 @@ void write_read_split(const string& outdir, const ReportRows& rows, const std::v
         const ReadStatRow& r = rows.row(y);
         out.write(r.id, std::streamsize(r.id_len));
         out << '\t' << r.cls << '\t' << (res[y].group == 0 ? "0" : res[y].group == 1 ? "1" : ".") << '\t' << res[y].vote << '\n';
+    }
+}
+
+void write_read_isoforms(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/read_isoforms.tsv", out);
+    out << "ClusterId\tRead\tIsoform\tHow\tSignature\tFirst\tEnd\tGaps\tGapRows\n";
+    for (size_t y = 0; y < rows.kept.size(); ++y) {
+        const ReadStatRow& r = rows.row(y);
+        out << r.cls << '\t';
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << read_isoform_columns(res[y].iso, res[y].iso_blocks) << '\n';
     }
 }
 
@@ -438,4 +500,5 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
     if (opts.split.on) write_read_split(outdir, rows, res);
     if (opts.stats) write_read_stats(outdir, rows, res);
     if (opts.correct.on) write_corrected_reads(outdir, res);
+    if (opts.isoforms.on) write_read_isoforms(outdir, rows, res);
 }

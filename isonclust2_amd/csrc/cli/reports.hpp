@@ -1,4 +1,4 @@
-// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct): every read of clusters.tsv
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms): every read of clusters.tsv
 // aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
 // formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
 #ifndef ISONCLUST2_CLI_REPORTS_HPP
@@ -25,6 +25,10 @@ struct CorrectOpt {  // --correct: the thresholds of ioc_host_read_correct
     bool on = false;
     int min_depth = 3, min_alt = 3, min_pct = 25, max_run = 10;
 };
+struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
+    bool on = false;
+    int min_gap = 20, min_depth = 3, min_alt = 3, min_pct = 25, min_block = 10, max_blocks = 32;
+};
 struct ReportOpts {
     bool stats = false;        // --read-stats
     bool pileup = false;       // --pileup
@@ -33,9 +37,10 @@ struct ReportOpts {
     SitesOpt sites;
     SplitOpt split;
     CorrectOpt correct;
+    IsoformsOpt isoforms;
     bool polish() const { return polish_min_depth > 0; }
     bool group_polish() const { return split.on && split.polish_min_depth > 0; }
-    bool segs() const { return polish() || sites.on || split.on || correct.on; }  // the calls that take the clusters as segments
+    bool segs() const { return polish() || sites.on || split.on || correct.on || isoforms.on; }  // the calls that take the clusters as segments
     bool groups() const { return pileup || segs(); }                // something is written per group
     bool any() const { return stats || groups(); }
 };
@@ -101,6 +106,21 @@ SiteCapacity site_capacity(const ReportGroup& g, int max_sites);
 
 // what the correction of every read of a group may return at most: every pair's segment's bound
 int64_t correct_capacity(const ReportGroup& g);
+
+// the blocks a block search may keep at most, for all segments of a group: min(max_blocks, the representative's length) each
+int64_t blocks_capacity(const ReportGroup& g, int max_blocks);
+// A signature: one character per kept block from the key's two bits each — '=' keep, '-' skip, '~' part, '.' none —, "*" where the
+// cluster has no block.
+std::string blocks_signature(uint64_t key, int32_t n_blocks);
+// the rows of cluster_blocks.tsv of one cluster: "# cluster <id>: kept <n> of <found> blocks" where the list was cut, then
+// "<id> <block> <first> <end> <keep> <skip> <part> <none>" per kept block
+std::string cluster_blocks_rows(size_t cluster, const ioc_blocks_seg& z, const ioc_pile_block* blocks);
+// the rows of cluster_isoforms.tsv of one cluster, "<id> <isoform> <signature> <direct> <assigned>" per isoform, from the records
+// of its reads (any order)
+std::string cluster_isoforms_rows(size_t cluster, const ioc_blocks_seg& z, const std::vector<ioc_read_blocks>& reads);
+// the columns of read_isoforms.tsv behind the cluster and the read: "<isoform or .> <direct|assigned|rare|ambiguous> <signature>
+// <first> <end> <gaps> <gap rows>"
+std::string read_isoform_columns(const ioc_read_blocks& r, int32_t n_blocks);
 
 char allele_char(int32_t kind, int32_t a);
 // "@<name> reads= subs= dels= ins= low=<tail>", the sequence, "+", the qualities

@@ -20,6 +20,7 @@
 #include "ioc_align_sink.h"
 #include "ioc_pile_call.h"
 #include "ioc_pile_sites.h"
+#include "ioc_read_blocks.h"
 #include "ioc_read_correct.h"
 #include "ioc_site_split.h"
 
@@ -624,6 +625,104 @@ int64_t ioc_host_read_correct(const uint8_t* base, const uint8_t* slots, int32_t
     s.out_len = int32_t(at);
     if (st) *st = s;
     return at;
+}
+
+// The exon blocks of one segment and every read's isoform (isonclust2_hip.h has the rules; blocks_row_variable, blocks_state and
+// blocks_key_agrees, ioc_read_blocks.h, decide for this function and for the kernels of ioc_read_blocks.hip alike).  The plain
+// loops: every read's long gaps, the row table, the runs of variable rows, a state per read and kept block, and the supported keys
+// in ascending unsigned order.
+int ioc_host_planes_blocks(const uint8_t* base, int32_t n_reads, int32_t rlen, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                           int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, ioc_read_blocks* out_reads,
+                           ioc_blocks_seg* out_seg)
+{
+    const BlocksRule rule{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks};
+    if (!rule.ok() || n_reads < 0 || rlen < 0 || !out_seg || (n_reads > 0 && (!base || !out_reads)) || (rlen > 0 && !out_blocks)) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1, n = size_t(n_reads);
+    std::vector<ioc_block_row> table(rows, ioc_block_row{0, 0});
+    std::vector<ioc_read_blocks> reads(n, ioc_read_blocks{});
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t* b = base + i * rows;
+        ioc_read_blocks& rd = reads[i];
+        for (int32_t p = 0; p < rlen; ++p)
+            if (blocks_covers(b[p])) {
+                ++table[size_t(p)].depth;
+                if (rd.end_row == 0) rd.first_row = p;
+                rd.end_row = p + 1;
+            }
+        for (int32_t a = 0; a < rlen;) {
+            int32_t e = a + 1;
+            if (b[a] == uint8_t(IOC_ALLELE_DEL)) {
+                while (e < rlen && b[e] == uint8_t(IOC_ALLELE_DEL)) ++e;
+                if (e - a >= min_gap) {
+                    ++rd.n_gaps, rd.gap_rows += e - a;
+                    for (int32_t p = a; p < e; ++p) ++table[size_t(p)].in_gap;
+                }
+            }
+            a = e;
+        }
+    }
+    std::vector<ioc_pile_block> blocks;
+    int32_t n_found = 0;
+    for (int32_t a = 0; a < rlen;) {
+        int32_t e = a + 1;
+        if (blocks_row_variable(rule, table[size_t(a)].depth, table[size_t(a)].in_gap)) {
+            while (e < rlen && blocks_row_variable(rule, table[size_t(e)].depth, table[size_t(e)].in_gap)) ++e;
+            if (e - a >= min_block) {
+                if (n_found < max_blocks) blocks.push_back(ioc_pile_block{a, e, 0, 0, 0, 0, {0, 0}});
+                ++n_found;
+            }
+        }
+        a = e;
+    }
+    const uint32_t nb = uint32_t(blocks.size());
+    const unsigned long long full = blocks_full_mask(nb);
+    std::vector<unsigned long long> mask(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t* b = base + i * rows;
+        for (uint32_t k = 0; k < nb; ++k) {
+            uint32_t c = 0, s = 0;
+            for (int32_t p = blocks[k].first; p < blocks[k].end; ++p) c += blocks_covers(b[p]), s += b[p] == uint8_t(IOC_ALLELE_DEL);
+            const uint32_t st = blocks_state(uint32_t(blocks[k].end - blocks[k].first), c, s);
+            reads[i].key |= uint64_t(st) << (2u * k);
+            mask[i] |= blocks_state_mask(k, st);
+            ++(st == IOC_BLOCK_KEEP ? blocks[k].n_keep : st == IOC_BLOCK_SKIP ? blocks[k].n_skip : st == IOC_BLOCK_PART ? blocks[k].n_part : blocks[k].n_none);
+        }
+    }
+    std::vector<uint64_t> complete, keys;  // the keys of the complete reads, sorted; the supported ones, ascending and unsigned
+    for (size_t i = 0; i < n; ++i)
+        if (mask[i] == full) complete.push_back(reads[i].key);
+    std::sort(complete.begin(), complete.end());
+    for (size_t a = 0; a < complete.size();) {
+        size_t e = a;
+        while (e < complete.size() && complete[e] == complete[a]) ++e;
+        if (e - a >= size_t(min_alt)) keys.push_back(complete[a]);
+        a = e;
+    }
+    ioc_blocks_seg seg{int32_t(nb), n_found, int32_t(keys.size()), n_reads, 0, 0, 0, 0};
+    for (size_t i = 0; i < n; ++i) {
+        ioc_read_blocks& rd = reads[i];
+        rd.group = -1;
+        if (mask[i] == full) {
+            const auto it = std::lower_bound(keys.begin(), keys.end(), rd.key);
+            if (it != keys.end() && *it == rd.key)
+                rd.group = int32_t(it - keys.begin()), rd.how = IOC_ISO_DIRECT, ++seg.n_direct;
+            else
+                rd.how = IOC_ISO_RARE, ++seg.n_rare;
+            continue;
+        }
+        int32_t agreeing = 0, which = -1;
+        for (size_t k = 0; k < keys.size() && mask[i] != 0ull; ++k)
+            if (blocks_key_agrees(rd.key, keys[k], mask[i])) ++agreeing, which = int32_t(k);
+        if (agreeing == 1)
+            rd.group = which, rd.how = IOC_ISO_ASSIGNED, ++seg.n_assigned;
+        else
+            rd.how = IOC_ISO_AMBIGUOUS, ++seg.n_ambiguous;
+    }
+    if (out_rows) std::copy(table.begin(), table.end(), out_rows);
+    std::copy(blocks.begin(), blocks.end(), out_blocks);
+    std::copy(reads.begin(), reads.end(), out_reads);
+    *out_seg = seg;
+    return IOC_OK;
 }
 
 // setGapOpen, src/cluster.cpp:425-440

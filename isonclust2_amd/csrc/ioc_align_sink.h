@@ -27,6 +27,7 @@ struct AlnTally {
     double ms_project_ins = 0;  // k_ops_project_ins' device time (a pile that projects what the pairs insert as well), and ...
     double ms_plane_pile = 0;   // ... k_plane_pile's (ioc_planes_polish, ioc_align_pairs_split_polish)
     double ms_correct = 0;      // k_read_correct's device time, both passes and the scan (ioc_planes_correct, ioc_align_pairs_correct)
+    double ms_blocks = 0;       // the eight kernels of ioc_read_blocks.hip, their device time together (ioc_planes_blocks, ioc_align_pairs_blocks)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
     int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };

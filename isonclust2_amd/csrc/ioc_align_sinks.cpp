@@ -3,7 +3,7 @@
 // (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.  An entry point checks its arguments, plans its
 // segments and pairs on the host (SinkPlan, ioc_sink_plan.h) and runs device stages in a row (SinkRun): pile -> sites -> alleles ->
 // [split] -> [group pile -> call] -> copy-out for the alleles family, pile -> call -> copy-out for the polish family, pile -> correct ->
-// copy-out for the read correction, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
+// copy-out for the read correction, pile -> blocks -> copy-out for the exon blocks, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +15,7 @@
 #include "ioc_align_sink.h"
 #include "ioc_internal.h"
 #include "ioc_plane_pile.h"
+#include "ioc_read_blocks.h"
 #include "ioc_read_correct.h"
 
 namespace {
@@ -61,6 +62,16 @@ struct CorrectOut {  // the rule of a read correction and where it leaves every 
     int64_t* off;
     ioc_correct_stats* stats;
     bool ok() const { return rule.ok() && off && cap >= 0; }
+};
+struct BlocksOut {  // the rule of a block search and where it leaves what it made (cap: the records `blocks` holds)
+    BlocksRule rule;
+    ioc_block_row* rows;
+    ioc_pile_block* blocks;
+    int64_t cap;
+    int64_t* block_off;
+    ioc_read_blocks* reads;
+    ioc_blocks_seg* seg;
+    bool ok() const { return rule.ok() && block_off && cap >= 0; }
 };
 // what a call refuses once its bound is known: IOC_OK, or the status with the message set
 int call_room_ok(ioc_ctx* c, const std::string& who, const CallOut& o, int64_t bound)
@@ -143,6 +154,7 @@ struct SinkRun {
     int group_pile(const SinkPlan& p, const int32_t* seg_of_pair, const Planes& host, Planes dev, GroupPiled& d);
     int correct(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* d_frames, uint64_t frame_bytes, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
                 const Planes& host, Planes dev, const CorrectOut& o);
+    int blocks(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o);
 };
 
 // Pile and project.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it (ins), or a_pile_w as [wcols][wins] (weighted)
@@ -397,6 +409,64 @@ int SinkRun::correct(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8
     settled();
     return copy_out({{o.off, p + o_off, (np + 1) * 8}, {o.stats, p + o_st, np * sizeof(ioc_correct_stats)}, {o.seq, q + o_seq, size_t(total)},
                      {o.qual, q + o_qual, size_t(total)}});
+}
+
+// The kernels of ioc_read_blocks.hip over the plan's pairs: the base planes lie on the device (dev_base) or are the host's and
+// uploaded.  a_blocks holds the host's tables [segments][seg_of_pair][plane offsets][mem_off][members][pair_word][seg_word][word_seg]
+// [block_base], the kernels' own [covered][deleted][long gaps][variable rows][masks][flags][row table][block slots][read records]
+// [segment records] and, uploaded, [base plane].  The segment records come back first: they say how many of a segment's slots are
+// blocks, and the blocks are packed on the host.
+int SinkRun::blocks(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o)
+{
+    const size_t n = pn.segs.size(), np = pn.plane.size(), B = size_t(pn.plane_bytes);
+    const BlocksTables bt = blocks_tables(pn, seg_of_pair, o.rule.max_blocks);
+    const MemberLists m = member_lists(n, np, seg_of_pair);
+    const size_t P = bt.P, T = bt.T, slots = size_t(bt.block_base[n]);
+    Arena l;
+    const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_plane = l.take(np * 8), o_moff = l.take((n + 1) * 4), o_mem = l.take(np * 4),
+                 o_pw = l.take(np * 8), o_sw = l.take((n + 1) * 8), o_ws = l.take(T * 4), o_bb = l.take((n + 1) * 8), tables = l.size();
+    const size_t o_cov = l.take(P * 8), o_del = l.take(P * 8), o_gap = l.take(P * 8), o_var = l.take(T * 8), o_mask = l.take(np * 8), o_flags = l.take(np),
+                 o_rows = l.take(size_t(pn.n_rows) * sizeof(ioc_block_row)), o_blk = l.take(slots * sizeof(ioc_pile_block)),
+                 o_reads = l.take(np * sizeof(ioc_read_blocks)), o_rec = l.take(n * sizeof(ioc_blocks_seg)), o_end = l.size(),
+                 o_base = l.take(dev_base ? 0 : B);
+    std::vector<uint8_t> stage(tables, 0);
+    auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
+    put(o_seg, pn.segs.data(), n * sizeof(IocPileSeg)), put(o_sop, seg_of_pair, np * 4), put(o_plane, pn.plane.data(), np * 8);
+    put(o_moff, m.mem_off.data(), (n + 1) * 4), put(o_mem, m.members.data(), np * 4), put(o_pw, bt.pair_word.data(), np * 8);
+    put(o_sw, bt.seg_word.data(), (n + 1) * 8), put(o_ws, bt.word_seg.data(), T * 4), put(o_bb, bt.block_base.data(), (n + 1) * 8);
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_blocks, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_blocks.p);
+    IOC_CHK(c, hipMemcpyAsync(p, stage.data(), tables, hipMemcpyHostToDevice, c->stream));
+    if (!dev_base && B) IOC_CHK(c, hipMemcpyAsync(p + o_base, host_base, B, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemsetAsync(p + o_blk, 0, o_end - o_blk, c->stream));  // (the block slots and both kinds of record)
+    auto u64p = [&](size_t at) { return reinterpret_cast<unsigned long long*>(p + at); };
+    const IocReadBlocksDev v{reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop),
+                             reinterpret_cast<const uint64_t*>(p + o_plane), dev_base ? dev_base : p + o_base, uint64_t(B),
+                             reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem),
+                             reinterpret_cast<const uint64_t*>(p + o_pw), reinterpret_cast<const uint64_t*>(p + o_sw), reinterpret_cast<const int32_t*>(p + o_ws),
+                             reinterpret_cast<const int64_t*>(p + o_bb), uint64_t(P), uint64_t(T), uint64_t(pn.n_rows), uint64_t(slots), u64p(o_cov), u64p(o_del),
+                             u64p(o_gap), u64p(o_var), u64p(o_mask), p + o_flags, reinterpret_cast<ioc_block_row*>(p + o_rows),
+                             reinterpret_cast<ioc_pile_block*>(p + o_blk), reinterpret_cast<ioc_read_blocks*>(p + o_reads), reinterpret_cast<ioc_blocks_seg*>(p + o_rec)};
+    const BlocksRule& k = o.rule;
+    IOC_TRY(begin(t.ms_blocks));
+    IOC_CHK(c, iock_read_blocks(c->stream, v, k.min_gap, k.min_depth, k.min_alt, k.min_pct, k.min_block, k.max_blocks));
+    IOC_TRY(end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    settled();
+    std::vector<ioc_blocks_seg> rec(n);
+    std::vector<ioc_pile_block> slot(slots);
+    IOC_TRY(copy_out({{rec.data(), p + o_rec, n * sizeof(ioc_blocks_seg)}, {slot.data(), p + o_blk, slots * sizeof(ioc_pile_block)}}));
+    for (size_t g = 0; g < n; ++g)
+        if (rec[g].n_blocks < 0 || rec[g].n_blocks > bt.block_base[g + 1] - bt.block_base[g])
+            return ioc_fail(c, IOC_ERR_HIP, "the block search returned a count outside its bound");
+    o.block_off[0] = 0;
+    for (size_t g = 0; g < n; ++g) {
+        std::copy(slot.begin() + bt.block_base[g], slot.begin() + bt.block_base[g] + rec[g].n_blocks, o.blocks + o.block_off[g]);
+        o.block_off[g + 1] = o.block_off[g] + rec[g].n_blocks;
+        o.seg[g] = rec[g];
+    }
+    return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_blocks)}, {o.rows, p + o_rows, size_t(pn.n_rows) * sizeof(ioc_block_row)}});
 }
 
 }  // namespace
@@ -835,6 +905,67 @@ int ioc_align_pairs_correct(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pai
         fprintf(stderr, "[ioc]   aligner: correct: %d segments, %lld rows, %d pairs, %lld bytes written, %.3f MB (corrected bytes, records, lengths%s%s) copied from the device in %.3f ms, k_ops_pileup<ins> %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, k_read_correct %.3f ms%s\n",
                 n_segs, (long long)p.n_rows, n_pairs, (long long)out_off[n_pairs], double(r.t.copied) * 1e-6, out_cols || out_ins ? ", tables" : "",
                 out_stats ? ", statistics" : "", r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_project_ins, r.t.ms_correct,
+                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+// what a block search refuses once its plan is known: IOC_OK, or the status with the message set
+static int blocks_room_ok(ioc_ctx* c, const std::string& who, const BlocksOut& o, const SinkPlan& p)
+{
+    const int64_t bound = p.blocks_bound(o.rule.max_blocks);
+    if (o.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": blocks_cap " + std::to_string(o.cap) + " below the bound " + std::to_string(bound));
+    return (bound > 0 && !o.blocks) || (!p.plane.empty() && !o.reads) || (!p.segs.empty() && !o.seg) ? IOC_ERR_ARG : IOC_OK;
+}
+
+// upload -> blocks -> copy-out.  The block search from base planes the caller holds: they are uploaded, and the kernels run as
+// behind ioc_align_pairs_blocks.
+int ioc_planes_blocks(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const uint8_t* base, int32_t min_gap,
+                      int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                      ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg)
+{
+    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || (n_segs > 0 && !rlen) || (n_pairs > 0 && !seg_of_pair)) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen("ioc_planes_blocks", n_segs, rlen, nullptr, nullptr, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && !base) return IOC_ERR_ARG;
+    IOC_TRY(blocks_room_ok(c, "ioc_planes_blocks", o, p));
+    block_off[0] = 0;
+    if (n_segs == 0) return IOC_OK;
+    SinkRun r{c};
+    IOC_TRY(r.blocks(p, seg_of_pair, base, nullptr, o));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes blocks: %d segments, %lld rows, %d pairs, %lld plane bytes, %lld blocks kept, the block kernels %.3f ms\n", n_segs,
+                (long long)p.n_rows, n_pairs, (long long)p.plane_bytes, (long long)block_off[n_segs], r.t.ms_blocks);
+    return IOC_OK;
+}
+
+// pile -> blocks -> copy-out.  ioc_align_pairs_alleles' pile, the table of counts with every pair projected beside it, and the block
+// kernels over the base planes where they lie: what comes back is the blocks, a record per pair and per segment, and the tables
+// only where they are asked for.
+int ioc_align_pairs_blocks(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                           int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
+                           const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
+                           int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off,
+                           ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols)
+{
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
+    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_pool("ioc_align_pairs_blocks", c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
+    IOC_TRY(blocks_room_ok(c, "ioc_align_pairs_blocks", o, p));
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    block_off[0] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    SinkRun r{c};
+    PiledDev d;
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d));
+    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o));  // (a_blocks is reserved here, after the walks)
+    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: blocks: %d segments, %lld rows, %d pairs, %lld blocks kept, %.3f MB (blocks, records%s%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms%s\n",
+                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], double(r.t.copied) * 1e-6, out_rows ? ", rows" : "", out_cols ? ", table" : "",
+                out_stats ? ", statistics" : "", r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_blocks,
                 out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
     return IOC_OK;
 }

@@ -221,6 +221,8 @@ struct ioc_ctx {
                       // from host planes, the uploaded member lists and planes
     DevBuf a_correct; // ioc_planes_correct, ioc_align_pairs_correct: segments, pairs, offsets, records and the corrected bytes (ioc_read_correct.hip) and,
                       // from host planes, the uploaded planes
+    DevBuf a_blocks;  // ioc_planes_blocks, ioc_align_pairs_blocks: segments, pairs, member lists, bit planes, tables and records (ioc_read_blocks.hip) and,
+                      // from host planes, the uploaded planes
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
     std::vector<uint8_t> aln_other;  // per pool sequence: holds a byte other than A C G T
     std::vector<int64_t> aln_offs;
@@ -441,6 +443,35 @@ hipError_t iock_read_correct_count(hipStream_t st, const IocReadCorrectDev& v, i
                                    int64_t* out_off);
 hipError_t iock_read_correct_emit(hipStream_t st, const IocReadCorrectDev& v, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
                                   const int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);
+
+// ioc_read_blocks.hip: the exon blocks of many segments and every read's isoform (ioc_host_planes_blocks per segment).  Everything
+// is a device pointer.  Pair i belongs to segment seg_of_pair[i], has its rows from byte plane[i] on of the base planes and its
+// words — ceil((rlen + 1) / 64) of each bit plane (cov, del, gap: n_pair_words words each) — from word pair_word[i] on.  Segment g:
+// the pairs members[mem_off[g] .. mem_off[g + 1]) in ascending order as its reads, its words of `var` from seg_word[g] on
+// (n_seg_words in all; word_seg says whose each is), its rows of `rows` from segs[g].row0 on and its min(max_blocks, rlen) block
+// slots from block_base[g] on (n_block_slots in all).  mask / flags: a word and a byte of scratch per pair.  reads and seg_out are
+// set to 0 by the caller.
+struct IocReadBlocksDev {
+    const IocPileSeg* segs;
+    uint32_t n_segs, n_pairs;
+    const int32_t* seg_of_pair;
+    const uint64_t* plane;
+    const uint8_t* base_planes;
+    uint64_t plane_bytes;
+    const uint32_t *mem_off, *members;
+    const uint64_t *pair_word, *seg_word;
+    const int32_t* word_seg;
+    const int64_t* block_base;
+    uint64_t n_pair_words, n_seg_words, n_rows, n_block_slots;
+    unsigned long long *cov, *del, *gap, *var, *mask;
+    uint8_t* flags;
+    ioc_block_row* rows;
+    ioc_pile_block* blocks;
+    ioc_read_blocks* reads;
+    ioc_blocks_seg* seg_out;
+};
+hipError_t iock_read_blocks(hipStream_t st, const IocReadBlocksDev& v, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                            int32_t min_block, int32_t max_blocks);
 
 // ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
 // is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in

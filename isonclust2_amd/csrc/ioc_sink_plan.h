@@ -75,6 +75,8 @@ inline SplitTables split_tables(size_t n_segs, const int64_t* site_off, const st
 // two, its insertion site and its base site, and row rlen one.
 inline int64_t pile_call_most(int64_t rlen) { return rlen + int64_t(IOC_PILE_INS_SLOTS) * (rlen + 1); }
 inline int64_t pile_sites_most(int64_t rlen, int32_t max_sites) { return std::min<int64_t>(max_sites, 2 * rlen + 1); }
+// (a block search keeps at most max_blocks blocks of a segment, and a block has at least one row)
+inline int64_t pile_blocks_most(int64_t rlen, int32_t max_blocks) { return std::min<int64_t>(max_blocks, rlen); }
 inline int64_t pile_call_bound(const std::vector<IocPileSeg>& segs)
 {
     return std::accumulate(segs.begin(), segs.end(), int64_t(0), [](int64_t b, const IocPileSeg& s) { return b + pile_call_most(s.rlen); });
@@ -87,7 +89,8 @@ inline int64_t pile_sites_bound(const std::vector<IocPileSeg>& segs, int32_t max
 // The segments and the pairs of a call.  Segment g owns the rows segs[g].row0 .. + rlen of the call's tables, n_rows in all; pair
 // i is piled from row_base[i] on, its segment's first row, and has rlen + 1 bytes from plane[i] on in every plane of plane_bytes
 // bytes (the pairs one behind the other); alleles_bound: a byte per pair and site its segment may keep (from_pool); correct_bound:
-// what the correction of every pair may write, its segment's call bound each (ioc_planes_correct asks it of cap).  frame_bytes:
+// what the correction of every pair may write, its segment's call bound each (ioc_planes_correct asks it of cap); blocks_bound(m):
+// the blocks a block search of max_blocks m may keep over all segments (ioc_planes_blocks asks it of blocks_cap).  frame_bytes:
 // what the frames take of their pool (from_rlen).  A constructor returns IOC_OK, or the status of what it refuses with msg set —
 // the caller hands both to ioc_fail; `who` names the entry point in it.  What only some entry points refuse: a segment of more than
 // 2^30 bases (the site search: two sites a row) / one that may call more than 2^31 - 1 bytes (the record's out_len, the kernels' byte counts).
@@ -97,6 +100,10 @@ struct SinkPlan {
     std::vector<int64_t> row_base, plane;
     int64_t n_rows = 0, frame_bytes = 0, plane_bytes = 0, alleles_bound = 0, correct_bound = 0;
     std::string msg;
+    int64_t blocks_bound(int32_t max_blocks) const
+    {
+        return std::accumulate(segs.begin(), segs.end(), int64_t(0), [=](int64_t b, const IocPileSeg& sg) { return b + pile_blocks_most(sg.rlen, max_blocks); });
+    }
     int refuse(int status, const std::string& who, const std::string& what) { return msg = who.empty() ? what : who + ": " + what, status; }
     void place_pair(size_t i, const IocPileSeg& sg, int32_t max_sites)
     {
@@ -159,6 +166,32 @@ struct SinkPlan {
         return IOC_OK;
     }
 };
+
+// The block search's tables (IocReadBlocksDev, ioc_internal.h): a bit plane holds ceil((rlen + 1) / 64) words of a pair from
+// pair_word[i] on, P words in all, and as many of a segment from seg_word[g] on, T in all — word_seg says whose each is —;
+// block_base: where a segment's min(max_blocks, rlen) block slots begin, and their sum.
+struct BlocksTables {
+    std::vector<uint64_t> pair_word, seg_word;
+    std::vector<int32_t> word_seg;
+    std::vector<int64_t> block_base;
+    size_t P = 0, T = 0;
+};
+inline BlocksTables blocks_tables(const SinkPlan& p, const int32_t* seg_of_pair, int32_t max_blocks)
+{
+    const size_t n = p.segs.size(), np = p.plane.size();
+    BlocksTables t;
+    auto words = [&](size_t g) { return size_t(p.segs[g].rlen) / 64 + 1; };
+    t.seg_word.assign(n + 1, 0), t.block_base.assign(n + 1, 0), t.pair_word.assign(np, 0);
+    for (size_t g = 0; g < n; ++g) {
+        t.seg_word[g + 1] = t.seg_word[g] + words(g);
+        t.block_base[g + 1] = t.block_base[g] + pile_blocks_most(p.segs[g].rlen, max_blocks);
+    }
+    t.T = size_t(t.seg_word[n]);
+    t.word_seg.resize(t.T);
+    for (size_t g = 0; g < n; ++g) std::fill(t.word_seg.begin() + int64_t(t.seg_word[g]), t.word_seg.begin() + int64_t(t.seg_word[g + 1]), int32_t(g));
+    for (size_t i = 0; i < np; ++i) t.pair_word[i] = t.P, t.P += words(size_t(seg_of_pair[i]));
+    return t;
+}
 
 #pragma GCC visibility pop
 

@@ -9,7 +9,8 @@
 //     over the needs puts them (pool + need > cap with a non-empty pool): no cluster is divided, a cluster without rows goes to
 //     the group that is open when it is met, and the groups' pairs one after the other are the pairs of the one-group plan.
 //  3. polish_record and allele_char on one hand-made input each; corrected_record with both clipped ends attached, with a short
-//     quality line, with clips that exceed the read, and with an alignment whose insertion is too long to correct.
+//     quality line, with clips that exceed the read, and with an alignment whose insertion is too long to correct; the rows of
+//     --isoforms: a signature of every state and of no block, a cut list's '#' line, the isoforms counted from the reads' records.
 //
 // Host code only (the planner does not touch the library, so neither common.cpp nor the library is linked); meant for the sanitizers:
 //
@@ -181,6 +182,20 @@ int main()
     a.lead_i = 2, a.trail_i = 3, a.longest_ins = IOC_PILE_INS_SLOTS + 1;
     EXPECT(corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, k, "ACGTTT", "IIIII!", 6) ==
            "@r1 cluster=4 subs=0 fills=0 removes=0 ins_add=0 ins_drop=0 low=0 guarded=0 uncorrected=long_insertion\nggCCCCCttt\n+\n0123456789\n");
+
+    // three kept blocks of four found; the states keep, skip, part at blocks 0 .. 2 make the key 0 + (1 << 2) + (2 << 4)
+    EXPECT(blocks_signature(0x24, 3) == "=-~" && blocks_signature(0x3, 1) == "." && blocks_signature(7, 0) == "*" && blocks_signature(~0ull, 32) == string(32, '.'));
+    const ioc_blocks_seg zs{3, 4, 2, 5, 3, 1, 0, 1};
+    const ioc_pile_block kept[3] = {{10, 50, 3, 2, 0, 0, {0, 0}}, {100, 220, 2, 2, 1, 0, {0, 0}}, {300, 310, 1, 2, 1, 1, {0, 0}}};
+    EXPECT(cluster_blocks_rows(9, zs, kept) == "# cluster 9: kept 3 of 4 blocks\n9\t0\t10\t50\t3\t2\t0\t0\n9\t1\t100\t220\t2\t2\t1\t0\n9\t2\t300\t310\t1\t2\t1\t1\n");
+    EXPECT(cluster_blocks_rows(9, ioc_blocks_seg{0, 0, 1, 5, 5, 0, 0, 0}, nullptr).empty());
+    const std::vector<ioc_read_blocks> recs = {{0x24, 1, IOC_ISO_DIRECT, 0, 400, 1, 40}, {0x0, 0, IOC_ISO_DIRECT, 0, 400, 0, 0}, {0x34, 1, IOC_ISO_ASSIGNED, 0, 290, 1, 40},
+                                               {0x24, 1, IOC_ISO_DIRECT, 2, 399, 1, 41}, {0x15, -1, IOC_ISO_RARE, 0, 400, 3, 170}};
+    EXPECT(cluster_isoforms_rows(9, zs, recs) == "9\t0\t===\t1\t0\n9\t1\t=-~\t2\t1\n");
+    EXPECT(read_isoform_columns(recs[2], 3) == "1\tassigned\t=-.\t0\t290\t1\t40" && read_isoform_columns(recs[4], 3) == ".\trare\t---\t0\t400\t3\t170");
+    ioc_read_blocks amb{};
+    amb.group = -1, amb.how = IOC_ISO_AMBIGUOUS;
+    EXPECT(read_isoform_columns(amb, 0) == ".\tambiguous\t*\t0\t0\t0\t0" && read_isoform_columns(recs[1], 3) == "0\tdirect\t===\t0\t400\t0\t0");
 
     if (faults) {
         fprintf(stderr, "%d checks failed\n", faults);
