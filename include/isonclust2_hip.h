@@ -673,6 +673,25 @@ int ioc_planes_polish(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const c
                       int32_t n_pairs, const int32_t* seg_of_pair, const uint8_t* group, const uint8_t* base, const uint8_t* slots,
                       int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
                       ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins);
+/* The same for ANY NUMBER of groups a segment: the consensus of every isoform of a cluster.  Segment g has n_groups[g] >= 0 groups
+ * and pair i is in group[i] of its segment, -1 .. n_groups[seg_of_pair[i]] - 1 (-1: in no table).  The group-segments are numbered
+ * in segment order — segment g's are gseg_off[g] .. gseg_off[g + 1], gseg_off the prefix sum of n_groups, G = gseg_off[n_segs] in
+ * all — and group-segment (g, h) is ioc_host_pileup_call(frame of g, min_depth) on the tables piled (ioc_host_planes_pile) from the
+ * planes of the pairs i with seg_of_pair[i] == g and group[i] == h; it owns the rows of both tables from the sum over the earlier
+ * group-segments of (rlen of their segment + 1) on.  A group-segment without reads returns its frame with quality 0 throughout.
+ * With n_groups[g] == 2 everywhere this is the row and index layout of ioc_planes_polish.  The library applies no verdict on whether
+ * an isoform is real.  The planes are host planes laid out as for ioc_planes_polish.  k_group_pile (ioc_group_pile.hip) adds them
+ * up: a workgroup per 64 rows of a group-segment that has reads walks that group's own member list — the lists are made on the
+ * host, 4 bytes a pair — with two members in flight per wave, no atomics, one writer per table word; the call kernels of
+ * ioc_pileup_call run over the G group-segments.  out_off has G + 1 entries, out_polish (may be NULL) G records, and out_gcols /
+ * out_gins (optional, both or either) receive the tables, the sum over g of n_groups[g] * (rlen[g] + 1) rows.  IOC_ERR_ARG, with
+ * nothing written, for what ioc_planes_polish refuses, a negative n_groups[g], a group[i] outside -1 .. n_groups[seg] - 1 and a G
+ * above 2^31 - 1; IOC_ERR_CAPACITY, with nothing written, for cap below the sum over g of n_groups[g] * the bound of segment g
+ * (ioc_pileup_call) and for a segment whose bound exceeds 2^31 - 1. */
+int ioc_planes_polish_groups(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                             const int32_t* n_groups, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group,
+                             const uint8_t* base, const uint8_t* slots, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
+                             int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins);
 /* ioc_align_pairs_split with the consensus of both groups of every segment called where the planes lie: everything
  * ioc_align_pairs_split returns comes back unchanged, and behind the split k_plane_pile and the call kernels run over the planes
  * the walks left — k_ops_project's base plane and the six slot planes of k_ops_project_ins, 8 bytes per row and pair in all,
@@ -1115,6 +1134,28 @@ int ioc_align_pairs_blocks(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pa
                            int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
                            ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
                            ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols);
+/* ioc_align_pairs_blocks with the consensus of every isoform called where the planes lie: everything ioc_align_pairs_blocks returns
+ * comes back unchanged, the pile projects the six slot planes of k_ops_project_ins beside the two (8 bytes per row and pair in all,
+ * which count against the checkpoint arena's budget like the table), and behind the block kernels k_group_pile and the call kernels
+ * run over the planes with the isoforms the block search just made.  Segment g's isoforms 0 .. min(n_groups, max_iso) - 1 are
+ * called (max_iso >= 1), each from its direct and assigned reads as ioc_planes_polish_groups defines it at polish_min_depth, the
+ * frame of segment g being its representative as the pairs were aligned against it; reads of a later isoform, rare reads and
+ * ambiguous reads are in no table.  iso_off (n_segs + 1 entries) says which group-segments are segment g's: iso_off[g] ..
+ * iso_off[g + 1]; out_off (room for iso_cap + 1 entries) and out_polish (may be NULL; iso_cap records) are indexed by group-segment.
+ * How many isoforms there are is not known before the call: a segment has at most as many as reads, so iso_cap must be at least the
+ * sum over g of min(max_iso, reads of g) and cap at least that sum weighted by the bound of segment g (ioc_pileup_call); there are
+ * no table outputs for the same reason.  Every pair is aligned, piled and projected exactly once.  The group tables and the stage's
+ * own memory are reserved after the walks.  The refusals of ioc_align_pairs_blocks; IOC_ERR_ARG for max_iso < 1, polish_min_depth <
+ * 1, a negative cap or iso_cap, a NULL out_off or iso_off, NULL out_seq / out_qual where something may be written; IOC_ERR_CAPACITY
+ * for iso_cap or cap below its bound and for a segment whose bound exceeds 2^31 - 1; nothing is written on any of them. */
+int ioc_align_pairs_blocks_polish(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                  int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                  int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                                  int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                                  ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                                  ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t max_iso, int32_t polish_min_depth,
+                                  char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                                  int64_t iso_cap, int64_t* iso_off);
 
 #ifdef __cplusplus
 }

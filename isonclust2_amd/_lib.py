@@ -189,6 +189,7 @@ SYMBOLS = [
     "ioc_dist_barrier", "ioc_dist_merge", "ioc_set_shard", "ioc_shard_exchanges", "ioc_shard_aligned_pairs", "ioc_dist_exchange", "ioc_dist_set_shard", "ioc_align_set_verdict_threshold",
     "ioc_host_read_correct", "ioc_planes_correct", "ioc_align_pairs_correct",
     "ioc_host_planes_blocks", "ioc_planes_blocks", "ioc_align_pairs_blocks",
+    "ioc_planes_polish_groups", "ioc_align_pairs_blocks_polish",
 ]
 
 _lib = None
@@ -343,6 +344,9 @@ def load():
     L.ioc_planes_blocks.argtypes = [vp, i32, pi32, i32, pi32, C.c_void_p, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_blocks.argtypes = [vp, i32, C.POINTER(AlnPair), i32, i32, i32, i32, pi32, pi64, pd, C.c_void_p, i32, C.POINTER(PolishSeg), pi32,
                                          i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_planes_polish_groups.argtypes = [vp, i32, pi32, C.c_char_p, pi64, pi32, i32, pi32, pi32, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, i64,
+                                           pi64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_align_pairs_blocks_polish.argtypes = L.ioc_align_pairs_blocks.argtypes + [i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, i64, pi64]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

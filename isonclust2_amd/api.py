@@ -288,6 +288,14 @@ def planes_blocks_bound(rlen, max_blocks):
     return min(int(max_blocks), int(rlen))
 
 
+def blocks_polish_bound(rlen, n_reads, max_iso):
+    """What the isoform consensus of a block search may call at most of a reference of rlen bases with n_reads reads: (isoforms,
+    bytes) — a segment has at most as many isoforms as reads, so min(max_iso, n_reads) of them, pileup_call_bound(rlen) bytes each.
+    align_pairs_blocks_polish asks the sums over the segments of iso_cap and cap."""
+    most = min(int(max_iso), int(n_reads))
+    return most, most * pileup_call_bound(rlen)
+
+
 def _blocks_rule(rule):
     unknown = set(rule) - set(BLOCKS_RULE)
     if unknown:
@@ -987,6 +995,90 @@ class Context:
                                                 _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
                                                 cols.ctypes.data if tables and n_rows else None))
         out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg)}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out.update(cols=cols, row0=self._row0(rlen))
+        return out
+
+    @staticmethod
+    def _groups_out(goff, seq, qual, off, pol):
+        """The flat outputs of a call over goff[g] .. goff[g + 1] group-segments of segment g as per-segment lists: `gseq` and
+        `gqual` (a list of bytes per group), `gpolish` (a POLISH_STATS_DTYPE array per segment), `gseg_off`."""
+        ns = len(goff) - 1
+        cut = lambda a, g: [a[off[x]:off[x + 1]].tobytes() for x in range(int(goff[g]), int(goff[g + 1]))]
+        return {"gseq": [cut(seq, g) for g in range(ns)], "gqual": [cut(qual, g) for g in range(ns)],
+                "gpolish": [pol[int(goff[g]):int(goff[g + 1])] for g in range(ns)], "gseg_off": goff}
+
+    def planes_polish_groups(self, frames, seg_of_pair, group, n_groups, base, slots, min_depth=3, tables=False, cap=None):
+        """ioc_planes_polish_groups: the consensus of every group of every segment on the device, from host planes — as
+        planes_polish, with n_groups[g] groups of segment g and group[i] in -1 .. n_groups[seg_of_pair[i]] - 1 (-1: in no table).
+        Returns a dict: `gseq` and `gqual` (per segment a list of bytes per group), `gpolish` (per segment a POLISH_STATS_DTYPE array,
+        a record per group), `gseg_off` (segment g's group-segments are gseg_off[g] .. gseg_off[g + 1]) and, with tables=True,
+        `gcols` and `gins` (rlen + 1 rows per group-segment, in group-segment order) and `grow0` (the first row of every
+        group-segment) — each group-segment as pileup_call defines it on the tables planes_pile adds up from the group's reads."""
+        ns, n = len(frames), len(base)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        sop, grp, ng = np.ascontiguousarray(seg_of_pair, np.int32), np.ascontiguousarray(group, np.int32), np.ascontiguousarray(n_groups, np.int32)
+        if sop.shape != (n,) or grp.shape != (n,) or len(slots) != n or ng.shape != (ns,):
+            raise ValueError("seg_of_pair, group, base and slots must hold one entry per pair and n_groups one per segment")
+        rows = [int(rlen[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (rows[i],) or np.shape(slots[i]) != (_lib.PILE_INS_SLOTS, rows[i]):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        P = sum(rows)
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        fs = np.ascontiguousarray(np.concatenate([np.zeros((_lib.PILE_INS_SLOTS, 0), np.uint8)] + [np.asarray(x, np.uint8) for x in slots], axis=1))
+        f_off = np.zeros(ns + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        groups = np.maximum(ng.astype(np.int64), 0)   # (a negative count: the library refuses the call)
+        goff = np.concatenate([[0], np.cumsum(groups)]).astype(np.int64)
+        G = int(goff[-1])
+        bound = sum(int(groups[g]) * pileup_call_bound(rlen[g]) for g in range(ns))
+        cap = bound if cap is None else int(cap)
+        per = np.repeat(rlen.astype(np.int64) + 1, groups)
+        n_rows = int(per.sum())
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, pol = np.zeros(G + 1, np.int64), np.zeros(G, POLISH_STATS_DTYPE)
+        gcols, gins = (np.zeros(n_rows, PILEUP_DTYPE), np.zeros(n_rows, PILEUP_INS_DTYPE)) if tables else (None, None)
+        self._chk(self.L.ioc_planes_polish_groups(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+                                                  _p(ng, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, _p(grp, C.c_int32) if n else None,
+                                                  fb.ctypes.data if P else None, fs.ctypes.data if P else None, int(min_depth), seq.ctypes.data,
+                                                  qual.ctypes.data, cap, _p(off, C.c_int64), pol.ctypes.data if G else None,
+                                                  gcols.ctypes.data if tables and n_rows else None, gins.ctypes.data if tables and n_rows else None))
+        out = self._groups_out(goff, seq, qual, off, pol)
+        if tables:
+            out.update(gcols=gcols, gins=gins, grow0=np.concatenate([[0], np.cumsum(per)])[:G].astype(np.int64))
+        return out
+
+    def align_pairs_blocks_polish(self, pairs, k, segs, seg_of_pair, max_iso=16, polish_min_depth=3, stats=False, tables=False, rows=True, cap=None,
+                                  polish_cap=None, iso_cap=None, match=2, mismatch=-2, gap_extend=1, **rule):
+        """ioc_align_pairs_blocks_polish: align_pairs_blocks with the consensus of the first min(n_groups, max_iso) isoforms of every
+        segment called from the reads' planes where they lie — no read is aligned a second time.  Returns align_pairs_blocks' dict
+        plus `gseq`, `gqual`, `gpolish` and `gseg_off` as planes_polish_groups returns them: isoform h of segment g from its direct
+        and assigned reads, against the segment's frame.  polish_cap / iso_cap default to the bounds (blocks_polish_bound)."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        r = _blocks_rule(rule)
+        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        reads = np.zeros(n, READ_BLOCKS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        count = np.bincount(sop[(sop >= 0) & (sop < ns)], minlength=ns) if ns else np.zeros(0, np.int64)
+        bounds = [blocks_polish_bound(rlen[g], count[g], max(int(max_iso), 0)) for g in range(ns)]
+        i_cap = sum(b[0] for b in bounds) if iso_cap is None else int(iso_cap)
+        p_cap = sum(b[1] for b in bounds) if polish_cap is None else int(polish_cap)
+        seq, qual = np.zeros(max(p_cap, 1), np.uint8), np.zeros(max(p_cap, 1), np.uint8)
+        off, pol, goff = np.zeros(max(i_cap, 0) + 1, np.int64), np.zeros(max(i_cap, 1), POLISH_STATS_DTYPE), np.zeros(ns + 1, np.int64)
+        self._chk(self.L.ioc_align_pairs_blocks_polish(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+                                                       _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
+                                                       _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
+                                                       cols.ctypes.data if tables and n_rows else None, int(max_iso), int(polish_min_depth), seq.ctypes.data,
+                                                       qual.ctypes.data, p_cap, _p(off, C.c_int64), pol.ctypes.data, i_cap, _p(goff, C.c_int64)))
+        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
+               **self._groups_out(goff, seq, qual, off, pol)}
         if stats:
             out["stats"] = st
         if tables:

@@ -32,6 +32,8 @@ struct DumpOptions {
     // --split-polish-min-depth: positions covered by fewer reads of the group keep the representative's base
     // --correct: corrected_reads.fq, every read corrected against the pileup of its cluster; --correct-*: its thresholds
     // --isoforms: cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, the exon blocks of a cluster and every read's isoform; --isoforms-*
+    // --isoforms-polish: cluster_isoforms.fq, the consensus of every isoform of every cluster that has a block
+    // --isoforms-polish-min-depth / --isoforms-polish-max: positions covered by fewer reads of the isoform keep the representative's base / the isoforms called per cluster
     ReportOpts reports;
 };
 
@@ -54,7 +56,8 @@ void print_dump_help()
          << "                     [--split-polish [--split-polish-min-depth N]]]" << endl
          << "                    [--correct [--correct-min-depth N] [--correct-min-alt N] [--correct-min-pct P] [--correct-max-run N]]" << endl
          << "                    [--isoforms [--isoforms-min-gap N] [--isoforms-min-depth N] [--isoforms-min-alt N] [--isoforms-min-pct P]" << endl
-         << "                     [--isoforms-min-block N] [--isoforms-max N]] final.cer" << endl
+         << "                     [--isoforms-min-block N] [--isoforms-max N]" << endl
+         << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N]]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -114,7 +117,15 @@ void print_dump_help()
          << "  --isoforms-min-pct P    ... and at least P percent of the depth either way, 1 .. 50 (default 25)" << endl
          << "  --isoforms-min-block N  a run of at least N variable positions is a block (default 10: a choice that was not measured on" << endl
          << "                 real data)" << endl
-         << "  --isoforms-max N        keep the first N blocks of a cluster, 1 .. 32 (default 32)" << endl;
+         << "  --isoforms-max N        keep the first N blocks of a cluster, 1 .. 32 (default 32)" << endl
+         << "  --isoforms-polish       with --isoforms: also write outdir/cluster_isoforms.fq, for every cluster that has a block the consensus" << endl
+         << "                 of each of its isoforms (records <cluster>/iso<n>, with the isoform's signature as key=), called from the" << endl
+         << "                 alignments of --isoforms over the isoform's direct and assigned reads: no read is aligned again.  An isoform" << endl
+         << "                 keeps the representative's coordinates: a skipped block is a deletion, an exon the representative lacks is" << endl
+         << "                 not found.  Whether an isoform is real is the reader's judgement of the counts" << endl
+         << "  --isoforms-polish-min-depth N   positions covered by fewer than N reads of the isoform keep the representative's base (default 3)" << endl
+         << "  --isoforms-polish-max N         call the first N isoforms of a cluster (default 16: a choice — it bounds what a cluster may" << endl
+         << "                 write before its isoforms are known — that was not measured on real data)" << endl;
 }
 
 DumpOptions parse_dump_options(int argc, char** argv)
@@ -135,11 +146,13 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms", no_argument, 0, 1021}, {"isoforms-min-gap", required_argument, 0, 1022},
                                        {"isoforms-min-depth", required_argument, 0, 1023}, {"isoforms-min-alt", required_argument, 0, 1024},
                                        {"isoforms-min-pct", required_argument, 0, 1025}, {"isoforms-min-block", required_argument, 0, 1026},
-                                       {"isoforms-max", required_argument, 0, 1027}, {0, 0, 0, 0}};
+                                       {"isoforms-max", required_argument, 0, 1027}, {"isoforms-polish", no_argument, 0, 1028},
+                                       {"isoforms-polish-min-depth", required_argument, 0, 1029}, {"isoforms-polish-max", required_argument, 0, 1030},
+                                       {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
-    bool polish = false, split_polish = false;
-    int polish_min_depth = 3, split_polish_min_depth = 3;
+    bool polish = false, split_polish = false, iso_polish = false;
+    int polish_min_depth = 3, split_polish_min_depth = 3, iso_polish_min_depth = 3;
     int o;
     while ((o = getopt_long(argc, argv, "dhvo:i:", lo, nullptr)) != -1) {
         switch (o) {
@@ -174,6 +187,9 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1025: r.isoforms.min_pct = number("--isoforms-min-pct", optarg, 1, 50); break;
             case 1026: r.isoforms.min_block = number("--isoforms-min-block", optarg, 1, INT32_MAX); break;
             case 1027: r.isoforms.max_blocks = number("--isoforms-max", optarg, 1, 32); break;
+            case 1028: iso_polish = true; break;
+            case 1029: iso_polish_min_depth = number("--isoforms-polish-min-depth", optarg, 1, INT32_MAX); break;
+            case 1030: r.isoforms.polish_max = number("--isoforms-polish-max", optarg, 1, INT32_MAX); break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -184,6 +200,8 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (r.polish_weighted && !polish) die("--polish-weighted asks for --polish!");
     if (split_polish && !r.split.on) die("--split-polish asks for --split!");
     if (split_polish) r.split.polish_min_depth = split_polish_min_depth;
+    if (iso_polish && !r.isoforms.on) die("--isoforms-polish asks for --isoforms!");
+    if (iso_polish) r.isoforms.polish_min_depth = iso_polish_min_depth;
     if (polish) r.polish_min_depth = polish_min_depth;
     if (d.index.empty()) die("Specifying the sorted read index is mandatory!");
     d.batch = argv[optind];
@@ -360,7 +378,7 @@ int main_dump(int argc, char** argv)
                              (reports.polish() ? "cluster_polished.fq, " : "") + (reports.sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") +
                              (reports.split.on ? "cluster_split.tsv, read_split.tsv, " : "") + (reports.group_polish() ? "cluster_split_polished.fq, " : "") +
                              (reports.correct.on ? "corrected_reads.fq, " : "") +
-                             (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "");
+                             (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "") + (reports.iso_polish() ? "cluster_isoforms.fq, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

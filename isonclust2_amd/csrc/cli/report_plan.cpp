@@ -125,6 +125,17 @@ int64_t blocks_capacity(const ReportGroup& g, int max_blocks)
     return cap;
 }
 
+IsoCapacity iso_polish_capacity(const ReportGroup& g, int max_iso)
+{
+    IsoCapacity cap;
+    for (size_t s = 0; s < g.segs.size(); ++s) {
+        const int64_t m = ref_len(g, g.segs[s]), most = std::min<int64_t>(max_iso, g.seg_reads[s]);
+        cap.isoforms += most;
+        cap.bytes += most * (m + IOC_PILE_INS_SLOTS * (m + 1));
+    }
+    return cap;
+}
+
 SiteCapacity site_capacity(const ReportGroup& g, int max_sites)
 {
     SiteCapacity cap;
@@ -201,6 +212,25 @@ string cluster_isoforms_rows(size_t cluster, const ioc_blocks_seg& z, const std:
     for (size_t x = 0; x < n; ++x)
         text += std::to_string(cluster) + '\t' + std::to_string(x) + '\t' + blocks_signature(key[x], z.n_blocks) + '\t' + std::to_string(direct[x]) + '\t' +
                 std::to_string(assigned[x]) + '\n';
+    return text;
+}
+
+string cluster_isoform_records(size_t cluster, const ioc_blocks_seg& z, const std::vector<ioc_read_blocks>& reads, int64_t n_called, const int64_t* off,
+                               const ioc_polish_stats* stats, const char* seq, const char* qual)
+{
+    if (z.n_blocks < 1) return "";
+    const size_t n = size_t(std::max<int64_t>(std::min<int64_t>(n_called, z.n_groups), 0));
+    std::vector<uint64_t> key(n, 0);
+    std::vector<int32_t> mine(n, 0);
+    for (const ioc_read_blocks& r : reads) {
+        if (r.group < 0 || size_t(r.group) >= n) continue;
+        if (r.how == IOC_ISO_DIRECT) key[size_t(r.group)] = r.key;
+        if (r.how == IOC_ISO_DIRECT || r.how == IOC_ISO_ASSIGNED) ++mine[size_t(r.group)];
+    }
+    string text;
+    for (size_t h = 0; h < n; ++h)
+        text += polish_record("cluster_" + std::to_string(cluster) + "/iso" + std::to_string(h) + " key=" + blocks_signature(key[h], z.n_blocks), mine[h], stats[h], "",
+                              seq + off[h], qual + off[h], size_t(off[h + 1] - off[h]));
     return text;
 }
 

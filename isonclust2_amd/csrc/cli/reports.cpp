@@ -58,6 +58,14 @@
 // representative that some of its reads skip, with how many reads keep, skip, half-skip or do not reach each; cluster_isoforms.tsv:
 // the signatures that enough reads carry; read_isoforms.tsv: one row per row read_stats.tsv has, in that order (report_plan.cpp
 // formats all three).  The other report files are what they are without the option.
+//
+// dump --isoforms --isoforms-polish: <outdir>/cluster_isoforms.fq (ioc_align_pairs_blocks_polish: the call of --isoforms with the
+// consensus of every isoform called on the device from the reads' planes, no read aligned a second time).  For every cluster
+// with at least one block, in cluster order, one record per called isoform in ascending order — the first
+// --isoforms-polish-max of them —, named after the cluster's record in cluster_cons.fq with "/iso<h>" appended:
+// "@cluster_<id>/iso<h> key=<signature as in cluster_isoforms.tsv> reads=<its direct and assigned reads> subs= dels= ins= low=", in
+// the frame of that record; positions covered by fewer than --isoforms-polish-min-depth reads of the isoform keep the
+// representative's base with quality '!'.  The other report files are what they are without the option.
 #include "reports.hpp"
 
 #include <cstdio>
@@ -105,6 +113,8 @@ struct GroupResult {
     std::vector<int64_t> block_off;
     std::vector<ioc_blocks_seg> blocks_seg;
     std::vector<ioc_read_blocks> read_blocks;
+    PolishedSet iso_polished;       // (--isoforms-polish) per called isoform: segment g's at [iso_off[g], iso_off[g + 1])
+    std::vector<int64_t> iso_off;
 };
 
 // a row of the three per-read tables
@@ -220,10 +230,23 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
         r.read_blocks.assign(np, ioc_read_blocks{});
         std::vector<ioc_aln_stats> aln(o.stats && !have_first ? np : 0);
         if (o.pileup && !have_first) r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
-        check(c, ioc_align_pairs_blocks(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
-                                        io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
-                                        r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr),
-              "exon blocks");
+        if (o.iso_polish()) {
+            PolishedSet& ip = r.iso_polished;
+            const IsoCapacity icap = iso_polish_capacity(g, io.polish_max);
+            ip.reset(icap.bytes, size_t(icap.isoforms));
+            r.iso_off.assign(ns + 1, 0);
+            check(c, ioc_align_pairs_blocks_polish(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
+                                                   g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
+                                                   r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
+                                                   o.pileup && !have_first ? r.cols.data() : nullptr, io.polish_max, io.polish_min_depth, &ip.seq[0], &ip.qual[0],
+                                                   icap.bytes, ip.off.data(), ip.stats.data(), icap.isoforms, r.iso_off.data()),
+                  "exon blocks with the isoforms' consensus");
+        } else {
+            check(c, ioc_align_pairs_blocks(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
+                                            io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
+                                            r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr),
+                  "exon blocks");
+        }
         if (o.stats && !have_first) r.stats = aln;
         have_first = true;
     }
@@ -362,7 +385,7 @@ void write_group_polish(std::ofstream& out, const ReportGroup& g, const GroupRes
     }
 }
 
-void write_blocks(std::ofstream& blocks, std::ofstream& isoforms, const ReportGroup& g, const GroupResult& r)
+void write_blocks(std::ofstream& blocks, std::ofstream& isoforms, std::ofstream* iso_fq, const ReportGroup& g, const GroupResult& r)
 {
     std::vector<std::vector<ioc_read_blocks>> mine(g.segs.size());
     for (size_t x = 0; x < g.pairs.size(); ++x) mine[size_t(g.seg_of_pair[x])].push_back(r.read_blocks[x]);
@@ -373,12 +396,18 @@ void write_blocks(std::ofstream& blocks, std::ofstream& isoforms, const ReportGr
         const string iso = cluster_isoforms_rows(g.group_cls[x].first, r.blocks_seg[size_t(s)], mine[size_t(s)]);
         blocks.write(rows.data(), std::streamsize(rows.size()));
         isoforms.write(iso.data(), std::streamsize(iso.size()));
+        if (!iso_fq) continue;
+        const PolishedSet& ip = r.iso_polished;
+        const int64_t i0 = r.iso_off[size_t(s)], i1 = r.iso_off[size_t(s) + 1];
+        const string fq = cluster_isoform_records(g.group_cls[x].first, r.blocks_seg[size_t(s)], mine[size_t(s)], i1 - i0, ip.off.data() + i0, ip.stats.data() + i0,
+                                                  ip.seq.data(), ip.qual.data());
+        iso_fq->write(fq.data(), std::streamsize(fq.size()));
     }
 }
 
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -401,6 +430,7 @@ struct GroupFiles {
             create_file(outdir + "/cluster_isoforms.tsv", isoforms);
             isoforms << "ClusterId\tIsoform\tSignature\tDirect\tAssigned\n";
         }
+        if (o.iso_polish()) create_file(outdir + "/cluster_isoforms.fq", iso_fq);
     }
     void write(const Batch& b, const ReportOpts& o, const ReportGroup& g, const GroupResult& r)
     {
@@ -409,7 +439,7 @@ struct GroupFiles {
         if (o.sites.on && !g.segs.empty()) write_sites(sites, g, r);
         if (o.split.on) write_split(split, g, r);
         if (o.group_polish() && !g.segs.empty()) write_group_polish(group_polish, g, r);
-        if (o.isoforms.on && !g.segs.empty()) write_blocks(blocks, isoforms, g, r);
+        if (o.isoforms.on && !g.segs.empty()) write_blocks(blocks, isoforms, o.iso_polish() ? &iso_fq : nullptr, g, r);
     }
 };
 

@@ -1,4 +1,4 @@
-// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms): every read of clusters.tsv
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish): every read of clusters.tsv
 // aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
 // formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
 #ifndef ISONCLUST2_CLI_REPORTS_HPP
@@ -28,6 +28,8 @@ struct CorrectOpt {  // --correct: the thresholds of ioc_host_read_correct
 struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     bool on = false;
     int min_gap = 20, min_depth = 3, min_alt = 3, min_pct = 25, min_block = 10, max_blocks = 32;
+    int polish_min_depth = 0;  // --isoforms-polish: > 0, the depth below which an isoform's call keeps the representative's base, and ...
+    int polish_max = 16;       // ... how many isoforms of a cluster are called
 };
 struct ReportOpts {
     bool stats = false;        // --read-stats
@@ -40,6 +42,7 @@ struct ReportOpts {
     IsoformsOpt isoforms;
     bool polish() const { return polish_min_depth > 0; }
     bool group_polish() const { return split.on && split.polish_min_depth > 0; }
+    bool iso_polish() const { return isoforms.on && isoforms.polish_min_depth > 0; }
     bool segs() const { return polish() || sites.on || split.on || correct.on || isoforms.on; }  // the calls that take the clusters as segments
     bool groups() const { return pileup || segs(); }                // something is written per group
     bool any() const { return stats || groups(); }
@@ -109,6 +112,12 @@ int64_t correct_capacity(const ReportGroup& g);
 
 // the blocks a block search may keep at most, for all segments of a group: min(max_blocks, the representative's length) each
 int64_t blocks_capacity(const ReportGroup& g, int max_blocks);
+// what the consensus of the isoforms may return at most, for all segments of a group: a segment has at most as many isoforms as
+// reads, so min(max_iso, its reads) of them (isoforms), each at most the consensus bound of its representative (bytes)
+struct IsoCapacity {
+    int64_t isoforms = 0, bytes = 0;
+};
+IsoCapacity iso_polish_capacity(const ReportGroup& g, int max_iso);
 // A signature: one character per kept block from the key's two bits each — '=' keep, '-' skip, '~' part, '.' none —, "*" where the
 // cluster has no block.
 std::string blocks_signature(uint64_t key, int32_t n_blocks);
@@ -118,6 +127,11 @@ std::string cluster_blocks_rows(size_t cluster, const ioc_blocks_seg& z, const i
 // the rows of cluster_isoforms.tsv of one cluster, "<id> <isoform> <signature> <direct> <assigned>" per isoform, from the records
 // of its reads (any order)
 std::string cluster_isoforms_rows(size_t cluster, const ioc_blocks_seg& z, const std::vector<ioc_read_blocks>& reads);
+// The records of cluster_isoforms.fq of one cluster: nothing for a cluster without a block; else one per called isoform h = 0 ..
+// n_called - 1, "@cluster_<id>/iso<h> key=<signature as in cluster_isoforms.tsv> reads=<direct + assigned> subs= dels= ins= low=",
+// the isoform's bytes seq / qual at [off[h], off[h + 1]) and its record stats[h]
+std::string cluster_isoform_records(size_t cluster, const ioc_blocks_seg& z, const std::vector<ioc_read_blocks>& reads, int64_t n_called, const int64_t* off,
+                                    const ioc_polish_stats* stats, const char* seq, const char* qual);
 // the columns of read_isoforms.tsv behind the cluster and the read: "<isoform or .> <direct|assigned|rare|ambiguous> <signature>
 // <first> <end> <gaps> <gap rows>"
 std::string read_isoform_columns(const ioc_read_blocks& r, int32_t n_blocks);

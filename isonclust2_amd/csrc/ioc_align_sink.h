@@ -26,6 +26,7 @@ struct AlnTally {
     double ms_alleles = 0; // ... k_site_alleles' (ioc_align_pairs_alleles)
     double ms_project_ins = 0;  // k_ops_project_ins' device time (a pile that projects what the pairs insert as well), and ...
     double ms_plane_pile = 0;   // ... k_plane_pile's (ioc_planes_polish, ioc_align_pairs_split_polish)
+    double ms_group_pile = 0;   // k_group_pile's device time (ioc_planes_polish_groups, ioc_align_pairs_blocks_polish)
     double ms_correct = 0;      // k_read_correct's device time, both passes and the scan (ioc_planes_correct, ioc_align_pairs_correct)
     double ms_blocks = 0;       // the eight kernels of ioc_read_blocks.hip, their device time together (ioc_planes_blocks, ioc_align_pairs_blocks)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ioc_align_sink.h"
+#include "ioc_group_pile.h"
 #include "ioc_internal.h"
 #include "ioc_plane_pile.h"
 #include "ioc_read_blocks.h"
@@ -99,6 +100,16 @@ struct GroupPiled {  // group pile (a_gpile): the tables of the 2 n group-segmen
     std::vector<IocPileSeg> gsegs;
     ioc_pileup_col* cols;
     ioc_pileup_ins* ins;
+    int64_t n_rows = 0;  // (groups_pile: the rows of its tables, the sum over the group-segments of rlen + 1, ...
+    GroupMemberLists lists;           // ... every group's member list and ...
+    std::vector<IocGroupWork> work;   // ... the work items, which the uploads read until the call stage has waited for the stream)
+};
+struct IsoPolish {  // the call of the first min(n_groups, max_iso) isoforms of every segment behind a block search (ioc_align_pairs_blocks_polish)
+    int32_t max_iso;
+    CallOut call;
+    int64_t iso_cap;
+    int64_t* iso_off;
+    bool ok() const { return max_iso >= 1 && call.ok() && iso_cap >= 0 && iso_off; }
 };
 // split (a_split): the member lists and the group bytes.  What a group pile reads beside the plan: those and the planes, on the
 // device (a NULL pointer: the array is the host's — Planes::host — and uploaded; ioc_planes_polish: all of them, behind a split: none)
@@ -152,6 +163,7 @@ struct SinkRun {
     int split(const SplitCall& sp, size_t n, size_t np, const int32_t* seg_of_pair, const int64_t* site_off, const int64_t* allele_off, const ioc_pile_site* sites,
               const uint8_t* alleles, bool on_device, Planes& d);
     int group_pile(const SinkPlan& p, const int32_t* seg_of_pair, const Planes& host, Planes dev, GroupPiled& d);
+    int groups_pile(const SinkPlan& p, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& host, Planes dev, GroupPiled& d);
     int correct(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* d_frames, uint64_t frame_bytes, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
                 const Planes& host, Planes dev, const CorrectOut& o);
     int blocks(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o);
@@ -358,6 +370,58 @@ int SinkRun::group_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const Pl
     IOC_CHK(c, iock_plane_pile(c->stream, reinterpret_cast<const IocPlaneWork*>(p + o_work), uint32_t(work.size()), reinterpret_cast<const IocPileSeg*>(p + o_gseg),
                                pd.mem_off, pd.members, uint32_t(np), pd.group, reinterpret_cast<const uint64_t*>(p + o_plane), pd.base, pd.slots,
                                uint64_t(P), d.cols, d.ins, uint64_t(n_rows)));
+    return end();
+}
+
+// k_group_pile over the G group-segments of the plan's segments, n_groups[g] of segment g in segment order: a_gpile holds
+// [group-segments][work items][plane offsets][gmem_off][gmembers][base plane][slot planes][gcols][gins], the planes only where they
+// are uploaded.  Every group's own member list is made on the host (group_member_lists) and uploaded, 4 bytes a pair that is in a
+// group.  Group-segment x owns the rows of both tables from the sum over the earlier group-segments of (rlen + 1) on; the tables
+// are set to 0 first: k_group_pile is launched over the group-segments that have reads alone.  The stream is not waited for: the
+// call stage behind it does that.  G is at least 1.
+int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& ph, Planes pd, GroupPiled& d)
+{
+    const std::vector<IocPileSeg>& ds = pn.segs;
+    const size_t n = ds.size(), np = pn.plane.size(), P = size_t(pn.plane_bytes);
+    const GroupMemberLists& m = d.lists = group_member_lists(n, np, seg_of_pair, group, n_groups);
+    const size_t G = m.gseg_off[n], M = m.gmembers.size();
+    std::vector<IocPileSeg>& gsegs = d.gsegs = std::vector<IocPileSeg>(G);
+    d.n_rows = 0;
+    for (size_t g = 0; g < n; ++g)
+        for (size_t x = m.gseg_off[g]; x < m.gseg_off[g + 1]; ++x) {
+            gsegs[x] = IocPileSeg{d.n_rows, ds[g].f_off, ds[g].rlen, ds[g].rc};
+            d.n_rows += int64_t(ds[g].rlen) + 1;
+        }
+    std::vector<IocGroupWork>& work = d.work;
+    work.clear();
+    for (size_t x = 0; x < G; ++x)
+        for (int64_t row = 0; m.gmem_off[x + 1] > m.gmem_off[x] && row <= int64_t(gsegs[x].rlen); row += IOC_GROUP_PILE_ROWS)
+            work.push_back(IocGroupWork{uint32_t(x), uint32_t(row)});
+    if (work.size() > size_t(INT32_MAX)) return ioc_fail(c, IOC_ERR_CAPACITY, "the group tables have more than 2^31 - 1 blocks of rows");
+    Arena l;
+    const size_t o_gseg = l.take(G * sizeof(IocPileSeg)), o_work = l.take(work.size() * sizeof(IocGroupWork)), o_plane = l.take(np * 8),
+                 o_goff = l.take((G + 1) * 4), o_gmem = l.take(M * 4), o_base = l.take(pd.base ? 0 : P),
+                 o_slots = l.take(pd.slots ? 0 : size_t(IOC_PILE_INS_SLOTS) * P), o_cols = l.take(size_t(d.n_rows) * sizeof(ioc_pileup_col)),
+                 o_ins = l.take(size_t(d.n_rows) * sizeof(ioc_pileup_ins));
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_gpile, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_gpile.p);
+    auto up = [&](size_t o, const void* src, size_t b) { return b ? hipMemcpyAsync(p + o, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(o_gseg, gsegs.data(), G * sizeof(IocPileSeg)));
+    IOC_CHK(c, up(o_work, work.data(), work.size() * sizeof(IocGroupWork)));
+    IOC_CHK(c, up(o_plane, pn.plane.data(), np * 8));
+    IOC_CHK(c, up(o_goff, m.gmem_off.data(), (G + 1) * 4));
+    IOC_CHK(c, up(o_gmem, m.gmembers.data(), M * 4));
+    if (!pd.base) IOC_CHK(c, up(o_base, ph.base, P));
+    if (!pd.slots) IOC_CHK(c, up(o_slots, ph.slots, size_t(IOC_PILE_INS_SLOTS) * P));
+    if (!pd.base) pd.base = p + o_base;  // (what does not lie on the device yet was uploaded)
+    if (!pd.slots) pd.slots = p + o_slots;
+    d.cols = reinterpret_cast<ioc_pileup_col*>(p + o_cols), d.ins = reinterpret_cast<ioc_pileup_ins*>(p + o_ins);
+    IOC_CHK(c, hipMemsetAsync(p + o_cols, 0, l.size() - o_cols, c->stream));
+    IOC_TRY(begin(t.ms_group_pile));
+    IOC_CHK(c, iock_group_pile(c->stream, reinterpret_cast<const IocGroupWork*>(p + o_work), uint32_t(work.size()), reinterpret_cast<const IocPileSeg*>(p + o_gseg),
+                               uint32_t(G), reinterpret_cast<const uint32_t*>(p + o_goff), reinterpret_cast<const uint32_t*>(p + o_gmem), uint32_t(M), uint32_t(np),
+                               reinterpret_cast<const uint64_t*>(p + o_plane), pd.base, pd.slots, uint64_t(P), d.cols, d.ins, uint64_t(d.n_rows)));
     return end();
 }
 
@@ -835,6 +899,67 @@ int ioc_planes_polish(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const cha
     return IOC_OK;
 }
 
+// what a call over n_groups[g] groups of segment g refuses once its segments are known, and what it may call: the bound is the sum
+// over the segments of n_groups[g] * pile_call_most(rlen[g])
+static int groups_polish_ok(ioc_ctx* c, const std::string& who, const CallOut& o, const std::vector<IocPileSeg>& ds, const int32_t* n_groups)
+{
+    int64_t bound = 0;
+    for (size_t g = 0; g < ds.size(); ++g) {
+        if (pile_call_most(ds[g].rlen) > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
+            return ioc_fail(c, IOC_ERR_CAPACITY, who + ": segment " + std::to_string(g) + " may call more than 2^31 - 1 bytes");
+        bound += int64_t(n_groups[g]) * pile_call_most(ds[g].rlen);
+    }
+    return call_room_ok(c, who, o, bound);
+}
+
+// groups pile -> call -> copy-out: the consensus of every group of every segment (frames in d_frames), the group tables where asked for
+static int groups_polish_device(SinkRun& r, const GroupPolish& gp, const SinkPlan& p, const uint8_t* d_frames, uint64_t frame_bytes, const int32_t* seg_of_pair,
+                                const int32_t* group, const int32_t* n_groups, const Planes& host, const Planes& dev)
+{
+    GroupPiled g;
+    IOC_TRY(r.groups_pile(p, seg_of_pair, group, n_groups, host, dev, g));
+    IOC_TRY(pile_call_device(r, g.gsegs, d_frames, frame_bytes, gp.call, g.cols, g.ins, nullptr, g.n_rows));
+    return r.copy_out({{gp.out_gcols, g.cols, size_t(g.n_rows) * sizeof(ioc_pileup_col)}, {gp.out_gins, g.ins, size_t(g.n_rows) * sizeof(ioc_pileup_ins)}});
+}
+
+// upload -> groups pile -> call -> copy-out.  ioc_planes_polish over any number of groups a segment: everything is uploaded, every
+// group's own member list with it, and k_group_pile and the call kernels run as behind ioc_align_pairs_blocks_polish.
+int ioc_planes_polish_groups(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups,
+                             int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base, const uint8_t* slots, int32_t min_depth,
+                             char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_gcols,
+                             ioc_pileup_ins* out_gins)
+{
+    const std::string who = "ioc_planes_polish_groups";
+    const GroupPolish gp{{min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_gcols, out_gins};
+    if (!c || n_segs < 0 || n_pairs < 0 || !gp.call.ok() || (n_segs > 0 && (!rlen || !frame_off || !n_groups)) || (n_pairs > 0 && (!seg_of_pair || !group)))
+        return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen(who, n_segs, rlen, frames, frame_off, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !slots)) return IOC_ERR_ARG;
+    int64_t G = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (n_groups[g] < 0) return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " has a negative number of groups");
+        if ((G += n_groups[g]) > INT32_MAX) return ioc_fail(c, IOC_ERR_ARG, who + ": more than 2^31 - 1 group-segments");
+    }
+    for (int32_t i = 0; i < n_pairs; ++i)
+        if (group[i] < -1 || group[i] >= n_groups[seg_of_pair[i]])
+            return ioc_fail(c, IOC_ERR_ARG, who + ": the group of pair " + std::to_string(i) + " is neither -1 nor one of its segment's");
+    IOC_TRY(groups_polish_ok(c, who, gp.call, p.segs, n_groups));
+    out_off[0] = 0;
+    if (G == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(p.frame_bytes)));
+    if (p.frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(p.frame_bytes), hipMemcpyHostToDevice, c->stream));
+    SinkRun r{c};
+    IOC_TRY(groups_polish_device(r, gp, p, static_cast<const uint8_t*>(d_frames.p), uint64_t(p.frame_bytes), seg_of_pair, group, n_groups,
+                                 Planes{nullptr, nullptr, nullptr, base, slots}, Planes{}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes polish groups: %lld group-segments, %d pairs, %lld plane bytes, %lld bytes called, k_group_pile %.3f ms, k_pile_call %.3f ms\n",
+                (long long)G, n_pairs, (long long)(7 * p.plane_bytes), (long long)out_off[G], r.t.ms_group_pile, r.t.ms_call);
+    return IOC_OK;
+}
+
 // what a read correction refuses once its plan is known: IOC_OK, or the status with the message set
 static int correct_room_ok(ioc_ctx* c, const std::string& who, const CorrectOut& o, const SinkPlan& p)
 {
@@ -966,6 +1091,64 @@ int ioc_align_pairs_blocks(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
         fprintf(stderr, "[ioc]   aligner: blocks: %d segments, %lld rows, %d pairs, %lld blocks kept, %.3f MB (blocks, records%s%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms%s\n",
                 n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], double(r.t.copied) * 1e-6, out_rows ? ", rows" : "", out_cols ? ", table" : "",
                 out_stats ? ", statistics" : "", r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_blocks,
+                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+// pile -> blocks -> groups pile -> call -> copy-out.  ioc_align_pairs_blocks with the six slot planes projected beside the two, and
+// behind the block kernels k_group_pile and the call kernels over the planes: the consensus of the first min(n_groups, max_iso)
+// isoforms of every segment, each from its direct and assigned reads, with no pair aligned a second time.  The read and segment
+// records are on the host when the block stage returns; they say which group-segments there are and who is in them.
+int ioc_align_pairs_blocks_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                  int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                  const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                  int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                  int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t max_iso,
+                                  int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                                  int64_t iso_cap, int64_t* iso_off)
+{
+    const std::string who = "ioc_align_pairs_blocks_polish";
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
+    const IsoPolish ip{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off};
+    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !ip.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
+    IOC_TRY(blocks_room_ok(c, who, o, p));
+    // what may be called: a segment has at most as many isoforms as reads (every isoform has min_alt >= 1 reads of its own)
+    std::vector<int64_t> reads(size_t(n_segs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i) ++reads[size_t(seg_of_pair[i])];
+    std::vector<int32_t> most(size_t(n_segs), 0);
+    int64_t iso_bound = 0;
+    for (int32_t g = 0; g < n_segs; ++g) iso_bound += most[size_t(g)] = int32_t(std::min<int64_t>(max_iso, reads[size_t(g)]));
+    if (iso_cap < iso_bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": iso_cap " + std::to_string(iso_cap) + " below the bound " + std::to_string(iso_bound));
+    IOC_TRY(groups_polish_ok(c, who, ip.call, p.segs, most.data()));
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    block_off[0] = 0, out_off[0] = 0;
+    for (int32_t g = 0; g <= n_segs; ++g) iso_off[g] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    SinkRun r{c};
+    PiledDev d;
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ true, d));
+    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o));  // (a_blocks is reserved here, after the walks; the records are the host's from here on)
+    std::vector<int32_t> n_iso(size_t(n_segs), 0), group(size_t(n_pairs), -1);
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (out_seg[g].n_groups < 0 || out_seg[g].n_groups > reads[size_t(g)]) return ioc_fail(c, IOC_ERR_HIP, "the block search returned more isoforms than reads");
+        n_iso[size_t(g)] = std::min(out_seg[g].n_groups, max_iso);
+        iso_off[g + 1] = iso_off[g] + n_iso[size_t(g)];
+    }
+    for (int32_t i = 0; i < n_pairs; ++i) group[size_t(i)] = out_reads[i].group;  // (an isoform behind the cut is in no list: group_member_lists)
+    const int64_t G = iso_off[n_segs];
+    if (G > 0) {
+        const GroupPolish gp{ip.call, nullptr, nullptr};
+        IOC_TRY(groups_polish_device(r, gp, p, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), seg_of_pair, group.data(), n_iso.data(), Planes{},
+                                     Planes{nullptr, nullptr, nullptr, d.base, d.slots}));
+    }
+    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: blocks polish: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, ms_blocks %.3f ms, k_group_pile %.3f ms, k_pile_call %.3f ms%s\n",
+                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)G, (long long)out_off[G], double(r.t.copied) * 1e-6, r.t.ms_copy,
+                r.t.ms_pileup, r.t.ms_project, r.t.ms_project_ins, r.t.ms_blocks, r.t.ms_group_pile, r.t.ms_call,
                 out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
     return IOC_OK;
 }

@@ -218,7 +218,8 @@ struct ioc_ctx {
                       // and, for ioc_align_pairs_split_polish, [slot planes x 6] behind them (k_ops_project_ins)
     DevBuf a_split;   // ioc_alleles_split, ioc_align_pairs_split: member lists, bit planes, per-site and per-pair words (ioc_site_split.hip)
     DevBuf a_gpile;   // ioc_planes_polish, ioc_align_pairs_split_polish: the group-segments, their work items and tables (k_plane_pile) and,
-                      // from host planes, the uploaded member lists and planes
+                      // from host planes, the uploaded member lists and planes; ioc_planes_polish_groups, ioc_align_pairs_blocks_polish: the
+                      // same of k_group_pile, with every group's own member list
     DevBuf a_correct; // ioc_planes_correct, ioc_align_pairs_correct: segments, pairs, offsets, records and the corrected bytes (ioc_read_correct.hip) and,
                       // from host planes, the uploaded planes
     DevBuf a_blocks;  // ioc_planes_blocks, ioc_align_pairs_blocks: segments, pairs, member lists, bit planes, tables and records (ioc_read_blocks.hip) and,
@@ -418,6 +419,14 @@ hipError_t iock_ops_project_ins(hipStream_t st, const uint8_t* buf, const uint64
 struct IocPlaneWork;  // (ioc_plane_pile.h: 64 rows of a group-segment)
 hipError_t iock_plane_pile(hipStream_t st, const IocPlaneWork* work, uint32_t n_work, const IocPileSeg* gsegs, const uint32_t* mem_off,
                            const uint32_t* members, uint32_t n_pairs, const uint8_t* group, const uint64_t* plane, const uint8_t* base_planes,
+                           const uint8_t* slot_planes, uint64_t plane_bytes, ioc_pileup_col* gcols, ioc_pileup_ins* gins, uint64_t n_rows);
+
+// ioc_group_pile.hip: the tables of any number of groups of every segment added up from the same planes: everything is a device
+// pointer; group-segment x (n_gsegs of them, in segment order) takes the pairs gmembers[gmem_off[x] .. gmem_off[x + 1]), its own
+// list in ascending order (group_member_lists, ioc_sink_plan.h), n_members in all
+struct IocGroupWork;  // (ioc_group_pile.h: 64 rows of a group-segment)
+hipError_t iock_group_pile(hipStream_t st, const IocGroupWork* work, uint32_t n_work, const IocPileSeg* gsegs, uint32_t n_gsegs, const uint32_t* gmem_off,
+                           const uint32_t* gmembers, uint32_t n_members, uint32_t n_pairs, const uint64_t* plane, const uint8_t* base_planes,
                            const uint8_t* slot_planes, uint64_t plane_bytes, ioc_pileup_col* gcols, ioc_pileup_ins* gins, uint64_t n_rows);
 
 // ioc_read_correct.hip: every pair's read corrected against the tables of its segment (ioc_host_read_correct per pair).  Everything

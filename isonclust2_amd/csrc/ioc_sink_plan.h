@@ -42,6 +42,33 @@ inline MemberLists member_lists(size_t n_segs, size_t n_pairs, const int32_t* se
     return m;
 }
 
+// The same per group.  Segment g has n_groups[g] groups and pair i is in group group[i] of its segment, or in none (-1, or a group
+// the segment does not have: a call that cuts the groups short leaves the reads of the later ones in no list).  The group-segments
+// are numbered in segment order, segment g's gseg_off[g] .. gseg_off[g + 1] (G = gseg_off[n_segs] in all), and group-segment x has
+// gmembers[gmem_off[x] .. gmem_off[x + 1]), its pairs in ascending order; a group without reads has an empty list.  The caller has
+// checked that every n_groups[g] is at least 0 and that G is at most 2^31 - 1.
+struct GroupMemberLists { std::vector<uint32_t> gseg_off, gmem_off, gmembers; };
+inline GroupMemberLists group_member_lists(size_t n_segs, size_t n_pairs, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups)
+{
+    GroupMemberLists m;
+    m.gseg_off.assign(n_segs + 1, 0);
+    for (size_t g = 0; g < n_segs; ++g) m.gseg_off[g + 1] = m.gseg_off[g] + uint32_t(n_groups[g]);
+    const size_t G = m.gseg_off[n_segs];
+    auto gseg_of = [&](size_t i) -> int64_t {
+        const size_t g = size_t(seg_of_pair[i]);
+        return group[i] >= 0 && group[i] < n_groups[g] ? int64_t(m.gseg_off[g]) + group[i] : -1;
+    };
+    m.gmem_off.assign(G + 1, 0);
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (const int64_t x = gseg_of(i); x >= 0) ++m.gmem_off[size_t(x) + 1];
+    for (size_t x = 0; x < G; ++x) m.gmem_off[x + 1] += m.gmem_off[x];
+    m.gmembers = std::vector<uint32_t>(m.gmem_off[G]);
+    std::vector<uint32_t> next(m.gmem_off.begin(), m.gmem_off.end() - 1);
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (const int64_t x = gseg_of(i); x >= 0) m.gmembers[next[size_t(x)]++] = uint32_t(i);
+    return m;
+}
+
 // The split's tables (IocSplitDev, ioc_internal.h): segment g has ceil(reads / 64) words a site — T words in all, tile_seg says
 // whose each is — and words x sites words of each bit plane from bit_off[g] on, P in all; seg_of_site: the segment of every site;
 // most: the largest segment's sites.

@@ -12,7 +12,8 @@
 //    overflow on the way: the sums are 64-bit);
 //  * ioc_sink_plan.h, each planner against a plain restatement written here: the arena layout (block sizes 0, 1, 15, 16, 17; the
 //    totals of one case per stage against the hand-chained sums the stages used to carry), member_lists (no segments, no pairs,
-//    segments without pairs, pairs out of segment order, one segment for all), the split's tables (0, 1, 64, 65 and 128 members,
+//    segments without pairs, pairs out of segment order, one segment for all), group_member_lists (the same per group: pairs in
+//    -1 or in a group their segment lacks, empty groups, segments without groups), the split's tables (0, 1, 64, 65 and 128 members,
 //    a segment without sites between two with), the bounds at their edges, and both constructors of SinkPlan with every refusal's
 //    status and message as the entry points have always worded them.
 //
@@ -339,6 +340,29 @@ void check_member_lists()
     }
 }
 
+void check_group_member_lists()
+{
+    g_what = "group_member_lists";
+    const struct { std::vector<int32_t> ng, sop, grp; } cases[] = {
+        {{}, {}, {}}, {{2, 0, 3}, {}, {}} /* no pairs */, {{0, 0}, {0, 1, 1}, {-1, -1, -1}} /* pairs and no groups */,
+        {{2, 4, 1, 0}, {1, 0, 1, 1, 0, 2, 1, 0, 1, 3}, {2, 0, 0, -1, 1, 0, 2, 0, 5, -1}} /* out of order, -1, an empty group, a group the segment lacks */,
+        {{3}, {0, 0, 0, 0}, {1, 1, 1, 1}} /* all in one */, {{1, 1}, {1, 0}, {0, 0}}};
+    for (const auto& k : cases) {
+        const size_t n = k.ng.size();
+        const GroupMemberLists m = group_member_lists(n, k.sop.size(), k.sop.data(), k.grp.data(), k.ng.data());
+        std::vector<uint32_t> gseg{0}, off{0}, mem;
+        for (size_t g = 0; g < n; ++g) {
+            for (int32_t h = 0; h < k.ng[g]; ++h) {
+                for (size_t i = 0; i < k.sop.size(); ++i)
+                    if (size_t(k.sop[i]) == g && k.grp[i] == h) mem.push_back(uint32_t(i));
+                off.push_back(uint32_t(mem.size()));
+            }
+            gseg.push_back(gseg.back() + uint32_t(k.ng[g]));
+        }
+        EXPECT(m.gseg_off == gseg && m.gmem_off == off && m.gmembers == mem);
+    }
+}
+
 void check_split_tables()
 {
     g_what = "split_tables";
@@ -481,6 +505,7 @@ int main()
     check_routes();
     check_arena();
     check_member_lists();
+    check_group_member_lists();
     check_split_tables();
     check_bounds();
     check_plan_rlen();

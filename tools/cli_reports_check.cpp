@@ -10,7 +10,8 @@
 //     the group that is open when it is met, and the groups' pairs one after the other are the pairs of the one-group plan.
 //  3. polish_record and allele_char on one hand-made input each; corrected_record with both clipped ends attached, with a short
 //     quality line, with clips that exceed the read, and with an alignment whose insertion is too long to correct; the rows of
-//     --isoforms: a signature of every state and of no block, a cut list's '#' line, the isoforms counted from the reads' records.
+//     --isoforms: a signature of every state and of no block, a cut list's '#' line, the isoforms counted from the reads' records, the records of
+//     --isoforms-polish and what they may take.
 //
 // Host code only (the planner does not touch the library, so neither common.cpp nor the library is linked); meant for the sanitizers:
 //
@@ -122,6 +123,9 @@ int main()
     EXPECT(polish_capacity(g) == 178 && polish_capacity(g, 2) == 356);
     // min(10, 2 * rlen + 1) = 10, 10, 9, 10 sites; times 2, 2, 1, 1 reads
     EXPECT(site_capacity(g, 10).sites == 39 && site_capacity(g, 10).alleles == 59);
+    // min(max_iso, reads) = 2, 2, 1, 1 isoforms at 16 and 1 each at 1; times the bounds above
+    EXPECT(iso_polish_capacity(g, 16).isoforms == 6 && iso_polish_capacity(g, 16).bytes == 2 * 48 + 2 * 41 + 34 + 55);
+    EXPECT(iso_polish_capacity(g, 1).isoforms == 4 && iso_polish_capacity(g, 1).bytes == 178);
     // without a per-group file nothing but the pool, the pairs and their maps is kept
     {
         ReportOpts stats_only;
@@ -193,6 +197,14 @@ int main()
                                                {0x24, 1, IOC_ISO_DIRECT, 2, 399, 1, 41}, {0x15, -1, IOC_ISO_RARE, 0, 400, 3, 170}};
     EXPECT(cluster_isoforms_rows(9, zs, recs) == "9\t0\t===\t1\t0\n9\t1\t=-~\t2\t1\n");
     EXPECT(read_isoform_columns(recs[2], 3) == "1\tassigned\t=-.\t0\t290\t1\t40" && read_isoform_columns(recs[4], 3) == ".\trare\t---\t0\t400\t3\t170");
+    // the records of cluster_isoforms.fq: both isoforms, the first alone (--isoforms-polish-max 1), and none for a cluster without a block
+    const int64_t ioff[3] = {4, 8, 10};
+    ioc_polish_stats zi[2] = {};
+    zi[1].n_del = 2, zi[1].n_low = 1;
+    const string both = "@cluster_9/iso0 key==== reads=1 subs=0 dels=0 ins=0 low=0\nACGT\n+\nIIII\n@cluster_9/iso1 key==-~ reads=3 subs=0 dels=2 ins=0 low=1\nTT\n+\n!J\n";
+    EXPECT(cluster_isoform_records(9, zs, recs, 2, ioff, zi, "....ACGTTT", "....IIII!J") == both);
+    EXPECT(cluster_isoform_records(9, zs, recs, 1, ioff, zi, "....ACGTTT", "....IIII!J") == both.substr(0, both.find("@cluster_9/iso1")));
+    EXPECT(cluster_isoform_records(9, ioc_blocks_seg{0, 0, 1, 5, 5, 0, 0, 0}, recs, 1, ioff, zi, "....ACGTTT", "....IIII!J").empty());
     ioc_read_blocks amb{};
     amb.group = -1, amb.how = IOC_ISO_AMBIGUOUS;
     EXPECT(read_isoform_columns(amb, 0) == ".\tambiguous\t*\t0\t0\t0\t0" && read_isoform_columns(recs[1], 3) == "0\tdirect\t===\t0\t400\t0\t0");
