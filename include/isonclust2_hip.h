@@ -418,6 +418,28 @@ int ioc_host_ops_project_ins(const char* ops, int64_t len, const char* query, in
  * That is what the planes are kept for: the tables of ANY subset of a cluster's reads can be added up after the alignments are
  * gone — the two sides of a split (ioc_planes_polish, ioc_align_pairs_split_polish). */
 int ioc_host_planes_pile(const uint8_t* base, const uint8_t* slots, int32_t rlen, ioc_pileup_col* cols, ioc_pileup_ins* ins);
+/* The weight part of a read's projection: the weight of every vote the read casts, kept beside its planes.  `wbase` holds rlen + 1
+ * bytes and `wslots` IOC_PILE_INS_SLOTS * (rlen + 1), slot-major like `slots` of ioc_host_ops_project_ins.  The call sets all of
+ * them to 0 and then walks the string as ioc_host_ops_pileup_weighted does: a '=' / 'X' at row r taking query[q] stores
+ * w(qual[q]) (ioc_host_qual_weight) at wbase[r]; a 'D' at row r stores the deletion weight of ioc_host_ops_pileup_weighted — the
+ * smaller of the weights of the query bases on its two sides where they exist, 1 where neither does; the j-th 'I' of its run,
+ * j < IOC_PILE_INS_SLOTS, stores w(qual[q]) at wslots[j][r].  A weight is 1 .. 93, so a byte holds one, and 0 says "no vote".
+ * Nothing is ever cleared: a second run in front of the same row overwrites, in string order.  What ioc_host_ops_pileup_weighted
+ * refuses is refused (IOC_ERR_ARG), with both outputs untouched. */
+int ioc_host_ops_project_weights(const char* ops, int64_t len, const char* query, const char* qual, int32_t qlen, int32_t rlen, uint8_t* wbase,
+                                 uint8_t* wslots);
+/* One read's planes and weight planes ADDED to the two tables of weights of its reference, rlen + 1 rows each: base[r] in 0 .. 5
+ * adds wbase[r] to that counter (a c g t other del) of wcols[r]; a slot byte s in 1 .. 5 at slots[j][r] adds wslots[j][r] to
+ * wins[r].slot[j][s - 1].  ins_runs and ins_bases of wcols and `longer` of wins are never touched, and the sums are modulo 2^32.
+ * What ioc_host_planes_pile refuses, a NULL weight plane and a NULL table: IOC_ERR_ARG, with both tables untouched.
+ * The relation to the weighted pileup: for a string with at most one run of 'I' in front of any row the tables piled this way
+ * from ioc_host_ops_project / _project_ins / _project_weights equal those of ioc_host_ops_pileup_weighted in every field but
+ * `longer`, which the weighted call (ioc_host_pileup_call_weighted) does not read.  So the weighted consensus of ANY subset of a
+ * cluster's reads can be called after the alignments are gone: group-segment (g, h) of ioc_planes_polish_groups_weighted is
+ * ioc_host_pileup_call_weighted(gcols, gwcols, gwins, frame of g, min_depth) with gcols from ioc_host_planes_pile and gwcols /
+ * gwins from this function over the pairs of segment g in group h. */
+int ioc_host_planes_pile_weighted(const uint8_t* base, const uint8_t* slots, const uint8_t* wbase, const uint8_t* wslots, int32_t rlen,
+                                  ioc_pileup_col* wcols, ioc_pileup_ins* wins);
 /* One variable site.  kind IOC_SITE_BASE: the alleles are the channels 0 .. 5 (A C G T other del) of row `row`; kind
  * IOC_SITE_INS: the alleles are 0 (no insertion in front of row `row`) and 1 (one).  depth / n_major / n_minor are the 64-bit
  * values of the definition below, saturated at 2^32 - 1. */
@@ -692,6 +714,22 @@ int ioc_planes_polish_groups(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, 
                              const int32_t* n_groups, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group,
                              const uint8_t* base, const uint8_t* slots, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
                              int64_t* out_off, ioc_polish_stats* out_polish, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins);
+/* ioc_planes_polish_groups with every read's vote counted by its weight: the quality-weighted consensus of every isoform of a
+ * cluster.  wbase / wslots are the host weight planes of the pairs (ioc_host_ops_project_weights), laid out as base / slots are and
+ * uploaded beside them.  Group-segment (g, h) is ioc_host_pileup_call_weighted(gcols, gwcols, gwins, frame of g, min_depth), gcols
+ * piled by ioc_host_planes_pile and gwcols / gwins by ioc_host_planes_pile_weighted from the pairs i with seg_of_pair[i] == g and
+ * group[i] == h; numbering, row ownership and the group without reads (its frame at quality 0) are those of
+ * ioc_planes_polish_groups.  k_group_pile_weighted (ioc_group_pile_weighted.hip) adds up the three tables, 14 bytes a member and
+ * row, and the weighted mode of the call kernels runs over the G group-segments.  out_gcols / out_gwcols / out_gwins (each
+ * optional) receive the tables: ins_runs / ins_bases of gwcols and `longer` / `reserved` of gwins are 0, and gcols is what
+ * ioc_planes_polish_groups returns.  With n_groups[g] == 2 everywhere this is the weighted consensus of both sides of a split.
+ * IOC_ERR_ARG / IOC_ERR_CAPACITY, with nothing written, for what ioc_planes_polish_groups refuses, and IOC_ERR_ARG for a NULL
+ * wbase or wslots with n_pairs > 0. */
+int ioc_planes_polish_groups_weighted(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                                      const int32_t* n_groups, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group,
+                                      const uint8_t* base, const uint8_t* slots, const uint8_t* wbase, const uint8_t* wslots, int32_t min_depth,
+                                      char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                                      ioc_pileup_col* out_gcols, ioc_pileup_col* out_gwcols, ioc_pileup_ins* out_gwins);
 /* ioc_align_pairs_split with the consensus of both groups of every segment called where the planes lie: everything
  * ioc_align_pairs_split returns comes back unchanged, and behind the split k_plane_pile and the call kernels run over the planes
  * the walks left — k_ops_project's base plane and the six slot planes of k_ops_project_ins, 8 bytes per row and pair in all,
@@ -1156,6 +1194,23 @@ int ioc_align_pairs_blocks_polish(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_p
                                   ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t max_iso, int32_t polish_min_depth,
                                   char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
                                   int64_t iso_cap, int64_t* iso_off);
+/* ioc_align_pairs_blocks_polish with every isoform called by weight, under the qualities of ioc_align_set_pool_qual: the pile
+ * projects the seven weight planes of k_ops_project_weights beside the eight (15 bytes per row and pair in all, which count
+ * against the checkpoint arena's budget; a call of ioc_align_pairs_blocks_polish reserves what it always did), and behind the block
+ * kernels k_group_pile_weighted and the weighted mode of the call kernels run: isoform h of segment g is called as
+ * ioc_planes_polish_groups_weighted defines it.  Everything but the isoforms' sequences, qualities and polish records — scores,
+ * statistics, blocks, rows, read and segment records, the table, iso_off — is what ioc_align_pairs_blocks_polish returns, byte for
+ * byte; with all qualities equal, or all at or below '"' (34), the sequences are too.  Every pair is aligned, piled and projected
+ * exactly once.  The refusals of ioc_align_pairs_blocks_polish, and IOC_ERR_ARG for a pool without qualities; nothing is written on
+ * any of them. */
+int ioc_align_pairs_blocks_polish_weighted(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match,
+                                           int32_t mismatch, int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio,
+                                           ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair,
+                                           int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
+                                           int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                           int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols,
+                                           int32_t max_iso, int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap,
+                                           int64_t* out_off, ioc_polish_stats* out_polish, int64_t iso_cap, int64_t* iso_off);
 
 #ifdef __cplusplus
 }

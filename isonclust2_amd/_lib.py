@@ -190,6 +190,7 @@ SYMBOLS = [
     "ioc_host_read_correct", "ioc_planes_correct", "ioc_align_pairs_correct",
     "ioc_host_planes_blocks", "ioc_planes_blocks", "ioc_align_pairs_blocks",
     "ioc_planes_polish_groups", "ioc_align_pairs_blocks_polish",
+    "ioc_host_ops_project_weights", "ioc_host_planes_pile_weighted", "ioc_planes_polish_groups_weighted", "ioc_align_pairs_blocks_polish_weighted",
 ]
 
 _lib = None
@@ -347,6 +348,11 @@ def load():
     L.ioc_planes_polish_groups.argtypes = [vp, i32, pi32, C.c_char_p, pi64, pi32, i32, pi32, pi32, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, i64,
                                            pi64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_blocks_polish.argtypes = L.ioc_align_pairs_blocks.argtypes + [i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, i64, pi64]
+    L.ioc_host_ops_project_weights.argtypes = [C.c_char_p, i64, C.c_char_p, C.c_char_p, i32, i32, C.c_void_p, C.c_void_p]
+    L.ioc_host_planes_pile_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p]
+    L.ioc_planes_polish_groups_weighted.argtypes = [vp, i32, pi32, C.c_char_p, pi64, pi32, i32, pi32, pi32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i32, C.c_void_p,
+                                                    C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_align_pairs_blocks_polish_weighted.argtypes = L.ioc_align_pairs_blocks_polish.argtypes
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

@@ -190,6 +190,45 @@ def pileup_call_weighted(cols, wcols, wins, frame, min_depth=3, cap=None):
     return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in POLISH_STATS_FIELDS}
 
 
+def ops_project_weights(ops, query, qual, rlen):
+    """ioc_host_ops_project_weights: the weight of every vote one read casts, beside its planes — (wbase, wslots): wbase[r] the
+    weight (qual_weight, 1 .. 93) of the read's base at row r or of its deletion there (the smaller of its neighbours' weights), 0
+    where it does not cover the row; wslots[j, r] the weight of the j-th base of the insertion in front of r, 0 where there is
+    none — laid out like ops_project's base and ops_project_ins' slots.  ValueError for what ops_pileup_weighted refuses."""
+    if len(qual) != len(query):
+        raise ValueError("qual must hold one byte per base of query")
+    wbase, wslots = np.full(rlen + 1, 0xEE, np.uint8), np.full((_lib.PILE_INS_SLOTS, rlen + 1), 0xEE, np.uint8)
+    rc = _lib.load().ioc_host_ops_project_weights(bytes(ops), len(ops), bytes(query), bytes(qual), len(query), int(rlen), wbase.ctypes.data, wslots.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_project_weights failed ({rc})")
+    return wbase, wslots
+
+
+def planes_pile_weighted(base, slots, wbase, wslots, wcols=None, wins=None):
+    """ioc_host_planes_pile_weighted: one read's planes and weight planes ADDED to the tables of weights `wcols` (PILEUP_DTYPE;
+    ins_runs / ins_bases untouched) and `wins` (PILEUP_INS_DTYPE; `longer` untouched), rlen + 1 rows each, where given, else to
+    zeros.  Returns (wcols, wins): for a string with at most one insertion run per row what ops_pileup_weighted gives, except that
+    `longer` stays 0.  ValueError, with both tables untouched, for a byte neither projection writes."""
+    base, slots = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(slots, np.uint8)
+    wbase, wslots = np.ascontiguousarray(wbase, np.uint8), np.ascontiguousarray(wslots, np.uint8)
+    if base.ndim != 1 or len(base) < 1 or slots.shape != (_lib.PILE_INS_SLOTS, len(base)) or wbase.shape != base.shape or wslots.shape != slots.shape:
+        raise ValueError("base and wbase must hold rlen + 1 bytes, slots and wslots PILE_INS_SLOTS x (rlen + 1)")
+    rlen = len(base) - 1
+    if wcols is None:
+        wcols = np.zeros(rlen + 1, PILEUP_DTYPE)
+    if wins is None:
+        wins = np.zeros(rlen + 1, PILEUP_INS_DTYPE)
+    if wcols.dtype != PILEUP_DTYPE or wcols.shape != (rlen + 1,) or not wcols.flags["C_CONTIGUOUS"]:
+        raise ValueError("wcols must be a contiguous array of rlen + 1 rows of PILEUP_DTYPE")
+    if wins.dtype != PILEUP_INS_DTYPE or wins.shape != (rlen + 1,) or not wins.flags["C_CONTIGUOUS"]:
+        raise ValueError("wins must be a contiguous array of rlen + 1 rows of PILEUP_INS_DTYPE")
+    rc = _lib.load().ioc_host_planes_pile_weighted(base.ctypes.data, slots.ctypes.data, wbase.ctypes.data, wslots.ctypes.data, rlen, wcols.ctypes.data,
+                                                   wins.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_planes_pile_weighted failed ({rc})")
+    return wcols, wins
+
+
 # ioc_pile_site as a numpy record, and the allele bytes
 PILE_SITE_DTYPE = np.dtype([(n, np.int32) for n in ("row", "kind", "major", "minor")] + [(n, np.uint32) for n in ("depth", "n_major", "n_minor", "reserved")])
 ALLELE_DEL, ALLELE_NONE = _lib.ALLELE_DEL, _lib.ALLELE_NONE
@@ -1052,7 +1091,7 @@ class Context:
         return out
 
     def align_pairs_blocks_polish(self, pairs, k, segs, seg_of_pair, max_iso=16, polish_min_depth=3, stats=False, tables=False, rows=True, cap=None,
-                                  polish_cap=None, iso_cap=None, match=2, mismatch=-2, gap_extend=1, **rule):
+                                  polish_cap=None, iso_cap=None, match=2, mismatch=-2, gap_extend=1, _entry="ioc_align_pairs_blocks_polish", **rule):
         """ioc_align_pairs_blocks_polish: align_pairs_blocks with the consensus of the first min(n_groups, max_iso) isoforms of every
         segment called from the reads' planes where they lie — no read is aligned a second time.  Returns align_pairs_blocks' dict
         plus `gseq`, `gqual`, `gpolish` and `gseg_off` as planes_polish_groups returns them: isoform h of segment g from its direct
@@ -1072,7 +1111,7 @@ class Context:
         p_cap = sum(b[1] for b in bounds) if polish_cap is None else int(polish_cap)
         seq, qual = np.zeros(max(p_cap, 1), np.uint8), np.zeros(max(p_cap, 1), np.uint8)
         off, pol, goff = np.zeros(max(i_cap, 0) + 1, np.int64), np.zeros(max(i_cap, 1), POLISH_STATS_DTYPE), np.zeros(ns + 1, np.int64)
-        self._chk(self.L.ioc_align_pairs_blocks_polish(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+        self._chk(getattr(self.L, _entry)(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
                                                        _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
                                                        _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
                                                        cols.ctypes.data if tables and n_rows else None, int(max_iso), int(polish_min_depth), seq.ctypes.data,
@@ -1084,6 +1123,54 @@ class Context:
         if tables:
             out.update(cols=cols, row0=self._row0(rlen))
         return out
+
+    def planes_polish_groups_weighted(self, frames, seg_of_pair, group, n_groups, base, slots, wbase, wslots, min_depth=3, tables=False, cap=None):
+        """ioc_planes_polish_groups_weighted: planes_polish_groups with every read's vote counted by its weight — wbase / wslots the
+        weight planes of every pair (ops_project_weights), laid out like base / slots.  Returns planes_polish_groups' dict; with
+        tables=True `gcols` (the counts, as planes_polish_groups returns them), `gwcols` and `gwins` (the sums of weights,
+        planes_pile_weighted over the group's reads) and `grow0` — each group-segment as pileup_call_weighted defines it on them."""
+        ns, n = len(frames), len(base)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        sop, grp, ng = np.ascontiguousarray(seg_of_pair, np.int32), np.ascontiguousarray(group, np.int32), np.ascontiguousarray(n_groups, np.int32)
+        if sop.shape != (n,) or grp.shape != (n,) or len(slots) != n or len(wbase) != n or len(wslots) != n or ng.shape != (ns,):
+            raise ValueError("seg_of_pair, group and the planes must hold one entry per pair and n_groups one per segment")
+        rows = [int(rlen[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (rows[i],) or np.shape(slots[i]) != (_lib.PILE_INS_SLOTS, rows[i]) or np.shape(wbase[i]) != (rows[i],) or \
+                    np.shape(wslots[i]) != (_lib.PILE_INS_SLOTS, rows[i]):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        P = sum(rows)
+        flat = lambda planes: np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in planes]))
+        flat6 = lambda planes: np.ascontiguousarray(np.concatenate([np.zeros((_lib.PILE_INS_SLOTS, 0), np.uint8)] + [np.asarray(x, np.uint8) for x in planes], axis=1))
+        fb, fs, fwb, fws = flat(base), flat6(slots), flat(wbase), flat6(wslots)
+        f_off = np.zeros(ns + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        groups = np.maximum(ng.astype(np.int64), 0)   # (a negative count: the library refuses the call)
+        goff = np.concatenate([[0], np.cumsum(groups)]).astype(np.int64)
+        G = int(goff[-1])
+        bound = sum(int(groups[g]) * pileup_call_bound(rlen[g]) for g in range(ns))
+        cap = bound if cap is None else int(cap)
+        per = np.repeat(rlen.astype(np.int64) + 1, groups)
+        n_rows = int(per.sum())
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, pol = np.zeros(G + 1, np.int64), np.zeros(G, POLISH_STATS_DTYPE)
+        gcols, gwcols, gwins = (np.zeros(n_rows, PILEUP_DTYPE), np.zeros(n_rows, PILEUP_DTYPE), np.zeros(n_rows, PILEUP_INS_DTYPE)) if tables else (None, None, None)
+        tab = lambda a: a.ctypes.data if tables and n_rows else None
+        self._chk(self.L.ioc_planes_polish_groups_weighted(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+                                                           _p(ng, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, _p(grp, C.c_int32) if n else None,
+                                                           fb.ctypes.data if P else None, fs.ctypes.data if P else None, fwb.ctypes.data if P else None,
+                                                           fws.ctypes.data if P else None, int(min_depth), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64),
+                                                           pol.ctypes.data if G else None, tab(gcols), tab(gwcols), tab(gwins)))
+        out = self._groups_out(goff, seq, qual, off, pol)
+        if tables:
+            out.update(gcols=gcols, gwcols=gwcols, gwins=gwins, grow0=np.concatenate([[0], np.cumsum(per)])[:G].astype(np.int64))
+        return out
+
+    def align_pairs_blocks_polish_weighted(self, pairs, k, segs, seg_of_pair, **kw):
+        """ioc_align_pairs_blocks_polish_weighted: align_pairs_blocks_polish with every isoform called by weight, under the quality
+        lines of align_set_pool_qual (IocError without them).  The arguments and the dict of align_pairs_blocks_polish; everything
+        but `gseq`, `gqual` and `gpolish` is what that call returns."""
+        return self.align_pairs_blocks_polish(pairs, k, segs, seg_of_pair, _entry="ioc_align_pairs_blocks_polish_weighted", **kw)
 
     @staticmethod
     def _gpolish_out(ns, rlen, seq, qual, off, pol, gcols, gins, tables):

@@ -34,6 +34,7 @@ struct DumpOptions {
     // --isoforms: cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, the exon blocks of a cluster and every read's isoform; --isoforms-*
     // --isoforms-polish: cluster_isoforms.fq, the consensus of every isoform of every cluster that has a block
     // --isoforms-polish-min-depth / --isoforms-polish-max: positions covered by fewer reads of the isoform keep the representative's base / the isoforms called per cluster
+    // --isoforms-polish-weighted: every isoform is called by weight, every read voting with its base qualities
     ReportOpts reports;
 };
 
@@ -57,7 +58,7 @@ void print_dump_help()
          << "                    [--correct [--correct-min-depth N] [--correct-min-alt N] [--correct-min-pct P] [--correct-max-run N]]" << endl
          << "                    [--isoforms [--isoforms-min-gap N] [--isoforms-min-depth N] [--isoforms-min-alt N] [--isoforms-min-pct P]" << endl
          << "                     [--isoforms-min-block N] [--isoforms-max N]" << endl
-         << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N]]] final.cer" << endl
+         << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N] [--isoforms-polish-weighted]]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -125,7 +126,10 @@ void print_dump_help()
          << "                 not found.  Whether an isoform is real is the reader's judgement of the counts" << endl
          << "  --isoforms-polish-min-depth N   positions covered by fewer than N reads of the isoform keep the representative's base (default 3)" << endl
          << "  --isoforms-polish-max N         call the first N isoforms of a cluster (default 16: a choice — it bounds what a cluster may" << endl
-         << "                 write before its isoforms are known — that was not measured on real data)" << endl;
+         << "                 write before its isoforms are known — that was not measured on real data)" << endl
+         << "  --isoforms-polish-weighted      with --isoforms-polish: call every isoform by weight — every read votes with the base qualities of" << endl
+         << "                 its line (Phred, 1 .. 93), a deletion with the smaller of its neighbours'; the depth gates stay counts of reads." << endl
+         << "                 The same records of cluster_isoforms.fq, names and order; still no read is aligned again" << endl;
 }
 
 DumpOptions parse_dump_options(int argc, char** argv)
@@ -148,7 +152,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms-min-pct", required_argument, 0, 1025}, {"isoforms-min-block", required_argument, 0, 1026},
                                        {"isoforms-max", required_argument, 0, 1027}, {"isoforms-polish", no_argument, 0, 1028},
                                        {"isoforms-polish-min-depth", required_argument, 0, 1029}, {"isoforms-polish-max", required_argument, 0, 1030},
-                                       {0, 0, 0, 0}};
+                                       {"isoforms-polish-weighted", no_argument, 0, 1031}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false, iso_polish = false;
@@ -190,6 +194,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1028: iso_polish = true; break;
             case 1029: iso_polish_min_depth = number("--isoforms-polish-min-depth", optarg, 1, INT32_MAX); break;
             case 1030: r.isoforms.polish_max = number("--isoforms-polish-max", optarg, 1, INT32_MAX); break;
+            case 1031: r.isoforms.polish_weighted = true; break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -201,6 +206,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (split_polish && !r.split.on) die("--split-polish asks for --split!");
     if (split_polish) r.split.polish_min_depth = split_polish_min_depth;
     if (iso_polish && !r.isoforms.on) die("--isoforms-polish asks for --isoforms!");
+    if (r.isoforms.polish_weighted && !iso_polish) die("--isoforms-polish-weighted asks for --isoforms-polish!");
     if (iso_polish) r.isoforms.polish_min_depth = iso_polish_min_depth;
     if (polish) r.polish_min_depth = polish_min_depth;
     if (d.index.empty()) die("Specifying the sorted read index is mandatory!");

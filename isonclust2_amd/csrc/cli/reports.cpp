@@ -66,6 +66,12 @@
 // "@cluster_<id>/iso<h> key=<signature as in cluster_isoforms.tsv> reads=<its direct and assigned reads> subs= dels= ins= low=", in
 // the frame of that record; positions covered by fewer than --isoforms-polish-min-depth reads of the isoform keep the
 // representative's base with quality '!'.  The other report files are what they are without the option.
+//
+// dump --isoforms --isoforms-polish --isoforms-polish-weighted: the same records of cluster_isoforms.fq, names and order, every
+// isoform called by weight (ioc_align_pairs_blocks_polish_weighted: the weight of every vote kept beside the reads' planes, still
+// no read aligned a second time): every read votes with the base qualities of its line as --polish-weighted has them.  Where
+// an isoform has 5 to 12 reads this is what keeps three low-quality reads from outvoting two good ones.  The other report files
+// are what they are without the option.
 #include "reports.hpp"
 
 #include <cstdio>
@@ -235,12 +241,17 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
             const IsoCapacity icap = iso_polish_capacity(g, io.polish_max);
             ip.reset(icap.bytes, size_t(icap.isoforms));
             r.iso_off.assign(ns + 1, 0);
-            check(c, ioc_align_pairs_blocks_polish(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
-                                                   g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
-                                                   r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
-                                                   o.pileup && !have_first ? r.cols.data() : nullptr, io.polish_max, io.polish_min_depth, &ip.seq[0], &ip.qual[0],
-                                                   icap.bytes, ip.off.data(), ip.stats.data(), icap.isoforms, r.iso_off.data()),
-                  "exon blocks with the isoforms' consensus");
+            if (io.polish_weighted) {
+                // (the quality lines lie in `quals` in the order and at the lengths of the sequences in `pool`)
+                if (g.qoffs != g.offs) die("--isoforms-polish-weighted: a quality line is not as long as its sequence!");
+                check(c, ioc_align_set_pool_qual(c, g.quals.data(), int64_t(g.quals.size())), "pool qualities");
+            }
+            const auto call = io.polish_weighted ? ioc_align_pairs_blocks_polish_weighted : ioc_align_pairs_blocks_polish;
+            check(c, call(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(), io.min_gap,
+                          io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(),
+                          r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr, io.polish_max, io.polish_min_depth, &ip.seq[0], &ip.qual[0],
+                          icap.bytes, ip.off.data(), ip.stats.data(), icap.isoforms, r.iso_off.data()),
+                  io.polish_weighted ? "exon blocks with the isoforms' weighted consensus" : "exon blocks with the isoforms' consensus");
         } else {
             check(c, ioc_align_pairs_blocks(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
                                             io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,

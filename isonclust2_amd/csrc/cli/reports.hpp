@@ -1,4 +1,4 @@
-// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish): every read of clusters.tsv
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish, --isoforms-polish-weighted): every read of clusters.tsv
 // aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
 // formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
 #ifndef ISONCLUST2_CLI_REPORTS_HPP
@@ -30,6 +30,7 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     int min_gap = 20, min_depth = 3, min_alt = 3, min_pct = 25, min_block = 10, max_blocks = 32;
     int polish_min_depth = 0;  // --isoforms-polish: > 0, the depth below which an isoform's call keeps the representative's base, and ...
     int polish_max = 16;       // ... how many isoforms of a cluster are called
+    bool polish_weighted = false;  // --isoforms-polish-weighted: every isoform is called by weight (ioc_align_pairs_blocks_polish_weighted)
 };
 struct ReportOpts {
     bool stats = false;        // --read-stats

@@ -486,6 +486,70 @@ int ioc_host_planes_pile(const uint8_t* base, const uint8_t* slots, int32_t rlen
     return IOC_OK;
 }
 
+// The weight part of a read's projection (isonclust2_hip.h has the rules): the weight of every vote of the read, a byte per
+// (plane, row) — the definition k_ops_project_weights (ioc_group_pile_weighted.hip) is tested against.  The walk, the weights and
+// the refusals of ioc_host_ops_pileup_weighted.
+int ioc_host_ops_project_weights(const char* ops, int64_t len, const char* query, const char* qual, int32_t qlen, int32_t rlen, uint8_t* wbase, uint8_t* wslots)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || qlen < 0 || rlen < 0 || (qlen > 0 && (!query || !qual)) || !wbase || !wslots) return IOC_ERR_ARG;
+    int64_t q = 0, r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        q += op == '=' || op == 'X' || op == 'I' || op == 'i';
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (q != qlen || r != rlen) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1;
+    memset(wbase, 0, rows);
+    memset(wslots, 0, size_t(IOC_PILE_INS_SLOTS) * rows);
+    q = r = 0;
+    int64_t j = 0;  // the index of an 'I' in its run
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (op == 'I') {
+            if (j < IOC_PILE_INS_SLOTS) wslots[size_t(j) * rows + size_t(r)] = uint8_t(pile_qual_weight(uint8_t(qual[q])));
+            ++j, ++q;
+            continue;
+        }
+        j = 0;
+        switch (op) {
+        case 'd': ++r; break;
+        case 'i': ++q; break;
+        case 'D': {
+            const uint32_t wa = q > 0 ? pile_qual_weight(uint8_t(qual[q - 1])) : 0u, wb = q < qlen ? pile_qual_weight(uint8_t(qual[q])) : 0u;
+            wbase[r++] = uint8_t(wa == 0u ? (wb == 0u ? 1u : wb) : wb == 0u ? wa : std::min(wa, wb));
+            break;
+        }
+        default: wbase[r++] = uint8_t(pile_qual_weight(uint8_t(qual[q++]))); break;  // ('=' 'X')
+        }
+    }
+    return IOC_OK;
+}
+
+// One read's planes and weight planes ADDED to the two tables of weights of its reference (isonclust2_hip.h has the rules) — the
+// definition k_group_pile_weighted (ioc_group_pile_weighted.hip) is tested against.  The planes are checked before either table
+// is touched.
+int ioc_host_planes_pile_weighted(const uint8_t* base, const uint8_t* slots, const uint8_t* wbase, const uint8_t* wslots, int32_t rlen, ioc_pileup_col* wcols,
+                                  ioc_pileup_ins* wins)
+{
+    if (rlen < 0 || !base || !slots || !wbase || !wslots || !wcols || !wins) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1;
+    for (size_t r = 0; r < rows; ++r)
+        if (base[r] > IOC_ALLELE_DEL && base[r] != IOC_ALLELE_NONE) return IOC_ERR_ARG;
+    for (size_t x = 0; x < size_t(IOC_PILE_INS_SLOTS) * rows; ++x)
+        if (slots[x] > 5) return IOC_ERR_ARG;
+    for (size_t r = 0; r < rows; ++r) {
+        uint32_t* const word = reinterpret_cast<uint32_t*>(&wcols[r]);  // (a c g t other del: the record's first six words, PILE_A .. PILE_DEL)
+        if (base[r] != IOC_ALLELE_NONE) word[base[r]] += wbase[r];
+        for (size_t j = 0; j < size_t(IOC_PILE_INS_SLOTS); ++j) {
+            const uint8_t s = slots[j * rows + r];
+            if (s != 0) wins[r].slot[j][s - 1] += wslots[j * rows + r];
+        }
+    }
+    return IOC_OK;
+}
+
 // The sites of one reference from its table of counts (isonclust2_hip.h has the rules; pile_sites_row, ioc_pile_sites.h, decides a
 // row for this function and for the kernels of ioc_pile_sites.hip alike).
 int64_t ioc_host_pileup_sites(const ioc_pileup_col* cols, int32_t rlen, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,

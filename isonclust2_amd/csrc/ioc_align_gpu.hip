@@ -1156,7 +1156,7 @@ struct OpsRun {
     std::vector<uint32_t> q_off;       // ... and where its query starts in the pool
     const int64_t* d_row_base = nullptr;
     const uint32_t* d_q_off = nullptr;
-    std::vector<uint32_t> q_len;  // (weighted pileup) per device pair: its query's length
+    std::vector<uint32_t> q_len;  // (weighted pileup, a pile that projects the weights) per device pair: its query's length
     const uint32_t* d_q_len = nullptr;
     std::vector<uint64_t> plane;  // (a pile that projects) per device pair: where its planes start
     const uint64_t* d_plane = nullptr;
@@ -1192,7 +1192,7 @@ int ops_reserve(ioc_ctx* c, OpsRun& o, uint64_t max_slice_bytes, const std::vect
         IOC_CHK(c, hipMemcpyAsync(p + lay.row_base, o.row_base.data(), np * 8, hipMemcpyHostToDevice, c->stream));
         IOC_CHK(c, hipMemcpyAsync(p + lay.q_off, o.q_off.data(), np * 4, hipMemcpyHostToDevice, c->stream));
     }
-    if (h.has_pile() && h.pile.kind == PileKind::weighted) {
+    if (h.has_pile() && (h.pile.kind == PileKind::weighted || h.projects_weights())) {
         o.q_len.resize(np);
         for (size_t x = 0; x < np; ++x) o.q_len[x] = dp[x].n;
         o.d_q_len = reinterpret_cast<const uint32_t*>(p + lay.q_len);
@@ -1219,7 +1219,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     int r;
     if (stats && (r = ioc_reserve(c, c->a_ostats, size_t(cnt) * sizeof(ioc_aln_stats))) != IOC_OK) return r;
     EventSet ev;
-    ev.v.assign(5, nullptr);
+    ev.v.assign(6, nullptr);
     for (auto& e : ev.v) IOC_CHK(c, hipEventCreate(&e));
     IOC_CHK(c, hipEventRecord(ev.v[0], c->stream));
     if (stats) IOC_CHK(c, iock_ops_stats(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, c->a_ostats.as<ioc_aln_stats>()));
@@ -1250,6 +1250,10 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
         IOC_CHK(c, iock_ops_project_ins(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_plane, pool,
                                         pool_bytes, pl.slot_planes, uint64_t(pl.plane_bytes)));
     IOC_CHK(c, hipEventRecord(ev.v[4], c->stream));
+    if (h.projects_weights())
+        IOC_CHK(c, iock_ops_project_weights(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_q_len, o.d_plane,
+                                            static_cast<const uint8_t*>(c->a_qual.p), pool_bytes, pl.weight_planes, uint64_t(pl.plane_bytes)));
+    IOC_CHK(c, hipEventRecord(ev.v[5], c->stream));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
@@ -1271,6 +1275,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     if (pile && hipEventElapsedTime(&ms, ev.v[1], ev.v[2]) == hipSuccess) t.ms_pileup += double(ms);
     if (h.projects() && hipEventElapsedTime(&ms, ev.v[2], ev.v[3]) == hipSuccess) t.ms_project += double(ms);
     if (h.projects_ins() && hipEventElapsedTime(&ms, ev.v[3], ev.v[4]) == hipSuccess) t.ms_project_ins += double(ms);
+    if (h.projects_weights() && hipEventElapsedTime(&ms, ev.v[4], ev.v[5]) == hipSuccess) t.ms_project_weights += double(ms);
     t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t.copied += int64_t(dp.size() * 4 + (stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
     if (stats) t.records += int64_t(cnt);

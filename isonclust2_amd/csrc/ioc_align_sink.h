@@ -27,6 +27,8 @@ struct AlnTally {
     double ms_project_ins = 0;  // k_ops_project_ins' device time (a pile that projects what the pairs insert as well), and ...
     double ms_plane_pile = 0;   // ... k_plane_pile's (ioc_planes_polish, ioc_align_pairs_split_polish)
     double ms_group_pile = 0;   // k_group_pile's device time (ioc_planes_polish_groups, ioc_align_pairs_blocks_polish)
+    double ms_project_weights = 0;      // k_ops_project_weights' device time (a pile that projects the weights of the votes as well), and ...
+    double ms_group_pile_weighted = 0;  // ... k_group_pile_weighted's (ioc_planes_polish_groups_weighted, ioc_align_pairs_blocks_polish_weighted)
     double ms_correct = 0;      // k_read_correct's device time, both passes and the scan (ioc_planes_correct, ioc_align_pairs_correct)
     double ms_blocks = 0;       // the eight kernels of ioc_read_blocks.hip, their device time together (ioc_planes_blocks, ioc_align_pairs_blocks)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
@@ -99,7 +101,7 @@ struct OpsLayout {
     size_t room;      // uint32: query length + reference length (a reduced sink)
     size_t row_base;  // int64: first row, -1 for a pair that has been added already (a pile)
     size_t q_off;     // uint32: where the query starts in the pool (a pile)
-    size_t q_len;     // uint32: the query's length (a weighted pile)
+    size_t q_len;     // uint32: the query's length (a weighted pile, a pile that projects the weights: a projecting table has the column)
     size_t plane;     // uint64: where the pair's planes start (a pile that projects)
     size_t bytes;     // the slice's bytes: the table, rounded up to 16
     size_t spare;     // behind the bytes: k_ops_stats and k_ops_pileup read the dword that holds a string's last byte whole
@@ -149,6 +151,10 @@ struct AlnSink {
         // bytes of each of IOC_PILE_INS_SLOTS more planes, one behind the other, from byte plane[i] of each on
         bool project_ins = false;
         uint8_t* slot_planes = nullptr;  // (device) [all slot-0 planes] .. [all slot-5 planes], plane_bytes each
+        // optional, with project_ins (project_weights): the weight of every vote of the pair is projected too (k_ops_project_weights),
+        // under the pool's quality bytes, into reference length + 1 bytes of each of 1 + IOC_PILE_INS_SLOTS more planes
+        bool project_weights = false;
+        uint8_t* weight_planes = nullptr;  // (device) [wbase plane][all wslot-0 planes] .. [all wslot-5 planes], plane_bytes each
     } pile;
 
     bool reduced() const { return kind == SinkKind::reduced; }
@@ -156,6 +162,8 @@ struct AlnSink {
     bool has_pile() const { return reduced() && pile.kind != PileKind::none; }
     bool projects() const { return has_pile() && pile.project; }
     bool projects_ins() const { return projects() && pile.project_ins; }
+    bool projects_weights() const { return projects_ins() && pile.project_weights; }
+    uint64_t planes() const { return !pile.project ? 0 : !pile.project_ins ? 2 : 2 + uint64_t(IOC_PILE_INS_SLOTS) + (pile.project_weights ? 1 + uint64_t(IOC_PILE_INS_SLOTS) : 0); }
     // what the tables hold of the device for the whole call (ck_budget's `held`)
     uint64_t pile_bytes() const
     {
@@ -163,7 +171,7 @@ struct AlnSink {
         const uint64_t per_row = pile.kind == PileKind::counts ? sizeof(ioc_pileup_col)
                                  : pile.kind == PileKind::ins  ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins)
                                                                : 2 * sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins);
-        return uint64_t(pile.rows) * per_row + (pile.project ? (pile.project_ins ? 2 + uint64_t(IOC_PILE_INS_SLOTS) : 2) * uint64_t(pile.plane_bytes) : 0);
+        return uint64_t(pile.rows) * per_row + planes() * uint64_t(pile.plane_bytes);
     }
     OpsLayout layout(size_t np) const { return ops_layout(np, kind, reduced() ? pile.kind : PileKind::none, projects()); }
 

@@ -14,6 +14,7 @@
 
 #include "ioc_align_sink.h"
 #include "ioc_group_pile.h"
+#include "ioc_group_pile_weighted.h"
 #include "ioc_internal.h"
 #include "ioc_plane_pile.h"
 #include "ioc_read_blocks.h"
@@ -85,7 +86,7 @@ int call_room_ok(ioc_ctx* c, const std::string& who, const CallOut& o, int64_t b
 struct PiledDev {  // pile: the tables of the kind (a_pile; a_pile_ins or a_pile_w) and, where it projects, the planes (a_planes)
     ioc_pileup_col *cols, *wcols;
     ioc_pileup_ins *ins, *wins;
-    uint8_t *base, *insf, *slots;
+    uint8_t *base, *insf, *slots, *weights;
 };
 struct SitesDev {  // sites (a_call): the segments, what was kept, and the room of the allele gather behind them
     const IocPileSeg* segs;
@@ -100,6 +101,8 @@ struct GroupPiled {  // group pile (a_gpile): the tables of the 2 n group-segmen
     std::vector<IocPileSeg> gsegs;
     ioc_pileup_col* cols;
     ioc_pileup_ins* ins;
+    ioc_pileup_col* wcols = nullptr;  // (groups_pile, weighted: cols holds the counts, these the sums of weights; ins is not made)
+    ioc_pileup_ins* wins = nullptr;
     int64_t n_rows = 0;  // (groups_pile: the rows of its tables, the sum over the group-segments of rlen + 1, ...
     GroupMemberLists lists;           // ... every group's member list and ...
     std::vector<IocGroupWork> work;   // ... the work items, which the uploads read until the call stage has waited for the stream)
@@ -116,6 +119,9 @@ struct IsoPolish {  // the call of the first min(n_groups, max_iso) isoforms of 
 struct Planes {
     const uint32_t *mem_off, *members;
     const uint8_t *group, *base, *slots;
+    // (a weighted groups pile) the seven weight planes: on the device one behind the other, [wbase plane][wslot planes x 6]; the
+    // host's as the caller holds them, wbase and wslots
+    const uint8_t *weights = nullptr, *wbase = nullptr, *wslots = nullptr;
 };
 struct Out { void* dst; const void* src; size_t bytes; };  // a block that goes back to the host where the caller asked for it (dst NULL: not)
 
@@ -157,13 +163,15 @@ struct SinkRun {
         t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return IOC_OK;
     }
-    int pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane, int64_t plane_bytes, bool project_ins, PiledDev& d);
+    int pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane, int64_t plane_bytes, bool project_ins, PiledDev& d,
+             bool project_weights = false);
     int sites(const SitesRule& r, const SinkPlan& p, const ioc_pileup_col* d_cols, ioc_pile_site* out_sites, int64_t* site_off, int64_t* n_found, SitesDev& d);
     int alleles(const SitesDev& d, const SinkPlan& p, const int32_t* seg_of_pair, const PiledDev& planes, const int64_t* site_off, int64_t* allele_off, uint8_t* out_alleles);
     int split(const SplitCall& sp, size_t n, size_t np, const int32_t* seg_of_pair, const int64_t* site_off, const int64_t* allele_off, const ioc_pile_site* sites,
               const uint8_t* alleles, bool on_device, Planes& d);
     int group_pile(const SinkPlan& p, const int32_t* seg_of_pair, const Planes& host, Planes dev, GroupPiled& d);
-    int groups_pile(const SinkPlan& p, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& host, Planes dev, GroupPiled& d);
+    int groups_pile(const SinkPlan& p, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& host, Planes dev, GroupPiled& d,
+                    bool weighted = false);
     int correct(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* d_frames, uint64_t frame_bytes, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
                 const Planes& host, Planes dev, const CorrectOut& o);
     int blocks(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o);
@@ -172,9 +180,11 @@ struct SinkRun {
 // Pile and project.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it (ins), or a_pile_w as [wcols][wins] (weighted)
 // — are reserved and zeroed and the pairs aligned into them (k_ops_pileup adds, where the walks' bytes lie, slice after slice and re-run after
 // re-run).  `plane` (the alleles family): every pair is projected as well, into the planes of a_planes, [base planes][ins planes] and, with
-// project_ins, [slot planes x 6] behind them, set to IOC_ALLELE_NONE / 0 once here.
+// project_ins, [slot planes x 6] behind them, set to IOC_ALLELE_NONE / 0 once here; with project_weights (which asks for project_ins
+// and for the pool's qualities), [weight planes x 7] behind those, set to 0 with them.  A call without project_weights reserves what
+// it always did.
 int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane,
-                  int64_t plane_bytes, bool project_ins, PiledDev& d)
+                  int64_t plane_bytes, bool project_ins, PiledDev& d, bool project_weights)
 {
     IOC_CHK(c, hipSetDevice(c->device));
     const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
@@ -192,18 +202,20 @@ int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, con
     if (weighted) pl.wcols = second->as<ioc_pileup_col>(), pl.wins = reinterpret_cast<ioc_pileup_ins*>(second->as<uint8_t>() + b_cols);  // (b_cols: a multiple of 32)
     if (plane) {
         const size_t b_plane = size_t(plane_bytes);
-        IOC_TRY(ioc_reserve(c, c->a_planes, (project_ins ? 2 + size_t(IOC_PILE_INS_SLOTS) : 2) * b_plane));
+        const size_t n_zeroed = !project_ins ? 1 : 1 + size_t(IOC_PILE_INS_SLOTS) + (project_weights ? size_t(IOC_WEIGHT_PLANES) : 0);  // (the ins planes and on)
+        IOC_TRY(ioc_reserve(c, c->a_planes, (1 + n_zeroed) * b_plane));
         pl.project = true, pl.base_planes = c->a_planes.as<uint8_t>(), pl.ins_planes = pl.base_planes + b_plane;
         pl.plane_bytes = plane_bytes, pl.plane = plane;
         if (project_ins) pl.project_ins = true, pl.slot_planes = pl.base_planes + 2 * b_plane;
+        if (project_ins && project_weights) pl.project_weights = true, pl.weight_planes = pl.slot_planes + size_t(IOC_PILE_INS_SLOTS) * b_plane;
         if (b_plane > 0) {
             IOC_CHK(c, hipMemsetAsync(pl.base_planes, IOC_ALLELE_NONE, b_plane, c->stream));
-            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, (project_ins ? 1 + size_t(IOC_PILE_INS_SLOTS) : 1) * b_plane, c->stream));  // (and the slot planes)
+            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, n_zeroed * b_plane, c->stream));  // (and the slot planes, and the weight planes)
         }
     }
     const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, out_stats != nullptr, out_stats, pl};
     IOC_TRY(a.run(c, a.n_pairs > 0 ? &sink : nullptr));
-    d = PiledDev{pl.cols, pl.wcols, pl.ins, pl.wins, pl.base_planes, pl.ins_planes, pl.slot_planes};
+    d = PiledDev{pl.cols, pl.wcols, pl.ins, pl.wins, pl.base_planes, pl.ins_planes, pl.slot_planes, pl.weight_planes};
     return IOC_OK;
 }
 
@@ -378,8 +390,10 @@ int SinkRun::group_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const Pl
 // are uploaded.  Every group's own member list is made on the host (group_member_lists) and uploaded, 4 bytes a pair that is in a
 // group.  Group-segment x owns the rows of both tables from the sum over the earlier group-segments of (rlen + 1) on; the tables
 // are set to 0 first: k_group_pile is launched over the group-segments that have reads alone.  The stream is not waited for: the
-// call stage behind it does that.  G is at least 1.
-int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& ph, Planes pd, GroupPiled& d)
+// call stage behind it does that.  G is at least 1.  weighted: k_group_pile_weighted in its place, over the seven weight planes
+// as well ([weight planes] behind the slot planes where they are uploaded), and the tables are [gcols][gwcols][gwins].
+int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& ph, Planes pd, GroupPiled& d,
+                         bool weighted)
 {
     const std::vector<IocPileSeg>& ds = pn.segs;
     const size_t n = ds.size(), np = pn.plane.size(), P = size_t(pn.plane_bytes);
@@ -401,8 +415,9 @@ int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const i
     Arena l;
     const size_t o_gseg = l.take(G * sizeof(IocPileSeg)), o_work = l.take(work.size() * sizeof(IocGroupWork)), o_plane = l.take(np * 8),
                  o_goff = l.take((G + 1) * 4), o_gmem = l.take(M * 4), o_base = l.take(pd.base ? 0 : P),
-                 o_slots = l.take(pd.slots ? 0 : size_t(IOC_PILE_INS_SLOTS) * P), o_cols = l.take(size_t(d.n_rows) * sizeof(ioc_pileup_col)),
-                 o_ins = l.take(size_t(d.n_rows) * sizeof(ioc_pileup_ins));
+                 o_slots = l.take(pd.slots ? 0 : size_t(IOC_PILE_INS_SLOTS) * P), o_weights = l.take(!weighted || pd.weights ? 0 : size_t(IOC_WEIGHT_PLANES) * P),
+                 o_cols = l.take(size_t(d.n_rows) * sizeof(ioc_pileup_col)), o_wcols = l.take(weighted ? size_t(d.n_rows) * sizeof(ioc_pileup_col) : 0),
+                 o_ins = l.take(size_t(d.n_rows) * sizeof(ioc_pileup_ins));  // (weighted: gwins)
     IOC_CHK(c, hipSetDevice(c->device));
     IOC_TRY(ioc_reserve(c, c->a_gpile, l.size()));
     uint8_t* p = static_cast<uint8_t*>(c->a_gpile.p);
@@ -414,10 +429,24 @@ int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const i
     IOC_CHK(c, up(o_gmem, m.gmembers.data(), M * 4));
     if (!pd.base) IOC_CHK(c, up(o_base, ph.base, P));
     if (!pd.slots) IOC_CHK(c, up(o_slots, ph.slots, size_t(IOC_PILE_INS_SLOTS) * P));
+    if (weighted && !pd.weights) {
+        IOC_CHK(c, up(o_weights, ph.wbase, P));
+        IOC_CHK(c, up(o_weights + P, ph.wslots, size_t(IOC_PILE_INS_SLOTS) * P));
+    }
     if (!pd.base) pd.base = p + o_base;  // (what does not lie on the device yet was uploaded)
     if (!pd.slots) pd.slots = p + o_slots;
+    if (weighted && !pd.weights) pd.weights = p + o_weights;
     d.cols = reinterpret_cast<ioc_pileup_col*>(p + o_cols), d.ins = reinterpret_cast<ioc_pileup_ins*>(p + o_ins);
     IOC_CHK(c, hipMemsetAsync(p + o_cols, 0, l.size() - o_cols, c->stream));
+    if (weighted) {
+        d.ins = nullptr, d.wcols = reinterpret_cast<ioc_pileup_col*>(p + o_wcols), d.wins = reinterpret_cast<ioc_pileup_ins*>(p + o_ins);
+        IOC_TRY(begin(t.ms_group_pile_weighted));
+        IOC_CHK(c, iock_group_pile_weighted(c->stream, reinterpret_cast<const IocGroupWork*>(p + o_work), uint32_t(work.size()),
+                                            reinterpret_cast<const IocPileSeg*>(p + o_gseg), uint32_t(G), reinterpret_cast<const uint32_t*>(p + o_goff),
+                                            reinterpret_cast<const uint32_t*>(p + o_gmem), uint32_t(M), uint32_t(np), reinterpret_cast<const uint64_t*>(p + o_plane),
+                                            pd.base, pd.slots, pd.weights, uint64_t(P), d.cols, d.wcols, d.wins, uint64_t(d.n_rows)));
+        return end();
+    }
     IOC_TRY(begin(t.ms_group_pile));
     IOC_CHK(c, iock_group_pile(c->stream, reinterpret_cast<const IocGroupWork*>(p + o_work), uint32_t(work.size()), reinterpret_cast<const IocPileSeg*>(p + o_gseg),
                                uint32_t(G), reinterpret_cast<const uint32_t*>(p + o_goff), reinterpret_cast<const uint32_t*>(p + o_gmem), uint32_t(M), uint32_t(np),
@@ -922,6 +951,22 @@ static int groups_polish_device(SinkRun& r, const GroupPolish& gp, const SinkPla
     return r.copy_out({{gp.out_gcols, g.cols, size_t(g.n_rows) * sizeof(ioc_pileup_col)}, {gp.out_gins, g.ins, size_t(g.n_rows) * sizeof(ioc_pileup_ins)}});
 }
 
+// weighted groups pile -> weighted call -> copy-out: the weighted consensus of every group of every segment (frames in d_frames) —
+// the counts gate, the sums of weights decide (pile_call_device with d_gate) —, the three group tables where asked for
+struct GroupTablesW {
+    ioc_pileup_col *out_gcols, *out_gwcols;
+    ioc_pileup_ins* out_gwins;
+};
+static int groups_polish_weighted_device(SinkRun& r, const CallOut& call, const GroupTablesW& o, const SinkPlan& p, const uint8_t* d_frames, uint64_t frame_bytes,
+                                         const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& host, const Planes& dev)
+{
+    GroupPiled g;
+    IOC_TRY(r.groups_pile(p, seg_of_pair, group, n_groups, host, dev, g, /*weighted*/ true));
+    IOC_TRY(pile_call_device(r, g.gsegs, d_frames, frame_bytes, call, g.wcols, g.wins, g.cols, g.n_rows));
+    const size_t b_cols = size_t(g.n_rows) * sizeof(ioc_pileup_col);
+    return r.copy_out({{o.out_gcols, g.cols, b_cols}, {o.out_gwcols, g.wcols, b_cols}, {o.out_gwins, g.wins, size_t(g.n_rows) * sizeof(ioc_pileup_ins)}});
+}
+
 // upload -> groups pile -> call -> copy-out.  ioc_planes_polish over any number of groups a segment: everything is uploaded, every
 // group's own member list with it, and k_group_pile and the call kernels run as behind ioc_align_pairs_blocks_polish.
 int ioc_planes_polish_groups(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups,
@@ -957,6 +1002,48 @@ int ioc_planes_polish_groups(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, co
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   planes polish groups: %lld group-segments, %d pairs, %lld plane bytes, %lld bytes called, k_group_pile %.3f ms, k_pile_call %.3f ms\n",
                 (long long)G, n_pairs, (long long)(7 * p.plane_bytes), (long long)out_off[G], r.t.ms_group_pile, r.t.ms_call);
+    return IOC_OK;
+}
+
+// upload -> weighted groups pile -> weighted call -> copy-out.  ioc_planes_polish_groups with every read's vote counted by its
+// weight: the seven weight planes are uploaded beside the seven, k_group_pile_weighted adds up the three tables of every group and
+// the weighted mode of the call kernels runs over the group-segments.  The checks of ioc_planes_polish_groups, in its order.
+int ioc_planes_polish_groups_weighted(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups,
+                                      int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base, const uint8_t* slots,
+                                      const uint8_t* wbase, const uint8_t* wslots, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                                      ioc_polish_stats* out_polish, ioc_pileup_col* out_gcols, ioc_pileup_col* out_gwcols, ioc_pileup_ins* out_gwins)
+{
+    const std::string who = "ioc_planes_polish_groups_weighted";
+    const CallOut call{min_depth, out_seq, out_qual, cap, out_off, out_polish};
+    if (!c || n_segs < 0 || n_pairs < 0 || !call.ok() || (n_segs > 0 && (!rlen || !frame_off || !n_groups)) || (n_pairs > 0 && (!seg_of_pair || !group)))
+        return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen(who, n_segs, rlen, frames, frame_off, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !slots)) return IOC_ERR_ARG;
+    if (n_pairs > 0 && (!wbase || !wslots)) return IOC_ERR_ARG;
+    int64_t G = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (n_groups[g] < 0) return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " has a negative number of groups");
+        if ((G += n_groups[g]) > INT32_MAX) return ioc_fail(c, IOC_ERR_ARG, who + ": more than 2^31 - 1 group-segments");
+    }
+    for (int32_t i = 0; i < n_pairs; ++i)
+        if (group[i] < -1 || group[i] >= n_groups[seg_of_pair[i]])
+            return ioc_fail(c, IOC_ERR_ARG, who + ": the group of pair " + std::to_string(i) + " is neither -1 nor one of its segment's");
+    IOC_TRY(groups_polish_ok(c, who, call, p.segs, n_groups));
+    out_off[0] = 0;
+    if (G == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(p.frame_bytes)));
+    if (p.frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(p.frame_bytes), hipMemcpyHostToDevice, c->stream));
+    SinkRun r{c};
+    Planes host{nullptr, nullptr, nullptr, base, slots};
+    host.wbase = wbase, host.wslots = wslots;
+    IOC_TRY(groups_polish_weighted_device(r, call, GroupTablesW{out_gcols, out_gwcols, out_gwins}, p, static_cast<const uint8_t*>(d_frames.p),
+                                          uint64_t(p.frame_bytes), seg_of_pair, group, n_groups, host, Planes{}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes polish groups weighted: %lld group-segments, %d pairs, %lld plane bytes, %lld bytes called, k_group_pile_weighted %.3f ms, k_pile_call<weighted> %.3f ms\n",
+                (long long)G, n_pairs, (long long)(14 * p.plane_bytes), (long long)out_off[G], r.t.ms_group_pile_weighted, r.t.ms_call);
     return IOC_OK;
 }
 
@@ -1099,19 +1186,19 @@ int ioc_align_pairs_blocks(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
 // behind the block kernels k_group_pile and the call kernels over the planes: the consensus of the first min(n_groups, max_iso)
 // isoforms of every segment, each from its direct and assigned reads, with no pair aligned a second time.  The read and segment
 // records are on the host when the block stage returns; they say which group-segments there are and who is in them.
-int ioc_align_pairs_blocks_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
-                                  int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
-                                  const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
-                                  int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
-                                  int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t max_iso,
-                                  int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
-                                  int64_t iso_cap, int64_t* iso_off)
+// weighted (ioc_align_pairs_blocks_polish_weighted): the pile projects the seven weight planes as well (k_ops_project_weights, under
+// the pool's qualities), k_group_pile_weighted stands in k_group_pile's place and the call kernels run in their weighted mode.
+static int align_pairs_blocks_polish(ioc_ctx* c, const std::string& who, bool weighted, const AlnCall& a, ioc_aln_stats* out_stats, int32_t n_segs,
+                                     const ioc_polish_seg* segs, const int32_t* seg_of_pair, const BlocksOut& o, ioc_pileup_col* out_cols, const IsoPolish& ip)
 {
-    const std::string who = "ioc_align_pairs_blocks_polish";
-    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
-    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
-    const IsoPolish ip{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off};
+    const int32_t n_pairs = a.n_pairs, max_iso = ip.max_iso;
+    const ioc_aln_pair* const pairs = a.pairs;
+    int64_t* const block_off = o.block_off, * const out_off = ip.call.off, * const iso_off = ip.iso_off;
+    ioc_read_blocks* const out_reads = o.reads;
+    ioc_blocks_seg* const out_seg = o.seg;
+    const int64_t iso_cap = ip.iso_cap;
     if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !ip.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
+    if (weighted && !c->aln_qual_set) return ioc_fail(c, IOC_ERR_ARG, who + ": no qualities are set for the current pool (ioc_align_set_pool_qual)");
     SinkPlan p;
     if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
     IOC_TRY(blocks_room_ok(c, who, o, p));
@@ -1129,7 +1216,7 @@ int ioc_align_pairs_blocks_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pai
     if (n_segs == 0) return a.run(c, nullptr);
     SinkRun r{c};
     PiledDev d;
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ true, d));
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ true, d, /*project_weights*/ weighted));
     IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o));  // (a_blocks is reserved here, after the walks; the records are the host's from here on)
     std::vector<int32_t> n_iso(size_t(n_segs), 0), group(size_t(n_pairs), -1);
     for (int32_t g = 0; g < n_segs; ++g) {
@@ -1139,18 +1226,57 @@ int ioc_align_pairs_blocks_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pai
     }
     for (int32_t i = 0; i < n_pairs; ++i) group[size_t(i)] = out_reads[i].group;  // (an isoform behind the cut is in no list: group_member_lists)
     const int64_t G = iso_off[n_segs];
-    if (G > 0) {
+    if (G > 0 && weighted) {
+        Planes dev{nullptr, nullptr, nullptr, d.base, d.slots};
+        dev.weights = d.weights;
+        IOC_TRY(groups_polish_weighted_device(r, ip.call, GroupTablesW{nullptr, nullptr, nullptr}, p, static_cast<const uint8_t*>(c->a_pool.p),
+                                              uint64_t(c->aln_offs.back()), seg_of_pair, group.data(), n_iso.data(), Planes{}, dev));
+    } else if (G > 0) {
         const GroupPolish gp{ip.call, nullptr, nullptr};
         IOC_TRY(groups_polish_device(r, gp, p, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), seg_of_pair, group.data(), n_iso.data(), Planes{},
                                      Planes{nullptr, nullptr, nullptr, d.base, d.slots}));
     }
     IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
-    if (getenv("IOC_TRACE"))
+    if (getenv("IOC_TRACE") && weighted)
+        fprintf(stderr, "[ioc]   aligner: blocks polish weighted: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, k_ops_project_weights %.3f ms, ms_blocks %.3f ms, k_group_pile_weighted %.3f ms, k_pile_call<weighted> %.3f ms%s\n",
+                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)G, (long long)out_off[G], double(r.t.copied) * 1e-6, r.t.ms_copy,
+                r.t.ms_pileup, r.t.ms_project, r.t.ms_project_ins, r.t.ms_project_weights, r.t.ms_blocks, r.t.ms_group_pile_weighted, r.t.ms_call,
+                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
+    else if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: blocks polish: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, ms_blocks %.3f ms, k_group_pile %.3f ms, k_pile_call %.3f ms%s\n",
                 n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)G, (long long)out_off[G], double(r.t.copied) * 1e-6, r.t.ms_copy,
                 r.t.ms_pileup, r.t.ms_project, r.t.ms_project_ins, r.t.ms_blocks, r.t.ms_group_pile, r.t.ms_call,
                 out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
     return IOC_OK;
+}
+
+int ioc_align_pairs_blocks_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                  int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                  const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                  int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                  int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t max_iso,
+                                  int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                                  int64_t iso_cap, int64_t* iso_off)
+{
+    return align_pairs_blocks_polish(c, "ioc_align_pairs_blocks_polish", false, AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio},
+                                     out_stats, n_segs, segs, seg_of_pair,
+                                     BlocksOut{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg},
+                                     out_cols, IsoPolish{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off});
+}
+
+// pile -> blocks -> weighted groups pile -> weighted call -> copy-out: ioc_align_pairs_blocks_polish with every isoform called by weight
+int ioc_align_pairs_blocks_polish_weighted(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                           int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                           const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt,
+                                           int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks,
+                                           int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols,
+                                           int32_t max_iso, int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                                           ioc_polish_stats* out_polish, int64_t iso_cap, int64_t* iso_off)
+{
+    return align_pairs_blocks_polish(c, "ioc_align_pairs_blocks_polish_weighted", true,
+                                     AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                                     BlocksOut{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg},
+                                     out_cols, IsoPolish{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off});
 }
 
 // upload -> split.  The split of segments whose sites and alleles the caller holds: both are uploaded, and the kernels run as

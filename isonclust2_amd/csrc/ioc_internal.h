@@ -215,11 +215,13 @@ struct ioc_ctx {
     DevBuf a_qual;      // ioc_align_set_pool_qual: one quality byte per byte of a_pool ...
     bool aln_qual_set = false;  // ... which it holds for the current pool
     DevBuf a_planes;  // ioc_align_pairs_alleles: every pair's projection, [base planes][ins planes] (k_ops_project)
-                      // and, for ioc_align_pairs_split_polish, [slot planes x 6] behind them (k_ops_project_ins)
+                      // and, for ioc_align_pairs_split_polish, [slot planes x 6] behind them (k_ops_project_ins) and, for
+                      // ioc_align_pairs_blocks_polish_weighted, [weight planes x 7] behind those (k_ops_project_weights)
     DevBuf a_split;   // ioc_alleles_split, ioc_align_pairs_split: member lists, bit planes, per-site and per-pair words (ioc_site_split.hip)
     DevBuf a_gpile;   // ioc_planes_polish, ioc_align_pairs_split_polish: the group-segments, their work items and tables (k_plane_pile) and,
                       // from host planes, the uploaded member lists and planes; ioc_planes_polish_groups, ioc_align_pairs_blocks_polish: the
-                      // same of k_group_pile, with every group's own member list
+                      // same of k_group_pile, with every group's own member list; ioc_planes_polish_groups_weighted,
+                      // ioc_align_pairs_blocks_polish_weighted: the same of k_group_pile_weighted, with the uploaded weight planes and gwcols / gwins
     DevBuf a_correct; // ioc_planes_correct, ioc_align_pairs_correct: segments, pairs, offsets, records and the corrected bytes (ioc_read_correct.hip) and,
                       // from host planes, the uploaded planes
     DevBuf a_blocks;  // ioc_planes_blocks, ioc_align_pairs_blocks: segments, pairs, member lists, bit planes, tables and records (ioc_read_blocks.hip) and,
@@ -428,6 +430,19 @@ struct IocGroupWork;  // (ioc_group_pile.h: 64 rows of a group-segment)
 hipError_t iock_group_pile(hipStream_t st, const IocGroupWork* work, uint32_t n_work, const IocPileSeg* gsegs, uint32_t n_gsegs, const uint32_t* gmem_off,
                            const uint32_t* gmembers, uint32_t n_members, uint32_t n_pairs, const uint64_t* plane, const uint8_t* base_planes,
                            const uint8_t* slot_planes, uint64_t plane_bytes, ioc_pileup_col* gcols, ioc_pileup_ins* gins, uint64_t n_rows);
+
+// ioc_group_pile_weighted.hip: the weight of every vote of the same strings into seven byte planes of the pairs' own
+// (ioc_host_ops_project_weights) — [wbase plane][wslot-0 planes] .. [wslot-5 planes], plane_bytes each, pair pid's bytes from
+// plane[pid] on of every one; quals: the pool's quality bytes (pool_bytes of them), q_len[pid]: the pair's query length —, and
+// the three tables of any number of groups of every segment added up from the planes and the weight planes
+// (ioc_host_planes_pile, ioc_host_planes_pile_weighted): the arguments of iock_group_pile, with gwcols / gwins beside gcols
+hipError_t iock_ops_project_weights(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room, const uint32_t* ord,
+                                    uint32_t cnt, const int64_t* row_base, const uint32_t* q_off, const uint32_t* q_len, const uint64_t* plane,
+                                    const uint8_t* quals, uint64_t pool_bytes, uint8_t* weight_planes, uint64_t plane_bytes);
+hipError_t iock_group_pile_weighted(hipStream_t st, const IocGroupWork* work, uint32_t n_work, const IocPileSeg* gsegs, uint32_t n_gsegs, const uint32_t* gmem_off,
+                                    const uint32_t* gmembers, uint32_t n_members, uint32_t n_pairs, const uint64_t* plane, const uint8_t* base_planes,
+                                    const uint8_t* slot_planes, const uint8_t* weight_planes, uint64_t plane_bytes, ioc_pileup_col* gcols,
+                                    ioc_pileup_col* gwcols, ioc_pileup_ins* gwins, uint64_t n_rows);
 
 // ioc_read_correct.hip: every pair's read corrected against the tables of its segment (ioc_host_read_correct per pair).  Everything
 // is a device pointer: pair i belongs to segment seg_of_pair[i] and has its rows from byte plane[i] on of the base plane and of the

@@ -51,7 +51,7 @@ struct Kind {
     SinkKind kind;
     bool stats;
     PileKind pile;
-    int project = 0;  // 1: the pile projects (two planes); 2: and what the pairs insert (project_ins: six more)
+    int project = 0;  // 1: the pile projects (two planes); 2: and what the pairs insert (project_ins: six more); 3: and the weights (project_weights: seven more)
 };
 const Kind KINDS[] = {{"bytes", SinkKind::bytes, false, PileKind::none},
                       {"stats", SinkKind::reduced, true, PileKind::none},
@@ -64,7 +64,9 @@ const Kind KINDS[] = {{"bytes", SinkKind::bytes, false, PileKind::none},
                       {"counts+project", SinkKind::reduced, false, PileKind::counts, 1},
                       {"counts+project+stats", SinkKind::reduced, true, PileKind::counts, 1},
                       {"counts+project_ins", SinkKind::reduced, false, PileKind::counts, 2},
-                      {"counts+project_ins+stats", SinkKind::reduced, true, PileKind::counts, 2}};
+                      {"counts+project_ins+stats", SinkKind::reduced, true, PileKind::counts, 2},
+                      {"counts+project_weights", SinkKind::reduced, false, PileKind::counts, 3},
+                      {"counts+project_weights+stats", SinkKind::reduced, true, PileKind::counts, 3}};
 
 // the caller's arrays of a call over P pairs, of exactly the sizes an entry point gives them (a read or write outside them is the
 // sanitizer's to find); the device tables are never dereferenced by the host: distinct addresses do
@@ -116,7 +118,8 @@ struct Caller {
             sink.pile.base_planes = t_planes, sink.pile.ins_planes = t_planes + 1;
             sink.pile.plane_bytes = PLANE_BYTES;
             sink.pile.plane = plane.data();
-            if (k.project == 2) sink.pile.project_ins = true, sink.pile.slot_planes = t_planes + 2;
+            if (k.project >= 2) sink.pile.project_ins = true, sink.pile.slot_planes = t_planes + 2;
+            if (k.project == 3) sink.pile.project_weights = true, sink.pile.weight_planes = t_planes + 3;
         }
     }
 };
@@ -157,11 +160,11 @@ void check_subset(const Kind& k, const std::vector<int32_t>& idx, const std::vec
             EXPECT(s.pile.piled[x] == piled_b[size_t(idx[x])]);
         }
     }
-    EXPECT(s.projects() == (k.project != 0) && s.projects_ins() == (k.project == 2));
+    EXPECT(s.projects() == (k.project != 0) && s.projects_ins() == (k.project >= 2) && s.projects_weights() == (k.project == 3));
     if (k.project) {
         EXPECT(sub.plane.size() == idx.size() && s.pile.plane == sub.plane.data() && s.pile.plane_bytes == Caller::PLANE_BYTES);
         EXPECT(s.pile.base_planes == c.sink.pile.base_planes && s.pile.ins_planes == c.sink.pile.ins_planes && s.pile.slot_planes == c.sink.pile.slot_planes);
-        EXPECT((s.pile.slot_planes != nullptr) == (k.project == 2));
+        EXPECT((s.pile.slot_planes != nullptr) == (k.project >= 2) && (s.pile.weight_planes != nullptr) == (k.project == 3));
         for (size_t x = 0; x < idx.size(); ++x) EXPECT(s.pile.plane[x] == c.plane[size_t(idx[x])]);
     } else {
         EXPECT(sub.plane.empty());
@@ -229,7 +232,8 @@ void check_empty(const Kind& k)
 void check_layout(const Kind& k)
 {
     g_what = k.name;
-    // (project_ins adds no column: the slot planes sit at the pair's `plane` offset like the two)
+    // (project_ins and project_weights add no column: their planes sit at the pair's `plane` offset like the two, and the q_len column a
+    // weight projection reads lies inside every projecting table, between q_off and plane)
     const size_t per_pair = k.kind == SinkKind::bytes ? 12 : k.project ? 40 : k.pile == PileKind::weighted ? 32 : k.pile != PileKind::none ? 28 : 16;
     for (size_t np : {size_t(0), size_t(1), size_t(3), size_t(5), size_t(1000)}) {
         Caller c(k);
@@ -244,6 +248,7 @@ void check_layout(const Kind& k)
         if (k.pile != PileKind::none) EXPECT(a.q_off + 4 * np <= a.bytes);
         if (k.pile == PileKind::weighted) EXPECT(a.q_len + 4 * np <= a.bytes);
         if (k.project) EXPECT(a.plane == 32 * np && a.plane % 8 == 0 && a.plane + 8 * np <= a.bytes);
+        if (k.project) EXPECT(a.q_len == 28 * np && a.q_len + 4 * np <= a.plane);
     }
 }
 
@@ -517,8 +522,8 @@ int main()
                                  : k.pile == PileKind::counts ? sizeof(ioc_pileup_col)
                                  : k.pile == PileKind::ins    ? sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins)
                                                               : 2 * sizeof(ioc_pileup_col) + sizeof(ioc_pileup_ins);
-        // the planes: a byte per row and pair each, two of them, and six more with project_ins
-        const uint64_t planes = k.project == 2 ? 2 + IOC_PILE_INS_SLOTS : k.project == 1 ? 2 : 0;
+        // the planes: a byte per row and pair each, two of them, six more with project_ins and seven more with project_weights
+        const uint64_t planes = k.project == 3 ? 3 + 2 * IOC_PILE_INS_SLOTS : k.project == 2 ? 2 + IOC_PILE_INS_SLOTS : k.project == 1 ? 2 : 0;
         EXPECT(c.sink.pile_bytes() == 700 * per_row + planes * uint64_t(Caller::PLANE_BYTES));
         EXPECT(c.sink.reduced() == (k.kind == SinkKind::reduced) && c.sink.has_stats() == k.stats && c.sink.has_pile() == (k.pile != PileKind::none));
         check_subset(k, {}, {}, {});
