@@ -1212,6 +1212,102 @@ int ioc_align_pairs_blocks_polish_weighted(ioc_ctx* ctx, int32_t n_pairs, const 
                                            int32_t max_iso, int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap,
                                            int64_t* out_off, ioc_polish_stats* out_polish, int64_t iso_cap, int64_t* iso_off);
 
+/* ---- Insertion sites: the exons a cluster's reads carry and its representative lacks, and isoforms over blocks and sites ----
+ * A block is a stretch of the representative that some reads skip; an exon the representative lacks is a long insertion, and the
+ * slot planes hold six inserted bases a run.  The length plane keeps how many there were.
+ *
+ * The length plane of one read: ilen[0 .. rlen], r the reference bases consumed as in ioc_host_ops_project.  A maximal run of n 'I'
+ * bytes in front of row r sets ilen[r] = min(n, 255); free-end 'i' bytes count for nothing; every other entry is 0.  (Two 'I' runs
+ * are separated by a byte that consumes a reference base, so a row receives one run.)  IOC_ERR_ARG, with nothing written, for a
+ * negative length, a NULL pointer that is needed, a byte outside "=XIDid" and a string that does not consume rlen reference bases. */
+int ioc_host_ops_project_ilen(const char* ops, int64_t len, int32_t rlen, uint8_t* ilen);
+/* One segment is a reference of rlen rows with n_reads reads, each read its base plane and its length plane, rlen + 1 bytes each.
+ * Junction p lies in front of row p.  A rule {min_ins in 1 .. 255, slack in 0 .. 32, min_depth >= 1, min_alt >= 1, min_pct in 1 ..
+ * 50, max_sites in 1 .. 32}.  All integers.
+ *  1. Read i spans junction p, 1 <= p <= rlen - 1, iff its base plane covers rows p - 1 and p (a byte of 0 .. 5).  Junctions 0 and
+ *     rlen are spanned by nobody.
+ *  2. The windowed sum W_i(p): the sum of ilen_i[q] over q = max(p - slack, 0) .. min(p + slack, rlen), every q, spanned or not.
+ *     (One 'I' run of min_ins bases is NOT the rule: at 8 % errors the aligner breaks a 40-base exon into runs of 19 + 14 a few
+ *     rows apart, as a stray match cuts a long gap.)
+ *  3. Near: N_i(p) = read i spans p and W_i(p) >= min_ins.
+ *  4. The row table: S(p) the reads that span p, in(p) the sum of N_i(p); junction p is variable iff S(p) >= min_depth, in(p) >=
+ *     need(S(p)) and S(p) - in(p) >= need(S(p)), need as in ioc_host_pileup_sites: the test of a block's rows.
+ *  5. A site [first, end): a maximal run of variable junctions, of any length from 1 (the window widens a site to about 2 slack + 1
+ *     junctions already).  In ascending order; the first max_sites are kept, n_found says how many there were.
+ *  6. A read's state at a kept site: IOC_INS_NONE unless it spans every junction of the site, else IOC_INS_CARRY if N_i(p) holds
+ *     for some p of the site, else IOC_INS_LACK.
+ *  7. The site record: the three state counts, and len_min / len_max, the smallest and the largest over the carriers of each
+ *     carrier's largest W_i(p) over the site's junctions (0 without carriers).
+ *  8. key = the sum over the kept sites b of state(b) << (2 b); the mask has both bits of every site whose state is not NONE.
+ *  9. The isoforms are step 6 of ioc_host_planes_blocks over PAIRS of words (pre_key, key): pre_key[i], pre_mask[i] per read and
+ *     pre_full per segment are meant to be the block stage's key, its mask and the mask of a complete read of its blocks; with
+ *     pre_key NULL all three are 0 and the stage stands on its own.  A read is complete iff its mask is that of all kept sites AND
+ *     pre_mask[i] == pre_full.  A pair carried by at least min_alt complete reads is supported; the supported pairs are the
+ *     isoforms 0 .. n_groups - 1 in ascending unsigned order, pre_key major, key minor.  Direct, rare, assigned and ambiguous as
+ *     there: agreement is tested under both masks, and "a state that is not NONE" means that either mask is not 0.
+ * 10. The read record: key, group, how (the COMBINED isoform), n_near the junctions with N_i, ins_bases the sum of ilen_i over the
+ *     junctions the read spans.
+ * What stays out: the sequence of an inserted exon (run the block stage with a carrier as the representative: there it is a
+ * block), alternative ends, more than 32 sites, runs beyond 255 bases (they count as 255).  20 bases and 8 junctions are choices
+ * made on simulated reads, not measured on real data. */
+#define IOC_INS_LACK 0
+#define IOC_INS_CARRY 1
+#define IOC_INS_NONE 3
+#define IOC_INSERTS_MAX 32
+#define IOC_INS_SLACK_MAX 32
+typedef struct {
+    uint32_t span, in_ins;        /* S(p) and in(p); rlen + 1 rows per segment, rows 0 and rlen zero */
+} ioc_insert_row;                 /* 8 bytes */
+typedef struct {
+    int32_t first, end;
+    uint32_t n_carry, n_lack, n_none;  /* over the segment's reads */
+    uint32_t len_min, len_max;
+    uint32_t reserved;
+} ioc_pile_insert;                /* 32 bytes */
+typedef struct {
+    uint64_t key;
+    int32_t group, how;
+    int32_t n_near, ins_bases;
+    uint32_t reserved[2];
+} ioc_read_inserts;               /* 32 bytes */
+typedef struct {
+    int32_t n_sites, n_found, n_groups, n_reads, n_direct, n_assigned, n_rare, n_ambiguous;
+} ioc_inserts_seg;                /* 32 bytes */
+/* The definition: one segment, both kinds of plane read-major (n_reads x (rlen + 1) bytes), the plain loops above.  out_rows (may
+ * be NULL): rlen + 1 rows; out_sites: room for min(max_sites, max(rlen - 1, 0)) records, of which the first out_seg->n_sites are
+ * written; out_reads: n_reads records.  pre_key and pre_mask: both or neither.  IOC_ERR_ARG, with nothing written, for a rule
+ * outside its ranges, a negative count or length and a NULL pointer that is needed. */
+int ioc_host_planes_inserts(const uint8_t* base, const uint8_t* ilen, int32_t n_reads, int32_t rlen, int32_t min_ins, int32_t slack,
+                            int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites, const uint64_t* pre_key,
+                            const uint64_t* pre_mask, uint64_t pre_full, ioc_insert_row* out_rows, ioc_pile_insert* out_sites,
+                            ioc_read_inserts* out_reads, ioc_inserts_seg* out_seg);
+/* Many segments at once on the device, from host planes laid out as for ioc_planes_blocks; pre_key / pre_mask per pair, pre_full per
+ * segment, all three or none.  The kernels of ioc_read_inserts.hip turn every pair of planes into two bit planes (spans, near; the
+ * windowed sum by a wave prefix sum) and work on those as the block kernels do; no atomics.  out_rows (may be NULL), out_sites packed
+ * with site_off (n_segs + 1 entries), out_reads per pair, out_seg per segment, each as ioc_host_planes_inserts defines it.
+ * IOC_ERR_ARG, with nothing written, for what the definition refuses, seg_of_pair outside the segments and a NULL pointer that is
+ * needed; IOC_ERR_CAPACITY, with nothing written, for sites_cap below the sum over the segments of min(max_sites, max(rlen[g] - 1, 0)). */
+int ioc_planes_inserts(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const uint8_t* base,
+                       const uint8_t* ilen, int32_t min_ins, int32_t slack, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                       int32_t max_sites, const uint64_t* pre_key, const uint64_t* pre_mask, const uint64_t* pre_full,
+                       ioc_insert_row* out_rows, ioc_pile_insert* out_sites, int64_t sites_cap, int64_t* site_off,
+                       ioc_read_inserts* out_reads, ioc_inserts_seg* out_seg);
+/* ioc_align_pairs_blocks with the length plane projected beside the base plane (k_ops_project_ilen: 3 bytes per row and pair in
+ * all, which count against the checkpoint arena's budget; a call of ioc_align_pairs_blocks reserves what it always did) and, behind
+ * the block kernels, the insert kernels with the block stage's keys and masks as pre_*, where they lie on the device.  Everything
+ * ioc_align_pairs_blocks returns comes back unchanged, byte for byte; added are the rows (may be NULL), sites, site_off, read and
+ * segment records of ioc_planes_inserts, group / how of the read records being the combined isoform.  The block search and the
+ * site search share min_depth, min_alt and min_pct.  Every pair is aligned, piled and projected exactly once; the stage's memory is
+ * reserved after the walks.  The refusals of both calls; nothing is written. */
+int ioc_align_pairs_blocks_inserts(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                   int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                   int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                                   int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                                   ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                                   ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins, int32_t slack, int32_t max_sites,
+                                   ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap, int64_t* site_off,
+                                   ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg);
+
 #ifdef __cplusplus
 }
 #endif

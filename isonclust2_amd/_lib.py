@@ -119,6 +119,8 @@ SPLIT_NONE = 255                # IOC_SPLIT_NONE
 BLOCK_KEEP, BLOCK_SKIP, BLOCK_PART, BLOCK_NONE = 0, 1, 2, 3    # IOC_BLOCK_*
 ISO_DIRECT, ISO_ASSIGNED, ISO_RARE, ISO_AMBIGUOUS = 0, 1, 2, 3  # IOC_ISO_*
 BLOCKS_MAX = 32                 # IOC_BLOCKS_MAX
+INS_LACK, INS_CARRY, INS_NONE = 0, 1, 3  # IOC_INS_*
+INSERTS_MAX, INS_SLACK_MAX = 32, 32      # IOC_INSERTS_MAX, IOC_INS_SLACK_MAX
 
 
 class BlockRow(C.Structure):  # ioc_block_row (8 bytes)
@@ -135,6 +137,22 @@ class ReadBlocks(C.Structure):  # ioc_read_blocks (32 bytes)
 
 class BlocksSeg(C.Structure):  # ioc_blocks_seg (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("n_blocks", "n_found", "n_groups", "n_reads", "n_direct", "n_assigned", "n_rare", "n_ambiguous")]
+
+
+class InsertRow(C.Structure):  # ioc_insert_row (8 bytes)
+    _fields_ = [("span", C.c_uint32), ("in_ins", C.c_uint32)]
+
+
+class PileInsert(C.Structure):  # ioc_pile_insert (32 bytes)
+    _fields_ = [("first", C.c_int32), ("end", C.c_int32)] + [(n, C.c_uint32) for n in ("n_carry", "n_lack", "n_none", "len_min", "len_max", "reserved")]
+
+
+class ReadInserts(C.Structure):  # ioc_read_inserts (32 bytes)
+    _fields_ = [("key", C.c_uint64)] + [(n, C.c_int32) for n in ("group", "how", "n_near", "ins_bases")] + [("reserved", C.c_uint32 * 2)]
+
+
+class InsertsSeg(C.Structure):  # ioc_inserts_seg (32 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("n_sites", "n_found", "n_groups", "n_reads", "n_direct", "n_assigned", "n_rare", "n_ambiguous")]
 
 
 class SplitSeg(C.Structure):  # ioc_split_seg (32 bytes)
@@ -191,6 +209,7 @@ SYMBOLS = [
     "ioc_host_planes_blocks", "ioc_planes_blocks", "ioc_align_pairs_blocks",
     "ioc_planes_polish_groups", "ioc_align_pairs_blocks_polish",
     "ioc_host_ops_project_weights", "ioc_host_planes_pile_weighted", "ioc_planes_polish_groups_weighted", "ioc_align_pairs_blocks_polish_weighted",
+    "ioc_host_ops_project_ilen", "ioc_host_planes_inserts", "ioc_planes_inserts", "ioc_align_pairs_blocks_inserts",
 ]
 
 _lib = None
@@ -353,6 +372,12 @@ def load():
     L.ioc_planes_polish_groups_weighted.argtypes = [vp, i32, pi32, C.c_char_p, pi64, pi32, i32, pi32, pi32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i32, C.c_void_p,
                                                     C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_blocks_polish_weighted.argtypes = L.ioc_align_pairs_blocks_polish.argtypes
+    L.ioc_host_ops_project_ilen.argtypes = [C.c_char_p, i64, i32, C.c_void_p]
+    L.ioc_host_planes_inserts.argtypes = [C.c_void_p, C.c_void_p, i32, i32, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_planes_inserts.argtypes = [vp, i32, pi32, i32, pi32, C.c_void_p, C.c_void_p, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
+    L.ioc_align_pairs_blocks_inserts.argtypes = L.ioc_align_pairs_blocks.argtypes + [i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

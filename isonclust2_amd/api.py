@@ -367,6 +367,75 @@ def planes_blocks(base, rows=True, **rule):
     return out
 
 
+def ops_project_ilen(ops, rlen):
+    """ioc_host_ops_project_ilen: how many bases one read inserts in front of every row of its reference — a uint8 array of rlen + 1
+    bytes: ilen[r] = min(n, 255) for the run of n 'I' in front of row r, 0 elsewhere; free-end 'i' bytes count for nothing.
+    ValueError for a byte outside "=XIDid" and for a string that does not consume rlen reference bases."""
+    ilen = np.full(int(rlen) + 1, 0xEE, np.uint8)
+    rc = _lib.load().ioc_host_ops_project_ilen(bytes(ops), len(ops), int(rlen), ilen.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_project_ilen failed ({rc})")
+    return ilen
+
+
+# ioc_insert_row, ioc_pile_insert, ioc_read_inserts and ioc_inserts_seg as numpy records
+INSERT_ROW_DTYPE = np.dtype([("span", np.uint32), ("in_ins", np.uint32)])
+PILE_INSERT_DTYPE = np.dtype([("first", np.int32), ("end", np.int32)] + [(n, np.uint32) for n in ("n_carry", "n_lack", "n_none", "len_min", "len_max", "reserved")])
+READ_INSERTS_DTYPE = np.dtype([("key", np.uint64)] + [(n, np.int32) for n in ("group", "how", "n_near", "ins_bases")] + [("reserved", np.uint32, 2)])
+INSERTS_SEG_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.InsertsSeg._fields_])
+INS_LACK, INS_CARRY, INS_NONE = _lib.INS_LACK, _lib.INS_CARRY, _lib.INS_NONE
+# (20 bases within 8 junctions: choices made on simulated reads, not measured on real data)
+INSERTS_RULE = dict(min_ins=20, slack=8, min_depth=3, min_alt=3, min_pct=25, max_sites=32)
+
+
+def planes_inserts_bound(rlen, max_sites):
+    """What a search for insertion sites of a reference of rlen bases may keep at most: min(max_sites, max(rlen - 1, 0))."""
+    return min(int(max_sites), max(int(rlen) - 1, 0))
+
+
+def _inserts_rule(rule):
+    unknown = set(rule) - set(INSERTS_RULE)
+    if unknown:
+        raise TypeError(f"unknown rule parameters: {sorted(unknown)}")
+    return [int({**INSERTS_RULE, **rule}[n]) for n in INSERTS_RULE]
+
+
+def planes_inserts(base, ilen, pre_key=None, pre_mask=None, pre_full=0, rows=True, **rule):
+    """ioc_host_planes_inserts: the insertion sites of one segment and every read's combined isoform — `base` and `ilen` the reads'
+    base planes and length planes as ops_project and ops_project_ilen give them, n_reads x (rlen + 1) bytes each; the rule as
+    keywords (INSERTS_RULE has the defaults).  A read spans a junction where it covers the rows on both sides, and is near an
+    insertion there where its inserted bases within `slack` junctions sum to min_ins; a junction is variable where enough spanning
+    reads are near one and enough are not; a site is a run of variable junctions; a read's state at a site is carry, lack or none.
+    pre_key / pre_mask (per read) and pre_full: the block stage's keys, masks and complete mask, with which the isoforms are counted
+    over blocks and sites together; without them the sites alone.  Returns a dict: `rows` (INSERT_ROW_DTYPE, rlen + 1 rows; with
+    rows=True), `sites` (PILE_INSERT_DTYPE, the kept ones), `reads` (READ_INSERTS_DTYPE per read), `seg` (an INSERTS_SEG_DTYPE
+    record).  IocError for a rule outside its ranges."""
+    base, ilen = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(ilen, np.uint8)
+    if base.ndim != 2 or base.shape[1] < 1 or ilen.shape != base.shape:
+        raise ValueError("base and ilen must hold n_reads x (rlen + 1) bytes each")
+    n, rlen = base.shape[0], base.shape[1] - 1
+    if (pre_key is None) != (pre_mask is None):
+        raise ValueError("pre_key and pre_mask: both or neither")
+    pk = pm = None
+    if pre_key is not None:
+        pk, pm = np.ascontiguousarray(pre_key, np.uint64), np.ascontiguousarray(pre_mask, np.uint64)
+        if pk.shape != (n,) or pm.shape != (n,):
+            raise ValueError("pre_key and pre_mask must hold one word per read")
+    r = _inserts_rule(rule)
+    tab = np.zeros(rlen + 1, INSERT_ROW_DTYPE)
+    sites, reads, seg = np.zeros(max(planes_inserts_bound(rlen, max(r[5], 0)), 1), PILE_INSERT_DTYPE), np.zeros(n, READ_INSERTS_DTYPE), np.zeros(1, INSERTS_SEG_DTYPE)
+    rc = _lib.load().ioc_host_planes_inserts(base.ctypes.data if n else None, ilen.ctypes.data if n else None, n, rlen, *r,
+                                             pk.ctypes.data if pk is not None and n else None, pm.ctypes.data if pm is not None and n else None,
+                                             int(pre_full) if pk is not None else 0, tab.ctypes.data if rows else None, sites.ctypes.data,
+                                             reads.ctypes.data if n else None, seg.ctypes.data)
+    if rc < 0:
+        raise IocError(int(rc), "ioc_host_planes_inserts")
+    out = {"sites": sites[:int(seg[0]["n_sites"])], "reads": reads, "seg": seg[0]}
+    if rows:
+        out["rows"] = tab
+    return out
+
+
 def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
     """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
     returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
@@ -1014,6 +1083,90 @@ class Context:
                                            *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap, _p(boff, C.c_int64),
                                            reads.ctypes.data if n else None, seg.ctypes.data if ns else None))
         return self._blocks_dict(ns, [int(m) for m in rl], n, tab, blocks, boff, reads, seg)
+
+    @staticmethod
+    def _inserts_out(ns, rlen, rule, rows, cap):
+        """the output arrays of a search for insertion sites over segments of these lengths"""
+        bound = sum(planes_inserts_bound(m, rule[5]) for m in rlen)
+        cap = bound if cap is None else int(cap)
+        tab = np.zeros(int(sum(rlen)) + ns, INSERT_ROW_DTYPE) if rows else None
+        sites, soff, seg = np.zeros(max(cap, 1), PILE_INSERT_DTYPE), np.zeros(ns + 1, np.int64), np.zeros(ns, INSERTS_SEG_DTYPE)
+        return (tab, sites, soff, seg), cap
+
+    def _inserts_dict(self, ns, rlen, tab, sites, soff, reads, seg):
+        out = {"sites": [sites[soff[g]:soff[g + 1]] for g in range(ns)], "site_off": soff, "reads": reads, "seg": seg}
+        if tab is not None:
+            r0 = np.concatenate([self._row0(rlen), [len(tab)]]).astype(np.int64) if ns else np.zeros(1, np.int64)
+            out.update(rows=[tab[r0[g]:r0[g + 1]] for g in range(ns)])
+        return out
+
+    def planes_inserts(self, rlen, seg_of_pair, base, ilen, pre_key=None, pre_mask=None, pre_full=None, rows=True, cap=None, **rule):
+        """ioc_planes_inserts: the insertion sites of many segments and every read's combined isoform on the device, from host
+        planes — `rlen` the segments' lengths, seg_of_pair per pair, `base` / `ilen` a list per pair of what ops_project /
+        ops_project_ilen give for that pair; pre_key / pre_mask per pair and pre_full per segment, all three or none; the rule as
+        keywords.  Returns a dict: `sites` (a PILE_INSERT_DTYPE array per segment), `site_off`, `reads` (READ_INSERTS_DTYPE per pair),
+        `seg` (INSERTS_SEG_DTYPE per segment) and, with rows=True, `rows` (an INSERT_ROW_DTYPE array per segment); each segment as
+        api.planes_inserts defines it."""
+        ns, n = len(rlen), len(base)
+        rl = np.ascontiguousarray(rlen, np.int32)
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,) or len(ilen) != n:
+            raise ValueError("seg_of_pair, base and ilen must hold one entry per pair")
+        want = [int(rl[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (want[i],) or np.shape(ilen[i]) != (want[i],):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        fl = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in ilen]))
+        given = [x is not None for x in (pre_key, pre_mask, pre_full)]
+        if any(given) and not all(given):
+            raise ValueError("pre_key, pre_mask and pre_full: all three or none")
+        pk = pm = pf = None
+        if all(given):
+            pk, pm, pf = (np.ascontiguousarray(x, np.uint64) for x in (pre_key, pre_mask, pre_full))
+            if pk.shape != (n,) or pm.shape != (n,) or pf.shape != (ns,):
+                raise ValueError("pre_key and pre_mask must hold one word per pair, pre_full one per segment")
+            pk, pm, pf = (np.concatenate([x, np.zeros(1, np.uint64)]) for x in (pk, pm, pf))  # (never an empty array's pointer)
+        r = _inserts_rule(rule)
+        (tab, sites, soff, seg), cap = self._inserts_out(ns, [max(int(m), 0) for m in rl], r, rows, cap)
+        reads = np.zeros(n, READ_INSERTS_DTYPE)
+        self._chk(self.L.ioc_planes_inserts(self.h, ns, _p(rl, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, fb.ctypes.data if len(fb) else None,
+                                            fl.ctypes.data if len(fl) else None, *r, *(x.ctypes.data if x is not None else None for x in (pk, pm, pf)),
+                                            tab.ctypes.data if rows and len(tab) else None, sites.ctypes.data, cap, _p(soff, C.c_int64),
+                                            reads.ctypes.data if n else None, seg.ctypes.data if ns else None))
+        return self._inserts_dict(ns, [int(m) for m in rl], tab, sites, soff, reads, seg)
+
+    def align_pairs_blocks_inserts(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, sites_cap=None, match=2, mismatch=-2,
+                                   gap_extend=1, min_ins=INSERTS_RULE["min_ins"], slack=INSERTS_RULE["slack"], max_sites=INSERTS_RULE["max_sites"], **rule):
+        """ioc_align_pairs_blocks_inserts: align_pairs_blocks with every pair's length plane projected beside its base plane and the
+        search for insertion sites behind the block search, on the device, every pair aligned once — the block rule as keywords,
+        min_ins / slack / max_sites for the sites (min_depth, min_alt and min_pct are shared).  Returns align_pairs_blocks' dict,
+        byte for byte, and under `inserts` what Context.planes_inserts returns, group / how of its reads being the isoform over blocks
+        and sites together."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        r = _blocks_rule(rule)
+        ir = [int(min_ins), int(slack), r[1], r[2], r[3], int(max_sites)]
+        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
+        (itab, sites, soff, iseg), sites_cap = self._inserts_out(ns, rlen, ir, rows, sites_cap)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        reads, ireads = np.zeros(n, READ_BLOCKS_DTYPE), np.zeros(n, READ_INSERTS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        self._chk(self.L.ioc_align_pairs_blocks_inserts(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+                                                        _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
+                                                        _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
+                                                        cols.ctypes.data if tables and n_rows else None, ir[0], ir[1], ir[5],
+                                                        itab.ctypes.data if rows and len(itab) else None, sites.ctypes.data, sites_cap, _p(soff, C.c_int64),
+                                                        ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None))
+        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
+               "inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg)}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out.update(cols=cols, row0=self._row0(rlen))
+        return out
 
     def align_pairs_blocks(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, match=2, mismatch=-2, gap_extend=1, **rule):
         """ioc_align_pairs_blocks: align_pairs, the table of counts, every pair's base plane and the block search over the planes, all

@@ -35,6 +35,7 @@ struct DumpOptions {
     // --isoforms-polish: cluster_isoforms.fq, the consensus of every isoform of every cluster that has a block
     // --isoforms-polish-min-depth / --isoforms-polish-max: positions covered by fewer reads of the isoform keep the representative's base / the isoforms called per cluster
     // --isoforms-polish-weighted: every isoform is called by weight, every read voting with its base qualities
+    // --isoforms-inserts: cluster_inserts.tsv, read_inserts.tsv, the exons a cluster's reads carry and its representative lacks, and isoforms over blocks and sites
     ReportOpts reports;
 };
 
@@ -58,7 +59,8 @@ void print_dump_help()
          << "                    [--correct [--correct-min-depth N] [--correct-min-alt N] [--correct-min-pct P] [--correct-max-run N]]" << endl
          << "                    [--isoforms [--isoforms-min-gap N] [--isoforms-min-depth N] [--isoforms-min-alt N] [--isoforms-min-pct P]" << endl
          << "                     [--isoforms-min-block N] [--isoforms-max N]" << endl
-         << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N] [--isoforms-polish-weighted]]] final.cer" << endl
+         << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N] [--isoforms-polish-weighted]]" << endl
+         << "                     [--isoforms-inserts [--isoforms-min-ins N] [--isoforms-ins-slack N] [--isoforms-ins-max N]]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -129,7 +131,20 @@ void print_dump_help()
          << "                 write before its isoforms are known — that was not measured on real data)" << endl
          << "  --isoforms-polish-weighted      with --isoforms-polish: call every isoform by weight — every read votes with the base qualities of" << endl
          << "                 its line (Phred, 1 .. 93), a deletion with the smaller of its neighbours'; the depth gates stay counts of reads." << endl
-         << "                 The same records of cluster_isoforms.fq, names and order; still no read is aligned again" << endl;
+         << "                 The same records of cluster_isoforms.fq, names and order; still no read is aligned again" << endl
+         << "  --isoforms-inserts      with --isoforms: also write outdir/cluster_inserts.tsv and read_inserts.tsv, from the same alignments: the" << endl
+         << "                 places where some reads carry an exon the representative lacks (insertion sites: the first junction and one" << endl
+         << "                 past the last, how many reads carry an insertion there, lack it or do not reach across, and the shortest and" << endl
+         << "                 longest insertion of the carriers; a '#' line where a cluster's list was cut), and per read its signature at the" << endl
+         << "                 sites ('=' lack, '+' carry, '.' not across), its isoform counted over blocks AND sites together (or '.') and how" << endl
+         << "                 it got it, as in read_isoforms.tsv.  The three files of --isoforms stay what they are.  The sequence of an" << endl
+         << "                 inserted exon is not written: with a carrier as the representative the exon is a block.  Not offered together" << endl
+         << "                 with --isoforms-polish: the isoforms' consensus is called over the blocks alone" << endl
+         << "  --isoforms-min-ins N    a read carries an insertion at a junction where the bases it inserts within --isoforms-ins-slack junctions" << endl
+         << "                 sum to at least N, 1 .. 255 (default 20: a choice that was not measured on real data)" << endl
+         << "  --isoforms-ins-slack N  ... the junctions on either side that count, 0 .. 32 (default 8: at 8 % errors the aligner breaks a 40-base" << endl
+         << "                 exon into two runs a few positions apart; a choice that was not measured on real data)" << endl
+         << "  --isoforms-ins-max N    keep the first N insertion sites of a cluster, 1 .. 32 (default 32)" << endl;
 }
 
 DumpOptions parse_dump_options(int argc, char** argv)
@@ -152,7 +167,9 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms-min-pct", required_argument, 0, 1025}, {"isoforms-min-block", required_argument, 0, 1026},
                                        {"isoforms-max", required_argument, 0, 1027}, {"isoforms-polish", no_argument, 0, 1028},
                                        {"isoforms-polish-min-depth", required_argument, 0, 1029}, {"isoforms-polish-max", required_argument, 0, 1030},
-                                       {"isoforms-polish-weighted", no_argument, 0, 1031}, {0, 0, 0, 0}};
+                                       {"isoforms-polish-weighted", no_argument, 0, 1031}, {"isoforms-inserts", no_argument, 0, 1032},
+                                       {"isoforms-min-ins", required_argument, 0, 1033}, {"isoforms-ins-slack", required_argument, 0, 1034},
+                                       {"isoforms-ins-max", required_argument, 0, 1035}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false, iso_polish = false;
@@ -195,6 +212,10 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1029: iso_polish_min_depth = number("--isoforms-polish-min-depth", optarg, 1, INT32_MAX); break;
             case 1030: r.isoforms.polish_max = number("--isoforms-polish-max", optarg, 1, INT32_MAX); break;
             case 1031: r.isoforms.polish_weighted = true; break;
+            case 1032: r.isoforms.inserts = true; break;
+            case 1033: r.isoforms.min_ins = number("--isoforms-min-ins", optarg, 1, 255); break;
+            case 1034: r.isoforms.ins_slack = number("--isoforms-ins-slack", optarg, 0, 32); break;
+            case 1035: r.isoforms.ins_max = number("--isoforms-ins-max", optarg, 1, 32); break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -208,6 +229,8 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (iso_polish && !r.isoforms.on) die("--isoforms-polish asks for --isoforms!");
     if (r.isoforms.polish_weighted && !iso_polish) die("--isoforms-polish-weighted asks for --isoforms-polish!");
     if (iso_polish) r.isoforms.polish_min_depth = iso_polish_min_depth;
+    if (r.isoforms.inserts && !r.isoforms.on) die("--isoforms-inserts asks for --isoforms!");
+    if (r.isoforms.inserts && iso_polish) die("--isoforms-inserts is not offered together with --isoforms-polish!");
     if (polish) r.polish_min_depth = polish_min_depth;
     if (d.index.empty()) die("Specifying the sorted read index is mandatory!");
     d.batch = argv[optind];
@@ -384,7 +407,8 @@ int main_dump(int argc, char** argv)
                              (reports.polish() ? "cluster_polished.fq, " : "") + (reports.sites.on ? "cluster_sites.tsv, read_alleles.tsv, " : "") +
                              (reports.split.on ? "cluster_split.tsv, read_split.tsv, " : "") + (reports.group_polish() ? "cluster_split_polished.fq, " : "") +
                              (reports.correct.on ? "corrected_reads.fq, " : "") +
-                             (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "") + (reports.iso_polish() ? "cluster_isoforms.fq, " : "");
+                             (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "") + (reports.iso_polish() ? "cluster_isoforms.fq, " : "") +
+                             (reports.isoforms.on && reports.isoforms.inserts ? "cluster_inserts.tsv, read_inserts.tsv, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

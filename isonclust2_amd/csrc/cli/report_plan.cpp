@@ -125,6 +125,13 @@ int64_t blocks_capacity(const ReportGroup& g, int max_blocks)
     return cap;
 }
 
+int64_t inserts_capacity(const ReportGroup& g, int max_sites)
+{
+    int64_t cap = 0;
+    for (const ioc_polish_seg& sg : g.segs) cap += std::min<int64_t>(max_sites, std::max<int64_t>(ref_len(g, sg) - 1, 0));
+    return cap;
+}
+
 IsoCapacity iso_polish_capacity(const ReportGroup& g, int max_iso)
 {
     IsoCapacity cap;
@@ -232,6 +239,32 @@ string cluster_isoform_records(size_t cluster, const ioc_blocks_seg& z, const st
         text += polish_record("cluster_" + std::to_string(cluster) + "/iso" + std::to_string(h) + " key=" + blocks_signature(key[h], z.n_blocks), mine[h], stats[h], "",
                               seq + off[h], qual + off[h], size_t(off[h + 1] - off[h]));
     return text;
+}
+
+string inserts_signature(uint64_t key, int32_t n_sites)
+{
+    string text;
+    for (int32_t b = 0; b < n_sites && b < IOC_INSERTS_MAX; ++b) text += "=+?."[(key >> (2 * b)) & 3u];
+    return text.empty() ? "*" : text;
+}
+
+string cluster_inserts_rows(size_t cluster, const ioc_inserts_seg& z, const ioc_pile_insert* sites)
+{
+    const string id = std::to_string(cluster);
+    string text;
+    if (z.n_found > z.n_sites) text += "# cluster " + id + ": kept " + std::to_string(z.n_sites) + " of " + std::to_string(z.n_found) + " sites\n";
+    for (int32_t b = 0; b < z.n_sites; ++b) {
+        const ioc_pile_insert& k = sites[b];
+        text += id + '\t' + std::to_string(k.first) + '\t' + std::to_string(k.end) + '\t' + std::to_string(k.n_carry) + '\t' + std::to_string(k.n_lack) + '\t' +
+                std::to_string(k.n_none) + '\t' + std::to_string(k.len_min) + '\t' + std::to_string(k.len_max) + '\n';
+    }
+    return text;
+}
+
+string read_insert_columns(const ioc_read_inserts& r, int32_t n_sites)
+{
+    const char* const how = r.how == IOC_ISO_DIRECT ? "direct" : r.how == IOC_ISO_ASSIGNED ? "assigned" : r.how == IOC_ISO_RARE ? "rare" : "ambiguous";
+    return inserts_signature(r.key, n_sites) + '\t' + (r.group < 0 ? string(".") : std::to_string(r.group)) + '\t' + how;
 }
 
 string read_isoform_columns(const ioc_read_blocks& r, int32_t n_blocks)

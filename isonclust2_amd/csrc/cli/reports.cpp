@@ -72,6 +72,13 @@
 // no read aligned a second time): every read votes with the base qualities of its line as --polish-weighted has them.  Where
 // an isoform has 5 to 12 reads this is what keeps three low-quality reads from outvoting two good ones.  The other report files
 // are what they are without the option.
+//
+// dump --isoforms --isoforms-inserts: <outdir>/cluster_inserts.tsv and read_inserts.tsv (ioc_align_pairs_blocks_inserts: the call of
+// --isoforms with every read's length plane kept beside its base plane and the search for insertion sites behind the block search,
+// no read aligned a second time): cluster_inserts.tsv: the places where some reads of a cluster carry an exon its representative
+// lacks, with how many reads carry it, lack it or do not reach across and the carriers' shortest and longest insertion;
+// read_inserts.tsv: one row per row read_stats.tsv has, in that order, with the read's signature at the sites and its isoform over
+// blocks and sites together.  The three files of --isoforms and the other report files are what they are without the option.
 #include "reports.hpp"
 
 #include <cstdio>
@@ -121,6 +128,10 @@ struct GroupResult {
     std::vector<ioc_read_blocks> read_blocks;
     PolishedSet iso_polished;       // (--isoforms-polish) per called isoform: segment g's at [iso_off[g], iso_off[g + 1])
     std::vector<int64_t> iso_off;
+    std::vector<ioc_pile_insert> inserts;  // (--isoforms-inserts) segment g's kept sites at [insert_off[g], insert_off[g + 1]), its record, and pair x's
+    std::vector<int64_t> insert_off;
+    std::vector<ioc_inserts_seg> inserts_seg;
+    std::vector<ioc_read_inserts> read_inserts;
 };
 
 // a row of the three per-read tables
@@ -138,6 +149,8 @@ struct RowResult {
     string corrected;
     ioc_read_blocks iso{};           // (--isoforms) the read's record, and how many blocks its cluster kept
     int32_t iso_blocks = 0;
+    ioc_read_inserts ins{};          // (--isoforms-inserts) the read's record, and how many sites its cluster kept
+    int32_t ins_sites = 0;
 };
 
 // The one place that chooses a library call.  --sites and / or --split come first; --polish, --correct and --isoforms are calls of their own,
@@ -252,6 +265,16 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
                           r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr, io.polish_max, io.polish_min_depth, &ip.seq[0], &ip.qual[0],
                           icap.bytes, ip.off.data(), ip.stats.data(), icap.isoforms, r.iso_off.data()),
                   io.polish_weighted ? "exon blocks with the isoforms' weighted consensus" : "exon blocks with the isoforms' consensus");
+        } else if (io.inserts) {
+            const int64_t icap = inserts_capacity(g, io.ins_max);
+            r.inserts.assign(size_t(std::max<int64_t>(icap, 1)), ioc_pile_insert{}), r.insert_off.assign(ns + 1, 0), r.inserts_seg.assign(ns, ioc_inserts_seg{});
+            r.read_inserts.assign(np, ioc_read_inserts{});
+            check(c, ioc_align_pairs_blocks_inserts(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
+                                                    g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
+                                                    r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
+                                                    o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr, r.inserts.data(),
+                                                    icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data()),
+                  "exon blocks with the insertion sites");
         } else {
             check(c, ioc_align_pairs_blocks(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
                                             io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
@@ -285,6 +308,7 @@ void scatter_to_rows(const ReportOpts& o, const ReportRows& rows, const ReportGr
             if (row.alleles.empty()) row.alleles = "*";
         }
         if (o.isoforms.on) row.iso = r.read_blocks[x], row.iso_blocks = r.blocks_seg[size_t(g.seg_of_pair[x])].n_blocks;
+        if (o.isoforms.on && o.isoforms.inserts) row.ins = r.read_inserts[x], row.ins_sites = r.inserts_seg[size_t(g.seg_of_pair[x])].n_sites;
         if (o.correct.on) {
             const ReadStatRow& rd = rows.row(g.pair_row[x]);
             const size_t q0 = size_t(g.offs[size_t(g.pairs[x].query)]), l0 = size_t(g.qoffs[size_t(g.pair_q[x])]), l1 = size_t(g.qoffs[size_t(g.pair_q[x]) + 1]);
@@ -416,9 +440,19 @@ void write_blocks(std::ofstream& blocks, std::ofstream& isoforms, std::ofstream*
     }
 }
 
+void write_inserts(std::ofstream& out, const ReportGroup& g, const GroupResult& r)
+{
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0) continue;
+        const string rows = cluster_inserts_rows(g.group_cls[x].first, r.inserts_seg[size_t(s)], r.inserts.data() + r.insert_off[size_t(s)]);
+        out.write(rows.data(), std::streamsize(rows.size()));
+    }
+}
+
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -442,6 +476,10 @@ struct GroupFiles {
             isoforms << "ClusterId\tIsoform\tSignature\tDirect\tAssigned\n";
         }
         if (o.iso_polish()) create_file(outdir + "/cluster_isoforms.fq", iso_fq);
+        if (o.isoforms.on && o.isoforms.inserts) {
+            create_file(outdir + "/cluster_inserts.tsv", inserts);
+            inserts << "ClusterId\tFirst\tEnd\tCarry\tLack\tNone\tLenMin\tLenMax\n";
+        }
     }
     void write(const Batch& b, const ReportOpts& o, const ReportGroup& g, const GroupResult& r)
     {
@@ -451,6 +489,7 @@ struct GroupFiles {
         if (o.split.on) write_split(split, g, r);
         if (o.group_polish() && !g.segs.empty()) write_group_polish(group_polish, g, r);
         if (o.isoforms.on && !g.segs.empty()) write_blocks(blocks, isoforms, o.iso_polish() ? &iso_fq : nullptr, g, r);
+        if (o.isoforms.on && o.isoforms.inserts && !g.segs.empty()) write_inserts(inserts, g, r);
     }
 };
 
@@ -489,6 +528,19 @@ void write_read_isoforms(const string& outdir, const ReportRows& rows, const std
         out << r.cls << '\t';
         out.write(r.id, std::streamsize(r.id_len));
         out << '\t' << read_isoform_columns(res[y].iso, res[y].iso_blocks) << '\n';
+    }
+}
+
+void write_read_inserts(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/read_inserts.tsv", out);
+    out << "ClusterId\tRead\tInserts\tIsoform\tHow\n";
+    for (size_t y = 0; y < rows.kept.size(); ++y) {
+        const ReadStatRow& r = rows.row(y);
+        out << r.cls << '\t';
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << read_insert_columns(res[y].ins, res[y].ins_sites) << '\n';
     }
 }
 
@@ -542,4 +594,5 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
     if (opts.stats) write_read_stats(outdir, rows, res);
     if (opts.correct.on) write_corrected_reads(outdir, res);
     if (opts.isoforms.on) write_read_isoforms(outdir, rows, res);
+    if (opts.isoforms.on && opts.isoforms.inserts) write_read_inserts(outdir, rows, res);
 }

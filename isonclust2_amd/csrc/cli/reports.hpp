@@ -1,4 +1,4 @@
-// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish, --isoforms-polish-weighted): every read of clusters.tsv
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish, --isoforms-polish-weighted, --isoforms-inserts): every read of clusters.tsv
 // aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
 // formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
 #ifndef ISONCLUST2_CLI_REPORTS_HPP
@@ -31,6 +31,8 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     int polish_min_depth = 0;  // --isoforms-polish: > 0, the depth below which an isoform's call keeps the representative's base, and ...
     int polish_max = 16;       // ... how many isoforms of a cluster are called
     bool polish_weighted = false;  // --isoforms-polish-weighted: every isoform is called by weight (ioc_align_pairs_blocks_polish_weighted)
+    bool inserts = false;                            // --isoforms-inserts: the insertion sites as well (ioc_align_pairs_blocks_inserts), and ...
+    int min_ins = 20, ins_slack = 8, ins_max = 32;   // ... the thresholds of ioc_host_planes_inserts the block search does not share
 };
 struct ReportOpts {
     bool stats = false;        // --read-stats
@@ -119,6 +121,16 @@ struct IsoCapacity {
     int64_t isoforms = 0, bytes = 0;
 };
 IsoCapacity iso_polish_capacity(const ReportGroup& g, int max_iso);
+// the insertion sites a search may keep at most, for all segments of a group: min(max_sites, the junctions of the representative) each
+int64_t inserts_capacity(const ReportGroup& g, int max_sites);
+// A signature of insertion sites: one character per kept site from the key's two bits each — '=' lack (as the representative), '+'
+// carry, '.' none —, "*" where the cluster has no site.
+std::string inserts_signature(uint64_t key, int32_t n_sites);
+// the rows of cluster_inserts.tsv of one cluster: "# cluster <id>: kept <n> of <found> sites" where the list was cut, then
+// "<id> <first> <end> <carry> <lack> <none> <len_min> <len_max>" per kept site
+std::string cluster_inserts_rows(size_t cluster, const ioc_inserts_seg& z, const ioc_pile_insert* sites);
+// the columns of read_inserts.tsv behind the cluster and the read: "<signature> <combined isoform or .> <direct|assigned|rare|ambiguous>"
+std::string read_insert_columns(const ioc_read_inserts& r, int32_t n_sites);
 // A signature: one character per kept block from the key's two bits each — '=' keep, '-' skip, '~' part, '.' none —, "*" where the
 // cluster has no block.
 std::string blocks_signature(uint64_t key, int32_t n_blocks);

@@ -21,6 +21,7 @@
 #include "ioc_pile_call.h"
 #include "ioc_pile_sites.h"
 #include "ioc_read_blocks.h"
+#include "ioc_read_inserts.h"
 #include "ioc_read_correct.h"
 #include "ioc_site_split.h"
 
@@ -784,6 +785,128 @@ int ioc_host_planes_blocks(const uint8_t* base, int32_t n_reads, int32_t rlen, i
     }
     if (out_rows) std::copy(table.begin(), table.end(), out_rows);
     std::copy(blocks.begin(), blocks.end(), out_blocks);
+    std::copy(reads.begin(), reads.end(), out_reads);
+    *out_seg = seg;
+    return IOC_OK;
+}
+
+// The length part of a read's projection (isonclust2_hip.h has the rules): how many bases the read inserts in front of every row,
+// a byte each — the definition k_ops_project_ilen (ioc_read_inserts.hip) is tested against.  The walk of ioc_host_ops_project.
+int ioc_host_ops_project_ilen(const char* ops, int64_t len, int32_t rlen, uint8_t* ilen)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || rlen < 0 || !ilen) return IOC_ERR_ARG;
+    int64_t r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (r != rlen) return IOC_ERR_ARG;
+    memset(ilen, 0, size_t(rlen) + 1);
+    r = 0;
+    for (int64_t a = 0; a < len;) {
+        int64_t e = a + 1;
+        if (ops[a] == 'I') {
+            while (e < len && ops[e] == 'I') ++e;
+            ilen[r] = inserts_len_byte((unsigned long long)(e - a));
+        } else {
+            r += ops[a] != 'i';
+        }
+        a = e;
+    }
+    return IOC_OK;
+}
+
+// The insertion sites of one segment and every read's combined isoform (isonclust2_hip.h has the rules; InsertsRule::variable,
+// inserts_state, inserts_key_agrees and inserts_key_less, ioc_read_inserts.h, decide for this function and for the kernels of
+// ioc_read_inserts.hip alike).  The plain loops: every read's spans and windowed sums, the row table, the runs of variable
+// junctions, a state per read and kept site, and the supported pairs of words in ascending unsigned order.
+int ioc_host_planes_inserts(const uint8_t* base, const uint8_t* ilen, int32_t n_reads, int32_t rlen, int32_t min_ins, int32_t slack, int32_t min_depth,
+                            int32_t min_alt, int32_t min_pct, int32_t max_sites, const uint64_t* pre_key, const uint64_t* pre_mask, uint64_t pre_full,
+                            ioc_insert_row* out_rows, ioc_pile_insert* out_sites, ioc_read_inserts* out_reads, ioc_inserts_seg* out_seg)
+{
+    const InsertsRule rule{min_ins, slack, min_depth, min_alt, min_pct, max_sites};
+    if (!rule.ok() || n_reads < 0 || rlen < 0 || !out_seg || (n_reads > 0 && (!base || !ilen || !out_reads)) || (rlen > 1 && !out_sites) ||
+        (n_reads > 0 && !pre_key != !pre_mask))
+        return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1, n = size_t(n_reads);
+    if (!pre_key) pre_full = 0;
+    auto pk = [&](size_t i) { return pre_key ? pre_key[i] : uint64_t(0); };
+    auto pm = [&](size_t i) { return pre_key ? pre_mask[i] : uint64_t(0); };
+    auto spans = [&](size_t i, int32_t p) { return p >= 1 && p <= rlen - 1 && blocks_covers(base[i * rows + size_t(p) - 1]) && blocks_covers(base[i * rows + size_t(p)]); };
+    auto window = [&](size_t i, int32_t p) {
+        uint32_t w = 0;
+        for (long long q = inserts_win_lo(p, slack); q <= inserts_win_hi(p, slack, rlen); ++q) w += ilen[i * rows + size_t(q)];
+        return w;
+    };
+    auto near = [&](size_t i, int32_t p) { return spans(i, p) && window(i, p) >= uint32_t(min_ins); };
+    std::vector<ioc_insert_row> table(rows, ioc_insert_row{0, 0});
+    std::vector<ioc_read_inserts> reads(n, ioc_read_inserts{});
+    for (size_t i = 0; i < n; ++i)
+        for (int32_t p = 1; p <= rlen - 1; ++p) {
+            if (!spans(i, p)) continue;
+            ++table[size_t(p)].span, reads[i].ins_bases += ilen[i * rows + size_t(p)];
+            if (near(i, p)) ++table[size_t(p)].in_ins, ++reads[i].n_near;
+        }
+    std::vector<ioc_pile_insert> sites;
+    int32_t n_found = 0;
+    for (int32_t a = 1; a <= rlen - 1;) {
+        int32_t e = a + 1;
+        if (rule.variable(table[size_t(a)].span, table[size_t(a)].in_ins)) {
+            while (e <= rlen - 1 && rule.variable(table[size_t(e)].span, table[size_t(e)].in_ins)) ++e;
+            if (n_found < max_sites) sites.push_back(ioc_pile_insert{a, e, 0, 0, 0, 0, 0, 0});
+            ++n_found;
+        }
+        a = e;
+    }
+    const uint32_t ns = uint32_t(sites.size());
+    const unsigned long long full = blocks_full_mask(ns);
+    std::vector<unsigned long long> mask(n, 0);
+    for (size_t i = 0; i < n; ++i)
+        for (uint32_t k = 0; k < ns; ++k) {
+            ioc_pile_insert& t = sites[k];
+            uint32_t c = 0, s = 0, longest = 0;
+            for (int32_t p = t.first; p < t.end; ++p) c += spans(i, p), s += near(i, p), longest = std::max(longest, window(i, p));
+            const uint32_t st = inserts_state(uint32_t(t.end - t.first), c, s);
+            reads[i].key |= uint64_t(st) << (2u * k);
+            mask[i] |= blocks_state_mask(k, st);
+            ++(st == IOC_INS_CARRY ? t.n_carry : st == IOC_INS_LACK ? t.n_lack : t.n_none);
+            if (st == IOC_INS_CARRY) t.len_min = t.n_carry == 1u ? longest : std::min(t.len_min, longest), t.len_max = std::max(t.len_max, longest);
+        }
+    typedef std::pair<uint64_t, uint64_t> Key;  // (the block stage's word, this stage's: compared in that order, unsigned)
+    std::vector<Key> complete, keys;
+    auto is_complete = [&](size_t i) { return mask[i] == full && pm(i) == pre_full; };
+    for (size_t i = 0; i < n; ++i)
+        if (is_complete(i)) complete.push_back(Key(pk(i), reads[i].key));
+    std::sort(complete.begin(), complete.end());
+    for (size_t a = 0; a < complete.size();) {
+        size_t e = a;
+        while (e < complete.size() && complete[e] == complete[a]) ++e;
+        if (e - a >= size_t(min_alt)) keys.push_back(complete[a]);
+        a = e;
+    }
+    ioc_inserts_seg seg{int32_t(ns), n_found, int32_t(keys.size()), n_reads, 0, 0, 0, 0};
+    for (size_t i = 0; i < n; ++i) {
+        ioc_read_inserts& rd = reads[i];
+        rd.group = -1;
+        if (is_complete(i)) {
+            const auto it = std::lower_bound(keys.begin(), keys.end(), Key(pk(i), rd.key));
+            if (it != keys.end() && *it == Key(pk(i), rd.key))
+                rd.group = int32_t(it - keys.begin()), rd.how = IOC_ISO_DIRECT, ++seg.n_direct;
+            else
+                rd.how = IOC_ISO_RARE, ++seg.n_rare;
+            continue;
+        }
+        int32_t agreeing = 0, which = -1;
+        for (size_t k = 0; k < keys.size() && (mask[i] | pm(i)) != 0ull; ++k)
+            if (inserts_key_agrees(pk(i), rd.key, keys[k].first, keys[k].second, pm(i), mask[i])) ++agreeing, which = int32_t(k);
+        if (agreeing == 1)
+            rd.group = which, rd.how = IOC_ISO_ASSIGNED, ++seg.n_assigned;
+        else
+            rd.how = IOC_ISO_AMBIGUOUS, ++seg.n_ambiguous;
+    }
+    if (out_rows) std::copy(table.begin(), table.end(), out_rows);
+    std::copy(sites.begin(), sites.end(), out_sites);
     std::copy(reads.begin(), reads.end(), out_reads);
     *out_seg = seg;
     return IOC_OK;

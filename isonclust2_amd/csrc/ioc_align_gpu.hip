@@ -1254,6 +1254,13 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
         IOC_CHK(c, iock_ops_project_weights(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_q_off, o.d_q_len, o.d_plane,
                                             static_cast<const uint8_t*>(c->a_qual.p), pool_bytes, pl.weight_planes, uint64_t(pl.plane_bytes)));
     IOC_CHK(c, hipEventRecord(ev.v[5], c->stream));
+    if (h.projects_ilen()) {  // (its own event, and only where it runs: every other call records what it always did)
+        ev.v.push_back(nullptr);
+        IOC_CHK(c, hipEventCreate(&ev.v.back()));
+        IOC_CHK(c, iock_ops_project_ilen(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_plane, pl.ilen_planes,
+                                         uint64_t(pl.plane_bytes)));
+        IOC_CHK(c, hipEventRecord(ev.v.back(), c->stream));
+    }
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
@@ -1276,6 +1283,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     if (h.projects() && hipEventElapsedTime(&ms, ev.v[2], ev.v[3]) == hipSuccess) t.ms_project += double(ms);
     if (h.projects_ins() && hipEventElapsedTime(&ms, ev.v[3], ev.v[4]) == hipSuccess) t.ms_project_ins += double(ms);
     if (h.projects_weights() && hipEventElapsedTime(&ms, ev.v[4], ev.v[5]) == hipSuccess) t.ms_project_weights += double(ms);
+    if (h.projects_ilen() && hipEventElapsedTime(&ms, ev.v[5], ev.v[6]) == hipSuccess) t.ms_project_ilen += double(ms);
     t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t.copied += int64_t(dp.size() * 4 + (stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
     if (stats) t.records += int64_t(cnt);

@@ -31,6 +31,8 @@ struct AlnTally {
     double ms_group_pile_weighted = 0;  // ... k_group_pile_weighted's (ioc_planes_polish_groups_weighted, ioc_align_pairs_blocks_polish_weighted)
     double ms_correct = 0;      // k_read_correct's device time, both passes and the scan (ioc_planes_correct, ioc_align_pairs_correct)
     double ms_blocks = 0;       // the eight kernels of ioc_read_blocks.hip, their device time together (ioc_planes_blocks, ioc_align_pairs_blocks)
+    double ms_project_ilen = 0; // k_ops_project_ilen's device time (a pile that projects the length plane as well), and ...
+    double ms_inserts[8] = {};  // ... the eight kernels of ioc_read_inserts.hip, in the order they run (ioc_planes_inserts, ioc_align_pairs_blocks_inserts)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
     int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };
@@ -155,6 +157,10 @@ struct AlnSink {
         // under the pool's quality bytes, into reference length + 1 bytes of each of 1 + IOC_PILE_INS_SLOTS more planes
         bool project_weights = false;
         uint8_t* weight_planes = nullptr;  // (device) [wbase plane][all wslot-0 planes] .. [all wslot-5 planes], plane_bytes each
+        // optional, with project (project_ilen): how many bases the pair inserts in front of every row is projected too
+        // (k_ops_project_ilen), into reference length + 1 bytes of one more plane from byte plane[i] on
+        bool project_ilen = false;
+        uint8_t* ilen_planes = nullptr;  // (device) plane_bytes
     } pile;
 
     bool reduced() const { return kind == SinkKind::reduced; }
@@ -163,7 +169,12 @@ struct AlnSink {
     bool projects() const { return has_pile() && pile.project; }
     bool projects_ins() const { return projects() && pile.project_ins; }
     bool projects_weights() const { return projects_ins() && pile.project_weights; }
-    uint64_t planes() const { return !pile.project ? 0 : !pile.project_ins ? 2 : 2 + uint64_t(IOC_PILE_INS_SLOTS) + (pile.project_weights ? 1 + uint64_t(IOC_PILE_INS_SLOTS) : 0); }
+    bool projects_ilen() const { return projects() && pile.project_ilen; }
+    uint64_t planes() const
+    {
+        const uint64_t ilen = pile.project && pile.project_ilen ? 1 : 0;
+        return ilen + (!pile.project ? 0 : !pile.project_ins ? 2 : 2 + uint64_t(IOC_PILE_INS_SLOTS) + (pile.project_weights ? 1 + uint64_t(IOC_PILE_INS_SLOTS) : 0));
+    }
     // what the tables hold of the device for the whole call (ck_budget's `held`)
     uint64_t pile_bytes() const
     {

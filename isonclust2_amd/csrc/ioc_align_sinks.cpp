@@ -3,7 +3,7 @@
 // (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.  An entry point checks its arguments, plans its
 // segments and pairs on the host (SinkPlan, ioc_sink_plan.h) and runs device stages in a row (SinkRun): pile -> sites -> alleles ->
 // [split] -> [group pile -> call] -> copy-out for the alleles family, pile -> call -> copy-out for the polish family, pile -> correct ->
-// copy-out for the read correction, pile -> blocks -> copy-out for the exon blocks, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
+// copy-out for the read correction, pile -> blocks -> [inserts] -> copy-out for the exon blocks and the insertion sites, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +19,7 @@
 #include "ioc_plane_pile.h"
 #include "ioc_read_blocks.h"
 #include "ioc_read_correct.h"
+#include "ioc_read_inserts.h"
 
 namespace {
 struct AlnCall {  // what every aligning entry point passes on
@@ -75,6 +76,23 @@ struct BlocksOut {  // the rule of a block search and where it leaves what it ma
     ioc_blocks_seg* seg;
     bool ok() const { return rule.ok() && block_off && cap >= 0; }
 };
+struct InsertsOut {  // the rule of a search for insertion sites and where it leaves what it made (cap: the records `sites` holds)
+    InsertsRule rule;
+    ioc_insert_row* rows;
+    ioc_pile_insert* sites;
+    int64_t cap;
+    int64_t* site_off;
+    ioc_read_inserts* reads;
+    ioc_inserts_seg* seg;
+    bool ok() const { return rule.ok() && site_off && cap >= 0; }
+};
+// the block stage's words an insert search combines with its own: the host's (uploaded), the device's (where the block stage left
+// them), or none (all NULL); pre_full is the host's, a word per segment
+struct InsertsPre {
+    const uint64_t *host_key = nullptr, *host_mask = nullptr, *pre_full = nullptr;
+    const unsigned long long *dev_key = nullptr, *dev_mask = nullptr;
+    uint32_t dev_key_stride = 1, dev_mask_stride = 1;
+};
 // what a call refuses once its bound is known: IOC_OK, or the status with the message set
 int call_room_ok(ioc_ctx* c, const std::string& who, const CallOut& o, int64_t bound)
 {
@@ -87,6 +105,11 @@ struct PiledDev {  // pile: the tables of the kind (a_pile; a_pile_ins or a_pile
     ioc_pileup_col *cols, *wcols;
     ioc_pileup_ins *ins, *wins;
     uint8_t *base, *insf, *slots, *weights;
+    uint8_t* ilen = nullptr;  // (a pile that projects the length plane: behind every other plane)
+};
+struct BlocksDev {  // blocks (a_blocks): where the block stage left every pair's record (its key) and its mask
+    const ioc_read_blocks* reads;
+    const unsigned long long* mask;
 };
 struct SitesDev {  // sites (a_call): the segments, what was kept, and the room of the allele gather behind them
     const IocPileSeg* segs;
@@ -164,7 +187,7 @@ struct SinkRun {
         return IOC_OK;
     }
     int pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane, int64_t plane_bytes, bool project_ins, PiledDev& d,
-             bool project_weights = false);
+             bool project_weights = false, bool project_ilen = false);
     int sites(const SitesRule& r, const SinkPlan& p, const ioc_pileup_col* d_cols, ioc_pile_site* out_sites, int64_t* site_off, int64_t* n_found, SitesDev& d);
     int alleles(const SitesDev& d, const SinkPlan& p, const int32_t* seg_of_pair, const PiledDev& planes, const int64_t* site_off, int64_t* allele_off, uint8_t* out_alleles);
     int split(const SplitCall& sp, size_t n, size_t np, const int32_t* seg_of_pair, const int64_t* site_off, const int64_t* allele_off, const ioc_pile_site* sites,
@@ -174,7 +197,9 @@ struct SinkRun {
                     bool weighted = false);
     int correct(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* d_frames, uint64_t frame_bytes, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
                 const Planes& host, Planes dev, const CorrectOut& o);
-    int blocks(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o);
+    int blocks(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o, BlocksDev* where = nullptr);
+    int inserts(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* host_ilen, const uint8_t* dev_base, const uint8_t* dev_ilen,
+                const InsertsPre& pre, const InsertsOut& o);
 };
 
 // Pile and project.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it (ins), or a_pile_w as [wcols][wins] (weighted)
@@ -182,9 +207,9 @@ struct SinkRun {
 // re-run).  `plane` (the alleles family): every pair is projected as well, into the planes of a_planes, [base planes][ins planes] and, with
 // project_ins, [slot planes x 6] behind them, set to IOC_ALLELE_NONE / 0 once here; with project_weights (which asks for project_ins
 // and for the pool's qualities), [weight planes x 7] behind those, set to 0 with them.  A call without project_weights reserves what
-// it always did.
+// it always did.  project_ilen: one more plane behind all of those, the length plane (k_ops_project_ilen), set to 0 with them.
 int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane,
-                  int64_t plane_bytes, bool project_ins, PiledDev& d, bool project_weights)
+                  int64_t plane_bytes, bool project_ins, PiledDev& d, bool project_weights, bool project_ilen)
 {
     IOC_CHK(c, hipSetDevice(c->device));
     const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
@@ -203,19 +228,20 @@ int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, con
     if (plane) {
         const size_t b_plane = size_t(plane_bytes);
         const size_t n_zeroed = !project_ins ? 1 : 1 + size_t(IOC_PILE_INS_SLOTS) + (project_weights ? size_t(IOC_WEIGHT_PLANES) : 0);  // (the ins planes and on)
-        IOC_TRY(ioc_reserve(c, c->a_planes, (1 + n_zeroed) * b_plane));
+        IOC_TRY(ioc_reserve(c, c->a_planes, (1 + n_zeroed + (project_ilen ? 1 : 0)) * b_plane));
         pl.project = true, pl.base_planes = c->a_planes.as<uint8_t>(), pl.ins_planes = pl.base_planes + b_plane;
         pl.plane_bytes = plane_bytes, pl.plane = plane;
         if (project_ins) pl.project_ins = true, pl.slot_planes = pl.base_planes + 2 * b_plane;
         if (project_ins && project_weights) pl.project_weights = true, pl.weight_planes = pl.slot_planes + size_t(IOC_PILE_INS_SLOTS) * b_plane;
+        if (project_ilen) pl.project_ilen = true, pl.ilen_planes = pl.base_planes + (1 + n_zeroed) * b_plane;
         if (b_plane > 0) {
             IOC_CHK(c, hipMemsetAsync(pl.base_planes, IOC_ALLELE_NONE, b_plane, c->stream));
-            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, n_zeroed * b_plane, c->stream));  // (and the slot planes, and the weight planes)
+            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, (n_zeroed + (project_ilen ? 1 : 0)) * b_plane, c->stream));  // (and the slot, weight and length planes)
         }
     }
     const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, out_stats != nullptr, out_stats, pl};
     IOC_TRY(a.run(c, a.n_pairs > 0 ? &sink : nullptr));
-    d = PiledDev{pl.cols, pl.wcols, pl.ins, pl.wins, pl.base_planes, pl.ins_planes, pl.slot_planes, pl.weight_planes};
+    d = PiledDev{pl.cols, pl.wcols, pl.ins, pl.wins, pl.base_planes, pl.ins_planes, pl.slot_planes, pl.weight_planes, pl.ilen_planes};
     return IOC_OK;
 }
 
@@ -509,7 +535,7 @@ int SinkRun::correct(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8
 // [block_base], the kernels' own [covered][deleted][long gaps][variable rows][masks][flags][row table][block slots][read records]
 // [segment records] and, uploaded, [base plane].  The segment records come back first: they say how many of a segment's slots are
 // blocks, and the blocks are packed on the host.
-int SinkRun::blocks(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o)
+int SinkRun::blocks(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o, BlocksDev* where)
 {
     const size_t n = pn.segs.size(), np = pn.plane.size(), B = size_t(pn.plane_bytes);
     const BlocksTables bt = blocks_tables(pn, seg_of_pair, o.rule.max_blocks);
@@ -541,6 +567,7 @@ int SinkRun::blocks(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_
                              reinterpret_cast<const int64_t*>(p + o_bb), uint64_t(P), uint64_t(T), uint64_t(pn.n_rows), uint64_t(slots), u64p(o_cov), u64p(o_del),
                              u64p(o_gap), u64p(o_var), u64p(o_mask), p + o_flags, reinterpret_cast<ioc_block_row*>(p + o_rows),
                              reinterpret_cast<ioc_pile_block*>(p + o_blk), reinterpret_cast<ioc_read_blocks*>(p + o_reads), reinterpret_cast<ioc_blocks_seg*>(p + o_rec)};
+    if (where) *where = BlocksDev{v.reads, v.mask};
     const BlocksRule& k = o.rule;
     IOC_TRY(begin(t.ms_blocks));
     IOC_CHK(c, iock_read_blocks(c->stream, v, k.min_gap, k.min_depth, k.min_alt, k.min_pct, k.min_block, k.max_blocks));
@@ -560,6 +587,92 @@ int SinkRun::blocks(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_
         o.seg[g] = rec[g];
     }
     return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_blocks)}, {o.rows, p + o_rows, size_t(pn.n_rows) * sizeof(ioc_block_row)}});
+}
+
+// The kernels of ioc_read_inserts.hip over the plan's pairs: the base and the length planes lie on the device (dev_base, dev_ilen)
+// or are the host's and uploaded; the block stage's words likewise, or there are none.  a_inserts holds the host's tables [segments]
+// [seg_of_pair][plane offsets][mem_off][members][pair_word][seg_word][word_seg][site_base][slot_seg][pre_full], the kernels' own
+// [spans][near][variable junctions][masks][flags][largest sums][row table][site slots][read records][segment records] and, uploaded, [base plane]
+// [length plane][pre_key][pre_mask].  The segment records come back first and the sites are packed on the host, as the blocks are.
+// Under IOC_TRACE every kernel is timed on its own (t.ms_inserts, in the order they run); otherwise ms_inserts[0] has all of them.
+int SinkRun::inserts(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* host_ilen, const uint8_t* dev_base,
+                     const uint8_t* dev_ilen, const InsertsPre& pre, const InsertsOut& o)
+{
+    const size_t n = pn.segs.size(), np = pn.plane.size(), B = size_t(pn.plane_bytes);
+    const BlocksTables bt = blocks_tables(pn, seg_of_pair, 1);  // (the words of a pair and of a segment are the block stage's)
+    const MemberLists m = member_lists(n, np, seg_of_pair);
+    std::vector<int64_t> site_base(n + 1, 0);
+    for (size_t g = 0; g < n; ++g) site_base[g + 1] = site_base[g] + inserts_sites_most(pn.segs[g].rlen, o.rule.max_sites);
+    const size_t P = bt.P, T = bt.T, slots = size_t(site_base[n]);
+    std::vector<int32_t> slot_seg(slots);
+    for (size_t g = 0; g < n; ++g) std::fill(slot_seg.begin() + site_base[g], slot_seg.begin() + site_base[g + 1], int32_t(g));
+    const bool pre_host = pre.host_key != nullptr, pre_dev = pre.dev_key != nullptr, with_pre = pre_host || pre_dev;
+    Arena l;
+    const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_plane = l.take(np * 8), o_moff = l.take((n + 1) * 4), o_mem = l.take(np * 4),
+                 o_pw = l.take(np * 8), o_sw = l.take((n + 1) * 8), o_ws = l.take(T * 4), o_sb = l.take((n + 1) * 8), o_ss = l.take(slots * 4),
+                 o_pf = l.take(with_pre ? n * 8 : 0), tables = l.size();
+    const size_t S = size_t(o.rule.max_sites);
+    const size_t o_span = l.take(P * 8), o_near = l.take(P * 8), o_var = l.take(T * 8), o_mask = l.take(np * 8), o_flags = l.take(np), o_wmax = l.take(np * S * 2),
+                 o_rows = l.take(size_t(pn.n_rows) * sizeof(ioc_insert_row)), o_sites = l.take(slots * sizeof(ioc_pile_insert)),
+                 o_reads = l.take(np * sizeof(ioc_read_inserts)), o_rec = l.take(n * sizeof(ioc_inserts_seg)), o_end = l.size(),
+                 o_base = l.take(dev_base ? 0 : B), o_ilen = l.take(dev_ilen ? 0 : B), o_pk = l.take(pre_host ? np * 8 : 0), o_pm = l.take(pre_host ? np * 8 : 0);
+    std::vector<uint8_t> stage(tables, 0);
+    auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
+    put(o_seg, pn.segs.data(), n * sizeof(IocPileSeg)), put(o_sop, seg_of_pair, np * 4), put(o_plane, pn.plane.data(), np * 8);
+    put(o_moff, m.mem_off.data(), (n + 1) * 4), put(o_mem, m.members.data(), np * 4), put(o_pw, bt.pair_word.data(), np * 8);
+    put(o_sw, bt.seg_word.data(), (n + 1) * 8), put(o_ws, bt.word_seg.data(), T * 4), put(o_sb, site_base.data(), (n + 1) * 8);
+    put(o_ss, slot_seg.data(), slots * 4);
+    if (with_pre) put(o_pf, pre.pre_full, n * 8);
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_inserts, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_inserts.p);
+    IOC_CHK(c, hipMemcpyAsync(p, stage.data(), tables, hipMemcpyHostToDevice, c->stream));
+    if (!dev_base && B) IOC_CHK(c, hipMemcpyAsync(p + o_base, host_base, B, hipMemcpyHostToDevice, c->stream));
+    if (!dev_ilen && B) IOC_CHK(c, hipMemcpyAsync(p + o_ilen, host_ilen, B, hipMemcpyHostToDevice, c->stream));
+    if (pre_host && np) {
+        IOC_CHK(c, hipMemcpyAsync(p + o_pk, pre.host_key, np * 8, hipMemcpyHostToDevice, c->stream));
+        IOC_CHK(c, hipMemcpyAsync(p + o_pm, pre.host_mask, np * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    IOC_CHK(c, hipMemsetAsync(p + o_sites, 0, o_end - o_sites, c->stream));  // (the site slots and both kinds of record)
+    auto u64p = [&](size_t at) { return reinterpret_cast<unsigned long long*>(p + at); };
+    const IocReadInsertsDev v{reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop),
+                              reinterpret_cast<const uint64_t*>(p + o_plane), dev_base ? dev_base : p + o_base, dev_ilen ? dev_ilen : p + o_ilen, uint64_t(B),
+                              reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem),
+                              reinterpret_cast<const uint64_t*>(p + o_pw), reinterpret_cast<const uint64_t*>(p + o_sw), reinterpret_cast<const int32_t*>(p + o_ws),
+                              reinterpret_cast<const int64_t*>(p + o_sb), reinterpret_cast<const int32_t*>(p + o_ss), uint64_t(P), uint64_t(T), uint64_t(pn.n_rows),
+                              uint64_t(slots), pre_dev ? pre.dev_key : pre_host ? u64p(o_pk) : nullptr, pre_dev ? pre.dev_mask : pre_host ? u64p(o_pm) : nullptr,
+                              with_pre ? u64p(o_pf) : nullptr, pre_dev ? pre.dev_key_stride : 1u, pre_dev ? pre.dev_mask_stride : 1u, u64p(o_span), u64p(o_near),
+                              u64p(o_var), u64p(o_mask), p + o_flags, reinterpret_cast<uint16_t*>(p + o_wmax), uint32_t(S), uint64_t(np * S),
+                              reinterpret_cast<ioc_insert_row*>(p + o_rows), reinterpret_cast<ioc_pile_insert*>(p + o_sites),
+                              reinterpret_cast<ioc_read_inserts*>(p + o_reads), reinterpret_cast<ioc_inserts_seg*>(p + o_rec)};
+    const InsertsRule& k = o.rule;
+    EventSet each;
+    if (getenv("IOC_TRACE")) {
+        each.v.assign(IOC_READ_INSERTS_KERNELS + 1, nullptr);
+        for (auto& e : each.v) IOC_CHK(c, hipEventCreate(&e));
+    }
+    IOC_TRY(begin(t.ms_inserts[0], each.v.empty()));
+    IOC_CHK(c, iock_read_inserts(c->stream, v, k.min_ins, k.slack, k.min_depth, k.min_alt, k.min_pct, k.max_sites, each.v.empty() ? nullptr : each.v.data()));
+    IOC_TRY(end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    settled();
+    for (size_t x = 0; x + 1 < each.v.size(); ++x) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, each.v[x], each.v[x + 1]) == hipSuccess) t.ms_inserts[x] += double(ms);
+    }
+    std::vector<ioc_inserts_seg> rec(n);
+    std::vector<ioc_pile_insert> slot(slots);
+    IOC_TRY(copy_out({{rec.data(), p + o_rec, n * sizeof(ioc_inserts_seg)}, {slot.data(), p + o_sites, slots * sizeof(ioc_pile_insert)}}));
+    for (size_t g = 0; g < n; ++g)
+        if (rec[g].n_sites < 0 || rec[g].n_sites > site_base[g + 1] - site_base[g])
+            return ioc_fail(c, IOC_ERR_HIP, "the search for insertion sites returned a count outside its bound");
+    o.site_off[0] = 0;
+    for (size_t g = 0; g < n; ++g) {
+        std::copy(slot.begin() + site_base[g], slot.begin() + site_base[g] + rec[g].n_sites, o.sites + o.site_off[g]);
+        o.site_off[g + 1] = o.site_off[g] + rec[g].n_sites;
+        o.seg[g] = rec[g];
+    }
+    return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_inserts)}, {o.rows, p + o_rows, size_t(pn.n_rows) * sizeof(ioc_insert_row)}});
 }
 
 }  // namespace
@@ -1178,6 +1291,102 @@ int ioc_align_pairs_blocks(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
         fprintf(stderr, "[ioc]   aligner: blocks: %d segments, %lld rows, %d pairs, %lld blocks kept, %.3f MB (blocks, records%s%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms%s\n",
                 n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], double(r.t.copied) * 1e-6, out_rows ? ", rows" : "", out_cols ? ", table" : "",
                 out_stats ? ", statistics" : "", r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_blocks,
+                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+// what a search for insertion sites refuses once its plan is known: IOC_OK, or the status with the message set
+static int64_t inserts_bound(const SinkPlan& p, int32_t max_sites)
+{
+    int64_t b = 0;
+    for (const IocPileSeg& sg : p.segs) b += inserts_sites_most(sg.rlen, max_sites);
+    return b;
+}
+static int inserts_room_ok(ioc_ctx* c, const std::string& who, const InsertsOut& o, const SinkPlan& p)
+{
+    const int64_t bound = inserts_bound(p, o.rule.max_sites);
+    if (o.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": sites_cap " + std::to_string(o.cap) + " below the bound " + std::to_string(bound));
+    return (bound > 0 && !o.sites) || (!p.plane.empty() && !o.reads) || (!p.segs.empty() && !o.seg) ? IOC_ERR_ARG : IOC_OK;
+}
+static std::string inserts_trace(const AlnTally& t)
+{
+    char buf[400];
+    snprintf(buf, sizeof buf, "k_ins_bits %.3f ms, k_ins_rows %.3f ms, k_ins_list %.3f ms, k_ins_states %.3f ms, k_ins_lens %.3f ms, k_ins_support %.3f ms, k_ins_isoforms %.3f ms, k_ins_record %.3f ms",
+             t.ms_inserts[0], t.ms_inserts[1], t.ms_inserts[2], t.ms_inserts[3], t.ms_inserts[4], t.ms_inserts[5], t.ms_inserts[6], t.ms_inserts[7]);
+    return buf;
+}
+
+// upload -> inserts -> copy-out.  The search for insertion sites from planes the caller holds: they are uploaded, and the kernels run
+// as behind ioc_align_pairs_blocks_inserts.
+int ioc_planes_inserts(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const uint8_t* base, const uint8_t* ilen,
+                       int32_t min_ins, int32_t slack, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites, const uint64_t* pre_key,
+                       const uint64_t* pre_mask, const uint64_t* pre_full, ioc_insert_row* out_rows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                       int64_t* site_off, ioc_read_inserts* out_reads, ioc_inserts_seg* out_seg)
+{
+    const InsertsOut o{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_rows, out_sites, sites_cap, site_off, out_reads, out_seg};
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || (n_segs > 0 && !rlen) || (n_pairs > 0 && !seg_of_pair)) return IOC_ERR_ARG;
+    const int given = (pre_key != nullptr) + (pre_mask != nullptr) + (pre_full != nullptr);
+    if (given != 0 && given != 3) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen("ioc_planes_inserts", n_segs, rlen, nullptr, nullptr, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !ilen)) return IOC_ERR_ARG;
+    IOC_TRY(inserts_room_ok(c, "ioc_planes_inserts", o, p));
+    site_off[0] = 0;
+    if (n_segs == 0) return IOC_OK;
+    SinkRun r{c};
+    InsertsPre pre;
+    if (given && n_pairs > 0) pre.host_key = pre_key, pre.host_mask = pre_mask, pre.pre_full = pre_full;
+    IOC_TRY(r.inserts(p, seg_of_pair, base, ilen, nullptr, nullptr, pre, o));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes inserts: %d segments, %lld rows, %d pairs, %lld plane bytes, %lld sites kept, %s\n", n_segs, (long long)p.n_rows, n_pairs,
+                (long long)p.plane_bytes, (long long)site_off[n_segs], inserts_trace(r.t).c_str());
+    return IOC_OK;
+}
+
+// pile -> blocks -> inserts -> copy-out.  ioc_align_pairs_blocks with the length plane projected beside the two, and behind the block
+// kernels the insert kernels over the planes where they lie, with the block stage's keys and masks where that stage left them: its
+// read records and masks stay in a_blocks, the insert stage has a_inserts.
+int ioc_align_pairs_blocks_inserts(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                   int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                   const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                   int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                   int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                   int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                   int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg)
+{
+    const std::string who = "ioc_align_pairs_blocks_inserts";
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
+    const InsertsOut io{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
+    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !io.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
+    IOC_TRY(blocks_room_ok(c, who, o, p));
+    IOC_TRY(inserts_room_ok(c, who, io, p));
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    block_off[0] = 0, site_off[0] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    SinkRun r{c};
+    PiledDev d;
+    BlocksDev bd{};
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d, /*project_weights*/ false,
+                   /*project_ilen*/ true));
+    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o, &bd));  // (a_blocks is reserved here, after the walks; the segment records are the host's from here on)
+    std::vector<uint64_t> pre_full(size_t(n_segs), 0);
+    for (int32_t g = 0; g < n_segs; ++g) pre_full[size_t(g)] = blocks_full_mask(uint32_t(out_seg[g].n_blocks));
+    InsertsPre pre;
+    pre.pre_full = pre_full.data();
+    if (n_pairs > 0) {
+        static_assert(sizeof(ioc_read_blocks) % 8 == 0 && offsetof(ioc_read_blocks, key) == 0, "a record's first word is its key");
+        pre.dev_key = reinterpret_cast<const unsigned long long*>(bd.reads), pre.dev_key_stride = uint32_t(sizeof(ioc_read_blocks) / 8);
+        pre.dev_mask = bd.mask, pre.dev_mask_stride = 1;
+    }
+    IOC_TRY(r.inserts(p, seg_of_pair, nullptr, nullptr, d.base, d.ilen, pre, io));  // (a_inserts likewise)
+    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: blocks inserts: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ilen %.3f ms, ms_blocks %.3f ms, %s%s\n",
+                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[n_segs], double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_pileup,
+                r.t.ms_project, r.t.ms_project_ilen, r.t.ms_blocks, inserts_trace(r.t).c_str(),
                 out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
     return IOC_OK;
 }

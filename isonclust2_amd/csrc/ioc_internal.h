@@ -224,6 +224,7 @@ struct ioc_ctx {
                       // ioc_align_pairs_blocks_polish_weighted: the same of k_group_pile_weighted, with the uploaded weight planes and gwcols / gwins
     DevBuf a_correct; // ioc_planes_correct, ioc_align_pairs_correct: segments, pairs, offsets, records and the corrected bytes (ioc_read_correct.hip) and,
                       // from host planes, the uploaded planes
+    DevBuf a_inserts; // ioc_planes_inserts, ioc_align_pairs_blocks_inserts: the tables, bit planes and records of ioc_read_inserts.hip and, uploaded, both planes
     DevBuf a_blocks;  // ioc_planes_blocks, ioc_align_pairs_blocks: segments, pairs, member lists, bit planes, tables and records (ioc_read_blocks.hip) and,
                       // from host planes, the uploaded planes
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
@@ -496,6 +497,44 @@ struct IocReadBlocksDev {
 };
 hipError_t iock_read_blocks(hipStream_t st, const IocReadBlocksDev& v, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
                             int32_t min_block, int32_t max_blocks);
+
+// ioc_read_inserts.hip: how many bases the same strings insert in front of every row, into one byte plane of the pairs' own
+// (ioc_host_ops_project_ilen) — pair pid's from ilen_planes + plane[pid] on (set to 0 by the caller); launched beside iock_ops_project —
+// and the insertion sites of many segments with every read's combined isoform (ioc_host_planes_inserts per segment).  Everything is
+// a device pointer, laid out as for IocReadBlocksDev: the words of the bit planes span and near per pair, those of var per segment,
+// min(max_sites, max(rlen - 1, 0)) site slots of segment g from site_base[g] on (n_site_slots in all; slot_seg says whose each is).
+// pre_key / pre_mask: pair i's block word and its mask at word i * stride (NULL: 0), pre_full per segment (NULL: 0).  sites, reads
+// and seg_out are set to 0 by the caller.
+hipError_t iock_ops_project_ilen(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room, const uint32_t* ord,
+                                 uint32_t cnt, const int64_t* row_base, const uint64_t* plane, uint8_t* ilen_planes, uint64_t plane_bytes);
+struct IocReadInsertsDev {
+    const IocPileSeg* segs;
+    uint32_t n_segs, n_pairs;
+    const int32_t* seg_of_pair;
+    const uint64_t* plane;
+    const uint8_t *base_planes, *ilen_planes;
+    uint64_t plane_bytes;
+    const uint32_t *mem_off, *members;
+    const uint64_t *pair_word, *seg_word;
+    const int32_t* word_seg;
+    const int64_t* site_base;
+    const int32_t* slot_seg;
+    uint64_t n_pair_words, n_seg_words, n_rows, n_site_slots;
+    const unsigned long long *pre_key, *pre_mask, *pre_full;
+    uint32_t pre_key_stride, pre_mask_stride;
+    unsigned long long *span, *near, *var, *mask;
+    uint8_t* flags;
+    uint16_t* wmax;  // scratch: a carrier's largest windowed sum at kept site k of its segment, at wmax[pair * wmax_stride + k]; n_wmax entries
+    uint32_t wmax_stride;
+    uint64_t n_wmax;
+    ioc_insert_row* rows;
+    ioc_pile_insert* sites;
+    ioc_read_inserts* reads;
+    ioc_inserts_seg* seg_out;
+};
+enum { IOC_READ_INSERTS_KERNELS = 8 };  // (each: IOC_READ_INSERTS_KERNELS + 1 events, or NULL)
+hipError_t iock_read_inserts(hipStream_t st, const IocReadInsertsDev& v, int32_t min_ins, int32_t slack, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                             int32_t max_sites, hipEvent_t* each);
 
 // ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
 // is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in
