@@ -1247,9 +1247,8 @@ int ioc_host_ops_project_ilen(const char* ops, int64_t len, int32_t rlen, uint8_
  *     there: agreement is tested under both masks, and "a state that is not NONE" means that either mask is not 0.
  * 10. The read record: key, group, how (the COMBINED isoform), n_near the junctions with N_i, ins_bases the sum of ilen_i over the
  *     junctions the read spans.
- * What stays out: the sequence of an inserted exon (run the block stage with a carrier as the representative: there it is a
- * block), alternative ends, more than 32 sites, runs beyond 255 bases (they count as 255).  20 bases and 8 junctions are choices
- * made on simulated reads, not measured on real data. */
+ * What stays out: alternative ends, more than 32 sites, runs beyond 255 bases (they count as 255).  The sequence of an inserted
+ * exon is the next section's.  20 bases and 8 junctions are choices made on simulated reads, not measured on real data. */
 #define IOC_INS_LACK 0
 #define IOC_INS_CARRY 1
 #define IOC_INS_NONE 3
@@ -1307,6 +1306,94 @@ int ioc_align_pairs_blocks_inserts(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_
                                    ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins, int32_t slack, int32_t max_sites,
                                    ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap, int64_t* site_off,
                                    ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg);
+
+/* ---- The sequence of an inserted exon: the consensus of the carriers' windows at every kept insertion site ----
+ * The insert stage says who carries an exon the representative lacks; the slot planes keep six of its bases.  What the carriers
+ * hold between two anchor rows of the representative is cut out of the reads themselves, aligned to one of them and called with
+ * the call that exists.  Nothing is aligned against the representative again.
+ *
+ * The position plane of one read: qpos[0 .. rlen], 32-bit.  qpos[0] = 0; for r >= 1, qpos[r] is the number of bytes of "=XIi"
+ * among all bytes up to and including the byte that consumes reference row r - 1.  The run of 'I' in front of row r therefore
+ * begins at query[qpos[r]].  What ioc_host_ops_project_ilen refuses: IOC_ERR_ARG, with nothing written. */
+int ioc_host_ops_project_qpos(const char* ops, int64_t len, int32_t rlen, uint32_t* qpos);
+/* A global alignment of two short strings, both ends anchored, linear gaps (both strings hold the same exon between the same
+ * anchors: a gap costs `gap` >= 0 a base, and affine gaps are left out).  H[0][j] = -j gap, H[i][0] = -i gap, H[i][j] = max(H[i-1]
+ * [j-1] + (query[i-1] == ref[j-1] ? match : mismatch), H[i][j-1] - gap, H[i-1][j] - gap), plain integers.  The walk goes back from
+ * (qlen, rlen) and takes the diagonal where it gives H, else 'D' (H[i][j-1] - gap: a reference base alone) where that does, else
+ * 'I'; on row 0 'D', on column 0 'I'.  The bytes "=XID" in forward order in ops (qlen + rlen at most), their number returned; the
+ * tie order is part of the definition, k_win_align returns the same alignment.  *out_score (may be NULL): H[qlen][rlen].
+ * IOC_ERR_ARG for a negative length or gap, |match|, |mismatch| or gap above 2^20 and a NULL pointer that is needed;
+ * IOC_ERR_CAPACITY for cap < qlen + rlen and for (qlen + 1)(rlen + 1) above 2^26. */
+int64_t ioc_host_align_global_ops(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match, int32_t mismatch, int32_t gap,
+                                  char* ops, int64_t cap, int32_t* out_score);
+/* A read's window at a kept site [first, end) of a segment of rlen rows, all integers, `slack` the insert stage's:
+ *   lo = max(first - slack, 1), hi = min(end + slack, rlen); the window rows are [lo, hi); read i's window is
+ *   query_i[qpos_i[lo], qpos_i[hi]): the insertions at junctions lo .. hi - 1 and the read's bases on rows lo .. hi - 1.
+ * Read i VOTES iff its state at the site is IOC_INS_CARRY, its base plane covers rows lo - 1 and hi - 1 (a byte of 0 .. 5) and its
+ * window length is in 1 .. max_win, max_win in 1 .. IOC_WIN_MAX.  A carrier that fails coverage counts as n_short; one that covers
+ * and fails the length test as n_long, and so does one whose window leaves its read (qpos[hi] < qpos[lo] or qpos[hi] > qlen_i: a
+ * plane that is not this read's).  The TEMPLATE is the voter at index (n - 1) / 2 of the voters sorted ascending by (window
+ * length, index): the lower median.  A site without a voter is not called: tlen = 0, template_pair = -1.
+ * All carriers of a site vote together, whichever isoform they are in: two different exons at one junction are not told apart.
+ * The consensus of a site: every voter's window is aligned to the template's (ioc_host_align_global_ops, the template the
+ * reference; the template to itself is all '='), its bytes projected (ioc_host_ops_project, ioc_host_ops_project_ins) and piled
+ * (ioc_host_planes_pile); the site is ioc_host_pileup_call(those tables, the template's window, polish_min_depth).  The sequence
+ * stands in the orientation the pairs were aligned in: the reverse complement's frame where the segment's ref_revcomp is set.
+ * lo and hi come back: the consensus stands for the representative's rows [lo, hi). */
+#define IOC_WIN_MAX 512
+#define IOC_WIN_NONE 0   /* a read's class at a site: no carrier; a voter; a carrier that does not cover; one whose window is too long */
+#define IOC_WIN_VOTER 1
+#define IOC_WIN_SHORT 2
+#define IOC_WIN_LONG 3
+typedef struct {
+    int32_t lo, hi;
+    int32_t template_pair;        /* the pair (ioc_host_insert_windows: the read) whose window is the template, -1 without */
+    int32_t tlen;                 /* its window's length, 0: the site is not called */
+    uint32_t n_voters, n_short, n_long;
+    uint32_t reserved;
+} ioc_insert_window;              /* 32 bytes */
+/* The definition of the windows of one segment: base planes and position planes read-major (n_reads x (rlen + 1) bytes / words),
+ * qlen per read, the kept sites (first and end are read) and every read's key (ioc_read_inserts.key).  out_win: n_sites records;
+ * out_class (may be NULL): a byte per read and site, read-major, IOC_WIN_*; out_start / out_len (may be NULL, both or neither): where
+ * a VOTER's window begins in its read and how long it is, 0 elsewhere.  IOC_ERR_ARG, with nothing written, for slack outside 0 ..
+ * 32, max_win outside 1 .. IOC_WIN_MAX, n_sites outside 0 .. 32, a site outside 1 <= first < end <= rlen, a negative count and a NULL
+ * pointer that is needed. */
+int ioc_host_insert_windows(const uint8_t* base, const uint32_t* qpos, const int32_t* qlen, int32_t n_reads, int32_t rlen,
+                            const ioc_pile_insert* sites, int32_t n_sites, const uint64_t* keys, int32_t slack, int32_t max_win,
+                            ioc_insert_window* out_win, uint8_t* out_class, uint32_t* out_start, uint32_t* out_len);
+/* Many segments at once on the device, over the pool that is set (ioc_align_set_pool): pair i's read is pool sequence query[i], its
+ * planes lie as for ioc_planes_inserts (base: bytes, qpos: 32-bit words, reference length + 1 each, the pairs one behind the other),
+ * sites packed with site_off (n_segs + 1 entries) and keys per pair as ioc_planes_inserts returned them.  The kernels of
+ * ioc_insert_windows.hip: k_win_bounds (a wave per pair, a lane per site), k_win_template (a wave per site: the lower median by
+ * counting smaller (length, pair) over the members), k_win_align (a wave per voter and site: the recurrence above with a lane per
+ * template column, two direction bits a cell, and the walk back, which writes the voter's base plane and slot planes in the
+ * template's frame), then k_group_pile with a group per site and k_pile_call, both unchanged.  No atomics.
+ * Outputs, per site in site order (n = site_off[n_segs]): out_win (template_pair: the pair of the call); out_seq / out_qual packed
+ * with out_off (n + 1 entries); out_stats; out_cols / out_ins (may be NULL, both or neither): the sites' tables, site x from the
+ * sum over the earlier sites of (tlen + 1) on, room for n (max_win + 1) rows.  IOC_ERR_ARG, with nothing written, for what the
+ * definitions refuse, polish_min_depth < 1, a query outside the pool, seg_of_pair outside the segments, site_off that does not
+ * ascend from 0 and a NULL pointer that is needed; IOC_ERR_CAPACITY, with nothing written, for cap below n (7 max_win + 6). */
+int ioc_planes_insert_windows(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* query,
+                              const uint8_t* base, const uint32_t* qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys,
+                              int32_t slack, int32_t max_win, int32_t match, int32_t mismatch, int32_t gap, int32_t polish_min_depth,
+                              ioc_insert_window* out_win, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats,
+                              ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins);
+/* ioc_align_pairs_blocks_inserts with the position plane projected beside the other two (k_ops_project_qpos: four more bytes per
+ * row and pair, which count against the checkpoint arena's budget; the calls that exist reserve what they always did) and, behind
+ * the insert kernels, the window kernels over the planes where they lie.  Everything ioc_align_pairs_blocks_inserts returns comes
+ * back unchanged, byte for byte; added are the outputs of ioc_planes_insert_windows over the sites kept, with win_match /
+ * win_mismatch / win_gap as its scoring triple.  win_cap must hold (sum over the segments of min(max_sites, max(rlen - 1, 0))) x
+ * (7 max_win + 6), which is known before the call.  Every pair is aligned once.  The refusals of both calls; nothing is written. */
+int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                       int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                       int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                                       int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                                       ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                                       ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins, int32_t slack, int32_t max_sites,
+                                       ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap, int64_t* site_off,
+                                       ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                       int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq,
+                                       char* out_wqual, int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,8 @@ ISO_DIRECT, ISO_ASSIGNED, ISO_RARE, ISO_AMBIGUOUS = 0, 1, 2, 3  # IOC_ISO_*
 BLOCKS_MAX = 32                 # IOC_BLOCKS_MAX
 INS_LACK, INS_CARRY, INS_NONE = 0, 1, 3  # IOC_INS_*
 INSERTS_MAX, INS_SLACK_MAX = 32, 32      # IOC_INSERTS_MAX, IOC_INS_SLACK_MAX
+WIN_MAX = 512                            # IOC_WIN_MAX
+WIN_NONE, WIN_VOTER, WIN_SHORT, WIN_LONG = 0, 1, 2, 3  # IOC_WIN_*
 
 
 class BlockRow(C.Structure):  # ioc_block_row (8 bytes)
@@ -153,6 +155,10 @@ class ReadInserts(C.Structure):  # ioc_read_inserts (32 bytes)
 
 class InsertsSeg(C.Structure):  # ioc_inserts_seg (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("n_sites", "n_found", "n_groups", "n_reads", "n_direct", "n_assigned", "n_rare", "n_ambiguous")]
+
+
+class InsertWindow(C.Structure):  # ioc_insert_window (32 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("lo", "hi", "template_pair", "tlen")] + [(n, C.c_uint32) for n in ("n_voters", "n_short", "n_long", "reserved")]
 
 
 class SplitSeg(C.Structure):  # ioc_split_seg (32 bytes)
@@ -210,6 +216,7 @@ SYMBOLS = [
     "ioc_planes_polish_groups", "ioc_align_pairs_blocks_polish",
     "ioc_host_ops_project_weights", "ioc_host_planes_pile_weighted", "ioc_planes_polish_groups_weighted", "ioc_align_pairs_blocks_polish_weighted",
     "ioc_host_ops_project_ilen", "ioc_host_planes_inserts", "ioc_planes_inserts", "ioc_align_pairs_blocks_inserts",
+    "ioc_host_ops_project_qpos", "ioc_host_align_global_ops", "ioc_host_insert_windows", "ioc_planes_insert_windows", "ioc_align_pairs_blocks_inserts_seq",
 ]
 
 _lib = None
@@ -378,6 +385,15 @@ def load():
     L.ioc_planes_inserts.argtypes = [vp, i32, pi32, i32, pi32, C.c_void_p, C.c_void_p, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_blocks_inserts.argtypes = L.ioc_align_pairs_blocks.argtypes + [i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
+    L.ioc_host_ops_project_qpos.argtypes = [C.c_char_p, i64, i32, C.c_void_p]
+    L.ioc_host_align_global_ops.argtypes = [C.c_char_p, i32, C.c_char_p, i32, i32, i32, i32, C.c_void_p, i64, pi32]
+    L.ioc_host_align_global_ops.restype = C.c_int64
+    L.ioc_host_insert_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, i32, i32, C.c_void_p, i32, C.c_void_p, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+    L.ioc_planes_insert_windows.argtypes = [vp, i32, pi32, i32, pi32, pi32, C.c_void_p, C.c_void_p, C.c_void_p, pi64, C.c_void_p, i32, i32, i32, i32, i32, i32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_align_pairs_blocks_inserts_seq.argtypes = L.ioc_align_pairs_blocks_inserts.argtypes + [i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, i64,
+                                                                                                 pi64, C.c_void_p]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

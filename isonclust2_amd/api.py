@@ -436,6 +436,67 @@ def planes_inserts(base, ilen, pre_key=None, pre_mask=None, pre_full=0, rows=Tru
     return out
 
 
+def ops_project_qpos(ops, rlen):
+    """ioc_host_ops_project_qpos: where every row of the reference lies in the read — a uint32 array of rlen + 1 words: qpos[0] = 0,
+    qpos[r] the bytes of "=XIi" up to and including the byte that consumes row r - 1, so that the run of 'I' in front of row r
+    begins at query[qpos[r]].  ValueError for what ops_project_ilen refuses."""
+    qpos = np.full(int(rlen) + 1, 0xEEEEEEEE, np.uint32)
+    rc = _lib.load().ioc_host_ops_project_qpos(bytes(ops), len(ops), int(rlen), qpos.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_project_qpos failed ({rc})")
+    return qpos
+
+
+# ioc_insert_window as a numpy record, and what a window call is run with where nothing else is said: the insert stage's slack, the
+# aligner's match and mismatch, and a gap that costs what a mismatch does
+INSERT_WINDOW_DTYPE = np.dtype([(n, np.int32) for n in ("lo", "hi", "template_pair", "tlen")] + [(n, np.uint32) for n in ("n_voters", "n_short", "n_long", "reserved")])
+WIN_MAX = _lib.WIN_MAX
+WIN_NONE, WIN_VOTER, WIN_SHORT, WIN_LONG = _lib.WIN_NONE, _lib.WIN_VOTER, _lib.WIN_SHORT, _lib.WIN_LONG
+WINDOWS_RULE = dict(slack=INSERTS_RULE["slack"], max_win=WIN_MAX, match=2, mismatch=-2, gap=2)
+
+
+def align_global_ops(query, ref, match=2, mismatch=-2, gap=2):
+    """ioc_host_align_global_ops: the global alignment of two short strings, both ends anchored, linear gaps — (ops, score), ops the
+    bytes "=XID" in forward order.  The walk prefers the diagonal, then 'D' (a reference base alone), then 'I': the tie order is
+    part of the definition.  IocError for a negative gap, a parameter above 2^20 and strings of more than 2^26 cells."""
+    query, ref = bytes(query), bytes(ref)
+    ops, score = np.zeros(max(len(query) + len(ref), 1), np.uint8), C.c_int32(0)
+    n = _lib.load().ioc_host_align_global_ops(query, len(query), ref, len(ref), int(match), int(mismatch), int(gap), ops.ctypes.data, len(query) + len(ref),
+                                              C.byref(score))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_align_global_ops")
+    return ops[:n].tobytes(), int(score.value)
+
+
+def insert_windows_bound(n_sites, max_win=WIN_MAX):
+    """What the windows of n_sites sites may call at most, in bytes of sequence (and of qualities): n_sites (7 max_win + 6).  For the
+    fused call n_sites is the sum over the segments of planes_inserts_bound(rlen, max_sites): known before the call."""
+    return int(n_sites) * pileup_call_bound(int(max_win))
+
+
+def insert_windows(base, qpos, qlen, sites, keys, slack=WINDOWS_RULE["slack"], max_win=WIN_MAX):
+    """ioc_host_insert_windows: the windows of one segment's carriers at its kept sites — `base` / `qpos` the reads' base planes and
+    position planes (n_reads x (rlen + 1)), qlen the reads' lengths, `sites` and `keys` as planes_inserts returned them.  Returns a
+    dict: `win` (INSERT_WINDOW_DTYPE per site; template_pair is the read), `cls` (n_reads x n_sites bytes, WIN_*), `start` and `len`
+    (where a voter's window begins in its read and how long it is)."""
+    base, qpos = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(qpos, np.uint32)
+    if base.ndim != 2 or base.shape[1] < 1 or qpos.shape != base.shape:
+        raise ValueError("base and qpos must hold n_reads x (rlen + 1) entries each")
+    n, rlen = base.shape[0], base.shape[1] - 1
+    ql, ky, st = np.ascontiguousarray(qlen, np.int32), np.ascontiguousarray(keys, np.uint64), np.ascontiguousarray(sites, PILE_INSERT_DTYPE)
+    if ql.shape != (n,) or ky.shape != (n,) or st.ndim != 1:
+        raise ValueError("qlen and keys must hold one entry per read")
+    S = len(st)
+    win = np.zeros(max(S, 1), INSERT_WINDOW_DTYPE)
+    cls, start, ln = np.zeros((n, S), np.uint8), np.zeros((n, S), np.uint32), np.zeros((n, S), np.uint32)
+    rc = _lib.load().ioc_host_insert_windows(base.ctypes.data if n else None, qpos.ctypes.data if n else None, ql.ctypes.data if n else None, n, rlen,
+                                             st.ctypes.data if S else None, S, ky.ctypes.data if n else None, int(slack), int(max_win), win.ctypes.data,
+                                             cls.ctypes.data if cls.size else None, start.ctypes.data if cls.size else None, ln.ctypes.data if cls.size else None)
+    if rc < 0:
+        raise IocError(int(rc), "ioc_host_insert_windows")
+    return {"win": win[:S], "cls": cls, "start": start, "len": ln}
+
+
 def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
     """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
     returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
@@ -1162,6 +1223,101 @@ class Context:
                                                         ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None))
         out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
                "inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg)}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out.update(cols=cols, row0=self._row0(rlen))
+        return out
+
+    @staticmethod
+    def _windows_dict(win, seq, qual, off, pol):
+        S = len(win)
+        return {"win": win, "seq": [seq[off[x]:off[x + 1]].tobytes() for x in range(S)], "qual": [qual[off[x]:off[x + 1]].tobytes() for x in range(S)],
+                "off": off, "polish": pol}
+
+    def planes_insert_windows(self, rlen, seg_of_pair, query, base, qpos, sites, keys, min_depth=3, tables=False, cap=None, site_off=None, **rule):
+        """ioc_planes_insert_windows: the consensus of the carriers' windows at every kept insertion site, on the device, over the pool
+        that is set — `rlen` the segments' lengths, seg_of_pair and `query` (the pool sequence that is its read) per pair, `base` /
+        `qpos` a list per pair of what ops_project / ops_project_qpos give, `sites` a PILE_INSERT_DTYPE array per segment and `keys`
+        per pair as planes_inserts returned them (site_off: in place of the offsets the arrays give, with `sites` packed); slack,
+        max_win, match, mismatch and gap as keywords (WINDOWS_RULE has the defaults).  Returns a dict, a site each in site order: `win`
+        (INSERT_WINDOW_DTYPE; template_pair is the pair), `seq` and `qual` (bytes; empty where a site has no voter), `off`, `polish`
+        (POLISH_STATS_DTYPE) and, with tables=True, `cols`, `ins` and `row0` (site x's tlen + 1 rows begin at row0[x]) — each site as
+        pileup_call defines it on the tables planes_pile adds up from its voters' alignments to the template."""
+        unknown = set(rule) - set(WINDOWS_RULE)
+        if unknown:
+            raise TypeError(f"unknown rule parameters: {sorted(unknown)}")
+        r = [int({**WINDOWS_RULE, **rule}[n]) for n in WINDOWS_RULE]
+        ns, n = len(rlen), len(base)
+        rl, sop, qy, ky = (np.ascontiguousarray(x, t) for x, t in ((rlen, np.int32), (seg_of_pair, np.int32), (query, np.int32), (keys, np.uint64)))
+        if sop.shape != (n,) or qy.shape != (n,) or ky.shape != (n,) or len(qpos) != n:
+            raise ValueError("seg_of_pair, query, keys, base and qpos must hold one entry per pair")
+        want = [int(rl[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (want[i],) or np.shape(qpos[i]) != (want[i],):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        fq = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint32)] + [np.asarray(b, np.uint32) for b in qpos]))
+        if site_off is None:
+            soff = np.concatenate([[0], np.cumsum([len(s) for s in sites])]).astype(np.int64)
+            st = np.ascontiguousarray(np.concatenate([np.zeros(0, PILE_INSERT_DTYPE)] + [np.asarray(s, PILE_INSERT_DTYPE) for s in sites]))
+        else:
+            soff, st = np.ascontiguousarray(site_off, np.int64), np.ascontiguousarray(sites, PILE_INSERT_DTYPE)
+        if soff.shape != (ns + 1,):
+            raise ValueError("the sites must hold one array per segment")
+        S = max(int(soff[-1]), 0)
+        cap = insert_windows_bound(S, r[1]) if cap is None else int(cap)
+        win, off, pol = np.zeros(max(S, 1), INSERT_WINDOW_DTYPE), np.zeros(S + 1, np.int64), np.zeros(max(S, 1), POLISH_STATS_DTYPE)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        n_rows = S * (max(r[1], 0) + 1)
+        cols, ins = (np.zeros(max(n_rows, 1), PILEUP_DTYPE), np.zeros(max(n_rows, 1), PILEUP_INS_DTYPE)) if tables else (None, None)
+        pad = lambda a: np.concatenate([a, np.zeros(1, a.dtype)])  # (never an empty array's pointer)
+        st, ky, qy, sop, fb, fq = (pad(x) for x in (st, ky, qy, sop, fb, fq))
+        self._chk(self.L.ioc_planes_insert_windows(self.h, ns, _p(rl, C.c_int32) if ns else None, n, _p(sop, C.c_int32), _p(qy, C.c_int32), fb.ctypes.data,
+                                                   fq.ctypes.data, st.ctypes.data, _p(soff, C.c_int64), ky.ctypes.data, r[0], r[1], r[2], r[3], r[4],
+                                                   int(min_depth), win.ctypes.data, seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64),
+                                                   pol.ctypes.data, cols.ctypes.data if tables else None, ins.ctypes.data if tables else None))
+        out = self._windows_dict(win[:S], seq, qual, off, pol[:S])
+        if tables:
+            per = win[:S]["tlen"].astype(np.int64) + (win[:S]["tlen"] > 0)
+            row0 = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+            out.update(cols=cols[:row0[-1]], ins=ins[:row0[-1]], row0=row0)
+        return out
+
+    def align_pairs_blocks_inserts_seq(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, sites_cap=None, win_cap=None, match=2,
+                                       mismatch=-2, gap_extend=1, min_ins=INSERTS_RULE["min_ins"], slack=INSERTS_RULE["slack"],
+                                       max_sites=INSERTS_RULE["max_sites"], max_win=WIN_MAX, win_match=WINDOWS_RULE["match"],
+                                       win_mismatch=WINDOWS_RULE["mismatch"], win_gap=WINDOWS_RULE["gap"], polish_min_depth=3, **rule):
+        """ioc_align_pairs_blocks_inserts_seq: align_pairs_blocks_inserts with every pair's position plane projected as well and the
+        window kernels behind the insert kernels, on the device, every pair aligned once.  Returns align_pairs_blocks_inserts' dict,
+        byte for byte, and under `insert_windows` what Context.planes_insert_windows returns (without tables) for the sites kept."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        r = _blocks_rule(rule)
+        ir = [int(min_ins), int(slack), r[1], r[2], r[3], int(max_sites)]
+        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
+        (itab, sites, soff, iseg), sites_cap = self._inserts_out(ns, rlen, ir, rows, sites_cap)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        reads, ireads = np.zeros(n, READ_BLOCKS_DTYPE), np.zeros(n, READ_INSERTS_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        S = sum(planes_inserts_bound(m, ir[5]) for m in rlen)
+        win_cap = insert_windows_bound(S, max_win) if win_cap is None else int(win_cap)
+        wrec, woff, wpol = np.zeros(max(S, 1), INSERT_WINDOW_DTYPE), np.zeros(S + 1, np.int64), np.zeros(max(S, 1), POLISH_STATS_DTYPE)
+        wseq, wqual = np.zeros(max(win_cap, 1), np.uint8), np.zeros(max(win_cap, 1), np.uint8)
+        self._chk(self.L.ioc_align_pairs_blocks_inserts_seq(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+                                                            _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
+                                                            _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
+                                                            cols.ctypes.data if tables and n_rows else None, ir[0], ir[1], ir[5],
+                                                            itab.ctypes.data if rows and len(itab) else None, sites.ctypes.data, sites_cap, _p(soff, C.c_int64),
+                                                            ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None, int(max_win), int(win_match),
+                                                            int(win_mismatch), int(win_gap), int(polish_min_depth), wrec.ctypes.data, wseq.ctypes.data,
+                                                            wqual.ctypes.data, win_cap, _p(woff, C.c_int64), wpol.ctypes.data))
+        kept = int(soff[ns]) if ns else 0
+        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
+               "inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg),
+               "insert_windows": self._windows_dict(wrec[:kept], wseq, wqual, woff[:kept + 1], wpol[:kept])}
         if stats:
             out["stats"] = st
         if tables:

@@ -60,7 +60,8 @@ void print_dump_help()
          << "                    [--isoforms [--isoforms-min-gap N] [--isoforms-min-depth N] [--isoforms-min-alt N] [--isoforms-min-pct P]" << endl
          << "                     [--isoforms-min-block N] [--isoforms-max N]" << endl
          << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N] [--isoforms-polish-weighted]]" << endl
-         << "                     [--isoforms-inserts [--isoforms-min-ins N] [--isoforms-ins-slack N] [--isoforms-ins-max N]]] final.cer" << endl
+         << "                     [--isoforms-inserts [--isoforms-min-ins N] [--isoforms-ins-slack N] [--isoforms-ins-max N]" << endl
+         << "                     [--isoforms-inserts-seq [--isoforms-inserts-max-win N]]]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -138,8 +139,13 @@ void print_dump_help()
          << "                 longest insertion of the carriers; a '#' line where a cluster's list was cut), and per read its signature at the" << endl
          << "                 sites ('=' lack, '+' carry, '.' not across), its isoform counted over blocks AND sites together (or '.') and how" << endl
          << "                 it got it, as in read_isoforms.tsv.  The three files of --isoforms stay what they are.  The sequence of an" << endl
-         << "                 inserted exon is not written: with a carrier as the representative the exon is a block.  Not offered together" << endl
-         << "                 with --isoforms-polish: the isoforms' consensus is called over the blocks alone" << endl
+         << "                 inserted exon: --isoforms-inserts-seq.  Not offered together with --isoforms-polish: the isoforms' consensus" << endl
+         << "                 is called over the blocks alone" << endl
+         << "  --isoforms-inserts-seq  with --isoforms-inserts: also write outdir/cluster_inserts.fq, from the same alignments: per site that has a" << endl
+         << "                 voter a record \"cluster_<id>/ins<b> rows=<lo>-<hi> voters=<n> template=<read>\", the consensus of what the carriers" << endl
+         << "                 hold between rows lo and hi of the representative (the site widened by --isoforms-ins-slack, in the orientation the" << endl
+         << "                 reads were aligned in), to stand in place of those rows.  All carriers of a site vote together" << endl
+         << "  --isoforms-inserts-max-win N  a carrier votes where its stretch between the two rows has at most N bases, 1 .. 512 (default 512)" << endl
          << "  --isoforms-min-ins N    a read carries an insertion at a junction where the bases it inserts within --isoforms-ins-slack junctions" << endl
          << "                 sum to at least N, 1 .. 255 (default 20: a choice that was not measured on real data)" << endl
          << "  --isoforms-ins-slack N  ... the junctions on either side that count, 0 .. 32 (default 8: at 8 % errors the aligner breaks a 40-base" << endl
@@ -169,7 +175,8 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms-polish-min-depth", required_argument, 0, 1029}, {"isoforms-polish-max", required_argument, 0, 1030},
                                        {"isoforms-polish-weighted", no_argument, 0, 1031}, {"isoforms-inserts", no_argument, 0, 1032},
                                        {"isoforms-min-ins", required_argument, 0, 1033}, {"isoforms-ins-slack", required_argument, 0, 1034},
-                                       {"isoforms-ins-max", required_argument, 0, 1035}, {0, 0, 0, 0}};
+                                       {"isoforms-ins-max", required_argument, 0, 1035}, {"isoforms-inserts-seq", no_argument, 0, 1036},
+                                       {"isoforms-inserts-max-win", required_argument, 0, 1037}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false, iso_polish = false;
@@ -216,6 +223,8 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1033: r.isoforms.min_ins = number("--isoforms-min-ins", optarg, 1, 255); break;
             case 1034: r.isoforms.ins_slack = number("--isoforms-ins-slack", optarg, 0, 32); break;
             case 1035: r.isoforms.ins_max = number("--isoforms-ins-max", optarg, 1, 32); break;
+            case 1036: r.isoforms.inserts_seq = true; break;
+            case 1037: r.isoforms.ins_max_win = number("--isoforms-inserts-max-win", optarg, 1, IOC_WIN_MAX); break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -231,6 +240,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (iso_polish) r.isoforms.polish_min_depth = iso_polish_min_depth;
     if (r.isoforms.inserts && !r.isoforms.on) die("--isoforms-inserts asks for --isoforms!");
     if (r.isoforms.inserts && iso_polish) die("--isoforms-inserts is not offered together with --isoforms-polish!");
+    if (r.isoforms.inserts_seq && !r.isoforms.inserts) die("--isoforms-inserts-seq asks for --isoforms-inserts!");
     if (polish) r.polish_min_depth = polish_min_depth;
     if (d.index.empty()) die("Specifying the sorted read index is mandatory!");
     d.batch = argv[optind];
@@ -408,7 +418,8 @@ int main_dump(int argc, char** argv)
                              (reports.split.on ? "cluster_split.tsv, read_split.tsv, " : "") + (reports.group_polish() ? "cluster_split_polished.fq, " : "") +
                              (reports.correct.on ? "corrected_reads.fq, " : "") +
                              (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "") + (reports.iso_polish() ? "cluster_isoforms.fq, " : "") +
-                             (reports.isoforms.on && reports.isoforms.inserts ? "cluster_inserts.tsv, read_inserts.tsv, " : "");
+                             (reports.isoforms.on && reports.isoforms.inserts ? "cluster_inserts.tsv, read_inserts.tsv, " : "") +
+                             (reports.isoforms.on && reports.isoforms.inserts && reports.isoforms.inserts_seq ? "cluster_inserts.fq, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

@@ -132,6 +132,10 @@ struct GroupResult {
     std::vector<int64_t> insert_off;
     std::vector<ioc_inserts_seg> inserts_seg;
     std::vector<ioc_read_inserts> read_inserts;
+    std::vector<ioc_insert_window> ins_windows;  // (--isoforms-inserts-seq) per kept site, in the order of `inserts`: its record, and its consensus at
+    std::vector<int64_t> win_off;            // [win_off[s], win_off[s + 1]) of wseq / wqual
+    std::vector<ioc_polish_stats> win_stats;
+    string wseq, wqual;
 };
 
 // a row of the three per-read tables
@@ -269,6 +273,20 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
             const int64_t icap = inserts_capacity(g, io.ins_max);
             r.inserts.assign(size_t(std::max<int64_t>(icap, 1)), ioc_pile_insert{}), r.insert_off.assign(ns + 1, 0), r.inserts_seg.assign(ns, ioc_inserts_seg{});
             r.read_inserts.assign(np, ioc_read_inserts{});
+            if (io.inserts_seq) {
+                // (the scoring of the windows: the aligner's match and mismatch, a gap that costs what a mismatch does; the call at depth 3)
+                const int64_t wcap = icap * (7 * int64_t(io.ins_max_win) + 6);
+                r.ins_windows.assign(size_t(std::max<int64_t>(icap, 1)), ioc_insert_window{}), r.win_off.assign(size_t(icap) + 1, 0);
+                r.win_stats.assign(size_t(std::max<int64_t>(icap, 1)), ioc_polish_stats{});
+                r.wseq.assign(size_t(std::max<int64_t>(wcap, 1)), '\0'), r.wqual.assign(size_t(std::max<int64_t>(wcap, 1)), '\0');
+                check(c, ioc_align_pairs_blocks_inserts_seq(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
+                                                            g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
+                                                            r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
+                                                            o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
+                                                            r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(), io.ins_max_win,
+                                                            2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(), r.win_stats.data()),
+                      "exon blocks with the insertion sites and their sequences");
+            } else
             check(c, ioc_align_pairs_blocks_inserts(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
                                                     g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
                                                     r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
@@ -450,9 +468,31 @@ void write_inserts(std::ofstream& out, const ReportGroup& g, const GroupResult& 
     }
 }
 
+// cluster_inserts.fq: a record per called site, "@cluster_<id>/ins<b> rows=<lo>-<hi> voters=<n> template=<read>" — the consensus of
+// what the voters hold between rows lo and hi of the representative, to stand in place of those rows
+void write_insert_windows(std::ofstream& out, const ReportRows& rows, const ReportGroup& g, const GroupResult& r)
+{
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0) continue;
+        for (int64_t a = r.insert_off[size_t(s)]; a < r.insert_off[size_t(s) + 1]; ++a) {
+            const ioc_insert_window& w = r.ins_windows[size_t(a)];
+            const int64_t b0 = r.win_off[size_t(a)], b1 = r.win_off[size_t(a) + 1];
+            if (w.tlen <= 0 || b1 <= b0 || w.template_pair < 0 || size_t(w.template_pair) >= g.pair_row.size()) continue;
+            const ReadStatRow& rd = rows.row(g.pair_row[size_t(w.template_pair)]);
+            out << "@cluster_" << g.group_cls[x].first << "/ins" << a - r.insert_off[size_t(s)] << " rows=" << w.lo << '-' << w.hi << " voters=" << w.n_voters
+                << " template=" << string(rd.id, rd.id_len) << '\n';
+            out.write(r.wseq.data() + b0, std::streamsize(b1 - b0));
+            out << "\n+\n";
+            out.write(r.wqual.data() + b0, std::streamsize(b1 - b0));
+            out << '\n';
+        }
+    }
+}
+
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -479,9 +519,10 @@ struct GroupFiles {
         if (o.isoforms.on && o.isoforms.inserts) {
             create_file(outdir + "/cluster_inserts.tsv", inserts);
             inserts << "ClusterId\tFirst\tEnd\tCarry\tLack\tNone\tLenMin\tLenMax\n";
+            if (o.isoforms.inserts_seq) create_file(outdir + "/cluster_inserts.fq", inserts_fq);
         }
     }
-    void write(const Batch& b, const ReportOpts& o, const ReportGroup& g, const GroupResult& r)
+    void write(const Batch& b, const ReportOpts& o, const ReportRows& rows, const ReportGroup& g, const GroupResult& r)
     {
         if (o.pileup) write_pileup(pileup, b, g, r);
         if (o.polish()) write_polish(polish, b, g, r, o.polish_weighted);
@@ -490,6 +531,7 @@ struct GroupFiles {
         if (o.group_polish() && !g.segs.empty()) write_group_polish(group_polish, g, r);
         if (o.isoforms.on && !g.segs.empty()) write_blocks(blocks, isoforms, o.iso_polish() ? &iso_fq : nullptr, g, r);
         if (o.isoforms.on && o.isoforms.inserts && !g.segs.empty()) write_inserts(inserts, g, r);
+        if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && !g.segs.empty() && !g.pairs.empty()) write_insert_windows(inserts_fq, rows, g, r);
     }
 };
 
@@ -586,7 +628,7 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
             align_group(c, k, opts, g, result);
             scatter_to_rows(opts, rows, g, result, res);
         }
-        if (opts.groups()) files.write(b, opts, g, result);
+        if (opts.groups()) files.write(b, opts, rows, g, result);
     });
     if (c) ioc_ctx_destroy(c);
     if (opts.sites.on) write_read_alleles(outdir, rows, res);

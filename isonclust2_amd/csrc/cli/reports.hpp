@@ -33,6 +33,8 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     bool polish_weighted = false;  // --isoforms-polish-weighted: every isoform is called by weight (ioc_align_pairs_blocks_polish_weighted)
     bool inserts = false;                            // --isoforms-inserts: the insertion sites as well (ioc_align_pairs_blocks_inserts), and ...
     int min_ins = 20, ins_slack = 8, ins_max = 32;   // ... the thresholds of ioc_host_planes_inserts the block search does not share
+    bool inserts_seq = false;                        // --isoforms-inserts-seq: the consensus of the carriers' windows at every kept site as well
+    int ins_max_win = IOC_WIN_MAX;                   // (ioc_align_pairs_blocks_inserts_seq), and the longest window that votes
 };
 struct ReportOpts {
     bool stats = false;        // --read-stats

@@ -22,6 +22,7 @@
 #include "ioc_pile_sites.h"
 #include "ioc_read_blocks.h"
 #include "ioc_read_inserts.h"
+#include "ioc_insert_windows.h"
 #include "ioc_read_correct.h"
 #include "ioc_site_split.h"
 
@@ -909,6 +910,102 @@ int ioc_host_planes_inserts(const uint8_t* base, const uint8_t* ilen, int32_t n_
     std::copy(sites.begin(), sites.end(), out_sites);
     std::copy(reads.begin(), reads.end(), out_reads);
     *out_seg = seg;
+    return IOC_OK;
+}
+
+// The position part of a read's projection (isonclust2_hip.h has the rules): where every row lies in the read, a 32-bit word each —
+// the definition k_ops_project_qpos (ioc_insert_windows.hip) is tested against.  The walk of ioc_host_ops_project_ilen.
+int ioc_host_ops_project_qpos(const char* ops, int64_t len, int32_t rlen, uint32_t* qpos)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || rlen < 0 || !qpos) return IOC_ERR_ARG;
+    int64_t r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+    }
+    if (r != rlen) return IOC_ERR_ARG;
+    std::fill(qpos, qpos + size_t(rlen) + 1, 0u);
+    uint32_t q = 0;
+    r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        q += op == '=' || op == 'X' || op == 'I' || op == 'i';
+        if (op == '=' || op == 'X' || op == 'D' || op == 'd') qpos[++r] = q;
+    }
+    return IOC_OK;
+}
+
+// The global alignment of two short strings with linear gaps (isonclust2_hip.h has the rules; win_dir and win_max3,
+// ioc_insert_windows.h, decide for this function and for k_win_align alike): the whole matrix, then the walk.
+int64_t ioc_host_align_global_ops(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match, int32_t mismatch, int32_t gap, char* ops,
+                                  int64_t cap, int32_t* out_score)
+{
+    if (qlen < 0 || rlen < 0 || !WinRule::score_ok(match, mismatch, gap) || (qlen > 0 && !query) || (rlen > 0 && !ref) || cap < 0 || (cap > 0 && !ops))
+        return IOC_ERR_ARG;
+    if (cap < int64_t(qlen) + rlen || (int64_t(qlen) + 1) * (int64_t(rlen) + 1) > (int64_t(1) << 26)) return IOC_ERR_CAPACITY;
+    const size_t W = size_t(rlen) + 1;
+    std::vector<int32_t> H((size_t(qlen) + 1) * W);
+    for (size_t j = 0; j < W; ++j) H[j] = -int32_t(j) * gap;
+    for (int32_t i = 1; i <= qlen; ++i) {
+        H[size_t(i) * W] = -i * gap;
+        for (int32_t j = 1; j <= rlen; ++j)
+            H[size_t(i) * W + size_t(j)] = win_max3(H[size_t(i - 1) * W + size_t(j - 1)] + (query[i - 1] == ref[j - 1] ? match : mismatch),
+                                                    H[size_t(i) * W + size_t(j - 1)] - gap, H[size_t(i - 1) * W + size_t(j)] - gap);
+    }
+    std::string back;
+    for (int32_t i = qlen, j = rlen; i > 0 || j > 0;) {
+        uint32_t d = i == 0 ? uint32_t(WIN_D) : uint32_t(WIN_I);
+        if (i > 0 && j > 0)
+            d = win_dir(H[size_t(i - 1) * W + size_t(j - 1)] + (query[i - 1] == ref[j - 1] ? match : mismatch), H[size_t(i) * W + size_t(j - 1)] - gap,
+                        H[size_t(i - 1) * W + size_t(j)] - gap);
+        if (d == WIN_DIAG)
+            back.push_back(query[i - 1] == ref[j - 1] ? '=' : 'X'), --i, --j;
+        else if (d == WIN_D)
+            back.push_back('D'), --j;
+        else
+            back.push_back('I'), --i;
+    }
+    std::copy(back.rbegin(), back.rend(), ops);
+    if (out_score) *out_score = H[size_t(qlen) * W + size_t(rlen)];
+    return int64_t(back.size());
+}
+
+// The windows of one segment's carriers at its kept sites (isonclust2_hip.h has the rules; win_lo, win_hi, win_class, win_voter_less
+// and win_median_rank, ioc_insert_windows.h, decide for this function and for the kernels of ioc_insert_windows.hip alike).
+int ioc_host_insert_windows(const uint8_t* base, const uint32_t* qpos, const int32_t* qlen, int32_t n_reads, int32_t rlen, const ioc_pile_insert* sites,
+                            int32_t n_sites, const uint64_t* keys, int32_t slack, int32_t max_win, ioc_insert_window* out_win, uint8_t* out_class,
+                            uint32_t* out_start, uint32_t* out_len)
+{
+    const WinRule rule{slack, max_win, 0, 0, 0};
+    if (!rule.bounds_ok() || n_reads < 0 || rlen < 0 || n_sites < 0 || n_sites > IOC_INSERTS_MAX || (n_sites > 0 && (!sites || !out_win)) ||
+        (n_reads > 0 && n_sites > 0 && (!base || !qpos || !qlen || !keys)) || !out_start != !out_len)
+        return IOC_ERR_ARG;
+    for (int32_t k = 0; k < n_sites; ++k)
+        if (!win_site_ok(sites[k].first, sites[k].end, rlen)) return IOC_ERR_ARG;
+    for (int32_t i = 0; i < n_reads && n_sites > 0; ++i)
+        if (qlen[i] < 0) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1, n = size_t(n_reads), S = size_t(n_sites);
+    for (size_t k = 0; k < S; ++k) {
+        const long long lo = win_lo(sites[k].first, slack), hi = win_hi(sites[k].end, slack, rlen);
+        ioc_insert_window w{int32_t(lo), int32_t(hi), -1, 0, 0, 0, 0, 0};
+        std::vector<std::pair<uint32_t, uint32_t>> voters;  // (window length, read)
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t len = 0;
+            const uint32_t cls = win_class(uint32_t(keys[i] >> (2 * k)) & 3u, base[i * rows + size_t(lo) - 1], base[i * rows + size_t(hi) - 1],
+                                           qpos[i * rows + size_t(lo)], qpos[i * rows + size_t(hi)], uint32_t(qlen[i]), max_win, &len);
+            w.n_voters += cls == IOC_WIN_VOTER, w.n_short += cls == IOC_WIN_SHORT, w.n_long += cls == IOC_WIN_LONG;
+            if (cls == IOC_WIN_VOTER) voters.push_back({len, uint32_t(i)});
+            if (out_class) out_class[i * S + k] = uint8_t(cls);
+            if (out_start) out_start[i * S + k] = cls == IOC_WIN_VOTER ? qpos[i * rows + size_t(lo)] : 0u, out_len[i * S + k] = len;
+        }
+        if (!voters.empty()) {
+            std::sort(voters.begin(), voters.end(), [](const auto& a, const auto& b) { return win_voter_less(a.first, a.second, b.first, b.second); });
+            const auto& t = voters[win_median_rank(uint32_t(voters.size()))];
+            w.template_pair = int32_t(t.second), w.tlen = int32_t(t.first);
+        }
+        out_win[k] = w;
+    }
     return IOC_OK;
 }
 

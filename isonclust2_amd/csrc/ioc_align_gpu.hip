@@ -1261,6 +1261,15 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
                                          uint64_t(pl.plane_bytes)));
         IOC_CHK(c, hipEventRecord(ev.v.back(), c->stream));
     }
+    size_t ev_qpos = 0;
+    if (h.projects_qpos()) {  // (likewise: its own event, behind whatever the calls that exist record)
+        ev.v.push_back(nullptr);
+        IOC_CHK(c, hipEventCreate(&ev.v.back()));
+        ev_qpos = ev.v.size() - 1;
+        IOC_CHK(c, iock_ops_project_qpos(c->stream, o.dev.buf, o.dev.end, o.dev.len, o.d_room, d_ord, cnt, o.d_row_base, o.d_plane, pl.qpos_planes,
+                                         uint64_t(pl.plane_bytes)));
+        IOC_CHK(c, hipEventRecord(ev.v.back(), c->stream));
+    }
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     o.len.resize(dp.size());
@@ -1284,6 +1293,7 @@ int ops_fetch_reduced(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, 
     if (h.projects_ins() && hipEventElapsedTime(&ms, ev.v[3], ev.v[4]) == hipSuccess) t.ms_project_ins += double(ms);
     if (h.projects_weights() && hipEventElapsedTime(&ms, ev.v[4], ev.v[5]) == hipSuccess) t.ms_project_weights += double(ms);
     if (h.projects_ilen() && hipEventElapsedTime(&ms, ev.v[5], ev.v[6]) == hipSuccess) t.ms_project_ilen += double(ms);
+    if (h.projects_qpos() && hipEventElapsedTime(&ms, ev.v[ev_qpos - 1], ev.v[ev_qpos]) == hipSuccess) t.ms_project_qpos += double(ms);
     t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t.copied += int64_t(dp.size() * 4 + (stats ? size_t(cnt) * sizeof(ioc_aln_stats) : 0));
     if (stats) t.records += int64_t(cnt);

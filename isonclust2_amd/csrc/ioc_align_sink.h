@@ -33,6 +33,9 @@ struct AlnTally {
     double ms_blocks = 0;       // the eight kernels of ioc_read_blocks.hip, their device time together (ioc_planes_blocks, ioc_align_pairs_blocks)
     double ms_project_ilen = 0; // k_ops_project_ilen's device time (a pile that projects the length plane as well), and ...
     double ms_inserts[8] = {};  // ... the eight kernels of ioc_read_inserts.hip, in the order they run (ioc_planes_inserts, ioc_align_pairs_blocks_inserts)
+    double ms_project_qpos = 0; // k_ops_project_qpos' device time (a pile that projects the position plane as well), and ...
+    double ms_win_walk = 0;     // (IOC_WIN_SPLIT: k_win_align's walk on its own; ms_windows[2] is the fill then)
+    double ms_windows[4] = {};  // ... k_win_bounds, k_win_template, k_win_align and k_group_pile over the sites (ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
     int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };
@@ -161,6 +164,10 @@ struct AlnSink {
         // (k_ops_project_ilen), into reference length + 1 bytes of one more plane from byte plane[i] on
         bool project_ilen = false;
         uint8_t* ilen_planes = nullptr;  // (device) plane_bytes
+        // optional, with project (project_qpos): where every row lies in the pair's query is projected too (k_ops_project_qpos),
+        // into reference length + 1 words of a plane of 32-bit words from word plane[i] on
+        bool project_qpos = false;
+        uint32_t* qpos_planes = nullptr;  // (device) plane_bytes words
     } pile;
 
     bool reduced() const { return kind == SinkKind::reduced; }
@@ -170,9 +177,10 @@ struct AlnSink {
     bool projects_ins() const { return projects() && pile.project_ins; }
     bool projects_weights() const { return projects_ins() && pile.project_weights; }
     bool projects_ilen() const { return projects() && pile.project_ilen; }
-    uint64_t planes() const
+    bool projects_qpos() const { return projects() && pile.project_qpos; }
+    uint64_t planes() const  // (in bytes per row and pair: a position plane counts four)
     {
-        const uint64_t ilen = pile.project && pile.project_ilen ? 1 : 0;
+        const uint64_t ilen = (pile.project && pile.project_ilen ? 1 : 0) + (pile.project && pile.project_qpos ? 4 : 0);
         return ilen + (!pile.project ? 0 : !pile.project_ins ? 2 : 2 + uint64_t(IOC_PILE_INS_SLOTS) + (pile.project_weights ? 1 + uint64_t(IOC_PILE_INS_SLOTS) : 0));
     }
     // what the tables hold of the device for the whole call (ck_budget's `held`)

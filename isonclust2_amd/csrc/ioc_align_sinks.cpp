@@ -20,6 +20,7 @@
 #include "ioc_read_blocks.h"
 #include "ioc_read_correct.h"
 #include "ioc_read_inserts.h"
+#include "ioc_insert_windows.h"
 
 namespace {
 struct AlnCall {  // what every aligning entry point passes on
@@ -106,6 +107,7 @@ struct PiledDev {  // pile: the tables of the kind (a_pile; a_pile_ins or a_pile
     ioc_pileup_ins *ins, *wins;
     uint8_t *base, *insf, *slots, *weights;
     uint8_t* ilen = nullptr;  // (a pile that projects the length plane: behind every other plane)
+    uint32_t* qpos = nullptr;  // (a pile that projects the position plane: behind the length plane, at a multiple of 16 bytes)
 };
 struct BlocksDev {  // blocks (a_blocks): where the block stage left every pair's record (its key) and its mask
     const ioc_read_blocks* reads;
@@ -187,7 +189,7 @@ struct SinkRun {
         return IOC_OK;
     }
     int pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane, int64_t plane_bytes, bool project_ins, PiledDev& d,
-             bool project_weights = false, bool project_ilen = false);
+             bool project_weights = false, bool project_ilen = false, bool project_qpos = false);
     int sites(const SitesRule& r, const SinkPlan& p, const ioc_pileup_col* d_cols, ioc_pile_site* out_sites, int64_t* site_off, int64_t* n_found, SitesDev& d);
     int alleles(const SitesDev& d, const SinkPlan& p, const int32_t* seg_of_pair, const PiledDev& planes, const int64_t* site_off, int64_t* allele_off, uint8_t* out_alleles);
     int split(const SplitCall& sp, size_t n, size_t np, const int32_t* seg_of_pair, const int64_t* site_off, const int64_t* allele_off, const ioc_pile_site* sites,
@@ -208,8 +210,9 @@ struct SinkRun {
 // project_ins, [slot planes x 6] behind them, set to IOC_ALLELE_NONE / 0 once here; with project_weights (which asks for project_ins
 // and for the pool's qualities), [weight planes x 7] behind those, set to 0 with them.  A call without project_weights reserves what
 // it always did.  project_ilen: one more plane behind all of those, the length plane (k_ops_project_ilen), set to 0 with them.
+// project_qpos: behind that, from the next multiple of 16 bytes on, the position plane (k_ops_project_qpos), four bytes a row, set to 0.
 int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane,
-                  int64_t plane_bytes, bool project_ins, PiledDev& d, bool project_weights, bool project_ilen)
+                  int64_t plane_bytes, bool project_ins, PiledDev& d, bool project_weights, bool project_ilen, bool project_qpos)
 {
     IOC_CHK(c, hipSetDevice(c->device));
     const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
@@ -228,20 +231,23 @@ int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, con
     if (plane) {
         const size_t b_plane = size_t(plane_bytes);
         const size_t n_zeroed = !project_ins ? 1 : 1 + size_t(IOC_PILE_INS_SLOTS) + (project_weights ? size_t(IOC_WEIGHT_PLANES) : 0);  // (the ins planes and on)
-        IOC_TRY(ioc_reserve(c, c->a_planes, (1 + n_zeroed + (project_ilen ? 1 : 0)) * b_plane));
+        const size_t b_bytes = (1 + n_zeroed + (project_ilen ? 1 : 0)) * b_plane, o_qpos = (b_bytes + 15) & ~size_t(15);
+        IOC_TRY(ioc_reserve(c, c->a_planes, project_qpos ? o_qpos + 4 * b_plane : b_bytes));
         pl.project = true, pl.base_planes = c->a_planes.as<uint8_t>(), pl.ins_planes = pl.base_planes + b_plane;
         pl.plane_bytes = plane_bytes, pl.plane = plane;
         if (project_ins) pl.project_ins = true, pl.slot_planes = pl.base_planes + 2 * b_plane;
         if (project_ins && project_weights) pl.project_weights = true, pl.weight_planes = pl.slot_planes + size_t(IOC_PILE_INS_SLOTS) * b_plane;
         if (project_ilen) pl.project_ilen = true, pl.ilen_planes = pl.base_planes + (1 + n_zeroed) * b_plane;
+        if (project_qpos) pl.project_qpos = true, pl.qpos_planes = reinterpret_cast<uint32_t*>(pl.base_planes + o_qpos);
         if (b_plane > 0) {
             IOC_CHK(c, hipMemsetAsync(pl.base_planes, IOC_ALLELE_NONE, b_plane, c->stream));
             IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, (n_zeroed + (project_ilen ? 1 : 0)) * b_plane, c->stream));  // (and the slot, weight and length planes)
+            if (project_qpos) IOC_CHK(c, hipMemsetAsync(pl.qpos_planes, 0, 4 * b_plane, c->stream));
         }
     }
     const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, out_stats != nullptr, out_stats, pl};
     IOC_TRY(a.run(c, a.n_pairs > 0 ? &sink : nullptr));
-    d = PiledDev{pl.cols, pl.wcols, pl.ins, pl.wins, pl.base_planes, pl.ins_planes, pl.slot_planes, pl.weight_planes, pl.ilen_planes};
+    d = PiledDev{pl.cols, pl.wcols, pl.ins, pl.wins, pl.base_planes, pl.ins_planes, pl.slot_planes, pl.weight_planes, pl.ilen_planes, pl.qpos_planes};
     return IOC_OK;
 }
 
@@ -1388,6 +1394,293 @@ int ioc_align_pairs_blocks_inserts(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pa
                 n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[n_segs], double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_pileup,
                 r.t.ms_project, r.t.ms_project_ilen, r.t.ms_blocks, inserts_trace(r.t).c_str(),
                 out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+// ---- the sequence of an inserted exon: the windows of the carriers at every kept site ----
+namespace {
+struct WindowsOut {  // the rule of a window call and where it leaves what it made (call.cap: what seq and qual hold each; call.off: sites + 1 entries)
+    WinRule rule;
+    CallOut call;
+    ioc_insert_window* win;
+    ioc_pileup_col* cols;
+    ioc_pileup_ins* ins;
+    bool ok() const { return rule.ok() && call.ok() && !cols == !ins; }
+};
+// the pairs' reads in the pool: where each begins and how long it is
+struct WindowsReads {
+    std::vector<int64_t> off;
+    std::vector<uint32_t> len;
+};
+constexpr uint64_t WIN_DIR_WORDS_MOST = uint64_t(1) << 25;  // the direction words of one launch of k_win_align: 128 MB, 2048 alignments of 512 x 512
+
+// what a window call refuses about its sites and its room: IOC_OK, or the status with the message set
+static int windows_ok(ioc_ctx* c, const std::string& who, const WindowsOut& o, const SinkPlan& p, const ioc_pile_insert* sites, const int64_t* site_off, int64_t n_sites_most)
+{
+    const size_t n = p.segs.size();
+    if (site_off) {  // (the sites are the caller's: ioc_planes_insert_windows)
+        if (site_off[0] != 0) return ioc_fail(c, IOC_ERR_ARG, who + ": site_off does not begin at 0");
+        for (size_t g = 0; g < n; ++g) {
+            if (site_off[g + 1] < site_off[g] || site_off[g + 1] - site_off[g] > IOC_INSERTS_MAX)
+                return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " has a negative number of sites or more than 32");
+            for (int64_t x = site_off[g]; x < site_off[g + 1]; ++x)
+                if (!sites || !win_site_ok(sites[x].first, sites[x].end, p.segs[g].rlen))
+                    return ioc_fail(c, IOC_ERR_ARG, who + ": site " + std::to_string(x) + " does not lie inside its segment");
+        }
+        n_sites_most = site_off[n];
+    }
+    const int64_t bound = n_sites_most * pile_call_most(o.rule.max_win);
+    if (o.call.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": cap " + std::to_string(o.call.cap) + " below the bound " + std::to_string(bound));
+    return n_sites_most > 0 && (!o.win || !o.call.stats || !o.call.seq || !o.call.qual) ? IOC_ERR_ARG : IOC_OK;
+}
+
+// bounds -> template -> [the host lists the voters] -> align -> group pile -> call -> copy-out.  The planes lie on the device (dev_*)
+// or are the host's and uploaded; sites, site_off and keys are the host's.  a_windows holds the tables [segments][seg_of_pair][plane
+// offsets][read lengths][member lists][sites][site_off][site_seg][keys], the (pair, site) entries and the records and, uploaded, the
+// planes.  The records and the entries come back; the host lists every called site's voters in pair order — an alignment each, a group
+// of k_group_pile per site — and a_gpile holds [items][group-segments][work items][plane offsets][gmem_off][gmembers][base plane]
+// [slot planes][gcols][gins][direction words], the direction words of at most WIN_DIR_WORDS_MOST a launch.
+static int windows_device(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_pair, const WindowsReads& reads, const uint8_t* host_base, const uint32_t* host_qpos,
+                   const uint8_t* dev_base, const uint32_t* dev_qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys,
+                   const WindowsOut& o)
+{
+    ioc_ctx* const c = r.c;
+    const size_t n = pn.segs.size(), np = pn.plane.size(), B = size_t(pn.plane_bytes), ns = size_t(site_off[n]);
+    for (size_t x = 0; x <= ns; ++x) o.call.off[x] = 0;
+    for (size_t x = 0; x < ns; ++x) o.call.stats[x] = ioc_polish_stats{};
+    if (ns == 0) return IOC_OK;
+    const MemberLists m = member_lists(n, np, seg_of_pair);
+    std::vector<int32_t> site_seg(ns);
+    size_t stride = 1;
+    for (size_t g = 0; g < n; ++g) {
+        std::fill(site_seg.begin() + site_off[g], site_seg.begin() + site_off[g + 1], int32_t(g));
+        stride = std::max(stride, size_t(site_off[g + 1] - site_off[g]));
+    }
+    Arena l;
+    const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_plane = l.take(np * 8), o_qlen = l.take(np * 4), o_moff = l.take((n + 1) * 4),
+                 o_mem = l.take(np * 4), o_sites = l.take(ns * sizeof(ioc_pile_insert)), o_soff = l.take((n + 1) * 8), o_sseg = l.take(ns * 4),
+                 o_keys = l.take(np * 8), tables = l.size();
+    const size_t o_slots = l.take(np * stride * sizeof(IocWinSlot)), o_win = l.take(ns * sizeof(ioc_insert_window)), o_end = l.size(),
+                 o_base = l.take(dev_base ? 0 : B), o_qpos = l.take(dev_qpos ? 0 : 4 * B);
+    std::vector<uint8_t> stage(tables, 0);
+    auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
+    put(o_seg, pn.segs.data(), n * sizeof(IocPileSeg)), put(o_sop, seg_of_pair, np * 4), put(o_plane, pn.plane.data(), np * 8), put(o_qlen, reads.len.data(), np * 4);
+    put(o_moff, m.mem_off.data(), (n + 1) * 4), put(o_mem, m.members.data(), np * 4), put(o_sites, sites, ns * sizeof(ioc_pile_insert));
+    put(o_soff, site_off, (n + 1) * 8), put(o_sseg, site_seg.data(), ns * 4), put(o_keys, keys, np * 8);
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_windows, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_windows.p);
+    IOC_CHK(c, hipMemcpyAsync(p, stage.data(), tables, hipMemcpyHostToDevice, c->stream));
+    if (!dev_base && B) IOC_CHK(c, hipMemcpyAsync(p + o_base, host_base, B, hipMemcpyHostToDevice, c->stream));
+    if (!dev_qpos && B) IOC_CHK(c, hipMemcpyAsync(p + o_qpos, host_qpos, 4 * B, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemsetAsync(p + o_slots, 0, o_end - o_slots, c->stream));  // (the entries and the records)
+    const IocWinDev v{reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop),
+                      reinterpret_cast<const uint64_t*>(p + o_plane), dev_base ? dev_base : p + o_base,
+                      dev_qpos ? dev_qpos : reinterpret_cast<const uint32_t*>(p + o_qpos), uint64_t(B), reinterpret_cast<const uint32_t*>(p + o_qlen),
+                      reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem), reinterpret_cast<const ioc_pile_insert*>(p + o_sites),
+                      reinterpret_cast<const int64_t*>(p + o_soff), reinterpret_cast<const int32_t*>(p + o_sseg), uint32_t(ns),
+                      reinterpret_cast<const unsigned long long*>(p + o_keys), reinterpret_cast<IocWinSlot*>(p + o_slots), uint32_t(stride), uint64_t(np * stride),
+                      reinterpret_cast<ioc_insert_window*>(p + o_win)};
+    EventSet each;
+    if (getenv("IOC_TRACE")) {
+        each.v.assign(3, nullptr);
+        for (auto& e : each.v) IOC_CHK(c, hipEventCreate(&e));
+    }
+    IOC_TRY(r.begin(r.t.ms_windows[0], each.v.empty()));
+    IOC_CHK(c, iock_win_bounds_template(c->stream, v, o.rule.slack, o.rule.max_win, each.v.empty() ? nullptr : each.v.data()));
+    IOC_TRY(r.end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    r.settled();
+    for (size_t x = 0; x + 1 < each.v.size(); ++x) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, each.v[x], each.v[x + 1]) == hipSuccess) r.t.ms_windows[x] += double(ms);
+    }
+    std::vector<ioc_insert_window> win(ns);
+    std::vector<IocWinSlot> slot(np * stride);
+    IOC_TRY(r.copy_out({{win.data(), p + o_win, ns * sizeof(ioc_insert_window)}, {slot.data(), p + o_slots, np * stride * sizeof(IocWinSlot)}}));
+
+    // every called site's voters, in pair order: an alignment each; the site is a group-segment of tlen + 1 rows
+    std::vector<IocPileSeg> gsegs;
+    std::vector<uint32_t> goff{0}, gmem;
+    std::vector<IocWinItem> items;
+    std::vector<uint64_t> vplane;
+    std::vector<IocGroupWork> work;
+    std::vector<size_t> called, launch{0};  // (launch: the first item of every launch of k_win_align, and the end)
+    int64_t rows = 0;
+    uint64_t P = 0, dir_at = 0, dir_most = 0;
+    auto voter = [&](size_t i, size_t k, uint32_t& start, uint32_t& len) {  // what the entry of pair i at site k says, held against the read
+        const IocWinSlot& s = slot[i * stride + k];
+        start = s.start, len = win_slot_len(s.cls_len);
+        return win_slot_class(s.cls_len) == uint32_t(IOC_WIN_VOTER) && len >= 1 && len <= uint32_t(o.rule.max_win) && uint64_t(start) + len <= reads.len[i];
+    };
+    for (size_t x = 0; x < ns; ++x) {
+        const size_t g = size_t(site_seg[x]), k = x - size_t(site_off[g]);
+        const ioc_insert_window& w = win[x];
+        if (w.tlen <= 0) continue;
+        uint32_t t_start = 0, t_len = 0;
+        if (w.template_pair < 0 || size_t(w.template_pair) >= np || size_t(seg_of_pair[w.template_pair]) != g || !voter(size_t(w.template_pair), k, t_start, t_len) ||
+            t_len != uint32_t(w.tlen))
+            return ioc_fail(c, IOC_ERR_HIP, "the window kernels returned a template that is no voter of its site");
+        const uint64_t t_off = uint64_t(reads.off[size_t(w.template_pair)]) + t_start;
+        for (uint32_t mi = m.mem_off[g]; mi < m.mem_off[g + 1]; ++mi) {
+            const size_t i = m.members[mi];
+            uint32_t start = 0, len = 0;
+            if (!voter(i, k, start, len)) continue;
+            const uint64_t words = win_dir_words(len, t_len);
+            if (dir_at + words > WIN_DIR_WORDS_MOST) launch.push_back(items.size()), dir_at = 0;
+            items.push_back(IocWinItem{uint64_t(reads.off[i]) + start, t_off, P, dir_at, len, t_len});
+            dir_at += words, dir_most = std::max(dir_most, dir_at);
+            vplane.push_back(P), gmem.push_back(uint32_t(items.size() - 1));
+            P += uint64_t(t_len) + 1;
+        }
+        for (int64_t row = 0; row <= int64_t(t_len); row += IOC_GROUP_PILE_ROWS) work.push_back(IocGroupWork{uint32_t(gsegs.size()), uint32_t(row)});
+        gsegs.push_back(IocPileSeg{rows, int64_t(t_off), int32_t(t_len), 0});
+        goff.push_back(uint32_t(gmem.size()));
+        rows += int64_t(t_len) + 1;
+        called.push_back(x);
+    }
+    launch.push_back(items.size());
+    std::copy(win.begin(), win.end(), o.win);
+    if (called.empty()) return IOC_OK;
+    if (items.size() > size_t(INT32_MAX) || P > (uint64_t(1) << 40)) return ioc_fail(c, IOC_ERR_CAPACITY, "the windows of the call have more than 2^31 - 1 voters");
+
+    const size_t G = gsegs.size(), M = items.size();
+    Arena a;
+    const size_t a_items = a.take(M * sizeof(IocWinItem)), a_gseg = a.take(G * sizeof(IocPileSeg)), a_work = a.take(work.size() * sizeof(IocGroupWork)),
+                 a_plane = a.take(M * 8), a_goff = a.take((G + 1) * 4), a_gmem = a.take(M * 4), a_base = a.take(size_t(P)),
+                 a_slots = a.take(size_t(IOC_PILE_INS_SLOTS) * size_t(P)), a_cols = a.take(size_t(rows) * sizeof(ioc_pileup_col)),
+                 a_ins = a.take(size_t(rows) * sizeof(ioc_pileup_ins)), a_dir = a.take(size_t(dir_most) * 4);
+    IOC_TRY(ioc_reserve(c, c->a_gpile, a.size()));
+    uint8_t* q = static_cast<uint8_t*>(c->a_gpile.p);
+    auto up = [&](size_t at, const void* src, size_t b) { return b ? hipMemcpyAsync(q + at, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(a_items, items.data(), M * sizeof(IocWinItem)));
+    IOC_CHK(c, up(a_gseg, gsegs.data(), G * sizeof(IocPileSeg)));
+    IOC_CHK(c, up(a_work, work.data(), work.size() * sizeof(IocGroupWork)));
+    IOC_CHK(c, up(a_plane, vplane.data(), M * 8));
+    IOC_CHK(c, up(a_goff, goff.data(), (G + 1) * 4));
+    IOC_CHK(c, up(a_gmem, gmem.data(), M * 4));
+    IOC_CHK(c, hipMemsetAsync(q + a_base, IOC_ALLELE_NONE, size_t(P), c->stream));
+    IOC_CHK(c, hipMemsetAsync(q + a_slots, 0, a_dir - a_slots, c->stream));  // (the slot planes and both tables)
+    const uint8_t* pool = static_cast<const uint8_t*>(c->a_pool.p);
+    const uint64_t pool_bytes = uint64_t(c->aln_offs.back());
+    // (IOC_TRACE with IOC_WIN_SPLIT, for the measurement: the fill and the walk of every launch as two launches, timed apart; the
+    // walk reads the words the fill left, so the planes are the same bytes)
+    const bool split = getenv("IOC_TRACE") && getenv("IOC_WIN_SPLIT");
+    for (size_t b = 0; b + 1 < launch.size(); ++b)
+        for (int ph = split ? 1 : 0; ph <= (split ? 2 : 0); ++ph) {  // (0: both halves in one launch; 1, 2: the fill, then the walk)
+            IOC_TRY(r.begin(ph == 2 ? r.t.ms_win_walk : r.t.ms_windows[2]));
+            IOC_CHK(c, iock_win_align(c->stream, reinterpret_cast<const IocWinItem*>(q + a_items) + launch[b], uint32_t(launch[b + 1] - launch[b]), pool, pool_bytes,
+                                      q + a_base, q + a_slots, P, reinterpret_cast<uint32_t*>(q + a_dir), dir_most, o.rule.match, o.rule.mismatch, o.rule.gap, ph));
+            IOC_TRY(r.end());
+        }
+    ioc_pileup_col* const d_cols = reinterpret_cast<ioc_pileup_col*>(q + a_cols);
+    ioc_pileup_ins* const d_ins = reinterpret_cast<ioc_pileup_ins*>(q + a_ins);
+    IOC_TRY(r.begin(r.t.ms_windows[3]));
+    IOC_CHK(c, iock_group_pile(c->stream, reinterpret_cast<const IocGroupWork*>(q + a_work), uint32_t(work.size()), reinterpret_cast<const IocPileSeg*>(q + a_gseg),
+                               uint32_t(G), reinterpret_cast<const uint32_t*>(q + a_goff), reinterpret_cast<const uint32_t*>(q + a_gmem), uint32_t(M), uint32_t(M),
+                               reinterpret_cast<const uint64_t*>(q + a_plane), q + a_base, q + a_slots, P, d_cols, d_ins, uint64_t(rows)));
+    IOC_TRY(r.end());
+    std::vector<int64_t> off(G + 1, 0);
+    std::vector<ioc_polish_stats> st(G);
+    const CallOut packed{o.call.min_depth, o.call.seq, o.call.qual, o.call.cap, off.data(), st.data()};  // (the called sites' bytes are all sites' bytes, packed)
+    IOC_TRY(pile_call_device(r, gsegs, pool, pool_bytes, packed, d_cols, d_ins, nullptr, rows));
+    for (size_t y = 0, x = 0; x < ns; ++x) {
+        const bool is = y < G && called[y] == x;
+        o.call.off[x + 1] = o.call.off[x] + (is ? off[y + 1] - off[y] : 0);
+        if (is) o.call.stats[x] = st[y++];
+    }
+    return r.copy_out({{o.cols, d_cols, size_t(rows) * sizeof(ioc_pileup_col)}, {o.ins, d_ins, size_t(rows) * sizeof(ioc_pileup_ins)}});
+}
+
+static std::string windows_trace(const AlnTally& t)
+{
+    char buf[240];
+    snprintf(buf, sizeof buf, "k_win_bounds %.3f ms, k_win_template %.3f ms, k_win_align %.3f ms, k_win_align_walk %.3f ms, k_win_group_pile %.3f ms, k_win_pile_call %.3f ms",
+             t.ms_windows[0], t.ms_windows[1], t.ms_windows[2], t.ms_win_walk, t.ms_windows[3], t.ms_call);
+    return buf;
+}
+}  // namespace
+
+// upload -> windows -> copy-out.  The windows from planes, sites and keys the caller holds, over the pool that is set.
+int ioc_planes_insert_windows(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* query, const uint8_t* base,
+                              const uint32_t* qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys, int32_t slack, int32_t max_win,
+                              int32_t match, int32_t mismatch, int32_t gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_seq, char* out_qual,
+                              int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats, ioc_pileup_col* out_cols, ioc_pileup_ins* out_ins)
+{
+    const std::string who = "ioc_planes_insert_windows";
+    const WindowsOut o{{slack, max_win, match, mismatch, gap}, {polish_min_depth, out_seq, out_qual, cap, out_off, out_stats}, out_win, out_cols, out_ins};
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || !site_off || (n_segs > 0 && !rlen) || (n_pairs > 0 && (!seg_of_pair || !query || !keys))) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen(who, n_segs, rlen, nullptr, nullptr, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !qpos)) return IOC_ERR_ARG;
+    WindowsReads reads;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        if (query[i] < 0 || size_t(query[i]) + 1 >= c->aln_offs.size()) return ioc_fail(c, IOC_ERR_ARG, who + ": the read of pair " + std::to_string(i) + " lies outside the pool");
+        reads.off.push_back(c->aln_offs[size_t(query[i])]), reads.len.push_back(uint32_t(ioc_seq_len(c, query[i])));
+    }
+    IOC_TRY(windows_ok(c, who, o, p, sites, site_off, 0));
+    SinkRun r{c};
+    IOC_TRY(windows_device(r, p, seg_of_pair, reads, base, qpos, nullptr, nullptr, sites, site_off, keys, o));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes insert windows: %d segments, %d pairs, %lld sites, %lld bytes called, %s\n", n_segs, n_pairs, (long long)site_off[n_segs],
+                (long long)out_off[site_off[n_segs]], windows_trace(r.t).c_str());
+    return IOC_OK;
+}
+
+// pile -> blocks -> inserts -> windows -> copy-out.  ioc_align_pairs_blocks_inserts with the position plane projected beside the other
+// two, and behind the insert kernels the window kernels over the planes where they lie; the sites and the keys are on the host when
+// the insert stage returns and travel back with the tables (32 bytes a site, 8 a pair).
+int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                       int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                       const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                       int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                       int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                       int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                       int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                       int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
+                                       int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats)
+{
+    const std::string who = "ioc_align_pairs_blocks_inserts_seq";
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
+    const InsertsOut io{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
+    const WindowsOut wo{{slack, max_win, win_match, win_mismatch, win_gap}, {polish_min_depth, out_wseq, out_wqual, win_cap, out_woff, out_wstats}, out_win, nullptr, nullptr};
+    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !io.ok() || !wo.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
+    IOC_TRY(blocks_room_ok(c, who, o, p));
+    IOC_TRY(inserts_room_ok(c, who, io, p));
+    IOC_TRY(windows_ok(c, who, wo, p, nullptr, nullptr, inserts_bound(p, max_sites)));
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    block_off[0] = 0, site_off[0] = 0, out_woff[0] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    SinkRun r{c};
+    PiledDev d;
+    BlocksDev bd{};
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d, /*project_weights*/ false,
+                   /*project_ilen*/ true, /*project_qpos*/ true));
+    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o, &bd));
+    std::vector<uint64_t> pre_full(size_t(n_segs), 0);
+    for (int32_t g = 0; g < n_segs; ++g) pre_full[size_t(g)] = blocks_full_mask(uint32_t(out_seg[g].n_blocks));
+    InsertsPre pre;
+    pre.pre_full = pre_full.data();
+    if (n_pairs > 0) {
+        pre.dev_key = reinterpret_cast<const unsigned long long*>(bd.reads), pre.dev_key_stride = uint32_t(sizeof(ioc_read_blocks) / 8);
+        pre.dev_mask = bd.mask, pre.dev_mask_stride = 1;
+    }
+    IOC_TRY(r.inserts(p, seg_of_pair, nullptr, nullptr, d.base, d.ilen, pre, io));
+    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));  // (before the window call: a_pile is the call stage's to take)
+    WindowsReads reads;
+    std::vector<uint64_t> keys(size_t(n_pairs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        reads.off.push_back(c->aln_offs[size_t(pairs[i].query)]), reads.len.push_back(uint32_t(ioc_seq_len(c, pairs[i].query)));
+        keys[size_t(i)] = out_ireads[i].key;
+    }
+    IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: blocks inserts seq: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_project_ilen %.3f ms, k_ops_project_qpos %.3f ms, ms_blocks %.3f ms, %s, %s\n",
+                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[n_segs], (long long)out_woff[site_off[n_segs]],
+                double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_project_ilen, r.t.ms_project_qpos, r.t.ms_blocks, inserts_trace(r.t).c_str(), windows_trace(r.t).c_str());
     return IOC_OK;
 }
 

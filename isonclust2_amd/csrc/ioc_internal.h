@@ -225,6 +225,9 @@ struct ioc_ctx {
     DevBuf a_correct; // ioc_planes_correct, ioc_align_pairs_correct: segments, pairs, offsets, records and the corrected bytes (ioc_read_correct.hip) and,
                       // from host planes, the uploaded planes
     DevBuf a_inserts; // ioc_planes_inserts, ioc_align_pairs_blocks_inserts: the tables, bit planes and records of ioc_read_inserts.hip and, uploaded, both planes
+    DevBuf a_windows; // ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq: the tables, the (pair, site) entries and the records of
+                      // k_win_bounds / k_win_template and, uploaded, both planes; the alignments' items, planes and direction words share a_gpile
+                      // with the group pile behind them
     DevBuf a_blocks;  // ioc_planes_blocks, ioc_align_pairs_blocks: segments, pairs, member lists, bit planes, tables and records (ioc_read_blocks.hip) and,
                       // from host planes, the uploaded planes
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
@@ -535,6 +538,46 @@ struct IocReadInsertsDev {
 enum { IOC_READ_INSERTS_KERNELS = 8 };  // (each: IOC_READ_INSERTS_KERNELS + 1 events, or NULL)
 hipError_t iock_read_inserts(hipStream_t st, const IocReadInsertsDev& v, int32_t min_ins, int32_t slack, int32_t min_depth, int32_t min_alt, int32_t min_pct,
                              int32_t max_sites, hipEvent_t* each);
+
+// ioc_insert_windows.hip: where every row of the same strings lies in the read, into one plane of 32-bit words of the pairs' own
+// (ioc_host_ops_project_qpos) — pair pid's from word plane[pid] on of qpos_planes, plane_rows words in all (set to 0 by the caller);
+// launched beside iock_ops_project — and the windows of the carriers at every kept insertion site (ioc_host_insert_windows per
+// segment).  Everything is a device pointer.  Segment g has the sites site_off[g] .. site_off[g + 1] of `sites` (n_sites in all;
+// site_seg says whose each is) and the pairs members[mem_off[g] .. mem_off[g + 1]); pair i has its read's length in qlen[i], its key
+// in keys[i] and the entry of site k of its segment at slots[i * stride + k], n_slots entries in all.
+hipError_t iock_ops_project_qpos(hipStream_t st, const uint8_t* buf, const uint64_t* end, const uint32_t* len, const uint32_t* room, const uint32_t* ord,
+                                 uint32_t cnt, const int64_t* row_base, const uint64_t* plane, uint32_t* qpos_planes, uint64_t plane_rows);
+struct IocWinSlot;
+struct IocWinItem;
+struct IocWinDev {
+    const IocPileSeg* segs;
+    uint32_t n_segs, n_pairs;
+    const int32_t* seg_of_pair;
+    const uint64_t* plane;
+    const uint8_t* base_planes;
+    const uint32_t* qpos_planes;
+    uint64_t plane_rows;
+    const uint32_t* qlen;
+    const uint32_t *mem_off, *members;
+    const ioc_pile_insert* sites;
+    const int64_t* site_off;
+    const int32_t* site_seg;
+    uint32_t n_sites;
+    const unsigned long long* keys;
+    IocWinSlot* slots;
+    uint32_t stride;
+    uint64_t n_slots;
+    ioc_insert_window* win;
+};
+// k_win_bounds and k_win_template over the view, in a row on `st`; `each` (3 events, or NULL) as for iock_read_inserts
+hipError_t iock_win_bounds_template(hipStream_t st, const IocWinDev& v, int32_t slack, int32_t max_win, hipEvent_t* each);
+// k_win_align over items[0 .. n_items): both strings in `pool`, the voters' planes (plane_bytes each: the base plane set to
+// IOC_ALLELE_NONE, the six slot planes one behind the other set to 0 by the caller) and the direction words (n_dir_words of them
+// from `dir` on, from which an item's offsets count).  phase: 0 both halves, 1 the fill alone, 2 the walk alone (over the words a
+// fill left), for the measurement.
+hipError_t iock_win_align(hipStream_t st, const IocWinItem* items, uint32_t n_items, const uint8_t* pool, uint64_t pool_bytes, uint8_t* base_planes,
+                          uint8_t* slot_planes, uint64_t plane_bytes, uint32_t* dir, uint64_t n_dir_words, int32_t match, int32_t mismatch, int32_t gap,
+                          int phase);
 
 // ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
 // is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in
