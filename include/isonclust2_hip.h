@@ -1395,6 +1395,100 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* ctx, int32_t n_pairs, const ioc_
                                        int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq,
                                        char* out_wqual, int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats);
 
+/* ---- The full-length sequence of a combined isoform: the windows of the exons it carries spliced into its consensus ----
+ * ioc_host_pileup_call calls an isoform in the representative's frame, where an exon the representative lacks is six slot bases at
+ * most; the window stage returns that exon's consensus beside the anchor rows lo and hi it stands between.  The splice puts the two
+ * together, for ONE isoform of one segment:
+ *   cols / ins, frame, rlen, min_depth: the isoform's tables (ioc_host_planes_pile of its reads) and what ioc_host_pileup_call takes;
+ *   key: the insert key of its direct reads (ioc_read_inserts.key), state at site b = (key >> 2 b) & 3;
+ *   win: the records of the segment's n_sites kept sites (lo, hi and tlen are read), n_sites in 0 .. IOC_INSERTS_MAX;
+ *   win_seq / win_qual / win_off: the sites' called windows, site b's bytes at win_off[b] .. win_off[b + 1] (n_sites + 1 entries).
+ *  1. The sites in ascending order.  Site b is IOC_SPLICE_LACK where the key's state at b is not IOC_INS_CARRY; else
+ *     IOC_SPLICE_UNCALLED where tlen == 0; else IOC_SPLICE_OVERLAP where lo is below the hi of the last DONE site of this isoform
+ *     (the windows of sites closer than 2 slack overlap; the earlier one wins); else IOC_SPLICE_DONE.
+ *  2. The output is ioc_host_pileup_call's walk over p = 0 .. rlen, except that for every DONE site the insertions in front of rows
+ *     lo .. hi - 1 and the bases of rows lo .. hi - 1 are neither emitted nor counted in the record, and in their place, at row lo,
+ *     stand the window's sequence and qualities as they are: the window is "the insertions at junctions lo .. hi - 1 and the read's
+ *     bases on rows lo .. hi - 1".  The insertions in front of row hi come from the tables as always.
+ *  3. An isoform with no DONE site is ioc_host_pileup_call byte for byte, record included.
+ * st (may be NULL): n_sub, n_del, n_ins and n_low over the rows that were called, out_len everything written, windows included.
+ * out_sites (n_sites records): the state, and for a DONE site where its window's bytes begin in the isoform's sequence and how many
+ * they are, -1 and 0 otherwise.  out_sstats (may be NULL): rows_replaced is the sum of hi - lo and spliced_bytes of len over the DONE
+ * sites.  Returns the length written.  IOC_ERR_ARG for what ioc_host_pileup_call refuses, n_sites outside 0 .. IOC_INSERTS_MAX, a
+ * record outside 1 <= lo < hi <= rlen or with tlen < 0, a win_off that does not ascend and a NULL pointer that is needed;
+ * IOC_ERR_CAPACITY for cap below rlen + IOC_PILE_INS_SLOTS * (rlen + 1) + win_off[n_sites] - win_off[0]; nothing is written on any. */
+#define IOC_SPLICE_LACK 0
+#define IOC_SPLICE_DONE 1
+#define IOC_SPLICE_UNCALLED 2
+#define IOC_SPLICE_OVERLAP 3
+typedef struct {
+    int32_t state;                /* IOC_SPLICE_* */
+    int32_t at, len;              /* DONE: the window's first byte in the isoform's sequence and its length; else -1 and 0 */
+    int32_t reserved;
+} ioc_splice_site;                /* 16 bytes */
+typedef struct {
+    int32_t n_done, n_uncalled, n_overlap;
+    int32_t rows_replaced, spliced_bytes;
+    int32_t reserved[3];
+} ioc_splice_stats;               /* 32 bytes */
+int64_t ioc_host_isoform_splice(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth,
+                                uint64_t key, const ioc_insert_window* win, int32_t n_sites, const char* win_seq, const char* win_qual,
+                                const int64_t* win_off, char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st,
+                                ioc_splice_site* out_sites, ioc_splice_stats* out_sstats);
+/* Every isoform of many segments at once on the device, from host planes laid out as for ioc_planes_polish_groups (rlen, frames,
+ * frame_off, n_groups, seg_of_pair, group, base, slots as there; G group-segments in segment order).  iso_key: a key per
+ * group-segment; win: the segments' window records packed with site_off (n_segs + 1 entries, at most IOC_INSERTS_MAX a segment);
+ * win_seq / win_qual packed with win_off (site_off[n_segs] + 1 entries), all as ioc_planes_insert_windows returns them.
+ * Group-segment (g, h) is ioc_host_isoform_splice over the tables ioc_host_planes_pile makes of its pairs, iso_key of (g, h) and
+ * the sites of g.  k_group_pile adds the planes up; then the kernels of ioc_iso_splice.hip: k_splice_plan (a wave per
+ * group-segment, a lane per site: the states, the site records and a list of at most 32 intervals), k_splice_call in a count
+ * pass, the scan of the call kernels, and k_splice_call in a write pass (a workgroup per group-segment, a lane per row; a window's
+ * bytes are copied by the whole workgroup).  No atomics: every byte has one writer and its place is a function of the tables and
+ * the plan.  out_seq / out_qual packed with out_off (G + 1 entries); out_polish and out_sstats (may be NULL) G records each;
+ * out_splice packed with splice_off (G + 1 entries): group-segment (g, h) has a record per kept site of g; out_gcols / out_gins
+ * (optional) the group tables as from ioc_planes_polish_groups.  IOC_ERR_ARG, with nothing written, for what
+ * ioc_planes_polish_groups and the definition refuse, site_off or win_off that does not ascend from 0, a segment with more than
+ * IOC_INSERTS_MAX sites and a NULL pointer that is needed; IOC_ERR_CAPACITY, with nothing written, for cap below the sum over g of
+ * n_groups[g] * (the call's bound of segment g + the bytes of g's windows), for a group-segment whose bound exceeds 2^31 - 1 and for
+ * splice_cap below the sum over g of n_groups[g] * the sites of g. */
+int ioc_planes_isoforms_full(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                             const int32_t* n_groups, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base,
+                             const uint8_t* slots, const uint64_t* iso_key, const ioc_insert_window* win, const int64_t* site_off,
+                             const char* win_seq, const char* win_qual, const int64_t* win_off, int32_t min_depth, char* out_seq,
+                             char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats,
+                             ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off, ioc_pileup_col* out_gcols,
+                             ioc_pileup_ins* out_gins);
+/* ioc_align_pairs_blocks_inserts_seq with the six slot planes projected beside base, length and position (13 bytes per row and pair,
+ * which count against the checkpoint arena's budget; the calls that exist reserve what they always did), behind the window kernels
+ * k_group_pile over the COMBINED isoforms (ioc_read_inserts.group: the first min(n_groups, max_iso) of a segment, each from its
+ * direct and assigned reads as ioc_align_pairs_blocks_polish takes them), and then the splice kernels: isoform h of segment g is
+ * ioc_host_isoform_splice over its tables, the key of its lowest-numbered direct read (all direct reads of a group carry the same
+ * key) and the windows of g the same call just made, the frame being g's representative as the pairs were aligned against it.
+ * polish_min_depth serves the windows and the isoforms.  Everything ioc_align_pairs_blocks_inserts_seq returns comes back byte for
+ * byte; added are iso_off (n_segs + 1 entries: segment g's group-segments are iso_off[g] .. iso_off[g + 1]) and, indexed by
+ * group-segment, out_seq / out_qual with out_off, out_polish, out_sstats (either may be NULL) and out_splice with splice_off, as
+ * ioc_planes_isoforms_full returns them.  The room is known before the call: iso_cap at least the sum over g of k_g = min(max_iso,
+ * reads of g) — out_off and splice_off hold iso_cap + 1 entries —, splice_cap the sum of k_g * s_g with s_g = min(max_sites,
+ * max(rlen_g - 1, 0)), and cap the sum of k_g * (the call's bound of rlen_g + s_g * (7 max_win + 6)).  That is 3590 bytes a site at
+ * max_win 512 and 32 sites a segment where nothing is known; a caller who knows its data keeps it small with max_sites (a cluster
+ * seldom has more than a few insertion sites), with max_win (the longest exon expected plus 2 slack + 1 rows) and with batches of
+ * segments.  Every pair is aligned, piled and projected exactly once.  The refusals of ioc_align_pairs_blocks_inserts_seq;
+ * IOC_ERR_ARG for max_iso < 1, a negative cap, splice_cap or iso_cap and a NULL pointer that is needed; IOC_ERR_CAPACITY for iso_cap,
+ * splice_cap or cap below its bound and for an isoform whose bound exceeds 2^31 - 1; nothing is written on any of them. */
+int ioc_align_pairs_isoforms_full(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                  int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                  int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                                  int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                                  ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                                  ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins, int32_t slack, int32_t max_sites,
+                                  ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap, int64_t* site_off,
+                                  ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                  int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq,
+                                  char* out_wqual, int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t max_iso,
+                                  char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
+                                  ioc_splice_stats* out_sstats, ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off,
+                                  int64_t iso_cap, int64_t* iso_off);
+
 #ifdef __cplusplus
 }
 #endif

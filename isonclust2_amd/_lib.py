@@ -123,6 +123,7 @@ INS_LACK, INS_CARRY, INS_NONE = 0, 1, 3  # IOC_INS_*
 INSERTS_MAX, INS_SLACK_MAX = 32, 32      # IOC_INSERTS_MAX, IOC_INS_SLACK_MAX
 WIN_MAX = 512                            # IOC_WIN_MAX
 WIN_NONE, WIN_VOTER, WIN_SHORT, WIN_LONG = 0, 1, 2, 3  # IOC_WIN_*
+SPLICE_LACK, SPLICE_DONE, SPLICE_UNCALLED, SPLICE_OVERLAP = 0, 1, 2, 3  # IOC_SPLICE_*
 
 
 class BlockRow(C.Structure):  # ioc_block_row (8 bytes)
@@ -159,6 +160,14 @@ class InsertsSeg(C.Structure):  # ioc_inserts_seg (32 bytes)
 
 class InsertWindow(C.Structure):  # ioc_insert_window (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("lo", "hi", "template_pair", "tlen")] + [(n, C.c_uint32) for n in ("n_voters", "n_short", "n_long", "reserved")]
+
+
+class SpliceSite(C.Structure):  # ioc_splice_site (16 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("state", "at", "len", "reserved")]
+
+
+class SpliceStats(C.Structure):  # ioc_splice_stats (32 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("n_done", "n_uncalled", "n_overlap", "rows_replaced", "spliced_bytes")] + [("reserved", C.c_int32 * 3)]
 
 
 class SplitSeg(C.Structure):  # ioc_split_seg (32 bytes)
@@ -217,6 +226,7 @@ SYMBOLS = [
     "ioc_host_ops_project_weights", "ioc_host_planes_pile_weighted", "ioc_planes_polish_groups_weighted", "ioc_align_pairs_blocks_polish_weighted",
     "ioc_host_ops_project_ilen", "ioc_host_planes_inserts", "ioc_planes_inserts", "ioc_align_pairs_blocks_inserts",
     "ioc_host_ops_project_qpos", "ioc_host_align_global_ops", "ioc_host_insert_windows", "ioc_planes_insert_windows", "ioc_align_pairs_blocks_inserts_seq",
+    "ioc_host_isoform_splice", "ioc_planes_isoforms_full", "ioc_align_pairs_isoforms_full",
 ]
 
 _lib = None
@@ -394,6 +404,14 @@ def load():
                                             C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_blocks_inserts_seq.argtypes = L.ioc_align_pairs_blocks_inserts.argtypes + [i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, i64,
                                                                                                  pi64, C.c_void_p]
+    L.ioc_host_isoform_splice.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, i32, i32, C.c_uint64, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, i64, C.POINTER(PolishStats), C.c_void_p, C.POINTER(SpliceStats)]
+    L.ioc_host_isoform_splice.restype = C.c_int64
+    L.ioc_planes_isoforms_full.argtypes = [vp, i32, pi32, C.c_char_p, pi64, pi32, i32, pi32, pi32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, pi64, C.c_void_p,
+                                           C.c_void_p, pi64, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p,
+                                           C.c_void_p]
+    L.ioc_align_pairs_isoforms_full.argtypes = L.ioc_align_pairs_blocks_inserts_seq.argtypes + [i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p,
+                                                                                               C.c_void_p, i64, pi64, i64, pi64]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

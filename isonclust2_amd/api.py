@@ -497,6 +497,55 @@ def insert_windows(base, qpos, qlen, sites, keys, slack=WINDOWS_RULE["slack"], m
     return {"win": win[:S], "cls": cls, "start": start, "len": ln}
 
 
+# ioc_splice_site / ioc_splice_stats as numpy records
+SPLICE_SITE_DTYPE = np.dtype([(n, np.int32) for n in ("state", "at", "len", "reserved")])
+SPLICE_STATS_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.SpliceStats._fields_[:-1]] + [("reserved", np.int32, (3,))])
+SPLICE_STATS_FIELDS = tuple(n for n, _ in _lib.SpliceStats._fields_[:-1])
+SPLICE_LACK, SPLICE_DONE, SPLICE_UNCALLED, SPLICE_OVERLAP = _lib.SPLICE_LACK, _lib.SPLICE_DONE, _lib.SPLICE_UNCALLED, _lib.SPLICE_OVERLAP
+
+
+def isoform_splice_bound(rlen, win_bytes):
+    """What the full-length sequence of one isoform may hold at most: the call's bound of its segment plus the bytes of the segment's
+    windows."""
+    return pileup_call_bound(rlen) + int(win_bytes)
+
+
+def isoforms_full_bound(rlen, n_reads, max_iso, max_sites=INSERTS_RULE["max_sites"], max_win=WIN_MAX):
+    """What the fused call may write, known before it runs — (bytes of sequence, group-segments, site records) over segments of rlen[g]
+    bases and n_reads[g] reads: an isoform of segment g holds at most the call's bound plus min(max_sites, max(rlen - 1, 0)) windows of
+    7 max_win + 6 bytes each.  A caller keeps it small with max_sites and max_win as the data allow, and with batches of segments."""
+    iso = [min(int(max_iso), int(m)) for m in n_reads]
+    sites = [planes_inserts_bound(m, max_sites) for m in rlen]
+    return (sum(k * isoform_splice_bound(m, s * pileup_call_bound(max_win)) for k, m, s in zip(iso, rlen, sites)), sum(iso),
+            sum(k * s for k, s in zip(iso, sites)))
+
+
+def isoform_splice(cols, ins, frame, key, win, win_seq, min_depth=3, cap=None):
+    """ioc_host_isoform_splice: the full-length sequence of one isoform — pileup_call over its tables with, for every site its key
+    carries (`key`: the insert key of its direct reads), the site's called window in place of the rows [lo, hi) it stands for.  `win`:
+    the segment's INSERT_WINDOW_DTYPE records; win_seq: a (sequence, qualities) pair of bytes per site.  Returns (sequence,
+    qualities, stats, sites, sstats): stats a dict of POLISH_STATS_FIELDS, sites a SPLICE_SITE_DTYPE array (state, and for a DONE site
+    where its window begins in the sequence and how long it is), sstats a dict of SPLICE_STATS_FIELDS.  IocError for what the
+    definition refuses."""
+    rlen = len(frame)
+    cols, ins = _tables(cols, ins, rlen + 1)
+    w = np.ascontiguousarray(win, INSERT_WINDOW_DTYPE)
+    S = len(w)
+    if len(win_seq) != S or any(len(s) != len(q) for s, q in win_seq):
+        raise ValueError("win_seq must hold a (sequence, qualities) pair of equal lengths per site")
+    woff = np.concatenate([[0], np.cumsum([len(s) for s, _ in win_seq])]).astype(np.int64)
+    wseq, wqual = b"".join(bytes(s) for s, _ in win_seq), b"".join(bytes(q) for _, q in win_seq)
+    cap = isoform_splice_bound(rlen, woff[-1]) if cap is None else int(cap)
+    seq, qual, st, ss = C.create_string_buffer(max(cap, 1)), C.create_string_buffer(max(cap, 1)), _lib.PolishStats(), _lib.SpliceStats()
+    rec = np.full(max(S, 1), -7, SPLICE_SITE_DTYPE)
+    n = _lib.load().ioc_host_isoform_splice(cols.ctypes.data, ins.ctypes.data, bytes(frame), rlen, int(min_depth), int(key), w.ctypes.data if S else None, S,
+                                            wseq, wqual, woff.ctypes.data, seq, qual, cap, C.byref(st), rec.ctypes.data, C.byref(ss))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_isoform_splice")
+    return (seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in POLISH_STATS_FIELDS}, rec[:S],
+            {f: int(getattr(ss, f)) for f in SPLICE_STATS_FIELDS})
+
+
 def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
     """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
     returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
@@ -1287,7 +1336,7 @@ class Context:
     def align_pairs_blocks_inserts_seq(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, sites_cap=None, win_cap=None, match=2,
                                        mismatch=-2, gap_extend=1, min_ins=INSERTS_RULE["min_ins"], slack=INSERTS_RULE["slack"],
                                        max_sites=INSERTS_RULE["max_sites"], max_win=WIN_MAX, win_match=WINDOWS_RULE["match"],
-                                       win_mismatch=WINDOWS_RULE["mismatch"], win_gap=WINDOWS_RULE["gap"], polish_min_depth=3, **rule):
+                                       win_mismatch=WINDOWS_RULE["mismatch"], win_gap=WINDOWS_RULE["gap"], polish_min_depth=3, _full=None, **rule):
         """ioc_align_pairs_blocks_inserts_seq: align_pairs_blocks_inserts with every pair's position plane projected as well and the
         window kernels behind the insert kernels, on the device, every pair aligned once.  Returns align_pairs_blocks_inserts' dict,
         byte for byte, and under `insert_windows` what Context.planes_insert_windows returns (without tables) for the sites kept."""
@@ -1306,23 +1355,48 @@ class Context:
         win_cap = insert_windows_bound(S, max_win) if win_cap is None else int(win_cap)
         wrec, woff, wpol = np.zeros(max(S, 1), INSERT_WINDOW_DTYPE), np.zeros(S + 1, np.int64), np.zeros(max(S, 1), POLISH_STATS_DTYPE)
         wseq, wqual = np.zeros(max(win_cap, 1), np.uint8), np.zeros(max(win_cap, 1), np.uint8)
-        self._chk(self.L.ioc_align_pairs_blocks_inserts_seq(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+        entry, more = self.L.ioc_align_pairs_blocks_inserts_seq, ()
+        if _full is not None:   # (align_pairs_isoforms_full: the same call with the isoforms' outputs behind it)
+            n_reads = np.bincount(sop[(sop >= 0) & (sop < ns)], minlength=ns) if n else np.zeros(ns, np.int64)
+            fb = isoforms_full_bound(rlen, n_reads, _full["max_iso"], ir[5], max_win)
+            f_cap, f_iso, f_rec = (fb[x] if _full[c] is None else int(_full[c]) for x, c in enumerate(("cap", "iso_cap", "splice_cap")))
+            f_seq, f_qual = np.zeros(max(f_cap, 1), np.uint8), np.zeros(max(f_cap, 1), np.uint8)
+            f_off, f_spoff, f_ioff = np.zeros(max(f_iso, 0) + 1, np.int64), np.zeros(max(f_iso, 0) + 1, np.int64), np.zeros(ns + 1, np.int64)
+            f_pol, f_sst = np.zeros(max(f_iso, 1), POLISH_STATS_DTYPE), np.zeros(max(f_iso, 1), SPLICE_STATS_DTYPE)
+            f_splice = np.zeros(max(f_rec, 1), SPLICE_SITE_DTYPE)
+            entry = self.L.ioc_align_pairs_isoforms_full
+            more = (int(_full["max_iso"]), f_seq.ctypes.data, f_qual.ctypes.data, f_cap, _p(f_off, C.c_int64), f_pol.ctypes.data, f_sst.ctypes.data,
+                    f_splice.ctypes.data, f_rec, _p(f_spoff, C.c_int64), f_iso, _p(f_ioff, C.c_int64))
+        self._chk(entry(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
                                                             _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
                                                             _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
                                                             cols.ctypes.data if tables and n_rows else None, ir[0], ir[1], ir[5],
                                                             itab.ctypes.data if rows and len(itab) else None, sites.ctypes.data, sites_cap, _p(soff, C.c_int64),
                                                             ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None, int(max_win), int(win_match),
                                                             int(win_mismatch), int(win_gap), int(polish_min_depth), wrec.ctypes.data, wseq.ctypes.data,
-                                                            wqual.ctypes.data, win_cap, _p(woff, C.c_int64), wpol.ctypes.data))
+                                                            wqual.ctypes.data, win_cap, _p(woff, C.c_int64), wpol.ctypes.data, *more))
         kept = int(soff[ns]) if ns else 0
         out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
                "inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg),
                "insert_windows": self._windows_dict(wrec[:kept], wseq, wqual, woff[:kept + 1], wpol[:kept])}
+        if _full is not None:
+            G = int(f_ioff[ns])
+            out["isoforms_full"] = {**self._groups_out(f_ioff, f_seq, f_qual, f_off, f_pol[:G]), "off": f_off[:G + 1], "sstats": f_sst[:G],
+                                    "splice": [f_splice[int(f_spoff[x]):int(f_spoff[x + 1])] for x in range(G)], "splice_off": f_spoff[:G + 1]}
         if stats:
             out["stats"] = st
         if tables:
             out.update(cols=cols, row0=self._row0(rlen))
         return out
+
+    def align_pairs_isoforms_full(self, pairs, k, segs, seg_of_pair, max_iso=16, full_cap=None, iso_cap=None, splice_cap=None, **kw):
+        """ioc_align_pairs_isoforms_full: align_pairs_blocks_inserts_seq with the six slot planes projected as well and, behind the
+        window kernels, the consensus of the first min(n_groups, max_iso) COMBINED isoforms of every segment with the windows of the
+        sites each carries spliced in — every isoform's full-length sequence from one alignment of every read.  Returns
+        align_pairs_blocks_inserts_seq's dict, byte for byte, and under `isoforms_full` what Context.planes_isoforms_full returns
+        (without tables; `gseg_off` is iso_off).  polish_min_depth serves the windows and the isoforms; full_cap, iso_cap and
+        splice_cap default to isoforms_full_bound of the segments."""
+        return self.align_pairs_blocks_inserts_seq(pairs, k, segs, seg_of_pair, _full=dict(max_iso=max_iso, cap=full_cap, iso_cap=iso_cap, splice_cap=splice_cap), **kw)
 
     def align_pairs_blocks(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, match=2, mismatch=-2, gap_extend=1, **rule):
         """ioc_align_pairs_blocks: align_pairs, the table of counts, every pair's base plane and the block search over the planes, all
@@ -1395,6 +1469,69 @@ class Context:
                                                   qual.ctypes.data, cap, _p(off, C.c_int64), pol.ctypes.data if G else None,
                                                   gcols.ctypes.data if tables and n_rows else None, gins.ctypes.data if tables and n_rows else None))
         out = self._groups_out(goff, seq, qual, off, pol)
+        if tables:
+            out.update(gcols=gcols, gins=gins, grow0=np.concatenate([[0], np.cumsum(per)])[:G].astype(np.int64))
+        return out
+
+    def planes_isoforms_full(self, frames, seg_of_pair, group, n_groups, base, slots, iso_key, win, win_seq, win_qual, min_depth=3, tables=False, cap=None,
+                             splice_cap=None):
+        """ioc_planes_isoforms_full: the full-length sequence of every group of every segment on the device, from host planes —
+        planes_polish_groups with, per group-segment, `iso_key` (the insert key of its direct reads, group-segment order) and, per
+        segment, `win` (an INSERT_WINDOW_DTYPE array, a record per kept site) and `win_seq` / `win_qual` (a list of bytes per site) as
+        planes_insert_windows returned them.  Returns planes_polish_groups' dict and `off`, `sstats` (SPLICE_STATS_DTYPE per
+        group-segment), `splice` (per group-segment a SPLICE_SITE_DTYPE array, a record per site of its segment) and `splice_off` —
+        each group-segment as isoform_splice defines it on the tables planes_pile adds up from the group's reads."""
+        ns, n = len(frames), len(base)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        sop, grp, ng = np.ascontiguousarray(seg_of_pair, np.int32), np.ascontiguousarray(group, np.int32), np.ascontiguousarray(n_groups, np.int32)
+        if sop.shape != (n,) or grp.shape != (n,) or len(slots) != n or ng.shape != (ns,) or len(win) != ns or len(win_seq) != ns or len(win_qual) != ns:
+            raise ValueError("seg_of_pair, group, base and slots must hold one entry per pair and n_groups, win, win_seq and win_qual one per segment")
+        rows = [int(rlen[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (rows[i],) or np.shape(slots[i]) != (_lib.PILE_INS_SLOTS, rows[i]):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        P = sum(rows)
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        fs = np.ascontiguousarray(np.concatenate([np.zeros((_lib.PILE_INS_SLOTS, 0), np.uint8)] + [np.asarray(x, np.uint8) for x in slots], axis=1))
+        f_off = np.zeros(ns + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        groups = np.maximum(ng.astype(np.int64), 0)   # (a negative count: the library refuses the call)
+        goff = np.concatenate([[0], np.cumsum(groups)]).astype(np.int64)
+        G = int(goff[-1])
+        keys = np.ascontiguousarray(iso_key, np.uint64)
+        if keys.shape != (G,):
+            raise ValueError("iso_key must hold one key per group-segment")
+        for g in range(ns):
+            if len(win_seq[g]) != len(win[g]) or len(win_qual[g]) != len(win[g]) or any(len(s) != len(q) for s, q in zip(win_seq[g], win_qual[g])):
+                raise ValueError(f"the windows of segment {g} are not one sequence and one string of qualities per site")
+        n_sites = np.array([len(w) for w in win], np.int64)
+        soff = np.concatenate([[0], np.cumsum(n_sites)]).astype(np.int64)
+        S = int(soff[-1])
+        wrec = np.ascontiguousarray(np.concatenate([np.zeros(0, INSERT_WINDOW_DTYPE)] + [np.asarray(w, INSERT_WINDOW_DTYPE) for w in win]))
+        flat = [bytes(s) for g in range(ns) for s in win_seq[g]]
+        woff = np.concatenate([[0], np.cumsum([len(s) for s in flat])]).astype(np.int64)
+        wseq, wqual = b"".join(flat), b"".join(bytes(q) for g in range(ns) for q in win_qual[g])
+        wbytes = [int(woff[soff[g + 1]] - woff[soff[g]]) for g in range(ns)]
+        bound = sum(int(groups[g]) * isoform_splice_bound(rlen[g], wbytes[g]) for g in range(ns))
+        cap = bound if cap is None else int(cap)
+        R = int((groups * n_sites).sum())
+        splice_cap = R if splice_cap is None else int(splice_cap)
+        per = np.repeat(rlen.astype(np.int64) + 1, groups)
+        n_rows = int(per.sum())
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, pol, sst = np.zeros(G + 1, np.int64), np.zeros(max(G, 1), POLISH_STATS_DTYPE), np.zeros(max(G, 1), SPLICE_STATS_DTYPE)
+        rec, spoff = np.zeros(max(splice_cap, 1), SPLICE_SITE_DTYPE), np.zeros(G + 1, np.int64)
+        gcols, gins = (np.zeros(n_rows, PILEUP_DTYPE), np.zeros(n_rows, PILEUP_INS_DTYPE)) if tables else (None, None)
+        pad = lambda a: np.concatenate([a, np.zeros(1, a.dtype)])  # (never an empty array's pointer)
+        keys, wrec = pad(keys), pad(wrec)
+        self._chk(self.L.ioc_planes_isoforms_full(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+                                                  _p(ng, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, _p(grp, C.c_int32) if n else None,
+                                                  fb.ctypes.data if P else None, fs.ctypes.data if P else None, keys.ctypes.data, wrec.ctypes.data,
+                                                  _p(soff, C.c_int64), wseq, wqual, _p(woff, C.c_int64), int(min_depth), seq.ctypes.data, qual.ctypes.data, cap,
+                                                  _p(off, C.c_int64), pol.ctypes.data, sst.ctypes.data, rec.ctypes.data, splice_cap, _p(spoff, C.c_int64),
+                                                  gcols.ctypes.data if tables and n_rows else None, gins.ctypes.data if tables and n_rows else None))
+        out = self._groups_out(goff, seq, qual, off, pol[:G])
+        out.update(off=off, sstats=sst[:G], splice=[rec[int(spoff[x]):int(spoff[x + 1])] for x in range(G)], splice_off=spoff)
         if tables:
             out.update(gcols=gcols, gins=gins, grow0=np.concatenate([[0], np.cumsum(per)])[:G].astype(np.int64))
         return out

@@ -61,7 +61,7 @@ void print_dump_help()
          << "                     [--isoforms-min-block N] [--isoforms-max N]" << endl
          << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N] [--isoforms-polish-weighted]]" << endl
          << "                     [--isoforms-inserts [--isoforms-min-ins N] [--isoforms-ins-slack N] [--isoforms-ins-max N]" << endl
-         << "                     [--isoforms-inserts-seq [--isoforms-inserts-max-win N]]]] final.cer" << endl
+         << "                     [--isoforms-inserts-seq [--isoforms-inserts-max-win N] [--isoforms-full [--isoforms-full-max N]]]]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -146,6 +146,12 @@ void print_dump_help()
          << "                 hold between rows lo and hi of the representative (the site widened by --isoforms-ins-slack, in the orientation the" << endl
          << "                 reads were aligned in), to stand in place of those rows.  All carriers of a site vote together" << endl
          << "  --isoforms-inserts-max-win N  a carrier votes where its stretch between the two rows has at most N bases, 1 .. 512 (default 512)" << endl
+         << "  --isoforms-full         with --isoforms-inserts-seq: also write outdir/cluster_isoforms_full.fq, from the same alignments: for every cluster" << endl
+         << "                 that has a block or a site, a record per isoform counted over blocks and sites together, \"cluster_<id>/iso<h>" << endl
+         << "                 key=<blocks>/<sites> reads=<n> subs= dels= ins= low= [ins<b>@<at>+<len> ..]\": the consensus of the isoform's reads in the" << endl
+         << "                 representative's frame with, for every site the isoform carries, the site's record of cluster_inserts.fq in place of" << endl
+         << "                 the rows it stands for (len bases from base at on) - the isoform's full-length sequence" << endl
+         << "  --isoforms-full-max N   call the first N isoforms of a cluster (default 16)" << endl
          << "  --isoforms-min-ins N    a read carries an insertion at a junction where the bases it inserts within --isoforms-ins-slack junctions" << endl
          << "                 sum to at least N, 1 .. 255 (default 20: a choice that was not measured on real data)" << endl
          << "  --isoforms-ins-slack N  ... the junctions on either side that count, 0 .. 32 (default 8: at 8 % errors the aligner breaks a 40-base" << endl
@@ -176,7 +182,8 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms-polish-weighted", no_argument, 0, 1031}, {"isoforms-inserts", no_argument, 0, 1032},
                                        {"isoforms-min-ins", required_argument, 0, 1033}, {"isoforms-ins-slack", required_argument, 0, 1034},
                                        {"isoforms-ins-max", required_argument, 0, 1035}, {"isoforms-inserts-seq", no_argument, 0, 1036},
-                                       {"isoforms-inserts-max-win", required_argument, 0, 1037}, {0, 0, 0, 0}};
+                                       {"isoforms-inserts-max-win", required_argument, 0, 1037}, {"isoforms-full", no_argument, 0, 1038},
+                                       {"isoforms-full-max", required_argument, 0, 1039}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false, iso_polish = false;
@@ -225,6 +232,8 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1035: r.isoforms.ins_max = number("--isoforms-ins-max", optarg, 1, 32); break;
             case 1036: r.isoforms.inserts_seq = true; break;
             case 1037: r.isoforms.ins_max_win = number("--isoforms-inserts-max-win", optarg, 1, IOC_WIN_MAX); break;
+            case 1038: r.isoforms.full = true; break;
+            case 1039: r.isoforms.full_max = number("--isoforms-full-max", optarg, 1, INT32_MAX); break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -241,6 +250,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (r.isoforms.inserts && !r.isoforms.on) die("--isoforms-inserts asks for --isoforms!");
     if (r.isoforms.inserts && iso_polish) die("--isoforms-inserts is not offered together with --isoforms-polish!");
     if (r.isoforms.inserts_seq && !r.isoforms.inserts) die("--isoforms-inserts-seq asks for --isoforms-inserts!");
+    if (r.isoforms.full && !r.isoforms.inserts_seq) die("--isoforms-full asks for --isoforms-inserts-seq!");
     if (polish) r.polish_min_depth = polish_min_depth;
     if (d.index.empty()) die("Specifying the sorted read index is mandatory!");
     d.batch = argv[optind];
@@ -419,7 +429,8 @@ int main_dump(int argc, char** argv)
                              (reports.correct.on ? "corrected_reads.fq, " : "") +
                              (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "") + (reports.iso_polish() ? "cluster_isoforms.fq, " : "") +
                              (reports.isoforms.on && reports.isoforms.inserts ? "cluster_inserts.tsv, read_inserts.tsv, " : "") +
-                             (reports.isoforms.on && reports.isoforms.inserts && reports.isoforms.inserts_seq ? "cluster_inserts.fq, " : "");
+                             (reports.isoforms.on && reports.isoforms.inserts && reports.isoforms.inserts_seq ? "cluster_inserts.fq, " : "") +
+                             (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.full ? "cluster_isoforms_full.fq, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

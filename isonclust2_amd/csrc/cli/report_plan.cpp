@@ -143,6 +143,17 @@ IsoCapacity iso_polish_capacity(const ReportGroup& g, int max_iso)
     return cap;
 }
 
+IsoCapacity iso_full_capacity(const ReportGroup& g, int max_iso, int max_sites, int max_win)
+{
+    IsoCapacity cap;
+    for (size_t s = 0; s < g.segs.size(); ++s) {
+        const int64_t m = ref_len(g, g.segs[s]), most = std::min<int64_t>(max_iso, g.seg_reads[s]), sites = std::min<int64_t>(max_sites, std::max<int64_t>(m - 1, 0));
+        cap.isoforms += most;
+        cap.bytes += most * (m + IOC_PILE_INS_SLOTS * (m + 1) + sites * (7 * int64_t(max_win) + 6));
+    }
+    return cap;
+}
+
 SiteCapacity site_capacity(const ReportGroup& g, int max_sites)
 {
     SiteCapacity cap;

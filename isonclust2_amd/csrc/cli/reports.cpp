@@ -83,6 +83,7 @@
 
 #include <cstdio>
 #include <fstream>
+#include <memory>
 
 #include "common.hpp"
 
@@ -136,6 +137,12 @@ struct GroupResult {
     std::vector<int64_t> win_off;            // [win_off[s], win_off[s + 1]) of wseq / wqual
     std::vector<ioc_polish_stats> win_stats;
     string wseq, wqual;
+    // (--isoforms-full) per called combined isoform, segment g's at [full_off[g], full_off[g + 1]): its bytes at [fseq_off[x], fseq_off[x + 1]) of
+    // fseq / fqual (room for the bound, written up to fseq_off's last entry), its records, and its site records from fsplice_off[x] on
+    std::unique_ptr<char[]> fseq, fqual;
+    std::vector<int64_t> full_off, fseq_off, fsplice_off;
+    std::vector<ioc_polish_stats> fstats;
+    std::vector<ioc_splice_site> fsplice;
 };
 
 // a row of the three per-read tables
@@ -279,6 +286,23 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
                 r.ins_windows.assign(size_t(std::max<int64_t>(icap, 1)), ioc_insert_window{}), r.win_off.assign(size_t(icap) + 1, 0);
                 r.win_stats.assign(size_t(std::max<int64_t>(icap, 1)), ioc_polish_stats{});
                 r.wseq.assign(size_t(std::max<int64_t>(wcap, 1)), '\0'), r.wqual.assign(size_t(std::max<int64_t>(wcap, 1)), '\0');
+                if (io.full) {
+                    // (the room is the bound, which is generous: a window's 7 max_win + 6 bytes a site an isoform; the pages the call does not write are never touched)
+                    const IsoCapacity fcap = iso_full_capacity(g, io.full_max, io.ins_max, io.ins_max_win);
+                    r.fseq.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]), r.fqual.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]);
+                    r.full_off.assign(ns + 1, 0), r.fseq_off.assign(size_t(fcap.isoforms) + 1, 0), r.fsplice_off.assign(size_t(fcap.isoforms) + 1, 0);
+                    r.fstats.assign(size_t(std::max<int64_t>(fcap.isoforms, 1)), ioc_polish_stats{});
+                    r.fsplice.assign(size_t(std::max<int64_t>(fcap.isoforms * io.ins_max, 1)), ioc_splice_site{});
+                    check(c, ioc_align_pairs_isoforms_full(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
+                                                           g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
+                                                           r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
+                                                           o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
+                                                           r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(), io.ins_max_win,
+                                                           2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(), r.win_stats.data(),
+                                                           io.full_max, r.fseq.get(), r.fqual.get(), fcap.bytes, r.fseq_off.data(), r.fstats.data(), nullptr,
+                                                           r.fsplice.data(), int64_t(r.fsplice.size()), r.fsplice_off.data(), fcap.isoforms, r.full_off.data()),
+                          "exon blocks with the insertion sites, their sequences and the isoforms' full-length sequences");
+                } else
                 check(c, ioc_align_pairs_blocks_inserts_seq(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
                                                             g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
                                                             r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
@@ -490,9 +514,39 @@ void write_insert_windows(std::ofstream& out, const ReportRows& rows, const Repo
     }
 }
 
+// cluster_isoforms_full.fq: a record per called combined isoform of every cluster that has a block or a site
+void write_isoforms_full(std::ofstream& out, const ReportGroup& g, const GroupResult& r)
+{
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0 || (r.blocks_seg[size_t(s)].n_blocks < 1 && r.inserts_seg[size_t(s)].n_sites < 1)) continue;
+        const int64_t i0 = r.full_off[size_t(s)], n = r.full_off[size_t(s) + 1] - i0;
+        std::vector<uint64_t> bkey(size_t(n), 0), ikey(size_t(n), 0);
+        std::vector<int32_t> mine(size_t(n), 0);
+        for (size_t p = 0; p < g.pairs.size(); ++p) {
+            const ioc_read_inserts& ri = r.read_inserts[p];
+            if (g.seg_of_pair[p] != s || ri.group < 0 || ri.group >= n) continue;
+            if (ri.how == IOC_ISO_DIRECT) bkey[size_t(ri.group)] = r.read_blocks[p].key, ikey[size_t(ri.group)] = ri.key;
+            if (ri.how == IOC_ISO_DIRECT || ri.how == IOC_ISO_ASSIGNED) ++mine[size_t(ri.group)];
+        }
+        for (int64_t h = 0; h < n; ++h) {
+            const size_t at = size_t(r.fseq_off[size_t(i0 + h)]), len = size_t(r.fseq_off[size_t(i0 + h) + 1]) - at;
+            string tail;
+            for (int64_t b = r.fsplice_off[size_t(i0 + h)]; b < r.fsplice_off[size_t(i0 + h) + 1]; ++b)
+                if (r.fsplice[size_t(b)].state == IOC_SPLICE_DONE)
+                    tail += " ins" + std::to_string(b - r.fsplice_off[size_t(i0 + h)]) + '@' + std::to_string(r.fsplice[size_t(b)].at) + '+' + std::to_string(r.fsplice[size_t(b)].len);
+            const string text = polish_record("cluster_" + std::to_string(g.group_cls[x].first) + "/iso" + std::to_string(h) + " key=" +
+                                                  blocks_signature(bkey[size_t(h)], r.blocks_seg[size_t(s)].n_blocks) + '/' +
+                                                  inserts_signature(ikey[size_t(h)], r.inserts_seg[size_t(s)].n_sites),
+                                              mine[size_t(h)], r.fstats[size_t(i0 + h)], tail.c_str(), r.fseq.get() + at, r.fqual.get() + at, len);
+            out.write(text.data(), std::streamsize(text.size()));
+        }
+    }
+}
+
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq, full_fq;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -520,6 +574,7 @@ struct GroupFiles {
             create_file(outdir + "/cluster_inserts.tsv", inserts);
             inserts << "ClusterId\tFirst\tEnd\tCarry\tLack\tNone\tLenMin\tLenMax\n";
             if (o.isoforms.inserts_seq) create_file(outdir + "/cluster_inserts.fq", inserts_fq);
+            if (o.isoforms.inserts_seq && o.isoforms.full) create_file(outdir + "/cluster_isoforms_full.fq", full_fq);
         }
     }
     void write(const Batch& b, const ReportOpts& o, const ReportRows& rows, const ReportGroup& g, const GroupResult& r)
@@ -532,6 +587,7 @@ struct GroupFiles {
         if (o.isoforms.on && !g.segs.empty()) write_blocks(blocks, isoforms, o.iso_polish() ? &iso_fq : nullptr, g, r);
         if (o.isoforms.on && o.isoforms.inserts && !g.segs.empty()) write_inserts(inserts, g, r);
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && !g.segs.empty() && !g.pairs.empty()) write_insert_windows(inserts_fq, rows, g, r);
+        if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && o.isoforms.full && !g.segs.empty() && !g.pairs.empty()) write_isoforms_full(full_fq, g, r);
     }
 };
 

@@ -35,6 +35,8 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     int min_ins = 20, ins_slack = 8, ins_max = 32;   // ... the thresholds of ioc_host_planes_inserts the block search does not share
     bool inserts_seq = false;                        // --isoforms-inserts-seq: the consensus of the carriers' windows at every kept site as well
     int ins_max_win = IOC_WIN_MAX;                   // (ioc_align_pairs_blocks_inserts_seq), and the longest window that votes
+    bool full = false;                               // --isoforms-full: every combined isoform's full-length sequence as well
+    int full_max = 16;                               // (ioc_align_pairs_isoforms_full), and how many isoforms of a cluster are called
 };
 struct ReportOpts {
     bool stats = false;        // --read-stats
@@ -123,6 +125,8 @@ struct IsoCapacity {
     int64_t isoforms = 0, bytes = 0;
 };
 IsoCapacity iso_polish_capacity(const ReportGroup& g, int max_iso);
+// ... and of ioc_align_pairs_isoforms_full: an isoform holds at most its call's bound and a window of 7 max_win + 6 bytes a site
+IsoCapacity iso_full_capacity(const ReportGroup& g, int max_iso, int max_sites, int max_win);
 // the insertion sites a search may keep at most, for all segments of a group: min(max_sites, the junctions of the representative) each
 int64_t inserts_capacity(const ReportGroup& g, int max_sites);
 // A signature of insertion sites: one character per kept site from the key's two bits each — '=' lack (as the representative), '+'

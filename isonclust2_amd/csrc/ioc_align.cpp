@@ -23,6 +23,7 @@
 #include "ioc_read_blocks.h"
 #include "ioc_read_inserts.h"
 #include "ioc_insert_windows.h"
+#include "ioc_iso_splice.h"
 #include "ioc_read_correct.h"
 #include "ioc_site_split.h"
 
@@ -1007,6 +1008,63 @@ int ioc_host_insert_windows(const uint8_t* base, const uint32_t* qpos, const int
         out_win[k] = w;
     }
     return IOC_OK;
+}
+
+// The full-length sequence of one isoform: ioc_host_pileup_call's walk with the windows of the sites it carries in place of their
+// rows (isonclust2_hip.h has the rules; splice_state and splice_row, ioc_iso_splice.h, decide for this function and for the kernels
+// of ioc_iso_splice.hip alike).
+int64_t ioc_host_isoform_splice(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth, uint64_t key,
+                                const ioc_insert_window* win, int32_t n_sites, const char* win_seq, const char* win_qual, const int64_t* win_off,
+                                char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st, ioc_splice_site* out_sites, ioc_splice_stats* out_sstats)
+{
+    if (min_depth < 1 || rlen < 0 || !cols || !ins || (rlen > 0 && !frame) || n_sites < 0 || n_sites > IOC_INSERTS_MAX || !win_off ||
+        (n_sites > 0 && (!win || !out_sites)))
+        return IOC_ERR_ARG;
+    for (int32_t b = 0; b < n_sites; ++b)
+        if (win[b].lo < 1 || win[b].lo >= win[b].hi || win[b].hi > rlen || win[b].tlen < 0 || win_off[b + 1] < win_off[b] ||
+            win_off[b + 1] - win_off[b] > INT32_MAX)
+            return IOC_ERR_ARG;
+    const int64_t win_bytes = win_off[n_sites] - win_off[0];
+    if (win_bytes > 0 && (!win_seq || !win_qual)) return IOC_ERR_ARG;
+    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1) + win_bytes;
+    if (cap < bound) return IOC_ERR_CAPACITY;
+    if (!out_seq || !out_qual) return IOC_ERR_ARG;
+    IocSpliceIv plan[IOC_SPLICE_PLAN_MAX];
+    uint32_t n_plan = 0;
+    ioc_splice_stats ss{};
+    int32_t last_hi = 0;
+    for (int32_t b = 0; b < n_sites; ++b) {
+        const int32_t state = splice_state(key, uint32_t(b), win[b], last_hi);
+        out_sites[b] = ioc_splice_site{state, -1, 0, 0};
+        ss.n_uncalled += state == IOC_SPLICE_UNCALLED, ss.n_overlap += state == IOC_SPLICE_OVERLAP;
+        if (state != IOC_SPLICE_DONE) continue;
+        plan[n_plan++] = IocSpliceIv{win[b].lo, win[b].hi, int32_t(win_off[b + 1] - win_off[b]), b, win_off[b]};
+        last_hi = win[b].hi;
+        ++ss.n_done, ss.rows_replaced += win[b].hi - win[b].lo, ss.spliced_bytes += int32_t(win_off[b + 1] - win_off[b]);
+    }
+    ioc_polish_stats s{};
+    int64_t at = 0;
+    for (int32_t p = 0; p <= rlen; ++p) {
+        const int32_t what = splice_row(plan, n_plan, p);
+        if (what == IOC_SPLICE_ROW_GONE) continue;
+        if (what >= 0) {
+            const IocSpliceIv& iv = plan[what];
+            out_sites[iv.site].at = int32_t(at), out_sites[iv.site].len = iv.len;
+            for (int32_t x = 0; x < iv.len; ++x) out_seq[at] = win_seq[iv.off + x], out_qual[at++] = win_qual[iv.off + x];
+            continue;
+        }
+        const unsigned long long d_ins = p < rlen ? pile_depth(cols[p]) : rlen > 0 ? pile_depth(cols[rlen - 1]) : 0ull;
+        const PileRowCall row = pile_call_row(cols[p], ins[p], d_ins, p < rlen, p < rlen ? uint8_t(frame[p]) : uint8_t(0), min_depth);
+        for (uint32_t x = 0; x < row.n; ++x) {
+            out_seq[at] = char((row.seq >> (8u * x)) & 0xFFu);
+            out_qual[at++] = char((row.qual >> (8u * x)) & 0xFFu);
+        }
+        s.n_ins += int32_t(row.n_ins), s.n_sub += int32_t(row.n_sub), s.n_del += int32_t(row.n_del), s.n_low += int32_t(row.n_low);
+    }
+    s.out_len = int32_t(at);
+    if (st) *st = s;
+    if (out_sstats) *out_sstats = ss;
+    return at;
 }
 
 // setGapOpen, src/cluster.cpp:425-440

@@ -36,6 +36,8 @@ struct AlnTally {
     double ms_project_qpos = 0; // k_ops_project_qpos' device time (a pile that projects the position plane as well), and ...
     double ms_win_walk = 0;     // (IOC_WIN_SPLIT: k_win_align's walk on its own; ms_windows[2] is the fill then)
     double ms_windows[4] = {};  // ... k_win_bounds, k_win_template, k_win_align and k_group_pile over the sites (ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq)
+    double ms_splice[3] = {};   // k_splice_plan, k_splice_call's count pass with the scan, and its write pass (ioc_planes_isoforms_full,
+                                // ioc_align_pairs_isoforms_full, where ms_group_pile is k_group_pile over the combined isoforms)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
     int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };

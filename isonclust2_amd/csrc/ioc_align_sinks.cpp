@@ -21,6 +21,7 @@
 #include "ioc_read_correct.h"
 #include "ioc_read_inserts.h"
 #include "ioc_insert_windows.h"
+#include "ioc_iso_splice.h"
 
 namespace {
 struct AlnCall {  // what every aligning entry point passes on
@@ -1627,10 +1628,189 @@ int ioc_planes_insert_windows(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, i
     return IOC_OK;
 }
 
+namespace {
+// what a splice reads beside the group tables, all the host's: a key per group-segment, the segments' window records packed with
+// site_off, their called bytes packed with win_off
+struct SpliceIn {
+    const uint64_t* keys;
+    const ioc_insert_window* win;
+    const int64_t* site_off;
+    const char *wseq, *wqual;
+    const int64_t* win_off;
+};
+struct SpliceOut {  // where a splice leaves what it made (call.off: G + 1 entries; cap: the records `splice` holds; splice_off: G + 1 entries)
+    CallOut call;
+    ioc_splice_stats* sstats;
+    ioc_splice_site* splice;
+    int64_t cap;
+    int64_t* splice_off;
+    bool ok() const { return call.ok() && splice_off && cap >= 0; }
+};
+
+// what a splice over n_groups[g] group-segments of segment g refuses about its windows and its room: IOC_OK, or the status with the
+// message set.  The bound is the sum over the segments of n_groups[g] * (pile_call_most(rlen[g]) + the bytes of g's windows).
+static int splice_ok(ioc_ctx* c, const std::string& who, const SpliceIn& in, const SpliceOut& o, const std::vector<IocPileSeg>& ds, const int32_t* n_groups, int64_t* out_bound)
+{
+    const size_t n = ds.size();
+    if (!in.site_off || !in.win_off) return IOC_ERR_ARG;
+    if (in.site_off[0] != 0 || in.win_off[0] != 0) return ioc_fail(c, IOC_ERR_ARG, who + ": site_off or win_off does not begin at 0");
+    int64_t bound = 0, records = 0, G = 0;
+    for (size_t g = 0; g < n; ++g) {
+        if (in.site_off[g + 1] < in.site_off[g] || in.site_off[g + 1] - in.site_off[g] > IOC_INSERTS_MAX)
+            return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " has a negative number of sites or more than 32");
+        for (int64_t x = in.site_off[g]; x < in.site_off[g + 1]; ++x) {
+            if (!in.win || in.win[x].lo < 1 || in.win[x].lo >= in.win[x].hi || in.win[x].hi > ds[g].rlen || in.win[x].tlen < 0)
+                return ioc_fail(c, IOC_ERR_ARG, who + ": the window of site " + std::to_string(x) + " does not lie inside its segment");
+            if (in.win_off[x + 1] < in.win_off[x]) return ioc_fail(c, IOC_ERR_ARG, who + ": win_off does not ascend at site " + std::to_string(x));
+        }
+        const int64_t most = pile_call_most(ds[g].rlen) + (in.win_off[in.site_off[g + 1]] - in.win_off[in.site_off[g]]);
+        if (most > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
+            return ioc_fail(c, IOC_ERR_CAPACITY, who + ": an isoform of segment " + std::to_string(g) + " may hold more than 2^31 - 1 bytes");
+        bound += int64_t(n_groups[g]) * most, records += int64_t(n_groups[g]) * (in.site_off[g + 1] - in.site_off[g]), G += n_groups[g];
+    }
+    if (in.win_off[in.site_off[n]] > 0 && (!in.wseq || !in.wqual)) return IOC_ERR_ARG;
+    if (G > 0 && !in.keys) return IOC_ERR_ARG;
+    if (o.cap < records) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": splice_cap " + std::to_string(o.cap) + " below the bound " + std::to_string(records));
+    if (records > 0 && !o.splice) return IOC_ERR_ARG;
+    *out_bound = bound;
+    return call_room_ok(c, who, o.call, bound);
+}
+
+// plan -> count -> scan -> write -> copy-out over group tables that lie on the device (g; gseg_off[s] .. gseg_off[s + 1] are segment
+// s's group-segments).  a_splice holds, uploaded in one piece, [group-segments][their segments][keys][window records][site_off][win_off]
+// [window sequences][window qualities][splice_off], and behind them [site records][splice records][plans][plan lengths][seg_len]
+// [out_off][records][sequence][qualities].
+static int splice_device(SinkRun& r, const GroupPiled& g, const std::vector<uint32_t>& gseg_off, const uint8_t* d_frames, uint64_t frame_bytes, const SpliceIn& in,
+                         const SpliceOut& o, int64_t bound)
+{
+    ioc_ctx* const c = r.c;
+    const size_t n = gseg_off.size() - 1, G = g.gsegs.size(), S = size_t(in.site_off[n]), W = size_t(in.win_off[S]);
+    std::vector<int32_t> gseg_seg(G);
+    o.splice_off[0] = 0;
+    for (size_t s = 0; s < n; ++s)
+        for (size_t x = gseg_off[s]; x < gseg_off[s + 1]; ++x) gseg_seg[x] = int32_t(s), o.splice_off[x + 1] = o.splice_off[x] + (in.site_off[s + 1] - in.site_off[s]);
+    const size_t R = size_t(o.splice_off[G]);
+    Arena l;
+    const size_t o_gseg = l.take(G * sizeof(IocPileSeg)), o_gs = l.take(G * 4), o_keys = l.take(G * 8), o_win = l.take(S * sizeof(ioc_insert_window)),
+                 o_soff = l.take((n + 1) * 8), o_woff = l.take((S + 1) * 8), o_wseq = l.take(W), o_wqual = l.take(W), o_spoff = l.take((G + 1) * 8), tables = l.size();
+    const size_t o_rec = l.take(R * sizeof(ioc_splice_site)), o_ss = l.take(G * sizeof(ioc_splice_stats)), o_plan = l.take(G * IOC_SPLICE_PLAN_MAX * sizeof(IocSpliceIv)),
+                 o_pn = l.take(G * 4), o_len = l.take(G * 8), o_off = l.take((G + 1) * 8), o_st = l.take(G * sizeof(ioc_polish_stats)), o_seq = l.take(size_t(bound)),
+                 o_qual = l.take(size_t(bound));
+    std::vector<uint8_t> stage(tables, 0);
+    auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
+    put(o_gseg, g.gsegs.data(), G * sizeof(IocPileSeg)), put(o_gs, gseg_seg.data(), G * 4), put(o_keys, in.keys, G * 8), put(o_win, in.win, S * sizeof(ioc_insert_window));
+    put(o_soff, in.site_off, (n + 1) * 8), put(o_woff, in.win_off, (S + 1) * 8), put(o_wseq, in.wseq, W), put(o_wqual, in.wqual, W), put(o_spoff, o.splice_off, (G + 1) * 8);
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_splice, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_splice.p);
+    IOC_CHK(c, hipMemcpyAsync(p, stage.data(), tables, hipMemcpyHostToDevice, c->stream));
+    const IocSpliceDev v{reinterpret_cast<const IocPileSeg*>(p + o_gseg), uint32_t(G), reinterpret_cast<const int32_t*>(p + o_gs),
+                         reinterpret_cast<const unsigned long long*>(p + o_keys), reinterpret_cast<const ioc_insert_window*>(p + o_win),
+                         reinterpret_cast<const long long*>(p + o_soff), reinterpret_cast<const long long*>(p + o_woff), uint64_t(S), p + o_wseq, p + o_wqual, uint64_t(W),
+                         reinterpret_cast<const long long*>(p + o_spoff), reinterpret_cast<ioc_splice_site*>(p + o_rec), uint64_t(R),
+                         reinterpret_cast<ioc_splice_stats*>(p + o_ss), reinterpret_cast<IocSpliceIv*>(p + o_plan), reinterpret_cast<uint32_t*>(p + o_pn)};
+    IOC_TRY(r.begin(r.t.ms_splice[0]));
+    IOC_CHK(c, iock_splice_plan(c->stream, v));
+    IOC_TRY(r.end());
+    IOC_TRY(r.begin(r.t.ms_splice[1]));
+    IOC_CHK(c, iock_splice_call(c->stream, v, /*emit*/ false, g.cols, g.ins, uint64_t(g.n_rows), d_frames, frame_bytes, o.call.min_depth, reinterpret_cast<int64_t*>(p + o_len),
+                                reinterpret_cast<ioc_polish_stats*>(p + o_st), nullptr, nullptr, nullptr, 0));
+    IOC_CHK(c, iock_pile_scan(c->stream, reinterpret_cast<const int64_t*>(p + o_len), uint32_t(G), reinterpret_cast<int64_t*>(p + o_off)));
+    IOC_TRY(r.end());
+    IOC_TRY(r.begin(r.t.ms_splice[2]));
+    IOC_CHK(c, iock_splice_call(c->stream, v, /*emit*/ true, g.cols, g.ins, uint64_t(g.n_rows), d_frames, frame_bytes, o.call.min_depth, nullptr, nullptr,
+                                reinterpret_cast<const int64_t*>(p + o_off), p + o_seq, p + o_qual, uint64_t(bound)));
+    IOC_TRY(r.end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    r.settled();
+    IOC_TRY(r.copy_out({{o.call.off, p + o_off, (G + 1) * 8}}));
+    const int64_t len = o.call.off[G];
+    if (len < 0 || len > bound) return ioc_fail(c, IOC_ERR_HIP, "the splice returned a length outside its bound");
+    return r.copy_out({{o.call.stats, p + o_st, G * sizeof(ioc_polish_stats)}, {o.sstats, p + o_ss, G * sizeof(ioc_splice_stats)},
+                       {o.splice, p + o_rec, R * sizeof(ioc_splice_site)}, {o.call.seq, p + o_seq, size_t(len)}, {o.call.qual, p + o_qual, size_t(len)}});
+}
+
+static std::string splice_trace(const AlnTally& t)
+{
+    char buf[160];
+    snprintf(buf, sizeof buf, "k_splice_plan %.3f ms, k_splice_call<count> + scan %.3f ms, k_splice_call<emit> %.3f ms", t.ms_splice[0], t.ms_splice[1], t.ms_splice[2]);
+    return buf;
+}
+}  // namespace
+
+// upload -> groups pile -> splice -> copy-out.  ioc_planes_polish_groups with the windows of the sites every isoform carries spliced
+// into its call: the checks of ioc_planes_polish_groups, in its order, then those of the windows.
+int ioc_planes_isoforms_full(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups, int32_t n_pairs,
+                             const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base, const uint8_t* slots, const uint64_t* iso_key,
+                             const ioc_insert_window* win, const int64_t* site_off, const char* win_seq, const char* win_qual, const int64_t* win_off, int32_t min_depth,
+                             char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats,
+                             ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins)
+{
+    const std::string who = "ioc_planes_isoforms_full";
+    const SpliceOut o{{min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off};
+    const SpliceIn in{iso_key, win, site_off, win_seq, win_qual, win_off};
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || (n_segs > 0 && (!rlen || !frame_off || !n_groups)) || (n_pairs > 0 && (!seg_of_pair || !group))) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen(who, n_segs, rlen, frames, frame_off, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !slots)) return IOC_ERR_ARG;
+    int64_t G = 0, bound = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (n_groups[g] < 0) return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " has a negative number of groups");
+        if ((G += n_groups[g]) > INT32_MAX) return ioc_fail(c, IOC_ERR_ARG, who + ": more than 2^31 - 1 group-segments");
+    }
+    for (int32_t i = 0; i < n_pairs; ++i)
+        if (group[i] < -1 || group[i] >= n_groups[seg_of_pair[i]])
+            return ioc_fail(c, IOC_ERR_ARG, who + ": the group of pair " + std::to_string(i) + " is neither -1 nor one of its segment's");
+    IOC_TRY(splice_ok(c, who, in, o, p.segs, n_groups, &bound));
+    out_off[0] = 0, splice_off[0] = 0;
+    if (G == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(p.frame_bytes)));
+    if (p.frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(p.frame_bytes), hipMemcpyHostToDevice, c->stream));
+    SinkRun r{c};
+    GroupPiled gp;
+    IOC_TRY(r.groups_pile(p, seg_of_pair, group, n_groups, Planes{nullptr, nullptr, nullptr, base, slots}, Planes{}, gp));
+    IOC_TRY(splice_device(r, gp, gp.lists.gseg_off, static_cast<const uint8_t*>(d_frames.p), uint64_t(p.frame_bytes), in, o, bound));
+    IOC_TRY(r.copy_out({{out_gcols, gp.cols, size_t(gp.n_rows) * sizeof(ioc_pileup_col)}, {out_gins, gp.ins, size_t(gp.n_rows) * sizeof(ioc_pileup_ins)}}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes isoforms full: %lld group-segments, %d pairs, %lld sites, %lld bytes called, k_group_pile %.3f ms, %s\n", (long long)G, n_pairs,
+                (long long)site_off[n_segs], (long long)out_off[G], r.t.ms_group_pile, splice_trace(r.t).c_str());
+    return IOC_OK;
+}
+
+namespace {
+// the isoforms of the fused call: how many of a segment are called and where they go (iso_off: n_segs + 1 entries; o.call.off and
+// o.splice_off: room for iso_cap + 1 entries)
+struct IsoFull {
+    int32_t max_iso;
+    SpliceOut o;
+    int64_t iso_cap;
+    int64_t* iso_off;
+    bool ok() const { return max_iso >= 1 && o.ok() && iso_cap >= 0 && iso_off; }
+};
+// what the fused call refuses about its isoforms' room, known before anything runs: a segment has at most min(max_iso, reads)
+// isoforms, each at most the call's bound plus min(max_sites, max(rlen - 1, 0)) windows of pile_call_most(max_win) bytes
+int iso_full_ok(ioc_ctx* c, const std::string& who, const IsoFull& f, const SinkPlan& p, const std::vector<int64_t>& n_reads, int32_t max_sites, int32_t max_win)
+{
+    int64_t iso = 0, bytes = 0, records = 0;
+    for (size_t g = 0; g < p.segs.size(); ++g) {
+        const int64_t k = std::min<int64_t>(f.max_iso, n_reads[g]), sites = std::min<int64_t>(max_sites, std::max<int64_t>(int64_t(p.segs[g].rlen) - 1, 0));
+        const int64_t most = pile_call_most(p.segs[g].rlen) + sites * pile_call_most(max_win);
+        if (most > INT32_MAX) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": an isoform of segment " + std::to_string(g) + " may hold more than 2^31 - 1 bytes");
+        iso += k, bytes += k * most, records += k * sites;
+    }
+    if (f.iso_cap < iso) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": iso_cap " + std::to_string(f.iso_cap) + " below the bound " + std::to_string(iso));
+    if (f.o.cap < records) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": splice_cap " + std::to_string(f.o.cap) + " below the bound " + std::to_string(records));
+    if (records > 0 && !f.o.splice) return IOC_ERR_ARG;
+    return call_room_ok(c, who, f.o.call, bytes);
+}
+}  // namespace
+
 // pile -> blocks -> inserts -> windows -> copy-out.  ioc_align_pairs_blocks_inserts with the position plane projected beside the other
 // two, and behind the insert kernels the window kernels over the planes where they lie; the sites and the keys are on the host when
 // the insert stage returns and travel back with the tables (32 bytes a site, 8 a pair).
-int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
                                        int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
                                        const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
                                        int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
@@ -1640,7 +1820,6 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_al
                                        int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
                                        int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats)
 {
-    const std::string who = "ioc_align_pairs_blocks_inserts_seq";
     const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
     const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
     const InsertsOut io{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
@@ -1651,14 +1830,23 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_al
     IOC_TRY(blocks_room_ok(c, who, o, p));
     IOC_TRY(inserts_room_ok(c, who, io, p));
     IOC_TRY(windows_ok(c, who, wo, p, nullptr, nullptr, inserts_bound(p, max_sites)));
+    std::vector<int64_t> n_reads(size_t(n_segs), 0);
+    if (full) {
+        for (int32_t i = 0; i < n_pairs; ++i) ++n_reads[size_t(seg_of_pair[i])];
+        IOC_TRY(iso_full_ok(c, who, *full, p, n_reads, max_sites, max_win));
+    }
     for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
     block_off[0] = 0, site_off[0] = 0, out_woff[0] = 0;
+    if (full) {
+        full->o.call.off[0] = 0, full->o.splice_off[0] = 0;
+        for (int32_t g = 0; g <= n_segs; ++g) full->iso_off[g] = 0;
+    }
     if (n_segs == 0) return a.run(c, nullptr);
     SinkRun r{c};
     PiledDev d;
     BlocksDev bd{};
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d, /*project_weights*/ false,
-                   /*project_ilen*/ true, /*project_qpos*/ true));
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ full != nullptr, d,
+                   /*project_weights*/ false, /*project_ilen*/ true, /*project_qpos*/ true));
     IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o, &bd));
     std::vector<uint64_t> pre_full(size_t(n_segs), 0);
     for (int32_t g = 0; g < n_segs; ++g) pre_full[size_t(g)] = blocks_full_mask(uint32_t(out_seg[g].n_blocks));
@@ -1677,11 +1865,73 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_al
         keys[size_t(i)] = out_ireads[i].key;
     }
     IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
+    if (full) {
+        // the combined isoforms the insert stage just made, the first min(n_groups, max_iso) of a segment: their reads, and the key
+        // of the lowest-numbered direct read of each (the records are on the host: they are one of the call's outputs)
+        std::vector<int32_t> n_iso(size_t(n_segs), 0), group(size_t(n_pairs), -1);
+        for (int32_t g = 0; g < n_segs; ++g) {
+            if (out_iseg[g].n_groups < 0 || out_iseg[g].n_groups > n_reads[size_t(g)]) return ioc_fail(c, IOC_ERR_HIP, "the insert search returned more isoforms than reads");
+            n_iso[size_t(g)] = std::min(out_iseg[g].n_groups, full->max_iso);
+            full->iso_off[g + 1] = full->iso_off[g] + n_iso[size_t(g)];
+        }
+        const int64_t G = full->iso_off[n_segs];
+        std::vector<uint64_t> iso_key(size_t(G), 0);
+        std::vector<uint8_t> has_key(size_t(G), 0);
+        for (int32_t i = 0; i < n_pairs; ++i) {
+            const int32_t g = seg_of_pair[i], h = group[size_t(i)] = out_ireads[i].group;  // (an isoform behind the cut is in no list: group_member_lists)
+            if (h < 0 || h >= n_iso[size_t(g)] || out_ireads[i].how != IOC_ISO_DIRECT || has_key[size_t(full->iso_off[g] + h)]) continue;
+            iso_key[size_t(full->iso_off[g] + h)] = out_ireads[i].key, has_key[size_t(full->iso_off[g] + h)] = 1;
+        }
+        if (G > 0) {
+            const SpliceIn in{iso_key.data(), out_win, site_off, out_wseq, out_wqual, out_woff};
+            int64_t bound = 0;
+            IOC_TRY(splice_ok(c, who, in, full->o, p.segs, n_iso.data(), &bound));
+            GroupPiled gp;
+            IOC_TRY(r.groups_pile(p, seg_of_pair, group.data(), n_iso.data(), Planes{}, Planes{nullptr, nullptr, nullptr, d.base, d.slots}, gp));
+            IOC_TRY(splice_device(r, gp, gp.lists.gseg_off, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), in, full->o, bound));
+        }
+        if (getenv("IOC_TRACE"))
+            fprintf(stderr, "[ioc]   aligner: isoforms full: %lld isoforms, %lld bytes called, k_ops_project_ins %.3f ms, k_group_pile over the isoforms %.3f ms, %s\n",
+                    (long long)G, (long long)full->o.call.off[G], r.t.ms_project_ins, r.t.ms_group_pile, splice_trace(r.t).c_str());
+    }
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: blocks inserts seq: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_project_ilen %.3f ms, k_ops_project_qpos %.3f ms, ms_blocks %.3f ms, %s, %s\n",
                 n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[n_segs], (long long)out_woff[site_off[n_segs]],
                 double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_project_ilen, r.t.ms_project_qpos, r.t.ms_blocks, inserts_trace(r.t).c_str(), windows_trace(r.t).c_str());
     return IOC_OK;
+}
+
+int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                       int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                       const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                       int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                       int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                       int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                       int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                       int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
+                                       int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats)
+{
+    return align_pairs_inserts_seq("ioc_align_pairs_blocks_inserts_seq", nullptr, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+}
+
+// ... -> windows -> groups pile over the combined isoforms -> splice -> copy-out.  ioc_align_pairs_blocks_inserts_seq with the six slot
+// planes projected as well (13 bytes per row and pair), and behind the window kernels k_group_pile over the combined isoforms and
+// the splice kernels.
+int ioc_align_pairs_isoforms_full(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                       int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                       const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                       int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                       int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                       int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                       int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                       int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
+                                       int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t max_iso, char* out_seq, char* out_qual, int64_t cap,
+                                  int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats, ioc_splice_site* out_splice, int64_t splice_cap,
+                                  int64_t* splice_off, int64_t iso_cap, int64_t* iso_off)
+{
+    const IsoFull full{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
+    if (!full.ok()) return IOC_ERR_ARG;
+    return align_pairs_inserts_seq("ioc_align_pairs_isoforms_full", &full, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
 }
 
 // pile -> blocks -> groups pile -> call -> copy-out.  ioc_align_pairs_blocks with the six slot planes projected beside the two, and

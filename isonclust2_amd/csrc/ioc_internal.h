@@ -228,6 +228,7 @@ struct ioc_ctx {
     DevBuf a_windows; // ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq: the tables, the (pair, site) entries and the records of
                       // k_win_bounds / k_win_template and, uploaded, both planes; the alignments' items, planes and direction words share a_gpile
                       // with the group pile behind them
+    DevBuf a_splice;  // ioc_planes_isoforms_full, ioc_align_pairs_isoforms_full: keys, windows, plans, records and the spliced bytes (ioc_iso_splice.hip)
     DevBuf a_blocks;  // ioc_planes_blocks, ioc_align_pairs_blocks: segments, pairs, member lists, bit planes, tables and records (ioc_read_blocks.hip) and,
                       // from host planes, the uploaded planes
     DevBuf a_pile;    // ioc_align_pairs_pileup: the table of the call's rows (k_ops_pileup adds into it, slice after slice)
@@ -578,6 +579,36 @@ hipError_t iock_win_bounds_template(hipStream_t st, const IocWinDev& v, int32_t 
 hipError_t iock_win_align(hipStream_t st, const IocWinItem* items, uint32_t n_items, const uint8_t* pool, uint64_t pool_bytes, uint8_t* base_planes,
                           uint8_t* slot_planes, uint64_t plane_bytes, uint32_t* dir, uint64_t n_dir_words, int32_t match, int32_t mismatch, int32_t gap,
                           int phase);
+
+// ioc_iso_splice.hip: the full-length sequence of every isoform (ioc_host_isoform_splice per group-segment).  Everything is a device
+// pointer.  Group-segment x (n_gsegs of them) is gsegs[x], belongs to segment gseg_seg[x] and carries keys[x]; segment g has the
+// window records site_off[g] .. site_off[g + 1] of `win` (n_sites in all), site k's called bytes at win_off[k] .. win_off[k + 1] of
+// wseq / wqual (win_bytes each).  Group-segment x's site records begin at splice[splice_off[x]] (n_splice in all), its plan at
+// plan[x * IOC_SPLICE_PLAN_MAX] and holds plan_n[x] intervals.
+struct IocSpliceIv;  // (ioc_iso_splice.h: the rows [lo, hi) and the window that replaces them)
+struct IocSpliceDev {
+    const IocPileSeg* gsegs;
+    uint32_t n_gsegs;
+    const int32_t* gseg_seg;
+    const unsigned long long* keys;
+    const ioc_insert_window* win;
+    const long long *site_off, *win_off;
+    uint64_t n_sites;
+    const uint8_t *wseq, *wqual;
+    uint64_t win_bytes;
+    const long long* splice_off;
+    ioc_splice_site* splice;
+    uint64_t n_splice;
+    ioc_splice_stats* sstats;
+    IocSpliceIv* plan;
+    uint32_t* plan_n;
+};
+hipError_t iock_splice_plan(hipStream_t st, const IocSpliceDev& v);
+// k_splice_call: the count pass (emit false: seg_len and stats, a word and a record per group-segment) or the write pass (emit true:
+// the bytes from out_off[x] on, out_bytes of room each, and `at` of the DONE sites); iock_pile_scan goes between them
+hipError_t iock_splice_call(hipStream_t st, const IocSpliceDev& v, bool emit, const ioc_pileup_col* cols, const ioc_pileup_ins* ins, uint64_t n_rows,
+                            const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth, int64_t* seg_len, ioc_polish_stats* stats, const int64_t* out_off,
+                            uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);
 
 // ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
 // is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in
