@@ -926,7 +926,12 @@ int ioc_cluster_consensus(ioc_ctx* ctx, const ioc_params* p, const char* table_p
  * spoa's alignments and consensus tie-breaks is unpinned).  Graphs and heaviest-bundle consensus on the host, the
  * sequence-to-graph DP (local, global or semi-global alignment — `cluster -A`, src/main.cpp:292-324 —, convex gaps as
  * two affine pieces, src/main.cpp:285-290: m 4, n -8, g -8, e -4, q -20, c -1) on the GPU.  Limits: sequences
- * <= 29 999 bases, <= 127 predecessors per node; scores are int32 (negative in global and semi-global alignment).
+ * < 2^20 bases, graphs < 2^21 nodes (more of either: IOC_ERR_CAPACITY from the operation that meets it), <= 127
+ * predecessors per node; cell scores are int32 (negative in global and semi-global alignment).
+ * The six scores: m >= 0, n <= 0, g <= e <= 0, q <= c <= 0 (a gap is never cheaper to open than to extend: the row scan
+ * relies on it), and each within int8, -128 .. 127, the type the reference passes them in — with the two size limits
+ * that keeps every cell's arithmetic inside int32 and apart from the engine's "no value" sentinel (derived at
+ * ioc_poa_create_mode in ioc_poa.hip).  Anything else: IOC_ERR_ARG from create.
  * The DP's rows: 0 = a virtual source, 1..R = the nodes in topological order; columns 0..L = the read;
  * gap(k) = max(g + (k-1) e, q + (k-1) c).
  *   local:        H >= 0 everywhere (row 0 and column 0: 0); the best cell of the matrix ends it; the walk ends at a 0.

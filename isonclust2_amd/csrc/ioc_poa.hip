@@ -44,6 +44,8 @@ constexpr int POA_NEG = INT32_MIN / 4;
 #endif
 constexpr int POA_THREADS = IOC_POA_THREADS;  // columns of a tile = threads of its workgroup (a multiple of 64)
 constexpr int POA_MAX_COLS = 1 << 20;
+constexpr int POA_MAX_ROWS = 1 << 21;   // rows of one alignment, row 0 included (ioc_poa_create_mode has the arithmetic behind both)
+constexpr int POA_MAX_SCORE = 128;      // |m|, |n|, |g|, |e|, |q|, |c| <= 128: create takes int8 values only
 constexpr int POA_MAX_PREDS = 127;
 
 // direction word: [1:0] source of Hn (0 stop, 1 diagonal, 2 F1, 3 F2)  [7] F1 extended  [8] F2 extended
@@ -204,7 +206,7 @@ k_poa_tile(const PoaJob* __restrict__ jobs, int diag, PoaScores S, int pred_lds)
     const bool active = j < W;
     const int jj = min(j, W - 1);  // threads past the last column run along and store nothing
     const uint32_t jb4 = uint32_t(jj) * 4u;  // (W <= 2^20: fits)
-    const int ofs_e = active ? -S.e * j : POA_NEG, ofs_c = active ? -S.c * j : POA_NEG;  // (hn < 2^23: POA_NEG + hn stays an outsider)
+    const int ofs_e = active ? -S.e * j : POA_NEG, ofs_c = active ? -S.c * j : POA_NEG;  // (hn < 2^27, ioc_poa_create_mode: POA_NEG + hn stays below every real hn - e j)
     const int r_lo = rb * POA_RB + 1, r_hi = min(R, r_lo + POA_RB - 1);
     const GI32* cin_row = carry + int64_t(max(cb, 1) - 1) * (R + 1) * 4;
     GI32* cout_row = carry + int64_t(cb) * (R + 1) * 4;
@@ -1128,6 +1130,7 @@ int poa_align_batch(ioc_poa* p, std::vector<HostJob>& jobs)
         l.R = int(G.n_nodes());
         l.L = int(seq.size());
         if (l.L + 1 > POA_MAX_COLS) return ioc_fail(c, IOC_ERR_CAPACITY, "POA: sequences above 2^20 bases are not supported");
+        if (l.R + 1 > POA_MAX_ROWS) return ioc_fail(c, IOC_ERR_CAPACITY, "POA: graphs above 2^21 nodes are not supported");
         l.ncb = (l.L + 1 + POA_CB - 1) / POA_CB;
         l.nrb = (l.R + POA_RB - 1) / POA_RB;
         l.cap = l.R + l.L + 2;
@@ -1623,6 +1626,23 @@ int ioc_poa_create_mode(ioc_ctx* ctx, int32_t mode, int32_t m, int32_t n, int32_
     // the row scan computes horizontal gaps from H-without-gaps: valid when opening is no cheaper than extending
     if (!(g <= e && e <= 0 && q <= c && c <= 0 && n <= 0 && m >= 0))
         return ioc_fail(ctx, IOC_ERR_ARG, "POA scores: need m >= 0, n <= 0, g <= e <= 0, q <= c <= 0");
+    // The scores' range.  k_poa_tile computes in int32 next to the sentinel POA_NEG = -2^29; with S = POA_MAX_SCORE = 128 (int8, the
+    // type the reference passes, src/main.cpp:285-290), W = L + 1 <= POA_MAX_COLS = 2^20 columns and R + 1 <= POA_MAX_ROWS = 2^21 rows:
+    //   * a real H is at most m min(R, L) <= 127 * 2^20 < 2^27 and, without a floor (global alignment), at least the all-gap walk
+    //     to its cell, -S (r + j) >= -S (R + L); F1 / F2 of a node row are at least H of a predecessor + g, so every real value
+    //     v has -S (R + L + 1) <= v < 2^27, and -S (R + L + 1) > -128 * 3 * 2^20 = -3 * 2^27;
+    //   * the scan's terms: hn + ofs with ofs = -e j <= 127 * 2^20 < 2^27 lies in (-3 * 2^27, 2^28); (j - 1) e >= -2^27, so
+    //     ex + g + (j - 1) e lies in (-4 * 2^27 - 128, 2^28); row 0's g + (j - 1) e >= -2^27 - 128.  All inside int32;
+    //   * a sentinel is added to at most once before a maximum drops it — POA_NEG + e or + c (row 0's F1 / F2; row 1's are
+    //     real again), POA_NEG + hn (the lanes past the last column) — and the sum lies in (-2^29 - 3 * 2^27, -2^29 + 2^27): above
+    //     INT32_MIN, and below every real value because -2^29 + 2^27 = -3 * 2^27.  A real value compared with a bare POA_NEG
+    //     (the left edge's carry, the floor-less hn, a tile without an end cell) wins for the same reason.
+    // So int8 scores are safe exactly because the rows are bounded: 128 (R + L + 1) < 3 * 2^27 needs R + L + 1 < 3 * 2^20, which
+    // L + 1 <= 2^20 and R + 1 <= 2^21 give (poa_align_batch refuses more of either).  Without the row bound a graph of 2^22 nodes
+    // against a short read — 5 bytes a cell, it fits — would take global alignment's column 0 below POA_NEG.
+    for (const int32_t v : {m, n, g, e, q, c})
+        if (v < -POA_MAX_SCORE || v > POA_MAX_SCORE - 1)
+            return ioc_fail(ctx, IOC_ERR_ARG, "POA scores: each of m, n, g, e, q, c must lie in -128 .. 127");
     ioc_poa* p = new ioc_poa;
     p->ctx = ctx;
     p->S = PoaScores{m, n, g, e, q, c};

@@ -4,7 +4,7 @@ SC = dict(m=4, n=-8, g=-8, e=-4, q=-20, c=-1)   # src/main.cpp:285-290
 NEG = -10 ** 9
 
 
-def _ref_score(bases, rank, ef, et, seq):
+def _ref_score(bases, rank, ef, et, seq, sc=SC):
     """Local sequence-to-graph alignment, convex gap = best of two affine pieces (plain loops)."""
     n, L = len(bases), len(seq)
     preds = {v: [] for v in range(n)}
@@ -19,21 +19,21 @@ def _ref_score(bases, rank, ef, et, seq):
         h, f1, f2 = [0] * (L + 1), [NEG] * (L + 1), [NEG] * (L + 1)
         e1 = e2 = NEG
         for j in range(L + 1):
-            f1[j] = max(max(H[p][j] + SC["g"], F1[p][j] + SC["e"]) for p in ps)
-            f2[j] = max(max(H[p][j] + SC["q"], F2[p][j] + SC["c"]) for p in ps)
+            f1[j] = max(max(H[p][j] + sc["g"], F1[p][j] + sc["e"]) for p in ps)
+            f2[j] = max(max(H[p][j] + sc["q"], F2[p][j] + sc["c"]) for p in ps)
             if j == 0:
                 h[j] = 0
                 continue
-            e1 = max(h[j - 1] + SC["g"], e1 + SC["e"])
-            e2 = max(h[j - 1] + SC["q"], e2 + SC["c"])
-            s = SC["m"] if bases[v] == seq[j - 1] else SC["n"]
+            e1 = max(h[j - 1] + sc["g"], e1 + sc["e"])
+            e2 = max(h[j - 1] + sc["q"], e2 + sc["c"])
+            s = sc["m"] if bases[v] == seq[j - 1] else sc["n"]
             h[j] = max(0, max(H[p][j - 1] for p in ps) + s, f1[j], f2[j], e1, e2)
             best = max(best, h[j])
         H[v], F1[v], F2[v] = h, f1, f2
     return best
 
 
-def _path_score(bases, ef, et, seq, nodes, pos):
+def _path_score(bases, ef, et, seq, nodes, pos, sc=SC):
     """Score of an alignment path, checking that it IS a walk through the graph and the read."""
     edges = set(zip(ef.tolist(), et.tolist()))
     total, run_kind, run_len = 0, None, 0
@@ -42,7 +42,7 @@ def _path_score(bases, ef, et, seq, nodes, pos):
     def close():
         nonlocal total, run_kind, run_len
         if run_len:
-            total += max(SC["g"] + (run_len - 1) * SC["e"], SC["q"] + (run_len - 1) * SC["c"])
+            total += max(sc["g"] + (run_len - 1) * sc["e"], sc["q"] + (run_len - 1) * sc["c"])
         run_kind, run_len = None, 0
 
     for v, p in zip(nodes.tolist(), pos.tolist()):
@@ -55,7 +55,7 @@ def _path_score(bases, ef, et, seq, nodes, pos):
         kind = "diag" if v >= 0 and p >= 0 else ("vert" if v >= 0 else "horz")
         if kind == "diag":
             close()
-            total += SC["m"] if bases[v] == seq[p] else SC["n"]
+            total += sc["m"] if bases[v] == seq[p] else sc["n"]
         else:
             if kind != run_kind:
                 close()

@@ -24,10 +24,12 @@ def _graph(n, ef, et):
     return preds, sink
 
 
-def mode_score(bases, rank, ef, et, seq, mode, sc=SC):
+def mode_score(bases, rank, ef, et, seq, mode, sc=SC, planes=None):
     """Best end cell of the sequence-to-graph DP.  Rows: row 0 the virtual source, then the nodes in the order `rank`;
     columns 0..L.  Per row, numpy over the columns: vertical moves F1 / F2 and the diagonal from the predecessors, then the
-    horizontal gaps as prefix maxima of H-without-them (opening right after a gap never beats extending it: g <= e, q <= c)."""
+    horizontal gaps as prefix maxima of H-without-them (opening right after a gap never beats extending it: g <= e, q <= c).
+    planes: a dict that receives the rows themselves, {"H" | "F1" | "F2": {node (-1: row 0): row}} and "preds": the
+    predecessor lists in in-edge order ([-1] for a node without in-edges)."""
     n, L = len(bases), len(seq)
     preds, sink = _graph(n, ef, et)
     read = np.frombuffer(bytes(seq), np.uint8).astype(np.int64)
@@ -53,6 +55,9 @@ def mode_score(bases, rank, ef, et, seq, mode, sc=SC):
             pm = np.maximum.accumulate(hn - e * cols)       # max over x <= j of Hn[x] - e x
             h[1:] = np.maximum(h[1:], pm[:-1] + g + (cols[1:] - 1) * e)
         H[v], F1[v], F2[v] = h, f1, f2
+        if planes is not None:
+            planes.update(H=H, F1=F1, F2=F2)
+            planes.setdefault("preds", {})[v] = ps
         if mode == LOCAL:
             cand = int(h.max())                                  # every cell
         elif mode == GLOBAL:
@@ -74,7 +79,7 @@ def mode_path_score(bases, ef, et, seq, nodes, pos, mode, sc=SC):
     """Score of an alignment path (poa_common._path_score checks that it is a walk) plus what its type's boundary charges: a
     semi-global walk that stopped on row 0 left the read's head unaligned at gap(first read position) (on column 0 that is 0).
     Global paths carry their row-0 insertions as pairs of their own."""
-    total = _path_score(bases, ef, et, seq, nodes, pos)
+    total = _path_score(bases, ef, et, seq, nodes, pos, sc)
     if mode == SEMI_GLOBAL:
         p0 = first_read_pos(pos)
         total += gap(p0, sc) if p0 is not None else 0

@@ -19,10 +19,11 @@ NEG = -10 ** 9
 
 
 class Poa:
-    def __init__(self, ctx):
+    def __init__(self, ctx, **sc):
+        sc = dict(SC, **sc)                          # (tests/test_gpu_poa_params.py: other scores than the reference's)
         self.L = _lib.load()
         self.h = C.c_void_p()
-        rc = self.L.ioc_poa_create(ctx.h, SC["m"], SC["n"], SC["g"], SC["e"], SC["q"], SC["c"], C.byref(self.h))
+        rc = self.L.ioc_poa_create(ctx.h, sc["m"], sc["n"], sc["g"], sc["e"], sc["q"], sc["c"], C.byref(self.h))
         assert rc == 0
         self.ops = _lib.ConsensusOps()
         self.L.ioc_poa_bind(self.h, C.byref(self.ops))

@@ -18,10 +18,11 @@ pytestmark = pytest.mark.gpu
 class ModePoa(Poa):
     """the engine of test_gpu_poa.Poa, created through ioc_poa_create_mode"""
 
-    def __init__(self, ctx, mode):
+    def __init__(self, ctx, mode, **sc):
+        sc = dict(SC, **sc)
         self.L = _lib.load()
         self.h = C.c_void_p()
-        rc = self.L.ioc_poa_create_mode(ctx.h, mode, SC["m"], SC["n"], SC["g"], SC["e"], SC["q"], SC["c"], C.byref(self.h))
+        rc = self.L.ioc_poa_create_mode(ctx.h, mode, sc["m"], sc["n"], sc["g"], sc["e"], sc["q"], sc["c"], C.byref(self.h))
         assert rc == 0, rc
         self.ops = _lib.ConsensusOps()
         self.L.ioc_poa_bind(self.h, C.byref(self.ops))

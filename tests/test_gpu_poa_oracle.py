@@ -35,9 +35,9 @@ def ctx():
 OFF_LOCAL = [GLOBAL, SEMI_GLOBAL]
 
 
-def _stores(ctx, t):
-    """the engine and the oracle under alignment type t"""
-    return (Poa(ctx) if t == LOCAL else ModePoa(ctx, t)), po.OraclePoa(mode=t)
+def _stores(ctx, t, **sc):
+    """the engine and the oracle under alignment type t (sc: scores other than the reference's, test_gpu_poa_params.py)"""
+    return (Poa(ctx, **sc) if t == LOCAL else ModePoa(ctx, t, **sc)), po.OraclePoa(mode=t, **sc)
 
 
 def _rand(rng, n, alphabet=b"ACGT"):
@@ -128,10 +128,10 @@ def test_random_additions_give_the_oracles_graphs_off_local(ctx, t):
     _random_additions(ctx, t)
 
 
-def _low_complexity(ctx, poa_type):
+def _low_complexity(ctx, poa_type, **sc):
     rng = random.Random(43)
     for g in range(12):
-        dev, orc = _stores(ctx, poa_type)
+        dev, orc = _stores(ctx, poa_type, **sc)
         unit = bytes(rng.choice(b"AC") for _ in range(rng.choice([2, 3, 5])))
         truth = (unit * 80)[: rng.choice([60, 150, 240])]
         dev.create(0, truth)
