@@ -1759,7 +1759,9 @@ struct V2Dev {
     V2PairEnd* pend;
     V2Item* items;
     int2 *lrow, *best;
-    uint32_t* ctl;  // [queue][err][pad ...][flags][rows of a tile's right edge that are out (v2_wait_rows)][ovf per pair][computed cells, 8-byte aligned]
+    // [queue][err][pad][pad][tiles computed][links without a left side][links with the left tile done][pad ...][flags][rows of a tile's
+    // right edge that are out (v2_wait_rows)][ovf per pair][claims, indexed like the flags (v2_fwd_body: links)][computed cells, 8-byte aligned]
+    uint32_t* ctl;
     size_t ctl_words;
     V2Scratch *scratch, *hscratch;
     uint32_t* resume;  // per pair: V2_RESUME_WORDS of parked state and records
@@ -1791,7 +1793,7 @@ int v2_tables(ioc_ctx* c, const V2Plan& pl, uint32_t help_wgs, V2Dev& t)
     IOC_TRY(ioc_reserve(c, c->a_lrow, (size_t(pl.lrow_total) + pl.best_total + 16) * sizeof(int2)));
     t.lrow = static_cast<int2*>(c->a_lrow.p);
     t.best = t.lrow + pl.lrow_total;
-    t.ctl_words = ((16 + 2 * size_t(pl.max_flags) + np + 1) & ~size_t(1)) + 2;
+    t.ctl_words = ((16 + 3 * size_t(pl.max_flags) + np + 1) & ~size_t(1)) + 2;
     IOC_TRY(ioc_reserve(c, c->a_xflags, t.ctl_words * 4));
     t.ctl = static_cast<uint32_t*>(c->a_xflags.p);
     // per pair: its own scratch and 16 words of parked state and records; (the helper buffers belong to the second launch's
@@ -1832,10 +1834,10 @@ uint32_t v2_per_cu(const V2Plan& pl, size_t si, const V2Opts& o, bool few_couple
 }
 
 // One slice's launches: profiles, probe, forward pass, ends, traceback (events ev[0 .. 3) around them), then its error word
-// (*xe: a bounded wait ran out) and computed cells.
+// (*xe: a bounded wait ran out), computed cells and links (link_sum[0 .. 3) += tiles computed, links of either kind).
 // `od`: an emitting call — the traceback launches are the emitting kernels, the same launches otherwise.
 int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Opts& o, const AlnParams& P, const uint32_t* d_order,
-             int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, uint32_t* xe, const AlnOpsDev* od, StageTrace& tr)
+             int32_t* d_score, uint32_t* d_count, const hipEvent_t* ev, uint32_t* xe, uint32_t* link_sum, const AlnOpsDev* od, StageTrace& tr)
 {
     hipStream_t s = c->stream;
     const uint32_t k_first = pl.slices[si].first, n_couples = pl.slices[si].second;
@@ -1848,6 +1850,9 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     // publishes its progress every block of 64 rows)
     const bool few_couples = n_couples <= o.few_limit;
     const uint32_t prog_every = few_couples ? 1u : 0u;
+    // (IOC_ALIGN_V2_LINK=0: no claims, no run goes on into the band below — v2_fwd_body)
+    const bool links = !(getenv("IOC_ALIGN_V2_LINK") && atoi(getenv("IOC_ALIGN_V2_LINK")) == 0);
+    uint32_t* const d_claims = links ? d_ctl + 16 + 2 * pl.max_flags + pl.np : static_cast<uint32_t*>(nullptr);
     // the slice's list of tiles, from the couples as the host planned them (v2_tables sent them up; the probe's verdicts, which
     // rewrite a couple's corridor, come after the list and never enter it)
     const bool items_check = !pl.items.empty();  // (IOC_V2_ITEMS_CHECK)
@@ -1868,14 +1873,14 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     }
     IOC_CHK(c, hipEventRecord(ev[0], s));
     // persistent waves: as many workgroups as the chip holds, but no more waves than tiles
-    auto fwd = [&](decltype(&k_fwd2) kernel, uint32_t n_wg, const V2Item* items, uint32_t n) {
+    auto fwd = [&](decltype(&k_fwd2) kernel, uint32_t n_wg, const V2Item* items, uint32_t n, uint32_t link_mode) {
         hipLaunchKernelGGL(kernel, dim3(n_wg), dim3(64 * V2_WAVES), 0, s, d_pairs, t.cps, items, n, d_ctl, d_ctl + 16, d_ctl + 1, d_pool, P,
                            static_cast<uint32_t*>(c->a_ck.p), t.lrow, t.best, d_ctl + 16 + 2 * pl.max_flags, o.guard, static_cast<const uint4*>(c->a_prof.p),
                            reinterpret_cast<unsigned long long*>(d_ctl + t.ctl_words - 2), few_couples ? d_ctl + 16 + pl.max_flags : static_cast<uint32_t*>(nullptr),
-                           prog_every);
+                           prog_every, d_claims, link_mode);
     };
     if (n_probe) {  // the probe launch and its verdicts (V2Couple): all on the device, nothing comes back to the host
-        fwd(k_fwd2, std::max(1u, std::min(uint32_t(o.occ) * uint32_t(o.n_cu), (n_probe + V2_WAVES - 1) / V2_WAVES)), t.items, n_probe);
+        fwd(k_fwd2, std::max(1u, std::min(uint32_t(o.occ) * uint32_t(o.n_cu), (n_probe + V2_WAVES - 1) / V2_WAVES)), t.items, n_probe, 2u);
         IOC_CHK(c, hipGetLastError());
         hipLaunchKernelGGL(k_fwd2_probe, dim3(n_couples), dim3(64), 0, s, d_pairs, t.cps + k_first, t.pend, static_cast<const uint32_t*>(c->a_ck.p), P);
         IOC_CHK(c, hipGetLastError());
@@ -1889,7 +1894,7 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner v2: shape: slice %zu: %u couples, waits for %s, per_cu %u, n_wg %u, kernel %s, n_probe %u\n", si, n_couples,
                 few_couples ? "rows" : "tiles", per_cu, n_wg, w2 ? "k_fwd2_w2" : "k_fwd2", n_probe);
-    fwd(w2 ? k_fwd2_w2 : k_fwd2, n_wg, t.items + n_probe, n_main);
+    fwd(w2 ? k_fwd2_w2 : k_fwd2, n_wg, t.items + n_probe, n_main, 1u);
     IOC_CHK(c, hipGetLastError());
     const uint32_t n_help = std::min<uint32_t>(n_pairs, o.help_wgs);
     hipLaunchKernelGGL(k_fwd2_ends, dim3(n_pairs), dim3(64), 0, s, d_pairs, t.cps, d_order + first_pair, n_pairs, t.pend, t.lrow, t.best,
@@ -1934,10 +1939,13 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
     unsigned long long cells_done = 0;
     IOC_CHK(c, hipMemcpyAsync(xe, d_ctl + 1, 4, hipMemcpyDeviceToHost, s));
     IOC_CHK(c, hipMemcpyAsync(&cells_done, d_ctl + t.ctl_words - 2, 8, hipMemcpyDeviceToHost, s));
+    uint32_t link_counts[3] = {0, 0, 0};
+    if (getenv("IOC_TRACE")) IOC_CHK(c, hipMemcpyAsync(link_counts, d_ctl + 4, sizeof link_counts, hipMemcpyDeviceToHost, s));
     tr.mark("v2_slice other launches");
     IOC_CHK(c, hipStreamSynchronize(s));
     tr.mark("v2_slice wait (device)");
     c->tm.n_align_cells_computed += int64_t(cells_done);
+    for (int x = 0; x < 3; ++x) link_sum[x] += link_counts[x];
     if (items_check) IOC_TRY(device_probe_report(c, pl, t.cps, si));
     return IOC_OK;
 }
@@ -2136,9 +2144,10 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan0).count());
     size_t evi = 0;
     bool bad = false;
+    uint32_t link_sum[3] = {0, 0, 0};  // (IOC_TRACE: tiles computed, links without a left side, links with the left tile done)
     for (size_t si = 0; si < pl.slices.size() && !bad; ++si, evi += 3) {
         uint32_t xe = 0;
-        if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe, ops ? &ops->dev : nullptr, tr)) != IOC_OK) return r;
+        if ((r = v2_slice(c, pl, t, si, o, P, d_order, d_score, d_count, &evs.v[evi], &xe, link_sum, ops ? &ops->dev : nullptr, tr)) != IOC_OK) return r;
         if (ops && !xe) {
             const uint32_t x0 = 2u * pl.slices[si].first, x1 = std::min(cnt, 2u * (pl.slices[si].first + pl.slices[si].second));
             if ((r = ops_fetch(c, *ops, dp, order + x0, d_order + x0, x1 - x0, slice_ops[si])) != IOC_OK) return r;
@@ -2148,6 +2157,9 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     }
     add_elapsed(c, evs.v, evi);
     tr.mark("elapsed times");
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner v2: links: %u of %u (%u without a left side, %u with the left tile done)\n", link_sum[1] + link_sum[2], link_sum[0],
+                link_sum[1], link_sum[2]);
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner v2: forward %.3f ms, traceback %.3f ms (device, all slices so far)%s\n", c->tm.ms_align_fwd,
                 c->tm.ms_align_trace, bad ? " — a wait ran out: falling back to version 1" : "");

@@ -22,6 +22,8 @@
 //    (V2Couple, k_fwd2_probe, k_fwd2_ends); a refuted pair runs again with every tile.  Results never depend on it.
 //  * The wrong candidates' walks run beside the others' (k_fwd2_ends routes them by their score to k_trace2_help on a side stream),
 //    a launch with few couples lets a tile follow its left neighbour row by row (v2_wait_rows).
+//  * LINKS: a wave goes on from a tile into the tile below it, skew and registers as they are, where that takes no wait
+//    (v2_fwd_body; IOC_ALIGN_V2_LINK=0: never).
 //
 // Slanted scores, Hq = H* - (go - ge), the profile in LDS, the look-ahead ring, the 4-row steps and the lane skew are
 // those of k_align_fwd (see there).
@@ -201,7 +203,9 @@ __device__ __forceinline__ void v2_lds_store(uint32_t lds_byte_addr, uint32_t v)
 enum V2Par : uint32_t {
     VP_N0 = 0, VP_N1, VP_M0, VP_M1, VP_GD0, VP_GD1, VP_LROW0, VP_LROW1, VP_BEST0, VP_BEST1, VP_PID0, VP_PID1,
     VP_RDAT_LO, VP_RDAT_HI, VP_RBASE_LO, VP_RBASE_HI, VP_CDAT_LO, VP_CDAT_HI, VP_CBASE_LO, VP_CBASE_HI,
-    VP_MPAD, VP_NQ, VP_FLAG, VP_BAND, VP_STRIP, VP_COLIN_LO, VP_COLIN_HI, VP_RHI0, VP_RHI1, VP_COUNT = 32
+    VP_MPAD, VP_NQ, VP_FLAG, VP_BAND, VP_STRIP, VP_COLIN_LO, VP_COLIN_HI, VP_RHI0, VP_RHI1,
+    VP_COUPLE, VP_FLAG_PREV, VP_BND_PREV,  // (links: the couple's number; the flag and the first row block of the band a run has just left)
+    VP_COUNT = 32
 };
 
 // The query profiles of every (couple, strip), made ONCE per batch: per pair, base code and lane the score increments of the lane's
@@ -317,8 +321,24 @@ static __device__ __forceinline__ void
 v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ couples, const V2Item* __restrict__ items, uint32_t n_items,
        uint32_t* __restrict__ queue, uint32_t* __restrict__ flags, uint32_t* __restrict__ err, const uint8_t* __restrict__ pool, AlnParams P,
        uint32_t* __restrict__ arena, int2* __restrict__ lrow, int2* __restrict__ bandbest, uint32_t* __restrict__ ovf_out, int guard,
-       const uint4* __restrict__ prof, unsigned long long* __restrict__ cells_done, uint32_t* __restrict__ prog, uint32_t prog_every)
+       const uint4* __restrict__ prof, unsigned long long* __restrict__ cells_done, uint32_t* __restrict__ prog, uint32_t prog_every,
+       uint32_t* __restrict__ claims, uint32_t link_mode)
 {
+    // LINKS (claims != nullptr).  A wave that is about to finish tile (b, p) goes on into (b + 1, p) with its lanes' skew and registers
+    // as they are — the run is one tall tile, and the 63 steps of pipeline fill of (b + 1, p) are never issued — whenever that
+    // needs NO WAIT: the tile has no left side (strip 0, or the leftmost strip of its band's corridor), or its left neighbour's
+    // flag reads done at the moment of the decision.  (The general case does not fit: the list orders tiles by anti-diagonal, so
+    // the left neighbour (b + 1, p - 1) was dequeued together with (b, p) and ends together with it — following it takes a wait
+    // row by row.)  A tile is owned by whoever adds to its CLAIM word first — the wave that dequeued it, once its waits are over,
+    // or the wave that runs into it —, the other leaves it alone.  The decision falls 32 steps before lane 0 leaves the band: from there the look-ahead
+    // ring fetches the next band's left edge and query codes.  Everything per band switches there for the wave (rows of either
+    // pair, last_band, the left edge, the flag, nsteps) or, where lanes of both bands are in flight, per lane by its row block
+    // (`bnd`: the run-relative row block the newest band starts at): the best of the last column, the tile's publication
+    // (once the last lane has left it: step bnd + 64) and the rows of its right edge that are out.  A run goes on while either
+    // pair has rows further down; the half of a pair that has none is put back to the bias once per band (finish_prev).
+    // link_mode 2 (the probe launch): only inside the probe's grid — a tile beyond it may get a wider corridor from k_fwd2_probe.
+    uint32_t* const link_stats = queue + 4;  // tiles computed, links without a left side, links with the left tile done
+    constexpr uint32_t NEVER = 0xFFFFFFFFu;
     __shared__ __attribute__((aligned(16))) uint32_t s_look_all[V2_WAVES][3][128];
     __shared__ __attribute__((aligned(16))) uint32_t s_prof_all[V2_WAVES][2][5][64][4];  // [wave][pair][base code][lane][4 words]
     __shared__ uint32_t s_par_all[V2_WAVES][VP_COUNT];
@@ -343,6 +363,8 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
         bool top_none = false;  // (corridor: nothing above this tile — the lanes' top row is "no score")
         bool left_rows = false;  // (few couples: the tile to the left is waited for row by row, v2_wait_rows)
         uint32_t left_idx = 0, nblk_band = 0, left_avail = 0;
+        uint32_t bnd = 0;           // (links) the row block of the run at which its newest band starts
+        uint32_t link_at = NEVER;   // (links) the step at which the run decides about the next band
         const uint8_t* q[2];
         int base[2];
         uint32_t gd2;
@@ -359,8 +381,11 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
             band = item.band;
             p = item.strip;
             // (corridor: a tile outside its couple's corridor is not computed; a tile the probe launch did is done)
+            // (links: ... and a tile a run went on into, or is about to, is that run's)
             if (p < cp.plo[band] || p > cp.phi[band] ||
-                __builtin_amdgcn_readfirstlane(int(__hip_atomic_load(&flags[cp.flag0 + band * cp.nstrips + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) != 0) {
+                __builtin_amdgcn_readfirstlane(int(__hip_atomic_load(&flags[cp.flag0 + band * cp.nstrips + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) != 0 ||
+                (claims != nullptr &&
+                 __builtin_amdgcn_readfirstlane(int(__hip_atomic_load(&claims[cp.flag0 + band * cp.nstrips + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) != 0)) {
                 it = v2_dequeue(queue);
                 continue;
             }
@@ -383,6 +408,12 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
             }
             if (left_in && !left_rows) (void)v2_wait(&flags[left_idx], err);
             if (left_rows) (void)v2_wait_rows(&prog[left_idx], &flags[left_idx], min(32u, nblk_band), err, left_avail);  // (the first two fetches: 128 rows)
+            // (links: the tile is this wave's only if it is the first to claim it — the wave that ran the tile above may have gone
+            // on into it while this one waited.  Claimed AFTER the waits: a wave that merely waits on a tile does not keep a run out of it.)
+            if (claims != nullptr && v2_dequeue(&claims[left_idx + 1u]) != 0u) {
+                it = v2_dequeue(queue);
+                continue;
+            }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             r_lo = uint32_t(cp.bstart[band]) * uint32_t(CK2);  // (both pairs: bands start on the same coarse rows)
             const uint32_t jb = p * strip_cols + lane * FW_C;
@@ -403,6 +434,10 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
                 last_band[h] = vh[h] && r_hi[h] == n[h];
             }
             gd2 = packu(uint32_t(gd[0]), uint32_t(gd[1]));
+            // (links: a band further down with rows of a pair that has columns here — then this band is whole: a multiple of 128 row blocks)
+            if (claims != nullptr && band + 1u < cp.nbands && nblk_band >= 128u &&
+                max(vh[0] ? n[0] : 0u, vh[1] ? n[1] : 0u) > uint32_t(cp.bstart[band + 1u]) * uint32_t(CK2))
+                link_at = nblk_band - 32u;
             mpad = cp.mpad;
             rd_off = cp.rdat + jb;
             rb_off = cp.rbase + uint64_t(jb / 16u) * 2u;
@@ -449,6 +484,9 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
                 s_par[VP_COLIN_HI] = uint32_t(colin >> 32);
                 s_par[VP_RHI0] = r_hi[0];
                 s_par[VP_RHI1] = r_hi[1];
+                s_par[VP_COUPLE] = item.couple;
+                s_par[VP_FLAG_PREV] = 0;
+                s_par[VP_BND_PREV] = 0;
             }
             // ---- top edge: row 0 of the matrices, or the coarse row the band above wrote ----
             int Ha[2][FW_C], Fa[2][FW_C], dga[2];
@@ -525,7 +563,7 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
         }
         // ---- per-lane facts of the tile (VGPRs) ----
         const uint32_t jb = p * strip_cols + lane * FW_C;
-        const uint32_t nsteps = max(nblk[0], nblk[1]) + 63u;
+        uint32_t nsteps = max(nblk[0], nblk[1]) + 63u;  // (links: grows with every band the run goes on into)
         uint32_t lanef = 0;  // bit h: has columns of pair h; bit 2 + h: owns the last column of pair h; bit 4: stores a coarse column
         int lastc[2];
         uint32_t ncl[2];
@@ -608,10 +646,95 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
         uint32_t bc_i[2] = {0, 0};
         uint32_t ovf = 0;
 
+        // (links) the band the run has left is out: the best of the last column of a pair that ended in it (a pair that goes on
+        // wrote its own when its lane crossed), every store of the wave, the release, the tile's flag — as at the end of a tile
+        auto finish_prev = [&]() {
+            const uint32_t bp = uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_BND_PREV))));
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (lastc[h] >= 0 && nblk[h] <= bnd && nblk[h] > bp) bandbest[par(VP_BEST0 + h) + band - 1u] = int2{bc[h], int(bc_i[h])};
+            const uint32_t prev_flag = uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_FLAG_PREV))));
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(&flags[prev_flag], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // A half without rows in the newest band is idle in every lane by now.  It starts the band the way a tile of its own would:
+            // at the bias.  (Nothing reads it; but it is not rebased with the live half, and left to itself down a long run the low
+            // one could drift to the top of its 16 bits and carry into the high one.)
+            uint32_t keep = 0xFFFFFFFFu, fill = 0u;
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (!vh[h] || nblk[h] <= bnd) {
+                    keep &= ~(0xFFFFu << (16 * h));
+                    fill |= uint32_t(U16_BIAS) << (16 * h);
+                }
+            if (keep != 0xFFFFFFFFu) {
+#pragma unroll
+                for (int c = 0; c < FW_C; ++c) {
+                    Hp[c] = (Hp[c] & keep) | fill;
+                    F[c] = (F[c] & keep) | fill;
+                }
+#pragma unroll
+                for (int rr = 0; rr < FW_R; ++rr) {
+                    hl[rr] = (hl[rr] & keep) | fill;
+                    el[rr] &= keep;
+                }
+                dg = (dg & keep) | fill;
+            }
+        };
+        // (links) the decision, wave-uniform, at step link_at = 32 steps before lane 0 leaves the band: no loop, no sleep, no wait
+        auto link_decide = [&]() {
+            const V2Couple* cq = couples + uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_COUPLE))));
+            const uint32_t nb = band + 1u;  // (< nbands: link_at is only set then)
+            const uint32_t lo = cq->plo[nb], hi = cq->phi[nb];
+            const uint32_t fi = cq->flag0 + nb * cq->nstrips + p;
+            bool go = p >= lo && p <= hi;
+            if (link_mode == 2u) go = go && nb <= uint32_t(cq->probe_band) && p <= uint32_t(cq->probe_strip);
+            uint32_t kind = 0;
+            if (go) {
+                if (p == 0u || p == lo) kind = 1u;
+                else if (__builtin_amdgcn_readfirstlane(int(__hip_atomic_load(&flags[fi - 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) != 0) kind = 2u;
+                go = kind != 0u && __builtin_amdgcn_readfirstlane(int(__hip_atomic_load(&flags[fi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) == 0 &&
+                     v2_dequeue(&claims[fi]) == 0u;
+            }
+            link_at = NEVER;
+            if (!go) return;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            const uint32_t bend = uint32_t(cq->bstart[nb + 1u]) * uint32_t(CK2);
+            uint32_t nn[2], rh[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                nn[h] = uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_N0 + h))));
+                rh[h] = min(nn[h], bend);
+                if (vh[h]) {  // (a pair that ended higher up keeps its rows; one that never had any keeps none)
+                    nblk[h] = (rh[h] - r_lo + FW_R - 1) / FW_R;
+                    last_band[h] = rh[h] == nn[h];
+                }
+            }
+            const uint32_t old_flag = par(VP_FLAG);
+            v2_lds_store(par_addr + 4u * VP_FLAG_PREV, old_flag);
+            v2_lds_store(par_addr + 4u * VP_BND_PREV, bnd);
+            v2_lds_store(par_addr + 4u * VP_FLAG, fi);
+            v2_lds_store(par_addr + 4u * VP_BAND, nb);
+            v2_lds_store(par_addr + 4u * VP_RHI0, rh[0]);
+            v2_lds_store(par_addr + 4u * VP_RHI1, rh[1]);
+            bnd = nblk_band;
+            nblk_band = (min(max(nn[0], nn[1]), bend) - r_lo + FW_R - 1) / FW_R;
+            nsteps = max(nblk[0], nblk[1]) + 63u;
+            band = nb;
+            left_ok = p == 0u || p > lo;
+            left_rows = false;  // (no left side, or a left tile that is done)
+            if (nb + 1u < cq->nbands && max(vh[0] ? nn[0] : 0u, vh[1] ? nn[1] : 0u) > bend) link_at = nblk_band - 32u;
+            (void)v2_dequeue(link_stats);  // (one more tile)
+            (void)v2_dequeue(link_stats + kind);
+        };
+
         // (first: the step may be the first of a group of 16 — rebase, publish, fetch; the loop below runs two steps per
         // iteration from an even number, so only the first of the two can be)
         auto step = [&](const uint32_t s, auto first) __attribute__((always_inline)) {
             if (decltype(first)::value && (s & (64 / FW_R - 1)) == 0) {
+                if (s == link_at) link_decide();
+                if (bnd != 0u && s == bnd + 64u) finish_prev();  // (lane 63 stored the last row block of the band above at step bnd + 62)
                 if (s) {
                     // ---- rebase: advance each base by the first column of a lane that is inside its band ----
                     int dl[2];
@@ -668,7 +791,12 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(&prog[uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_FLAG))))], s - 63u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    // (links: counted from the start of the band lane 63 is in — the newest of the run from step bnd + 64)
+                    if (s >= bnd + 64u)
+                        __hip_atomic_store(&prog[uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_FLAG))))], s - 63u - bnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else
+                        __hip_atomic_store(&prog[uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_FLAG_PREV))))],
+                                           s - 63u - uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_BND_PREV)))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 publish(blk);
                 if (left_rows) {  // (the rows the next fetch reads: 64 of them, two blocks of the ring ahead)
@@ -720,6 +848,12 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
                             const uint32_t i = r_lo + uint32_t(bi) * FW_R + rr;  // 0-based row
                             const uint32_t nh = par(VP_N0 + h), mh = par(VP_M0 + h);
                             const int gdh = int(par(VP_GD0 + h));
+                            if (rr == 0 && bnd != 0u && uint32_t(bi) == bnd && act[h] && lastc[h] >= 0) {
+                                // (links: this lane's first row block of the band the run went on into — the best of the band above is complete)
+                                bandbest[par(VP_BEST0 + h) + band - 1u] = int2{bc[h], int(bc_i[h])};
+                                bc[h] = ALN_NEG;
+                                bc_i[h] = 0;
+                            }
                             if (act[h] && i < nh) {  // (rows of the band: i < r_hi <= n)
                                 if (lastc[h] >= 0) {
                                     const uint32_t lc = uint32_t(lastc[h]);
@@ -796,9 +930,11 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
             }
             for (; s < nsteps; ++s) step(s, std::true_type{});
         }
+        if (bnd != 0u && nsteps <= bnd + 64u) finish_prev();  // (links: a last band of one row block — the loop ended before step bnd + 64)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            if (lastc[h] >= 0) bandbest[par(VP_BEST0 + h) + band] = int2{bc[h], int(bc_i[h])};
+            // (links: a pair without rows in the run's newest band wrote the best of its last band when that band was left)
+            if (lastc[h] >= 0 && (bnd == 0u || nblk[h] > bnd)) bandbest[par(VP_BEST0 + h) + band] = int2{bc[h], int(bc_i[h])};
             if ((ovf >> h) & 1u) {
                 const uint32_t pidh = par(VP_PID0 + h);
                 if (pidh != 0xFFFFFFFFu) atomicOr(&ovf_out[pidh], 1u);
@@ -810,6 +946,7 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
             for (int h = 0; h < 2; ++h)
                 if (vh[h]) cells += (unsigned long long)(par(VP_RHI0 + h) - r_lo) * (unsigned long long)min(strip_cols, par(VP_M0 + h) - p * strip_cols);
             atomicAdd(cells_done, cells);
+            atomicAdd(link_stats, 1u);  // (the run's first tile; the tiles it went on into were counted as they were entered)
         }
         // ---- publish: every store of the wave has landed, then the release, then the flag ----
         const uint32_t my_flag = uint32_t(__builtin_amdgcn_readfirstlane(int(par(VP_FLAG))));
@@ -825,16 +962,19 @@ v2_fwd_body(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
     const AlnPairDev *__restrict__ pairs, const V2Couple *__restrict__ couples, const V2Item *__restrict__ items, uint32_t n_items,        \
         uint32_t *__restrict__ queue, uint32_t *__restrict__ flags, uint32_t *__restrict__ err, const uint8_t *__restrict__ pool, AlnParams P, \
         uint32_t *__restrict__ arena, int2 *__restrict__ lrow, int2 *__restrict__ bandbest, uint32_t *__restrict__ ovf_out, int guard,     \
-        const uint4 *__restrict__ prof, unsigned long long *__restrict__ cells_done, uint32_t *__restrict__ prog, uint32_t prog_every
+        const uint4 *__restrict__ prof, unsigned long long *__restrict__ cells_done, uint32_t *__restrict__ prog, uint32_t prog_every,  \
+        uint32_t *__restrict__ claims, uint32_t link_mode
 __global__ void __launch_bounds__(64 * V2_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8))) k_fwd2(V2_FWD_ARGS)
 {
-    v2_fwd_body(pairs, couples, items, n_items, queue, flags, err, pool, P, arena, lrow, bandbest, ovf_out, guard, prof, cells_done, prog, prog_every);
+    v2_fwd_body(pairs, couples, items, n_items, queue, flags, err, pool, P, arena, lrow, bandbest, ovf_out, guard, prof, cells_done, prog, prog_every, claims,
+                link_mode);
 }
 // A launch that puts two workgroups on a compute unit (align_v2_run: the corridor's launches are bound by tiles in flight) has 256
 // registers per lane to itself: the same body without the 19 registers k_fwd2 keeps in scratch.
 __global__ void __launch_bounds__(64 * V2_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) k_fwd2_w2(V2_FWD_ARGS)
 {
-    v2_fwd_body(pairs, couples, items, n_items, queue, flags, err, pool, P, arena, lrow, bandbest, ovf_out, guard, prof, cells_done, prog, prog_every);
+    v2_fwd_body(pairs, couples, items, n_items, queue, flags, err, pool, P, arena, lrow, bandbest, ovf_out, guard, prof, cells_done, prog, prog_every, claims,
+                link_mode);
 }
 
 
