@@ -1252,7 +1252,8 @@ int ioc_host_ops_project_ilen(const char* ops, int64_t len, int32_t rlen, uint8_
  *     there: agreement is tested under both masks, and "a state that is not NONE" means that either mask is not 0.
  * 10. The read record: key, group, how (the COMBINED isoform), n_near the junctions with N_i, ins_bases the sum of ilen_i over the
  *     junctions the read spans.
- * What stays out: alternative ends, more than 32 sites, runs beyond 255 bases (they count as 255).  The sequence of an inserted
+ * What stays out: more than 32 sites, runs beyond 255 bases (they count as 255); alternative ends are a stage of their own
+ * (ioc_host_reads_ends, below), which this one does not combine its isoforms with.  The sequence of an inserted
  * exon is the next section's.  20 bases and 8 junctions are choices made on simulated reads, not measured on real data. */
 #define IOC_INS_LACK 0
 #define IOC_INS_CARRY 1
@@ -1493,6 +1494,111 @@ int ioc_align_pairs_isoforms_full(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_p
                                   char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
                                   ioc_splice_stats* out_sstats, ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off,
                                   int64_t iso_cap, int64_t* iso_off);
+
+/* ---- Alternative ends: where the reads of a cluster start and stop on their representative, and the variants that makes ----
+ * A read that starts late or stops early has state IOC_BLOCK_NONE at the blocks it does not reach; this stage says where the ends
+ * lie: start sites (an alternative first exon or start site), stop sites (an early polyadenylation site), which reads go on beyond
+ * the representative there, and which (earlier isoform, start site, stop site) triples enough reads carry.
+ *
+ * The extent of one read, from its operation string: first_row / end_row the first row the base plane of ioc_host_ops_project
+ * covers and one past the last ((0, 0) if it covers none: these are first_row / end_row of ioc_host_planes_blocks' read record),
+ * head the 'i' bytes before the first walk byte (lead_i of ioc_host_ops_stats) and tail trail_i: the bases the read has in front of
+ * and behind what it aligns.  The refusals of ioc_host_ops_project_ilen (IOC_ERR_ARG, nothing written). */
+typedef struct {
+    int32_t first_row, end_row, head, tail;
+} ioc_read_extent;                /* 16 bytes */
+int ioc_host_ops_extent(const char* ops, int64_t len, int32_t rlen, ioc_read_extent* out);
+/* One segment is a reference of rlen rows with n_reads extents and, optionally, pre_group[i] >= -1 per read (NULL: all 0), meant
+ * to be the isoform of an earlier stage.  A rule {slack in 0 .. 32, min_over >= 1, min_depth >= 1, min_alt >= 1, min_pct in 1 ..
+ * 100, max_sites in 1 .. 32, max_variants >= 1}.  All integers.
+ *  1. Read i takes part iff end_row > first_row; N is the number of reads that take part, a_i its first_row and z_i its end_row.
+ *  2. hs(p), p = 0 .. rlen: the reads that take part with a_i == p; he(p) the same for z_i == p.
+ *  3. Ws(p): the sum of hs(q) over q = max(p - slack, 0) .. min(p + slack, rlen); We(p) the same for he.
+ *  4. Row p is a start row iff N >= min_depth and Ws(p) >= need(N), need(N) = max(min_alt, ceil(min_pct * N / 100)) as in
+ *     ioc_host_pileup_sites — one-sided here: an end site is a site even if every read uses it.  Stop rows likewise with We.
+ *  5. A start site [first, end): a maximal run of start rows.  In ascending order; the first max_sites are kept, n_found says how
+ *     many there were.  Stop sites likewise.  Two true ends fewer than about 2 slack rows apart become ONE site.
+ *  6. A read's distance to a kept start site b: 0 if first_b <= a_i < end_b, first_b - a_i below it, a_i - end_b + 1 above it.  Its
+ *     start site is the b with the smallest distance <= slack, the lower b on a tie; -1 if there is none or the read takes no part.
+ *     Its stop site likewise with z_i.  (The reach of slack is needed: with slack 1 and need 2, reads at rows 0 and 2 make row 1 the
+ *     only start row, and both must land in site [1, 2).)
+ *  7. The site record: n_reads the reads whose site it is; n_over those of them with head >= min_over (a start site) or tail >=
+ *     min_over (a stop site) — reads that go on beyond what the representative has there: a start site at row 0 with a high n_over
+ *     says the representative is the short one, one elsewhere a replaced first exon rather than a shorter transcript —; peak_row the
+ *     row of [first, end) with the largest hs (stop site: he), the lowest on a tie, and peak_reads its count; kind 0 start, 1 stop.
+ *  8. A read is placed when pre_group, start site and stop site are all >= 0.  The triples carried by at least min_alt placed reads
+ *     are supported; in ascending order (pre_group major, then start site, then stop site) they are the variants.  The first
+ *     max_variants are kept, n_found says how many there were.  A read's variant is the index of its triple among the kept, else -1.
+ * No verdict on whether a variant is real is applied.  The sequence of a variant comes from what exists: the reads' `variant` as
+ * `group` of ioc_planes_polish_groups; rows below its min_depth keep the representative's base, so that call trims nothing.
+ * The defaults — slack 10, min_over 20, min_depth 3, min_alt 3, min_pct 10, max_sites 32, max_variants 64 — are choices made on
+ * simulated reads, not measured on real data.  What stays out: telling two ends closer than 2 slack apart, a verdict on
+ * degradation against real start sites, re-clustering. */
+#define IOC_ENDS_MAX 32
+#define IOC_ENDS_SLACK_MAX 32
+#define IOC_END_START 0
+#define IOC_END_STOP 1
+typedef struct {
+    int32_t first, end;
+    uint32_t n_reads, n_over;
+    int32_t peak_row;
+    uint32_t peak_reads;
+    int32_t kind;
+    uint32_t reserved;
+} ioc_end_site;                   /* 32 bytes */
+typedef struct {
+    int32_t pre_group, start_site, stop_site;
+    uint32_t n_reads;
+} ioc_end_variant;                /* 16 bytes */
+typedef struct {
+    int32_t start_site, stop_site, variant, reserved;
+} ioc_read_ends;                  /* 16 bytes */
+typedef struct {
+    int32_t n_reads, n_starts, n_starts_found, n_stops, n_stops_found, n_variants, n_variants_found, n_placed;
+} ioc_ends_seg;                   /* 32 bytes; n_reads is N */
+typedef struct {
+    uint32_t starts, stops, w_starts, w_stops;  /* hs, he, Ws, We; rlen + 1 rows per segment */
+} ioc_end_row;                    /* 16 bytes */
+/* The definition: one segment, the plain loops above.  out_rows (may be NULL): rlen + 1 rows; out_starts / out_stops: room for
+ * min(max_sites, rlen + 1) records each, of which the first out_seg->n_starts / n_stops are written; out_variants: room for
+ * min(max_variants, n_reads) records, of which the first out_seg->n_variants are written; out_reads: n_reads records.  IOC_ERR_ARG,
+ * with nothing written, for a rule outside its ranges, a negative count or length, pre_group[i] < -1, an extent with first_row <
+ * 0, end_row > rlen, end_row < first_row, head < 0 or tail < 0, and a NULL pointer that is needed. */
+int ioc_host_reads_ends(const ioc_read_extent* extents, const int32_t* pre_group, int32_t n_reads, int32_t rlen, int32_t slack,
+                        int32_t min_over, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites, int32_t max_variants,
+                        ioc_end_row* out_rows, ioc_end_site* out_starts, ioc_end_site* out_stops, ioc_end_variant* out_variants,
+                        ioc_read_ends* out_reads, ioc_ends_seg* out_seg);
+/* Many segments at once on the device, from host arrays, which are uploaded: extents (and pre_group, or NULL) per pair, a segment's
+ * reads its pairs in ascending order.  The kernels of ioc_read_ends.hip: the two histograms by integer adds into zeroed rows, the
+ * windowed sums by a wave prefix sum with a halo, start and stop rows as bit planes by ballot, the runs of set bits across words, a
+ * wave per read for its nearest sites, a wave per kept site for its counts and its peak, and the variants as the isoforms of the
+ * block stage over one 64-bit key a read.  out_rows (may be NULL): the segments' tables one behind the other; out_sites: segment
+ * g's start sites at site_off[2 g] .. site_off[2 g + 1], its stop sites at site_off[2 g + 1] .. site_off[2 g + 2] (2 n_segs + 1
+ * entries); out_variants packed with var_off (n_segs + 1 entries); out_reads per pair, out_seg per segment; each as
+ * ioc_host_reads_ends defines it, byte for byte.  IOC_ERR_ARG, with nothing written, for what the definition refuses, seg_of_pair
+ * outside the segments and a NULL pointer that is needed; IOC_ERR_CAPACITY, with nothing written, for sites_cap below the sum over g
+ * of 2 min(max_sites, rlen[g] + 1) and for variants_cap below the sum over g of min(max_variants, reads of g). */
+int ioc_reads_ends(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair,
+                   const ioc_read_extent* extents, const int32_t* pre_group, int32_t slack, int32_t min_over, int32_t min_depth,
+                   int32_t min_alt, int32_t min_pct, int32_t max_sites, int32_t max_variants, ioc_end_row* out_rows,
+                   ioc_end_site* out_sites, int64_t sites_cap, int64_t* site_off, ioc_end_variant* out_variants, int64_t variants_cap,
+                   int64_t* var_off, ioc_read_ends* out_reads, ioc_ends_seg* out_seg);
+/* ioc_align_pairs_blocks with the ends stage behind the block kernels: everything ioc_align_pairs_blocks returns comes back
+ * unchanged, byte for byte; added are out_extents per pair — first_row / end_row the block record's, head / tail lead_i / trail_i of
+ * the pair's statistics record, for which k_ops_stats runs over every slice whether or not out_stats is asked; out_extents[i] is
+ * ioc_host_ops_extent of what ioc_align_pairs_ops returns for pair i, all zero for a pair without an alignment — and the outputs of
+ * ioc_reads_ends over them, pre_group being the block stage's group, read where it lies on the device.  The block search and the
+ * ends share min_depth and min_alt; min_pct is each stage's own (ends_min_pct).  Every pair is aligned, piled and projected exactly
+ * once; the stage's memory is reserved after the walks.  The refusals of both calls; nothing is written. */
+int ioc_align_pairs_blocks_ends(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                                int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                                ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                                ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t slack, int32_t min_over, int32_t ends_min_pct,
+                                int32_t max_sites, int32_t max_variants, ioc_read_extent* out_extents, ioc_end_row* out_erows,
+                                ioc_end_site* out_sites, int64_t sites_cap, int64_t* site_off, ioc_end_variant* out_variants,
+                                int64_t variants_cap, int64_t* var_off, ioc_read_ends* out_ereads, ioc_ends_seg* out_eseg);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,35 @@ class SpliceStats(C.Structure):  # ioc_splice_stats (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("n_done", "n_uncalled", "n_overlap", "rows_replaced", "spliced_bytes")] + [("reserved", C.c_int32 * 3)]
 
 
+ENDS_MAX, ENDS_SLACK_MAX = 32, 32  # IOC_ENDS_MAX, IOC_ENDS_SLACK_MAX
+END_START, END_STOP = 0, 1         # IOC_END_*
+
+
+class ReadExtent(C.Structure):  # ioc_read_extent (16 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("first_row", "end_row", "head", "tail")]
+
+
+class EndSite(C.Structure):  # ioc_end_site (32 bytes)
+    _fields_ = [("first", C.c_int32), ("end", C.c_int32), ("n_reads", C.c_uint32), ("n_over", C.c_uint32), ("peak_row", C.c_int32), ("peak_reads", C.c_uint32),
+                ("kind", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class EndVariant(C.Structure):  # ioc_end_variant (16 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("pre_group", "start_site", "stop_site")] + [("n_reads", C.c_uint32)]
+
+
+class ReadEnds(C.Structure):  # ioc_read_ends (16 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("start_site", "stop_site", "variant", "reserved")]
+
+
+class EndsSeg(C.Structure):  # ioc_ends_seg (32 bytes)
+    _fields_ = [(n, C.c_int32) for n in ("n_reads", "n_starts", "n_starts_found", "n_stops", "n_stops_found", "n_variants", "n_variants_found", "n_placed")]
+
+
+class EndRow(C.Structure):  # ioc_end_row (16 bytes)
+    _fields_ = [(n, C.c_uint32) for n in ("starts", "stops", "w_starts", "w_stops")]
+
+
 class SplitSeg(C.Structure):  # ioc_split_seg (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("seed", "n_linked", "n_reads", "n_group0", "n_group1", "n_none")] + [("seed_link", C.c_int64)]
 
@@ -227,6 +256,7 @@ SYMBOLS = [
     "ioc_host_ops_project_ilen", "ioc_host_planes_inserts", "ioc_planes_inserts", "ioc_align_pairs_blocks_inserts",
     "ioc_host_ops_project_qpos", "ioc_host_align_global_ops", "ioc_host_insert_windows", "ioc_planes_insert_windows", "ioc_align_pairs_blocks_inserts_seq",
     "ioc_host_isoform_splice", "ioc_planes_isoforms_full", "ioc_align_pairs_isoforms_full",
+    "ioc_host_ops_extent", "ioc_host_reads_ends", "ioc_reads_ends", "ioc_align_pairs_blocks_ends",
 ]
 
 _lib = None
@@ -412,6 +442,14 @@ def load():
                                            C.c_void_p]
     L.ioc_align_pairs_isoforms_full.argtypes = L.ioc_align_pairs_blocks_inserts_seq.argtypes + [i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p,
                                                                                                C.c_void_p, i64, pi64, i64, pi64]
+    L.ioc_host_ops_extent.argtypes = [C.c_char_p, i64, i32, C.POINTER(ReadExtent)]
+    L.ioc_host_reads_ends.argtypes = [C.c_void_p, C.c_void_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
+    ends_out = [i32, i32, i32, i32, i32, i32, i32]  # (the rule; the fused call has min_depth and min_alt from the block rule)
+    L.ioc_reads_ends.argtypes = [vp, i32, pi32, i32, pi32, C.c_void_p, C.c_void_p] + ends_out + [C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, i64, pi64,
+                                                                                                 C.c_void_p, C.c_void_p]
+    L.ioc_align_pairs_blocks_ends.argtypes = L.ioc_align_pairs_blocks.argtypes + [i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64,
+                                                                                  C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

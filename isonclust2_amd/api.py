@@ -436,6 +436,85 @@ def planes_inserts(base, ilen, pre_key=None, pre_mask=None, pre_full=0, rows=Tru
     return out
 
 
+# ioc_read_extent, ioc_end_site, ioc_end_variant, ioc_read_ends, ioc_ends_seg and ioc_end_row as numpy records
+READ_EXTENT_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.ReadExtent._fields_])
+END_SITE_DTYPE = np.dtype([("first", np.int32), ("end", np.int32), ("n_reads", np.uint32), ("n_over", np.uint32), ("peak_row", np.int32),
+                           ("peak_reads", np.uint32), ("kind", np.int32), ("reserved", np.uint32)])
+END_VARIANT_DTYPE = np.dtype([(n, np.int32) for n in ("pre_group", "start_site", "stop_site")] + [("n_reads", np.uint32)])
+READ_ENDS_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.ReadEnds._fields_])
+ENDS_SEG_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.EndsSeg._fields_])
+END_ROW_DTYPE = np.dtype([(n, np.uint32) for n, _ in _lib.EndRow._fields_])
+END_START, END_STOP = _lib.END_START, _lib.END_STOP
+# (ends within 10 rows of each other, 20 bases beyond the representative, a tenth of the reads: choices made on simulated reads, not
+# measured on real data)
+ENDS_RULE = dict(slack=10, min_over=20, min_depth=3, min_alt=3, min_pct=10, max_sites=32, max_variants=64)
+
+
+def reads_ends_bound(rlen, n_reads, max_sites=ENDS_RULE["max_sites"], max_variants=ENDS_RULE["max_variants"]):
+    """What a search for ends may keep at most of a reference of rlen bases with n_reads reads: (sites, variants) — min(max_sites,
+    rlen + 1) start sites and as many stop sites, min(max_variants, n_reads) variants.  Context.reads_ends and
+    Context.align_pairs_blocks_ends ask the sums over the segments of sites_cap and variants_cap."""
+    return 2 * min(int(max_sites), int(rlen) + 1), min(int(max_variants), int(n_reads))
+
+
+def _ends_rule(rule):
+    unknown = set(rule) - set(ENDS_RULE)
+    if unknown:
+        raise TypeError(f"unknown rule parameters: {sorted(unknown)}")
+    return [int({**ENDS_RULE, **rule}[n]) for n in ENDS_RULE]
+
+
+def host_ops_extent(ops, rlen):
+    """ioc_host_ops_extent: the extent of one read on its reference from its operation string — a READ_EXTENT_DTYPE record:
+    first_row / end_row the first row its base plane covers and one past the last ((0, 0): none), head / tail the free-end 'i' bytes
+    before and behind the walk.  ValueError for a byte outside "=XIDid" and for a string that does not consume rlen reference bases."""
+    e = _lib.ReadExtent(-0x11111112, -0x11111112, -0x11111112, -0x11111112)
+    rc = _lib.load().ioc_host_ops_extent(bytes(ops), len(ops), int(rlen), C.byref(e))
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_extent failed ({rc})")
+    return np.array([(e.first_row, e.end_row, e.head, e.tail)], READ_EXTENT_DTYPE)[0]
+
+
+def _extents(extents):
+    ext = np.ascontiguousarray(extents, READ_EXTENT_DTYPE)
+    if ext.ndim != 1:
+        raise ValueError("extents must hold one READ_EXTENT_DTYPE record per read")
+    return ext
+
+
+def host_reads_ends(extents, rlen, pre_group=None, rows=True, **rule):
+    """ioc_host_reads_ends: the alternative ends of one segment — `extents` a READ_EXTENT_DTYPE record per read (host_ops_extent),
+    rlen the reference's length, pre_group (optional, >= -1 per read) the isoform of an earlier stage; the rule as keywords
+    (ENDS_RULE has the defaults).  A row is a start row where at least need(N) of the N reads that cover anything start within
+    `slack` rows of it; a start site is a run of start rows, a read's start site the nearest within `slack`; stop sites likewise; the
+    (pre_group, start site, stop site) triples that at least min_alt reads carry are the variants, in ascending order.  Returns a
+    dict: `starts` and `stops` (END_SITE_DTYPE, the kept ones), `variants` (END_VARIANT_DTYPE), `reads` (READ_ENDS_DTYPE per read),
+    `seg` (an ENDS_SEG_DTYPE record) and, with rows=True, `rows` (END_ROW_DTYPE, rlen + 1 rows).  IocError for a rule, an extent or
+    a pre_group outside its range."""
+    ext = _extents(extents)
+    n, rlen = len(ext), int(rlen)
+    pg = None
+    if pre_group is not None:
+        pg = np.ascontiguousarray(pre_group, np.int32)
+        if pg.shape != (n,):
+            raise ValueError("pre_group must hold one entry per read")
+    r = _ends_rule(rule)
+    most_s, most_v = reads_ends_bound(max(rlen, 0), n, max(r[5], 0), max(r[6], 0))
+    tab = np.zeros(max(rlen, 0) + 1, END_ROW_DTYPE)
+    starts, stops = np.zeros(max(most_s // 2, 1), END_SITE_DTYPE), np.zeros(max(most_s // 2, 1), END_SITE_DTYPE)
+    variants, reads, seg = np.zeros(max(most_v, 1), END_VARIANT_DTYPE), np.zeros(n, READ_ENDS_DTYPE), np.zeros(1, ENDS_SEG_DTYPE)
+    rc = _lib.load().ioc_host_reads_ends(ext.ctypes.data if n else None, pg.ctypes.data if pg is not None and n else None, n, rlen, *r,
+                                         tab.ctypes.data if rows else None, starts.ctypes.data, stops.ctypes.data, variants.ctypes.data,
+                                         reads.ctypes.data if n else None, seg.ctypes.data)
+    if rc < 0:
+        raise IocError(int(rc), "ioc_host_reads_ends")
+    out = {"starts": starts[:int(seg[0]["n_starts"])], "stops": stops[:int(seg[0]["n_stops"])], "variants": variants[:int(seg[0]["n_variants"])],
+           "reads": reads, "seg": seg[0]}
+    if rows:
+        out["rows"] = tab
+    return out
+
+
 def ops_project_qpos(ops, rlen):
     """ioc_host_ops_project_qpos: where every row of the reference lies in the read — a uint32 array of rlen + 1 words: qpos[0] = 0,
     qpos[r] the bytes of "=XIi" up to and including the byte that consumes row r - 1, so that the run of 'I' in front of row r
@@ -1417,6 +1496,88 @@ class Context:
                                                 _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
                                                 cols.ctypes.data if tables and n_rows else None))
         out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg)}
+        if stats:
+            out["stats"] = st
+        if tables:
+            out.update(cols=cols, row0=self._row0(rlen))
+        return out
+
+    @staticmethod
+    def _ends_out(ns, rlen, n_reads, rule, rows, sites_cap, variants_cap):
+        """the output arrays of a search for ends over segments of these lengths and read counts"""
+        bounds = [reads_ends_bound(m, k, rule[5], rule[6]) for m, k in zip(rlen, n_reads)]
+        sites_cap = sum(b[0] for b in bounds) if sites_cap is None else int(sites_cap)
+        variants_cap = sum(b[1] for b in bounds) if variants_cap is None else int(variants_cap)
+        tab = np.zeros(int(sum(rlen)) + ns, END_ROW_DTYPE) if rows else None
+        sites, soff = np.zeros(max(sites_cap, 1), END_SITE_DTYPE), np.zeros(2 * ns + 1, np.int64)
+        variants, voff, seg = np.zeros(max(variants_cap, 1), END_VARIANT_DTYPE), np.zeros(ns + 1, np.int64), np.zeros(ns, ENDS_SEG_DTYPE)
+        return (tab, sites, soff, variants, voff, seg), sites_cap, variants_cap
+
+    def _ends_dict(self, ns, rlen, tab, sites, soff, variants, voff, reads, seg):
+        out = {"starts": [sites[soff[2 * g]:soff[2 * g + 1]] for g in range(ns)], "stops": [sites[soff[2 * g + 1]:soff[2 * g + 2]] for g in range(ns)],
+               "site_off": soff, "variants": [variants[voff[g]:voff[g + 1]] for g in range(ns)], "var_off": voff, "reads": reads, "seg": seg}
+        if tab is not None:
+            r0 = np.concatenate([self._row0(rlen), [len(tab)]]).astype(np.int64) if ns else np.zeros(1, np.int64)
+            out.update(rows=[tab[r0[g]:r0[g + 1]] for g in range(ns)])
+        return out
+
+    def reads_ends(self, rlen, seg_of_pair, extents, pre_group=None, rows=True, sites_cap=None, variants_cap=None, **rule):
+        """ioc_reads_ends: the alternative ends of many segments on the device, from host arrays — `rlen` the segments' lengths,
+        seg_of_pair and `extents` (READ_EXTENT_DTYPE) per pair, pre_group per pair or None; the rule as keywords.  Returns a dict:
+        `starts`, `stops` (an END_SITE_DTYPE array per segment each), `site_off`, `variants` (an END_VARIANT_DTYPE array per segment),
+        `var_off`, `reads` (READ_ENDS_DTYPE per pair), `seg` (ENDS_SEG_DTYPE per segment) and, with rows=True, `rows` (an
+        END_ROW_DTYPE array per segment); each segment as api.host_reads_ends defines it."""
+        ext = _extents(extents)
+        ns, n = len(rlen), len(ext)
+        rl = np.ascontiguousarray(rlen, np.int32)
+        sop = np.ascontiguousarray(seg_of_pair, np.int32)
+        if sop.shape != (n,):
+            raise ValueError("seg_of_pair and extents must hold one entry per pair")
+        pg = None
+        if pre_group is not None:
+            pg = np.ascontiguousarray(pre_group, np.int32)
+            if pg.shape != (n,):
+                raise ValueError("pre_group must hold one entry per pair")
+            pg = np.concatenate([pg, np.zeros(1, np.int32)])  # (never an empty array's pointer)
+        r = _ends_rule(rule)
+        counts = np.bincount(sop[(sop >= 0) & (sop < ns)], minlength=ns) if ns else []
+        (tab, sites, soff, variants, voff, seg), sites_cap, variants_cap = self._ends_out(ns, [max(int(m), 0) for m in rl], counts, r, rows, sites_cap, variants_cap)
+        reads = np.zeros(n, READ_ENDS_DTYPE)
+        self._chk(self.L.ioc_reads_ends(self.h, ns, _p(rl, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, ext.ctypes.data if n else None,
+                                        pg.ctypes.data if pg is not None else None, *r, tab.ctypes.data if rows and len(tab) else None, sites.ctypes.data,
+                                        sites_cap, _p(soff, C.c_int64), variants.ctypes.data, variants_cap, _p(voff, C.c_int64),
+                                        reads.ctypes.data if n else None, seg.ctypes.data if ns else None))
+        return self._ends_dict(ns, [int(m) for m in rl], tab, sites, soff, variants, voff, reads, seg)
+
+    def align_pairs_blocks_ends(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, sites_cap=None, variants_cap=None, match=2,
+                                mismatch=-2, gap_extend=1, slack=ENDS_RULE["slack"], min_over=ENDS_RULE["min_over"], ends_min_pct=ENDS_RULE["min_pct"],
+                                max_sites=ENDS_RULE["max_sites"], max_variants=ENDS_RULE["max_variants"], **rule):
+        """ioc_align_pairs_blocks_ends: align_pairs_blocks with the search for ends behind the block search, on the device, every
+        pair aligned once — the block rule as keywords, slack / min_over / ends_min_pct / max_sites / max_variants for the ends
+        (min_depth and min_alt are shared), pre_group being the block stage's isoform.  Returns align_pairs_blocks' dict, byte for
+        byte, `extents` (READ_EXTENT_DTYPE per pair) and under `ends` what Context.reads_ends returns."""
+        n, ns = len(pairs), len(segs)
+        arr = self._aln_pairs(pairs)
+        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        r = _blocks_rule(rule)
+        er = [int(slack), int(min_over), r[1], r[2], int(ends_min_pct), int(max_sites), int(max_variants)]
+        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
+        sopa = np.asarray(sop, np.int64)
+        counts = np.bincount(sopa[(sopa >= 0) & (sopa < ns)], minlength=ns) if ns else []
+        (etab, sites, soff, variants, voff, eseg), sites_cap, variants_cap = self._ends_out(ns, rlen, counts, er, rows, sites_cap, variants_cap)
+        (score, win, ratio), ptrs = self._aln_out(n)
+        reads, ereads, ext = np.zeros(n, READ_BLOCKS_DTYPE), np.zeros(n, READ_ENDS_DTYPE), np.zeros(n, READ_EXTENT_DTYPE)
+        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        self._chk(self.L.ioc_align_pairs_blocks_ends(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
+                                                     _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
+                                                     _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
+                                                     cols.ctypes.data if tables and n_rows else None, er[0], er[1], er[4], er[5], er[6],
+                                                     ext.ctypes.data if n else None, etab.ctypes.data if rows and len(etab) else None, sites.ctypes.data,
+                                                     sites_cap, _p(soff, C.c_int64), variants.ctypes.data, variants_cap, _p(voff, C.c_int64),
+                                                     ereads.ctypes.data if n else None, eseg.ctypes.data if ns else None))
+        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg), "extents": ext,
+               "ends": self._ends_dict(ns, rlen, etab, sites, soff, variants, voff, ereads, eseg)}
         if stats:
             out["stats"] = st
         if tables:

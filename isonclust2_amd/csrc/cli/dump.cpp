@@ -36,6 +36,7 @@ struct DumpOptions {
     // --isoforms-polish-min-depth / --isoforms-polish-max: positions covered by fewer reads of the isoform keep the representative's base / the isoforms called per cluster
     // --isoforms-polish-weighted: every isoform is called by weight, every read voting with its base qualities
     // --isoforms-inserts: cluster_inserts.tsv, read_inserts.tsv, the exons a cluster's reads carry and its representative lacks, and isoforms over blocks and sites
+    // --isoforms-ends: cluster_ends.tsv, cluster_end_variants.tsv, read_ends.tsv, where the reads of a cluster start and stop on its representative, and the variants
     ReportOpts reports;
 };
 
@@ -61,7 +62,9 @@ void print_dump_help()
          << "                     [--isoforms-min-block N] [--isoforms-max N]" << endl
          << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N] [--isoforms-polish-weighted]]" << endl
          << "                     [--isoforms-inserts [--isoforms-min-ins N] [--isoforms-ins-slack N] [--isoforms-ins-max N]" << endl
-         << "                     [--isoforms-inserts-seq [--isoforms-inserts-max-win N] [--isoforms-full [--isoforms-full-max N]]]]] final.cer" << endl
+         << "                     [--isoforms-inserts-seq [--isoforms-inserts-max-win N] [--isoforms-full [--isoforms-full-max N]]]]" << endl
+         << "                     [--isoforms-ends [--isoforms-ends-slack N] [--isoforms-ends-min-over N] [--isoforms-ends-min-pct P]" << endl
+         << "                     [--isoforms-ends-max N] [--isoforms-ends-max-variants N]]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -156,7 +159,22 @@ void print_dump_help()
          << "                 sum to at least N, 1 .. 255 (default 20: a choice that was not measured on real data)" << endl
          << "  --isoforms-ins-slack N  ... the junctions on either side that count, 0 .. 32 (default 8: at 8 % errors the aligner breaks a 40-base" << endl
          << "                 exon into two runs a few positions apart; a choice that was not measured on real data)" << endl
-         << "  --isoforms-ins-max N    keep the first N insertion sites of a cluster, 1 .. 32 (default 32)" << endl;
+         << "  --isoforms-ins-max N    keep the first N insertion sites of a cluster, 1 .. 32 (default 32)" << endl
+         << "  --isoforms-ends         with --isoforms: also write outdir/cluster_ends.tsv, cluster_end_variants.tsv and read_ends.tsv, from the same" << endl
+         << "                 alignments: where the reads of a cluster start and stop on its representative (start and stop sites: the first row" << endl
+         << "                 and one past the last, the row most reads use and how many, the reads of the site and how many of them go on beyond" << endl
+         << "                 the representative there; a '#' line where a list was cut), the (isoform, start site, stop site) triples that at" << endl
+         << "                 least --isoforms-min-alt reads carry (variants), and per read the rows it covers, the bases it has in front of and" << endl
+         << "                 behind its alignment, its start site, its stop site and its variant (or '.').  A start site at row 0 whose reads" << endl
+         << "                 mostly go on says the representative is the short one.  Two ends closer than about twice the slack are one site." << endl
+         << "                 The three files of --isoforms stay what they are.  Not offered together with --isoforms-inserts or" << endl
+         << "                 --isoforms-polish: one fused call a run" << endl
+         << "  --isoforms-ends-slack N         reads that start (stop) within N rows of each other share a site, 0 .. 32 (default 10: a choice that" << endl
+         << "                 was not measured on real data)" << endl
+         << "  --isoforms-ends-min-over N      a read goes on beyond the representative where it has at least N unaligned bases there (default 20)" << endl
+         << "  --isoforms-ends-min-pct P       a site needs at least P percent of the cluster's reads, 1 .. 100 (default 10), and --isoforms-min-alt reads" << endl
+         << "  --isoforms-ends-max N           keep the first N start sites and the first N stop sites of a cluster, 1 .. 32 (default 32)" << endl
+         << "  --isoforms-ends-max-variants N  keep the first N variants of a cluster (default 64)" << endl;
 }
 
 DumpOptions parse_dump_options(int argc, char** argv)
@@ -183,7 +201,10 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms-min-ins", required_argument, 0, 1033}, {"isoforms-ins-slack", required_argument, 0, 1034},
                                        {"isoforms-ins-max", required_argument, 0, 1035}, {"isoforms-inserts-seq", no_argument, 0, 1036},
                                        {"isoforms-inserts-max-win", required_argument, 0, 1037}, {"isoforms-full", no_argument, 0, 1038},
-                                       {"isoforms-full-max", required_argument, 0, 1039}, {0, 0, 0, 0}};
+                                       {"isoforms-full-max", required_argument, 0, 1039}, {"isoforms-ends", no_argument, 0, 1040},
+                                       {"isoforms-ends-slack", required_argument, 0, 1041}, {"isoforms-ends-min-over", required_argument, 0, 1042},
+                                       {"isoforms-ends-min-pct", required_argument, 0, 1043}, {"isoforms-ends-max", required_argument, 0, 1044},
+                                       {"isoforms-ends-max-variants", required_argument, 0, 1045}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false, iso_polish = false;
@@ -234,6 +255,12 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1037: r.isoforms.ins_max_win = number("--isoforms-inserts-max-win", optarg, 1, IOC_WIN_MAX); break;
             case 1038: r.isoforms.full = true; break;
             case 1039: r.isoforms.full_max = number("--isoforms-full-max", optarg, 1, INT32_MAX); break;
+            case 1040: r.isoforms.ends = true; break;
+            case 1041: r.isoforms.ends_slack = number("--isoforms-ends-slack", optarg, 0, IOC_ENDS_SLACK_MAX); break;
+            case 1042: r.isoforms.ends_min_over = number("--isoforms-ends-min-over", optarg, 1, INT32_MAX); break;
+            case 1043: r.isoforms.ends_min_pct = number("--isoforms-ends-min-pct", optarg, 1, 100); break;
+            case 1044: r.isoforms.ends_max = number("--isoforms-ends-max", optarg, 1, IOC_ENDS_MAX); break;
+            case 1045: r.isoforms.ends_max_variants = number("--isoforms-ends-max-variants", optarg, 1, INT32_MAX); break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -251,6 +278,9 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (r.isoforms.inserts && iso_polish) die("--isoforms-inserts is not offered together with --isoforms-polish!");
     if (r.isoforms.inserts_seq && !r.isoforms.inserts) die("--isoforms-inserts-seq asks for --isoforms-inserts!");
     if (r.isoforms.full && !r.isoforms.inserts_seq) die("--isoforms-full asks for --isoforms-inserts-seq!");
+    if (r.isoforms.ends && !r.isoforms.on) die("--isoforms-ends asks for --isoforms!");
+    if (r.isoforms.ends && r.isoforms.inserts) die("--isoforms-ends is not offered together with --isoforms-inserts!");
+    if (r.isoforms.ends && iso_polish) die("--isoforms-ends is not offered together with --isoforms-polish!");
     if (polish) r.polish_min_depth = polish_min_depth;
     if (d.index.empty()) die("Specifying the sorted read index is mandatory!");
     d.batch = argv[optind];
@@ -430,7 +460,8 @@ int main_dump(int argc, char** argv)
                              (reports.isoforms.on ? "cluster_blocks.tsv, cluster_isoforms.tsv, read_isoforms.tsv, " : "") + (reports.iso_polish() ? "cluster_isoforms.fq, " : "") +
                              (reports.isoforms.on && reports.isoforms.inserts ? "cluster_inserts.tsv, read_inserts.tsv, " : "") +
                              (reports.isoforms.on && reports.isoforms.inserts && reports.isoforms.inserts_seq ? "cluster_inserts.fq, " : "") +
-                             (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.full ? "cluster_isoforms_full.fq, " : "");
+                             (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.full ? "cluster_isoforms_full.fq, " : "") +
+                             (reports.isoforms.on && reports.isoforms.ends ? "cluster_ends.tsv, cluster_end_variants.tsv, read_ends.tsv, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

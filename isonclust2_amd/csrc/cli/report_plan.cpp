@@ -278,6 +278,51 @@ string read_insert_columns(const ioc_read_inserts& r, int32_t n_sites)
     return inserts_signature(r.key, n_sites) + '\t' + (r.group < 0 ? string(".") : std::to_string(r.group)) + '\t' + how;
 }
 
+EndsCapacity ends_capacity(const ReportGroup& g, int max_sites, int max_variants)
+{
+    EndsCapacity cap;
+    for (size_t s = 0; s < g.segs.size(); ++s) {
+        cap.sites += 2 * std::min<int64_t>(max_sites, ref_len(g, g.segs[s]) + 1);
+        cap.variants += std::min<int64_t>(max_variants, g.seg_reads[s]);
+    }
+    return cap;
+}
+
+string cluster_ends_rows(size_t cluster, const ioc_ends_seg& z, const ioc_end_site* starts, const ioc_end_site* stops)
+{
+    const string id = std::to_string(cluster);
+    string text;
+    if (z.n_starts_found > z.n_starts) text += "# cluster " + id + ": kept " + std::to_string(z.n_starts) + " of " + std::to_string(z.n_starts_found) + " start sites\n";
+    if (z.n_stops_found > z.n_stops) text += "# cluster " + id + ": kept " + std::to_string(z.n_stops) + " of " + std::to_string(z.n_stops_found) + " stop sites\n";
+    for (int kind = 0; kind < 2; ++kind)
+        for (int32_t b = 0; b < (kind ? z.n_stops : z.n_starts); ++b) {
+            const ioc_end_site& k = (kind ? stops : starts)[b];
+            text += id + '\t' + (kind ? "stop" : "start") + '\t' + std::to_string(b) + '\t' + std::to_string(k.first) + '\t' + std::to_string(k.end) + '\t' +
+                    std::to_string(k.peak_row) + '\t' + std::to_string(k.peak_reads) + '\t' + std::to_string(k.n_reads) + '\t' + std::to_string(k.n_over) + '\n';
+        }
+    return text;
+}
+
+string cluster_end_variants_rows(size_t cluster, const ioc_ends_seg& z, const ioc_end_variant* variants)
+{
+    const string id = std::to_string(cluster);
+    string text;
+    if (z.n_variants_found > z.n_variants) text += "# cluster " + id + ": kept " + std::to_string(z.n_variants) + " of " + std::to_string(z.n_variants_found) + " variants\n";
+    for (int32_t v = 0; v < z.n_variants; ++v) {
+        const ioc_end_variant& k = variants[v];
+        text += id + '\t' + std::to_string(v) + '\t' + std::to_string(k.pre_group) + '\t' + std::to_string(k.start_site) + '\t' + std::to_string(k.stop_site) + '\t' +
+                std::to_string(k.n_reads) + '\n';
+    }
+    return text;
+}
+
+string read_end_columns(const ioc_read_extent& e, const ioc_read_ends& r)
+{
+    auto or_dot = [](int32_t v) { return v < 0 ? string(".") : std::to_string(v); };
+    return std::to_string(e.first_row) + '\t' + std::to_string(e.end_row) + '\t' + std::to_string(e.head) + '\t' + std::to_string(e.tail) + '\t' + or_dot(r.start_site) +
+           '\t' + or_dot(r.stop_site) + '\t' + or_dot(r.variant);
+}
+
 string read_isoform_columns(const ioc_read_blocks& r, int32_t n_blocks)
 {
     const char* const how = r.how == IOC_ISO_DIRECT ? "direct" : r.how == IOC_ISO_ASSIGNED ? "assigned" : r.how == IOC_ISO_RARE ? "rare" : "ambiguous";

@@ -79,6 +79,13 @@
 // lacks, with how many reads carry it, lack it or do not reach across and the carriers' shortest and longest insertion;
 // read_inserts.tsv: one row per row read_stats.tsv has, in that order, with the read's signature at the sites and its isoform over
 // blocks and sites together.  The three files of --isoforms and the other report files are what they are without the option.
+//
+// dump --isoforms --isoforms-ends: <outdir>/cluster_ends.tsv, cluster_end_variants.tsv and read_ends.tsv (ioc_align_pairs_blocks_ends: the
+// call of --isoforms with the search for ends behind the block search, no read aligned a second time): cluster_ends.tsv: where the
+// reads of a cluster start and stop on its representative, with the row most of them use, how many reads use the site and how many
+// of those go on beyond the representative there; cluster_end_variants.tsv: the (isoform, start site, stop site) triples that enough
+// reads carry; read_ends.tsv: one row per row read_stats.tsv has, in that order, with the rows the read covers, the bases it has in
+// front of and behind its alignment, its sites and its variant.  The three files of --isoforms are what they are without the option.
 #include "reports.hpp"
 
 #include <cstdio>
@@ -133,6 +140,12 @@ struct GroupResult {
     std::vector<int64_t> insert_off;
     std::vector<ioc_inserts_seg> inserts_seg;
     std::vector<ioc_read_inserts> read_inserts;
+    std::vector<ioc_end_site> end_sites;  // (--isoforms-ends) segment g's start sites at [end_off[2 g], end_off[2 g + 1]), its stop sites behind them, its
+    std::vector<int64_t> end_off, var_off;  // variants at [var_off[g], var_off[g + 1]), its record, and pair x's extent and record
+    std::vector<ioc_end_variant> end_variants;
+    std::vector<ioc_ends_seg> ends_seg;
+    std::vector<ioc_read_extent> extents;
+    std::vector<ioc_read_ends> read_ends;
     std::vector<ioc_insert_window> ins_windows;  // (--isoforms-inserts-seq) per kept site, in the order of `inserts`: its record, and its consensus at
     std::vector<int64_t> win_off;            // [win_off[s], win_off[s + 1]) of wseq / wqual
     std::vector<ioc_polish_stats> win_stats;
@@ -162,6 +175,8 @@ struct RowResult {
     int32_t iso_blocks = 0;
     ioc_read_inserts ins{};          // (--isoforms-inserts) the read's record, and how many sites its cluster kept
     int32_t ins_sites = 0;
+    ioc_read_extent extent{};        // (--isoforms-ends) the read's extent and its record
+    ioc_read_ends ends{-1, -1, -1, 0};
 };
 
 // The one place that chooses a library call.  --sites and / or --split come first; --polish, --correct and --isoforms are calls of their own,
@@ -317,6 +332,18 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
                                                     o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr, r.inserts.data(),
                                                     icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data()),
                   "exon blocks with the insertion sites");
+        } else if (io.ends) {
+            const EndsCapacity ecap = ends_capacity(g, io.ends_max, io.ends_max_variants);
+            r.end_sites.assign(size_t(std::max<int64_t>(ecap.sites, 1)), ioc_end_site{}), r.end_off.assign(2 * ns + 1, 0), r.var_off.assign(ns + 1, 0);
+            r.end_variants.assign(size_t(std::max<int64_t>(ecap.variants, 1)), ioc_end_variant{}), r.ends_seg.assign(ns, ioc_ends_seg{});
+            r.extents.assign(np, ioc_read_extent{}), r.read_ends.assign(np, ioc_read_ends{});
+            check(c, ioc_align_pairs_blocks_ends(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
+                                                 io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
+                                                 r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr,
+                                                 io.ends_slack, io.ends_min_over, io.ends_min_pct, io.ends_max, io.ends_max_variants, r.extents.data(), nullptr,
+                                                 r.end_sites.data(), ecap.sites, r.end_off.data(), r.end_variants.data(), ecap.variants, r.var_off.data(),
+                                                 r.read_ends.data(), r.ends_seg.data()),
+                  "exon blocks with the alternative ends");
         } else {
             check(c, ioc_align_pairs_blocks(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
                                             io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
@@ -351,6 +378,7 @@ void scatter_to_rows(const ReportOpts& o, const ReportRows& rows, const ReportGr
         }
         if (o.isoforms.on) row.iso = r.read_blocks[x], row.iso_blocks = r.blocks_seg[size_t(g.seg_of_pair[x])].n_blocks;
         if (o.isoforms.on && o.isoforms.inserts) row.ins = r.read_inserts[x], row.ins_sites = r.inserts_seg[size_t(g.seg_of_pair[x])].n_sites;
+        if (o.isoforms.on && o.isoforms.ends) row.extent = r.extents[x], row.ends = r.read_ends[x];
         if (o.correct.on) {
             const ReadStatRow& rd = rows.row(g.pair_row[x]);
             const size_t q0 = size_t(g.offs[size_t(g.pairs[x].query)]), l0 = size_t(g.qoffs[size_t(g.pair_q[x])]), l1 = size_t(g.qoffs[size_t(g.pair_q[x]) + 1]);
@@ -492,6 +520,19 @@ void write_inserts(std::ofstream& out, const ReportGroup& g, const GroupResult& 
     }
 }
 
+void write_ends(std::ofstream& ends, std::ofstream& variants, const ReportGroup& g, const GroupResult& r)
+{
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0) continue;
+        const ioc_ends_seg& z = r.ends_seg[size_t(s)];
+        const string rows = cluster_ends_rows(g.group_cls[x].first, z, r.end_sites.data() + r.end_off[2 * size_t(s)], r.end_sites.data() + r.end_off[2 * size_t(s) + 1]);
+        const string vars = cluster_end_variants_rows(g.group_cls[x].first, z, r.end_variants.data() + r.var_off[size_t(s)]);
+        ends.write(rows.data(), std::streamsize(rows.size()));
+        variants.write(vars.data(), std::streamsize(vars.size()));
+    }
+}
+
 // cluster_inserts.fq: a record per called site, "@cluster_<id>/ins<b> rows=<lo>-<hi> voters=<n> template=<read>" — the consensus of
 // what the voters hold between rows lo and hi of the representative, to stand in place of those rows
 void write_insert_windows(std::ofstream& out, const ReportRows& rows, const ReportGroup& g, const GroupResult& r)
@@ -546,7 +587,7 @@ void write_isoforms_full(std::ofstream& out, const ReportGroup& g, const GroupRe
 
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq, full_fq;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq, full_fq, ends, end_variants;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -576,6 +617,12 @@ struct GroupFiles {
             if (o.isoforms.inserts_seq) create_file(outdir + "/cluster_inserts.fq", inserts_fq);
             if (o.isoforms.inserts_seq && o.isoforms.full) create_file(outdir + "/cluster_isoforms_full.fq", full_fq);
         }
+        if (o.isoforms.on && o.isoforms.ends) {
+            create_file(outdir + "/cluster_ends.tsv", ends);
+            ends << "ClusterId\tKind\tIndex\tFirst\tEnd\tPeakRow\tPeakReads\tReads\tOver\n";
+            create_file(outdir + "/cluster_end_variants.tsv", end_variants);
+            end_variants << "ClusterId\tVariant\tIsoform\tStartSite\tStopSite\tReads\n";
+        }
     }
     void write(const Batch& b, const ReportOpts& o, const ReportRows& rows, const ReportGroup& g, const GroupResult& r)
     {
@@ -586,6 +633,7 @@ struct GroupFiles {
         if (o.group_polish() && !g.segs.empty()) write_group_polish(group_polish, g, r);
         if (o.isoforms.on && !g.segs.empty()) write_blocks(blocks, isoforms, o.iso_polish() ? &iso_fq : nullptr, g, r);
         if (o.isoforms.on && o.isoforms.inserts && !g.segs.empty()) write_inserts(inserts, g, r);
+        if (o.isoforms.on && o.isoforms.ends && !g.segs.empty() && !g.pairs.empty()) write_ends(ends, end_variants, g, r);
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && !g.segs.empty() && !g.pairs.empty()) write_insert_windows(inserts_fq, rows, g, r);
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && o.isoforms.full && !g.segs.empty() && !g.pairs.empty()) write_isoforms_full(full_fq, g, r);
     }
@@ -642,6 +690,18 @@ void write_read_inserts(const string& outdir, const ReportRows& rows, const std:
     }
 }
 
+void write_read_ends(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/read_ends.tsv", out);
+    out << "Read\tClusterId\tFirstRow\tEndRow\tHead\tTail\tStartSite\tStopSite\tVariant\n";
+    for (size_t y = 0; y < rows.kept.size(); ++y) {
+        const ReadStatRow& r = rows.row(y);
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << r.cls << '\t' << read_end_columns(res[y].extent, res[y].ends) << '\n';
+    }
+}
+
 void write_corrected_reads(const string& outdir, const std::vector<RowResult>& res)
 {
     std::ofstream out;
@@ -693,4 +753,5 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
     if (opts.correct.on) write_corrected_reads(outdir, res);
     if (opts.isoforms.on) write_read_isoforms(outdir, rows, res);
     if (opts.isoforms.on && opts.isoforms.inserts) write_read_inserts(outdir, rows, res);
+    if (opts.isoforms.on && opts.isoforms.ends) write_read_ends(outdir, rows, res);
 }

@@ -1,4 +1,4 @@
-// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish, --isoforms-polish-weighted, --isoforms-inserts): every read of clusters.tsv
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish, --isoforms-polish-weighted, --isoforms-inserts, --isoforms-ends): every read of clusters.tsv
 // aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
 // formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
 #ifndef ISONCLUST2_CLI_REPORTS_HPP
@@ -37,6 +37,8 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     int ins_max_win = IOC_WIN_MAX;                   // (ioc_align_pairs_blocks_inserts_seq), and the longest window that votes
     bool full = false;                               // --isoforms-full: every combined isoform's full-length sequence as well
     int full_max = 16;                               // (ioc_align_pairs_isoforms_full), and how many isoforms of a cluster are called
+    bool ends = false;                               // --isoforms-ends: the alternative ends as well (ioc_align_pairs_blocks_ends), and the
+    int ends_slack = 10, ends_min_over = 20, ends_min_pct = 10, ends_max = 32, ends_max_variants = 64;  // thresholds of ioc_host_reads_ends the block search does not share
 };
 struct ReportOpts {
     bool stats = false;        // --read-stats
@@ -137,6 +139,21 @@ std::string inserts_signature(uint64_t key, int32_t n_sites);
 std::string cluster_inserts_rows(size_t cluster, const ioc_inserts_seg& z, const ioc_pile_insert* sites);
 // the columns of read_inserts.tsv behind the cluster and the read: "<signature> <combined isoform or .> <direct|assigned|rare|ambiguous>"
 std::string read_insert_columns(const ioc_read_inserts& r, int32_t n_sites);
+// the end sites (start and stop sites together) and the variants a search for ends may keep at most, for all segments of a group:
+// 2 min(max_sites, the representative's length + 1) and min(max_variants, its reads) each
+struct EndsCapacity {
+    int64_t sites = 0, variants = 0;
+};
+EndsCapacity ends_capacity(const ReportGroup& g, int max_sites, int max_variants);
+// the rows of cluster_ends.tsv of one cluster: "# cluster <id>: kept <n> of <found> start sites" (stop sites likewise) where a list
+// was cut, then "<id> <start|stop> <index> <first> <end> <peak row> <peak reads> <reads> <over>" per kept site, the start sites first
+std::string cluster_ends_rows(size_t cluster, const ioc_ends_seg& z, const ioc_end_site* starts, const ioc_end_site* stops);
+// the rows of cluster_end_variants.tsv of one cluster: "# cluster <id>: kept <n> of <found> variants" where the list was cut, then
+// "<id> <variant> <isoform> <start site> <stop site> <reads>" per kept variant
+std::string cluster_end_variants_rows(size_t cluster, const ioc_ends_seg& z, const ioc_end_variant* variants);
+// the columns of read_ends.tsv behind the read and the cluster: "<first row> <end row> <head> <tail> <start site or .> <stop site or .>
+// <variant or .>"
+std::string read_end_columns(const ioc_read_extent& e, const ioc_read_ends& r);
 // A signature: one character per kept block from the key's two bits each — '=' keep, '-' skip, '~' part, '.' none —, "*" where the
 // cluster has no block.
 std::string blocks_signature(uint64_t key, int32_t n_blocks);

@@ -22,6 +22,7 @@
 #include "ioc_pile_sites.h"
 #include "ioc_read_blocks.h"
 #include "ioc_read_inserts.h"
+#include "ioc_read_ends.h"
 #include "ioc_insert_windows.h"
 #include "ioc_iso_splice.h"
 #include "ioc_read_correct.h"
@@ -1080,6 +1081,124 @@ int32_t ioc_host_gap_open(double e)
 int ioc_host_align_route(int32_t match, int32_t mismatch, int32_t gap_extend, int32_t gap_open)
 {
     return aln_route(match, mismatch, gap_extend, gap_open);
+}
+
+// The extent of one read on its reference (isonclust2_hip.h has the rules): the rows its base plane covers — the bytes "=XD" of
+// the walk of ioc_host_ops_project — and the 'i' bytes before the first and behind the last byte of "=XID", as ioc_host_ops_stats
+// counts them.
+int ioc_host_ops_extent(const char* ops, int64_t len, int32_t rlen, ioc_read_extent* out)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || rlen < 0 || !out) return IOC_ERR_ARG;
+    int64_t r = 0, first = len, last = -1;  // the walk's first and last byte
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        r += op == '=' || op == 'X' || op == 'D' || op == 'd';
+        if (op == 'i' || op == 'd') continue;
+        if (first == len) first = a;
+        last = a;
+    }
+    if (r != rlen) return IOC_ERR_ARG;
+    ioc_read_extent e{0, 0, 0, 0};
+    r = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (op == 'i') a < first ? ++e.head : a > last ? ++e.tail : 0;  // (a string without a walk byte: all leading)
+        if (op == '=' || op == 'X' || op == 'D') {
+            if (e.end_row == 0) e.first_row = int32_t(r);
+            e.end_row = int32_t(r) + 1;
+        }
+        r += op != 'i' && op != 'I';
+    }
+    *out = e;
+    return IOC_OK;
+}
+
+// The alternative ends of one segment (isonclust2_hip.h has the rules; EndsRule::row, ends_distance, ends_near_word and ends_key,
+// ioc_read_ends.h, decide for this function and for the kernels of ioc_read_ends.hip alike).  The plain loops: the two histograms,
+// their windowed sums, the runs of start and of stop rows, every read's nearest sites, the sites' counts and peaks, and the
+// supported triples in ascending order.
+int ioc_host_reads_ends(const ioc_read_extent* extents, const int32_t* pre_group, int32_t n_reads, int32_t rlen, int32_t slack, int32_t min_over,
+                        int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites, int32_t max_variants, ioc_end_row* out_rows,
+                        ioc_end_site* out_starts, ioc_end_site* out_stops, ioc_end_variant* out_variants, ioc_read_ends* out_reads, ioc_ends_seg* out_seg)
+{
+    const EndsRule rule{slack, min_over, min_depth, min_alt, min_pct, max_sites, max_variants};
+    if (!rule.ok() || n_reads < 0 || rlen < 0 || !out_seg || !out_starts || !out_stops || (n_reads > 0 && (!extents || !out_reads || !out_variants)))
+        return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1, n = size_t(n_reads);
+    for (size_t i = 0; i < n; ++i)
+        if (!ends_extent_ok(extents[i], rlen) || (pre_group && pre_group[i] < -1)) return IOC_ERR_ARG;
+    auto pre = [&](size_t i) { return pre_group ? pre_group[i] : 0; };
+    std::vector<ioc_end_row> table(rows, ioc_end_row{0, 0, 0, 0});
+    uint32_t N = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (ends_takes_part(extents[i])) ++N, ++table[size_t(extents[i].first_row)].starts, ++table[size_t(extents[i].end_row)].stops;
+    for (int64_t p = 0; p <= rlen; ++p)
+        for (int64_t q = std::max<int64_t>(p - slack, 0); q <= std::min<int64_t>(p + slack, rlen); ++q)
+            table[size_t(p)].w_starts += table[size_t(q)].starts, table[size_t(p)].w_stops += table[size_t(q)].stops;
+    std::vector<ioc_end_site> sites[2];
+    int32_t n_found[2] = {0, 0};
+    for (int kind = 0; kind < 2; ++kind) {
+        auto is_row = [&](int64_t p) { return rule.row(N, kind ? table[size_t(p)].w_stops : table[size_t(p)].w_starts); };
+        auto count = [&](int64_t p) { return kind ? table[size_t(p)].stops : table[size_t(p)].starts; };
+        for (int64_t a = 0; a <= rlen;) {
+            int64_t e = a + 1;
+            if (is_row(a)) {
+                while (e <= rlen && is_row(e)) ++e;
+                if (n_found[kind] < max_sites) {
+                    unsigned long long peak = 0;
+                    for (int64_t p = a; p < e; ++p) peak = std::max(peak, ends_peak_word(count(p), uint32_t(rlen), uint32_t(p)));
+                    sites[kind].push_back(ioc_end_site{int32_t(a), int32_t(e), 0, 0, ends_peak_row(peak, uint32_t(rlen)), ends_peak_count(peak), kind, 0});
+                }
+                ++n_found[kind];
+            }
+            a = e;
+        }
+    }
+    std::vector<ioc_read_ends> reads(n, ioc_read_ends{-1, -1, -1, 0});
+    std::vector<unsigned long long> placed;  // the keys of the placed reads, sorted; then the supported ones, ascending
+    for (size_t i = 0; i < n; ++i) {
+        const ioc_read_extent& x = extents[i];
+        if (!ends_takes_part(x)) continue;
+        for (int kind = 0; kind < 2; ++kind) {
+            uint32_t best = ENDS_FAR;
+            for (size_t b = 0; b < sites[kind].size(); ++b)
+                best = std::min(best, ends_near_word(ends_distance(sites[kind][b].first, sites[kind][b].end, kind ? x.end_row : x.first_row), uint32_t(b), slack));
+            const int32_t site = ends_near_site(best);
+            (kind ? reads[i].stop_site : reads[i].start_site) = site;
+            if (site >= 0) ++sites[kind][size_t(site)].n_reads, sites[kind][size_t(site)].n_over += (kind ? x.tail : x.head) >= min_over;
+        }
+        if (ends_placed(pre(i), reads[i].start_site, reads[i].stop_site)) placed.push_back(ends_key(pre(i), reads[i].start_site, reads[i].stop_site));
+    }
+    const size_t n_placed = placed.size();
+    std::sort(placed.begin(), placed.end());
+    std::vector<unsigned long long> keys;
+    std::vector<ioc_end_variant> variants;
+    int32_t variants_found = 0;
+    for (size_t a = 0; a < placed.size();) {
+        size_t e = a;
+        while (e < placed.size() && placed[e] == placed[a]) ++e;
+        if (e - a >= size_t(min_alt)) {
+            if (variants_found < max_variants) {
+                keys.push_back(placed[a]);
+                variants.push_back(ioc_end_variant{int32_t(placed[a] >> 32), int32_t((placed[a] >> 8) & 0xFFu), int32_t(placed[a] & 0xFFu), uint32_t(e - a)});
+            }
+            ++variants_found;
+        }
+        a = e;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (!ends_placed(pre(i), reads[i].start_site, reads[i].stop_site)) continue;
+        const auto it = std::lower_bound(keys.begin(), keys.end(), ends_key(pre(i), reads[i].start_site, reads[i].stop_site));
+        if (it != keys.end() && *it == ends_key(pre(i), reads[i].start_site, reads[i].stop_site)) reads[i].variant = int32_t(it - keys.begin());
+    }
+    if (out_rows) std::copy(table.begin(), table.end(), out_rows);
+    std::copy(sites[0].begin(), sites[0].end(), out_starts);
+    std::copy(sites[1].begin(), sites[1].end(), out_stops);
+    std::copy(variants.begin(), variants.end(), out_variants);
+    std::copy(reads.begin(), reads.end(), out_reads);
+    *out_seg = ioc_ends_seg{int32_t(N), int32_t(sites[0].size()), n_found[0], int32_t(sites[1].size()), n_found[1], int32_t(variants.size()), variants_found, int32_t(n_placed)};
+    return IOC_OK;
 }
 
 // getAlnRatio, src/cluster.cpp:442-459

@@ -38,6 +38,7 @@ struct AlnTally {
     double ms_windows[4] = {};  // ... k_win_bounds, k_win_template, k_win_align and k_group_pile over the sites (ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq)
     double ms_splice[3] = {};   // k_splice_plan, k_splice_call's count pass with the scan, and its write pass (ioc_planes_isoforms_full,
                                 // ioc_align_pairs_isoforms_full, where ms_group_pile is k_group_pile over the combined isoforms)
+    double ms_ends[8] = {};     // the eight kernels of ioc_read_ends.hip, in the order they run (ioc_reads_ends, ioc_align_pairs_blocks_ends)
     double ms_split[9] = {};     // the split's kernels, in the order of IocSplitStep (timed under IOC_TRACE only), and ...
     int64_t split_uploaded = 0;  // ... what the split uploaded (ioc_alleles_split, ioc_align_pairs_split)
 };

@@ -3,7 +3,7 @@
 // (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.  An entry point checks its arguments, plans its
 // segments and pairs on the host (SinkPlan, ioc_sink_plan.h) and runs device stages in a row (SinkRun): pile -> sites -> alleles ->
 // [split] -> [group pile -> call] -> copy-out for the alleles family, pile -> call -> copy-out for the polish family, pile -> correct ->
-// copy-out for the read correction, pile -> blocks -> [inserts] -> copy-out for the exon blocks and the insertion sites, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
+// copy-out for the read correction, pile -> blocks -> [inserts | ends] -> copy-out for the exon blocks, the insertion sites and the alternative ends, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +20,7 @@
 #include "ioc_read_blocks.h"
 #include "ioc_read_correct.h"
 #include "ioc_read_inserts.h"
+#include "ioc_read_ends.h"
 #include "ioc_insert_windows.h"
 #include "ioc_iso_splice.h"
 
@@ -87,6 +88,19 @@ struct InsertsOut {  // the rule of a search for insertion sites and where it le
     ioc_read_inserts* reads;
     ioc_inserts_seg* seg;
     bool ok() const { return rule.ok() && site_off && cap >= 0; }
+};
+struct EndsOut {  // the rule of a search for ends and where it leaves what it made (cap / vcap: the records `sites` / `variants` hold)
+    EndsRule rule;
+    ioc_end_row* rows;
+    ioc_end_site* sites;
+    int64_t cap;
+    int64_t* site_off;
+    ioc_end_variant* variants;
+    int64_t vcap;
+    int64_t* var_off;
+    ioc_read_ends* reads;
+    ioc_ends_seg* seg;
+    bool ok() const { return rule.ok() && site_off && var_off && cap >= 0 && vcap >= 0; }
 };
 // the block stage's words an insert search combines with its own: the host's (uploaded), the device's (where the block stage left
 // them), or none (all NULL); pre_full is the host's, a word per segment
@@ -203,6 +217,8 @@ struct SinkRun {
     int blocks(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o, BlocksDev* where = nullptr);
     int inserts(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* host_ilen, const uint8_t* dev_base, const uint8_t* dev_ilen,
                 const InsertsPre& pre, const InsertsOut& o);
+    int ends(const SinkPlan& p, const int32_t* seg_of_pair, const ioc_read_extent* extents, const int32_t* host_pre, const int32_t* dev_pre, uint32_t dev_pre_stride,
+             const EndsOut& o);
 };
 
 // Pile and project.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it (ins), or a_pile_w as [wcols][wins] (weighted)
@@ -680,6 +696,97 @@ int SinkRun::inserts(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8
         o.seg[g] = rec[g];
     }
     return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_inserts)}, {o.rows, p + o_rows, size_t(pn.n_rows) * sizeof(ioc_insert_row)}});
+}
+
+// The kernels of ioc_read_ends.hip over the plan's pairs: the extents are the host's and uploaded; pre_group likewise (host_pre), or
+// lies on the device (dev_pre, a word every dev_pre_stride words), or there is none.  a_rends holds the host's tables [segments]
+// [seg_of_pair][mem_off][members][seg_word][word_seg][site_base][slot_unit][var_base][extents][pre_group], what the kernels add into
+// and what comes back packed on the host, set to 0 — [histograms][N per segment][site slots][variant slots][segment records] — and the
+// kernels' own [start rows][stop rows][keys][same][flags][read records][row table].  The segment records come back first and the
+// sites and variants are packed on the host, as the blocks are.  Under IOC_TRACE every kernel is timed on its own (t.ms_ends, in the
+// order they run); otherwise ms_ends[0] has all of them.
+int SinkRun::ends(const SinkPlan& pn, const int32_t* seg_of_pair, const ioc_read_extent* extents, const int32_t* host_pre, const int32_t* dev_pre,
+                  uint32_t dev_pre_stride, const EndsOut& o)
+{
+    const size_t n = pn.segs.size(), np = pn.plane.size();
+    const MemberLists m = member_lists(n, np, seg_of_pair);
+    std::vector<uint64_t> seg_word(n + 1, 0);
+    std::vector<int64_t> site_base(2 * n + 1, 0), var_base(n + 1, 0);
+    for (size_t g = 0; g < n; ++g) {
+        seg_word[g + 1] = seg_word[g] + uint64_t(pn.segs[g].rlen) / 64 + 1;
+        site_base[2 * g + 1] = site_base[2 * g] + ends_sites_most(pn.segs[g].rlen, o.rule.max_sites);
+        site_base[2 * g + 2] = site_base[2 * g + 1] + ends_sites_most(pn.segs[g].rlen, o.rule.max_sites);
+        var_base[g + 1] = var_base[g] + ends_variants_most(int64_t(m.mem_off[g + 1] - m.mem_off[g]), o.rule.max_variants);
+    }
+    const size_t T = size_t(seg_word[n]), slots = size_t(site_base[2 * n]), vslots = size_t(var_base[n]), R = size_t(pn.n_rows);
+    std::vector<int32_t> word_seg(T), slot_unit(slots);
+    for (size_t g = 0; g < n; ++g) std::fill(word_seg.begin() + int64_t(seg_word[g]), word_seg.begin() + int64_t(seg_word[g + 1]), int32_t(g));
+    for (size_t u = 0; u < 2 * n; ++u) std::fill(slot_unit.begin() + site_base[u], slot_unit.begin() + site_base[u + 1], int32_t(u));
+    Arena l;
+    const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_moff = l.take((n + 1) * 4), o_mem = l.take(np * 4), o_sw = l.take((n + 1) * 8),
+                 o_ws = l.take(T * 4), o_sb = l.take((2 * n + 1) * 8), o_su = l.take(slots * 4), o_vb = l.take((n + 1) * 8),
+                 o_ext = l.take(np * sizeof(ioc_read_extent)), o_pre = l.take(host_pre ? np * 4 : 0), tables = l.size();
+    const size_t o_hist = l.take(R * sizeof(uint2)), o_part = l.take(n * 4), o_sites = l.take(slots * sizeof(ioc_end_site)),
+                 o_vars = l.take(vslots * sizeof(ioc_end_variant)), o_rec = l.take(n * sizeof(ioc_ends_seg)), o_zend = l.size();
+    const size_t o_bs = l.take(T * 8), o_be = l.take(T * 8), o_key = l.take(np * 8), o_same = l.take(np * 4), o_flags = l.take(np),
+                 o_reads = l.take(np * sizeof(ioc_read_ends)), o_rows = l.take(o.rows ? R * sizeof(ioc_end_row) : 0);
+    std::vector<uint8_t> stage(tables, 0);
+    auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
+    put(o_seg, pn.segs.data(), n * sizeof(IocPileSeg)), put(o_sop, seg_of_pair, np * 4), put(o_moff, m.mem_off.data(), (n + 1) * 4);
+    put(o_mem, m.members.data(), np * 4), put(o_sw, seg_word.data(), (n + 1) * 8), put(o_ws, word_seg.data(), T * 4);
+    put(o_sb, site_base.data(), (2 * n + 1) * 8), put(o_su, slot_unit.data(), slots * 4), put(o_vb, var_base.data(), (n + 1) * 8);
+    put(o_ext, extents, np * sizeof(ioc_read_extent));
+    if (host_pre) put(o_pre, host_pre, np * 4);
+    IOC_CHK(c, hipSetDevice(c->device));
+    IOC_TRY(ioc_reserve(c, c->a_rends, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_rends.p);
+    IOC_CHK(c, hipMemcpyAsync(p, stage.data(), tables, hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemsetAsync(p + o_hist, 0, o_zend - o_hist, c->stream));  // (the histograms, N, the slots and the segment records)
+    auto u64p = [&](size_t at) { return reinterpret_cast<unsigned long long*>(p + at); };
+    const IocReadEndsDev v{reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop),
+                           reinterpret_cast<const ioc_read_extent*>(p + o_ext), dev_pre ? dev_pre : host_pre ? reinterpret_cast<const int32_t*>(p + o_pre) : nullptr,
+                           dev_pre ? dev_pre_stride : 1u, reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem),
+                           reinterpret_cast<const uint64_t*>(p + o_sw), reinterpret_cast<const int32_t*>(p + o_ws), reinterpret_cast<const int64_t*>(p + o_sb),
+                           reinterpret_cast<const int64_t*>(p + o_vb), reinterpret_cast<const int32_t*>(p + o_su), uint64_t(T), uint64_t(R), uint64_t(slots),
+                           uint64_t(vslots), reinterpret_cast<uint2*>(p + o_hist), reinterpret_cast<uint32_t*>(p + o_part), u64p(o_bs), u64p(o_be), u64p(o_key),
+                           reinterpret_cast<uint32_t*>(p + o_same), p + o_flags, o.rows ? reinterpret_cast<ioc_end_row*>(p + o_rows) : nullptr,
+                           reinterpret_cast<ioc_end_site*>(p + o_sites), reinterpret_cast<ioc_end_variant*>(p + o_vars),
+                           reinterpret_cast<ioc_read_ends*>(p + o_reads), reinterpret_cast<ioc_ends_seg*>(p + o_rec)};
+    const EndsRule& k = o.rule;
+    EventSet each;
+    if (getenv("IOC_TRACE")) {
+        each.v.assign(IOC_READ_ENDS_KERNELS + 1, nullptr);
+        for (auto& e : each.v) IOC_CHK(c, hipEventCreate(&e));
+    }
+    IOC_TRY(begin(t.ms_ends[0], each.v.empty()));
+    IOC_CHK(c, iock_read_ends(c->stream, v, k.slack, k.min_over, k.min_depth, k.min_alt, k.min_pct, k.max_sites, k.max_variants, each.v.empty() ? nullptr : each.v.data()));
+    IOC_TRY(end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    settled();
+    for (size_t x = 0; x + 1 < each.v.size(); ++x) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, each.v[x], each.v[x + 1]) == hipSuccess) t.ms_ends[x] += double(ms);
+    }
+    std::vector<ioc_ends_seg> rec(n);
+    std::vector<ioc_end_site> slot(slots);
+    std::vector<ioc_end_variant> vslot(vslots);
+    IOC_TRY(copy_out({{rec.data(), p + o_rec, n * sizeof(ioc_ends_seg)}, {slot.data(), p + o_sites, slots * sizeof(ioc_end_site)},
+                      {vslot.data(), p + o_vars, vslots * sizeof(ioc_end_variant)}}));
+    for (size_t g = 0; g < n; ++g)
+        if (rec[g].n_starts < 0 || rec[g].n_starts > site_base[2 * g + 1] - site_base[2 * g] || rec[g].n_stops < 0 ||
+            rec[g].n_stops > site_base[2 * g + 2] - site_base[2 * g + 1] || rec[g].n_variants < 0 || rec[g].n_variants > var_base[g + 1] - var_base[g])
+            return ioc_fail(c, IOC_ERR_HIP, "the search for ends returned a count outside its bound");
+    o.site_off[0] = 0, o.var_off[0] = 0;
+    for (size_t g = 0; g < n; ++g) {
+        std::copy(slot.begin() + site_base[2 * g], slot.begin() + site_base[2 * g] + rec[g].n_starts, o.sites + o.site_off[2 * g]);
+        o.site_off[2 * g + 1] = o.site_off[2 * g] + rec[g].n_starts;
+        std::copy(slot.begin() + site_base[2 * g + 1], slot.begin() + site_base[2 * g + 1] + rec[g].n_stops, o.sites + o.site_off[2 * g + 1]);
+        o.site_off[2 * g + 2] = o.site_off[2 * g + 1] + rec[g].n_stops;
+        std::copy(vslot.begin() + var_base[g], vslot.begin() + var_base[g] + rec[g].n_variants, o.variants + o.var_off[g]);
+        o.var_off[g + 1] = o.var_off[g] + rec[g].n_variants;
+        o.seg[g] = rec[g];
+    }
+    return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_ends)}, {o.rows, p + o_rows, R * sizeof(ioc_end_row)}});
 }
 
 }  // namespace
@@ -1395,6 +1502,99 @@ int ioc_align_pairs_blocks_inserts(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pa
                 n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[n_segs], double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_pileup,
                 r.t.ms_project, r.t.ms_project_ilen, r.t.ms_blocks, inserts_trace(r.t).c_str(),
                 out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
+    return IOC_OK;
+}
+
+// what a search for ends refuses once its plan is known: IOC_OK, or the status with the message set
+static int ends_room_ok(ioc_ctx* c, const std::string& who, const EndsOut& o, const SinkPlan& p, const int32_t* seg_of_pair)
+{
+    int64_t bound = 0, vbound = 0;
+    std::vector<int64_t> reads(p.segs.size(), 0);
+    for (size_t i = 0; i < p.plane.size(); ++i) ++reads[size_t(seg_of_pair[i])];
+    for (size_t g = 0; g < p.segs.size(); ++g)
+        bound += 2 * ends_sites_most(p.segs[g].rlen, o.rule.max_sites), vbound += ends_variants_most(reads[g], o.rule.max_variants);
+    if (o.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": sites_cap " + std::to_string(o.cap) + " below the bound " + std::to_string(bound));
+    if (o.vcap < vbound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": variants_cap " + std::to_string(o.vcap) + " below the bound " + std::to_string(vbound));
+    return (bound > 0 && !o.sites) || (vbound > 0 && !o.variants) || (!p.plane.empty() && !o.reads) || (!p.segs.empty() && !o.seg) ? IOC_ERR_ARG : IOC_OK;
+}
+static std::string ends_trace(const AlnTally& t)
+{
+    char buf[400];
+    snprintf(buf, sizeof buf, "k_end_hist %.3f ms, k_end_rows %.3f ms, k_end_list %.3f ms, k_end_class %.3f ms, k_end_count %.3f ms, k_end_support %.3f ms, k_end_variants %.3f ms, k_ends_record %.3f ms",
+             t.ms_ends[0], t.ms_ends[1], t.ms_ends[2], t.ms_ends[3], t.ms_ends[4], t.ms_ends[5], t.ms_ends[6], t.ms_ends[7]);
+    return buf;
+}
+
+// upload -> ends -> copy-out.  The search for ends from extents the caller holds: they are uploaded, and the kernels run as behind
+// ioc_align_pairs_blocks_ends.
+int ioc_reads_ends(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const ioc_read_extent* extents,
+                   const int32_t* pre_group, int32_t slack, int32_t min_over, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_sites,
+                   int32_t max_variants, ioc_end_row* out_rows, ioc_end_site* out_sites, int64_t sites_cap, int64_t* site_off, ioc_end_variant* out_variants,
+                   int64_t variants_cap, int64_t* var_off, ioc_read_ends* out_reads, ioc_ends_seg* out_seg)
+{
+    const EndsOut o{{slack, min_over, min_depth, min_alt, min_pct, max_sites, max_variants}, out_rows, out_sites, sites_cap, site_off, out_variants, variants_cap,
+                    var_off, out_reads, out_seg};
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || (n_segs > 0 && !rlen) || (n_pairs > 0 && (!seg_of_pair || !extents))) return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen("ioc_reads_ends", n_segs, rlen, nullptr, nullptr, n_pairs, seg_of_pair, nullptr, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
+    for (int32_t i = 0; i < n_pairs; ++i)
+        if (!ends_extent_ok(extents[i], rlen[seg_of_pair[i]]) || (pre_group && pre_group[i] < -1))
+            return ioc_fail(c, IOC_ERR_ARG, "ioc_reads_ends: the extent or pre_group of pair " + std::to_string(i) + " is outside its segment's range");
+    IOC_TRY(ends_room_ok(c, "ioc_reads_ends", o, p, seg_of_pair));
+    site_off[0] = 0, var_off[0] = 0;
+    if (n_segs == 0) return IOC_OK;
+    SinkRun r{c};
+    IOC_TRY(r.ends(p, seg_of_pair, extents, pre_group, nullptr, 1, o));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   reads ends: %d segments, %lld rows, %d pairs, %lld sites kept, %lld variants kept, %s\n", n_segs, (long long)p.n_rows, n_pairs,
+                (long long)site_off[2 * n_segs], (long long)var_off[n_segs], ends_trace(r.t).c_str());
+    return IOC_OK;
+}
+
+// pile -> blocks -> ends -> copy-out.  ioc_align_pairs_blocks with the statistics kernel run over every slice (into the caller's
+// records, or into the call's own where none are asked), and behind the block kernels the ends kernels: the extents are put together
+// on the host from the block records and the statistics, both of which the call holds there anyway, and uploaded with the stage's
+// tables; pre_group is the block stage's group where that stage left it (a_blocks), the ends stage has a_rends.
+int ioc_align_pairs_blocks_ends(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
+                                const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
+                                int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off,
+                                ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t slack, int32_t min_over,
+                                int32_t ends_min_pct, int32_t max_sites, int32_t max_variants, ioc_read_extent* out_extents, ioc_end_row* out_erows,
+                                ioc_end_site* out_sites, int64_t sites_cap, int64_t* site_off, ioc_end_variant* out_variants, int64_t variants_cap,
+                                int64_t* var_off, ioc_read_ends* out_ereads, ioc_ends_seg* out_eseg)
+{
+    const std::string who = "ioc_align_pairs_blocks_ends";
+    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
+    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
+    const EndsOut eo{{slack, min_over, min_depth, min_alt, ends_min_pct, max_sites, max_variants}, out_erows, out_sites, sites_cap, site_off, out_variants,
+                     variants_cap, var_off, out_ereads, out_eseg};
+    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !eo.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair || !out_extents)) || (n_segs > 0 && !segs))
+        return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
+    IOC_TRY(blocks_room_ok(c, who, o, p));
+    IOC_TRY(ends_room_ok(c, who, eo, p, seg_of_pair));
+    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
+    for (int32_t i = 0; i < n_pairs; ++i) out_extents[i] = ioc_read_extent{0, 0, 0, 0};
+    block_off[0] = 0, site_off[0] = 0, var_off[0] = 0;
+    if (n_segs == 0) return a.run(c, nullptr);
+    std::vector<ioc_aln_stats> own_stats(out_stats ? 0 : size_t(n_pairs), ioc_aln_stats{});
+    const ioc_aln_stats* stats = out_stats ? out_stats : own_stats.data();
+    SinkRun r{c};
+    PiledDev d;
+    BlocksDev bd{};
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats ? out_stats : own_stats.data(), p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d));
+    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o, &bd));  // (a_blocks is reserved here, after the walks)
+    for (int32_t i = 0; i < n_pairs; ++i) out_extents[i] = ioc_read_extent{out_reads[i].first_row, out_reads[i].end_row, stats[i].lead_i, stats[i].trail_i};
+    static_assert(sizeof(ioc_read_blocks) % 4 == 0 && offsetof(ioc_read_blocks, group) % 4 == 0, "a record's group is a word of its own");
+    const int32_t* dev_group = n_pairs > 0 ? reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(bd.reads) + offsetof(ioc_read_blocks, group)) : nullptr;
+    IOC_TRY(r.ends(p, seg_of_pair, out_extents, nullptr, dev_group, uint32_t(sizeof(ioc_read_blocks) / 4), eo));  // (a_rends likewise)
+    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: blocks ends: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld end sites kept, %lld variants kept, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms, k_ops_stats %.3f ms, %s\n",
+                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[2 * n_segs], (long long)var_off[n_segs],
+                double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_blocks, r.t.ms_stats, ends_trace(r.t).c_str());
     return IOC_OK;
 }
 

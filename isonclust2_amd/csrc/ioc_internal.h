@@ -228,6 +228,8 @@ struct ioc_ctx {
     DevBuf a_windows; // ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq: the tables, the (pair, site) entries and the records of
                       // k_win_bounds / k_win_template and, uploaded, both planes; the alignments' items, planes and direction words share a_gpile
                       // with the group pile behind them
+    DevBuf a_rends;   // ioc_reads_ends, ioc_align_pairs_blocks_ends: the tables, histograms, bit planes and records of ioc_read_ends.hip and, uploaded,
+                      // the extents and pre_group
     DevBuf a_splice;  // ioc_planes_isoforms_full, ioc_align_pairs_isoforms_full: keys, windows, plans, records and the spliced bytes (ioc_iso_splice.hip)
     DevBuf a_blocks;  // ioc_planes_blocks, ioc_align_pairs_blocks: segments, pairs, member lists, bit planes, tables and records (ioc_read_blocks.hip) and,
                       // from host planes, the uploaded planes
@@ -609,6 +611,42 @@ hipError_t iock_splice_plan(hipStream_t st, const IocSpliceDev& v);
 hipError_t iock_splice_call(hipStream_t st, const IocSpliceDev& v, bool emit, const ioc_pileup_col* cols, const ioc_pileup_ins* ins, uint64_t n_rows,
                             const uint8_t* frames, uint64_t frame_bytes, int32_t min_depth, int64_t* seg_len, ioc_polish_stats* stats, const int64_t* out_off,
                             uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);
+
+// ioc_read_ends.hip: the alternative ends of many segments (ioc_host_reads_ends per segment).  Everything is a device pointer.
+// Pair i belongs to segment seg_of_pair[i], has the extent extents[i] and pre_group[i * pre_stride] (pre_group NULL: 0).  Segment
+// g: the pairs members[mem_off[g] .. mem_off[g + 1]) in ascending order as its reads, its rows of `hist` (and of `rows`, which may
+// be NULL) from segs[g].row0 on, its ceil((rlen + 1) / 64) words of either bit plane from seg_word[g] on (n_seg_words in all;
+// word_seg says whose each is), its min(max_sites, rlen + 1) start slots from site_base[2 g] on and as many stop slots from
+// site_base[2 g + 1] on (n_site_slots in all; slot_unit says which 2 g + kind each belongs to) and its min(max_variants, reads)
+// variant slots from var_base[g] on (n_var_slots in all).  hist (starts, stops a row), n_part (a word per segment), sites,
+// variants and seg_out are set to 0 by the caller; key, same and flags are a word, a word and a byte of scratch per pair.
+struct IocReadEndsDev {
+    const IocPileSeg* segs;
+    uint32_t n_segs, n_pairs;
+    const int32_t* seg_of_pair;
+    const ioc_read_extent* extents;
+    const int32_t* pre_group;
+    uint32_t pre_stride;
+    const uint32_t *mem_off, *members;
+    const uint64_t* seg_word;
+    const int32_t* word_seg;
+    const int64_t *site_base, *var_base;
+    const int32_t* slot_unit;
+    uint64_t n_seg_words, n_rows, n_site_slots, n_var_slots;
+    uint2* hist;
+    uint32_t* n_part;
+    unsigned long long *bits_start, *bits_stop, *key;
+    uint32_t* same;
+    uint8_t* flags;
+    ioc_end_row* rows;
+    ioc_end_site* sites;
+    ioc_end_variant* variants;
+    ioc_read_ends* reads;
+    ioc_ends_seg* seg_out;
+};
+enum { IOC_READ_ENDS_KERNELS = 8 };  // (each: IOC_READ_ENDS_KERNELS + 1 events, or NULL)
+hipError_t iock_read_ends(hipStream_t st, const IocReadEndsDev& v, int32_t slack, int32_t min_over, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                          int32_t max_sites, int32_t max_variants, hipEvent_t* each);
 
 // ioc_site_split.hip: the split of many segments' reads by their linked sites (ioc_host_alleles_split per segment).  Everything
 // is a device pointer.  Segment g: the sites site_off[g] .. site_off[g + 1], the pairs members[mem_off[g] .. mem_off[g + 1]) in
