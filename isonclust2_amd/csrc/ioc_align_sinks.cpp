@@ -165,6 +165,29 @@ struct Planes {
 };
 struct Out { void* dst; const void* src; size_t bytes; };  // a block that goes back to the host where the caller asked for it (dst NULL: not)
 
+// The events that time every kernel of a stage on its own under IOC_TRACE: one in front of each of the `kernels` and one behind the
+// last, or none.  events() is what the stage's launcher takes (NULL: none); once the stream has been waited for, add_to(ms) adds
+// what lay between every two to ms[0 .. kernels).
+struct KernelTimes {
+    EventSet each;
+    int create(ioc_ctx* c, size_t kernels)
+    {
+        if (!getenv("IOC_TRACE")) return IOC_OK;
+        each.v.assign(kernels + 1, nullptr);
+        for (auto& e : each.v) IOC_CHK(c, hipEventCreate(&e));
+        return IOC_OK;
+    }
+    bool on() const { return !each.v.empty(); }
+    hipEvent_t* events() { return on() ? each.v.data() : nullptr; }
+    void add_to(double* ms) const
+    {
+        for (size_t x = 0; x + 1 < each.v.size(); ++x) {
+            float one = 0;
+            if (hipEventElapsedTime(&one, each.v[x], each.v[x + 1]) == hipSuccess) ms[x] += double(one);
+        }
+    }
+};
+
 // One call's stages over a context, the tally of its trace line and the device time of its launches: begin / end record an event
 // either side of a launch (timed false: none is created), and settled(), once the stream has been waited for, adds what lay
 // between them to `ms`.
@@ -603,12 +626,8 @@ int SinkRun::blocks(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8_
     for (size_t g = 0; g < n; ++g)
         if (rec[g].n_blocks < 0 || rec[g].n_blocks > bt.block_base[g + 1] - bt.block_base[g])
             return ioc_fail(c, IOC_ERR_HIP, "the block search returned a count outside its bound");
-    o.block_off[0] = 0;
-    for (size_t g = 0; g < n; ++g) {
-        std::copy(slot.begin() + bt.block_base[g], slot.begin() + bt.block_base[g] + rec[g].n_blocks, o.blocks + o.block_off[g]);
-        o.block_off[g + 1] = o.block_off[g] + rec[g].n_blocks;
-        o.seg[g] = rec[g];
-    }
+    pack_kept_slots(slot, bt.block_base.data(), n, [&](size_t g) { return rec[g].n_blocks; }, o.blocks, o.block_off);
+    std::copy(rec.begin(), rec.end(), o.seg);
     return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_blocks)}, {o.rows, p + o_rows, size_t(pn.n_rows) * sizeof(ioc_block_row)}});
 }
 
@@ -627,8 +646,7 @@ int SinkRun::inserts(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8
     std::vector<int64_t> site_base(n + 1, 0);
     for (size_t g = 0; g < n; ++g) site_base[g + 1] = site_base[g] + inserts_sites_most(pn.segs[g].rlen, o.rule.max_sites);
     const size_t P = bt.P, T = bt.T, slots = size_t(site_base[n]);
-    std::vector<int32_t> slot_seg(slots);
-    for (size_t g = 0; g < n; ++g) std::fill(slot_seg.begin() + site_base[g], slot_seg.begin() + site_base[g + 1], int32_t(g));
+    const std::vector<int32_t> slot_seg = slot_owners(site_base.data(), n);
     const bool pre_host = pre.host_key != nullptr, pre_dev = pre.dev_key != nullptr, with_pre = pre_host || pre_dev;
     Arena l;
     const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_plane = l.take(np * 8), o_moff = l.take((n + 1) * 4), o_mem = l.take(np * 4),
@@ -669,32 +687,22 @@ int SinkRun::inserts(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8
                               reinterpret_cast<ioc_insert_row*>(p + o_rows), reinterpret_cast<ioc_pile_insert*>(p + o_sites),
                               reinterpret_cast<ioc_read_inserts*>(p + o_reads), reinterpret_cast<ioc_inserts_seg*>(p + o_rec)};
     const InsertsRule& k = o.rule;
-    EventSet each;
-    if (getenv("IOC_TRACE")) {
-        each.v.assign(IOC_READ_INSERTS_KERNELS + 1, nullptr);
-        for (auto& e : each.v) IOC_CHK(c, hipEventCreate(&e));
-    }
-    IOC_TRY(begin(t.ms_inserts[0], each.v.empty()));
-    IOC_CHK(c, iock_read_inserts(c->stream, v, k.min_ins, k.slack, k.min_depth, k.min_alt, k.min_pct, k.max_sites, each.v.empty() ? nullptr : each.v.data()));
+    KernelTimes each;
+    IOC_TRY(each.create(c, IOC_READ_INSERTS_KERNELS));
+    IOC_TRY(begin(t.ms_inserts[0], !each.on()));
+    IOC_CHK(c, iock_read_inserts(c->stream, v, k.min_ins, k.slack, k.min_depth, k.min_alt, k.min_pct, k.max_sites, each.events()));
     IOC_TRY(end());
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     settled();
-    for (size_t x = 0; x + 1 < each.v.size(); ++x) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, each.v[x], each.v[x + 1]) == hipSuccess) t.ms_inserts[x] += double(ms);
-    }
+    each.add_to(t.ms_inserts);
     std::vector<ioc_inserts_seg> rec(n);
     std::vector<ioc_pile_insert> slot(slots);
     IOC_TRY(copy_out({{rec.data(), p + o_rec, n * sizeof(ioc_inserts_seg)}, {slot.data(), p + o_sites, slots * sizeof(ioc_pile_insert)}}));
     for (size_t g = 0; g < n; ++g)
         if (rec[g].n_sites < 0 || rec[g].n_sites > site_base[g + 1] - site_base[g])
             return ioc_fail(c, IOC_ERR_HIP, "the search for insertion sites returned a count outside its bound");
-    o.site_off[0] = 0;
-    for (size_t g = 0; g < n; ++g) {
-        std::copy(slot.begin() + site_base[g], slot.begin() + site_base[g] + rec[g].n_sites, o.sites + o.site_off[g]);
-        o.site_off[g + 1] = o.site_off[g] + rec[g].n_sites;
-        o.seg[g] = rec[g];
-    }
+    pack_kept_slots(slot, site_base.data(), n, [&](size_t g) { return rec[g].n_sites; }, o.sites, o.site_off);
+    std::copy(rec.begin(), rec.end(), o.seg);
     return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_inserts)}, {o.rows, p + o_rows, size_t(pn.n_rows) * sizeof(ioc_insert_row)}});
 }
 
@@ -710,18 +718,15 @@ int SinkRun::ends(const SinkPlan& pn, const int32_t* seg_of_pair, const ioc_read
 {
     const size_t n = pn.segs.size(), np = pn.plane.size();
     const MemberLists m = member_lists(n, np, seg_of_pair);
-    std::vector<uint64_t> seg_word(n + 1, 0);
+    const SegWordTable sw = seg_word_table(pn.segs);  // (the words of a segment are the block stage's)
     std::vector<int64_t> site_base(2 * n + 1, 0), var_base(n + 1, 0);
     for (size_t g = 0; g < n; ++g) {
-        seg_word[g + 1] = seg_word[g] + uint64_t(pn.segs[g].rlen) / 64 + 1;
         site_base[2 * g + 1] = site_base[2 * g] + ends_sites_most(pn.segs[g].rlen, o.rule.max_sites);
         site_base[2 * g + 2] = site_base[2 * g + 1] + ends_sites_most(pn.segs[g].rlen, o.rule.max_sites);
         var_base[g + 1] = var_base[g] + ends_variants_most(int64_t(m.mem_off[g + 1] - m.mem_off[g]), o.rule.max_variants);
     }
-    const size_t T = size_t(seg_word[n]), slots = size_t(site_base[2 * n]), vslots = size_t(var_base[n]), R = size_t(pn.n_rows);
-    std::vector<int32_t> word_seg(T), slot_unit(slots);
-    for (size_t g = 0; g < n; ++g) std::fill(word_seg.begin() + int64_t(seg_word[g]), word_seg.begin() + int64_t(seg_word[g + 1]), int32_t(g));
-    for (size_t u = 0; u < 2 * n; ++u) std::fill(slot_unit.begin() + site_base[u], slot_unit.begin() + site_base[u + 1], int32_t(u));
+    const size_t T = sw.T, slots = size_t(site_base[2 * n]), vslots = size_t(var_base[n]), R = size_t(pn.n_rows);
+    const std::vector<int32_t> slot_unit = slot_owners(site_base.data(), 2 * n);
     Arena l;
     const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_moff = l.take((n + 1) * 4), o_mem = l.take(np * 4), o_sw = l.take((n + 1) * 8),
                  o_ws = l.take(T * 4), o_sb = l.take((2 * n + 1) * 8), o_su = l.take(slots * 4), o_vb = l.take((n + 1) * 8),
@@ -733,7 +738,7 @@ int SinkRun::ends(const SinkPlan& pn, const int32_t* seg_of_pair, const ioc_read
     std::vector<uint8_t> stage(tables, 0);
     auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
     put(o_seg, pn.segs.data(), n * sizeof(IocPileSeg)), put(o_sop, seg_of_pair, np * 4), put(o_moff, m.mem_off.data(), (n + 1) * 4);
-    put(o_mem, m.members.data(), np * 4), put(o_sw, seg_word.data(), (n + 1) * 8), put(o_ws, word_seg.data(), T * 4);
+    put(o_mem, m.members.data(), np * 4), put(o_sw, sw.seg_word.data(), (n + 1) * 8), put(o_ws, sw.word_seg.data(), T * 4);
     put(o_sb, site_base.data(), (2 * n + 1) * 8), put(o_su, slot_unit.data(), slots * 4), put(o_vb, var_base.data(), (n + 1) * 8);
     put(o_ext, extents, np * sizeof(ioc_read_extent));
     if (host_pre) put(o_pre, host_pre, np * 4);
@@ -753,20 +758,14 @@ int SinkRun::ends(const SinkPlan& pn, const int32_t* seg_of_pair, const ioc_read
                            reinterpret_cast<ioc_end_site*>(p + o_sites), reinterpret_cast<ioc_end_variant*>(p + o_vars),
                            reinterpret_cast<ioc_read_ends*>(p + o_reads), reinterpret_cast<ioc_ends_seg*>(p + o_rec)};
     const EndsRule& k = o.rule;
-    EventSet each;
-    if (getenv("IOC_TRACE")) {
-        each.v.assign(IOC_READ_ENDS_KERNELS + 1, nullptr);
-        for (auto& e : each.v) IOC_CHK(c, hipEventCreate(&e));
-    }
-    IOC_TRY(begin(t.ms_ends[0], each.v.empty()));
-    IOC_CHK(c, iock_read_ends(c->stream, v, k.slack, k.min_over, k.min_depth, k.min_alt, k.min_pct, k.max_sites, k.max_variants, each.v.empty() ? nullptr : each.v.data()));
+    KernelTimes each;
+    IOC_TRY(each.create(c, IOC_READ_ENDS_KERNELS));
+    IOC_TRY(begin(t.ms_ends[0], !each.on()));
+    IOC_CHK(c, iock_read_ends(c->stream, v, k.slack, k.min_over, k.min_depth, k.min_alt, k.min_pct, k.max_sites, k.max_variants, each.events()));
     IOC_TRY(end());
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     settled();
-    for (size_t x = 0; x + 1 < each.v.size(); ++x) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, each.v[x], each.v[x + 1]) == hipSuccess) t.ms_ends[x] += double(ms);
-    }
+    each.add_to(t.ms_ends);
     std::vector<ioc_ends_seg> rec(n);
     std::vector<ioc_end_site> slot(slots);
     std::vector<ioc_end_variant> vslot(vslots);
@@ -776,16 +775,9 @@ int SinkRun::ends(const SinkPlan& pn, const int32_t* seg_of_pair, const ioc_read
         if (rec[g].n_starts < 0 || rec[g].n_starts > site_base[2 * g + 1] - site_base[2 * g] || rec[g].n_stops < 0 ||
             rec[g].n_stops > site_base[2 * g + 2] - site_base[2 * g + 1] || rec[g].n_variants < 0 || rec[g].n_variants > var_base[g + 1] - var_base[g])
             return ioc_fail(c, IOC_ERR_HIP, "the search for ends returned a count outside its bound");
-    o.site_off[0] = 0, o.var_off[0] = 0;
-    for (size_t g = 0; g < n; ++g) {
-        std::copy(slot.begin() + site_base[2 * g], slot.begin() + site_base[2 * g] + rec[g].n_starts, o.sites + o.site_off[2 * g]);
-        o.site_off[2 * g + 1] = o.site_off[2 * g] + rec[g].n_starts;
-        std::copy(slot.begin() + site_base[2 * g + 1], slot.begin() + site_base[2 * g + 1] + rec[g].n_stops, o.sites + o.site_off[2 * g + 1]);
-        o.site_off[2 * g + 2] = o.site_off[2 * g + 1] + rec[g].n_stops;
-        std::copy(vslot.begin() + var_base[g], vslot.begin() + var_base[g] + rec[g].n_variants, o.variants + o.var_off[g]);
-        o.var_off[g + 1] = o.var_off[g] + rec[g].n_variants;
-        o.seg[g] = rec[g];
-    }
+    pack_kept_slots(slot, site_base.data(), 2 * n, [&](size_t u) { return u & 1 ? rec[u / 2].n_stops : rec[u / 2].n_starts; }, o.sites, o.site_off);
+    pack_kept_slots(vslot, var_base.data(), n, [&](size_t g) { return rec[g].n_variants; }, o.variants, o.var_off);
+    std::copy(rec.begin(), rec.end(), o.seg);
     return copy_out({{o.reads, p + o_reads, np * sizeof(ioc_read_ends)}, {o.rows, p + o_rows, R * sizeof(ioc_end_row)}});
 }
 
@@ -1651,12 +1643,9 @@ static int windows_device(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_
     for (size_t x = 0; x < ns; ++x) o.call.stats[x] = ioc_polish_stats{};
     if (ns == 0) return IOC_OK;
     const MemberLists m = member_lists(n, np, seg_of_pair);
-    std::vector<int32_t> site_seg(ns);
+    const std::vector<int32_t> site_seg = slot_owners(site_off, n);
     size_t stride = 1;
-    for (size_t g = 0; g < n; ++g) {
-        std::fill(site_seg.begin() + site_off[g], site_seg.begin() + site_off[g + 1], int32_t(g));
-        stride = std::max(stride, size_t(site_off[g + 1] - site_off[g]));
-    }
+    for (size_t g = 0; g < n; ++g) stride = std::max(stride, size_t(site_off[g + 1] - site_off[g]));
     Arena l;
     const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_plane = l.take(np * 8), o_qlen = l.take(np * 4), o_moff = l.take((n + 1) * 4),
                  o_mem = l.take(np * 4), o_sites = l.take(ns * sizeof(ioc_pile_insert)), o_soff = l.take((n + 1) * 8), o_sseg = l.take(ns * 4),
@@ -1682,20 +1671,14 @@ static int windows_device(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_
                       reinterpret_cast<const int64_t*>(p + o_soff), reinterpret_cast<const int32_t*>(p + o_sseg), uint32_t(ns),
                       reinterpret_cast<const unsigned long long*>(p + o_keys), reinterpret_cast<IocWinSlot*>(p + o_slots), uint32_t(stride), uint64_t(np * stride),
                       reinterpret_cast<ioc_insert_window*>(p + o_win)};
-    EventSet each;
-    if (getenv("IOC_TRACE")) {
-        each.v.assign(3, nullptr);
-        for (auto& e : each.v) IOC_CHK(c, hipEventCreate(&e));
-    }
-    IOC_TRY(r.begin(r.t.ms_windows[0], each.v.empty()));
-    IOC_CHK(c, iock_win_bounds_template(c->stream, v, o.rule.slack, o.rule.max_win, each.v.empty() ? nullptr : each.v.data()));
+    KernelTimes each;
+    IOC_TRY(each.create(c, 2));
+    IOC_TRY(r.begin(r.t.ms_windows[0], !each.on()));
+    IOC_CHK(c, iock_win_bounds_template(c->stream, v, o.rule.slack, o.rule.max_win, each.events()));
     IOC_TRY(r.end());
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     r.settled();
-    for (size_t x = 0; x + 1 < each.v.size(); ++x) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, each.v[x], each.v[x + 1]) == hipSuccess) r.t.ms_windows[x] += double(ms);
-    }
+    each.add_to(r.t.ms_windows);
     std::vector<ioc_insert_window> win(ns);
     std::vector<IocWinSlot> slot(np * stride);
     IOC_TRY(r.copy_out({{win.data(), p + o_win, ns * sizeof(ioc_insert_window)}, {slot.data(), p + o_slots, np * stride * sizeof(IocWinSlot)}}));

@@ -30,6 +30,7 @@
 #include "ioc_insert_windows.h"
 #include "ioc_internal.h"
 #include "ioc_ops_pileup.h"
+#include "ioc_wave.h"
 
 namespace {
 
@@ -78,8 +79,6 @@ k_ops_project_qpos(const uint8_t* __restrict__ buf, const uint64_t* __restrict__
         w = w_next;
     }
 }
-
-__device__ __forceinline__ uint32_t shfl32(uint32_t v, uint32_t src) { return uint32_t(__shfl(int(v), int(src), 64)); }
 
 __global__ void __launch_bounds__(64 * WAVES)
 k_win_bounds(IocWinDev v, int32_t slack, int32_t max_win)

@@ -9,7 +9,7 @@
 //   k_splice_call<false> the shape of k_pile_call: a workgroup per group-segment, chunks of IOC_PILE_CALL_CHUNK rows, a lane per
 //                       row.  The plan sits in LDS; a row inside an interval counts nothing, the row lo of one counts its window's
 //                       length (up to 7 IOC_WIN_MAX + 6 bytes, so the sums are 32-bit words all the way, never the 7 bytes a row
-//                       has in k_pile_call), any other row is decided by pile_call_row as always.  seg_len[x] and the record.
+//                       has in k_pile_call), any other row is decided as always (pile_call_seg_row, ioc_pile_call.h).  seg_len[x] and the record.
 //   (iock_pile_scan)    out_off = the exclusive scan of seg_len: the scan kernel of ioc_pile_call.hip.
 //   k_splice_call<true> decides again and writes: the wave scan and the workgroup scan give every lane where its bytes begin; the
 //                       lane of a row lo writes nothing itself, it notes the place in LDS and in the site's record (`at`), and once
@@ -23,6 +23,7 @@
 #include "ioc_internal.h"
 #include "ioc_iso_splice.h"
 #include "ioc_pile_call.h"
+#include "ioc_wave.h"
 
 namespace {
 
@@ -30,48 +31,6 @@ constexpr uint32_t CHUNK = IOC_PILE_CALL_CHUNK;  // rows per step of a workgroup
 constexpr uint32_t WAVES = CHUNK / 64u;
 constexpr uint32_t PLAN_MAX = IOC_SPLICE_PLAN_MAX;
 static_assert(CHUNK % 64u == 0 && WAVES >= 1 && WAVES <= 16 && PLAN_MAX <= 64u && PLAN_MAX <= CHUNK, "whole waves, a lane per site");
-
-__device__ __forceinline__ uint8_t comp_base(uint8_t ch)  // (the aligner's: anything but A C G T stays)
-{
-    return ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
-}
-
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t up = uint32_t(__shfl_up(int(v), d, 64));
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) v += uint32_t(__shfl_xor(int(v), int(d), 64));
-    return v;
-}
-
-// row p of group-segment s (p <= s.rlen) as k_pile_call decides it, or nothing where its records or its frame byte lie outside
-// what was passed
-__device__ __forceinline__ PileRowCall decide(const IocPileSeg& s, uint32_t p, const ioc_pileup_col* __restrict__ cols,
-                                              const ioc_pileup_ins* __restrict__ ins, uint64_t n_rows, const uint8_t* __restrict__ frames,
-                                              uint64_t frame_bytes, int32_t min_depth)
-{
-    const uint32_t rlen = uint32_t(s.rlen);
-    const uint64_t row = uint64_t(s.row0) + p;
-    if (row >= n_rows) return PileRowCall{};
-    const bool has_base = p < rlen;
-    uint8_t fb = 0;
-    if (has_base) {
-        const uint64_t at = uint64_t(s.f_off) + (s.rc ? rlen - 1u - p : p);
-        if (at >= frame_bytes) return PileRowCall{};
-        fb = s.rc ? comp_base(frames[at]) : frames[at];
-    }
-    const unsigned long long d_ins = has_base ? pile_depth(cols[row]) : rlen > 0u ? pile_depth(cols[row - 1u]) : 0ull;
-    return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth);
-}
 
 // a wave per group-segment, a lane per site
 __global__ void __launch_bounds__(CHUNK)
@@ -148,7 +107,7 @@ k_splice_call(IocSpliceDev v, const ioc_pileup_col* __restrict__ cols, const ioc
                 n += uint32_t(plan[what].len);
                 continue;
             }
-            const PileRowCall r = decide(s, p, cols, ins, n_rows, frames, frame_bytes, min_depth);
+            const PileRowCall r = pile_call_seg_row<false>(s, p, cols, ins, nullptr, n_rows, frames, frame_bytes, min_depth);
             n += r.n, k_ins += r.n_ins, k_sub += r.n_sub, k_del += r.n_del, k_low += r.n_low;
         }
         // (the bytes of a group-segment fit 32 bits like the record's out_len: the entries refuse a longer bound)
@@ -174,7 +133,7 @@ k_splice_call(IocSpliceDev v, const ioc_pileup_col* __restrict__ cols, const ioc
         const uint32_t p = c * CHUNK + tid;
         const int32_t what = p < rows ? splice_row(plan, np, int32_t(p)) : IOC_SPLICE_ROW_GONE;
         PileRowCall r{};
-        if (p < rows && what == IOC_SPLICE_ROW_CALL) r = decide(s, p, cols, ins, n_rows, frames, frame_bytes, min_depth);
+        if (p < rows && what == IOC_SPLICE_ROW_CALL) r = pile_call_seg_row<false>(s, p, cols, ins, nullptr, n_rows, frames, frame_bytes, min_depth);
         const uint32_t n = what >= 0 ? uint32_t(plan[what].len) : r.n;
         const uint32_t incl = wave_scan_incl(n, lane);
         uint32_t* tot = part[c & 1u];  // (two sets: a wave may be a step ahead of another one's reads)

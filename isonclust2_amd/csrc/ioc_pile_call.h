@@ -90,3 +90,41 @@ IOC_PILE_HD PileRowCall pile_call_row(const ioc_pileup_col& col, const ioc_pileu
 {
     return pile_call_row(col, in, d_ins, has_base, frame, min_depth, d_ins, has_base ? pile_depth(col) : 0ull);
 }
+
+#if defined(__HIPCC__)
+// Device code only from here on: a lane of the call kernels (ioc_pile_call.hip, ioc_iso_splice.hip) fetches its row and decides it.
+#include <hip/hip_runtime.h>
+
+#include "ioc_sink_plan.h"
+
+// the complement of a frame byte where a segment is read reverse-complemented (the aligner's rule, ioc_align_gpu.hip, which keeps
+// its own copy beside its kernels: anything but A C G T stays)
+__device__ __forceinline__ uint8_t comp_base(uint8_t ch)
+{
+    return ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
+}
+
+// Row p of segment s (p <= s.rlen) fetched and called, or nothing where its records or its frame byte lie outside what was passed.
+// WEIGHTED (ioc_host_pileup_call_weighted): cols / ins are the tables of weights, which decide, and `gate` is the table of counts,
+// whose depths min_depth is held against (n_rows records like the others); the majority call does not read `gate`.
+template <bool WEIGHTED>
+__device__ __forceinline__ PileRowCall pile_call_seg_row(const IocPileSeg& s, uint32_t p, const ioc_pileup_col* __restrict__ cols,
+                                                         const ioc_pileup_ins* __restrict__ ins, const ioc_pileup_col* __restrict__ gate,
+                                                         uint64_t n_rows, const uint8_t* __restrict__ frames, uint64_t frame_bytes, int32_t min_depth)
+{
+    const uint32_t rlen = uint32_t(s.rlen);
+    const uint64_t row = uint64_t(s.row0) + p;
+    if (row >= n_rows) return PileRowCall{};
+    const bool has_base = p < rlen;
+    uint8_t fb = 0;
+    if (has_base) {
+        const uint64_t at = uint64_t(s.f_off) + (s.rc ? rlen - 1u - p : p);
+        if (at >= frame_bytes) return PileRowCall{};
+        fb = s.rc ? comp_base(frames[at]) : frames[at];
+    }
+    const unsigned long long d_ins = has_base ? pile_depth(cols[row]) : rlen > 0u ? pile_depth(cols[row - 1u]) : 0ull;
+    if (!WEIGHTED) return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth);
+    const unsigned long long c_ins = has_base ? pile_depth(gate[row]) : rlen > 0u ? pile_depth(gate[row - 1u]) : 0ull;
+    return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth, c_ins, has_base ? pile_depth(gate[row]) : 0ull);
+}
+#endif

@@ -3,7 +3,7 @@
 //
 // A segment is one reference: rlen + 1 rows of both tables from a row base on, and its frame in a pool of sequences, read
 // reverse-complemented on the fly where the segment says so (as the aligner reads its references).  One workgroup per segment
-// walks it in chunks of IOC_PILE_CALL_CHUNK rows, a lane per row: the lane decides its row (pile_call_row, ioc_pile_call.h — the
+// walks it in chunks of IOC_PILE_CALL_CHUNK rows, a lane per row: the lane decides its row (pile_call_seg_row and pile_call_row, ioc_pile_call.h — the
 // function the definition uses) and holds the 0 to 7 bytes it emits, sequence and qualities, in two 64-bit registers.
 //
 //   (each of the two passes in two modes: the majority call, and the weighted call of ioc_host_pileup_call_weighted, which
@@ -23,70 +23,13 @@
 
 #include "ioc_internal.h"
 #include "ioc_pile_call.h"
+#include "ioc_wave.h"
 
 namespace {
 
 constexpr uint32_t CHUNK = IOC_PILE_CALL_CHUNK;  // rows per step of a workgroup = its threads
 constexpr uint32_t WAVES = CHUNK / 64u;
 static_assert(CHUNK % 64u == 0 && WAVES >= 1 && WAVES <= 16, "whole waves");
-
-__device__ __forceinline__ uint8_t comp_base(uint8_t ch)  // (the aligner's: anything but A C G T stays)
-{
-    return ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
-}
-
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t up = uint32_t(__shfl_up(int(v), d, 64));
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long shfl_up64(unsigned long long v, uint32_t d)
-{
-    const uint32_t lo = uint32_t(__shfl_up(int(uint32_t(v)), d, 64)), hi = uint32_t(__shfl_up(int(uint32_t(v >> 32)), d, 64));
-    return (unsigned long long)hi << 32 | lo;
-}
-
-__device__ __forceinline__ unsigned long long shfl64(unsigned long long v, uint32_t from)
-{
-    const uint32_t lo = uint32_t(__shfl(int(uint32_t(v)), int(from), 64)), hi = uint32_t(__shfl(int(uint32_t(v >> 32)), int(from), 64));
-    return (unsigned long long)hi << 32 | lo;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) v += uint32_t(__shfl_xor(int(v), int(d), 64));
-    return v;
-}
-
-// row p of segment s (p <= s.rlen), or nothing where its records or its frame byte lie outside what was passed.  WEIGHTED
-// (ioc_host_pileup_call_weighted): cols / ins are the tables of weights, which decide, and `gate` is the table of counts, whose
-// depths min_depth is held against (n_rows records like the others); the majority call does not read `gate`.
-template <bool WEIGHTED>
-__device__ __forceinline__ PileRowCall decide(const IocPileSeg& s, uint32_t p, const ioc_pileup_col* __restrict__ cols,
-                                              const ioc_pileup_ins* __restrict__ ins, const ioc_pileup_col* __restrict__ gate, uint64_t n_rows,
-                                              const uint8_t* __restrict__ frames, uint64_t frame_bytes, int32_t min_depth)
-{
-    const uint32_t rlen = uint32_t(s.rlen);
-    const uint64_t row = uint64_t(s.row0) + p;
-    if (row >= n_rows) return PileRowCall{};
-    const bool has_base = p < rlen;
-    uint8_t fb = 0;
-    if (has_base) {
-        const uint64_t at = uint64_t(s.f_off) + (s.rc ? rlen - 1u - p : p);
-        if (at >= frame_bytes) return PileRowCall{};
-        fb = s.rc ? comp_base(frames[at]) : frames[at];
-    }
-    const unsigned long long d_ins = has_base ? pile_depth(cols[row]) : rlen > 0u ? pile_depth(cols[row - 1u]) : 0ull;
-    if (!WEIGHTED) return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth);
-    const unsigned long long c_ins = has_base ? pile_depth(gate[row]) : rlen > 0u ? pile_depth(gate[row - 1u]) : 0ull;
-    return pile_call_row(cols[row], ins[row], d_ins, has_base, fb, min_depth, c_ins, has_base ? pile_depth(gate[row]) : 0ull);
-}
 
 template <bool EMIT, bool WEIGHTED>
 __global__ void __launch_bounds__(CHUNK)
@@ -107,7 +50,7 @@ k_pile_call(const IocPileSeg* __restrict__ segs, uint32_t n_segs, const ioc_pile
         for (uint32_t c = 0; c < nchunks; ++c) {
             const uint32_t p = c * CHUNK + tid;
             if (p >= rows) break;
-            const PileRowCall r = decide<WEIGHTED>(s, p, cols, ins, gate, n_rows, frames, frame_bytes, min_depth);
+            const PileRowCall r = pile_call_seg_row<WEIGHTED>(s, p, cols, ins, gate, n_rows, frames, frame_bytes, min_depth);
             n += r.n, k_ins += r.n_ins, k_sub += r.n_sub, k_del += r.n_del, k_low += r.n_low;
         }
         // (the bytes of a segment, at most 7 per row, fit 32 bits like the record's out_len: the entries refuse longer segments)
@@ -131,7 +74,7 @@ k_pile_call(const IocPileSeg* __restrict__ segs, uint32_t n_segs, const ioc_pile
     for (uint32_t c = 0; c < nchunks; ++c) {  // (every lane of the workgroup takes every step: there are barriers in it)
         const uint32_t p = c * CHUNK + tid;
         PileRowCall r{};
-        if (p < rows) r = decide<WEIGHTED>(s, p, cols, ins, gate, n_rows, frames, frame_bytes, min_depth);
+        if (p < rows) r = pile_call_seg_row<WEIGHTED>(s, p, cols, ins, gate, n_rows, frames, frame_bytes, min_depth);
         const uint32_t incl = wave_scan_incl(r.n, lane);
         uint32_t* tot = part[c & 1u];  // (two sets: a wave may be a step ahead of another one's reads)
         if (lane == 63u) tot[wave] = incl;

@@ -23,6 +23,7 @@
 
 #include "ioc_internal.h"
 #include "ioc_pile_sites.h"
+#include "ioc_wave.h"
 
 namespace {
 
@@ -80,35 +81,6 @@ k_ops_project(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ end,
         }
         w = w_next;
     }
-}
-
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t up = uint32_t(__shfl_up(int(v), d, 64));
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) v += uint32_t(__shfl_xor(int(v), int(d), 64));
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long shfl_up64(unsigned long long v, uint32_t d)
-{
-    const uint32_t lo = uint32_t(__shfl_up(int(uint32_t(v)), d, 64)), hi = uint32_t(__shfl_up(int(uint32_t(v >> 32)), d, 64));
-    return (unsigned long long)hi << 32 | lo;
-}
-
-__device__ __forceinline__ unsigned long long shfl64(unsigned long long v, uint32_t from)
-{
-    const uint32_t lo = uint32_t(__shfl(int(uint32_t(v)), int(from), 64)), hi = uint32_t(__shfl(int(uint32_t(v >> 32)), int(from), 64));
-    return (unsigned long long)hi << 32 | lo;
 }
 
 // row p of segment s (p <= s.rlen), or nothing where its record lies outside the table

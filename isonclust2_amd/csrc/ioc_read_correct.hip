@@ -22,33 +22,12 @@
 
 #include "ioc_internal.h"
 #include "ioc_read_correct.h"
+#include "ioc_wave.h"
 
 namespace {
 
 constexpr uint32_t WAVES = IOC_READ_CORRECT_WAVES;
 constexpr uint32_t SLOTS = IOC_PILE_INS_SLOTS;
-
-__device__ __forceinline__ uint8_t comp_base(uint8_t ch)  // (the aligner's: anything but A C G T stays)
-{
-    return ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
-}
-
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t up = uint32_t(__shfl_up(int(v), d, 64));
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) v += uint32_t(__shfl_xor(int(v), int(d), 64));
-    return v;
-}
 
 // what a wave reads of its pair: the tables, the frames and the planes with their sizes, and where the pair's rows lie in them
 struct PairView {

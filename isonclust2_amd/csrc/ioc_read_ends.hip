@@ -7,11 +7,10 @@
 //                   inputs alone.  The other way, a lane per row over the segment's extents, reads every extent of a segment once per
 //                   64 rows: 24 passes over 600 extents for a 1500-row representative, against three adds a read.
 //   k_end_rows      a wave per 64 rows of a segment, a lane per row: Ws and We from two wave prefix sums each, over the 64 rows and
-//                   over a halo of 32 on either side (k_ins_bits' window_sums on counts; slack <= 32 fits the halo), the row test, the
+//                   over a halo of 32 on either side (window_sums, ioc_read_stage.h; slack <= 32 fits the halo), the row test, the
 //                   start-row and stop-row words by ballot, and the row table where it is asked for.
-//   k_end_list      a wave per (segment, kind) sweeps its words for runs as k_ins_list does: across a word where the neighbour's edge
-//                   bit is set (run_starts / run_ends, ioc_read_blocks.h), across a 64-word batch by a carried bit and one word read
-//                   ahead; ranks by a wave scan and a running base; the first max_sites are written.
+//   k_end_list      a wave per (segment, kind) sweeps its words for runs of any length (run_list_any, ioc_read_stage.h); the first
+//                   max_sites are written.
 //   k_end_class     a wave per read: lanes 0 .. 31 the kept start sites, lanes 32 .. 63 the kept stop sites; (distance, site) as one
 //                   word, its minimum over each half of the wave; then the read's key and whether it is placed.
 //   k_end_count     a wave per kept site: the segment's reads 64 at a time, n_reads and n_over by ballot and popcount; then the peak,
@@ -19,9 +18,10 @@
 //                   k_end_list: there the lanes that would read a site's bounds are not the lanes that wrote them, within one wave
 //                   and with no kernel boundary between the store and the load; here the bounds come from an earlier kernel.)
 //   k_end_support, k_end_variants, k_ends_record
-//                   k_key_support, k_read_isoforms and k_blocks_record over one unsigned 64-bit key a read whose order is the
-//                   variants'; unplaced reads are left out by a flag.  A wave per read over its segment's reads: the two kernels
-//                   quadratic in a segment's reads.
+//                   the shape of key_support, key_isoform and key_tallies (ioc_read_stage.h) over one unsigned 64-bit key a read
+//                   whose order is the variants'; unplaced reads are left out by a flag and a read's support is a `same` word, not
+//                   masks, so these keep bodies of their own and share tally_hits.  A wave per read over its segment's reads: the
+//                   two kernels quadratic in a segment's reads.
 // No floating point, no LDS; but for the adds of k_end_hist every output word has one writer.  Every row, word, slot and record is
 // held against the sizes passed.
 #include <hip/hip_runtime.h>
@@ -30,6 +30,7 @@
 
 #include "ioc_internal.h"
 #include "ioc_read_ends.h"
+#include "ioc_read_stage.h"
 
 namespace {
 
@@ -38,50 +39,6 @@ typedef unsigned long long u64;
 
 enum : uint8_t { END_PLACED = 1 };
 enum : uint32_t { SAME_FIRST = 0x80000000u, SAME_COUNT = 0x7FFFFFFFu };  // `same`: how many placed reads carry the read's key; bit 31: none before it
-
-__device__ __forceinline__ uint32_t shfl32(uint32_t v, uint32_t src) { return uint32_t(__shfl(int(v), int(src), 64)); }
-__device__ __forceinline__ u64 shfl64(u64 v, uint32_t src)
-{
-    const uint32_t lo = shfl32(uint32_t(v), src), hi = shfl32(uint32_t(v >> 32), src);
-    return u64(hi) << 32 | lo;
-}
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t up = uint32_t(__shfl_up(int(v), d, 64));
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 wave_max64(u64 v)
-{
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) {
-        const uint32_t lo = uint32_t(__shfl_xor(int(uint32_t(v)), int(d), 64)), hi = uint32_t(__shfl_xor(int(uint32_t(v >> 32)), int(d), 64));
-        v = max(v, u64(hi) << 32 | lo);
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t seg_words(const IocPileSeg& s) { return uint32_t(s.rlen) / 64u + 1u; }  // ceil((rlen + 1) / 64)
-
-// W(p0 + lane) of counts of which the lane holds own = the one at p0 + lane and halo = the one at p0 - 32 + lane (lanes 0 .. 31) or
-// p0 + 32 + lane (lanes 32 .. 63), 0 outside rows 0 .. rlen so that the window needs no clamping.  Every lane of the wave takes
-// part.  A[0 .. 128) = the 32 below p0, the 64 from p0 on, the 32 behind them; sV and sH are the inclusive prefix sums of the middle
-// and of the halo, and the inclusive prefix of A at idx is sH[idx], sH[31] + sV[idx - 32] or sV[63] + sH[idx - 64].  W = prefix(32 +
-// lane + slack) - prefix(32 + lane - slack - 1); slack <= 32 keeps both inside -1 .. 127.
-__device__ __forceinline__ uint32_t window_sums(uint32_t own, uint32_t halo, uint32_t slack, uint32_t lane)
-{
-    const uint32_t sV = wave_scan_incl(own, lane), sH = wave_scan_incl(halo, lane);
-    const uint32_t left = shfl32(sH, 31u), mid = shfl32(sV, 63u);
-    auto prefix = [&](int idx) -> uint32_t {
-        const uint32_t fromH = shfl32(sH, uint32_t(idx < 32 ? idx : idx - 64) & 63u), fromV = shfl32(sV, uint32_t(idx - 32) & 63u);
-        return idx < 0 ? 0u : idx < 32 ? fromH : idx < 96 ? left + fromV : mid + fromH;
-    };
-    const uint32_t hi = prefix(int(32u + lane + slack)), lo = prefix(int(32u + lane) - int(slack) - 1);
-    return hi - lo;
-}
 
 __global__ void __launch_bounds__(64 * WAVES)
 k_end_hist(IocReadEndsDev v)
@@ -131,24 +88,7 @@ k_end_list(IocReadEndsDev v)
     const u64 sb = u64(v.site_base[u]), at = v.seg_word[g];
     const uint32_t most = uint32_t(u64(v.site_base[u + 1u]) - sb);  // min(max_sites, rlen + 1)
     const u64* bits = kind ? v.bits_stop : v.bits_start;
-    auto load = [&](uint32_t i) -> u64 { return i < W && at + i < v.n_seg_words ? bits[at + i] : 0ull; };
-    uint32_t base_s = 0, base_e = 0;  // the starts and the ends of runs below the batch
-    u64 top = 0;                      // whether the row right below the batch is set
-    for (uint32_t b0 = 0; b0 < W; b0 += 64u) {
-        const u64 w = load(b0 + lane);
-        const u64 dn = shfl64(w, (lane + 63u) & 63u), up = shfl64(w, (lane + 1u) & 63u);
-        const uint32_t left = uint32_t(lane ? dn >> 63 : top), right = uint32_t((lane < 63u ? up : load(b0 + 64u)) & 1ull);
-        u64 st = run_starts(w, left), en = run_ends(w, right);
-        const uint32_t ns = uint32_t(__popcll(st)), ne = uint32_t(__popcll(en));
-        const uint32_t is = wave_scan_incl(ns, lane), ie = wave_scan_incl(ne, lane);
-        const uint32_t row = (b0 + lane) * 64u;
-        for (uint32_t k = base_s + is - ns; st && k < most; ++k, st &= st - 1ull)
-            if (sb + k < v.n_site_slots) v.sites[sb + k].first = int32_t(row + uint32_t(__builtin_ctzll(st)));
-        for (uint32_t k = base_e + ie - ne; en && k < most; ++k, en &= en - 1ull)
-            if (sb + k < v.n_site_slots) v.sites[sb + k].end = int32_t(row + uint32_t(__builtin_ctzll(en)) + 1u);
-        base_s += shfl32(is, 63), base_e += shfl32(ie, 63);
-        top = shfl64(w, 63u) >> 63;
-    }
+    const uint32_t base_s = run_list_any(bits, at, v.n_seg_words, W, lane, v.sites, sb, v.n_site_slots, most);
     if (lane == 0) {
         ioc_ends_seg* r = v.seg_out + g;
         if (kind) r->n_stops = int32_t(min(base_s, most)), r->n_stops_found = int32_t(base_s);
@@ -229,14 +169,14 @@ k_end_count(IocReadEndsDev v, EndsRule rule)
 }
 
 // what a wave reads of member m of its segment (lane's member of a chunk): the pair, whether it is placed, its key, its `same` word
-struct Member {
+struct EndMember {
     uint32_t pair = 0xFFFFFFFFu, same = 0;
     u64 key = 0;
     bool placed = false;
 };
-__device__ __forceinline__ Member member_at(const IocReadEndsDev& v, uint32_t m, uint32_t me, bool with_same)
+__device__ __forceinline__ EndMember end_member_at(const IocReadEndsDev& v, uint32_t m, uint32_t me, bool with_same)
 {
-    Member x;
+    EndMember x;
     if (m >= me) return x;
     x.pair = v.members[m];
     if (x.pair >= v.n_pairs) return x;
@@ -257,10 +197,9 @@ k_end_support(IocReadEndsDev v)
         const u64 key = v.key[i];
         const uint32_t mb = v.mem_off[g], me = v.mem_off[g + 1u];
         for (uint32_t m0 = mb; m0 < me; m0 += 64u) {
-            const Member x = member_at(v, m0 + lane, me, false);
+            const EndMember x = end_member_at(v, m0 + lane, me, false);
             const bool hit = x.placed && x.key == key;
-            same += uint32_t(__popcll(__ballot(hit)));
-            earlier += uint32_t(__popcll(__ballot(hit && x.pair < i)));  // (a segment's reads are its pairs in ascending order)
+            tally_hits(hit, x.pair < i, same, earlier);  // (a segment's reads are its pairs in ascending order)
         }
     }
     if (lane == 0) v.same[i] = same ? (same & SAME_COUNT) | (earlier == 0u ? uint32_t(SAME_FIRST) : 0u) : 0u;
@@ -279,7 +218,7 @@ k_end_variants(IocReadEndsDev v, EndsRule rule)
     uint32_t rank = 0;  // the supported keys below the read's, each counted at its first read
     const uint32_t mb = v.mem_off[g], me = v.mem_off[g + 1u];
     for (uint32_t m0 = mb; m0 < me; m0 += 64u) {
-        const Member x = member_at(v, m0 + lane, me, true);
+        const EndMember x = end_member_at(v, m0 + lane, me, true);
         rank += uint32_t(__popcll(__ballot(x.placed && (x.same & SAME_FIRST) && (x.same & SAME_COUNT) >= uint32_t(rule.min_alt) && x.key < key)));
     }
     const u64 vb = u64(v.var_base[g]);
@@ -298,7 +237,7 @@ k_ends_record(IocReadEndsDev v, EndsRule rule)
     const uint32_t mb = v.mem_off[g], me = v.mem_off[g + 1u];
     uint32_t placed = 0, found = 0;
     for (uint32_t m0 = mb; m0 < me; m0 += 64u) {
-        const Member x = member_at(v, m0 + lane, me, true);
+        const EndMember x = end_member_at(v, m0 + lane, me, true);
         placed += uint32_t(__popcll(__ballot(x.placed)));
         found += uint32_t(__popcll(__ballot(x.placed && (x.same & SAME_FIRST) && (x.same & SAME_COUNT) >= uint32_t(rule.min_alt))));
     }

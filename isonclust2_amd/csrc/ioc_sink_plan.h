@@ -194,29 +194,61 @@ struct SinkPlan {
     }
 };
 
-// The block search's tables (IocReadBlocksDev, ioc_internal.h): a bit plane holds ceil((rlen + 1) / 64) words of a pair from
-// pair_word[i] on, P words in all, and as many of a segment from seg_word[g] on, T in all — word_seg says whose each is —;
-// block_base: where a segment's min(max_blocks, rlen) block slots begin, and their sum.
-struct BlocksTables {
-    std::vector<uint64_t> pair_word, seg_word;
+// Whose slot is this: unit u (a segment, or a segment's starts or stops) has the slots base[u] .. base[u + 1] of a row of slots,
+// and entry x of the table names the unit of slot x.
+template <class Off>
+inline std::vector<int32_t> slot_owners(const Off* base, size_t units)
+{
+    std::vector<int32_t> owner(units ? size_t(base[units]) : 0);
+    for (size_t u = 0; u < units; ++u) std::fill(owner.begin() + int64_t(base[u]), owner.begin() + int64_t(base[u + 1]), int32_t(u));
+    return owner;
+}
+
+// A search leaves unit u's records in its slots from base[u] on and says how many of them it kept, kept(u), which the caller has
+// held against the slots the unit has: the kept ones are packed into `out`, unit after unit, and off[0 .. units] says where each
+// unit's begin.
+template <class Rec, class Kept>
+inline void pack_kept_slots(const std::vector<Rec>& slot, const int64_t* base, size_t units, Kept kept, Rec* out, int64_t* off)
+{
+    off[0] = 0;
+    for (size_t u = 0; u < units; ++u) {
+        std::copy(slot.begin() + base[u], slot.begin() + base[u] + kept(u), out + off[u]);
+        off[u + 1] = off[u] + kept(u);
+    }
+}
+
+// The words of the segments' bit planes (the stages of ioc_read_blocks.hip, ioc_read_inserts.hip and ioc_read_ends.hip): segment g
+// has ceil((rlen + 1) / 64) words from seg_word[g] on, T in all, and word_seg says whose each is.
+struct SegWordTable {
+    std::vector<uint64_t> seg_word;
     std::vector<int32_t> word_seg;
+    size_t T = 0;
+};
+inline SegWordTable seg_word_table(const std::vector<IocPileSeg>& segs)
+{
+    SegWordTable t;
+    t.seg_word.assign(segs.size() + 1, 0);
+    for (size_t g = 0; g < segs.size(); ++g) t.seg_word[g + 1] = t.seg_word[g] + uint64_t(segs[g].rlen) / 64 + 1;
+    t.T = size_t(t.seg_word[segs.size()]);
+    t.word_seg = slot_owners(t.seg_word.data(), segs.size());
+    return t;
+}
+
+// The block search's tables (IocReadBlocksDev, ioc_internal.h): the segments' words, and as many words of a pair from pair_word[i]
+// on, P words in all; block_base: where a segment's min(max_blocks, rlen) block slots begin, and their sum.
+struct BlocksTables : SegWordTable {
+    std::vector<uint64_t> pair_word;
     std::vector<int64_t> block_base;
-    size_t P = 0, T = 0;
+    size_t P = 0;
 };
 inline BlocksTables blocks_tables(const SinkPlan& p, const int32_t* seg_of_pair, int32_t max_blocks)
 {
     const size_t n = p.segs.size(), np = p.plane.size();
     BlocksTables t;
-    auto words = [&](size_t g) { return size_t(p.segs[g].rlen) / 64 + 1; };
-    t.seg_word.assign(n + 1, 0), t.block_base.assign(n + 1, 0), t.pair_word.assign(np, 0);
-    for (size_t g = 0; g < n; ++g) {
-        t.seg_word[g + 1] = t.seg_word[g] + words(g);
-        t.block_base[g + 1] = t.block_base[g] + pile_blocks_most(p.segs[g].rlen, max_blocks);
-    }
-    t.T = size_t(t.seg_word[n]);
-    t.word_seg.resize(t.T);
-    for (size_t g = 0; g < n; ++g) std::fill(t.word_seg.begin() + int64_t(t.seg_word[g]), t.word_seg.begin() + int64_t(t.seg_word[g + 1]), int32_t(g));
-    for (size_t i = 0; i < np; ++i) t.pair_word[i] = t.P, t.P += words(size_t(seg_of_pair[i]));
+    static_cast<SegWordTable&>(t) = seg_word_table(p.segs);
+    t.block_base.assign(n + 1, 0), t.pair_word.assign(np, 0);
+    for (size_t g = 0; g < n; ++g) t.block_base[g + 1] = t.block_base[g] + pile_blocks_most(p.segs[g].rlen, max_blocks);
+    for (size_t i = 0; i < np; ++i) t.pair_word[i] = t.P, t.P += size_t(t.seg_word[size_t(seg_of_pair[i]) + 1] - t.seg_word[size_t(seg_of_pair[i])]);
     return t;
 }
 

@@ -25,6 +25,7 @@
 
 #include "ioc_internal.h"
 #include "ioc_site_split.h"
+#include "ioc_wave.h"
 
 namespace {
 
@@ -32,29 +33,6 @@ using u64 = unsigned long long;
 
 constexpr int SP_WAVES = 4;      // waves per workgroup of the kernels that give a wave a site or a pair
 constexpr uint32_t TILE_ROW = 68;  // bytes per read of the LDS tile: 64 and a pad that spreads a column over the banks
-
-__device__ __forceinline__ u64 shfl64(u64 v, uint32_t from)
-{
-    const uint32_t lo = uint32_t(__shfl(int(uint32_t(v)), int(from), 64)), hi = uint32_t(__shfl(int(uint32_t(v >> 32)), int(from), 64));
-    return u64(hi) << 32 | lo;
-}
-
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) {
-        const uint32_t lo = uint32_t(__shfl_xor(int(uint32_t(v)), int(d), 64)), hi = uint32_t(__shfl_xor(int(uint32_t(v >> 32)), int(d), 64));
-        v += u64(hi) << 32 | lo;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int32_t wave_sum32(int32_t v)
-{
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1) v += __shfl_xor(v, int(d), 64);
-    return v;
-}
 
 // d of the pair of words (a_minor, a_major) — wave-uniform or a lane's own — with site t's, over the W words of a segment
 __device__ __forceinline__ int32_t d_with_site(const u64* __restrict__ a_minor, const u64* __restrict__ a_major, uint64_t a_stride,

@@ -14,7 +14,8 @@
 //    totals of one case per stage against the hand-chained sums the stages used to carry), member_lists (no segments, no pairs,
 //    segments without pairs, pairs out of segment order, one segment for all), group_member_lists (the same per group: pairs in
 //    -1 or in a group their segment lacks, empty groups, segments without groups), the split's tables (0, 1, 64, 65 and 128 members,
-//    a segment without sites between two with), the bounds at their edges, and both constructors of SinkPlan with every refusal's
+//    a segment without sites between two with), the words of the segments' bit planes with the block search's tables on top of
+//    them (63, 64, 65, 128 and 129 rows), whose slot is whose and the packing of kept slots, the bounds at their edges, and both constructors of SinkPlan with every refusal's
 //    status and message as the entry points have always worded them.
 //
 // Host code only (the header includes no HIP header); meant for the sanitizers:
@@ -397,6 +398,50 @@ void check_split_tables()
     for (size_t g = 0; g < 5; ++g) EXPECT(split_tables(1, std::vector<int64_t>{0, 1}.data(), {0, members[g]}).T == words_of[g]);
 }
 
+// the words of the segments' bit planes, the blocks' tables on top of them, whose slot is whose, and the packing of kept slots
+void check_slot_tables()
+{
+    g_what = "slot tables";
+    const std::vector<int32_t> rlens{0, 1, 62, 63, 64, 127, 128, 600, 0};  // rlen + 1 rows: 63 | 64 | 65 and 128 | 129 rows either side of a word
+    for (size_t n = 0; n <= rlens.size(); ++n) {
+        std::vector<IocPileSeg> segs;
+        std::vector<uint64_t> seg_word{0};
+        std::vector<int32_t> word_seg;
+        for (size_t g = 0; g < n; ++g) {
+            uint64_t words = 0;
+            while (64 * words < uint64_t(rlens[g]) + 1) ++words;
+            segs.push_back(IocPileSeg{0, 0, rlens[g], 0});
+            seg_word.push_back(seg_word[g] + words), word_seg.insert(word_seg.end(), size_t(words), int32_t(g));
+        }
+        const SegWordTable t = seg_word_table(segs);
+        EXPECT(t.seg_word == seg_word && t.word_seg == word_seg && t.T == word_seg.size());
+        SinkPlan pn;
+        pn.segs = segs;
+        std::vector<int32_t> sop;
+        for (size_t g = n; g-- > 0;) sop.push_back(int32_t(g)), sop.push_back(int32_t(g));  // (two pairs a segment, out of segment order)
+        pn.plane.assign(sop.size(), 0);
+        const BlocksTables b = blocks_tables(pn, sop.data(), 4);
+        EXPECT(b.seg_word == seg_word && b.word_seg == word_seg && b.T == t.T && b.P == 2 * t.T && b.block_base.size() == n + 1);
+        uint64_t at = 0;
+        for (size_t i = 0; i < sop.size(); ++i) {
+            EXPECT(b.pair_word[i] == at);
+            at += seg_word[size_t(sop[i]) + 1] - seg_word[size_t(sop[i])];
+        }
+        for (size_t g = 0; g < n; ++g) EXPECT(b.block_base[g + 1] - b.block_base[g] == (rlens[g] < 4 ? rlens[g] : 4));
+    }
+    const std::vector<int64_t> base{0, 3, 3, 4, 9};  // (a unit without slots between two with)
+    EXPECT(slot_owners(base.data(), 4) == (std::vector<int32_t>{0, 0, 0, 2, 3, 3, 3, 3, 3}));
+    EXPECT(slot_owners(base.data(), 0).empty() && slot_owners(std::vector<uint64_t>{0, 0}.data(), 1).empty());
+    const std::vector<int32_t> slot{10, 11, 12, 20, 30, 31, 32, 33, 34}, kept{2, 0, 1, 5};
+    std::vector<int32_t> out(8, -1);
+    std::vector<int64_t> off(5, -1);
+    pack_kept_slots(slot, base.data(), 4, [&](size_t u) { return kept[u]; }, out.data(), off.data());
+    EXPECT(out == (std::vector<int32_t>{10, 11, 20, 30, 31, 32, 33, 34}) && off == (std::vector<int64_t>{0, 2, 2, 3, 8}));
+    int64_t none = -1;
+    pack_kept_slots(std::vector<int32_t>{}, base.data(), 0, [](size_t) { return 0; }, static_cast<int32_t*>(nullptr), &none);
+    EXPECT(none == 0);
+}
+
 void check_bounds()
 {
     g_what = "bounds";
@@ -512,6 +557,7 @@ int main()
     check_member_lists();
     check_group_member_lists();
     check_split_tables();
+    check_slot_tables();
     check_bounds();
     check_plan_rlen();
     check_plan_pool();
