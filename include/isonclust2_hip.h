@@ -287,6 +287,16 @@ int ioc_host_align(const char* query, int32_t qlen, const char* ref, int32_t rle
 int ioc_host_align_ops(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match,
                        int32_t mismatch, int32_t gap_open, int32_t gap_extend, char* ops, int32_t ops_cap,
                        int32_t* score_out);
+/* The same aligner restricted to a corridor of tiles, with the certificate of its result: what version 2 of the GPU aligner
+ * computes under a corridor, stated on the host.  Band b holds the rows (r0, r0 + band_rows[b]] (r0: the heights before it; they
+ * add up to qlen or more), strip p the columns (p strip_cols, (p + 1) strip_cols]; tile (b, p) is computed iff plo[b] <= p <= phi[b].
+ * out[0 .. 8): restricted score, end row, end column | parent bound, start bound, exit bound (INT32_MIN: no such cell; parent
+ * bound INT32_MAX: a skipped cell on the diagonal) | tiles skipped, tiles.  The restricted alignment is the alignment whenever
+ * out[0] > min(out[3], max(out[4], out[5])).  ops (may be null, else ops_cap >= qlen + rlen + 1): the restricted alignment's
+ * operation bytes; returns their length (0 without ops). */
+int ioc_host_align_corridor(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match, int32_t mismatch,
+                            int32_t gap_open, int32_t gap_extend, const int32_t* band_rows, int32_t nbands, int32_t strip_cols,
+                            const int32_t* plo, const int32_t* phi, char* ops, int32_t ops_cap, int32_t* out);
 /* Run-length text of an operation string ("12=1X3I...", end gaps as runs of i / d), NUL-terminated; returns its length,
  * IOC_ERR_CAPACITY if cap is too small (2 bytes per operation + 1 always suffice), IOC_ERR_ARG for a byte that is no operation. */
 int64_t ioc_host_ops_to_cigar(const char* ops, int64_t len, char* out, int64_t cap);

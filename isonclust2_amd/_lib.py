@@ -241,7 +241,7 @@ SYMBOLS = [
     "ioc_extract_minimizers", "ioc_extracted_download", "ioc_extracted_hpc_download", "ioc_queries_from_extracted",
     "ioc_get_timings", "ioc_count_reference_postings", "ioc_host_gap_limits", "ioc_host_err_cell", "ioc_host_min_total",
     "ioc_cluster_batch", "ioc_cluster_merge", "ioc_cluster_resident", "ioc_host_align", "ioc_host_gap_open", "ioc_host_align_route",
-    "ioc_host_aln_ratio", "ioc_host_align_ops", "ioc_host_ops_to_cigar", "ioc_host_ops_stats", "ioc_host_ops_pileup", "ioc_host_ops_pileup_ins", "ioc_host_pileup_call", "ioc_host_qual_weight", "ioc_host_ops_pileup_weighted", "ioc_host_pileup_call_weighted", "ioc_host_ops_project", "ioc_host_pileup_sites", "ioc_host_site_alleles", "ioc_host_alleles_split", "ioc_host_ops_project_ins", "ioc_host_planes_pile", "ioc_align_set_pool", "ioc_align_pairs", "ioc_align_ops_bound",
+    "ioc_host_aln_ratio", "ioc_host_align_ops", "ioc_host_align_corridor","ioc_host_ops_to_cigar", "ioc_host_ops_stats", "ioc_host_ops_pileup", "ioc_host_ops_pileup_ins", "ioc_host_pileup_call", "ioc_host_qual_weight", "ioc_host_ops_pileup_weighted", "ioc_host_pileup_call_weighted", "ioc_host_ops_project", "ioc_host_pileup_sites", "ioc_host_site_alleles", "ioc_host_alleles_split", "ioc_host_ops_project_ins", "ioc_host_planes_pile", "ioc_align_set_pool", "ioc_align_pairs", "ioc_align_ops_bound",
     "ioc_align_pairs_ops", "ioc_align_pairs_stats", "ioc_align_pairs_pileup", "ioc_pileup_call", "ioc_align_pairs_polish", "ioc_align_set_pool_qual", "ioc_pileup_call_weighted", "ioc_align_pairs_polish_weighted", "ioc_pileup_sites", "ioc_align_pairs_alleles", "ioc_alleles_split", "ioc_align_pairs_split", "ioc_planes_polish", "ioc_align_pairs_split_polish", "ioc_set_aln_verdicts", "ioc_get_ties", "ioc_resident_set_sequences",
     "ioc_index_update", "ioc_left_export", "ioc_left_adopt", "ioc_cluster_consensus",
     "ioc_poa_create", "ioc_poa_create_mode", "ioc_poa_destroy", "ioc_poa_bind", "ioc_poa_graph_export", "ioc_poa_last_alignment",
@@ -341,6 +341,7 @@ def load():
     L.ioc_poa_graph_load_many.argtypes = [vp, C.c_int, C.c_int32, C.POINTER(C.c_int32), C.POINTER(pu8), C.POINTER(i64)]
     L.ioc_host_align.argtypes = [C.c_char_p, i32, C.c_char_p, i32, i32, i32, i32, i32, C.c_char_p, i32, pi32]
     L.ioc_host_align_ops.argtypes = [C.c_char_p, i32, C.c_char_p, i32, i32, i32, i32, i32, C.c_char_p, i32, pi32]
+    L.ioc_host_align_corridor.argtypes = [C.c_char_p, i32, C.c_char_p, i32, i32, i32, i32, i32, pi32, i32, i32, pi32, pi32, C.c_char_p, i32, pi32]
     L.ioc_host_ops_to_cigar.argtypes = [C.c_char_p, i64, C.c_char_p, i64]
     L.ioc_host_ops_to_cigar.restype = C.c_int64
     L.ioc_host_ops_stats.argtypes = [C.c_char_p, i64, C.POINTER(AlnStats)]

@@ -36,9 +36,19 @@ enum : uint8_t { H_DIAG = 0, H_FROM_E = 1, H_FROM_F = 2, H_MASK = 3, E_EXT = 4, 
 // The aligner behind ioc_host_align and ioc_host_align_ops: one DP, one walk.  `comp` receives one byte per alignment column,
 // forward order, NUL-terminated — OPS: the operation bytes ('=' 'X' 'I' 'D', free end gaps 'i' 'd'), else the comparison
 // string ('|' where the operation is '=', ' ' everywhere else).  Returns the length, or a negative ioc_status.
+// `cor` (ioc_host_align_corridor alone, null otherwise): only the cells (i, cor->jlo[i] .. cor->jhi[i]) of row i >= 1 are computed,
+// every other cell off row 0 and column 0 counts as "no score"; what comes out is the best alignment among the paths that stay
+// inside the computed cells, with the exit bound of its certificate (HostCorridor).
+struct HostCorridor {
+    std::vector<int> jlo, jhi;  // [0 .. n + 1]: the computed columns of a row (jlo > jhi: none); row n + 1 stands for "no such row"
+    bool skipped(int i, int j) const { return j < jlo[size_t(i)] || j > jhi[size_t(i)]; }
+    int64_t exit_bound = INT64_MIN;  // the largest H_C(y) + match x min(n - i, m - j) over the exit cells y = (i, j)
+    int end_i = 0, end_j = 0;
+};
+
 template <bool OPS>
 int host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match, int32_t mismatch, int32_t gap_open,
-               int32_t gap_extend, char* comp, int32_t comp_cap, int32_t* score_out)
+               int32_t gap_extend, char* comp, int32_t comp_cap, int32_t* score_out, HostCorridor* cor = nullptr)
 {
     // what a column of each kind is written as
     constexpr char C_EQ = OPS ? '=' : '|', C_X = OPS ? 'X' : ' ', C_I = OPS ? 'I' : ' ', C_D = OPS ? 'D' : ' ', C_EI = OPS ? 'i' : ' ',
@@ -59,6 +69,10 @@ int host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, i
         const char qc = query[i - 1];
         uint8_t* row = tb.data() + size_t(i) * size_t(m + 1);
         for (int j = 1; j <= m; ++j) {
+            if (cor && cor->skipped(i, j)) {
+                H[j] = F[j] = E = NEG;
+                continue;
+            }
             // E: gap in the query (horizontal move), F: gap in the reference (vertical move)
             const int e_open = H[j - 1] - gap_open, e_ext = E - gap_extend;
             uint8_t d = 0;
@@ -88,6 +102,19 @@ int host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, i
             }
             H[j] = h;
             row[j] = uint8_t(d | from);
+            if (cor) {
+                // ("no score" stays where it is: sums of it do not drift towards the scores)
+                if (E < NEG / 2) E = NEG;
+                if (F[j] < NEG / 2) F[j] = NEG;
+                if (h < NEG / 2) {
+                    H[j] = NEG;
+                    continue;
+                }
+                // an exit cell: a computed cell whose right, lower or lower-right neighbour exists and is skipped
+                const bool right = j < m && cor->skipped(i, j + 1), below = i < n && cor->skipped(i + 1, j),
+                           corner = i < n && j < m && cor->skipped(i + 1, j + 1);
+                if (right || below || corner) cor->exit_bound = std::max(cor->exit_bound, int64_t(h) + int64_t(match) * std::min(n - i, m - j));
+            }
         }
         // free trailing gap on the reference: best of the last column
         if (H[m] > best) {
@@ -107,6 +134,10 @@ int host_align(const char* query, int32_t qlen, const char* ref, int32_t rlen, i
         }
     }
     if (score_out) *score_out = best;
+    if (cor) {
+        cor->end_i = bi;
+        cor->end_j = bj;
+    }
     // traceback from (bi, bj); trailing end gaps first (they are the tail of the strings)
     std::string rev;
     rev.reserve(size_t(n + m));
@@ -166,6 +197,70 @@ int ioc_host_align_ops(const char* query, int32_t qlen, const char* ref, int32_t
                        int32_t gap_open, int32_t gap_extend, char* ops, int32_t ops_cap, int32_t* score_out)
 {
     return host_align<true>(query, qlen, ref, rlen, match, mismatch, gap_open, gap_extend, ops, ops_cap, score_out);
+}
+
+// The aligner restricted to a corridor of tiles, and the certificate of what it finds: the host's statement of what version 2 of
+// the GPU aligner computes under a corridor.  Band b holds the rows (r0, r0 + band_rows[b]] with r0 the heights
+// before it (they must add up to qlen or more), strip p the columns (p strip_cols, (p + 1) strip_cols]; tile (b, p) is computed iff
+// plo[b] <= p <= phi[b] (phi is cut to the pair's last strip).  Row 0 and column 0 always hold their zeros.
+// out[0 .. 8): restricted score, end row, end column | the parent bound match x (max(n, m) - Beff - 1) (INT32_MAX: some skipped
+// cell is on the diagonal), the start bound, the exit bound (INT32_MIN each: no such cell) | tiles skipped, tiles of the grid.
+// The restricted alignment IS the alignment whenever out[0] > min(out[3], max(out[4], out[5])).
+// `ops` (may be null): the restricted alignment's operation bytes, as ioc_host_align_ops writes them; returns their length (0
+// without `ops`) or a negative ioc_status.
+int ioc_host_align_corridor(const char* query, int32_t qlen, const char* ref, int32_t rlen, int32_t match, int32_t mismatch, int32_t gap_open,
+                            int32_t gap_extend, const int32_t* band_rows, int32_t nbands, int32_t strip_cols, const int32_t* plo, const int32_t* phi,
+                            char* ops, int32_t ops_cap, int32_t* out)
+{
+    if (!query || !ref || !band_rows || !plo || !phi || !out || qlen < 1 || rlen < 1 || nbands < 1 || strip_cols < 1 || match < 0) return IOC_ERR_ARG;
+    const int n = qlen, m = rlen, W = strip_cols, nstrips = (m + W - 1) / W;
+    HostCorridor cor;
+    cor.jlo.assign(size_t(n) + 2, 1);
+    cor.jhi.assign(size_t(n) + 2, 0);
+    int64_t beff = INT64_MAX, tiles = 0, skipped = 0;
+    int64_t start = INT64_MIN;
+    int r0 = 0;
+    for (int b = 0; b < nbands && r0 < n; ++b) {
+        if (band_rows[b] < 1 || plo[b] < 0) return IOC_ERR_ARG;
+        const int r1 = int(std::min<int64_t>(n, int64_t(r0) + band_rows[b])), lo = plo[b], hi = std::min(phi[b], nstrips - 1);
+        if (lo > hi) return IOC_ERR_ARG;
+        for (int i = r0 + 1; i <= r1; ++i) {
+            cor.jlo[size_t(i)] = lo * W + 1;
+            cor.jhi[size_t(i)] = int(std::min<int64_t>(m, (int64_t(hi) + 1) * W));
+        }
+        tiles += nstrips;
+        skipped += lo + (nstrips - 1 - hi);
+        // (the least |row - column| of a skipped cell, short by one on either side: plan_corridor's)
+        if (lo > 0) beff = std::min<int64_t>(beff, int64_t(r0) - int64_t(lo) * W);
+        if ((int64_t(hi) + 1) * W < m) beff = std::min<int64_t>(beff, (int64_t(hi) + 1) * W - r1);
+        r0 = r1;
+    }
+    if (r0 < n) return IOC_ERR_ARG;
+    // the start bound: a path whose first cell off row 0 and column 0 is skipped leaves (0, j) or (i, 0) by a step down or right
+    // or diagonally, and has min(n, m - j) or min(n - i, m) diagonal steps at most
+    for (int j = 0; j < m; ++j)
+        if (cor.skipped(1, j + 1) || (j >= 1 && cor.skipped(1, j))) start = std::max(start, int64_t(match) * std::min(n, m - j));
+    for (int i = 0; i < n; ++i)
+        if (cor.skipped(i + 1, 1) || (i >= 1 && cor.skipped(i, 1))) start = std::max(start, int64_t(match) * std::min(n - i, m));
+    int32_t score = 0;
+    std::vector<char> own;
+    if (!ops) {
+        own.resize(size_t(n) + size_t(m) + 1);
+        ops = own.data();
+        ops_cap = int32_t(own.size());
+    }
+    const int len = host_align<true>(query, qlen, ref, rlen, match, mismatch, gap_open, gap_extend, ops, ops_cap, &score, &cor);
+    if (len < 0) return len;
+    auto i32 = [](int64_t v) { return int32_t(std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, v))); };
+    out[0] = score;
+    out[1] = cor.end_i;
+    out[2] = cor.end_j;
+    out[3] = beff == INT64_MAX ? INT32_MIN : beff <= 0 ? INT32_MAX : i32(int64_t(match) * std::max<int64_t>(0, int64_t(std::max(n, m)) - beff - 1));
+    out[4] = i32(start);
+    out[5] = i32(cor.exit_bound);
+    out[6] = i32(skipped);
+    out[7] = i32(tiles);
+    return own.empty() ? len : 0;
 }
 
 // Run-length text of an operation string ("12=1X3I", end gaps as runs of 'i' / 'd'), NUL-terminated.  Returns its length,

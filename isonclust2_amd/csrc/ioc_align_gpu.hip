@@ -1345,11 +1345,17 @@ struct CorridorModel {
     double frac;  // the fraction without a model (0: no corridor)
     bool fixed;   // (IOC_ALIGN_CORRIDOR: one fraction for every couple, as in round 4)
     bool fit_ok;  // ioc_ctx::aln_fit belongs to these scores
-    double pair_frac(const AlnPairDev& d) const
+    bool taper;   // the model's corridor narrows down the grid (IOC_ALIGN_CORRIDOR_TAPER=0: one width, the certificate of round 4)
+    uint32_t taper_margin;  // columns on top of the taper's least passing width (IOC_ALIGN_CORRIDOR_MARGIN)
+    // ... and the score per base it was derived from (rho_lo; 0: no model behind the fraction)
+    struct Width {
+        double frac, rho;
+    };
+    Width pair_width(const AlnPairDev& d) const
     {
-        if (fixed || !(P.match > 0)) return frac;
+        if (fixed || !(P.match > 0)) return {frac, 0.0};
         const double e = double(d.e_sum);
-        if (!(e > 0.0) || !(e < 1.0)) return frac;
+        if (!(e > 0.0) || !(e < 1.0)) return {frac, 0.0};
         const int go = std::max(2, std::min(5, d.gap_open));
         double rho = double(P.match) - e * (double(P.match - P.mismatch) / 3.0 + 2.0 / 3.0 * double(go + P.match)), margin = 0.02;
         const ioc_ctx::CorridorFit& f = c->aln_fit[go - 2];
@@ -1360,17 +1366,20 @@ struct CorridorModel {
             rho = mr + slope * (e - me) - 4.5 * std::max(sd, 0.004);
             margin = 0.003;
         }
-        return std::max(0.03, std::min(0.45, 1.0 - rho / double(P.match) + margin));
+        return {std::max(0.03, std::min(0.45, 1.0 - rho / double(P.match) + margin)), rho};
     }
+    double pair_frac(const AlnPairDev& d) const { return pair_width(d).frac; }
 };
 
 CorridorModel corridor_model(const ioc_ctx* c, const AlnParams& P, bool corridor)
 {
-    CorridorModel m{c, P, corridor ? 0.2 : 0.0, false, false};
+    CorridorModel m{c, P, corridor ? 0.2 : 0.0, false, false, true, 256u};
     if (const char* e = getenv("IOC_ALIGN_CORRIDOR")) {
         m.frac = corridor ? std::max(0.0, std::min(1.0, atof(e))) : 0.0;
         m.fixed = true;
     }
+    if (const char* e = getenv("IOC_ALIGN_CORRIDOR_TAPER")) m.taper = atoi(e) != 0;
+    if (const char* e = getenv("IOC_ALIGN_CORRIDOR_MARGIN")) m.taper_margin = uint32_t(std::max(0, std::min(1 << 20, atoi(e))));
     m.fit_ok = c->aln_fit_sig[0] == P.match && c->aln_fit_sig[1] == P.mismatch && c->aln_fit_sig[2] == P.gap_extend && !getenv("IOC_ALIGN_CORRIDOR_NO_FIT");
     return m;
 }
@@ -1437,8 +1446,9 @@ void plan_bands(V2Couple& cp, uint32_t ncoarse, uint32_t want_bands, bool corrid
 }
 
 // The corridor (V2Couple): tiles that meet |row - column| <= B, if that leaves out a fifth of the grid or more, and the probe.
-// Returns the tiles the corridor skips; cert[h]: the score pair h has to beat (V2PairEnd::cert).
-uint32_t plan_corridor(V2Couple& cp, const std::vector<AlnPairDev>& dp, const CorridorModel& cm, uint32_t nmax, uint32_t mmax, int32_t cert[2])
+// Returns the tiles the corridor skips; cert[h], start[h]: the parent bound and the start bound of pair h (V2PairEnd).
+uint32_t plan_corridor(V2Couple& cp, const std::vector<AlnPairDev>& dp, const CorridorModel& cm, uint32_t nmax, uint32_t mmax, int32_t cert[2],
+                       int32_t start[2])
 {
     const AlnParams& P = cm.P;
     constexpr uint32_t probe_rows = 1024;
@@ -1448,9 +1458,13 @@ uint32_t plan_corridor(V2Couple& cp, const std::vector<AlnPairDev>& dp, const Co
         cp.phi[b] = uint16_t(std::min<uint32_t>(65535u, cp.nstrips - 1u));  // (V2Item::strip is 16 bits wide)
     }
     const uint32_t strip_cols = 64u * FW_C;
-    double frac = 0.0;
+    double frac = 0.0, rho = double(P.match);
     for (int h = 0; h < 2; ++h)
-        if (cp.pid[h] != 0xFFFFFFFFu) frac = std::max(frac, cm.pair_frac(dp[cp.pid[h]]));
+        if (cp.pid[h] != 0xFFFFFFFFu) {  // (the wider plan of the two pairs)
+            const CorridorModel::Width w = cm.pair_width(dp[cp.pid[h]]);
+            frac = std::max(frac, w.frac);
+            rho = std::min(rho, w.rho);
+        }
     if (cm.frac <= 0.0) frac = 0.0;
     const uint32_t B = uint32_t(frac * double(std::max(nmax, mmax)));
     cp.b0 = B;
@@ -1458,38 +1472,64 @@ uint32_t plan_corridor(V2Couple& cp, const std::vector<AlnPairDev>& dp, const Co
     uint32_t skipped = 0;
     uint16_t lo[V2_MAX_BANDS], hi[V2_MAX_BANDS];
     // (the bound behind the certificate: a column of an alignment scores `match` at most — no reward for mismatches or gaps)
-    bool fits = cm.frac > 0.0 && B >= strip_cols && cp.nstrips <= 65535u && cp.nbands <= uint32_t(V2_MAX_BANDS) && P.match > 0 && P.mismatch <= P.match &&
-                P.gap_extend >= 0;
+    const bool can = cm.frac > 0.0 && B >= strip_cols && cp.nstrips <= 65535u && cp.nbands <= uint32_t(V2_MAX_BANDS) && P.match > 0 && P.mismatch <= P.match &&
+                     P.gap_extend >= 0;
+    bool fits = can;
     for (int h = 0; fits && h < 2; ++h)
         if (cp.pid[h] != 0xFFFFFFFFu) fits = dp[cp.pid[h]].gap_open >= 0;
-    for (uint32_t b = 0; fits && b < cp.nbands; ++b) {
-        const uint32_t r0 = uint32_t(cp.bstart[b]) * uint32_t(CK2), r1 = std::min(nmax, uint32_t(cp.bstart[b + 1u]) * uint32_t(CK2));
-        const uint32_t c_lo = r0 > B ? r0 - B : 0u, c_hi = std::min<uint64_t>(mmax, uint64_t(r1) + B);
-        if (c_hi <= c_lo) {  // (a band wholly below the last column's corridor: rows the longer query has alone)
-            fits = false;
-            break;
-        }
-        lo[b] = uint16_t(c_lo / strip_cols);
-        hi[b] = uint16_t((c_hi - 1u) / strip_cols);
-        skipped += lo[b] + (cp.nstrips - 1u - hi[b]);
-        if (lo[b] > 0) beff = std::min<int64_t>(beff, int64_t(r0) - int64_t(lo[b]) * strip_cols);
-        if ((uint64_t(hi[b]) + 1u) * strip_cols < mmax) beff = std::min<int64_t>(beff, int64_t(hi[b] + 1u) * strip_cols - int64_t(r1));
-    }
-    // the probe (V2Couple): the first band that ends at row 2048 or below, the strip its last diagonal cell is in; every tile
-    // above and to the left of it must be inside the corridor with nothing missing around it, both pairs must reach it
+    // THE TAPER (model-planned corridors): a path that enters a skipped cell from a computed one is bound by the score the pass
+    // stored at that exit cell (k_fwd2_cert), so the width only has to keep the exit cells' scores low enough — a cell d columns off
+    // the diagonal at row i holds about rho i - go - ge d, and passes if d > (match - rho)(n - i) / (match + ge) to the right,
+    // (match - rho)(n - i) / (rho + ge) to the left.  The top keeps today's width: there the start bound applies.
+    const double g_right = rho > 0.0 ? std::max(0.0, double(P.match) - rho) / double(P.match + P.gap_extend) : 0.0;
+    const double g_left = rho > 0.0 ? std::max(0.0, double(P.match) - rho) / (rho + double(P.gap_extend)) : 0.0;
     uint32_t pb = 0, ps = 0;
-    if (fits) {
+    auto geometry = [&](bool taper) {
+        bool ok = true;
+        beff = INT64_MAX;
+        skipped = 0;
+        for (uint32_t b = 0; ok && b < cp.nbands; ++b) {
+            const uint32_t r0 = uint32_t(cp.bstart[b]) * uint32_t(CK2), r1 = std::min(nmax, uint32_t(cp.bstart[b + 1u]) * uint32_t(CK2));
+            uint64_t d_left = B, d_right = B;
+            if (taper) {
+                const double left = nmax > r0 ? double(nmax - r0) : 0.0, top = B > r0 ? double(B - r0) : 0.0;
+                d_left = uint64_t(std::max(top, g_left * left)) + cm.taper_margin;
+                d_right = uint64_t(std::max(top, g_right * left)) + cm.taper_margin;
+            }
+            const uint32_t c_lo = r0 > d_left ? uint32_t(r0 - d_left) : 0u, c_hi = uint32_t(std::min<uint64_t>(mmax, uint64_t(r1) + d_right));
+            if (c_hi <= c_lo) return false;  // (a band wholly below the last column's corridor: rows the longer query has alone)
+            lo[b] = uint16_t(c_lo / strip_cols);
+            hi[b] = uint16_t((c_hi - 1u) / strip_cols);
+            skipped += lo[b] + (cp.nstrips - 1u - hi[b]);
+            if (lo[b] > 0) beff = std::min<int64_t>(beff, int64_t(r0) - int64_t(lo[b]) * strip_cols);
+            if ((uint64_t(hi[b]) + 1u) * strip_cols < mmax) beff = std::min<int64_t>(beff, int64_t(hi[b] + 1u) * strip_cols - int64_t(r1));
+            // what v2_fwd_body relies on — of a computed tile off the border at most one of the tile above and the tile to its
+            // left is missing — follows from: plo and phi never fall down the bands, and every band holds the strips of its own
+            // diagonal cells (r0, r0) .. (r1, r1).  (One width for every band meets this by construction.)
+            if (taper) {
+                const uint32_t s0 = (r0 ? r0 - 1u : 0u) / strip_cols, s1 = std::min((r1 - 1u) / strip_cols, cp.nstrips - 1u);
+                ok = lo[b] <= s0 && hi[b] >= s1 && (b == 0 || (lo[b] >= lo[b - 1u] && hi[b] >= hi[b - 1u]));
+            }
+        }
+        if (!ok) return false;
+        // the probe (V2Couple): the first band that ends at row 2048 or below, the strip its last diagonal cell is in; every tile
+        // above and to the left of it must be inside the corridor with nothing missing around it, both pairs must reach it
+        pb = 0;
         while (pb + 1u < cp.nbands && uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2) < probe_rows) ++pb;  // (3072 rows: a probe launch of 4.2 ms; 2048: 2.3)
         const uint32_t R = uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2);
         ps = (R - 1u) / strip_cols;
-        fits = pb + 1u < cp.nbands && R >= probe_rows;
-        for (uint32_t b = 0; fits && b <= pb; ++b) fits = lo[b] == 0 && hi[b] >= ps;
-        for (int h = 0; fits && h < 2; ++h)
-            if (cp.pid[h] != 0xFFFFFFFFu) fits = dp[cp.pid[h]].n >= R && dp[cp.pid[h]].m > ps * strip_cols;
-    }
-    cp.probe_band = uint16_t(pb);
-    cp.probe_strip = uint16_t(ps);
-    if (fits && skipped * 5u >= cp.nbands * cp.nstrips && beff > 0 && beff < INT64_MAX) {
+        ok = pb + 1u < cp.nbands && R >= probe_rows;
+        for (uint32_t b = 0; ok && b <= pb; ++b) ok = lo[b] == 0 && hi[b] >= ps;
+        for (int h = 0; ok && h < 2; ++h)
+            if (cp.pid[h] != 0xFFFFFFFFu) ok = dp[cp.pid[h]].n >= R && dp[cp.pid[h]].m > ps * strip_cols;
+        return ok && skipped * 5u >= cp.nbands * cp.nstrips && beff > 0 && beff < INT64_MAX;
+    };
+    // (a couple whose taper breaks a rule gets the one width of round 4, and its certificate)
+    bool tapered = fits && cm.taper && !cm.fixed && rho > 0.0 && rho < double(P.match) && geometry(true);
+    fits = tapered || (fits && geometry(false));
+    cp.probe_band = uint16_t(fits ? pb : 0u);
+    cp.probe_strip = uint16_t(fits ? ps : 0u);
+    if (fits) {
         cp.corridor = 1;
         for (uint32_t b = 0; b < cp.nbands; ++b) {
             cp.plo[b] = lo[b];
@@ -1498,10 +1538,12 @@ uint32_t plan_corridor(V2Couple& cp, const std::vector<AlnPairDev>& dp, const Co
     }
     for (int h = 0; h < 2; ++h) {
         cert[h] = INT32_MIN;
+        start[h] = INT32_MAX;  // (no exit-cell certificate: the parent bound alone, k_fwd2_ends)
         if (cp.pid[h] == 0xFFFFFFFFu || !cp.corridor) continue;
         const AlnPairDev& d = dp[cp.pid[h]];
         // (a path through a skipped cell has at most max(n, m) - Beff - 1 diagonal steps, each worth `match` at most)
         cert[h] = int32_t(std::min<int64_t>(INT32_MAX, int64_t(P.match) * std::max<int64_t>(0, int64_t(std::max(d.n, d.m)) - beff - 1)));
+        if (tapered) start[h] = v2_start_bound(cp, d.n, d.m, P.match);
     }
     return cp.corridor ? skipped : 0u;
 }
@@ -1545,8 +1587,8 @@ void plan_couples(V2Plan& pl, const std::vector<AlnPairDev>& dp, const uint32_t*
             }
         cp.nstrips = (mmax + 64u * FW_C - 1) / (64u * FW_C);
         plan_bands(cp, (nmax + CK2 - 1) / CK2, want_bands, cm.frac > 0.0);
-        int32_t cert[2];
-        pl.tiles_skipped += plan_corridor(cp, dp, cm, nmax, mmax, cert);
+        int32_t cert[2], start[2];
+        pl.tiles_skipped += plan_corridor(cp, dp, cm, nmax, mmax, cert, start);
         pl.tiles_all += uint64_t(cp.nbands) * cp.nstrips;
         pl.cwords[k2] = couple_words(cp, nmax, mmax);
         cp.prof = 0;  // (uint4 entries; placed per slice: the profiles of a slice's couples count against the budget with its checkpoints)
@@ -1557,7 +1599,7 @@ void plan_couples(V2Plan& pl, const std::vector<AlnPairDev>& dp, const uint32_t*
             if (cp.pid[h] == 0xFFFFFFFFu) continue;
             const AlnPairDev& d = dp[cp.pid[h]];
             const uint32_t nstr = (d.m + 64u * FW_C - 1) / (64u * FW_C);
-            pl.pend[cp.pid[h]] = V2PairEnd{pl.lrow_total, pl.best_total, cp.nbands, k2, cert[h]};
+            pl.pend[cp.pid[h]] = V2PairEnd{pl.lrow_total, pl.best_total, cp.nbands, k2, cert[h], start[h], INT32_MIN};
             pl.lrow_total += nstr * 64u;
             pl.best_total += cp.nbands;
         }
@@ -1896,6 +1938,15 @@ int v2_slice(ioc_ctx* c, const V2Plan& pl, const V2Dev& t, size_t si, const V2Op
                 few_couples ? "rows" : "tiles", per_cu, n_wg, w2 ? "k_fwd2_w2" : "k_fwd2", n_probe);
     fwd(w2 ? k_fwd2_w2 : k_fwd2, n_wg, t.items + n_probe, n_main, 1u);
     IOC_CHK(c, hipGetLastError());
+    bool tapered = false;  // (some pair of the slice is vouched for by its exit cells: V2PairEnd)
+    for (uint32_t k2 = k_first; k2 < k_first + n_couples && !tapered; ++k2)
+        for (int h = 0; h < 2; ++h)
+            if (pl.cps[k2].pid[h] != 0xFFFFFFFFu && pl.pend[pl.cps[k2].pid[h]].start != INT32_MAX) tapered = true;
+    if (tapered) {
+        hipLaunchKernelGGL(k_fwd2_cert, dim3(n_pairs, V2_CERT_Y), dim3(V2_CERT_T), 0, s, d_pairs, t.cps, d_order + first_pair, n_pairs, t.pend,
+                           static_cast<const uint32_t*>(c->a_ck.p), P);
+        IOC_CHK(c, hipGetLastError());
+    }
     const uint32_t n_help = std::min<uint32_t>(n_pairs, o.help_wgs);
     hipLaunchKernelGGL(k_fwd2_ends, dim3(n_pairs), dim3(64), 0, s, d_pairs, t.cps, d_order + first_pair, n_pairs, t.pend, t.lrow, t.best,
                        d_ctl + 16 + 2 * pl.max_flags, static_cast<int4*>(c->a_ends2.p), t.resume, t.early, o.side_help ? int(P.match) : 0, n_help);
@@ -2053,6 +2104,77 @@ int v2_report(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* ord
     return IOC_OK;
 }
 
+// IOC_V2_CERT_CHECK (developer switch): after a slice, every pair of up to 12 kb that kept its corridor once more on the host
+// (ioc_host_align_corridor, with the corridor as the probe left it): the restricted score and end cell and the bounds of the
+// certificate must be the device's; the call fails at the first pair that differs.  The parent bound is planned per couple — with the
+// larger pair's rows and columns — so a shorter pair's may exceed the host's.
+int v2_cert_check(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* order, const V2Plan& pl, const V2Dev& t, size_t si, const AlnParams& P)
+{
+    const uint32_t k_first = pl.slices[si].first, n_couples = pl.slices[si].second, first_pair = 2u * k_first;
+    const uint32_t n_pairs = std::min(pl.cnt, 2u * (k_first + n_couples)) - first_pair;
+    std::vector<V2Couple> cps(n_couples);
+    std::vector<V2PairEnd> pe(pl.np);
+    std::vector<int4> he(pl.np);
+    IOC_CHK(c, hipMemcpy(cps.data(), t.cps + k_first, size_t(n_couples) * sizeof(V2Couple), hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(pe.data(), t.pend, size_t(pl.np) * sizeof(V2PairEnd), hipMemcpyDeviceToHost));
+    IOC_CHK(c, hipMemcpy(he.data(), c->a_ends2.p, size_t(pl.np) * sizeof(int4), hipMemcpyDeviceToHost));
+    uint32_t checked = 0, tapered = 0, refuted = 0;
+    std::vector<char> q, r;
+    for (uint32_t x = 0; x < n_pairs; ++x) {
+        const uint32_t pid = order[first_pair + x];
+        const AlnPairDev& d = dp[pid];
+        const V2PairEnd& e = pe[pid];
+        const V2Couple& cp = cps[e.couple - k_first];
+        if (!cp.corridor || e.cert == INT32_MIN || std::max(d.n, d.m) > 12288u || d.n == 0 || d.m == 0 || (he[pid].w & 1)) continue;
+        q.resize(d.n);
+        r.resize(d.m);
+        IOC_CHK(c, hipMemcpy(q.data(), static_cast<const uint8_t*>(c->a_pool.p) + d.q_off, d.n, hipMemcpyDeviceToHost));
+        IOC_CHK(c, hipMemcpy(r.data(), static_cast<const uint8_t*>(c->a_pool.p) + d.r_off, d.m, hipMemcpyDeviceToHost));
+        auto acgt = [](char ch) { return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; };
+        if (d.rc) {
+            std::reverse(r.begin(), r.end());
+            for (char& ch : r) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
+        }
+        for (char& ch : q)  // (the kernels' rule: a letter other than A, C, G, T equals nothing)
+            if (!acgt(ch)) ch = 1;
+        for (char& ch : r)
+            if (!acgt(ch)) ch = 2;
+        int32_t rows[V2_MAX_BANDS], lo[V2_MAX_BANDS], hi[V2_MAX_BANDS], out[8];
+        uint32_t nmax = 0, mmax = 0;
+        for (int h = 0; h < 2; ++h)
+            if (cp.pid[h] != 0xFFFFFFFFu) {
+                nmax = std::max(nmax, dp[cp.pid[h]].n);
+                mmax = std::max(mmax, dp[cp.pid[h]].m);
+            }
+        for (uint32_t b = 0; b < cp.nbands; ++b) {
+            rows[b] = int32_t(uint32_t(cp.bstart[b + 1u]) - uint32_t(cp.bstart[b])) * CK2;
+            lo[b] = cp.plo[b];
+            hi[b] = cp.phi[b];
+        }
+        const int hr = ioc_host_align_corridor(q.data(), int32_t(d.n), r.data(), int32_t(d.m), P.match, P.mismatch, d.gap_open, P.gap_extend, rows,
+                                               int32_t(cp.nbands), 64 * FW_C, lo, hi, nullptr, 0, out);
+        const bool own = e.start != INT32_MAX, largest = d.n == nmax && d.m == mmax;
+        const int32_t cert = own ? std::min(e.cert, std::max(e.start, e.exit)) : e.cert;
+        const bool same = hr >= 0 && out[0] == he[pid].x && out[1] == he[pid].y && out[2] == he[pid].z && (largest ? e.cert == out[3] : e.cert >= out[3]) &&
+                          (!own || (e.start == out[4] && e.exit == out[5])) && ((he[pid].w & 2) != 0) == (he[pid].x <= cert);
+        if (!same)
+            return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_CERT_CHECK: slice " + std::to_string(si) + ": pair " + std::to_string(pid) + " (n " + std::to_string(d.n) +
+                                                  ", m " + std::to_string(d.m) + ", half " + std::to_string(cp.pid[0] == pid ? 0 : 1) + "): the device has score " +
+                                                  std::to_string(he[pid].x) + " at (" + std::to_string(he[pid].y) + ", " + std::to_string(he[pid].z) + "), flags " +
+                                                  std::to_string(he[pid].w) + ", bounds " + std::to_string(e.cert) + " / " + std::to_string(e.start) + " / " +
+                                                  std::to_string(e.exit) + "; the host (" + std::to_string(hr) + ") score " + std::to_string(out[0]) + " at (" +
+                                                  std::to_string(out[1]) + ", " + std::to_string(out[2]) + "), bounds " + std::to_string(out[3]) + " / " +
+                                                  std::to_string(out[4]) + " / " + std::to_string(out[5]));
+        ++checked;
+        tapered += own ? 1u : 0u;
+        refuted += (he[pid].w & 2) ? 1u : 0u;
+    }
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner v2: IOC_V2_CERT_CHECK: slice %zu: %u pairs equal the host's (%u with a tapered corridor, %u refuted)\n", si, checked,
+                tapered, refuted);
+    return IOC_OK;
+}
+
 // Version 2: the pairs order[0 .. cnt) (all of the query-profile kind, heaviest first) through k_fwd2 / k_fwd2_ends / k_trace2, with
 // the corridor (`corridor` false: every tile).  Returns IOC_OK with *fell_back = true when a bounded wait of the forward pass ran
 // out (the caller then runs the same pairs through version 1).
@@ -2153,6 +2275,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
             if ((r = ops_fetch(c, *ops, dp, order + x0, d_order + x0, x1 - x0, slice_ops[si])) != IOC_OK) return r;
         }
         if ((r = v2_report(c, dp, order, pl, t, si, o.deadline)) != IOC_OK) return r;
+        if (!xe && pl.tiles_skipped && getenv("IOC_V2_CERT_CHECK") && (r = v2_cert_check(c, dp, order, pl, t, si, P)) != IOC_OK) return r;
         bad = xe != 0;
     }
     add_elapsed(c, evs.v, evi);

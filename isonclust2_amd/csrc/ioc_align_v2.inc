@@ -983,7 +983,35 @@ __global__ void __launch_bounds__(64 * V2_WAVES) __attribute__((amdgpu_waves_per
 struct V2PairEnd {
     uint32_t lrow0, best0, nbands, couple;
     int32_t cert;  // corridor: the score the pair has to BEAT for the corridor's result to stand (INT32_MIN: no corridor)
+    // A TAPERED corridor (plan_corridor) is vouched for by the exit cells' scores instead: `cert` is then the parent bound, and
+    // the pair has to beat min(cert, max(start, exit)).  A path through a skipped cell either has its first cell off row 0 and
+    // column 0 skipped — `start`: match x the diagonal steps left from the first such cell of row 0 and of column 0
+    // (v2_start_bound; INT32_MAX: one width for every band, `cert` alone decides) — or steps into its first skipped cell from a
+    // computed cell y, its prefix inside the computed tiles: it scores H_C(y) + match x min(n - i_y, m - j_y) at most, H_C being
+    // what the pass has just stored at y.  `exit`: the largest of these over the pair's exit cells (k_fwd2_cert; INT32_MIN: none).
+    int32_t start, exit;
 };
+
+// the start bound of a pair (n rows, m columns) in its couple's corridor, whose band 0 starts at strip 0: row 0 is left for a skipped
+// tile from column (phi[0] + 1) strips on, column 0 from the first row of the first band with plo > 0 on
+__host__ __device__ inline int32_t v2_start_bound(const V2Couple& cp, uint32_t n, uint32_t m, int32_t match)
+{
+    const unsigned long long strip_cols = 64ull * FW_C, j0 = (uint32_t(cp.phi[0]) + 1ull) * strip_cols;
+    long long steps = -1;
+    if (j0 < m) steps = (long long)(n < m - j0 ? n : m - j0);
+    for (uint32_t b = 0; b < cp.nbands; ++b)
+        if (cp.plo[b] > 0) {
+            const unsigned long long r0 = (unsigned long long)cp.bstart[b] * uint32_t(CK2);
+            if (r0 < n) {
+                const long long down = (long long)(n - r0 < m ? n - r0 : m);
+                steps = steps > down ? steps : down;
+            }
+            break;
+        }
+    if (steps < 0) return INT32_MIN;
+    const long long v = steps * (long long)match;
+    return v > 0x7FFFFFFFll ? 0x7FFFFFFF : int32_t(v);
+}
 // per pair: i, j, state, window bits, pushed, count, flag (0 done / not parked, 1 parked by the first traceback launch, 2 sent to the
 // helper launch before any traceback: see k_fwd2_ends), - | the two launches' walk records (IOC_V2_TRACE_TIMES)
 constexpr uint32_t V2_RESUME_WORDS = 16;
@@ -1061,6 +1089,8 @@ k_fwd2_probe(const AlnPairDev* __restrict__ pairs, V2Couple* __restrict__ couple
                     const AlnPairDev pr = pairs[cp.pid[h]];
                     const long long ct = (long long)P.match * max(0ll, (long long)max(pr.n, pr.m) - beff - 1ll);
                     pe[cp.pid[h]].cert = beff == 0x7FFFFFFFFFFFll ? INT32_MIN : int32_t(min(ct, 0x7FFFFFFFll));
+                    // (a tapered plan: the one width `need` joined with it, the start bound of the grid as it is now)
+                    if (pe[cp.pid[h]].start != INT32_MAX) pe[cp.pid[h]].start = v2_start_bound(cp, pr.n, pr.m, P.match);
                 }
             if (skipped * 5u < cp.nbands * cp.nstrips) cp.corridor = 2u;  // (not worth it: open the grid below)
         }
@@ -1076,6 +1106,70 @@ k_fwd2_probe(const AlnPairDev* __restrict__ pairs, V2Couple* __restrict__ couple
         for (int h = 0; h < 2; ++h)
             if (cp.pid[h] != 0xFFFFFFFFu) pe[cp.pid[h]].cert = INT32_MIN;
     }
+}
+
+// The exit bound of every pair with a tapered corridor (V2PairEnd::exit), after the main launch: the pair's exit cells are the
+// computed cells with a right, lower or lower-right neighbour that exists in the pair's own matrix and is skipped —
+//   * the right edge of tile (b, phi[b]) where the pair has columns beyond it: the coarse column the tile wrote;
+//   * the bottom row of a tile (b, p) whose tile (b + 1, p) is skipped, where the pair has rows below it: the band's coarse row —
+// about n + m words per pair, read out of the arena as k_fwd2_probe reads them (true H = half + base + gd - ge (i + j); the zero
+// half is "no score").  With plo and phi as the probe left them: no checkpoint of a skipped tile is read — the arena holds an
+// earlier call's words there.  Plain loads, one maximum per wave at the end; blockIdx.y takes every gridDim.y-th band.
+constexpr int V2_CERT_T = 256, V2_CERT_Y = 8;
+__global__ void __launch_bounds__(V2_CERT_T)
+k_fwd2_cert(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ couples, const uint32_t* __restrict__ order, uint32_t count, V2PairEnd* __restrict__ pe,
+            const uint32_t* __restrict__ arena, AlnParams P)
+{
+    const uint32_t pslot = blockIdx.x;
+    if (pslot >= count) return;
+    const uint32_t pid = order[pslot];
+    const V2PairEnd e = pe[pid];
+    if (e.cert == INT32_MIN || e.start == INT32_MAX) return;  // (no corridor, or the parent bound alone)
+    const V2Couple& cp = couples[e.couple];
+    if (!cp.corridor) return;
+    const AlnPairDev pr = pairs[pid];
+    const int h = cp.pid[0] == pid ? 0 : 1;
+    const uint32_t n = pr.n, m = pr.m, strip_cols = 64u * FW_C;
+    const long long ge = P.gap_extend, gd = pr.gap_open - P.gap_extend, match = P.match;
+    const uint32_t* cdat = arena + cp.cdat;
+    const int2* cbase = reinterpret_cast<const int2*>(arena + cp.cbase);
+    long long best = INT32_MIN;
+    for (uint32_t b = blockIdx.y; b < cp.nbands; b += gridDim.y) {
+        const uint32_t r0 = uint32_t(cp.bstart[b]) * uint32_t(CK2), R = uint32_t(cp.bstart[b + 1u]) * uint32_t(CK2);
+        if (r0 >= n) break;
+        const uint32_t r1 = min(n, R), lo = cp.plo[b], hi = cp.phi[b];
+        const unsigned long long j = (hi + 1ull) * strip_cols;  // the right edge's column
+        if (j < m) {
+            const unsigned long long cc = j / uint32_t(CK2) - 1u;
+            for (uint32_t row = r0 + threadIdx.x; row < r1; row += V2_CERT_T) {
+                const unsigned long long en = cc * cp.nq + row / 4u;
+                const int half = v2_half(cdat[en * 8u + (row & 3u)], h);
+                if (half == 0) continue;
+                const int2 bb = cbase[en];
+                const long long i = row + 1u, H = half + (long long)(h ? bb.y : bb.x) + gd - ge * (i + (long long)j);
+                best = max(best, H + match * min((long long)n - i, (long long)m - (long long)j));
+            }
+        }
+        if (b + 1u < cp.nbands && R < n) {
+            const uint32_t ckr = R / uint32_t(CK2) - 1u, lo2 = cp.plo[b + 1u], hi2 = cp.phi[b + 1u];
+            const uint32_t* rh = arena + cp.rdat + uint64_t(2u * ckr) * cp.mpad;
+            const int2* rb = reinterpret_cast<const int2*>(arena + cp.rbase) + uint64_t(ckr) * (cp.mpad / 16u);
+            for (uint32_t p = lo; p <= hi; ++p) {
+                if (p >= lo2 && p <= hi2) continue;
+                const uint32_t x1 = uint32_t(min((unsigned long long)m, (p + 1ull) * strip_cols));
+                for (uint32_t x = p * strip_cols + threadIdx.x; x < x1; x += V2_CERT_T) {
+                    const int half = v2_half(rh[x], h);
+                    if (half == 0) continue;
+                    const int2 bb = rb[x / 16u];
+                    const long long jj = x + 1u, H = half + (long long)(h ? bb.y : bb.x) + gd - ge * ((long long)R + jj);
+                    best = max(best, H + match * min((long long)n - (long long)R, (long long)m - jj));
+                }
+            }
+        }
+    }
+    int v = int(min(best, 0x7FFFFFFFll));
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    if ((threadIdx.x & 63u) == 0 && v != INT32_MIN) atomicMax(&pe[pid].exit, v);
 }
 
 __global__ void __launch_bounds__(64)
@@ -1125,7 +1219,9 @@ k_fwd2_ends(const AlnPairDev* __restrict__ pairs, const V2Couple* __restrict__ c
             bjj = bj;
         }
         // (corridor: the result stands only if it beats what a path through a skipped cell can reach — else flag 2: run again without)
-        const bool refuted = e.cert != INT32_MIN && fin <= e.cert;
+        // (a tapered corridor: ... or the larger of the start bound and the exit cells' bound, if that is less — V2PairEnd)
+        const int cert = e.start == INT32_MAX ? e.cert : min(e.cert, max(e.start, e.exit));
+        const bool refuted = e.cert != INT32_MIN && fin <= cert;
         ends[pid] = int4{fin, int(bi), int(bjj), int(ovf[pid] & 1u) | (refuted ? 2 : 0)};
         // Verdict mode: a WRONG candidate (10 % of a sahlin batch's pairs) aligns with a score of ~0.02 per base where a pair of one
         // transcript has ~1.7 (IOC_V2_TRACE_TIMES prints both), its walk wanders through four times the blocks, and it is decided
