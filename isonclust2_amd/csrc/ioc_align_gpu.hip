@@ -21,6 +21,9 @@
 // consecutive columns of a strip of NT * C columns and walks down the rows skewed by g (systolic wavefront):
 // at step s it computes row s - g.  Its right-edge (H, E) and the query base move to thread g + 1 by one DPP
 // wave shift (through LDS between waves, one barrier per step).
+//
+// This file: the kernels, the launches and whatever needs the context.  What a call decides on the host before it launches — bands,
+// corridors, couples, slices, tile counts, version 1's waves and arena — and the records host and kernels share: ioc_align_plan.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,33 +36,14 @@
 #include <type_traits>
 #include <vector>
 
+#include "ioc_align_plan.h"
 #include "ioc_align_sink.h"
 #include "ioc_internal.h"
 
 namespace {
 
-constexpr int ALN_C = 8;             // columns per thread
-constexpr int ALN_MAXW = 8;          // waves per workgroup
 constexpr int ALN_NEG = INT32_MIN / 4;
 constexpr uint32_t ALN_LEN_SHIFT = 26;  // window statistics word: [31:26] min(len, k), [25:0] qualifying windows
-
-struct AlnPairDev {
-    uint32_t q_off, n;   // query (rows)
-    uint32_t r_off, m;   // reference (columns)
-    int32_t gap_open, ilimit;
-    uint32_t rc;         // reference is read reverse-complemented
-    uint32_t pad;
-    // verdict mode (ioc_align_set_verdict_threshold): the traceback may stop once the count of good windows has reached stop_at
-    // (the ratio is >= the threshold whatever follows) or can no longer reach it; 0 = walk to the end
-    uint32_t stop_at;
-    float e_sum;         // (host side only) the pair's summed error rate e1 + e2 (ioc_aln_pair::e): what the corridor is planned from
-};
-
-struct AlnParams {
-    int32_t match, mismatch, gap_extend;
-    uint32_t k;     // window length, 1..32
-    uint32_t mbit;  // 1 << (32 - k): where a new comparison bit enters the (top-aligned) window
-};
 
 struct St {  // one DP state: score + statistics of its best path
     int s;
@@ -396,25 +380,7 @@ k_align_carry(const AlnPairDev* __restrict__ pairs, const uint32_t* __restrict__
 }
 
 // ---- "trace" variant ------------------------------------------------------------------------------
-constexpr int FW_C = 16;      // columns per thread in the forward pass
-#ifndef IOC_ALIGN_TILE
-#define IOC_ALIGN_TILE 128
-#endif
-constexpr int TILE = IOC_ALIGN_TILE;  // checkpoint pitch = traceback tile edge (128 or 256)
-static_assert(TILE == 128 || TILE == 256, "tile edge");
 constexpr int TR_C = TILE / 64;  // columns per lane in the traceback tile (one wave per pair)
-
-struct AlnCk {  // where a pair's checkpoints live in the arena, in int2 units
-    uint64_t row_off;  // [(n - 1) / TILE][2][row_pitch(m)] ints: the Hq plane, then the F* plane, of rows TILE, 2 TILE, ...
-    uint64_t col_off;  // [(m - 1) / TILE][col_pitch(n)]  (H, E) of columns TILE, 2 TILE, ...
-};
-
-// row checkpoints are padded to whole lane blocks (16 columns): a lane stores its block without per-column
-// bounds checks — the store block runs in EVERY step of a wave (for the two lanes whose skewed row block ends a
-// tile), so its instruction count matters as much as the cells'
-__host__ __device__ __forceinline__ uint64_t row_pitch(uint32_t m) { return (uint64_t(m) + 15u) & ~uint64_t(15); }
-// column checkpoints: 4 rows (one step of a lane) go out as two 16-byte stores
-__host__ __device__ __forceinline__ uint64_t col_pitch(uint32_t n) { return (uint64_t(n) + 3u) & ~uint64_t(3); }
 
 __device__ __forceinline__ uint32_t ref_byte(const uint8_t* __restrict__ r, uint32_t m, uint32_t rc, uint32_t j)
 {
@@ -1329,408 +1295,24 @@ int ops_fetch(ioc_ctx* c, OpsRun& o, const std::vector<AlnPairDev>& dp, const ui
 // thousand at most, two cells of it being joined through a common ancestor by paths no longer than the window
 constexpr int P16_GUARD = ALN_V2_GUARD;  // (ioc_align_sink.h: the routing predicate reasons from it)
 
-// The corridor's half width as a fraction of the longer sequence (V2Couple; IOC_ALIGN_CORRIDOR=0: every tile; a pair whose
-// result the corridor cannot vouch for is run again by the every-tile route).  0.2: a pair of one transcript scores 1.62 - 1.8
-// per base at match 2 — it passes if 2 (1 - B / len) < 1.62 — and the tile grid of a 16.7 kb pair shrinks to about half.
-// ROUND 5: the half width PER COUPLE, from the pairs' summed error rates.  A pair of one transcript scores
-// rho = match - e x c per base, and passes the certificate iff B / length > 1 - rho / match.  Before anything has been aligned
-// c comes from the error model behind setGapOpen's classes — a third each of substitutions (match - mismatch lost), insertions
-// and deletions (gap open + the match) — plus 0.02 x length; once a gap-open class has 64 related pairs behind it (this
-// context's earlier batches: ioc_ctx::aln_fit, fed by learn_corridor) the line fitted to THEM, 4.5 standard deviations down.
-// Config 3: mean width 0.157 x length (round 4: 0.2 for everybody — set by the least similar pair of the batch).  A wrong
-// guess costs time (the probe widens, or the pair is refuted and run again), never a result.
-struct CorridorModel {
-    const ioc_ctx* c;
-    AlnParams P;
-    double frac;  // the fraction without a model (0: no corridor)
-    bool fixed;   // (IOC_ALIGN_CORRIDOR: one fraction for every couple, as in round 4)
-    bool fit_ok;  // ioc_ctx::aln_fit belongs to these scores
-    bool taper;   // the model's corridor narrows down the grid (IOC_ALIGN_CORRIDOR_TAPER=0: one width, the certificate of round 4)
-    uint32_t taper_margin;  // columns on top of the taper's least passing width (IOC_ALIGN_CORRIDOR_MARGIN)
-    // ... and the score per base it was derived from (rho_lo; 0: no model behind the fraction)
-    struct Width {
-        double frac, rho;
-    };
-    Width pair_width(const AlnPairDev& d) const
-    {
-        if (fixed || !(P.match > 0)) return {frac, 0.0};
-        const double e = double(d.e_sum);
-        if (!(e > 0.0) || !(e < 1.0)) return {frac, 0.0};
-        const int go = std::max(2, std::min(5, d.gap_open));
-        double rho = double(P.match) - e * (double(P.match - P.mismatch) / 3.0 + 2.0 / 3.0 * double(go + P.match)), margin = 0.02;
-        const ioc_ctx::CorridorFit& f = c->aln_fit[go - 2];
-        if (fit_ok && f.n >= 64.0 && e >= f.e_lo - 0.02 && e <= f.e_hi + 0.02) {
-            const double me = f.se / f.n, mr = f.sr / f.n, vee = f.see / f.n - me * me, ver = f.ser / f.n - me * mr, vrr = f.srr / f.n - mr * mr;
-            const double slope = vee > 1e-9 ? ver / vee : 0.0;
-            const double sd = std::sqrt(std::max(0.0, vrr - slope * ver));
-            rho = mr + slope * (e - me) - 4.5 * std::max(sd, 0.004);
-            margin = 0.003;
-        }
-        return {std::max(0.03, std::min(0.45, 1.0 - rho / double(P.match) + margin)), rho};
-    }
-    double pair_frac(const AlnPairDev& d) const { return pair_width(d).frac; }
-};
-
-CorridorModel corridor_model(const ioc_ctx* c, const AlnParams& P, bool corridor)
+// the switches that shape a plan (ioc_align_plan.h), read once per call of align_pairs: the tests change them between calls
+AlnPlanOpts plan_opts()
 {
-    CorridorModel m{c, P, corridor ? 0.2 : 0.0, false, false, true, 256u};
+    AlnPlanOpts o;
     if (const char* e = getenv("IOC_ALIGN_CORRIDOR")) {
-        m.frac = corridor ? std::max(0.0, std::min(1.0, atof(e))) : 0.0;
-        m.fixed = true;
+        o.corridor_frac = std::max(0.0, std::min(1.0, atof(e)));
+        o.corridor_fixed = true;
     }
-    if (const char* e = getenv("IOC_ALIGN_CORRIDOR_TAPER")) m.taper = atoi(e) != 0;
-    if (const char* e = getenv("IOC_ALIGN_CORRIDOR_MARGIN")) m.taper_margin = uint32_t(std::max(0, std::min(1 << 20, atoi(e))));
-    m.fit_ok = c->aln_fit_sig[0] == P.match && c->aln_fit_sig[1] == P.mismatch && c->aln_fit_sig[2] == P.gap_extend && !getenv("IOC_ALIGN_CORRIDOR_NO_FIT");
-    return m;
-}
-
-// Bands per couple.  A full batch (config 3: 811 couples) is bound by throughput: 11 bands of 1536 rows (66.8 ms; 7 of 2560:
-// 69.2; 17 of 1024: worse again).  A small one (a merge aligns a few hundred representatives) is bound by ONE couple's
-// critical path, (bands + strips - 1) tiles of rows / (4 bands) + 63 steps: more, shorter bands shorten it as long as the
-// waves the chip holds outnumber the tiles in flight.
-uint32_t band_target(uint32_t ncouples, uint32_t few_limit, int occ, int n_cu)
-{
-    const uint32_t waves = uint32_t(occ) * uint32_t(n_cu) * uint32_t(V2_WAVES);
-    uint32_t want = std::max(12u, std::min(uint32_t(V2_MAX_BANDS), (waves + ncouples - 1u) / std::max(1u, ncouples)));
-    // (with tiles that follow their left neighbours row by row — v2_wait_rows — a strip starts ~120 steps after the one on its
-    // left whatever the band's height: fewer, taller bands win again.  A second round of 31 couples of 16.7 kb: 33 bands of 512
-    // rows 16.6 ms, 17 of 1024 rows 14.9, 11 of 1536 rows 16.2; without: 16.9 / 19.4 / 23.5)
-    if (few_limit && ncouples <= few_limit) want = std::min(want, 17u);
-    return want;
-}
-
-// what align_v2_run plans on the host before its first launch
-struct V2Plan {
-    uint32_t cnt = 0, np = 0, ncouples = 0;
-    std::vector<V2Couple> cps;
-    std::vector<V2PairCk> pck;
-    std::vector<V2PairEnd> pend;
-    std::vector<uint64_t> cwords;  // arena words of a couple
-    uint32_t lrow_total = 0, best_total = 0, max_strips = 1;
-    uint64_t tiles_skipped = 0, tiles_all = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> slices;  // [first couple, count)
-    uint64_t arena_words = 0, prof_total = 0;
-    std::vector<uint32_t> n_items, n_probe, n_diag;  // per slice: tiles of its list, the probe launch's (they come first), anti-diagonals
-    std::vector<std::vector<V2Item>> items;          // per slice: the host's list (tile_lists: IOC_V2_ITEMS_CHECK alone)
-    uint32_t max_items = 0, max_flags = 0, max_pairs = 0;
-};
-
-// bands of whole coarse rows: enough of them for the anti-diagonals of the tile grid to keep the chip busy, each long enough
-// (>= 1024 rows = 256 steps) for the 63 steps of pipeline fill to stay small (V2Couple::bstart)
-void plan_bands(V2Couple& cp, uint32_t ncoarse, uint32_t want_bands, bool corridor)
-{
-    // (a pair long enough for a corridor: shorter bands follow the diagonal more closely — config 3 with the corridor: 17 bands
-    // of 1024 rows 45.9 ms, 11 of 1536 47.6, 22 of 1024 / 512 46.1)
-    const uint32_t wb = (corridor && ncoarse >= 16u) ? std::max(want_bands, 17u) : want_bands;
-    const uint32_t reg = std::max<uint32_t>(want_bands > 16u ? 1u : 2u, (ncoarse + wb - 1) / wb);  // (coarse rows per band)
-    // (measured on config 3: short first and last bands — 1, 2, 4 coarse rows, then the regular height, then 4, 2, 1 — cost
-    // more in pipeline fill than they win: 69.9 against 69.2 ms at 7 regular bands)
-    std::vector<uint32_t> hts;
-    for (uint32_t left = ncoarse; left;) {
-        const uint32_t hgt = std::min(reg, left);
-        hts.push_back(hgt);
-        left -= hgt;
+    if (const char* e = getenv("IOC_ALIGN_CORRIDOR_TAPER")) o.taper = atoi(e) != 0;
+    if (const char* e = getenv("IOC_ALIGN_CORRIDOR_MARGIN")) o.taper_margin = uint32_t(std::max(0, std::min(1 << 20, atoi(e))));
+    o.no_fit = getenv("IOC_ALIGN_CORRIDOR_NO_FIT") != nullptr;
+    if (const char* e = getenv("IOC_ALIGN_V2_FEW")) o.few_limit = uint32_t(std::max(0, atoi(e)));
+    if (const char* e = getenv("IOC_ALIGN_WAVES")) {
+        o.waves = atoi(e);
+        o.waves_set = true;
     }
-    while (hts.size() > size_t(V2_MAX_BANDS)) {  // (very long pairs: merge from the middle)
-        const size_t mid = hts.size() / 2;
-        hts[mid - 1] += hts[mid];
-        hts.erase(hts.begin() + long(mid));
-    }
-    cp.nbands = uint32_t(hts.size());
-    cp.tpb = reg;
-    uint32_t acc = 0;
-    for (uint32_t b = 0; b <= uint32_t(V2_MAX_BANDS); ++b) {
-        cp.bstart[b] = uint16_t(std::min<uint32_t>(acc, 0xFFFFu));
-        if (b < cp.nbands) acc += hts[b];
-    }
-}
-
-// The corridor (V2Couple): tiles that meet |row - column| <= B, if that leaves out a fifth of the grid or more, and the probe.
-// Returns the tiles the corridor skips; cert[h], start[h]: the parent bound and the start bound of pair h (V2PairEnd).
-uint32_t plan_corridor(V2Couple& cp, const std::vector<AlnPairDev>& dp, const CorridorModel& cm, uint32_t nmax, uint32_t mmax, int32_t cert[2],
-                       int32_t start[2])
-{
-    const AlnParams& P = cm.P;
-    constexpr uint32_t probe_rows = 1024;
-    cp.corridor = 0;
-    for (uint32_t b = 0; b < uint32_t(V2_MAX_BANDS); ++b) {
-        cp.plo[b] = 0;
-        cp.phi[b] = uint16_t(std::min<uint32_t>(65535u, cp.nstrips - 1u));  // (V2Item::strip is 16 bits wide)
-    }
-    const uint32_t strip_cols = 64u * FW_C;
-    double frac = 0.0, rho = double(P.match);
-    for (int h = 0; h < 2; ++h)
-        if (cp.pid[h] != 0xFFFFFFFFu) {  // (the wider plan of the two pairs)
-            const CorridorModel::Width w = cm.pair_width(dp[cp.pid[h]]);
-            frac = std::max(frac, w.frac);
-            rho = std::min(rho, w.rho);
-        }
-    if (cm.frac <= 0.0) frac = 0.0;
-    const uint32_t B = uint32_t(frac * double(std::max(nmax, mmax)));
-    cp.b0 = B;
-    int64_t beff = INT64_MAX;
-    uint32_t skipped = 0;
-    uint16_t lo[V2_MAX_BANDS], hi[V2_MAX_BANDS];
-    // (the bound behind the certificate: a column of an alignment scores `match` at most — no reward for mismatches or gaps)
-    const bool can = cm.frac > 0.0 && B >= strip_cols && cp.nstrips <= 65535u && cp.nbands <= uint32_t(V2_MAX_BANDS) && P.match > 0 && P.mismatch <= P.match &&
-                     P.gap_extend >= 0;
-    bool fits = can;
-    for (int h = 0; fits && h < 2; ++h)
-        if (cp.pid[h] != 0xFFFFFFFFu) fits = dp[cp.pid[h]].gap_open >= 0;
-    // THE TAPER (model-planned corridors): a path that enters a skipped cell from a computed one is bound by the score the pass
-    // stored at that exit cell (k_fwd2_cert), so the width only has to keep the exit cells' scores low enough — a cell d columns off
-    // the diagonal at row i holds about rho i - go - ge d, and passes if d > (match - rho)(n - i) / (match + ge) to the right,
-    // (match - rho)(n - i) / (rho + ge) to the left.  The top keeps today's width: there the start bound applies.
-    const double g_right = rho > 0.0 ? std::max(0.0, double(P.match) - rho) / double(P.match + P.gap_extend) : 0.0;
-    const double g_left = rho > 0.0 ? std::max(0.0, double(P.match) - rho) / (rho + double(P.gap_extend)) : 0.0;
-    uint32_t pb = 0, ps = 0;
-    auto geometry = [&](bool taper) {
-        bool ok = true;
-        beff = INT64_MAX;
-        skipped = 0;
-        for (uint32_t b = 0; ok && b < cp.nbands; ++b) {
-            const uint32_t r0 = uint32_t(cp.bstart[b]) * uint32_t(CK2), r1 = std::min(nmax, uint32_t(cp.bstart[b + 1u]) * uint32_t(CK2));
-            uint64_t d_left = B, d_right = B;
-            if (taper) {
-                const double left = nmax > r0 ? double(nmax - r0) : 0.0, top = B > r0 ? double(B - r0) : 0.0;
-                d_left = uint64_t(std::max(top, g_left * left)) + cm.taper_margin;
-                d_right = uint64_t(std::max(top, g_right * left)) + cm.taper_margin;
-            }
-            const uint32_t c_lo = r0 > d_left ? uint32_t(r0 - d_left) : 0u, c_hi = uint32_t(std::min<uint64_t>(mmax, uint64_t(r1) + d_right));
-            if (c_hi <= c_lo) return false;  // (a band wholly below the last column's corridor: rows the longer query has alone)
-            lo[b] = uint16_t(c_lo / strip_cols);
-            hi[b] = uint16_t((c_hi - 1u) / strip_cols);
-            skipped += lo[b] + (cp.nstrips - 1u - hi[b]);
-            if (lo[b] > 0) beff = std::min<int64_t>(beff, int64_t(r0) - int64_t(lo[b]) * strip_cols);
-            if ((uint64_t(hi[b]) + 1u) * strip_cols < mmax) beff = std::min<int64_t>(beff, int64_t(hi[b] + 1u) * strip_cols - int64_t(r1));
-            // what v2_fwd_body relies on — of a computed tile off the border at most one of the tile above and the tile to its
-            // left is missing — follows from: plo and phi never fall down the bands, and every band holds the strips of its own
-            // diagonal cells (r0, r0) .. (r1, r1).  (One width for every band meets this by construction.)
-            if (taper) {
-                const uint32_t s0 = (r0 ? r0 - 1u : 0u) / strip_cols, s1 = std::min((r1 - 1u) / strip_cols, cp.nstrips - 1u);
-                ok = lo[b] <= s0 && hi[b] >= s1 && (b == 0 || (lo[b] >= lo[b - 1u] && hi[b] >= hi[b - 1u]));
-            }
-        }
-        if (!ok) return false;
-        // the probe (V2Couple): the first band that ends at row 2048 or below, the strip its last diagonal cell is in; every tile
-        // above and to the left of it must be inside the corridor with nothing missing around it, both pairs must reach it
-        pb = 0;
-        while (pb + 1u < cp.nbands && uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2) < probe_rows) ++pb;  // (3072 rows: a probe launch of 4.2 ms; 2048: 2.3)
-        const uint32_t R = uint32_t(cp.bstart[pb + 1u]) * uint32_t(CK2);
-        ps = (R - 1u) / strip_cols;
-        ok = pb + 1u < cp.nbands && R >= probe_rows;
-        for (uint32_t b = 0; ok && b <= pb; ++b) ok = lo[b] == 0 && hi[b] >= ps;
-        for (int h = 0; ok && h < 2; ++h)
-            if (cp.pid[h] != 0xFFFFFFFFu) ok = dp[cp.pid[h]].n >= R && dp[cp.pid[h]].m > ps * strip_cols;
-        return ok && skipped * 5u >= cp.nbands * cp.nstrips && beff > 0 && beff < INT64_MAX;
-    };
-    // (a couple whose taper breaks a rule gets the one width of round 4, and its certificate)
-    bool tapered = fits && cm.taper && !cm.fixed && rho > 0.0 && rho < double(P.match) && geometry(true);
-    fits = tapered || (fits && geometry(false));
-    cp.probe_band = uint16_t(fits ? pb : 0u);
-    cp.probe_strip = uint16_t(fits ? ps : 0u);
-    if (fits) {
-        cp.corridor = 1;
-        for (uint32_t b = 0; b < cp.nbands; ++b) {
-            cp.plo[b] = lo[b];
-            cp.phi[b] = hi[b];
-        }
-    }
-    for (int h = 0; h < 2; ++h) {
-        cert[h] = INT32_MIN;
-        start[h] = INT32_MAX;  // (no exit-cell certificate: the parent bound alone, k_fwd2_ends)
-        if (cp.pid[h] == 0xFFFFFFFFu || !cp.corridor) continue;
-        const AlnPairDev& d = dp[cp.pid[h]];
-        // (a path through a skipped cell has at most max(n, m) - Beff - 1 diagonal steps, each worth `match` at most)
-        cert[h] = int32_t(std::min<int64_t>(INT32_MAX, int64_t(P.match) * std::max<int64_t>(0, int64_t(std::max(d.n, d.m)) - beff - 1)));
-        if (tapered) start[h] = v2_start_bound(cp, d.n, d.m, P.match);
-    }
-    return cp.corridor ? skipped : 0u;
-}
-
-// the couple's checkpoints (V2Couple: rdat, rbase, cdat, cbase from the couple's start; slice_couples places them) in arena words
-uint64_t couple_words(V2Couple& cp, uint32_t nmax, uint32_t mmax)
-{
-    auto up4 = [](uint64_t x) { return (x + 3u) & ~uint64_t(3); };
-    cp.mpad = uint32_t((uint64_t(mmax) + 15u) & ~uint64_t(15));
-    cp.nq = (nmax + 3u) / 4u;
-    const uint64_t ncr = (nmax - 1u) / CK2, ncc = (mmax - 1u) / CK2;
-    uint64_t w = 0;
-    cp.rdat = w;
-    w += up4(ncr * 2u * cp.mpad);
-    cp.rbase = w;
-    w += up4(ncr * (cp.mpad / 16u) * 2u);
-    cp.cdat = w;
-    w += up4(ncc * uint64_t(cp.nq) * 8u);
-    cp.cbase = w;
-    w += up4(ncc * uint64_t(cp.nq) * 2u);
-    return w;
-}
-
-// the couples (pairs order[2 k2], order[2 k2 + 1]): tile grid, bands, corridor, probe, checkpoint words, and every pair's entries of
-// the last-row and last-column bests
-void plan_couples(V2Plan& pl, const std::vector<AlnPairDev>& dp, const uint32_t* order, const CorridorModel& cm, uint32_t want_bands)
-{
-    pl.cps.resize(pl.ncouples);
-    pl.pck.resize(pl.np);
-    pl.pend.resize(pl.np);
-    pl.cwords.resize(pl.ncouples);
-    for (uint32_t k2 = 0; k2 < pl.ncouples; ++k2) {
-        V2Couple& cp = pl.cps[k2];
-        cp.pid[0] = order[2u * k2];
-        cp.pid[1] = 2u * k2 + 1u < pl.cnt ? order[2u * k2 + 1u] : 0xFFFFFFFFu;
-        uint32_t nmax = 0, mmax = 0;
-        for (int h = 0; h < 2; ++h)
-            if (cp.pid[h] != 0xFFFFFFFFu) {
-                nmax = std::max(nmax, dp[cp.pid[h]].n);
-                mmax = std::max(mmax, dp[cp.pid[h]].m);
-            }
-        cp.nstrips = (mmax + 64u * FW_C - 1) / (64u * FW_C);
-        plan_bands(cp, (nmax + CK2 - 1) / CK2, want_bands, cm.frac > 0.0);
-        int32_t cert[2], start[2];
-        pl.tiles_skipped += plan_corridor(cp, dp, cm, nmax, mmax, cert, start);
-        pl.tiles_all += uint64_t(cp.nbands) * cp.nstrips;
-        pl.cwords[k2] = couple_words(cp, nmax, mmax);
-        cp.prof = 0;  // (uint4 entries; placed per slice: the profiles of a slice's couples count against the budget with its checkpoints)
-        pl.max_strips = std::max(pl.max_strips, cp.nstrips);
-        for (int h = 0; h < 2; ++h) {
-            cp.lrow0[h] = pl.lrow_total;
-            cp.best0[h] = pl.best_total;
-            if (cp.pid[h] == 0xFFFFFFFFu) continue;
-            const AlnPairDev& d = dp[cp.pid[h]];
-            const uint32_t nstr = (d.m + 64u * FW_C - 1) / (64u * FW_C);
-            pl.pend[cp.pid[h]] = V2PairEnd{pl.lrow_total, pl.best_total, cp.nbands, k2, cert[h], start[h], INT32_MIN};
-            pl.lrow_total += nstr * 64u;
-            pl.best_total += cp.nbands;
-        }
-    }
-}
-
-// slices of couples whose checkpoints and query profiles — and, in an emitting call, the operation bytes of their pairs (cops:
-// per couple; empty otherwise) — fit the budget together
-void slice_couples(V2Plan& pl, uint64_t budget, const std::vector<uint64_t>& cops)
-{
-    for (uint32_t first = 0; first < pl.ncouples;) {
-        uint64_t used = 0;
-        uint32_t k2 = first;
-        uint64_t prof_used = 0;  // uint4 entries of query profiles in this slice (they used to be made for every couple of the call at once)
-        uint64_t ops_used = 0;
-        while (k2 < pl.ncouples) {
-            const uint64_t prof_k = uint64_t(pl.cps[k2].nstrips) * 2u * 5u * 64u, ops_k = cops.empty() ? 0u : cops[k2];
-            if (k2 != first && (used + pl.cwords[k2]) * 4ull + (prof_used + prof_k) * sizeof(uint4) + ops_used + ops_k > budget) break;
-            V2Couple& cp = pl.cps[k2];
-            cp.prof = prof_used;
-            prof_used += prof_k;
-            cp.rdat += used;
-            cp.rbase += used;
-            cp.cdat += used;
-            cp.cbase += used;
-            for (int h = 0; h < 2; ++h)
-                if (cp.pid[h] != 0xFFFFFFFFu) pl.pck[cp.pid[h]] = V2PairCk{cp.rdat, cp.rbase, cp.cdat, cp.cbase, cp.mpad, cp.nq, uint32_t(h), k2};
-            used += pl.cwords[k2];
-            ops_used += ops_k;
-            ++k2;
-        }
-        pl.arena_words = std::max(pl.arena_words, used);
-        pl.prof_total = std::max(pl.prof_total, prof_used);
-        pl.slices.emplace_back(first, k2 - first);
-        first = k2;
-    }
-}
-
-// every slice's flags (V2Couple::flag0) and what the launches need to know of its list of tiles, in closed form from the grids:
-// the list itself is made on the device (k_fwd2_items), in the order tile_lists defines
-void tile_counts(V2Plan& pl)
-{
-    const size_t ns = pl.slices.size();
-    pl.n_items.assign(ns, 0);
-    pl.n_probe.assign(ns, 0);
-    pl.n_diag.assign(ns, 1);
-    for (size_t si = 0; si < ns; ++si) {
-        const uint32_t k_lo = pl.slices[si].first, k_hi = pl.slices[si].first + pl.slices[si].second;
-        uint32_t nf = 0;
-        uint64_t n_all = 0, n_probe = 0;
-        for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
-            V2Couple& cp = pl.cps[k2];
-            cp.flag0 = nf;
-            nf += cp.nbands * cp.nstrips;
-            n_all += uint64_t(cp.nbands) * cp.nstrips;
-            if (cp.corridor) n_probe += (uint64_t(cp.probe_band) + 1u) * (uint64_t(cp.probe_strip) + 1u);
-            pl.n_diag[si] = std::max(pl.n_diag[si], cp.nbands + cp.nstrips - 1u);
-        }
-        pl.n_probe[si] = uint32_t(n_probe);
-        pl.n_items[si] = uint32_t(n_probe + n_all);
-        pl.max_items = std::max(pl.max_items, pl.n_items[si]);
-        pl.max_flags = std::max(pl.max_flags, nf);
-        pl.max_pairs = std::max(pl.max_pairs, std::min(pl.cnt, 2u * k_hi) - 2u * k_lo);
-    }
-}
-
-// every slice's list of tiles and flags (V2Couple::flag0) on the host: the definition of the list's order, and what
-// IOC_V2_ITEMS_CHECK holds the device's list against
-void tile_lists(V2Plan& pl)
-{
-    pl.items.resize(pl.slices.size());
-    pl.n_probe.assign(pl.slices.size(), 0);
-    for (size_t si = 0; si < pl.slices.size(); ++si) {
-        const uint32_t k_lo = pl.slices[si].first, k_hi = pl.slices[si].first + pl.slices[si].second;
-        uint32_t nf = 0;
-        auto& it = pl.items[si];
-        uint32_t maxdiag = 0;
-        size_t total_items = 0;
-        for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
-            V2Couple& cp = pl.cps[k2];
-            cp.flag0 = nf;
-            nf += cp.nbands * cp.nstrips;
-            total_items += size_t(cp.nbands) * cp.nstrips;
-            maxdiag = std::max(maxdiag, cp.nbands + cp.nstrips - 2u);
-        }
-        // anti-diagonal by anti-diagonal, couples side by side: every tile comes after the tile above it and the tile to its left
-        // (generated in that order: sorting 150 000 items cost 4 ms of host time per call)
-        it.reserve(total_items + 64u * pl.slices[si].second);
-        // first the probe's tiles (couples with a corridor: the top left corner of the grid, V2Couple), in the same order
-        for (uint32_t dg = 0; dg <= maxdiag; ++dg) {
-            bool any = false;
-            for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
-                const V2Couple& cp = pl.cps[k2];
-                if (!cp.corridor || dg > uint32_t(cp.probe_band) + cp.probe_strip) continue;
-                any = true;
-                const uint32_t b_lo = dg >= uint32_t(cp.probe_strip) + 1u ? dg - cp.probe_strip : 0u, b_hi = std::min<uint32_t>(dg, cp.probe_band);
-                for (uint32_t b = b_lo; b <= b_hi; ++b) it.push_back(V2Item{k2, uint16_t(b), uint16_t(dg - b)});
-            }
-            if (!any && dg > 64u) break;
-        }
-        pl.n_probe[si] = uint32_t(it.size());
-        for (uint32_t dg = 0; dg <= maxdiag; ++dg)
-            for (uint32_t k2 = k_lo; k2 < k_hi; ++k2) {
-                const V2Couple& cp = pl.cps[k2];
-                if (dg > cp.nbands + cp.nstrips - 2u) continue;
-                const uint32_t b_lo = dg >= cp.nstrips ? dg - cp.nstrips + 1u : 0u, b_hi = std::min(dg, cp.nbands - 1u);
-                for (uint32_t b = b_lo; b <= b_hi; ++b) it.push_back(V2Item{k2, uint16_t(b), uint16_t(dg - b)});
-            }
-        pl.max_items = std::max<uint32_t>(pl.max_items, uint32_t(it.size()));
-        pl.max_flags = std::max(pl.max_flags, nf);
-        pl.max_pairs = std::max(pl.max_pairs, std::min(pl.cnt, 2u * k_hi) - 2u * k_lo);
-    }
-}
-
-// IOC_V2_ITEMS_CHECK (developer switch): the host's lists into pl.items, and tile_counts' closed forms against what they say
-int tile_lists_check(ioc_ctx* c, V2Plan& pl)
-{
-    V2Plan ref = pl;
-    ref.max_items = ref.max_flags = ref.max_pairs = 0;
-    tile_lists(ref);
-    for (size_t si = 0; si < pl.slices.size(); ++si)
-        if (ref.items[si].size() != pl.n_items[si] || ref.n_probe[si] != pl.n_probe[si])
-            return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_ITEMS_CHECK: slice " + std::to_string(si) + ": " + std::to_string(pl.n_items[si]) + " tiles, " +
-                                                  std::to_string(pl.n_probe[si]) + " of the probe planned; the host's list has " +
-                                                  std::to_string(ref.items[si].size()) + " and " + std::to_string(ref.n_probe[si]));
-    for (uint32_t k2 = 0; k2 < pl.ncouples; ++k2)
-        if (ref.cps[k2].flag0 != pl.cps[k2].flag0) return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_ITEMS_CHECK: flag0 of couple " + std::to_string(k2) + " differs");
-    if (ref.max_items != pl.max_items || ref.max_flags != pl.max_flags || ref.max_pairs != pl.max_pairs)
-        return ioc_fail(c, IOC_ERR_STATE, "IOC_V2_ITEMS_CHECK: max_items / max_flags / max_pairs differ from the host lists'");
-    pl.items = std::move(ref.items);
-    return IOC_OK;
+    o.no_cross_tail = getenv("IOC_ALIGN_NO_CROSS_TAIL") != nullptr;
+    return o;
 }
 
 // ... and a slice's list as the device made it against the host's, item by item (behind a wait for the stream)
@@ -2180,7 +1762,8 @@ int v2_cert_check(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t*
 // out (the caller then runs the same pairs through version 1).
 // `ops`: an emitting call (null otherwise).
 int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* order, uint32_t cnt, const uint32_t* d_order,
-                 const AlnParams& P, int32_t* d_score, uint32_t* d_count, bool corridor, bool* fell_back, OpsRun* ops, StageTrace& tr)
+                 const AlnParams& P, const AlnPlanOpts& po, int32_t* d_score, uint32_t* d_count, bool corridor, bool* fell_back, OpsRun* ops,
+                 StageTrace& tr)
 {
     *fell_back = false;
     if (cnt == 0) return IOC_OK;
@@ -2193,8 +1776,7 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     // the 16-bit window's guard (|relative score| at a rebase): a pair beyond it is flagged and re-run by version 1
     o.guard = P16_GUARD;
     if (const char* e = getenv("IOC_ALIGN_V2_GUARD")) o.guard = std::max(1, std::min(P16_GUARD, atoi(e)));
-    o.few_limit = 128;
-    if (const char* e = getenv("IOC_ALIGN_V2_FEW")) o.few_limit = uint32_t(std::max(0, atoi(e)));
+    o.few_limit = po.few_limit;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o.occ, reinterpret_cast<const void*>(k_fwd2), 64 * V2_WAVES, 0) != hipSuccess) o.occ = 0;
     (void)hipGetLastError();
     if (o.occ < 1) o.occ = 3;
@@ -2208,7 +1790,8 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
     if (getenv("IOC_TRACE"))  // (which shape the call runs in: tests/test_gpu_align_shapes.py reads this line and v2_slice's)
         fprintf(stderr, "[ioc]   aligner v2: shape: %u couples, band target %u, few_limit %u, occ %d, n_cu %d\n", pl.ncouples, want_bands, o.few_limit, o.occ,
                 o.n_cu);
-    plan_couples(pl, dp, order, corridor_model(c, P, corridor), want_bands);
+    const bool fit_sig_ok = c->aln_fit_sig[0] == P.match && c->aln_fit_sig[1] == P.mismatch && c->aln_fit_sig[2] == P.gap_extend;
+    plan_couples(pl, dp, order, corridor_model(P, corridor, po, c->aln_fit, fit_sig_ok), want_bands);
     tr.mark("plan_couples");
     std::vector<uint64_t> cops;  // (emitting call) the operation bytes of a couple's pairs: query length + reference length each
     if (ops) {
@@ -2239,7 +1822,10 @@ int align_v2_run(ioc_ctx* c, const std::vector<AlnPairDev>& dp, const uint32_t* 
                 (unsigned long long)pl.tiles_skipped, (unsigned long long)pl.tiles_all);
     tr.mark("arena reserve");
     tile_counts(pl);
-    if (getenv("IOC_V2_ITEMS_CHECK") && (r = tile_lists_check(c, pl)) != IOC_OK) return r;
+    if (getenv("IOC_V2_ITEMS_CHECK")) {
+        const std::string differs = tile_lists_check(pl);
+        if (!differs.empty()) return ioc_fail(c, IOC_ERR_STATE, differs);
+    }
     tr.mark("tile_counts");
 
     o.deadline = 4;  // (blocks of slack on top of what a pair of one transcript needs to be decided: 2 per 512 windows of its threshold)
@@ -2423,44 +2009,19 @@ void order_pairs(AlnBatch& b, const ioc_aln_pair* pairs)
     std::stable_partition(order.begin(), order.end(), [&](uint32_t x) { return dp[x].pad == uint32_t(ALN_ROUTE_V2); });
 }
 
-// 3. waves per pair: few pairs -> wide workgroups (latency), many pairs -> narrow ones (no fill/drain waste)
-struct WavePlan {
-    uint32_t waves;
-    bool few_pairs;  // a handful of long pairs (the later alignment rounds of a batch): 4-wave workgroups, several per pair (v1_slice)
-};
-WavePlan plan_waves(const AlnBatch& b, bool carry)
-{
-    const uint32_t np = uint32_t(b.dp.size());
-    uint32_t waves = ALN_MAXW;
-    if (const char* e = getenv("IOC_ALIGN_WAVES")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= ALN_MAXW) waves = uint32_t(v);
-    } else {
-        while (waves > 1 && uint64_t(np) * waves > 4096) waves >>= 1;
-        if (carry) {
-            while (waves > 1 && uint64_t(waves / 2) * 64 * ALN_C >= b.max_m) waves >>= 1;
-        } else {
-            // row bands x column strips run as a pipeline: it needs a few strips per band to fill, and
-            // whole tiles per band
-            const uint32_t strips = (b.max_m + 64 * FW_C - 1) / (64 * FW_C), tiles = (b.max_n + TILE - 1) / TILE;
-            while (waves > 1 && (strips < 2 * waves || tiles < 2 * waves)) waves >>= 1;
-        }
-    }
-    const bool few_pairs = !carry && !getenv("IOC_ALIGN_WAVES") && np <= 64 && waves >= 4 && !getenv("IOC_ALIGN_NO_CROSS_TAIL");
-    return WavePlan{few_pairs ? 4u : waves, few_pairs};
-}
+// 3. waves per pair: plan_waves (ioc_align_plan.h)
 
 // 4. version 2 takes the pairs it may (aln_v2_ok) — the front of `order`; *n_v2: how many it answered (0 when a bounded wait ran out
 // and they all go to version 1)
-int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2, const AlnSink* oh,
-           StageTrace& tr)
+int run_v2(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, const AlnPlanOpts& po, int32_t* d_score, uint32_t* d_count, AlnRoute route, uint32_t* n_v2,
+           const AlnSink* oh, StageTrace& tr)
 {
     const uint32_t np = uint32_t(b.dp.size());
     uint32_t n = 0;
     while (n < np && b.dp[b.order[n]].pad == uint32_t(ALN_ROUTE_V2)) ++n;
     bool fell_back = false;
     OpsRun ops{oh, b.back.data()};
-    const int r = align_v2_run(c, b.dp, b.order.data(), n, static_cast<const uint32_t*>(c->a_order.p), P, d_score, d_count, route != AlnRoute::every_tile,
+    const int r = align_v2_run(c, b.dp, b.order.data(), n, static_cast<const uint32_t*>(c->a_order.p), P, po, d_score, d_count, route != AlnRoute::every_tile,
                                &fell_back, oh ? &ops : nullptr, tr);
     if (r != IOC_OK) return r;
     if (fell_back) {
@@ -2514,50 +2075,6 @@ size_t fwd_lds_limit(ioc_ctx* c, bool prof, const void* kfn, size_t fallback, si
         (void)hipGetLastError();
     }
     return lim;
-}
-
-// checkpoint arena: slices of pairs (in `order`, from n_v2 on) whose checkpoints fit the budget together, one kernel per slice
-struct V1Plan {
-    std::vector<AlnCk> cko;
-    std::vector<std::pair<uint32_t, uint32_t>> slices;  // [first, count) in `order`
-    uint64_t arena = 0;                                 // int2 units
-    uint32_t max_cnt = 0;
-    std::vector<uint64_t> ops_end, slice_ops;           // (emitting call) per pair: the end of its region of operation bytes; per slice: its bytes
-    uint64_t ops_most = 0;
-};
-uint64_t v1_row_units(const AlnPairDev& d) { return uint64_t((d.n - 1) / TILE) * row_pitch(d.m); }
-
-V1Plan plan_v1(const AlnBatch& b, uint32_t n_v2, uint64_t budget, bool emit)
-{
-    const std::vector<AlnPairDev>& dp = b.dp;
-    const uint32_t np = uint32_t(dp.size());
-    V1Plan pl;
-    pl.cko.resize(np);
-    if (emit) pl.ops_end.assign(np, 0);
-    for (uint32_t first = n_v2; first < np;) {
-        uint64_t used = 0, ops_used = 0;
-        uint32_t cnt = 0;
-        while (first + cnt < np) {
-            const AlnPairDev& d = dp[b.order[first + cnt]];
-            const uint64_t u = v1_row_units(d) + uint64_t((d.m - 1) / TILE) * col_pitch(d.n);
-            const uint64_t ops_u = emit ? uint64_t(d.n) + d.m : 0u;
-            if (cnt > 0 && (used + u) * 8ull + ops_used + ops_u > budget) break;
-            if (cnt > 0 && (d.pad != 0) != (dp[b.order[first]].pad != 0)) break;  // one kernel per slice
-            // (rows first: their pitch is a multiple of 16 int2, `used` stays 16-byte aligned for the int4 stores)
-            pl.cko[b.order[first + cnt]] = AlnCk{used, used + v1_row_units(d)};
-            used += u;
-            ops_used += ops_u;
-            if (emit) pl.ops_end[b.order[first + cnt]] = ops_used;
-            ++cnt;
-        }
-        pl.slice_ops.push_back(ops_used);
-        pl.ops_most = std::max(pl.ops_most, ops_used);
-        pl.arena = std::max(pl.arena, used);
-        pl.slices.emplace_back(first, cnt);
-        pl.max_cnt = std::max(pl.max_cnt, cnt);
-        first += cnt;
-    }
-    return pl;
 }
 
 // version 1's forward pass over the pairs o[0 .. cnt) of a slice (k_align_fwd, see there for the arguments)
@@ -2740,7 +2257,7 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
     for (const AlnPairDev& d : b.dp)
         if (v1_row_units(d) >= (uint64_t(1) << 29))
             return ioc_fail(c, IOC_ERR_CAPACITY, "alignment of " + std::to_string(d.n) + " x " + std::to_string(d.m) + " bases: row checkpoints above 4 GB per pair");
-    V1Plan pl = plan_v1(b, n_v2, budget, oh != nullptr);
+    V1Plan pl = plan_v1(b.dp, b.order.data(), n_v2, budget, oh != nullptr);
     OpsRun ops{oh, b.back.data()};
     if (oh) {
         ops.end.swap(pl.ops_end);
@@ -2781,7 +2298,7 @@ int run_v1(ioc_ctx* c, const AlnBatch& b, uint32_t n_v2, const WavePlan& wp, con
 void learn_corridor(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, const std::vector<int32_t>& hs, const std::vector<uint32_t>& hc)
 {
     if (c->aln_fit_sig[0] != P.match || c->aln_fit_sig[1] != P.mismatch || c->aln_fit_sig[2] != P.gap_extend) {
-        for (auto& f : c->aln_fit) f = ioc_ctx::CorridorFit();
+        for (auto& f : c->aln_fit) f = CorridorFit();
         c->aln_fit_sig[0] = P.match, c->aln_fit_sig[1] = P.mismatch, c->aln_fit_sig[2] = P.gap_extend;
     }
     for (size_t x = 0; x < b.dp.size(); ++x) {
@@ -2790,7 +2307,7 @@ void learn_corridor(ioc_ctx* c, const AlnBatch& b, const AlnParams& P, const std
         if (hc[x] == 0xFFFFFFFFu || len < 4096u || !(d.e_sum > 0.0f) || std::min(d.n, d.m) * 10u < len * 9u) continue;
         const double rho = double(hs[x]) / double(len), e = double(d.e_sum);
         if (rho * 2.0 < double(P.match)) continue;  // (not a pair of one transcript)
-        ioc_ctx::CorridorFit& f = c->aln_fit[std::max(2, std::min(5, d.gap_open)) - 2];
+        CorridorFit& f = c->aln_fit[std::max(2, std::min(5, d.gap_open)) - 2];
         if (f.n >= 1e6) continue;  // (enough)
         f.n += 1.0, f.se += e, f.sr += rho, f.see += e * e, f.ser += e * rho, f.srr += rho * rho;
         f.e_lo = std::min(f.e_lo, e), f.e_hi = std::max(f.e_hi, e);
@@ -2898,7 +2415,8 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     tr.mark("order_pairs");
     const char* ev = getenv("IOC_ALIGN_VARIANT");
     const bool carry = ev && strcmp(ev, "carry") == 0 && !out.ops;  // (the carry variant has no walk: an emitting call takes the traced route)
-    const WavePlan wp = plan_waves(b, carry);
+    const AlnPlanOpts po = plan_opts();
+    const WavePlan wp = plan_waves(b.max_n, b.max_m, np, carry, po);
     IOC_TRY(ioc_reserve(c, c->a_pairs, size_t(np) * sizeof(AlnPairDev)));
     IOC_TRY(ioc_reserve(c, c->a_order, size_t(np) * 4));
     IOC_TRY(ioc_reserve(c, c->a_out, size_t(np) * 8));
@@ -2910,7 +2428,7 @@ int align_pairs(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t 
     const bool v2 = route != AlnRoute::v1_only && !carry && !getenv("IOC_ALIGN_V1") && !(arena_mode && strcmp(arena_mode, "fat") == 0);
     uint32_t n_v2 = 0;
     tr.mark("pairs and order up");
-    if (v2 && (r = run_v2(c, b, P, d_score, d_count, route, &n_v2, out.ops, tr)) != IOC_OK) return r;
+    if (v2 && (r = run_v2(c, b, P, po, d_score, d_count, route, &n_v2, out.ops, tr)) != IOC_OK) return r;
     if (carry)
         r = run_carry(c, b, wp.waves, P, d_score, d_count);
     else if (n_v2 < np)

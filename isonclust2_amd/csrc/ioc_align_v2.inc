@@ -28,57 +28,8 @@
 // Slanted scores, Hq = H* - (go - ge), the profile in LDS, the look-ahead ring, the 4-row steps and the lane skew are
 // those of k_align_fwd (see there).
 
-constexpr int CK2 = 512;          // coarse checkpoint pitch (rows and columns); a multiple of TILE
-constexpr int V2_WAVES = 4;       // waves per workgroup: independent workers with LDS of their own
 constexpr int V2_BLK_C = 8;       // columns per lane in the traceback's block recompute (64 x 8 = CK2)
-constexpr int V2_MAX_BANDS = 40;  // bands per couple (a 16.7 kb pair has 33 coarse rows: a band each when few couples share the chip)
-static_assert(CK2 % TILE == 0 && CK2 == 64 * V2_BLK_C, "block geometry");
-
-struct V2Couple {
-    uint32_t pid[2];          // the two pairs (0xFFFFFFFF: none)
-    uint32_t nbands, nstrips; // tile grid of the couple (the larger of the two pairs)
-    uint32_t tpb;             // (unused: bands have their own heights, see bstart)
-    uint32_t flag0;           // flags[flag0 + band * nstrips + strip]
-    uint32_t mpad;            // row-checkpoint pitch in words (multiple of 16)
-    uint32_t nq;              // entries per checkpoint column: ceil(max n / 4)
-    uint64_t rdat;            // [coarse row][plane Hq, F*][mpad] words                      (word offsets into the arena)
-    uint64_t rbase;           // [coarse row][mpad / 16] int2: the two bases of a lane block
-    uint64_t cdat;            // [coarse column][nq][8] words: hl[0..3], el[0..3] of a 4-row step
-    uint64_t cbase;           // [coarse column][nq] int2
-    uint64_t prof;            // query profiles of the couple's strips: [strip][pair][base code][lane] uint4 (uint4 index into the profile arena)
-    uint32_t lrow0[2];        // per pair: first entry of its last-row bests [strip][lane] (int2)
-    uint32_t best0[2];        // per pair: first entry of its per-band bests of the last column (int2)
-    // band b covers the coarse rows [bstart[b], bstart[b + 1]).  (Heights may differ: short bands at the top and the bottom
-    // of the matrix were tried as a way to shorten the ramp of the tile grid, and measured slower.)
-    uint16_t bstart[V2_MAX_BANDS + 1];
-    // THE CORRIDOR: only the tiles (band b, strips plo[b] .. phi[b]) are computed — those that meet |row - column| <= B —, the
-    // others count as "no score".  What comes out is the alignment restricted to paths inside the computed tiles; it IS the
-    // alignment (score, end cell, every choice along the traceback) whenever its score beats the most a path through a skipped
-    // cell can reach, match x (max(n, m) - Beff - 1) with Beff the least |row - column| of a skipped cell: k_fwd2_ends checks
-    // that per pair (V2PairEnd::cert) and the host runs a pair that fails it again without a corridor.  Pairs of one transcript
-    // pass (their score is 1.6 - 1.8 per base where match = 2: B = 0.2 x length), wrong candidates do not.
-    // Whether a pair is worth a corridor is not known beforehand: a PROBE launch computes the top left corner of every couple's
-    // grid (bands 0 .. probe_band — 2048 rows —, strips 0 .. probe_strip: exact values, nothing is missing there), k_fwd2_probe reads the diagonal's
-    // neighbourhood out of the coarse row at the probe band's end — a pair of one transcript has ~1.7 per base there, a wrong
-    // candidate next to nothing — and opens the couple's grid (corridor = 0, every strip) if either pair looks wrong; the main
-    // launch takes the full list of tiles and skips what is outside its couple's corridor or done already.
-    uint16_t plo[V2_MAX_BANDS], phi[V2_MAX_BANDS];
-    uint32_t corridor;        // some tile of the grid is skipped
-    uint16_t probe_band, probe_strip;
-    uint32_t b0;              // the half width the host planned the corridor with (columns)
-};
-
-struct V2Item {
-    uint32_t couple;
-    uint16_t band, strip;
-};
-
-// where a pair's checkpoints are: what the traceback needs of its couple
-struct V2PairCk {
-    uint64_t rdat, rbase, cdat, cbase;
-    uint32_t mpad, nq, half, couple;
-};
-
+static_assert(CK2 == 64 * V2_BLK_C, "block geometry");
 
 // bounded wait for a flag another workgroup sets: relaxed agent-scope polls, then ONE acquire by the wave (the caller's).
 // Wave-uniform on purpose — every lane polls the same word (one request) and the loop condition is a scalar: with the poll
@@ -978,40 +929,6 @@ __global__ void __launch_bounds__(64 * V2_WAVES) __attribute__((amdgpu_waves_per
 }
 
 
-// end cell of every pair: best of the last column (rows ascending: bands top to bottom), replaced only by a strictly larger
-// cell of the last row (columns ascending) — the host aligner's scan order (ioc_align.cpp).  One wave per pair.
-struct V2PairEnd {
-    uint32_t lrow0, best0, nbands, couple;
-    int32_t cert;  // corridor: the score the pair has to BEAT for the corridor's result to stand (INT32_MIN: no corridor)
-    // A TAPERED corridor (plan_corridor) is vouched for by the exit cells' scores instead: `cert` is then the parent bound, and
-    // the pair has to beat min(cert, max(start, exit)).  A path through a skipped cell either has its first cell off row 0 and
-    // column 0 skipped — `start`: match x the diagonal steps left from the first such cell of row 0 and of column 0
-    // (v2_start_bound; INT32_MAX: one width for every band, `cert` alone decides) — or steps into its first skipped cell from a
-    // computed cell y, its prefix inside the computed tiles: it scores H_C(y) + match x min(n - i_y, m - j_y) at most, H_C being
-    // what the pass has just stored at y.  `exit`: the largest of these over the pair's exit cells (k_fwd2_cert; INT32_MIN: none).
-    int32_t start, exit;
-};
-
-// the start bound of a pair (n rows, m columns) in its couple's corridor, whose band 0 starts at strip 0: row 0 is left for a skipped
-// tile from column (phi[0] + 1) strips on, column 0 from the first row of the first band with plo > 0 on
-__host__ __device__ inline int32_t v2_start_bound(const V2Couple& cp, uint32_t n, uint32_t m, int32_t match)
-{
-    const unsigned long long strip_cols = 64ull * FW_C, j0 = (uint32_t(cp.phi[0]) + 1ull) * strip_cols;
-    long long steps = -1;
-    if (j0 < m) steps = (long long)(n < m - j0 ? n : m - j0);
-    for (uint32_t b = 0; b < cp.nbands; ++b)
-        if (cp.plo[b] > 0) {
-            const unsigned long long r0 = (unsigned long long)cp.bstart[b] * uint32_t(CK2);
-            if (r0 < n) {
-                const long long down = (long long)(n - r0 < m ? n - r0 : m);
-                steps = steps > down ? steps : down;
-            }
-            break;
-        }
-    if (steps < 0) return INT32_MIN;
-    const long long v = steps * (long long)match;
-    return v > 0x7FFFFFFFll ? 0x7FFFFFFF : int32_t(v);
-}
 // per pair: i, j, state, window bits, pushed, count, flag (0 done / not parked, 1 parked by the first traceback launch, 2 sent to the
 // helper launch before any traceback: see k_fwd2_ends), - | the two launches' walk records (IOC_V2_TRACE_TIMES)
 constexpr uint32_t V2_RESUME_WORDS = 16;

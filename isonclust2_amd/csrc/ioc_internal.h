@@ -18,6 +18,7 @@
 #include <utility>
 #include <vector>
 
+#include "ioc_align_plan.h"
 #include "ioc_sink_plan.h"
 #include "isonclust2_hip.h"
 
@@ -240,13 +241,7 @@ struct ioc_ctx {
     hipEvent_t ev_side[2]{};
     size_t aln_lds_max = 0, aln_lds_max2 = 0;  // dynamic LDS a k_align_fwd<true/false> workgroup may reserve (residency cap)
     double aln_verdict_thr = -1.0;  // ioc_align_set_verdict_threshold (<= 0: exact counts)
-    // The aligner's corridor model (ioc_align_gpu.hip, align_v2_run): score per base of the pairs aligned so far against their summed
-    // error rate, one straight line per gap-open class (setGapOpen: 2..5).  Decides how wide a couple's corridor is PLANNED — which
-    // tiles are computed, never what comes out (the certificate and the re-run see to that).
-    struct CorridorFit {
-        double n = 0, se = 0, sr = 0, see = 0, ser = 0, srr = 0, e_lo = 1e9, e_hi = -1e9;
-    };
-    CorridorFit aln_fit[4];
+    CorridorFit aln_fit[4];              // the aligner's corridor model (ioc_align_plan.h), fed by ioc_align_gpu.hip's learn_corridor
     int32_t aln_fit_sig[3] = {0, 0, 0};  // (match, mismatch, gap_extend) the sums belong to
 
     // ---- host drivers (ioc_host.cpp, ioc_consensus.cpp) ----

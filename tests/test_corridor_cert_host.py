@@ -8,7 +8,11 @@ unrelated pairs; corridors that taper down the grid as plan_corridor's do (a top
 ones (the same, every band's ends jittered and shifted, made monotone again — they may leave out the diagonal).  The widths are
 drawn for 2 / -2 / 3 / 1 and scaled for another score set by what an error costs there in matches (_loss: the same error rates
 take a wider corridor where a gap costs four matches than where it costs two, as plan_corridor's own widths do).  At least a quarter
-of the cases with skipped tiles must certify: a certificate that refuted everything would pass the first check for nothing."""
+of the cases with skipped tiles must certify: a certificate that refuted everything would pass the first check for nothing.
+
+The corridors here are drawn, and cover shapes the planner never makes.  The planner's own corridors — the bands and plo / phi that
+plan_couples (csrc/ioc_align_plan.h) plans for pairs of 5 - 9 kb, tapered and of one width — go through the same certificate in
+tools/align_plan_check.cpp, a stand-alone program for the CPU."""
 import ctypes as C
 import random
 
