@@ -1350,7 +1350,8 @@ int64_t ioc_host_align_global_ops(const char* query, int32_t qlen, const char* r
  * and fails the length test as n_long, and so does one whose window leaves its read (qpos[hi] < qpos[lo] or qpos[hi] > qlen_i: a
  * plane that is not this read's).  The TEMPLATE is the voter at index (n - 1) / 2 of the voters sorted ascending by (window
  * length, index): the lower median.  A site without a voter is not called: tlen = 0, template_pair = -1.
- * All carriers of a site vote together, whichever isoform they are in: two different exons at one junction are not told apart.
+ * All carriers of a site vote together here, whichever isoform they are in: two different exons at one junction are told apart by
+ * the section after this one (ioc_host_insert_window_variants), not by these calls.
  * The consensus of a site: every voter's window is aligned to the template's (ioc_host_align_global_ops, the template the
  * reference; the template to itself is all '='), its bytes projected (ioc_host_ops_project, ioc_host_ops_project_ins) and piled
  * (ioc_host_planes_pile); the site is ioc_host_pileup_call(those tables, the template's window, polish_min_depth).  The sequence
@@ -1410,6 +1411,131 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* ctx, int32_t n_pairs, const ioc_
                                        ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
                                        int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq,
                                        char* out_wqual, int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats);
+
+/* ---- Two exons at one junction: the variants of an insertion site ----
+ * The window stage lets all carriers of a site vote together.  Where they carry two different exons (mutually exclusive exons), the
+ * voters are split in two here, each variant gets a consensus of its own, every read a second key and the isoforms are counted again.
+ * The rule: the window rule {slack, max_win, match, mismatch, gap}, min_agree in 1 .. 100, and min_alt >= 1 and min_pct in 1 .. 50,
+ * the insert stage's.  All integers.  Per kept site:
+ *  1. The AGREEMENT of an alignment is #'=' - #'X' - #'D' - #'I' over its bytes (ioc_host_ops_agreement).  A voter of qlen bases is
+ *     NEAR a template of tlen bases iff its agreement a from ioc_host_align_global_ops(voter, template) has a >= 1 and 100 a >=
+ *     min_agree max(qlen, tlen).  A template is NEAR itself, a = tlen.
+ *  2. Round A: the classes, the template and lo / hi are ioc_host_insert_windows' and come back unchanged.  Every voter is tested
+ *     against template A; n_far voters are not NEAR.
+ *  3. Round B runs iff n_far >= need and n_voters - n_far >= need, need = need(n_voters) as in ioc_host_pileup_sites with this
+ *     rule's min_alt and min_pct.  Template B is the lower median of the FAR voters by (window length, index); every far voter is
+ *     tested against it: n_b of them are NEAR it, n_other are not.
+ *  4. The site SPLITS iff round B ran and n_b >= need.  At a split site the near voters are variant A, the far voters near
+ *     template B variant B, the rest OTHER: they vote nowhere.  At a site that does not split every voter is variant A, the far
+ *     ones included, and the site's consensus is ioc_planes_insert_windows', byte for byte.  (Where round B did not run, n_b and
+ *     n_other are 0 and template_pair_b is -1; where it ran and the site does not split, they say what it found.)
+ *  5. The consensus of a variant: the window stage's chain over its voters and its template (project, pile, ioc_host_pileup_call
+ *     with the template's window as the frame).  A site has two slots, 2 x for A and 2 x + 1 for B; slot B is empty where the site
+ *     does not split.
+ *  6. key2 is the read's insert key with its state changed at every SPLIT site: a variant-B voter gets IOC_INS_CARRY_B, an OTHER
+ *     voter IOC_INS_NONE, a carrier that is no voter (IOC_WIN_SHORT, IOC_WIN_LONG) IOC_INS_NONE — nobody knows which exon it holds
+ *     —, everything else stays.  mask2 has both bits of every site whose state is not NONE.
+ *  7. The isoforms again: step 9 of ioc_host_planes_inserts over (pre_key, key2), (pre_mask, mask2) and pre_full
+ *     (ioc_host_key_isoforms, which that definition calls as well).
+ * min_agree 45 is a choice made on simulated windows, not measured on real data: 8 + exon + 9 bases, scoring 2 / -2 / 2, 8 % errors
+ * in voter and template, 60 trials a shape.  The lowest 100 a / max between two copies of one exon against the highest between two
+ * different exons: 57 / 33 at 60 and 60 bases, 59 / 31 at 60 and 45, 61 / 22 at 120 and 100.  At 30 bases and below the ranges
+ * overlap (49 / 42), at 15 % errors they touch (35 / 31): exons under about 40 bases and reads beyond about 10 % errors are outside
+ * what the default separates.
+ * What stays out: the splice (ioc_host_isoform_splice reads state 2 as "does not carry"), more than two variants, a
+ * quality-weighted variant call and re-clustering.  State 2 appears in the outputs of the calls of this section alone. */
+#define IOC_INS_CARRY_B 2
+#define IOC_WINVAR_NONE 0    /* a read's variant at a site: no voter; variant A; variant B; a voter near neither template */
+#define IOC_WINVAR_A 1
+#define IOC_WINVAR_B 2
+#define IOC_WINVAR_OTHER 3
+#define IOC_WINVAR_MIN_AGREE 45
+typedef struct {
+    int32_t split;                /* 1: the site splits */
+    int32_t template_pair_b;      /* the pair (ioc_host_insert_window_variants: the read) whose window is template B, -1 without */
+    int32_t tlen_b;
+    uint32_t n_a, n_b, n_other;   /* n_a: the voters of variant A (all of them where the site does not split) */
+    uint32_t n_far;
+    uint32_t reserved;
+} ioc_window_variant;             /* 32 bytes */
+typedef struct {
+    uint64_t key2;
+    int32_t group, how;
+} ioc_read_variants;              /* 16 bytes */
+typedef struct {
+    int32_t n_sites, n_split, n_groups, n_reads, n_direct, n_assigned, n_rare, n_ambiguous;
+} ioc_variants_seg;               /* 32 bytes */
+/* *out = #'=' - #'X' - #'D' - #'I' over the bytes; 'i' and 'd' count for nothing.  IOC_ERR_ARG, with nothing written, for a negative
+ * length, a NULL pointer that is needed and a byte outside "=XIDid". */
+int ioc_host_ops_agreement(const char* ops, int64_t len, int32_t* out);
+/* The isoforms of n_reads reads from two-word keys: read i is complete iff mask[i] == full and pre_mask[i] == pre_full; a pair
+ * (pre_key, key) carried by at least min_alt complete reads is supported, the supported pairs are the groups 0 .. n - 1 in
+ * ascending unsigned order, pre_key major; direct, rare, assigned and ambiguous as step 9 of ioc_host_planes_inserts has them.
+ * pre_key and pre_mask: both or neither (then all three are 0).  out_group / out_how per read; out_counts: n_groups, n_direct,
+ * n_assigned, n_rare, n_ambiguous.  IOC_ERR_ARG, with nothing written, for a negative count, min_alt < 1 and a NULL pointer that is
+ * needed. */
+int ioc_host_key_isoforms(const uint64_t* pre_key, const uint64_t* pre_mask, uint64_t pre_full, const uint64_t* key, const uint64_t* mask,
+                          uint64_t full, int32_t n_reads, int32_t min_alt, int32_t* out_group, int32_t* out_how, int32_t* out_counts);
+/* The definition, one segment: ioc_host_insert_windows' inputs, the reads' bytes (read i is reads[read_off[i] .. read_off[i + 1]),
+ * which must be qlen[i] long), the scoring triple and the rule.  out_win: n_sites records; out_var: n_sites records; out_variant: a
+ * byte per read and site, read-major, IOC_WINVAR_*; out_agree (may be NULL): two words per read and site, [(i n_sites + k) 2 + round],
+ * INT32_MIN where the round did not align the read; out_seq / out_qual (may be NULL, both or neither, and then out_off and
+ * out_stats are not written): the 2 n_sites slots packed with out_off (2 n_sites + 1 entries), out_stats a record per slot, cap what
+ * seq and qual hold each; out_key2 / out_mask2 per read.  IOC_ERR_ARG, with nothing written, for what ioc_host_insert_windows
+ * refuses, a scoring triple ioc_host_align_global_ops refuses, min_agree outside 1 .. 100, min_alt < 1, min_pct outside 1 .. 50,
+ * polish_min_depth < 1, read_off that does not fit qlen and a NULL pointer that is needed; IOC_ERR_CAPACITY, with nothing written,
+ * for cap below 2 n_sites (7 max_win + 6). */
+int ioc_host_insert_window_variants(const uint8_t* base, const uint32_t* qpos, const int32_t* qlen, int32_t n_reads, int32_t rlen,
+                                    const ioc_pile_insert* sites, int32_t n_sites, const uint64_t* keys, const char* reads,
+                                    const int64_t* read_off, int32_t slack, int32_t max_win, int32_t match, int32_t mismatch, int32_t gap,
+                                    int32_t polish_min_depth, int32_t min_agree, int32_t min_alt, int32_t min_pct,
+                                    ioc_insert_window* out_win, ioc_window_variant* out_var, uint8_t* out_variant, int32_t* out_agree,
+                                    char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats,
+                                    uint64_t* out_key2, uint64_t* out_mask2);
+/* Many segments at once on the device: ioc_planes_insert_windows' arguments, the rule, and pre_key / pre_mask per pair with pre_full
+ * per segment (all three or none), the block stage's.  The kernels of ioc_window_variants.hip behind those of the window stage:
+ * k_win_agree (a wave per alignment: the agreement from the voter's base plane in the template's frame as k_win_align left it,
+ * nothing is aligned or walked again), k_win_template_far (template B: k_win_template's ranking over the far voters), k_win_align
+ * again for round B, k_win_decide (a wave per site), k_win_rekey (a wave per pair) and the isoform count of ioc_read_stage.h over
+ * key2 / mask2; then k_group_pile with a group per (site, variant) and k_pile_call.  No atomics.
+ * Outputs, n = site_off[n_segs]: out_win and out_var per site; out_seq / out_qual packed with out_off (2 n + 1 entries: slot 2 x is
+ * site x's variant A, 2 x + 1 its B) and out_stats per slot; out_variant: IOC_INSERTS_MAX bytes per pair, byte k the pair's variant
+ * at site k of its segment (0 behind the segment's sites); out_agree (may be NULL): 2 IOC_INSERTS_MAX words per pair, [2 k + round];
+ * out_reads per pair (key2 and the isoform counted again) and out_seg per segment.  The refusals of ioc_planes_insert_windows and of
+ * the definition; IOC_ERR_CAPACITY, with nothing written, for cap below 2 n (7 max_win + 6).
+ * RESTRICTION: the pool's sequences are taken to hold A C G T and N alone (upper case).  k_win_agree compares channels (A C G T
+ * other), the definition compares bytes: two DIFFERENT bytes outside A C G T in one column of an alignment — 'R' against 'N', 'a'
+ * against 'c' — count as '=' on the device and as 'X' in the definition, so the device's agreement of such a pair is too high by two
+ * a column and a site may fail to split.  Nothing checks this (ioc_align_set_pool takes any bytes): a caller with IUPAC codes or
+ * lower case maps them to N first.  It holds for ioc_align_pairs_blocks_inserts_variants as well. */
+int ioc_planes_insert_window_variants(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair,
+                                      const int32_t* query, const uint8_t* base, const uint32_t* qpos, const ioc_pile_insert* sites,
+                                      const int64_t* site_off, const uint64_t* keys, int32_t slack, int32_t max_win, int32_t match,
+                                      int32_t mismatch, int32_t gap, int32_t polish_min_depth, int32_t min_agree, int32_t min_alt,
+                                      int32_t min_pct, const uint64_t* pre_key, const uint64_t* pre_mask, const uint64_t* pre_full,
+                                      ioc_insert_window* out_win, ioc_window_variant* out_var, char* out_seq, char* out_qual, int64_t cap,
+                                      int64_t* out_off, ioc_polish_stats* out_stats, uint8_t* out_variant, int32_t* out_agree,
+                                      ioc_read_variants* out_reads, ioc_variants_seg* out_seg);
+
+/* ioc_align_pairs_blocks_inserts_seq with the variant kernels behind the window kernels, over the planes where they lie.  Everything
+ * ioc_align_pairs_blocks_inserts_seq returns comes back unchanged, byte for byte — the window call's own consensus of a site, all
+ * voters voting, is one more group of the pile over round A's planes —; added are the outputs of ioc_planes_insert_window_variants
+ * over the sites kept, the block stage's keys, masks and full masks serving as pre_* and min_alt / min_pct being the searches'.
+ * var_cap must hold twice what win_cap must.  Every pair is aligned once, every voter once a round.  The refusals of both calls;
+ * nothing is written. */
+int ioc_align_pairs_blocks_inserts_variants(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                            int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                            int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                                            int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                                            ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                                            ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins, int32_t slack, int32_t max_sites,
+                                            ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap, int64_t* site_off,
+                                            ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                            int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq,
+                                            char* out_wqual, int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t min_agree,
+                                            ioc_window_variant* out_var, char* out_vseq, char* out_vqual, int64_t var_cap, int64_t* out_voff,
+                                            ioc_polish_stats* out_vstats, uint8_t* out_variant, int32_t* out_agree, ioc_read_variants* out_vreads,
+                                            ioc_variants_seg* out_vseg);
 
 /* ---- The full-length sequence of a combined isoform: the windows of the exons it carries spliced into its consensus ----
  * ioc_host_pileup_call calls an isoform in the representative's frame, where an exon the representative lacks is six slot bases at

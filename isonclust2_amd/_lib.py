@@ -122,6 +122,9 @@ BLOCKS_MAX = 32                 # IOC_BLOCKS_MAX
 INS_LACK, INS_CARRY, INS_NONE = 0, 1, 3  # IOC_INS_*
 INSERTS_MAX, INS_SLACK_MAX = 32, 32      # IOC_INSERTS_MAX, IOC_INS_SLACK_MAX
 WIN_MAX = 512                            # IOC_WIN_MAX
+INS_CARRY_B = 2                          # IOC_INS_CARRY_B
+WINVAR_NONE, WINVAR_A, WINVAR_B, WINVAR_OTHER = 0, 1, 2, 3  # IOC_WINVAR_*
+WINVAR_MIN_AGREE = 45                    # IOC_WINVAR_MIN_AGREE
 WIN_NONE, WIN_VOTER, WIN_SHORT, WIN_LONG = 0, 1, 2, 3  # IOC_WIN_*
 SPLICE_LACK, SPLICE_DONE, SPLICE_UNCALLED, SPLICE_OVERLAP = 0, 1, 2, 3  # IOC_SPLICE_*
 
@@ -255,6 +258,7 @@ SYMBOLS = [
     "ioc_host_ops_project_weights", "ioc_host_planes_pile_weighted", "ioc_planes_polish_groups_weighted", "ioc_align_pairs_blocks_polish_weighted",
     "ioc_host_ops_project_ilen", "ioc_host_planes_inserts", "ioc_planes_inserts", "ioc_align_pairs_blocks_inserts",
     "ioc_host_ops_project_qpos", "ioc_host_align_global_ops", "ioc_host_insert_windows", "ioc_planes_insert_windows", "ioc_align_pairs_blocks_inserts_seq",
+    "ioc_host_ops_agreement", "ioc_host_key_isoforms", "ioc_host_insert_window_variants", "ioc_planes_insert_window_variants", "ioc_align_pairs_blocks_inserts_variants",
     "ioc_host_isoform_splice", "ioc_planes_isoforms_full", "ioc_align_pairs_isoforms_full",
     "ioc_host_ops_extent", "ioc_host_reads_ends", "ioc_reads_ends", "ioc_align_pairs_blocks_ends",
 ]
@@ -435,6 +439,14 @@ def load():
                                             C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_blocks_inserts_seq.argtypes = L.ioc_align_pairs_blocks_inserts.argtypes + [i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, i64,
                                                                                                  pi64, C.c_void_p]
+    L.ioc_host_ops_agreement.argtypes = [C.c_char_p, i64, pi32]
+    L.ioc_host_key_isoforms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_host_insert_window_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, i32, i32, C.c_void_p, i32, C.c_void_p, C.c_char_p, C.c_void_p] + [i32] * 9 + [
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_planes_insert_window_variants.argtypes = [vp, i32, pi32, i32, pi32, pi32, C.c_void_p, C.c_void_p, C.c_void_p, pi64, C.c_void_p] + [i32] * 9 + [
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ioc_align_pairs_blocks_inserts_variants.argtypes = L.ioc_align_pairs_blocks_inserts_seq.argtypes + [i32, C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p,
+                                                                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ioc_host_isoform_splice.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, i32, i32, C.c_uint64, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, i64, C.POINTER(PolishStats), C.c_void_p, C.POINTER(SpliceStats)]
     L.ioc_host_isoform_splice.restype = C.c_int64

@@ -576,6 +576,98 @@ def insert_windows(base, qpos, qlen, sites, keys, slack=WINDOWS_RULE["slack"], m
     return {"win": win[:S], "cls": cls, "start": start, "len": ln}
 
 
+# ioc_window_variant / ioc_read_variants / ioc_variants_seg as numpy records, and the rule of a variant call beside the window rule:
+# min_agree 45 is a choice made on simulated windows (8 % errors, exons of 45 bases and more), not measured on real data
+WINDOW_VARIANT_DTYPE = np.dtype([(n, np.int32) for n in ("split", "template_pair_b", "tlen_b")] + [(n, np.uint32) for n in ("n_a", "n_b", "n_other", "n_far", "reserved")])
+READ_VARIANTS_DTYPE = np.dtype([("key2", np.uint64), ("group", np.int32), ("how", np.int32)])
+VARIANTS_SEG_DTYPE = np.dtype([(n, np.int32) for n in ("n_sites", "n_split", "n_groups", "n_reads", "n_direct", "n_assigned", "n_rare", "n_ambiguous")])
+INS_CARRY_B = _lib.INS_CARRY_B
+WINVAR_NONE, WINVAR_A, WINVAR_B, WINVAR_OTHER = _lib.WINVAR_NONE, _lib.WINVAR_A, _lib.WINVAR_B, _lib.WINVAR_OTHER
+VARIANTS_RULE = dict(min_agree=_lib.WINVAR_MIN_AGREE, min_alt=INSERTS_RULE["min_alt"], min_pct=INSERTS_RULE["min_pct"])
+NO_AGREEMENT = -2 ** 31
+
+
+def ops_agreement(ops):
+    """ioc_host_ops_agreement: #'=' - #'X' - #'D' - #'I' over the bytes of an alignment ('i' and 'd' count for nothing).  ValueError
+    for a byte outside "=XIDid"."""
+    out = C.c_int32(0)
+    rc = _lib.load().ioc_host_ops_agreement(bytes(ops), len(ops), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"ioc_host_ops_agreement failed ({rc})")
+    return int(out.value)
+
+
+def key_isoforms(key, mask, full, min_alt, pre_key=None, pre_mask=None, pre_full=0):
+    """ioc_host_key_isoforms: the isoforms of a segment's reads from two-word keys (step 9 of ioc_host_planes_inserts) — (group, how,
+    counts), counts a dict of n_groups, n_direct, n_assigned, n_rare and n_ambiguous."""
+    ky, mk = np.ascontiguousarray(key, np.uint64), np.ascontiguousarray(mask, np.uint64)
+    n = len(ky)
+    if mk.shape != (n,) or (pre_key is None) != (pre_mask is None):
+        raise ValueError("key and mask must hold one entry per read; pre_key and pre_mask: both or neither")
+    pk = None if pre_key is None else np.ascontiguousarray(pre_key, np.uint64)
+    pm = None if pre_mask is None else np.ascontiguousarray(pre_mask, np.uint64)
+    if pk is not None and (pk.shape != (n,) or pm.shape != (n,)):
+        raise ValueError("pre_key and pre_mask must hold one entry per read")
+    group, how, counts = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(5, np.int32)
+    pad = lambda a: None if a is None else np.concatenate([a, np.zeros(1, a.dtype)])
+    ky, mk, pk, pm = pad(ky), pad(mk), pad(pk), pad(pm)
+    rc = _lib.load().ioc_host_key_isoforms(pk.ctypes.data if pk is not None else None, pm.ctypes.data if pm is not None else None, int(pre_full),
+                                           ky.ctypes.data, mk.ctypes.data, int(full), n, int(min_alt), group.ctypes.data, how.ctypes.data, counts.ctypes.data)
+    if rc < 0:
+        raise IocError(int(rc), "ioc_host_key_isoforms")
+    return group[:n], how[:n], dict(zip(("n_groups", "n_direct", "n_assigned", "n_rare", "n_ambiguous"), (int(x) for x in counts)))
+
+
+def insert_window_variants_bound(n_sites, max_win=WIN_MAX):
+    """What the variants of n_sites sites may call at most, in bytes of sequence (and of qualities): two slots a site."""
+    return 2 * insert_windows_bound(n_sites, max_win)
+
+
+def _variants_rule(rule):
+    unknown = set(rule) - set(WINDOWS_RULE) - set(VARIANTS_RULE)
+    if unknown:
+        raise TypeError(f"unknown rule parameters: {sorted(unknown)}")
+    return [int({**WINDOWS_RULE, **rule}[n]) for n in WINDOWS_RULE], [int({**VARIANTS_RULE, **rule}[n]) for n in VARIANTS_RULE]
+
+
+def insert_window_variants(base, qpos, qlen, sites, keys, reads, min_depth=3, call=True, cap=None, **rule):
+    """ioc_host_insert_window_variants: the variants of one segment's kept sites — insert_windows' inputs, `reads` the reads' bytes (a
+    list), slack, max_win, match, mismatch, gap, min_agree, min_alt and min_pct as keywords (WINDOWS_RULE and VARIANTS_RULE have the
+    defaults).  Returns a dict: `win` (INSERT_WINDOW_DTYPE), `var` (WINDOW_VARIANT_DTYPE), `variant` (n_reads x n_sites bytes,
+    WINVAR_*), `agree` (n_reads x n_sites x 2, NO_AGREEMENT where a round did not align the read), `key2`, `mask2` and, with call=True,
+    `seq` / `qual` (2 n_sites slots: 2 x is site x's variant A, 2 x + 1 its B), `off` and `polish`."""
+    w, v = _variants_rule(rule)
+    base, qpos = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(qpos, np.uint32)
+    if base.ndim != 2 or base.shape[1] < 1 or qpos.shape != base.shape:
+        raise ValueError("base and qpos must hold n_reads x (rlen + 1) entries each")
+    n, rlen = base.shape[0], base.shape[1] - 1
+    ql, ky, st = np.ascontiguousarray(qlen, np.int32), np.ascontiguousarray(keys, np.uint64), np.ascontiguousarray(sites, PILE_INSERT_DTYPE)
+    if ql.shape != (n,) or ky.shape != (n,) or st.ndim != 1 or len(reads) != n:
+        raise ValueError("qlen, keys and reads must hold one entry per read")
+    S = len(st)
+    blob = b"".join(bytes(r) for r in reads) + b"\0"
+    roff = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.int64)
+    cap = insert_window_variants_bound(S, w[1]) if cap is None else int(cap)
+    win, var = np.zeros(max(S, 1), INSERT_WINDOW_DTYPE), np.zeros(max(S, 1), WINDOW_VARIANT_DTYPE)
+    variant, agree = np.zeros((n, S), np.uint8), np.zeros((n, S, 2), np.int32)
+    seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+    off, pol = np.zeros(2 * S + 1, np.int64), np.zeros(max(2 * S, 1), POLISH_STATS_DTYPE)
+    key2, mask2 = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+    pad = lambda a: np.concatenate([a.reshape(-1), np.zeros(1, a.dtype)])  # (never an empty array's pointer)
+    fb, fq, ql, ky, st, variant_f, agree_f = (pad(x) for x in (base, qpos, ql, ky, st, variant, agree))
+    rc = _lib.load().ioc_host_insert_window_variants(fb.ctypes.data, fq.ctypes.data, ql.ctypes.data, n, rlen, st.ctypes.data, S, ky.ctypes.data, blob,
+                                                     roff.ctypes.data, *w, int(min_depth), *v, win.ctypes.data, var.ctypes.data, variant_f.ctypes.data,
+                                                     agree_f.ctypes.data, seq.ctypes.data if call else None, qual.ctypes.data if call else None, cap,
+                                                     off.ctypes.data, pol.ctypes.data, key2.ctypes.data, mask2.ctypes.data)
+    if rc < 0:
+        raise IocError(int(rc), "ioc_host_insert_window_variants")
+    out = {"win": win[:S], "var": var[:S], "variant": variant_f[:-1].reshape(n, S), "agree": agree_f[:-1].reshape(n, S, 2), "key2": key2[:n], "mask2": mask2[:n]}
+    if call:
+        out.update(seq=[seq[off[x]:off[x + 1]].tobytes() for x in range(2 * S)], qual=[qual[off[x]:off[x + 1]].tobytes() for x in range(2 * S)], off=off,
+                   polish=pol[:2 * S])
+    return out
+
+
 # ioc_splice_site / ioc_splice_stats as numpy records
 SPLICE_SITE_DTYPE = np.dtype([(n, np.int32) for n in ("state", "at", "len", "reserved")])
 SPLICE_STATS_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.SpliceStats._fields_[:-1]] + [("reserved", np.int32, (3,))])
@@ -1412,10 +1504,63 @@ class Context:
             out.update(cols=cols[:row0[-1]], ins=ins[:row0[-1]], row0=row0)
         return out
 
+    def planes_insert_window_variants(self, rlen, seg_of_pair, query, base, qpos, sites, keys, min_depth=3, pre_key=None, pre_mask=None, pre_full=None, agree=True,
+                                      cap=None, site_off=None, **rule):
+        """ioc_planes_insert_window_variants: planes_insert_windows with the voters of every kept site split in two where they are two
+        exons, on the device — its arguments, pre_key / pre_mask per pair and pre_full per segment (the block stage's: all three or
+        none), and min_agree, min_alt and min_pct beside the window rule as keywords (VARIANTS_RULE has the defaults).  Returns a dict:
+        `win` (INSERT_WINDOW_DTYPE) and `var` (WINDOW_VARIANT_DTYPE; template_pair_b is the pair) per site; `seq`, `qual` and `polish`
+        per slot (2 x: site x's variant A, 2 x + 1: its B, empty where the site does not split) with `off`; `variant` (n_pairs x 32
+        bytes, WINVAR_*: byte k the pair's variant at site k of its segment) and, with agree=True, `agree` (n_pairs x 32 x 2,
+        NO_AGREEMENT where a round did not align the pair); `reads` (READ_VARIANTS_DTYPE: key2 and the isoform counted again) and `seg`
+        (VARIANTS_SEG_DTYPE)."""
+        w, v = _variants_rule(rule)
+        ns, n = len(rlen), len(base)
+        rl, sop, qy, ky = (np.ascontiguousarray(x, t) for x, t in ((rlen, np.int32), (seg_of_pair, np.int32), (query, np.int32), (keys, np.uint64)))
+        if sop.shape != (n,) or qy.shape != (n,) or ky.shape != (n,) or len(qpos) != n:
+            raise ValueError("seg_of_pair, query, keys, base and qpos must hold one entry per pair")
+        want = [int(rl[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (want[i],) or np.shape(qpos[i]) != (want[i],):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        fb = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(b, np.uint8) for b in base]))
+        fq = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint32)] + [np.asarray(b, np.uint32) for b in qpos]))
+        if site_off is None:
+            soff = np.concatenate([[0], np.cumsum([len(s) for s in sites])]).astype(np.int64)
+            st = np.ascontiguousarray(np.concatenate([np.zeros(0, PILE_INSERT_DTYPE)] + [np.asarray(s, PILE_INSERT_DTYPE) for s in sites]))
+        else:
+            soff, st = np.ascontiguousarray(site_off, np.int64), np.ascontiguousarray(sites, PILE_INSERT_DTYPE)
+        if soff.shape != (ns + 1,):
+            raise ValueError("the sites must hold one array per segment")
+        pre = [None if x is None else np.ascontiguousarray(x, np.uint64) for x in (pre_key, pre_mask, pre_full)]
+        if any(x is not None for x in pre) and (any(x is None for x in pre) or pre[0].shape != (n,) or pre[1].shape != (n,) or pre[2].shape != (ns,)):
+            raise ValueError("pre_key and pre_mask per pair and pre_full per segment: all three or none")
+        S = max(int(soff[-1]), 0)
+        cap = insert_window_variants_bound(S, w[1]) if cap is None else int(cap)
+        win, var = np.zeros(max(S, 1), INSERT_WINDOW_DTYPE), np.zeros(max(S, 1), WINDOW_VARIANT_DTYPE)
+        off, pol = np.zeros(2 * S + 1, np.int64), np.zeros(max(2 * S, 1), POLISH_STATS_DTYPE)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        variant, agr = np.zeros((max(n, 1), _lib.INSERTS_MAX), np.uint8), np.zeros((max(n, 1), _lib.INSERTS_MAX, 2), np.int32)
+        reads, seg = np.zeros(max(n, 1), READ_VARIANTS_DTYPE), np.zeros(max(ns, 1), VARIANTS_SEG_DTYPE)
+        pad = lambda a: np.concatenate([a, np.zeros(1, a.dtype)])  # (never an empty array's pointer)
+        st, ky, qy, sop, fb, fq = (pad(x) for x in (st, ky, qy, sop, fb, fq))
+        pre = [None if x is None else pad(x) for x in pre]
+        self._chk(self.L.ioc_planes_insert_window_variants(self.h, ns, _p(rl, C.c_int32) if ns else None, n, _p(sop, C.c_int32), _p(qy, C.c_int32), fb.ctypes.data,
+                                                           fq.ctypes.data, st.ctypes.data, _p(soff, C.c_int64), ky.ctypes.data, *w, int(min_depth), *v,
+                                                           *(None if x is None else x.ctypes.data for x in pre), win.ctypes.data, var.ctypes.data,
+                                                           seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64), pol.ctypes.data, variant.ctypes.data,
+                                                           agr.ctypes.data if agree else None, reads.ctypes.data, seg.ctypes.data))
+        out = {"win": win[:S], "var": var[:S], "seq": [seq[off[x]:off[x + 1]].tobytes() for x in range(2 * S)],
+               "qual": [qual[off[x]:off[x + 1]].tobytes() for x in range(2 * S)], "off": off, "polish": pol[:2 * S], "variant": variant[:n], "reads": reads[:n],
+               "seg": seg[:ns]}
+        if agree:
+            out["agree"] = agr[:n]
+        return out
+
     def align_pairs_blocks_inserts_seq(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, sites_cap=None, win_cap=None, match=2,
                                        mismatch=-2, gap_extend=1, min_ins=INSERTS_RULE["min_ins"], slack=INSERTS_RULE["slack"],
                                        max_sites=INSERTS_RULE["max_sites"], max_win=WIN_MAX, win_match=WINDOWS_RULE["match"],
-                                       win_mismatch=WINDOWS_RULE["mismatch"], win_gap=WINDOWS_RULE["gap"], polish_min_depth=3, _full=None, **rule):
+                                       win_mismatch=WINDOWS_RULE["mismatch"], win_gap=WINDOWS_RULE["gap"], polish_min_depth=3, _full=None, _variants=None, **rule):
         """ioc_align_pairs_blocks_inserts_seq: align_pairs_blocks_inserts with every pair's position plane projected as well and the
         window kernels behind the insert kernels, on the device, every pair aligned once.  Returns align_pairs_blocks_inserts' dict,
         byte for byte, and under `insert_windows` what Context.planes_insert_windows returns (without tables) for the sites kept."""
@@ -1446,6 +1591,15 @@ class Context:
             entry = self.L.ioc_align_pairs_isoforms_full
             more = (int(_full["max_iso"]), f_seq.ctypes.data, f_qual.ctypes.data, f_cap, _p(f_off, C.c_int64), f_pol.ctypes.data, f_sst.ctypes.data,
                     f_splice.ctypes.data, f_rec, _p(f_spoff, C.c_int64), f_iso, _p(f_ioff, C.c_int64))
+        if _variants is not None:   # (align_pairs_blocks_inserts_variants: the same call with the variants' outputs behind it)
+            v_cap = insert_window_variants_bound(S, max_win) if _variants["cap"] is None else int(_variants["cap"])
+            v_var, v_off, v_pol = np.zeros(max(S, 1), WINDOW_VARIANT_DTYPE), np.zeros(2 * S + 1, np.int64), np.zeros(max(2 * S, 1), POLISH_STATS_DTYPE)
+            v_seq, v_qual = np.zeros(max(v_cap, 1), np.uint8), np.zeros(max(v_cap, 1), np.uint8)
+            v_variant, v_agree = np.zeros((max(n, 1), _lib.INSERTS_MAX), np.uint8), np.zeros((max(n, 1), _lib.INSERTS_MAX, 2), np.int32)
+            v_reads, v_seg = np.zeros(max(n, 1), READ_VARIANTS_DTYPE), np.zeros(max(ns, 1), VARIANTS_SEG_DTYPE)
+            entry = self.L.ioc_align_pairs_blocks_inserts_variants
+            more = (int(_variants["min_agree"]), v_var.ctypes.data, v_seq.ctypes.data, v_qual.ctypes.data, v_cap, _p(v_off, C.c_int64), v_pol.ctypes.data,
+                    v_variant.ctypes.data, v_agree.ctypes.data, v_reads.ctypes.data, v_seg.ctypes.data)
         self._chk(entry(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
                                                             _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
                                                             _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
@@ -1458,6 +1612,10 @@ class Context:
         out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
                "inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg),
                "insert_windows": self._windows_dict(wrec[:kept], wseq, wqual, woff[:kept + 1], wpol[:kept])}
+        if _variants is not None:
+            out["insert_variants"] = {"win": wrec[:kept], "var": v_var[:kept], "seq": [v_seq[v_off[x]:v_off[x + 1]].tobytes() for x in range(2 * kept)],
+                                      "qual": [v_qual[v_off[x]:v_off[x + 1]].tobytes() for x in range(2 * kept)], "off": v_off[:2 * kept + 1], "polish": v_pol[:2 * kept],
+                                      "variant": v_variant[:n], "agree": v_agree[:n], "reads": v_reads[:n], "seg": v_seg[:ns]}
         if _full is not None:
             G = int(f_ioff[ns])
             out["isoforms_full"] = {**self._groups_out(f_ioff, f_seq, f_qual, f_off, f_pol[:G]), "off": f_off[:G + 1], "sstats": f_sst[:G],
@@ -1467,6 +1625,13 @@ class Context:
         if tables:
             out.update(cols=cols, row0=self._row0(rlen))
         return out
+
+    def align_pairs_blocks_inserts_variants(self, pairs, k, segs, seg_of_pair, min_agree=VARIANTS_RULE["min_agree"], var_cap=None, **kw):
+        """ioc_align_pairs_blocks_inserts_variants: align_pairs_blocks_inserts_seq with the variant kernels behind the window kernels —
+        two exons at one junction told apart, every read re-keyed and the isoforms counted again, every pair aligned once.  Returns
+        align_pairs_blocks_inserts_seq's dict, byte for byte, and under `insert_variants` what Context.planes_insert_window_variants
+        returns for the sites kept, the block stage's keys serving as pre_*; min_alt and min_pct are the searches'."""
+        return self.align_pairs_blocks_inserts_seq(pairs, k, segs, seg_of_pair, _variants=dict(min_agree=min_agree, cap=var_cap), **kw)
 
     def align_pairs_isoforms_full(self, pairs, k, segs, seg_of_pair, max_iso=16, full_cap=None, iso_cap=None, splice_cap=None, **kw):
         """ioc_align_pairs_isoforms_full: align_pairs_blocks_inserts_seq with the six slot planes projected as well and, behind the

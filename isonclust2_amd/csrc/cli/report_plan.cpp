@@ -278,6 +278,19 @@ string read_insert_columns(const ioc_read_inserts& r, int32_t n_sites)
     return inserts_signature(r.key, n_sites) + '\t' + (r.group < 0 ? string(".") : std::to_string(r.group)) + '\t' + how;
 }
 
+string variants_signature(uint64_t key2, int32_t n_sites)
+{
+    string text;
+    for (int32_t b = 0; b < n_sites && b < IOC_INSERTS_MAX; ++b) text += "=AB."[(key2 >> (2 * b)) & 3u];
+    return text.empty() ? "*" : text;
+}
+
+string read_variant_columns(const ioc_read_variants& r, int32_t n_sites)
+{
+    const char* const how = r.how == IOC_ISO_DIRECT ? "direct" : r.how == IOC_ISO_ASSIGNED ? "assigned" : r.how == IOC_ISO_RARE ? "rare" : "ambiguous";
+    return variants_signature(r.key2, n_sites) + '\t' + (r.group < 0 ? string(".") : std::to_string(r.group)) + '\t' + how;
+}
+
 EndsCapacity ends_capacity(const ReportGroup& g, int max_sites, int max_variants)
 {
     EndsCapacity cap;

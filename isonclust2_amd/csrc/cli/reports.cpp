@@ -150,6 +150,15 @@ struct GroupResult {
     std::vector<int64_t> win_off;            // [win_off[s], win_off[s + 1]) of wseq / wqual
     std::vector<ioc_polish_stats> win_stats;
     string wseq, wqual;
+    // (--isoforms-inserts-variants) per kept site its record and its two slots, slot 2 s + h at [vslot_off[2 s + h], vslot_off[2 s + h + 1]) of vseq /
+    // vqual; per pair its variant bytes (IOC_INSERTS_MAX each) and its record; per segment its record
+    std::vector<ioc_window_variant> win_variants;
+    std::vector<int64_t> vslot_off;
+    std::vector<ioc_polish_stats> var_stats;
+    string vseq, vqual;
+    std::vector<uint8_t> variant;
+    std::vector<ioc_read_variants> read_variants;
+    std::vector<ioc_variants_seg> variants_seg;
     // (--isoforms-full) per called combined isoform, segment g's at [full_off[g], full_off[g + 1]): its bytes at [fseq_off[x], fseq_off[x + 1]) of
     // fseq / fqual (room for the bound, written up to fseq_off's last entry), its records, and its site records from fsplice_off[x] on
     std::unique_ptr<char[]> fseq, fqual;
@@ -175,6 +184,8 @@ struct RowResult {
     int32_t iso_blocks = 0;
     ioc_read_inserts ins{};          // (--isoforms-inserts) the read's record, and how many sites its cluster kept
     int32_t ins_sites = 0;
+    ioc_read_variants var{0, -1, 0};  // (--isoforms-inserts-variants) the read's record and its variant at every kept site
+    string variants;
     ioc_read_extent extent{};        // (--isoforms-ends) the read's extent and its record
     ioc_read_ends ends{-1, -1, -1, 0};
 };
@@ -317,6 +328,21 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
                                                            io.full_max, r.fseq.get(), r.fqual.get(), fcap.bytes, r.fseq_off.data(), r.fstats.data(), nullptr,
                                                            r.fsplice.data(), int64_t(r.fsplice.size()), r.fsplice_off.data(), fcap.isoforms, r.full_off.data()),
                           "exon blocks with the insertion sites, their sequences and the isoforms' full-length sequences");
+                } else if (io.variants) {
+                    r.win_variants.assign(size_t(std::max<int64_t>(icap, 1)), ioc_window_variant{}), r.vslot_off.assign(2 * size_t(icap) + 1, 0);
+                    r.var_stats.assign(size_t(std::max<int64_t>(2 * icap, 1)), ioc_polish_stats{});
+                    r.vseq.assign(size_t(std::max<int64_t>(2 * wcap, 1)), '\0'), r.vqual.assign(size_t(std::max<int64_t>(2 * wcap, 1)), '\0');
+                    r.variant.assign(np * size_t(IOC_INSERTS_MAX), 0), r.read_variants.assign(np, ioc_read_variants{}), r.variants_seg.assign(ns, ioc_variants_seg{});
+                    check(c, ioc_align_pairs_blocks_inserts_variants(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
+                                                                     g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks,
+                                                                     nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
+                                                                     o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
+                                                                     r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(),
+                                                                     io.ins_max_win, 2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(),
+                                                                     r.win_stats.data(), io.variants_min_agree, r.win_variants.data(), &r.vseq[0], &r.vqual[0], 2 * wcap,
+                                                                     r.vslot_off.data(), r.var_stats.data(), r.variant.data(), nullptr, r.read_variants.data(),
+                                                                     r.variants_seg.data()),
+                          "exon blocks with the insertion sites, their sequences and their variants");
                 } else
                 check(c, ioc_align_pairs_blocks_inserts_seq(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
                                                             g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
@@ -378,6 +404,11 @@ void scatter_to_rows(const ReportOpts& o, const ReportRows& rows, const ReportGr
         }
         if (o.isoforms.on) row.iso = r.read_blocks[x], row.iso_blocks = r.blocks_seg[size_t(g.seg_of_pair[x])].n_blocks;
         if (o.isoforms.on && o.isoforms.inserts) row.ins = r.read_inserts[x], row.ins_sites = r.inserts_seg[size_t(g.seg_of_pair[x])].n_sites;
+        if (o.isoforms.on && o.isoforms.inserts && o.isoforms.variants) {
+            row.var = r.read_variants[x];
+            row.variants.clear();
+            for (int32_t b = 0; b < row.ins_sites && b < IOC_INSERTS_MAX; ++b) row.variants += ".ABo"[r.variant[x * size_t(IOC_INSERTS_MAX) + size_t(b)] & 3u];
+        }
         if (o.isoforms.on && o.isoforms.ends) row.extent = r.extents[x], row.ends = r.read_ends[x];
         if (o.correct.on) {
             const ReadStatRow& rd = rows.row(g.pair_row[x]);
@@ -555,6 +586,32 @@ void write_insert_windows(std::ofstream& out, const ReportRows& rows, const Repo
     }
 }
 
+// cluster_insert_variants.fq: a record per called variant of a site, "@cluster_<id>/ins<b>/<A|B> rows=<lo>-<hi> voters=<n> template=<read>
+// split=<0|1>" — variant A is the one of the site's template, and the only one where the site does not split
+void write_insert_variants(std::ofstream& out, const ReportRows& rows, const ReportGroup& g, const GroupResult& r)
+{
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0) continue;
+        for (int64_t a = r.insert_off[size_t(s)]; a < r.insert_off[size_t(s) + 1]; ++a) {
+            const ioc_insert_window& w = r.ins_windows[size_t(a)];
+            const ioc_window_variant& v = r.win_variants[size_t(a)];
+            for (int h = 0; h < 2; ++h) {
+                const int64_t b0 = r.vslot_off[2 * size_t(a) + size_t(h)], b1 = r.vslot_off[2 * size_t(a) + size_t(h) + 1];
+                const int32_t pair = h ? v.template_pair_b : w.template_pair;
+                if (b1 <= b0 || pair < 0 || size_t(pair) >= g.pair_row.size()) continue;
+                const ReadStatRow& rd = rows.row(g.pair_row[size_t(pair)]);
+                out << "@cluster_" << g.group_cls[x].first << "/ins" << a - r.insert_off[size_t(s)] << '/' << "AB"[h] << " rows=" << w.lo << '-' << w.hi
+                    << " voters=" << (h ? v.n_b : v.n_a) << " template=" << string(rd.id, rd.id_len) << " split=" << v.split << '\n';
+                out.write(r.vseq.data() + b0, std::streamsize(b1 - b0));
+                out << "\n+\n";
+                out.write(r.vqual.data() + b0, std::streamsize(b1 - b0));
+                out << '\n';
+            }
+        }
+    }
+}
+
 // cluster_isoforms_full.fq: a record per called combined isoform of every cluster that has a block or a site
 void write_isoforms_full(std::ofstream& out, const ReportGroup& g, const GroupResult& r)
 {
@@ -587,7 +644,7 @@ void write_isoforms_full(std::ofstream& out, const ReportGroup& g, const GroupRe
 
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq, full_fq, ends, end_variants;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq, variants_fq, full_fq, ends, end_variants;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -616,6 +673,7 @@ struct GroupFiles {
             inserts << "ClusterId\tFirst\tEnd\tCarry\tLack\tNone\tLenMin\tLenMax\n";
             if (o.isoforms.inserts_seq) create_file(outdir + "/cluster_inserts.fq", inserts_fq);
             if (o.isoforms.inserts_seq && o.isoforms.full) create_file(outdir + "/cluster_isoforms_full.fq", full_fq);
+            if (o.isoforms.inserts_seq && o.isoforms.variants) create_file(outdir + "/cluster_insert_variants.fq", variants_fq);
         }
         if (o.isoforms.on && o.isoforms.ends) {
             create_file(outdir + "/cluster_ends.tsv", ends);
@@ -636,6 +694,7 @@ struct GroupFiles {
         if (o.isoforms.on && o.isoforms.ends && !g.segs.empty() && !g.pairs.empty()) write_ends(ends, end_variants, g, r);
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && !g.segs.empty() && !g.pairs.empty()) write_insert_windows(inserts_fq, rows, g, r);
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && o.isoforms.full && !g.segs.empty() && !g.pairs.empty()) write_isoforms_full(full_fq, g, r);
+        if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && o.isoforms.variants && !g.segs.empty() && !g.pairs.empty()) write_insert_variants(variants_fq, rows, g, r);
     }
 };
 
@@ -687,6 +746,20 @@ void write_read_inserts(const string& outdir, const ReportRows& rows, const std:
         out << r.cls << '\t';
         out.write(r.id, std::streamsize(r.id_len));
         out << '\t' << read_insert_columns(res[y].ins, res[y].ins_sites) << '\n';
+    }
+}
+
+// read_insert_variants.tsv: one row per row read_inserts.tsv has, in that order
+void write_read_insert_variants(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/read_insert_variants.tsv", out);
+    out << "ClusterId\tRead\tVariants\tInserts\tIsoform\tHow\n";
+    for (size_t y = 0; y < rows.kept.size(); ++y) {
+        const ReadStatRow& r = rows.row(y);
+        out << r.cls << '\t';
+        out.write(r.id, std::streamsize(r.id_len));
+        out << '\t' << (res[y].variants.empty() ? string("*") : res[y].variants) << '\t' << read_variant_columns(res[y].var, res[y].ins_sites) << '\n';
     }
 }
 
@@ -753,5 +826,6 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
     if (opts.correct.on) write_corrected_reads(outdir, res);
     if (opts.isoforms.on) write_read_isoforms(outdir, rows, res);
     if (opts.isoforms.on && opts.isoforms.inserts) write_read_inserts(outdir, rows, res);
+    if (opts.isoforms.on && opts.isoforms.inserts && opts.isoforms.variants) write_read_insert_variants(outdir, rows, res);
     if (opts.isoforms.on && opts.isoforms.ends) write_read_ends(outdir, rows, res);
 }

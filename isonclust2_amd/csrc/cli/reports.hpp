@@ -35,6 +35,8 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     int min_ins = 20, ins_slack = 8, ins_max = 32;   // ... the thresholds of ioc_host_planes_inserts the block search does not share
     bool inserts_seq = false;                        // --isoforms-inserts-seq: the consensus of the carriers' windows at every kept site as well
     int ins_max_win = IOC_WIN_MAX;                   // (ioc_align_pairs_blocks_inserts_seq), and the longest window that votes
+    bool variants = false;                           // --isoforms-inserts-variants: two exons at one junction told apart as well
+    int variants_min_agree = IOC_WINVAR_MIN_AGREE;   // (ioc_align_pairs_blocks_inserts_variants), and the agreement a voter is near a template at
     bool full = false;                               // --isoforms-full: every combined isoform's full-length sequence as well
     int full_max = 16;                               // (ioc_align_pairs_isoforms_full), and how many isoforms of a cluster are called
     bool ends = false;                               // --isoforms-ends: the alternative ends as well (ioc_align_pairs_blocks_ends), and the
@@ -139,6 +141,9 @@ std::string inserts_signature(uint64_t key, int32_t n_sites);
 std::string cluster_inserts_rows(size_t cluster, const ioc_inserts_seg& z, const ioc_pile_insert* sites);
 // the columns of read_inserts.tsv behind the cluster and the read: "<signature> <combined isoform or .> <direct|assigned|rare|ambiguous>"
 std::string read_insert_columns(const ioc_read_inserts& r, int32_t n_sites);
+// ... of read_insert_variants.tsv: the signature with the variants told apart ('=' lack, 'A' / 'B' carry, '.' not across or unknown), and the columns behind it
+std::string variants_signature(uint64_t key2, int32_t n_sites);
+std::string read_variant_columns(const ioc_read_variants& r, int32_t n_sites);
 // the end sites (start and stop sites together) and the variants a search for ends may keep at most, for all segments of a group:
 // 2 min(max_sites, the representative's length + 1) and min(max_variants, its reads) each
 struct EndsCapacity {

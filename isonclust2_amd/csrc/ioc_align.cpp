@@ -24,6 +24,8 @@
 #include "ioc_read_inserts.h"
 #include "ioc_read_ends.h"
 #include "ioc_insert_windows.h"
+#include "ioc_window_variants.h"
+#include "ioc_sink_plan.h"
 #include "ioc_iso_splice.h"
 #include "ioc_read_correct.h"
 #include "ioc_site_split.h"
@@ -915,6 +917,61 @@ int ioc_host_ops_project_ilen(const char* ops, int64_t len, int32_t rlen, uint8_
     return IOC_OK;
 }
 
+// The isoforms of a segment's reads from two-word keys (isonclust2_hip.h has the rules: step 9 of ioc_host_planes_inserts, which
+// ioc_host_insert_window_variants takes again over key2): the supported pairs of words in ascending unsigned order, and every
+// read's group and how it came to it.  pre_key NULL: the major word, its mask and pre_full are 0.
+namespace {
+struct KeyCounts { int32_t n_groups, n_direct, n_assigned, n_rare, n_ambiguous; };
+KeyCounts host_key_isoforms(const uint64_t* pre_key, const uint64_t* pre_mask, uint64_t pre_full, const uint64_t* key, const uint64_t* mask, uint64_t full, size_t n,
+                            int32_t min_alt, int32_t* group, int32_t* how)
+{
+    if (!pre_key) pre_full = 0;
+    auto pk = [&](size_t i) { return pre_key ? pre_key[i] : uint64_t(0); };
+    auto pm = [&](size_t i) { return pre_key ? pre_mask[i] : uint64_t(0); };
+    typedef std::pair<uint64_t, uint64_t> Key;  // (the block stage's word, this stage's: compared in that order, unsigned)
+    std::vector<Key> complete, keys;
+    auto is_complete = [&](size_t i) { return mask[i] == full && pm(i) == pre_full; };
+    for (size_t i = 0; i < n; ++i)
+        if (is_complete(i)) complete.push_back(Key(pk(i), key[i]));
+    std::sort(complete.begin(), complete.end());
+    for (size_t a = 0; a < complete.size();) {
+        size_t e = a;
+        while (e < complete.size() && complete[e] == complete[a]) ++e;
+        if (e - a >= size_t(min_alt)) keys.push_back(complete[a]);
+        a = e;
+    }
+    KeyCounts kc{int32_t(keys.size()), 0, 0, 0, 0};
+    for (size_t i = 0; i < n; ++i) {
+        group[i] = -1, how[i] = 0;
+        if (is_complete(i)) {
+            const auto it = std::lower_bound(keys.begin(), keys.end(), Key(pk(i), key[i]));
+            if (it != keys.end() && *it == Key(pk(i), key[i]))
+                group[i] = int32_t(it - keys.begin()), how[i] = IOC_ISO_DIRECT, ++kc.n_direct;
+            else
+                how[i] = IOC_ISO_RARE, ++kc.n_rare;
+            continue;
+        }
+        int32_t agreeing = 0, which = -1;
+        for (size_t k = 0; k < keys.size() && (mask[i] | pm(i)) != 0ull; ++k)
+            if (inserts_key_agrees(pk(i), key[i], keys[k].first, keys[k].second, pm(i), mask[i])) ++agreeing, which = int32_t(k);
+        if (agreeing == 1)
+            group[i] = which, how[i] = IOC_ISO_ASSIGNED, ++kc.n_assigned;
+        else
+            how[i] = IOC_ISO_AMBIGUOUS, ++kc.n_ambiguous;
+    }
+    return kc;
+}
+}  // namespace
+
+int ioc_host_key_isoforms(const uint64_t* pre_key, const uint64_t* pre_mask, uint64_t pre_full, const uint64_t* key, const uint64_t* mask, uint64_t full,
+                          int32_t n_reads, int32_t min_alt, int32_t* out_group, int32_t* out_how, int32_t* out_counts)
+{
+    if (n_reads < 0 || min_alt < 1 || !out_counts || (n_reads > 0 && (!key || !mask || !out_group || !out_how)) || (n_reads > 0 && !pre_key != !pre_mask)) return IOC_ERR_ARG;
+    const KeyCounts kc = host_key_isoforms(pre_key, pre_mask, pre_full, key, mask, full, size_t(n_reads), min_alt, out_group, out_how);
+    out_counts[0] = kc.n_groups, out_counts[1] = kc.n_direct, out_counts[2] = kc.n_assigned, out_counts[3] = kc.n_rare, out_counts[4] = kc.n_ambiguous;
+    return IOC_OK;
+}
+
 // The insertion sites of one segment and every read's combined isoform (isonclust2_hip.h has the rules; InsertsRule::variable,
 // inserts_state, inserts_key_agrees and inserts_key_less, ioc_read_inserts.h, decide for this function and for the kernels of
 // ioc_read_inserts.hip alike).  The plain loops: every read's spans and windowed sums, the row table, the runs of variable
@@ -929,8 +986,6 @@ int ioc_host_planes_inserts(const uint8_t* base, const uint8_t* ilen, int32_t n_
         return IOC_ERR_ARG;
     const size_t rows = size_t(rlen) + 1, n = size_t(n_reads);
     if (!pre_key) pre_full = 0;
-    auto pk = [&](size_t i) { return pre_key ? pre_key[i] : uint64_t(0); };
-    auto pm = [&](size_t i) { return pre_key ? pre_mask[i] : uint64_t(0); };
     auto spans = [&](size_t i, int32_t p) { return p >= 1 && p <= rlen - 1 && blocks_covers(base[i * rows + size_t(p) - 1]) && blocks_covers(base[i * rows + size_t(p)]); };
     auto window = [&](size_t i, int32_t p) {
         uint32_t w = 0;
@@ -971,38 +1026,12 @@ int ioc_host_planes_inserts(const uint8_t* base, const uint8_t* ilen, int32_t n_
             ++(st == IOC_INS_CARRY ? t.n_carry : st == IOC_INS_LACK ? t.n_lack : t.n_none);
             if (st == IOC_INS_CARRY) t.len_min = t.n_carry == 1u ? longest : std::min(t.len_min, longest), t.len_max = std::max(t.len_max, longest);
         }
-    typedef std::pair<uint64_t, uint64_t> Key;  // (the block stage's word, this stage's: compared in that order, unsigned)
-    std::vector<Key> complete, keys;
-    auto is_complete = [&](size_t i) { return mask[i] == full && pm(i) == pre_full; };
-    for (size_t i = 0; i < n; ++i)
-        if (is_complete(i)) complete.push_back(Key(pk(i), reads[i].key));
-    std::sort(complete.begin(), complete.end());
-    for (size_t a = 0; a < complete.size();) {
-        size_t e = a;
-        while (e < complete.size() && complete[e] == complete[a]) ++e;
-        if (e - a >= size_t(min_alt)) keys.push_back(complete[a]);
-        a = e;
-    }
-    ioc_inserts_seg seg{int32_t(ns), n_found, int32_t(keys.size()), n_reads, 0, 0, 0, 0};
-    for (size_t i = 0; i < n; ++i) {
-        ioc_read_inserts& rd = reads[i];
-        rd.group = -1;
-        if (is_complete(i)) {
-            const auto it = std::lower_bound(keys.begin(), keys.end(), Key(pk(i), rd.key));
-            if (it != keys.end() && *it == Key(pk(i), rd.key))
-                rd.group = int32_t(it - keys.begin()), rd.how = IOC_ISO_DIRECT, ++seg.n_direct;
-            else
-                rd.how = IOC_ISO_RARE, ++seg.n_rare;
-            continue;
-        }
-        int32_t agreeing = 0, which = -1;
-        for (size_t k = 0; k < keys.size() && (mask[i] | pm(i)) != 0ull; ++k)
-            if (inserts_key_agrees(pk(i), rd.key, keys[k].first, keys[k].second, pm(i), mask[i])) ++agreeing, which = int32_t(k);
-        if (agreeing == 1)
-            rd.group = which, rd.how = IOC_ISO_ASSIGNED, ++seg.n_assigned;
-        else
-            rd.how = IOC_ISO_AMBIGUOUS, ++seg.n_ambiguous;
-    }
+    std::vector<uint64_t> key(n), msk(mask.begin(), mask.end());
+    std::vector<int32_t> group(n), how(n);
+    for (size_t i = 0; i < n; ++i) key[i] = reads[i].key;
+    const KeyCounts kc = host_key_isoforms(pre_key, pre_mask, pre_full, key.data(), msk.data(), full, n, min_alt, group.data(), how.data());
+    for (size_t i = 0; i < n; ++i) reads[i].group = group[i], reads[i].how = how[i];
+    const ioc_inserts_seg seg{int32_t(ns), n_found, kc.n_groups, n_reads, kc.n_direct, kc.n_assigned, kc.n_rare, kc.n_ambiguous};
     if (out_rows) std::copy(table.begin(), table.end(), out_rows);
     std::copy(sites.begin(), sites.end(), out_sites);
     std::copy(reads.begin(), reads.end(), out_reads);
@@ -1103,6 +1132,146 @@ int ioc_host_insert_windows(const uint8_t* base, const uint32_t* qpos, const int
         }
         out_win[k] = w;
     }
+    return IOC_OK;
+}
+
+// The agreement of an alignment (isonclust2_hip.h has the rule; winvar_agreement, ioc_window_variants.h, decides for this function
+// and for k_win_agree alike).
+int ioc_host_ops_agreement(const char* ops, int64_t len, int32_t* out)
+{
+    if (len < 0 || len > INT32_MAX || (len > 0 && !ops) || !out) return IOC_ERR_ARG;
+    uint32_t eq = 0, x = 0, d = 0, in = 0;
+    for (int64_t a = 0; a < len; ++a) {
+        const char op = ops[a];
+        if (!strchr("=XIDid", op) || op == 0) return IOC_ERR_ARG;
+        eq += op == '=', x += op == 'X', d += op == 'D', in += op == 'I';
+    }
+    *out = winvar_agreement(eq, x, d, in);
+    return IOC_OK;
+}
+
+// The variants of one segment's kept sites (isonclust2_hip.h has the rules; winvar_near, winvar_round_b, winvar_splits,
+// winvar_variant and winvar_state, ioc_window_variants.h, decide for this function and for the kernels of ioc_window_variants.hip
+// alike).  The plain loops: the windows, round A, round B, the decision, a consensus per slot by the calls that exist, and key2.
+int ioc_host_insert_window_variants(const uint8_t* base, const uint32_t* qpos, const int32_t* qlen, int32_t n_reads, int32_t rlen, const ioc_pile_insert* sites,
+                                    int32_t n_sites, const uint64_t* keys, const char* reads, const int64_t* read_off, int32_t slack, int32_t max_win, int32_t match,
+                                    int32_t mismatch, int32_t gap, int32_t polish_min_depth, int32_t min_agree, int32_t min_alt, int32_t min_pct,
+                                    ioc_insert_window* out_win, ioc_window_variant* out_var, uint8_t* out_variant, int32_t* out_agree, char* out_seq, char* out_qual,
+                                    int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats, uint64_t* out_key2, uint64_t* out_mask2)
+{
+    const WinRule wrule{slack, max_win, match, mismatch, gap};
+    const WinVarRule rule{min_agree, min_alt, min_pct};
+    const bool live = n_reads > 0 && n_sites > 0, call = out_seq != nullptr;
+    if (!wrule.ok() || !rule.ok() || polish_min_depth < 1 || n_reads < 0 || rlen < 0 || n_sites < 0 || n_sites > IOC_INSERTS_MAX || cap < 0 || !out_seq != !out_qual ||
+        (call && (!out_off || (n_sites > 0 && !out_stats))) || (n_sites > 0 && (!sites || !out_win || !out_var)) ||
+        (live && (!base || !qpos || !qlen || !out_variant || !reads || !read_off)) ||
+        (n_reads > 0 && (!keys || !out_key2 || !out_mask2)))
+        return IOC_ERR_ARG;
+    for (int32_t i = 0; i < n_reads && live; ++i)
+        if (qlen[i] < 0 || read_off[i + 1] - read_off[i] != int64_t(qlen[i])) return IOC_ERR_ARG;
+    const size_t n = size_t(n_reads), S = size_t(n_sites);
+    std::vector<ioc_insert_window> win(S);
+    std::vector<uint8_t> cls(n * S);
+    std::vector<uint32_t> start(n * S), len(n * S);
+    if (const int st = ioc_host_insert_windows(base, qpos, qlen, n_reads, rlen, sites, n_sites, keys, slack, max_win, win.data(), cls.data(), start.data(), len.data()))
+        return st;
+    if (call && cap < 2 * int64_t(S) * pile_call_most(max_win)) return IOC_ERR_CAPACITY;
+
+    std::vector<ioc_window_variant> var(S, ioc_window_variant{0, -1, 0, 0, 0, 0, 0, 0});
+    std::vector<uint8_t> variant(n * S, uint8_t(IOC_WINVAR_NONE));
+    std::vector<int32_t> agree(n * S * 2, INT32_MIN);
+    std::vector<uint64_t> key2(n), mask2(n, 0);
+    std::string seq, qual;
+    std::vector<int64_t> off{0};
+    std::vector<ioc_polish_stats> stats;
+    auto window = [&](size_t i, size_t k) { return reads + read_off[i] + start[i * S + k]; };
+    // one round at site k: every listed voter against the template t; the flag of each, and its alignment's bytes kept for the call
+    std::vector<std::string> kept[2];
+    auto round = [&](size_t k, const std::vector<size_t>& who, size_t t, int which, std::vector<uint8_t>& flag) {
+        const int32_t tlen = int32_t(len[t * S + k]);
+        kept[which].assign(n, std::string());
+        for (const size_t i : who) {
+            const int32_t ql = int32_t(len[i * S + k]);
+            std::string& ops = kept[which][i];
+            ops.assign(size_t(ql) + size_t(tlen), 0);
+            const int64_t L = ioc_host_align_global_ops(window(i, k), ql, window(t, k), tlen, match, mismatch, gap, &ops[0], int64_t(ops.size()), nullptr);
+            ops.resize(size_t(L));
+            int32_t a = 0;
+            ioc_host_ops_agreement(ops.data(), L, &a);
+            agree[(i * S + k) * 2 + size_t(which)] = a;
+            flag[i] = winvar_near(a, uint32_t(ql), uint32_t(tlen), min_agree) ? WINVAR_NEAR : WINVAR_FAR;
+        }
+    };
+    // a slot's consensus: the voters listed, as round `which` aligned them to the template t, projected, piled and called
+    auto consensus = [&](size_t k, const std::vector<size_t>& who, size_t t, int which) {
+        const int32_t tlen = int32_t(len[t * S + k]);
+        const size_t rows = size_t(tlen) + 1;
+        std::vector<ioc_pileup_col> cols(rows, ioc_pileup_col{});
+        std::vector<ioc_pileup_ins> ins(rows, ioc_pileup_ins{});
+        std::vector<uint8_t> pb(rows), pf(rows), ps(size_t(IOC_PILE_INS_SLOTS) * rows);
+        for (const size_t i : who) {
+            const int32_t ql = int32_t(len[i * S + k]);
+            const std::string& ops = kept[which][i];
+            const int64_t L = int64_t(ops.size());
+            ioc_host_ops_project(ops.data(), L, window(i, k), ql, tlen, pb.data(), pf.data());
+            ioc_host_ops_project_ins(ops.data(), L, window(i, k), ql, tlen, ps.data());
+            ioc_host_planes_pile(pb.data(), ps.data(), tlen, cols.data(), ins.data());
+        }
+        std::string s(size_t(pile_call_most(tlen)), 0), q(s.size(), 0);
+        ioc_polish_stats st{};
+        const int64_t L = ioc_host_pileup_call(cols.data(), ins.data(), window(t, k), tlen, polish_min_depth, &s[0], &q[0], int64_t(s.size()), &st);
+        seq.append(s.data(), size_t(L)), qual.append(q.data(), size_t(L));
+        off.push_back(int64_t(seq.size())), stats.push_back(st);
+    };
+    auto no_call = [&]() { off.push_back(int64_t(seq.size())), stats.push_back(ioc_polish_stats{}); };
+    for (size_t i = 0; i < n; ++i) key2[i] = keys[i];
+    for (size_t k = 0; k < S; ++k) {
+        const ioc_insert_window& w = win[k];
+        ioc_window_variant& v = var[k];
+        std::vector<size_t> voters, far, va, vb;
+        for (size_t i = 0; i < n; ++i)
+            if (cls[i * S + k] == IOC_WIN_VOTER) voters.push_back(i);
+        std::vector<uint8_t> fa(n, WINVAR_UNSEEN), fb(n, WINVAR_UNSEEN);
+        if (w.tlen > 0) round(k, voters, size_t(w.template_pair), 0, fa);
+        for (const size_t i : voters)
+            if (fa[i] == WINVAR_FAR) far.push_back(i);
+        v.n_far = uint32_t(far.size());
+        if (winvar_round_b(rule, w.n_voters, v.n_far)) {
+            std::vector<std::pair<uint32_t, uint32_t>> order;  // (window length, read)
+            for (const size_t i : far) order.push_back({len[i * S + k], uint32_t(i)});
+            std::sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return win_voter_less(a.first, a.second, b.first, b.second); });
+            const auto& t = order[win_median_rank(uint32_t(order.size()))];
+            v.template_pair_b = int32_t(t.second), v.tlen_b = int32_t(t.first);
+            round(k, far, size_t(t.second), 1, fb);
+            for (const size_t i : far) ++(fb[i] == WINVAR_NEAR ? v.n_b : v.n_other);
+        }
+        v.split = winvar_splits(rule, w.n_voters, v.n_far, v.n_b) ? 1 : 0;
+        for (size_t i = 0; i < n; ++i) {
+            const uint8_t x = winvar_variant(cls[i * S + k], v.split != 0, fa[i], fb[i]);
+            variant[i * S + k] = x;
+            if (x == IOC_WINVAR_A) va.push_back(i);
+            if (x == IOC_WINVAR_B) vb.push_back(i);
+            const uint32_t st = winvar_state(uint32_t(keys[i] >> (2 * k)) & 3u, cls[i * S + k], v.split != 0, x);
+            key2[i] = (key2[i] & ~(uint64_t(3) << (2 * k))) | uint64_t(st) << (2 * k);
+        }
+        v.n_a = uint32_t(va.size());
+        if (!call) continue;
+        if (w.tlen > 0) consensus(k, va, size_t(w.template_pair), 0); else no_call();
+        if (v.split) consensus(k, vb, size_t(v.template_pair_b), 1); else no_call();
+    }
+    for (size_t i = 0; i < n; ++i)
+        for (size_t k = 0; k < S; ++k) mask2[i] |= blocks_state_mask(uint32_t(k), uint32_t(key2[i] >> (2 * k)) & 3u);
+    if (call && int64_t(seq.size()) > cap) return IOC_ERR_CAPACITY;  // (the bound above holds it: pile_call_most a slot)
+    std::copy(win.begin(), win.end(), out_win);
+    std::copy(var.begin(), var.end(), out_var);
+    if (out_variant) std::copy(variant.begin(), variant.end(), out_variant);
+    if (out_agree) std::copy(agree.begin(), agree.end(), out_agree);
+    if (call) {
+        std::copy(seq.begin(), seq.end(), out_seq), std::copy(qual.begin(), qual.end(), out_qual);
+        std::copy(off.begin(), off.end(), out_off), std::copy(stats.begin(), stats.end(), out_stats);
+    }
+    std::copy(key2.begin(), key2.end(), out_key2);
+    std::copy(mask2.begin(), mask2.end(), out_mask2);
     return IOC_OK;
 }
 

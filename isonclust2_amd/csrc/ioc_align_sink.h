@@ -36,6 +36,9 @@ struct AlnTally {
     double ms_project_qpos = 0; // k_ops_project_qpos' device time (a pile that projects the position plane as well), and ...
     double ms_win_walk = 0;     // (IOC_WIN_SPLIT: k_win_align's walk on its own; ms_windows[2] is the fill then)
     double ms_windows[4] = {};  // ... k_win_bounds, k_win_template, k_win_align and k_group_pile over the sites (ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq)
+    double ms_winvar[8] = {};   // k_win_agree (both rounds), k_win_template_far, k_win_align over round B, then k_win_decide, k_win_rekey and the three of the
+                                // recount, in the order they run (ioc_planes_insert_window_variants); ms_windows[2] is round A then, ms_windows[3] the slots' pile
+    int64_t win_voters = 0, win_voters_b = 0;  // ... the alignments of round A, and those of round B
     double ms_splice[3] = {};   // k_splice_plan, k_splice_call's count pass with the scan, and its write pass (ioc_planes_isoforms_full,
                                 // ioc_align_pairs_isoforms_full, where ms_group_pile is k_group_pile over the combined isoforms)
     double ms_ends[8] = {};     // the eight kernels of ioc_read_ends.hip, in the order they run (ioc_reads_ends, ioc_align_pairs_blocks_ends)

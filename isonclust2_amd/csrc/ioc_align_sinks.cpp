@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -22,6 +23,7 @@
 #include "ioc_read_inserts.h"
 #include "ioc_read_ends.h"
 #include "ioc_insert_windows.h"
+#include "ioc_window_variants.h"
 #include "ioc_iso_splice.h"
 
 namespace {
@@ -1608,7 +1610,8 @@ struct WindowsReads {
 constexpr uint64_t WIN_DIR_WORDS_MOST = uint64_t(1) << 25;  // the direction words of one launch of k_win_align: 128 MB, 2048 alignments of 512 x 512
 
 // what a window call refuses about its sites and its room: IOC_OK, or the status with the message set
-static int windows_ok(ioc_ctx* c, const std::string& who, const WindowsOut& o, const SinkPlan& p, const ioc_pile_insert* sites, const int64_t* site_off, int64_t n_sites_most)
+static int windows_ok(ioc_ctx* c, const std::string& who, const WindowsOut& o, const SinkPlan& p, const ioc_pile_insert* sites, const int64_t* site_off, int64_t n_sites_most,
+                      int64_t slots_a_site = 1)
 {
     const size_t n = p.segs.size();
     if (site_off) {  // (the sites are the caller's: ioc_planes_insert_windows)
@@ -1622,30 +1625,43 @@ static int windows_ok(ioc_ctx* c, const std::string& who, const WindowsOut& o, c
         }
         n_sites_most = site_off[n];
     }
-    const int64_t bound = n_sites_most * pile_call_most(o.rule.max_win);
+    const int64_t bound = n_sites_most * slots_a_site * pile_call_most(o.rule.max_win);
     if (o.call.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": cap " + std::to_string(o.call.cap) + " below the bound " + std::to_string(bound));
     return n_sites_most > 0 && (!o.win || !o.call.stats || !o.call.seq || !o.call.qual) ? IOC_ERR_ARG : IOC_OK;
 }
 
-// bounds -> template -> [the host lists the voters] -> align -> group pile -> call -> copy-out.  The planes lie on the device (dev_*)
-// or are the host's and uploaded; sites, site_off and keys are the host's.  a_windows holds the tables [segments][seg_of_pair][plane
-// offsets][read lengths][member lists][sites][site_off][site_seg][keys], the (pair, site) entries and the records and, uploaded, the
-// planes.  The records and the entries come back; the host lists every called site's voters in pair order — an alignment each, a group
-// of k_group_pile per site — and a_gpile holds [items][group-segments][work items][plane offsets][gmem_off][gmembers][base plane]
-// [slot planes][gcols][gins][direction words], the direction words of at most WIN_DIR_WORDS_MOST a launch.
-static int windows_device(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_pair, const WindowsReads& reads, const uint8_t* host_base, const uint32_t* host_qpos,
-                   const uint8_t* dev_base, const uint32_t* dev_qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys,
-                   const WindowsOut& o)
+// What k_win_bounds and k_win_template left of a call: a_windows' tables on the device — [segments][seg_of_pair][plane offsets][read
+// lengths][member lists][sites][site_off][site_seg][keys], the (pair, site) entries and the records and, uploaded, the planes — and
+// the records and the entries on the host.
+struct WinTables {
+    MemberLists m;
+    std::vector<int32_t> site_seg;
+    size_t stride = 1;
+    IocWinDev v{};
+    std::vector<ioc_insert_window> win;
+    std::vector<IocWinSlot> slot;
+    // what the entry of pair i at site k says, held against the read
+    bool voter(const WindowsReads& reads, int32_t max_win, size_t i, size_t k, uint32_t& start, uint32_t& len) const
+    {
+        const IocWinSlot& s = slot[i * stride + k];
+        start = s.start, len = win_slot_len(s.cls_len);
+        return win_slot_class(s.cls_len) == uint32_t(IOC_WIN_VOTER) && len >= 1 && len <= uint32_t(max_win) && uint64_t(start) + len <= reads.len[i];
+    }
+};
+
+// upload -> bounds -> template -> the records and the entries back.  The planes lie on the device (dev_*) or are the host's and
+// uploaded; sites, site_off and keys are the host's.
+static int windows_tables(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_pair, const WindowsReads& reads, const uint8_t* host_base, const uint32_t* host_qpos,
+                          const uint8_t* dev_base, const uint32_t* dev_qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys,
+                          const WinRule& rule, WinTables& t)
 {
     ioc_ctx* const c = r.c;
     const size_t n = pn.segs.size(), np = pn.plane.size(), B = size_t(pn.plane_bytes), ns = size_t(site_off[n]);
-    for (size_t x = 0; x <= ns; ++x) o.call.off[x] = 0;
-    for (size_t x = 0; x < ns; ++x) o.call.stats[x] = ioc_polish_stats{};
-    if (ns == 0) return IOC_OK;
-    const MemberLists m = member_lists(n, np, seg_of_pair);
-    const std::vector<int32_t> site_seg = slot_owners(site_off, n);
+    t.m = member_lists(n, np, seg_of_pair);
+    t.site_seg = slot_owners(site_off, n);
     size_t stride = 1;
     for (size_t g = 0; g < n; ++g) stride = std::max(stride, size_t(site_off[g + 1] - site_off[g]));
+    t.stride = stride;
     Arena l;
     const size_t o_seg = l.take(n * sizeof(IocPileSeg)), o_sop = l.take(np * 4), o_plane = l.take(np * 8), o_qlen = l.take(np * 4), o_moff = l.take((n + 1) * 4),
                  o_mem = l.take(np * 4), o_sites = l.take(ns * sizeof(ioc_pile_insert)), o_soff = l.take((n + 1) * 8), o_sseg = l.take(ns * 4),
@@ -1655,124 +1671,209 @@ static int windows_device(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_
     std::vector<uint8_t> stage(tables, 0);
     auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
     put(o_seg, pn.segs.data(), n * sizeof(IocPileSeg)), put(o_sop, seg_of_pair, np * 4), put(o_plane, pn.plane.data(), np * 8), put(o_qlen, reads.len.data(), np * 4);
-    put(o_moff, m.mem_off.data(), (n + 1) * 4), put(o_mem, m.members.data(), np * 4), put(o_sites, sites, ns * sizeof(ioc_pile_insert));
-    put(o_soff, site_off, (n + 1) * 8), put(o_sseg, site_seg.data(), ns * 4), put(o_keys, keys, np * 8);
+    put(o_moff, t.m.mem_off.data(), (n + 1) * 4), put(o_mem, t.m.members.data(), np * 4), put(o_sites, sites, ns * sizeof(ioc_pile_insert));
+    put(o_soff, site_off, (n + 1) * 8), put(o_sseg, t.site_seg.data(), ns * 4), put(o_keys, keys, np * 8);
     IOC_CHK(c, hipSetDevice(c->device));
     IOC_TRY(ioc_reserve(c, c->a_windows, l.size()));
     uint8_t* p = static_cast<uint8_t*>(c->a_windows.p);
     IOC_CHK(c, hipMemcpyAsync(p, stage.data(), tables, hipMemcpyHostToDevice, c->stream));
     if (!dev_base && B) IOC_CHK(c, hipMemcpyAsync(p + o_base, host_base, B, hipMemcpyHostToDevice, c->stream));
     if (!dev_qpos && B) IOC_CHK(c, hipMemcpyAsync(p + o_qpos, host_qpos, 4 * B, hipMemcpyHostToDevice, c->stream));
-    IOC_CHK(c, hipMemsetAsync(p + o_slots, 0, o_end - o_slots, c->stream));  // (the entries and the records)
-    const IocWinDev v{reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop),
-                      reinterpret_cast<const uint64_t*>(p + o_plane), dev_base ? dev_base : p + o_base,
-                      dev_qpos ? dev_qpos : reinterpret_cast<const uint32_t*>(p + o_qpos), uint64_t(B), reinterpret_cast<const uint32_t*>(p + o_qlen),
-                      reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem), reinterpret_cast<const ioc_pile_insert*>(p + o_sites),
-                      reinterpret_cast<const int64_t*>(p + o_soff), reinterpret_cast<const int32_t*>(p + o_sseg), uint32_t(ns),
-                      reinterpret_cast<const unsigned long long*>(p + o_keys), reinterpret_cast<IocWinSlot*>(p + o_slots), uint32_t(stride), uint64_t(np * stride),
-                      reinterpret_cast<ioc_insert_window*>(p + o_win)};
+    if (o_end > o_slots) IOC_CHK(c, hipMemsetAsync(p + o_slots, 0, o_end - o_slots, c->stream));  // (the entries and the records)
+    t.v = IocWinDev{reinterpret_cast<const IocPileSeg*>(p + o_seg), uint32_t(n), uint32_t(np), reinterpret_cast<const int32_t*>(p + o_sop),
+                    reinterpret_cast<const uint64_t*>(p + o_plane), dev_base ? dev_base : p + o_base,
+                    dev_qpos ? dev_qpos : reinterpret_cast<const uint32_t*>(p + o_qpos), uint64_t(B), reinterpret_cast<const uint32_t*>(p + o_qlen),
+                    reinterpret_cast<const uint32_t*>(p + o_moff), reinterpret_cast<const uint32_t*>(p + o_mem), reinterpret_cast<const ioc_pile_insert*>(p + o_sites),
+                    reinterpret_cast<const int64_t*>(p + o_soff), reinterpret_cast<const int32_t*>(p + o_sseg), uint32_t(ns),
+                    reinterpret_cast<const unsigned long long*>(p + o_keys), reinterpret_cast<IocWinSlot*>(p + o_slots), uint32_t(stride), uint64_t(np * stride),
+                    reinterpret_cast<ioc_insert_window*>(p + o_win)};
     KernelTimes each;
     IOC_TRY(each.create(c, 2));
     IOC_TRY(r.begin(r.t.ms_windows[0], !each.on()));
-    IOC_CHK(c, iock_win_bounds_template(c->stream, v, o.rule.slack, o.rule.max_win, each.events()));
+    IOC_CHK(c, iock_win_bounds_template(c->stream, t.v, rule.slack, rule.max_win, each.events()));
     IOC_TRY(r.end());
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     r.settled();
     each.add_to(r.t.ms_windows);
-    std::vector<ioc_insert_window> win(ns);
-    std::vector<IocWinSlot> slot(np * stride);
-    IOC_TRY(r.copy_out({{win.data(), p + o_win, ns * sizeof(ioc_insert_window)}, {slot.data(), p + o_slots, np * stride * sizeof(IocWinSlot)}}));
+    t.win.assign(ns, ioc_insert_window{});
+    t.slot.assign(np * stride, IocWinSlot{});
+    return r.copy_out({{t.win.data(), p + o_win, ns * sizeof(ioc_insert_window)}, {t.slot.data(), p + o_slots, np * stride * sizeof(IocWinSlot)}});
+}
 
-    // every called site's voters, in pair order: an alignment each; the site is a group-segment of tlen + 1 rows
-    std::vector<IocPileSeg> gsegs;
-    std::vector<uint32_t> goff{0}, gmem;
+// The alignments of one round of k_win_align, as the host lists them: an item each, its planes of tlen + 1 bytes one behind the
+// other (P in all), its (pair, site) entry, and its direction words, of at most WIN_DIR_WORDS_MOST a launch.
+struct WinRound {
     std::vector<IocWinItem> items;
-    std::vector<uint64_t> vplane;
-    std::vector<IocGroupWork> work;
-    std::vector<size_t> called, launch{0};  // (launch: the first item of every launch of k_win_align, and the end)
-    int64_t rows = 0;
+    std::vector<uint64_t> vplane, entry;
+    std::vector<size_t> launch{0};  // (the first item of every launch of k_win_align, and after close() the end)
     uint64_t P = 0, dir_at = 0, dir_most = 0;
-    auto voter = [&](size_t i, size_t k, uint32_t& start, uint32_t& len) {  // what the entry of pair i at site k says, held against the read
-        const IocWinSlot& s = slot[i * stride + k];
-        start = s.start, len = win_slot_len(s.cls_len);
-        return win_slot_class(s.cls_len) == uint32_t(IOC_WIN_VOTER) && len >= 1 && len <= uint32_t(o.rule.max_win) && uint64_t(start) + len <= reads.len[i];
-    };
-    for (size_t x = 0; x < ns; ++x) {
-        const size_t g = size_t(site_seg[x]), k = x - size_t(site_off[g]);
-        const ioc_insert_window& w = win[x];
-        if (w.tlen <= 0) continue;
-        uint32_t t_start = 0, t_len = 0;
-        if (w.template_pair < 0 || size_t(w.template_pair) >= np || size_t(seg_of_pair[w.template_pair]) != g || !voter(size_t(w.template_pair), k, t_start, t_len) ||
-            t_len != uint32_t(w.tlen))
-            return ioc_fail(c, IOC_ERR_HIP, "the window kernels returned a template that is no voter of its site");
-        const uint64_t t_off = uint64_t(reads.off[size_t(w.template_pair)]) + t_start;
-        for (uint32_t mi = m.mem_off[g]; mi < m.mem_off[g + 1]; ++mi) {
-            const size_t i = m.members[mi];
-            uint32_t start = 0, len = 0;
-            if (!voter(i, k, start, len)) continue;
-            const uint64_t words = win_dir_words(len, t_len);
-            if (dir_at + words > WIN_DIR_WORDS_MOST) launch.push_back(items.size()), dir_at = 0;
-            items.push_back(IocWinItem{uint64_t(reads.off[i]) + start, t_off, P, dir_at, len, t_len});
-            dir_at += words, dir_most = std::max(dir_most, dir_at);
-            vplane.push_back(P), gmem.push_back(uint32_t(items.size() - 1));
-            P += uint64_t(t_len) + 1;
-        }
-        for (int64_t row = 0; row <= int64_t(t_len); row += IOC_GROUP_PILE_ROWS) work.push_back(IocGroupWork{uint32_t(gsegs.size()), uint32_t(row)});
-        gsegs.push_back(IocPileSeg{rows, int64_t(t_off), int32_t(t_len), 0});
-        goff.push_back(uint32_t(gmem.size()));
-        rows += int64_t(t_len) + 1;
-        called.push_back(x);
+    void add(uint64_t q_off, uint64_t t_off, uint32_t len, uint32_t t_len, uint64_t e)
+    {
+        const uint64_t words = win_dir_words(len, t_len);
+        if (dir_at + words > WIN_DIR_WORDS_MOST) launch.push_back(items.size()), dir_at = 0;
+        items.push_back(IocWinItem{q_off, t_off, P, dir_at, len, t_len});
+        dir_at += words, dir_most = std::max(dir_most, dir_at);
+        vplane.push_back(P), entry.push_back(e);
+        P += uint64_t(t_len) + 1;
     }
-    launch.push_back(items.size());
-    std::copy(win.begin(), win.end(), o.win);
-    if (called.empty()) return IOC_OK;
-    if (items.size() > size_t(INT32_MAX) || P > (uint64_t(1) << 40)) return ioc_fail(c, IOC_ERR_CAPACITY, "the windows of the call have more than 2^31 - 1 voters");
-
-    const size_t G = gsegs.size(), M = items.size();
-    Arena a;
-    const size_t a_items = a.take(M * sizeof(IocWinItem)), a_gseg = a.take(G * sizeof(IocPileSeg)), a_work = a.take(work.size() * sizeof(IocGroupWork)),
-                 a_plane = a.take(M * 8), a_goff = a.take((G + 1) * 4), a_gmem = a.take(M * 4), a_base = a.take(size_t(P)),
-                 a_slots = a.take(size_t(IOC_PILE_INS_SLOTS) * size_t(P)), a_cols = a.take(size_t(rows) * sizeof(ioc_pileup_col)),
-                 a_ins = a.take(size_t(rows) * sizeof(ioc_pileup_ins)), a_dir = a.take(size_t(dir_most) * 4);
-    IOC_TRY(ioc_reserve(c, c->a_gpile, a.size()));
-    uint8_t* q = static_cast<uint8_t*>(c->a_gpile.p);
-    auto up = [&](size_t at, const void* src, size_t b) { return b ? hipMemcpyAsync(q + at, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
-    IOC_CHK(c, up(a_items, items.data(), M * sizeof(IocWinItem)));
-    IOC_CHK(c, up(a_gseg, gsegs.data(), G * sizeof(IocPileSeg)));
-    IOC_CHK(c, up(a_work, work.data(), work.size() * sizeof(IocGroupWork)));
-    IOC_CHK(c, up(a_plane, vplane.data(), M * 8));
-    IOC_CHK(c, up(a_goff, goff.data(), (G + 1) * 4));
-    IOC_CHK(c, up(a_gmem, gmem.data(), M * 4));
-    IOC_CHK(c, hipMemsetAsync(q + a_base, IOC_ALLELE_NONE, size_t(P), c->stream));
-    IOC_CHK(c, hipMemsetAsync(q + a_slots, 0, a_dir - a_slots, c->stream));  // (the slot planes and both tables)
+    void close() { launch.push_back(items.size()); }
+    bool fits() const { return items.size() <= size_t(INT32_MAX) && P <= (uint64_t(1) << 40); }
+};
+// where a round's blocks lie in its buffer: [items][base plane][slot planes][direction words]
+struct WinRoundAt {
+    size_t items, base, slots, dir;
+    static WinRoundAt take(Arena& a, const WinRound& w)
+    {
+        WinRoundAt at;
+        at.items = a.take(w.items.size() * sizeof(IocWinItem)), at.base = a.take(size_t(w.P)), at.slots = a.take(size_t(IOC_PILE_INS_SLOTS) * size_t(w.P)),
+        at.dir = a.take(size_t(w.dir_most) * 4);
+        return at;
+    }
+};
+// the site's template, held against the entries: where its window lies in the pool and how long it is
+static bool windows_template_at(const WinTables& t, const WindowsReads& reads, int32_t max_win, const int32_t* seg_of_pair, size_t g, size_t k, int32_t pair,
+                                int32_t tlen, uint64_t& t_off, uint32_t& t_len)
+{
+    uint32_t t_start = 0;
+    if (pair < 0 || size_t(pair) >= reads.len.size() || size_t(seg_of_pair[pair]) != g || !t.voter(reads, max_win, size_t(pair), k, t_start, t_len) || t_len != uint32_t(tlen))
+        return false;
+    t_off = uint64_t(reads.off[size_t(pair)]) + t_start;
+    return true;
+}
+// upload the items -> set the planes -> k_win_align, launch after launch (`into`: what its device time is added to)
+static int windows_align(SinkRun& r, uint8_t* q, const WinRoundAt& at, const WinRound& w, const WinRule& rule, double& into)
+{
+    ioc_ctx* const c = r.c;
+    if (w.items.empty()) return IOC_OK;
+    IOC_CHK(c, hipMemcpyAsync(q + at.items, w.items.data(), w.items.size() * sizeof(IocWinItem), hipMemcpyHostToDevice, c->stream));
+    IOC_CHK(c, hipMemsetAsync(q + at.base, IOC_ALLELE_NONE, size_t(w.P), c->stream));
+    IOC_CHK(c, hipMemsetAsync(q + at.slots, 0, size_t(IOC_PILE_INS_SLOTS) * size_t(w.P), c->stream));
     const uint8_t* pool = static_cast<const uint8_t*>(c->a_pool.p);
     const uint64_t pool_bytes = uint64_t(c->aln_offs.back());
     // (IOC_TRACE with IOC_WIN_SPLIT, for the measurement: the fill and the walk of every launch as two launches, timed apart; the
     // walk reads the words the fill left, so the planes are the same bytes)
     const bool split = getenv("IOC_TRACE") && getenv("IOC_WIN_SPLIT");
-    for (size_t b = 0; b + 1 < launch.size(); ++b)
+    for (size_t b = 0; b + 1 < w.launch.size(); ++b)
         for (int ph = split ? 1 : 0; ph <= (split ? 2 : 0); ++ph) {  // (0: both halves in one launch; 1, 2: the fill, then the walk)
-            IOC_TRY(r.begin(ph == 2 ? r.t.ms_win_walk : r.t.ms_windows[2]));
-            IOC_CHK(c, iock_win_align(c->stream, reinterpret_cast<const IocWinItem*>(q + a_items) + launch[b], uint32_t(launch[b + 1] - launch[b]), pool, pool_bytes,
-                                      q + a_base, q + a_slots, P, reinterpret_cast<uint32_t*>(q + a_dir), dir_most, o.rule.match, o.rule.mismatch, o.rule.gap, ph));
+            IOC_TRY(r.begin(ph == 2 ? r.t.ms_win_walk : into));
+            IOC_CHK(c, iock_win_align(c->stream, reinterpret_cast<const IocWinItem*>(q + at.items) + w.launch[b], uint32_t(w.launch[b + 1] - w.launch[b]), pool, pool_bytes,
+                                      q + at.base, q + at.slots, w.P, reinterpret_cast<uint32_t*>(q + at.dir), w.dir_most, rule.match, rule.mismatch, rule.gap, ph));
             IOC_TRY(r.end());
         }
+    return IOC_OK;
+}
+
+// A site's template in a round and the round's items that are its voters', first .. end - 1 (t_len 0: the site has no round).
+struct WinSite {
+    uint64_t t_off = 0;
+    uint32_t t_len = 0;
+    size_t first = 0, end = 0;
+};
+// One round listed: for every site x that template_of(x, pair, tlen) gives a template, the members i of its segment that vote and
+// that take(i, k) lets in, in pair order, against that template.  IOC_OK, or IOC_ERR_HIP where a template is no voter of its site.
+// (no template: this stands inside extern "C" with the entry points)
+static int windows_list_round(const WinTables& t, const WindowsReads& reads, int32_t max_win, const int32_t* seg_of_pair, const int64_t* site_off,
+                              const std::function<bool(size_t, int32_t&, int32_t&)>& template_of, const std::function<bool(size_t, size_t)>& take,
+                              std::vector<WinSite>& site, WinRound& round)
+{
+    site.assign(t.win.size(), WinSite{});
+    for (size_t x = 0; x < t.win.size(); ++x) {
+        const size_t g = size_t(t.site_seg[x]), k = x - size_t(site_off[g]);
+        WinSite& s = site[x];
+        s.first = s.end = round.items.size();
+        int32_t pair = -1, tlen = 0;
+        if (!template_of(x, pair, tlen)) continue;
+        if (!windows_template_at(t, reads, max_win, seg_of_pair, g, k, pair, tlen, s.t_off, s.t_len)) return IOC_ERR_HIP;
+        for (uint32_t mi = t.m.mem_off[g]; mi < t.m.mem_off[g + 1]; ++mi) {
+            const size_t i = t.m.members[mi];
+            uint32_t start = 0, len = 0;
+            if (take(i, k) && t.voter(reads, max_win, i, k, start, len)) round.add(uint64_t(reads.off[i]) + start, s.t_off, len, s.t_len, uint64_t(i) * t.stride + k);
+        }
+        s.end = round.items.size();
+    }
+    round.close();
+    return IOC_OK;
+}
+// What a packed call made of the group-segments y (off, st: a record each), spread over n_slots slots of which slot_of[y] is group-segment y's.
+static void spread_called(const std::vector<int64_t>& off, const std::vector<ioc_polish_stats>& st, const size_t* slot_of, size_t n_slots, const CallOut& out)
+{
+    for (size_t y = 0, x = 0; x < n_slots; ++x) {
+        const bool is = y < st.size() && slot_of[y] == x;
+        out.off[x + 1] = out.off[x] + (is ? off[y + 1] - off[y] : 0);
+        if (is) out.stats[x] = st[y++];
+    }
+}
+
+// tables -> [the host lists the voters] -> align -> group pile -> call -> copy-out.  The host lists every called site's voters in pair
+// order — an alignment each, a group of k_group_pile per site — and a_gpile holds the round's blocks (WinRoundAt) and [group-segments]
+// [work items][plane offsets][gmem_off][gmembers][gcols][gins].
+static int windows_device(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_pair, const WindowsReads& reads, const uint8_t* host_base, const uint32_t* host_qpos,
+                   const uint8_t* dev_base, const uint32_t* dev_qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys,
+                   const WindowsOut& o)
+{
+    ioc_ctx* const c = r.c;
+    const size_t n = pn.segs.size(), ns = size_t(site_off[n]);
+    for (size_t x = 0; x <= ns; ++x) o.call.off[x] = 0;
+    for (size_t x = 0; x < ns; ++x) o.call.stats[x] = ioc_polish_stats{};
+    if (ns == 0) return IOC_OK;
+    WinTables t;
+    IOC_TRY(windows_tables(r, pn, seg_of_pair, reads, host_base, host_qpos, dev_base, dev_qpos, sites, site_off, keys, o.rule, t));
+
+    // every called site's voters, in pair order: an alignment each; the site is a group-segment of tlen + 1 rows
+    std::vector<IocPileSeg> gsegs;
+    std::vector<uint32_t> goff{0}, gmem;
+    WinRound round;
+    std::vector<WinSite> site;
+    std::vector<IocGroupWork> work;
+    std::vector<size_t> called;
+    int64_t rows = 0;
+    if (windows_list_round(t, reads, o.rule.max_win, seg_of_pair, site_off,
+                           [&](size_t x, int32_t& pair, int32_t& tlen) { return pair = t.win[x].template_pair, (tlen = t.win[x].tlen) > 0; },
+                           [](size_t, size_t) { return true; }, site, round))
+        return ioc_fail(c, IOC_ERR_HIP, "the window kernels returned a template that is no voter of its site");
+    for (size_t x = 0; x < ns; ++x) {
+        const WinSite& w = site[x];
+        if (w.t_len == 0) continue;
+        for (size_t y = w.first; y < w.end; ++y) gmem.push_back(uint32_t(y));
+        for (int64_t row = 0; row <= int64_t(w.t_len); row += IOC_GROUP_PILE_ROWS) work.push_back(IocGroupWork{uint32_t(gsegs.size()), uint32_t(row)});
+        gsegs.push_back(IocPileSeg{rows, int64_t(w.t_off), int32_t(w.t_len), 0});
+        goff.push_back(uint32_t(gmem.size()));
+        rows += int64_t(w.t_len) + 1;
+        called.push_back(x);
+    }
+    std::copy(t.win.begin(), t.win.end(), o.win);
+    if (called.empty()) return IOC_OK;
+    if (!round.fits()) return ioc_fail(c, IOC_ERR_CAPACITY, "the windows of the call have more than 2^31 - 1 voters");
+
+    const size_t G = gsegs.size(), M = round.items.size();
+    Arena a;
+    const WinRoundAt at = WinRoundAt::take(a, round);
+    const size_t a_gseg = a.take(G * sizeof(IocPileSeg)), a_work = a.take(work.size() * sizeof(IocGroupWork)), a_plane = a.take(M * 8), a_goff = a.take((G + 1) * 4),
+                 a_gmem = a.take(M * 4), a_cols = a.take(size_t(rows) * sizeof(ioc_pileup_col)), a_ins = a.take(size_t(rows) * sizeof(ioc_pileup_ins)), a_end = a.size();
+    IOC_TRY(ioc_reserve(c, c->a_gpile, a.size()));
+    uint8_t* q = static_cast<uint8_t*>(c->a_gpile.p);
+    auto up = [&](size_t at_, const void* src, size_t b) { return b ? hipMemcpyAsync(q + at_, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(a_gseg, gsegs.data(), G * sizeof(IocPileSeg)));
+    IOC_CHK(c, up(a_work, work.data(), work.size() * sizeof(IocGroupWork)));
+    IOC_CHK(c, up(a_plane, round.vplane.data(), M * 8));
+    IOC_CHK(c, up(a_goff, goff.data(), (G + 1) * 4));
+    IOC_CHK(c, up(a_gmem, gmem.data(), M * 4));
+    IOC_CHK(c, hipMemsetAsync(q + a_cols, 0, a_end - a_cols, c->stream));  // (both tables)
+    IOC_TRY(windows_align(r, q, at, round, o.rule, r.t.ms_windows[2]));
+    const uint8_t* pool = static_cast<const uint8_t*>(c->a_pool.p);
+    const uint64_t pool_bytes = uint64_t(c->aln_offs.back());
     ioc_pileup_col* const d_cols = reinterpret_cast<ioc_pileup_col*>(q + a_cols);
     ioc_pileup_ins* const d_ins = reinterpret_cast<ioc_pileup_ins*>(q + a_ins);
     IOC_TRY(r.begin(r.t.ms_windows[3]));
     IOC_CHK(c, iock_group_pile(c->stream, reinterpret_cast<const IocGroupWork*>(q + a_work), uint32_t(work.size()), reinterpret_cast<const IocPileSeg*>(q + a_gseg),
                                uint32_t(G), reinterpret_cast<const uint32_t*>(q + a_goff), reinterpret_cast<const uint32_t*>(q + a_gmem), uint32_t(M), uint32_t(M),
-                               reinterpret_cast<const uint64_t*>(q + a_plane), q + a_base, q + a_slots, P, d_cols, d_ins, uint64_t(rows)));
+                               reinterpret_cast<const uint64_t*>(q + a_plane), q + at.base, q + at.slots, round.P, d_cols, d_ins, uint64_t(rows)));
     IOC_TRY(r.end());
     std::vector<int64_t> off(G + 1, 0);
     std::vector<ioc_polish_stats> st(G);
     const CallOut packed{o.call.min_depth, o.call.seq, o.call.qual, o.call.cap, off.data(), st.data()};  // (the called sites' bytes are all sites' bytes, packed)
     IOC_TRY(pile_call_device(r, gsegs, pool, pool_bytes, packed, d_cols, d_ins, nullptr, rows));
-    for (size_t y = 0, x = 0; x < ns; ++x) {
-        const bool is = y < G && called[y] == x;
-        o.call.off[x + 1] = o.call.off[x] + (is ? off[y + 1] - off[y] : 0);
-        if (is) o.call.stats[x] = st[y++];
-    }
+    spread_called(off, st, called.data(), ns, o.call);
     return r.copy_out({{o.cols, d_cols, size_t(rows) * sizeof(ioc_pileup_col)}, {o.ins, d_ins, size_t(rows) * sizeof(ioc_pileup_ins)}});
 }
 
@@ -1781,6 +1882,279 @@ static std::string windows_trace(const AlnTally& t)
     char buf[240];
     snprintf(buf, sizeof buf, "k_win_bounds %.3f ms, k_win_template %.3f ms, k_win_align %.3f ms, k_win_align_walk %.3f ms, k_win_group_pile %.3f ms, k_win_pile_call %.3f ms",
              t.ms_windows[0], t.ms_windows[1], t.ms_windows[2], t.ms_win_walk, t.ms_windows[3], t.ms_call);
+    return buf;
+}
+// ---- two exons at one junction: the variants of the kept sites ----
+struct VariantsOut {  // the rule of a variant call beside the window rule, and where it leaves what it made beside the windows' outputs
+    WinVarRule rule;
+    ioc_window_variant* var;
+    uint8_t* variant;   // IOC_INSERTS_MAX bytes a pair
+    int32_t* agree;     // (may be NULL) 2 IOC_INSERTS_MAX words a pair
+    ioc_read_variants* reads;
+    ioc_variants_seg* seg;
+};
+
+struct VariantsFused {  // the variant stage behind the insert stage (ioc_align_pairs_blocks_inserts_variants): its rule and outputs, and its slots' bytes
+    VariantsOut vo;
+    CallOut call;
+};
+
+// One round of the variant stage where it lies on the device: the host's list, its sites, the buffer its blocks are in and where.
+struct VariantRound {
+    WinRound w;
+    std::vector<WinSite> site;
+    uint8_t* q = nullptr;
+    WinRoundAt at{};
+};
+
+// The slots of a variant call: a group-segment per (called site, variant that has one), its members the items of its round whose voter
+// is of the variant — round B's items count from round A's last —, the work items of either round's launch of k_group_pile, and
+// slot_of, the slot 2 x + h of every group-segment.  With `with_all` (the fused call) the window call's own sites stand behind the
+// n_slots slots: every item of round A, all voters voting.
+struct VariantSlots {
+    std::vector<IocPileSeg> gsegs;
+    std::vector<uint32_t> goff{0}, gmem;
+    std::vector<IocGroupWork> work_a, work_b;
+    std::vector<size_t> slot_of;
+    int64_t rows = 0;
+    size_t n_slots = 0;
+    void add(size_t slot, const WinSite& st, const WinRound& w, size_t item0, const std::vector<uint8_t>* variant, uint8_t which, std::vector<IocGroupWork>& work)
+    {
+        for (size_t y = st.first; y < st.end; ++y)
+            if (!variant || (*variant)[size_t(w.entry[y])] == which) gmem.push_back(uint32_t(item0 + y));
+        for (int64_t row = 0; row <= int64_t(st.t_len); row += IOC_GROUP_PILE_ROWS) work.push_back(IocGroupWork{uint32_t(gsegs.size()), uint32_t(row)});
+        gsegs.push_back(IocPileSeg{rows, int64_t(st.t_off), int32_t(st.t_len), 0});
+        goff.push_back(uint32_t(gmem.size()));
+        rows += int64_t(st.t_len) + 1;
+        slot_of.push_back(slot);
+    }
+    static VariantSlots list(const VariantRound& ra, const VariantRound& rb, const std::vector<ioc_window_variant>& var, const std::vector<uint8_t>& variant, bool with_all)
+    {
+        VariantSlots v;
+        const size_t ns = var.size(), MA = ra.w.items.size();
+        for (size_t x = 0; x < ns; ++x) {
+            if (ra.site[x].t_len > 0) v.add(2 * x, ra.site[x], ra.w, 0, &variant, uint8_t(IOC_WINVAR_A), v.work_a);
+            if (var[x].split && rb.site[x].t_len > 0) v.add(2 * x + 1, rb.site[x], rb.w, MA, &variant, uint8_t(IOC_WINVAR_B), v.work_b);
+        }
+        v.n_slots = v.gsegs.size();
+        for (size_t x = 0; x < ns && with_all; ++x)
+            if (ra.site[x].t_len > 0) v.add(x, ra.site[x], ra.w, 0, nullptr, 0, v.work_a);
+        return v;
+    }
+};
+// what the slots may need at most, known once round B is listed: every site of round B splitting
+struct VariantSlotsMost {
+    size_t slots = 0, work = 0, members = 0;
+    int64_t rows = 0;
+    void add(const WinSite& s) { ++slots, rows += int64_t(s.t_len) + 1, work += s.t_len / IOC_GROUP_PILE_ROWS + 1; }
+    bool holds(const VariantSlots& v) const { return v.gsegs.size() <= slots && v.rows <= rows && v.work_a.size() + v.work_b.size() <= work && v.gmem.size() <= members; }
+};
+// where the slots' blocks lie in round B's buffer, behind its own: [group-segments][work items][plane offsets][gmem_off][gmembers][gcols][gins]
+struct VariantSlotsAt {
+    size_t gseg, work, plane, goff, gmem, cols, ins, end;
+    static VariantSlotsAt take(Arena& b, const VariantSlotsMost& most, size_t items)
+    {
+        VariantSlotsAt at;
+        at.gseg = b.take(most.slots * sizeof(IocPileSeg)), at.work = b.take(most.work * sizeof(IocGroupWork)), at.plane = b.take(items * 8);
+        at.goff = b.take((most.slots + 1) * 4), at.gmem = b.take(most.members * 4), at.cols = b.take(size_t(most.rows) * sizeof(ioc_pileup_col));
+        at.ins = b.take(size_t(most.rows) * sizeof(ioc_pileup_ins)), at.end = b.size();
+        return at;
+    }
+};
+
+// upload the slots -> group pile, a launch a round (a member's plane offset counts from its own round's planes) -> call the slots ->
+// call the window call's own sites behind them (all; NULL: there are none).
+static int variants_call_slots(SinkRun& r, const VariantSlots& v, const VariantSlotsAt& at, const VariantRound& ra, const VariantRound& rb, const CallOut& slots,
+                               size_t n_sites, const CallOut* all)
+{
+    ioc_ctx* const c = r.c;
+    const size_t G = v.n_slots, MA = ra.w.items.size(), MB = rb.w.items.size();
+    if (G == 0) return IOC_OK;
+    uint8_t* const qb = rb.q;
+    std::vector<uint64_t> vplane(ra.w.vplane);
+    vplane.insert(vplane.end(), rb.w.vplane.begin(), rb.w.vplane.end());
+    auto up = [&](size_t at_, const void* src, size_t b) { return b ? hipMemcpyAsync(qb + at_, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(at.gseg, v.gsegs.data(), v.gsegs.size() * sizeof(IocPileSeg)));
+    IOC_CHK(c, up(at.work, v.work_a.data(), v.work_a.size() * sizeof(IocGroupWork)));
+    IOC_CHK(c, up(at.work + v.work_a.size() * sizeof(IocGroupWork), v.work_b.data(), v.work_b.size() * sizeof(IocGroupWork)));
+    IOC_CHK(c, up(at.plane, vplane.data(), (MA + MB) * 8));
+    IOC_CHK(c, up(at.goff, v.goff.data(), v.goff.size() * 4));
+    IOC_CHK(c, up(at.gmem, v.gmem.data(), v.gmem.size() * 4));
+    IOC_CHK(c, hipMemsetAsync(qb + at.cols, 0, at.end - at.cols, c->stream));  // (both tables)
+    ioc_pileup_col* const d_cols = reinterpret_cast<ioc_pileup_col*>(qb + at.cols);
+    ioc_pileup_ins* const d_ins = reinterpret_cast<ioc_pileup_ins*>(qb + at.ins);
+    const IocGroupWork* const d_work = reinterpret_cast<const IocGroupWork*>(qb + at.work);
+    auto pile = [&](const IocGroupWork* work, size_t n_work, const VariantRound& of) {
+        return iock_group_pile(c->stream, work, uint32_t(n_work), reinterpret_cast<const IocPileSeg*>(qb + at.gseg), uint32_t(v.gsegs.size()),
+                               reinterpret_cast<const uint32_t*>(qb + at.goff), reinterpret_cast<const uint32_t*>(qb + at.gmem), uint32_t(v.gmem.size()), uint32_t(MA + MB),
+                               reinterpret_cast<const uint64_t*>(qb + at.plane), of.q + of.at.base, of.q + of.at.slots, of.w.P, d_cols, d_ins, uint64_t(v.rows));
+    };
+    IOC_TRY(r.begin(r.t.ms_windows[3]));
+    IOC_CHK(c, pile(d_work, v.work_a.size(), ra));
+    if (!v.work_b.empty()) IOC_CHK(c, pile(d_work + v.work_a.size(), v.work_b.size(), rb));
+    IOC_TRY(r.end());
+    const uint8_t* pool = static_cast<const uint8_t*>(c->a_pool.p);
+    const uint64_t pool_bytes = uint64_t(c->aln_offs.back());
+    // (the called slots' bytes are all slots' bytes, packed; and so are the sites')
+    auto call = [&](size_t first, size_t end, size_t n_out, const CallOut& out) {
+        std::vector<int64_t> off(end - first + 1, 0);
+        std::vector<ioc_polish_stats> st(end - first);
+        const CallOut packed{out.min_depth, out.seq, out.qual, out.cap, off.data(), st.data()};
+        IOC_TRY(pile_call_device(r, std::vector<IocPileSeg>(v.gsegs.begin() + int64_t(first), v.gsegs.begin() + int64_t(end)), pool, pool_bytes, packed, d_cols, d_ins, nullptr,
+                                 v.rows));
+        spread_called(off, st, v.slot_of.data() + first, n_out, out);
+        return int(IOC_OK);
+    };
+    IOC_TRY(call(0, G, 2 * n_sites, slots));
+    if (all && v.gsegs.size() > G) IOC_TRY(call(G, v.gsegs.size(), n_sites, *all));
+    return IOC_OK;
+}
+
+// tables -> [round A listed] -> align -> agree -> template B -> [round B listed] -> align -> agree -> decide -> rekey -> the isoforms
+// again -> [the slots listed] -> group pile -> call -> copy-out.  o.call: 2 sites slots (off: 2 sites + 1 entries), slot 2 x site x's
+// variant A and 2 x + 1 its B.  Round A lies in a_gpile as the window call has it; a_winvar holds [round A's entries][pre_key]
+// [pre_mask][pre_full], the flags, agreements, records and variant bytes and the recount's records; a_winvar_b round B's blocks and
+// entries and the slots' (VariantSlotsAt).  all (the fused call; else NULL): where the window call's own consensus of every site goes,
+// all voters voting — one more group-segment a called site over round A's planes, piled with the slots and called behind them.
+static int variants_device(SinkRun& r, const SinkPlan& pn, const int32_t* seg_of_pair, const WindowsReads& reads, const uint8_t* host_base, const uint32_t* host_qpos,
+                           const uint8_t* dev_base, const uint32_t* dev_qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys,
+                           const uint64_t* pre_key, const uint64_t* pre_mask, const uint64_t* pre_full, const WindowsOut& o, const VariantsOut& vo,
+                           const CallOut* all = nullptr)
+{
+    ioc_ctx* const c = r.c;
+    const size_t n = pn.segs.size(), np = pn.plane.size(), ns = size_t(site_off[n]), S = size_t(IOC_INSERTS_MAX);
+    for (size_t x = 0; x <= 2 * ns; ++x) o.call.off[x] = 0;
+    for (size_t x = 0; x < 2 * ns; ++x) o.call.stats[x] = ioc_polish_stats{};
+    for (size_t x = 0; x <= ns && all; ++x) all->off[x] = 0;
+    for (size_t x = 0; x < ns && all; ++x) all->stats[x] = ioc_polish_stats{};
+    if (n == 0) return IOC_OK;
+    WinTables t;
+    IOC_TRY(windows_tables(r, pn, seg_of_pair, reads, host_base, host_qpos, dev_base, dev_qpos, sites, site_off, keys, o.rule, t));
+    const size_t E = np * t.stride;  // the (pair, site) entries
+
+    // round A: every called site's voters against its template
+    VariantRound ra, rb;
+    if (windows_list_round(t, reads, o.rule.max_win, seg_of_pair, site_off,
+                           [&](size_t x, int32_t& pair, int32_t& tlen) { return pair = t.win[x].template_pair, (tlen = t.win[x].tlen) > 0; },
+                           [](size_t, size_t) { return true; }, ra.site, ra.w))
+        return ioc_fail(c, IOC_ERR_HIP, "the window kernels returned a template that is no voter of its site");
+    if (!ra.w.fits()) return ioc_fail(c, IOC_ERR_CAPACITY, "the windows of the call have more than 2^31 - 1 voters");
+    Arena a;
+    ra.at = WinRoundAt::take(a, ra.w);
+    IOC_TRY(ioc_reserve(c, c->a_gpile, a.size()));
+    ra.q = static_cast<uint8_t*>(c->a_gpile.p);
+    IOC_TRY(windows_align(r, ra.q, ra.at, ra.w, o.rule, r.t.ms_windows[2]));
+
+    const size_t MA = ra.w.items.size();
+    const bool with_pre = pre_key != nullptr;  // (all three or none: the entry point has seen to it)
+    Arena l;
+    const size_t o_at = l.take(MA * 8), o_pk = l.take(with_pre ? np * 8 : 0), o_pm = l.take(with_pre ? np * 8 : 0), o_pf = l.take(with_pre ? n * 8 : 0);
+    const size_t o_flag = l.take(2 * E), o_var = l.take(ns * sizeof(ioc_window_variant)), o_variant = l.take(E), o_reads = l.take(np * sizeof(ioc_read_inserts)),
+                 o_mask = l.take(np * 8), o_kflags = l.take(np), o_rec = l.take(n * sizeof(ioc_variants_seg)), o_zend = l.size(), o_agree = l.take(2 * E * 4);
+    IOC_TRY(ioc_reserve(c, c->a_winvar, l.size()));
+    uint8_t* const p = static_cast<uint8_t*>(c->a_winvar.p);
+    auto up = [&](uint8_t* base, size_t at_, const void* src, size_t b) { return b ? hipMemcpyAsync(base + at_, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(p, o_at, ra.w.entry.data(), MA * 8));
+    if (with_pre) {
+        IOC_CHK(c, up(p, o_pk, pre_key, np * 8));
+        IOC_CHK(c, up(p, o_pm, pre_mask, np * 8));
+        IOC_CHK(c, up(p, o_pf, pre_full, n * 8));
+    }
+    if (o_zend > o_flag) IOC_CHK(c, hipMemsetAsync(p + o_flag, 0, o_zend - o_flag, c->stream));  // (the flags, the records, the variant bytes and the recount's)
+    if (E) IOC_CHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p + o_agree), int(INT32_MIN), 2 * E, c->stream));
+    const IocWinVarDev v{t.v, p + o_flag, reinterpret_cast<int32_t*>(p + o_agree), reinterpret_cast<ioc_window_variant*>(p + o_var), p + o_variant};
+    const uint8_t* pool = static_cast<const uint8_t*>(c->a_pool.p);
+    const uint64_t pool_bytes = uint64_t(c->aln_offs.back());
+    auto agree_round = [&](const VariantRound& of, const uint64_t* d_at, size_t which) {
+        return iock_win_agree(c->stream, reinterpret_cast<const IocWinItem*>(of.q + of.at.items), d_at, uint32_t(of.w.items.size()), pool, pool_bytes, of.q + of.at.base,
+                              of.w.P, v.agree + which * E, v.flag + which * E, uint64_t(E), vo.rule.min_agree);
+    };
+    IOC_TRY(r.begin(r.t.ms_winvar[0]));
+    IOC_CHK(c, agree_round(ra, reinterpret_cast<const uint64_t*>(p + o_at), 0));
+    IOC_TRY(r.end());
+    IOC_TRY(r.begin(r.t.ms_winvar[1]));
+    IOC_CHK(c, iock_win_template_far(c->stream, v, vo.rule));
+    IOC_TRY(r.end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    r.settled();
+    std::vector<ioc_window_variant> var(ns);
+    std::vector<uint8_t> flag_a(E);
+    IOC_TRY(r.copy_out({{var.data(), p + o_var, ns * sizeof(ioc_window_variant)}, {flag_a.data(), p + o_flag, E}}));
+
+    // round B: the far voters of the sites that reach it against template B; and what the slots may need at most
+    auto far = [&](size_t i, size_t k) { return flag_a[i * t.stride + k] == WINVAR_FAR; };
+    if (windows_list_round(t, reads, o.rule.max_win, seg_of_pair, site_off,
+                           [&](size_t x, int32_t& pair, int32_t& tlen) { return pair = var[x].template_pair_b, tlen = var[x].tlen_b, pair >= 0; }, far, rb.site, rb.w))
+        return ioc_fail(c, IOC_ERR_HIP, "the variant kernels returned a template B that is no voter of its site");
+    VariantSlotsMost most;
+    for (size_t x = 0; x < ns; ++x) {
+        const size_t g = size_t(t.site_seg[x]), k = x - size_t(site_off[g]);
+        if (rb.site[x].t_len > 0 && (ra.site[x].t_len == 0 || !far(size_t(var[x].template_pair_b), k)))
+            return ioc_fail(c, IOC_ERR_HIP, "the variant kernels returned a template B that is no far voter of its site");
+        if (ra.site[x].t_len > 0) most.add(ra.site[x]);
+        if (ra.site[x].t_len > 0 && all) most.add(ra.site[x]);
+        if (rb.site[x].t_len > 0) most.add(rb.site[x]);
+    }
+    const size_t MB = rb.w.items.size();
+    most.members = 2 * MA + MB;
+    r.t.win_voters += int64_t(MA), r.t.win_voters_b += int64_t(MB);
+    Arena b;
+    rb.at = WinRoundAt::take(b, rb.w);
+    const size_t b_at = b.take(MB * 8);
+    const VariantSlotsAt slots_at = VariantSlotsAt::take(b, most, MA + MB);
+    IOC_TRY(ioc_reserve(c, c->a_winvar_b, b.size()));
+    rb.q = static_cast<uint8_t*>(c->a_winvar_b.p);
+    IOC_CHK(c, up(rb.q, b_at, rb.w.entry.data(), MB * 8));
+    IOC_TRY(windows_align(r, rb.q, rb.at, rb.w, o.rule, r.t.ms_winvar[2]));
+    IOC_TRY(r.begin(r.t.ms_winvar[0]));
+    IOC_CHK(c, agree_round(rb, reinterpret_cast<const uint64_t*>(rb.q + b_at), 1));
+    IOC_TRY(r.end());
+
+    // decide -> rekey -> the isoforms again
+    IocReadInsertsDev kv{};
+    kv.n_segs = uint32_t(n), kv.n_pairs = uint32_t(np), kv.seg_of_pair = t.v.seg_of_pair, kv.mem_off = t.v.mem_off, kv.members = t.v.members;
+    if (with_pre) {
+        kv.pre_key = reinterpret_cast<const unsigned long long*>(p + o_pk), kv.pre_mask = reinterpret_cast<const unsigned long long*>(p + o_pm);
+        kv.pre_full = reinterpret_cast<const unsigned long long*>(p + o_pf);
+    }
+    kv.pre_key_stride = kv.pre_mask_stride = 1;
+    kv.mask = reinterpret_cast<unsigned long long*>(p + o_mask), kv.flags = p + o_kflags, kv.reads = reinterpret_cast<ioc_read_inserts*>(p + o_reads);
+    KernelTimes each;
+    IOC_TRY(each.create(c, IOC_WIN_VARIANTS_KERNELS));
+    IOC_TRY(r.begin(r.t.ms_winvar[3], !each.on()));
+    IOC_CHK(c, iock_win_decide_rekey(c->stream, v, vo.rule, kv, reinterpret_cast<ioc_variants_seg*>(p + o_rec), each.events()));
+    IOC_TRY(r.end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    r.settled();
+    each.add_to(r.t.ms_winvar + 3);
+    std::vector<uint8_t> variant(E);
+    std::vector<int32_t> agree(vo.agree ? 2 * E : 0);
+    std::vector<ioc_read_inserts> rec(np);
+    IOC_TRY(r.copy_out({{var.data(), p + o_var, ns * sizeof(ioc_window_variant)}, {variant.data(), p + o_variant, E}, {rec.data(), p + o_reads, np * sizeof(ioc_read_inserts)},
+                        {vo.seg, p + o_rec, n * sizeof(ioc_variants_seg)}, {vo.agree ? agree.data() : nullptr, p + o_agree, 2 * E * 4}}));
+    for (size_t i = 0; i < np; ++i) {  // (the entries are `stride` a pair on the device, IOC_INSERTS_MAX a pair for the caller)
+        const size_t g = size_t(seg_of_pair[i]), kept = size_t(site_off[g + 1] - site_off[g]);
+        vo.reads[i] = ioc_read_variants{rec[i].key, rec[i].group, rec[i].how};
+        for (size_t k = 0; k < S; ++k) {
+            vo.variant[i * S + k] = k < kept ? variant[i * t.stride + k] : uint8_t(IOC_WINVAR_NONE);
+            for (size_t h = 0; h < 2 && vo.agree; ++h) vo.agree[(i * S + k) * 2 + h] = k < kept ? agree[h * E + i * t.stride + k] : INT32_MIN;
+        }
+    }
+    std::copy(t.win.begin(), t.win.end(), o.win);
+    std::copy(var.begin(), var.end(), vo.var);
+
+    const VariantSlots slots = VariantSlots::list(ra, rb, var, variant, all != nullptr);
+    if (!most.holds(slots)) return ioc_fail(c, IOC_ERR_HIP, "the variant kernels returned more slots than the sites of round B allow");
+    return variants_call_slots(r, slots, slots_at, ra, rb, o.call, ns, all);
+}
+
+static std::string variants_trace(const AlnTally& t)
+{
+    char buf[400];
+    snprintf(buf, sizeof buf, "k_win_agree %.3f ms, k_win_template_far %.3f ms, k_win_align_b %.3f ms, k_win_decide %.3f ms, k_win_rekey %.3f ms, k_winvar_support %.3f ms, "
+             "k_winvar_isoforms %.3f ms, k_winvar_record %.3f ms, %lld voters, %lld of them in round B",
+             t.ms_winvar[0], t.ms_winvar[1], t.ms_winvar[2], t.ms_winvar[3], t.ms_winvar[4], t.ms_winvar[5], t.ms_winvar[6], t.ms_winvar[7], (long long)t.win_voters,
+             (long long)t.win_voters_b);
     return buf;
 }
 }  // namespace
@@ -1808,6 +2182,39 @@ int ioc_planes_insert_windows(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, i
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   planes insert windows: %d segments, %d pairs, %lld sites, %lld bytes called, %s\n", n_segs, n_pairs, (long long)site_off[n_segs],
                 (long long)out_off[site_off[n_segs]], windows_trace(r.t).c_str());
+    return IOC_OK;
+}
+
+// upload -> windows and variants -> copy-out.  From planes, sites and keys the caller holds, over the pool that is set.
+int ioc_planes_insert_window_variants(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* query,
+                                      const uint8_t* base, const uint32_t* qpos, const ioc_pile_insert* sites, const int64_t* site_off, const uint64_t* keys, int32_t slack,
+                                      int32_t max_win, int32_t match, int32_t mismatch, int32_t gap, int32_t polish_min_depth, int32_t min_agree, int32_t min_alt,
+                                      int32_t min_pct, const uint64_t* pre_key, const uint64_t* pre_mask, const uint64_t* pre_full, ioc_insert_window* out_win,
+                                      ioc_window_variant* out_var, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_stats,
+                                      uint8_t* out_variant, int32_t* out_agree, ioc_read_variants* out_reads, ioc_variants_seg* out_seg)
+{
+    const std::string who = "ioc_planes_insert_window_variants";
+    const WindowsOut o{{slack, max_win, match, mismatch, gap}, {polish_min_depth, out_seq, out_qual, cap, out_off, out_stats}, out_win, nullptr, nullptr};
+    const VariantsOut vo{{min_agree, min_alt, min_pct}, out_var, out_variant, out_agree, out_reads, out_seg};
+    const bool some_pre = pre_key || pre_mask || pre_full, all_pre = pre_key && pre_mask && pre_full;
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || !vo.rule.ok() || !site_off || (n_segs > 0 && (!rlen || !out_seg)) ||
+        (n_pairs > 0 && (!seg_of_pair || !query || !keys || !out_variant || !out_reads)) || (some_pre && !all_pre))
+        return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen(who, n_segs, rlen, nullptr, nullptr, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !qpos)) return IOC_ERR_ARG;
+    WindowsReads reads;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        if (query[i] < 0 || size_t(query[i]) + 1 >= c->aln_offs.size()) return ioc_fail(c, IOC_ERR_ARG, who + ": the read of pair " + std::to_string(i) + " lies outside the pool");
+        reads.off.push_back(c->aln_offs[size_t(query[i])]), reads.len.push_back(uint32_t(ioc_seq_len(c, query[i])));
+    }
+    IOC_TRY(windows_ok(c, who, o, p, sites, site_off, 0, /*slots a site*/ 2));
+    if (site_off[n_segs] > 0 && !out_var) return IOC_ERR_ARG;
+    SinkRun r{c};
+    IOC_TRY(variants_device(r, p, seg_of_pair, reads, base, qpos, nullptr, nullptr, sites, site_off, keys, pre_key, pre_mask, pre_full, o, vo));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes insert window variants: %d segments, %d pairs, %lld sites, %lld bytes called, %s, %s\n", n_segs, n_pairs, (long long)site_off[n_segs],
+                (long long)out_off[2 * site_off[n_segs]], windows_trace(r.t).c_str(), variants_trace(r.t).c_str());
     return IOC_OK;
 }
 
@@ -1992,8 +2399,10 @@ int iso_full_ok(ioc_ctx* c, const std::string& who, const IsoFull& f, const Sink
 
 // pile -> blocks -> inserts -> windows -> copy-out.  ioc_align_pairs_blocks_inserts with the position plane projected beside the other
 // two, and behind the insert kernels the window kernels over the planes where they lie; the sites and the keys are on the host when
-// the insert stage returns and travel back with the tables (32 bytes a site, 8 a pair).
-static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+// the insert stage returns and travel back with the tables (32 bytes a site, 8 a pair).  vf (ioc_align_pairs_blocks_inserts_variants;
+// else NULL): the variant stage in the window stage's place, which returns the window call's outputs as well; the block stage's keys
+// are on the host by then and serve as pre_*, a read's mask being both bits of every block its key has a state at.
+static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, const VariantsFused* vf, ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
                                        int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
                                        const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
                                        int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
@@ -2013,6 +2422,13 @@ static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, 
     IOC_TRY(blocks_room_ok(c, who, o, p));
     IOC_TRY(inserts_room_ok(c, who, io, p));
     IOC_TRY(windows_ok(c, who, wo, p, nullptr, nullptr, inserts_bound(p, max_sites)));
+    if (vf) {
+        const WindowsOut vw{wo.rule, vf->call, out_win, nullptr, nullptr};
+        if (!vf->vo.rule.ok() || !vw.ok() || (n_pairs > 0 && (!vf->vo.variant || !vf->vo.reads)) || (n_segs > 0 && !vf->vo.seg)) return IOC_ERR_ARG;
+        IOC_TRY(windows_ok(c, who, vw, p, nullptr, nullptr, inserts_bound(p, max_sites), /*slots a site*/ 2));
+        if (inserts_bound(p, max_sites) > 0 && !vf->vo.var) return IOC_ERR_ARG;
+        vf->call.off[0] = 0;
+    }
     std::vector<int64_t> n_reads(size_t(n_segs), 0);
     if (full) {
         for (int32_t i = 0; i < n_pairs; ++i) ++n_reads[size_t(seg_of_pair[i])];
@@ -2047,7 +2463,30 @@ static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, 
         reads.off.push_back(c->aln_offs[size_t(pairs[i].query)]), reads.len.push_back(uint32_t(ioc_seq_len(c, pairs[i].query)));
         keys[size_t(i)] = out_ireads[i].key;
     }
-    IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
+    if (vf && site_off[n_segs] == 0) {
+        // no site kept anywhere: key2 is the key and the isoforms counted again are the insert stage's, which are on the host already
+        for (int32_t i = 0; i < n_pairs; ++i) {
+            vf->vo.reads[i] = ioc_read_variants{out_ireads[i].key, out_ireads[i].group, out_ireads[i].how};
+            std::fill(vf->vo.variant + size_t(i) * IOC_INSERTS_MAX, vf->vo.variant + (size_t(i) + 1) * IOC_INSERTS_MAX, uint8_t(IOC_WINVAR_NONE));
+            if (vf->vo.agree) std::fill(vf->vo.agree + size_t(i) * 2 * IOC_INSERTS_MAX, vf->vo.agree + (size_t(i) + 1) * 2 * IOC_INSERTS_MAX, INT32_MIN);
+        }
+        for (int32_t g = 0; g < n_segs; ++g) {
+            const ioc_inserts_seg& z = out_iseg[g];
+            vf->vo.seg[g] = ioc_variants_seg{0, 0, z.n_groups, z.n_reads, z.n_direct, z.n_assigned, z.n_rare, z.n_ambiguous};
+        }
+        IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
+    } else if (vf) {
+        std::vector<uint64_t> pk(size_t(n_pairs), 0), pm(size_t(n_pairs), 0);
+        for (int32_t i = 0; i < n_pairs; ++i) {
+            pk[size_t(i)] = out_reads[i].key;
+            for (uint32_t b = 0; b < uint32_t(out_seg[seg_of_pair[i]].n_blocks); ++b) pm[size_t(i)] |= blocks_state_mask(b, uint32_t(out_reads[i].key >> (2u * b)) & 3u);
+        }
+        const WindowsOut vw{wo.rule, vf->call, out_win, nullptr, nullptr};
+        IOC_TRY(variants_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), n_pairs > 0 ? pk.data() : nullptr,
+                                n_pairs > 0 ? pm.data() : nullptr, n_pairs > 0 ? pre_full.data() : nullptr, vw, vf->vo, &wo.call));
+        if (getenv("IOC_TRACE")) fprintf(stderr, "[ioc]   aligner: window variants: %lld bytes called, %s\n", (long long)vf->call.off[2 * site_off[n_segs]], variants_trace(r.t).c_str());
+    } else
+        IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
     if (full) {
         // the combined isoforms the insert stage just made, the first min(n_groups, max_iso) of a segment: their reads, and the key
         // of the lowest-numbered direct read of each (the records are on the host: they are one of the call's outputs)
@@ -2094,7 +2533,26 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_al
                                        int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
                                        int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats)
 {
-    return align_pairs_inserts_seq("ioc_align_pairs_blocks_inserts_seq", nullptr, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+    return align_pairs_inserts_seq("ioc_align_pairs_blocks_inserts_seq", nullptr, nullptr, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+}
+
+// ... -> inserts -> windows and variants -> copy-out.  ioc_align_pairs_blocks_inserts_seq with the variant kernels behind the window
+// kernels, over the planes where they lie.
+int ioc_align_pairs_blocks_inserts_variants(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                            int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                            const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                            int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                            int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                            int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                            int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                            int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
+                                            int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t min_agree, ioc_window_variant* out_var,
+                                            char* out_vseq, char* out_vqual, int64_t var_cap, int64_t* out_voff, ioc_polish_stats* out_vstats, uint8_t* out_variant,
+                                            int32_t* out_agree, ioc_read_variants* out_vreads, ioc_variants_seg* out_vseg)
+{
+    const VariantsFused vf{{{min_agree, min_alt, min_pct}, out_var, out_variant, out_agree, out_vreads, out_vseg}, {polish_min_depth, out_vseq, out_vqual, var_cap, out_voff, out_vstats}};
+    if (!out_voff) return IOC_ERR_ARG;
+    return align_pairs_inserts_seq("ioc_align_pairs_blocks_inserts_variants", nullptr, &vf, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
 }
 
 // ... -> windows -> groups pile over the combined isoforms -> splice -> copy-out.  ioc_align_pairs_blocks_inserts_seq with the six slot
@@ -2114,7 +2572,7 @@ int ioc_align_pairs_isoforms_full(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pai
 {
     const IsoFull full{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
     if (!full.ok()) return IOC_ERR_ARG;
-    return align_pairs_inserts_seq("ioc_align_pairs_isoforms_full", &full, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+    return align_pairs_inserts_seq("ioc_align_pairs_isoforms_full", &full, nullptr, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
 }
 
 // pile -> blocks -> groups pile -> call -> copy-out.  ioc_align_pairs_blocks with the six slot planes projected beside the two, and

@@ -196,7 +196,7 @@ int ioc_ctx_trim(ioc_ctx* c)
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     if (c->side_stream) IOC_CHK(c, hipStreamSynchronize(c->side_stream));
     // the aligner's arenas: checkpoints (8 GB for config 3's batch), tables, profiles, traceback scratch
-    for (DevBuf* b : {&c->a_ck, &c->a_cko, &c->a_prof, &c->a_bnd, &c->a_lrow, &c->a_xflags, &c->a_ends, &c->a_ends2, &c->a_ops, &c->a_pile, &c->a_pile_ins, &c->a_pile_w, &c->a_planes, &c->a_split, &c->a_gpile, &c->a_call, &c->a_correct, &c->a_blocks, &c->a_inserts, &c->a_rends, &c->a_windows, &c->a_splice}) b->release();
+    for (DevBuf* b : {&c->a_ck, &c->a_cko, &c->a_prof, &c->a_bnd, &c->a_lrow, &c->a_xflags, &c->a_ends, &c->a_ends2, &c->a_ops, &c->a_pile, &c->a_pile_ins, &c->a_pile_w, &c->a_planes, &c->a_split, &c->a_gpile, &c->a_call, &c->a_correct, &c->a_blocks, &c->a_inserts, &c->a_rends, &c->a_windows, &c->a_winvar, &c->a_winvar_b, &c->a_splice}) b->release();
     return IOC_OK;
 }
 

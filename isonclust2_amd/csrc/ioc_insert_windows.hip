@@ -10,8 +10,9 @@
 //                       bytes of the base plane where the pair carries, and the pair's class and window (win_class).
 //   k_win_template      a wave per site over the segment's members, 64 at a time: the three counts by ballot, then every voter's
 //                       rank as the number of voters with a smaller (length, pair) — the voters of a chunk are handed round the
-//                       wave one by one, unsigned compares —, and the voter of rank (n - 1) / 2 is the template.  Quadratic in a
-//                       site's voters, as the block stage's rank kernels are.
+//                       wave one by one, unsigned compares —, and the voter of rank (n - 1) / 2 is the template (win_lower_median,
+//                       ioc_win_stage.h, which k_win_template_far of ioc_window_variants.hip ranks the far voters with).  Quadratic
+//                       in a site's voters, as the block stage's rank kernels are.
 //   k_win_align         a wave per (voter, site), one wave a workgroup.  The fill: a lane per template column in strips of 64, the
 //                       rows skewed down the lanes (lane l is at row t - l + 1 in step t), the left neighbour's value by a shuffle
 //                       and the diagonal kept from the step before; a strip's last column goes to the next strip through 513 words
@@ -31,6 +32,7 @@
 #include "ioc_internal.h"
 #include "ioc_ops_pileup.h"
 #include "ioc_wave.h"
+#include "ioc_win_stage.h"
 
 namespace {
 
@@ -134,27 +136,12 @@ k_win_template(IocWinDev v, int32_t slack)
         n_short += uint32_t(__popcll(__ballot(cl == uint32_t(IOC_WIN_SHORT))));
         n_long += uint32_t(__popcll(__ballot(cl == uint32_t(IOC_WIN_LONG))));
     }
-    int32_t t_pair = -1, t_len = 0;
-    if (n_voters > 0u) {  // (the same in every lane, like everything the loops below branch on)
-        const uint32_t want = win_median_rank(n_voters);
-        for (uint32_t a0 = mb; a0 < me && t_pair < 0; a0 += 64u) {
-            uint32_t a_pair;
-            const uint32_t a = member(a0 + lane, a_pair);
-            const bool a_votes = win_slot_class(a) == uint32_t(IOC_WIN_VOTER);
-            if (!__ballot(a_votes)) continue;
-            uint32_t rank = 0;
-            for (uint32_t b0 = mb; b0 < me; b0 += 64u) {
-                uint32_t b_pair;
-                const uint32_t b = member(b0 + lane, b_pair);
-                for (u64 left = __ballot(win_slot_class(b) == uint32_t(IOC_WIN_VOTER)); left; left &= left - 1ull) {
-                    const uint32_t r = uint32_t(__builtin_ctzll(left));
-                    rank += win_voter_less(win_slot_len(shfl32(b, r)), shfl32(b_pair, r), win_slot_len(a), a_pair) ? 1u : 0u;
-                }
-            }
-            const u64 hit = __ballot(a_votes && rank == want);
-            if (hit) t_pair = int32_t(shfl32(a_pair, uint32_t(__builtin_ctzll(hit)))), t_len = int32_t(win_slot_len(shfl32(a, uint32_t(__builtin_ctzll(hit)))));
-        }
-    }
+    const WinMedian t = win_lower_median(mb, me, n_voters, [&](uint32_t m, uint32_t& pair, uint32_t& len) {
+        const uint32_t cl = member(m, pair);
+        len = win_slot_len(cl);
+        return win_slot_class(cl) == uint32_t(IOC_WIN_VOTER);
+    });
+    const int32_t t_pair = t.pair, t_len = t.len;
     if (lane == 0) {
         const long long first = v.sites[x].first, end = v.sites[x].end, rlen = v.segs[g].rlen;
         const bool ok = win_site_ok(first, end, rlen);

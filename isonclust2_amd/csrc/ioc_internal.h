@@ -229,6 +229,9 @@ struct ioc_ctx {
     DevBuf a_windows; // ioc_planes_insert_windows, ioc_align_pairs_blocks_inserts_seq: the tables, the (pair, site) entries and the records of
                       // k_win_bounds / k_win_template and, uploaded, both planes; the alignments' items, planes and direction words share a_gpile
                       // with the group pile behind them
+    DevBuf a_winvar;  // ioc_planes_insert_window_variants: the flags, agreements, records and variant bytes of ioc_window_variants.hip, key2 / mask2 and the
+                      // recount's records and, uploaded, pre_key / pre_mask / pre_full and round A's entries; round A's alignments lie in a_gpile
+    DevBuf a_winvar_b; // ... round B's items, entries, planes and direction words, and the group pile of the (site, variant) slots behind both rounds
     DevBuf a_rends;   // ioc_reads_ends, ioc_align_pairs_blocks_ends: the tables, histograms, bit planes and records of ioc_read_ends.hip and, uploaded,
                       // the extents and pre_group
     DevBuf a_splice;  // ioc_planes_isoforms_full, ioc_align_pairs_isoforms_full: keys, windows, plans, records and the spliced bytes (ioc_iso_splice.hip)
@@ -576,6 +579,31 @@ hipError_t iock_win_bounds_template(hipStream_t st, const IocWinDev& v, int32_t 
 hipError_t iock_win_align(hipStream_t st, const IocWinItem* items, uint32_t n_items, const uint8_t* pool, uint64_t pool_bytes, uint8_t* base_planes,
                           uint8_t* slot_planes, uint64_t plane_bytes, uint32_t* dir, uint64_t n_dir_words, int32_t match, int32_t mismatch, int32_t gap,
                           int phase);
+
+// ioc_window_variants.hip: two exons at one junction (ioc_host_insert_window_variants per segment) behind the window kernels.
+// Everything is a device pointer.  `w` is the window stage's view as k_win_bounds and k_win_template left it; an entry is a (pair,
+// site) place of its table, w.n_slots of them.  Round r (0: against template A, 1: against template B) leaves entry e's flag at
+// flag[r * n_slots + e] (WINVAR_*, ioc_window_variants.h; set to 0 by the caller) and its agreement at agree[r * n_slots + e] (set
+// to INT32_MIN by the caller); var: a record per site; variant: a byte per entry.
+struct IocWinVarDev {
+    IocWinDev w;
+    uint8_t* flag;
+    int32_t* agree;
+    ioc_window_variant* var;
+    uint8_t* variant;
+};
+struct WinVarRule;
+// k_win_agree over the items of a round that k_win_align has run over: item x's entry is at[x]
+hipError_t iock_win_agree(hipStream_t st, const IocWinItem* items, const uint64_t* at, uint32_t n_items, const uint8_t* pool, uint64_t pool_bytes,
+                          const uint8_t* base_planes, uint64_t plane_bytes, int32_t* agree, uint8_t* flag, uint64_t n_entries, int32_t min_agree);
+// k_win_template_far: n_far and template B of every site where round B runs, into var
+hipError_t iock_win_template_far(hipStream_t st, const IocWinVarDev& v, const WinVarRule& rule);
+// k_win_decide, k_win_rekey and the isoform count over key2 / mask2, in a row on `st`.  `k` is the view the key functions of
+// ioc_read_stage.h read: n_segs, n_pairs, seg_of_pair, mem_off, members, pre_*, reads (key: key2, set to 0 by the caller), mask, flags;
+// seg_out: a record per segment.  `each` (IOC_WIN_VARIANTS_KERNELS + 1 events, or NULL) as for iock_read_inserts.
+enum { IOC_WIN_VARIANTS_KERNELS = 5 };
+hipError_t iock_win_decide_rekey(hipStream_t st, const IocWinVarDev& v, const WinVarRule& rule, const IocReadInsertsDev& k, ioc_variants_seg* seg_out,
+                                 hipEvent_t* each);
 
 // ioc_iso_splice.hip: the full-length sequence of every isoform (ioc_host_isoform_splice per group-segment).  Everything is a device
 // pointer.  Group-segment x (n_gsegs of them) is gsegs[x], belongs to segment gseg_seg[x] and carries keys[x]; segment g has the

@@ -1,5 +1,5 @@
 // ioc_read_stage.h — the bodies that the three read stages over bit planes share (ioc_read_blocks.hip, ioc_read_inserts.hip,
-// ioc_read_ends.hip), each written once: the words of a segment, the windowed sum of 128 counts, the sweep that lists the runs of
+// ioc_read_ends.hip; the key functions serve ioc_window_variants.hip as well, over key2), each written once: the words of a segment, the windowed sum of 128 counts, the sweep that lists the runs of
 // a plane into slots, the per-row counts over a segment's members, the masked popcounts of a slot's rows, and the keys of blocks
 // and inserts — support, rank, isoform and the record's tallies.  Device code only.  A function here takes values and pointers, or
 // the stage's view where the fields it reads have the same names in both; none takes a flag that says which stage is calling.

@@ -1,5 +1,5 @@
 // ioc_wave.h — what passes from lane to lane of a 64-lane wave in the stages behind the aligner (pile_sites, pile_call, site_split,
-// read_correct, read_blocks, read_inserts, read_ends, insert_windows, iso_splice): shuffles of 32 and 64 bits, the inclusive scan
+// read_correct, read_blocks, read_inserts, read_ends, insert_windows, window_variants, iso_splice): shuffles of 32 and 64 bits, the inclusive scan
 // and the reductions, each written once.  Device code only; every lane of the wave has to take part in every call.
 //
 // wave_scan_incl is the shuffle form: six __shfl_up steps.  ioc_kdev.h has wave_incl_scan, the data-parallel-move form that the
