@@ -1442,8 +1442,9 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* ctx, int32_t n_pairs, const ioc_
  * different exons: 57 / 33 at 60 and 60 bases, 59 / 31 at 60 and 45, 61 / 22 at 120 and 100.  At 30 bases and below the ranges
  * overlap (49 / 42), at 15 % errors they touch (35 / 31): exons under about 40 bases and reads beyond about 10 % errors are outside
  * what the default separates.
- * What stays out: the splice (ioc_host_isoform_splice reads state 2 as "does not carry"), more than two variants, a
- * quality-weighted variant call and re-clustering.  State 2 appears in the outputs of the calls of this section alone. */
+ * What stays out: more than two variants, a quality-weighted variant call and re-clustering.  ioc_host_isoform_splice reads state 2
+ * as "does not carry"; the splice that takes each variant's own slot is ioc_host_isoform_splice_variants, further down.  State 2
+ * appears in the outputs of the calls of this section alone. */
 #define IOC_INS_CARRY_B 2
 #define IOC_WINVAR_NONE 0    /* a read's variant at a site: no voter; variant A; variant B; a voter near neither template */
 #define IOC_WINVAR_A 1
@@ -1630,6 +1631,66 @@ int ioc_align_pairs_isoforms_full(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_p
                                   char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
                                   ioc_splice_stats* out_sstats, ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off,
                                   int64_t iso_cap, int64_t* iso_off);
+
+/* ---- The full-length sequence by variant: every exon's own window spliced in ----
+ * ioc_host_isoform_splice over the variant stage's outputs.  Its inputs are that function's, except that
+ *   key is a read's key2 (ioc_read_variants.key2);
+ *   var holds the segment's ioc_window_variant records beside win (split and tlen_b are read);
+ *   slot_seq / slot_qual / slot_off are the variant stage's slots in place of one window a site: 2 n_sites + 1 entries, slot 2 b
+ *   is site b's variant A and 2 b + 1 its B.
+ * Rule 1 becomes, for site b in ascending order with state s = (key >> 2 b) & 3: s == IOC_INS_CARRY takes slot 2 b and the template
+ * length win[b].tlen; s == IOC_INS_CARRY_B takes slot 2 b + 1 and the template length var[b].split ? var[b].tlen_b : 0 (a key that
+ * claims B where nothing split makes the site UNCALLED, not an error); any other state is IOC_SPLICE_LACK.  Then as before:
+ * UNCALLED where that template length is 0, OVERLAP where lo lies below the hi of the last DONE site (lo and hi are the site's, the
+ * same for both variants), otherwise DONE.  Rules 2 and 3, the records, the statistics and the capacity rule are
+ * ioc_host_isoform_splice's with "the window" read as "the slot's bytes"; which variant a DONE site took is the key's state there.
+ * Put differently: the result is ioc_host_isoform_splice over the key with every 2 turned into 1, win with tlen replaced as above
+ * and the chosen slot of every site as that site's window.  IOC_ERR_ARG for what ioc_host_isoform_splice refuses, a NULL var with
+ * n_sites > 0, a slot_off that does not ascend, a var[b].split outside 0 / 1 and a negative tlen_b; IOC_ERR_CAPACITY for cap below
+ * rlen + IOC_PILE_INS_SLOTS * (rlen + 1) + slot_off[2 n_sites] - slot_off[0]; nothing is written on any. */
+int64_t ioc_host_isoform_splice_variants(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth,
+                                         uint64_t key, const ioc_insert_window* win, const ioc_window_variant* var, int32_t n_sites,
+                                         const char* slot_seq, const char* slot_qual, const int64_t* slot_off, char* out_seq, char* out_qual,
+                                         int64_t cap, ioc_polish_stats* st, ioc_splice_site* out_sites, ioc_splice_stats* out_sstats);
+/* ioc_planes_isoforms_full by variant: its arguments, except that iso_key holds a key2 per group-segment, var is packed with site_off
+ * like win, and slot_seq / slot_qual / slot_off (2 site_off[n_segs] + 1 entries, as ioc_planes_insert_window_variants returns them)
+ * stand in place of win_seq / win_qual / win_off.  Group-segment (g, h) is ioc_host_isoform_splice_variants over the tables
+ * ioc_host_planes_pile makes of its pairs.  The kernels are ioc_planes_isoforms_full's; the plan kernel runs in its slot-aware
+ * instantiation (a lane loads its window record, its variant record and both ends of its chosen slot), the call passes are the same
+ * code.  The refusals and the capacity rule are ioc_planes_isoforms_full's, with "the bytes of g's windows" read as the bytes of g's
+ * slots, plus what the definition refuses about var and slot_off (which must ascend from 0). */
+int ioc_planes_isoforms_full_variants(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                                      const int32_t* n_groups, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group,
+                                      const uint8_t* base, const uint8_t* slots, const uint64_t* iso_key, const ioc_insert_window* win,
+                                      const ioc_window_variant* var, const int64_t* site_off, const char* slot_seq, const char* slot_qual,
+                                      const int64_t* slot_off, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                                      ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats, ioc_splice_site* out_splice,
+                                      int64_t splice_cap, int64_t* splice_off, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins);
+/* ioc_align_pairs_blocks_inserts_variants and ioc_align_pairs_isoforms_full in one fused call: the arguments of the first followed by
+ * max_iso and the isoform outputs of the second.  The six slot planes are projected as for the full call; the isoforms piled are
+ * those counted again (ioc_read_variants.group: the first min(ioc_variants_seg.n_groups, max_iso) of a segment, direct and assigned
+ * reads), the key of isoform h is key2 of its lowest-numbered direct read, and the splice runs the slot-aware plan over the slots the
+ * same call just made.  Everything ioc_align_pairs_blocks_inserts_variants returns comes back byte for byte.  Where no site is kept
+ * anywhere, and where sites are kept and none splits (key2 == key, slot 2 b is the window call's consensus), the isoform outputs are
+ * ioc_align_pairs_isoforms_full's byte for byte.  iso_cap, splice_cap and cap follow ioc_align_pairs_isoforms_full's formulas — one
+ * slot a site is taken, and a slot holds at most 7 max_win + 6 bytes, so a cap that passes before the call is never refused behind
+ * the variant stage —, var_cap is the variant call's.  Every pair is aligned, piled and projected once, every voter aligned once
+ * a round.  The refusals of both calls; nothing is written. */
+int ioc_align_pairs_isoforms_full_variants(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                           int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats,
+                                           int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth,
+                                           int32_t min_alt, int32_t min_pct, int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows,
+                                           ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off, ioc_read_blocks* out_reads,
+                                           ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins, int32_t slack, int32_t max_sites,
+                                           ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap, int64_t* site_off,
+                                           ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                           int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq,
+                                           char* out_wqual, int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t min_agree,
+                                           ioc_window_variant* out_var, char* out_vseq, char* out_vqual, int64_t var_cap, int64_t* out_voff,
+                                           ioc_polish_stats* out_vstats, uint8_t* out_variant, int32_t* out_agree, ioc_read_variants* out_vreads,
+                                           ioc_variants_seg* out_vseg, int32_t max_iso, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
+                                           ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats, ioc_splice_site* out_splice,
+                                           int64_t splice_cap, int64_t* splice_off, int64_t iso_cap, int64_t* iso_off);
 
 /* ---- Alternative ends: where the reads of a cluster start and stop on their representative, and the variants that makes ----
  * A read that starts late or stops early has state IOC_BLOCK_NONE at the blocks it does not reach; this stage says where the ends

@@ -260,6 +260,7 @@ SYMBOLS = [
     "ioc_host_ops_project_qpos", "ioc_host_align_global_ops", "ioc_host_insert_windows", "ioc_planes_insert_windows", "ioc_align_pairs_blocks_inserts_seq",
     "ioc_host_ops_agreement", "ioc_host_key_isoforms", "ioc_host_insert_window_variants", "ioc_planes_insert_window_variants", "ioc_align_pairs_blocks_inserts_variants",
     "ioc_host_isoform_splice", "ioc_planes_isoforms_full", "ioc_align_pairs_isoforms_full",
+    "ioc_host_isoform_splice_variants", "ioc_planes_isoforms_full_variants", "ioc_align_pairs_isoforms_full_variants",
     "ioc_host_ops_extent", "ioc_host_reads_ends", "ioc_reads_ends", "ioc_align_pairs_blocks_ends",
 ]
 
@@ -455,6 +456,13 @@ def load():
                                            C.c_void_p]
     L.ioc_align_pairs_isoforms_full.argtypes = L.ioc_align_pairs_blocks_inserts_seq.argtypes + [i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p,
                                                                                                C.c_void_p, i64, pi64, i64, pi64]
+    a = L.ioc_host_isoform_splice.argtypes
+    L.ioc_host_isoform_splice_variants.argtypes = a[:7] + [C.c_void_p] + a[7:]   # (var behind win)
+    L.ioc_host_isoform_splice_variants.restype = C.c_int64
+    a = L.ioc_planes_isoforms_full.argtypes
+    L.ioc_planes_isoforms_full_variants.argtypes = a[:13] + [C.c_void_p] + a[13:]   # (var behind win)
+    n_seq = len(L.ioc_align_pairs_blocks_inserts_seq.argtypes)
+    L.ioc_align_pairs_isoforms_full_variants.argtypes = L.ioc_align_pairs_blocks_inserts_variants.argtypes + L.ioc_align_pairs_isoforms_full.argtypes[n_seq:]
     L.ioc_host_ops_extent.argtypes = [C.c_char_p, i64, i32, C.POINTER(ReadExtent)]
     L.ioc_host_reads_ends.argtypes = [C.c_void_p, C.c_void_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]

@@ -717,6 +717,31 @@ def isoform_splice(cols, ins, frame, key, win, win_seq, min_depth=3, cap=None):
             {f: int(getattr(ss, f)) for f in SPLICE_STATS_FIELDS})
 
 
+def isoform_splice_variants(cols, ins, frame, key2, win, var, slot_seq, min_depth=3, cap=None):
+    """ioc_host_isoform_splice_variants: isoform_splice by variant — `key2` a read's second key (READ_VARIANTS_DTYPE), `var` the
+    segment's WINDOW_VARIANT_DTYPE records beside `win`, slot_seq a (sequence, qualities) pair of bytes per SLOT, 2 b site b's variant
+    A and 2 b + 1 its B, as insert_window_variants returns them.  A site whose state is INS_CARRY takes slot 2 b, one whose state is
+    INS_CARRY_B slot 2 b + 1 (UNCALLED where the site did not split).  Returns what isoform_splice returns."""
+    rlen = len(frame)
+    cols, ins = _tables(cols, ins, rlen + 1)
+    w, v = np.ascontiguousarray(win, INSERT_WINDOW_DTYPE), np.ascontiguousarray(var, WINDOW_VARIANT_DTYPE)
+    S = len(w)
+    if len(v) != S or len(slot_seq) != 2 * S or any(len(s) != len(q) for s, q in slot_seq):
+        raise ValueError("var must hold a record per site and slot_seq a (sequence, qualities) pair of equal lengths per slot, two a site")
+    soff = np.concatenate([[0], np.cumsum([len(s) for s, _ in slot_seq])]).astype(np.int64)
+    sseq, squal = b"".join(bytes(s) for s, _ in slot_seq), b"".join(bytes(q) for _, q in slot_seq)
+    cap = isoform_splice_bound(rlen, soff[-1]) if cap is None else int(cap)
+    seq, qual, st, ss = C.create_string_buffer(max(cap, 1)), C.create_string_buffer(max(cap, 1)), _lib.PolishStats(), _lib.SpliceStats()
+    rec = np.full(max(S, 1), -7, SPLICE_SITE_DTYPE)
+    n = _lib.load().ioc_host_isoform_splice_variants(cols.ctypes.data, ins.ctypes.data, bytes(frame), rlen, int(min_depth), int(key2), w.ctypes.data if S else None,
+                                                     v.ctypes.data if S else None, S, sseq, squal, soff.ctypes.data, seq, qual, cap, C.byref(st), rec.ctypes.data,
+                                                     C.byref(ss))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_isoform_splice_variants")
+    return (seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in POLISH_STATS_FIELDS}, rec[:S],
+            {f: int(getattr(ss, f)) for f in SPLICE_STATS_FIELDS})
+
+
 def pileup_sites(cols, min_depth=3, min_alt=3, min_pct=25, max_sites=4096):
     """ioc_host_pileup_sites: the variable sites of one reference from its table of counts (rlen + 1 rows of PILEUP_DTYPE) —
     returns (sites, n_found): the first max_sites sites (PILE_SITE_DTYPE), insertion site before base site row by row, and how
@@ -1589,8 +1614,8 @@ class Context:
             f_pol, f_sst = np.zeros(max(f_iso, 1), POLISH_STATS_DTYPE), np.zeros(max(f_iso, 1), SPLICE_STATS_DTYPE)
             f_splice = np.zeros(max(f_rec, 1), SPLICE_SITE_DTYPE)
             entry = self.L.ioc_align_pairs_isoforms_full
-            more = (int(_full["max_iso"]), f_seq.ctypes.data, f_qual.ctypes.data, f_cap, _p(f_off, C.c_int64), f_pol.ctypes.data, f_sst.ctypes.data,
-                    f_splice.ctypes.data, f_rec, _p(f_spoff, C.c_int64), f_iso, _p(f_ioff, C.c_int64))
+            more_full = more = (int(_full["max_iso"]), f_seq.ctypes.data, f_qual.ctypes.data, f_cap, _p(f_off, C.c_int64), f_pol.ctypes.data, f_sst.ctypes.data,
+                                f_splice.ctypes.data, f_rec, _p(f_spoff, C.c_int64), f_iso, _p(f_ioff, C.c_int64))
         if _variants is not None:   # (align_pairs_blocks_inserts_variants: the same call with the variants' outputs behind it)
             v_cap = insert_window_variants_bound(S, max_win) if _variants["cap"] is None else int(_variants["cap"])
             v_var, v_off, v_pol = np.zeros(max(S, 1), WINDOW_VARIANT_DTYPE), np.zeros(2 * S + 1, np.int64), np.zeros(max(2 * S, 1), POLISH_STATS_DTYPE)
@@ -1600,6 +1625,8 @@ class Context:
             entry = self.L.ioc_align_pairs_blocks_inserts_variants
             more = (int(_variants["min_agree"]), v_var.ctypes.data, v_seq.ctypes.data, v_qual.ctypes.data, v_cap, _p(v_off, C.c_int64), v_pol.ctypes.data,
                     v_variant.ctypes.data, v_agree.ctypes.data, v_reads.ctypes.data, v_seg.ctypes.data)
+            if _full is not None:   # (align_pairs_isoforms_full_variants: both, the variants' outputs first)
+                entry, more = self.L.ioc_align_pairs_isoforms_full_variants, more + more_full
         self._chk(entry(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
                                                             _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
                                                             _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
@@ -1641,6 +1668,16 @@ class Context:
         (without tables; `gseg_off` is iso_off).  polish_min_depth serves the windows and the isoforms; full_cap, iso_cap and
         splice_cap default to isoforms_full_bound of the segments."""
         return self.align_pairs_blocks_inserts_seq(pairs, k, segs, seg_of_pair, _full=dict(max_iso=max_iso, cap=full_cap, iso_cap=iso_cap, splice_cap=splice_cap), **kw)
+
+    def align_pairs_isoforms_full_variants(self, pairs, k, segs, seg_of_pair, max_iso=16, min_agree=VARIANTS_RULE["min_agree"], var_cap=None, full_cap=None,
+                                           iso_cap=None, splice_cap=None, **kw):
+        """ioc_align_pairs_isoforms_full_variants: align_pairs_blocks_inserts_variants and align_pairs_isoforms_full in one fused call —
+        the isoforms are those the variant stage counted again, each keyed by key2 of its lowest-numbered direct read, and every
+        carried site's window is the slot of the variant the isoform holds there.  Returns align_pairs_blocks_inserts_variants' dict,
+        byte for byte, and `isoforms_full` as align_pairs_isoforms_full shapes it; full_cap, iso_cap and splice_cap default to
+        isoforms_full_bound of the segments."""
+        return self.align_pairs_blocks_inserts_seq(pairs, k, segs, seg_of_pair, _variants=dict(min_agree=min_agree, cap=var_cap),
+                                                   _full=dict(max_iso=max_iso, cap=full_cap, iso_cap=iso_cap, splice_cap=splice_cap), **kw)
 
     def align_pairs_blocks(self, pairs, k, segs, seg_of_pair, stats=False, tables=False, rows=True, cap=None, match=2, mismatch=-2, gap_extend=1, **rule):
         """ioc_align_pairs_blocks: align_pairs, the table of counts, every pair's base plane and the block search over the planes, all
@@ -1800,7 +1837,7 @@ class Context:
         return out
 
     def planes_isoforms_full(self, frames, seg_of_pair, group, n_groups, base, slots, iso_key, win, win_seq, win_qual, min_depth=3, tables=False, cap=None,
-                             splice_cap=None):
+                             splice_cap=None, _var=None):
         """ioc_planes_isoforms_full: the full-length sequence of every group of every segment on the device, from host planes —
         planes_polish_groups with, per group-segment, `iso_key` (the insert key of its direct reads, group-segment order) and, per
         segment, `win` (an INSERT_WINDOW_DTYPE array, a record per kept site) and `win_seq` / `win_qual` (a list of bytes per site) as
@@ -1808,6 +1845,7 @@ class Context:
         group-segment), `splice` (per group-segment a SPLICE_SITE_DTYPE array, a record per site of its segment) and `splice_off` —
         each group-segment as isoform_splice defines it on the tables planes_pile adds up from the group's reads."""
         ns, n = len(frames), len(base)
+        per_site = 1 if _var is None else 2   # (planes_isoforms_full_variants: win_seq / win_qual hold two slots a site)
         rlen = np.array([len(f) for f in frames], np.int32)
         sop, grp, ng = np.ascontiguousarray(seg_of_pair, np.int32), np.ascontiguousarray(group, np.int32), np.ascontiguousarray(n_groups, np.int32)
         if sop.shape != (n,) or grp.shape != (n,) or len(slots) != n or ng.shape != (ns,) or len(win) != ns or len(win_seq) != ns or len(win_qual) != ns:
@@ -1828,7 +1866,7 @@ class Context:
         if keys.shape != (G,):
             raise ValueError("iso_key must hold one key per group-segment")
         for g in range(ns):
-            if len(win_seq[g]) != len(win[g]) or len(win_qual[g]) != len(win[g]) or any(len(s) != len(q) for s, q in zip(win_seq[g], win_qual[g])):
+            if len(win_seq[g]) != per_site * len(win[g]) or len(win_qual[g]) != per_site * len(win[g]) or any(len(s) != len(q) for s, q in zip(win_seq[g], win_qual[g])):
                 raise ValueError(f"the windows of segment {g} are not one sequence and one string of qualities per site")
         n_sites = np.array([len(w) for w in win], np.int64)
         soff = np.concatenate([[0], np.cumsum(n_sites)]).astype(np.int64)
@@ -1837,7 +1875,7 @@ class Context:
         flat = [bytes(s) for g in range(ns) for s in win_seq[g]]
         woff = np.concatenate([[0], np.cumsum([len(s) for s in flat])]).astype(np.int64)
         wseq, wqual = b"".join(flat), b"".join(bytes(q) for g in range(ns) for q in win_qual[g])
-        wbytes = [int(woff[soff[g + 1]] - woff[soff[g]]) for g in range(ns)]
+        wbytes = [int(woff[per_site * soff[g + 1]] - woff[per_site * soff[g]]) for g in range(ns)]
         bound = sum(int(groups[g]) * isoform_splice_bound(rlen[g], wbytes[g]) for g in range(ns))
         cap = bound if cap is None else int(cap)
         R = int((groups * n_sites).sum())
@@ -1850,9 +1888,15 @@ class Context:
         gcols, gins = (np.zeros(n_rows, PILEUP_DTYPE), np.zeros(n_rows, PILEUP_INS_DTYPE)) if tables else (None, None)
         pad = lambda a: np.concatenate([a, np.zeros(1, a.dtype)])  # (never an empty array's pointer)
         keys, wrec = pad(keys), pad(wrec)
-        self._chk(self.L.ioc_planes_isoforms_full(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+        entry, var_arg = self.L.ioc_planes_isoforms_full, ()
+        if _var is not None:
+            if len(_var) != ns or any(len(_var[g]) != len(win[g]) for g in range(ns)):
+                raise ValueError("var must hold a record per site of every segment")
+            vrec = pad(np.ascontiguousarray(np.concatenate([np.zeros(0, WINDOW_VARIANT_DTYPE)] + [np.asarray(v, WINDOW_VARIANT_DTYPE) for v in _var])))
+            entry, var_arg = self.L.ioc_planes_isoforms_full_variants, (vrec.ctypes.data,)
+        self._chk(entry(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
                                                   _p(ng, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, _p(grp, C.c_int32) if n else None,
-                                                  fb.ctypes.data if P else None, fs.ctypes.data if P else None, keys.ctypes.data, wrec.ctypes.data,
+                                                  fb.ctypes.data if P else None, fs.ctypes.data if P else None, keys.ctypes.data, wrec.ctypes.data, *var_arg,
                                                   _p(soff, C.c_int64), wseq, wqual, _p(woff, C.c_int64), int(min_depth), seq.ctypes.data, qual.ctypes.data, cap,
                                                   _p(off, C.c_int64), pol.ctypes.data, sst.ctypes.data, rec.ctypes.data, splice_cap, _p(spoff, C.c_int64),
                                                   gcols.ctypes.data if tables and n_rows else None, gins.ctypes.data if tables and n_rows else None))
@@ -1861,6 +1905,15 @@ class Context:
         if tables:
             out.update(gcols=gcols, gins=gins, grow0=np.concatenate([[0], np.cumsum(per)])[:G].astype(np.int64))
         return out
+
+    def planes_isoforms_full_variants(self, frames, seg_of_pair, group, n_groups, base, slots, iso_key, win, var, slot_seq, slot_qual, min_depth=3, tables=False,
+                                      cap=None, splice_cap=None):
+        """ioc_planes_isoforms_full_variants: planes_isoforms_full by variant — `iso_key` holds a key2 per group-segment, `var` per
+        segment a WINDOW_VARIANT_DTYPE array beside `win`, and slot_seq / slot_qual per segment a list of bytes per SLOT (2 b: site b's
+        variant A, 2 b + 1: its B) as planes_insert_window_variants returned them.  Returns planes_isoforms_full's dict, each
+        group-segment as isoform_splice_variants defines it."""
+        return self.planes_isoforms_full(frames, seg_of_pair, group, n_groups, base, slots, iso_key, win, slot_seq, slot_qual, min_depth=min_depth, tables=tables,
+                                         cap=cap, splice_cap=splice_cap, _var=var)
 
     def align_pairs_blocks_polish(self, pairs, k, segs, seg_of_pair, max_iso=16, polish_min_depth=3, stats=False, tables=False, rows=True, cap=None,
                                   polish_cap=None, iso_cap=None, match=2, mismatch=-2, gap_extend=1, _entry="ioc_align_pairs_blocks_polish", **rule):

@@ -63,7 +63,7 @@ void print_dump_help()
          << "                     [--isoforms-polish [--isoforms-polish-min-depth N] [--isoforms-polish-max N] [--isoforms-polish-weighted]]" << endl
          << "                     [--isoforms-inserts [--isoforms-min-ins N] [--isoforms-ins-slack N] [--isoforms-ins-max N]" << endl
          << "                     [--isoforms-inserts-seq [--isoforms-inserts-max-win N] [--isoforms-full [--isoforms-full-max N]]" << endl
-         << "                      [--isoforms-inserts-variants [--isoforms-inserts-variants-min-agree N]]]]" << endl
+         << "                      [--isoforms-inserts-variants [--isoforms-inserts-variants-min-agree N] [--isoforms-full-variants]]]]" << endl
          << "                     [--isoforms-ends [--isoforms-ends-slack N] [--isoforms-ends-min-over N] [--isoforms-ends-min-pct P]" << endl
          << "                     [--isoforms-ends-max N] [--isoforms-ends-max-variants N]]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
@@ -156,7 +156,7 @@ void print_dump_help()
          << "                 variant A being the one of the site's template; per read its variant at every site ('A', 'B', 'o' a voter near neither," << endl
          << "                 '.' no voter), its signature with the variants told apart ('=' lack, 'A' / 'B' carry, '.' not across or unknown) and its" << endl
          << "                 isoform counted again over blocks and sites.  The files that exist stay what they are.  Not offered together with" << endl
-         << "                 --isoforms-full: the splice reads one window a site" << endl
+         << "                 --isoforms-full: the splice reads one window a site (--isoforms-full-variants splices each variant's own)" << endl
          << "  --isoforms-inserts-variants-min-agree N  a voter is near a template where matches minus mismatches minus gaps of its alignment reach N" << endl
          << "                 percent of the longer of the two, 1 .. 100 (default 45: a choice made on simulated windows at 8 % errors, not measured on" << endl
          << "                 real data; exons under about 40 bases and reads beyond about 10 % errors are outside what it separates)" << endl
@@ -166,6 +166,11 @@ void print_dump_help()
          << "                 representative's frame with, for every site the isoform carries, the site's record of cluster_inserts.fq in place of" << endl
          << "                 the rows it stands for (len bases from base at on) - the isoform's full-length sequence" << endl
          << "  --isoforms-full-max N   call the first N isoforms of a cluster (default 16)" << endl
+         << "  --isoforms-full-variants  with --isoforms-inserts-variants: also write outdir/cluster_isoforms_full_variants.fq, from the same alignments:" << endl
+         << "                 the records of cluster_isoforms_full.fq for the isoforms counted again over the variants, the sites half of key= in the" << endl
+         << "                 letters of read_insert_variants.tsv ('=', 'A', 'B', '.'), and every site the isoform carries as ins<b>/<A|B>@<at>+<len>:" << endl
+         << "                 the record of cluster_insert_variants.fq that stands there - two exons at one junction, each in its own transcript." << endl
+         << "                 --isoforms-full-max applies.  Not offered together with --isoforms-full: one fused call a run" << endl
          << "  --isoforms-min-ins N    a read carries an insertion at a junction where the bases it inserts within --isoforms-ins-slack junctions" << endl
          << "                 sum to at least N, 1 .. 255 (default 20: a choice that was not measured on real data)" << endl
          << "  --isoforms-ins-slack N  ... the junctions on either side that count, 0 .. 32 (default 8: at 8 % errors the aligner breaks a 40-base" << endl
@@ -216,7 +221,8 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms-ends-slack", required_argument, 0, 1041}, {"isoforms-ends-min-over", required_argument, 0, 1042},
                                        {"isoforms-ends-min-pct", required_argument, 0, 1043}, {"isoforms-ends-max", required_argument, 0, 1044},
                                        {"isoforms-ends-max-variants", required_argument, 0, 1045}, {"isoforms-inserts-variants", no_argument, 0, 1046},
-                                       {"isoforms-inserts-variants-min-agree", required_argument, 0, 1047}, {0, 0, 0, 0}};
+                                       {"isoforms-inserts-variants-min-agree", required_argument, 0, 1047},
+                                       {"isoforms-full-variants", no_argument, 0, 1048}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false, iso_polish = false;
@@ -275,6 +281,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1045: r.isoforms.ends_max_variants = number("--isoforms-ends-max-variants", optarg, 1, INT32_MAX); break;
             case 1046: r.isoforms.variants = true; break;
             case 1047: r.isoforms.variants_min_agree = number("--isoforms-inserts-variants-min-agree", optarg, 1, 100); break;
+            case 1048: r.isoforms.full_variants = true; break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -293,7 +300,9 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (r.isoforms.inserts_seq && !r.isoforms.inserts) die("--isoforms-inserts-seq asks for --isoforms-inserts!");
     if (r.isoforms.full && !r.isoforms.inserts_seq) die("--isoforms-full asks for --isoforms-inserts-seq!");
     if (r.isoforms.variants && !r.isoforms.inserts_seq) die("--isoforms-inserts-variants asks for --isoforms-inserts-seq!");
+    if (r.isoforms.full_variants && r.isoforms.full) die("--isoforms-full-variants is not offered together with --isoforms-full: one fused call a run!");
     if (r.isoforms.variants && r.isoforms.full) die("--isoforms-inserts-variants is not offered together with --isoforms-full!");
+    if (r.isoforms.full_variants && !r.isoforms.variants) die("--isoforms-full-variants asks for --isoforms-inserts-variants!");
     if (r.isoforms.ends && !r.isoforms.on) die("--isoforms-ends asks for --isoforms!");
     if (r.isoforms.ends && r.isoforms.inserts) die("--isoforms-ends is not offered together with --isoforms-inserts!");
     if (r.isoforms.ends && iso_polish) die("--isoforms-ends is not offered together with --isoforms-polish!");
@@ -478,6 +487,7 @@ int main_dump(int argc, char** argv)
                              (reports.isoforms.on && reports.isoforms.inserts && reports.isoforms.inserts_seq ? "cluster_inserts.fq, " : "") +
                              (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.full ? "cluster_isoforms_full.fq, " : "") +
                              (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.variants ? "cluster_insert_variants.fq, read_insert_variants.tsv, " : "") +
+                             (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.variants && reports.isoforms.full_variants ? "cluster_isoforms_full_variants.fq, " : "") +
                              (reports.isoforms.on && reports.isoforms.ends ? "cluster_ends.tsv, cluster_end_variants.tsv, read_ends.tsv, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }

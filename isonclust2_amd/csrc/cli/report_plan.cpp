@@ -291,6 +291,15 @@ string read_variant_columns(const ioc_read_variants& r, int32_t n_sites)
     return variants_signature(r.key2, n_sites) + '\t' + (r.group < 0 ? string(".") : std::to_string(r.group)) + '\t' + how;
 }
 
+string full_variants_tail(uint64_t key2, const ioc_splice_site* sites, int64_t n_sites)
+{
+    string text;
+    for (int64_t b = 0; b < n_sites && b < IOC_INSERTS_MAX; ++b)
+        if (sites[b].state == IOC_SPLICE_DONE)
+            text += " ins" + std::to_string(b) + '/' + (((key2 >> (2 * b)) & 3u) == IOC_INS_CARRY_B ? 'B' : 'A') + '@' + std::to_string(sites[b].at) + '+' + std::to_string(sites[b].len);
+    return text;
+}
+
 EndsCapacity ends_capacity(const ReportGroup& g, int max_sites, int max_variants)
 {
     EndsCapacity cap;

@@ -333,16 +333,37 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
                     r.var_stats.assign(size_t(std::max<int64_t>(2 * icap, 1)), ioc_polish_stats{});
                     r.vseq.assign(size_t(std::max<int64_t>(2 * wcap, 1)), '\0'), r.vqual.assign(size_t(std::max<int64_t>(2 * wcap, 1)), '\0');
                     r.variant.assign(np * size_t(IOC_INSERTS_MAX), 0), r.read_variants.assign(np, ioc_read_variants{}), r.variants_seg.assign(ns, ioc_variants_seg{});
-                    check(c, ioc_align_pairs_blocks_inserts_variants(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
-                                                                     g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks,
-                                                                     nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
-                                                                     o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
-                                                                     r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(),
-                                                                     io.ins_max_win, 2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(),
-                                                                     r.win_stats.data(), io.variants_min_agree, r.win_variants.data(), &r.vseq[0], &r.vqual[0], 2 * wcap,
-                                                                     r.vslot_off.data(), r.var_stats.data(), r.variant.data(), nullptr, r.read_variants.data(),
-                                                                     r.variants_seg.data()),
-                          "exon blocks with the insertion sites, their sequences and their variants");
+                    if (io.full_variants) {
+                        // (the full call's room: one slot a site is taken)
+                        const IsoCapacity fcap = iso_full_capacity(g, io.full_max, io.ins_max, io.ins_max_win);
+                        r.fseq.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]), r.fqual.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]);
+                        r.full_off.assign(ns + 1, 0), r.fseq_off.assign(size_t(fcap.isoforms) + 1, 0), r.fsplice_off.assign(size_t(fcap.isoforms) + 1, 0);
+                        r.fstats.assign(size_t(std::max<int64_t>(fcap.isoforms, 1)), ioc_polish_stats{});
+                        r.fsplice.assign(size_t(std::max<int64_t>(fcap.isoforms * io.ins_max, 1)), ioc_splice_site{});
+                        check(c, ioc_align_pairs_isoforms_full_variants(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
+                                                                        g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks,
+                                                                        nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
+                                                                        o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
+                                                                        r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(),
+                                                                        io.ins_max_win, 2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(),
+                                                                        r.win_stats.data(), io.variants_min_agree, r.win_variants.data(), &r.vseq[0], &r.vqual[0], 2 * wcap,
+                                                                        r.vslot_off.data(), r.var_stats.data(), r.variant.data(), nullptr, r.read_variants.data(),
+                                                                        r.variants_seg.data(), io.full_max, r.fseq.get(), r.fqual.get(), fcap.bytes, r.fseq_off.data(),
+                                                                        r.fstats.data(), nullptr, r.fsplice.data(), int64_t(r.fsplice.size()), r.fsplice_off.data(),
+                                                                        fcap.isoforms, r.full_off.data()),
+                              "exon blocks with the insertion sites, their sequences, their variants and the isoforms' full-length sequences by variant");
+                    } else {
+                        check(c, ioc_align_pairs_blocks_inserts_variants(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
+                                                                         g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks,
+                                                                         nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
+                                                                         o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
+                                                                         r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(),
+                                                                         io.ins_max_win, 2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(),
+                                                                         r.win_stats.data(), io.variants_min_agree, r.win_variants.data(), &r.vseq[0], &r.vqual[0], 2 * wcap,
+                                                                         r.vslot_off.data(), r.var_stats.data(), r.variant.data(), nullptr, r.read_variants.data(),
+                                                                         r.variants_seg.data()),
+                              "exon blocks with the insertion sites, their sequences and their variants");
+                    }
                 } else
                 check(c, ioc_align_pairs_blocks_inserts_seq(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
                                                             g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
@@ -642,9 +663,40 @@ void write_isoforms_full(std::ofstream& out, const ReportGroup& g, const GroupRe
     }
 }
 
+// cluster_isoforms_full_variants.fq: a record per called isoform as the variant stage counted them again, of every cluster that has a
+// block or a site — cluster_isoforms_full.fq's records, the sites half of key= in the variant file's letters and every spliced site
+// with the variant whose record of cluster_insert_variants.fq stands there
+void write_isoforms_full_variants(std::ofstream& out, const ReportGroup& g, const GroupResult& r)
+{
+    for (size_t x = 0; x < g.group_cls.size(); ++x) {
+        const int32_t s = g.group_seg[x];
+        if (s < 0 || (r.blocks_seg[size_t(s)].n_blocks < 1 && r.inserts_seg[size_t(s)].n_sites < 1)) continue;
+        const int64_t i0 = r.full_off[size_t(s)], n = r.full_off[size_t(s) + 1] - i0;
+        std::vector<uint64_t> bkey(size_t(n), 0), key2(size_t(n), 0);
+        std::vector<uint8_t> has(size_t(n), 0);
+        std::vector<int32_t> mine(size_t(n), 0);
+        for (size_t p = 0; p < g.pairs.size(); ++p) {
+            const ioc_read_variants& rv = r.read_variants[p];
+            if (g.seg_of_pair[p] != s || rv.group < 0 || rv.group >= n) continue;
+            if (rv.how == IOC_ISO_DIRECT && !has[size_t(rv.group)]) bkey[size_t(rv.group)] = r.read_blocks[p].key, key2[size_t(rv.group)] = rv.key2, has[size_t(rv.group)] = 1;
+            if (rv.how == IOC_ISO_DIRECT || rv.how == IOC_ISO_ASSIGNED) ++mine[size_t(rv.group)];
+        }
+        for (int64_t h = 0; h < n; ++h) {
+            const size_t at = size_t(r.fseq_off[size_t(i0 + h)]), len = size_t(r.fseq_off[size_t(i0 + h) + 1]) - at;
+            const int64_t b0 = r.fsplice_off[size_t(i0 + h)];
+            const string tail = full_variants_tail(key2[size_t(h)], r.fsplice.data() + b0, r.fsplice_off[size_t(i0 + h) + 1] - b0);
+            const string text = polish_record("cluster_" + std::to_string(g.group_cls[x].first) + "/iso" + std::to_string(h) + " key=" +
+                                                  blocks_signature(bkey[size_t(h)], r.blocks_seg[size_t(s)].n_blocks) + '/' +
+                                                  variants_signature(key2[size_t(h)], r.inserts_seg[size_t(s)].n_sites),
+                                              mine[size_t(h)], r.fstats[size_t(i0 + h)], tail.c_str(), r.fseq.get() + at, r.fqual.get() + at, len);
+            out.write(text.data(), std::streamsize(text.size()));
+        }
+    }
+}
+
 // the files that grow group by group
 struct GroupFiles {
-    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq, variants_fq, full_fq, ends, end_variants;
+    std::ofstream pileup, polish, sites, split, group_polish, blocks, isoforms, iso_fq, inserts, inserts_fq, variants_fq, full_fq, full_variants_fq, ends, end_variants;
     GroupFiles(const string& outdir, const ReportOpts& o)
     {
         if (o.pileup) {
@@ -674,6 +726,7 @@ struct GroupFiles {
             if (o.isoforms.inserts_seq) create_file(outdir + "/cluster_inserts.fq", inserts_fq);
             if (o.isoforms.inserts_seq && o.isoforms.full) create_file(outdir + "/cluster_isoforms_full.fq", full_fq);
             if (o.isoforms.inserts_seq && o.isoforms.variants) create_file(outdir + "/cluster_insert_variants.fq", variants_fq);
+            if (o.isoforms.inserts_seq && o.isoforms.variants && o.isoforms.full_variants) create_file(outdir + "/cluster_isoforms_full_variants.fq", full_variants_fq);
         }
         if (o.isoforms.on && o.isoforms.ends) {
             create_file(outdir + "/cluster_ends.tsv", ends);
@@ -695,6 +748,8 @@ struct GroupFiles {
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && !g.segs.empty() && !g.pairs.empty()) write_insert_windows(inserts_fq, rows, g, r);
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && o.isoforms.full && !g.segs.empty() && !g.pairs.empty()) write_isoforms_full(full_fq, g, r);
         if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && o.isoforms.variants && !g.segs.empty() && !g.pairs.empty()) write_insert_variants(variants_fq, rows, g, r);
+        if (o.isoforms.on && o.isoforms.inserts && o.isoforms.inserts_seq && o.isoforms.variants && o.isoforms.full_variants && !g.segs.empty() && !g.pairs.empty())
+            write_isoforms_full_variants(full_variants_fq, g, r);
     }
 };
 

@@ -39,6 +39,8 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     int variants_min_agree = IOC_WINVAR_MIN_AGREE;   // (ioc_align_pairs_blocks_inserts_variants), and the agreement a voter is near a template at
     bool full = false;                               // --isoforms-full: every combined isoform's full-length sequence as well
     int full_max = 16;                               // (ioc_align_pairs_isoforms_full), and how many isoforms of a cluster are called
+    bool full_variants = false;                      // --isoforms-full-variants: with the variants, the full-length sequence of every isoform counted
+                                                     // again, each exon's own variant spliced in (ioc_align_pairs_isoforms_full_variants); full_max applies
     bool ends = false;                               // --isoforms-ends: the alternative ends as well (ioc_align_pairs_blocks_ends), and the
     int ends_slack = 10, ends_min_over = 20, ends_min_pct = 10, ends_max = 32, ends_max_variants = 64;  // thresholds of ioc_host_reads_ends the block search does not share
 };
@@ -129,7 +131,8 @@ struct IsoCapacity {
     int64_t isoforms = 0, bytes = 0;
 };
 IsoCapacity iso_polish_capacity(const ReportGroup& g, int max_iso);
-// ... and of ioc_align_pairs_isoforms_full: an isoform holds at most its call's bound and a window of 7 max_win + 6 bytes a site
+// ... and of ioc_align_pairs_isoforms_full and ioc_align_pairs_isoforms_full_variants (one slot a site is taken): an isoform holds at
+// most its call's bound and a window of 7 max_win + 6 bytes a site
 IsoCapacity iso_full_capacity(const ReportGroup& g, int max_iso, int max_sites, int max_win);
 // the insertion sites a search may keep at most, for all segments of a group: min(max_sites, the junctions of the representative) each
 int64_t inserts_capacity(const ReportGroup& g, int max_sites);
@@ -144,6 +147,9 @@ std::string read_insert_columns(const ioc_read_inserts& r, int32_t n_sites);
 // ... of read_insert_variants.tsv: the signature with the variants told apart ('=' lack, 'A' / 'B' carry, '.' not across or unknown), and the columns behind it
 std::string variants_signature(uint64_t key2, int32_t n_sites);
 std::string read_variant_columns(const ioc_read_variants& r, int32_t n_sites);
+// ... of a record of cluster_isoforms_full_variants.fq: " ins<b>/<A|B>@<at>+<len>" for every DONE site of an isoform, the letter being the
+// state of key2 there — the record of cluster_insert_variants.fq that stands at base `at`
+std::string full_variants_tail(uint64_t key2, const ioc_splice_site* sites, int64_t n_sites);
 // the end sites (start and stop sites together) and the variants a search for ends may keep at most, for all segments of a group:
 // 2 min(max_sites, the representative's length + 1) and min(max_variants, its reads) each
 struct EndsCapacity {

@@ -1277,35 +1277,25 @@ int ioc_host_insert_window_variants(const uint8_t* base, const uint32_t* qpos, c
 
 // The full-length sequence of one isoform: ioc_host_pileup_call's walk with the windows of the sites it carries in place of their
 // rows (isonclust2_hip.h has the rules; splice_state and splice_row, ioc_iso_splice.h, decide for this function and for the kernels
-// of ioc_iso_splice.hip alike).
-int64_t ioc_host_isoform_splice(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth, uint64_t key,
-                                const ioc_insert_window* win, int32_t n_sites, const char* win_seq, const char* win_qual, const int64_t* win_off,
-                                char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st, ioc_splice_site* out_sites, ioc_splice_stats* out_sstats)
+// of ioc_iso_splice.hip alike).  The body both definitions share: site b carries iff carries[b], its template length is tlen[b] and
+// its bytes are from[b] .. to[b] of seq / qual; the arguments are checked by then.
+static int64_t isoform_splice_walk(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth,
+                                   const ioc_insert_window* win, int32_t n_sites, const uint8_t* carries, const int32_t* tlen, const int64_t* from, const int64_t* to,
+                                   const char* win_seq, const char* win_qual, char* out_seq, char* out_qual, ioc_polish_stats* st, ioc_splice_site* out_sites,
+                                   ioc_splice_stats* out_sstats)
 {
-    if (min_depth < 1 || rlen < 0 || !cols || !ins || (rlen > 0 && !frame) || n_sites < 0 || n_sites > IOC_INSERTS_MAX || !win_off ||
-        (n_sites > 0 && (!win || !out_sites)))
-        return IOC_ERR_ARG;
-    for (int32_t b = 0; b < n_sites; ++b)
-        if (win[b].lo < 1 || win[b].lo >= win[b].hi || win[b].hi > rlen || win[b].tlen < 0 || win_off[b + 1] < win_off[b] ||
-            win_off[b + 1] - win_off[b] > INT32_MAX)
-            return IOC_ERR_ARG;
-    const int64_t win_bytes = win_off[n_sites] - win_off[0];
-    if (win_bytes > 0 && (!win_seq || !win_qual)) return IOC_ERR_ARG;
-    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1) + win_bytes;
-    if (cap < bound) return IOC_ERR_CAPACITY;
-    if (!out_seq || !out_qual) return IOC_ERR_ARG;
     IocSpliceIv plan[IOC_SPLICE_PLAN_MAX];
     uint32_t n_plan = 0;
     ioc_splice_stats ss{};
     int32_t last_hi = 0;
     for (int32_t b = 0; b < n_sites; ++b) {
-        const int32_t state = splice_state(key, uint32_t(b), win[b], last_hi);
+        const int32_t state = splice_state_of(carries[b] != 0, tlen[b], win[b].lo, last_hi);
         out_sites[b] = ioc_splice_site{state, -1, 0, 0};
         ss.n_uncalled += state == IOC_SPLICE_UNCALLED, ss.n_overlap += state == IOC_SPLICE_OVERLAP;
         if (state != IOC_SPLICE_DONE) continue;
-        plan[n_plan++] = IocSpliceIv{win[b].lo, win[b].hi, int32_t(win_off[b + 1] - win_off[b]), b, win_off[b]};
+        plan[n_plan++] = IocSpliceIv{win[b].lo, win[b].hi, int32_t(to[b] - from[b]), b, from[b]};
         last_hi = win[b].hi;
-        ++ss.n_done, ss.rows_replaced += win[b].hi - win[b].lo, ss.spliced_bytes += int32_t(win_off[b + 1] - win_off[b]);
+        ++ss.n_done, ss.rows_replaced += win[b].hi - win[b].lo, ss.spliced_bytes += int32_t(to[b] - from[b]);
     }
     ioc_polish_stats s{};
     int64_t at = 0;
@@ -1330,6 +1320,61 @@ int64_t ioc_host_isoform_splice(const ioc_pileup_col* cols, const ioc_pileup_ins
     if (st) *st = s;
     if (out_sstats) *out_sstats = ss;
     return at;
+}
+
+int64_t ioc_host_isoform_splice(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth, uint64_t key,
+                                const ioc_insert_window* win, int32_t n_sites, const char* win_seq, const char* win_qual, const int64_t* win_off,
+                                char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st, ioc_splice_site* out_sites, ioc_splice_stats* out_sstats)
+{
+    if (min_depth < 1 || rlen < 0 || !cols || !ins || (rlen > 0 && !frame) || n_sites < 0 || n_sites > IOC_INSERTS_MAX || !win_off ||
+        (n_sites > 0 && (!win || !out_sites)))
+        return IOC_ERR_ARG;
+    for (int32_t b = 0; b < n_sites; ++b)
+        if (win[b].lo < 1 || win[b].lo >= win[b].hi || win[b].hi > rlen || win[b].tlen < 0 || win_off[b + 1] < win_off[b] ||
+            win_off[b + 1] - win_off[b] > INT32_MAX)
+            return IOC_ERR_ARG;
+    const int64_t win_bytes = win_off[n_sites] - win_off[0];
+    if (win_bytes > 0 && (!win_seq || !win_qual)) return IOC_ERR_ARG;
+    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1) + win_bytes;
+    if (cap < bound) return IOC_ERR_CAPACITY;
+    if (!out_seq || !out_qual) return IOC_ERR_ARG;
+    uint8_t carries[IOC_INSERTS_MAX];
+    int32_t tlen[IOC_INSERTS_MAX];
+    for (int32_t b = 0; b < n_sites; ++b) carries[b] = ((key >> (2 * b)) & 3u) == uint64_t(IOC_INS_CARRY), tlen[b] = win[b].tlen;
+    return isoform_splice_walk(cols, ins, frame, rlen, min_depth, win, n_sites, carries, tlen, win_off, win_off + 1, win_seq, win_qual, out_seq, out_qual, st, out_sites,
+                               out_sstats);
+}
+
+// The same by variant: a site's state under key2 chooses one of its two slots (splice_variant_which and splice_variant_tlen,
+// ioc_iso_splice.h, which the slot-aware plan kernel asks as well); everything behind that choice is the walk above.
+int64_t ioc_host_isoform_splice_variants(const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, int32_t rlen, int32_t min_depth, uint64_t key,
+                                         const ioc_insert_window* win, const ioc_window_variant* var, int32_t n_sites, const char* slot_seq, const char* slot_qual,
+                                         const int64_t* slot_off, char* out_seq, char* out_qual, int64_t cap, ioc_polish_stats* st, ioc_splice_site* out_sites,
+                                         ioc_splice_stats* out_sstats)
+{
+    if (min_depth < 1 || rlen < 0 || !cols || !ins || (rlen > 0 && !frame) || n_sites < 0 || n_sites > IOC_INSERTS_MAX || !slot_off ||
+        (n_sites > 0 && (!win || !var || !out_sites)))
+        return IOC_ERR_ARG;
+    for (int32_t b = 0; b < n_sites; ++b) {
+        if (win[b].lo < 1 || win[b].lo >= win[b].hi || win[b].hi > rlen || win[b].tlen < 0 || (var[b].split != 0 && var[b].split != 1) || var[b].tlen_b < 0)
+            return IOC_ERR_ARG;
+        for (int32_t y = 2 * b; y < 2 * b + 2; ++y)
+            if (slot_off[y + 1] < slot_off[y] || slot_off[y + 1] - slot_off[y] > INT32_MAX) return IOC_ERR_ARG;
+    }
+    const int64_t slot_bytes = slot_off[2 * n_sites] - slot_off[0];
+    if (slot_bytes > 0 && (!slot_seq || !slot_qual)) return IOC_ERR_ARG;
+    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1) + slot_bytes;
+    if (cap < bound) return IOC_ERR_CAPACITY;
+    if (!out_seq || !out_qual) return IOC_ERR_ARG;
+    uint8_t carries[IOC_INSERTS_MAX];
+    int32_t tlen[IOC_INSERTS_MAX];
+    int64_t from[IOC_INSERTS_MAX], to[IOC_INSERTS_MAX];
+    for (int32_t b = 0; b < n_sites; ++b) {
+        const int32_t which = splice_variant_which(uint32_t(key >> (2 * b)) & 3u);
+        carries[b] = which >= 0, tlen[b] = which >= 0 ? splice_variant_tlen(which, win[b], var[b]) : 0;
+        from[b] = slot_off[2 * b + std::max(which, 0)], to[b] = slot_off[2 * b + std::max(which, 0) + 1];
+    }
+    return isoform_splice_walk(cols, ins, frame, rlen, min_depth, win, n_sites, carries, tlen, from, to, slot_seq, slot_qual, out_seq, out_qual, st, out_sites, out_sstats);
 }
 
 // setGapOpen, src/cluster.cpp:425-440

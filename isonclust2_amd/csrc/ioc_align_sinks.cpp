@@ -2220,13 +2220,28 @@ int ioc_planes_insert_window_variants(ioc_ctx* c, int32_t n_segs, const int32_t*
 
 namespace {
 // what a splice reads beside the group tables, all the host's: a key per group-segment, the segments' window records packed with
-// site_off, their called bytes packed with win_off
+// site_off, their called bytes packed with win_off.  by_variant (ioc_host_isoform_splice_variants): the keys are key2, `var` holds a
+// record per site beside `win`, and wseq / wqual / win_off are the variant stage's slots, two a site (2 site_off[n] + 1 offsets).
 struct SpliceIn {
     const uint64_t* keys;
     const ioc_insert_window* win;
     const int64_t* site_off;
     const char *wseq, *wqual;
     const int64_t* win_off;
+    const ioc_window_variant* var = nullptr;
+    bool by_variant = false;
+    // the fused call's room counts one slot a site, the longer one: an isoform takes one, and the caller's cap was checked against one
+    // window's most a site before anything ran — so no refusal comes after the stages have written.  The planes entry keeps the
+    // definition's rule, the bytes of all slots.
+    bool longer_slot_room = false;
+    int64_t per_site() const { return by_variant ? 2 : 1; }
+    int64_t room(int64_t s0, int64_t s1) const  // what the windows of sites s0 .. s1 add to an isoform's bound
+    {
+        if (!longer_slot_room) return win_off[per_site() * s1] - win_off[per_site() * s0];
+        int64_t sum = 0;
+        for (int64_t x = s0; x < s1; ++x) sum += std::max(win_off[2 * x + 1] - win_off[2 * x], win_off[2 * x + 2] - win_off[2 * x + 1]);
+        return sum;
+    }
 };
 struct SpliceOut {  // where a splice leaves what it made (call.off: G + 1 entries; cap: the records `splice` holds; splice_off: G + 1 entries)
     CallOut call;
@@ -2245,20 +2260,24 @@ static int splice_ok(ioc_ctx* c, const std::string& who, const SpliceIn& in, con
     if (!in.site_off || !in.win_off) return IOC_ERR_ARG;
     if (in.site_off[0] != 0 || in.win_off[0] != 0) return ioc_fail(c, IOC_ERR_ARG, who + ": site_off or win_off does not begin at 0");
     int64_t bound = 0, records = 0, G = 0;
+    const int64_t u = in.per_site();
     for (size_t g = 0; g < n; ++g) {
         if (in.site_off[g + 1] < in.site_off[g] || in.site_off[g + 1] - in.site_off[g] > IOC_INSERTS_MAX)
             return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " has a negative number of sites or more than 32");
         for (int64_t x = in.site_off[g]; x < in.site_off[g + 1]; ++x) {
             if (!in.win || in.win[x].lo < 1 || in.win[x].lo >= in.win[x].hi || in.win[x].hi > ds[g].rlen || in.win[x].tlen < 0)
                 return ioc_fail(c, IOC_ERR_ARG, who + ": the window of site " + std::to_string(x) + " does not lie inside its segment");
-            if (in.win_off[x + 1] < in.win_off[x]) return ioc_fail(c, IOC_ERR_ARG, who + ": win_off does not ascend at site " + std::to_string(x));
+            if (in.by_variant && (!in.var || (in.var[x].split != 0 && in.var[x].split != 1) || in.var[x].tlen_b < 0))
+                return ioc_fail(c, IOC_ERR_ARG, who + ": the variant record of site " + std::to_string(x) + " has a split outside 0 / 1 or a negative tlen_b");
+            for (int64_t y = u * x; y < u * (x + 1); ++y)
+                if (in.win_off[y + 1] < in.win_off[y]) return ioc_fail(c, IOC_ERR_ARG, who + (in.by_variant ? ": slot_off" : ": win_off") + " does not ascend at site " + std::to_string(x));
         }
-        const int64_t most = pile_call_most(ds[g].rlen) + (in.win_off[in.site_off[g + 1]] - in.win_off[in.site_off[g]]);
+        const int64_t most = pile_call_most(ds[g].rlen) + in.room(in.site_off[g], in.site_off[g + 1]);
         if (most > INT32_MAX)  // (the record's out_len, the kernels' byte counts)
             return ioc_fail(c, IOC_ERR_CAPACITY, who + ": an isoform of segment " + std::to_string(g) + " may hold more than 2^31 - 1 bytes");
         bound += int64_t(n_groups[g]) * most, records += int64_t(n_groups[g]) * (in.site_off[g + 1] - in.site_off[g]), G += n_groups[g];
     }
-    if (in.win_off[in.site_off[n]] > 0 && (!in.wseq || !in.wqual)) return IOC_ERR_ARG;
+    if (in.win_off[u * in.site_off[n]] > 0 && (!in.wseq || !in.wqual)) return IOC_ERR_ARG;
     if (G > 0 && !in.keys) return IOC_ERR_ARG;
     if (o.cap < records) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": splice_cap " + std::to_string(o.cap) + " below the bound " + std::to_string(records));
     if (records > 0 && !o.splice) return IOC_ERR_ARG;
@@ -2268,13 +2287,14 @@ static int splice_ok(ioc_ctx* c, const std::string& who, const SpliceIn& in, con
 
 // plan -> count -> scan -> write -> copy-out over group tables that lie on the device (g; gseg_off[s] .. gseg_off[s + 1] are segment
 // s's group-segments).  a_splice holds, uploaded in one piece, [group-segments][their segments][keys][window records][site_off][win_off]
-// [window sequences][window qualities][splice_off], and behind them [site records][splice records][plans][plan lengths][seg_len]
+// [window sequences][window qualities][splice_off][variant records, by variant], and behind them [site records][splice records][plans][plan lengths][seg_len]
 // [out_off][records][sequence][qualities].
 static int splice_device(SinkRun& r, const GroupPiled& g, const std::vector<uint32_t>& gseg_off, const uint8_t* d_frames, uint64_t frame_bytes, const SpliceIn& in,
                          const SpliceOut& o, int64_t bound)
 {
     ioc_ctx* const c = r.c;
-    const size_t n = gseg_off.size() - 1, G = g.gsegs.size(), S = size_t(in.site_off[n]), W = size_t(in.win_off[S]);
+    const size_t n = gseg_off.size() - 1, G = g.gsegs.size(), S = size_t(in.site_off[n]), U = size_t(in.per_site()) * S, W = size_t(in.win_off[U]);
+    const bool vars = in.by_variant && S > 0;  // (without a site either plan kernel writes the same: nothing)
     std::vector<int32_t> gseg_seg(G);
     o.splice_off[0] = 0;
     for (size_t s = 0; s < n; ++s)
@@ -2282,14 +2302,16 @@ static int splice_device(SinkRun& r, const GroupPiled& g, const std::vector<uint
     const size_t R = size_t(o.splice_off[G]);
     Arena l;
     const size_t o_gseg = l.take(G * sizeof(IocPileSeg)), o_gs = l.take(G * 4), o_keys = l.take(G * 8), o_win = l.take(S * sizeof(ioc_insert_window)),
-                 o_soff = l.take((n + 1) * 8), o_woff = l.take((S + 1) * 8), o_wseq = l.take(W), o_wqual = l.take(W), o_spoff = l.take((G + 1) * 8), tables = l.size();
+                 o_soff = l.take((n + 1) * 8), o_woff = l.take((U + 1) * 8), o_wseq = l.take(W), o_wqual = l.take(W), o_spoff = l.take((G + 1) * 8),
+                 o_var = l.take(vars ? S * sizeof(ioc_window_variant) : 0), tables = l.size();
     const size_t o_rec = l.take(R * sizeof(ioc_splice_site)), o_ss = l.take(G * sizeof(ioc_splice_stats)), o_plan = l.take(G * IOC_SPLICE_PLAN_MAX * sizeof(IocSpliceIv)),
                  o_pn = l.take(G * 4), o_len = l.take(G * 8), o_off = l.take((G + 1) * 8), o_st = l.take(G * sizeof(ioc_polish_stats)), o_seq = l.take(size_t(bound)),
                  o_qual = l.take(size_t(bound));
     std::vector<uint8_t> stage(tables, 0);
     auto put = [&](size_t at, const void* src, size_t b) { if (b) memcpy(stage.data() + at, src, b); };
     put(o_gseg, g.gsegs.data(), G * sizeof(IocPileSeg)), put(o_gs, gseg_seg.data(), G * 4), put(o_keys, in.keys, G * 8), put(o_win, in.win, S * sizeof(ioc_insert_window));
-    put(o_soff, in.site_off, (n + 1) * 8), put(o_woff, in.win_off, (S + 1) * 8), put(o_wseq, in.wseq, W), put(o_wqual, in.wqual, W), put(o_spoff, o.splice_off, (G + 1) * 8);
+    put(o_soff, in.site_off, (n + 1) * 8), put(o_woff, in.win_off, (U + 1) * 8), put(o_wseq, in.wseq, W), put(o_wqual, in.wqual, W), put(o_spoff, o.splice_off, (G + 1) * 8);
+    if (vars) put(o_var, in.var, S * sizeof(ioc_window_variant));
     IOC_CHK(c, hipSetDevice(c->device));
     IOC_TRY(ioc_reserve(c, c->a_splice, l.size()));
     uint8_t* p = static_cast<uint8_t*>(c->a_splice.p);
@@ -2298,7 +2320,8 @@ static int splice_device(SinkRun& r, const GroupPiled& g, const std::vector<uint
                          reinterpret_cast<const unsigned long long*>(p + o_keys), reinterpret_cast<const ioc_insert_window*>(p + o_win),
                          reinterpret_cast<const long long*>(p + o_soff), reinterpret_cast<const long long*>(p + o_woff), uint64_t(S), p + o_wseq, p + o_wqual, uint64_t(W),
                          reinterpret_cast<const long long*>(p + o_spoff), reinterpret_cast<ioc_splice_site*>(p + o_rec), uint64_t(R),
-                         reinterpret_cast<ioc_splice_stats*>(p + o_ss), reinterpret_cast<IocSpliceIv*>(p + o_plan), reinterpret_cast<uint32_t*>(p + o_pn)};
+                         reinterpret_cast<ioc_splice_stats*>(p + o_ss), reinterpret_cast<IocSpliceIv*>(p + o_plan), reinterpret_cast<uint32_t*>(p + o_pn),
+                         vars ? reinterpret_cast<const ioc_window_variant*>(p + o_var) : nullptr};
     IOC_TRY(r.begin(r.t.ms_splice[0]));
     IOC_CHK(c, iock_splice_plan(c->stream, v));
     IOC_TRY(r.end());
@@ -2330,15 +2353,14 @@ static std::string splice_trace(const AlnTally& t)
 
 // upload -> groups pile -> splice -> copy-out.  ioc_planes_polish_groups with the windows of the sites every isoform carries spliced
 // into its call: the checks of ioc_planes_polish_groups, in its order, then those of the windows.
-int ioc_planes_isoforms_full(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups, int32_t n_pairs,
-                             const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base, const uint8_t* slots, const uint64_t* iso_key,
-                             const ioc_insert_window* win, const int64_t* site_off, const char* win_seq, const char* win_qual, const int64_t* win_off, int32_t min_depth,
-                             char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats,
-                             ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins)
+// `in` says whether the windows are one a site or the variant stage's slots (ioc_planes_isoforms_full_variants).
+static int planes_isoforms_full(const std::string& who, const SpliceIn& in, ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                                const int32_t* n_groups, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base, const uint8_t* slots,
+                                int32_t min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats,
+                                ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins)
 {
-    const std::string who = "ioc_planes_isoforms_full";
+    const int64_t* const site_off = in.site_off;
     const SpliceOut o{{min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off};
-    const SpliceIn in{iso_key, win, site_off, win_seq, win_qual, win_off};
     if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || (n_segs > 0 && (!rlen || !frame_off || !n_groups)) || (n_pairs > 0 && (!seg_of_pair || !group))) return IOC_ERR_ARG;
     SinkPlan p;
     if (int st = p.from_rlen(who, n_segs, rlen, frames, frame_off, n_pairs, seg_of_pair, nullptr, 0)) return ioc_fail(c, st, p.msg);
@@ -2364,9 +2386,34 @@ int ioc_planes_isoforms_full(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, co
     IOC_TRY(splice_device(r, gp, gp.lists.gseg_off, static_cast<const uint8_t*>(d_frames.p), uint64_t(p.frame_bytes), in, o, bound));
     IOC_TRY(r.copy_out({{out_gcols, gp.cols, size_t(gp.n_rows) * sizeof(ioc_pileup_col)}, {out_gins, gp.ins, size_t(gp.n_rows) * sizeof(ioc_pileup_ins)}}));
     if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   planes isoforms full: %lld group-segments, %d pairs, %lld sites, %lld bytes called, k_group_pile %.3f ms, %s\n", (long long)G, n_pairs,
-                (long long)site_off[n_segs], (long long)out_off[G], r.t.ms_group_pile, splice_trace(r.t).c_str());
+        fprintf(stderr, "[ioc]   planes isoforms full%s: %lld group-segments, %d pairs, %lld sites, %lld bytes called, k_group_pile %.3f ms, %s\n",
+                in.by_variant ? " by variant" : "", (long long)G, n_pairs, (long long)site_off[n_segs], (long long)out_off[G], r.t.ms_group_pile, splice_trace(r.t).c_str());
     return IOC_OK;
+}
+
+int ioc_planes_isoforms_full(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups, int32_t n_pairs,
+                             const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base, const uint8_t* slots, const uint64_t* iso_key,
+                             const ioc_insert_window* win, const int64_t* site_off, const char* win_seq, const char* win_qual, const int64_t* win_off, int32_t min_depth,
+                             char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats,
+                             ioc_splice_site* out_splice, int64_t splice_cap, int64_t* splice_off, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins)
+{
+    const SpliceIn in{iso_key, win, site_off, win_seq, win_qual, win_off};
+    return planes_isoforms_full("ioc_planes_isoforms_full", in, c, n_segs, rlen, frames, frame_off, n_groups, n_pairs, seg_of_pair, group, base, slots, min_depth, out_seq,
+                                out_qual, cap, out_off, out_polish, out_sstats, out_splice, splice_cap, splice_off, out_gcols, out_gins);
+}
+
+// ... by variant: the same stages, the plan kernel in its slot-aware instantiation over the slots and the variant records uploaded
+// beside the window records.
+int ioc_planes_isoforms_full_variants(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups,
+                                      int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group, const uint8_t* base, const uint8_t* slots,
+                                      const uint64_t* iso_key, const ioc_insert_window* win, const ioc_window_variant* var, const int64_t* site_off,
+                                      const char* slot_seq, const char* slot_qual, const int64_t* slot_off, int32_t min_depth, char* out_seq, char* out_qual, int64_t cap,
+                                      int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats, ioc_splice_site* out_splice, int64_t splice_cap,
+                                      int64_t* splice_off, ioc_pileup_col* out_gcols, ioc_pileup_ins* out_gins)
+{
+    const SpliceIn in{iso_key, win, site_off, slot_seq, slot_qual, slot_off, var, /*by_variant*/ true};
+    return planes_isoforms_full("ioc_planes_isoforms_full_variants", in, c, n_segs, rlen, frames, frame_off, n_groups, n_pairs, seg_of_pair, group, base, slots, min_depth,
+                                out_seq, out_qual, cap, out_off, out_polish, out_sstats, out_splice, splice_cap, splice_off, out_gcols, out_gins);
 }
 
 namespace {
@@ -2489,23 +2536,29 @@ static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, 
         IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
     if (full) {
         // the combined isoforms the insert stage just made, the first min(n_groups, max_iso) of a segment: their reads, and the key
-        // of the lowest-numbered direct read of each (the records are on the host: they are one of the call's outputs)
+        // of the lowest-numbered direct read of each (the records are on the host: they are one of the call's outputs).  With the
+        // variant stage in the same call (ioc_align_pairs_isoforms_full_variants) the isoforms are those it counted again, the keys
+        // key2, and the windows its slots.
         std::vector<int32_t> n_iso(size_t(n_segs), 0), group(size_t(n_pairs), -1);
+        auto read_of = [&](int32_t i) { return vf ? vf->vo.reads[i] : ioc_read_variants{out_ireads[i].key, out_ireads[i].group, out_ireads[i].how}; };
         for (int32_t g = 0; g < n_segs; ++g) {
-            if (out_iseg[g].n_groups < 0 || out_iseg[g].n_groups > n_reads[size_t(g)]) return ioc_fail(c, IOC_ERR_HIP, "the insert search returned more isoforms than reads");
-            n_iso[size_t(g)] = std::min(out_iseg[g].n_groups, full->max_iso);
+            const int32_t found = vf ? vf->vo.seg[g].n_groups : out_iseg[g].n_groups;
+            if (found < 0 || found > n_reads[size_t(g)]) return ioc_fail(c, IOC_ERR_HIP, "the insert search returned more isoforms than reads");
+            n_iso[size_t(g)] = std::min(found, full->max_iso);
             full->iso_off[g + 1] = full->iso_off[g] + n_iso[size_t(g)];
         }
         const int64_t G = full->iso_off[n_segs];
         std::vector<uint64_t> iso_key(size_t(G), 0);
         std::vector<uint8_t> has_key(size_t(G), 0);
         for (int32_t i = 0; i < n_pairs; ++i) {
-            const int32_t g = seg_of_pair[i], h = group[size_t(i)] = out_ireads[i].group;  // (an isoform behind the cut is in no list: group_member_lists)
-            if (h < 0 || h >= n_iso[size_t(g)] || out_ireads[i].how != IOC_ISO_DIRECT || has_key[size_t(full->iso_off[g] + h)]) continue;
-            iso_key[size_t(full->iso_off[g] + h)] = out_ireads[i].key, has_key[size_t(full->iso_off[g] + h)] = 1;
+            const ioc_read_variants rd = read_of(i);
+            const int32_t g = seg_of_pair[i], h = group[size_t(i)] = rd.group;  // (an isoform behind the cut is in no list: group_member_lists)
+            if (h < 0 || h >= n_iso[size_t(g)] || rd.how != IOC_ISO_DIRECT || has_key[size_t(full->iso_off[g] + h)]) continue;
+            iso_key[size_t(full->iso_off[g] + h)] = rd.key2, has_key[size_t(full->iso_off[g] + h)] = 1;
         }
         if (G > 0) {
-            const SpliceIn in{iso_key.data(), out_win, site_off, out_wseq, out_wqual, out_woff};
+            const SpliceIn in = vf ? SpliceIn{iso_key.data(), out_win, site_off, vf->call.seq, vf->call.qual, vf->call.off, vf->vo.var, /*by_variant*/ true, /*longer_slot_room*/ true}
+                                   : SpliceIn{iso_key.data(), out_win, site_off, out_wseq, out_wqual, out_woff};
             int64_t bound = 0;
             IOC_TRY(splice_ok(c, who, in, full->o, p.segs, n_iso.data(), &bound));
             GroupPiled gp;
@@ -2513,8 +2566,8 @@ static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, 
             IOC_TRY(splice_device(r, gp, gp.lists.gseg_off, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), in, full->o, bound));
         }
         if (getenv("IOC_TRACE"))
-            fprintf(stderr, "[ioc]   aligner: isoforms full: %lld isoforms, %lld bytes called, k_ops_project_ins %.3f ms, k_group_pile over the isoforms %.3f ms, %s\n",
-                    (long long)G, (long long)full->o.call.off[G], r.t.ms_project_ins, r.t.ms_group_pile, splice_trace(r.t).c_str());
+            fprintf(stderr, "[ioc]   aligner: isoforms full%s: %lld isoforms, %lld bytes called, k_ops_project_ins %.3f ms, k_group_pile over the isoforms %.3f ms, %s\n",
+                    vf ? " by variant" : "", (long long)G, (long long)full->o.call.off[G], r.t.ms_project_ins, r.t.ms_group_pile, splice_trace(r.t).c_str());
     }
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   aligner: blocks inserts seq: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_project_ilen %.3f ms, k_ops_project_qpos %.3f ms, ms_blocks %.3f ms, %s, %s\n",
@@ -2573,6 +2626,28 @@ int ioc_align_pairs_isoforms_full(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pai
     const IsoFull full{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
     if (!full.ok()) return IOC_ERR_ARG;
     return align_pairs_inserts_seq("ioc_align_pairs_isoforms_full", &full, nullptr, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+}
+
+// ... -> windows and variants -> groups pile over the isoforms counted again -> splice by variant -> copy-out.  The two calls above in
+// one: the variant stage's key2, groups and slots feed the splice where the insert stage's keys, groups and windows did.
+int ioc_align_pairs_isoforms_full_variants(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                           int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                           const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                           int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                           int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                           int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                           int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                           int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
+                                           int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t min_agree, ioc_window_variant* out_var,
+                                           char* out_vseq, char* out_vqual, int64_t var_cap, int64_t* out_voff, ioc_polish_stats* out_vstats, uint8_t* out_variant,
+                                           int32_t* out_agree, ioc_read_variants* out_vreads, ioc_variants_seg* out_vseg, int32_t max_iso, char* out_seq, char* out_qual,
+                                           int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats, ioc_splice_site* out_splice,
+                                           int64_t splice_cap, int64_t* splice_off, int64_t iso_cap, int64_t* iso_off)
+{
+    const VariantsFused vf{{{min_agree, min_alt, min_pct}, out_var, out_variant, out_agree, out_vreads, out_vseg}, {polish_min_depth, out_vseq, out_vqual, var_cap, out_voff, out_vstats}};
+    const IsoFull full{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
+    if (!out_voff || !full.ok()) return IOC_ERR_ARG;
+    return align_pairs_inserts_seq("ioc_align_pairs_isoforms_full_variants", &full, &vf, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
 }
 
 // pile -> blocks -> groups pile -> call -> copy-out.  ioc_align_pairs_blocks with the six slot planes projected beside the two, and

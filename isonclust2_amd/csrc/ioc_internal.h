@@ -627,6 +627,8 @@ struct IocSpliceDev {
     ioc_splice_stats* sstats;
     IocSpliceIv* plan;
     uint32_t* plan_n;
+    const ioc_window_variant* var;  // NULL, or the splice by variant: a record per site, keys are key2, and win_off / wseq / wqual /
+                                    // win_bytes describe the variant stage's slots (2 n_sites + 1 offsets, slot 2 k + h of site k)
 };
 hipError_t iock_splice_plan(hipStream_t st, const IocSpliceDev& v);
 // k_splice_call: the count pass (emit false: seg_len and stats, a word and a record per group-segment) or the write pass (emit true:

@@ -6,6 +6,9 @@
 //                       group-segment's key (splice_state; OVERLAP depends on the last DONE site, so the wave walks the sites in
 //                       turn, a broadcast a site), the site records, the splice record and the plan — the DONE sites' intervals
 //                       [lo, hi) with where their window's bytes lie, at most 32, ascending.
+//   k_splice_plan<true>  the same over the variant stage's slots (ioc_host_isoform_splice_variants): the lane loads its variant record
+//                       too and both ends of the slot its key2 state takes, 2 b for CARRY and 2 b + 1 for CARRY_B; the walk and what
+//                       it writes are the same, so the call passes below serve both.
 //   k_splice_call<false> the shape of k_pile_call: a workgroup per group-segment, chunks of IOC_PILE_CALL_CHUNK rows, a lane per
 //                       row.  The plan sits in LDS; a row inside an interval counts nothing, the row lo of one counts its window's
 //                       length (up to 7 IOC_WIN_MAX + 6 bytes, so the sums are 32-bit words all the way, never the 7 bytes a row
@@ -32,7 +35,9 @@ constexpr uint32_t WAVES = CHUNK / 64u;
 constexpr uint32_t PLAN_MAX = IOC_SPLICE_PLAN_MAX;
 static_assert(CHUNK % 64u == 0 && WAVES >= 1 && WAVES <= 16 && PLAN_MAX <= 64u && PLAN_MAX <= CHUNK, "whole waves, a lane per site");
 
-// a wave per group-segment, a lane per site
+// a wave per group-segment, a lane per site.  VARIANTS (ioc_planes_isoforms_full_variants): keys are key2, the lane loads its variant
+// record as well, and win_off is the slots' — the lane's bytes are those of the slot its state takes.
+template <bool VARIANTS>
 __global__ void __launch_bounds__(CHUNK)
 k_splice_plan(IocSpliceDev v)
 {
@@ -45,12 +50,21 @@ k_splice_plan(IocSpliceDev v)
     const unsigned long long key = v.keys[x];
     const bool mine = lane < ns && uint64_t(s0) + lane < v.n_sites;
     ioc_insert_window w{};
+    ioc_window_variant wv{};
     long long off = 0, end = 0;
-    if (mine) w = v.win[s0 + lane], off = v.win_off[s0 + lane], end = v.win_off[s0 + lane + 1];
+    if (VARIANTS) {
+        if (mine) {  // (lane < 32: the shift stays inside the key; slot_off has 2 n_sites + 1 entries)
+            w = v.win[s0 + lane], wv = v.var[s0 + lane];
+            const int32_t which = splice_variant_which(uint32_t(key >> (2u * lane)) & 3u);
+            const uint64_t slot = 2u * (uint64_t(s0) + lane) + uint32_t(which > 0);
+            off = v.win_off[slot], end = v.win_off[slot + 1u];
+        }
+    } else if (mine)
+        w = v.win[s0 + lane], off = v.win_off[s0 + lane], end = v.win_off[s0 + lane + 1];
     int32_t state = IOC_SPLICE_LACK, last_hi = 0;
     uint32_t idx = 0, n_done = 0;
     for (uint32_t b = 0; b < ns; ++b) {  // (uniform: every lane of the wave takes every step)
-        int32_t s = lane == b && mine ? splice_state(key, b, w, last_hi) : IOC_SPLICE_LACK;
+        int32_t s = lane == b && mine ? (VARIANTS ? splice_state_variants(key, b, w, wv, last_hi) : splice_state(key, b, w, last_hi)) : IOC_SPLICE_LACK;
         s = __shfl(s, int(b), 64);
         const int32_t hi = __shfl(w.hi, int(b), 64);
         if (lane == b) state = s, idx = n_done;
@@ -174,11 +188,15 @@ k_splice_call(IocSpliceDev v, const ioc_pileup_col* __restrict__ cols, const ioc
 
 }  // namespace
 
-// k_splice_plan over the view's group-segments: the site records, the splice records and the plans
+// k_splice_plan over the view's group-segments: the site records, the splice records and the plans; the slot-aware instantiation
+// where the view has variant records
 hipError_t iock_splice_plan(hipStream_t st, const IocSpliceDev& v)
 {
     if (v.n_gsegs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_splice_plan, dim3((v.n_gsegs + WAVES - 1u) / WAVES), dim3(CHUNK), 0, st, v);
+    if (v.var)
+        hipLaunchKernelGGL((k_splice_plan<true>), dim3((v.n_gsegs + WAVES - 1u) / WAVES), dim3(CHUNK), 0, st, v);
+    else
+        hipLaunchKernelGGL((k_splice_plan<false>), dim3((v.n_gsegs + WAVES - 1u) / WAVES), dim3(CHUNK), 0, st, v);
     return hipGetLastError();
 }
 
