@@ -4,6 +4,7 @@ Everything here calls the C ABI of libisonclust2_hip.so; numpy arrays are only t
 the flat SoA the ABI takes.  No compute happens in Python and nothing falls back to the CPU.
 """
 import ctypes as C
+import types
 
 import numpy as np
 
@@ -1366,6 +1367,34 @@ class Context:
             out.update(rows=[tab[r0[g]:r0[g + 1]] for g in range(ns)])
         return out
 
+    def _blocks_family(self, pairs, k, segs, seg_of_pair, rule, stats, tables, rows, cap, match, mismatch, gap_extend):
+        """What every call of the block family (align_pairs_blocks and the calls that go on from its block search) begins with: the
+        pairs', the segments' and the block search's arrays.  Returns them as one record; `lead` is the arguments all of the entry
+        points take first, the context's handle to out_cols."""
+        f = types.SimpleNamespace(n=len(pairs), ns=len(segs), stats=stats, tables=tables, rows=rows)
+        n, ns = f.n, f.ns
+        arr = self._aln_pairs(pairs)
+        sarr, f.sop, f.rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
+        f.r = _blocks_rule(rule)
+        (f.tab, f.blocks, f.boff, f.seg), cap = self._blocks_out(ns, f.rlen, f.r, rows, cap)
+        (f.score, f.win, f.ratio), ptrs = self._aln_out(n)
+        f.reads = np.zeros(n, READ_BLOCKS_DTYPE)
+        f.st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
+        f.cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        f.lead = (self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, f.st.ctypes.data if stats and n else None, ns, sarr, _p(f.sop, C.c_int32), *f.r,
+                  f.tab.ctypes.data if rows and len(f.tab) else None, f.blocks.ctypes.data, cap, _p(f.boff, C.c_int64), f.reads.ctypes.data if n else None,
+                  f.seg.ctypes.data if ns else None, f.cols.ctypes.data if tables and n_rows else None)
+        return f
+
+    def _blocks_family_out(self, f, **more):
+        """... and what every one of them ends with: align_pairs_blocks' dict, what the later stages made (`more`), `stats`, `cols` and `row0`"""
+        out = {"score": f.score, "windows": f.win, "ratio": f.ratio, **self._blocks_dict(f.ns, f.rlen, f.n, f.tab, f.blocks, f.boff, f.reads, f.seg), **more}
+        if f.stats:
+            out["stats"] = f.st
+        if f.tables:
+            out.update(cols=f.cols, row0=self._row0(f.rlen))
+        return out
+
     def planes_blocks(self, rlen, seg_of_pair, base, rows=True, cap=None, **rule):
         """ioc_planes_blocks: the exon blocks of many segments and every read's isoform on the device, from host base planes — `rlen`
         the segments' lengths, seg_of_pair per pair, `base` a list per pair of what ops_project gives for that pair (a segment's
@@ -1449,30 +1478,14 @@ class Context:
         min_ins / slack / max_sites for the sites (min_depth, min_alt and min_pct are shared).  Returns align_pairs_blocks' dict,
         byte for byte, and under `inserts` what Context.planes_inserts returns, group / how of its reads being the isoform over blocks
         and sites together."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
-        r = _blocks_rule(rule)
-        ir = [int(min_ins), int(slack), r[1], r[2], r[3], int(max_sites)]
-        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
+        f = self._blocks_family(pairs, k, segs, seg_of_pair, rule, stats, tables, rows, cap, match, mismatch, gap_extend)
+        n, ns, rlen = f.n, f.ns, f.rlen
+        ir = [int(min_ins), int(slack), f.r[1], f.r[2], f.r[3], int(max_sites)]
         (itab, sites, soff, iseg), sites_cap = self._inserts_out(ns, rlen, ir, rows, sites_cap)
-        (score, win, ratio), ptrs = self._aln_out(n)
-        reads, ireads = np.zeros(n, READ_BLOCKS_DTYPE), np.zeros(n, READ_INSERTS_DTYPE)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        self._chk(self.L.ioc_align_pairs_blocks_inserts(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
-                                                        _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
-                                                        _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
-                                                        cols.ctypes.data if tables and n_rows else None, ir[0], ir[1], ir[5],
-                                                        itab.ctypes.data if rows and len(itab) else None, sites.ctypes.data, sites_cap, _p(soff, C.c_int64),
-                                                        ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None))
-        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
-               "inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg)}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out.update(cols=cols, row0=self._row0(rlen))
-        return out
+        ireads = np.zeros(n, READ_INSERTS_DTYPE)
+        self._chk(self.L.ioc_align_pairs_blocks_inserts(*f.lead, ir[0], ir[1], ir[5], itab.ctypes.data if rows and len(itab) else None, sites.ctypes.data, sites_cap,
+                                                        _p(soff, C.c_int64), ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None))
+        return self._blocks_family_out(f, inserts=self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg))
 
     @staticmethod
     def _windows_dict(win, seq, qual, off, pol):
@@ -1589,17 +1602,11 @@ class Context:
         """ioc_align_pairs_blocks_inserts_seq: align_pairs_blocks_inserts with every pair's position plane projected as well and the
         window kernels behind the insert kernels, on the device, every pair aligned once.  Returns align_pairs_blocks_inserts' dict,
         byte for byte, and under `insert_windows` what Context.planes_insert_windows returns (without tables) for the sites kept."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
-        r = _blocks_rule(rule)
-        ir = [int(min_ins), int(slack), r[1], r[2], r[3], int(max_sites)]
-        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
+        f = self._blocks_family(pairs, k, segs, seg_of_pair, rule, stats, tables, rows, cap, match, mismatch, gap_extend)
+        n, ns, rlen, sop = f.n, f.ns, f.rlen, f.sop
+        ir = [int(min_ins), int(slack), f.r[1], f.r[2], f.r[3], int(max_sites)]
         (itab, sites, soff, iseg), sites_cap = self._inserts_out(ns, rlen, ir, rows, sites_cap)
-        (score, win, ratio), ptrs = self._aln_out(n)
-        reads, ireads = np.zeros(n, READ_BLOCKS_DTYPE), np.zeros(n, READ_INSERTS_DTYPE)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        ireads = np.zeros(n, READ_INSERTS_DTYPE)
         S = sum(planes_inserts_bound(m, ir[5]) for m in rlen)
         win_cap = insert_windows_bound(S, max_win) if win_cap is None else int(win_cap)
         wrec, woff, wpol = np.zeros(max(S, 1), INSERT_WINDOW_DTYPE), np.zeros(S + 1, np.int64), np.zeros(max(S, 1), POLISH_STATS_DTYPE)
@@ -1627,31 +1634,21 @@ class Context:
                     v_variant.ctypes.data, v_agree.ctypes.data, v_reads.ctypes.data, v_seg.ctypes.data)
             if _full is not None:   # (align_pairs_isoforms_full_variants: both, the variants' outputs first)
                 entry, more = self.L.ioc_align_pairs_isoforms_full_variants, more + more_full
-        self._chk(entry(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
-                                                            _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
-                                                            _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
-                                                            cols.ctypes.data if tables and n_rows else None, ir[0], ir[1], ir[5],
-                                                            itab.ctypes.data if rows and len(itab) else None, sites.ctypes.data, sites_cap, _p(soff, C.c_int64),
-                                                            ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None, int(max_win), int(win_match),
-                                                            int(win_mismatch), int(win_gap), int(polish_min_depth), wrec.ctypes.data, wseq.ctypes.data,
-                                                            wqual.ctypes.data, win_cap, _p(woff, C.c_int64), wpol.ctypes.data, *more))
+        self._chk(entry(*f.lead, ir[0], ir[1], ir[5], itab.ctypes.data if rows and len(itab) else None, sites.ctypes.data, sites_cap, _p(soff, C.c_int64),
+                        ireads.ctypes.data if n else None, iseg.ctypes.data if ns else None, int(max_win), int(win_match), int(win_mismatch), int(win_gap),
+                        int(polish_min_depth), wrec.ctypes.data, wseq.ctypes.data, wqual.ctypes.data, win_cap, _p(woff, C.c_int64), wpol.ctypes.data, *more))
         kept = int(soff[ns]) if ns else 0
-        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
-               "inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg),
-               "insert_windows": self._windows_dict(wrec[:kept], wseq, wqual, woff[:kept + 1], wpol[:kept])}
+        made = {"inserts": self._inserts_dict(ns, rlen, itab, sites, soff, ireads, iseg),
+                "insert_windows": self._windows_dict(wrec[:kept], wseq, wqual, woff[:kept + 1], wpol[:kept])}
         if _variants is not None:
-            out["insert_variants"] = {"win": wrec[:kept], "var": v_var[:kept], "seq": [v_seq[v_off[x]:v_off[x + 1]].tobytes() for x in range(2 * kept)],
-                                      "qual": [v_qual[v_off[x]:v_off[x + 1]].tobytes() for x in range(2 * kept)], "off": v_off[:2 * kept + 1], "polish": v_pol[:2 * kept],
-                                      "variant": v_variant[:n], "agree": v_agree[:n], "reads": v_reads[:n], "seg": v_seg[:ns]}
+            made["insert_variants"] = {"win": wrec[:kept], "var": v_var[:kept], "seq": [v_seq[v_off[x]:v_off[x + 1]].tobytes() for x in range(2 * kept)],
+                                       "qual": [v_qual[v_off[x]:v_off[x + 1]].tobytes() for x in range(2 * kept)], "off": v_off[:2 * kept + 1], "polish": v_pol[:2 * kept],
+                                       "variant": v_variant[:n], "agree": v_agree[:n], "reads": v_reads[:n], "seg": v_seg[:ns]}
         if _full is not None:
             G = int(f_ioff[ns])
-            out["isoforms_full"] = {**self._groups_out(f_ioff, f_seq, f_qual, f_off, f_pol[:G]), "off": f_off[:G + 1], "sstats": f_sst[:G],
-                                    "splice": [f_splice[int(f_spoff[x]):int(f_spoff[x + 1])] for x in range(G)], "splice_off": f_spoff[:G + 1]}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out.update(cols=cols, row0=self._row0(rlen))
-        return out
+            made["isoforms_full"] = {**self._groups_out(f_ioff, f_seq, f_qual, f_off, f_pol[:G]), "off": f_off[:G + 1], "sstats": f_sst[:G],
+                                     "splice": [f_splice[int(f_spoff[x]):int(f_spoff[x + 1])] for x in range(G)], "splice_off": f_spoff[:G + 1]}
+        return self._blocks_family_out(f, **made)
 
     def align_pairs_blocks_inserts_variants(self, pairs, k, segs, seg_of_pair, min_agree=VARIANTS_RULE["min_agree"], var_cap=None, **kw):
         """ioc_align_pairs_blocks_inserts_variants: align_pairs_blocks_inserts_seq with the variant kernels behind the window kernels —
@@ -1684,25 +1681,9 @@ class Context:
         on the device, every pair aligned once — segs / seg_of_pair as for align_pairs_alleles; the rule as keywords.  Returns a dict:
         score, windows, ratio, and `blocks`, `block_off`, `reads`, `seg`, `rows` as Context.planes_blocks returns them; with stats=True
         `stats` (ALN_STATS_DTYPE per pair), with tables=True `cols` and `row0`."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
-        r = _blocks_rule(rule)
-        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
-        (score, win, ratio), ptrs = self._aln_out(n)
-        reads = np.zeros(n, READ_BLOCKS_DTYPE)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        self._chk(self.L.ioc_align_pairs_blocks(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
-                                                _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
-                                                _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
-                                                cols.ctypes.data if tables and n_rows else None))
-        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg)}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out.update(cols=cols, row0=self._row0(rlen))
-        return out
+        f = self._blocks_family(pairs, k, segs, seg_of_pair, rule, stats, tables, rows, cap, match, mismatch, gap_extend)
+        self._chk(self.L.ioc_align_pairs_blocks(*f.lead))
+        return self._blocks_family_out(f)
 
     @staticmethod
     def _ends_out(ns, rlen, n_reads, rule, rows, sites_cap, variants_cap):
@@ -1758,33 +1739,18 @@ class Context:
         pair aligned once — the block rule as keywords, slack / min_over / ends_min_pct / max_sites / max_variants for the ends
         (min_depth and min_alt are shared), pre_group being the block stage's isoform.  Returns align_pairs_blocks' dict, byte for
         byte, `extents` (READ_EXTENT_DTYPE per pair) and under `ends` what Context.reads_ends returns."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
-        r = _blocks_rule(rule)
-        er = [int(slack), int(min_over), r[1], r[2], int(ends_min_pct), int(max_sites), int(max_variants)]
-        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
-        sopa = np.asarray(sop, np.int64)
+        f = self._blocks_family(pairs, k, segs, seg_of_pair, rule, stats, tables, rows, cap, match, mismatch, gap_extend)
+        n, ns, rlen = f.n, f.ns, f.rlen
+        er = [int(slack), int(min_over), f.r[1], f.r[2], int(ends_min_pct), int(max_sites), int(max_variants)]
+        sopa = np.asarray(f.sop, np.int64)
         counts = np.bincount(sopa[(sopa >= 0) & (sopa < ns)], minlength=ns) if ns else []
         (etab, sites, soff, variants, voff, eseg), sites_cap, variants_cap = self._ends_out(ns, rlen, counts, er, rows, sites_cap, variants_cap)
-        (score, win, ratio), ptrs = self._aln_out(n)
-        reads, ereads, ext = np.zeros(n, READ_BLOCKS_DTYPE), np.zeros(n, READ_ENDS_DTYPE), np.zeros(n, READ_EXTENT_DTYPE)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
-        self._chk(self.L.ioc_align_pairs_blocks_ends(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
-                                                     _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
-                                                     _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
-                                                     cols.ctypes.data if tables and n_rows else None, er[0], er[1], er[4], er[5], er[6],
-                                                     ext.ctypes.data if n else None, etab.ctypes.data if rows and len(etab) else None, sites.ctypes.data,
-                                                     sites_cap, _p(soff, C.c_int64), variants.ctypes.data, variants_cap, _p(voff, C.c_int64),
-                                                     ereads.ctypes.data if n else None, eseg.ctypes.data if ns else None))
-        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg), "extents": ext,
-               "ends": self._ends_dict(ns, rlen, etab, sites, soff, variants, voff, ereads, eseg)}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out.update(cols=cols, row0=self._row0(rlen))
-        return out
+        ereads, ext = np.zeros(n, READ_ENDS_DTYPE), np.zeros(n, READ_EXTENT_DTYPE)
+        self._chk(self.L.ioc_align_pairs_blocks_ends(*f.lead, er[0], er[1], er[4], er[5], er[6], ext.ctypes.data if n else None,
+                                                     etab.ctypes.data if rows and len(etab) else None, sites.ctypes.data, sites_cap, _p(soff, C.c_int64),
+                                                     variants.ctypes.data, variants_cap, _p(voff, C.c_int64), ereads.ctypes.data if n else None,
+                                                     eseg.ctypes.data if ns else None))
+        return self._blocks_family_out(f, extents=ext, ends=self._ends_dict(ns, rlen, etab, sites, soff, variants, voff, ereads, eseg))
 
     @staticmethod
     def _groups_out(goff, seq, qual, off, pol):
@@ -1921,33 +1887,17 @@ class Context:
         segment called from the reads' planes where they lie — no read is aligned a second time.  Returns align_pairs_blocks' dict
         plus `gseq`, `gqual`, `gpolish` and `gseg_off` as planes_polish_groups returns them: isoform h of segment g from its direct
         and assigned reads, against the segment's frame.  polish_cap / iso_cap default to the bounds (blocks_polish_bound)."""
-        n, ns = len(pairs), len(segs)
-        arr = self._aln_pairs(pairs)
-        sarr, sop, rlen, n_rows = self._seg_args(n, segs, seg_of_pair)
-        r = _blocks_rule(rule)
-        (tab, blocks, boff, seg), cap = self._blocks_out(ns, rlen, r, rows, cap)
-        (score, win, ratio), ptrs = self._aln_out(n)
-        reads = np.zeros(n, READ_BLOCKS_DTYPE)
-        st = np.zeros(n, ALN_STATS_DTYPE) if stats else None
-        cols = np.zeros(n_rows, PILEUP_DTYPE) if tables else None
+        f = self._blocks_family(pairs, k, segs, seg_of_pair, rule, stats, tables, rows, cap, match, mismatch, gap_extend)
+        ns, rlen, sop = f.ns, f.rlen, f.sop
         count = np.bincount(sop[(sop >= 0) & (sop < ns)], minlength=ns) if ns else np.zeros(0, np.int64)
         bounds = [blocks_polish_bound(rlen[g], count[g], max(int(max_iso), 0)) for g in range(ns)]
         i_cap = sum(b[0] for b in bounds) if iso_cap is None else int(iso_cap)
         p_cap = sum(b[1] for b in bounds) if polish_cap is None else int(polish_cap)
         seq, qual = np.zeros(max(p_cap, 1), np.uint8), np.zeros(max(p_cap, 1), np.uint8)
         off, pol, goff = np.zeros(max(i_cap, 0) + 1, np.int64), np.zeros(max(i_cap, 1), POLISH_STATS_DTYPE), np.zeros(ns + 1, np.int64)
-        self._chk(getattr(self.L, _entry)(self.h, n, arr, k, match, mismatch, gap_extend, *ptrs, st.ctypes.data if stats and n else None, ns, sarr,
-                                                       _p(sop, C.c_int32), *r, tab.ctypes.data if rows and len(tab) else None, blocks.ctypes.data, cap,
-                                                       _p(boff, C.c_int64), reads.ctypes.data if n else None, seg.ctypes.data if ns else None,
-                                                       cols.ctypes.data if tables and n_rows else None, int(max_iso), int(polish_min_depth), seq.ctypes.data,
-                                                       qual.ctypes.data, p_cap, _p(off, C.c_int64), pol.ctypes.data, i_cap, _p(goff, C.c_int64)))
-        out = {"score": score, "windows": win, "ratio": ratio, **self._blocks_dict(ns, rlen, n, tab, blocks, boff, reads, seg),
-               **self._groups_out(goff, seq, qual, off, pol)}
-        if stats:
-            out["stats"] = st
-        if tables:
-            out.update(cols=cols, row0=self._row0(rlen))
-        return out
+        self._chk(getattr(self.L, _entry)(*f.lead, int(max_iso), int(polish_min_depth), seq.ctypes.data, qual.ctypes.data, p_cap, _p(off, C.c_int64), pol.ctypes.data,
+                                          i_cap, _p(goff, C.c_int64)))
+        return self._blocks_family_out(f, **self._groups_out(goff, seq, qual, off, pol))
 
     def planes_polish_groups_weighted(self, frames, seg_of_pair, group, n_groups, base, slots, wbase, wslots, min_depth=3, tables=False, cap=None):
         """ioc_planes_polish_groups_weighted: planes_polish_groups with every read's vote counted by its weight — wbase / wslots the

@@ -286,6 +286,13 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
         r.read_blocks.assign(np, ioc_read_blocks{});
         std::vector<ioc_aln_stats> aln(o.stats && !have_first ? np : 0);
         if (o.pileup && !have_first) r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
+        // every call of the block family begins with the same arguments, the context's to the table's: `more` is what its later stages take
+        const auto blocks_call = [&](auto entry, const char* what, auto... more) {
+            check(c, entry(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(), io.min_gap,
+                           io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(),
+                           r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr, more...),
+                  what);
+        };
         if (o.iso_polish()) {
             PolishedSet& ip = r.iso_polished;
             const IsoCapacity icap = iso_polish_capacity(g, io.polish_max);
@@ -296,106 +303,72 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
                 if (g.qoffs != g.offs) die("--isoforms-polish-weighted: a quality line is not as long as its sequence!");
                 check(c, ioc_align_set_pool_qual(c, g.quals.data(), int64_t(g.quals.size())), "pool qualities");
             }
-            const auto call = io.polish_weighted ? ioc_align_pairs_blocks_polish_weighted : ioc_align_pairs_blocks_polish;
-            check(c, call(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(), io.min_gap,
-                          io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(),
-                          r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr, io.polish_max, io.polish_min_depth, &ip.seq[0], &ip.qual[0],
-                          icap.bytes, ip.off.data(), ip.stats.data(), icap.isoforms, r.iso_off.data()),
-                  io.polish_weighted ? "exon blocks with the isoforms' weighted consensus" : "exon blocks with the isoforms' consensus");
+            blocks_call(io.polish_weighted ? ioc_align_pairs_blocks_polish_weighted : ioc_align_pairs_blocks_polish,
+                        io.polish_weighted ? "exon blocks with the isoforms' weighted consensus" : "exon blocks with the isoforms' consensus", io.polish_max,
+                        io.polish_min_depth, &ip.seq[0], &ip.qual[0], icap.bytes, ip.off.data(), ip.stats.data(), icap.isoforms, r.iso_off.data());
         } else if (io.inserts) {
             const int64_t icap = inserts_capacity(g, io.ins_max);
             r.inserts.assign(size_t(std::max<int64_t>(icap, 1)), ioc_pile_insert{}), r.insert_off.assign(ns + 1, 0), r.inserts_seg.assign(ns, ioc_inserts_seg{});
             r.read_inserts.assign(np, ioc_read_inserts{});
+            const auto inserts_call = [&](auto entry, const char* what, auto... more) {
+                blocks_call(entry, what, io.min_ins, io.ins_slack, io.ins_max, nullptr, r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(),
+                            r.inserts_seg.data(), more...);
+            };
             if (io.inserts_seq) {
                 // (the scoring of the windows: the aligner's match and mismatch, a gap that costs what a mismatch does; the call at depth 3)
                 const int64_t wcap = icap * (7 * int64_t(io.ins_max_win) + 6);
                 r.ins_windows.assign(size_t(std::max<int64_t>(icap, 1)), ioc_insert_window{}), r.win_off.assign(size_t(icap) + 1, 0);
                 r.win_stats.assign(size_t(std::max<int64_t>(icap, 1)), ioc_polish_stats{});
                 r.wseq.assign(size_t(std::max<int64_t>(wcap, 1)), '\0'), r.wqual.assign(size_t(std::max<int64_t>(wcap, 1)), '\0');
-                if (io.full) {
-                    // (the room is the bound, which is generous: a window's 7 max_win + 6 bytes a site an isoform; the pages the call does not write are never touched)
-                    const IsoCapacity fcap = iso_full_capacity(g, io.full_max, io.ins_max, io.ins_max_win);
-                    r.fseq.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]), r.fqual.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]);
-                    r.full_off.assign(ns + 1, 0), r.fseq_off.assign(size_t(fcap.isoforms) + 1, 0), r.fsplice_off.assign(size_t(fcap.isoforms) + 1, 0);
-                    r.fstats.assign(size_t(std::max<int64_t>(fcap.isoforms, 1)), ioc_polish_stats{});
-                    r.fsplice.assign(size_t(std::max<int64_t>(fcap.isoforms * io.ins_max, 1)), ioc_splice_site{});
-                    check(c, ioc_align_pairs_isoforms_full(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
-                                                           g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
-                                                           r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
-                                                           o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
-                                                           r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(), io.ins_max_win,
-                                                           2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(), r.win_stats.data(),
-                                                           io.full_max, r.fseq.get(), r.fqual.get(), fcap.bytes, r.fseq_off.data(), r.fstats.data(), nullptr,
-                                                           r.fsplice.data(), int64_t(r.fsplice.size()), r.fsplice_off.data(), fcap.isoforms, r.full_off.data()),
-                          "exon blocks with the insertion sites, their sequences and the isoforms' full-length sequences");
-                } else if (io.variants) {
+                const bool variants = io.variants && !io.full, full = io.full || (variants && io.full_variants);
+                if (variants) {
                     r.win_variants.assign(size_t(std::max<int64_t>(icap, 1)), ioc_window_variant{}), r.vslot_off.assign(2 * size_t(icap) + 1, 0);
                     r.var_stats.assign(size_t(std::max<int64_t>(2 * icap, 1)), ioc_polish_stats{});
                     r.vseq.assign(size_t(std::max<int64_t>(2 * wcap, 1)), '\0'), r.vqual.assign(size_t(std::max<int64_t>(2 * wcap, 1)), '\0');
                     r.variant.assign(np * size_t(IOC_INSERTS_MAX), 0), r.read_variants.assign(np, ioc_read_variants{}), r.variants_seg.assign(ns, ioc_variants_seg{});
-                    if (io.full_variants) {
-                        // (the full call's room: one slot a site is taken)
-                        const IsoCapacity fcap = iso_full_capacity(g, io.full_max, io.ins_max, io.ins_max_win);
-                        r.fseq.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]), r.fqual.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]);
-                        r.full_off.assign(ns + 1, 0), r.fseq_off.assign(size_t(fcap.isoforms) + 1, 0), r.fsplice_off.assign(size_t(fcap.isoforms) + 1, 0);
-                        r.fstats.assign(size_t(std::max<int64_t>(fcap.isoforms, 1)), ioc_polish_stats{});
-                        r.fsplice.assign(size_t(std::max<int64_t>(fcap.isoforms * io.ins_max, 1)), ioc_splice_site{});
-                        check(c, ioc_align_pairs_isoforms_full_variants(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
-                                                                        g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks,
-                                                                        nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
-                                                                        o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
-                                                                        r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(),
-                                                                        io.ins_max_win, 2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(),
-                                                                        r.win_stats.data(), io.variants_min_agree, r.win_variants.data(), &r.vseq[0], &r.vqual[0], 2 * wcap,
-                                                                        r.vslot_off.data(), r.var_stats.data(), r.variant.data(), nullptr, r.read_variants.data(),
-                                                                        r.variants_seg.data(), io.full_max, r.fseq.get(), r.fqual.get(), fcap.bytes, r.fseq_off.data(),
-                                                                        r.fstats.data(), nullptr, r.fsplice.data(), int64_t(r.fsplice.size()), r.fsplice_off.data(),
-                                                                        fcap.isoforms, r.full_off.data()),
+                }
+                // (the full-length room is the bound, which is generous: a window's 7 max_win + 6 bytes a site an isoform — by variant one
+                // slot a site is taken; the pages the call does not write are never touched)
+                const IsoCapacity fcap = full ? iso_full_capacity(g, io.full_max, io.ins_max, io.ins_max_win) : IsoCapacity{};
+                if (full) {
+                    r.fseq.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]), r.fqual.reset(new char[size_t(std::max<int64_t>(fcap.bytes, 1))]);
+                    r.full_off.assign(ns + 1, 0), r.fseq_off.assign(size_t(fcap.isoforms) + 1, 0), r.fsplice_off.assign(size_t(fcap.isoforms) + 1, 0);
+                    r.fstats.assign(size_t(std::max<int64_t>(fcap.isoforms, 1)), ioc_polish_stats{});
+                    r.fsplice.assign(size_t(std::max<int64_t>(fcap.isoforms * io.ins_max, 1)), ioc_splice_site{});
+                }
+                // the window stage's arguments behind the insert stage's, the variant stage's behind those, the isoforms' last
+                const auto windows_call = [&](auto entry, const char* what, auto... more) {
+                    inserts_call(entry, what, io.ins_max_win, 2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(), r.win_stats.data(), more...);
+                };
+                const auto variants_call = [&](auto entry, const char* what, auto... more) {
+                    windows_call(entry, what, io.variants_min_agree, r.win_variants.data(), &r.vseq[0], &r.vqual[0], 2 * wcap, r.vslot_off.data(), r.var_stats.data(),
+                                 r.variant.data(), nullptr, r.read_variants.data(), r.variants_seg.data(), more...);
+                };
+                const auto full_call = [&](const auto& call, auto entry, const char* what) {
+                    call(entry, what, io.full_max, r.fseq.get(), r.fqual.get(), fcap.bytes, r.fseq_off.data(), r.fstats.data(), nullptr, r.fsplice.data(),
+                         int64_t(r.fsplice.size()), r.fsplice_off.data(), fcap.isoforms, r.full_off.data());
+                };
+                if (variants && full)
+                    full_call(variants_call, ioc_align_pairs_isoforms_full_variants,
                               "exon blocks with the insertion sites, their sequences, their variants and the isoforms' full-length sequences by variant");
-                    } else {
-                        check(c, ioc_align_pairs_blocks_inserts_variants(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
-                                                                         g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks,
-                                                                         nullptr, r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
-                                                                         o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
-                                                                         r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(),
-                                                                         io.ins_max_win, 2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(),
-                                                                         r.win_stats.data(), io.variants_min_agree, r.win_variants.data(), &r.vseq[0], &r.vqual[0], 2 * wcap,
-                                                                         r.vslot_off.data(), r.var_stats.data(), r.variant.data(), nullptr, r.read_variants.data(),
-                                                                         r.variants_seg.data()),
-                              "exon blocks with the insertion sites, their sequences and their variants");
-                    }
-                } else
-                check(c, ioc_align_pairs_blocks_inserts_seq(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
-                                                            g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
-                                                            r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
-                                                            o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr,
-                                                            r.inserts.data(), icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data(), io.ins_max_win,
-                                                            2, -2, 2, 3, r.ins_windows.data(), &r.wseq[0], &r.wqual[0], wcap, r.win_off.data(), r.win_stats.data()),
-                      "exon blocks with the insertion sites and their sequences");
+                else if (full)
+                    full_call(windows_call, ioc_align_pairs_isoforms_full, "exon blocks with the insertion sites, their sequences and the isoforms' full-length sequences");
+                else if (variants)
+                    variants_call(ioc_align_pairs_blocks_inserts_variants, "exon blocks with the insertion sites, their sequences and their variants");
+                else
+                    windows_call(ioc_align_pairs_blocks_inserts_seq, "exon blocks with the insertion sites and their sequences");
             } else
-            check(c, ioc_align_pairs_blocks_inserts(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(),
-                                                    g.seg_of_pair.data(), io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr,
-                                                    r.blocks.data(), cap, r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(),
-                                                    o.pileup && !have_first ? r.cols.data() : nullptr, io.min_ins, io.ins_slack, io.ins_max, nullptr, r.inserts.data(),
-                                                    icap, r.insert_off.data(), r.read_inserts.data(), r.inserts_seg.data()),
-                  "exon blocks with the insertion sites");
+                inserts_call(ioc_align_pairs_blocks_inserts, "exon blocks with the insertion sites");
         } else if (io.ends) {
             const EndsCapacity ecap = ends_capacity(g, io.ends_max, io.ends_max_variants);
             r.end_sites.assign(size_t(std::max<int64_t>(ecap.sites, 1)), ioc_end_site{}), r.end_off.assign(2 * ns + 1, 0), r.var_off.assign(ns + 1, 0);
             r.end_variants.assign(size_t(std::max<int64_t>(ecap.variants, 1)), ioc_end_variant{}), r.ends_seg.assign(ns, ioc_ends_seg{});
             r.extents.assign(np, ioc_read_extent{}), r.read_ends.assign(np, ioc_read_ends{});
-            check(c, ioc_align_pairs_blocks_ends(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
-                                                 io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
-                                                 r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr,
-                                                 io.ends_slack, io.ends_min_over, io.ends_min_pct, io.ends_max, io.ends_max_variants, r.extents.data(), nullptr,
-                                                 r.end_sites.data(), ecap.sites, r.end_off.data(), r.end_variants.data(), ecap.variants, r.var_off.data(),
-                                                 r.read_ends.data(), r.ends_seg.data()),
-                  "exon blocks with the alternative ends");
+            blocks_call(ioc_align_pairs_blocks_ends, "exon blocks with the alternative ends", io.ends_slack, io.ends_min_over, io.ends_min_pct, io.ends_max,
+                        io.ends_max_variants, r.extents.data(), nullptr, r.end_sites.data(), ecap.sites, r.end_off.data(), r.end_variants.data(), ecap.variants,
+                        r.var_off.data(), r.read_ends.data(), r.ends_seg.data());
         } else {
-            check(c, ioc_align_pairs_blocks(c, n, pairs, k, 2, -2, 1, sc, win, nullptr, aln.empty() ? nullptr : aln.data(), n_segs, g.segs.data(), g.seg_of_pair.data(),
-                                            io.min_gap, io.min_depth, io.min_alt, io.min_pct, io.min_block, io.max_blocks, nullptr, r.blocks.data(), cap,
-                                            r.block_off.data(), r.read_blocks.data(), r.blocks_seg.data(), o.pileup && !have_first ? r.cols.data() : nullptr),
-                  "exon blocks");
+            blocks_call(ioc_align_pairs_blocks, "exon blocks");
         }
         if (o.stats && !have_first) r.stats = aln;
         have_first = true;

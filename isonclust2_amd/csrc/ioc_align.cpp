@@ -1259,8 +1259,7 @@ int ioc_host_insert_window_variants(const uint8_t* base, const uint32_t* qpos, c
         if (w.tlen > 0) consensus(k, va, size_t(w.template_pair), 0); else no_call();
         if (v.split) consensus(k, vb, size_t(v.template_pair_b), 1); else no_call();
     }
-    for (size_t i = 0; i < n; ++i)
-        for (size_t k = 0; k < S; ++k) mask2[i] |= blocks_state_mask(uint32_t(k), uint32_t(key2[i] >> (2 * k)) & 3u);
+    for (size_t i = 0; i < n; ++i) mask2[i] = blocks_key_mask(key2[i], uint32_t(S));
     if (call && int64_t(seq.size()) > cap) return IOC_ERR_CAPACITY;  // (the bound above holds it: pile_call_most a slot)
     std::copy(win.begin(), win.end(), out_win);
     std::copy(var.begin(), var.end(), out_var);

@@ -3,13 +3,16 @@
 // (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.  An entry point checks its arguments, plans its
 // segments and pairs on the host (SinkPlan, ioc_sink_plan.h) and runs device stages in a row (SinkRun): pile -> sites -> alleles ->
 // [split] -> [group pile -> call] -> copy-out for the alleles family, pile -> call -> copy-out for the polish family, pile -> correct ->
-// copy-out for the read correction, pile -> blocks -> [inserts | ends] -> copy-out for the exon blocks, the insertion sites and the alternative ends, upload -> the same stage for the calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
+// copy-out for the read correction, pile -> blocks -> [inserts -> [windows | variants] -> [full]] | [ends] | [polish] -> copy-out for the
+// block family (nine entry points, one record and one runner: BlocksCall, align_pairs_blocks_call), upload -> the same stage for the
+// calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <functional>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -118,6 +121,12 @@ int call_room_ok(ioc_ctx* c, const std::string& who, const CallOut& o, int64_t b
     return bound > 0 && (!o.seq || !o.qual) ? IOC_ERR_ARG : IOC_OK;
 }
 
+// what a pile that projects (`plane` given) lays down beside the base and the ins planes: the six slot planes, the seven weight
+// planes (which ask for the slot planes and for the pool's qualities), the length plane, the position plane
+struct PileProject {
+    bool ins = false, weights = false, ilen = false, qpos = false;
+};
+
 // ---- where the stages leave what they made (device pointers) ----
 struct PiledDev {  // pile: the tables of the kind (a_pile; a_pile_ins or a_pile_w) and, where it projects, the planes (a_planes)
     ioc_pileup_col *cols, *wcols;
@@ -154,6 +163,7 @@ struct IsoPolish {  // the call of the first min(n_groups, max_iso) isoforms of 
     CallOut call;
     int64_t iso_cap;
     int64_t* iso_off;
+    bool weighted = false;  // (ioc_align_pairs_blocks_polish_weighted: every isoform called by weight)
     bool ok() const { return max_iso >= 1 && call.ok() && iso_cap >= 0 && iso_off; }
 };
 // split (a_split): the member lists and the group bytes.  What a group pile reads beside the plan: those and the planes, on the
@@ -228,8 +238,8 @@ struct SinkRun {
         t.ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return IOC_OK;
     }
-    int pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane, int64_t plane_bytes, bool project_ins, PiledDev& d,
-             bool project_weights = false, bool project_ilen = false, bool project_qpos = false);
+    int pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane, int64_t plane_bytes, PileProject project,
+             PiledDev& d);
     int sites(const SitesRule& r, const SinkPlan& p, const ioc_pileup_col* d_cols, ioc_pile_site* out_sites, int64_t* site_off, int64_t* n_found, SitesDev& d);
     int alleles(const SitesDev& d, const SinkPlan& p, const int32_t* seg_of_pair, const PiledDev& planes, const int64_t* site_off, int64_t* allele_off, uint8_t* out_alleles);
     int split(const SplitCall& sp, size_t n, size_t np, const int32_t* seg_of_pair, const int64_t* site_off, const int64_t* allele_off, const ioc_pile_site* sites,
@@ -249,12 +259,12 @@ struct SinkRun {
 // Pile and project.  The tables of `kind`, n_rows records each — a_pile; a_pile_ins beside it (ins), or a_pile_w as [wcols][wins] (weighted)
 // — are reserved and zeroed and the pairs aligned into them (k_ops_pileup adds, where the walks' bytes lie, slice after slice and re-run after
 // re-run).  `plane` (the alleles family): every pair is projected as well, into the planes of a_planes, [base planes][ins planes] and, with
-// project_ins, [slot planes x 6] behind them, set to IOC_ALLELE_NONE / 0 once here; with project_weights (which asks for project_ins
-// and for the pool's qualities), [weight planes x 7] behind those, set to 0 with them.  A call without project_weights reserves what
-// it always did.  project_ilen: one more plane behind all of those, the length plane (k_ops_project_ilen), set to 0 with them.
-// project_qpos: behind that, from the next multiple of 16 bytes on, the position plane (k_ops_project_qpos), four bytes a row, set to 0.
+// pj.ins, [slot planes x 6] behind them, set to IOC_ALLELE_NONE / 0 once here; with pj.weights (which asks for pj.ins
+// and for the pool's qualities), [weight planes x 7] behind those, set to 0 with them.  A call without pj.weights reserves what
+// it always did.  pj.ilen: one more plane behind all of those, the length plane (k_ops_project_ilen), set to 0 with them.
+// pj.qpos: behind that, from the next multiple of 16 bytes on, the position plane (k_ops_project_qpos), four bytes a row, set to 0.
 int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, const int64_t* row_base, int64_t n_rows, const int64_t* plane,
-                  int64_t plane_bytes, bool project_ins, PiledDev& d, bool project_weights, bool project_ilen, bool project_qpos)
+                  int64_t plane_bytes, PileProject pj, PiledDev& d)
 {
     IOC_CHK(c, hipSetDevice(c->device));
     const size_t b_cols = size_t(n_rows) * sizeof(ioc_pileup_col), b_ins = size_t(n_rows) * sizeof(ioc_pileup_ins);
@@ -272,19 +282,19 @@ int SinkRun::pile(const AlnCall& a, PileKind kind, ioc_aln_stats* out_stats, con
     if (weighted) pl.wcols = second->as<ioc_pileup_col>(), pl.wins = reinterpret_cast<ioc_pileup_ins*>(second->as<uint8_t>() + b_cols);  // (b_cols: a multiple of 32)
     if (plane) {
         const size_t b_plane = size_t(plane_bytes);
-        const size_t n_zeroed = !project_ins ? 1 : 1 + size_t(IOC_PILE_INS_SLOTS) + (project_weights ? size_t(IOC_WEIGHT_PLANES) : 0);  // (the ins planes and on)
-        const size_t b_bytes = (1 + n_zeroed + (project_ilen ? 1 : 0)) * b_plane, o_qpos = (b_bytes + 15) & ~size_t(15);
-        IOC_TRY(ioc_reserve(c, c->a_planes, project_qpos ? o_qpos + 4 * b_plane : b_bytes));
+        const size_t n_zeroed = !pj.ins ? 1 : 1 + size_t(IOC_PILE_INS_SLOTS) + (pj.weights ? size_t(IOC_WEIGHT_PLANES) : 0);  // (the ins planes and on)
+        const size_t b_bytes = (1 + n_zeroed + (pj.ilen ? 1 : 0)) * b_plane, o_qpos = (b_bytes + 15) & ~size_t(15);
+        IOC_TRY(ioc_reserve(c, c->a_planes, pj.qpos ? o_qpos + 4 * b_plane : b_bytes));
         pl.project = true, pl.base_planes = c->a_planes.as<uint8_t>(), pl.ins_planes = pl.base_planes + b_plane;
         pl.plane_bytes = plane_bytes, pl.plane = plane;
-        if (project_ins) pl.project_ins = true, pl.slot_planes = pl.base_planes + 2 * b_plane;
-        if (project_ins && project_weights) pl.project_weights = true, pl.weight_planes = pl.slot_planes + size_t(IOC_PILE_INS_SLOTS) * b_plane;
-        if (project_ilen) pl.project_ilen = true, pl.ilen_planes = pl.base_planes + (1 + n_zeroed) * b_plane;
-        if (project_qpos) pl.project_qpos = true, pl.qpos_planes = reinterpret_cast<uint32_t*>(pl.base_planes + o_qpos);
+        if (pj.ins) pl.project_ins = true, pl.slot_planes = pl.base_planes + 2 * b_plane;
+        if (pj.ins && pj.weights) pl.project_weights = true, pl.weight_planes = pl.slot_planes + size_t(IOC_PILE_INS_SLOTS) * b_plane;
+        if (pj.ilen) pl.project_ilen = true, pl.ilen_planes = pl.base_planes + (1 + n_zeroed) * b_plane;
+        if (pj.qpos) pl.project_qpos = true, pl.qpos_planes = reinterpret_cast<uint32_t*>(pl.base_planes + o_qpos);
         if (b_plane > 0) {
             IOC_CHK(c, hipMemsetAsync(pl.base_planes, IOC_ALLELE_NONE, b_plane, c->stream));
-            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, (n_zeroed + (project_ilen ? 1 : 0)) * b_plane, c->stream));  // (and the slot, weight and length planes)
-            if (project_qpos) IOC_CHK(c, hipMemsetAsync(pl.qpos_planes, 0, 4 * b_plane, c->stream));
+            IOC_CHK(c, hipMemsetAsync(pl.ins_planes, 0, (n_zeroed + (pj.ilen ? 1 : 0)) * b_plane, c->stream));  // (and the slot, weight and length planes)
+            if (pj.qpos) IOC_CHK(c, hipMemsetAsync(pl.qpos_planes, 0, 4 * b_plane, c->stream));
         }
     }
     const AlnSink sink{SinkKind::reduced, len.data(), &t, {}, out_stats != nullptr, out_stats, pl};
@@ -785,6 +795,11 @@ int SinkRun::ends(const SinkPlan& pn, const int32_t* seg_of_pair, const ioc_read
 
 }  // namespace
 
+// (two weak instantiations the symbol list has held since the optimiser left them out of line in the function that carried four of
+// the block family's calls: instantiated here, so that the list does not hang on what is inlined where)
+template void std::vector<int64_t>::push_back(const int64_t&);
+template void std::vector<uint32_t>::push_back(uint32_t&&);
+
 // (pile_call_bound, pile_call_device, group_polish_ok, group_polish_device, pileup_call_tables and align_pairs_polish stand inside
 // extern "C", where they have always stood: there a function has external linkage even in an unnamed namespace, and these plain
 // names are part of the library's symbol list — which is why the call stage and the group polish are no members of SinkRun)
@@ -893,7 +908,7 @@ int align_pairs_polish(ioc_ctx* c, const AlnCall& a, ioc_aln_stats* out_stats, i
     if (n_segs == 0) return a.run(c, nullptr);
     SinkRun r{c};
     PiledDev d;
-    IOC_TRY(r.pile(a, weighted ? PileKind::weighted : PileKind::ins, out_stats, p.row_base.data(), p.n_rows, nullptr, 0, false, d));
+    IOC_TRY(r.pile(a, weighted ? PileKind::weighted : PileKind::ins, out_stats, p.row_base.data(), p.n_rows, nullptr, 0, PileProject{}, d));
     IOC_TRY(pile_call_device(r, p.segs, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), o, weighted ? d.wcols : d.cols, weighted ? d.wins : d.ins,
                    weighted ? d.cols : nullptr, p.n_rows));
     const size_t b_cols = size_t(p.n_rows) * sizeof(ioc_pileup_col);
@@ -946,7 +961,7 @@ static int align_pairs_alleles(const std::string& who, ioc_ctx* c, const AlnCall
     PiledDev piled;
     SitesDev sd;
     Planes laid{};  // (where each stage leaves what it made)
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, gp != nullptr, piled));
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, PileProject{/*ins*/ gp != nullptr}, piled));
     IOC_TRY(r.sites(rule, p, piled.cols, o.out_sites, o.site_off, o.n_found, sd));
     IOC_TRY(r.alleles(sd, p, o.seg_of_pair, piled, o.site_off, o.allele_off, o.out_alleles));
     if (split) IOC_TRY(r.split(*split, size_t(n_segs), size_t(n_pairs), o.seg_of_pair, o.site_off, o.allele_off, sd.sites, sd.alleles, true, laid));
@@ -1043,7 +1058,7 @@ int ioc_align_pairs_pileup(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pair
     if (n_pairs == 0 || n_rows == 0) return a.run(c, nullptr);
     SinkRun r{c};
     PiledDev d;
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, row_base, n_rows, nullptr, 0, false, d));
+    IOC_TRY(r.pile(a, PileKind::counts, out_stats, row_base, n_rows, nullptr, 0, PileProject{}, d));
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(n_rows) * sizeof(ioc_pileup_col)}}));
     if (getenv("IOC_TRACE"))
@@ -1329,7 +1344,7 @@ int ioc_align_pairs_correct(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pai
     if (n_segs == 0) return a.run(c, nullptr);
     SinkRun r{c};
     PiledDev d;
-    IOC_TRY(r.pile(a, PileKind::ins, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ true, d));
+    IOC_TRY(r.pile(a, PileKind::ins, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, PileProject{/*ins*/ true}, d));
     IOC_TRY(r.correct(p, seg_of_pair, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), d.cols, d.ins, Planes{},
                       Planes{nullptr, nullptr, nullptr, d.base, d.slots}, o));
     IOC_CHK(c, hipStreamSynchronize(c->stream));  // (a call without pairs has launched nothing that waited)
@@ -1369,37 +1384,6 @@ int ioc_planes_blocks(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   planes blocks: %d segments, %lld rows, %d pairs, %lld plane bytes, %lld blocks kept, the block kernels %.3f ms\n", n_segs,
                 (long long)p.n_rows, n_pairs, (long long)p.plane_bytes, (long long)block_off[n_segs], r.t.ms_blocks);
-    return IOC_OK;
-}
-
-// pile -> blocks -> copy-out.  ioc_align_pairs_alleles' pile, the table of counts with every pair projected beside it, and the block
-// kernels over the base planes where they lie: what comes back is the blocks, a record per pair and per segment, and the tables
-// only where they are asked for.
-int ioc_align_pairs_blocks(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
-                           int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
-                           const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
-                           int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off,
-                           ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols)
-{
-    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
-    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
-    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
-    SinkPlan p;
-    if (int st = p.from_pool("ioc_align_pairs_blocks", c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
-    IOC_TRY(blocks_room_ok(c, "ioc_align_pairs_blocks", o, p));
-    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
-    block_off[0] = 0;
-    if (n_segs == 0) return a.run(c, nullptr);
-    SinkRun r{c};
-    PiledDev d;
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d));
-    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o));  // (a_blocks is reserved here, after the walks)
-    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: blocks: %d segments, %lld rows, %d pairs, %lld blocks kept, %.3f MB (blocks, records%s%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms%s\n",
-                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], double(r.t.copied) * 1e-6, out_rows ? ", rows" : "", out_cols ? ", table" : "",
-                out_stats ? ", statistics" : "", r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_blocks,
-                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
     return IOC_OK;
 }
 
@@ -1451,60 +1435,10 @@ int ioc_planes_inserts(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t 
     return IOC_OK;
 }
 
-// pile -> blocks -> inserts -> copy-out.  ioc_align_pairs_blocks with the length plane projected beside the two, and behind the block
-// kernels the insert kernels over the planes where they lie, with the block stage's keys and masks where that stage left them: its
-// read records and masks stay in a_blocks, the insert stage has a_inserts.
-int ioc_align_pairs_blocks_inserts(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
-                                   int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
-                                   const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
-                                   int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
-                                   int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
-                                   int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
-                                   int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg)
-{
-    const std::string who = "ioc_align_pairs_blocks_inserts";
-    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
-    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
-    const InsertsOut io{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
-    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !io.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
-    SinkPlan p;
-    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
-    IOC_TRY(blocks_room_ok(c, who, o, p));
-    IOC_TRY(inserts_room_ok(c, who, io, p));
-    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
-    block_off[0] = 0, site_off[0] = 0;
-    if (n_segs == 0) return a.run(c, nullptr);
-    SinkRun r{c};
-    PiledDev d;
-    BlocksDev bd{};
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d, /*project_weights*/ false,
-                   /*project_ilen*/ true));
-    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o, &bd));  // (a_blocks is reserved here, after the walks; the segment records are the host's from here on)
-    std::vector<uint64_t> pre_full(size_t(n_segs), 0);
-    for (int32_t g = 0; g < n_segs; ++g) pre_full[size_t(g)] = blocks_full_mask(uint32_t(out_seg[g].n_blocks));
-    InsertsPre pre;
-    pre.pre_full = pre_full.data();
-    if (n_pairs > 0) {
-        static_assert(sizeof(ioc_read_blocks) % 8 == 0 && offsetof(ioc_read_blocks, key) == 0, "a record's first word is its key");
-        pre.dev_key = reinterpret_cast<const unsigned long long*>(bd.reads), pre.dev_key_stride = uint32_t(sizeof(ioc_read_blocks) / 8);
-        pre.dev_mask = bd.mask, pre.dev_mask_stride = 1;
-    }
-    IOC_TRY(r.inserts(p, seg_of_pair, nullptr, nullptr, d.base, d.ilen, pre, io));  // (a_inserts likewise)
-    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: blocks inserts: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ilen %.3f ms, ms_blocks %.3f ms, %s%s\n",
-                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[n_segs], double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_pileup,
-                r.t.ms_project, r.t.ms_project_ilen, r.t.ms_blocks, inserts_trace(r.t).c_str(),
-                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
-    return IOC_OK;
-}
-
-// what a search for ends refuses once its plan is known: IOC_OK, or the status with the message set
-static int ends_room_ok(ioc_ctx* c, const std::string& who, const EndsOut& o, const SinkPlan& p, const int32_t* seg_of_pair)
+// what a search for ends refuses once its plan is known (reads: reads_per_seg): IOC_OK, or the status with the message set
+static int ends_room_ok(ioc_ctx* c, const std::string& who, const EndsOut& o, const SinkPlan& p, const std::vector<int64_t>& reads)
 {
     int64_t bound = 0, vbound = 0;
-    std::vector<int64_t> reads(p.segs.size(), 0);
-    for (size_t i = 0; i < p.plane.size(); ++i) ++reads[size_t(seg_of_pair[i])];
     for (size_t g = 0; g < p.segs.size(); ++g)
         bound += 2 * ends_sites_most(p.segs[g].rlen, o.rule.max_sites), vbound += ends_variants_most(reads[g], o.rule.max_variants);
     if (o.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": sites_cap " + std::to_string(o.cap) + " below the bound " + std::to_string(bound));
@@ -1534,7 +1468,7 @@ int ioc_reads_ends(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n_pa
     for (int32_t i = 0; i < n_pairs; ++i)
         if (!ends_extent_ok(extents[i], rlen[seg_of_pair[i]]) || (pre_group && pre_group[i] < -1))
             return ioc_fail(c, IOC_ERR_ARG, "ioc_reads_ends: the extent or pre_group of pair " + std::to_string(i) + " is outside its segment's range");
-    IOC_TRY(ends_room_ok(c, "ioc_reads_ends", o, p, seg_of_pair));
+    IOC_TRY(ends_room_ok(c, "ioc_reads_ends", o, p, reads_per_seg(size_t(n_segs), size_t(n_pairs), seg_of_pair)));
     site_off[0] = 0, var_off[0] = 0;
     if (n_segs == 0) return IOC_OK;
     SinkRun r{c};
@@ -1545,52 +1479,6 @@ int ioc_reads_ends(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, int32_t n_pa
     return IOC_OK;
 }
 
-// pile -> blocks -> ends -> copy-out.  ioc_align_pairs_blocks with the statistics kernel run over every slice (into the caller's
-// records, or into the call's own where none are asked), and behind the block kernels the ends kernels: the extents are put together
-// on the host from the block records and the statistics, both of which the call holds there anyway, and uploaded with the stage's
-// tables; pre_group is the block stage's group where that stage left it (a_blocks), the ends stage has a_rends.
-int ioc_align_pairs_blocks_ends(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
-                                int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
-                                const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
-                                int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off,
-                                ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t slack, int32_t min_over,
-                                int32_t ends_min_pct, int32_t max_sites, int32_t max_variants, ioc_read_extent* out_extents, ioc_end_row* out_erows,
-                                ioc_end_site* out_sites, int64_t sites_cap, int64_t* site_off, ioc_end_variant* out_variants, int64_t variants_cap,
-                                int64_t* var_off, ioc_read_ends* out_ereads, ioc_ends_seg* out_eseg)
-{
-    const std::string who = "ioc_align_pairs_blocks_ends";
-    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
-    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
-    const EndsOut eo{{slack, min_over, min_depth, min_alt, ends_min_pct, max_sites, max_variants}, out_erows, out_sites, sites_cap, site_off, out_variants,
-                     variants_cap, var_off, out_ereads, out_eseg};
-    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !eo.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair || !out_extents)) || (n_segs > 0 && !segs))
-        return IOC_ERR_ARG;
-    SinkPlan p;
-    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
-    IOC_TRY(blocks_room_ok(c, who, o, p));
-    IOC_TRY(ends_room_ok(c, who, eo, p, seg_of_pair));
-    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
-    for (int32_t i = 0; i < n_pairs; ++i) out_extents[i] = ioc_read_extent{0, 0, 0, 0};
-    block_off[0] = 0, site_off[0] = 0, var_off[0] = 0;
-    if (n_segs == 0) return a.run(c, nullptr);
-    std::vector<ioc_aln_stats> own_stats(out_stats ? 0 : size_t(n_pairs), ioc_aln_stats{});
-    const ioc_aln_stats* stats = out_stats ? out_stats : own_stats.data();
-    SinkRun r{c};
-    PiledDev d;
-    BlocksDev bd{};
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats ? out_stats : own_stats.data(), p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ false, d));
-    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o, &bd));  // (a_blocks is reserved here, after the walks)
-    for (int32_t i = 0; i < n_pairs; ++i) out_extents[i] = ioc_read_extent{out_reads[i].first_row, out_reads[i].end_row, stats[i].lead_i, stats[i].trail_i};
-    static_assert(sizeof(ioc_read_blocks) % 4 == 0 && offsetof(ioc_read_blocks, group) % 4 == 0, "a record's group is a word of its own");
-    const int32_t* dev_group = n_pairs > 0 ? reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(bd.reads) + offsetof(ioc_read_blocks, group)) : nullptr;
-    IOC_TRY(r.ends(p, seg_of_pair, out_extents, nullptr, dev_group, uint32_t(sizeof(ioc_read_blocks) / 4), eo));  // (a_rends likewise)
-    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: blocks ends: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld end sites kept, %lld variants kept, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms, k_ops_stats %.3f ms, %s\n",
-                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[2 * n_segs], (long long)var_off[n_segs],
-                double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_pileup, r.t.ms_project, r.t.ms_blocks, r.t.ms_stats, ends_trace(r.t).c_str());
-    return IOC_OK;
-}
 
 // ---- the sequence of an inserted exon: the windows of the carriers at every kept site ----
 namespace {
@@ -2444,138 +2332,338 @@ int iso_full_ok(ioc_ctx* c, const std::string& who, const IsoFull& f, const Sink
 }
 }  // namespace
 
-// pile -> blocks -> inserts -> windows -> copy-out.  ioc_align_pairs_blocks_inserts with the position plane projected beside the other
-// two, and behind the insert kernels the window kernels over the planes where they lie; the sites and the keys are on the host when
-// the insert stage returns and travel back with the tables (32 bytes a site, 8 a pair).  vf (ioc_align_pairs_blocks_inserts_variants;
-// else NULL): the variant stage in the window stage's place, which returns the window call's outputs as well; the block stage's keys
-// are on the host by then and serve as pre_*, a read's mask being both bits of every block its key has a state at.
-static int align_pairs_inserts_seq(const std::string& who, const IsoFull* full, const VariantsFused* vf, ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
-                                       int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
-                                       const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
-                                       int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
-                                       int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
-                                       int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
-                                       int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
-                                       int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
-                                       int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats)
+// ---- the block family: pile -> blocks -> the stages that are on -> copy-out, one runner behind nine entry points ----
+namespace {
+struct EndsStage {  // the ends stage behind the block stage, and where the extents the call puts together for it go (a record a pair)
+    EndsOut o;
+    ioc_read_extent* extents;
+};
+// What a block-family call is: the alignment, the segments, the block search, and one member per later stage, set where the stage
+// is on.  Nine combinations are reachable, an entry point each: none | inserts | ends | inserts windows | inserts windows variants |
+// inserts windows full | inserts windows variants full | polish | polish weighted.
+struct BlocksCall {
+    std::string who;  // the entry point, as its refusals name it
+    AlnCall a;
+    ioc_aln_stats* out_stats;
+    int32_t n_segs;
+    const ioc_polish_seg* segs;
+    const int32_t* seg_of_pair;
+    BlocksOut o;
+    ioc_pileup_col* out_cols;
+    std::optional<InsertsOut> inserts;
+    std::optional<EndsStage> ends;
+    std::optional<WindowsOut> windows;     // (behind inserts; its slack and its call's min_depth are the entry point's to set)
+    std::optional<VariantsFused> variants;  // (in the window stage's place, which it runs as well)
+    std::optional<IsoFull> full;            // (behind windows or variants)
+    std::optional<IsoPolish> polish;
+    // the variant stage's slots as a window call's outputs: the window rule, the slots' room
+    WindowsOut variant_windows() const { return WindowsOut{windows->rule, variants->call, windows->win, nullptr, nullptr}; }
+};
+
+// what the isoform call behind a block search refuses once its plan is known: a segment has at most as many isoforms as reads
+// (every isoform has min_alt >= 1 reads of its own)
+static int polish_room_ok(ioc_ctx* c, const std::string& who, const IsoPolish& ip, const SinkPlan& p, const std::vector<int64_t>& reads)
 {
-    const AlnCall a{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio};
-    const BlocksOut o{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg};
-    const InsertsOut io{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
-    const WindowsOut wo{{slack, max_win, win_match, win_mismatch, win_gap}, {polish_min_depth, out_wseq, out_wqual, win_cap, out_woff, out_wstats}, out_win, nullptr, nullptr};
-    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !io.ok() || !wo.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
-    SinkPlan p;
-    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
-    IOC_TRY(blocks_room_ok(c, who, o, p));
-    IOC_TRY(inserts_room_ok(c, who, io, p));
-    IOC_TRY(windows_ok(c, who, wo, p, nullptr, nullptr, inserts_bound(p, max_sites)));
-    if (vf) {
-        const WindowsOut vw{wo.rule, vf->call, out_win, nullptr, nullptr};
-        if (!vf->vo.rule.ok() || !vw.ok() || (n_pairs > 0 && (!vf->vo.variant || !vf->vo.reads)) || (n_segs > 0 && !vf->vo.seg)) return IOC_ERR_ARG;
-        IOC_TRY(windows_ok(c, who, vw, p, nullptr, nullptr, inserts_bound(p, max_sites), /*slots a site*/ 2));
-        if (inserts_bound(p, max_sites) > 0 && !vf->vo.var) return IOC_ERR_ARG;
-        vf->call.off[0] = 0;
+    std::vector<int32_t> most(p.segs.size(), 0);
+    int64_t iso_bound = 0;
+    for (size_t g = 0; g < p.segs.size(); ++g) iso_bound += most[g] = int32_t(std::min<int64_t>(ip.max_iso, reads[g]));
+    if (ip.iso_cap < iso_bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": iso_cap " + std::to_string(ip.iso_cap) + " below the bound " + std::to_string(iso_bound));
+    return groups_polish_ok(c, who, ip.call, p.segs, most.data());
+}
+
+// The room of every stage that is on, in the order the entry points have always refused in: blocks, inserts or ends, windows, the
+// variant checks, the full-length isoforms, the isoform call.
+static int blocks_call_room_ok(ioc_ctx* c, const BlocksCall& b, const SinkPlan& p, const std::vector<int64_t>& reads)
+{
+    IOC_TRY(blocks_room_ok(c, b.who, b.o, p));
+    if (b.inserts) IOC_TRY(inserts_room_ok(c, b.who, *b.inserts, p));
+    if (b.ends) IOC_TRY(ends_room_ok(c, b.who, b.ends->o, p, reads));
+    const int64_t sites_most = b.windows ? inserts_bound(p, b.inserts->rule.max_sites) : 0;
+    if (b.windows) IOC_TRY(windows_ok(c, b.who, *b.windows, p, nullptr, nullptr, sites_most));
+    if (b.variants) {
+        const VariantsOut& vo = b.variants->vo;
+        if (!vo.rule.ok() || !b.variant_windows().ok() || (b.a.n_pairs > 0 && (!vo.variant || !vo.reads)) || (b.n_segs > 0 && !vo.seg)) return IOC_ERR_ARG;
+        IOC_TRY(windows_ok(c, b.who, b.variant_windows(), p, nullptr, nullptr, sites_most, /*slots a site*/ 2));
+        if (sites_most > 0 && !vo.var) return IOC_ERR_ARG;
+        b.variants->call.off[0] = 0;  // (here, where it has always been set: a call the next check refuses leaves it written)
     }
-    std::vector<int64_t> n_reads(size_t(n_segs), 0);
-    if (full) {
-        for (int32_t i = 0; i < n_pairs; ++i) ++n_reads[size_t(seg_of_pair[i])];
-        IOC_TRY(iso_full_ok(c, who, *full, p, n_reads, max_sites, max_win));
-    }
-    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
-    block_off[0] = 0, site_off[0] = 0, out_woff[0] = 0;
-    if (full) {
-        full->o.call.off[0] = 0, full->o.splice_off[0] = 0;
-        for (int32_t g = 0; g <= n_segs; ++g) full->iso_off[g] = 0;
-    }
-    if (n_segs == 0) return a.run(c, nullptr);
-    SinkRun r{c};
-    PiledDev d;
-    BlocksDev bd{};
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ full != nullptr, d,
-                   /*project_weights*/ false, /*project_ilen*/ true, /*project_qpos*/ true));
-    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o, &bd));
-    std::vector<uint64_t> pre_full(size_t(n_segs), 0);
-    for (int32_t g = 0; g < n_segs; ++g) pre_full[size_t(g)] = blocks_full_mask(uint32_t(out_seg[g].n_blocks));
-    InsertsPre pre;
-    pre.pre_full = pre_full.data();
-    if (n_pairs > 0) {
-        pre.dev_key = reinterpret_cast<const unsigned long long*>(bd.reads), pre.dev_key_stride = uint32_t(sizeof(ioc_read_blocks) / 8);
-        pre.dev_mask = bd.mask, pre.dev_mask_stride = 1;
-    }
-    IOC_TRY(r.inserts(p, seg_of_pair, nullptr, nullptr, d.base, d.ilen, pre, io));
-    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));  // (before the window call: a_pile is the call stage's to take)
-    WindowsReads reads;
-    std::vector<uint64_t> keys(size_t(n_pairs), 0);
-    for (int32_t i = 0; i < n_pairs; ++i) {
-        reads.off.push_back(c->aln_offs[size_t(pairs[i].query)]), reads.len.push_back(uint32_t(ioc_seq_len(c, pairs[i].query)));
-        keys[size_t(i)] = out_ireads[i].key;
-    }
-    if (vf && site_off[n_segs] == 0) {
-        // no site kept anywhere: key2 is the key and the isoforms counted again are the insert stage's, which are on the host already
-        for (int32_t i = 0; i < n_pairs; ++i) {
-            vf->vo.reads[i] = ioc_read_variants{out_ireads[i].key, out_ireads[i].group, out_ireads[i].how};
-            std::fill(vf->vo.variant + size_t(i) * IOC_INSERTS_MAX, vf->vo.variant + (size_t(i) + 1) * IOC_INSERTS_MAX, uint8_t(IOC_WINVAR_NONE));
-            if (vf->vo.agree) std::fill(vf->vo.agree + size_t(i) * 2 * IOC_INSERTS_MAX, vf->vo.agree + (size_t(i) + 1) * 2 * IOC_INSERTS_MAX, INT32_MIN);
-        }
-        for (int32_t g = 0; g < n_segs; ++g) {
-            const ioc_inserts_seg& z = out_iseg[g];
-            vf->vo.seg[g] = ioc_variants_seg{0, 0, z.n_groups, z.n_reads, z.n_direct, z.n_assigned, z.n_rare, z.n_ambiguous};
-        }
-        IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
-    } else if (vf) {
-        std::vector<uint64_t> pk(size_t(n_pairs), 0), pm(size_t(n_pairs), 0);
-        for (int32_t i = 0; i < n_pairs; ++i) {
-            pk[size_t(i)] = out_reads[i].key;
-            for (uint32_t b = 0; b < uint32_t(out_seg[seg_of_pair[i]].n_blocks); ++b) pm[size_t(i)] |= blocks_state_mask(b, uint32_t(out_reads[i].key >> (2u * b)) & 3u);
-        }
-        const WindowsOut vw{wo.rule, vf->call, out_win, nullptr, nullptr};
-        IOC_TRY(variants_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), n_pairs > 0 ? pk.data() : nullptr,
-                                n_pairs > 0 ? pm.data() : nullptr, n_pairs > 0 ? pre_full.data() : nullptr, vw, vf->vo, &wo.call));
-        if (getenv("IOC_TRACE")) fprintf(stderr, "[ioc]   aligner: window variants: %lld bytes called, %s\n", (long long)vf->call.off[2 * site_off[n_segs]], variants_trace(r.t).c_str());
-    } else
-        IOC_TRY(windows_device(r, p, seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, out_sites, site_off, keys.data(), wo));
-    if (full) {
-        // the combined isoforms the insert stage just made, the first min(n_groups, max_iso) of a segment: their reads, and the key
-        // of the lowest-numbered direct read of each (the records are on the host: they are one of the call's outputs).  With the
-        // variant stage in the same call (ioc_align_pairs_isoforms_full_variants) the isoforms are those it counted again, the keys
-        // key2, and the windows its slots.
-        std::vector<int32_t> n_iso(size_t(n_segs), 0), group(size_t(n_pairs), -1);
-        auto read_of = [&](int32_t i) { return vf ? vf->vo.reads[i] : ioc_read_variants{out_ireads[i].key, out_ireads[i].group, out_ireads[i].how}; };
-        for (int32_t g = 0; g < n_segs; ++g) {
-            const int32_t found = vf ? vf->vo.seg[g].n_groups : out_iseg[g].n_groups;
-            if (found < 0 || found > n_reads[size_t(g)]) return ioc_fail(c, IOC_ERR_HIP, "the insert search returned more isoforms than reads");
-            n_iso[size_t(g)] = std::min(found, full->max_iso);
-            full->iso_off[g + 1] = full->iso_off[g] + n_iso[size_t(g)];
-        }
-        const int64_t G = full->iso_off[n_segs];
-        std::vector<uint64_t> iso_key(size_t(G), 0);
-        std::vector<uint8_t> has_key(size_t(G), 0);
-        for (int32_t i = 0; i < n_pairs; ++i) {
-            const ioc_read_variants rd = read_of(i);
-            const int32_t g = seg_of_pair[i], h = group[size_t(i)] = rd.group;  // (an isoform behind the cut is in no list: group_member_lists)
-            if (h < 0 || h >= n_iso[size_t(g)] || rd.how != IOC_ISO_DIRECT || has_key[size_t(full->iso_off[g] + h)]) continue;
-            iso_key[size_t(full->iso_off[g] + h)] = rd.key2, has_key[size_t(full->iso_off[g] + h)] = 1;
-        }
-        if (G > 0) {
-            const SpliceIn in = vf ? SpliceIn{iso_key.data(), out_win, site_off, vf->call.seq, vf->call.qual, vf->call.off, vf->vo.var, /*by_variant*/ true, /*longer_slot_room*/ true}
-                                   : SpliceIn{iso_key.data(), out_win, site_off, out_wseq, out_wqual, out_woff};
-            int64_t bound = 0;
-            IOC_TRY(splice_ok(c, who, in, full->o, p.segs, n_iso.data(), &bound));
-            GroupPiled gp;
-            IOC_TRY(r.groups_pile(p, seg_of_pair, group.data(), n_iso.data(), Planes{}, Planes{nullptr, nullptr, nullptr, d.base, d.slots}, gp));
-            IOC_TRY(splice_device(r, gp, gp.lists.gseg_off, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), in, full->o, bound));
-        }
-        if (getenv("IOC_TRACE"))
-            fprintf(stderr, "[ioc]   aligner: isoforms full%s: %lld isoforms, %lld bytes called, k_ops_project_ins %.3f ms, k_group_pile over the isoforms %.3f ms, %s\n",
-                    vf ? " by variant" : "", (long long)G, (long long)full->o.call.off[G], r.t.ms_project_ins, r.t.ms_group_pile, splice_trace(r.t).c_str());
-    }
-    if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: blocks inserts seq: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_project_ilen %.3f ms, k_ops_project_qpos %.3f ms, ms_blocks %.3f ms, %s, %s\n",
-                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)site_off[n_segs], (long long)out_woff[site_off[n_segs]],
-                double(r.t.copied) * 1e-6, r.t.ms_copy, r.t.ms_project_ilen, r.t.ms_project_qpos, r.t.ms_blocks, inserts_trace(r.t).c_str(), windows_trace(r.t).c_str());
+    if (b.full) IOC_TRY(iso_full_ok(c, b.who, *b.full, p, reads, b.inserts->rule.max_sites, b.windows->rule.max_win));
+    if (b.polish) IOC_TRY(polish_room_ok(c, b.who, *b.polish, p, reads));
     return IOC_OK;
 }
 
+// blocks -> inserts: the insert kernels over the planes where they lie, with the block stage's keys and masks where that stage
+// left them (its read records and masks stay in a_blocks, the insert stage has a_inserts) and a word per segment from the host
+static int blocks_then_inserts(SinkRun& r, const BlocksCall& b, const SinkPlan& p, const PiledDev& d, const BlocksDev& bd, const std::vector<uint64_t>& pre_full)
+{
+    InsertsPre pre;
+    pre.pre_full = pre_full.data();
+    if (b.a.n_pairs > 0) {
+        static_assert(sizeof(ioc_read_blocks) % 8 == 0 && offsetof(ioc_read_blocks, key) == 0, "a record's first word is its key");
+        pre.dev_key = reinterpret_cast<const unsigned long long*>(bd.reads), pre.dev_key_stride = uint32_t(sizeof(ioc_read_blocks) / 8);
+        pre.dev_mask = bd.mask, pre.dev_mask_stride = 1;
+    }
+    return r.inserts(p, b.seg_of_pair, nullptr, nullptr, d.base, d.ilen, pre, *b.inserts);  // (a_inserts is reserved here, after the walks)
+}
+
+// blocks -> ends: the extents are put together on the host from the block records and the statistics, both of which the call holds
+// there anyway, and uploaded with the stage's tables; pre_group is the block stage's group where that stage left it (a_blocks), the
+// ends stage has a_rends
+static int blocks_then_ends(SinkRun& r, const BlocksCall& b, const SinkPlan& p, const BlocksDev& bd, const ioc_aln_stats* stats)
+{
+    const int32_t n_pairs = b.a.n_pairs;
+    ioc_read_extent* const ext = b.ends->extents;
+    for (int32_t i = 0; i < n_pairs; ++i) ext[i] = ioc_read_extent{b.o.reads[i].first_row, b.o.reads[i].end_row, stats[i].lead_i, stats[i].trail_i};
+    static_assert(sizeof(ioc_read_blocks) % 4 == 0 && offsetof(ioc_read_blocks, group) % 4 == 0, "a record's group is a word of its own");
+    const int32_t* dev_group = n_pairs > 0 ? reinterpret_cast<const int32_t*>(reinterpret_cast<const uint8_t*>(bd.reads) + offsetof(ioc_read_blocks, group)) : nullptr;
+    return r.ends(p, b.seg_of_pair, ext, nullptr, dev_group, uint32_t(sizeof(ioc_read_blocks) / 4), b.ends->o);
+}
+
+// what the variant stage hands back where no site is kept anywhere: key2 is the key and the isoforms counted again are the insert
+// stage's, which are on the host already
+static void variants_of_no_site(const VariantsOut& vo, const InsertsOut& io, int32_t n_pairs, int32_t n_segs)
+{
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        vo.reads[i] = ioc_read_variants{io.reads[i].key, io.reads[i].group, io.reads[i].how};
+        std::fill(vo.variant + size_t(i) * IOC_INSERTS_MAX, vo.variant + (size_t(i) + 1) * IOC_INSERTS_MAX, uint8_t(IOC_WINVAR_NONE));
+        if (vo.agree) std::fill(vo.agree + size_t(i) * 2 * IOC_INSERTS_MAX, vo.agree + (size_t(i) + 1) * 2 * IOC_INSERTS_MAX, INT32_MIN);
+    }
+    for (int32_t g = 0; g < n_segs; ++g) {
+        const ioc_inserts_seg& z = io.seg[g];
+        vo.seg[g] = ioc_variants_seg{0, 0, z.n_groups, z.n_reads, z.n_direct, z.n_assigned, z.n_rare, z.n_ambiguous};
+    }
+}
+
+// inserts -> windows, or -> windows and variants: the window kernels over the planes where they lie; the sites and the keys are on
+// the host when the insert stage returns and travel back with the tables (32 bytes a site, 8 a pair).  With the variant stage on it
+// runs in the window stage's place and returns the window call's outputs as well; the block stage's keys are on the host by then and
+// serve as pre_*, a read's mask being both bits of every block its key has a state at.
+static int inserts_then_windows(SinkRun& r, const BlocksCall& b, const SinkPlan& p, const PiledDev& d, const std::vector<uint64_t>& pre_full)
+{
+    ioc_ctx* const c = r.c;
+    const int32_t n_pairs = b.a.n_pairs, n_segs = b.n_segs;
+    const InsertsOut& io = *b.inserts;
+    WindowsReads reads;
+    std::vector<uint64_t> keys(size_t(n_pairs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        reads.off.push_back(c->aln_offs[size_t(b.a.pairs[i].query)]), reads.len.push_back(uint32_t(ioc_seq_len(c, b.a.pairs[i].query)));
+        keys[size_t(i)] = io.reads[i].key;
+    }
+    if (!b.variants || io.site_off[n_segs] == 0) {
+        if (b.variants) variants_of_no_site(b.variants->vo, io, n_pairs, n_segs);
+        return windows_device(r, p, b.seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, io.sites, io.site_off, keys.data(), *b.windows);
+    }
+    std::vector<uint64_t> pk(size_t(n_pairs), 0), pm(size_t(n_pairs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i)
+        pk[size_t(i)] = b.o.reads[i].key, pm[size_t(i)] = blocks_key_mask(b.o.reads[i].key, uint32_t(b.o.seg[b.seg_of_pair[i]].n_blocks));
+    IOC_TRY(variants_device(r, p, b.seg_of_pair, reads, nullptr, nullptr, d.base, d.qpos, io.sites, io.site_off, keys.data(), n_pairs > 0 ? pk.data() : nullptr,
+                            n_pairs > 0 ? pm.data() : nullptr, n_pairs > 0 ? pre_full.data() : nullptr, b.variant_windows(), b.variants->vo, &b.windows->call));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: window variants: %lld bytes called, %s\n", (long long)b.variants->call.off[2 * io.site_off[n_segs]], variants_trace(r.t).c_str());
+    return IOC_OK;
+}
+
+// windows -> groups pile over the combined isoforms -> splice: the combined isoforms the insert stage just made, the first
+// min(n_groups, max_iso) of a segment — their reads, and the key of the lowest-numbered direct read of each (the records are on the
+// host: they are one of the call's outputs) — piled by k_group_pile and spliced.  With the variant stage in the same call the
+// isoforms are those it counted again, the keys key2, and the windows its slots.
+static int windows_then_full(SinkRun& r, const BlocksCall& b, const SinkPlan& p, const PiledDev& d, const std::vector<int64_t>& n_reads)
+{
+    ioc_ctx* const c = r.c;
+    const size_t n_pairs = size_t(b.a.n_pairs), n_segs = size_t(b.n_segs);
+    const IsoFull& full = *b.full;
+    const InsertsOut& io = *b.inserts;
+    const VariantsFused* const vf = b.variants ? &*b.variants : nullptr;
+    std::vector<int32_t> found(n_segs, 0), group(n_pairs, -1);
+    std::vector<ioc_read_variants> rd(n_pairs);
+    for (size_t g = 0; g < n_segs; ++g) found[g] = vf ? vf->vo.seg[g].n_groups : io.seg[g].n_groups;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        rd[i] = vf ? vf->vo.reads[i] : ioc_read_variants{io.reads[i].key, io.reads[i].group, io.reads[i].how};
+        group[i] = rd[i].group;  // (an isoform behind the cut is in no list: group_member_lists)
+    }
+    IsoCut cut;
+    if (int st = cut.from("insert", n_segs, found.data(), n_reads.data(), full.max_iso, full.iso_off)) return ioc_fail(c, st, cut.msg);
+    const int64_t G = full.iso_off[n_segs];
+    const std::vector<uint64_t> iso_key = iso_keys(n_pairs, b.seg_of_pair, rd.data(), cut.n_iso.data(), full.iso_off, n_segs);
+    if (G > 0) {
+        const WindowsOut& wo = *b.windows;
+        const SpliceIn in = vf ? SpliceIn{iso_key.data(), wo.win, io.site_off, vf->call.seq, vf->call.qual, vf->call.off, vf->vo.var, /*by_variant*/ true, /*longer_slot_room*/ true}
+                               : SpliceIn{iso_key.data(), wo.win, io.site_off, wo.call.seq, wo.call.qual, wo.call.off};
+        int64_t bound = 0;
+        IOC_TRY(splice_ok(c, b.who, in, full.o, p.segs, cut.n_iso.data(), &bound));
+        GroupPiled gp;
+        IOC_TRY(r.groups_pile(p, b.seg_of_pair, group.data(), cut.n_iso.data(), Planes{}, Planes{nullptr, nullptr, nullptr, d.base, d.slots}, gp));
+        IOC_TRY(splice_device(r, gp, gp.lists.gseg_off, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), in, full.o, bound));
+    }
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   aligner: isoforms full%s: %lld isoforms, %lld bytes called, k_ops_project_ins %.3f ms, k_group_pile over the isoforms %.3f ms, %s\n",
+                vf ? " by variant" : "", (long long)G, (long long)full.o.call.off[G], r.t.ms_project_ins, r.t.ms_group_pile, splice_trace(r.t).c_str());
+    return IOC_OK;
+}
+
+// blocks -> groups pile -> call: the consensus of the first min(n_groups, max_iso) isoforms of every segment, each from its direct
+// and assigned reads, with no pair aligned a second time.  The read and segment records are on the host when the block stage
+// returns; they say which group-segments there are and who is in them.  weighted: k_group_pile_weighted stands in k_group_pile's
+// place over the seven weight planes as well, and the call kernels run in their weighted mode.
+static int blocks_then_polish(SinkRun& r, const BlocksCall& b, const SinkPlan& p, const PiledDev& d, const std::vector<int64_t>& n_reads)
+{
+    ioc_ctx* const c = r.c;
+    const size_t n_pairs = size_t(b.a.n_pairs), n_segs = size_t(b.n_segs);
+    const IsoPolish& ip = *b.polish;
+    std::vector<int32_t> found(n_segs, 0), group(n_pairs, -1);
+    for (size_t g = 0; g < n_segs; ++g) found[g] = b.o.seg[g].n_groups;
+    for (size_t i = 0; i < n_pairs; ++i) group[i] = b.o.reads[i].group;  // (an isoform behind the cut is in no list: group_member_lists)
+    IsoCut cut;
+    if (int st = cut.from("block", n_segs, found.data(), n_reads.data(), ip.max_iso, ip.iso_off)) return ioc_fail(c, st, cut.msg);
+    if (ip.iso_off[n_segs] == 0) return IOC_OK;
+    const uint8_t* const frames = static_cast<const uint8_t*>(c->a_pool.p);
+    Planes dev{nullptr, nullptr, nullptr, d.base, d.slots};
+    if (!ip.weighted)
+        return groups_polish_device(r, GroupPolish{ip.call, nullptr, nullptr}, p, frames, uint64_t(c->aln_offs.back()), b.seg_of_pair, group.data(), cut.n_iso.data(), Planes{}, dev);
+    dev.weights = d.weights;
+    return groups_polish_weighted_device(r, ip.call, GroupTablesW{nullptr, nullptr, nullptr}, p, frames, uint64_t(c->aln_offs.back()), b.seg_of_pair, group.data(),
+                                         cut.n_iso.data(), Planes{}, dev);
+}
+
+// the call's own trace line (the variant and the full-length stages have printed theirs): the tags and the `name X ms` fields are
+// what tools/align_*_bench.py read
+static void blocks_call_trace(const BlocksCall& b, const SinkPlan& p, const AlnTally& t)
+{
+    const int32_t n_segs = b.n_segs, n_pairs = b.a.n_pairs;
+    const long long rows = (long long)p.n_rows, kept = (long long)b.o.block_off[n_segs];
+    const double mb = double(t.copied) * 1e-6;
+    const std::string stats = b.out_stats ? ", k_ops_stats " + std::to_string(t.ms_stats) + " ms" : "";
+    if (b.windows)
+        fprintf(stderr, "[ioc]   aligner: blocks inserts seq: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_project_ilen %.3f ms, k_ops_project_qpos %.3f ms, ms_blocks %.3f ms, %s, %s\n",
+                n_segs, rows, n_pairs, kept, (long long)b.inserts->site_off[n_segs], (long long)b.windows->call.off[b.inserts->site_off[n_segs]], mb, t.ms_copy,
+                t.ms_project_ilen, t.ms_project_qpos, t.ms_blocks, inserts_trace(t).c_str(), windows_trace(t).c_str());
+    else if (b.inserts)
+        fprintf(stderr, "[ioc]   aligner: blocks inserts: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld sites kept, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ilen %.3f ms, ms_blocks %.3f ms, %s%s\n",
+                n_segs, rows, n_pairs, kept, (long long)b.inserts->site_off[n_segs], mb, t.ms_copy, t.ms_pileup, t.ms_project, t.ms_project_ilen, t.ms_blocks,
+                inserts_trace(t).c_str(), stats.c_str());
+    else if (b.ends)
+        fprintf(stderr, "[ioc]   aligner: blocks ends: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld end sites kept, %lld variants kept, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms, k_ops_stats %.3f ms, %s\n",
+                n_segs, rows, n_pairs, kept, (long long)b.ends->o.site_off[2 * n_segs], (long long)b.ends->o.var_off[n_segs], mb, t.ms_copy, t.ms_pileup, t.ms_project,
+                t.ms_blocks, t.ms_stats, ends_trace(t).c_str());
+    else if (b.polish && b.polish->weighted)
+        fprintf(stderr, "[ioc]   aligner: blocks polish weighted: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, k_ops_project_weights %.3f ms, ms_blocks %.3f ms, k_group_pile_weighted %.3f ms, k_pile_call<weighted> %.3f ms%s\n",
+                n_segs, rows, n_pairs, kept, (long long)b.polish->iso_off[n_segs], (long long)b.polish->call.off[b.polish->iso_off[n_segs]], mb, t.ms_copy, t.ms_pileup,
+                t.ms_project, t.ms_project_ins, t.ms_project_weights, t.ms_blocks, t.ms_group_pile_weighted, t.ms_call, stats.c_str());
+    else if (b.polish)
+        fprintf(stderr, "[ioc]   aligner: blocks polish: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, ms_blocks %.3f ms, k_group_pile %.3f ms, k_pile_call %.3f ms%s\n",
+                n_segs, rows, n_pairs, kept, (long long)b.polish->iso_off[n_segs], (long long)b.polish->call.off[b.polish->iso_off[n_segs]], mb, t.ms_copy, t.ms_pileup,
+                t.ms_project, t.ms_project_ins, t.ms_blocks, t.ms_group_pile, t.ms_call, stats.c_str());
+    else
+        fprintf(stderr, "[ioc]   aligner: blocks: %d segments, %lld rows, %d pairs, %lld blocks kept, %.3f MB (blocks, records%s%s%s) copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, ms_blocks %.3f ms%s\n",
+                n_segs, rows, n_pairs, kept, mb, b.o.rows ? ", rows" : "", b.out_cols ? ", table" : "", b.out_stats ? ", statistics" : "", t.ms_copy, t.ms_pileup, t.ms_project,
+                t.ms_blocks, stats.c_str());
+}
+
+// The runner.  ioc_align_pairs_alleles' pile, the table of counts with every pair projected beside it — and with the planes the
+// stages that are on read: the length plane for the inserts, the position plane for the windows, the six slot planes for the
+// isoforms that are called or spliced, the seven weight planes for the weighted call —, the block kernels over the base planes
+// where they lie, and the later stages one behind the other.  What comes back is what each stage made, a record per pair and per
+// segment, and the table only where it is asked for.
+static int align_pairs_blocks_call(ioc_ctx* c, const BlocksCall& b)
+{
+    const int32_t n_pairs = b.a.n_pairs, n_segs = b.n_segs;
+    if (!c || n_pairs < 0 || n_segs < 0 || !b.o.ok() || (b.inserts && !b.inserts->ok()) || (b.ends && !b.ends->o.ok()) || (b.windows && !b.windows->ok()) ||
+        (b.variants && !b.variants->call.off) || (b.full && !b.full->ok()) || (b.polish && !b.polish->ok()) ||
+        (n_pairs > 0 && (!b.a.pairs || !b.seg_of_pair || (b.ends && !b.ends->extents))) || (n_segs > 0 && !b.segs))
+        return IOC_ERR_ARG;
+    if (b.polish && b.polish->weighted && !c->aln_qual_set)
+        return ioc_fail(c, IOC_ERR_ARG, b.who + ": no qualities are set for the current pool (ioc_align_set_pool_qual)");
+    SinkPlan p;
+    if (int st = p.from_pool(b.who, c->aln_offs, n_segs, b.segs, n_pairs, b.a.pairs, b.seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
+    const std::vector<int64_t> n_reads = reads_per_seg(size_t(n_segs), size_t(n_pairs), b.seg_of_pair);
+    IOC_TRY(blocks_call_room_ok(c, b, p, n_reads));
+
+    for (int32_t i = 0; i < n_pairs && b.out_stats; ++i) b.out_stats[i] = ioc_aln_stats{};
+    for (int32_t i = 0; i < n_pairs && b.ends; ++i) b.ends->extents[i] = ioc_read_extent{0, 0, 0, 0};
+    b.o.block_off[0] = 0;
+    if (b.inserts) b.inserts->site_off[0] = 0;
+    if (b.ends) b.ends->o.site_off[0] = 0, b.ends->o.var_off[0] = 0;
+    if (b.windows) b.windows->call.off[0] = 0;
+    if (b.full) b.full->o.call.off[0] = 0, b.full->o.splice_off[0] = 0;
+    if (b.polish) b.polish->call.off[0] = 0;
+    for (int32_t g = 0; g <= n_segs && b.full; ++g) b.full->iso_off[g] = 0;
+    for (int32_t g = 0; g <= n_segs && b.polish; ++g) b.polish->iso_off[g] = 0;
+    if (n_segs == 0) return b.a.run(c, nullptr);
+
+    // (the ends stage reads every pair's statistics: the statistics kernel runs for it, into the call's own records where none are asked)
+    std::vector<ioc_aln_stats> own_stats(b.ends && !b.out_stats ? size_t(n_pairs) : 0, ioc_aln_stats{});
+    ioc_aln_stats* const stats = b.ends && !b.out_stats ? own_stats.data() : b.out_stats;
+    SinkRun r{c};
+    PiledDev d;
+    BlocksDev bd{};
+    IOC_TRY(r.pile(b.a, PileKind::counts, stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes,
+                   PileProject{/*ins*/ b.full || b.polish, /*weights*/ b.polish && b.polish->weighted, /*ilen*/ b.inserts.has_value(), /*qpos*/ b.windows.has_value()}, d));
+    IOC_TRY(r.blocks(p, b.seg_of_pair, nullptr, d.base, b.o, &bd));  // (a_blocks is reserved here, after the walks; the records are the host's from here on)
+    const auto cols_out = [&] { return r.copy_out({{b.out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}); };
+    if (b.inserts) {
+        const std::vector<uint64_t> pre_full = blocks_pre_full(size_t(n_segs), b.o.seg);
+        IOC_TRY(blocks_then_inserts(r, b, p, d, bd, pre_full));
+        if (b.windows) {
+            IOC_TRY(cols_out());  // (before the window call: a_pile is the call stage's to take)
+            IOC_TRY(inserts_then_windows(r, b, p, d, pre_full));
+        }
+        if (b.full) IOC_TRY(windows_then_full(r, b, p, d, n_reads));
+    }
+    if (b.ends) IOC_TRY(blocks_then_ends(r, b, p, bd, stats));
+    if (b.polish) IOC_TRY(blocks_then_polish(r, b, p, d, n_reads));
+    if (!b.windows) IOC_TRY(cols_out());
+    if (getenv("IOC_TRACE")) blocks_call_trace(b, p, r.t);
+    return IOC_OK;
+}
+}  // namespace
+
+// The nine entry points: each packs its arguments into the record and runs it.
+// pile -> blocks -> copy-out
+int ioc_align_pairs_blocks(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                           int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
+                           const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
+                           int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off,
+                           ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols)
+{
+    const BlocksCall b{"ioc_align_pairs_blocks", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                       {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    return align_pairs_blocks_call(c, b);
+}
+
+// pile -> blocks -> inserts -> copy-out: the length plane projected beside the two, and the insert kernels behind the block kernels
+int ioc_align_pairs_blocks_inserts(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                   int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                   const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                   int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                   int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                   int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                   int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg)
+{
+    BlocksCall b{"ioc_align_pairs_blocks_inserts", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.inserts = InsertsOut{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
+    return align_pairs_blocks_call(c, b);
+}
+
+// pile -> blocks -> ends -> copy-out: the statistics kernel run over every slice, and the ends kernels behind the block kernels
+int ioc_align_pairs_blocks_ends(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
+                                const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
+                                int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap, int64_t* block_off,
+                                ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t slack, int32_t min_over,
+                                int32_t ends_min_pct, int32_t max_sites, int32_t max_variants, ioc_read_extent* out_extents, ioc_end_row* out_erows,
+                                ioc_end_site* out_sites, int64_t sites_cap, int64_t* site_off, ioc_end_variant* out_variants, int64_t variants_cap,
+                                int64_t* var_off, ioc_read_ends* out_ereads, ioc_ends_seg* out_eseg)
+{
+    BlocksCall b{"ioc_align_pairs_blocks_ends", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.ends = EndsStage{{{slack, min_over, min_depth, min_alt, ends_min_pct, max_sites, max_variants}, out_erows, out_sites, sites_cap, site_off, out_variants, variants_cap,
+                        var_off, out_ereads, out_eseg}, out_extents};
+    return align_pairs_blocks_call(c, b);
+}
+
+// pile -> blocks -> inserts -> windows -> copy-out: the position plane projected beside the other two, and the window kernels behind
+// the insert kernels
 int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
                                        int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
                                        const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
@@ -2586,11 +2674,14 @@ int ioc_align_pairs_blocks_inserts_seq(ioc_ctx* c, int32_t n_pairs, const ioc_al
                                        int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
                                        int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats)
 {
-    return align_pairs_inserts_seq("ioc_align_pairs_blocks_inserts_seq", nullptr, nullptr, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+    BlocksCall b{"ioc_align_pairs_blocks_inserts_seq", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.inserts = InsertsOut{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
+    b.windows = WindowsOut{{slack, max_win, win_match, win_mismatch, win_gap}, {polish_min_depth, out_wseq, out_wqual, win_cap, out_woff, out_wstats}, out_win, nullptr, nullptr};
+    return align_pairs_blocks_call(c, b);
 }
 
-// ... -> inserts -> windows and variants -> copy-out.  ioc_align_pairs_blocks_inserts_seq with the variant kernels behind the window
-// kernels, over the planes where they lie.
+// ... -> inserts -> windows and variants -> copy-out: the variant kernels behind the window kernels, over the planes where they lie
 int ioc_align_pairs_blocks_inserts_variants(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
                                             int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
                                             const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
@@ -2603,29 +2694,34 @@ int ioc_align_pairs_blocks_inserts_variants(ioc_ctx* c, int32_t n_pairs, const i
                                             char* out_vseq, char* out_vqual, int64_t var_cap, int64_t* out_voff, ioc_polish_stats* out_vstats, uint8_t* out_variant,
                                             int32_t* out_agree, ioc_read_variants* out_vreads, ioc_variants_seg* out_vseg)
 {
-    const VariantsFused vf{{{min_agree, min_alt, min_pct}, out_var, out_variant, out_agree, out_vreads, out_vseg}, {polish_min_depth, out_vseq, out_vqual, var_cap, out_voff, out_vstats}};
-    if (!out_voff) return IOC_ERR_ARG;
-    return align_pairs_inserts_seq("ioc_align_pairs_blocks_inserts_variants", nullptr, &vf, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+    BlocksCall b{"ioc_align_pairs_blocks_inserts_variants", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.inserts = InsertsOut{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
+    b.windows = WindowsOut{{slack, max_win, win_match, win_mismatch, win_gap}, {polish_min_depth, out_wseq, out_wqual, win_cap, out_woff, out_wstats}, out_win, nullptr, nullptr};
+    b.variants = VariantsFused{{{min_agree, min_alt, min_pct}, out_var, out_variant, out_agree, out_vreads, out_vseg}, {polish_min_depth, out_vseq, out_vqual, var_cap, out_voff, out_vstats}};
+    return align_pairs_blocks_call(c, b);
 }
 
-// ... -> windows -> groups pile over the combined isoforms -> splice -> copy-out.  ioc_align_pairs_blocks_inserts_seq with the six slot
-// planes projected as well (13 bytes per row and pair), and behind the window kernels k_group_pile over the combined isoforms and
-// the splice kernels.
+// ... -> windows -> groups pile over the combined isoforms -> splice -> copy-out: the six slot planes projected as well (13 bytes per
+// row and pair), and behind the window kernels k_group_pile over the combined isoforms and the splice kernels
 int ioc_align_pairs_isoforms_full(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
-                                       int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
-                                       const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
-                                       int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
-                                       int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
-                                       int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
-                                       int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
-                                       int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
-                                       int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t max_iso, char* out_seq, char* out_qual, int64_t cap,
+                                  int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                  const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                  int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                  int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t min_ins,
+                                  int32_t slack, int32_t max_sites, ioc_insert_row* out_irows, ioc_pile_insert* out_sites, int64_t sites_cap,
+                                  int64_t* site_off, ioc_read_inserts* out_ireads, ioc_inserts_seg* out_iseg, int32_t max_win, int32_t win_match,
+                                  int32_t win_mismatch, int32_t win_gap, int32_t polish_min_depth, ioc_insert_window* out_win, char* out_wseq, char* out_wqual,
+                                  int64_t win_cap, int64_t* out_woff, ioc_polish_stats* out_wstats, int32_t max_iso, char* out_seq, char* out_qual, int64_t cap,
                                   int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats, ioc_splice_site* out_splice, int64_t splice_cap,
                                   int64_t* splice_off, int64_t iso_cap, int64_t* iso_off)
 {
-    const IsoFull full{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
-    if (!full.ok()) return IOC_ERR_ARG;
-    return align_pairs_inserts_seq("ioc_align_pairs_isoforms_full", &full, nullptr, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+    BlocksCall b{"ioc_align_pairs_isoforms_full", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.inserts = InsertsOut{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
+    b.windows = WindowsOut{{slack, max_win, win_match, win_mismatch, win_gap}, {polish_min_depth, out_wseq, out_wqual, win_cap, out_woff, out_wstats}, out_win, nullptr, nullptr};
+    b.full = IsoFull{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
+    return align_pairs_blocks_call(c, b);
 }
 
 // ... -> windows and variants -> groups pile over the isoforms counted again -> splice by variant -> copy-out.  The two calls above in
@@ -2644,80 +2740,17 @@ int ioc_align_pairs_isoforms_full_variants(ioc_ctx* c, int32_t n_pairs, const io
                                            int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish, ioc_splice_stats* out_sstats, ioc_splice_site* out_splice,
                                            int64_t splice_cap, int64_t* splice_off, int64_t iso_cap, int64_t* iso_off)
 {
-    const VariantsFused vf{{{min_agree, min_alt, min_pct}, out_var, out_variant, out_agree, out_vreads, out_vseg}, {polish_min_depth, out_vseq, out_vqual, var_cap, out_voff, out_vstats}};
-    const IsoFull full{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
-    if (!out_voff || !full.ok()) return IOC_ERR_ARG;
-    return align_pairs_inserts_seq("ioc_align_pairs_isoforms_full_variants", &full, &vf, c, n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio, out_stats, n_segs, segs, seg_of_pair, min_gap, min_depth, min_alt, min_pct, min_block, max_blocks, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg, out_cols, min_ins, slack, max_sites, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg, max_win, win_match, win_mismatch, win_gap, polish_min_depth, out_win, out_wseq, out_wqual, win_cap, out_woff, out_wstats);
+    BlocksCall b{"ioc_align_pairs_isoforms_full_variants", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.inserts = InsertsOut{{min_ins, slack, min_depth, min_alt, min_pct, max_sites}, out_irows, out_sites, sites_cap, site_off, out_ireads, out_iseg};
+    b.windows = WindowsOut{{slack, max_win, win_match, win_mismatch, win_gap}, {polish_min_depth, out_wseq, out_wqual, win_cap, out_woff, out_wstats}, out_win, nullptr, nullptr};
+    b.variants = VariantsFused{{{min_agree, min_alt, min_pct}, out_var, out_variant, out_agree, out_vreads, out_vseg}, {polish_min_depth, out_vseq, out_vqual, var_cap, out_voff, out_vstats}};
+    b.full = IsoFull{max_iso, {{polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, out_sstats, out_splice, splice_cap, splice_off}, iso_cap, iso_off};
+    return align_pairs_blocks_call(c, b);
 }
 
-// pile -> blocks -> groups pile -> call -> copy-out.  ioc_align_pairs_blocks with the six slot planes projected beside the two, and
-// behind the block kernels k_group_pile and the call kernels over the planes: the consensus of the first min(n_groups, max_iso)
-// isoforms of every segment, each from its direct and assigned reads, with no pair aligned a second time.  The read and segment
-// records are on the host when the block stage returns; they say which group-segments there are and who is in them.
-// weighted (ioc_align_pairs_blocks_polish_weighted): the pile projects the seven weight planes as well (k_ops_project_weights, under
-// the pool's qualities), k_group_pile_weighted stands in k_group_pile's place and the call kernels run in their weighted mode.
-static int align_pairs_blocks_polish(ioc_ctx* c, const std::string& who, bool weighted, const AlnCall& a, ioc_aln_stats* out_stats, int32_t n_segs,
-                                     const ioc_polish_seg* segs, const int32_t* seg_of_pair, const BlocksOut& o, ioc_pileup_col* out_cols, const IsoPolish& ip)
-{
-    const int32_t n_pairs = a.n_pairs, max_iso = ip.max_iso;
-    const ioc_aln_pair* const pairs = a.pairs;
-    int64_t* const block_off = o.block_off, * const out_off = ip.call.off, * const iso_off = ip.iso_off;
-    ioc_read_blocks* const out_reads = o.reads;
-    ioc_blocks_seg* const out_seg = o.seg;
-    const int64_t iso_cap = ip.iso_cap;
-    if (!c || n_pairs < 0 || n_segs < 0 || !o.ok() || !ip.ok() || (n_pairs > 0 && (!pairs || !seg_of_pair)) || (n_segs > 0 && !segs)) return IOC_ERR_ARG;
-    if (weighted && !c->aln_qual_set) return ioc_fail(c, IOC_ERR_ARG, who + ": no qualities are set for the current pool (ioc_align_set_pool_qual)");
-    SinkPlan p;
-    if (int st = p.from_pool(who, c->aln_offs, n_segs, segs, n_pairs, pairs, seg_of_pair, 0, PLAN_REFUSE_LONG)) return ioc_fail(c, st, p.msg);
-    IOC_TRY(blocks_room_ok(c, who, o, p));
-    // what may be called: a segment has at most as many isoforms as reads (every isoform has min_alt >= 1 reads of its own)
-    std::vector<int64_t> reads(size_t(n_segs), 0);
-    for (int32_t i = 0; i < n_pairs; ++i) ++reads[size_t(seg_of_pair[i])];
-    std::vector<int32_t> most(size_t(n_segs), 0);
-    int64_t iso_bound = 0;
-    for (int32_t g = 0; g < n_segs; ++g) iso_bound += most[size_t(g)] = int32_t(std::min<int64_t>(max_iso, reads[size_t(g)]));
-    if (iso_cap < iso_bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": iso_cap " + std::to_string(iso_cap) + " below the bound " + std::to_string(iso_bound));
-    IOC_TRY(groups_polish_ok(c, who, ip.call, p.segs, most.data()));
-    for (int32_t i = 0; i < n_pairs && out_stats; ++i) out_stats[i] = ioc_aln_stats{};
-    block_off[0] = 0, out_off[0] = 0;
-    for (int32_t g = 0; g <= n_segs; ++g) iso_off[g] = 0;
-    if (n_segs == 0) return a.run(c, nullptr);
-    SinkRun r{c};
-    PiledDev d;
-    IOC_TRY(r.pile(a, PileKind::counts, out_stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes, /*project_ins*/ true, d, /*project_weights*/ weighted));
-    IOC_TRY(r.blocks(p, seg_of_pair, nullptr, d.base, o));  // (a_blocks is reserved here, after the walks; the records are the host's from here on)
-    std::vector<int32_t> n_iso(size_t(n_segs), 0), group(size_t(n_pairs), -1);
-    for (int32_t g = 0; g < n_segs; ++g) {
-        if (out_seg[g].n_groups < 0 || out_seg[g].n_groups > reads[size_t(g)]) return ioc_fail(c, IOC_ERR_HIP, "the block search returned more isoforms than reads");
-        n_iso[size_t(g)] = std::min(out_seg[g].n_groups, max_iso);
-        iso_off[g + 1] = iso_off[g] + n_iso[size_t(g)];
-    }
-    for (int32_t i = 0; i < n_pairs; ++i) group[size_t(i)] = out_reads[i].group;  // (an isoform behind the cut is in no list: group_member_lists)
-    const int64_t G = iso_off[n_segs];
-    if (G > 0 && weighted) {
-        Planes dev{nullptr, nullptr, nullptr, d.base, d.slots};
-        dev.weights = d.weights;
-        IOC_TRY(groups_polish_weighted_device(r, ip.call, GroupTablesW{nullptr, nullptr, nullptr}, p, static_cast<const uint8_t*>(c->a_pool.p),
-                                              uint64_t(c->aln_offs.back()), seg_of_pair, group.data(), n_iso.data(), Planes{}, dev));
-    } else if (G > 0) {
-        const GroupPolish gp{ip.call, nullptr, nullptr};
-        IOC_TRY(groups_polish_device(r, gp, p, static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), seg_of_pair, group.data(), n_iso.data(), Planes{},
-                                     Planes{nullptr, nullptr, nullptr, d.base, d.slots}));
-    }
-    IOC_TRY(r.copy_out({{out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}));
-    if (getenv("IOC_TRACE") && weighted)
-        fprintf(stderr, "[ioc]   aligner: blocks polish weighted: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, k_ops_project_weights %.3f ms, ms_blocks %.3f ms, k_group_pile_weighted %.3f ms, k_pile_call<weighted> %.3f ms%s\n",
-                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)G, (long long)out_off[G], double(r.t.copied) * 1e-6, r.t.ms_copy,
-                r.t.ms_pileup, r.t.ms_project, r.t.ms_project_ins, r.t.ms_project_weights, r.t.ms_blocks, r.t.ms_group_pile_weighted, r.t.ms_call,
-                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
-    else if (getenv("IOC_TRACE"))
-        fprintf(stderr, "[ioc]   aligner: blocks polish: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, ms_blocks %.3f ms, k_group_pile %.3f ms, k_pile_call %.3f ms%s\n",
-                n_segs, (long long)p.n_rows, n_pairs, (long long)block_off[n_segs], (long long)G, (long long)out_off[G], double(r.t.copied) * 1e-6, r.t.ms_copy,
-                r.t.ms_pileup, r.t.ms_project, r.t.ms_project_ins, r.t.ms_blocks, r.t.ms_group_pile, r.t.ms_call,
-                out_stats ? (", k_ops_stats " + std::to_string(r.t.ms_stats) + " ms").c_str() : "");
-    return IOC_OK;
-}
-
+// pile -> blocks -> groups pile -> call -> copy-out: the six slot planes projected beside the two, and behind the block kernels
+// k_group_pile and the call kernels over the planes
 int ioc_align_pairs_blocks_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
                                   int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
                                   const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
@@ -2726,13 +2759,14 @@ int ioc_align_pairs_blocks_polish(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pai
                                   int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_polish_stats* out_polish,
                                   int64_t iso_cap, int64_t* iso_off)
 {
-    return align_pairs_blocks_polish(c, "ioc_align_pairs_blocks_polish", false, AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio},
-                                     out_stats, n_segs, segs, seg_of_pair,
-                                     BlocksOut{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg},
-                                     out_cols, IsoPolish{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off});
+    BlocksCall b{"ioc_align_pairs_blocks_polish", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.polish = IsoPolish{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off};
+    return align_pairs_blocks_call(c, b);
 }
 
-// pile -> blocks -> weighted groups pile -> weighted call -> copy-out: ioc_align_pairs_blocks_polish with every isoform called by weight
+// pile -> blocks -> weighted groups pile -> weighted call -> copy-out: ioc_align_pairs_blocks_polish with every isoform called by
+// weight — the pile projects the seven weight planes as well (k_ops_project_weights, under the pool's qualities)
 int ioc_align_pairs_blocks_polish_weighted(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
                                            int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
                                            const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt,
@@ -2741,10 +2775,10 @@ int ioc_align_pairs_blocks_polish_weighted(ioc_ctx* c, int32_t n_pairs, const io
                                            int32_t max_iso, int32_t polish_min_depth, char* out_seq, char* out_qual, int64_t cap, int64_t* out_off,
                                            ioc_polish_stats* out_polish, int64_t iso_cap, int64_t* iso_off)
 {
-    return align_pairs_blocks_polish(c, "ioc_align_pairs_blocks_polish_weighted", true,
-                                     AlnCall{n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
-                                     BlocksOut{{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg},
-                                     out_cols, IsoPolish{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off});
+    BlocksCall b{"ioc_align_pairs_blocks_polish_weighted", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.polish = IsoPolish{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off, /*weighted*/ true};
+    return align_pairs_blocks_call(c, b);
 }
 
 // upload -> split.  The split of segments whose sites and alleles the caller holds: both are uploaded, and the kernels run as

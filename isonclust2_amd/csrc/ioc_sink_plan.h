@@ -69,6 +69,67 @@ inline GroupMemberLists group_member_lists(size_t n_segs, size_t n_pairs, const 
     return m;
 }
 
+// The host lists of the block family (the calls that pile, search exon blocks and go on from there), each written once.
+// How many pairs every segment has.
+inline std::vector<int64_t> reads_per_seg(size_t n_segs, size_t n_pairs, const int32_t* seg_of_pair)
+{
+    std::vector<int64_t> reads(n_segs, 0);
+    for (size_t i = 0; i < n_pairs; ++i) ++reads[size_t(seg_of_pair[i])];
+    return reads;
+}
+
+// The isoform cut: of the found[g] isoforms a search counted in segment g the first min(found[g], max_iso) are kept, n_iso[g] of
+// them, segment g's in iso_off[g] .. iso_off[g + 1] of the call's isoforms (iso_off[0] is the caller's 0).  A segment has at most as
+// many isoforms as reads, every isoform having min_alt >= 1 reads of its own: a count outside 0 .. reads[g] is refused with
+// IOC_ERR_HIP and msg set, `search` naming the stage that counted ("block", "insert").
+struct IsoCut {
+    std::vector<int32_t> n_iso;
+    std::string msg;
+    int from(const std::string& search, size_t n_segs, const int32_t* found, const int64_t* reads, int32_t max_iso, int64_t* iso_off)
+    {
+        n_iso.assign(n_segs, 0);
+        for (size_t g = 0; g < n_segs; ++g) {
+            if (found[g] < 0 || found[g] > reads[g]) return msg = "the " + search + " search returned more isoforms than reads", IOC_ERR_HIP;
+            n_iso[g] = std::min(found[g], max_iso);
+            iso_off[g + 1] = iso_off[g] + n_iso[g];
+        }
+        return IOC_OK;
+    }
+};
+
+// The key of every kept isoform: that of its lowest-numbered IOC_ISO_DIRECT read, 0 where it has none.  A read in group -1 or in an
+// isoform behind the cut speaks for none (and is in no list: group_member_lists).
+inline std::vector<uint64_t> iso_keys(size_t n_pairs, const int32_t* seg_of_pair, const ioc_read_variants* reads, const int32_t* n_iso, const int64_t* iso_off, size_t n_segs)
+{
+    std::vector<uint64_t> key(n_segs ? size_t(iso_off[n_segs]) : 0, 0);
+    std::vector<uint8_t> has(key.size(), 0);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const int32_t g = seg_of_pair[i], h = reads[i].group;
+        if (h < 0 || h >= n_iso[g] || reads[i].how != IOC_ISO_DIRECT || has[size_t(iso_off[g] + h)]) continue;
+        key[size_t(iso_off[g] + h)] = reads[i].key2, has[size_t(iso_off[g] + h)] = 1;
+    }
+    return key;
+}
+
+// The mask of a key of n states (n <= 32): both bits of every block, or site, at which the state is not IOC_BLOCK_NONE — the
+// blocks_state_mask (ioc_read_blocks.h) of every state, which tools/align_sink_check.cpp holds it against.
+inline uint64_t blocks_key_mask(uint64_t key, uint32_t n)
+{
+    uint64_t mask = 0;
+    for (uint32_t b = 0; b < n; ++b)
+        if (((key >> (2u * b)) & 3u) != uint64_t(IOC_BLOCK_NONE)) mask |= uint64_t(3) << (2u * b);
+    return mask;
+}
+
+// The word of every segment an insert search takes from the block stage: the mask of a complete read of its n_blocks blocks
+// (blocks_full_mask, ioc_read_blocks.h, likewise held against it).
+inline std::vector<uint64_t> blocks_pre_full(size_t n_segs, const ioc_blocks_seg* seg)
+{
+    std::vector<uint64_t> full(n_segs, 0);
+    for (size_t g = 0; g < n_segs; ++g) full[g] = seg[g].n_blocks >= 32 ? ~uint64_t(0) : (uint64_t(1) << (2u * uint32_t(seg[g].n_blocks))) - 1;
+    return full;
+}
+
 // The split's tables (IocSplitDev, ioc_internal.h): segment g has ceil(reads / 64) words a site — T words in all, tile_seg says
 // whose each is — and words x sites words of each bit plane from bit_off[g] on, P in all; seg_of_site: the segment of every site;
 // most: the largest segment's sites.

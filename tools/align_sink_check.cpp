@@ -16,7 +16,12 @@
 //    -1 or in a group their segment lacks, empty groups, segments without groups), the split's tables (0, 1, 64, 65 and 128 members,
 //    a segment without sites between two with), the words of the segments' bit planes with the block search's tables on top of
 //    them (63, 64, 65, 128 and 129 rows), whose slot is whose and the packing of kept slots, the bounds at their edges, and both constructors of SinkPlan with every refusal's
-//    status and message as the entry points have always worded them.
+//    status and message as the entry points have always worded them;
+//  * the block family's host lists, likewise: reads per segment (no segments, segments without pairs), the isoform cut (found 0,
+//    found above max_iso, found above the reads and found negative, both refused with IOC_ERR_HIP and the callers' words), the key
+//    of every kept isoform (group -1, a group behind the cut, two direct reads in one isoform, an isoform without a direct read),
+//    a key's mask against blocks_state_mask state by state (IOC_BLOCK_NONE states among them) and the segments' full masks against
+//    blocks_full_mask (n_blocks 0, 31 and 32).
 //
 // Host code only (the header includes no HIP header); meant for the sanitizers:
 //
@@ -31,6 +36,7 @@
 #include <vector>
 
 #include "ioc_align_sink.h"
+#include "ioc_read_blocks.h"
 #include "ioc_sink_plan.h"
 
 namespace {
@@ -548,6 +554,90 @@ void check_plan_pool()
     }
 }
 
+// The block family's host lists, each against a plain restatement: reads per segment, the isoform cut with both refusals, the keys
+// of the kept isoforms, a key's mask and the segments' full masks.
+void check_block_lists()
+{
+    g_what = "block family lists";
+    // reads per segment: no segments, segments without pairs (1 and 3), pairs out of segment order
+    EXPECT(reads_per_seg(0, 0, nullptr).empty());
+    const int32_t sop[] = {2, 0, 2, 2, 0, 4, 2, 4};
+    const size_t n = 5, np = sizeof sop / sizeof sop[0];
+    const std::vector<int64_t> reads = reads_per_seg(n, np, sop);
+    EXPECT(reads == (std::vector<int64_t>{2, 0, 4, 0, 2}) && reads_per_seg(3, 0, nullptr) == (std::vector<int64_t>{0, 0, 0}));
+
+    // the cut: found 0 (with and without reads), found below, at and above max_iso, found as large as the reads
+    const int32_t max_iso = 2;
+    const int32_t found[] = {2, 0, 4, 0, 1};
+    std::vector<int64_t> iso_off(n + 1, 0);
+    IsoCut cut;
+    EXPECT(cut.from("insert", n, found, reads.data(), max_iso, iso_off.data()) == IOC_OK && cut.msg.empty());
+    int64_t at = 0;
+    for (size_t g = 0; g < n; ++g) {
+        const int32_t want = found[g] < max_iso ? found[g] : max_iso;
+        EXPECT(cut.n_iso[g] == want && iso_off[g] == at);
+        at += want;
+    }
+    EXPECT(iso_off[n] == at && at == 2 + 0 + 2 + 0 + 1);
+    IsoCut none;
+    int64_t zero = 0;
+    EXPECT(none.from("block", 0, nullptr, nullptr, max_iso, &zero) == IOC_OK && none.n_iso.empty() && zero == 0);
+    // the refusals: more isoforms than reads (one more than the two reads; any at all in a segment without reads), fewer than none —
+    // IOC_ERR_HIP, the words the block and the insert callers have always used, the offsets of the segments before it written
+    for (const char* search : {"block", "insert"}) {
+        const std::string text = std::string("the ") + search + " search returned more isoforms than reads";
+        const int32_t over[] = {2, 0, 4, 0, 3}, empty_seg[] = {2, 1, 4, 0, 1}, neg[] = {2, 0, -1, 0, 1};
+        for (const int32_t* bad : {over, empty_seg, neg}) {
+            std::vector<int64_t> off(n + 1, 0);
+            IsoCut c;
+            EXPECT(c.from(search, n, bad, reads.data(), max_iso, off.data()) == IOC_ERR_HIP && c.msg == text);
+            const size_t stop = bad == over ? 4 : bad == empty_seg ? 1 : 2;
+            for (size_t g = 0; g <= n; ++g) EXPECT(off[g] == (g <= stop ? iso_off[g] : 0));
+        }
+    }
+
+    // the keys.  Segment 2 (pairs 0, 2, 3, 6; isoforms 0 and 1 kept, 2 and 3 behind the cut): isoform 0 has two direct reads, pairs 3
+    // and 6 — the lower pair number wins, though its key is the larger; isoform 1 has no direct read, pair 0 being assigned: key 0;
+    // pair 2 is direct in isoform 3, behind the cut.  Segment 0: pair 1 direct in isoform 1, pair 4 rare in group -1, isoform 0 without
+    // reads.  Segment 4: pair 5 direct in isoform 0, pair 7 direct in isoform 1, which the cut leaves the segment without.
+    const ioc_read_variants rd[] = {{0x11, 1, IOC_ISO_ASSIGNED},   {0x22, 1, IOC_ISO_DIRECT},  {0x33, 3, IOC_ISO_DIRECT}, {0x44, 0, IOC_ISO_DIRECT},
+                                    {0x55, -1, IOC_ISO_RARE},      {0x66, 0, IOC_ISO_DIRECT},  {0x04, 0, IOC_ISO_DIRECT}, {0x88, 1, IOC_ISO_DIRECT}};
+    const std::vector<uint64_t> keys = iso_keys(np, sop, rd, cut.n_iso.data(), iso_off.data(), n);
+    std::vector<uint64_t> want(size_t(iso_off[n]), 0);
+    std::vector<int> has(want.size(), 0);
+    for (size_t i = 0; i < np; ++i) {  // (the restatement: in pair order, the first direct read of a kept isoform)
+        const int32_t g = sop[i], h = rd[i].group;
+        if (h < 0 || h >= (found[g] < max_iso ? found[g] : max_iso) || rd[i].how != IOC_ISO_DIRECT) continue;
+        const size_t x = size_t(iso_off[g] + h);
+        if (!has[x]) want[x] = rd[i].key2, has[x] = 1;
+    }
+    EXPECT(keys == want && keys == (std::vector<uint64_t>{0, 0x22, 0x44, 0, 0x66}));
+    {  // an assigned read in front of the direct one does not speak for the isoform
+        const ioc_read_variants two[] = {{0x7, 0, IOC_ISO_ASSIGNED}, {0x9, 0, IOC_ISO_DIRECT}};
+        const int32_t s0[] = {0, 0}, n1[] = {1};
+        const int64_t o1[] = {0, 1};
+        EXPECT(iso_keys(2, s0, two, n1, o1, 1) == std::vector<uint64_t>{0x9});
+    }
+    EXPECT(iso_keys(0, nullptr, nullptr, nullptr, &zero, 0).empty());
+
+    // a key's mask against blocks_state_mask state by state, and the full masks against blocks_full_mask: n_blocks 0, 1, 31, 32
+    const uint64_t some[] = {0, ~uint64_t(0), 0x5555555555555555ull, 0xAAAAAAAAAAAAAAAAull, 0xC000000000000003ull, 0x3ull << 60, 0x1B1B1B1B1B1B1B1Bull, 0xE4E4E4E4E4E4E4E4ull};
+    for (const uint64_t key : some)
+        for (const uint32_t nb : {0u, 1u, 2u, 31u, 32u}) {
+            uint64_t m = 0;
+            for (uint32_t b = 0; b < nb; ++b) m |= blocks_state_mask(b, uint32_t(key >> (2u * b)) & 3u);
+            EXPECT(blocks_key_mask(key, nb) == m && (m & ~blocks_full_mask(nb)) == 0);
+        }
+    EXPECT(blocks_key_mask(~uint64_t(0), 32) == 0 && blocks_key_mask(0, 32) == ~uint64_t(0) && blocks_key_mask(0, 31) == ~uint64_t(0) >> 2);
+    EXPECT(blocks_key_mask(uint64_t(IOC_BLOCK_NONE) << 2 | IOC_BLOCK_SKIP, 3) == 0x33);  // (NONE at block 1 between two states)
+    const ioc_blocks_seg none_seg{};
+    std::vector<ioc_blocks_seg> bs(4, none_seg);
+    bs[1].n_blocks = 31, bs[2].n_blocks = 32, bs[3].n_blocks = 1;
+    const std::vector<uint64_t> full = blocks_pre_full(bs.size(), bs.data());
+    for (size_t g = 0; g < bs.size(); ++g) EXPECT(full[g] == blocks_full_mask(uint32_t(bs[g].n_blocks)));
+    EXPECT(full == (std::vector<uint64_t>{0, ~uint64_t(0) >> 2, ~uint64_t(0), 3}) && blocks_pre_full(0, nullptr).empty());
+}
+
 }  // namespace
 
 int main()
@@ -561,6 +651,7 @@ int main()
     check_bounds();
     check_plan_rlen();
     check_plan_pool();
+    check_block_lists();
     for (const Kind& k : KINDS) {
         Caller c(k);
         g_what = k.name;
