@@ -1797,6 +1797,76 @@ int ioc_align_pairs_blocks_ends(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pai
                                 ioc_end_site* out_sites, int64_t sites_cap, int64_t* site_off, ioc_end_variant* out_variants,
                                 int64_t variants_cap, int64_t* var_off, ioc_read_ends* out_ereads, ioc_ends_seg* out_eseg);
 
+/* ---- Read correction by isoform: every read held against the tables of its own isoform, long insertions kept ----
+ * ioc_host_read_correct holds a read against the pileup of its whole cluster and cannot take a read whose alignment inserts more
+ * than IOC_PILE_INS_SLOTS bases in a row.  Here the tables are those of the read's isoform, and such a run is carried through as
+ * the read has it while the rest of the read is corrected.
+ *
+ * The definition, one read: ioc_host_read_correct's inputs, the read's length plane ilen[rlen + 1] (ioc_host_ops_project_ilen),
+ * its position plane qpos[rlen + 1] (ioc_host_ops_project_qpos) and the read itself, query[qlen].  All integers.
+ *  A row p, 0 <= p <= rlen, with ilen[p] > IOC_PILE_INS_SLOTS is a long row: its insertion step emits query[qpos[p] .. qpos[p] +
+ *  ilen[p]) as the read has it, each byte at quality 0 ('!'), whatever the depth; the slot rule is not applied at that row and it
+ *  adds nothing to n_sub, n_ins_add or n_ins_drop.  Its base, and every other row, is exactly ioc_host_read_correct's: the base
+ *  decision, the run guard (long rows neither start nor end a run) and the qualities.  With no long row the output is
+ *  ioc_host_read_correct's, byte for byte.  n_long_runs counts the long rows, n_long_bases their bytes.
+ *  The pair is unresolved — out_len 0, nothing written, every counter 0 and IOC_ISOC_UNRESOLVED set in flags; not an error of the
+ *  call — where some ilen[p] == 255 (the plane's cap: the length is not known), where a long row has qpos[p] + ilen[p] > qlen (a
+ *  plane that is not this read's) and where a long row stands at a row the read does not span (as ioc_host_read_correct spans).
+ *  The long runs of a read do not overlap, so together they are no longer than the read, which is what the bound on cap counts
+ *  on: planes whose long rows sum to more than qlen are not this read's either, and the pair is unresolved likewise.
+ *  `table` is the batched calls' to set; the definition writes 0. */
+#define IOC_ISOC_UNRESOLVED 1
+typedef struct {
+    int32_t out_len, n_sub, n_fill, n_remove;
+    int32_t n_ins_add, n_ins_drop, n_low, n_guarded;
+    int32_t table;                /* the group-segment held against, or -1 - segment for the cluster's table */
+    int32_t n_long_runs, n_long_bases;
+    int32_t flags;
+} ioc_iso_correct_stats;          /* 48 bytes */
+/* Returns the length written (0 for an unresolved pair); *st (may be NULL) the record.  IOC_ERR_ARG for what ioc_host_read_correct
+ * refuses, a NULL ilen or qpos, qlen < 0 and a NULL query with qlen > 0; IOC_ERR_CAPACITY for cap below rlen + IOC_PILE_INS_SLOTS *
+ * (rlen + 1) + qlen; nothing is written on either. */
+int64_t ioc_host_read_correct_long(const uint8_t* base, const uint8_t* slots, const uint8_t* ilen, const uint32_t* qpos, int32_t rlen,
+                                   const ioc_pileup_col* cols, const ioc_pileup_ins* ins, const char* frame, const char* query,
+                                   int32_t qlen, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run, char* out_seq,
+                                   char* out_qual, int64_t cap, ioc_iso_correct_stats* st);
+/* Every pair of many segments at once on the device, from host planes.  The segments and their frames as for ioc_pileup_call;
+ * n_groups, group and seg_of_pair as for ioc_planes_polish_groups (gseg_off its numbering, G group-segments in all); query[i] a
+ * sequence of the pool that is set, as for ioc_planes_insert_windows; base, slots, ilen (a byte a row) and qpos (a word a row) the
+ * pairs' planes laid out as for ioc_planes_polish.
+ *  Which table: T(g, h) is piled (ioc_host_planes_pile) from the planes of the pairs of segment g in group h, T(g, *) from all
+ *  pairs of segment g whatever their group.  Pair i of segment g is held against T(g, group[i]) where group[i] >= 0 and that group
+ *  has at least min_depth members (table = gseg_off[g] + group[i]), else against T(g, *) (table = -1 - g): what
+ *  ioc_planes_correct does for every read.  Pair i is ioc_host_read_correct_long over that table and the frame of g.
+ * k_group_pile (ioc_group_pile.hip) piles the G + n_segs tables — the extra one per segment lists all of its pairs, and is left
+ * empty where no pair of the segment is held against it —, and
+ * k_iso_correct_count / k_iso_correct_emit (ioc_iso_correct.hip) take a wave per pair, a lane per row: a count pass, a scan, and
+ * a write pass in which the whole wave copies a long run from the pool.  Pair i's bytes stand at out_off[i] .. out_off[i + 1] of
+ * out_seq / out_qual (out_off: n_pairs + 1 entries), its record in out_stats[i] (may be NULL).
+ * IOC_ERR_ARG, with nothing written, for what ioc_planes_correct and ioc_planes_polish_groups refuse and for a query outside the
+ * pool; IOC_ERR_CAPACITY, with nothing written, for cap below the sum over the pairs of (their segment's bound + their query's
+ * length) and for a segment whose bound exceeds 2^31 - 1. */
+int ioc_planes_correct_groups(ioc_ctx* ctx, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off,
+                              const int32_t* n_groups, int32_t n_pairs, const int32_t* seg_of_pair, const int32_t* group,
+                              const int32_t* query, const uint8_t* base, const uint8_t* slots, const uint8_t* ilen,
+                              const uint32_t* qpos, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
+                              char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_iso_correct_stats* out_stats);
+/* ioc_align_pairs_blocks with the correction by isoform behind the block kernels: everything ioc_align_pairs_blocks returns comes
+ * back unchanged, byte for byte; the pile projects the slot, length and position planes as well (12 bytes per row and pair, which
+ * count against the checkpoint arena's budget; a call of ioc_align_pairs_blocks reserves what it always did), and behind the block
+ * kernels ioc_planes_correct_groups' kernels run over the planes where they lie, with ioc_read_blocks.group as the groups and the
+ * block stage's n_groups, under the rule correct_*.  out_seq / out_qual / out_off / out_correct per PAIR as from
+ * ioc_planes_correct_groups.  Every pair is aligned, piled and projected exactly once; the stage's memory is reserved after the
+ * walks.  The refusals of both calls; nothing is written. */
+int ioc_align_pairs_blocks_correct(ioc_ctx* ctx, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch,
+                                   int32_t gap_extend, int32_t* out_score, int64_t* out_windows, double* out_ratio,
+                                   ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs, const int32_t* seg_of_pair,
+                                   int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t min_block,
+                                   int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                   int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols,
+                                   int32_t correct_min_depth, int32_t correct_min_alt, int32_t correct_min_pct, int32_t correct_max_run,
+                                   char* out_seq, char* out_qual, int64_t cap, int64_t* out_off, ioc_iso_correct_stats* out_correct);
+
 #ifdef __cplusplus
 }
 #endif

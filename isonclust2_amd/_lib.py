@@ -109,6 +109,13 @@ class CorrectStats(C.Structure):  # ioc_correct_stats (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("out_len", "n_sub", "n_fill", "n_remove", "n_ins_add", "n_ins_drop", "n_low", "n_guarded")]
 
 
+class IsoCorrectStats(C.Structure):  # ioc_iso_correct_stats (48 bytes)
+    _fields_ = CorrectStats._fields_ + [(n, C.c_int32) for n in ("table", "n_long_runs", "n_long_bases", "flags")]
+
+
+ISOC_UNRESOLVED = 1  # IOC_ISOC_UNRESOLVED
+
+
 class PileSite(C.Structure):  # ioc_pile_site (32 bytes)
     _fields_ = [(n, C.c_int32) for n in ("row", "kind", "major", "minor")] + [(n, C.c_uint32) for n in ("depth", "n_major", "n_minor", "reserved")]
 
@@ -262,6 +269,7 @@ SYMBOLS = [
     "ioc_host_isoform_splice", "ioc_planes_isoforms_full", "ioc_align_pairs_isoforms_full",
     "ioc_host_isoform_splice_variants", "ioc_planes_isoforms_full_variants", "ioc_align_pairs_isoforms_full_variants",
     "ioc_host_ops_extent", "ioc_host_reads_ends", "ioc_reads_ends", "ioc_align_pairs_blocks_ends",
+    "ioc_host_read_correct_long", "ioc_planes_correct_groups", "ioc_align_pairs_blocks_correct",
 ]
 
 _lib = None
@@ -471,6 +479,12 @@ def load():
                                                                                                  C.c_void_p, C.c_void_p]
     L.ioc_align_pairs_blocks_ends.argtypes = L.ioc_align_pairs_blocks.argtypes + [i32, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, i64, pi64,
                                                                                   C.c_void_p, i64, pi64, C.c_void_p, C.c_void_p]
+    L.ioc_host_read_correct_long.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, i32, i32, i32, i32, i32,
+                                             C.c_void_p, C.c_void_p, i64, C.POINTER(IsoCorrectStats)]
+    L.ioc_host_read_correct_long.restype = C.c_int64
+    L.ioc_planes_correct_groups.argtypes = [vp, i32, pi32, C.c_char_p, pi64, pi32, i32, pi32, pi32, pi32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i32, i32, i32, i32,
+                                            C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p]
+    L.ioc_align_pairs_blocks_correct.argtypes = L.ioc_align_pairs_blocks.argtypes + [i32, i32, i32, i32, C.c_void_p, C.c_void_p, i64, pi64, C.c_void_p]
     L.ioc_dist_unique_id.argtypes = [pu8]
     L.ioc_dist_init.argtypes = [vp, pu8, i32, i32]
     L.ioc_dist_shutdown.argtypes = [vp]

@@ -313,6 +313,40 @@ def read_correct(base, slots, cols, ins, frame, min_depth=3, min_alt=3, min_pct=
     return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in CORRECT_STATS_FIELDS}
 
 
+# ioc_iso_correct_stats as a numpy record
+ISO_CORRECT_STATS_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.IsoCorrectStats._fields_])
+ISO_CORRECT_STATS_FIELDS = tuple(n for n, _ in _lib.IsoCorrectStats._fields_)
+
+
+def read_correct_long_bound(rlen, qlen):
+    """what ioc_host_read_correct_long asks of cap: read_correct's bound and the read's length"""
+    return pileup_call_bound(rlen) + int(qlen)
+
+
+def read_correct_long(base, slots, ilen, qpos, cols, ins, frame, query, min_depth=3, min_alt=3, min_pct=25, max_run=10, cap=None):
+    """ioc_host_read_correct_long: read_correct with a long insertion carried through — `ilen` and `qpos` the read's length and
+    position planes as ops_project_ilen and ops_project_qpos give them (len(frame) + 1 entries each), `query` the read (bytes).  A
+    row with ilen > PILE_INS_SLOTS emits query[qpos : qpos + ilen] at quality 0 in place of its slot rule; everything else is
+    read_correct's.  Returns (sequence, qualities, stats): bytes, bytes and a dict of ISO_CORRECT_STATS_FIELDS; an unresolved pair
+    (`flags` & ISOC_UNRESOLVED) comes back empty.  IocError for a rule outside its ranges and for a `cap` (default: the bound)
+    below the bound."""
+    rlen = len(frame)
+    cols, ins = _tables(cols, ins, rlen + 1)
+    base, slots = np.ascontiguousarray(base, np.uint8), np.ascontiguousarray(slots, np.uint8)
+    ilen, qpos = np.ascontiguousarray(ilen, np.uint8), np.ascontiguousarray(qpos, np.uint32)
+    if base.shape != (rlen + 1,) or slots.shape != (_lib.PILE_INS_SLOTS, rlen + 1) or ilen.shape != (rlen + 1,) or qpos.shape != (rlen + 1,):
+        raise ValueError("base, ilen and qpos must hold len(frame) + 1 entries and slots PILE_INS_SLOTS x (len(frame) + 1)")
+    query = bytes(query)
+    cap = read_correct_long_bound(rlen, len(query)) if cap is None else int(cap)
+    seq, qual, st = C.create_string_buffer(max(cap, 1)), C.create_string_buffer(max(cap, 1)), _lib.IsoCorrectStats()
+    n = _lib.load().ioc_host_read_correct_long(base.ctypes.data, slots.ctypes.data, ilen.ctypes.data, qpos.ctypes.data, rlen, cols.ctypes.data, ins.ctypes.data,
+                                               bytes(frame), query, len(query), int(min_depth), int(min_alt), int(min_pct), int(max_run), seq, qual, cap,
+                                               C.byref(st))
+    if n < 0:
+        raise IocError(int(n), "ioc_host_read_correct_long")
+    return seq.raw[:n], qual.raw[:n], {f: int(getattr(st, f)) for f in ISO_CORRECT_STATS_FIELDS}
+
+
 # ioc_block_row, ioc_pile_block, ioc_read_blocks and ioc_blocks_seg as numpy records
 BLOCK_ROW_DTYPE = np.dtype([("depth", np.uint32), ("in_gap", np.uint32)])
 PILE_BLOCK_DTYPE = np.dtype([("first", np.int32), ("end", np.int32)] + [(n, np.uint32) for n in ("n_keep", "n_skip", "n_part", "n_none")] + [("reserved", np.uint32, 2)])
@@ -1023,6 +1057,11 @@ class Context:
         """Where the sequences of the last align_set_pool start (n + 1 offsets; empty pool: [0])."""
         return getattr(self, "_aln_pool_offs", np.zeros(1, np.int64))
 
+    def _pool_len(self, q):
+        """the length of sequence q of the pool that is set (0 for one outside it: the library refuses the call)"""
+        offs = self.align_pool_offsets()
+        return int(offs[q + 1] - offs[q]) if 0 <= int(q) < len(offs) - 1 else 0
+
     def align_set_verdict_threshold(self, thr):
         """ioc_align_set_verdict_threshold: > 0 lets tracebacks stop once ratio >= thr is decided (windows / ratio become bounds)."""
         self._chk(self.L.ioc_align_set_verdict_threshold(self.h, float(thr)))
@@ -1319,6 +1358,41 @@ class Context:
                                             cols.ctypes.data if n_rows else None, ins.ctypes.data if n_rows else None, n, _p(sop, C.c_int32) if n else None,
                                             fb.ctypes.data if P else None, fs.ctypes.data if P else None, int(min_depth), int(min_alt), int(min_pct),
                                             int(max_run), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64), st.ctypes.data if n else None))
+        return ([seq[off[i]:off[i + 1]].tobytes() for i in range(n)], [qual[off[i]:off[i + 1]].tobytes() for i in range(n)], st)
+
+    def planes_correct_groups(self, frames, seg_of_pair, group, n_groups, query, base, slots, ilen, qpos, min_depth=3, min_alt=3, min_pct=25, max_run=10,
+                              cap=None):
+        """ioc_planes_correct_groups: every read of many segments corrected against the tables of its own isoform on the device,
+        from host planes, over the pool that is set — frames, seg_of_pair, group and n_groups as for planes_polish_groups, `query`
+        (the pool sequence that is its read) per pair, base / slots / ilen / qpos lists per pair of what ops_project,
+        ops_project_ins, ops_project_ilen and ops_project_qpos give for that pair.  A pair in a group of at least min_depth
+        members is held against that group's tables, any other against those of all pairs of its segment.  Returns ([sequence per
+        pair], [qualities per pair], stats), stats an array of ISO_CORRECT_STATS_DTYPE; each pair as read_correct_long defines it."""
+        ns, n = len(frames), len(base)
+        rlen = np.array([len(f) for f in frames], np.int32)
+        sop, grp, ng, qy = (np.ascontiguousarray(x, np.int32) for x in (seg_of_pair, group, n_groups, query))
+        if sop.shape != (n,) or grp.shape != (n,) or qy.shape != (n,) or len(slots) != n or len(ilen) != n or len(qpos) != n or ng.shape != (ns,):
+            raise ValueError("seg_of_pair, group, query and the planes must hold one entry per pair and n_groups one per segment")
+        rows = [int(rlen[g]) + 1 if 0 <= g < ns else 0 for g in sop]
+        for i in range(n):
+            if np.shape(base[i]) != (rows[i],) or np.shape(slots[i]) != (_lib.PILE_INS_SLOTS, rows[i]) or np.shape(ilen[i]) != (rows[i],) or \
+                    np.shape(qpos[i]) != (rows[i],):
+                raise ValueError(f"the planes of pair {i} are not those of its segment")
+        P = sum(rows)
+        flat = lambda planes, t: np.ascontiguousarray(np.concatenate([np.zeros(0, t)] + [np.asarray(b, t) for b in planes]))
+        fb, fl, fq = flat(base, np.uint8), flat(ilen, np.uint8), flat(qpos, np.uint32)
+        fs = np.ascontiguousarray(np.concatenate([np.zeros((_lib.PILE_INS_SLOTS, 0), np.uint8)] + [np.asarray(x, np.uint8) for x in slots], axis=1))
+        f_off = np.zeros(ns + 1, np.int64)
+        np.cumsum(rlen, out=f_off[1:])
+        bound = sum(pileup_call_bound(rlen[g]) for g in sop if 0 <= g < ns) + sum(self._pool_len(q) for q in qy)
+        cap = bound if cap is None else int(cap)
+        seq, qual = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        off, st = np.zeros(n + 1, np.int64), np.zeros(n, ISO_CORRECT_STATS_DTYPE)
+        self._chk(self.L.ioc_planes_correct_groups(self.h, ns, _p(rlen, C.c_int32) if ns else None, b"".join(bytes(f) for f in frames), _p(f_off, C.c_int64),
+                                                   _p(ng, C.c_int32) if ns else None, n, _p(sop, C.c_int32) if n else None, _p(grp, C.c_int32) if n else None,
+                                                   _p(qy, C.c_int32) if n else None, fb.ctypes.data if P else None, fs.ctypes.data if P else None,
+                                                   fl.ctypes.data if P else None, fq.ctypes.data if P else None, int(min_depth), int(min_alt), int(min_pct),
+                                                   int(max_run), seq.ctypes.data, qual.ctypes.data, cap, _p(off, C.c_int64), st.ctypes.data if n else None))
         return ([seq[off[i]:off[i + 1]].tobytes() for i in range(n)], [qual[off[i]:off[i + 1]].tobytes() for i in range(n)], st)
 
     def align_pairs_correct(self, pairs, k, segs, seg_of_pair, min_depth=3, min_alt=3, min_pct=25, max_run=10, stats=False, tables=False, cap=None,
@@ -1898,6 +1972,23 @@ class Context:
         self._chk(getattr(self.L, _entry)(*f.lead, int(max_iso), int(polish_min_depth), seq.ctypes.data, qual.ctypes.data, p_cap, _p(off, C.c_int64), pol.ctypes.data,
                                           i_cap, _p(goff, C.c_int64)))
         return self._blocks_family_out(f, **self._groups_out(goff, seq, qual, off, pol))
+
+    def align_pairs_blocks_correct(self, pairs, k, segs, seg_of_pair, correct_min_depth=3, correct_min_alt=3, correct_min_pct=25, correct_max_run=10, stats=False,
+                                   tables=False, rows=True, cap=None, correct_cap=None, match=2, mismatch=-2, gap_extend=1, **rule):
+        """ioc_align_pairs_blocks_correct: align_pairs_blocks with every read corrected against the tables of its own isoform — the
+        block search's group — from the planes where they lie; no read is aligned a second time.  Returns align_pairs_blocks' dict
+        plus `seq` and `qual` (lists of bytes per PAIR) and `correct` (ISO_CORRECT_STATS_DTYPE per pair) as planes_correct_groups
+        returns them.  correct_cap defaults to the bound: every pair's segment bound and its query's length."""
+        f = self._blocks_family(pairs, k, segs, seg_of_pair, rule, stats, tables, rows, cap, match, mismatch, gap_extend)
+        n, ns = f.n, f.ns
+        bound = sum(pileup_call_bound(f.rlen[g]) for g in f.sop if 0 <= g < ns) + sum(self._pool_len(p[0]) for p in pairs)
+        c_cap = bound if correct_cap is None else int(correct_cap)
+        seq, qual = np.zeros(max(c_cap, 1), np.uint8), np.zeros(max(c_cap, 1), np.uint8)
+        off, cor = np.zeros(n + 1, np.int64), np.zeros(n, ISO_CORRECT_STATS_DTYPE)
+        self._chk(self.L.ioc_align_pairs_blocks_correct(*f.lead, int(correct_min_depth), int(correct_min_alt), int(correct_min_pct), int(correct_max_run),
+                                                        seq.ctypes.data, qual.ctypes.data, c_cap, _p(off, C.c_int64), cor.ctypes.data if n else None))
+        return self._blocks_family_out(f, correct=cor, seq=[seq[off[i]:off[i + 1]].tobytes() for i in range(n)],
+                                       qual=[qual[off[i]:off[i + 1]].tobytes() for i in range(n)])
 
     def planes_polish_groups_weighted(self, frames, seg_of_pair, group, n_groups, base, slots, wbase, wslots, min_depth=3, tables=False, cap=None):
         """ioc_planes_polish_groups_weighted: planes_polish_groups with every read's vote counted by its weight — wbase / wslots the

@@ -36,6 +36,7 @@ struct DumpOptions {
     // --isoforms-polish-min-depth / --isoforms-polish-max: positions covered by fewer reads of the isoform keep the representative's base / the isoforms called per cluster
     // --isoforms-polish-weighted: every isoform is called by weight, every read voting with its base qualities
     // --isoforms-inserts: cluster_inserts.tsv, read_inserts.tsv, the exons a cluster's reads carry and its representative lacks, and isoforms over blocks and sites
+    // --isoforms-correct: corrected_reads_isoforms.fq, every read corrected against the tables of its own isoform, long insertions carried through
     // --isoforms-ends: cluster_ends.tsv, cluster_end_variants.tsv, read_ends.tsv, where the reads of a cluster start and stop on its representative, and the variants
     ReportOpts reports;
 };
@@ -65,7 +66,8 @@ void print_dump_help()
          << "                     [--isoforms-inserts-seq [--isoforms-inserts-max-win N] [--isoforms-full [--isoforms-full-max N]]" << endl
          << "                      [--isoforms-inserts-variants [--isoforms-inserts-variants-min-agree N] [--isoforms-full-variants]]]]" << endl
          << "                     [--isoforms-ends [--isoforms-ends-slack N] [--isoforms-ends-min-over N] [--isoforms-ends-min-pct P]" << endl
-         << "                     [--isoforms-ends-max N] [--isoforms-ends-max-variants N]]] final.cer" << endl
+         << "                     [--isoforms-ends-max N] [--isoforms-ends-max-variants N]]" << endl
+         << "                     [--isoforms-correct]] final.cer" << endl
          << "  --read-stats   also write outdir/read_stats.tsv: every read of clusters.tsv aligned against its cluster's representative" << endl
          << "                 as cluster_cons.fq has it (GPU): score, windows, identity, gaps and where the alignment begins and ends" << endl
          << "  --pileup       also write outdir/cluster_pileup.tsv: per position of every representative of cluster_cons.fq, how many reads of" << endl
@@ -190,7 +192,16 @@ void print_dump_help()
          << "  --isoforms-ends-min-over N      a read goes on beyond the representative where it has at least N unaligned bases there (default 20)" << endl
          << "  --isoforms-ends-min-pct P       a site needs at least P percent of the cluster's reads, 1 .. 100 (default 10), and --isoforms-min-alt reads" << endl
          << "  --isoforms-ends-max N           keep the first N start sites and the first N stop sites of a cluster, 1 .. 32 (default 32)" << endl
-         << "  --isoforms-ends-max-variants N  keep the first N variants of a cluster (default 64)" << endl;
+         << "  --isoforms-ends-max-variants N  keep the first N variants of a cluster (default 64)" << endl
+         << "  --isoforms-correct      with --isoforms: also write outdir/corrected_reads_isoforms.fq, from the same alignments: every read of" << endl
+         << "                 clusters.tsv corrected as --correct corrects it, but against the reads of its own isoform (read_isoforms.tsv) where" << endl
+         << "                 that has at least --correct-min-depth reads, else against its whole cluster; an insertion of more than 6 bases in a" << endl
+         << "                 row — an exon the representative lacks — is carried through as the read has it, at quality '!', while the rest of" << endl
+         << "                 the read is corrected.  The header has --correct's counters and isoform=<h or ->, table=<isoform|cluster>," << endl
+         << "                 long_runs= and long_bases=; a read whose insertion cannot be placed is written as it is, with" << endl
+         << "                 uncorrected=unresolved_insertion.  The thresholds are --correct-*'s; --correct itself is not needed and stays" << endl
+         << "                 what it is.  Not offered together with --isoforms-inserts, --isoforms-ends or --isoforms-polish: one fused" << endl
+         << "                 call a run" << endl;
 }
 
 DumpOptions parse_dump_options(int argc, char** argv)
@@ -222,7 +233,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
                                        {"isoforms-ends-min-pct", required_argument, 0, 1043}, {"isoforms-ends-max", required_argument, 0, 1044},
                                        {"isoforms-ends-max-variants", required_argument, 0, 1045}, {"isoforms-inserts-variants", no_argument, 0, 1046},
                                        {"isoforms-inserts-variants-min-agree", required_argument, 0, 1047},
-                                       {"isoforms-full-variants", no_argument, 0, 1048}, {0, 0, 0, 0}};
+                                       {"isoforms-full-variants", no_argument, 0, 1048}, {"isoforms-correct", no_argument, 0, 1049}, {0, 0, 0, 0}};
     DumpOptions d;
     ReportOpts& r = d.reports;
     bool polish = false, split_polish = false, iso_polish = false;
@@ -282,6 +293,7 @@ DumpOptions parse_dump_options(int argc, char** argv)
             case 1046: r.isoforms.variants = true; break;
             case 1047: r.isoforms.variants_min_agree = number("--isoforms-inserts-variants-min-agree", optarg, 1, 100); break;
             case 1048: r.isoforms.full_variants = true; break;
+            case 1049: r.isoforms.correct = true; break;
             case 'h': print_dump_help(); exit(0);
             default: break;
         }
@@ -306,6 +318,10 @@ DumpOptions parse_dump_options(int argc, char** argv)
     if (r.isoforms.ends && !r.isoforms.on) die("--isoforms-ends asks for --isoforms!");
     if (r.isoforms.ends && r.isoforms.inserts) die("--isoforms-ends is not offered together with --isoforms-inserts!");
     if (r.isoforms.ends && iso_polish) die("--isoforms-ends is not offered together with --isoforms-polish!");
+    if (r.isoforms.correct && !r.isoforms.on) die("--isoforms-correct asks for --isoforms!");
+    if (r.isoforms.correct && r.isoforms.inserts) die("--isoforms-correct is not offered together with --isoforms-inserts: one fused call a run!");
+    if (r.isoforms.correct && r.isoforms.ends) die("--isoforms-correct is not offered together with --isoforms-ends: one fused call a run!");
+    if (r.isoforms.correct && iso_polish) die("--isoforms-correct is not offered together with --isoforms-polish: one fused call a run!");
     if (polish) r.polish_min_depth = polish_min_depth;
     if (d.index.empty()) die("Specifying the sorted read index is mandatory!");
     d.batch = argv[optind];
@@ -488,7 +504,8 @@ int main_dump(int argc, char** argv)
                              (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.full ? "cluster_isoforms_full.fq, " : "") +
                              (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.variants ? "cluster_insert_variants.fq, read_insert_variants.tsv, " : "") +
                              (reports.isoforms.on && reports.isoforms.inserts_seq && reports.isoforms.variants && reports.isoforms.full_variants ? "cluster_isoforms_full_variants.fq, " : "") +
-                             (reports.isoforms.on && reports.isoforms.ends ? "cluster_ends.tsv, cluster_end_variants.tsv, read_ends.tsv, " : "");
+                             (reports.isoforms.on && reports.isoforms.ends ? "cluster_ends.tsv, cluster_end_variants.tsv, read_ends.tsv, " : "") +
+                             (reports.isoforms.on && reports.isoforms.correct ? "corrected_reads_isoforms.fq, " : "");
         lap((names.substr(0, names.size() - 2) + " (GPU alignments)").c_str());
     }
     if (VERBOSE) cerr << "Dump complete." << endl;

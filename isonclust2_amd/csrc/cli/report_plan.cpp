@@ -118,6 +118,13 @@ int64_t correct_capacity(const ReportGroup& g)
     return cap;
 }
 
+int64_t iso_correct_capacity(const ReportGroup& g)
+{
+    int64_t cap = correct_capacity(g);
+    for (const ioc_aln_pair& p : g.pairs) cap += g.offs[size_t(p.query) + 1] - g.offs[size_t(p.query)];
+    return cap;
+}
+
 int64_t blocks_capacity(const ReportGroup& g, int max_blocks)
 {
     int64_t cap = 0;
@@ -189,6 +196,24 @@ string corrected_record(const char* id, size_t id_len, unsigned cls, const char*
     string text = "@" + string(id, id_len) + " cluster=" + std::to_string(cls) + " subs=" + std::to_string(k.n_sub) + " fills=" + std::to_string(k.n_fill) +
                   " removes=" + std::to_string(k.n_remove) + " ins_add=" + std::to_string(k.n_ins_add) + " ins_drop=" + std::to_string(k.n_ins_drop) +
                   " low=" + std::to_string(k.n_low) + " guarded=" + std::to_string(k.n_guarded) + (as_it_is ? " uncorrected=long_insertion" : "") + "\n";
+    if (as_it_is) return text.append(read, read_len).append("\n+\n").append(own_qual).append("\n");
+    const size_t lead = std::min(size_t(std::max(a.lead_i, 0)), read_len), trail = std::min(size_t(std::max(a.trail_i, 0)), read_len - lead);
+    text.append(read, lead).append(cseq, clen).append(read + read_len - trail, trail).append("\n+\n");
+    text.append(own_qual, 0, lead).append(cqual, clen).append(own_qual, read_len - trail, trail).append("\n");
+    return text;
+}
+
+string iso_corrected_record(const char* id, size_t id_len, unsigned cls, const char* read, size_t read_len, const char* qual, size_t qual_len,
+                            const ioc_aln_stats& a, const ioc_iso_correct_stats& z, int32_t isoform, const char* cseq, const char* cqual, size_t clen)
+{
+    string own_qual(qual, std::min(qual_len, read_len));
+    own_qual.resize(read_len, '!');
+    const bool as_it_is = (z.flags & IOC_ISOC_UNRESOLVED) != 0;
+    string text = "@" + string(id, id_len) + " cluster=" + std::to_string(cls) + " subs=" + std::to_string(z.n_sub) + " fills=" + std::to_string(z.n_fill) +
+                  " removes=" + std::to_string(z.n_remove) + " ins_add=" + std::to_string(z.n_ins_add) + " ins_drop=" + std::to_string(z.n_ins_drop) +
+                  " low=" + std::to_string(z.n_low) + " guarded=" + std::to_string(z.n_guarded) + " isoform=" + (isoform >= 0 ? std::to_string(isoform) : string("-")) +
+                  " table=" + (z.table >= 0 ? "isoform" : "cluster") + " long_runs=" + std::to_string(z.n_long_runs) + " long_bases=" + std::to_string(z.n_long_bases) +
+                  (as_it_is ? " uncorrected=unresolved_insertion" : "") + "\n";
     if (as_it_is) return text.append(read, read_len).append("\n+\n").append(own_qual).append("\n");
     const size_t lead = std::min(size_t(std::max(a.lead_i, 0)), read_len), trail = std::min(size_t(std::max(a.trail_i, 0)), read_len - lead);
     text.append(read, lead).append(cseq, clen).append(read + read_len - trail, trail).append("\n+\n");

@@ -67,6 +67,10 @@
 // the frame of that record; positions covered by fewer than --isoforms-polish-min-depth reads of the isoform keep the
 // representative's base with quality '!'.  The other report files are what they are without the option.
 //
+// dump --isoforms --isoforms-correct: <outdir>/corrected_reads_isoforms.fq (ioc_align_pairs_blocks_correct: the call of --isoforms with
+// the slot, length and position planes projected beside it and every read corrected against the tables of its own isoform — its
+// cluster's where its isoform has fewer than --correct-min-depth reads or it has none —, a long insertion carried through as the
+// read has it): one record per row of clusters.tsv, in that order (iso_corrected_record, report_plan.cpp).
 // dump --isoforms --isoforms-polish --isoforms-polish-weighted: the same records of cluster_isoforms.fq, names and order, every
 // isoform called by weight (ioc_align_pairs_blocks_polish_weighted: the weight of every vote kept beside the reads' planes, still
 // no read aligned a second time): every read votes with the base qualities of its line as --polish-weighted has them.  Where
@@ -130,6 +134,10 @@ struct GroupResult {
     std::vector<int64_t> coff;
     std::vector<ioc_correct_stats> cstats;
     std::vector<ioc_aln_stats> caln;
+    string icseq, icqual;        // (--isoforms-correct) the same of the correction by isoform
+    std::vector<int64_t> icoff;
+    std::vector<ioc_iso_correct_stats> icstats;
+    std::vector<ioc_aln_stats> icaln;
     std::vector<ioc_pile_block> blocks;  // (--isoforms) segment g's kept blocks at [block_off[g], block_off[g + 1]), its record, and pair x's
     std::vector<int64_t> block_off;
     std::vector<ioc_blocks_seg> blocks_seg;
@@ -180,6 +188,7 @@ struct RowResult {
     // FASTQ and so interleave the clusters, while the groups come cluster by cluster: the records wait here until the last group
     // is done, the whole corrected read set in host memory (the other per-read tables keep a few words a row)
     string corrected;
+    string iso_corrected;            // (--isoforms-correct) the read's record of corrected_reads_isoforms.fq, kept likewise
     ioc_read_blocks iso{};           // (--isoforms) the read's record, and how many blocks its cluster kept
     int32_t iso_blocks = 0;
     ioc_read_inserts ins{};          // (--isoforms-inserts) the read's record, and how many sites its cluster kept
@@ -284,7 +293,10 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
         const int64_t cap = blocks_capacity(g, io.max_blocks);
         r.blocks.assign(size_t(std::max<int64_t>(cap, 1)), ioc_pile_block{}), r.block_off.assign(ns + 1, 0), r.blocks_seg.assign(ns, ioc_blocks_seg{});
         r.read_blocks.assign(np, ioc_read_blocks{});
-        std::vector<ioc_aln_stats> aln(o.stats && !have_first ? np : 0);
+        // (a corrected record needs the free ends of its alignment: the statistics an earlier call of the group left — --correct's, or
+        // those of --read-stats — serve where there are any, and the reduction does not run again for the same pairs)
+        const std::vector<ioc_aln_stats>* const earlier = !io.correct ? nullptr : r.caln.size() == np ? &r.caln : have_first && r.stats.size() == np ? &r.stats : nullptr;
+        std::vector<ioc_aln_stats> aln((o.stats && !have_first) || (io.correct && !earlier) ? np : 0);
         if (o.pileup && !have_first) r.cols.assign(size_t(g.group_rows), ioc_pileup_col{});
         // every call of the block family begins with the same arguments, the context's to the table's: `more` is what its later stages take
         const auto blocks_call = [&](auto entry, const char* what, auto... more) {
@@ -367,6 +379,14 @@ void align_group(ioc_ctx* c, int k, const ReportOpts& o, ReportGroup& g, GroupRe
             blocks_call(ioc_align_pairs_blocks_ends, "exon blocks with the alternative ends", io.ends_slack, io.ends_min_over, io.ends_min_pct, io.ends_max,
                         io.ends_max_variants, r.extents.data(), nullptr, r.end_sites.data(), ecap.sites, r.end_off.data(), r.end_variants.data(), ecap.variants,
                         r.var_off.data(), r.read_ends.data(), r.ends_seg.data());
+        } else if (io.correct) {
+            const CorrectOpt& co = o.correct;
+            const int64_t ccap = iso_correct_capacity(g);
+            r.icseq.assign(size_t(std::max<int64_t>(ccap, 1)), '\0'), r.icqual.assign(size_t(std::max<int64_t>(ccap, 1)), '\0');
+            r.icoff.assign(np + 1, 0), r.icstats.assign(np, ioc_iso_correct_stats{});
+            blocks_call(ioc_align_pairs_blocks_correct, "exon blocks with every read corrected against its isoform", co.min_depth, co.min_alt, co.min_pct, co.max_run,
+                        &r.icseq[0], &r.icqual[0], ccap, r.icoff.data(), r.icstats.data());
+            r.icaln = earlier ? *earlier : aln;
         } else {
             blocks_call(ioc_align_pairs_blocks, "exon blocks");
         }
@@ -404,6 +424,13 @@ void scatter_to_rows(const ReportOpts& o, const ReportRows& rows, const ReportGr
             for (int32_t b = 0; b < row.ins_sites && b < IOC_INSERTS_MAX; ++b) row.variants += ".ABo"[r.variant[x * size_t(IOC_INSERTS_MAX) + size_t(b)] & 3u];
         }
         if (o.isoforms.on && o.isoforms.ends) row.extent = r.extents[x], row.ends = r.read_ends[x];
+        if (o.isoforms.on && o.isoforms.correct) {
+            const ReadStatRow& rd = rows.row(g.pair_row[x]);
+            const size_t q0 = size_t(g.offs[size_t(g.pairs[x].query)]), l0 = size_t(g.qoffs[size_t(g.pair_q[x])]), l1 = size_t(g.qoffs[size_t(g.pair_q[x]) + 1]);
+            row.iso_corrected = iso_corrected_record(rd.id, rd.id_len, rd.cls, g.pool.data() + q0, rd.seq_len, g.quals.data() + l0, l1 - l0, r.icaln[x], r.icstats[x],
+                                                     r.read_blocks[x].group, r.icseq.data() + r.icoff[x], r.icqual.data() + r.icoff[x],
+                                                     size_t(r.icoff[x + 1] - r.icoff[x]));
+        }
         if (o.correct.on) {
             const ReadStatRow& rd = rows.row(g.pair_row[x]);
             const size_t q0 = size_t(g.offs[size_t(g.pairs[x].query)]), l0 = size_t(g.qoffs[size_t(g.pair_q[x])]), l1 = size_t(g.qoffs[size_t(g.pair_q[x]) + 1]);
@@ -810,6 +837,14 @@ void write_corrected_reads(const string& outdir, const std::vector<RowResult>& r
     for (const RowResult& r : res) out.write(r.corrected.data(), std::streamsize(r.corrected.size()));
 }
 
+// corrected_reads_isoforms.fq: one record per row of clusters.tsv, in that order
+void write_iso_corrected_reads(const string& outdir, const std::vector<RowResult>& res)
+{
+    std::ofstream out;
+    create_file(outdir + "/corrected_reads_isoforms.fq", out);
+    for (const RowResult& r : res) out.write(r.iso_corrected.data(), std::streamsize(r.iso_corrected.size()));
+}
+
 void write_read_stats(const string& outdir, const ReportRows& rows, const std::vector<RowResult>& res)
 {
     std::ofstream out;
@@ -852,6 +887,7 @@ void write_read_reports(const Batch& b, const string& outdir, const std::vector<
     if (opts.split.on) write_read_split(outdir, rows, res);
     if (opts.stats) write_read_stats(outdir, rows, res);
     if (opts.correct.on) write_corrected_reads(outdir, res);
+    if (opts.isoforms.on && opts.isoforms.correct) write_iso_corrected_reads(outdir, res);
     if (opts.isoforms.on) write_read_isoforms(outdir, rows, res);
     if (opts.isoforms.on && opts.isoforms.inserts) write_read_inserts(outdir, rows, res);
     if (opts.isoforms.on && opts.isoforms.inserts && opts.isoforms.variants) write_read_insert_variants(outdir, rows, res);

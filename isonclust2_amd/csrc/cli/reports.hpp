@@ -1,4 +1,4 @@
-// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish, --isoforms-polish-weighted, --isoforms-inserts, --isoforms-ends): every read of clusters.tsv
+// The read reports of `dump` (--read-stats, --pileup, --polish, --sites, --split, --split-polish, --correct, --isoforms, --isoforms-polish, --isoforms-polish-weighted, --isoforms-inserts, --isoforms-ends, --isoforms-correct): every read of clusters.tsv
 // aligned against its cluster's representative on the GPU, in groups of whole clusters.  report_plan.cpp cuts the groups and
 // formats records (host only, checked by tools/cli_reports_check.cpp); reports.cpp aligns a group and writes its share of the files.
 #ifndef ISONCLUST2_CLI_REPORTS_HPP
@@ -42,6 +42,8 @@ struct IsoformsOpt {  // --isoforms: the thresholds of ioc_host_planes_blocks
     bool full_variants = false;                      // --isoforms-full-variants: with the variants, the full-length sequence of every isoform counted
                                                      // again, each exon's own variant spliced in (ioc_align_pairs_isoforms_full_variants); full_max applies
     bool ends = false;                               // --isoforms-ends: the alternative ends as well (ioc_align_pairs_blocks_ends), and the
+    bool correct = false;                            // --isoforms-correct: every read corrected against the tables of its own isoform as well
+                                                     // (ioc_align_pairs_blocks_correct), under the thresholds of --correct-*
     int ends_slack = 10, ends_min_over = 20, ends_min_pct = 10, ends_max = 32, ends_max_variants = 64;  // thresholds of ioc_host_reads_ends the block search does not share
 };
 struct ReportOpts {
@@ -122,6 +124,8 @@ SiteCapacity site_capacity(const ReportGroup& g, int max_sites);
 
 // what the correction of every read of a group may return at most: every pair's segment's bound
 int64_t correct_capacity(const ReportGroup& g);
+// ... and the correction by isoform, which carries long insertions through: that and every pair's read
+int64_t iso_correct_capacity(const ReportGroup& g);
 
 // the blocks a block search may keep at most, for all segments of a group: min(max_blocks, the representative's length) each
 int64_t blocks_capacity(const ReportGroup& g, int max_blocks);
@@ -194,6 +198,12 @@ std::string polish_record(const std::string& name, int32_t reads, const ioc_poli
 // would cut it).
 std::string corrected_record(const char* id, size_t id_len, unsigned cls, const char* read, size_t read_len, const char* qual, size_t qual_len,
                              const ioc_aln_stats& a, const ioc_correct_stats& z, const char* cseq, const char* cqual, size_t clen);
+
+// A record of corrected_reads_isoforms.fq: corrected_record's layout with " isoform=<h or -> table=<isoform|cluster> long_runs=
+// long_bases=" behind its counters; a long insertion is carried through, so no read is left as it is for one.  An unresolved pair
+// (IOC_ISOC_UNRESOLVED): the read as it is, " uncorrected=unresolved_insertion" and counters of 0.
+std::string iso_corrected_record(const char* id, size_t id_len, unsigned cls, const char* read, size_t read_len, const char* qual, size_t qual_len,
+                                 const ioc_aln_stats& a, const ioc_iso_correct_stats& z, int32_t isoform, const char* cseq, const char* cqual, size_t clen);
 
 void write_read_reports(const cer::Batch& b, const std::string& outdir, const std::vector<ReadStatRow>& rows, const ReportOpts& opts);
 

@@ -28,6 +28,7 @@
 #include "ioc_sink_plan.h"
 #include "ioc_iso_splice.h"
 #include "ioc_read_correct.h"
+#include "ioc_iso_correct.h"
 #include "ioc_site_split.h"
 
 namespace {
@@ -745,10 +746,29 @@ int ioc_host_alleles_split(const ioc_pile_site* sites, int32_t n_sites, const ui
     return IOC_OK;
 }
 
+// The rows of a read decided and the guard's verdict on each, the runs of "fill" and of "remove" measured end to end: for
+// ioc_host_read_correct and for ioc_host_read_correct_long.
+static void host_read_decide(const uint8_t* base, int32_t rlen, const ioc_pileup_col* cols, const char* frame, const ReadRule& rule, std::vector<uint32_t>& dec,
+                             std::vector<uint8_t>& guarded)
+{
+    const size_t rows = size_t(rlen) + 1;
+    dec.assign(rows, uint32_t(READ_NONE)), guarded.assign(rows, 0);
+    for (int32_t p = 0; p < rlen; ++p) dec[size_t(p)] = read_base_decide(cols[p], base[p], uint8_t(frame[p]), rule);
+    for (size_t a = 0; a < size_t(rlen);) {
+        const uint32_t kind = read_kind(dec[a]);
+        size_t b = a + 1;
+        if (kind == READ_FILL || kind == READ_REMOVE) {
+            while (b < size_t(rlen) && read_kind(dec[b]) == kind) ++b;
+            if (b - a > size_t(rule.max_run)) std::fill(guarded.begin() + int64_t(a), guarded.begin() + int64_t(b), uint8_t(1));
+        }
+        a = b;
+    }
+}
+
 // One read corrected against the tables of its reference (isonclust2_hip.h has the rules; read_base_decide and read_correct_row,
 // ioc_read_correct.h, decide and form a row for this function and for k_read_correct alike).  The plain loop: the rows are decided,
-// the runs of "fill" and of "remove" are measured end to end — k_read_correct and tools/read_correct_check.cpp do the same with
-// read_run_exceeds over masks of 64 rows — and the rows are written.
+// the runs of "fill" and of "remove" are measured end to end (host_read_decide) — k_read_correct and tools/read_correct_check.cpp do
+// the same with read_run_exceeds over masks of 64 rows — and the rows are written.
 int64_t ioc_host_read_correct(const uint8_t* base, const uint8_t* slots, int32_t rlen, const ioc_pileup_col* cols, const ioc_pileup_ins* ins,
                               const char* frame, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run, char* out_seq, char* out_qual,
                               int64_t cap, ioc_correct_stats* st)
@@ -759,18 +779,9 @@ int64_t ioc_host_read_correct(const uint8_t* base, const uint8_t* slots, int32_t
     if (cap < bound) return IOC_ERR_CAPACITY;
     if (!out_seq || !out_qual) return IOC_ERR_ARG;
     const size_t rows = size_t(rlen) + 1;
-    std::vector<uint32_t> dec(rows, uint32_t(READ_NONE));
-    std::vector<uint8_t> guarded(rows, 0);
-    for (int32_t p = 0; p < rlen; ++p) dec[size_t(p)] = read_base_decide(cols[p], base[p], uint8_t(frame[p]), rule);
-    for (size_t a = 0; a < size_t(rlen);) {
-        const uint32_t kind = read_kind(dec[a]);
-        size_t b = a + 1;
-        if (kind == READ_FILL || kind == READ_REMOVE) {
-            while (b < size_t(rlen) && read_kind(dec[b]) == kind) ++b;
-            if (b - a > size_t(max_run)) std::fill(guarded.begin() + int64_t(a), guarded.begin() + int64_t(b), uint8_t(1));
-        }
-        a = b;
-    }
+    std::vector<uint32_t> dec;
+    std::vector<uint8_t> guarded;
+    host_read_decide(base, rlen, cols, frame, rule, dec, guarded);
     ioc_correct_stats s{};
     int64_t at = 0;
     for (int32_t p = 0; p <= rlen; ++p) {
@@ -788,6 +799,60 @@ int64_t ioc_host_read_correct(const uint8_t* base, const uint8_t* slots, int32_t
         s.n_ins_drop += int32_t(row.n_ins_drop), s.n_low += int32_t(row.n_low), s.n_guarded += int32_t(row.n_guarded);
     }
     s.out_len = int32_t(at);
+    if (st) *st = s;
+    return at;
+}
+
+// One read corrected against the tables of its isoform, a long insertion carried through (isonclust2_hip.h has the rules;
+// iso_correct_row, ioc_iso_correct.h, forms a row for this function and for the kernels of ioc_iso_correct.hip alike).  The loop of
+// ioc_host_read_correct, in two passes as the kernels make them: the rows are formed and counted — an unresolved pair ends there —
+// and then written.
+int64_t ioc_host_read_correct_long(const uint8_t* base, const uint8_t* slots, const uint8_t* ilen, const uint32_t* qpos, int32_t rlen, const ioc_pileup_col* cols,
+                                   const ioc_pileup_ins* ins, const char* frame, const char* query, int32_t qlen, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                   int32_t max_run, char* out_seq, char* out_qual, int64_t cap, ioc_iso_correct_stats* st)
+{
+    const ReadRule rule{min_depth, min_alt, min_pct, max_run};
+    if (!rule.ok() || rlen < 0 || qlen < 0 || !base || !slots || !ilen || !qpos || !cols || !ins || (rlen > 0 && !frame) || (qlen > 0 && !query)) return IOC_ERR_ARG;
+    const int64_t bound = int64_t(rlen) + int64_t(IOC_PILE_INS_SLOTS) * (int64_t(rlen) + 1) + qlen;
+    if (cap < bound) return IOC_ERR_CAPACITY;
+    if (!out_seq || !out_qual) return IOC_ERR_ARG;
+    const size_t rows = size_t(rlen) + 1;
+    std::vector<uint32_t> dec;
+    std::vector<uint8_t> guarded;
+    host_read_decide(base, rlen, cols, frame, rule, dec, guarded);
+    std::vector<IsoRowOut> made(rows);
+    ioc_iso_correct_stats s{};
+    bool unresolved = false;
+    int64_t long_bases = 0;
+    for (int32_t p = 0; p <= rlen; ++p) {
+        const int32_t pi = p < rlen ? p : rlen - 1;  // (as ioc_host_read_correct: the row the insertions in front of p are held against)
+        const unsigned long long D = pi >= 0 ? pile_depth(cols[pi]) : 0ull;
+        const bool spans = pi >= 0 && read_covers(base[pi]);
+        unsigned long long own_slots = 0;
+        for (size_t j = 0; j < size_t(IOC_PILE_INS_SLOTS); ++j) own_slots |= (unsigned long long)slots[j * rows + size_t(p)] << (8u * j);
+        const IsoRowOut& m = made[size_t(p)] = iso_correct_row(cols[p], ins[p], D, spans, base[p], own_slots, ilen[p], qpos[p], uint32_t(qlen), dec[size_t(p)],
+                                                              guarded[size_t(p)] != 0, rule);
+        unresolved = unresolved || m.unresolved;
+        s.out_len += int32_t(m.bytes());
+        s.n_sub += int32_t(m.row.n_sub), s.n_fill += int32_t(m.row.n_fill), s.n_remove += int32_t(m.row.n_remove), s.n_ins_add += int32_t(m.row.n_ins_add);
+        s.n_ins_drop += int32_t(m.row.n_ins_drop), s.n_low += int32_t(m.row.n_low), s.n_guarded += int32_t(m.row.n_guarded);
+        s.n_long_runs += m.long_len > 0, long_bases += m.long_len;
+    }
+    s.n_long_bases = int32_t(std::min<int64_t>(long_bases, INT32_MAX));
+    if (unresolved || long_bases > qlen) {  // (runs that together are longer than the read overlap: not this read's planes, and past the bound)
+        s = ioc_iso_correct_stats{};
+        s.flags = IOC_ISOC_UNRESOLVED;
+        if (st) *st = s;
+        return 0;
+    }
+    int64_t at = 0;
+    for (const IsoRowOut& m : made) {
+        for (uint32_t x = 0; x < m.long_len; ++x) out_seq[at] = query[m.long_from + x], out_qual[at++] = '!';
+        for (uint32_t x = 0; x < m.row.n; ++x) {
+            out_seq[at] = char((m.row.seq >> (8u * x)) & 0xFFu);
+            out_qual[at++] = char((m.row.qual >> (8u * x)) & 0xFFu);
+        }
+    }
     if (st) *st = s;
     return at;
 }

@@ -30,6 +30,7 @@ struct AlnTally {
     double ms_project_weights = 0;      // k_ops_project_weights' device time (a pile that projects the weights of the votes as well), and ...
     double ms_group_pile_weighted = 0;  // ... k_group_pile_weighted's (ioc_planes_polish_groups_weighted, ioc_align_pairs_blocks_polish_weighted)
     double ms_correct = 0;      // k_read_correct's device time, both passes and the scan (ioc_planes_correct, ioc_align_pairs_correct)
+    double ms_iso_correct = 0;  // k_iso_correct_count with the scan and k_iso_correct_emit (ioc_planes_correct_groups, ioc_align_pairs_blocks_correct)
     double ms_blocks = 0;       // the eight kernels of ioc_read_blocks.hip, their device time together (ioc_planes_blocks, ioc_align_pairs_blocks)
     double ms_project_ilen = 0; // k_ops_project_ilen's device time (a pile that projects the length plane as well), and ...
     double ms_inserts[8] = {};  // ... the eight kernels of ioc_read_inserts.hip, in the order they run (ioc_planes_inserts, ioc_align_pairs_blocks_inserts)

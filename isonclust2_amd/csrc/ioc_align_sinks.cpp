@@ -3,8 +3,8 @@
 // (ioc_align_gpu.hip).  Host code only: the kernels are behind the iock_* launchers.  An entry point checks its arguments, plans its
 // segments and pairs on the host (SinkPlan, ioc_sink_plan.h) and runs device stages in a row (SinkRun): pile -> sites -> alleles ->
 // [split] -> [group pile -> call] -> copy-out for the alleles family, pile -> call -> copy-out for the polish family, pile -> correct ->
-// copy-out for the read correction, pile -> blocks -> [inserts -> [windows | variants] -> [full]] | [ends] | [polish] -> copy-out for the
-// block family (nine entry points, one record and one runner: BlocksCall, align_pairs_blocks_call), upload -> the same stage for the
+// copy-out for the read correction, pile -> blocks -> [inserts -> [windows | variants] -> [full]] | [ends] | [polish] | [correct] -> copy-out for the
+// block family (ten entry points, one record and one runner: BlocksCall, align_pairs_blocks_call), upload -> the same stage for the
 // calls that bring their own tables.  A stage takes device pointers and says where it left what it made; none calls the next.
 #include <chrono>
 #include <cstdio>
@@ -23,6 +23,7 @@
 #include "ioc_plane_pile.h"
 #include "ioc_read_blocks.h"
 #include "ioc_read_correct.h"
+#include "ioc_iso_correct.h"
 #include "ioc_read_inserts.h"
 #include "ioc_read_ends.h"
 #include "ioc_insert_windows.h"
@@ -72,6 +73,14 @@ struct CorrectOut {  // the rule of a read correction and where it leaves every 
     int64_t cap;
     int64_t* off;
     ioc_correct_stats* stats;
+    bool ok() const { return rule.ok() && off && cap >= 0; }
+};
+struct IsoCorrectOut {  // the rule of a read correction by isoform and where it leaves every pair's bytes (cap: what seq and qual hold each)
+    ReadRule rule;
+    char *seq, *qual;
+    int64_t cap;
+    int64_t* off;
+    ioc_iso_correct_stats* stats;
     bool ok() const { return rule.ok() && off && cap >= 0; }
 };
 struct BlocksOut {  // the rule of a block search and where it leaves what it made (cap: the records `blocks` holds)
@@ -157,6 +166,8 @@ struct GroupPiled {  // group pile (a_gpile): the tables of the 2 n group-segmen
     int64_t n_rows = 0;  // (groups_pile: the rows of its tables, the sum over the group-segments of rlen + 1, ...
     GroupMemberLists lists;           // ... every group's member list and ...
     std::vector<IocGroupWork> work;   // ... the work items, which the uploads read until the call stage has waited for the stream)
+    const IocPileSeg* dev_gsegs = nullptr;            // (groups_pile: the group-segments on the device, and the base and the slot planes it
+    const uint8_t *base = nullptr, *slots = nullptr;  // piled from, where they lay or where it uploaded them: all in a_gpile or the caller's)
 };
 struct IsoPolish {  // the call of the first min(n_groups, max_iso) isoforms of every segment behind a block search (ioc_align_pairs_blocks_polish)
     int32_t max_iso;
@@ -174,6 +185,11 @@ struct Planes {
     // (a weighted groups pile) the seven weight planes: on the device one behind the other, [wbase plane][wslot planes x 6]; the
     // host's as the caller holds them, wbase and wslots
     const uint8_t *weights = nullptr, *wbase = nullptr, *wslots = nullptr;
+};
+// the length and the position plane beside those (the read correction by isoform): the host's, or the device's where a pile projected them
+struct LongPlanes {
+    const uint8_t* ilen = nullptr;
+    const uint32_t* qpos = nullptr;
 };
 struct Out { void* dst; const void* src; size_t bytes; };  // a block that goes back to the host where the caller asked for it (dst NULL: not)
 
@@ -246,7 +262,10 @@ struct SinkRun {
               const uint8_t* alleles, bool on_device, Planes& d);
     int group_pile(const SinkPlan& p, const int32_t* seg_of_pair, const Planes& host, Planes dev, GroupPiled& d);
     int groups_pile(const SinkPlan& p, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& host, Planes dev, GroupPiled& d,
-                    bool weighted = false);
+                    bool weighted = false, int32_t all_below = 0);
+    int iso_correct(const SinkPlan& p, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const uint8_t* d_frames, uint64_t frame_bytes,
+                    const Planes& host, Planes dev, const LongPlanes& host_long, LongPlanes dev_long, const std::vector<uint64_t>& q_off, const std::vector<uint32_t>& q_len,
+                    const IsoCorrectOut& o);
     int correct(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* d_frames, uint64_t frame_bytes, const ioc_pileup_col* d_cols, const ioc_pileup_ins* d_ins,
                 const Planes& host, Planes dev, const CorrectOut& o);
     int blocks(const SinkPlan& p, const int32_t* seg_of_pair, const uint8_t* host_base, const uint8_t* dev_base, const BlocksOut& o, BlocksDev* where = nullptr);
@@ -476,13 +495,18 @@ int SinkRun::group_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const Pl
 // are set to 0 first: k_group_pile is launched over the group-segments that have reads alone.  The stream is not waited for: the
 // call stage behind it does that.  G is at least 1.  weighted: k_group_pile_weighted in its place, over the seven weight planes
 // as well ([weight planes] behind the slot planes where they are uploaded), and the tables are [gcols][gwcols][gwins].
+// all_below > 0 (the read correction by isoform, its min_depth): behind the group-segments stands one more per segment that lists
+// all of its pairs, whatever their group — group-segment gseg_off[n] + g, n more in all, piled by the same launch.  A segment whose
+// pairs are all in groups of at least all_below members holds nobody against that table (iso_uses_group): its list stays empty
+// and nothing is piled for it.
 int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const Planes& ph, Planes pd, GroupPiled& d,
-                         bool weighted)
+                         bool weighted, int32_t all_below)
 {
+    const bool with_all = all_below > 0;
     const std::vector<IocPileSeg>& ds = pn.segs;
     const size_t n = ds.size(), np = pn.plane.size(), P = size_t(pn.plane_bytes);
-    const GroupMemberLists& m = d.lists = group_member_lists(n, np, seg_of_pair, group, n_groups);
-    const size_t G = m.gseg_off[n], M = m.gmembers.size();
+    GroupMemberLists& m = d.lists = group_member_lists(n, np, seg_of_pair, group, n_groups);
+    const size_t G = m.gseg_off[n] + (with_all ? n : 0);
     std::vector<IocPileSeg>& gsegs = d.gsegs = std::vector<IocPileSeg>(G);
     d.n_rows = 0;
     for (size_t g = 0; g < n; ++g)
@@ -490,6 +514,26 @@ int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const i
             gsegs[x] = IocPileSeg{d.n_rows, ds[g].f_off, ds[g].rlen, ds[g].rc};
             d.n_rows += int64_t(ds[g].rlen) + 1;
         }
+    if (with_all) {
+        const MemberLists all = member_lists(n, np, seg_of_pair);
+        std::vector<uint8_t> needed(n, 0);  // some pair of the segment is in no group, or in one of fewer than all_below members
+        for (size_t i = 0; i < np; ++i) {
+            const size_t g = size_t(seg_of_pair[i]);
+            const bool in_group = group[i] >= 0 && group[i] < n_groups[g];
+            const size_t x = in_group ? m.gseg_off[g] + size_t(group[i]) : 0;
+            if (!in_group || !iso_uses_group(group[i], m.gmem_off[x + 1] - m.gmem_off[x], all_below)) needed[g] = 1;
+        }
+        std::vector<uint32_t> off(m.gmem_off), mem(m.gmembers);
+        off.reserve(G + 1), mem.reserve(m.gmembers.size() + np);
+        for (size_t g = 0; g < n; ++g) {
+            for (uint32_t y = all.mem_off[g]; needed[g] && y < all.mem_off[g + 1]; ++y) mem.emplace_back(all.members[y]);
+            off.emplace_back(uint32_t(mem.size()));
+            gsegs[m.gseg_off[n] + g] = IocPileSeg{d.n_rows, ds[g].f_off, ds[g].rlen, ds[g].rc};
+            d.n_rows += int64_t(ds[g].rlen) + 1;
+        }
+        m.gmem_off.swap(off), m.gmembers.swap(mem);
+    }
+    const size_t M = m.gmembers.size();
     std::vector<IocGroupWork>& work = d.work;
     work.clear();
     for (size_t x = 0; x < G; ++x)
@@ -520,6 +564,7 @@ int SinkRun::groups_pile(const SinkPlan& pn, const int32_t* seg_of_pair, const i
     if (!pd.base) pd.base = p + o_base;  // (what does not lie on the device yet was uploaded)
     if (!pd.slots) pd.slots = p + o_slots;
     if (weighted && !pd.weights) pd.weights = p + o_weights;
+    d.dev_gsegs = reinterpret_cast<const IocPileSeg*>(p + o_gseg), d.base = pd.base, d.slots = pd.slots;
     d.cols = reinterpret_cast<ioc_pileup_col*>(p + o_cols), d.ins = reinterpret_cast<ioc_pileup_ins*>(p + o_ins);
     IOC_CHK(c, hipMemsetAsync(p + o_cols, 0, l.size() - o_cols, c->stream));
     if (weighted) {
@@ -585,6 +630,75 @@ int SinkRun::correct(const SinkPlan& pn, const int32_t* seg_of_pair, const uint8
     IOC_CHK(c, hipStreamSynchronize(c->stream));
     settled();
     return copy_out({{o.off, p + o_off, (np + 1) * 8}, {o.stats, p + o_st, np * sizeof(ioc_correct_stats)}, {o.seq, q + o_seq, size_t(total)},
+                     {o.qual, q + o_qual, size_t(total)}});
+}
+
+// groups pile -> iso correct -> copy-out: every pair held against the tables of its own isoform.  k_group_pile piles the G tables of
+// the groups and one more per segment over all of its pairs where some pair is held against it (groups_pile, all_below); the member counts it made its lists from say
+// which table a pair takes (iso_uses_group), a word a pair.  The planes lie on the device (dev, dev_long) or are the host's and
+// uploaded; the reads lie in the pool, pair i's q_len[i] bytes from q_off[i] on.  a_correct holds [table][plane offsets][q_off]
+// [q_len][pair_len][out_off][records] and, uploaded, [length plane][position plane] (the base and slot planes: where groups_pile has them).  The
+// count pass and the scan run first; the one word that comes back then, out_off[pairs], is what a_call is reserved for, and the
+// write pass fills it.
+int SinkRun::iso_correct(const SinkPlan& pn, const int32_t* seg_of_pair, const int32_t* group, const int32_t* n_groups, const uint8_t* d_frames, uint64_t frame_bytes,
+                         const Planes& ph, Planes pd, const LongPlanes& lh, LongPlanes ld, const std::vector<uint64_t>& q_off, const std::vector<uint32_t>& q_len,
+                         const IsoCorrectOut& o)
+{
+    const size_t n = pn.segs.size(), np = pn.plane.size(), P = size_t(pn.plane_bytes);
+    o.off[0] = 0;
+    if (np == 0) return IOC_OK;
+    GroupPiled g;
+    IOC_TRY(groups_pile(pn, seg_of_pair, group, n_groups, ph, pd, g, /*weighted*/ false, /*all_below*/ o.rule.min_depth));
+    const GroupMemberLists& m = g.lists;
+    const uint32_t G = m.gseg_off[n];
+    std::vector<uint32_t> table(np);
+    for (size_t i = 0; i < np; ++i) {
+        const size_t s = size_t(seg_of_pair[i]);
+        const bool in_group = group[i] >= 0 && group[i] < n_groups[s];
+        const uint32_t x = in_group ? m.gseg_off[s] + uint32_t(group[i]) : 0u;
+        table[i] = in_group && iso_uses_group(group[i], m.gmem_off[x + 1] - m.gmem_off[x], o.rule.min_depth) ? x : G + uint32_t(s);
+    }
+    Arena l;
+    const size_t o_tab = l.take(np * 4), o_plane = l.take(np * 8), o_qoff = l.take(np * 8), o_qlen = l.take(np * 4), o_len = l.take(np * 8), o_off = l.take((np + 1) * 8),
+                 o_st = l.take(np * sizeof(ioc_iso_correct_stats)), o_ilen = l.take(ld.ilen ? 0 : P), o_qpos = l.take(ld.qpos ? 0 : 4 * P);
+    IOC_TRY(ioc_reserve(c, c->a_correct, l.size()));
+    uint8_t* p = static_cast<uint8_t*>(c->a_correct.p);
+    auto up = [&](size_t at, const void* src, size_t b) { return b ? hipMemcpyAsync(p + at, src, b, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    IOC_CHK(c, up(o_tab, table.data(), np * 4));
+    IOC_CHK(c, up(o_plane, pn.plane.data(), np * 8));
+    IOC_CHK(c, up(o_qoff, q_off.data(), np * 8));
+    IOC_CHK(c, up(o_qlen, q_len.data(), np * 4));
+    if (!ld.ilen) IOC_CHK(c, up(o_ilen, lh.ilen, P));
+    if (!ld.qpos) IOC_CHK(c, up(o_qpos, lh.qpos, 4 * P));
+    if (!ld.ilen) ld.ilen = p + o_ilen;  // (what does not lie on the device yet was uploaded)
+    if (!ld.qpos) ld.qpos = reinterpret_cast<const uint32_t*>(p + o_qpos);
+    const IocIsoCorrectDev v{g.dev_gsegs, uint32_t(g.gsegs.size()), G, uint32_t(np), reinterpret_cast<const uint32_t*>(p + o_tab),
+                             reinterpret_cast<const uint64_t*>(p + o_plane), g.cols, g.ins, uint64_t(g.n_rows), d_frames, frame_bytes, g.base, g.slots, ld.ilen, ld.qpos,
+                             uint64_t(P), static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.empty() ? 0 : c->aln_offs.back()),
+                             reinterpret_cast<const uint64_t*>(p + o_qoff), reinterpret_cast<const uint32_t*>(p + o_qlen), reinterpret_cast<int64_t*>(p + o_len),
+                             reinterpret_cast<ioc_iso_correct_stats*>(p + o_st)};
+    const ReadRule& k = o.rule;
+    int64_t bound = pn.correct_bound;
+    for (const uint32_t len : q_len) bound += len;
+    IOC_TRY(begin(t.ms_iso_correct));
+    IOC_CHK(c, iock_iso_correct_count(c->stream, v, k.min_depth, k.min_alt, k.min_pct, k.max_run, reinterpret_cast<int64_t*>(p + o_off)));
+    IOC_TRY(end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    settled();
+    int64_t total = 0;
+    IOC_TRY(copy_out({{&total, p + o_off + np * 8, 8}}));
+    if (total < 0 || total > bound) return ioc_fail(c, IOC_ERR_HIP, "the read correction by isoform counted a length outside its bound");
+    Arena w;
+    const size_t o_seq = w.take(size_t(total)), o_qual = w.take(size_t(total));
+    IOC_TRY(ioc_reserve(c, c->a_call, w.size()));
+    uint8_t* q = static_cast<uint8_t*>(c->a_call.p);
+    IOC_TRY(begin(t.ms_iso_correct));
+    IOC_CHK(c, iock_iso_correct_emit(c->stream, v, k.min_depth, k.min_alt, k.min_pct, k.max_run, reinterpret_cast<const int64_t*>(p + o_off), q + o_seq, q + o_qual,
+                                     uint64_t(total)));
+    IOC_TRY(end());
+    IOC_CHK(c, hipStreamSynchronize(c->stream));
+    settled();
+    return copy_out({{o.off, p + o_off, (np + 1) * 8}, {o.stats, p + o_st, np * sizeof(ioc_iso_correct_stats)}, {o.seq, q + o_seq, size_t(total)},
                      {o.qual, q + o_qual, size_t(total)}});
 }
 
@@ -1322,6 +1436,65 @@ int ioc_planes_correct(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const ch
     if (getenv("IOC_TRACE"))
         fprintf(stderr, "[ioc]   planes correct: %d segments, %lld rows, %d pairs, %lld plane bytes, %lld bytes written, k_read_correct %.3f ms\n", n_segs,
                 (long long)p.n_rows, n_pairs, (long long)(7 * p.plane_bytes), (long long)out_off[n_pairs], r.t.ms_correct);
+    return IOC_OK;
+}
+
+// what a read correction by isoform refuses once its plan and its reads are known: IOC_OK, or the status with the message set.
+// The bound is the sum over the pairs of their segment's call bound and their read's length; a pair's own share fits 31 bits (the
+// record's out_len, the kernels' byte counts).
+static int iso_correct_room_ok(ioc_ctx* c, const std::string& who, const IsoCorrectOut& o, const SinkPlan& p, const int32_t* seg_of_pair, const std::vector<uint32_t>& q_len)
+{
+    int64_t bound = p.correct_bound;
+    for (size_t i = 0; i < q_len.size(); ++i) {
+        if (pile_call_most(p.segs[size_t(seg_of_pair[i])].rlen) + int64_t(q_len[i]) > INT32_MAX)
+            return ioc_fail(c, IOC_ERR_CAPACITY, who + ": pair " + std::to_string(i) + " may write more than 2^31 - 1 bytes");
+        bound += q_len[i];
+    }
+    if (o.cap < bound) return ioc_fail(c, IOC_ERR_CAPACITY, who + ": cap " + std::to_string(o.cap) + " below the bound " + std::to_string(bound));
+    return bound > 0 && (!o.seq || !o.qual) ? IOC_ERR_ARG : IOC_OK;
+}
+
+// upload -> groups pile -> iso correct -> copy-out.  The read correction by isoform from planes the caller holds, over the pool that
+// is set: everything is uploaded, and the kernels run as behind ioc_align_pairs_blocks_correct.  The checks of ioc_planes_correct and
+// of ioc_planes_polish_groups, in their order, then the queries.
+int ioc_planes_correct_groups(ioc_ctx* c, int32_t n_segs, const int32_t* rlen, const char* frames, const int64_t* frame_off, const int32_t* n_groups, int32_t n_pairs,
+                              const int32_t* seg_of_pair, const int32_t* group, const int32_t* query, const uint8_t* base, const uint8_t* slots, const uint8_t* ilen,
+                              const uint32_t* qpos, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run, char* out_seq, char* out_qual, int64_t cap,
+                              int64_t* out_off, ioc_iso_correct_stats* out_stats)
+{
+    const std::string who = "ioc_planes_correct_groups";
+    const IsoCorrectOut o{{min_depth, min_alt, min_pct, max_run}, out_seq, out_qual, cap, out_off, out_stats};
+    if (!c || n_segs < 0 || n_pairs < 0 || !o.ok() || (n_segs > 0 && (!rlen || !frame_off || !n_groups)) || (n_pairs > 0 && (!seg_of_pair || !group || !query)))
+        return IOC_ERR_ARG;
+    SinkPlan p;
+    if (int st = p.from_rlen(who, n_segs, rlen, frames, frame_off, n_pairs, seg_of_pair, nullptr, PLAN_REFUSE_CALLED)) return ioc_fail(c, st, p.msg);
+    if (p.plane_bytes > 0 && (!base || !slots || !ilen || !qpos)) return IOC_ERR_ARG;
+    int64_t G = 0;
+    for (int32_t g = 0; g < n_segs; ++g) {
+        if (n_groups[g] < 0) return ioc_fail(c, IOC_ERR_ARG, who + ": segment " + std::to_string(g) + " has a negative number of groups");
+        if ((G += n_groups[g]) + n_segs > INT32_MAX) return ioc_fail(c, IOC_ERR_ARG, who + ": more than 2^31 - 1 group-segments");
+    }
+    std::vector<uint64_t> q_off(size_t(n_pairs), 0);
+    std::vector<uint32_t> q_len(size_t(n_pairs), 0);
+    for (int32_t i = 0; i < n_pairs; ++i) {
+        if (group[i] < -1 || group[i] >= n_groups[seg_of_pair[i]])
+            return ioc_fail(c, IOC_ERR_ARG, who + ": the group of pair " + std::to_string(i) + " is neither -1 nor one of its segment's");
+        if (query[i] < 0 || size_t(query[i]) + 1 >= c->aln_offs.size()) return ioc_fail(c, IOC_ERR_ARG, who + ": the read of pair " + std::to_string(i) + " lies outside the pool");
+        q_off[size_t(i)] = uint64_t(c->aln_offs[size_t(query[i])]), q_len[size_t(i)] = uint32_t(ioc_seq_len(c, query[i]));
+    }
+    IOC_TRY(iso_correct_room_ok(c, who, o, p, seg_of_pair, q_len));
+    out_off[0] = 0;
+    if (n_pairs == 0) return IOC_OK;
+    IOC_CHK(c, hipSetDevice(c->device));
+    DevBuf d_frames;
+    IOC_TRY(ioc_alloc(c, d_frames, size_t(p.frame_bytes)));
+    if (p.frame_bytes > 0) IOC_CHK(c, hipMemcpyAsync(d_frames.p, frames, size_t(p.frame_bytes), hipMemcpyHostToDevice, c->stream));
+    SinkRun r{c};
+    IOC_TRY(r.iso_correct(p, seg_of_pair, group, n_groups, static_cast<const uint8_t*>(d_frames.p), uint64_t(p.frame_bytes), Planes{nullptr, nullptr, nullptr, base, slots},
+                          Planes{}, LongPlanes{ilen, qpos}, LongPlanes{}, q_off, q_len, o));
+    if (getenv("IOC_TRACE"))
+        fprintf(stderr, "[ioc]   planes correct groups: %d segments, %lld group-segments and %d of all pairs, %d pairs, %lld plane bytes, %lld bytes written, k_group_pile %.3f ms, k_iso_correct %.3f ms\n",
+                n_segs, (long long)G, n_segs, n_pairs, (long long)(12 * p.plane_bytes), (long long)out_off[n_pairs], r.t.ms_group_pile, r.t.ms_iso_correct);
     return IOC_OK;
 }
 
@@ -2332,15 +2505,15 @@ int iso_full_ok(ioc_ctx* c, const std::string& who, const IsoFull& f, const Sink
 }
 }  // namespace
 
-// ---- the block family: pile -> blocks -> the stages that are on -> copy-out, one runner behind nine entry points ----
+// ---- the block family: pile -> blocks -> the stages that are on -> copy-out, one runner behind ten entry points ----
 namespace {
 struct EndsStage {  // the ends stage behind the block stage, and where the extents the call puts together for it go (a record a pair)
     EndsOut o;
     ioc_read_extent* extents;
 };
 // What a block-family call is: the alignment, the segments, the block search, and one member per later stage, set where the stage
-// is on.  Nine combinations are reachable, an entry point each: none | inserts | ends | inserts windows | inserts windows variants |
-// inserts windows full | inserts windows variants full | polish | polish weighted.
+// is on.  Ten combinations are reachable, an entry point each: none | inserts | ends | inserts windows | inserts windows variants |
+// inserts windows full | inserts windows variants full | polish | polish weighted | correct.
 struct BlocksCall {
     std::string who;  // the entry point, as its refusals name it
     AlnCall a;
@@ -2356,6 +2529,7 @@ struct BlocksCall {
     std::optional<VariantsFused> variants;  // (in the window stage's place, which it runs as well)
     std::optional<IsoFull> full;            // (behind windows or variants)
     std::optional<IsoPolish> polish;
+    std::optional<IsoCorrectOut> correct;   // (the read correction by isoform, over the block stage's groups)
     // the variant stage's slots as a window call's outputs: the window rule, the slots' room
     WindowsOut variant_windows() const { return WindowsOut{windows->rule, variants->call, windows->win, nullptr, nullptr}; }
 };
@@ -2389,6 +2563,11 @@ static int blocks_call_room_ok(ioc_ctx* c, const BlocksCall& b, const SinkPlan& 
     }
     if (b.full) IOC_TRY(iso_full_ok(c, b.who, *b.full, p, reads, b.inserts->rule.max_sites, b.windows->rule.max_win));
     if (b.polish) IOC_TRY(polish_room_ok(c, b.who, *b.polish, p, reads));
+    if (b.correct) {
+        std::vector<uint32_t> q_len(size_t(b.a.n_pairs), 0);
+        for (int32_t i = 0; i < b.a.n_pairs; ++i) q_len[size_t(i)] = uint32_t(ioc_seq_len(c, b.a.pairs[i].query));
+        IOC_TRY(iso_correct_room_ok(c, b.who, *b.correct, p, b.seg_of_pair, q_len));
+    }
     return IOC_OK;
 }
 
@@ -2525,6 +2704,26 @@ static int blocks_then_polish(SinkRun& r, const BlocksCall& b, const SinkPlan& p
                                          cut.n_iso.data(), Planes{}, dev);
 }
 
+// blocks -> groups pile -> iso correct: every read held against the tables of its own isoform, the block stage's group, with no pair
+// aligned a second time.  The read and segment records are on the host when the block stage returns; the planes — base, slots,
+// length, position — lie where the pile projected them, the reads in the pool.
+static int blocks_then_correct(SinkRun& r, const BlocksCall& b, const SinkPlan& p, const PiledDev& d)
+{
+    ioc_ctx* const c = r.c;
+    const size_t n_pairs = size_t(b.a.n_pairs), n_segs = size_t(b.n_segs);
+    std::vector<int32_t> found(n_segs, 0), group(n_pairs, -1);
+    std::vector<uint64_t> q_off(n_pairs, 0);
+    std::vector<uint32_t> q_len(n_pairs, 0);
+    for (size_t g = 0; g < n_segs; ++g) found[g] = std::max(b.o.seg[g].n_groups, 0);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const int32_t h = b.o.reads[i].group;
+        group[i] = h >= 0 && h < found[size_t(b.seg_of_pair[i])] ? h : -1;
+        q_off[i] = uint64_t(c->aln_offs[size_t(b.a.pairs[i].query)]), q_len[i] = uint32_t(ioc_seq_len(c, b.a.pairs[i].query));
+    }
+    return r.iso_correct(p, b.seg_of_pair, group.data(), found.data(), static_cast<const uint8_t*>(c->a_pool.p), uint64_t(c->aln_offs.back()), Planes{},
+                         Planes{nullptr, nullptr, nullptr, d.base, d.slots}, LongPlanes{}, LongPlanes{d.ilen, d.qpos}, q_off, q_len, *b.correct);
+}
+
 // the call's own trace line (the variant and the full-length stages have printed theirs): the tags and the `name X ms` fields are
 // what tools/align_*_bench.py read
 static void blocks_call_trace(const BlocksCall& b, const SinkPlan& p, const AlnTally& t)
@@ -2549,6 +2748,10 @@ static void blocks_call_trace(const BlocksCall& b, const SinkPlan& p, const AlnT
         fprintf(stderr, "[ioc]   aligner: blocks polish weighted: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, k_ops_project_weights %.3f ms, ms_blocks %.3f ms, k_group_pile_weighted %.3f ms, k_pile_call<weighted> %.3f ms%s\n",
                 n_segs, rows, n_pairs, kept, (long long)b.polish->iso_off[n_segs], (long long)b.polish->call.off[b.polish->iso_off[n_segs]], mb, t.ms_copy, t.ms_pileup,
                 t.ms_project, t.ms_project_ins, t.ms_project_weights, t.ms_blocks, t.ms_group_pile_weighted, t.ms_call, stats.c_str());
+    else if (b.correct)
+        fprintf(stderr, "[ioc]   aligner: blocks correct: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld bytes written, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, k_ops_project_ilen %.3f ms, k_ops_project_qpos %.3f ms, ms_blocks %.3f ms, k_group_pile %.3f ms, k_iso_correct %.3f ms%s\n",
+                n_segs, rows, n_pairs, kept, (long long)b.correct->off[n_pairs], mb, t.ms_copy, t.ms_pileup, t.ms_project, t.ms_project_ins, t.ms_project_ilen, t.ms_project_qpos,
+                t.ms_blocks, t.ms_group_pile, t.ms_iso_correct, stats.c_str());
     else if (b.polish)
         fprintf(stderr, "[ioc]   aligner: blocks polish: %d segments, %lld rows, %d pairs, %lld blocks kept, %lld isoforms called, %lld bytes called, %.3f MB copied from the device in %.3f ms, k_ops_pileup %.3f ms, k_ops_project %.3f ms, k_ops_project_ins %.3f ms, ms_blocks %.3f ms, k_group_pile %.3f ms, k_pile_call %.3f ms%s\n",
                 n_segs, rows, n_pairs, kept, (long long)b.polish->iso_off[n_segs], (long long)b.polish->call.off[b.polish->iso_off[n_segs]], mb, t.ms_copy, t.ms_pileup,
@@ -2568,7 +2771,7 @@ static int align_pairs_blocks_call(ioc_ctx* c, const BlocksCall& b)
 {
     const int32_t n_pairs = b.a.n_pairs, n_segs = b.n_segs;
     if (!c || n_pairs < 0 || n_segs < 0 || !b.o.ok() || (b.inserts && !b.inserts->ok()) || (b.ends && !b.ends->o.ok()) || (b.windows && !b.windows->ok()) ||
-        (b.variants && !b.variants->call.off) || (b.full && !b.full->ok()) || (b.polish && !b.polish->ok()) ||
+        (b.variants && !b.variants->call.off) || (b.full && !b.full->ok()) || (b.polish && !b.polish->ok()) || (b.correct && !b.correct->ok()) ||
         (n_pairs > 0 && (!b.a.pairs || !b.seg_of_pair || (b.ends && !b.ends->extents))) || (n_segs > 0 && !b.segs))
         return IOC_ERR_ARG;
     if (b.polish && b.polish->weighted && !c->aln_qual_set)
@@ -2586,6 +2789,7 @@ static int align_pairs_blocks_call(ioc_ctx* c, const BlocksCall& b)
     if (b.windows) b.windows->call.off[0] = 0;
     if (b.full) b.full->o.call.off[0] = 0, b.full->o.splice_off[0] = 0;
     if (b.polish) b.polish->call.off[0] = 0;
+    if (b.correct) b.correct->off[0] = 0;
     for (int32_t g = 0; g <= n_segs && b.full; ++g) b.full->iso_off[g] = 0;
     for (int32_t g = 0; g <= n_segs && b.polish; ++g) b.polish->iso_off[g] = 0;
     if (n_segs == 0) return b.a.run(c, nullptr);
@@ -2597,7 +2801,9 @@ static int align_pairs_blocks_call(ioc_ctx* c, const BlocksCall& b)
     PiledDev d;
     BlocksDev bd{};
     IOC_TRY(r.pile(b.a, PileKind::counts, stats, p.row_base.data(), p.n_rows, p.plane.data(), p.plane_bytes,
-                   PileProject{/*ins*/ b.full || b.polish, /*weights*/ b.polish && b.polish->weighted, /*ilen*/ b.inserts.has_value(), /*qpos*/ b.windows.has_value()}, d));
+                   PileProject{/*ins*/ b.full || b.polish || b.correct, /*weights*/ b.polish && b.polish->weighted, /*ilen*/ b.inserts || b.correct,
+                               /*qpos*/ b.windows || b.correct},
+                   d));
     IOC_TRY(r.blocks(p, b.seg_of_pair, nullptr, d.base, b.o, &bd));  // (a_blocks is reserved here, after the walks; the records are the host's from here on)
     const auto cols_out = [&] { return r.copy_out({{b.out_cols, d.cols, size_t(p.n_rows) * sizeof(ioc_pileup_col)}}); };
     if (b.inserts) {
@@ -2611,13 +2817,14 @@ static int align_pairs_blocks_call(ioc_ctx* c, const BlocksCall& b)
     }
     if (b.ends) IOC_TRY(blocks_then_ends(r, b, p, bd, stats));
     if (b.polish) IOC_TRY(blocks_then_polish(r, b, p, d, n_reads));
+    if (b.correct) IOC_TRY(blocks_then_correct(r, b, p, d));
     if (!b.windows) IOC_TRY(cols_out());
     if (getenv("IOC_TRACE")) blocks_call_trace(b, p, r.t);
     return IOC_OK;
 }
 }  // namespace
 
-// The nine entry points: each packs its arguments into the record and runs it.
+// The ten entry points: each packs its arguments into the record and runs it.
 // pile -> blocks -> copy-out
 int ioc_align_pairs_blocks(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
                            int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs, const ioc_polish_seg* segs,
@@ -2778,6 +2985,22 @@ int ioc_align_pairs_blocks_polish_weighted(ioc_ctx* c, int32_t n_pairs, const io
     BlocksCall b{"ioc_align_pairs_blocks_polish_weighted", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
                  {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
     b.polish = IsoPolish{max_iso, {polish_min_depth, out_seq, out_qual, cap, out_off, out_polish}, iso_cap, iso_off, /*weighted*/ true};
+    return align_pairs_blocks_call(c, b);
+}
+
+// pile -> blocks -> groups pile -> iso correct -> copy-out: the slot, length and position planes projected beside the base plane, and
+// every read corrected against the tables of its own isoform behind the block kernels
+int ioc_align_pairs_blocks_correct(ioc_ctx* c, int32_t n_pairs, const ioc_aln_pair* pairs, int32_t k, int32_t match, int32_t mismatch, int32_t gap_extend,
+                                   int32_t* out_score, int64_t* out_windows, double* out_ratio, ioc_aln_stats* out_stats, int32_t n_segs,
+                                   const ioc_polish_seg* segs, const int32_t* seg_of_pair, int32_t min_gap, int32_t min_depth, int32_t min_alt, int32_t min_pct,
+                                   int32_t min_block, int32_t max_blocks, ioc_block_row* out_rows, ioc_pile_block* out_blocks, int64_t blocks_cap,
+                                   int64_t* block_off, ioc_read_blocks* out_reads, ioc_blocks_seg* out_seg, ioc_pileup_col* out_cols, int32_t correct_min_depth,
+                                   int32_t correct_min_alt, int32_t correct_min_pct, int32_t correct_max_run, char* out_seq, char* out_qual, int64_t cap,
+                                   int64_t* out_off, ioc_iso_correct_stats* out_correct)
+{
+    BlocksCall b{"ioc_align_pairs_blocks_correct", {n_pairs, pairs, k, match, mismatch, gap_extend, out_score, out_windows, out_ratio}, out_stats, n_segs, segs, seg_of_pair,
+                 {{min_gap, min_depth, min_alt, min_pct, min_block, max_blocks}, out_rows, out_blocks, blocks_cap, block_off, out_reads, out_seg}, out_cols};
+    b.correct = IsoCorrectOut{{correct_min_depth, correct_min_alt, correct_min_pct, correct_max_run}, out_seq, out_qual, cap, out_off, out_correct};
     return align_pairs_blocks_call(c, b);
 }
 

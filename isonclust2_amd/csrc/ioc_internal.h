@@ -473,6 +473,38 @@ hipError_t iock_read_correct_count(hipStream_t st, const IocReadCorrectDev& v, i
 hipError_t iock_read_correct_emit(hipStream_t st, const IocReadCorrectDev& v, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
                                   const int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);
 
+// ioc_iso_correct.hip: every pair's read corrected against the tables of its own isoform, long insertions carried through
+// (ioc_host_read_correct_long per pair).  Everything is a device pointer.  The tables are those of n_tables group-segments (gsegs:
+// their rows, and the frame of their segment), the first n_group_tables a group's and the rest a whole segment's; pair i is held
+// against group-segment table[i], has its rows from byte plane[i] on of the base plane, the six slot planes and the length plane
+// (plane_bytes each) and from word plane[i] on of the position plane, and its read q_len[i] bytes from q_off[i] on of the pool.
+// pair_len / stats: n_pairs words of scratch and the records.  The count pass and the scan first; the write pass once out_seq /
+// out_qual hold out_off[n_pairs] bytes.
+struct IocIsoCorrectDev {
+    const IocPileSeg* gsegs;
+    uint32_t n_tables, n_group_tables, n_pairs;
+    const uint32_t* table;
+    const uint64_t* plane;
+    const ioc_pileup_col* cols;
+    const ioc_pileup_ins* ins;
+    uint64_t n_rows;
+    const uint8_t* frames;
+    uint64_t frame_bytes;
+    const uint8_t *base_planes, *slot_planes, *ilen_planes;
+    const uint32_t* qpos_planes;
+    uint64_t plane_bytes;
+    const uint8_t* pool;
+    uint64_t pool_bytes;
+    const uint64_t* q_off;
+    const uint32_t* q_len;
+    int64_t* pair_len;
+    ioc_iso_correct_stats* stats;
+};
+hipError_t iock_iso_correct_count(hipStream_t st, const IocIsoCorrectDev& v, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
+                                  int64_t* out_off);
+hipError_t iock_iso_correct_emit(hipStream_t st, const IocIsoCorrectDev& v, int32_t min_depth, int32_t min_alt, int32_t min_pct, int32_t max_run,
+                                 const int64_t* out_off, uint8_t* out_seq, uint8_t* out_qual, uint64_t out_bytes);
+
 // ioc_read_blocks.hip: the exon blocks of many segments and every read's isoform (ioc_host_planes_blocks per segment).  Everything
 // is a device pointer.  Pair i belongs to segment seg_of_pair[i], has its rows from byte plane[i] on of the base planes and its
 // words — ceil((rlen + 1) / 64) of each bit plane (cov, del, gap: n_pair_words words each) — from word pair_word[i] on.  Segment g:

@@ -144,3 +144,63 @@ IOC_PILE_HD ReadRowOut read_correct_row(const ioc_pileup_col& col, const ioc_pil
     if (ch != uint32_t(PILE_DEL)) out.put(read_letter(ch), pile_qual(read_count(col, ch), depth));
     return out;
 }
+
+#if defined(__HIPCC__)
+// Device code only from here on: a lane fetches its row and decides it.  What a wave of k_read_correct, and of the kernels of
+// ioc_iso_correct.hip, reads of its pair: the tables, the frames and the planes with their sizes, and where the pair's rows lie in
+// them.
+struct ReadPairView {
+    const ioc_pileup_col* __restrict__ cols;
+    const ioc_pileup_ins* __restrict__ ins;
+    uint64_t n_rows;
+    const uint8_t* __restrict__ frames;
+    uint64_t frame_bytes;
+    const uint8_t* __restrict__ base_planes;
+    const uint8_t* __restrict__ slot_planes;
+    uint64_t plane_bytes;
+    IocPileSeg s;
+    uint64_t po;  // the pair's first byte in every plane
+
+    // row p <= rlen lies inside everything that was passed
+    __device__ __forceinline__ bool inside(uint32_t p) const
+    {
+        const uint32_t rlen = uint32_t(s.rlen);
+        if (uint64_t(s.row0) + p >= n_rows || po + p >= plane_bytes) return false;
+        return p >= rlen || uint64_t(s.f_off) + (s.rc ? rlen - 1u - p : p) < frame_bytes;
+    }
+    // the decision of the base of row p (READ_NONE for row rlen and for a row outside)
+    __device__ __forceinline__ uint32_t decide(uint32_t p, const ReadRule& k) const
+    {
+        const uint32_t rlen = uint32_t(s.rlen);
+        if (p >= rlen || !inside(p)) return READ_NONE;
+        const uint64_t at = uint64_t(s.f_off) + (s.rc ? rlen - 1u - p : p);
+        const uint8_t fb = s.rc ? comp_base(frames[at]) : frames[at];
+        return read_base_decide(cols[uint64_t(s.row0) + p], base_planes[po + p], fb, k);
+    }
+    // Row p <= rlen fetched and formed: form(r, at, D, spans, own, slots) takes the row of the tables, the row's byte in every plane
+    // and what read_correct_row takes of the planes; a row outside, of which nothing is read, yields form's result as it is made.
+    template <class Form>
+    __device__ __forceinline__ auto row_as(uint32_t p, Form form) const -> decltype(form(uint64_t(0), uint64_t(0), 0ull, false, uint8_t(0), 0ull))
+    {
+        const uint32_t rlen = uint32_t(s.rlen);
+        if (p > rlen || !inside(p)) return decltype(form(uint64_t(0), uint64_t(0), 0ull, false, uint8_t(0), 0ull)){};
+        const uint64_t r = uint64_t(s.row0) + p, at = po + p;
+        const bool has_base = p < rlen;
+        // (row rlen: the depth and the span of row rlen - 1, which lies inside where row rlen does)
+        const unsigned long long D = has_base ? pile_depth(cols[r]) : rlen > 0u ? pile_depth(cols[r - 1u]) : 0ull;
+        const uint8_t own = base_planes[at];
+        const uint8_t span = has_base ? own : rlen > 0u ? base_planes[at - 1u] : uint8_t(IOC_ALLELE_NONE);
+        unsigned long long slots = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < uint32_t(IOC_PILE_INS_SLOTS); ++j) slots |= (unsigned long long)slot_planes[uint64_t(j) * plane_bytes + at] << (8u * j);
+        return form(r, at, D, read_covers(span), own, slots);
+    }
+    // what row p emits, its decision and the guard's verdict known
+    __device__ __forceinline__ ReadRowOut row(uint32_t p, uint32_t decision, bool guarded, const ReadRule& k) const
+    {
+        return row_as(p, [&](uint64_t r, uint64_t, unsigned long long D, bool spans, uint8_t own, unsigned long long slots) {
+            return read_correct_row(cols[r], ins[r], D, spans, own, slots, decision, guarded, k);
+        });
+    }
+};
+#endif

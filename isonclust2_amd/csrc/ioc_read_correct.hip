@@ -27,54 +27,6 @@
 namespace {
 
 constexpr uint32_t WAVES = IOC_READ_CORRECT_WAVES;
-constexpr uint32_t SLOTS = IOC_PILE_INS_SLOTS;
-
-// what a wave reads of its pair: the tables, the frames and the planes with their sizes, and where the pair's rows lie in them
-struct PairView {
-    const ioc_pileup_col* __restrict__ cols;
-    const ioc_pileup_ins* __restrict__ ins;
-    uint64_t n_rows;
-    const uint8_t* __restrict__ frames;
-    uint64_t frame_bytes;
-    const uint8_t* __restrict__ base_planes;
-    const uint8_t* __restrict__ slot_planes;
-    uint64_t plane_bytes;
-    IocPileSeg s;
-    uint64_t po;  // the pair's first byte in every plane
-
-    // row p <= rlen lies inside everything that was passed
-    __device__ __forceinline__ bool inside(uint32_t p) const
-    {
-        const uint32_t rlen = uint32_t(s.rlen);
-        if (uint64_t(s.row0) + p >= n_rows || po + p >= plane_bytes) return false;
-        return p >= rlen || uint64_t(s.f_off) + (s.rc ? rlen - 1u - p : p) < frame_bytes;
-    }
-    // the decision of the base of row p (READ_NONE for row rlen and for a row outside)
-    __device__ __forceinline__ uint32_t decide(uint32_t p, const ReadRule& k) const
-    {
-        const uint32_t rlen = uint32_t(s.rlen);
-        if (p >= rlen || !inside(p)) return READ_NONE;
-        const uint64_t at = uint64_t(s.f_off) + (s.rc ? rlen - 1u - p : p);
-        const uint8_t fb = s.rc ? comp_base(frames[at]) : frames[at];
-        return read_base_decide(cols[uint64_t(s.row0) + p], base_planes[po + p], fb, k);
-    }
-    // what row p emits, its decision and the guard's verdict known
-    __device__ __forceinline__ ReadRowOut row(uint32_t p, uint32_t decision, bool guarded, const ReadRule& k) const
-    {
-        const uint32_t rlen = uint32_t(s.rlen);
-        if (p > rlen || !inside(p)) return ReadRowOut{};
-        const uint64_t r = uint64_t(s.row0) + p, at = po + p;
-        const bool has_base = p < rlen;
-        // (row rlen: the depth and the span of row rlen - 1, which lies inside where row rlen does)
-        const unsigned long long D = has_base ? pile_depth(cols[r]) : rlen > 0u ? pile_depth(cols[r - 1u]) : 0ull;
-        const uint8_t own = base_planes[at];
-        const uint8_t span = has_base ? own : rlen > 0u ? base_planes[at - 1u] : uint8_t(IOC_ALLELE_NONE);
-        unsigned long long slots = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < SLOTS; ++j) slots |= (unsigned long long)slot_planes[uint64_t(j) * plane_bytes + at] << (8u * j);
-        return read_correct_row(cols[r], ins[r], D, read_covers(span), own, slots, decision, guarded, k);
-    }
-};
 
 template <bool EMIT>
 __global__ void __launch_bounds__(64 * WAVES)
@@ -93,7 +45,7 @@ k_read_correct(const IocPileSeg* __restrict__ segs, uint32_t n_segs, const int32
         if (!EMIT && lane == 0) pair_len[i] = 0, stats[i] = ioc_correct_stats{};
         return;
     }
-    const PairView v{cols, ins, n_rows, frames, frame_bytes, base_planes, slot_planes, plane_bytes, segs[g], plane[i]};
+    const ReadPairView v{cols, ins, n_rows, frames, frame_bytes, base_planes, slot_planes, plane_bytes, segs[g], plane[i]};
     const uint32_t rows = uint32_t(v.s.rlen) + 1u, nchunks = (rows + 63u) / 64u;
 
     uint32_t n = 0, k_sub = 0, k_fill = 0, k_rem = 0, k_add = 0, k_drop = 0, k_low = 0, k_guard = 0;

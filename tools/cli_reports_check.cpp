@@ -126,6 +126,10 @@ int main()
     // min(max_iso, reads) = 2, 2, 1, 1 isoforms at 16 and 1 each at 1; times the bounds above
     EXPECT(iso_polish_capacity(g, 16).isoforms == 6 && iso_polish_capacity(g, 16).bytes == 2 * 48 + 2 * 41 + 34 + 55);
     EXPECT(iso_polish_capacity(g, 1).isoforms == 4 && iso_polish_capacity(g, 1).bytes == 178);
+    // the correction by isoform: every pair's segment's bound and its own read beside it
+    int64_t reads_bytes = 0;
+    for (const ioc_aln_pair& pr : g.pairs) reads_bytes += g.offs[size_t(pr.query) + 1] - g.offs[size_t(pr.query)];
+    EXPECT(reads_bytes > 0 && iso_correct_capacity(g) == correct_capacity(g) + reads_bytes);
     // without a per-group file nothing but the pool, the pairs and their maps is kept
     {
         ReportOpts stats_only;
@@ -186,6 +190,24 @@ int main()
     a.lead_i = 2, a.trail_i = 3, a.longest_ins = IOC_PILE_INS_SLOTS + 1;
     EXPECT(corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, k, "ACGTTT", "IIIII!", 6) ==
            "@r1 cluster=4 subs=0 fills=0 removes=0 ins_add=0 ins_drop=0 low=0 guarded=0 uncorrected=long_insertion\nggCCCCCttt\n+\n0123456789\n");
+
+    // the record of the correction by isoform: corrected_record's layout with four more fields; a long insertion is no reason to
+    // leave the read as it is, an unresolved pair is (the library hands back counters of 0 for it)
+    ioc_iso_correct_stats zc{6, 1, 2, 3, 4, 5, 6, 7, 3, 1, 40, 0};
+    const char* const ihead = "@r1 cluster=4 subs=1 fills=2 removes=3 ins_add=4 ins_drop=5 low=6 guarded=7 isoform=1 table=isoform long_runs=1 long_bases=40\n";
+    EXPECT(iso_corrected_record("r1 x", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, zc, 1, "ACGTTT", "IIIII!", 6) == string(ihead) + "ggACGTTTttt\n+\n01IIIII!789\n");
+    EXPECT(iso_corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123", 4, a, zc, 1, "ACGTTT", "IIIII!", 6) == string(ihead) + "ggACGTTTttt\n+\n01IIIII!!!!\n");
+    zc.table = -1 - 2;
+    EXPECT(iso_corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, zc, -1, "ACGTTT", "IIIII!", 6).find(" isoform=- table=cluster long_runs=1 ") != string::npos);
+    a.lead_i = 8, a.trail_i = 5;  // (clips that do not fit the read: the trailing one gives way)
+    const string clipped = iso_corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123456789", 10, a, zc, -1, "", "", 0), whole = "\nggCCCCCttt\n+\n0123456789\n";
+    EXPECT(clipped.size() > whole.size() && clipped.substr(clipped.size() - whole.size()) == whole);
+    a.lead_i = 2, a.trail_i = 3;
+    ioc_iso_correct_stats zu{};
+    zu.table = 0, zu.flags = IOC_ISOC_UNRESOLVED;
+    EXPECT(iso_corrected_record("r1", 2, 4, "ggCCCCCttt", 10, "0123", 4, a, zu, 0, "", "", 0) ==
+           "@r1 cluster=4 subs=0 fills=0 removes=0 ins_add=0 ins_drop=0 low=0 guarded=0 isoform=0 table=isoform long_runs=0 long_bases=0 uncorrected=unresolved_insertion\n"
+           "ggCCCCCttt\n+\n0123!!!!!!\n");
 
     // three kept blocks of four found; the states keep, skip, part at blocks 0 .. 2 make the key 0 + (1 << 2) + (2 << 4)
     EXPECT(blocks_signature(0x24, 3) == "=-~" && blocks_signature(0x3, 1) == "." && blocks_signature(7, 0) == "*" && blocks_signature(~0ull, 32) == string(32, '.'));

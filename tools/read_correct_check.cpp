@@ -48,7 +48,7 @@ struct Call {  // what the kernel is launched over, every block exactly as large
     uint64_t plane_bytes = 0;
 };
 
-// PairView of the kernel
+// ReadPairView of the kernel (ioc_read_correct.h)
 struct View {
     const Call& k;
     IocPileSeg s;
